@@ -2,6 +2,7 @@
 """bench.py — detector FPS @1080p, 8 scales/octave, FACE80 model on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--contexts C] [--config {2,4,5}] [--frames-total T]
+                    [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (acf_hip_run: chnsPyramid + acfDetect, then the device-side export of the
 detection records) over batches of synthetic frames that are already resident in HBM.  With N > 1 (launched by
@@ -240,6 +241,30 @@ def cpu_baseline(model, frames_np, H, W, budget_s=12.0):
     return out
 
 
+DUMP_LIMIT = 64 << 20  # bytes of .npy payload --dump-outputs may write
+
+
+def dump_outputs(path, recs, cap):
+    """--dump-outputs: the export records of the last timed step ([frames, 1 + 6 * cap] int32, acf_hip_export_detections) decoded into
+    counts.npy (detections per frame), boxes.npy (x, y, w, h), scores.npy, levels.npy ([frames, cap, ...], zero past a frame's count)
+    and frames.npy (the frame of each row).  Beyond DUMP_LIMIT bytes a fixed, seeded sample of the frames is written, in frame order."""
+    n = recs.shape[0]
+    per_frame = 8 + cap * (4 * 8 + 4 + 8) + 8
+    keep = np.arange(n)
+    if n * per_frame > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT // per_frame, replace=False))
+    recs = recs[keep]
+    counts = np.minimum(recs[:, 0], cap)
+    body = recs[:, 1:1 + 6 * cap].reshape(len(keep), cap, 6).copy()
+    body[np.arange(cap)[None, :] >= counts[:, None]] = 0
+    os.makedirs(path, exist_ok=True)
+    out = {"counts": recs[:, 0].astype(np.float64), "boxes": body[:, :, :4].astype(np.float64),
+           "scores": body[:, :, 4].copy().view(np.float32), "levels": body[:, :, 5].astype(np.float64), "frames": keep.astype(np.float64)}
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return {"dir": path, "frames": int(len(keep)), "frames_total": int(n), "bytes": int(sum(v.nbytes for v in out.values()))}
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: re-run this command line as N ranks under torch.distributed.run
     (one process per GPU, LOCAL_RANK -> device, rendezvous on 127.0.0.1 at a free port).  Rank 0's JSON line is this
@@ -313,6 +338,8 @@ def main():
                     "call is detection only — Detector::operator()(image) — and the levels leave the level kernel as 16-bit threshold-rank cells")
     ap.add_argument("--no-repeats", action="store_true", help="skip the two extra timed regions behind `value_repeats` (profiling passes)")
     ap.add_argument("--no-verify", action="store_true", help="skip the post-run check of three timed frames against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last timed step exported "
+                    "(every frame's detections: counts, boxes, scores, levels) as DIR/<name>.npy, float32 / float64, at most %d MB in all" % (DUMP_LIMIT >> 20))
     ap.add_argument("--dry-launch", action="store_true", help="launch plumbing only (spawn, rendezvous, max-over-ranks clock, per-rank gather) "
                     "with no detector work: runs without a GPU over gloo (tests/test_bench_launch.py); never a measurement")
     args = ap.parse_args()
@@ -320,6 +347,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "0"))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if world == 0 and args.gpus > 1:
         # plain `python bench.py --gpus N`: become N ranks (one per GPU) under torch.distributed.run, rendezvous on 127.0.0.1
         sys.exit(spawn_ranks(args.gpus))
@@ -442,6 +471,11 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # what the last timed step handed its caller, read before anything else runs on the contexts: every context's records (on rank 0,
+    # every rank's, gathered inside the step), frames in (rank, context, frame) order
+    last_recs = [p_.finish() for p_ in pipes] if args.dump_outputs else None
+    if last_recs is not None and rank == 0:
+        last_recs = torch.cat([r_.view(world, B, -1) for r_ in last_recs], dim=1).reshape(world * C * B, -1).cpu().numpy()
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -799,6 +833,8 @@ def main():
             out["cpu_baseline"] = None
         if gathered is not None and world > 1:
             out["config"]["gathered_records"] = int(gathered.shape[0])
+        if args.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(args.dump_outputs, last_recs, args.cap)
         print(json.dumps(out))
     pool.close()
     if world > 1:

@@ -68,3 +68,41 @@ def test_two_ranks_on_a_one_gpu_box_fail_with_the_missing_device():
     assert r.returncode != 0
     assert "rank 1 needs GPU 1 but 1 device(s) are visible" in out, out[-3000:]
     assert not [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]  # no bench line from a broken launch
+
+
+def test_dump_outputs_decodes_the_export_records(tmp_path, monkeypatch):
+    """--dump-outputs: each frame's export record (acf_amd.dist record layout) comes back as counts / boxes / scores / levels, exact,
+    zero past the frame's count (stale record slots never leak into a dump); past the size limit a seeded sample of the frames."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from acf_amd import capi
+    from acf_amd.dist import detections_to_record
+    rng = np.random.default_rng(5)
+    cap, recs, want = 8, [], []
+    for n in (0, 3, 8, 12, 1):
+        d = np.zeros(n, dtype=capi.DET_DTYPE)
+        for k in ("x", "y", "w", "h", "scale"):
+            d[k] = rng.integers(0, 500, n)
+        d["score"] = rng.standard_normal(n).astype(np.float32)
+        r = detections_to_record(d, cap)
+        r[1 + 6 * min(n, cap):] = 12345  # stale slots
+        recs.append(r)
+        want.append(d[:cap])
+    recs = np.stack(recs)
+    info = bench.dump_outputs(str(tmp_path / "a"), recs, cap)
+    z = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("counts", "boxes", "scores", "levels", "frames")}
+    assert info["frames"] == info["frames_total"] == 5 and info["bytes"] <= bench.DUMP_LIMIT
+    assert all(v.dtype in (np.float32, np.float64) for v in z.values())
+    assert z["counts"].tolist() == [0, 3, 8, 12, 1] and z["frames"].tolist() == [0, 1, 2, 3, 4]
+    for i, d in enumerate(want):
+        n = len(d)
+        assert np.array_equal(z["boxes"][i, :n], np.stack([d[k] for k in ("x", "y", "w", "h")], axis=1))
+        assert np.array_equal(z["scores"][i, :n].view(np.uint32), d["score"].view(np.uint32))
+        assert np.array_equal(z["levels"][i, :n], d["scale"])
+        assert not z["boxes"][i, n:].any() and not z["scores"][i, n:].any() and not z["levels"][i, n:].any()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 2 * (16 + cap * 44))
+    info = bench.dump_outputs(str(tmp_path / "b"), recs, cap)
+    f = np.load(str(tmp_path / "b" / "frames.npy"))
+    assert info["frames"] == 2 and len(f) == 2 and np.all(np.diff(f) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "boxes.npy")), z["boxes"][f.astype(int)])
