@@ -120,6 +120,67 @@ struct CascState
     int rankMaxWP = 0;
 };
 
+// acf_hip_set_option's keys, one field each (OPTION_KEYS), except "graph" and "streams": those stay the parent's, and
+// sub-batch children hold a copy of everything here.  Every field is an int so that the key table can point at it.
+struct Options
+{
+    int taps = 0;
+    int arith = 0;   // 1 = the reference's rcpps / rsqrtps bits from d_x86 (acf_hip_set_x86_tables)
+    int profile = 0;
+    int fusedSmooth = 1; // 0: separate smoothing / half resample / colour-channel kernels
+    // 0 = gradMag as its own kernel (k_grad_mag_vec), 1 = inside the gradient plane's smoothing chain (k_smooth_grad) where that
+    // pays (big planes, many frames), 2 = wherever k_smooth_grad applies
+    int fusedGrad = 1;
+    // convTri's x pass over M inside that chain as well (k_smooth_grad_tri; the gradient plane is then ONE segment): 0 = never
+    // (k_tri_x5v), 1 = where k_smooth_grad runs in batches of >= 64 frames of a context that shares its device, 2 = wherever
+    // k_smooth_grad runs
+    int fusedTri = 1;
+    // this context runs beside other contexts on the same device (the pools set it).  Kernel forms are then chosen for the least
+    // WORK instead of the shortest time alone: a lone context cuts the smoothing chains into segments to fill the machine (20 % more
+    // columns, a verify and a repair launch per scale) and keeps the x pass a kernel of its own; beside other contexts a thin
+    // chain's latency is covered by their kernels and only its work counts (3 x 96 frames at 1080p: +4.3 % frames/s; alone, 96
+    // frames: -7 %)
+    int sharedDevice = 0;
+    // the pooled tile kernel runs as persistent workgroups that draw tiles from a counter (best alone on the device: -8 % on that
+    // kernel) or one short-lived workgroup per tile (best beside other contexts' kernels, which then find free LDS)
+    int tilePersist = 1;
+    int cascadeTiles = 1; // 0: force the global-memory staged cascade (A/B and parity of both paths)
+    // 1: the tile kernel of depth-2 models reads 16-bit threshold-rank cells (host_plan.h) — identical decisions, half the tile;
+    // 0: it reads the float pyramid (A/B and parity of both forms)
+    int rankCells = 1;
+    // 1: the real scales of a batch run on their own streams (best for ONE context: +8 % frames/s, batch-1 latency 2.1 -> 1.5 ms);
+    // 0: on the context's stream in order — what an application that runs several contexts side by side wants (three contexts:
+    // 12.1k instead of 11.6k frames/s; they already fill each other's gaps, more streams only multiplex the hardware queues)
+    int scaleStreams = 1;
+    // the tile kernels of the contexts of one device take turns (each waits for the tile kernel submitted before it on that
+    // device, whichever context's): contexts that run in phase otherwise run their cascades — bound by LDS and VALU, not by
+    // memory — beside each other instead of beside the other contexts' memory-bound pyramid kernels
+    int cascadeTurns = 0;
+    int fusedLevels = 1; // 1 fused resample+smooth, 2 separate resample + wave-per-plane smooth, 0 separate launches
+    // k_smooth_vec's speculative column segments (kernels.hip.h): the image smoothing's recursion along image-x cut into column
+    // segments that start smoothWarm columns early and are checked against each other: 0 = as many as fill the GPU for the batch,
+    // 1 = one chain per plane, n = n segments; smoothForceRedo = 1 marks every plane for the repair launch (tests)
+    int smoothSegments = 0;
+    // 96 warm-up columns: a value decays fourfold per column, so 12-25 columns settle the last bit of ordinary values — but where
+    // the image turns exactly 0 (a black bar) the true chain carries a tail that only reaches 0 by underflow, after ~75 columns,
+    // while a warm-up started inside the bar is 0 at once (profiles/r03_repair_rates.json: 3 % of planes repaired at 48, none
+    // at 64+ on frames with black and flat bands); at 96 frames per launch 48 / 64 / 96 columns cost the same (0.36-0.38 ms)
+    int smoothWarm = 64, smoothForceRedo = 0; // (profiles/r03_repair_rates.json: no repair from 64 columns on)
+    // The level chains' segments: 0 (default) = AUTO — batches of at most levelSegFrames (8) frames run the speculative segmented
+    // k_level_all + k_level_verify + the repair launch, bigger batches one chain per plane; 1 = off; n > 1 = n segments whatever
+    // the batch.  A level is at most 480 columns, so segments only pay with warm-ups of ~32 columns (levelWarm; one frame:
+    // 372 -> 124 us), and channel planes have exactly-zero regions wherever the image is flat (no gradient): a plane whose
+    // hand-over differs costs its whole chain again in the repair launch (tests/test_gpu_segments.py counts the repairs of a
+    // frame with flat bands so that this cost stays visible).
+    int levelSegments = 0;
+    int levelWarm = 32;
+    // planes the repair launches had to recompute (synchronises after every verify: measurements only)
+    int countRepairs = 0;
+    // 0: the caller only wants detections (acf_hip_run / acf_hip_detect): when the levels leave as rank cells the float pyramid is
+    // not written at all (acf_hip_read_level and the Pyramid-returning entries then fail with ACF_HIP_E_INVALID); 1 (default): both
+    int keepPyramid = 1;
+};
+
 struct acf_hip_ctx
 {
     int device = 0;
@@ -138,36 +199,15 @@ struct acf_hip_ctx
     std::vector<hipEvent_t> evJoin;
     mutable std::string err;
     bool hasModel = false, hasPlan = false;
-    int taps = 0;
-    int arith = 0;            // option "arith": 1 = the reference's rcpps / rsqrtps bits from d_x86 (acf_hip_set_x86_tables)
+    Options opt; // acf_hip_set_option's settings (sub-batch children hold the parent's)
     bool x86Owned = false;
     uint32_t* d_x86 = nullptr; // [X86_BUF_N]: rcp over [1, 2) by m >> 11 (4096), rsqrt over [1, 4) by parity and m >> 11 (2 x 4096), then gradMag's composed pairs
-    int profile = 0;
-    int noFusedSmooth = 0; // option "fused_smooth" = 0: separate smoothing / half resample / colour-channel kernels
-    // option "fused_grad": 0 = gradMag as its own kernel (k_grad_mag_vec), 1 = inside the gradient plane's smoothing chain
-    // (k_smooth_grad) where that pays (big planes, many frames), 2 = wherever k_smooth_grad applies
-    int fusedGrad = 1;
-    // option "fused_tri": convTri's x pass over M inside that chain as well (k_smooth_grad_tri; the gradient plane is then ONE segment):
-    // 0 = never (k_tri_x5v), 1 = where k_smooth_grad runs in batches of >= 64 frames of a context that shares its device, 2 = wherever
-    // k_smooth_grad runs
-    int fusedTri = 1;
-    // option "shared_device": this context runs beside other contexts on the same device (the pools set it).  Kernel forms are then
-    // chosen for the least WORK instead of the shortest time alone: a lone context cuts the smoothing chains into segments to fill the
-    // machine (20 % more columns, a verify and a repair launch per scale) and keeps the x pass a kernel of its own; beside other
-    // contexts a thin chain's latency is covered by their kernels and only its work counts (3 x 96 frames at 1080p: +4.3 % frames/s;
-    // alone, 96 frames: -7 %)
-    int sharedDevice = 0;
-    // option "tile_persist": the pooled tile kernel runs as persistent workgroups that draw tiles from a counter (best alone on the
-    // device: -8 % on that kernel) or one short-lived workgroup per tile (best beside other contexts' kernels, which then find free LDS)
-    int tilePersist = 1;
     // the device as hipGetDeviceProperties describes it (acf_hip_create): the persistent grids are sized from these.  The
     // counters the persistent workgroups draw tiles from are eight (blockIdx.x & 7: one per XCD of an MI355X, whose
     // dispatcher deals consecutive workgroups to consecutive XCDs); on a part with another XCD count the ranges still
     // cover every tile, only their locality is lost.
     int numCus = 256;
     size_t ldsPerCu = size_t(160) * 1024;
-    int noTiles = 0; // option "cascade_tiles" = 0: force the global-memory staged cascade (A/B and parity of both paths)
-    int noRank = 0;  // option "rank_cells" = 0: the tile kernel reads the float pyramid (A/B and parity of both forms)
     bool ranksValid = false; // the rank pyramid of the last batch has been written (by the level kernels or by k_rank)
     bool floatPyramid = true; // the float pyramid of the last batch exists (option keep_pyramid = 0: it may not)
     std::vector<hipEvent_t> evPool;
@@ -175,11 +215,6 @@ struct acf_hip_ctx
     size_t evUsed = 0;
     std::vector<hipStream_t> evStream; // the stream each profile event was recorded on (a kernel ends at the next event of ITS stream)
     std::vector<hipEvent_t> evScale;   // pyramid: "real scale k has been smoothed" (the next real scale starts from it on its own stream)
-    bool scaleStreams = true;          // option scale_streams
-    // option cascade_turns: the tile kernels of the contexts of one device take turns (each waits for the tile kernel submitted
-    // before it on that device, whichever context's): contexts that run in phase otherwise run their cascades — bound by
-    // LDS and VALU, not by memory — beside each other instead of beside the other contexts' memory-bound pyramid kernels
-    int cascTurns = 0;
     hipEvent_t evTurn[2] = { nullptr, nullptr }; // [0] tile kernel, [1] level kernel (bit 1 of the option: own turns; bit 2: the tile kernels' turns)
 
     acf_hip_params p{};
@@ -232,19 +267,11 @@ struct acf_hip_ctx
     };
     std::vector<LevelGroup> levelGroups, levelGroupsRaw; // jobs sorted into runs of equal (R, mode)
     int nAllJobs = 0, nAllJobsRaw = 0; // leading jobs of d_levelJobs(/Raw) that go to the single k_level_all launch
-    int levelMode = 1;                  // option "fused_levels": 1 fused resample+smooth, 2 separate resample + wave-per-plane smooth, 0 separate launches
     bool fusedOk = false;      // the fused resample+smooth level kernel covers this plan
-    int noFused = 0;           // option "fused_levels" = 0: separate resample and smoothing launches
     PadJob* d_padJobs = nullptr;
     PadJob* d_padJobsR = nullptr; // the same borders in the rank pyramid's layout
     bool levelsEmitRank = false;  // every level goes through k_level_all: the level kernels can write the rank cells themselves
-    // k_smooth_vec's speculative column segments (kernels.hip.h): options smooth_segments (0 auto, 1 off, n), smooth_warm, smooth_force_redo
-    int smoothSegments = 0;
-    // 96 warm-up columns: a value decays fourfold per column, so 12-25 columns settle the last bit of ordinary values — but where
-    // the image turns exactly 0 (a black bar) the true chain carries a tail that only reaches 0 by underflow, after ~75 columns,
-    // while a warm-up started inside the bar is 0 at once (profiles/r03_repair_rates.json: 3 % of planes repaired at 48, none
-    // at 64+ on frames with black and flat bands); at 96 frames per launch 48 / 64 / 96 columns cost the same (0.36-0.38 ms)
-    int smoothWarm = 64, smoothForceRedo = 0; // (profiles/r03_repair_rates.json: no repair from 64 columns on)
+    // k_smooth_vec's speculative column segments (kernels.hip.h): state of the segments' hand-overs, planes to repair
     float *d_specState = nullptr, *d_trueState = nullptr;
     bool countersZeroed = false; // acf_hip_run has cleared the tiled cascade's counters in front of the pyramid's launches
     int32_t* d_redo = nullptr;
@@ -253,16 +280,6 @@ struct acf_hip_ctx
     float *d_lvSpec = nullptr, *d_lvTrue = nullptr;
     int32_t* d_lvRedo = nullptr;
     int levelSegFrames = 0, levelSegCap = 0, levelHMax = 0;
-    // The level chains' segments: option level_segments 0 (default) = AUTO — batches of at most levelSegFrames (8) frames run the
-    // speculative segmented k_level_all + k_level_verify + the repair launch, bigger batches one chain per plane; 1 = off; n > 1 =
-    // n segments whatever the batch.  A level is at most 480 columns, so segments only pay with warm-ups of ~32 columns (option
-    // level_warm; one frame: 372 -> 124 us), and channel planes have exactly-zero regions wherever the image is flat (no
-    // gradient): a plane whose hand-over differs costs its whole chain again in the repair launch (tests/test_gpu_segments.py
-    // counts the repairs of a frame with flat bands so that this cost stays visible).
-    int levelSegments = 0; // option level_segments: 0 = auto (small batches only), 1 = off
-    int levelWarm = 32; // option level_warm
-    // option count_repairs: planes the repair launches had to recompute (synchronises after every verify: measurements only)
-    int countRepairs = 0;
     // option "graph": acf_hip_run replays a HIP graph captured from its own launches (same frames pointer, same batch size):
     // one host call instead of ~45 launches per frame — what a single frame's latency is made of when the kernels take 20 us
     int useGraph = 0;
@@ -281,7 +298,6 @@ struct acf_hip_ctx
     int plainRuns = 0, graphBroken = 0;
     int64_t repairs[4] = { 0, 0, 0, 0 }; // {smoothing planes checked, redone, level planes checked, redone}
     int segCap = 0;               // segments the state buffers hold per plane
-    int keepPyramid = 1;          // option "keep_pyramid": 0 = a run()/detect-only caller does not need the float pyramid (levels leave as rank cells only)
     int finalMaxH = 0;
     int approxMaxBlocks = 0;
     int64_t padMaxElems = 0;
@@ -425,12 +441,12 @@ int fail(const acf_hip_ctx* c, int code, const std::string& msg)
 // the CPU tables the three approximate sites evaluate (option "arith" = 1), or null: exact arithmetic
 inline const uint32_t* x86T(const acf_hip_ctx* c)
 {
-    return c->arith ? c->d_x86 : nullptr;
+    return c->opt.arith ? c->d_x86 : nullptr;
 }
 
 void prof(acf_hip_ctx* c, const char* name)
 {
-    if (!c->profile)
+    if (!c->opt.profile)
     {
         return;
     }
@@ -1212,6 +1228,54 @@ const char* acf_hip_last_error(const acf_hip_ctx* c)
     return c ? c->err.c_str() : "null context";
 }
 
+// acf_hip_set_option's keys (each described in include/acf_hip.h).  `field` is the Options member the value goes to, in the
+// context and in each of its sub-batch children; "graph" and "streams" have none: `after` sets them on the parent alone
+// (children never capture graphs; "streams" takes effect at the next acf_hip_plan).
+struct OptionKey
+{
+    const char* key;
+    int Options::*field;
+    bool nonzero;                               // stores value != 0 (else the value as given)
+    bool (*refuse)(const acf_hip_ctx*, int);    // null: any value
+    const char* why;                            // acf_hip_last_error of a refused value
+    void (*after)(acf_hip_ctx*, int);           // side effect, on every context the value is set on
+};
+
+static bool negative(const acf_hip_ctx*, int v)
+{
+    return v < 0;
+}
+
+static const char* const LEVEL_RANGE = "option: level_warm a positive multiple of 4, level_segments >= 0";
+static const char* const SMOOTH_RANGE = "option: smooth_segments >= 0, smooth_warm a multiple of 16";
+
+static const OptionKey OPTION_KEYS[] = {
+    { "graph", nullptr, false, nullptr, nullptr, [](acf_hip_ctx* c, int v) { c->useGraph = v; c->graphBroken = 0; } },
+    { "streams", nullptr, false, [](const acf_hip_ctx*, int v) { return v < 1 || v > 6; }, "streams: 1..6",
+        [](acf_hip_ctx* c, int v) { c->nStreams = v; } },
+    { "taps", &Options::taps, true },
+    { "arith", &Options::arith, true, [](const acf_hip_ctx* c, int v) { return v != 0 && !c->d_x86; },
+        "arith: install a CPU's tables first (acf_hip_set_x86_tables)" },
+    { "profile", &Options::profile, true, nullptr, nullptr, [](acf_hip_ctx* c, int) { c->evUsed = 0; } },
+    { "fused_levels", &Options::fusedLevels, false },
+    { "fused_smooth", &Options::fusedSmooth, true },
+    { "fused_grad", &Options::fusedGrad, false },
+    { "fused_tri", &Options::fusedTri, false },
+    { "shared_device", &Options::sharedDevice, true },
+    { "cascade_tiles", &Options::cascadeTiles, true },
+    { "rank_cells", &Options::rankCells, true, nullptr, nullptr, [](acf_hip_ctx* c, int) { c->detectValid = false; } },
+    { "tile_persist", &Options::tilePersist, false },
+    { "cascade_turns", &Options::cascadeTurns, false },
+    { "scale_streams", &Options::scaleStreams, true },
+    { "keep_pyramid", &Options::keepPyramid, true },
+    { "count_repairs", &Options::countRepairs, false, negative, LEVEL_RANGE },
+    { "level_segments", &Options::levelSegments, false, negative, LEVEL_RANGE },
+    { "level_warm", &Options::levelWarm, false, [](const acf_hip_ctx*, int v) { return v < 4 || v % 4 != 0; }, LEVEL_RANGE },
+    { "smooth_segments", &Options::smoothSegments, false, negative, SMOOTH_RANGE },
+    { "smooth_force_redo", &Options::smoothForceRedo, false, negative, SMOOTH_RANGE },
+    { "smooth_warm", &Options::smoothWarm, false, [](const acf_hip_ctx*, int v) { return v < 0 || v % 16 != 0; }, SMOOTH_RANGE },
+};
+
 int acf_hip_set_option(acf_hip_ctx* c, const char* key, int value)
 {
     if (!c || !key)
@@ -1219,159 +1283,34 @@ int acf_hip_set_option(acf_hip_ctx* c, const char* key, int value)
         return ACF_HIP_E_INVALID;
     }
     dropGraph(c); // (whatever changes, a captured graph no longer describes the next run)
-    if (!strcmp(key, "graph"))
+    const OptionKey* o =
+        std::find_if(std::begin(OPTION_KEYS), std::end(OPTION_KEYS), [&](const OptionKey& r) { return !strcmp(key, r.key); });
+    if (o == std::end(OPTION_KEYS))
     {
-        c->useGraph = value;
-        c->graphBroken = 0;
+        return fail(c, ACF_HIP_E_INVALID, std::string("unknown option ") + key);
+    }
+    if (o->refuse && o->refuse(c, value))
+    {
+        return fail(c, ACF_HIP_E_INVALID, o->why); // (a child holds the parent's d_x86: it would refuse the same values)
+    }
+    if (!o->field)
+    {
+        o->after(c, value);
         return ACF_HIP_OK;
     }
-    if (!strcmp(key, "streams"))
-    {
-        if (value < 1 || value > 6)
+    auto set = [&](acf_hip_ctx* t) {
+        t->opt.*o->field = o->nonzero ? value != 0 : value;
+        if (o->after)
         {
-            return fail(c, ACF_HIP_E_INVALID, "streams: 1..6");
+            o->after(t, value);
         }
-        c->nStreams = value; // takes effect at the next acf_hip_plan
-        return ACF_HIP_OK;
-    }
+    };
+    set(c);
     for (acf_hip_ctx* k : c->kids)
     {
-        (void)acf_hip_set_option(k, key, value);
+        set(k);
     }
-    if (!strcmp(key, "taps"))
-    {
-        c->taps = value != 0;
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "arith"))
-    {
-        if (value != 0 && !c->d_x86)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "arith: install a CPU's tables first (acf_hip_set_x86_tables)");
-        }
-        c->arith = value != 0;
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "profile"))
-    {
-        c->profile = value != 0;
-        c->evUsed = 0;
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "fused_levels"))
-    {
-        c->noFused = value == 0;
-        c->levelMode = value;
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "fused_smooth"))
-    {
-        c->noFusedSmooth = value == 0;
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "fused_grad"))
-    {
-        c->fusedGrad = value;
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "fused_tri"))
-    {
-        c->fusedTri = value;
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "shared_device"))
-    {
-        c->sharedDevice = value != 0;
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "cascade_tiles"))
-    {
-        c->noTiles = value == 0;
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "count_repairs") || !strcmp(key, "level_warm") || !strcmp(key, "level_segments"))
-    {
-        if ((!strcmp(key, "level_warm") && (value < 4 || value % 4 != 0)) || value < 0)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "option: level_warm a positive multiple of 4, level_segments >= 0");
-        }
-        (!strcmp(key, "count_repairs") ? c->countRepairs : (!strcmp(key, "level_warm") ? c->levelWarm : c->levelSegments)) = value;
-        for (acf_hip_ctx* k : c->kids)
-        {
-            (void)acf_hip_set_option(k, key, value);
-        }
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "smooth_segments") || !strcmp(key, "smooth_warm") || !strcmp(key, "smooth_force_redo"))
-    {
-        // the image smoothing's recursion along image-x cut into column segments that start `smooth_warm` columns early and are
-        // checked against each other (kernels.hip.h, "speculative segments"): 0 = as many as fill the GPU for the batch, 1 = one
-        // chain per plane, n = n segments; smooth_force_redo = 1 marks every plane for the repair launch (tests)
-        int& dst = !strcmp(key, "smooth_segments") ? c->smoothSegments : (!strcmp(key, "smooth_warm") ? c->smoothWarm : c->smoothForceRedo);
-        if (value < 0 || (!strcmp(key, "smooth_warm") && value % 16 != 0))
-        {
-            return fail(c, ACF_HIP_E_INVALID, "option: smooth_segments >= 0, smooth_warm a multiple of 16");
-        }
-        dst = value;
-        for (acf_hip_ctx* k : c->kids)
-        {
-            (void)acf_hip_set_option(k, key, value);
-        }
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "keep_pyramid"))
-    {
-        // 0: the caller only wants detections (acf_hip_run / acf_hip_detect): when the levels leave as rank cells the float
-        // pyramid is not written at all (acf_hip_read_level and the Pyramid-returning entries then fail with
-        // ACF_HIP_E_INVALID); 1 (default): both
-        c->keepPyramid = value != 0;
-        for (acf_hip_ctx* k : c->kids)
-        {
-            k->keepPyramid = c->keepPyramid;
-        }
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "rank_cells"))
-    {
-        // 1 (default): the tile kernel of depth-2 models reads 16-bit threshold-rank cells (host_plan.h) — identical decisions,
-        // half the tile; 0: it reads the float pyramid
-        c->noRank = value == 0;
-        c->detectValid = false;
-        for (acf_hip_ctx* k : c->kids)
-        {
-            k->noRank = c->noRank;
-            k->detectValid = false;
-        }
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "tile_persist"))
-    {
-        c->tilePersist = value;
-        for (acf_hip_ctx* k : c->kids)
-        {
-            k->tilePersist = value;
-        }
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "cascade_turns"))
-    {
-        c->cascTurns = value;
-        for (acf_hip_ctx* k : c->kids)
-        {
-            k->cascTurns = value;
-        }
-        return ACF_HIP_OK;
-    }
-    if (!strcmp(key, "scale_streams"))
-    {
-        // 1 (default): the real scales of a batch run on their own streams (best for ONE context: +8 % frames/s, batch-1 latency
-        // 2.1 -> 1.5 ms); 0: on the context's stream in order — what an application that runs several contexts side by side
-        // wants (three contexts: 12.1k instead of 11.6k frames/s; they already fill each other's gaps, more streams only
-        // multiplex the hardware queues)
-        c->scaleStreams = value != 0;
-        return ACF_HIP_OK;
-    }
-    return fail(c, ACF_HIP_E_INVALID, std::string("unknown option ") + key);
+    return ACF_HIP_OK;
 }
 
 int acf_hip_get_scales(int nPerOct, int nOctUp, int minDs_h, int minDs_w, int shrink, int h, int w,
@@ -1554,28 +1493,8 @@ int acf_hip_plan(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_
                 return fail(c, rc, "plan: cannot create a sub-batch context");
             }
             c->kids.push_back(k);
-            k->taps = c->taps;
+            k->opt = c->opt;
             k->d_x86 = c->d_x86; // (the parent's tables; the parent frees them)
-            k->arith = c->arith;
-            k->profile = c->profile;
-            k->noTiles = c->noTiles;
-            k->noRank = c->noRank;
-            k->keepPyramid = c->keepPyramid;
-            k->smoothSegments = c->smoothSegments;
-            k->smoothWarm = c->smoothWarm;
-            k->smoothForceRedo = c->smoothForceRedo;
-            k->levelWarm = c->levelWarm;
-            k->levelSegments = c->levelSegments;
-            k->countRepairs = c->countRepairs;
-            k->noFusedSmooth = c->noFusedSmooth;
-            k->fusedGrad = c->fusedGrad;
-            k->fusedTri = c->fusedTri;
-            k->sharedDevice = c->sharedDevice;
-            k->noFused = c->noFused;
-            k->levelMode = c->levelMode;
-            k->scaleStreams = c->scaleStreams;
-            k->cascTurns = c->cascTurns;
-            k->tilePersist = c->tilePersist;
             k->nmsOn = c->nmsOn; // (acf_hip_set_nms before the plan, or a re-plan: the new children run what the parent reports)
             k->nms = c->nms;
             if ((rc = acf_hip_set_model(k, &c->p)) || (rc = acf_hip_plan(k, H, W, d_in, c->kidChunk, max_hits)))
@@ -2184,8 +2103,8 @@ int acf_hip_run(acf_hip_ctx* c, const float* frames, int nF)
     // option "graph": the launches of this call — same frames pointer, same batch size, nothing in the path that reads back or
     // records events of its own — as one captured graph.  The first calls run plainly (they may allocate); a capture that the
     // runtime refuses switches the option off for this context and the call runs plainly.
-    const bool graphable = c && c->useGraph && !c->graphBroken && c->hasPlan && !c->profile && !c->taps && !c->countRepairs && !c->autoLambdas &&
-        c->cascTurns == 0 && frames && nF > 0 && nF <= c->maxBatch;
+    const bool graphable = c && c->useGraph && !c->graphBroken && c->hasPlan && !c->opt.profile && !c->opt.taps && !c->opt.countRepairs && !c->autoLambdas &&
+        c->opt.cascadeTurns == 0 && frames && nF > 0 && nF <= c->maxBatch;
     if (graphable)
     {
         for (auto& gs : c->graphs)
@@ -3015,7 +2934,7 @@ int acf_hip_read_rank_level(acf_hip_ctx* c, int frame, int level, uint16_t* host
     {
         return ACF_HIP_E_NOPLAN;
     }
-    if (!c->cs.useRank || c->noRank)
+    if (!c->cs.useRank || !c->opt.rankCells)
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, "read_rank_level: the plan has no rank cells (model not depth 2 / thresholds too dense / option rank_cells off / LDCF)");
     }

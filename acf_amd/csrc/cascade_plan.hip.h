@@ -542,7 +542,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             cs.d_tileOffD = tsD.d_tileOffD;
             // ---- the pooled kernel on threshold-rank cells (the rank tables do not depend on the depth): half the fill, three
             // workgroups per CU.  The float pyramid is still written for these depths (the queue's overflow path reads it).
-            if ((tsD.g.pooled || p.treeDepth == 1) && wantRank && !c->noRank && !fallbackForced(FB_TILED_STAGED))
+            if ((tsD.g.pooled || p.treeDepth == 1) && wantRank && c->opt.rankCells && !fallbackForced(FB_TILED_STAGED))
             {
                 const int mHc = p.modelDsPad_h / p.shrink, mWc = p.modelDsPad_w / p.shrink;
                 std::vector<int32_t> chnOfNode(nNodes, -1);
@@ -671,7 +671,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             }
             cs.useTiles = true;
             // ---- the same tiles over threshold-rank cells (16 bits per cell): half the fill, half the LDS
-            if (wantRank && !c->noRank)
+            if (wantRank && c->opt.rankCells)
             {
                 std::vector<int32_t> chnOfNode(nNodes, -1);
                 for (size_t q = 0; q < nNodes; q++)

@@ -17,7 +17,7 @@ static int allowLds(acf_hip_ctx* c, const void* kernel, size_t bytes)
 // the ONE statement of "the cascade runs on LDS tiles": runCascade's branch and acf_hip_run's early counter clear both ask it
 static inline bool tiledCascadeSelected(const acf_hip_ctx* c)
 {
-    return c->cs.useTiles && !c->noTiles;
+    return c->cs.useTiles && c->opt.cascadeTiles;
 }
 
 static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int nF, int nChns)
@@ -73,7 +73,7 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
         HIPCHK(c, hipMalloc(&a.stamps, size_t((total + 7) / 8 * 8) * 8 * sizeof(long long)));
         HIPCHK(c, hipMemsetAsync(a.stamps, 0, size_t((total + 7) / 8 * 8) * 8 * sizeof(long long), c->stream));
     }
-    const bool rank = cs.useRank && !c->noRank && pyr == c->d_pyr;
+    const bool rank = cs.useRank && c->opt.rankCells && pyr == c->d_pyr;
     if (rank && !c->ranksValid)
     {
         // the float pyramid -> threshold-rank cells (levels whose kernels did not emit them)
@@ -112,15 +112,15 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
         // (tilePersist: 0 one workgroup per tile, 1 as many workgroups as the device's CUs hold at once, n > 1 that many, rounded up
         // to a multiple of 8 = the tile counters)
         const int64_t resident = int64_t(c->numCus) * std::max<int64_t>(1, int64_t(c->ldsPerCu) / int64_t((lds + 1279) / 1280 * 1280));
-        const int64_t gridP = c->tilePersist > 1 ? int64_t(c->tilePersist) : resident;
-        const bool persist = gt.pooled && c->tilePersist > 0 && (gridP + 7) / 8 * 8 < perX * 8;
+        const int64_t gridP = c->opt.tilePersist > 1 ? int64_t(c->opt.tilePersist) : resident;
+        const bool persist = gt.pooled && c->opt.tilePersist > 0 && (gridP + 7) / 8 * 8 < perX * 8;
         if (!persist)
         {
             at.tileNext = nullptr;
         }
         dim3 grid((unsigned int)(persist ? (gridP + 7) / 8 * 8 : perX * 8)), block(gt.NW * 64);
         int rc = 0;
-        if ((c->cascTurns & 1) && (rc = turnBegin(c, 0, 0))) // (before the profile event: the wait for the turn is not the kernel's time)
+        if ((c->opt.cascadeTurns & 1) && (rc = turnBegin(c, 0, 0))) // (before the profile event: the wait for the turn is not the kernel's time)
         {
             return rc;
         }
@@ -155,7 +155,7 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
 #undef TILE2_NW
 #undef TILE2_LAUNCH
         LAUNCHCHK(c, "k_cascade_tile");
-        if ((c->cascTurns & 1) && (rc = turnEnd(c, 0, 0)))
+        if ((c->opt.cascadeTurns & 1) && (rc = turnEnd(c, 0, 0)))
         {
             return rc;
         }
@@ -334,7 +334,7 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
     const uint32_t* d_cidAll = c->cs.d_cidAll;
     const CascNode2* d_nodes2 = c->cs.d_nodes2;
     prof(c, "k_cascade");
-    const bool rankPath = c->cs.useTiles && !c->noTiles && c->cs.useRank && !c->noRank;
+    const bool rankPath = c->cs.useTiles && c->opt.cascadeTiles && c->cs.useRank && c->opt.rankCells;
     if (pyr == c->d_pyr && !c->floatPyramid && !(rankPath && c->ranksValid))
     {
         // (options changed between acf_hip_pyramid and acf_hip_detect: the float cells this path reads were never written)
@@ -397,13 +397,13 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
         const int qGrid[3] = { std::max(1, blocksPerFrame / 2), std::max(1, blocksPerFrame / 8), std::max(1, std::min(blocksPerFrame, 64)) };
         int firstStage = 0;
         bool pooledTail = false; // k_cascade_tile3D has written the tail's leaf codes: no k_tail_codesD
-        if (c->cs.useTileD && !c->noTiles)
+        if (c->cs.useTileD && c->opt.cascadeTiles)
         {
             // depths 1, 3, 4: trees [0, t1D) of every window from LDS tiles (k_cascade_tileD) instead of the first stages'
             // per-lane gathers from the pyramid; its survivors enter the queue of the stage that ends at t1D
             const auto& cs = c->cs;
             int sD = -1;
-            const bool rankD = cs.useRankD && !c->noRank && pyr == c->d_pyr;
+            const bool rankD = cs.useRankD && c->opt.rankCells && pyr == c->d_pyr;
             const bool pooledRun = rankD || cs.geomD.pooled;
             const int endD = rankD ? cs.geomDR.b[4] : (cs.geomD.pooled ? cs.geomD.b[4] : cs.t1D); // last tree the tile kernel evaluates
             for (int i = 0; i < nStages; i++)
@@ -479,8 +479,8 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
                     const size_t lds = size_t(128) * 4 * (size_t(1) << p.treeDepth) + size_t(at.g.tileFloats) * (rankD ? 2 : 4) +
                         ((std::max(nwin * 8, size_t(at.g.passW) * size_t(at.g.pitchC)) + 15) / 16 * 16) + nwin * 8;
                     const int64_t resident = int64_t(c->numCus) * std::max<int64_t>(1, int64_t(c->ldsPerCu) / int64_t((lds + 1279) / 1280 * 1280));
-                    const int64_t gridP = c->tilePersist > 1 ? int64_t(c->tilePersist) : resident;
-                    const bool persist = c->tilePersist > 0 && (gridP + 7) / 8 * 8 < perX * 8;
+                    const int64_t gridP = c->opt.tilePersist > 1 ? int64_t(c->opt.tilePersist) : resident;
+                    const bool persist = c->opt.tilePersist > 0 && (gridP + 7) / 8 * 8 < perX * 8;
                     // (the staged path's counters [stage][frame] start at d_qcounts; the tile counters sit behind them)
                     at.tileNext = persist ? cs.d_qcounts + size_t(8) * c->maxBatch : nullptr;
                     if (persist)

@@ -133,7 +133,7 @@ int PlanBuild::realScales()
                     return rc;
                 }
             }
-            if (c->taps)
+            if (c->opt.taps)
             {
                 if ((rc = devAlloc(c, &rs.Mn, size_t(B) * np)))
                 {

@@ -192,12 +192,12 @@ int PyramidRun::prepareScales()
     // follows the smoothing of scale k — gradMag, convTri, the cells: column-sequential chains that leave most of the machine
     // idle — runs beside the smaller scales' own chains: every scale gets a stream, ordered by "scale k has been smoothed"
     // events (option scale_streams).
-    if (c->scaleStreams && c->real.size() > 1 && !c->taps)
+    if (c->opt.scaleStreams && c->real.size() > 1 && !c->opt.taps)
     {
         ensureSide(c);
     }
     const size_t nSideS = c->side.size();
-    scalePar = c->scaleStreams && c->real.size() > 1 && nSideS >= c->real.size() - 1 && c->evJoin.size() >= nSideS && !c->taps;
+    scalePar = c->opt.scaleStreams && c->real.size() > 1 && nSideS >= c->real.size() - 1 && c->evJoin.size() >= nSideS && !c->opt.taps;
     while (scalePar && c->evScale.size() < c->real.size())
     {
         hipEvent_t e;
@@ -274,7 +274,7 @@ int PyramidRun::imageResample(size_t k, const float*& img, int64_t& img_fs)
     else if (rs.strip.ok && !exactHalf && !resampleGenericOnly() && (uintptr_t(cur) & 15) == 0)
     {
         // (with the scales on their own streams the next scale's chain would need one more event: the pair is for the one-stream order)
-        const bool pair = rs.stripPair.ok && k + 1 < c->real.size() && srcIdx[k + 1] == srcIdx[k] && !c->taps && !scalePar;
+        const bool pair = rs.stripPair.ok && k + 1 < c->real.size() && srcIdx[k + 1] == srcIdx[k] && !c->opt.taps && !scalePar;
         if (pair)
         {
             pairDone[k + 1] = 1;
@@ -316,7 +316,7 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, SmoothOu
     // convTri(I, I, pColor.smooth, 1) in place (chnsCompute.cpp:239)
     bool& colorDone = so.colorDone;
     bool &gradFused = so.gradFused, &gradBlocked = so.gradBlocked, &triXFused = so.triXFused;
-    const bool fuseSm = p.colorSmooth > 0 && p.colorEnabled && !c->taps && !c->noFusedSmooth && shrink == 4 && rs.h % 4 == 0 && rs.w % 4 == 0 && rs.w >= 16 &&
+    const bool fuseSm = p.colorSmooth > 0 && p.colorEnabled && !c->opt.taps && c->opt.fusedSmooth && shrink == 4 && rs.h % 4 == 0 && rs.w % 4 == 0 && rs.w >= 16 &&
         rs.h / 4 <= SV_MAXW * SV_OWN && img_fs % 4 == 0 && np % 4 == 0 && pl.raw_floats % 1 == 0 && (uintptr_t(img) & 15) == 0;
     if (fuseSm)
     {
@@ -373,10 +373,10 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, SmoothOu
             sa.nPlanes = d;
             // column segments: as many as give a launch ~6 waves per SIMD (a plane is a chain of column steps with
             // nt / 64 waves), each at least 4 warm-ups long; one segment = the plain recursion.  `planesOf`: planes in the launch
-            const int warm = std::max(16, c->smoothWarm);
+            const int warm = std::max(16, c->opt.smoothWarm);
             auto segmentsFor = [&](int planesOf, int& segW_) {
-                int n = c->smoothSegments;
-                if (n == 0 && c->sharedDevice && nF >= 64)
+                int n = c->opt.smoothSegments;
+                if (n == 0 && c->opt.sharedDevice && nF >= 64)
                 {
                     n = 1; // (beside other contexts: the plain chain — no warm-up columns, nothing to verify or repair)
                 }
@@ -408,7 +408,7 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, SmoothOu
             const int64_t gradMinPx = int64_t(1) << 20;
             const int gradMinF = 16;
             const bool wantGrad = (p.gradMagEnabled || p.gradHistEnabled) && gradVecOk && !(d_in == 5 && k == 0) && // (five planes: M, O came with the image)
-                (c->fusedGrad >= 2 || (c->fusedGrad == 1 && np >= gradMinPx && nF >= gradMinF));
+                (c->opt.fusedGrad >= 2 || (c->opt.fusedGrad == 1 && np >= gradMinPx && nF >= gradMinF));
             if (wantGrad)
             {
                 const bool wantTri0 = (p.gradMagEnabled || p.gradHistEnabled) && p.normRad;
@@ -440,7 +440,7 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, SmoothOu
                 // convTri's x pass on the same chain: running sums have no warm-up, so the gradient plane is then one segment
                 // (96 workgroups for 96 frames: slower alone, faster beside other contexts' kernels — DESIGN.md 3.0)
                 const int triMinF = 64;
-                if (blocked0 && p.normRad == 5 && rs.w >= 48 && nt <= 512 && (c->fusedTri >= 2 || (c->fusedTri == 1 && c->sharedDevice && nF >= triMinF)))
+                if (blocked0 && p.normRad == 5 && rs.w >= 48 && nt <= 512 && (c->opt.fusedTri >= 2 || (c->opt.fusedTri == 1 && c->opt.sharedDevice && nF >= triMinF)))
                 {
                     triXFused = true;
                     sa.tU = rs.U;
@@ -464,7 +464,7 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, SmoothOu
                 sa.nSeg = nSeg;
                 sa.segStride = std::max(nSeg, nSegG);
             }
-            const size_t ldsG = ldsB + size_t(GM_ACOS_N) * sizeof(float) + (c->arith ? size_t(X86_GM_N) * sizeof(uint2) : 0); // (+ gradMag's table pairs, option "arith")
+            const size_t ldsG = ldsB + size_t(GM_ACOS_N) * sizeof(float) + (c->opt.arith ? size_t(X86_GM_N) * sizeof(uint2) : 0); // (+ gradMag's table pairs, option "arith")
             if (wantGrad && d == 1 && triXFused)
             {
                 nSeg = nSegG = 1; // (one launch: the gradient plane's)
@@ -571,9 +571,9 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, SmoothOu
             {
                 // the segments' hand-overs, bit for bit; planes with a difference are recomputed as one chain
                 hipLaunchKernelGGL(k_smooth_verify, dim3(nSegMax - 1, d, nF), dim3(256), 0, c->stream, (const float*)c->d_specState, (const float*)c->d_trueState,
-                    rs.h, sa.segStride, d, c->d_redo, c->smoothForceRedo, nSeg, wantGrad ? p.colorChn : -1, nSegG);
+                    rs.h, sa.segStride, d, c->d_redo, c->opt.smoothForceRedo, nSeg, wantGrad ? p.colorChn : -1, nSegG);
                 LAUNCHCHK(c, "k_smooth_verify");
-                if (c->countRepairs)
+                if (c->opt.countRepairs)
                 {
                     std::vector<int32_t> fl(size_t(nF) * d);
                     HIPCHK(c, hipMemcpyAsync(fl.data(), c->d_redo, fl.size() * 4, hipMemcpyDeviceToHost, c->stream));
@@ -622,7 +622,7 @@ int PyramidRun::gradientChannels(size_t k, const SmoothOut& so)
     a.M = rs.M;
     a.S = rs.S;
     a.O = rs.O;
-    a.Mn = c->taps ? rs.Mn : nullptr;
+    a.Mn = c->opt.taps ? rs.Mn : nullptr;
     a.chns = c->d_chns + pl.raw_off[rs.level];
     a.sm_fs = int64_t(d) * np;
     a.m_fs = np;
@@ -654,7 +654,7 @@ int PyramidRun::gradientChannels(size_t k, const SmoothOut& so)
         return launchChns(c, a, shrink, nF);
     }
     const bool gradVec = rs.h % 4 == 0 && np % 4 == 0;
-    const bool fuseCells = shrink == 4 && !c->taps; // k_triy_chns; else S is written and k_chns normalises
+    const bool fuseCells = shrink == 4 && !c->opt.taps; // k_triy_chns; else S is written and k_chns normalises
     a.x86 = x86T(c);
     const bool wantTri = (p.gradMagEnabled || p.gradHistEnabled) && p.normRad;
     const bool blockedMO = wantTri &&
@@ -757,8 +757,8 @@ int PyramidRun::levels(int f0, int nLF)
     float* const chnsF = c->d_chns + int64_t(f0) * pl.raw_floats;
     float* const pyrF = c->d_pyr + int64_t(f0) * pl.pyr_floats;
     const int nL = int(pl.levels.size());
-    const bool waveSmooth = p.smooth > 0 && c->finalMaxH <= 64 * LEVEL_MAX_R_REAL && c->levelMode != 0;
-    const bool fused = waveSmooth && c->fusedOk && c->levelMode == 1;
+    const bool waveSmooth = p.smooth > 0 && c->finalMaxH <= 64 * LEVEL_MAX_R_REAL && c->opt.fusedLevels != 0;
+    const bool fused = waveSmooth && c->fusedOk && c->opt.fusedLevels == 1;
     if (!fused && c->nApproxDescs > 0)
     {
         // ---- approximated levels: one launch, blockIdx.y = level (chnsPyramid.cpp:385-397)
@@ -771,12 +771,12 @@ int PyramidRun::levels(int f0, int nLF)
     {
         // ---- (approximated-scale resample +) smoothing + placement in the padded pyramid: one wave per plane (k_level)
         const float pS = float(12.0 / p.smooth / (p.smooth + 2.0) - 2.0);
-        float* rawOut = (fused && c->taps) ? chnsF : nullptr;
+        float* rawOut = (fused && c->opt.taps) ? chnsF : nullptr;
         const LevelJob* ljobs = fused ? c->d_levelJobs : c->d_levelJobsRaw;
         const auto& groups = fused ? c->levelGroups : c->levelGroupsRaw;
         const ResampleDesc* dd = c->d_descs + c->nImgDescs;
-        const int lvChain = (c->cascTurns & 4) ? 0 : 1;
-        const bool lvTurns = (c->cascTurns & 6) && fused && c->nAllJobs > 0;
+        const int lvChain = (c->opt.cascadeTurns & 4) ? 0 : 1;
+        const bool lvTurns = (c->opt.cascadeTurns & 6) && fused && c->nAllJobs > 0;
         if (lvTurns && (rc = turnBegin(c, 1, lvChain)))
         {
             return rc;
@@ -800,9 +800,9 @@ int PyramidRun::levels(int f0, int nLF)
         // what the levels leave as: floats (always, unless the caller has declared the float pyramid unneeded), and the
         // cascade's 16-bit rank cells when every level goes through this one launch
         // (the rank cells have one reader, the tile kernel: a plan or option that routes the cascade elsewhere keeps floats)
-        const bool emitRank = fused && c->levelsEmitRank && c->cs.useRank && !c->noRank && !c->taps && (c->cs.useTiles || c->cs.useRankD) && !c->noTiles;
+        const bool emitRank = fused && c->levelsEmitRank && c->cs.useRank && c->opt.rankCells && !c->opt.taps && (c->cs.useTiles || c->cs.useRankD) && c->opt.cascadeTiles;
         // (depths other than 2 keep the floats: their queue's overflow path reads them)
-        const bool emitF32 = !(emitRank && !c->keepPyramid && !c->autoLambdas) || c->cs.useRankD;
+        const bool emitF32 = !(emitRank && !c->opt.keepPyramid && !c->autoLambdas) || c->cs.useRankD;
         wroteRank = emitRank;
         wroteF32 = emitF32;
         if (nAll > 0)
@@ -820,11 +820,11 @@ int PyramidRun::levels(int f0, int nLF)
             // column segments for small batches (a level's chain of up to wC column steps is then the launch's duration):
             // as many as give the launch ~4 waves per SIMD, at most levelSegCap; every hand-over verified on the device
             int nSegL = 1;
-            const int warmL = std::max(4, c->levelWarm / 4 * 4);
-            if (fused && !c->taps && nLF <= c->levelSegFrames && c->levelSegments != 1 && !c->autoLambdas)
+            const int warmL = std::max(4, c->opt.levelWarm / 4 * 4);
+            if (fused && !c->opt.taps && nLF <= c->levelSegFrames && c->opt.levelSegments != 1 && !c->autoLambdas)
             {
                 const int64_t wavesL = int64_t(nAll) * pl.nChns * nLF;
-                nSegL = c->levelSegments > 1 ? c->levelSegments : int((4 * 1024 + wavesL - 1) / wavesL); // 0: ~4 waves per SIMD
+                nSegL = c->opt.levelSegments > 1 ? c->opt.levelSegments : int((4 * 1024 + wavesL - 1) / wavesL); // 0: ~4 waves per SIMD
                 nSegL = std::max(1, std::min(nSegL, c->levelSegCap));
             }
             LevelSegArgs lsa{};
@@ -844,8 +844,8 @@ if (nSegL > 1)                                                                  
     hipLaunchKernelGGL((k_level_all<OUT, 1>), lgrid, lblock, ldsL, c->stream, (const float*)chnsF, pyrF, rawOut, ljobs, dd, \
         (const int32_t*)c->d_it, (const float*)c->d_ft, pl.nChns, pl.raw_floats, pl.pyr_floats, pS, c->d_dump, nLF, ra, lsa); \
     hipLaunchKernelGGL(k_level_verify, dim3(nAll * nSegL, pl.nChns, nLF), dim3(64), 0, c->stream, (const float*)c->d_lvSpec,  \
-        (const float*)c->d_lvTrue, ljobs, lsa, pl.nChns, c->d_lvRedo, c->smoothForceRedo);                               \
-    if (c->countRepairs)                                                                                                \
+        (const float*)c->d_lvTrue, ljobs, lsa, pl.nChns, c->d_lvRedo, c->opt.smoothForceRedo);                           \
+    if (c->opt.countRepairs)                                                                                            \
     {                                                                                                                   \
         std::vector<int32_t> fl(size_t(nLF) * nAll * pl.nChns);                                                         \
         HIPCHK(c, hipMemcpyAsync(fl.data(), c->d_lvRedo, fl.size() * 4, hipMemcpyDeviceToHost, c->stream));             \

@@ -134,6 +134,29 @@ def test_capacity_error_is_reported():
     det.close()
 
 
+def test_option_ranges_and_errors():
+    """acf_hip_set_option's accepted ranges and error texts, on a context with sub-batch children (options set after the plan)."""
+    from acf_amd.detector import HipDetector, HipError
+    H, W, kind, d_in, kw = CONFIGS["tiny_luv"]
+    det = HipDetector(synth.make_model(seed=3, **kw), H, W, d_in, max_batch=4, max_hits=1 << 12, streams=2)
+    level = "option: level_warm a positive multiple of 4, level_segments >= 0"
+    smooth = "option: smooth_segments >= 0, smooth_warm a multiple of 16"
+    for key, value, msg in [("streams", 0, "streams: 1..6"), ("streams", 7, "streams: 1..6"),
+                            ("level_warm", 0, level), ("level_warm", 6, level), ("level_segments", -1, level), ("count_repairs", -1, level),
+                            ("smooth_segments", -1, smooth), ("smooth_force_redo", -1, smooth), ("smooth_warm", 8, smooth),
+                            ("smooth_warm", -16, smooth),
+                            ("arith", 1, "arith: install a CPU's tables first (acf_hip_set_x86_tables)"),
+                            ("no_such_option", 1, "unknown option no_such_option")]:
+        with pytest.raises(HipError) as e:
+            det.set_option(key, value)
+        assert e.value.code == 1 and str(e.value).endswith(": " + msg), (key, value, str(e.value))
+    for key, value in [("streams", 1), ("streams", 6), ("level_warm", 4), ("level_warm", 36), ("level_segments", 0), ("count_repairs", 0),
+                       ("smooth_segments", 0), ("smooth_force_redo", 0), ("smooth_warm", 0), ("smooth_warm", 48), ("arith", 0),
+                       ("fused_levels", 3), ("fused_levels", 1), ("tile_persist", 24), ("tile_persist", 1), ("graph", 1), ("graph", 0)]:
+        det.set_option(key, value)
+    det.close()
+
+
 @pytest.mark.parametrize("max_hits", [128, 1 << 16])
 def test_windows_sharing_an_offset(oracle, max_hits):
     """stride < shrink: the cascade runs once per distinct cell offset and k_expand_hits writes every window of a surviving

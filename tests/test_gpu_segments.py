@@ -114,8 +114,10 @@ def test_one_plane_input_with_its_colour_channel(oracle, H, W, fused_tri):
     det.close()
 
 
-def test_segmented_smoothing_rgb_and_sub_batches(oracle):
-    """RGB input (the smoothing follows rgb2luv), sub-batch contexts (option streams) and the rank-cell cascade together."""
+@pytest.mark.parametrize("options_after_plan", [False, True], ids=["options_before_plan", "options_after_plan"])
+def test_segmented_smoothing_rgb_and_sub_batches(oracle, options_after_plan):
+    """RGB input (the smoothing follows rgb2luv), sub-batch contexts (option streams) and the rank-cell cascade together.  The options
+    reach the two children either through acf_hip_plan (set before it) or through acf_hip_set_option (set after it)."""
     import torch
     from acf_amd.detector import HipDetector
     H, W = 200, 512
@@ -123,11 +125,24 @@ def test_segmented_smoothing_rgb_and_sub_batches(oracle):
     frames = np.stack([synth.make_frame(71 + i, H, W, "rgb") for i in range(4)])
     det = HipDetector(streams=2)
     det.set_model(model)
+    if options_after_plan:
+        det.plan(H, W, 3, max_batch=4, max_hits=1 << 15)
+        det.set_option("count_repairs", 1)
+        det.set_option("smooth_force_redo", 1)
     det.set_option("smooth_segments", 6)
     det.set_option("smooth_warm", 32)
     det.set_option("fused_grad", 2)
-    det.plan(H, W, 3, max_batch=4, max_hits=1 << 15)
+    if not options_after_plan:
+        det.plan(H, W, 3, max_batch=4, max_hits=1 << 15)
     _check(oracle, det, frames, model, H, W)
+    if options_after_plan:
+        # planes were forced through the repair launch and counted, in both children: each ran two frames, and a batch of two
+        # runs in the first child alone and counts half as many
+        r4 = det.repairs()
+        assert r4[1] > 0, r4
+        det.run(torch.from_numpy(frames[:2]).cuda())
+        r2 = [b - a for a, b in zip(r4, det.repairs())]
+        assert [2 * x for x in r2] == list(r4), (r2, r4)
     det.close()
 
 
