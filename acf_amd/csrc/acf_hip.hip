@@ -51,6 +51,30 @@ struct RealScale
 
 } // namespace
 
+// One set of tile tables of the LDS-tiled cascade (buildTileSet): geometry, tile list, node records with tile-layout offsets, on
+// float cells or on 16-bit threshold-rank cells (thresholds then as rank indices).
+struct TileSet
+{
+    bool ok = false;
+    TileGeom g{};
+    int nTiles = 0, aTB = 4;
+    CascTile* d_tiles = nullptr;
+    TreeNode* d_tileNodes = nullptr;  // depth 2: every tree
+    uint32_t* d_tileNodesS = nullptr; // depth 2, stage A of k_cascade_tile3: 10 * aTB dwords per batch of aTB trees
+    // depths other than 2 (k_cascade_tileD): records of trees [0, t1D) in batches of tbD
+    uint32_t* d_nodesD = nullptr;
+    int tbD = 0, t1D = 0;
+    uint32_t* d_tileOffD = nullptr; // k_cascade_tile3D: tile offsets of every node, [tree][nTreeNodes]
+    uint32_t* d_thrsRankD = nullptr; // ... and, on rank cells, the thresholds' rank indices in the same layout
+};
+
+// A leaf-code buffer: [frame][cap][pitch] bytes, 4 * leaf index of every tail tree of the first cap queue entries of a frame.
+struct LeafCodes
+{
+    uint8_t* d = nullptr;
+    int cap = 0, pitch = 0;
+};
+
 // Everything the cascade launch needs on the device.
 struct CascState
 {
@@ -72,45 +96,20 @@ struct CascState
     uint2* d_queue[2] = { nullptr, nullptr }; // survivor queues between cascade stages
     int32_t* d_qcounts = nullptr;             // [stage][frame]
     int qcap = 0;
-    // LDS-tiled path (depth-2 models, stride a multiple of shrink)
-    bool useTiles = false;
-    CascTile* d_tiles = nullptr;
-    int nTiles = 0;
-    TreeNode* d_tileNodes = nullptr; // offsets in the tile's LDS layout, every tree
-    uint32_t* d_tileNodesS = nullptr; // stage A of k_cascade_tile3: 40 dwords per batch of four trees
-    int aTB = 4;                      // trees per stage-A batch of the tile kernels
+    // LDS-tiled path (stride a multiple of shrink): the tile sets over float cells and over threshold-rank cells (host_plan.h).
+    // Depth 2: k_cascade_tile3 + the tail; depths 1, 3, 4: the staged path's first stages (k_cascade_tile3D if g.pooled, else
+    // k_cascade_tileD).  A set that is not in use has ok == false; tilesR.ok implies tiles.ok.
+    TileSet tiles, tilesR;
+    // depth 2: the tail beyond tiles.g.b[4] (k_cascade_tail3, k_cascade_tail_rank)
     TreeNode* d_tailNodes = nullptr; // offsets = feature ids (window-local layout), all trees
-    TileGeom geom{};
+    TreeNode* d_tailNodesR = nullptr; // k_cascade_tail_rank: packed (z, c, r) feature positions, thresholds as rank indices
     int tailWaves = 0;
     float* d_tailScratch = nullptr; // k_cascade_tail3 leaf matrices: [blocks][tailWaves][TAIL_G][tailPad]
     int tailPad = 0, tailSlab = 0, tailBlocks = 0, tailNodesLds = 0;
-    // stage E of the tile kernels + k_tail_scan: leaf codes of the first codeCap queue entries per frame
-    uint8_t* d_tailCodes = nullptr;
-    int codeCap = 0, codePitch = 0;
-    // fixed depths other than 2 (k_cascade_tileD): stage 0 of the staged path on float tiles
-    bool useTileD = false;
-    CascTile* d_tilesD = nullptr;
-    uint32_t* d_tileOffD = nullptr;
-    // the same tiles over rank cells (k_cascade_tile3D<.., CellRank>)
-    bool useRankD = false;
-    TileGeom geomDR{};
-    CascTile* d_tilesDR = nullptr;
-    int nTilesDR = 0;
-    uint32_t *d_nodesDR = nullptr, *d_tileOffDR = nullptr, *d_thrsRankD = nullptr;
-    int nTilesD = 0, tbD = 0, t1D = 0;
-    TileGeom geomD{};
-    uint32_t* d_nodesD = nullptr;
-    // fixed depths 1..4, last stage [128, nTrees) of the staged path as leaf codes + ordered scan (k_tail_codesD / k_tail_scanD)
-    uint8_t* d_codesD = nullptr;
-    int codeCapD = 0, codePitchD = 0;
-    // threshold-rank cells (host_plan.h): the tile kernel's second form, reading a 16-bit pyramid
-    bool useRank = false;
-    TileGeom geomR{};
-    CascTile* d_tilesR = nullptr;
-    int nTilesR = 0;
-    TreeNode* d_tileNodesR = nullptr;  // rank-tile offsets, thresholds as rank indices
-    TreeNode* d_tailNodesR = nullptr;  // k_cascade_tail_rank: packed (z, c, r) feature positions, thresholds as rank indices
-    uint32_t* d_tileNodesSR = nullptr;
+    // the tail's leaf codes of the first codes.cap queue entries per frame (depth 2: stage E of k_cascade_tile3 + k_tail_scan;
+    // depths 1..4: stage E of k_cascade_tile3D or k_tail_codesD, + k_tail_scanD)
+    LeafCodes codes;
+    // the rank pyramid (threshold-rank cells, 16 bits each) and the tables that make it from the float pyramid (k_rank)
     RankChan* d_rankChan = nullptr;
     RankRec* d_rankRec = nullptr;
     int rankMaxRec = 0;
@@ -341,6 +340,12 @@ struct acf_hip_ctx
         uint8_t* d_out = nullptr; // [maxBatch][plan.H][plan.W][4]
     } rz;
 };
+
+// the ONE statement of "the plan has rank cells and option rank_cells is on"; each reader adds its own terms
+static inline bool rankCellsOn(const acf_hip_ctx* c)
+{
+    return c->cs.tilesR.ok && c->opt.rankCells;
+}
 
 #define HIPCHK(ctx, call)                                                                                  \
     do                                                                                                     \
@@ -1445,7 +1450,7 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
     return ACF_HIP_OK;
 }
 
-#include "cascade_plan.hip.h"  // ShrinkScope, TileSet, buildTileSet, buildCascadeTables
+#include "cascade_plan.hip.h"  // ShrinkScope, splitFid, pooledTileLds, buildTileSet, buildCascadeTables
 
 #include "resample_plan.hip.h" // stripPlan, launchStrip, resampleTilePlan
 
@@ -1970,7 +1975,7 @@ int acf_hip_op_resize_u8(acf_hip_ctx* c, const uint8_t* src, int rows, int cols,
     return rc;
 }
 
-#include "cascade_run.hip.h"    // allowLds, runCascadeTiled, launchNms, runCascade
+#include "cascade_run.hip.h"    // allowLds, wholeCascadeTiled, runCascadeTiled, runTileStageD, launchNms, runCascade
 
 int acf_hip_detect(acf_hip_ctx* c)
 {
@@ -2066,7 +2071,7 @@ static void graphRunState(acf_hip_ctx* c, const acf_hip_ctx::GraphSlot& gs)
 // frame waits for every node of the chain (runCascade / runCascadeTiled then skip their own memsets)
 static int preZeroCounters(acf_hip_ctx* c, int nF)
 {
-    if (!c || !c->hasPlan || !c->kids.empty() || !tiledCascadeSelected(c) || c->p.ldcfK > 0 || !c->cs.d_counts || !c->cs.d_qcounts || nF <= 0 ||
+    if (!c || !c->hasPlan || !c->kids.empty() || !wholeCascadeTiled(c) || c->p.ldcfK > 0 || !c->cs.d_counts || !c->cs.d_qcounts || nF <= 0 ||
         nF > c->maxBatch)
     {
         return ACF_HIP_OK;
@@ -2934,7 +2939,7 @@ int acf_hip_read_rank_level(acf_hip_ctx* c, int frame, int level, uint16_t* host
     {
         return ACF_HIP_E_NOPLAN;
     }
-    if (!c->cs.useRank || !c->opt.rankCells)
+    if (!rankCellsOn(c))
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, "read_rank_level: the plan has no rank cells (model not depth 2 / thresholds too dense / option rank_cells off / LDCF)");
     }

@@ -14,25 +14,27 @@ struct ShrinkScope
     ~ShrinkScope() { c->p.shrink = saved; }
 };
 
-// Build the cascade tables for a list of level geometries (hP, wP) into the
-// context.  Shared by acf_hip_plan and acf_hip_op_acf_detect1.
-// One set of tile tables of the LDS-tiled cascade: geometry, tile list, node records with tile-layout offsets.  `rank` ==
-// nullptr: float cells, thresholds as float bits; else 16-bit threshold-rank cells, thresholds as rank indices.
-struct TileSet
+// A feature id's channel, column and row in the model window (computeChannelIndexColMajor, acfDetect1.cpp:390-406).
+struct FeatPos
 {
-    bool ok = false;
-    TileGeom g{};
-    int nTiles = 0, aTB = 4;
-    CascTile* d_tiles = nullptr;
-    TreeNode* d_tileNodes = nullptr;
-    uint32_t* d_tileNodesS = nullptr;
-    // depths other than 2 (k_cascade_tileD): records of trees [0, t1D) in batches of tbD
-    uint32_t* d_nodesD = nullptr;
-    int tbD = 0, t1D = 0;
-    uint32_t* d_tileOffD = nullptr; // k_cascade_tile3D: tile offsets of every node, [tree][nTreeNodes]
-    uint32_t* d_thrsRankD = nullptr; // ... and, on rank cells, the thresholds' rank indices in the same layout
+    uint32_t z, cc, rr;
 };
 
+static inline FeatPos splitFid(uint32_t f, int mW, int mH)
+{
+    return { f / uint32_t(mW * mH), (f / uint32_t(mH)) % uint32_t(mW), f % uint32_t(mH) };
+}
+
+// Dynamic LDS of the pooled tile kernels: leaf table (k_cascade_tile3: TILE3_LEAF_BYTES, k_cascade_tile3D: 128 * 4 << depth) +
+// footprint + list 1 (later the codes of 64 windows) + list 2.  The kernels add a few static words.
+static size_t pooledTileLds(const TileGeom& g, int cellBytes, size_t leafBytes)
+{
+    const size_t nwin = size_t(g.NW) * 64;
+    return leafBytes + size_t(g.tileFloats) * cellBytes + ((std::max(nwin * 8, size_t(g.passW) * size_t(g.pitchC)) + 15) / 16 * 16) + nwin * 8;
+}
+
+// One set of tile tables for the levels lv into `out` (ok == false: no tiled form fits).  `rank` == nullptr: float cells,
+// thresholds as float bits; else 16-bit threshold-rank cells, thresholds as rank indices.
 static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nChns, const RankTables* rank, TileSet& out, bool allowPooledD = true)
 {
     const acf_hip_params& p = c->p;
@@ -91,23 +93,26 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
     // waves per tile: the largest of 8/4/2/1 whose footprint + survivor lists leave room for several workgroups per CU
     // (160 KiB LDS: three with rank cells, two with floats), else one
     const int W = 1; // windows per lane in stage A
+    const size_t leafBytes = pooledD ? size_t(128) * 4 << p.treeDepth : size_t(TILE3_LEAF_BYTES);
     auto ldsBytes = [&](int nw, int passW) {
         const int tc = nw * W * (64 / g.TR);
         const int64_t rows = int64_t(g.TR - 1) * g.step + mH, cols = int64_t(tc - 1) * g.step + mW;
         const int64_t rowsP = (rows + CPB - 1) / CPB * CPB;
+        const int64_t cells = int64_t(nChns) * rowsP * cols;
         // k_cascade_tileD (depths other than 2 on float cells): footprint + one survivor list segment per wave (+ its few static words)
         if (!g.pooled)
         {
-            return int64_t(nChns) * rowsP * cols * cellBytes + int64_t(nw) * 64 * 8 + 64;
+            return cells * cellBytes + int64_t(nw) * 64 * 8 + 64;
         }
-        // k_cascade_tile3: leaf table + footprint + list 1 (later the codes of 64 windows) + list 2
-        const int64_t nwin = int64_t(nw) * 64;
-        const int64_t leafBytes = pooledD ? int64_t(128) * 4 * (int64_t(1) << p.treeDepth) : int64_t(TILE3_LEAF_BYTES);
-        if (int64_t(nChns) * rowsP * cols > 65535)
+        if (cells > 65535)
         {
-            return int64_t(1) << 40; // (its list entries hold a window's first cell in 16 bits)
+            return int64_t(1) << 40; // (the pooled kernels' list entries hold a window's first cell in 16 bits)
         }
-        return leafBytes + int64_t(nChns) * rowsP * cols * cellBytes + ((std::max<int64_t>(nwin * 8, passW * int64_t(g.pitchC)) + 15) / 16 * 16) + nwin * 8 + 64;
+        TileGeom t = g;
+        t.NW = nw;
+        t.passW = passW;
+        t.tileFloats = int(cells);
+        return int64_t(pooledTileLds(t, cellBytes, leafBytes)) + 64; // (+ the kernels' static words)
     };
     int nw = 0;
     if (const char* e = getenv("ACF_HIP_TILE_TR")) // tuning knobs: rows of windows per tile, waves per tile
@@ -204,12 +209,11 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
             const int tq = t % TB;
             for (int k = 0; k < NN; k++)
             {
-                const uint32_t f = c->fids[q + k];
-                const uint32_t z = f / (mW * mH), cc = (f / mH) % mW, rr = f % mH; // computeChannelIndexColMajor, acfDetect1.cpp:390-406
-                d[tq * NN + k] = (z * uint32_t(g.colsT) + cc) * uint32_t(g.rowsP) + rr;
+                const FeatPos f = splitFid(c->fids[q + k], mW, mH);
+                d[tq * NN + k] = (f.z * uint32_t(g.colsT) + f.cc) * uint32_t(g.rowsP) + f.rr;
                 if (rank)
                 {
-                    d[TB * NN + tq * NN + k] = rank->rankOfThreshold(int(z), c->thrs[q + k]);
+                    d[TB * NN + tq * NN + k] = rank->rankOfThreshold(int(f.z), c->thrs[q + k]);
                 }
                 else
                 {
@@ -232,12 +236,11 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
             {
                 for (int k = 0; k < NN; k++)
                 {
-                    const uint32_t f = c->fids[size_t(t) * p.nTreeNodes + k];
-                    const uint32_t z = f / (mW * mH), cc = (f / mH) % mW, rr = f % mH;
-                    to[size_t(t) * p.nTreeNodes + k] = (z * uint32_t(g.colsT) + cc) * uint32_t(g.rowsP) + rr;
+                    const FeatPos f = splitFid(c->fids[size_t(t) * p.nTreeNodes + k], mW, mH);
+                    to[size_t(t) * p.nTreeNodes + k] = (f.z * uint32_t(g.colsT) + f.cc) * uint32_t(g.rowsP) + f.rr;
                     if (rank)
                     {
-                        tr[size_t(t) * p.nTreeNodes + k] = rank->rankOfThreshold(int(z), c->thrs[size_t(t) * p.nTreeNodes + k]);
+                        tr[size_t(t) * p.nTreeNodes + k] = rank->rankOfThreshold(int(f.z), c->thrs[size_t(t) * p.nTreeNodes + k]);
                     }
                 }
             }
@@ -264,12 +267,11 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
         TreeNode a{};
         for (int k = 0; k < 3; k++)
         {
-            const uint32_t f = c->fids[q + k];
-            const uint32_t z = f / (mW * mH), cc = (f / mH) % mW, rr = f % mH; // computeChannelIndexColMajor, acfDetect1.cpp:390-406
-            a.off[k] = (z * uint32_t(g.colsT) + cc) * uint32_t(g.rowsP) + rr;
+            const FeatPos f = splitFid(c->fids[q + k], mW, mH);
+            a.off[k] = (f.z * uint32_t(g.colsT) + f.cc) * uint32_t(g.rowsP) + f.rr;
             if (rank)
             {
-                const uint32_t rk = rank->rankOfThreshold(int(z), c->thrs[q + k]);
+                const uint32_t rk = rank->rankOfThreshold(int(f.z), c->thrs[q + k]);
                 memcpy(&a.thr[k], &rk, 4);
             }
             else
@@ -316,6 +318,54 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
     return ACF_HIP_OK;
 }
 
+// The leaf-code buffer of a tail of nT trees, batch-wide.  Entries per frame with codes: 1/64 of the windows (the tail sees ~1/700
+// of them on natural images), at most 256 MB for the batch (the rows are touched per survivor: ~1k of them per 1080p frame);
+// whatever is beyond goes to the tail kernels, and so does everything if the buffer cannot be had (cap == 0).
+static LeafCodes leafCodeBuffer(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nT)
+{
+    LeafCodes lc;
+    lc.pitch = (nT + 63) / 64 * 64; // stage E writes whole 64-tree batches
+    int64_t nWinTotal = 0;
+    for (const auto& l : lv)
+    {
+        nWinTotal += int64_t(std::max(l.nWinR, 0)) * std::max(l.nWinC, 0);
+    }
+    int64_t cap = std::min<int64_t>(std::max<int64_t>(nWinTotal / 64, 1024), 8192);
+    cap = std::min(cap, std::max<int64_t>((int64_t(1) << 28) / (int64_t(std::max(c->maxBatch, 1)) * lc.pitch), 256));
+    cap = std::min<int64_t>(cap, std::max<int64_t>(nWinTotal, 1));
+    void* codes = nullptr;
+    if (hipMalloc(&codes, size_t(std::max(c->maxBatch, 1)) * size_t(cap) * size_t(lc.pitch)) == hipSuccess)
+    {
+        c->allocs.push_back(codes);
+        lc.d = static_cast<uint8_t*>(codes);
+        lc.cap = int(cap);
+    }
+    else
+    {
+        (void)hipGetLastError();
+    }
+    return lc;
+}
+
+// The rank tables of the model's thresholds (host_plan.h; they do not depend on the depth) and, if there are any, the tile set
+// over rank cells; `internal`: which nodes carry a feature test.
+static int buildRankSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nChns, const std::vector<uint8_t>& internal, RankTables& rt, TileSet& ts)
+{
+    const int mH = c->p.modelDsPad_h / c->p.shrink, mW = c->p.modelDsPad_w / c->p.shrink;
+    std::vector<int32_t> chnOfNode(internal.size(), -1);
+    for (size_t q = 0; q < internal.size(); q++)
+    {
+        if (internal[q])
+        {
+            chnOfNode[q] = int32_t(splitFid(c->fids[q], mW, mH).z);
+        }
+    }
+    buildRankTables(c->thrs.data(), chnOfNode.data(), internal.size(), nChns, rt);
+    return rt.ok ? buildTileSet(c, lv, nChns, &rt, ts) : ACF_HIP_OK;
+}
+
+// Build the cascade tables for a list of level geometries (hP, wP) into the
+// context.  Shared by acf_hip_plan and acf_hip_op_acf_detect1.
 static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nChns, CascState& cs, bool wantRank = false)
 {
     CascLevel** d_levels = &cs.d_cascLevels;
@@ -399,9 +449,8 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
                 uint32_t v = 0;
                 if (internal[q])
                 {
-                    const uint32_t f = c->fids[q];
-                    const uint32_t z = f / (mW * mH), cc = (f / mH) % mW, rr = f % mH;
-                    v = uint32_t(z * area + int64_t(cc) * L.hP + rr);
+                    const FeatPos f = splitFid(c->fids[q], mW, mH);
+                    v = uint32_t(f.z * area + int64_t(f.cc) * L.hP + f.rr);
                 }
                 cidAll.push_back(v);
             }
@@ -422,9 +471,8 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             const size_t q = size_t(t) * p.nTreeNodes;
             for (int k = 0; k < 3; k++)
             {
-                const uint32_t f = c->fids[q + k];
-                const uint32_t z = f / (mW * mH), cc = (f / mH) % mW, rr = f % mH;
-                nd.zcr[k] = (z << 24) | (cc << 12) | rr;
+                const FeatPos f = splitFid(c->fids[q + k], mW, mH);
+                nd.zcr[k] = (f.z << 24) | (f.cc << 12) | f.rr;
                 nd.thr[k] = c->thrs[q + k];
             }
             for (int k = 0; k < 4; k++)
@@ -456,39 +504,18 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
     {
         return rc;
     }
-    // ---- LDS-tiled path (kernels.hip.h, k_cascade_tile3 + stage E + k_tail_scan, k_cascade_tail3 for queue overflow)
-    cs.useTiles = false;
-    cs.useRank = false;
-    cs.useTileD = false;
-    cs.useRankD = false;
-    cs.codeCapD = 0;
+    // ---- LDS-tiled path (kernels.hip.h): a tile set is kept only where its kernels take it
+    cs.tiles = TileSet{};
+    cs.tilesR = TileSet{};
+    cs.codes = LeafCodes{};
+    const bool tiled = p.treeDepth >= 1 && p.treeDepth <= 4 && p.stride % p.shrink == 0 && p.stride >= p.shrink;
     if (!packed && p.treeDepth >= 1 && p.treeDepth <= 4 && p.nTrees > 128 && !fallbackForced(FB_NO_TAIL_CODES))
     {
-        // the staged path's last stage [128, nTrees) as leaf codes + ordered scan: the first codeCapD queue entries of a frame
-        // (sized like the depth-2 path's), when the scan's leaf table fits a workgroup's LDS
+        // the staged path's last stage [128, nTrees) as leaf codes + ordered scan, when the scan's leaf table fits a workgroup's LDS
         const int nT = p.nTrees - 128, NL = 1 << p.treeDepth;
         if (int64_t((nT + 15) / 16 * 16) * NL * 4 <= 150 * 1024)
         {
-            cs.codePitchD = (nT + 63) / 64 * 64;
-            int64_t nWinTotal = 0;
-            for (const auto& l : lv)
-            {
-                nWinTotal += int64_t(std::max(l.nWinR, 0)) * std::max(l.nWinC, 0);
-            }
-            int64_t cap = std::min<int64_t>(std::max<int64_t>(nWinTotal / 64, 1024), 8192);
-            cap = std::min(cap, std::max<int64_t>((int64_t(1) << 28) / (int64_t(std::max(c->maxBatch, 1)) * cs.codePitchD), 256));
-            cap = std::min<int64_t>(cap, std::max<int64_t>(nWinTotal, 1));
-            void* codes = nullptr;
-            if (hipMalloc(&codes, size_t(std::max(c->maxBatch, 1)) * size_t(cap) * size_t(cs.codePitchD)) == hipSuccess)
-            {
-                c->allocs.push_back(codes);
-                cs.d_codesD = static_cast<uint8_t*>(codes);
-                cs.codeCapD = int(cap);
-            }
-            else
-            {
-                (void)hipGetLastError();
-            }
+            cs.codes = leafCodeBuffer(c, lv, nT);
         }
     }
     // the rank pyramid of a plan: per level nChns planes [wP][pitchR], pitchR = hP rounded up to 8 cells (16 bytes); bucket tables on
@@ -523,71 +550,48 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
         HIPCHK(c, hipMemcpy(*d_levels, cl.data(), cl.size() * sizeof(CascLevel), hipMemcpyHostToDevice));
         return ACF_HIP_OK;
     };
-    if (!packed && p.treeDepth >= 1 && p.treeDepth <= 4 && p.stride % p.shrink == 0 && p.stride >= p.shrink)
+    if (!packed && tiled)
     {
-        TileSet tsD;
-        if ((rc = buildTileSet(c, lv, nChns, nullptr, tsD)))
+        // depths 1, 3, 4: the staged path's first stages from LDS tiles
+        TileSet ts;
+        if ((rc = buildTileSet(c, lv, nChns, nullptr, ts)))
         {
             return rc;
         }
-        if (tsD.ok && (tsD.g.NW == 8 || tsD.g.NW == 4))
+        if (ts.ok && (ts.g.NW == 8 || ts.g.NW == 4))
         {
-            cs.useTileD = true;
-            cs.d_tilesD = tsD.d_tiles;
-            cs.nTilesD = tsD.nTiles;
-            cs.tbD = tsD.tbD;
-            cs.t1D = tsD.t1D;
-            cs.geomD = tsD.g;
-            cs.d_nodesD = tsD.d_nodesD;
-            cs.d_tileOffD = tsD.d_tileOffD;
-            // ---- the pooled kernel on threshold-rank cells (the rank tables do not depend on the depth): half the fill, three
-            // workgroups per CU.  The float pyramid is still written for these depths (the queue's overflow path reads it).
-            if ((tsD.g.pooled || p.treeDepth == 1) && wantRank && c->opt.rankCells && !fallbackForced(FB_TILED_STAGED))
+            cs.tiles = ts;
+            // ---- the pooled kernel on threshold-rank cells: half the fill, three workgroups per CU.  The float pyramid is still
+            // written for these depths (the queue's overflow path reads it).
+            if ((ts.g.pooled || p.treeDepth == 1) && wantRank && c->opt.rankCells && !fallbackForced(FB_TILED_STAGED))
             {
-                const int mHc = p.modelDsPad_h / p.shrink, mWc = p.modelDsPad_w / p.shrink;
-                std::vector<int32_t> chnOfNode(nNodes, -1);
-                for (size_t q = 0; q < nNodes; q++)
-                {
-                    if (internal[q])
-                    {
-                        chnOfNode[q] = int32_t(c->fids[q] / uint32_t(mWc * mHc));
-                    }
-                }
                 RankTables rt;
-                buildRankTables(c->thrs.data(), chnOfNode.data(), nNodes, nChns, rt);
                 TileSet tsR;
-                if (rt.ok && (rc = buildTileSet(c, lv, nChns, &rt, tsR)))
+                if ((rc = buildRankSet(c, lv, nChns, internal, rt, tsR)))
                 {
                     return rc;
                 }
-                if (rt.ok && tsR.ok && tsR.g.pooled && tsR.d_thrsRankD && (tsR.g.NW == 8 || tsR.g.NW == 4))
+                if (tsR.ok && tsR.g.pooled && tsR.d_thrsRankD && (tsR.g.NW == 8 || tsR.g.NW == 4))
                 {
                     if ((rc = setupRankPyramid(rt)))
                     {
                         return rc;
                     }
-                    cs.geomDR = tsR.g;
-                    cs.d_tilesDR = tsR.d_tiles;
-                    cs.nTilesDR = tsR.nTiles;
-                    cs.d_nodesDR = tsR.d_nodesD;
-                    cs.d_tileOffDR = tsR.d_tileOffD;
-                    cs.d_thrsRankD = tsR.d_thrsRankD;
-                    cs.useRank = true;
-                    cs.useRankD = true;
+                    cs.tilesR = tsR;
                 }
             }
         }
     }
-    if (packed && p.stride % p.shrink == 0 && p.stride >= p.shrink)
+    if (packed && tiled)
     {
-        TileSet tsF;
-        if ((rc = buildTileSet(c, lv, nChns, nullptr, tsF)))
+        // depth 2: k_cascade_tile3 + stage E + k_tail_scan, k_cascade_tail3 for queue overflow
+        TileSet ts;
+        if ((rc = buildTileSet(c, lv, nChns, nullptr, ts)))
         {
             return rc;
         }
-        const int mHc = p.modelDsPad_h / p.shrink, mWc = p.modelDsPad_w / p.shrink;
         int tw = 0;
-        const int winFloats = nChns * mWc * mHc;
+        const int winFloats = nChns * mW * mH;
         const int tailSlab = (std::max(winFloats, TAIL_G * TAIL_PITCH) + 3) / 4 * 4; // footprint, reused as phase 2's transposition tile (16-byte rows)
         for (int64_t limit : { int64_t(80) * 1024, int64_t(159) * 1024 })
         {
@@ -599,9 +603,9 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
                 }
             }
         }
-        if (tsF.ok && tw)
+        if (ts.ok && tw)
         {
-            const TileGeom& g = tsF.g;
+            const TileGeom& g = ts.g;
             std::vector<TreeNode> tailNodes(static_cast<size_t>(p.nTrees));
             for (int t = 0; t < p.nTrees; t++)
             {
@@ -618,12 +622,6 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
                 }
                 tailNodes[size_t(t)] = b;
             }
-            cs.aTB = tsF.aTB;
-            cs.d_tileNodesS = tsF.d_tileNodesS;
-            cs.d_tileNodes = tsF.d_tileNodes;
-            cs.d_tiles = tsF.d_tiles;
-            cs.nTiles = tsF.nTiles;
-            cs.geom = g;
             cs.tailWaves = tw;
             cs.tailSlab = tailSlab;
             cs.tailPad = (std::max(p.nTrees - g.b[4], 1) + 63) / 64 * 64;
@@ -636,59 +634,25 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             {
                 return rc;
             }
-            cs.codeCap = 0;
             if (g.b[4] < p.nTrees && !fallbackForced(FB_TAIL3)) // (forced: every tail window goes to k_cascade_tail3)
             {
-                const int nT = p.nTrees - g.b[4];
-                cs.codePitch = (nT + 63) / 64 * 64; // stage E writes whole 64-tree batches
-                int64_t nWinTotal = 0;
-                for (const auto& l : lv)
-                {
-                    nWinTotal += int64_t(std::max(l.nWinR, 0)) * std::max(l.nWinC, 0);
-                }
-                // entries per frame with codes: 1/64 of the windows (the tail sees ~1/700 of them on natural
-                // images), at most 256 MB for the batch (the rows are touched per survivor: ~1k of them per 1080p
-                // frame); whatever is beyond goes to k_cascade_tail3, and so does everything if the buffer cannot be had
-                int64_t cap = std::min<int64_t>(std::max<int64_t>(nWinTotal / 64, 1024), 8192);
-                cap = std::min(cap, std::max<int64_t>((int64_t(1) << 28) / (int64_t(std::max(c->maxBatch, 1)) * cs.codePitch), 256));
-                cap = std::min<int64_t>(cap, std::max<int64_t>(nWinTotal, 1));
-                cs.codeCap = int(cap);
-                void* codes = nullptr;
-                if (hipMalloc(&codes, size_t(std::max(c->maxBatch, 1)) * size_t(cs.codeCap) * size_t(cs.codePitch)) == hipSuccess)
-                {
-                    c->allocs.push_back(codes);
-                    cs.d_tailCodes = static_cast<uint8_t*>(codes);
-                }
-                else
-                {
-                    (void)hipGetLastError();
-                    cs.codeCap = 0;
-                }
+                cs.codes = leafCodeBuffer(c, lv, p.nTrees - g.b[4]);
             }
             if ((rc = devUpload(c, &cs.d_tailNodes, tailNodes)))
             {
                 return rc;
             }
-            cs.useTiles = true;
+            cs.tiles = ts;
             // ---- the same tiles over threshold-rank cells (16 bits per cell): half the fill, half the LDS
             if (wantRank && c->opt.rankCells)
             {
-                std::vector<int32_t> chnOfNode(nNodes, -1);
-                for (size_t q = 0; q < nNodes; q++)
-                {
-                    if (internal[q])
-                    {
-                        chnOfNode[q] = int32_t(c->fids[q] / uint32_t(mWc * mHc));
-                    }
-                }
                 RankTables rt;
-                buildRankTables(c->thrs.data(), chnOfNode.data(), nNodes, nChns, rt);
                 TileSet tsR;
-                if (rt.ok && (rc = buildTileSet(c, lv, nChns, &rt, tsR)))
+                if ((rc = buildRankSet(c, lv, nChns, internal, rt, tsR)))
                 {
                     return rc;
                 }
-                if (rt.ok && tsR.ok)
+                if (tsR.ok)
                 {
                     if ((rc = setupRankPyramid(rt)))
                     {
@@ -701,10 +665,9 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
                         TreeNode b{};
                         for (int k = 0; k < 3; k++)
                         {
-                            const uint32_t f = c->fids[q + k];
-                            const uint32_t z = f / uint32_t(mWc * mHc), cc = (f / uint32_t(mHc)) % uint32_t(mWc), rr = f % uint32_t(mHc);
-                            b.off[k] = (z << 24) | (cc << 12) | rr; // (mW, mH <= 4095 and nChns <= 255: checked for the packed node table above)
-                            const uint32_t rk = rt.rankOfThreshold(int(z), c->thrs[q + k]);
+                            const FeatPos f = splitFid(c->fids[q + k], mW, mH);
+                            b.off[k] = (f.z << 24) | (f.cc << 12) | f.rr; // (mW, mH <= 4095 and nChns <= 255: checked for the packed node table above)
+                            const uint32_t rk = rt.rankOfThreshold(int(f.z), c->thrs[q + k]);
                             memcpy(&b.thr[k], &rk, 4);
                         }
                         for (int k = 0; k < 4; k++)
@@ -717,12 +680,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
                     {
                         return rc;
                     }
-                    cs.geomR = tsR.g;
-                    cs.d_tilesR = tsR.d_tiles;
-                    cs.nTilesR = tsR.nTiles;
-                    cs.d_tileNodesR = tsR.d_tileNodes;
-                    cs.d_tileNodesSR = tsR.d_tileNodesS;
-                    cs.useRank = true;
+                    cs.tilesR = tsR;
                 }
             }
         }

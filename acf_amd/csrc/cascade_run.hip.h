@@ -1,6 +1,7 @@
 // cascade_run.hip.h — part of acf_hip.hip (included there and nowhere else): acf_hip_detect's launch logic.
-//   runCascadeTiled   the LDS-tiled cascade (depth 2: k_cascade_tile3; depths 1, 3, 4: tile3D / tileD) + tail (leaf codes +
-//                     k_tail_scan, or k_cascade_tail3 / _tail_rank for what does not fit the code buffers)
+//   runCascadeTiled   the LDS-tiled cascade of depth 2 (k_cascade_tile3) + tail (leaf codes + k_tail_scan, or
+//                     k_cascade_tail3 / _tail_rank for what does not fit the code buffers)
+//   runTileStageD     depths 1, 3, 4: the staged path's first stages from LDS tiles (k_cascade_tile3D / tileD)
 //   runCascade        acfDetect1 on every level of a batch (tiled or staged), k_expand_hits for stride < shrink, k_sort_map
 //                     (scale-ordered output + box mapping, ACF.cpp:302-329), launchNms (bbNms + prune on the device)
 #pragma once
@@ -14,36 +15,178 @@ static int allowLds(acf_hip_ctx* c, const void* kernel, size_t bytes)
     return ACF_HIP_OK;
 }
 
-// the ONE statement of "the cascade runs on LDS tiles": runCascade's branch and acf_hip_run's early counter clear both ask it
-static inline bool tiledCascadeSelected(const acf_hip_ctx* c)
+extern "C++" // (this file is included inside acf_hip.hip's extern "C" block)
 {
-    return c->cs.useTiles && c->opt.cascadeTiles;
+// allowLds + the launch of a kernel that takes its arguments as one struct
+template <class Args>
+static int launchLds(acf_hip_ctx* c, void (*kernel)(Args), dim3 grid, dim3 block, size_t lds, const Args& a)
+{
+    int rc;
+    if ((rc = allowLds(c, reinterpret_cast<const void*>(kernel), lds)))
+    {
+        return rc;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, a);
+    return ACF_HIP_OK;
+}
+}
+
+// The instantiations of the tile kernels by waves per workgroup (NW), tree depth (D, with TB trees per batch) and cell type.
+// (Each is named in a statement of its own: the order in which they are first named is their order in the code object.)
+using TileKernel = void (*)(TileArgs);
+using TileDKernel = void (*)(TileDArgs);
+
+static TileKernel tile3Kernel(int nw, bool rank)
+{
+#define TILE3_NW(CT)                         \
+    switch (nw)                              \
+    {                                        \
+        case 16: return k_cascade_tile3<16, CT>; \
+        case 8: return k_cascade_tile3<8, CT>;   \
+        case 4: return k_cascade_tile3<4, CT>;   \
+        case 2: return k_cascade_tile3<2, CT>;   \
+        default: return k_cascade_tile3<1, CT>;  \
+    }
+    if (rank)
+    {
+        TILE3_NW(CellRank)
+    }
+    TILE3_NW(CellF32)
+#undef TILE3_NW
+}
+
+static TileKernel tail3Kernel(int waves, bool nodesLds)
+{
+    switch (waves)
+    {
+        case 4:
+            if (nodesLds)
+            {
+                return k_cascade_tail3<4, true>;
+            }
+            return k_cascade_tail3<4, false>;
+        case 2:
+            if (nodesLds)
+            {
+                return k_cascade_tail3<2, true>;
+            }
+            return k_cascade_tail3<2, false>;
+        default:
+            if (nodesLds)
+            {
+                return k_cascade_tail3<1, true>;
+            }
+            return k_cascade_tail3<1, false>;
+    }
+}
+
+static TileDKernel tile3DKernel(int nw, int depth, bool rank)
+{
+#define TILE3D_DEPTH(N)                                                                                      \
+    switch (depth)                                                                                           \
+    {                                                                                                        \
+        case 1: if (rank) return k_cascade_tile3D<N, 1, 4, CellRank>; return k_cascade_tile3D<N, 1, 4, CellF32>; \
+        case 3: if (rank) return k_cascade_tile3D<N, 3, 2, CellRank>; return k_cascade_tile3D<N, 3, 2, CellF32>; \
+        default: if (rank) return k_cascade_tile3D<N, 4, 1, CellRank>; return k_cascade_tile3D<N, 4, 1, CellF32>; \
+    }
+    if (nw == 8)
+    {
+        TILE3D_DEPTH(8)
+    }
+    TILE3D_DEPTH(4)
+#undef TILE3D_DEPTH
+}
+
+static TileDKernel tileDKernel(int nw, int depth)
+{
+#define TILED_DEPTH(N)                                  \
+    switch (depth)                                      \
+    {                                                   \
+        case 1: return k_cascade_tileD<N, 1, 4>;        \
+        case 3: return k_cascade_tileD<N, 3, 2>;        \
+        default: return k_cascade_tileD<N, 4, 1>;       \
+    }
+    if (nw == 8)
+    {
+        TILED_DEPTH(8)
+    }
+    TILED_DEPTH(4)
+#undef TILED_DEPTH
+}
+
+// depth 2 with a float tile set and option cascade_tiles: runCascadeTiled takes the whole cascade (runCascade's branch and
+// acf_hip_run's early counter clear both ask this)
+static inline bool wholeCascadeTiled(const acf_hip_ctx* c)
+{
+    return c->cs.tiles.ok && c->p.treeDepth == 2 && c->opt.cascadeTiles;
+}
+
+// the float pyramid -> threshold-rank cells (levels whose kernels did not emit them): the one k_rank launch
+static int launchRankCells(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int nF, int nChns)
+{
+    const CascState& cs = c->cs;
+    const size_t ldsR = size_t(cs.rankMaxRec) * sizeof(RankRec);
+    int rc;
+    if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_rank), ldsR)))
+    {
+        return rc;
+    }
+    prof(c, "k_rank");
+    hipLaunchKernelGGL(k_rank, dim3(cdiv(cs.rankMaxWP, RANK_CHUNK_COLS), int(c->plan.levels.size()) * nChns, nF), dim3(256), ldsR, c->stream, pyr, pyr_fs,
+        cs.d_pyrR, cs.pyrRCells, (const RankJob*)cs.d_rankJobs, nChns, (const RankChan*)cs.d_rankChan, (const RankRec*)cs.d_rankRec);
+    LAUNCHCHK(c, "k_rank");
+    c->ranksValid = true;
+    return ACF_HIP_OK;
+}
+
+// The pooled tile kernels' grid for `total` tiles (of all frames) at `lds` bytes per workgroup: one workgroup per tile, or
+// persistent workgroups that draw their tiles from one counter per XCD (option tile_persist: 0 one workgroup per tile, 1 as many
+// workgroups as the device's CUs hold at once, n > 1 that many; rounded up to a multiple of 8 = the tile counters)
+struct TileGrid
+{
+    unsigned int blocks;
+    bool persist;
+};
+
+static TileGrid tileGrid(const acf_hip_ctx* c, size_t lds, int64_t total)
+{
+    const int64_t perX = (total + 7) / 8;
+    const int64_t resident = int64_t(c->numCus) * std::max<int64_t>(1, int64_t(c->ldsPerCu) / int64_t((lds + 1279) / 1280 * 1280));
+    const int64_t gridP = c->opt.tilePersist > 1 ? int64_t(c->opt.tilePersist) : resident;
+    const bool persist = c->opt.tilePersist > 0 && (gridP + 7) / 8 * 8 < perX * 8;
+    return { (unsigned int)(persist ? (gridP + 7) / 8 * 8 : perX * 8), persist };
+}
+
+// a TileArgs' view of one tile set: geometry, tile list and node records
+static void setTiles(TileArgs& a, const TileSet& ts)
+{
+    a.g = ts.g;
+    a.tiles = ts.d_tiles;
+    a.nTiles = ts.nTiles;
+    a.tileNodes = ts.d_tileNodes;
+    a.tileNodesS = ts.d_tileNodesS;
+    a.aTB = ts.aTB;
 }
 
 static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int nF, int nChns)
 {
     const acf_hip_params& p = c->p;
     const CascState& cs = c->cs;
-    const TileGeom& g = cs.geom;
+    const TileGeom& g = cs.tiles.g;
     if (!c->countersZeroed)
     {
         HIPCHK(c, hipMemsetAsync(cs.d_qcounts, 0, sizeof(int32_t) * (2 * size_t(c->maxBatch) + 8), c->stream));
     }
     TileArgs a{};
+    setTiles(a, cs.tiles);
     a.pyr = pyr;
     a.pyr_fs = pyr_fs;
     a.levels = cs.d_cascLevels;
-    a.tiles = cs.d_tiles;
-    a.nTiles = cs.nTiles;
     a.nFrames = nF;
     a.nChns = nChns;
     a.mH = p.modelDsPad_h / p.shrink;
     a.mW = p.modelDsPad_w / p.shrink;
     a.nTrees = p.nTrees;
-    a.g = g;
-    a.tileNodes = cs.d_tileNodes;
-    a.tileNodesS = cs.d_tileNodesS;
-    a.aTB = cs.aTB;
     a.tailNodes = cs.d_tailNodes;
     a.cascThr = float(p.cascThr); // DetectionParams::cascThr is a float (acfDetect1.cpp:63,323)
     a.q = cs.d_queue[0];
@@ -58,9 +201,9 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
     a.tailPad = cs.tailPad;
     a.tailSlab = cs.tailSlab;
     a.tailNodesLds = cs.tailNodesLds;
-    a.tailCodes = cs.d_tailCodes;
-    a.codeCap = cs.codeCap;
-    a.codePitch = cs.codePitch;
+    a.tailCodes = cs.codes.d;
+    a.codeCap = cs.codes.cap;
+    a.codePitch = cs.codes.pitch;
     a.debug = 0;
 #ifdef ACF_HIP_STAMPS
     static const int cascDebug = getenv("ACF_HIP_CASC_DEBUG") ? atoi(getenv("ACF_HIP_CASC_DEBUG")) : 0; // timing experiments (profiles/ab_*.sh)
@@ -69,91 +212,42 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
     if (a.debug & 12)
     {
         a.debug |= 4;
-        const int64_t total = int64_t(std::max(cs.nTiles, cs.nTilesR)) * nF;
+        const int64_t total = int64_t(std::max(cs.tiles.nTiles, cs.tilesR.nTiles)) * nF;
         HIPCHK(c, hipMalloc(&a.stamps, size_t((total + 7) / 8 * 8) * 8 * sizeof(long long)));
         HIPCHK(c, hipMemsetAsync(a.stamps, 0, size_t((total + 7) / 8 * 8) * 8 * sizeof(long long), c->stream));
     }
-    const bool rank = cs.useRank && c->opt.rankCells && pyr == c->d_pyr;
-    if (rank && !c->ranksValid)
+    const bool rank = rankCellsOn(c) && pyr == c->d_pyr;
+    int rc = 0;
+    if (rank && !c->ranksValid && (rc = launchRankCells(c, pyr, pyr_fs, nF, nChns)))
     {
-        // the float pyramid -> threshold-rank cells (levels whose kernels did not emit them)
-        int rc = 0;
-        const size_t ldsR = size_t(cs.rankMaxRec) * sizeof(RankRec);
-        if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_rank), ldsR)))
-        {
-            return rc;
-        }
-        prof(c, "k_rank");
-        hipLaunchKernelGGL(k_rank, dim3(cdiv(cs.rankMaxWP, RANK_CHUNK_COLS), int(c->plan.levels.size()) * nChns, nF), dim3(256), ldsR, c->stream, pyr, pyr_fs,
-            cs.d_pyrR, cs.pyrRCells, (const RankJob*)cs.d_rankJobs, nChns, (const RankChan*)cs.d_rankChan, (const RankRec*)cs.d_rankRec);
-        LAUNCHCHK(c, "k_rank");
-        c->ranksValid = true;
+        return rc;
     }
-    if (cs.nTiles > 0)
+    if (cs.tiles.nTiles > 0)
     {
         TileArgs at = a; // the tile kernel's view: the rank form has its own tile geometry, tile list and node records
         if (rank)
         {
+            setTiles(at, cs.tilesR);
             at.pyrR = cs.d_pyrR;
             at.pyrR_fs = cs.pyrRCells;
-            at.g = cs.geomR;
-            at.tiles = cs.d_tilesR;
-            at.nTiles = cs.nTilesR;
-            at.tileNodes = cs.d_tileNodesR;
-            at.tileNodesS = cs.d_tileNodesSR;
         }
         const TileGeom& gt = at.g;
-        const int64_t total = int64_t(at.nTiles) * nF;
-        const int64_t perX = (total + 7) / 8;
-        const size_t nwin = size_t(gt.NW) * 64;
-        const size_t lds = gt.pooled ? size_t(TILE3_LEAF_BYTES) + size_t(gt.tileFloats) * (rank ? 2 : 4) + ((std::max(nwin * 8, size_t(gt.passW) * size_t(gt.pitchC)) + 15) / 16 * 16) + nwin * 8
-                                     : size_t(gt.tileFloats) * (rank ? 2 : 4) + nwin * 8;
-        // k_cascade_tile3: persistent workgroups (as many as the CUs hold at once) that draw their tiles from one counter per XCD
-        // (tilePersist: 0 one workgroup per tile, 1 as many workgroups as the device's CUs hold at once, n > 1 that many, rounded up
-        // to a multiple of 8 = the tile counters)
-        const int64_t resident = int64_t(c->numCus) * std::max<int64_t>(1, int64_t(c->ldsPerCu) / int64_t((lds + 1279) / 1280 * 1280));
-        const int64_t gridP = c->opt.tilePersist > 1 ? int64_t(c->opt.tilePersist) : resident;
-        const bool persist = gt.pooled && c->opt.tilePersist > 0 && (gridP + 7) / 8 * 8 < perX * 8;
-        if (!persist)
+        const size_t lds = pooledTileLds(gt, rank ? 2 : 4, TILE3_LEAF_BYTES);
+        const TileGrid tg = tileGrid(c, lds, int64_t(at.nTiles) * nF);
+        if (!tg.persist)
         {
             at.tileNext = nullptr;
         }
-        dim3 grid((unsigned int)(persist ? (gridP + 7) / 8 * 8 : perX * 8)), block(gt.NW * 64);
-        int rc = 0;
+        dim3 grid(tg.blocks), block(gt.NW * 64);
         if ((c->opt.cascadeTurns & 1) && (rc = turnBegin(c, 0, 0))) // (before the profile event: the wait for the turn is not the kernel's time)
         {
             return rc;
         }
         prof(c, "k_cascade_tile");
-#define TILE2_LAUNCH(N, CT)                                                                           \
-    {                                                                                                 \
-        if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_cascade_tile3<N, CT>), lds)))          \
-            return rc;                                                                                \
-        hipLaunchKernelGGL((k_cascade_tile3<N, CT>), grid, block, lds, c->stream, at);                \
-    }
-#define TILE3_LAUNCH16(CT)                                                                        \
-    if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_cascade_tile3<16, CT>), lds)))             \
-        return rc;                                                                                    \
-    hipLaunchKernelGGL((k_cascade_tile3<16, CT>), grid, block, lds, c->stream, at);
-#define TILE2_NW(CT)                              \
-    switch (gt.NW)                                \
-    {                                             \
-        case 16: TILE3_LAUNCH16(CT); break;       \
-        case 8: TILE2_LAUNCH(8, CT); break;       \
-        case 4: TILE2_LAUNCH(4, CT); break;       \
-        case 2: TILE2_LAUNCH(2, CT); break;       \
-        default: TILE2_LAUNCH(1, CT); break;      \
-    }
-        if (rank)
+        if ((rc = launchLds(c, tile3Kernel(gt.NW, rank), grid, block, lds, at)))
         {
-            TILE2_NW(CellRank);
+            return rc;
         }
-        else
-        {
-            TILE2_NW(CellF32);
-        }
-#undef TILE2_NW
-#undef TILE2_LAUNCH
         LAUNCHCHK(c, "k_cascade_tile");
         if ((c->opt.cascadeTurns & 1) && (rc = turnEnd(c, 0, 0)))
         {
@@ -166,58 +260,33 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
             HIPCHK(c, hipStreamSynchronize(c->stream));
             std::vector<long long> st(size_t(grid.x) * 8);
             HIPCHK(c, hipMemcpy(st.data(), a.stamps, st.size() * 8, hipMemcpyDeviceToHost));
-            if (gt.pooled)
+            double acc[6] = { 0, 0, 0, 0, 0, 0 }, n1 = 0, n2 = 0, nE = 0, accE = 0;
+            long long nb = 0, nbE = 0;
+            for (size_t b = 0; b < size_t(grid.x); b++)
             {
-                double acc[6] = { 0, 0, 0, 0, 0, 0 }, n1 = 0, n2 = 0, nE = 0, accE = 0;
-                long long nb = 0, nbE = 0;
-                for (size_t b = 0; b < size_t(grid.x); b++)
+                if (st[b * 8 + 5] > st[b * 8])
                 {
-                    if (st[b * 8 + 5] > st[b * 8])
+                    for (int k = 0; k < 5; k++)
                     {
-                        for (int k = 0; k < 5; k++)
-                        {
-                            acc[k] += double(st[b * 8 + k + 1] - st[b * 8 + k]);
-                        }
-                        n1 += double(st[b * 8 + 7] & 0xffff);
-                        n2 += double((st[b * 8 + 7] >> 16) & 0xffff);
-                        nE += double(st[b * 8 + 7] >> 32);
-                        nb++;
-                        if ((st[b * 8 + 7] >> 32) > 0 && st[b * 8 + 6] > st[b * 8 + 5]) // (tiles with windows in the tail queue: stage E ran)
-                        {
-                            accE += double(st[b * 8 + 6] - st[b * 8 + 5]);
-                            nbE++;
-                        }
+                        acc[k] += double(st[b * 8 + k + 1] - st[b * 8 + k]);
+                    }
+                    n1 += double(st[b * 8 + 7] & 0xffff);
+                    n2 += double((st[b * 8 + 7] >> 16) & 0xffff);
+                    nE += double(st[b * 8 + 7] >> 32);
+                    nb++;
+                    if ((st[b * 8 + 7] >> 32) > 0 && st[b * 8 + 6] > st[b * 8 + 5]) // (tiles with windows in the tail queue: stage E ran)
+                    {
+                        accE += double(st[b * 8 + 6] - st[b * 8 + 5]);
+                        nbE++;
                     }
                 }
-                fprintf(stderr, "[casc stamps, pooled] blocks %lld  fill %.0f  A1 (thread 0) %.0f  barrier %.0f  A2 + barrier %.0f  S %.0f cycles;  survivors per tile: A1 %.1f  A2 %.1f  S %.2f;  E %.0f cycles in %.1f %% of the tiles\n",
-                    nb, acc[0] / nb, acc[1] / nb, acc[2] / nb, acc[3] / nb, acc[4] / nb, n1 / nb, n2 / nb, nE / nb, nbE ? accE / nbE : 0.0, 100.0 * nbE / std::max<long long>(nb, 1));
             }
-            else
-            {
-                double acc[4] = { 0, 0, 0, 0 }, sub[3] = { 0, 0, 0 };
-                long long nb = 0;
-                for (size_t b = 0; b < size_t(grid.x); b++)
-                {
-                    if (st[b * 8 + 4] > st[b * 8])
-                    {
-                        for (int k = 0; k < 4; k++)
-                        {
-                            acc[k] += double(st[b * 8 + k + 1] - st[b * 8 + k]);
-                        }
-                        for (int k = 0; k < 3; k++)
-                        {
-                            sub[k] += double(st[b * 8 + 5 + k]);
-                        }
-                        nb++;
-                    }
-                }
-                fprintf(stderr, "[casc stamps] blocks %lld (those with tail windows)  fill %.0f  wave 0: A + sparse pieces %.0f  barrier %.0f  E %.0f cycles   (since the fill barrier: A starts %.0f, A evaluated %.0f, compacted %.0f)\n", nb,
-                    acc[0] / nb, acc[1] / nb, acc[2] / nb, acc[3] / nb, sub[0] / nb, sub[1] / nb, sub[2] / nb);
-            }
+            fprintf(stderr, "[casc stamps, pooled] blocks %lld  fill %.0f  A1 (thread 0) %.0f  barrier %.0f  A2 + barrier %.0f  S %.0f cycles;  survivors per tile: A1 %.1f  A2 %.1f  S %.2f;  E %.0f cycles in %.1f %% of the tiles\n",
+                nb, acc[0] / nb, acc[1] / nb, acc[2] / nb, acc[3] / nb, acc[4] / nb, n1 / nb, n2 / nb, nE / nb, nbE ? accE / nbE : 0.0, 100.0 * nbE / std::max<long long>(nb, 1));
             (void)hipFree(a.stamps);
         }
 #endif
-        if (g.b[4] < p.nTrees && cs.codeCap > 0)
+        if (g.b[4] < p.nTrees && cs.codes.cap > 0)
         {
             // the first codeCap queue entries of every frame carry leaf codes (stage E of the tile kernel): the ordered scan
             const size_t ldsS = size_t(p.nTrees - g.b[4]) * 16;
@@ -226,7 +295,7 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
                 return rc;
             }
             prof(c, "k_tail_scan");
-            hipLaunchKernelGGL(k_tail_scan, dim3(nF * ((cs.codeCap + 255) / 256)), dim3(256), ldsS, c->stream, a);
+            hipLaunchKernelGGL(k_tail_scan, dim3(nF * ((cs.codes.cap + 255) / 256)), dim3(256), ldsS, c->stream, a);
             LAUNCHCHK(c, "k_tail_scan");
         }
         if (g.b[4] < p.nTrees && rank)
@@ -244,32 +313,10 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
             dim3 tgrid(std::min(cs.tailBlocks, std::max(1, 512 / nF) * nF)), tblock(cs.tailWaves * 64);
             const size_t tl = (size_t(cs.tailWaves) * a.tailSlab + size_t(a.tailNodesLds)) * 4;
             prof(c, "k_cascade_tail3");
-#define TAIL_LAUNCH(N)                                                                                              \
-    if (a.tailNodesLds)                                                                                             \
-    {                                                                                                               \
-        if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_cascade_tail3<N, true>), tl)))                       \
-            return rc;                                                                                              \
-        hipLaunchKernelGGL((k_cascade_tail3<N, true>), tgrid, tblock, tl, c->stream, a);                            \
-    }                                                                                                               \
-    else                                                                                                            \
-    {                                                                                                               \
-        if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_cascade_tail3<N, false>), tl)))                      \
-            return rc;                                                                                              \
-        hipLaunchKernelGGL((k_cascade_tail3<N, false>), tgrid, tblock, tl, c->stream, a);                           \
-    }
-            switch (cs.tailWaves)
+            if ((rc = launchLds(c, tail3Kernel(cs.tailWaves, a.tailNodesLds != 0), tgrid, tblock, tl, a)))
             {
-                case 4:
-                    TAIL_LAUNCH(4);
-                    break;
-                case 2:
-                    TAIL_LAUNCH(2);
-                    break;
-                default:
-                    TAIL_LAUNCH(1);
-                    break;
+                return rc;
             }
-#undef TAIL_LAUNCH
             LAUNCHCHK(c, "k_cascade_tail3");
         }
     }
@@ -325,16 +372,111 @@ static inline bool nmsActive(const acf_hip_ctx* c)
     return c->nmsOn && c->nms.type != 0 && c->d_nmsDets;
 }
 
+// Depths 1, 3, 4: trees [0, end) of every window from LDS tiles (k_cascade_tile3D on a pooled set: everything up to tree g.b[4],
+// the tail's leaf codes from its stage E; k_cascade_tileD: trees [0, t1D)) instead of the staged path's first per-lane gathers
+// from the pyramid.  Its survivors enter the queue of the stage that ends at `end`.  firstStage: the first stage the staged path
+// still runs (0 when no stage ends there: the tile kernel does not run); pooledTail: the tile kernel has written the tail's leaf codes.
+static int runTileStageD(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int nF, int nChns, const std::vector<int>& bounds, int& firstStage, bool& pooledTail)
+{
+    const acf_hip_params& p = c->p;
+    const CascState& cs = c->cs;
+    const bool rank = rankCellsOn(c) && pyr == c->d_pyr;
+    const TileSet& ts = rank ? cs.tilesR : cs.tiles; // (the rank set is always pooled)
+    const int end = ts.g.pooled ? ts.g.b[4] : ts.t1D; // last tree the tile kernel evaluates
+    const int nStages = int(bounds.size());
+    int sD = -1;
+    for (int i = 0; i < nStages; i++)
+    {
+        if (bounds[size_t(i)] == end)
+        {
+            sD = i;
+        }
+    }
+    if (sD < 0)
+    {
+        return ACF_HIP_OK;
+    }
+    TileDArgs at{};
+    at.pyr = pyr;
+    at.pyr_fs = pyr_fs;
+    at.levels = cs.d_cascLevels;
+    at.tiles = ts.d_tiles;
+    at.nTiles = ts.nTiles;
+    at.nFrames = nF;
+    at.nChns = nChns;
+    at.nBatches = ts.t1D / ts.tbD;
+    at.g = ts.g;
+    at.nodesD = ts.d_nodesD;
+    at.cascThr = float(p.cascThr);
+    at.last = sD == nStages - 1;
+    at.qout = cs.d_queue[sD & 1];
+    at.qoutCount = cs.d_qcounts + size_t(sD) * c->maxBatch;
+    at.qcap = cs.qcap;
+    at.hits = cs.d_hits;
+    at.counts = cs.d_counts;
+    at.maxHits = c->maxHits;
+    const int64_t total = int64_t(ts.nTiles) * nF;
+    int rc = 0;
+    if (rank && !c->ranksValid)
+    {
+        if ((rc = launchRankCells(c, pyr, pyr_fs, nF, nChns)))
+        {
+            return rc;
+        }
+        prof(c, "k_cascade");
+    }
+    // k_cascade_tile3D on a pooled set (persistent workgroups where option tile_persist says so), else k_cascade_tileD
+    size_t lds = size_t(ts.g.tileFloats) * 4;
+    TileGrid tg = { (unsigned int)((total + 7) / 8 * 8), false };
+    TileDKernel kernel = tileDKernel(ts.g.NW, p.treeDepth);
+    if (ts.g.pooled)
+    {
+        // the model's nodes [tree][nTreeNodes] and leaves; the tail's leaf codes from stage E
+        at.tileOff = ts.d_tileOffD;
+        at.thrs = rank ? reinterpret_cast<const float*>(ts.d_thrsRankD) : cs.d_thrs;
+        at.hs = cs.d_hs;
+        at.nTrees = p.nTrees;
+        at.nTreeNodes = p.nTreeNodes;
+        if (rank)
+        {
+            at.pyrR = cs.d_pyrR;
+            at.pyrR_fs = cs.pyrRCells;
+        }
+        pooledTail = !at.last && cs.codes.cap > 0;
+        at.codes = pooledTail ? cs.codes.d : nullptr;
+        at.codeCap = pooledTail ? cs.codes.cap : 0;
+        at.codePitch = cs.codes.pitch;
+        lds = pooledTileLds(ts.g, rank ? 2 : 4, size_t(128) * 4 << p.treeDepth);
+        tg = tileGrid(c, lds, total);
+        // (the staged path's counters [stage][frame] start at d_qcounts; the tile counters sit behind them)
+        at.tileNext = tg.persist ? cs.d_qcounts + size_t(8) * c->maxBatch : nullptr;
+        if (tg.persist)
+        {
+            HIPCHK(c, hipMemsetAsync(at.tileNext, 0, sizeof(int32_t) * 8, c->stream));
+        }
+        kernel = tile3DKernel(ts.g.NW, p.treeDepth, rank);
+        prof(c, "k_cascade_tile");
+    }
+    if ((rc = launchLds(c, kernel, dim3(tg.blocks), dim3(ts.g.NW * 64), lds, at)))
+    {
+        return rc;
+    }
+    LAUNCHCHK(c, (ts.g.pooled ? "k_cascade_tile3D" : "k_cascade_tileD"));
+    if (ts.g.pooled)
+    {
+        prof(c, "k_cascade");
+    }
+    firstStage = sD + 1;
+    return ACF_HIP_OK;
+}
+
 static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const BoxLevel* d_box, int nF, int nChns)
 {
     const acf_hip_params& p = c->p;
-    const CascLevel* d_levels = c->cs.d_cascLevels;
-    const int32_t* d_blockLevel = c->cs.d_blockLevel;
-    const int blocksPerFrame = c->cs.blocksPerFrame;
-    const uint32_t* d_cidAll = c->cs.d_cidAll;
-    const CascNode2* d_nodes2 = c->cs.d_nodes2;
+    const CascState& cs = c->cs;
+    const int blocksPerFrame = cs.blocksPerFrame;
     prof(c, "k_cascade");
-    const bool rankPath = c->cs.useTiles && c->opt.cascadeTiles && c->cs.useRank && c->opt.rankCells;
+    const bool rankPath = wholeCascadeTiled(c) && rankCellsOn(c);
     if (pyr == c->d_pyr && !c->floatPyramid && !(rankPath && c->ranksValid))
     {
         // (options changed between acf_hip_pyramid and acf_hip_detect: the float cells this path reads were never written)
@@ -342,12 +484,12 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
     }
     if (!c->countersZeroed)
     {
-        HIPCHK(c, hipMemsetAsync(c->cs.d_counts, 0, sizeof(int32_t) * nF, c->stream));
+        HIPCHK(c, hipMemsetAsync(cs.d_counts, 0, sizeof(int32_t) * nF, c->stream));
     }
-    if (tiledCascadeSelected(c))
+    int rc = 0;
+    if (wholeCascadeTiled(c))
     {
-        int rc = runCascadeTiled(c, pyr, pyr_fs, nF, nChns);
-        if (rc)
+        if ((rc = runCascadeTiled(c, pyr, pyr_fs, nF, nChns)))
         {
             return rc;
         }
@@ -365,204 +507,51 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
         }
         bounds.push_back(p.nTrees);
         const int nStages = int(bounds.size());
-        HIPCHK(c, hipMemsetAsync(c->cs.d_qcounts, 0, sizeof(int32_t) * size_t(nStages) * c->maxBatch, c->stream));
+        HIPCHK(c, hipMemsetAsync(cs.d_qcounts, 0, sizeof(int32_t) * size_t(nStages) * c->maxBatch, c->stream));
         CascArgs a{};
         a.pyr = pyr;
         a.pyr_fs = pyr_fs;
-        a.levels = d_levels;
-        a.blockLevel = d_blockLevel;
+        a.levels = cs.d_cascLevels;
+        a.blockLevel = cs.d_blockLevel;
         a.blocksPerFrame = blocksPerFrame;
         a.nFrames = nF;
         a.mH = p.modelDsPad_h / p.shrink;
         a.mW = p.modelDsPad_w / p.shrink;
         a.nChns = nChns;
-        a.fids = c->cs.d_fids;
+        a.fids = cs.d_fids;
         a.nTrees = p.nTrees;
         a.nTreeNodes = p.nTreeNodes;
         a.treeDepth = p.treeDepth;
-        a.stride = c->cs.dedupQ > 1 ? p.shrink : p.stride; // (the grid of distinct offsets: its windows are one cell apart)
+        a.stride = cs.dedupQ > 1 ? p.shrink : p.stride; // (the grid of distinct offsets: its windows are one cell apart)
         a.shrink = p.shrink;
         a.cascThr = float(p.cascThr); // DetectionParams::cascThr is a float (acfDetect1.cpp:63,323)
-        a.cidAll = d_cidAll;
-        a.thrs = c->cs.d_thrs;
-        a.hs = c->cs.d_hs;
-        a.child = c->cs.d_child;
-        a.nodes2 = d_nodes2;
-        a.qcap = c->cs.qcap;
-        a.hits = c->cs.d_hits;
-        a.counts = c->cs.d_counts;
+        a.cidAll = cs.d_cidAll;
+        a.thrs = cs.d_thrs;
+        a.hs = cs.d_hs;
+        a.child = cs.d_child;
+        a.nodes2 = cs.d_nodes2;
+        a.qcap = cs.qcap;
+        a.hits = cs.d_hits;
+        a.counts = cs.d_counts;
         a.maxHits = c->maxHits;
         const int mode = p.treeDepth == 2 ? 2 : (p.treeDepth > 0 ? 1 : 0);
         // later stages see a shrinking survivor set; grid-stride loops cover any count
         const int qGrid[3] = { std::max(1, blocksPerFrame / 2), std::max(1, blocksPerFrame / 8), std::max(1, std::min(blocksPerFrame, 64)) };
         int firstStage = 0;
         bool pooledTail = false; // k_cascade_tile3D has written the tail's leaf codes: no k_tail_codesD
-        if (c->cs.useTileD && c->opt.cascadeTiles)
+        if (cs.tiles.ok && p.treeDepth != 2 && c->opt.cascadeTiles && (rc = runTileStageD(c, pyr, pyr_fs, nF, nChns, bounds, firstStage, pooledTail)))
         {
-            // depths 1, 3, 4: trees [0, t1D) of every window from LDS tiles (k_cascade_tileD) instead of the first stages'
-            // per-lane gathers from the pyramid; its survivors enter the queue of the stage that ends at t1D
-            const auto& cs = c->cs;
-            int sD = -1;
-            const bool rankD = cs.useRankD && c->opt.rankCells && pyr == c->d_pyr;
-            const bool pooledRun = rankD || cs.geomD.pooled;
-            const int endD = rankD ? cs.geomDR.b[4] : (cs.geomD.pooled ? cs.geomD.b[4] : cs.t1D); // last tree the tile kernel evaluates
-            for (int i = 0; i < nStages; i++)
-            {
-                if (bounds[size_t(i)] == endD)
-                {
-                    sD = i;
-                }
-            }
-            if (sD >= 0)
-            {
-                TileDArgs at{};
-                at.pyr = pyr;
-                at.pyr_fs = pyr_fs;
-                at.levels = d_levels;
-                at.tiles = cs.d_tilesD;
-                at.nTiles = cs.nTilesD;
-                at.nFrames = nF;
-                at.nChns = nChns;
-                at.nBatches = cs.t1D / cs.tbD;
-                at.g = cs.geomD;
-                at.nodesD = cs.d_nodesD;
-                at.cascThr = float(p.cascThr);
-                at.last = sD == nStages - 1;
-                at.qout = cs.d_queue[sD & 1];
-                at.qoutCount = cs.d_qcounts + size_t(sD) * c->maxBatch;
-                at.qcap = cs.qcap;
-                at.hits = cs.d_hits;
-                at.counts = cs.d_counts;
-                at.maxHits = c->maxHits;
-                int rcl = 0;
-                const int64_t total = int64_t(rankD ? cs.nTilesDR : at.nTiles) * nF;
-                const int64_t perX = (total + 7) / 8;
-                if (rankD && !c->ranksValid)
-                {
-                    // the float pyramid -> threshold-rank cells (levels whose kernels did not emit them)
-                    const size_t ldsR = size_t(cs.rankMaxRec) * sizeof(RankRec);
-                    if ((rcl = allowLds(c, reinterpret_cast<const void*>(&k_rank), ldsR)))
-                    {
-                        return rcl;
-                    }
-                    prof(c, "k_rank");
-                    hipLaunchKernelGGL(k_rank, dim3(cdiv(cs.rankMaxWP, RANK_CHUNK_COLS), int(c->plan.levels.size()) * nChns, nF), dim3(256), ldsR, c->stream, pyr, pyr_fs,
-                        cs.d_pyrR, cs.pyrRCells, (const RankJob*)cs.d_rankJobs, nChns, (const RankChan*)cs.d_rankChan, (const RankRec*)cs.d_rankRec);
-                    LAUNCHCHK(c, "k_rank");
-                    c->ranksValid = true;
-                    prof(c, "k_cascade");
-                }
-                if (pooledRun)
-                {
-                    // k_cascade_tile3D: everything up to tree b[4]; the tail's codes come from its stage E
-                    at.tileOff = cs.d_tileOffD;
-                    at.thrs = c->cs.d_thrs;
-                    if (rankD)
-                    {
-                        at.g = cs.geomDR;
-                        at.tiles = cs.d_tilesDR;
-                        at.nTiles = cs.nTilesDR;
-                        at.nodesD = cs.d_nodesDR;
-                        at.tileOff = cs.d_tileOffDR;
-                        at.thrs = reinterpret_cast<const float*>(cs.d_thrsRankD);
-                        at.pyrR = cs.d_pyrR;
-                        at.pyrR_fs = cs.pyrRCells;
-                    }
-                    at.hs = c->cs.d_hs;
-                    at.nTrees = p.nTrees;
-                    at.nTreeNodes = p.nTreeNodes;
-                    pooledTail = !at.last && cs.codeCapD > 0;
-                    at.codes = pooledTail ? cs.d_codesD : nullptr;
-                    at.codeCap = pooledTail ? cs.codeCapD : 0;
-                    at.codePitch = cs.codePitchD;
-                    const size_t nwin = size_t(at.g.NW) * 64;
-                    const size_t lds = size_t(128) * 4 * (size_t(1) << p.treeDepth) + size_t(at.g.tileFloats) * (rankD ? 2 : 4) +
-                        ((std::max(nwin * 8, size_t(at.g.passW) * size_t(at.g.pitchC)) + 15) / 16 * 16) + nwin * 8;
-                    const int64_t resident = int64_t(c->numCus) * std::max<int64_t>(1, int64_t(c->ldsPerCu) / int64_t((lds + 1279) / 1280 * 1280));
-                    const int64_t gridP = c->opt.tilePersist > 1 ? int64_t(c->opt.tilePersist) : resident;
-                    const bool persist = c->opt.tilePersist > 0 && (gridP + 7) / 8 * 8 < perX * 8;
-                    // (the staged path's counters [stage][frame] start at d_qcounts; the tile counters sit behind them)
-                    at.tileNext = persist ? cs.d_qcounts + size_t(8) * c->maxBatch : nullptr;
-                    if (persist)
-                    {
-                        HIPCHK(c, hipMemsetAsync(at.tileNext, 0, sizeof(int32_t) * 8, c->stream));
-                    }
-                    dim3 grid((unsigned int)(persist ? (gridP + 7) / 8 * 8 : perX * 8)), block(at.g.NW * 64);
-                    prof(c, "k_cascade_tile");
-#define TILE3D_LAUNCH(N, DD, TT)                                                                                   \
-    if (rankD)                                                                                                     \
-    {                                                                                                              \
-        if ((rcl = allowLds(c, reinterpret_cast<const void*>(&k_cascade_tile3D<N, DD, TT, CellRank>), lds)))       \
-            return rcl;                                                                                            \
-        hipLaunchKernelGGL((k_cascade_tile3D<N, DD, TT, CellRank>), grid, block, lds, c->stream, at);              \
-    }                                                                                                              \
-    else                                                                                                           \
-    {                                                                                                              \
-        if ((rcl = allowLds(c, reinterpret_cast<const void*>(&k_cascade_tile3D<N, DD, TT, CellF32>), lds)))        \
-            return rcl;                                                                                            \
-        hipLaunchKernelGGL((k_cascade_tile3D<N, DD, TT, CellF32>), grid, block, lds, c->stream, at);               \
-    }
-#define TILE3D_DEPTH(N)                                    \
-    switch (p.treeDepth)                                   \
-    {                                                      \
-        case 1: TILE3D_LAUNCH(N, 1, 4); break;             \
-        case 3: TILE3D_LAUNCH(N, 3, 2); break;             \
-        default: TILE3D_LAUNCH(N, 4, 1); break;            \
-    }
-                    if (at.g.NW == 8)
-                    {
-                        TILE3D_DEPTH(8)
-                    }
-                    else
-                    {
-                        TILE3D_DEPTH(4)
-                    }
-#undef TILE3D_DEPTH
-#undef TILE3D_LAUNCH
-                    LAUNCHCHK(c, "k_cascade_tile3D");
-                    prof(c, "k_cascade");
-                }
-                else
-                {
-                const size_t lds = size_t(at.g.tileFloats) * 4;
-                dim3 grid((unsigned int)(perX * 8)), block(at.g.NW * 64);
-#define TILED_LAUNCH(N, DD, TT)                                                                          \
-    {                                                                                                    \
-        if ((rcl = allowLds(c, reinterpret_cast<const void*>(&k_cascade_tileD<N, DD, TT>), lds)))        \
-            return rcl;                                                                                  \
-        hipLaunchKernelGGL((k_cascade_tileD<N, DD, TT>), grid, block, lds, c->stream, at);               \
-    }
-#define TILED_DEPTH(N)                                    \
-    switch (p.treeDepth)                                  \
-    {                                                     \
-        case 1: TILED_LAUNCH(N, 1, 4); break;             \
-        case 3: TILED_LAUNCH(N, 3, 2); break;             \
-        default: TILED_LAUNCH(N, 4, 1); break;            \
-    }
-                if (at.g.NW == 8)
-                {
-                    TILED_DEPTH(8)
-                }
-                else
-                {
-                    TILED_DEPTH(4)
-                }
-#undef TILED_DEPTH
-#undef TILED_LAUNCH
-                LAUNCHCHK(c, "k_cascade_tileD");
-                }
-                firstStage = sD + 1;
-            }
+            return rc;
         }
         for (int sidx = firstStage; sidx < nStages; sidx++)
         {
             a.t0 = sidx == 0 ? 0 : bounds[sidx - 1];
             a.t1 = bounds[sidx];
             a.last = sidx == nStages - 1;
-            a.qin = sidx > 0 ? c->cs.d_queue[(sidx - 1) & 1] : nullptr;
-            a.qinCount = sidx > 0 ? c->cs.d_qcounts + size_t(sidx - 1) * c->maxBatch : nullptr;
-            a.qout = c->cs.d_queue[sidx & 1];
-            a.qoutCount = c->cs.d_qcounts + size_t(sidx) * c->maxBatch;
+            a.qin = sidx > 0 ? cs.d_queue[(sidx - 1) & 1] : nullptr;
+            a.qinCount = sidx > 0 ? cs.d_qcounts + size_t(sidx - 1) * c->maxBatch : nullptr;
+            a.qout = cs.d_queue[sidx & 1];
+            a.qoutCount = cs.d_qcounts + size_t(sidx) * c->maxBatch;
             dim3 block(256);
             const size_t winBytes = sizeof(float) * size_t(nChns) * a.mH * a.mW;
             const bool tail = a.last && sidx > 0 && a.t0 >= 128 && winBytes <= 64 * 1024;
@@ -586,13 +575,13 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
             {
                 // one wave per surviving window; enough waves per frame to fill the chip
                 dim3 grid(std::max(1, 8192 / nF) * nF);
-                if (mode == 1 && c->cs.codeCapD > 0 && a.t0 == 128)
+                if (mode == 1 && cs.codes.cap > 0 && a.t0 == 128)
                 {
-                    // leaf codes of the first codeCapD entries, then their ordered sums with lanes = windows; k_cascade_tail
+                    // leaf codes of the first codes.cap entries, then their ordered sums with lanes = windows; k_cascade_tail
                     // (below) takes the entries beyond and leaves at once when there are none
-                    a.codes = c->cs.d_codesD;
-                    a.codeCap = c->cs.codeCapD;
-                    a.codePitch = c->cs.codePitchD;
+                    a.codes = cs.codes.d;
+                    a.codeCap = cs.codes.cap;
+                    a.codePitch = cs.codes.pitch;
                     if (!pooledTail)
                     {
                         hipLaunchKernelGGL(k_tail_codesD, grid, dim3(64), winBytes, c->stream, a);
@@ -601,21 +590,18 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
                     const int nT = a.t1 - a.t0, NL = 1 << p.treeDepth;
                     const size_t ldsS = size_t((nT + 15) / 16 * 16) * NL * sizeof(float);
                     dim3 gridS(nF * ((a.codeCap + 255) / 256));
-                    int rcl = 0;
-#define TSD_LAUNCH(DD)                                                                              \
-    {                                                                                               \
-        if ((rcl = allowLds(c, reinterpret_cast<const void*>(&k_tail_scanD<DD>), ldsS)))            \
-            return rcl;                                                                             \
-        hipLaunchKernelGGL(k_tail_scanD<DD>, gridS, dim3(256), ldsS, c->stream, a);                 \
-    }
+                    void (*scan)(CascArgs) = nullptr;
                     switch (p.treeDepth)
                     {
-                        case 1: TSD_LAUNCH(1); break;
-                        case 3: TSD_LAUNCH(3); break;
-                        case 4: TSD_LAUNCH(4); break;
-                        default: TSD_LAUNCH(2); break;
+                        case 1: scan = k_tail_scanD<1>; break;
+                        case 3: scan = k_tail_scanD<3>; break;
+                        case 4: scan = k_tail_scanD<4>; break;
+                        default: scan = k_tail_scanD<2>; break;
                     }
-#undef TSD_LAUNCH
+                    if ((rc = launchLds(c, scan, gridS, dim3(256), ldsS, a)))
+                    {
+                        return rc;
+                    }
                     LAUNCHCHK(c, "k_tail_scanD");
                     a.qskip = a.codeCap;
                 }
@@ -654,29 +640,25 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
     // shift = (modelDsPad - modelDs)/2 - pad (ACF.cpp:275; cv::Size integer arithmetic)
     const int shift_h = (p.modelDsPad_h - p.modelDs_h) / 2 - p.pad_h;
     const int shift_w = (p.modelDsPad_w - p.modelDs_w) / 2 - p.pad_w;
-    const acf_hip_hit* hitsForSort = c->cs.d_hits;
-    if (c->cs.dedupQ > 1)
+    const acf_hip_hit* hitsForSort = cs.d_hits;
+    if (cs.dedupQ > 1)
     {
-        if (!c->cs.d_hitsX || !c->cs.d_realWin)
+        if (!cs.d_hitsX || !cs.d_realWin)
         {
             return fail(c, ACF_HIP_E_INVALID, "detect: no buffer for the windows that share an offset (stride < shrink)");
         }
-        hipLaunchKernelGGL(k_expand_hits, dim3(nF), dim3(256), 0, c->stream, (const acf_hip_hit*)c->cs.d_hits, c->cs.d_counts, c->cs.d_hitsX, c->maxHits,
-            (const int2*)c->cs.d_realWin, c->cs.dedupQ);
+        hipLaunchKernelGGL(k_expand_hits, dim3(nF), dim3(256), 0, c->stream, (const acf_hip_hit*)cs.d_hits, cs.d_counts, cs.d_hitsX, c->maxHits,
+            (const int2*)cs.d_realWin, cs.dedupQ);
         LAUNCHCHK(c, "k_expand_hits");
-        hitsForSort = c->cs.d_hitsX;
+        hitsForSort = cs.d_hitsX;
     }
     prof(c, "k_sort_map");
-    hipLaunchKernelGGL(k_sort_map, dim3(SM_BLOCKS, nF), dim3(256), 0, c->stream, hitsForSort, (const int32_t*)c->cs.d_counts, c->maxHits,
-        d_box, p.stride, shift_h, shift_w, c->cs.d_sorted, c->cs.d_dets);
+    hipLaunchKernelGGL(k_sort_map, dim3(SM_BLOCKS, nF), dim3(256), 0, c->stream, hitsForSort, (const int32_t*)cs.d_counts, c->maxHits,
+        d_box, p.stride, shift_h, shift_w, cs.d_sorted, cs.d_dets);
     LAUNCHCHK(c, "k_sort_map");
-    if (c->nmsOn && c->nms.type != 0)
+    if (c->nmsOn && c->nms.type != 0 && (rc = launchNms(c, nF)))
     {
-        int rc = launchNms(c, nF);
-        if (rc)
-        {
-            return rc;
-        }
+        return rc;
     }
     prof(c, "(end)");
     c->countsFetched = false;
