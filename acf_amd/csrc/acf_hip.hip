@@ -644,6 +644,20 @@ inline int cdiv(int64_t a, int64_t b)
 }
 
 // ---- kernel launch helpers (shared by the pyramid and the op_* entry points) ----
+// (A picker returns the instantiation a launch takes; each names its instantiations in the order the code object lists them.)
+
+using SmoothTri1Kernel = void (*)(const float*, float*, const SmoothJob*, int64_t, int64_t, float, int, float*);
+
+static SmoothTri1Kernel smoothTri1Kernel(int R, bool aliased)
+{
+    switch (R)
+    {
+        case 1: return aliased ? k_smooth_tri1<1, true> : k_smooth_tri1<1, false>;
+        case 2: return aliased ? k_smooth_tri1<2, true> : k_smooth_tri1<2, false>;
+        case 3: return aliased ? k_smooth_tri1<3, true> : k_smooth_tri1<3, false>;
+        default: return aliased ? k_smooth_tri1<4, true> : k_smooth_tri1<4, false>;
+    }
+}
 
 int launchSmooth(acf_hip_ctx* c, const float* in, float* out, const SmoothJob* d_jobs, int nJobs, int maxPlanes, int maxH,
     int64_t in_fs, int64_t out_fs, int nFrames, float p, bool aliased)
@@ -669,30 +683,8 @@ int launchSmooth(acf_hip_ctx* c, const float* in, float* out, const SmoothJob* d
     const int ldsStride = maxH + 1;
     prof(c, nJobs > 1 ? "k_smooth_tri1(levels)" : "k_smooth_tri1(image)");
     const size_t lds = 2 * size_t(ldsStride) * sizeof(float);
-    dim3 grid(maxPlanes, nJobs, nFrames), block(nt);
-#define SM_LAUNCH(RR)                                                                                                    \
-    if (aliased)                                                                                                         \
-        hipLaunchKernelGGL((k_smooth_tri1<RR, true>), grid, block, lds, c->stream, in, out, d_jobs, in_fs, out_fs, p, ldsStride, c->d_dump); \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((k_smooth_tri1<RR, false>), grid, block, lds, c->stream, in, out, d_jobs, in_fs, out_fs, p, ldsStride, c->d_dump);
-    switch (R)
-    {
-        case 1:
-            SM_LAUNCH(1);
-            break;
-        case 2:
-            SM_LAUNCH(2);
-            break;
-        case 3:
-            SM_LAUNCH(3);
-            break;
-        case 4:
-            SM_LAUNCH(4);
-            break;
-        default:
-            return fail(c, ACF_HIP_E_UNSUPPORTED, "smooth: plane taller than 4096 rows");
-    }
-#undef SM_LAUNCH
+    hipLaunchKernelGGL(smoothTri1Kernel(R, aliased), dim3(maxPlanes, nJobs, nFrames), dim3(nt), lds, c->stream, in, out, d_jobs, in_fs, out_fs, p, ldsStride,
+        c->d_dump);
     LAUNCHCHK(c, "k_smooth_tri1");
     return ACF_HIP_OK;
 }
@@ -731,6 +723,31 @@ static TriPlan triPlan(const float* in, const float* U, int h, int w, int rad, i
     return t;
 }
 
+using TriX5Kernel = void (*)(const float*, float*, int, int, int64_t, int64_t, int, int);
+using TriyChnsKernel = void (*)(const float*, ChnsArgs, int64_t, int);
+
+static TriX5Kernel triX5Kernel(bool ut)
+{
+    return ut ? k_tri_x5v<true> : k_tri_x5v<false>;
+}
+
+static TriyChnsKernel triyChnsKernel(bool maxO6, bool ut, bool x86)
+{
+    if (maxO6)
+    {
+        if (ut)
+        {
+            return x86 ? k_triy_chns<6, true, true> : k_triy_chns<6, true, false>;
+        }
+        return x86 ? k_triy_chns<6, false, true> : k_triy_chns<6, false, false>;
+    }
+    if (ut)
+    {
+        return x86 ? k_triy_chns<12, true, true> : k_triy_chns<12, true, false>;
+    }
+    return x86 ? k_triy_chns<12, false, true> : k_triy_chns<12, false, false>;
+}
+
 // uCapacity / moCapacity: floats per frame the U and the M, O buffers hold (>= fs); blocked: M and O ARE in the blocked layout
 // (the caller ran k_grad_mag_vec<true> after asking triPlan)
 // xDone: U is there already (k_smooth_grad_tri wrote it, blocked)
@@ -761,14 +778,8 @@ int launchTri(acf_hip_ctx* c, const float* in, float* U, float* S, int h, int w,
         prof(c, "k_tri_x");
         if (vecX)
         {
-            if (ut)
-            {
-                hipLaunchKernelGGL((k_tri_x5v<true>), dim3(cdiv(h / 4, 64), 1, nFrames), dim3(64), 0, c->stream, in, U, h, w, mfs, ufs, nyb, nybM);
-            }
-            else
-            {
-                hipLaunchKernelGGL((k_tri_x5v<false>), dim3(cdiv(h / 4, 64), 1, nFrames), dim3(64), 0, c->stream, in, U, h, w, fs, fs, 0, 0);
-            }
+            hipLaunchKernelGGL(triX5Kernel(ut), dim3(cdiv(h / 4, 64), 1, nFrames), dim3(64), 0, c->stream, in, U, h, w,
+                ut ? mfs : fs, ut ? ufs : fs, ut ? nyb : 0, ut ? nybM : 0);
         }
         else
         {
@@ -788,36 +799,8 @@ int launchTri(acf_hip_ctx* c, const float* in, float* U, float* S, int h, int w,
             fuse->m_fs = mfs;
             fuse->nybM = nybM;
         }
-        const dim3 grid(cdiv(w, 256), 1, nFrames), block(256);
-#define TRIY_LAUNCH(MAXO_, UT_)                                                                                                         \
-    if (fuse->x86)                                                                                                                      \
-    {                                                                                                                                   \
-        hipLaunchKernelGGL((k_triy_chns<MAXO_, UT_, true>), grid, block, 0, c->stream, (const float*)U, *fuse, UT_ ? ufs : fs, UT_ ? nyb : 0); \
-    }                                                                                                                                   \
-    else                                                                                                                                \
-    {                                                                                                                                   \
-        hipLaunchKernelGGL((k_triy_chns<MAXO_, UT_, false>), grid, block, 0, c->stream, (const float*)U, *fuse, UT_ ? ufs : fs, UT_ ? nyb : 0); \
-    }
-        if (fuse->nOrients <= 6)
-        {
-            if (ut)
-            {
-                TRIY_LAUNCH(6, true)
-            }
-            else
-            {
-                TRIY_LAUNCH(6, false)
-            }
-        }
-        else if (ut)
-        {
-            TRIY_LAUNCH(12, true)
-        }
-        else
-        {
-            TRIY_LAUNCH(12, false)
-        }
-#undef TRIY_LAUNCH
+        hipLaunchKernelGGL(triyChnsKernel(fuse->nOrients <= 6, ut, fuse->x86 != nullptr), dim3(cdiv(w, 256), 1, nFrames), dim3(256), 0, c->stream,
+            (const float*)U, *fuse, ut ? ufs : fs, ut ? nyb : 0);
         LAUNCHCHK(c, "k_triy_chns");
         *fused = true;
         return ACF_HIP_OK;
@@ -844,35 +827,37 @@ float shrinkGainY(int S)
     return r / (float)S;
 }
 
+using ChnsKernel = void (*)(ChnsArgs);
+
+static ChnsKernel chnsKernel(int shrink, bool maxO6)
+{
+    if (shrink == 4)
+    {
+        return maxO6 ? k_chns<4, 6> : k_chns<4, 12>;
+    }
+    return maxO6 ? k_chns<2, 6> : k_chns<2, 12>;
+}
+
 int launchChns(acf_hip_ctx* c, const ChnsArgs& a, int shrink, int nFrames)
 {
     const int hc = a.h / shrink, wc = a.w / shrink;
-    dim3 grid(cdiv(int64_t(hc) * wc, 256), 1, nFrames), block(256);
     prof(c, "k_chns");
-    if (shrink == 4)
-    {
-        if (a.nOrients <= 6)
-        {
-            hipLaunchKernelGGL((k_chns<4, 6>), grid, block, 0, c->stream, a);
-        }
-        else
-        {
-            hipLaunchKernelGGL((k_chns<4, 12>), grid, block, 0, c->stream, a);
-        }
-    }
-    else
-    {
-        if (a.nOrients <= 6)
-        {
-            hipLaunchKernelGGL((k_chns<2, 6>), grid, block, 0, c->stream, a);
-        }
-        else
-        {
-            hipLaunchKernelGGL((k_chns<2, 12>), grid, block, 0, c->stream, a);
-        }
-    }
+    hipLaunchKernelGGL(chnsKernel(shrink, a.nOrients <= 6), dim3(cdiv(int64_t(hc) * wc, 256), 1, nFrames), dim3(256), 0, c->stream, a);
     LAUNCHCHK(c, "k_chns");
     return ACF_HIP_OK;
+}
+
+// rgbConvert's gray weights (rgbConvertMex.cpp)
+struct GrayWeights
+{
+    float r, g, b;
+};
+constexpr GrayWeights kGray = { (float).2989360213 * 1.0f, (float).5870430745 * 1.0f, (float).1140209043 * 1.0f };
+
+// the input planes are the colour planes as they are: no conversion (chnsPyramid.cpp:230-263, rgbConvert.cpp:101-170)
+static bool colourPassthrough(const acf_hip_params& p, int nIn)
+{
+    return nIn >= 3 && (p.colorSpace == ACF_HIP_CS_ORIG || p.colorSpace == ACF_HIP_CS_RGB || (p.isLuv && p.colorSpace == ACF_HIP_CS_LUV));
 }
 
 } // namespace
@@ -1683,6 +1668,19 @@ int acf_hip_pyramid(acf_hip_ctx* c, const float* frames, int nF)
 
 namespace
 {
+using IngestKernel = void (*)(IngestArgs);
+
+static IngestKernel ingestKernel(int mode, bool aligned)
+{
+    switch (mode)
+    {
+        case IG_LUV_VEC: return aligned ? k_ingest_u8<IG_LUV_VEC, true> : k_ingest_u8<IG_LUV_VEC, false>;
+        case IG_LUV: return aligned ? k_ingest_u8<IG_LUV, true> : k_ingest_u8<IG_LUV, false>;
+        case IG_GRAY: return aligned ? k_ingest_u8<IG_GRAY, true> : k_ingest_u8<IG_GRAY, false>;
+        default: return aligned ? k_ingest_u8<IG_PLANAR, true> : k_ingest_u8<IG_PLANAR, false>;
+    }
+}
+
 int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t out_fs, bool convert)
 {
     const acf_hip_params& p = c->p;
@@ -1693,9 +1691,9 @@ int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t
     a.lTable = c->d_lTable;
     a.k = makeLuvConsts();
     a.x86 = x86T(c);
-    a.mr = (float).2989360213 * 1.0f;
-    a.mg = (float).5870430745 * 1.0f;
-    a.mb = (float).1140209043 * 1.0f;
+    a.mr = kGray.r;
+    a.mg = kGray.g;
+    a.mb = kGray.b;
     a.H = pl.H;
     a.W = pl.W;
     switch (u.pix)
@@ -1738,26 +1736,35 @@ int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t
             a.nOut = 3; // ORIG / RGB with a 1-plane input: replicate (chnsPyramid.cpp:242-243)
         }
     }
-    dim3 grid(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF), block(256);
-#define IG_LAUNCH(M)                                                                  \
-    if (aligned)                                                                      \
-    {                                                                                 \
-        hipLaunchKernelGGL((k_ingest_u8<M, true>), grid, block, 0, c->stream, a);     \
-    }                                                                                 \
-    else                                                                              \
-    {                                                                                 \
-        hipLaunchKernelGGL((k_ingest_u8<M, false>), grid, block, 0, c->stream, a);    \
-    }
-    switch (mode)
-    {
-        case IG_LUV_VEC: IG_LAUNCH(IG_LUV_VEC) break;
-        case IG_LUV: IG_LAUNCH(IG_LUV) break;
-        case IG_GRAY: IG_LAUNCH(IG_GRAY) break;
-        default: IG_LAUNCH(IG_PLANAR) break;
-    }
-#undef IG_LAUNCH
+    hipLaunchKernelGGL(ingestKernel(mode, aligned), dim3(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF), dim3(256), 0, c->stream, a);
     LAUNCHCHK(c, "k_ingest_u8");
     return ACF_HIP_OK;
+}
+
+// rgbConvert of nF frames of n pixels: `in` holds nIn planes a frame (frame stride in_fs), `out` the converted planes (out_fs).  LUV takes
+// the vector body iff n % 4 == 0 (rgbConvertMex.cpp:92,343); a 1-plane input is replicated first (chnsPyramid.cpp:234-244): gray from
+// it is k_rgb2gray<true>, ORIG / RGB k_replicate3.  The caller checks the launch.
+static void launchColour(acf_hip_ctx* c, const float* in, float* out, int64_t n, int nF, int64_t in_fs, int64_t out_fs, int colorSpace, int nIn)
+{
+    const dim3 grid(cdiv(n, 256), 1, nF), block(256);
+    if (colorSpace == ACF_HIP_CS_LUV)
+    {
+        hipLaunchKernelGGL((n % 4 == 0 ? k_rgb2luv<true> : k_rgb2luv<false>), grid, block, 0, c->stream, in, out, (const float*)c->d_lTable, makeLuvConsts(),
+            int(n), in_fs, out_fs, x86T(c));
+    }
+    else if (colorSpace == ACF_HIP_CS_GRAY)
+    {
+        hipLaunchKernelGGL((nIn == 1 ? k_rgb2gray<true> : k_rgb2gray<false>), grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs, kGray.r, kGray.g,
+            kGray.b);
+    }
+    else if (colorSpace == ACF_HIP_CS_HSV)
+    {
+        hipLaunchKernelGGL(k_rgb2hsv, grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs);
+    }
+    else
+    {
+        hipLaunchKernelGGL(k_replicate3, grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs);
+    }
 }
 
 static int pixCpp(int pix)
@@ -3143,36 +3150,57 @@ int acf_hip_op_rgb_convert(acf_hip_ctx* c, const float* in, float* out, int h, i
     {
         return fail(c, ACF_HIP_E_HIP, "op_rgb_convert: allocation");
     }
-    dim3 grid(cdiv(n, 256), 1, 1), block(256);
-    if (flag == ACF_HIP_CS_LUV)
-    {
-        if (n % 4 == 0)
-        {
-            hipLaunchKernelGGL(k_rgb2luv<true>, grid, block, 0, c->stream, (const float*)di, dout, (const float*)c->d_lTable, makeLuvConsts(), n, int64_t(0), int64_t(0), x86T(c));
-        }
-        else
-        {
-            hipLaunchKernelGGL(k_rgb2luv<false>, grid, block, 0, c->stream, (const float*)di, dout, (const float*)c->d_lTable, makeLuvConsts(), n, int64_t(0), int64_t(0), x86T(c));
-        }
-    }
-    else if (flag == ACF_HIP_CS_GRAY)
-    {
-        const float mr = (float).2989360213 * 1.0f, mg = (float).5870430745 * 1.0f, mb = (float).1140209043 * 1.0f;
-        hipLaunchKernelGGL(k_rgb2gray<false>, grid, block, 0, c->stream, (const float*)di, dout, n, int64_t(0), int64_t(0), mr, mg, mb);
-    }
-    else if (flag == ACF_HIP_CS_HSV)
-    {
-        hipLaunchKernelGGL(k_rgb2hsv, grid, block, 0, c->stream, (const float*)di, dout, n, int64_t(0), int64_t(0));
-    }
-    else
+    if (flag != ACF_HIP_CS_LUV && flag != ACF_HIP_CS_GRAY && flag != ACF_HIP_CS_HSV)
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, "op_rgb_convert: flag");
     }
+    launchColour(c, di, dout, n, 1, 0, 0, flag, 3);
     LAUNCHCHK(c, "op_rgb_convert");
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, dout, sizeof(float) * dOut * n, hipMemcpyDeviceToHost));
     return ACF_HIP_OK;
 }
+
+namespace
+{
+// convTri with a radius <= 1 (k_smooth_tri1) of the d planes of ONE h x w frame, tight, through a one-job SmoothJob; `who` prefixes the
+// error texts
+int smoothOne(acf_hip_ctx* c, Scratch& s, const char* who, const float* in, float* out, int h, int w, int d, int64_t fs, float p, bool aliased)
+{
+    SmoothJob j{};
+    j.h = h;
+    j.w = w;
+    j.nplanes = d;
+    j.out_cs = h;
+    j.in_ps = int64_t(h) * w;
+    j.out_ps = int64_t(h) * w;
+    SmoothJob* dj = s.upload(&j, 1);
+    if (!dj)
+    {
+        return fail(c, ACF_HIP_E_HIP, std::string(who) + ": allocation");
+    }
+    return launchSmooth(c, in, out, dj, 1, d, h, fs, fs, 1, p, aliased);
+}
+
+// gradMag of ONE h x w plane I into M and O (k_grad_mag_strip), then convTri(M, normRad) into S through U when normRad > 0; `who`
+// prefixes the launch's error text, normRadErr is the text for a normRad the plane is too small for
+int gradMagOne(acf_hip_ctx* c, const char* who, const char* normRadErr, const float* I, float* M, float* O, float* U, float* S, int h, int w, int full,
+    int normRad)
+{
+    hipLaunchKernelGGL(k_grad_mag_strip, dim3(cdiv(h, GM_ROWS), 1, 1), dim3(GM_ROWS), 0, c->stream, I, M, O, (const float*)c->d_acos, h, w, full, int64_t(0),
+        int64_t(0), cdiv(w, GM_XT), x86T(c));
+    LAUNCHCHK(c, std::string(who) + ": k_grad_mag");
+    if (!normRad)
+    {
+        return ACF_HIP_OK;
+    }
+    if (std::min(h, w) < 4 || 2 * normRad + 1 >= std::min(h, w) || normRad < 2)
+    {
+        return fail(c, ACF_HIP_E_UNSUPPORTED, normRadErr);
+    }
+    return launchTri(c, M, U, S, h, w, normRad, int64_t(h) * w, 1);
+}
+} // namespace
 
 int acf_hip_op_conv_tri(acf_hip_ctx* c, const float* in, float* out, int h, int w, int d, double r, int aliased)
 {
@@ -3197,20 +3225,7 @@ int acf_hip_op_conv_tri(acf_hip_ctx* c, const float* in, float* out, int h, int 
     int rc;
     if (r > 0 && r <= 1.0)
     {
-        SmoothJob j{};
-        j.h = h;
-        j.w = w;
-        j.nplanes = d;
-        j.out_cs = h;
-        j.in_ps = np;
-        j.out_ps = np;
-        SmoothJob* dj = s.upload(&j, 1);
-        if (!dj)
-        {
-            return fail(c, ACF_HIP_E_HIP, "op_conv_tri: allocation");
-        }
-        const float p = float(12.0 / r / (r + 2.0) - 2.0);
-        if ((rc = launchSmooth(c, di, dout, dj, 1, d, h, 0, 0, 1, p, aliased != 0)))
+        if ((rc = smoothOne(c, s, "op_conv_tri", di, dout, h, w, d, 0, float(12.0 / r / (r + 2.0) - 2.0), aliased != 0)))
         {
             return rc;
         }
@@ -3368,19 +3383,12 @@ int acf_hip_op_gradient_mag(acf_hip_ctx* c, const float* in, float* M, float* O,
     {
         return fail(c, ACF_HIP_E_HIP, "op_gradient_mag: allocation");
     }
-    hipLaunchKernelGGL(k_grad_mag_strip, dim3(cdiv(h, GM_ROWS), 1, 1), dim3(GM_ROWS), 0, c->stream, (const float*)di, dM, dO, (const float*)c->d_acos, h, w, full, int64_t(0), int64_t(0), cdiv(w, GM_XT), x86T(c));
-    LAUNCHCHK(c, "k_grad_mag");
+    if (int rc = gradMagOne(c, "op_gradient_mag", "op_gradient_mag: normRad", di, dM, dO, dU, dS, h, w, full, normRad))
+    {
+        return rc;
+    }
     if (normRad)
     {
-        if (std::min(h, w) < 4 || 2 * normRad + 1 >= std::min(h, w) || normRad < 2)
-        {
-            return fail(c, ACF_HIP_E_UNSUPPORTED, "op_gradient_mag: normRad");
-        }
-        int rc = launchTri(c, dM, dU, dS, h, w, normRad, np, 1);
-        if (rc)
-        {
-            return rc;
-        }
         hipLaunchKernelGGL(k_norm, dim3(cdiv(np, 256)), dim3(256), 0, c->stream, dM, (const float*)dS, int(np), float(normConst), x86T(c));
         LAUNCHCHK(c, "k_norm");
     }
@@ -3475,44 +3483,13 @@ int acf_hip_chns_compute(acf_hip_ctx* c, const acf_hip_params* pIn, const float*
         return fail(c, ACF_HIP_E_HIP, "chns_compute: allocation");
     }
     // rgbConvert(I, I, colorSpace, true, isLuv) (chnsCompute.cpp:235; rgbConvert.cpp:101-170)
-    const bool passthrough = (d >= 3) && (p.colorSpace == ACF_HIP_CS_ORIG || p.colorSpace == ACF_HIP_CS_RGB || (p.isLuv && p.colorSpace == ACF_HIP_CS_LUV));
+    if (colourPassthrough(p, d))
     {
-        dim3 grid(cdiv(np, 256), 1, 1), block(256);
-        if (passthrough)
-        {
-            HIPCHK(c, hipMemcpyAsync(dCol, dI, sizeof(float) * 3 * np, hipMemcpyDeviceToDevice, c->stream));
-        }
-        else if (p.colorSpace == ACF_HIP_CS_LUV)
-        {
-            if (np % 4 == 0)
-            {
-                hipLaunchKernelGGL(k_rgb2luv<true>, grid, block, 0, c->stream, (const float*)dI, dCol, (const float*)c->d_lTable, makeLuvConsts(), int(np), int64_t(0), int64_t(0), x86T(c));
-            }
-            else
-            {
-                hipLaunchKernelGGL(k_rgb2luv<false>, grid, block, 0, c->stream, (const float*)dI, dCol, (const float*)c->d_lTable, makeLuvConsts(), int(np), int64_t(0), int64_t(0), x86T(c));
-            }
-        }
-        else if (p.colorSpace == ACF_HIP_CS_GRAY)
-        {
-            const float mr = (float).2989360213 * 1.0f, mg = (float).5870430745 * 1.0f, mb = (float).1140209043 * 1.0f;
-            if (d == 1)
-            {
-                hipLaunchKernelGGL(k_rgb2gray<true>, grid, block, 0, c->stream, (const float*)dI, dCol, int(np), int64_t(0), int64_t(0), mr, mg, mb);
-            }
-            else
-            {
-                hipLaunchKernelGGL(k_rgb2gray<false>, grid, block, 0, c->stream, (const float*)dI, dCol, int(np), int64_t(0), int64_t(0), mr, mg, mb);
-            }
-        }
-        else if (p.colorSpace == ACF_HIP_CS_HSV)
-        {
-            hipLaunchKernelGGL(k_rgb2hsv, grid, block, 0, c->stream, (const float*)dI, dCol, int(np), int64_t(0), int64_t(0));
-        }
-        else
-        {
-            hipLaunchKernelGGL(k_replicate3, grid, block, 0, c->stream, (const float*)dI, dCol, int(np), int64_t(0), int64_t(0));
-        }
+        HIPCHK(c, hipMemcpyAsync(dCol, dI, sizeof(float) * 3 * np, hipMemcpyDeviceToDevice, c->stream));
+    }
+    else
+    {
+        launchColour(c, dI, dCol, np, 1, 0, 0, p.colorSpace, d);
         LAUNCHCHK(c, "chns_compute: colour conversion");
     }
     // convTri(I, I, pColor.smooth, 1) in place (chnsCompute.cpp:239)
@@ -3522,21 +3499,8 @@ int acf_hip_chns_compute(acf_hip_ctx* c, const acf_hip_params* pIn, const float*
         {
             return fail(c, ACF_HIP_E_UNSUPPORTED, "chns_compute: pColor.smooth > 1 (convTri with a radius) is not built for the colour planes");
         }
-        SmoothJob j{};
-        j.h = hc;
-        j.w = wc;
-        j.nplanes = dcol;
-        j.out_cs = hc;
-        j.in_ps = np;
-        j.out_ps = np;
-        SmoothJob* dJ = s.upload(&j, 1);
-        if (!dJ)
-        {
-            return fail(c, ACF_HIP_E_HIP, "chns_compute: allocation");
-        }
         const float pColor = float(12.0 / p.colorSmooth / (p.colorSmooth + 2.0) - 2.0);
-        int rc = launchSmooth(c, dCol, dCol, dJ, 1, dcol, hc, int64_t(dcol) * np, int64_t(dcol) * np, 1, pColor, true);
-        if (rc)
+        if (int rc = smoothOne(c, s, "chns_compute", dCol, dCol, hc, wc, dcol, int64_t(dcol) * np, pColor, true))
         {
             return rc;
         }
@@ -3572,20 +3536,10 @@ int acf_hip_chns_compute(acf_hip_ctx* c, const acf_hip_params* pIn, const float*
     }
     else if (p.gradMagEnabled || p.gradHistEnabled)
     {
-        hipLaunchKernelGGL(k_grad_mag_strip, dim3(cdiv(hc, GM_ROWS), 1, 1), dim3(GM_ROWS), 0, c->stream, (const float*)(dCol + int64_t(p.colorChn) * np), dM, dO,
-            (const float*)c->d_acos, hc, wc, p.full, int64_t(0), int64_t(0), cdiv(wc, GM_XT), x86T(c));
-        LAUNCHCHK(c, "chns_compute: k_grad_mag");
-        if (p.normRad)
+        if (int rc = gradMagOne(c, "chns_compute", "chns_compute: normRad against the image size", dCol + int64_t(p.colorChn) * np, dM, dO, dU, dS, hc, wc,
+                p.full, p.normRad))
         {
-            if (std::min(hc, wc) < 4 || 2 * p.normRad + 1 >= std::min(hc, wc) || p.normRad < 2)
-            {
-                return fail(c, ACF_HIP_E_UNSUPPORTED, "chns_compute: normRad against the image size");
-            }
-            int rc = launchTri(c, dM, dU, dS, hc, wc, p.normRad, np, 1);
-            if (rc)
-            {
-                return rc;
-            }
+            return rc;
         }
     }
     int rc = launchChns(c, a, shrink, 1);

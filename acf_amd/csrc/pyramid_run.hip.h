@@ -5,7 +5,8 @@
 //   ingest()            packed 8-bit frames -> planar f32 (ACF.cpp:114-119,137), the apps' Resizer in front of it
 //   colour()            rgbConvert once at full resolution (chnsPyramid.cpp:230-263)
 //   prepareScales()     which image every real scale is resampled from (the I = I1 adoption, :313-316), the scales' streams
-//   realScale(k)        imageResample(k) -> smoothImage(k) -> gradientChannels(k): chnsCompute at a real scale (:297-338, chnsCompute.cpp:146-338)
+//   realScale(k)        imageResample(k) -> planScale(k) -> smoothImage(k) -> gradientChannels(k): chnsCompute at a real scale (:297-338,
+//                       chnsCompute.cpp:146-338)
 //   joinScales()
 //   levels(f0, n)       the approximated levels + final smoothing + padding of frames [f0, f0 + n) (:385-435)
 //   levelsWithImageLambdas()   the same behind the per-image lambda estimate (:341-374)
@@ -13,13 +14,120 @@
 
 namespace
 {
-// what smoothImage leaves for gradientChannels
-struct SmoothOut
+// How a real scale is computed, decided once after its image is there (PyramidRun::planScale); smoothImage and gradientChannels only read it
+struct ScalePlan
 {
-    bool colorDone = false;                       // the level's colour channels were written from the smoothing chain's registers
-    bool gradFused = false, gradBlocked = false;  // M and O written by k_smooth_grad (in 64 x 16 blocks)
-    bool triXFused = false;                       // ... and U by k_smooth_grad_tri
+    bool fuseSm = false;      // k_smooth_vec: smoothing + the level's colour channels from registers (colorDone), in column segments
+    bool halfNext = false;    // ... + the next real scale's image, an exact half of this one
+    uint32_t fullMask = 0;    // ... the planes whose full-resolution smoothed image is written
+    bool wantGrad = false;    // ... the gradient plane's chain also emits gradMag (k_smooth_grad): M and O
+    bool triXFused = false;   // ... and convTri's x pass: U (k_smooth_grad_tri)
+    bool fuseCells = false;   // convTri's y pass may write the channel cells (k_triy_chns); else S is written and k_chns normalises
+    bool blocked = false;     // M, O and U in 64 x 16 blocks (triPlan)
+    ChnsArgs a{};             // the level's channel arguments (without the arith tables)
+    int nt = 0, warm = 0;     // k_smooth_vec's threads, warm-up columns
+    int nSeg = 1, segW = 0;   // column segments of the other planes' launch (and their width)
+    int nSegG = 1, segWG = 0; // ... of the gradient plane's launch
+    int segStride = 1;        // max(nSeg, nSegG): the hand-over state's segments
+    size_t ldsB = 0, ldsG = 0; // LDS bytes of the two launches
 };
+
+// The instantiations of the pyramid's kernels.  (Each picker names them in the order the code object lists them.)
+using SmoothVecKernel = void (*)(SmoothVecArgs, uint32_t);
+using GradMagVecKernel = void (*)(const float*, float*, float*, const float*, int, int, int, int64_t, int64_t, int, int, const uint32_t*);
+using LevelAllKernel = void (*)(const float*, float*, float*, const LevelJob*, const ResampleDesc*, const int32_t*, const float*, int, int64_t, int64_t, float,
+    float*, int, LevelRankArgs, LevelSegArgs);
+using LevelKernel = void (*)(const float*, float*, float*, const LevelJob*, const ResampleDesc*, const int32_t*, const float*, int, int64_t, int64_t, float,
+    float*, int);
+
+static SmoothVecKernel smoothGradKernel(bool tri, bool half, bool x86)
+{
+    if (!x86)
+    {
+        if (!tri)
+        {
+            return half ? k_smooth_grad<true, false> : k_smooth_grad<false, false>;
+        }
+        return half ? k_smooth_grad_tri<true, false> : k_smooth_grad_tri<false, false>;
+    }
+    if (!tri)
+    {
+        return half ? k_smooth_grad<true, true> : k_smooth_grad<false, true>;
+    }
+    return half ? k_smooth_grad_tri<true, true> : k_smooth_grad_tri<false, true>;
+}
+
+static SmoothVecKernel smoothVecKernel(bool half)
+{
+    return half ? k_smooth_vec<true> : k_smooth_vec<false>;
+}
+
+static GradMagVecKernel gradMagVecKernel(bool blocked, bool x86)
+{
+    if (blocked)
+    {
+        return x86 ? k_grad_mag_vec<true, true> : k_grad_mag_vec<true, false>;
+    }
+    return x86 ? k_grad_mag_vec<false, true> : k_grad_mag_vec<false, false>;
+}
+
+static LevelAllKernel levelAllKernel(bool f32, bool rank, bool segmented)
+{
+    if (f32 && rank)
+    {
+        return segmented ? k_level_all<LO_F32 | LO_RANK, 1> : k_level_all<LO_F32 | LO_RANK, 0>;
+    }
+    if (rank)
+    {
+        return segmented ? k_level_all<LO_RANK, 1> : k_level_all<LO_RANK, 0>;
+    }
+    return segmented ? k_level_all<LO_F32, 1> : k_level_all<LO_F32, 0>;
+}
+
+// null: R rows per lane are not instantiated for the mode
+static LevelKernel levelKernel(int R, int mode)
+{
+#define LEVEL_R(RR)                                 \
+    switch (mode)                                   \
+    {                                               \
+        case LM_REAL: return k_level<RR, LM_REAL>;  \
+        case LM_DD: return k_level<RR, LM_DD>;      \
+        default: return k_level<RR, LM_UU>;         \
+    }
+    switch (R)
+    {
+        case 1: LEVEL_R(1)
+        case 2: LEVEL_R(2)
+        case 3: LEVEL_R(3)
+        case 4: LEVEL_R(4)
+        case 5: LEVEL_R(5)
+        case 6: LEVEL_R(6)
+        case 7: LEVEL_R(7)
+        case 8: LEVEL_R(8)
+        default:
+            // nine rows per lane: the full-resolution level of a 4K frame (540 cells); a real level's copy + smoothing only
+            return R == LEVEL_MAX_R_REAL && mode == LM_REAL ? k_level<9, LM_REAL> : nullptr;
+    }
+#undef LEVEL_R
+}
+
+// option count_repairs: the n planes a verify kernel judged (its flags at d_flags) into c->repairs[slot], those it flagged into [slot + 1]
+static int countRepairs(acf_hip_ctx* c, const int32_t* d_flags, size_t n, int slot)
+{
+    if (!c->opt.countRepairs)
+    {
+        return ACF_HIP_OK;
+    }
+    std::vector<int32_t> fl(n);
+    HIPCHK(c, hipMemcpyAsync(fl.data(), d_flags, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->repairs[slot] += int64_t(n);
+    for (int32_t v : fl)
+    {
+        c->repairs[slot + 1] += v != 0;
+    }
+    return ACF_HIP_OK;
+}
 
 struct PyramidRun
 {
@@ -53,8 +161,9 @@ struct PyramidRun
     int prepareScales();
     int realScale(size_t k);
     int imageResample(size_t k, const float*& img, int64_t& img_fs);
-    int smoothImage(size_t k, const float* img, int64_t img_fs, SmoothOut& so);
-    int gradientChannels(size_t k, const SmoothOut& so);
+    ScalePlan planScale(size_t k, const float* img, int64_t img_fs);
+    int smoothImage(size_t k, const float* img, int64_t img_fs, const ScalePlan& sp);
+    int gradientChannels(size_t k, const ScalePlan& sp);
     int joinScales();
     int levels(int f0, int nLF);
     int levelsWithImageLambdas();
@@ -127,40 +236,8 @@ int PyramidRun::colour(bool ingestConverted)
     else if (c->d_color)
     {
         prof(c, "k_colour");
-        dim3 grid(cdiv(np0, 256), 1, nF), block(256);
         const int64_t out_fs = int64_t(d) * np0;
-        if (p.colorSpace == ACF_HIP_CS_LUV)
-        {
-            // d_in == 3, RGB -> LUV; the reference takes the SSE body iff n % 4 == 0 (rgbConvertMex.cpp:92,343)
-            if (np0 % 4 == 0)
-            {
-                hipLaunchKernelGGL(k_rgb2luv<true>, grid, block, 0, c->stream, frames, c->d_color, (const float*)c->d_lTable, makeLuvConsts(), int(np0), cur_fs, out_fs, x86T(c));
-            }
-            else
-            {
-                hipLaunchKernelGGL(k_rgb2luv<false>, grid, block, 0, c->stream, frames, c->d_color, (const float*)c->d_lTable, makeLuvConsts(), int(np0), cur_fs, out_fs, x86T(c));
-            }
-        }
-        else if (p.colorSpace == ACF_HIP_CS_GRAY)
-        {
-            const float mr = (float).2989360213 * 1.0f, mg = (float).5870430745 * 1.0f, mb = (float).1140209043 * 1.0f;
-            if (d_in == 1)
-            {
-                hipLaunchKernelGGL(k_rgb2gray<true>, grid, block, 0, c->stream, frames, c->d_color, int(np0), cur_fs, out_fs, mr, mg, mb);
-            }
-            else
-            {
-                hipLaunchKernelGGL(k_rgb2gray<false>, grid, block, 0, c->stream, frames, c->d_color, int(np0), cur_fs, out_fs, mr, mg, mb);
-            }
-        }
-        else if (p.colorSpace == ACF_HIP_CS_HSV)
-        {
-            hipLaunchKernelGGL(k_rgb2hsv, grid, block, 0, c->stream, frames, c->d_color, int(np0), cur_fs, out_fs); // (d_in == 3: the plan checked)
-        }
-        else // ORIG / RGB with a 1-plane input: replicate
-        {
-            hipLaunchKernelGGL(k_replicate3, grid, block, 0, c->stream, frames, c->d_color, int(np0), cur_fs, out_fs);
-        }
+        launchColour(c, frames, c->d_color, np0, nF, cur_fs, out_fs, p.colorSpace, d_in); // (hsv: d_in == 3, the plan checked)
         LAUNCHCHK(c, "colour conversion");
         cur = c->d_color;
         cur_fs = out_fs;
@@ -230,8 +307,8 @@ int PyramidRun::realScale(size_t k)
     {
         return rc;
     }
-    SmoothOut so;
-    if ((rc = smoothImage(k, img, img_fs, so)))
+    const ScalePlan sp = planScale(k, img, img_fs);
+    if ((rc = smoothImage(k, img, img_fs, sp)))
     {
         return rc;
     }
@@ -246,7 +323,7 @@ int PyramidRun::realScale(size_t k)
         curH = rs.h;
         curW = rs.w;
     }
-    return gradientChannels(k, so);
+    return gradientChannels(k, sp);
 }
 
 // the real scale's image from the adopted image (chnsPyramid.cpp:305-311)
@@ -308,316 +385,17 @@ int PyramidRun::imageResample(size_t k, const float*& img, int64_t& img_fs)
     return ACF_HIP_OK;
 }
 
-int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, SmoothOut& so)
+// the scale's plan: which forms smoothImage and gradientChannels take (the one triPlan of the scale gives the M / O / U layout)
+ScalePlan PyramidRun::planScale(size_t k, const float* img, int64_t img_fs)
 {
-    int rc;
-    RealScale& rs = c->real[k];
+    const RealScale& rs = c->real[k];
     const int64_t np = int64_t(rs.h) * rs.w;
-    // convTri(I, I, pColor.smooth, 1) in place (chnsCompute.cpp:239)
-    bool& colorDone = so.colorDone;
-    bool &gradFused = so.gradFused, &gradBlocked = so.gradBlocked, &triXFused = so.triXFused;
-    const bool fuseSm = p.colorSmooth > 0 && p.colorEnabled && !c->opt.taps && c->opt.fusedSmooth && shrink == 4 && rs.h % 4 == 0 && rs.w % 4 == 0 && rs.w >= 16 &&
-        rs.h / 4 <= SV_MAXW * SV_OWN && img_fs % 4 == 0 && np % 4 == 0 && pl.raw_floats % 1 == 0 && (uintptr_t(img) & 15) == 0;
-    if (fuseSm)
-    {
-        // k_smooth_vec: smoothing + the level's colour channels (+ the next real scale's image when it is an exact half
-        // of this one) from registers; full-resolution smoothed planes are written only where something still reads them
-        const bool halfNext = k + 1 < c->real.size() && srcIdx[k + 1] == int(k) && c->real[k + 1].resampled &&
-            [&] { const ResampleDesc& nd = c->h_descs[c->real[k + 1].descIndex];
-                  return nd.xmode == RS_EXACT && nd.ymode == RS_EXACT && nd.xk == 2 && nd.yk == 2 && nd.ha == rs.h && nd.wa == rs.w; }();
-        bool needFullAll = false;
-        for (size_t m = k + 1; m < c->real.size(); m++)
-        {
-            if (srcIdx[m] == int(k) && !(m == k + 1 && halfNext))
-            {
-                needFullAll = true;
-            }
-        }
-        SmoothVecArgs sa{};
-        sa.in = img;
-        sa.in_fs = img_fs;
-        sa.in_ps = np;
-        sa.sm = rs.sm;
-        sa.sm_fs = int64_t(d) * np;
-        sa.sm_ps = np;
-        sa.chns = c->d_chns + pl.raw_off[rs.level];
-        sa.chns_fs = pl.raw_floats;
-        sa.cells = int64_t(rs.h / 4) * (rs.w / 4);
-        sa.h = rs.h;
-        sa.w = rs.w;
-        sa.p = pColor;
-        sa.rq_y = shrinkGainY(shrink);
-        sa.dump = c->d_dump;
-        if (halfNext)
-        {
-            const RealScale& nx = c->real[k + 1];
-            const ResampleDesc& nd = c->h_descs[nx.descIndex];
-            sa.half = nx.img;
-            sa.half_ps = int64_t(nx.h) * nx.w;
-            sa.half_fs = int64_t(d) * sa.half_ps;
-            sa.rkHalf = nd.rk[0];
-            halfDone[k + 1] = true;
-        }
-        const int nq = rs.h / 4, nt = cdiv(nq, SV_OWN) * 64; // a wave owns SV_OWN row quads and shadows SV_K of each neighbour
-        const size_t ldsB = size_t(2) * SV_MAXW * 2 * SV_K * 4 * sizeof(float);
-        {
-            uint32_t fullMask = 0;
-            for (int z = 0; z < d; z++)
-            {
-                if (needFullAll || ((p.gradMagEnabled || p.gradHistEnabled) && z == p.colorChn))
-                {
-                    fullMask |= 1u << z;
-                }
-            }
-            sa.plane0 = 0;
-            sa.nPlanes = d;
-            // column segments: as many as give a launch ~6 waves per SIMD (a plane is a chain of column steps with
-            // nt / 64 waves), each at least 4 warm-ups long; one segment = the plain recursion.  `planesOf`: planes in the launch
-            const int warm = std::max(16, c->opt.smoothWarm);
-            auto segmentsFor = [&](int planesOf, int& segW_) {
-                int n = c->opt.smoothSegments;
-                if (n == 0 && c->opt.sharedDevice && nF >= 64)
-                {
-                    n = 1; // (beside other contexts: the plain chain — no warm-up columns, nothing to verify or repair)
-                }
-                if (n == 0)
-                {
-                    const int64_t waves = int64_t(std::max(planesOf, 1)) * nF * (nt / 64);
-                    n = int(std::min<int64_t>((6 * 1024 + waves - 1) / waves, rs.w / (4 * warm)));
-                }
-                n = std::max(1, std::min(n, std::min(c->segCap, rs.w / 16)));
-                segW_ = cdiv(cdiv(rs.w, n), 16) * 16;
-                return cdiv(rs.w, segW_);
-            };
-            int segW = 0;
-            int nSeg = segmentsFor(d, segW);
-            sa.segW = segW;
-            sa.warm = warm;
-            sa.nSeg = nSeg;
-            sa.segStride = nSeg;
-            sa.specState = c->d_specState;
-            sa.trueState = c->d_trueState;
-            sa.redo = nullptr;
-            sa.skipZ = -1;
-            // the gradient plane's chain also emits gradMag (k_smooth_grad): its smoothed plane is then written only
-            // where a later scale is resampled from it, and k_grad_mag_vec does not run for this scale
-            const bool gradVecOk = rs.h % 4 == 0 && np % 4 == 0;
-            // Where it pays (measured at 1080p, 3 x 96 frames: +4 % frames/s with scale 0 fused, +2 % with every scale; one
-            // frame alone 1.21 -> 1.61 / 2.40 ms): the gradient work rides on a chain of column steps, so it needs many
-            // chains (frames x segments) and a plane big enough for the saved round trip to matter.  A/B: the variables.
-            const int64_t gradMinPx = int64_t(1) << 20;
-            const int gradMinF = 16;
-            const bool wantGrad = (p.gradMagEnabled || p.gradHistEnabled) && gradVecOk && !(d_in == 5 && k == 0) && // (five planes: M, O came with the image)
-                (c->opt.fusedGrad >= 2 || (c->opt.fusedGrad == 1 && np >= gradMinPx && nF >= gradMinF));
-            if (wantGrad)
-            {
-                const bool wantTri0 = (p.gradMagEnabled || p.gradHistEnabled) && p.normRad;
-                // (the layout of M and O: the decision the y pass takes below, from the same inputs)
-                ChnsArgs a0{};
-                a0.M = rs.M;
-                a0.O = rs.O;
-                a0.Mn = nullptr; // (no taps on this path)
-                a0.doNorm = p.normRad != 0;
-                a0.colorDone = 1;
-                a0.colorEnabled = p.colorEnabled;
-                a0.magEnabled = p.gradMagEnabled;
-                a0.histEnabled = p.gradHistEnabled;
-                a0.nOrients = p.nOrients;
-                const bool blocked0 = wantTri0 && triPlan(rs.M, rs.U, rs.h, rs.w, p.normRad, np, &a0, rs.uFloats, rs.moFloats, true).blocked;
-                gradBlocked = blocked0;
-                sa.skipZ = p.colorChn;
-                sa.gM = rs.M;
-                sa.gO = rs.O;
-                sa.acos = c->d_acos;
-                sa.mo_fs = blocked0 ? moBlockedFloats(rs.h, rs.w) : np;
-                sa.nybM = blocked0 ? (rs.h + 15) / 16 : 0;
-                sa.full = p.full;
-                gradFused = true;
-                if (!needFullAll)
-                {
-                    fullMask &= ~(1u << p.colorChn);
-                }
-                // convTri's x pass on the same chain: running sums have no warm-up, so the gradient plane is then one segment
-                // (96 workgroups for 96 frames: slower alone, faster beside other contexts' kernels — DESIGN.md 3.0)
-                const int triMinF = 64;
-                if (blocked0 && p.normRad == 5 && rs.w >= 48 && nt <= 512 && (c->opt.fusedTri >= 2 || (c->opt.fusedTri == 1 && c->opt.sharedDevice && nF >= triMinF)))
-                {
-                    triXFused = true;
-                    sa.tU = rs.U;
-                    sa.u_fs = uBlockedFloats(rs.h, rs.w);
-                    sa.nybU = (rs.h + 8 + 15) / 16;
-                }
-            }
-            // the two launches cut their planes on their own: the gradient plane's launch has a third of the chains (more
-            // segments), the other planes' launch two thirds
-            int nSegG = nSeg, segWG = segW;
-            if (wantGrad && d > 1)
-            {
-                nSeg = segmentsFor(d - 1, segW);
-                nSegG = segmentsFor(1, segWG);
-                if (triXFused)
-                {
-                    nSegG = 1;
-                    segWG = cdiv(rs.w, 16) * 16;
-                }
-                sa.segW = segW;
-                sa.nSeg = nSeg;
-                sa.segStride = std::max(nSeg, nSegG);
-            }
-            const size_t ldsG = ldsB + size_t(GM_ACOS_N) * sizeof(float) + (c->opt.arith ? size_t(X86_GM_N) * sizeof(uint2) : 0); // (+ gradMag's table pairs, option "arith")
-            if (wantGrad && d == 1 && triXFused)
-            {
-                nSeg = nSegG = 1; // (one launch: the gradient plane's)
-                segW = segWG = cdiv(rs.w, 16) * 16;
-                sa.segW = segW;
-                sa.nSeg = 1;
-                sa.segStride = 1;
-            }
-            if (wantGrad)
-            {
-                int rcl = 0;
-                if ((rcl = allowLds(c, reinterpret_cast<const void*>(&k_smooth_grad<true, false>), ldsG)) ||
-                    (rcl = allowLds(c, reinterpret_cast<const void*>(&k_smooth_grad<false, false>), ldsG)) ||
-                    (rcl = allowLds(c, reinterpret_cast<const void*>(&k_smooth_grad_tri<true, false>), ldsG)) ||
-                    (rcl = allowLds(c, reinterpret_cast<const void*>(&k_smooth_grad_tri<false, false>), ldsG)) ||
-                    (rcl = allowLds(c, reinterpret_cast<const void*>(&k_smooth_grad<true, true>), ldsG)) ||
-                    (rcl = allowLds(c, reinterpret_cast<const void*>(&k_smooth_grad<false, true>), ldsG)) ||
-                    (rcl = allowLds(c, reinterpret_cast<const void*>(&k_smooth_grad_tri<true, true>), ldsG)) ||
-                    (rcl = allowLds(c, reinterpret_cast<const void*>(&k_smooth_grad_tri<false, true>), ldsG)))
-                {
-                    return rcl;
-                }
-            }
-            auto launchSv = [&](dim3 grid) {
-                // (profile names: the gradient plane's launch by its form, the other planes' launch "k_smooth_vec")
-                prof(c, !wantGrad ? "k_smooth_vec" : triXFused ? "k_smooth_grad_tri" : "k_smooth_grad");
-                if (wantGrad)
-                {
-                    // (first: its chains are the long ones)
-                    SmoothVecArgs sg = sa;
-                    sg.plane0 = p.colorChn;
-                    sg.skipZ = -1;
-                    if (sa.nSeg > 1 || nSegG > 1) // (not the repair launch: that one is one chain per plane)
-                    {
-                        if (!sa.redo)
-                        {
-                            sg.segW = segWG;
-                            sg.nSeg = nSegG;
-                            grid.y = unsigned(nSegG);
-                        }
-                    }
-                    if (sa.redo && nSegG == 1)
-                    {
-                        // (nothing to repair: the plane was one chain)
-                    }
-                    else
-                    {
-                        // (the gradient plane's launch: with convTri's x pass on the chain or without, the next scale's half image or not,
-                        // exact reciprocals or — option "arith" — one x86 CPU's)
-                        sg.x86 = x86T(c);
-                        const dim3 gg = triXFused ? dim3(1, 1, grid.z) : dim3(1, grid.y, grid.z);
-#define SG_LAUNCH(KERNEL)                                                                                          \
-    if (halfNext)                                                                                                  \
-    {                                                                                                              \
-        if (sg.x86)                                                                                                \
-        {                                                                                                          \
-            hipLaunchKernelGGL((KERNEL<true, true>), gg, dim3(nt), ldsG, c->stream, sg, fullMask);                 \
-        }                                                                                                          \
-        else                                                                                                       \
-        {                                                                                                          \
-            hipLaunchKernelGGL((KERNEL<true, false>), gg, dim3(nt), ldsG, c->stream, sg, fullMask);                \
-        }                                                                                                          \
-    }                                                                                                              \
-    else if (sg.x86)                                                                                               \
-    {                                                                                                              \
-        hipLaunchKernelGGL((KERNEL<false, true>), gg, dim3(nt), ldsG, c->stream, sg, fullMask);                    \
-    }                                                                                                              \
-    else                                                                                                           \
-    {                                                                                                              \
-        hipLaunchKernelGGL((KERNEL<false, false>), gg, dim3(nt), ldsG, c->stream, sg, fullMask);                   \
-    }
-                        if (triXFused)
-                        {
-                            SG_LAUNCH(k_smooth_grad_tri)
-                        }
-                        else
-                        {
-                            SG_LAUNCH(k_smooth_grad)
-                        }
-#undef SG_LAUNCH
-                    }
-                    grid.x -= 1;
-                    grid.y = unsigned(sa.nSeg);
-                    if (grid.x == 0)
-                    {
-                        return;
-                    }
-                    prof(c, "k_smooth_vec");
-                }
-                if (halfNext)
-                {
-                    hipLaunchKernelGGL((k_smooth_vec<true>), grid, dim3(nt), ldsB, c->stream, sa, fullMask);
-                }
-                else
-                {
-                    hipLaunchKernelGGL((k_smooth_vec<false>), grid, dim3(nt), ldsB, c->stream, sa, fullMask);
-                }
-            };
-            const int nSegMax = std::max(nSeg, wantGrad ? nSegG : nSeg);
-            // (the repair flags are zero here: set by k_smooth_verify, taken down by the repair launch that reads them)
-            launchSv(dim3(d, nSeg, nF));
-            LAUNCHCHK(c, "k_smooth_vec");
-            if (nSegMax > 1)
-            {
-                // the segments' hand-overs, bit for bit; planes with a difference are recomputed as one chain
-                hipLaunchKernelGGL(k_smooth_verify, dim3(nSegMax - 1, d, nF), dim3(256), 0, c->stream, (const float*)c->d_specState, (const float*)c->d_trueState,
-                    rs.h, sa.segStride, d, c->d_redo, c->opt.smoothForceRedo, nSeg, wantGrad ? p.colorChn : -1, nSegG);
-                LAUNCHCHK(c, "k_smooth_verify");
-                if (c->opt.countRepairs)
-                {
-                    std::vector<int32_t> fl(size_t(nF) * d);
-                    HIPCHK(c, hipMemcpyAsync(fl.data(), c->d_redo, fl.size() * 4, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    c->repairs[0] += int64_t(fl.size());
-                    for (int32_t v : fl)
-                    {
-                        c->repairs[1] += v != 0;
-                    }
-                }
-                sa.segW = rs.w;
-                sa.warm = 0;
-                sa.nSeg = 1;
-                sa.redo = c->d_redo;
-                launchSv(dim3(d, 1, nF));
-                LAUNCHCHK(c, "k_smooth_vec(repair)");
-            }
-        }
-        colorDone = true;
-    }
-    else if (p.colorSmooth > 0)
-    {
-        if ((rc = launchSmooth(c, img, rs.sm, c->d_realJobs + k, 1, d, rs.h, img_fs, int64_t(d) * np, nF, pColor, true)))
-        {
-            return rc;
-        }
-    }
-    else
-    {
-        hipLaunchKernelGGL(k_copy_planes, dim3(cdiv(np * d, 256), 1, nF), dim3(256), 0, c->stream, img, rs.sm,
-            (const SmoothJob*)(c->d_realJobs + k), img_fs, int64_t(d) * np);
-        LAUNCHCHK(c, "k_copy_planes");
-    }
-    return ACF_HIP_OK;
-}
-
-// gradMag, convTri(M), gradMagNorm, gradHist and the shrunk channels of a real scale (chnsCompute.cpp:263-331, addChn :340-370)
-int PyramidRun::gradientChannels(size_t k, const SmoothOut& so)
-{
-    int rc;
-    RealScale& rs = c->real[k];
-    const int64_t np = int64_t(rs.h) * rs.w;
-    const bool gradFused = so.gradFused, gradBlocked = so.gradBlocked, triXFused = so.triXFused;
-    ChnsArgs a{};
+    const bool grad = p.gradMagEnabled || p.gradHistEnabled;
+    const bool moWithImage = d_in == 5 && k == 0; // (five planes: M, O came with the image)
+    ScalePlan sp;
+    sp.fuseSm = p.colorSmooth > 0 && p.colorEnabled && !c->opt.taps && c->opt.fusedSmooth && shrink == 4 && rs.h % 4 == 0 && rs.w % 4 == 0 && rs.w >= 16 &&
+        rs.h / 4 <= SV_MAXW * SV_OWN && img_fs % 4 == 0 && np % 4 == 0 && (uintptr_t(img) & 15) == 0;
+    ChnsArgs& a = sp.a;
     a.sm = rs.sm;
     a.M = rs.M;
     a.S = rs.S;
@@ -631,7 +409,7 @@ int PyramidRun::gradientChannels(size_t k, const SmoothOut& so)
     a.w = rs.w;
     a.d = d;
     a.colorEnabled = p.colorEnabled;
-    a.colorDone = so.colorDone ? 1 : 0;
+    a.colorDone = sp.fuseSm ? 1 : 0;
     a.magEnabled = p.gradMagEnabled;
     a.histEnabled = p.gradHistEnabled;
     a.nOrients = p.nOrients;
@@ -640,7 +418,235 @@ int PyramidRun::gradientChannels(size_t k, const SmoothOut& so)
     a.hardBin = p.softBin < 0;
     a.normConst = float(p.normConst);
     a.rq_y = shrinkGainY(shrink);
-    // M, O and U of this scale in 64 x 16 blocks when every kernel that touches them is the vector form (triPlan)
+    // M, O and U of this scale in 64 x 16 blocks when every kernel that touches them is the vector form
+    const bool gradVec = rs.h % 4 == 0 && np % 4 == 0;
+    sp.fuseCells = shrink == 4 && !c->opt.taps;
+    sp.blocked = grad && p.normRad && !moWithImage &&
+        triPlan(rs.M, rs.U, rs.h, rs.w, p.normRad, np, sp.fuseCells ? &a : nullptr, rs.uFloats, rs.moFloats, gradVec).blocked;
+    if (!sp.fuseSm)
+    {
+        return sp;
+    }
+    // k_smooth_vec: smoothing + the level's colour channels (+ the next real scale's image when it is an exact half of this one) from
+    // registers; full-resolution smoothed planes are written only where something still reads them
+    sp.halfNext = k + 1 < c->real.size() && srcIdx[k + 1] == int(k) && c->real[k + 1].resampled && [&] {
+        const ResampleDesc& nd = c->h_descs[c->real[k + 1].descIndex];
+        return nd.xmode == RS_EXACT && nd.ymode == RS_EXACT && nd.xk == 2 && nd.yk == 2 && nd.ha == rs.h && nd.wa == rs.w;
+    }();
+    bool needFullAll = false;
+    for (size_t m = k + 1; m < c->real.size(); m++)
+    {
+        if (srcIdx[m] == int(k) && !(m == k + 1 && sp.halfNext))
+        {
+            needFullAll = true;
+        }
+    }
+    sp.nt = cdiv(rs.h / 4, SV_OWN) * 64; // a wave owns SV_OWN row quads and shadows SV_K of each neighbour
+    // the gradient plane's chain also emits gradMag (k_smooth_grad): its smoothed plane is then written only where a later scale is
+    // resampled from it, and k_grad_mag_vec does not run for this scale.  Where it pays (measured at 1080p, 3 x 96 frames: +4 % frames/s
+    // with scale 0 fused, +2 % with every scale; one frame alone 1.21 -> 1.61 / 2.40 ms): the gradient work rides on a chain of column
+    // steps, so it needs many chains (frames x segments) and a plane big enough for the saved round trip to matter.  A/B: the variables.
+    const int64_t gradMinPx = int64_t(1) << 20;
+    const int gradMinF = 16;
+    sp.wantGrad = grad && gradVec && !moWithImage && (c->opt.fusedGrad >= 2 || (c->opt.fusedGrad == 1 && np >= gradMinPx && nF >= gradMinF));
+    // convTri's x pass on the same chain: running sums have no warm-up, so the gradient plane is then one segment
+    // (96 workgroups for 96 frames: slower alone, faster beside other contexts' kernels — DESIGN.md 3.0)
+    const int triMinF = 64;
+    sp.triXFused = sp.wantGrad && sp.blocked && p.normRad == 5 && rs.w >= 48 && sp.nt <= 512 &&
+        (c->opt.fusedTri >= 2 || (c->opt.fusedTri == 1 && c->opt.sharedDevice && nF >= triMinF));
+    for (int z = 0; z < d; z++)
+    {
+        if (needFullAll || (grad && z == p.colorChn && !sp.wantGrad))
+        {
+            sp.fullMask |= 1u << z;
+        }
+    }
+    // column segments: as many as give a launch ~6 waves per SIMD (a plane is a chain of column steps with nt / 64 waves), each at least
+    // 4 warm-ups long; one segment = the plain recursion.  `planesOf`: planes in the launch
+    sp.warm = std::max(16, c->opt.smoothWarm);
+    auto segmentsFor = [&](int planesOf, int& segW_) {
+        int n = c->opt.smoothSegments;
+        if (n == 0 && c->opt.sharedDevice && nF >= 64)
+        {
+            n = 1; // (beside other contexts: the plain chain — no warm-up columns, nothing to verify or repair)
+        }
+        if (n == 0)
+        {
+            const int64_t waves = int64_t(std::max(planesOf, 1)) * nF * (sp.nt / 64);
+            n = int(std::min<int64_t>((6 * 1024 + waves - 1) / waves, rs.w / (4 * sp.warm)));
+        }
+        n = std::max(1, std::min(n, std::min(c->segCap, rs.w / 16)));
+        segW_ = cdiv(cdiv(rs.w, n), 16) * 16;
+        return cdiv(rs.w, segW_);
+    };
+    // the two launches cut their planes on their own: the gradient plane's launch has a third of the chains (more segments), the
+    // other planes' launch two thirds
+    if (!sp.wantGrad)
+    {
+        sp.nSeg = sp.nSegG = segmentsFor(d, sp.segW);
+        sp.segWG = sp.segW;
+    }
+    else
+    {
+        if (sp.triXFused)
+        {
+            sp.nSegG = 1;
+            sp.segWG = cdiv(rs.w, 16) * 16;
+        }
+        else
+        {
+            sp.nSegG = segmentsFor(1, sp.segWG);
+        }
+        sp.nSeg = sp.nSegG;
+        sp.segW = sp.segWG;
+        if (d > 1)
+        {
+            sp.nSeg = segmentsFor(d - 1, sp.segW);
+        }
+    }
+    sp.segStride = std::max(sp.nSeg, sp.nSegG);
+    sp.ldsB = size_t(2) * SV_MAXW * 2 * SV_K * 4 * sizeof(float);
+    sp.ldsG = sp.ldsB + size_t(GM_ACOS_N) * sizeof(float) + (c->opt.arith ? size_t(X86_GM_N) * sizeof(uint2) : 0); // (+ gradMag's table pairs, option "arith")
+    return sp;
+}
+
+int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, const ScalePlan& sp)
+{
+    int rc;
+    RealScale& rs = c->real[k];
+    const int64_t np = int64_t(rs.h) * rs.w;
+    // convTri(I, I, pColor.smooth, 1) in place (chnsCompute.cpp:239)
+    if (!sp.fuseSm)
+    {
+        if (p.colorSmooth > 0)
+        {
+            return launchSmooth(c, img, rs.sm, c->d_realJobs + k, 1, d, rs.h, img_fs, int64_t(d) * np, nF, pColor, true);
+        }
+        hipLaunchKernelGGL(k_copy_planes, dim3(cdiv(np * d, 256), 1, nF), dim3(256), 0, c->stream, img, rs.sm, (const SmoothJob*)(c->d_realJobs + k), img_fs,
+            int64_t(d) * np);
+        LAUNCHCHK(c, "k_copy_planes");
+        return ACF_HIP_OK;
+    }
+    SmoothVecArgs sa{};
+    sa.in = img;
+    sa.in_fs = img_fs;
+    sa.in_ps = np;
+    sa.sm = rs.sm;
+    sa.sm_fs = int64_t(d) * np;
+    sa.sm_ps = np;
+    sa.chns = c->d_chns + pl.raw_off[rs.level];
+    sa.chns_fs = pl.raw_floats;
+    sa.cells = int64_t(rs.h / 4) * (rs.w / 4);
+    sa.h = rs.h;
+    sa.w = rs.w;
+    sa.p = pColor;
+    sa.rq_y = shrinkGainY(shrink);
+    sa.dump = c->d_dump;
+    if (sp.halfNext)
+    {
+        const RealScale& nx = c->real[k + 1];
+        sa.half = nx.img;
+        sa.half_ps = int64_t(nx.h) * nx.w;
+        sa.half_fs = int64_t(d) * sa.half_ps;
+        sa.rkHalf = c->h_descs[nx.descIndex].rk[0];
+        halfDone[k + 1] = true;
+    }
+    sa.plane0 = 0;
+    sa.nPlanes = d;
+    sa.segW = sp.segW;
+    sa.warm = sp.warm;
+    sa.nSeg = sp.nSeg;
+    sa.segStride = sp.segStride;
+    sa.specState = c->d_specState;
+    sa.trueState = c->d_trueState;
+    sa.redo = nullptr;
+    sa.skipZ = -1;
+    if (sp.wantGrad)
+    {
+        sa.skipZ = p.colorChn;
+        sa.gM = rs.M;
+        sa.gO = rs.O;
+        sa.acos = c->d_acos;
+        sa.mo_fs = sp.blocked ? moBlockedFloats(rs.h, rs.w) : np;
+        sa.nybM = sp.blocked ? (rs.h + 15) / 16 : 0;
+        sa.full = p.full;
+        if (sp.triXFused)
+        {
+            sa.tU = rs.U;
+            sa.u_fs = uBlockedFloats(rs.h, rs.w);
+            sa.nybU = (rs.h + 8 + 15) / 16;
+        }
+    }
+    // the gradient plane's launch (with convTri's x pass on the chain or without, the next scale's half image or not, exact reciprocals
+    // or — option "arith" — one x86 CPU's): first, its chains are the long ones; then the other planes' launch "k_smooth_vec"
+    auto gradArgs = [&](int segW, int nSeg) {
+        SmoothVecArgs g = sa;
+        g.plane0 = p.colorChn;
+        g.skipZ = -1;
+        g.segW = segW;
+        g.nSeg = nSeg;
+        g.x86 = x86T(c);
+        return g;
+    };
+    const SmoothVecKernel gradKernel = smoothGradKernel(sp.triXFused, sp.halfNext, x86T(c) != nullptr), vecKernel = smoothVecKernel(sp.halfNext);
+    const char* gradName = sp.triXFused ? "k_smooth_grad_tri" : "k_smooth_grad";
+    const int nVec = sp.wantGrad ? d - 1 : d;
+    // (the repair flags are zero here: set by k_smooth_verify, taken down by the repair launch that reads them)
+    if (sp.wantGrad)
+    {
+        if ((rc = allowLds(c, reinterpret_cast<const void*>(gradKernel), sp.ldsG)))
+        {
+            return rc;
+        }
+        prof(c, gradName);
+        hipLaunchKernelGGL(gradKernel, dim3(1, sp.nSegG, nF), dim3(sp.nt), sp.ldsG, c->stream, gradArgs(sp.segWG, sp.nSegG), sp.fullMask);
+    }
+    if (nVec > 0)
+    {
+        prof(c, "k_smooth_vec");
+        hipLaunchKernelGGL(vecKernel, dim3(nVec, sp.nSeg, nF), dim3(sp.nt), sp.ldsB, c->stream, sa, sp.fullMask);
+    }
+    LAUNCHCHK(c, "k_smooth_vec");
+    if (sp.segStride == 1)
+    {
+        return ACF_HIP_OK;
+    }
+    // the segments' hand-overs, bit for bit; planes with a difference are recomputed as one chain
+    hipLaunchKernelGGL(k_smooth_verify, dim3(sp.segStride - 1, d, nF), dim3(256), 0, c->stream, (const float*)c->d_specState, (const float*)c->d_trueState,
+        rs.h, sp.segStride, d, c->d_redo, c->opt.smoothForceRedo, sp.nSeg, sp.wantGrad ? p.colorChn : -1, sp.nSegG);
+    LAUNCHCHK(c, "k_smooth_verify");
+    if ((rc = countRepairs(c, c->d_redo, size_t(nF) * d, 0)))
+    {
+        return rc;
+    }
+    sa.segW = rs.w;
+    sa.warm = 0;
+    sa.nSeg = 1;
+    sa.redo = c->d_redo;
+    if (sp.wantGrad)
+    {
+        prof(c, gradName);
+        if (sp.nSegG > 1) // (else nothing to repair: the plane was one chain)
+        {
+            hipLaunchKernelGGL(gradKernel, dim3(1, 1, nF), dim3(sp.nt), sp.ldsG, c->stream, gradArgs(rs.w, 1), sp.fullMask);
+        }
+    }
+    if (nVec > 0)
+    {
+        prof(c, "k_smooth_vec");
+        hipLaunchKernelGGL(vecKernel, dim3(nVec, 1, nF), dim3(sp.nt), sp.ldsB, c->stream, sa, sp.fullMask);
+    }
+    LAUNCHCHK(c, "k_smooth_vec(repair)");
+    return ACF_HIP_OK;
+}
+
+// gradMag, convTri(M), gradMagNorm, gradHist and the shrunk channels of a real scale (chnsCompute.cpp:263-331, addChn :340-370)
+int PyramidRun::gradientChannels(size_t k, const ScalePlan& sp)
+{
+    int rc;
+    RealScale& rs = c->real[k];
+    const int64_t np = int64_t(rs.h) * rs.w;
+    ChnsArgs a = sp.a;
     if (d_in == 5 && k == 0)
     {
         // chnsCompute.cpp:219-226,265-269 (chnsPyramid.cpp:318-322): the first real scale takes the M, O planes that came with the image —
@@ -653,54 +659,19 @@ int PyramidRun::gradientChannels(size_t k, const SmoothOut& so)
         a.doNorm = 0;
         return launchChns(c, a, shrink, nF);
     }
-    const bool gradVec = rs.h % 4 == 0 && np % 4 == 0;
-    const bool fuseCells = shrink == 4 && !c->opt.taps; // k_triy_chns; else S is written and k_chns normalises
     a.x86 = x86T(c);
-    const bool wantTri = (p.gradMagEnabled || p.gradHistEnabled) && p.normRad;
-    const bool blockedMO = wantTri &&
-        triPlan(rs.M, rs.U, rs.h, rs.w, p.normRad, np, fuseCells ? &a : nullptr, rs.uFloats, rs.moFloats, gradVec).blocked;
-    if (gradFused)
-    {
-        // (M and O are there already)
-        if (gradBlocked != blockedMO)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "k_smooth_grad: M / O layout differs from the y pass's");
-        }
-    }
-    else if (p.gradMagEnabled || p.gradHistEnabled)
+    if ((p.gradMagEnabled || p.gradHistEnabled) && !sp.wantGrad) // (with it, M and O are there already)
     {
         prof(c, "k_grad_mag");
-        if (gradVec)
+        if (rs.h % 4 == 0 && np % 4 == 0)
         {
             // 16 bytes per lane, persistent grid (one 16-wave workgroup per CU around the 80 KB LDS table), grid-stride over (frame, strip, row quad)
             const int64_t items = int64_t(cdiv(rs.w, GMV_XT)) * (rs.h / 4) * nF;
             const int gmvMax = 256;
             const int blocks = int(std::min<int64_t>(gmvMax, (items + GMV_BLOCK - 1) / GMV_BLOCK));
-            const float* gsrc = rs.sm + int64_t(p.colorChn) * np;
-            const uint32_t* xt = x86T(c);
-#define GMV_LAUNCH(BL_, AR_, FS_, NYB_)                                                                                                     \
-    hipLaunchKernelGGL((k_grad_mag_vec<BL_, AR_>), dim3(blocks), dim3(GMV_BLOCK), 0, c->stream, gsrc, rs.M, rs.O, (const float*)c->d_acos, rs.h, rs.w, p.full, \
-        int64_t(d) * np, FS_, nF, NYB_, xt);
-            if (blockedMO)
-            {
-                if (xt)
-                {
-                    GMV_LAUNCH(true, true, moBlockedFloats(rs.h, rs.w), (rs.h + 15) / 16)
-                }
-                else
-                {
-                    GMV_LAUNCH(true, false, moBlockedFloats(rs.h, rs.w), (rs.h + 15) / 16)
-                }
-            }
-            else if (xt)
-            {
-                GMV_LAUNCH(false, true, np, 0)
-            }
-            else
-            {
-                GMV_LAUNCH(false, false, np, 0)
-            }
-#undef GMV_LAUNCH
+            hipLaunchKernelGGL(gradMagVecKernel(sp.blocked, a.x86 != nullptr), dim3(blocks), dim3(GMV_BLOCK), 0, c->stream,
+                (const float*)(rs.sm + int64_t(p.colorChn) * np), rs.M, rs.O, (const float*)c->d_acos, rs.h, rs.w, p.full, int64_t(d) * np,
+                sp.blocked ? moBlockedFloats(rs.h, rs.w) : np, nF, sp.blocked ? (rs.h + 15) / 16 : 0, a.x86);
         }
         else
         {
@@ -718,21 +689,13 @@ int PyramidRun::gradientChannels(size_t k, const SmoothOut& so)
     {
         // convTri(M, normRad): x running sums, then the y pass — fused with the channel cells when the level allows it
         // (S then never reaches HBM), else S is written for k_chns
-        if ((rc = launchTri(c, rs.M, rs.U, rs.S, rs.h, rs.w, p.normRad, np, nF, fuseCells ? &a : nullptr, &cellsDone, rs.uFloats, rs.moFloats,
-                 blockedMO, triXFused)))
+        if ((rc = launchTri(c, rs.M, rs.U, rs.S, rs.h, rs.w, p.normRad, np, nF, sp.fuseCells ? &a : nullptr, &cellsDone, rs.uFloats, rs.moFloats,
+                 sp.blocked, sp.triXFused)))
         {
             return rc;
         }
     }
-    if (cellsDone)
-    {
-        return ACF_HIP_OK;
-    }
-    if ((rc = launchChns(c, a, shrink, nF)))
-    {
-        return rc;
-    }
-    return ACF_HIP_OK;
+    return cellsDone ? ACF_HIP_OK : launchChns(c, a, shrink, nF);
 }
 
 int PyramidRun::joinScales()
@@ -835,53 +798,29 @@ int PyramidRun::levels(int f0, int nLF)
             lsa.spec = c->d_lvSpec;
             lsa.tru = c->d_lvTrue;
             lsa.redo = nullptr;
-            dim3 lgrid(pl.nChns, cdiv(nLF, LEVEL_WAVES), nAll * nSegL), lblock(64 * LEVEL_WAVES);
-#define LVALL_LAUNCH(OUT)                                                                                                   \
-if (nSegL > 1)                                                                                                          \
-{                                                                                                                       \
-    if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_level_all<OUT, 1>), ldsL)))                                  \
-        return rc;                                                                                                      \
-    hipLaunchKernelGGL((k_level_all<OUT, 1>), lgrid, lblock, ldsL, c->stream, (const float*)chnsF, pyrF, rawOut, ljobs, dd, \
-        (const int32_t*)c->d_it, (const float*)c->d_ft, pl.nChns, pl.raw_floats, pl.pyr_floats, pS, c->d_dump, nLF, ra, lsa); \
-    hipLaunchKernelGGL(k_level_verify, dim3(nAll * nSegL, pl.nChns, nLF), dim3(64), 0, c->stream, (const float*)c->d_lvSpec,  \
-        (const float*)c->d_lvTrue, ljobs, lsa, pl.nChns, c->d_lvRedo, c->opt.smoothForceRedo);                           \
-    if (c->opt.countRepairs)                                                                                            \
-    {                                                                                                                   \
-        std::vector<int32_t> fl(size_t(nLF) * nAll * pl.nChns);                                                         \
-        HIPCHK(c, hipMemcpyAsync(fl.data(), c->d_lvRedo, fl.size() * 4, hipMemcpyDeviceToHost, c->stream));             \
-        HIPCHK(c, hipStreamSynchronize(c->stream));                                                                     \
-        c->repairs[2] += int64_t(fl.size());                                                                            \
-        for (int32_t v : fl)                                                                                            \
-        {                                                                                                               \
-            c->repairs[3] += v != 0;                                                                                    \
-        }                                                                                                               \
-    }                                                                                                                   \
-    lsa.nSeg = 1;                                                                                                       \
-    lsa.redo = c->d_lvRedo;                                                                                             \
-    hipLaunchKernelGGL((k_level_all<OUT, 1>), dim3(pl.nChns, cdiv(nLF, LEVEL_WAVES), nAll), lblock, ldsL, c->stream,    \
-        (const float*)chnsF, pyrF, rawOut, ljobs, dd, (const int32_t*)c->d_it, (const float*)c->d_ft, pl.nChns,         \
-        pl.raw_floats, pl.pyr_floats, pS, c->d_dump, nLF, ra, lsa);                                                     \
-}                                                                                                                       \
-else                                                                                                                    \
-{                                                                                                                       \
-    if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_level_all<OUT, 0>), ldsL)))                                  \
-        return rc;                                                                                                      \
-    hipLaunchKernelGGL((k_level_all<OUT, 0>), lgrid, lblock, ldsL, c->stream, (const float*)chnsF, pyrF, rawOut, ljobs, dd, \
-        (const int32_t*)c->d_it, (const float*)c->d_ft, pl.nChns, pl.raw_floats, pl.pyr_floats, pS, c->d_dump, nLF, ra, lsa); \
-}
-            if (emitRank && emitF32)
+            const LevelAllKernel lk = levelAllKernel(emitF32, emitRank, nSegL > 1);
+            if ((rc = allowLds(c, reinterpret_cast<const void*>(lk), ldsL)))
             {
-                LVALL_LAUNCH(LO_F32 | LO_RANK);
+                return rc;
             }
-            else if (emitRank)
+            auto launchAll = [&](int nz) {
+                hipLaunchKernelGGL(lk, dim3(pl.nChns, cdiv(nLF, LEVEL_WAVES), nz), dim3(64 * LEVEL_WAVES), ldsL, c->stream, (const float*)chnsF, pyrF, rawOut,
+                    ljobs, dd, (const int32_t*)c->d_it, (const float*)c->d_ft, pl.nChns, pl.raw_floats, pl.pyr_floats, pS, c->d_dump, nLF, ra, lsa);
+            };
+            launchAll(nAll * nSegL);
+            if (nSegL > 1)
             {
-                LVALL_LAUNCH(LO_RANK);
+                // the segments' hand-overs, bit for bit; level planes with a difference are recomputed as one chain
+                hipLaunchKernelGGL(k_level_verify, dim3(nAll * nSegL, pl.nChns, nLF), dim3(64), 0, c->stream, (const float*)c->d_lvSpec,
+                    (const float*)c->d_lvTrue, ljobs, lsa, pl.nChns, c->d_lvRedo, c->opt.smoothForceRedo);
+                if ((rc = countRepairs(c, c->d_lvRedo, size_t(nLF) * nAll * pl.nChns, 2)))
+                {
+                    return rc;
+                }
+                lsa.nSeg = 1;
+                lsa.redo = c->d_lvRedo;
+                launchAll(nAll);
             }
-            else
-            {
-                LVALL_LAUNCH(LO_F32);
-            }
-#undef LVALL_LAUNCH
             LAUNCHCHK(c, "k_level_all");
             if (lvTurns && (rc = turnEnd(c, 1, lvChain)))
             {
@@ -894,37 +833,13 @@ else                                                                            
             const auto& g = *git;
             hipStream_t lst = (nSide && c->evFork) ? c->side[gi % nSide] : c->stream;
             dim3 grid(pl.nChns, g.count, cdiv(nLF, LEVEL_WAVES)), block(64 * LEVEL_WAVES);
-#define LV_LAUNCH(RR, MM)                                                                                                         \
-    hipLaunchKernelGGL((k_level<RR, MM>), grid, block, 0, lst, (const float*)chnsF, pyrF, rawOut, ljobs + g.first, dd, \
-        (const int32_t*)c->d_it, (const float*)c->d_ft, pl.nChns, pl.raw_floats, pl.pyr_floats, pS, c->d_dump, nLF);
-#define LV_MODES(RR)                                  \
-    switch (g.mode)                                   \
-    {                                                 \
-        case LM_REAL: LV_LAUNCH(RR, LM_REAL); break;  \
-        case LM_DD: LV_LAUNCH(RR, LM_DD); break;      \
-        default: LV_LAUNCH(RR, LM_UU); break;         \
-    }
-            switch (g.R)
+            const LevelKernel lk = levelKernel(g.R, g.mode);
+            if (!lk)
             {
-                case 1: LV_MODES(1); break;
-                case 2: LV_MODES(2); break;
-                case 3: LV_MODES(3); break;
-                case 4: LV_MODES(4); break;
-                case 5: LV_MODES(5); break;
-                case 6: LV_MODES(6); break;
-                case 7: LV_MODES(7); break;
-                case 8: LV_MODES(8); break;
-                default:
-                    // nine rows per lane: the full-resolution level of a 4K frame (540 cells); a real level's copy + smoothing only
-                    if (g.R != LEVEL_MAX_R_REAL || g.mode != LM_REAL)
-                    {
-                        return fail(c, ACF_HIP_E_UNSUPPORTED, "pyramid: level taller than the level kernels' rows per lane");
-                    }
-                    LV_LAUNCH(9, LM_REAL);
-                    break;
+                return fail(c, ACF_HIP_E_UNSUPPORTED, "pyramid: level taller than the level kernels' rows per lane");
             }
-#undef LV_MODES
-#undef LV_LAUNCH
+            hipLaunchKernelGGL(lk, grid, block, 0, lst, (const float*)chnsF, pyrF, rawOut, ljobs + g.first, dd, (const int32_t*)c->d_it, (const float*)c->d_ft,
+                pl.nChns, pl.raw_floats, pl.pyr_floats, pS, c->d_dump, nLF);
             LAUNCHCHK(c, "k_level");
         }
         if (nSide && c->evFork)
@@ -936,12 +851,9 @@ else                                                                            
             }
         }
     }
-    // ---- smooth every plane of every level into the fused, padded pyramid (chnsPyramid.cpp:399-435)
-    if (waveSmooth)
-    {
-    }
     else if (p.smooth > 0)
     {
+        // ---- smooth every plane of every level into the fused, padded pyramid (chnsPyramid.cpp:399-435)
         const float pS = float(12.0 / p.smooth / (p.smooth + 2.0) - 2.0);
         if ((rc = launchSmooth(c, chnsF, pyrF, c->d_finalJobs, nL, pl.nChns, c->finalMaxH, pl.raw_floats, pl.pyr_floats, nLF, pS, true)))
         {
