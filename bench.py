@@ -2,7 +2,7 @@
 """bench.py — detector FPS @1080p, 8 scales/octave, FACE80 model on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--contexts C] [--config {2,4,5}] [--frames-total T]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (acf_hip_run: chnsPyramid + acfDetect, then the device-side export of the
 detection records) over batches of synthetic frames that are already resident in HBM.  With N > 1 (launched by
@@ -13,8 +13,16 @@ BASELINE.json's cfg 3 as worded: T frames per step shared by the N GPUs (T/N per
 Prints ONE JSON line on rank 0 (contract in the task description) with
  - value: whole-job frames/s,
  - roofline: the dominant kernel's algorithmic bytes per launch over its average launch duration INSIDE the timed region
-   (HIP events on the launch stream), the same kernel alone on the GPU under `solo`, the whole path under `path_*`,
- - latency_ms_batch1: one frame, one context, submit to synchronise,
+   (HIP events on the launch stream), the whole path under `path_*`.
+
+A plain run does only that: set up, warm up, time the K steps, write --dump-outputs, print the line.  --full also runs,
+after the timed steps, everything else the line can report (the --no-* flags still leave parts out):
+ - value_repeats: the same K steps timed twice more,
+ - roofline.solo: the dominant kernel alone on the GPU (without it, roofline.kernel is the timed region's largest),
+   roofline.stream_copy_GBps: a 256 MiB device copy,
+ - config.keep_pyramid_fps, config.ref_arith_fps (+ its oracle check), latency_ms_batch1, config.cfg3_64_frames_per_step_fps_1gpu,
+   config.batch8_fps_1gpu / batch8_pipelined_fps_1gpu: other calls, tiers and batch sizes on the same contexts,
+ - verified_frames: three timed frames against the oracle,
  - cpu_baseline: the oracle (CPU restatement) on a bounded sample of the same workload, rank 0 at N=1 only.
 """
 import argparse
@@ -241,6 +249,26 @@ def cpu_baseline(model, frames_np, H, W, budget_s=12.0):
     return out
 
 
+def stream_copy_gbps(dev):
+    """What this GPU delivers to a plain stream: a device-to-device copy of 256 MiB (read + write), outside the timed region, in GB/s —
+    the practical ceiling beside the 8 TB/s of `peak` (profiles/ubench/copy_bw.py: ~4.8 TB/s).  None if it cannot run."""
+    import torch
+    try:
+        cx = torch.empty(1 << 26, dtype=torch.float32, device=dev)
+        cy = torch.empty_like(cx)
+        for _ in range(2):
+            cy.copy_(cx)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(8):
+            cy.copy_(cx)
+        e1.record()
+        torch.cuda.synchronize()
+        return round(8 * 2 * cx.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
+    except Exception:  # (a reported extra, never a reason to lose the line)
+        return None
+
+
 DUMP_LIMIT = 64 << 20  # bytes of .npy payload --dump-outputs may write
 
 
@@ -340,6 +368,8 @@ def main():
     ap.add_argument("--no-verify", action="store_true", help="skip the post-run check of three timed frames against the oracle")
     ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what the last timed step exported "
                     "(every frame's detections: counts, boxes, scores, levels) as DIR/<name>.npy, float32 / float64, at most %d MB in all" % (DUMP_LIMIT >> 20))
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the extra measurements and checks (repeats, solo kernels, "
+                    "copy rate, other tiers and batch sizes, latency, oracle self-check, CPU baseline); a plain run times the headline only")
     ap.add_argument("--dry-launch", action="store_true", help="launch plumbing only (spawn, rendezvous, max-over-ranks clock, per-rank gather) "
                     "with no detector work: runs without a GPU over gloo (tests/test_bench_launch.py); never a measurement")
     args = ap.parse_args()
@@ -492,7 +522,7 @@ def main():
     if not args.no_profile:
         prof_first = [d_.profile() for d_ in dets]  # (the per-kernel figures stay those of the first region)
     repeat_fps = [C * B * world * args.steps / dt]
-    for _ in range(0 if args.no_repeats else 2):
+    for _ in range(2 if args.full and not args.no_repeats else 0):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -519,6 +549,7 @@ def main():
             for k_, (ms_, n_) in pf.items():
                 a_ = prof.get(k_, (0.0, 0))
                 prof[k_] = (a_[0] + ms_, a_[1] + n_)
+    if args.full and not args.no_profile:
         # outside the timed region: the same launches with one context alone on the machine, so that a kernel's own speed
         # can be read next to its speed while sharing the chip with the other contexts' kernels
         with torch.cuda.stream(streams[0]):
@@ -527,7 +558,7 @@ def main():
         dets[0].synchronize()
         solo = dets[0].profile()
     keep_fps = None
-    if world == 1 and not args.keep_pyramid and args.config != 5 and not args.no_latency:
+    if args.full and world == 1 and not args.keep_pyramid and args.config != 5 and not args.no_latency:
         # the chnsPyramid-returning call beside the headline's detection-only call: the same steps with the float pyramid
         # materialised as well (option keep_pyramid = 1), timed the same way; reported in config, never `value`
         for d_ in dets:
@@ -549,7 +580,7 @@ def main():
             for d_ in dets:
                 d_.profile()  # these launches are not the timed region's
     ref_fps, ref_verified = None, None
-    if world == 1 and not args.ref_arith and not args.keep_pyramid and args.config != 5 and not args.no_latency:
+    if args.full and world == 1 and not args.ref_arith and not args.keep_pyramid and args.config != 5 and not args.no_latency:
         # the reference-arithmetic tier beside the headline (option arith = 1 with the committed build-host tables: the reference's own
         # rsqrtps / rcpps bits): the same steps, timed the same way, one frame per context checked against the
         # oracle's table tier; reported in config, never `value`
@@ -577,7 +608,7 @@ def main():
         if not args.no_profile:
             for d_ in dets:
                 d_.profile()
-    if rank == 0 and not args.no_latency:
+    if args.full and rank == 0 and not args.no_latency:
         # one frame through one context, submit -> results on the device (cfg 2 is worded "single frame")
         lat = []
         dets[0].set_option("scale_streams", 1)  # one frame alone: the scales' chains run beside each other
@@ -598,13 +629,13 @@ def main():
             dets[0].profile()
     counts = pipes[0].rec[(pipes[0].k - 1) & 1][:, 0].cpu().numpy()
     verified = None
-    if rank == 0 and not args.no_verify and args.config != 5:
+    if args.full and rank == 0 and not args.no_verify and args.config != 5:
         # the timed contexts' own last records (still in their record buffers), three frames of three different contexts
         recs = [pipes[i].rec[(pipes[i].k - 1) & 1].cpu().numpy() for i in range(C)]
         picks = [(i % C, (7 + 31 * i) % B) for i in range(3)]
         verified = verify_frames(model, H, W, [frames[i * B:(i + 1) * B] for i in range(C)], recs, args.cap, nms_params, picks, ref_arith=args.ref_arith)
     strong64 = None
-    if rank == 0 and world == 1 and args.config == 2 and not args.no_latency and not args.frames_total and C * B >= 64:
+    if args.full and rank == 0 and world == 1 and args.config == 2 and not args.no_latency and not args.frames_total and C * B >= 64:
         # BASELINE cfg 3 as worded (64 frames per step) on this one GPU: 2 contexts x 32 frames, same contexts and buffers
         c2 = min(C, 2)
         per = 64 // c2
@@ -628,7 +659,7 @@ def main():
                 for d_ in dets:
                     d_.profile()
     batch8 = batch8_pipe = None
-    if rank == 0 and world == 1 and args.config == 2 and not args.no_latency and not args.frames_total and B >= 8:
+    if args.full and rank == 0 and world == 1 and args.config == 2 and not args.no_latency and not args.frames_total and B >= 8:
         # one GPU's share of BASELINE cfg 3 AS WORDED (64 frames per step over 8 GPUs = 8 frames per GPU and step): one context,
         # 8 frames per call, the scales' chains beside each other, the call replayed as one HIP graph; submit -> synchronise per step
         dets[0].set_option("scale_streams", 1)
@@ -809,25 +840,9 @@ def main():
             roof.update({"path_bytes_per_frame": b_frame, "path_achieved": path, "path_frac": path / HBM_PEAK_GBS,
                          "path_rank_bytes_per_frame": b_frame_rank, "path_frac_rank_bytes": path * b_frame_rank / b_frame / HBM_PEAK_GBS,
                          "note": "per-kernel events disabled: whole path on the wall clock only"})
-        # what this box delivers to a plain stream: a device-to-device copy of 256 MiB (read + write), outside the timed region —
-        # the practical ceiling beside the 8 TB/s of `peak` (profiles/ubench/copy_bw.py: ~4.8 TB/s)
-        try:
-            cx = torch.empty(1 << 26, dtype=torch.float32, device=dev)
-            cy = torch.empty_like(cx)
-            for _ in range(2):
-                cy.copy_(cx)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(8):
-                cy.copy_(cx)
-            e1.record()
-            torch.cuda.synchronize()
-            roof["stream_copy_GBps"] = round(8 * 2 * cx.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
-            del cx, cy
-        except Exception:  # (a reported extra, never a reason to lose the line)
-            roof["stream_copy_GBps"] = None
+        roof["stream_copy_GBps"] = stream_copy_gbps(dev) if args.full else None
         out["roofline"] = roof
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model, base_np, H, W)
         else:
             out["cpu_baseline"] = None

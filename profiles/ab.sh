@@ -7,7 +7,7 @@ out=${OUT:-gpurun_out/ab.txt}
 K=${KERNELS:-k_cascade_tile,k_level(fused),k_rank,k_smooth_vec}
 for e in "$@"; do
   echo "== $e" >> $out
-  env $e python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-latency $BENCH_FLAGS 2>/dev/null | K="$K" python -c "
+  env $e python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-latency $BENCH_FLAGS 2>/dev/null | K="$K" python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s=d['roofline']['solo']['kernels_ms_per_launch']

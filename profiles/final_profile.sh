@@ -4,7 +4,7 @@ set -x
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/final; rm -rf $OUT; mkdir -p $OUT
 cd $R
-python bench.py --steps 8 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 8 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt -o trace -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $OUT/kt_bench.log 2>&1
 python profiles/summarize.py $OUT/kt/trace_results.db > $OUT/kernel_stats.md
 for C in FETCH_SIZE WRITE_SIZE; do

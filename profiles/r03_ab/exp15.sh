@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 : > gpurun_out/exp15.txt
 for e in "A=1" "ACF_HIP_RTILE_NW=4" "ACF_HIP_RTILE_NW=4 ACF_HIP_RTILE_TR=16" "ACF_HIP_RTILE_WG=2" "ACF_HIP_RTILE_WG=4" "A=2" "ACF_HIP_RTILE_NW=4 ACF_HIP_RTILE_WG=4"; do
   echo "== $e" >> gpurun_out/exp15.txt
-  env $e python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-verify --no-latency 2>/dev/null | python -c "
+  env $e python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-verify --no-latency 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -5,7 +5,7 @@ tail -5 gpurun_out/exp9_pytest.log
 : > gpurun_out/exp9.txt
 for e in "ACF_HIP_LIB=acf_amd/libacf_hip_base.so" "A=1" "ACF_HIP_FUSED_GRAD=2" "ACF_HIP_LIB=acf_amd/libacf_hip_base.so" "A=2" "ACF_HIP_FUSED_GRAD_MINPX=400000"; do
   echo "== $e" >> gpurun_out/exp9.txt
-  env $e python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-verify 2>/dev/null | python -c "
+  env $e python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-verify 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s=d['roofline']['solo']['kernels_ms_per_launch']

@@ -5,10 +5,10 @@ set -x
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/r03; rm -rf $OUT; mkdir -p $OUT
 cd $R
-python bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt -o trace -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $OUT/kt_bench.log 2>&1
 python profiles/summarize.py $OUT/kt/trace_results.db > $OUT/kernel_stats.md
-ACF_HIP_SCALES_SERIAL=1 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kts -o trace -- python bench.py --contexts 1 --batch 96 --steps 6 --warmup 2 --no-cpu-baseline > $OUT/solo_bench.log 2>&1
+ACF_HIP_SCALES_SERIAL=1 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kts -o trace -- python bench.py --full --contexts 1 --batch 96 --steps 6 --warmup 2 --no-cpu-baseline > $OUT/solo_bench.log 2>&1
 python profiles/summarize.py $OUT/kts/trace_results.db > $OUT/solo_kernel_stats.md
 grep '^{"metric"' $OUT/solo_bench.log | tail -1 > $OUT/solo_bench.json
 for C in FETCH_SIZE WRITE_SIZE; do

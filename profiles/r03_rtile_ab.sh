@@ -5,7 +5,7 @@ out=gpurun_out/r03_rtile_ab.txt
 : > $out
 run() {
   echo "== $*" >> $out
-  env "$@" python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-latency 2>/dev/null | python -c "
+  env "$@" python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-latency 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s=d['roofline']['solo']['kernels_ms_per_launch']

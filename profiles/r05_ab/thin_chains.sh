@@ -1,5 +1,5 @@
 # with one-segment smoothing chains (smooth_segments=1 + fused_tri): every scale fused, scales on their own streams, context counts
-run() { python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-latency --no-verify "$@" 2>/dev/null | tail -1 | python -c "
+run() { python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-latency --no-verify "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print(d.get('value_repeats'))"; }
 B="--opt smooth_segments=1"
 for a in "$B" "$B --opt fused_grad=2 --opt fused_tri=2" "$B --opt scale_streams=1" "$B --opt fused_grad=2 --opt fused_tri=2 --opt scale_streams=1" \

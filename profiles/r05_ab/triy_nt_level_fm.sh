@@ -1,7 +1,7 @@
 # (1) k_triy_chns's M / O / U reads non-temporal (default build) against plain loads (libacf_hip_plainld.so: -DACF_TRIY_PLAIN_LOADS): frames/s and
 #     the kernel's WRITE_SIZE / FETCH_SIZE; (2) k_level_all dispatched frame-group-major (ACF_HIP_LEVEL_FRAME_MAJOR=1)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-run() { python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-latency --no-verify "$@" 2>/dev/null | tail -1 | python -c "
+run() { python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-latency --no-verify "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); s=d['roofline']['solo']['kernels_ms_per_batch']; print(d.get('value_repeats'), {k:round(v,3) for k,v in s.items() if k in ('k_triy_chns','k_level(fused)')})"; }
 for i in 1 2; do
 echo "== nt loads (default)"; run

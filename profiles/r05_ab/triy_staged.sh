@@ -1,7 +1,7 @@
 # k_triy_chns's cells staged in LDS over four steps (64-byte stores; default build) against one 4-byte store per lane, channel and step
 # (libacf_hip_direct.so: -DACF_TRIY_DIRECT): frames/s, the kernel alone, its WRITE_SIZE / FETCH_SIZE
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-run() { python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-latency --no-verify "$@" 2>/dev/null | tail -1 | python -c "
+run() { python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-latency --no-verify "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); s=d['roofline']['solo']['kernels_ms_per_batch']; print(d.get('value_repeats'), {k:round(v,3) for k,v in s.items() if k in ('k_triy_chns','k_level(fused)')})"; }
 for i in 1 2 3; do
 echo "== staged (default)"; run

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B on one box: k_smooth_grad_tri as one workgroup per frame (thin_parts=1) against two row bands per frame (thin_parts=0: auto = 2 at 96 frames)
 out=gpurun_out/ab_thin_parts.txt; : > $out
-run() { echo "== $1" >> $out; python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-latency $1 2>/dev/null | python -c "
+run() { echo "== $1" >> $out; python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-latency $1 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -2,7 +2,7 @@
 # thin-chain sensitivity: duration (s_sleep) and work (idle waves), 3 x 96 frames, one box
 export ACF_HIP_LIB=$GRAFT_REPO_ROOT/acf_amd/libacf_hip_probe.so
 out=gpurun_out/probe.txt; : > $out
-run() { echo "== $1" >> $out; env $1 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-latency 2>/dev/null | python -c "
+run() { echo "== $1" >> $out; env $1 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-latency 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -6,10 +6,10 @@ set -x
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/r06; rm -rf $OUT; mkdir -p $OUT
 cd $R
-python bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt -o trace -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-repeats > $OUT/kt_bench.log 2>&1
 python profiles/summarize.py $OUT/kt/trace_results.db > $OUT/kernel_stats.md
-timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kts -o trace -- python bench.py --contexts 1 --opt shared_device=1 --opt scale_streams=0 --batch 96 --steps 6 --warmup 2 --no-cpu-baseline --no-repeats > $OUT/solo_bench.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kts -o trace -- python bench.py --full --contexts 1 --opt shared_device=1 --opt scale_streams=0 --batch 96 --steps 6 --warmup 2 --no-cpu-baseline --no-repeats > $OUT/solo_bench.log 2>&1
 python profiles/summarize.py $OUT/kts/trace_results.db > $OUT/solo_kernel_stats.md
 grep '^{"metric"' $OUT/solo_bench.log | tail -1 > $OUT/solo_bench.json
 for C in FETCH_SIZE WRITE_SIZE; do
@@ -25,8 +25,8 @@ done
 rm -rf $OUT/kt $OUT/kts $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE $OUT/pmc_sq
 tail -c 1200 $OUT/bench.json; head -16 $OUT/kernel_stats.md | cut -c1-150; head -14 $OUT/solo_kernel_stats.md | cut -c1-150; cat $OUT/pmc_traffic.json | tail -30
 # cfg 4 / cfg 5 lines, the depth cliff, the single-frame latency breakdown
-python bench.py --config 4 --steps 6 --warmup 2 > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err
-python bench.py --config 5 --steps 6 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
+python bench.py --full --config 4 --steps 6 --warmup 2 > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err
+python bench.py --full --config 5 --steps 6 --warmup 2 > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
 python profiles/depth_cliff.py > $OUT/depth_cliff.json 2>/dev/null
 python profiles/latency_breakdown.py > $OUT/latency.json 2>/dev/null
 python profiles/ubench/level_seg_latency.py > $OUT/level_seg_latency.json 2>/dev/null

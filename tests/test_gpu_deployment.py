@@ -106,14 +106,12 @@ def test_the_timed_configuration_as_it_is_timed():
     pool.close()
 
 
-def test_bench_line_contract():
-    """`python bench.py` (a small step: 2 contexts x 8 frames, no CPU leg) prints ONE JSON line with the fields the driver reads: the
-    metric and unit, value = frames of the timed steps / time, the repeats, the roofline block with its kernel, the as-worded figures."""
+def _bench_line(*flags):
+    """`python bench.py` on a small step (2 contexts x 8 frames, no CPU leg) plus `flags`: its one JSON line, parsed."""
     import json
     import subprocess
-    import sys
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--contexts", "2", "--batch", "8", "--no-cpu-baseline"],
-                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--contexts", "2", "--batch", "8", "--no-cpu-baseline"]
+                         + list(flags), cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -121,14 +119,39 @@ def test_bench_line_contract():
     assert d["metric"].startswith("detector FPS @1080p") and d["unit"] == "frames/s" and d["higher_is_better"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "f32"
     assert d["value"] > 0 and abs(d["value"] - 2 * 8 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
-    assert len(d["value_repeats"]) == 3 and d["value_min"] <= d["value_median"] <= d["value_max"]
-    assert d["verified_frames"] == 3
     r = d["roofline"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel"):
         assert k in r, k
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and 0 < r["frac"] < 1
     cfg = d["config"]
     assert "workload" in cfg and cfg["contexts"] == 2 and cfg["frames_per_launch"] == 8
+    return d
+
+
+def test_bench_line_contract():
+    """`python bench.py --full` prints ONE JSON line with the fields the driver reads: the metric and unit, value = frames of the timed
+    steps / time, the repeats, the roofline block with its kernel, the as-worded figures."""
+    d = _bench_line("--full")
+    assert len(d["value_repeats"]) == 3 and d["value_min"] <= d["value_median"] <= d["value_max"]
+    assert d["verified_frames"] == 3
+    assert "solo" in d["roofline"] and d["roofline"]["stream_copy_GBps"] > 0
+    cfg = d["config"]
     assert cfg["batch8_fps_1gpu"] > 0 and cfg["batch8_pipelined_fps_1gpu"] > 0 and d["latency_ms_batch1"] > 0
     assert cfg["ref_arith_fps"] > 0 and cfg["ref_arith_verified_frames"] == 2   # the reference-arithmetic tier beside the headline, self-checked
     assert d["cpu_baseline"] is None or "value" in d["cpu_baseline"]
+
+
+def test_plain_bench_line_times_the_headline_only(tmp_path):
+    """A plain `python bench.py` (no --full) prints the same headline and the timed region's roofline, writes --dump-outputs, and runs
+    none of the extra legs: one timed region, no solo kernels, copy rate, other tiers or batch sizes, latency or oracle check."""
+    d = _bench_line("--dump-outputs", str(tmp_path / "out"))
+    assert d["value_repeats"] == [round(d["value"], 1)] and d["value_median"] == d["value"]
+    assert d["verified_frames"] is None and d["latency_ms_batch1"] is None and d["cpu_baseline"] is None
+    assert "solo" not in d["roofline"] and d["roofline"]["stream_copy_GBps"] is None and d["roofline"]["kernels_ms_per_step"]
+    cfg = d["config"]
+    for k in ("keep_pyramid_fps", "ref_arith_fps", "ref_arith_verified_frames", "cfg3_64_frames_per_step_fps_1gpu", "batch8_fps_1gpu",
+              "batch8_pipelined_fps_1gpu"):
+        assert cfg[k] is None, k
+    assert d["dumped_outputs"]["frames"] == 2 * 8
+    for k in ("counts", "boxes", "scores", "levels", "frames"):
+        assert np.load(str(tmp_path / "out" / (k + ".npy"))).shape[0] == 2 * 8, k
