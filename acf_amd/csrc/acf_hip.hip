@@ -957,15 +957,38 @@ int kidsJoin(acf_hip_ctx* c)
     }
     return ACF_HIP_OK;
 }
-int kidFail(acf_hip_ctx* c, acf_hip_ctx* k, int rc)
+// fn(kid, first, n) for every child that owns frames of a batch of nF (child i: [i * chunk, min(nF, (i+1) * chunk))), forked from
+// and joined into c's stream; the first failure returns its code with the child's text on c
+template <class Fn>
+int forEachKid(acf_hip_ctx* c, int nF, Fn fn)
 {
-    c->err = k->err;
-    return rc;
+    int rc = kidsFork(c);
+    for (size_t i = 0; i < c->kids.size() && !rc; i++)
+    {
+        const int first = int(i) * c->kidChunk, n = std::min(nF - first, c->kidChunk);
+        if (n > 0 && (rc = fn(c->kids[i], first, n)))
+        {
+            return fail(c, rc, c->kids[i]->err);
+        }
+    }
+    return rc ? rc : kidsJoin(c);
 }
-// frames of the last batch owned by child i: [i * chunk, min(n, (i+1) * chunk))
-int kidCount(const acf_hip_ctx* c, size_t i, int n)
+// fn(ctx, frame) for one frame of the last batch: on a context with children, on the child that owns the frame with the frame's
+// index within it (outOfRange: the reader's own text for a frame outside the batch); a child's failure leaves its text on c
+template <class Fn>
+int onFrameOwner(acf_hip_ctx* c, int frame, const char* outOfRange, Fn fn)
 {
-    return std::max(0, std::min(n, int(i + 1) * c->kidChunk) - int(i) * c->kidChunk);
+    if (!c || c->kids.empty())
+    {
+        return fn(c, frame);
+    }
+    if (frame < 0 || frame >= c->lastBatch)
+    {
+        return fail(c, ACF_HIP_E_INVALID, outOfRange);
+    }
+    acf_hip_ctx* k = c->kids[size_t(frame / c->kidChunk)];
+    const int rc = fn(k, frame % c->kidChunk);
+    return rc ? fail(c, rc, k->err) : rc;
 }
 } // namespace
 
@@ -1489,7 +1512,7 @@ int acf_hip_plan(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_
             k->nms = c->nms;
             if ((rc = acf_hip_set_model(k, &c->p)) || (rc = acf_hip_plan(k, H, W, d_in, c->kidChunk, max_hits)))
             {
-                return kidFail(c, k, rc);
+                return fail(c, rc, k->err);
             }
         }
         c->maxBatch = max_batch;
@@ -1610,28 +1633,21 @@ int acf_hip_get_lambdas(acf_hip_ctx* c, int frame, double out[3])
     {
         return ACF_HIP_E_INVALID;
     }
-    if (!c->kids.empty())
-    {
+    return onFrameOwner(c, frame, "get_lambdas: frame out of range", [&](acf_hip_ctx* c, int frame) -> int {
+        if (!c->hasPlan || !c->pyramidValid)
+        {
+            return fail(c, ACF_HIP_E_NOPLAN, "get_lambdas: no pyramid");
+        }
         if (frame < 0 || frame >= c->lastBatch)
         {
             return fail(c, ACF_HIP_E_INVALID, "get_lambdas: frame out of range");
         }
-        const int k = frame / std::max(c->kidChunk, 1);
-        return acf_hip_get_lambdas(c->kids[size_t(k)], frame - k * c->kidChunk, out);
-    }
-    if (!c->hasPlan || !c->pyramidValid)
-    {
-        return fail(c, ACF_HIP_E_NOPLAN, "get_lambdas: no pyramid");
-    }
-    if (frame < 0 || frame >= c->lastBatch)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "get_lambdas: frame out of range");
-    }
-    for (int j = 0; j < 3; j++)
-    {
-        out[j] = c->h_lambdas[size_t(frame) * 3 + j];
-    }
-    return ACF_HIP_OK;
+        for (int j = 0; j < 3; j++)
+        {
+            out[j] = c->h_lambdas[size_t(frame) * 3 + j];
+        }
+        return ACF_HIP_OK;
+    });
 }
 
 static int allowLds(acf_hip_ctx* c, const void* kernel, size_t bytes);
@@ -1992,16 +2008,12 @@ int acf_hip_detect(acf_hip_ctx* c)
         {
             return fail(c, ACF_HIP_E_INVALID, "detect: no pyramid (call acf_hip_pyramid)");
         }
-        int rc = kidsFork(c);
-        for (size_t i = 0; i < c->kids.size() && !rc; i++)
+        const int rc = forEachKid(c, c->lastBatch, [](acf_hip_ctx* k, int, int) { return acf_hip_detect(k); });
+        if (!rc)
         {
-            if (kidCount(c, i, c->lastBatch) > 0 && (rc = acf_hip_detect(c->kids[i])))
-            {
-                return kidFail(c, c->kids[i], rc);
-            }
+            c->detectValid = true;
         }
-        c->detectValid = true;
-        return rc ? rc : kidsJoin(c);
+        return rc;
     }
     if (!c || !c->hasPlan)
     {
@@ -2099,18 +2111,13 @@ int acf_hip_run(acf_hip_ctx* c, const float* frames, int nF)
             return fail(c, ACF_HIP_E_INVALID, "run: n_frames out of range");
         }
         const size_t per = size_t(c->plan.d_in) * c->plan.H * c->plan.W;
-        int rc = kidsFork(c);
-        for (size_t i = 0; i < c->kids.size() && !rc; i++)
+        const int rc = forEachKid(c, nF, [&](acf_hip_ctx* k, int first, int n) { return acf_hip_run(k, frames + first * per, n); });
+        if (!rc)
         {
-            const int n = kidCount(c, i, nF);
-            if (n > 0 && (rc = acf_hip_run(c->kids[i], frames + i * size_t(c->kidChunk) * per, n)))
-            {
-                return kidFail(c, c->kids[i], rc);
-            }
+            c->lastBatch = nF;
+            c->pyramidValid = c->detectValid = true;
         }
-        c->lastBatch = nF;
-        c->pyramidValid = c->detectValid = true;
-        return rc ? rc : kidsJoin(c);
+        return rc;
     }
     // option "graph": the launches of this call — same frames pointer, same batch size, nothing in the path that reads back or
     // records events of its own — as one captured graph.  The first calls run plainly (they may allocate); a capture that the
@@ -2211,18 +2218,13 @@ int acf_hip_run_host(acf_hip_ctx* c, const float* frames_host, int nF)
             return fail(c, ACF_HIP_E_INVALID, "run_host: n_frames out of range");
         }
         const size_t per = size_t(c->plan.d_in) * c->plan.H * c->plan.W;
-        int rc = kidsFork(c);
-        for (size_t i = 0; i < c->kids.size() && !rc; i++)
+        const int rc = forEachKid(c, nF, [&](acf_hip_ctx* k, int first, int n) { return acf_hip_run_host(k, frames_host + first * per, n); });
+        if (!rc)
         {
-            const int n = kidCount(c, i, nF);
-            if (n > 0 && (rc = acf_hip_run_host(c->kids[i], frames_host + i * size_t(c->kidChunk) * per, n)))
-            {
-                return kidFail(c, c->kids[i], rc);
-            }
+            c->lastBatch = nF;
+            c->pyramidValid = c->detectValid = true;
         }
-        c->lastBatch = nF;
-        c->pyramidValid = c->detectValid = true;
-        return rc ? rc : kidsJoin(c);
+        return rc;
     }
     if (!c || !c->hasPlan)
     {
@@ -2471,7 +2473,7 @@ int acf_hip_profile_get(acf_hip_ctx* c, int* n, const char** names, float* ms, i
             int rc = acf_hip_profile_get(k, &kn, knames, kms, kl, 64);
             if (rc)
             {
-                return kidFail(c, k, rc);
+                return fail(c, rc, k->err);
             }
             for (int i = 0; i < std::min(kn, 64); i++)
             {
@@ -2678,52 +2680,6 @@ int acf_hip_op_nms(acf_hip_ctx* c, const int32_t* boxes, const double* scores, i
     return ACF_HIP_OK;
 }
 
-int acf_hip_get_detections(acf_hip_ctx* c, int frame, acf_hip_detection* out, int cap, int* count)
-{
-    if (c && !c->kids.empty())
-    {
-        if (frame < 0 || frame >= c->lastBatch)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "frame index");
-        }
-        acf_hip_ctx* k = c->kids[size_t(frame / c->kidChunk)];
-        const int rc = acf_hip_get_detections(k, frame % c->kidChunk, out, cap, count);
-        return rc ? kidFail(c, k, rc) : rc;
-    }
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
-    int rc = fetchCounts(c);
-    if (rc)
-    {
-        return rc;
-    }
-    if (frame < 0 || frame >= c->lastBatch)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "get_detections: frame index");
-    }
-    const int n = c->h_counts[frame];
-    if (n < 0)
-    {
-        return fail(c, ACF_HIP_E_CAPACITY, "more than ACF_HIP_NMS_CAP detections into the device NMS: take the raw list (acf_hip_get_raw_detections) and suppress it on the host");
-    }
-    if (count)
-    {
-        *count = n;
-    }
-    const int m = std::min(std::min(n, c->maxHits), cap);
-    if (m > 0 && out)
-    {
-        HIPCHK(c, hipMemcpy(out, (nmsActive(c) ? c->d_nmsDets : c->cs.d_dets) + size_t(frame) * c->maxHits, sizeof(acf_hip_detection) * m, hipMemcpyDeviceToHost));
-    }
-    if (n > c->maxHits)
-    {
-        return fail(c, ACF_HIP_E_CAPACITY, "more hits than max_hits; re-plan with a larger capacity");
-    }
-    return ACF_HIP_OK;
-}
-
 // raw (pre-NMS) count of one frame of the last batch
 static int rawCount(acf_hip_ctx* c, int frame, int* n)
 {
@@ -2739,131 +2695,108 @@ static int rawCount(acf_hip_ctx* c, int frame, int* n)
     return ACF_HIP_OK;
 }
 
-int acf_hip_get_raw_detections(acf_hip_ctx* c, int frame, acf_hip_detection* out, int cap, int* count)
+enum RecordList
 {
-    if (c && !c->kids.empty())
-    {
-        if (frame < 0 || frame >= c->lastBatch)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "frame index");
-        }
-        acf_hip_ctx* k = c->kids[size_t(frame / c->kidChunk)];
-        const int rc = acf_hip_get_raw_detections(k, frame % c->kidChunk, out, cap, count);
-        return rc ? kidFail(c, k, rc) : rc;
-    }
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
-    int rc = fetchCounts(c);
-    if (rc)
-    {
-        return rc;
-    }
-    if (frame < 0 || frame >= c->lastBatch)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "get_raw_detections: frame index");
-    }
-    int n = 0;
-    if ((rc = rawCount(c, frame, &n)))
-    {
-        return rc;
-    }
-    if (count)
-    {
-        *count = n;
-    }
-    const int m = std::min(std::min(n, c->maxHits), cap);
-    if (m > 0 && out)
-    {
-        HIPCHK(c, hipMemcpy(out, c->cs.d_dets + size_t(frame) * c->maxHits, sizeof(acf_hip_detection) * m, hipMemcpyDeviceToHost));
-    }
-    if (n > c->maxHits)
-    {
-        return fail(c, ACF_HIP_E_CAPACITY, "more hits than max_hits; re-plan with a larger capacity");
-    }
-    return ACF_HIP_OK;
-}
+    REC_DETECTIONS, // the detections, after the device NMS when it is on
+    REC_RAW,        // the detections before the device NMS
+    REC_HITS        // the hits behind REC_DETECTIONS, one per detection
+};
 
-int acf_hip_get_hits(acf_hip_ctx* c, int frame, acf_hip_hit* out, int cap, int* count)
+// One frame's list of the last batch: *count = its length, at most min(cap, max_hits) records into out
+static int readRecords(acf_hip_ctx* c, int frame, RecordList which, void* out, int cap, int* count)
 {
-    if (c && !c->kids.empty())
-    {
+    static const char* const frameText[] = { "get_detections: frame index", "get_raw_detections: frame index", "get_hits: frame index" };
+    return onFrameOwner(c, frame, frameText[which], [&](acf_hip_ctx* c, int frame) -> int {
+        if (!c || !c->hasPlan)
+        {
+            return ACF_HIP_E_NOPLAN;
+        }
+        int rc = fetchCounts(c);
+        if (rc)
+        {
+            return rc;
+        }
         if (frame < 0 || frame >= c->lastBatch)
         {
-            return fail(c, ACF_HIP_E_INVALID, "frame index");
+            return fail(c, ACF_HIP_E_INVALID, frameText[which]);
         }
-        acf_hip_ctx* k = c->kids[size_t(frame / c->kidChunk)];
-        const int rc = acf_hip_get_hits(k, frame % c->kidChunk, out, cap, count);
-        return rc ? kidFail(c, k, rc) : rc;
-    }
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
-    int rc = fetchCounts(c);
-    if (rc)
-    {
-        return rc;
-    }
-    if (frame < 0 || frame >= c->lastBatch)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "get_hits: frame index");
-    }
-    const int n = c->h_counts[frame];
-    if (nmsActive(c))
-    {
-        // hit i belongs to detection i of acf_hip_get_detections: the survivors' entries of the raw list, through k_nms's keep indices
-        if (n < 0)
+        int n = c->h_counts[frame];
+        if (which == REC_RAW && (rc = rawCount(c, frame, &n)))
         {
-            return fail(c, ACF_HIP_E_CAPACITY, "more than ACF_HIP_NMS_CAP detections into the device NMS: take the raw list (acf_hip_get_raw_detections)");
+            return rc;
         }
-        if (n > c->maxHits)
+        if (n < 0) // (k_nms's count for a frame with more than NMS_CAP detections; a raw count is never negative)
         {
-            return fail(c, ACF_HIP_E_CAPACITY, "more hits than max_hits; re-plan with a larger capacity");
+            return fail(c, ACF_HIP_E_CAPACITY, "more than ACF_HIP_NMS_CAP detections into the device NMS: take the raw list (acf_hip_get_raw_detections) and suppress it on the host");
+        }
+        if (which == REC_HITS && nmsActive(c))
+        {
+            // hit i belongs to detection i of acf_hip_get_detections: the survivors' entries of the raw list, through k_nms's keep indices
+            if (n > c->maxHits)
+            {
+                return fail(c, ACF_HIP_E_CAPACITY, "more hits than max_hits; re-plan with a larger capacity");
+            }
+            if (count)
+            {
+                *count = n;
+            }
+            const int m = std::min(n, cap);
+            if (m > 0 && out)
+            {
+                int nRaw = 0;
+                if ((rc = rawCount(c, frame, &nRaw)))
+                {
+                    return rc;
+                }
+                nRaw = std::min(nRaw, c->maxHits);
+                std::vector<int32_t> keep(static_cast<size_t>(m));
+                std::vector<acf_hip_hit> raw(static_cast<size_t>(std::max(nRaw, 1)));
+                HIPCHK(c, hipMemcpy(keep.data(), c->d_nmsKeep + size_t(frame) * NMS_CAP, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+                HIPCHK(c, hipMemcpy(raw.data(), c->cs.d_sorted + size_t(frame) * c->maxHits, sizeof(acf_hip_hit) * nRaw, hipMemcpyDeviceToHost));
+                for (int i = 0; i < m; i++)
+                {
+                    if (keep[size_t(i)] < 0 || keep[size_t(i)] >= nRaw)
+                    {
+                        return fail(c, ACF_HIP_E_INVALID, "get_hits: survivor index outside the raw list");
+                    }
+                    static_cast<acf_hip_hit*>(out)[i] = raw[size_t(keep[size_t(i)])];
+                }
+            }
+            return ACF_HIP_OK;
         }
         if (count)
         {
             *count = n;
         }
-        const int m = std::min(n, cap);
+        const int m = std::min(std::min(n, c->maxHits), cap);
         if (m > 0 && out)
         {
-            int nRaw = 0;
-            if ((rc = rawCount(c, frame, &nRaw)))
-            {
-                return rc;
-            }
-            nRaw = std::min(nRaw, c->maxHits);
-            std::vector<int32_t> keep(static_cast<size_t>(m));
-            std::vector<acf_hip_hit> raw(static_cast<size_t>(std::max(nRaw, 1)));
-            HIPCHK(c, hipMemcpy(keep.data(), c->d_nmsKeep + size_t(frame) * NMS_CAP, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(raw.data(), c->cs.d_sorted + size_t(frame) * c->maxHits, sizeof(acf_hip_hit) * nRaw, hipMemcpyDeviceToHost));
-            for (int i = 0; i < m; i++)
-            {
-                if (keep[size_t(i)] < 0 || keep[size_t(i)] >= nRaw)
-                {
-                    return fail(c, ACF_HIP_E_INVALID, "get_hits: survivor index outside the raw list");
-                }
-                out[i] = raw[size_t(keep[size_t(i)])];
-            }
+            const size_t at = size_t(frame) * c->maxHits, rec = which == REC_HITS ? sizeof(acf_hip_hit) : sizeof(acf_hip_detection);
+            const void* src = which == REC_HITS ? static_cast<const void*>(c->cs.d_sorted + at)
+                                                : (which == REC_DETECTIONS && nmsActive(c) ? c->d_nmsDets : c->cs.d_dets) + at;
+            HIPCHK(c, hipMemcpy(out, src, rec * m, hipMemcpyDeviceToHost));
+        }
+        if (n > c->maxHits)
+        {
+            return fail(c, ACF_HIP_E_CAPACITY, "more hits than max_hits; re-plan with a larger capacity");
         }
         return ACF_HIP_OK;
-    }
-    if (count)
-    {
-        *count = n;
-    }
-    const int m = std::min(std::min(n, c->maxHits), cap);
-    if (m > 0 && out)
-    {
-        HIPCHK(c, hipMemcpy(out, c->cs.d_sorted + size_t(frame) * c->maxHits, sizeof(acf_hip_hit) * m, hipMemcpyDeviceToHost));
-    }
-    if (n > c->maxHits)
-    {
-        return fail(c, ACF_HIP_E_CAPACITY, "more hits than max_hits; re-plan with a larger capacity");
-    }
-    return ACF_HIP_OK;
+    });
+}
+
+int acf_hip_get_detections(acf_hip_ctx* c, int frame, acf_hip_detection* out, int cap, int* count)
+{
+    return readRecords(c, frame, REC_DETECTIONS, out, cap, count);
+}
+
+int acf_hip_get_raw_detections(acf_hip_ctx* c, int frame, acf_hip_detection* out, int cap, int* count)
+{
+    return readRecords(c, frame, REC_RAW, out, cap, count);
+}
+
+int acf_hip_get_hits(acf_hip_ctx* c, int frame, acf_hip_hit* out, int cap, int* count)
+{
+    return readRecords(c, frame, REC_HITS, out, cap, count);
 }
 
 int acf_hip_export_detections(acf_hip_ctx* c, int32_t* dst_dev, int cap)
@@ -2874,16 +2807,8 @@ int acf_hip_export_detections(acf_hip_ctx* c, int32_t* dst_dev, int cap)
         {
             return fail(c, ACF_HIP_E_INVALID, "export_detections: nothing to export");
         }
-        int rc = kidsFork(c);
-        for (size_t i = 0; i < c->kids.size() && !rc; i++)
-        {
-            if (kidCount(c, i, c->lastBatch) > 0 &&
-                (rc = acf_hip_export_detections(c->kids[i], dst_dev + i * size_t(c->kidChunk) * (1 + 6 * size_t(cap)), cap)))
-            {
-                return kidFail(c, c->kids[i], rc);
-            }
-        }
-        return rc ? rc : kidsJoin(c);
+        return forEachKid(c, c->lastBatch,
+            [&](acf_hip_ctx* k, int first, int) { return acf_hip_export_detections(k, dst_dev + first * (1 + 6 * size_t(cap)), cap); });
     }
     if (!c || !c->hasPlan)
     {
@@ -2902,69 +2827,53 @@ int acf_hip_export_detections(acf_hip_ctx* c, int32_t* dst_dev, int cap)
 
 int acf_hip_read_level(acf_hip_ctx* c, int frame, int level, float* host_out)
 {
-    if (c && !c->kids.empty())
-    {
-        if (frame < 0 || frame >= c->lastBatch)
+    return onFrameOwner(c, frame, "read_level: arguments", [&](acf_hip_ctx* c, int frame) -> int {
+        if (!c || !c->hasPlan)
         {
-            return fail(c, ACF_HIP_E_INVALID, "frame index");
+            return ACF_HIP_E_NOPLAN;
         }
-        acf_hip_ctx* k = c->kids[size_t(frame / c->kidChunk)];
-        const int rc = acf_hip_read_level(k, frame % c->kidChunk, level, host_out);
-        return rc ? kidFail(c, k, rc) : rc;
-    }
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
-    if (!c->pyramidValid || frame < 0 || frame >= c->lastBatch || level < 0 || level >= int(c->plan.levels.size()) || !host_out)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "read_level: arguments");
-    }
-    if (!c->floatPyramid)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "read_level: the float pyramid was not kept (option keep_pyramid = 0: the levels left as rank cells only)");
-    }
-    const acf_hip_level& l = c->plan.levels[level];
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(host_out, c->d_pyr + size_t(frame) * c->plan.pyr_floats + l.offset, sizeof(float) * c->plan.nChns * l.hP * l.wP, hipMemcpyDeviceToHost));
-    return ACF_HIP_OK;
+        if (!c->pyramidValid || frame < 0 || frame >= c->lastBatch || level < 0 || level >= int(c->plan.levels.size()) || !host_out)
+        {
+            return fail(c, ACF_HIP_E_INVALID, "read_level: arguments");
+        }
+        if (!c->floatPyramid)
+        {
+            return fail(c, ACF_HIP_E_INVALID, "read_level: the float pyramid was not kept (option keep_pyramid = 0: the levels left as rank cells only)");
+        }
+        const acf_hip_level& l = c->plan.levels[level];
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(host_out, c->d_pyr + size_t(frame) * c->plan.pyr_floats + l.offset, sizeof(float) * c->plan.nChns * l.hP * l.wP, hipMemcpyDeviceToHost));
+        return ACF_HIP_OK;
+    });
 }
 
 int acf_hip_read_rank_level(acf_hip_ctx* c, int frame, int level, uint16_t* host_out)
 {
-    if (c && !c->kids.empty())
-    {
-        if (frame < 0 || frame >= c->lastBatch)
+    return onFrameOwner(c, frame, "read_rank_level: arguments, or no detect since the last pyramid", [&](acf_hip_ctx* c, int frame) -> int {
+        if (!c || !c->hasPlan)
         {
-            return fail(c, ACF_HIP_E_INVALID, "frame index");
+            return ACF_HIP_E_NOPLAN;
         }
-        acf_hip_ctx* k = c->kids[size_t(frame / c->kidChunk)];
-        const int rc = acf_hip_read_rank_level(k, frame % c->kidChunk, level, host_out);
-        return rc ? kidFail(c, k, rc) : rc;
-    }
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
-    if (!rankCellsOn(c))
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "read_rank_level: the plan has no rank cells (model not depth 2 / thresholds too dense / option rank_cells off / LDCF)");
-    }
-    if (!c->pyramidValid || !c->ranksValid || frame < 0 || frame >= c->lastBatch || level < 0 || level >= int(c->plan.levels.size()) || !host_out)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "read_rank_level: arguments, or no detect since the last pyramid");
-    }
-    const acf_hip_level& l = c->plan.levels[level];
-    const int pitch = rankPitch(l.hP);
-    int64_t off = 0;
-    for (int i = 0; i < level; i++)
-    {
-        off += int64_t(c->plan.nChns) * rankPitch(c->plan.levels[i].hP) * c->plan.levels[i].wP;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy2D(host_out, size_t(l.hP) * 2, c->cs.d_pyrR + size_t(frame) * c->cs.pyrRCells + off, size_t(pitch) * 2, size_t(l.hP) * 2,
-        size_t(c->plan.nChns) * l.wP, hipMemcpyDeviceToHost));
-    return ACF_HIP_OK;
+        if (!rankCellsOn(c))
+        {
+            return fail(c, ACF_HIP_E_UNSUPPORTED, "read_rank_level: the plan has no rank cells (model not depth 2 / thresholds too dense / option rank_cells off / LDCF)");
+        }
+        if (!c->pyramidValid || !c->ranksValid || frame < 0 || frame >= c->lastBatch || level < 0 || level >= int(c->plan.levels.size()) || !host_out)
+        {
+            return fail(c, ACF_HIP_E_INVALID, "read_rank_level: arguments, or no detect since the last pyramid");
+        }
+        const acf_hip_level& l = c->plan.levels[level];
+        const int pitch = rankPitch(l.hP);
+        int64_t off = 0;
+        for (int i = 0; i < level; i++)
+        {
+            off += int64_t(c->plan.nChns) * rankPitch(c->plan.levels[i].hP) * c->plan.levels[i].wP;
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy2D(host_out, size_t(l.hP) * 2, c->cs.d_pyrR + size_t(frame) * c->cs.pyrRCells + off, size_t(pitch) * 2, size_t(l.hP) * 2,
+            size_t(c->plan.nChns) * l.wP, hipMemcpyDeviceToHost));
+        return ACF_HIP_OK;
+    });
 }
 
 int acf_hip_rank_cells_host(const acf_hip_params* p, int nChns, int chn, const float* v, int n, uint16_t* cells_out, uint32_t* thr_index_out, int32_t* info)
@@ -3014,107 +2923,99 @@ int acf_hip_rank_cells_host(const acf_hip_params* p, int nChns, int chn, const f
 
 int acf_hip_read_tap(acf_hip_ctx* c, int frame, int tap, int index, float* host_out, int64_t cap)
 {
-    if (c && !c->kids.empty())
-    {
-        if (frame < 0 || frame >= c->lastBatch)
+    return onFrameOwner(c, frame, "read_tap: arguments", [&](acf_hip_ctx* c, int frame) -> int {
+        if (!c || !c->hasPlan)
         {
-            return fail(c, ACF_HIP_E_INVALID, "frame index");
+            return ACF_HIP_E_NOPLAN;
         }
-        acf_hip_ctx* k = c->kids[size_t(frame / c->kidChunk)];
-        const int rc = acf_hip_read_tap(k, frame % c->kidChunk, tap, index, host_out, cap);
-        return rc ? kidFail(c, k, rc) : rc;
-    }
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
-    if (!c->pyramidValid || frame < 0 || frame >= c->lastBatch || !host_out)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "read_tap: arguments");
-    }
-    const Plan& pl = c->plan;
-    const float* src = nullptr;
-    int64_t n = 0;
-    if (tap == ACF_HIP_TAP_LDCF)
-    {
-        if (c->p.ldcfK <= 0 || !c->detectValid || index < 0 || index >= int(c->ldcfLevels.size()))
+        if (!c->pyramidValid || frame < 0 || frame >= c->lastBatch || !host_out)
         {
-            return fail(c, ACF_HIP_E_INVALID, "read_tap: LDCF levels exist after acf_hip_detect on a model with ldcfK > 0");
+            return fail(c, ACF_HIP_E_INVALID, "read_tap: arguments");
         }
-        const acf_hip_level& l = c->ldcfLevels[size_t(index)];
-        n = int64_t(pl.nChns) * c->p.ldcfK * l.hP * l.wP;
-        src = c->d_ldcfPyr + size_t(frame) * c->ldcfFloats + l.offset;
-    }
-    else if (tap == ACF_HIP_TAP_CHNS)
-    {
-        if (index < 0 || index >= int(pl.levels.size()))
+        const Plan& pl = c->plan;
+        const float* src = nullptr;
+        int64_t n = 0;
+        if (tap == ACF_HIP_TAP_LDCF)
         {
-            return fail(c, ACF_HIP_E_INVALID, "read_tap: level");
+            if (c->p.ldcfK <= 0 || !c->detectValid || index < 0 || index >= int(c->ldcfLevels.size()))
+            {
+                return fail(c, ACF_HIP_E_INVALID, "read_tap: LDCF levels exist after acf_hip_detect on a model with ldcfK > 0");
+            }
+            const acf_hip_level& l = c->ldcfLevels[size_t(index)];
+            n = int64_t(pl.nChns) * c->p.ldcfK * l.hP * l.wP;
+            src = c->d_ldcfPyr + size_t(frame) * c->ldcfFloats + l.offset;
         }
-        const acf_hip_level& l = pl.levels[index];
-        n = int64_t(pl.nChns) * l.hC * l.wC;
-        src = c->d_chns + size_t(frame) * pl.raw_floats + pl.raw_off[index];
-    }
-    else
-    {
-        if (index < 0 || index >= int(c->real.size()))
+        else if (tap == ACF_HIP_TAP_CHNS)
         {
-            return fail(c, ACF_HIP_E_INVALID, "read_tap: real-scale ordinal");
+            if (index < 0 || index >= int(pl.levels.size()))
+            {
+                return fail(c, ACF_HIP_E_INVALID, "read_tap: level");
+            }
+            const acf_hip_level& l = pl.levels[index];
+            n = int64_t(pl.nChns) * l.hC * l.wC;
+            src = c->d_chns + size_t(frame) * pl.raw_floats + pl.raw_off[index];
         }
-        const RealScale& rs = c->real[index];
-        const int64_t np = int64_t(rs.h) * rs.w;
-        switch (tap)
+        else
         {
-            case ACF_HIP_TAP_IMAGE:
-                n = np * pl.d;
-                if (rs.resampled)
-                {
-                    src = rs.img + size_t(frame) * n;
-                }
-                else if (c->d_color)
-                {
-                    src = c->d_color + size_t(frame) * n;
-                }
-                else
-                {
-                    src = c->lastFrames + size_t(frame) * n;
-                }
-                break;
-            case ACF_HIP_TAP_SMOOTHED:
-                n = np * pl.d;
-                src = rs.sm + size_t(frame) * n;
-                break;
-            case ACF_HIP_TAP_M:
-                n = np;
-                src = rs.M ? rs.M + size_t(frame) * n : nullptr;
-                break;
-            case ACF_HIP_TAP_O:
-                n = np;
-                src = rs.O ? rs.O + size_t(frame) * n : nullptr;
-                break;
-            case ACF_HIP_TAP_S:
-                n = np;
-                src = rs.S ? rs.S + size_t(frame) * n : nullptr;
-                break;
-            case ACF_HIP_TAP_MNORM:
-                n = np;
-                src = rs.Mn ? rs.Mn + size_t(frame) * n : nullptr;
-                break;
-            default:
-                return fail(c, ACF_HIP_E_INVALID, "read_tap: unknown tap");
+            if (index < 0 || index >= int(c->real.size()))
+            {
+                return fail(c, ACF_HIP_E_INVALID, "read_tap: real-scale ordinal");
+            }
+            const RealScale& rs = c->real[index];
+            const int64_t np = int64_t(rs.h) * rs.w;
+            switch (tap)
+            {
+                case ACF_HIP_TAP_IMAGE:
+                    n = np * pl.d;
+                    if (rs.resampled)
+                    {
+                        src = rs.img + size_t(frame) * n;
+                    }
+                    else if (c->d_color)
+                    {
+                        src = c->d_color + size_t(frame) * n;
+                    }
+                    else
+                    {
+                        src = c->lastFrames + size_t(frame) * n;
+                    }
+                    break;
+                case ACF_HIP_TAP_SMOOTHED:
+                    n = np * pl.d;
+                    src = rs.sm + size_t(frame) * n;
+                    break;
+                case ACF_HIP_TAP_M:
+                    n = np;
+                    src = rs.M ? rs.M + size_t(frame) * n : nullptr;
+                    break;
+                case ACF_HIP_TAP_O:
+                    n = np;
+                    src = rs.O ? rs.O + size_t(frame) * n : nullptr;
+                    break;
+                case ACF_HIP_TAP_S:
+                    n = np;
+                    src = rs.S ? rs.S + size_t(frame) * n : nullptr;
+                    break;
+                case ACF_HIP_TAP_MNORM:
+                    n = np;
+                    src = rs.Mn ? rs.Mn + size_t(frame) * n : nullptr;
+                    break;
+                default:
+                    return fail(c, ACF_HIP_E_INVALID, "read_tap: unknown tap");
+            }
+            if (!src)
+            {
+                return fail(c, ACF_HIP_E_INVALID, "read_tap: tap not kept (set option \"taps\" before acf_hip_plan)");
+            }
         }
-        if (!src)
+        if (cap < n)
         {
-            return fail(c, ACF_HIP_E_INVALID, "read_tap: tap not kept (set option \"taps\" before acf_hip_plan)");
+            return fail(c, ACF_HIP_E_INVALID, "read_tap: capacity");
         }
-    }
-    if (cap < n)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "read_tap: capacity");
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(host_out, src, sizeof(float) * n, hipMemcpyDeviceToHost));
-    return ACF_HIP_OK;
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(host_out, src, sizeof(float) * n, hipMemcpyDeviceToHost));
+        return ACF_HIP_OK;
+    });
 }
 
 /* ---- single operators on host planes ---------------------------------- */

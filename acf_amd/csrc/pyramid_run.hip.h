@@ -979,19 +979,14 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
             return fail(c, ACF_HIP_E_INVALID, "pyramid: n_frames out of range");
         }
         const size_t per = size_t(c->plan.d_in) * c->plan.H * c->plan.W;
-        int rc = kidsFork(c);
-        for (size_t i = 0; i < c->kids.size() && !rc; i++)
+        const int rc = forEachKid(c, nF, [&](acf_hip_ctx* k, int first, int n) { return acf_hip_pyramid(k, frames + first * per, n); });
+        if (!rc)
         {
-            const int n = kidCount(c, i, nF);
-            if (n > 0 && (rc = acf_hip_pyramid(c->kids[i], frames + i * size_t(c->kidChunk) * per, n)))
-            {
-                return kidFail(c, c->kids[i], rc);
-            }
+            c->lastBatch = nF;
+            c->pyramidValid = true;
+            c->detectValid = false;
         }
-        c->lastBatch = nF;
-        c->pyramidValid = true;
-        c->detectValid = false;
-        return rc ? rc : kidsJoin(c);
+        return rc;
     }
     if (!c || !c->hasPlan)
     {

@@ -238,6 +238,64 @@ def test_sub_batch_streams(oracle, streams):
                 assert a[:4] == (int(b["x"]), int(b["y"]), int(b["w"]), int(b["h"])) and np.float32(a[4]) == b["score"]
     det.close()
 
+    # Every per-frame reader and per-batch entry routed through the children equals a single context, on a model whose
+    # lambdas are estimated per frame (and whose lower threshold leaves detections in every frame); a frame outside the
+    # batch and a child's own failure read the same on both.
+    import ctypes as C
+    from acf_amd.detector import HipError
+    lam_model = synth.make_model(seed=3, name="TINY", nTrees=160, lambdas=[], cascThr=-2.0)
+    kids = HipDetector(lam_model, H, W, 3, max_batch=n, max_hits=1 << 14, taps=True, streams=streams)
+    lone = HipDetector(lam_model, H, W, 3, max_batch=n, max_hits=1 << 14, taps=True)
+    real, approx = 1, plan.nScales - 2  # a real scale's ordinal; an approximated level (it follows the frame's lambdas)
+    assert approx not in plan.real
+
+    def hits(d, f):
+        out, cnt = np.zeros(d.max_hits, dtype=capi.HIT_DTYPE), C.c_int()
+        d._chk(d.lib.acf_hip_get_hits(d.ctx, f, out.ctypes.data_as(C.POINTER(capi.Hit)), d.max_hits, C.byref(cnt)))
+        return out[:cnt.value]
+
+    def tap(d, f, t, i):
+        return d.read_tap(f, t, i, (3 * H * W,))
+
+    readers = {  # each returns the bytes of what it read
+        "detections": lambda d, f: b"".join(a.tobytes() for a in d.detections(f)),
+        "raw_detections": lambda d, f: d.raw_detections(f).tobytes(),
+        "hits": lambda d, f: hits(d, f).tobytes(),
+        "lambdas": lambda d, f: np.array(d.lambdas(f)).tobytes(),
+        "read_level": lambda d, f: d.read_level(f, approx).tobytes(),
+        "read_rank_level": lambda d, f: d.read_rank_level(f, approx).tobytes(),
+        "read_tap real scale": lambda d, f: tap(d, f, capi.TAP_MNORM, real).tobytes(),
+        "read_tap chns": lambda d, f: tap(d, f, capi.TAP_CHNS, approx).tobytes(),
+    }
+
+    def same_text(fn):
+        errs = []
+        for d in (kids, lone):
+            with pytest.raises(HipError) as e:
+                fn(d)
+            errs.append(e.value)
+        assert errs[0].code == errs[1].code == capi.E_INVALID and str(errs[0]) == str(errs[1]), (str(errs[0]), str(errs[1]))
+        return str(errs[0])
+
+    for nrun in (n, n - 2):
+        for how in ("run_host", "pyramid+detect"):
+            for d in (kids, lone):
+                if how == "run_host":
+                    d.run_host(frames[:nrun])
+                else:
+                    d.pyramid(fr, nrun)
+                    d.detect()
+            for f in range(nrun):
+                for name, read in readers.items():
+                    assert read(kids, f) == read(lone, f), (how, nrun, f, name)
+                assert len(lone.raw_detections(f)) > 0
+                assert np.any(tap(lone, f, capi.TAP_MNORM, real)) and np.any(tap(lone, f, capi.TAP_CHNS, approx))
+            for name, read in readers.items():
+                same_text(lambda d: read(d, nrun))
+            assert same_text(lambda d: d.read_tap(0, 99, real, (3 * H * W,))).endswith("read_tap: unknown tap")
+    kids.close()
+    lone.close()
+
 
 @pytest.mark.parametrize("fused_smooth", [2, 1, 0])   # 2: with convTri's x pass on the gradient plane's chain as well (k_smooth_grad_tri)
 @pytest.mark.parametrize("H,W,kw", [
