@@ -2963,6 +2963,11 @@ int acf_hip_read_tap(acf_hip_ctx* c, int frame, int tap, int index, float* host_
             }
             const RealScale& rs = c->real[index];
             const int64_t np = int64_t(rs.h) * rs.w;
+            if (pl.d_in == 5 && index == 0 && (tap == ACF_HIP_TAP_M || tap == ACF_HIP_TAP_O || tap == ACF_HIP_TAP_S || tap == ACF_HIP_TAP_MNORM))
+            {
+                // chnsCompute.cpp:265-269: M and O came with the frame; nothing was computed here, and the reference logs none of them
+                return fail(c, ACF_HIP_E_INVALID, "read_tap: M, O, S and Mnorm of the first real scale came with the five-plane frame (none computed)");
+            }
             switch (tap)
             {
                 case ACF_HIP_TAP_IMAGE:
@@ -2977,7 +2982,7 @@ int acf_hip_read_tap(acf_hip_ctx* c, int frame, int tap, int index, float* host_
                     }
                     else
                     {
-                        src = c->lastFrames + size_t(frame) * n;
+                        src = c->lastFrames + size_t(frame) * pl.d_in * np; // (the caller's frames: d_in planes a frame, M and O behind the image's)
                     }
                     break;
                 case ACF_HIP_TAP_SMOOTHED:
@@ -3330,9 +3335,15 @@ int acf_hip_chns_compute(acf_hip_ctx* c, const acf_hip_params* pIn, const float*
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, "chns_compute: nOrients must be 1..12");
     }
+    if (d == 1 && p.colorChn != 0)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "chns_compute: colorChn of a 1-plane image must be 0 (gradientMag reads I[colorChn], chnsCompute.cpp:278-282)");
+    }
     const int shrink = p.shrink;
     const int hc = h - h % shrink, wc = w - w % shrink; // crop so divisible by shrink (chnsCompute.cpp:203-217)
-    const int dcol = colorPlanes(p), nC = numChannels(p);
+    // a 1-plane image is its own colour plane for gray and orig alike (rgbConvert.cpp:129-148); replicating it is chnsPyramid's rule only
+    // (chnsPyramid.cpp:234-244)
+    const int dcol = d == 1 ? 1 : colorPlanes(p), nC = numChannels(p, dcol);
     const int hs = hc / shrink, ws = wc / shrink;
     if (nChnsOut)
     {
@@ -3384,9 +3395,9 @@ int acf_hip_chns_compute(acf_hip_ctx* c, const acf_hip_params* pIn, const float*
         return fail(c, ACF_HIP_E_HIP, "chns_compute: allocation");
     }
     // rgbConvert(I, I, colorSpace, true, isLuv) (chnsCompute.cpp:235; rgbConvert.cpp:101-170)
-    if (colourPassthrough(p, d))
+    if (d == 1 || colourPassthrough(p, d))
     {
-        HIPCHK(c, hipMemcpyAsync(dCol, dI, sizeof(float) * 3 * np, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dCol, dI, sizeof(float) * dcol * np, hipMemcpyDeviceToDevice, c->stream));
     }
     else
     {

@@ -320,7 +320,12 @@ int colorPlanes(const acf_hip_params& p)
 
 int numChannels(const acf_hip_params& p)
 {
-    return (p.colorEnabled ? colorPlanes(p) : 0) + (p.gradMagEnabled ? 1 : 0) + (p.gradHistEnabled ? p.nOrients : 0);
+    return numChannels(p, colorPlanes(p));
+}
+
+int numChannels(const acf_hip_params& p, int dcol)
+{
+    return (p.colorEnabled ? dcol : 0) + (p.gradMagEnabled ? 1 : 0) + (p.gradHistEnabled ? p.nOrients : 0);
 }
 
 // The checks on the Options::Pyramid::Chns fields (and the input's planes) that every entry computing channels makes:

@@ -172,5 +172,6 @@ int buildResizeTables(int rows, int cols, double scale, ResizeTables& t);
 
 int colorPlanes(const acf_hip_params& p);
 int numChannels(const acf_hip_params& p);
+int numChannels(const acf_hip_params& p, int dcol); // (dcol colour planes: acf_hip_chns_compute's 1-plane image keeps one)
 
 } // namespace acfhip

@@ -758,7 +758,8 @@ int HipDetector::chnsPyramid(const MatP& I, const Options::Pyramid* pPyramid, Py
                 MatP plane(w1, h1, 1, sm[z]);
                 logger(plane, tag(d == 3 ? luv[z] : "L", h1, w1));
             }
-            if (ch.pGradMag.enabled || ch.pGradHist.enabled)
+            // (five planes: the first real scale's M and O came with the image; the reference logs none of them, chnsCompute.cpp:265-269)
+            if ((ch.pGradMag.enabled || ch.pGradHist.enabled) && !(I.channels() == 5 && ordinal == 0))
             {
                 for (const auto& t : { std::make_pair(int(ACF_HIP_TAP_M), "M"), std::make_pair(int(ACF_HIP_TAP_MNORM), "Mnorm"), std::make_pair(int(ACF_HIP_TAP_O), "O") })
                 {
@@ -1118,7 +1119,8 @@ int HipDetector::chnsCompute(const MatP& IIn, const Options::Pyramid::Chns& pChn
     const int h = IIn.cols(), w = IIn.rows(), d = IIn.channels(); // rows = image width, cols = image height
     int nC = 0, hc = 0, wc = 0;
     utilCheck(api, c, api.acf_hip_chns_compute(c, &p, IIn.data(), h, w, d, nullptr, 0, &nC, &hc, &wc), "acf_hip_chns_compute");
-    const int dcol = p.colorSpace == ACF_HIP_CS_GRAY ? 1 : 3;
+    // the colour planes: a 1-plane image passes through for gray and orig alike (rgbConvert.cpp:129-148)
+    const int dcol = (d == 1 || p.colorSpace == ACF_HIP_CS_GRAY) ? 1 : 3;
     std::vector<float> all(size_t(nC) * hc * wc);
     if (!pLogger)
     {
@@ -1139,26 +1141,10 @@ int HipDetector::chnsCompute(const MatP& IIn, const Options::Pyramid::Chns& pChn
             }
         }
         MatP col(W, H, dcol);
-        const bool pass = dImg == 3 && (p.colorSpace == ACF_HIP_CS_ORIG || p.colorSpace == ACF_HIP_CS_RGB || (p.isLuv && p.colorSpace == ACF_HIP_CS_LUV));
+        const bool pass = d == 1 || (dImg == 3 && (p.colorSpace == ACF_HIP_CS_ORIG || p.colorSpace == ACF_HIP_CS_RGB || (p.isLuv && p.colorSpace == ACF_HIP_CS_LUV)));
         if (pass)
         {
-            std::memcpy(col.data(), I.data(), sizeof(float) * 3 * np);
-        }
-        else if (d == 1 && p.colorSpace == ACF_HIP_CS_ORIG)
-        {
-            for (int z = 0; z < 3; z++)
-            {
-                std::memcpy(col[z], I.data(), sizeof(float) * np); // (a 1-plane image replicated: chnsPyramid.cpp:242-243)
-            }
-        }
-        else if (d == 1)
-        {
-            MatP rep(W, H, 3);
-            for (int z = 0; z < 3; z++)
-            {
-                std::memcpy(rep[z], I.data(), sizeof(float) * np);
-            }
-            utilCheck(api, c, api.acf_hip_op_rgb_convert(c, rep.data(), col.data(), H, W, p.colorSpace), "acf_hip_op_rgb_convert");
+            std::memcpy(col.data(), I.data(), sizeof(float) * dcol * np);
         }
         else
         {

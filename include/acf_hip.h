@@ -296,8 +296,9 @@ ACF_HIP_API int acf_hip_set_model(acf_hip_ctx* ctx, const acf_hip_params* p);
 
 /* Plan for frames of h x w with `d` input planes (1 or 3; or 5 = three image planes followed by the gradient magnitude and
  * orientation that come WITH the image — the GL pipeline's LUVMO frames, chnsPyramid.cpp:248-255: M and O then replace
- * gradientMag at the first real scale, :318-322, which must be the image's own size: nOctUp = 0) and up to
- * `max_batch` frames per call and `max_hits` hits per frame: runs getScales
+ * gradientMag at the first real scale, :318-322, which must be the image's own size: nOctUp = 0; they are used verbatim whatever
+ * colorSpace and normRad say, as in the reference; 4 planes are refused on purpose, where the reference would drop the lone extra
+ * plane) and up to `max_batch` frames per call and `max_hits` hits per frame: runs getScales
  * (chnsPyramid.cpp:461-529) and the real/approximate split
  * (chnsPyramid.cpp:272-292), builds resampling tables and allocates every
  * device buffer.  Nothing is allocated after this call. */
@@ -460,7 +461,9 @@ enum {
     ACF_HIP_TAP_CHNS = 6,     /* unsmoothed, unpadded channels of a level: nChns planes [wC][hC] */
     ACF_HIP_TAP_LDCF = 7      /* LDCF level the cascade reads: nChns*k planes [round(wP/2)][round(hP/2)] (after acf_hip_detect) */
 };
-/* `index`: real-scale ordinal for taps 0-5, level for ACF_HIP_TAP_CHNS. */
+/* `index`: real-scale ordinal for taps 0-5, level for ACF_HIP_TAP_CHNS.  With five input planes, M, O, S and MNORM do not exist
+ * at ordinal 0 (the frame brought M and O; nothing is computed and the reference logs none of them, chnsCompute.cpp:265-269):
+ * ACF_HIP_E_INVALID. */
 ACF_HIP_API int acf_hip_read_tap(acf_hip_ctx* ctx, int frame, int tap, int index, float* host_out, int64_t cap_floats);
 
 /* ---- single operators on host planes ---------------------------------
@@ -482,13 +485,17 @@ ACF_HIP_API int acf_hip_op_gradient_mag(acf_hip_ctx* ctx, const float* in, float
  * *first_bad_bits = the smallest such pattern.  0 .. 0x7f7fffff (every finite m2 >= 0) must give 0. */
 ACF_HIP_API int acf_hip_selftest_gradmag(acf_hip_ctx* ctx, uint32_t first_bits, uint32_t last_bits, uint64_t* mismatches, uint32_t* first_bad_bits);
 /* Detector::chnsCompute (ACF.h:342-349, chnsCompute.cpp:146-338; addChn :340-370): the channels of ONE image at its own scale,
- * without a pyramid plan — crop to a multiple of shrink (:203-217), rgbConvert (:235; skipped for colorSpace orig / rgb and for
- * isLuv), convTri(I, I, pColor.smooth, 1) in place (:239), gradientMag with its normalisation (:263-283), gradientHist (:310-331),
- * every enabled type reduced by `shrink` (addChn's imResample) and concatenated: colour, magnitude, histogram.
+ * without a pyramid plan — crop to a multiple of shrink (:203-217), rgbConvert (:235; skipped for colorSpace orig / rgb, for
+ * isLuv and for a 1-plane image), convTri(I, I, pColor.smooth, 1) in place (:239), gradientMag with its normalisation (:263-283),
+ * gradientHist (:310-331), every enabled type reduced by `shrink` (addChn's imResample) and concatenated: colour, magnitude,
+ * histogram.
  *   p     the Options::Pyramid::Chns fields of acf_hip_params are read (shrink .. isLuv; classifier and pyramid fields ignored);
  *         NULL: the context's model (acf_hip_set_model)
  *   in    HOST planes [d][w][h], d = 1 or 3 — or 5: three image planes followed by the gradient magnitude and orientation that came
- *         with the image (chnsCompute.cpp:219-226: they replace gradientMag and its normalisation) —, the transposed planar layout
+ *         with the image (chnsCompute.cpp:219-226: they replace gradientMag and its normalisation, verbatim whatever colorSpace and
+ *         normRad say) —, the transposed planar layout.  d = 1 (colorSpace gray or orig, colorChn 0) is its own single colour plane
+ *         (rgbConvert.cpp:129-148): nChns = 1 + 1 + nOrients with every type on; unlike acf_hip_plan, which replicates it to three
+ *         planes first (chnsPyramid.cpp:234-244).  d = 4 is refused on purpose (the reference would drop the lone extra plane)
  *   out   HOST buffer of `cap` floats receiving [nChns][w / shrink][h / shrink] (cropped sizes); NULL: only the sizes are reported
  * *nChns, *hC, *wC (each may be NULL) receive the channel count and the cell-plane size.  Honours option "arith". */
 ACF_HIP_API int acf_hip_chns_compute(acf_hip_ctx* ctx, const acf_hip_params* p, const float* in, int h, int w, int d, float* out, int64_t cap,

@@ -345,8 +345,8 @@ def chns_pyramid(plan, frame, want_taps=False, want_chns=False):
 
 def chns_compute(model, frame):
     """Detector::chnsCompute as the oracle restates it, on one image [d][w][h]: crop to a multiple of shrink (chnsCompute.cpp:203-217),
-    rgbConvert (:235; acfo_rgb2luv / acfo_rgb2gray / acfo_rgb2hsv, skipped for orig / rgb / isLuv), then acfo_chns_compute (convTri in
-    place, gradMag, gradHist, addChn).  -> [nChns][w / shrink][h / shrink]."""
+    rgbConvert (:235; acfo_rgb2luv / acfo_rgb2gray / acfo_rgb2hsv, skipped for orig / rgb / isLuv and for a 1-plane image), then
+    acfo_chns_compute (convTri in place, gradMag, gradHist, addChn).  -> [nChns][w / shrink][h / shrink]."""
     o = lib()
     prm, keep = capi.make_params(model)
     frame = np.ascontiguousarray(frame, dtype=np.float32)
@@ -361,20 +361,23 @@ def chns_compute(model, frame):
     I = aligned_copy(frame[:, :wc, :hc])
     n = hc * wc
     cs = int(prm.colorSpace)
-    if d == 3 and (cs in (capi.CS_ORIG, capi.CS_RGB) or (prm.isLuv and cs == capi.CS_LUV)):
+    if d == 1:
+        # gray and orig pass a 1-plane image through (rgbConvert.cpp:129-148): no replication, which is chnsPyramid's alone
+        # (chnsPyramid.cpp:234-244); gradientMag then reads I[colorChn] of that one plane (chnsCompute.cpp:278-282)
+        if cs not in (capi.CS_GRAY, capi.CS_ORIG) or int(prm.colorChn) != 0:
+            raise ValueError("a 1-plane image needs colorSpace gray or orig and colorChn 0")
+        col = I
+    elif cs in (capi.CS_ORIG, capi.CS_RGB) or (prm.isLuv and cs == capi.CS_LUV):
         col = I
     elif cs == capi.CS_LUV:
         col = aligned((3, wc, hc))
         o.acfo_rgb2luv(F(I), F(col), n)
     elif cs == capi.CS_GRAY:
         col = aligned((1, wc, hc))
-        src = I if d == 3 else aligned_copy(np.repeat(I, 3, axis=0))
-        o.acfo_rgb2gray(F(src), F(col), n)
-    elif cs == capi.CS_HSV:
+        o.acfo_rgb2gray(F(I), F(col), n)
+    else:
         col = aligned((3, wc, hc))
         o.acfo_rgb2hsv(F(I), F(col), n)
-    else:
-        col = aligned_copy(np.repeat(I, 3, axis=0))
     dcol = col.shape[0]
     nC = (dcol if prm.colorEnabled else 0) + (1 if prm.gradMagEnabled else 0) + (int(prm.nOrients) if prm.gradHistEnabled else 0)
     out = aligned((nC, wc // sh, hc // sh))

@@ -331,3 +331,49 @@ def test_extreme_but_finite_planes_in_both_tiers(oracle, arith):
         assert np.isfinite(want).all()
         assert np.array_equal(bits(det.read_pyramid(f)), bits(want)), (arith, f)
     det.close()
+
+
+def test_tables_replaced_while_a_sub_batch_run_is_in_flight(oracle):
+    """acf_hip_set_x86_tables while an asynchronous run with option "streams" = 2 is in flight: the child contexts read the shared
+    tables on their own streams; the run joins them into the parent's stream, which the call synchronises before it overwrites the
+    tables.  The batch in flight must keep the tables it started with, the next batch must see the new ones.  (The race cannot be
+    forced; this pins the ordering.)"""
+    import torch
+    from acf_amd.detector import HipDetector
+    H, W = 240, 320
+    model = synth.make_model(seed=3, name="INRIA", nTrees=64)
+    frames = np.stack([synth.make_frame(15 + f, H, W, "rgb") for f in range(6)])
+    plan = oracle.Plan(model, H, W, 3)
+    xeon = oracle.x86_fixture()
+    z = np.load(os.path.join(GOLD, "x86_rcp_rsqrt_amd_epyc_9575f.npz"))
+    epyc = (np.ascontiguousarray(z["rcp"], np.uint32), np.ascontiguousarray(z["rsqrt"], np.uint32))
+    want = {}
+    try:
+        for name, t in (("xeon", xeon), ("epyc", epyc)):
+            oracle.set_x86_tables(*t)
+            want[name] = []
+            for f in range(6):
+                oracle.set_approx(3)
+                try:
+                    pyr, _, _ = oracle.chns_pyramid(plan, frames[f])
+                finally:
+                    oracle.set_approx(0)
+                want[name].append((pyr, oracle.detect(plan, pyr)))
+    finally:
+        oracle.set_x86_tables(*xeon)
+    assert any(not np.array_equal(bits(a[0]), bits(b[0])) for a, b in zip(want["xeon"], want["epyc"]))
+    det = HipDetector(model, H, W, 3, max_batch=6, max_hits=1 << 15, streams=2)
+    det.set_x86_tables(*xeon)
+    det.set_option("arith", 1)
+    fr = torch.from_numpy(frames).cuda()
+    torch.cuda.synchronize()
+    for name in ("xeon", "epyc"):
+        det.run(fr)
+        if name == "xeon":
+            det.set_x86_tables(*epyc)     # no synchronisation in between: the batch above is in flight
+        for f in range(6):
+            pyr, (d, h) = want[name][f]
+            assert np.array_equal(bits(det.read_pyramid(f)), bits(pyr)), (name, f)
+            got_d, got_h = det.detections(f)
+            assert got_d.tobytes() == d.tobytes() and got_h.tobytes() == h.tobytes(), (name, f)
+    det.close()

@@ -5,6 +5,8 @@ entries that compute the channels of ONE image at its own scale, without a pyram
    sizes that are not multiples of shrink), bit for bit; in the reference's arithmetic too (option "arith");
  * the oracle's single-scale function against its own pyramid (scale 1 of chnsPyramid IS chnsCompute of the converted frame):
    CPU, so the checker is not a second opinion of itself only;
+ * a 1-plane image I against the 3-plane orig image (I, I, I), on the oracle and the device: its one colour plane is I itself
+   (rgbConvert.cpp:129-148), not chnsPyramid's replication (chnsPyramid.cpp:234-244);
  * C++ acf::HipDetector::chnsCompute / computeChannels / setLogger / setReferenceArithmetic through the CLI.
 """
 import os
@@ -30,8 +32,10 @@ CASES = [
     ("luv_in_crop", 97, 131, "luv", 3, dict(name="TINY", isLuv=1)),          # 97 x 131 -> 96 x 128
     ("rgb_to_luv", 120, 150, "rgb", 3, dict(name="INRIA")),                  # 150 % 4 != 0
     ("rgb_to_luv_odd_n", 61, 45, "rgb", 3, dict(name="INRIA")),              # cropped to 60 x 44
-    ("gray", 240, 320, "gray", 1, dict(name="FACE64")),
+    ("gray_1plane", 240, 320, "gray", 1, dict(name="FACE64")),                                       # colour off; passes through
     ("gray_from_rgb", 64, 80, "rgb", 3, dict(name="FACE64", colorEnabled=1)),
+    ("gray_1plane_color", 96, 128, "gray", 1, dict(name="FACE64", colorEnabled=1)),                  # the plane passes through
+    ("orig_1plane", 96, 128, "gray", 1, dict(name="TINY", colorSpace=capi.CS_ORIG, isLuv=0)),       # one colour plane, not three
     ("hsv", 72, 88, "rgb", 3, dict(name="TINY", colorSpace=capi.CS_HSV, isLuv=0)),
     ("orig", 72, 88, "rgb", 3, dict(name="TINY", colorSpace=capi.CS_ORIG, isLuv=0)),
     ("no_hist", 96, 128, "luv", 3, dict(name="TINY", isLuv=1, gradHistEnabled=0)),
@@ -58,8 +62,48 @@ def test_oracle_single_scale_equals_its_pyramids_scale_one(oracle, case):
     if plan.levels[0].scale != 1.0:
         pytest.skip("first scale is not 1 (nOctUp)")
     _, _, chns = oracle.chns_pyramid(plan, frame, want_chns=True)
-    got = oracle.chns_compute(model, frame)
+    # chnsPyramid replicates a 1-plane image to three planes before chnsCompute sees it (chnsPyramid.cpp:234-244); chnsCompute
+    # itself passes one plane through (rgbConvert.cpp:129-148), so scale 1 is chnsCompute of the replicated image
+    got = oracle.chns_compute(model, np.repeat(frame, 3, 0) if d == 1 else frame)
     assert np.array_equal(bits(got), bits(chns[0]))
+
+
+ONE_PLANE = [("color", 96, 128, dict()), ("color_crop", 97, 131, dict()), ("no_color", 96, 128, dict(colorEnabled=0)),
+             ("shrink2_no_norm", 98, 130, dict(shrink=2, stride=2, normRad=0)), ("orients9_full_hardbin", 96, 128, dict(nOrients=9, full=1, softBin=-2))]
+
+
+def one_plane_identity(chns_compute, H, W, kw):
+    """chnsCompute of a 1-plane image I == chnsCompute of the 3-plane orig image (I, I, I) less its planes 1 and 2 (the colour
+    planes are I itself, the gradients come from plane colorChn = 0 of either) — an answer that does not rest on the 1-plane
+    reading; and gray == orig for a 1-plane image (both pass it through, rgbConvert.cpp:129-148).  Returns the channels."""
+    orig = synth.make_model(seed=3, nTrees=16, name="TINY", colorSpace=capi.CS_ORIG, isLuv=0, **kw)
+    gray = synth.make_model(seed=3, nTrees=16, name="TINY", colorSpace=capi.CS_GRAY, isLuv=0, **kw)
+    frame = synth.make_frame(23, H, W, "gray")
+    got = chns_compute(frame, orig)
+    three = chns_compute(np.repeat(frame, 3, 0), orig)
+    nO = orig["nOrients"]
+    if orig["colorEnabled"]:
+        assert got.shape[0] == 2 + nO and three.shape[0] == 4 + nO
+        assert np.array_equal(bits(got[:1]), bits(three[:1])) and np.array_equal(bits(got[1:]), bits(three[3:]))
+    else:
+        assert got.shape[0] == 1 + nO and np.array_equal(bits(got), bits(three))
+    assert np.array_equal(bits(chns_compute(frame, gray)), bits(got))
+    sh = orig["shrink"]
+    assert got.shape[1:] == (W // sh, H // sh)
+    return got
+
+
+@pytest.mark.parametrize("case", ONE_PLANE, ids=[c[0] for c in ONE_PLANE])
+def test_oracle_one_plane_chns_compute_is_the_plane_passed_through(oracle, case):
+    _, H, W, kw = case
+    one_plane_identity(lambda a, m: oracle.chns_compute(m, a), H, W, kw)
+
+
+def test_oracle_refuses_a_one_plane_image_it_cannot_read(oracle):
+    frame = synth.make_frame(23, 96, 128, "gray")
+    for kw in (dict(colorSpace=capi.CS_LUV, isLuv=0), dict(colorSpace=capi.CS_RGB, isLuv=0), dict(colorSpace=capi.CS_ORIG, isLuv=0, colorChn=1)):
+        with pytest.raises(ValueError):
+            oracle.chns_compute(synth.make_model(seed=3, nTrees=16, name="TINY", **kw), frame)
 
 
 @pytest.fixture(scope="module")
@@ -83,7 +127,30 @@ def test_chns_compute_equals_the_oracle(oracle, dev, case):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", [CASES[2], CASES[3], CASES[4], CASES[0]], ids=lambda c: c[0])
+@pytest.mark.parametrize("case", ONE_PLANE, ids=[c[0] for c in ONE_PLANE])
+def test_one_plane_chns_compute_is_the_plane_passed_through(oracle, dev, case):
+    _, H, W, kw = case
+    got = one_plane_identity(lambda a, m: dev.chns_compute(a, m), H, W, kw)
+    frame = synth.make_frame(23, H, W, "gray")
+    orig = synth.make_model(seed=3, nTrees=16, name="TINY", colorSpace=capi.CS_ORIG, isLuv=0, **kw)
+    assert np.array_equal(bits(got), bits(oracle.chns_compute(orig, frame)))
+
+
+@pytest.mark.gpu
+def test_one_plane_chns_compute_refusals(dev):
+    from acf_amd.detector import HipError
+    frame = synth.make_frame(23, 96, 128, "gray")
+    for kw in (dict(colorSpace=capi.CS_LUV, isLuv=0), dict(colorSpace=capi.CS_RGB, isLuv=0), dict(colorSpace=capi.CS_ORIG, isLuv=0, colorChn=1)):
+        with pytest.raises(HipError) as e:
+            dev.chns_compute(frame, synth.make_model(seed=3, nTrees=16, name="TINY", **kw))
+        assert e.value.code == capi.E_INVALID, kw
+
+
+ARITH_CASES = [c for c in CASES if c[0] in ("rgb_to_luv", "rgb_to_luv_odd_n", "gray_1plane", "luv_in", "gray_1plane_color", "orig_1plane")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ARITH_CASES, ids=lambda c: c[0])
 def test_chns_compute_in_reference_arithmetic(oracle, case):
     from acf_amd.detector import HipDetector
     _, H, W, kind, d, kw = case
@@ -171,6 +238,34 @@ def test_cli_static_chns_compute(cli, oracle, tmp_path, logger):
     taps = [l.split()[1] for l in p.stdout.splitlines() if l.startswith("tap ")]
     if logger:
         assert taps[:7] == ["L:96x132", "U:96x132", "V:96x132", "M:96x132", "Mnorm:96x132", "O:96x132", "H:144x33"]
+    else:
+        assert not taps
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("logger", [False, True])
+@pytest.mark.parametrize("cs", ["orig", "gray"])
+def test_cli_static_chns_compute_one_plane(cli, oracle, tmp_path, cs, logger):
+    """acf::HipDetector::chnsCompute on a 1-plane MatP: one colour plane passed through (rgbConvert.cpp:129-148), on the direct and
+    on the stage-by-stage logger path alike."""
+    H, W = 98, 133   # cropped to 96 x 132
+    kw = dict(name="TINY", colorSpace=capi.CS_ORIG, isLuv=0) if cs == "orig" else dict(name="FACE64", colorEnabled=1)
+    model = synth.make_model(seed=3, nTrees=16, **kw)
+    frames = [synth.make_frame(60 + i, H, W, "gray") for i in range(2)]
+    write_model(str(tmp_path / "m.acfm"), model)
+    (tmp_path / "f.raw").write_bytes(np.stack(frames).tobytes())
+    out = tmp_path / "c.raw"
+    p = run(cli, ["--model", str(tmp_path / "m.acfm"), "--frames", str(tmp_path / "f.raw"), "--rows", str(W), "--cols", str(H), "--channels", "1",
+                  "--count", "2", "--chns", str(out)] + (["--log-taps"] if logger else []))
+    lines = [l for l in p.stdout.splitlines() if l.startswith("chns ")]
+    assert lines[0] == "chns 0 types 3 [color channels|1|replicate|24x33] [gradient magnitude|1||24x33] [gradient histogram|6||24x33]"
+    got = np.fromfile(str(out), np.float32).reshape(2, 8, 33, 24)
+    for f in range(2):
+        assert np.array_equal(bits(got[f]), bits(oracle.chns_compute(model, frames[f]))), f
+    taps = [l.split()[1] for l in p.stdout.splitlines() if l.startswith("tap ")]
+    if logger:
+        assert taps[:5] == ["L:96x132", "M:96x132", "Mnorm:96x132", "O:96x132", "H:144x33"]   # exactly one colour plane
+        assert sum(t.split(":")[0] in ("L", "U", "V") for t in taps) == 2                       # (one per frame)
     else:
         assert not taps
 

@@ -13,6 +13,13 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+def _fnv1a(b):
+    h = 1469598103934665603
+    for x in b:
+        h = ((h ^ x) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
 CASES = [("luv", dict(name="TINY", nTrees=64, cascThr=-2.0), 120, 160),
          ("rgb", dict(name="TINY", nTrees=64, cascThr=-2.0, isLuv=0), 96, 128),
          ("luv", dict(name="FACE80", nTrees=128, minDs_h=80, minDs_w=80), 272, 480)]
@@ -149,3 +156,51 @@ def test_cpp_host_takes_five_plane_matp(oracle, tmp_path):
         assert np.array_equal(bits(chn[f]), bits(oracle.chns_compute(model, frames5[f]))), f
     taps = [l.split()[1].split(":")[0] for l in p.stdout.splitlines() if l.startswith("tap ")]
     assert taps[:4] == ["L", "U", "V", "H"]      # (M, Mnorm, O are not logged when they came with the image)
+
+
+@pytest.mark.gpu
+def test_cpp_host_pyramid_logger_with_five_planes(oracle, tmp_path):
+    """chnsPyramid(..., MatLoggerType) on a five-plane MatP: the first real scale logs L, U, V, H only — its M and O came with the
+    image, nothing computed them and the reference logs none of them (chnsCompute.cpp:265-269) —, every later real scale
+    L, U, V, M, Mnorm, O, H; tags and bytes those of the oracle's taps."""
+    import os
+    import subprocess
+    from acf_amd import capi
+    from acf_amd.modelio import write_model
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    host = os.path.join(root, "acf_amd", "host")
+    subprocess.check_call(["make", "-s", "-C", host])
+    H, W = 120, 160
+    model = synth.make_model(seed=3, name="TINY", nTrees=32)
+    frames5 = []
+    for f in range(2):
+        _, f5 = _with_own_mo(oracle, model, synth.make_frame(41 + f, H, W, "luv"), H, W)
+        f5[3] = np.roll(f5[3], 9 * f, axis=0)
+        frames5.append(f5)
+    write_model(str(tmp_path / "m.acfm"), model)
+    (tmp_path / "f.raw").write_bytes(np.stack(frames5).tobytes())
+    e = dict(os.environ)
+    e["ACF_HIP_LIBRARY"] = capi.LIB_PATH
+    p = subprocess.run([os.path.join(host, "acf_hip_detect"), "--model", str(tmp_path / "m.acfm"), "--frames", str(tmp_path / "f.raw"),
+                        "--rows", str(W), "--cols", str(H), "--channels", "5", "--count", "2", "--luv", "--log-taps"],
+                       env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
+    assert p.returncode == 0, p.stderr
+    got = [tuple(l.split()[1:]) for l in p.stdout.splitlines() if l.startswith("tap ")]
+    plan = oracle.Plan(model, H, W, 5)
+    nO = model["nOrients"]
+    want = []
+    for f in range(2):
+        _, taps, chns = oracle.chns_pyramid(plan, frames5[f], want_taps=True, want_chns=True)
+        for k, lvl in enumerate(plan.real):
+            t = taps[k]
+            w1, h1 = t["M"].shape
+            for z, name in enumerate("LUV"):
+                want.append(("%s:%dx%d" % (name, h1, w1), "%016x" % _fnv1a(np.ascontiguousarray(t["smoothed"][z]).tobytes())))
+            if k:
+                for name in ("M", "Mnorm", "O"):
+                    want.append(("%s:%dx%d" % (name, h1, w1), "%016x" % _fnv1a(np.ascontiguousarray(t[name]).tobytes())))
+            c = chns[lvl]
+            hc = np.concatenate([c[4 + b] for b in range(nO)], axis=1)
+            want.append(("H:%dx%d" % (hc.shape[1], hc.shape[0]), "%016x" % _fnv1a(np.ascontiguousarray(hc).tobytes())))
+    assert len(plan.real) > 1 and [g[0].split(":")[0] for g in got[:5]] == ["L", "U", "V", "H", "L"]
+    assert got == want
