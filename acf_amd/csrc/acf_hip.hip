@@ -75,9 +75,13 @@ struct LeafCodes
     int cap = 0, pitch = 0;
 };
 
-// Everything the cascade launch needs on the device.
+// Everything the cascade launch needs on the device, and what it was built for.
 struct CascState
 {
+    int cell = 0;    // pixels per cell: shrink, or 2 * shrink on the LDCF pyramid
+    int nLevels = 0; // levels of a frame
+    int batch = 0;   // frames the per-frame buffers hold
+    int maxHits = 0; // hits per frame d_hits, d_hitsX, d_sorted and d_dets hold (allocCascadeRun)
     CascLevel* d_cascLevels = nullptr;
     int32_t* d_blockLevel = nullptr;
     int blocksPerFrame = 0;
@@ -117,6 +121,24 @@ struct CascState
     uint16_t* d_pyrR = nullptr;
     int64_t pyrRCells = 0; // cells per frame
     int rankMaxWP = 0;
+};
+
+// The LDCF post-stage (acf_hip_params::ldcfK > 0; PlanBuild::ldcf, runLdcf): every level of the pyramid filtered (k 5x5 filters per
+// channel) and halved into the LDCF pyramid, on which the cascade then runs.
+struct LdcfStage
+{
+    std::vector<float> filters;        // the model's (acf_hip_set_model): they outlive a plan
+    std::vector<acf_hip_level> levels; // level table of the LDCF pyramid
+    int descBase = 0;                  // the levels' resample descriptors in h_descs / d_descs
+    int64_t floats = 0, tmpFloats = 0; // floats per frame of the LDCF pyramid and of the filtered scratch
+    float* d_filt = nullptr;
+    LdcfJob* d_jobs = nullptr;
+    // k_ldcf_tile (filters + half resample fused): flat list of output tiles over all levels, LDS geometry
+    LdcfTileJob* d_tileJobs = nullptr;
+    int tiles = 0, tileRows = 0, tileCols = 0;
+    int maxCells = 0, maxBlocks = 0; // k_ldcf_conv + k_resample (no tile list): grid sizes
+    float* d_tmp = nullptr;
+    float* d_pyr = nullptr;
 };
 
 // acf_hip_set_option's keys, one field each (OPTION_KEYS), except "graph" and "streams": those stay the parent's, and
@@ -219,19 +241,7 @@ struct acf_hip_ctx
     acf_hip_params p{};
     std::vector<uint32_t> fids, child;
     std::vector<float> thrs, hs;
-    // LDCF post-stage (acf_hip_params::ldcfK > 0): filters, level table of the LDCF pyramid, per-level resample descriptors
-    std::vector<float> ldcfFilters;
-    std::vector<acf_hip_level> ldcfLevels;
-    int ldcfDescBase = 0;
-    int64_t ldcfFloats = 0, ldcfTmpFloats = 0;
-    float* d_ldcfFilt = nullptr;
-    LdcfJob* d_ldcfJobs = nullptr;
-    // k_ldcf_tile (filters + half resample fused): flat list of output tiles over all levels, LDS geometry
-    LdcfTileJob* d_ldcfTileJobs = nullptr;
-    int ldcfTiles = 0, ldcfTileRows = 0, ldcfTileCols = 0;
-    int ldcfMaxCells = 0, ldcfMaxBlocks = 0;
-    float* d_ldcfTmp = nullptr;
-    float* d_ldcfPyr = nullptr;
+    LdcfStage ldcf;
 
     Plan plan;
     // image-specific lambdas (model without lambdas, chnsPyramid.cpp:341-374): per-frame plane sums of two real levels on
@@ -318,8 +328,7 @@ struct acf_hip_ctx
     std::vector<StreamSlot> slots;
     hipStream_t copyStream = nullptr;
     int stPix = 0, stStride = 0, stCap = 0, nextTicket = 0, nextCollect = 0;
-    // cascade (tables, model arrays, work queues, outputs): one value so that
-    // acf_hip_op_acf_detect1 can swap in a temporary set and restore the plan's
+    // the plan's cascade (tables, model arrays, work queues, outputs); acf_hip_op_acf_detect1 builds and runs a state of its own
     CascState cs;
     BoxLevel* d_boxLevels = nullptr;
     // device bbNms + prune (acf_hip_set_nms): survivors of every frame, what get_detections / export then return
@@ -341,10 +350,10 @@ struct acf_hip_ctx
     } rz;
 };
 
-// the ONE statement of "the plan has rank cells and option rank_cells is on"; each reader adds its own terms
-static inline bool rankCellsOn(const acf_hip_ctx* c)
+// the ONE statement of "the cascade state has rank cells and option rank_cells is on"; each reader adds its own terms
+static inline bool rankCellsOn(const acf_hip_ctx* c, const CascState& cs)
 {
-    return c->cs.tilesR.ok && c->opt.rankCells;
+    return cs.tilesR.ok && c->opt.rankCells;
 }
 
 #define HIPCHK(ctx, call)                                                                                  \
@@ -532,12 +541,9 @@ void freeAll(acf_hip_ctx* c)
     c->levelSegFrames = 0;
     c->d_color = c->d_stage = c->d_chns = c->d_pyr = nullptr; // a re-plan must not see the previous plan's buffers
     c->rz = acf_hip_ctx::InputResize();
-    c->d_ldcfFilt = c->d_ldcfTmp = c->d_ldcfPyr = nullptr;
-    c->d_ldcfJobs = nullptr;
-    c->d_ldcfTileJobs = nullptr;
+    c->ldcf = LdcfStage{ std::move(c->ldcf.filters) }; // (the model's filters stay where acf_hip_params::ldcfFilters points)
     c->d_nmsKeep = c->d_nmsN = c->d_nmsCounts = nullptr;
     c->d_nmsDets = nullptr;
-    c->ldcfTiles = 0;
     c->lastFrames = nullptr;
     c->pyramidValid = c->detectValid = false;
 }
@@ -1424,15 +1430,15 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
     }
     const size_t n = size_t(p->nTrees) * p->nTreeNodes;
     c->p = *p;
-    c->ldcfFilters.clear();
+    c->ldcf.filters.clear();
     c->p.ldcfK = ldcf ? p->ldcfK : 0;
     c->p.ldcfFilters = nullptr;
     if (ldcf)
     {
         const int dcol = p->colorSpace == ACF_HIP_CS_GRAY ? 1 : 3;
         const int nC = (p->colorEnabled ? dcol : 0) + (p->gradMagEnabled ? 1 : 0) + (p->gradHistEnabled ? p->nOrients : 0);
-        c->ldcfFilters.assign(p->ldcfFilters, p->ldcfFilters + size_t(p->ldcfK) * nC * 25);
-        c->p.ldcfFilters = c->ldcfFilters.data();
+        c->ldcf.filters.assign(p->ldcfFilters, p->ldcfFilters + size_t(p->ldcfK) * nC * 25);
+        c->p.ldcfFilters = c->ldcf.filters.data();
     }
     c->fids.assign(p->fids, p->fids + n);
     c->thrs.assign(p->thrs, p->thrs + n);
@@ -1458,7 +1464,7 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
     return ACF_HIP_OK;
 }
 
-#include "cascade_plan.hip.h"  // ShrinkScope, splitFid, pooledTileLds, buildTileSet, buildCascadeTables
+#include "cascade_plan.hip.h"  // splitFid, pooledTileLds, buildTileSet, buildCascadeTables, allocCascadeRun
 
 #include "resample_plan.hip.h" // stripPlan, launchStrip, resampleTilePlan
 
@@ -1591,12 +1597,12 @@ int acf_hip_get_ldcf_levels(const acf_hip_ctx* c, acf_hip_level* out, int cap)
         return ACF_HIP_E_INVALID;
     }
     const acf_hip_ctx* src = c->kids.empty() ? c : c->kids[0];
-    if (src->p.ldcfK <= 0 || src->ldcfLevels.empty())
+    if (src->p.ldcfK <= 0 || src->ldcf.levels.empty())
     {
         return ACF_HIP_E_INVALID;
     }
-    const int n = std::min(cap, int(src->ldcfLevels.size()));
-    std::copy(src->ldcfLevels.begin(), src->ldcfLevels.begin() + n, out);
+    const int n = std::min(cap, int(src->ldcf.levels.size()));
+    std::copy(src->ldcf.levels.begin(), src->ldcf.levels.begin() + n, out);
     return ACF_HIP_OK;
 }
 
@@ -2024,53 +2030,23 @@ int acf_hip_detect(acf_hip_ctx* c)
         return fail(c, ACF_HIP_E_INVALID, "detect: no pyramid (call acf_hip_pyramid)");
     }
     HIPCHK(c, hipSetDevice(c->device));
+    const bool ldcf = c->p.ldcfK > 0;
+    const int nF = c->lastBatch;
+    if (!ldcf && !c->floatPyramid && !(wholeCascadeTiled(c, c->cs) && rankCellsOn(c, c->cs) && c->ranksValid))
+    {
+        // (options changed between acf_hip_pyramid and acf_hip_detect: the float cells this path reads were never written)
+        return fail(c, ACF_HIP_E_INVALID, "detect: the float pyramid of this batch was not written (keep_pyramid = 0) and the selected cascade reads floats");
+    }
     int rc;
-    if (c->p.ldcfK > 0)
-    {
-        // LDCF: every level is filtered (k 5x5 filters per channel) into a scratch buffer, halved into the LDCF pyramid, and the
-        // cascade runs there with cells of 2*shrink pixels (include/acf_hip.h, acf_hip_params::ldcfK)
-        const Plan& pl = c->plan;
-        const int nF = c->lastBatch, nCk = pl.nChns * c->p.ldcfK;
-        const int nL = int(pl.levels.size());
-        if (c->ldcfTiles > 0)
-        {
-            // filters + half resample in one kernel: the filtered full-resolution planes stay in LDS
-            prof(c, "k_ldcf_tile");
-            const int xoT = 16;
-            const size_t ldsB = ldcfTileLdsFloats(c->ldcfTileRows, c->ldcfTileCols, xoT) * sizeof(float);
-            auto kern = &k_ldcf_tile<8, 4>;
-            if ((rc = allowLds(c, reinterpret_cast<const void*>(kern), ldsB)))
-            {
-                return rc;
-            }
-            hipLaunchKernelGGL(kern, dim3(c->ldcfTiles, pl.nChns, nF), dim3(256), ldsB, c->stream, (const float*)c->d_pyr, c->d_ldcfPyr,
-                (const float*)c->d_ldcfFilt, (const LdcfTileJob*)c->d_ldcfTileJobs, (const LdcfJob*)c->d_ldcfJobs,
-                (const ResampleDesc*)(c->d_descs + c->ldcfDescBase), (const int32_t*)c->d_it, (const float*)c->d_ft, c->ldcfTileRows, c->ldcfTileCols, xoT,
-                c->p.ldcfK, pl.nChns, pl.pyr_floats);
-            LAUNCHCHK(c, "k_ldcf_tile");
-        }
-        else
-        {
-            prof(c, "k_ldcf_conv");
-            hipLaunchKernelGGL(k_ldcf_conv, dim3(cdiv(c->ldcfMaxCells, 256), nCk, nF * nL), dim3(256), 0, c->stream, (const float*)c->d_pyr, c->d_ldcfTmp,
-                (const float*)c->d_ldcfFilt, (const LdcfJob*)c->d_ldcfJobs, nL, pl.nChns, pl.pyr_floats, c->ldcfTmpFloats);
-            LAUNCHCHK(c, "k_ldcf_conv");
-            prof(c, "k_resample(ldcf)");
-            hipLaunchKernelGGL(k_resample, dim3(c->ldcfMaxBlocks, nL, nF), dim3(64, 4), 0, c->stream, (const float*)c->d_ldcfTmp, c->d_ldcfPyr,
-                (const ResampleDesc*)(c->d_descs + c->ldcfDescBase), (const int32_t*)c->d_it, (const float*)c->d_ft, RS_XT);
-            LAUNCHCHK(c, "k_resample(ldcf)");
-        }
-        ShrinkScope ss(c, 2);
-        rc = runCascade(c, c->d_ldcfPyr, c->ldcfFloats, c->d_boxLevels, nF, nCk);
-    }
-    else
-    {
-        rc = runCascade(c, c->d_pyr, c->plan.pyr_floats, c->d_boxLevels, c->lastBatch, c->plan.nChns);
-    }
-    if (rc)
+    if ((ldcf && (rc = runLdcf(c, nF))) ||
+        (rc = runCascade(c, c->cs, ldcf ? c->ldcf.d_pyr : c->d_pyr, ldcf ? c->ldcf.floats : c->plan.pyr_floats, c->d_boxLevels, nF,
+             c->plan.nChns * std::max(c->p.ldcfK, 1), &c->ranksValid)) ||
+        (c->nmsOn && c->nms.type != 0 && (rc = launchNms(c, nF))))
     {
         return rc;
     }
+    prof(c, "(end)");
+    c->countsFetched = false;
     c->detectValid = true;
     return ACF_HIP_OK;
 }
@@ -2090,7 +2066,7 @@ static void graphRunState(acf_hip_ctx* c, const acf_hip_ctx::GraphSlot& gs)
 // frame waits for every node of the chain (runCascade / runCascadeTiled then skip their own memsets)
 static int preZeroCounters(acf_hip_ctx* c, int nF)
 {
-    if (!c || !c->hasPlan || !c->kids.empty() || !wholeCascadeTiled(c) || c->p.ldcfK > 0 || !c->cs.d_counts || !c->cs.d_qcounts || nF <= 0 ||
+    if (!c || !c->hasPlan || !c->kids.empty() || !wholeCascadeTiled(c, c->cs) || c->p.ldcfK > 0 || !c->cs.d_counts || !c->cs.d_qcounts || nF <= 0 ||
         nF > c->maxBatch)
     {
         return ACF_HIP_OK;
@@ -2854,7 +2830,7 @@ int acf_hip_read_rank_level(acf_hip_ctx* c, int frame, int level, uint16_t* host
         {
             return ACF_HIP_E_NOPLAN;
         }
-        if (!rankCellsOn(c))
+        if (!rankCellsOn(c, c->cs))
         {
             return fail(c, ACF_HIP_E_UNSUPPORTED, "read_rank_level: the plan has no rank cells (model not depth 2 / thresholds too dense / option rank_cells off / LDCF)");
         }
@@ -2937,13 +2913,13 @@ int acf_hip_read_tap(acf_hip_ctx* c, int frame, int tap, int index, float* host_
         int64_t n = 0;
         if (tap == ACF_HIP_TAP_LDCF)
         {
-            if (c->p.ldcfK <= 0 || !c->detectValid || index < 0 || index >= int(c->ldcfLevels.size()))
+            if (c->p.ldcfK <= 0 || !c->detectValid || index < 0 || index >= int(c->ldcf.levels.size()))
             {
                 return fail(c, ACF_HIP_E_INVALID, "read_tap: LDCF levels exist after acf_hip_detect on a model with ldcfK > 0");
             }
-            const acf_hip_level& l = c->ldcfLevels[size_t(index)];
+            const acf_hip_level& l = c->ldcf.levels[size_t(index)];
             n = int64_t(pl.nChns) * c->p.ldcfK * l.hP * l.wP;
-            src = c->d_ldcfPyr + size_t(frame) * c->ldcfFloats + l.offset;
+            src = c->ldcf.d_pyr + size_t(frame) * c->ldcf.floats + l.offset;
         }
         else if (tap == ACF_HIP_TAP_CHNS)
         {
@@ -3579,11 +3555,11 @@ int acf_hip_thrs_u8(const float* thrs, int n, uint8_t* out)
     return ACF_HIP_OK;
 }
 
-static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count);
+static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::vector<float>* thrs, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count);
 
 int acf_hip_op_acf_detect1(acf_hip_ctx* c, const float* chns, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count)
 {
-    return opAcfDetect1(c, chns, false, hP, wP, nChns, out, cap, count);
+    return opAcfDetect1(c, chns, false, nullptr, hP, wP, nChns, out, cap, count);
 }
 
 // The uint8_t body of acfDetect1 (acfDetect1.cpp:157-166,187-192): features and thresholds are bytes, compared after
@@ -3607,13 +3583,12 @@ int acf_hip_op_acf_detect1_u8(acf_hip_ctx* c, const uint8_t* chns, int hP, int w
     {
         wide[i] = float(thrsU8[i]);
     }
-    c->thrs.swap(wide);
-    const int rc = opAcfDetect1(c, chns, true, hP, wP, nChns, out, cap, count);
-    c->thrs.swap(wide);
-    return rc;
+    return opAcfDetect1(c, chns, true, &wide, hP, wP, nChns, out, cap, count);
 }
 
-static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count)
+// acfDetect1 on one caller's channel buffer: a cascade state of its own (one level, one frame, cap hits), built, run and freed
+// here.  The plan's state, its batch and its resident results are not touched.  thrs == nullptr: the model's thresholds.
+static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::vector<float>* thrs, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count)
 {
     OP_PROLOGUE(c);
     if (!c->hasModel)
@@ -3634,137 +3609,65 @@ static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, int hP, int w
     lv[0].nWinR = std::max(0, int(std::ceil(float(hP * p.shrink - p.modelDsPad_h + 1) / p.stride)));
     lv[0].nWinC = std::max(0, int(std::ceil(float(wP * p.shrink - p.modelDsPad_w + 1) / p.stride)));
     lv[0].offset = 0;
-    // temporary tables are registered in the context's allocation list only for the duration of this call;
-    // the plan's cascade state is swapped out and back
-    const size_t mark = c->allocs.size();
-    const int savedMaxHits = c->maxHits, savedMaxBatch = c->maxBatch;
-    const CascState saved = c->cs;
-    c->cs = CascState{};
-    auto restore = [&]() {
-        for (size_t i = mark; i < c->allocs.size(); i++)
-        {
-            (void)hipFree(c->allocs[i]);
-        }
-        c->allocs.resize(mark);
-        c->maxHits = savedMaxHits;
-        c->maxBatch = savedMaxBatch;
-        c->cs = saved;
-    };
-    BoxLevel* dBox = nullptr;
-    float* dChn = nullptr;
-    int rc = buildCascadeTables(c, lv, nChns, c->cs);
     std::vector<BoxLevel> box(1);
     box[0].shw_h = box[0].shw_w = 1.0;
     box[0].bw = p.modelDs_w;
     box[0].bh = p.modelDs_h;
-    c->maxHits = cap;
-    c->maxBatch = 1;
-    if (!rc)
+    // the temporary buffers are in the context's allocation list for the duration of this call only
+    struct Temporaries
     {
-        rc = devUpload(c, &dBox, box);
-    }
-    if (!rc)
-    {
-        rc = devUpload(c, &c->cs.d_thrs, c->thrs);
-    }
-    if (!rc)
-    {
-        rc = devUpload(c, &c->cs.d_hs, c->hs);
-    }
-    if (!rc)
-    {
-        rc = devUpload(c, &c->cs.d_child, c->child);
-    }
-    if (!rc)
-    {
-        rc = devUpload(c, &c->cs.d_fids, c->fids);
-    }
-    if (!rc)
-    {
-        rc = devAlloc(c, &c->cs.d_hits, size_t(cap));
-    }
-    if (!rc && c->cs.dedupQ > 1)
-    {
-        rc = devAlloc(c, &c->cs.d_hitsX, size_t(cap));
-    }
-    if (!rc)
-    {
-        rc = devAlloc(c, &c->cs.d_sorted, size_t(cap));
-    }
-    if (!rc)
-    {
-        rc = devAlloc(c, &c->cs.d_dets, size_t(cap));
-    }
-    if (!rc)
-    {
-        rc = devAlloc(c, &c->cs.d_counts, 1);
-    }
-    if (!rc)
-    {
-        c->cs.qcap = std::max(1, lv[0].nWinR * lv[0].nWinC);
-        rc = devAlloc(c, &c->cs.d_queue[0], size_t(c->cs.qcap));
-    }
-    if (!rc)
-    {
-        rc = devAlloc(c, &c->cs.d_queue[1], size_t(c->cs.qcap));
-    }
-    if (!rc)
-    {
-        rc = devAlloc(c, &c->cs.d_qcounts, 16);
-    }
-    if (!rc)
-    {
-        rc = devAlloc(c, &dChn, size_t(nChns) * hP * wP + 64);
-    }
-    if (!rc && !u8 && hipMemcpy(dChn, chns, sizeof(float) * nChns * hP * wP, hipMemcpyHostToDevice) != hipSuccess)
-    {
-        rc = fail(c, ACF_HIP_E_HIP, "op_acf_detect1: upload");
-    }
-    if (!rc && u8)
-    {
-        uint8_t* dBytes = nullptr;
-        const size_t n = size_t(nChns) * hP * wP;
-        rc = devAlloc(c, &dBytes, n);
-        if (!rc && hipMemcpy(dBytes, chns, n, hipMemcpyHostToDevice) != hipSuccess)
+        acf_hip_ctx* c;
+        size_t mark;
+        ~Temporaries()
         {
-            rc = fail(c, ACF_HIP_E_HIP, "op_acf_detect1_u8: upload");
-        }
-        if (!rc)
-        {
-            hipLaunchKernelGGL(k_widen_u8, dim3(cdiv(int64_t(n), 256)), dim3(256), 0, c->stream, (const uint8_t*)dBytes, dChn, int64_t(n));
-            if (hipGetLastError() != hipSuccess)
+            for (size_t i = mark; i < c->allocs.size(); i++)
             {
-                rc = fail(c, ACF_HIP_E_HIP, "launch k_widen_u8");
+                (void)hipFree(c->allocs[i]);
             }
+            c->allocs.resize(mark);
         }
-    }
-    if (!rc)
+    } temporaries{ c, c->allocs.size() };
+    const std::vector<float>& th = thrs ? *thrs : c->thrs;
+    const size_t n = size_t(nChns) * hP * wP;
+    CascState cs;
+    BoxLevel* dBox = nullptr;
+    float* dChn = nullptr;
+    uint8_t* dBytes = nullptr;
+    int rc;
+    if ((rc = buildCascadeTables(c, lv, nChns, p.shrink, 1, th, cs)) || (rc = allocCascadeRun(c, cs, lv, th, cap)) || (rc = devUpload(c, &dBox, box)) ||
+        (rc = devAlloc(c, &dChn, n + 64)) || (u8 && (rc = devAlloc(c, &dBytes, n))))
     {
-        rc = runCascade(c, dChn, 0, dBox, 1, nChns);
+        return rc;
     }
-    int n = 0;
-    if (!rc)
+    if (hipMemcpy(u8 ? static_cast<void*>(dBytes) : dChn, chns, n * (u8 ? 1 : sizeof(float)), hipMemcpyHostToDevice) != hipSuccess)
     {
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, c->cs.d_counts, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-        {
-            rc = fail(c, ACF_HIP_E_HIP, "op_acf_detect1: sync");
-        }
+        return fail(c, ACF_HIP_E_HIP, u8 ? "op_acf_detect1_u8: upload" : "op_acf_detect1: upload");
     }
-    if (!rc)
+    if (u8)
     {
-        *count = n;
-        const int m = std::min(n, cap);
-        if (m > 0 && out && hipMemcpy(out, c->cs.d_sorted, sizeof(acf_hip_hit) * m, hipMemcpyDeviceToHost) != hipSuccess)
+        hipLaunchKernelGGL(k_widen_u8, dim3(cdiv(int64_t(n), 256)), dim3(256), 0, c->stream, (const uint8_t*)dBytes, dChn, int64_t(n));
+        if (hipGetLastError() != hipSuccess)
         {
-            rc = fail(c, ACF_HIP_E_HIP, "op_acf_detect1: download");
-        }
-        if (!rc && n > cap)
-        {
-            rc = fail(c, ACF_HIP_E_CAPACITY, "op_acf_detect1: more hits than cap");
+            return fail(c, ACF_HIP_E_HIP, "launch k_widen_u8");
         }
     }
-    restore();
-    return rc;
+    if ((rc = runCascade(c, cs, dChn, 0, dBox, 1, nChns)))
+    {
+        return rc;
+    }
+    prof(c, "(end)");
+    int nHits = 0;
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&nHits, cs.d_counts, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+    {
+        return fail(c, ACF_HIP_E_HIP, "op_acf_detect1: sync");
+    }
+    *count = nHits;
+    const int m = std::min(nHits, cap);
+    if (m > 0 && out && hipMemcpy(out, cs.d_sorted, sizeof(acf_hip_hit) * m, hipMemcpyDeviceToHost) != hipSuccess)
+    {
+        return fail(c, ACF_HIP_E_HIP, "op_acf_detect1: download");
+    }
+    return nHits > cap ? fail(c, ACF_HIP_E_CAPACITY, "op_acf_detect1: more hits than cap") : ACF_HIP_OK;
 }
 
 int acf_hip_op_evaluate(acf_hip_ctx* c, const float* chns, int hP, int wP, int nChns, double cascThr, float* score)

@@ -2,17 +2,10 @@
 // tables.  buildTileSet: tile geometry, the tile list and the node records in tile-layout offsets of the LDS-tiled cascade
 // (k_cascade_tile3 / tile3D / tileD), on float cells or on 16-bit threshold-rank cells.  buildCascadeTables: everything
 // acf_hip_plan and acf_hip_op_acf_detect1 need for a list of level geometries — cids (acfDetect1.cpp:390-406), packed node
-// records, rank tables (host_plan.h), tile sets, tail tables, leaf-code buffers.
+// records, rank tables (host_plan.h), tile sets, tail tables, leaf-code buffers.  allocCascadeRun: the model uploads and the
+// per-batch buffers of a cascade run.  Both work on the CascState they are given: its cell size (shrink, or 2 * shrink on the
+// LDCF pyramid), its batch and hit capacities, and the thresholds the caller passes (the model's, or widened bytes).
 #pragma once
-
-// The cascade code reads the cell size from c->p.shrink; the LDCF cascade works on cells of 2*shrink pixels.
-struct ShrinkScope
-{
-    acf_hip_ctx* c;
-    int saved;
-    ShrinkScope(acf_hip_ctx* ctx, int factor) : c(ctx), saved(ctx->p.shrink) { c->p.shrink = saved * factor; }
-    ~ShrinkScope() { c->p.shrink = saved; }
-};
 
 // A feature id's channel, column and row in the model window (computeChannelIndexColMajor, acfDetect1.cpp:390-406).
 struct FeatPos
@@ -35,14 +28,15 @@ static size_t pooledTileLds(const TileGeom& g, int cellBytes, size_t leafBytes)
 
 // One set of tile tables for the levels lv into `out` (ok == false: no tiled form fits).  `rank` == nullptr: float cells,
 // thresholds as float bits; else 16-bit threshold-rank cells, thresholds as rank indices.
-static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nChns, const RankTables* rank, TileSet& out, bool allowPooledD = true)
+static int buildTileSet(acf_hip_ctx* c, const CascState& cs, const std::vector<float>& thrs, const std::vector<acf_hip_level>& lv, int nChns, const RankTables* rank,
+    TileSet& out, bool allowPooledD = true)
 {
     const acf_hip_params& p = c->p;
-    const int mH = p.modelDsPad_h / p.shrink, mW = p.modelDsPad_w / p.shrink;
+    const int mH = p.modelDsPad_h / cs.cell, mW = p.modelDsPad_w / cs.cell;
     const int cellBytes = rank ? 2 : 4, CPB = 16 / cellBytes; // cells per 16-byte fill chunk
     int rc;
     TileGeom g{};
-    g.step = p.stride / p.shrink;
+    g.step = p.stride / cs.cell;
     g.TR = 32;
     g.winFloats = nChns * mW * mH;
     // Stage boundaries.  k_cascade_tile3 (pooled survivors, the default for depth 2): dense [0,16) on every window, dense
@@ -141,7 +135,7 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
     }
     if (!nw)
     {
-        return pooledD ? buildTileSet(c, lv, nChns, rank, out, false) : ACF_HIP_OK;
+        return pooledD ? buildTileSet(c, cs, thrs, lv, nChns, rank, out, false) : ACF_HIP_OK;
     }
     g.NW = nw;
     g.W = W;
@@ -213,11 +207,11 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
                 d[tq * NN + k] = (f.z * uint32_t(g.colsT) + f.cc) * uint32_t(g.rowsP) + f.rr;
                 if (rank)
                 {
-                    d[TB * NN + tq * NN + k] = rank->rankOfThreshold(int(f.z), c->thrs[q + k]);
+                    d[TB * NN + tq * NN + k] = rank->rankOfThreshold(int(f.z), thrs[q + k]);
                 }
                 else
                 {
-                    memcpy(&d[TB * NN + tq * NN + k], &c->thrs[q + k], 4);
+                    memcpy(&d[TB * NN + tq * NN + k], &thrs[q + k], 4);
                 }
             }
             for (int j = 0; j < NL; j++)
@@ -229,7 +223,7 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
         {
             if (t1 != 32 || p.nTreeNodes < NN + NL || g.tileFloats > 65535)
             {
-                return buildTileSet(c, lv, nChns, rank, out, false); // (k_cascade_tileD + the staged queue)
+                return buildTileSet(c, cs, thrs, lv, nChns, rank, out, false); // (k_cascade_tileD + the staged queue)
             }
             std::vector<uint32_t> to(size_t(p.nTrees) * p.nTreeNodes, 0u), tr(rank ? size_t(p.nTrees) * p.nTreeNodes : 0, 0u);
             for (int t = 0; t < p.nTrees; t++)
@@ -240,7 +234,7 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
                     to[size_t(t) * p.nTreeNodes + k] = (f.z * uint32_t(g.colsT) + f.cc) * uint32_t(g.rowsP) + f.rr;
                     if (rank)
                     {
-                        tr[size_t(t) * p.nTreeNodes + k] = rank->rankOfThreshold(int(f.z), c->thrs[size_t(t) * p.nTreeNodes + k]);
+                        tr[size_t(t) * p.nTreeNodes + k] = rank->rankOfThreshold(int(f.z), thrs[size_t(t) * p.nTreeNodes + k]);
                     }
                 }
             }
@@ -271,12 +265,12 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
             a.off[k] = (f.z * uint32_t(g.colsT) + f.cc) * uint32_t(g.rowsP) + f.rr;
             if (rank)
             {
-                const uint32_t rk = rank->rankOfThreshold(int(f.z), c->thrs[q + k]);
+                const uint32_t rk = rank->rankOfThreshold(int(f.z), thrs[q + k]);
                 memcpy(&a.thr[k], &rk, 4);
             }
             else
             {
-                a.thr[k] = c->thrs[q + k];
+                a.thr[k] = thrs[q + k];
             }
         }
         for (int k = 0; k < 4; k++)
@@ -321,7 +315,7 @@ static int buildTileSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
 // The leaf-code buffer of a tail of nT trees, batch-wide.  Entries per frame with codes: 1/64 of the windows (the tail sees ~1/700
 // of them on natural images), at most 256 MB for the batch (the rows are touched per survivor: ~1k of them per 1080p frame);
 // whatever is beyond goes to the tail kernels, and so does everything if the buffer cannot be had (cap == 0).
-static LeafCodes leafCodeBuffer(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nT)
+static LeafCodes leafCodeBuffer(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nT, int batch)
 {
     LeafCodes lc;
     lc.pitch = (nT + 63) / 64 * 64; // stage E writes whole 64-tree batches
@@ -331,10 +325,10 @@ static LeafCodes leafCodeBuffer(acf_hip_ctx* c, const std::vector<acf_hip_level>
         nWinTotal += int64_t(std::max(l.nWinR, 0)) * std::max(l.nWinC, 0);
     }
     int64_t cap = std::min<int64_t>(std::max<int64_t>(nWinTotal / 64, 1024), 8192);
-    cap = std::min(cap, std::max<int64_t>((int64_t(1) << 28) / (int64_t(std::max(c->maxBatch, 1)) * lc.pitch), 256));
+    cap = std::min(cap, std::max<int64_t>((int64_t(1) << 28) / (int64_t(std::max(batch, 1)) * lc.pitch), 256));
     cap = std::min<int64_t>(cap, std::max<int64_t>(nWinTotal, 1));
     void* codes = nullptr;
-    if (hipMalloc(&codes, size_t(std::max(c->maxBatch, 1)) * size_t(cap) * size_t(lc.pitch)) == hipSuccess)
+    if (hipMalloc(&codes, size_t(std::max(batch, 1)) * size_t(cap) * size_t(lc.pitch)) == hipSuccess)
     {
         c->allocs.push_back(codes);
         lc.d = static_cast<uint8_t*>(codes);
@@ -349,9 +343,10 @@ static LeafCodes leafCodeBuffer(acf_hip_ctx* c, const std::vector<acf_hip_level>
 
 // The rank tables of the model's thresholds (host_plan.h; they do not depend on the depth) and, if there are any, the tile set
 // over rank cells; `internal`: which nodes carry a feature test.
-static int buildRankSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nChns, const std::vector<uint8_t>& internal, RankTables& rt, TileSet& ts)
+static int buildRankSet(acf_hip_ctx* c, const CascState& cs, const std::vector<float>& thrs, const std::vector<acf_hip_level>& lv, int nChns,
+    const std::vector<uint8_t>& internal, RankTables& rt, TileSet& ts)
 {
-    const int mH = c->p.modelDsPad_h / c->p.shrink, mW = c->p.modelDsPad_w / c->p.shrink;
+    const int mH = c->p.modelDsPad_h / cs.cell, mW = c->p.modelDsPad_w / cs.cell;
     std::vector<int32_t> chnOfNode(internal.size(), -1);
     for (size_t q = 0; q < internal.size(); q++)
     {
@@ -360,21 +355,20 @@ static int buildRankSet(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, in
             chnOfNode[q] = int32_t(splitFid(c->fids[q], mW, mH).z);
         }
     }
-    buildRankTables(c->thrs.data(), chnOfNode.data(), internal.size(), nChns, rt);
-    return rt.ok ? buildTileSet(c, lv, nChns, &rt, ts) : ACF_HIP_OK;
+    buildRankTables(thrs.data(), chnOfNode.data(), internal.size(), nChns, rt);
+    return rt.ok ? buildTileSet(c, cs, thrs, lv, nChns, &rt, ts) : ACF_HIP_OK;
 }
 
-// Build the cascade tables for a list of level geometries (hP, wP) into the
-// context.  Shared by acf_hip_plan and acf_hip_op_acf_detect1.
-static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nChns, CascState& cs, bool wantRank = false)
+// Build the cascade tables for a list of level geometries (hP, wP) with cells of `cell` pixels and the node thresholds `thrs`
+// into `cs`, for batches of up to `batch` frames.  Shared by acf_hip_plan and acf_hip_op_acf_detect1.
+static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& lv, int nChns, int cell, int batch, const std::vector<float>& thrs, CascState& cs,
+    bool wantRank = false)
 {
-    CascLevel** d_levels = &cs.d_cascLevels;
-    int32_t** d_blockLevel = &cs.d_blockLevel;
-    int* blocksPerFrame = &cs.blocksPerFrame;
-    uint32_t** d_cidAll = &cs.d_cidAll;
-    CascNode2** d_nodes2 = &cs.d_nodes2;
+    cs.cell = cell;
+    cs.batch = batch;
+    cs.nLevels = int(lv.size());
     const acf_hip_params& p = c->p;
-    const int mH = p.modelDsPad_h / p.shrink, mW = p.modelDsPad_w / p.shrink;
+    const int mH = p.modelDsPad_h / cell, mW = p.modelDsPad_w / cell;
     const uint32_t nF = uint32_t(nChns) * mH * mW;
     const size_t nNodes = size_t(p.nTrees) * p.nTreeNodes;
     const bool packed = p.treeDepth == 2;
@@ -407,7 +401,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
         }
     }
     int block = 0;
-    cs.dedupQ = (p.stride < p.shrink && p.shrink % p.stride == 0 && !fallbackForced(FB_NO_DEDUP)) ? p.shrink / p.stride : 1;
+    cs.dedupQ = (p.stride < cell && cell % p.stride == 0 && !fallbackForced(FB_NO_DEDUP)) ? cell / p.stride : 1;
     std::vector<int2> realWin(lv.size());
     for (size_t i = 0; i < lv.size(); i++)
     {
@@ -473,7 +467,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             {
                 const FeatPos f = splitFid(c->fids[q + k], mW, mH);
                 nd.zcr[k] = (f.z << 24) | (f.cc << 12) | f.rr;
-                nd.thr[k] = c->thrs[q + k];
+                nd.thr[k] = thrs[q + k];
             }
             for (int k = 0; k < 4; k++)
             {
@@ -482,25 +476,25 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             nodes2.push_back(nd);
         }
     }
-    *blocksPerFrame = block;
+    cs.blocksPerFrame = block;
     int rc;
     if (cs.dedupQ > 1 && (rc = devUpload(c, &cs.d_realWin, realWin)))
     {
         return rc;
     }
-    if ((rc = devUpload(c, d_levels, cl)))
+    if ((rc = devUpload(c, &cs.d_cascLevels, cl)))
     {
         return rc;
     }
-    if ((rc = devUpload(c, d_blockLevel, bl)))
+    if ((rc = devUpload(c, &cs.d_blockLevel, bl)))
     {
         return rc;
     }
-    if ((rc = devUpload(c, d_cidAll, cidAll)))
+    if ((rc = devUpload(c, &cs.d_cidAll, cidAll)))
     {
         return rc;
     }
-    if ((rc = devUpload(c, d_nodes2, nodes2)))
+    if ((rc = devUpload(c, &cs.d_nodes2, nodes2)))
     {
         return rc;
     }
@@ -508,14 +502,14 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
     cs.tiles = TileSet{};
     cs.tilesR = TileSet{};
     cs.codes = LeafCodes{};
-    const bool tiled = p.treeDepth >= 1 && p.treeDepth <= 4 && p.stride % p.shrink == 0 && p.stride >= p.shrink;
+    const bool tiled = p.treeDepth >= 1 && p.treeDepth <= 4 && p.stride % cell == 0 && p.stride >= cell;
     if (!packed && p.treeDepth >= 1 && p.treeDepth <= 4 && p.nTrees > 128 && !fallbackForced(FB_NO_TAIL_CODES))
     {
         // the staged path's last stage [128, nTrees) as leaf codes + ordered scan, when the scan's leaf table fits a workgroup's LDS
         const int nT = p.nTrees - 128, NL = 1 << p.treeDepth;
         if (int64_t((nT + 15) / 16 * 16) * NL * 4 <= 150 * 1024)
         {
-            cs.codes = leafCodeBuffer(c, lv, nT);
+            cs.codes = leafCodeBuffer(c, lv, nT, batch);
         }
     }
     // the rank pyramid of a plan: per level nChns planes [wP][pitchR], pitchR = hP rounded up to 8 cells (16 bytes); bucket tables on
@@ -542,19 +536,19 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
         int rcl;
         // + slack: a tile's 16-byte fill chunks run up to rowsP cells past the last column of the last plane
         if ((rcl = devUpload(c, &cs.d_rankChan, rt.chan)) || (rcl = devUpload(c, &cs.d_rankRec, rt.rec)) || (rcl = devUpload(c, &cs.d_rankJobs, jobs)) ||
-            (rcl = devAlloc(c, &cs.d_pyrR, size_t(std::max(c->maxBatch, 1)) * size_t(off) + 4096)))
+            (rcl = devAlloc(c, &cs.d_pyrR, size_t(std::max(cs.batch, 1)) * size_t(off) + 4096)))
         {
             return rcl;
         }
-        HIPCHK(c, hipMemset(cs.d_pyrR, 0, (size_t(std::max(c->maxBatch, 1)) * size_t(off) + 4096) * sizeof(uint16_t))); // pitch padding cells: defined
-        HIPCHK(c, hipMemcpy(*d_levels, cl.data(), cl.size() * sizeof(CascLevel), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemset(cs.d_pyrR, 0, (size_t(std::max(cs.batch, 1)) * size_t(off) + 4096) * sizeof(uint16_t))); // pitch padding cells: defined
+        HIPCHK(c, hipMemcpy(cs.d_cascLevels, cl.data(), cl.size() * sizeof(CascLevel), hipMemcpyHostToDevice));
         return ACF_HIP_OK;
     };
     if (!packed && tiled)
     {
         // depths 1, 3, 4: the staged path's first stages from LDS tiles
         TileSet ts;
-        if ((rc = buildTileSet(c, lv, nChns, nullptr, ts)))
+        if ((rc = buildTileSet(c, cs, thrs, lv, nChns, nullptr, ts)))
         {
             return rc;
         }
@@ -567,7 +561,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             {
                 RankTables rt;
                 TileSet tsR;
-                if ((rc = buildRankSet(c, lv, nChns, internal, rt, tsR)))
+                if ((rc = buildRankSet(c, cs, thrs, lv, nChns, internal, rt, tsR)))
                 {
                     return rc;
                 }
@@ -586,7 +580,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
     {
         // depth 2: k_cascade_tile3 + stage E + k_tail_scan, k_cascade_tail3 for queue overflow
         TileSet ts;
-        if ((rc = buildTileSet(c, lv, nChns, nullptr, ts)))
+        if ((rc = buildTileSet(c, cs, thrs, lv, nChns, nullptr, ts)))
         {
             return rc;
         }
@@ -614,7 +608,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
                 for (int k = 0; k < 3; k++)
                 {
                     b.off[k] = c->fids[q + k];
-                    b.thr[k] = c->thrs[q + k];
+                    b.thr[k] = thrs[q + k];
                 }
                 for (int k = 0; k < 4; k++)
                 {
@@ -625,7 +619,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             cs.tailWaves = tw;
             cs.tailSlab = tailSlab;
             cs.tailPad = (std::max(p.nTrees - g.b[4], 1) + 63) / 64 * 64;
-            cs.tailBlocks = std::max(512, c->maxBatch);
+            cs.tailBlocks = std::max(512, cs.batch);
             // k_cascade_tail3 only takes queue overflow now: its LDS stays small (footprint slabs only, node table from
             // L2) so that its blocks — which leave at once in the normal case — never wait for a whole CU's LDS while
             // other streams' kernels are resident (measured: up to 2.7 ms of queueing per launch with 156 KB blocks)
@@ -636,7 +630,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             }
             if (g.b[4] < p.nTrees && !fallbackForced(FB_TAIL3)) // (forced: every tail window goes to k_cascade_tail3)
             {
-                cs.codes = leafCodeBuffer(c, lv, p.nTrees - g.b[4]);
+                cs.codes = leafCodeBuffer(c, lv, p.nTrees - g.b[4], batch);
             }
             if ((rc = devUpload(c, &cs.d_tailNodes, tailNodes)))
             {
@@ -648,7 +642,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
             {
                 RankTables rt;
                 TileSet tsR;
-                if ((rc = buildRankSet(c, lv, nChns, internal, rt, tsR)))
+                if ((rc = buildRankSet(c, cs, thrs, lv, nChns, internal, rt, tsR)))
                 {
                     return rc;
                 }
@@ -667,7 +661,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
                         {
                             const FeatPos f = splitFid(c->fids[q + k], mW, mH);
                             b.off[k] = (f.z << 24) | (f.cc << 12) | f.rr; // (mW, mH <= 4095 and nChns <= 255: checked for the packed node table above)
-                            const uint32_t rk = rt.rankOfThreshold(int(f.z), c->thrs[q + k]);
+                            const uint32_t rk = rt.rankOfThreshold(int(f.z), thrs[q + k]);
                             memcpy(&b.thr[k], &rk, 4);
                         }
                         for (int k = 0; k < 4; k++)
@@ -684,6 +678,30 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
                 }
             }
         }
+    }
+    return ACF_HIP_OK;
+}
+
+// The model uploads and the per-batch buffers of a cascade run over the levels lv, for cs.batch frames (buildCascadeTables) of up
+// to max_hits hits each.
+static int allocCascadeRun(acf_hip_ctx* c, CascState& cs, const std::vector<acf_hip_level>& lv, const std::vector<float>& thrs, int max_hits)
+{
+    const size_t B = size_t(cs.batch);
+    int64_t nWinTotal = 0;
+    for (const auto& l : lv)
+    {
+        nWinTotal += int64_t(l.nWinR) * l.nWinC;
+    }
+    cs.maxHits = max_hits;
+    cs.qcap = int(std::max<int64_t>(nWinTotal, 1));
+    int rc;
+    if ((rc = devUpload(c, &cs.d_thrs, thrs)) || (rc = devUpload(c, &cs.d_hs, c->hs)) || (rc = devUpload(c, &cs.d_child, c->child)) ||
+        (rc = devUpload(c, &cs.d_fids, c->fids)) || (cs.dedupQ > 1 && (rc = devAlloc(c, &cs.d_hitsX, B * max_hits))) ||
+        (rc = devAlloc(c, &cs.d_hits, B * max_hits)) || (rc = devAlloc(c, &cs.d_sorted, B * max_hits)) || (rc = devAlloc(c, &cs.d_dets, B * max_hits)) ||
+        (rc = devAlloc(c, &cs.d_counts, B)) || (rc = devAlloc(c, &cs.d_queue[0], B * cs.qcap)) || (rc = devAlloc(c, &cs.d_queue[1], B * cs.qcap)) ||
+        (rc = devAlloc(c, &cs.d_qcounts, 8 * B + 8))) // (+ 8: k_cascade_tile3's tile counters, one per XCD)
+    {
+        return rc;
     }
     return ACF_HIP_OK;
 }

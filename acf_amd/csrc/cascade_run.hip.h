@@ -3,7 +3,13 @@
 //                     k_cascade_tail3 / _tail_rank for what does not fit the code buffers)
 //   runTileStageD     depths 1, 3, 4: the staged path's first stages from LDS tiles (k_cascade_tile3D / tileD)
 //   runCascade        acfDetect1 on every level of a batch (tiled or staged), k_expand_hits for stride < shrink, k_sort_map
-//                     (scale-ordered output + box mapping, ACF.cpp:302-329), launchNms (bbNms + prune on the device)
+//                     (scale-ordered output + box mapping, ACF.cpp:302-329)
+//   launchNms         bbNms + prune of the plan's batch on the device
+//   runLdcf           the LDCF post-stage: the pyramid filtered and halved into the LDCF pyramid
+// The cascade functions run on the CascState they are given (cell size, capacities, buffers): the plan's, or the one
+// acf_hip_op_acf_detect1 built for its caller's buffer.  `ranks` != nullptr says that the cells are the plan's pyramid of the
+// current batch: rank cells may stand for them, *ranks tells whether they have been written, and acf_hip_run may have cleared
+// the counters already.
 #pragma once
 
 static int allowLds(acf_hip_ctx* c, const void* kernel, size_t bytes)
@@ -116,15 +122,14 @@ static TileDKernel tileDKernel(int nw, int depth)
 
 // depth 2 with a float tile set and option cascade_tiles: runCascadeTiled takes the whole cascade (runCascade's branch and
 // acf_hip_run's early counter clear both ask this)
-static inline bool wholeCascadeTiled(const acf_hip_ctx* c)
+static inline bool wholeCascadeTiled(const acf_hip_ctx* c, const CascState& cs)
 {
-    return c->cs.tiles.ok && c->p.treeDepth == 2 && c->opt.cascadeTiles;
+    return cs.tiles.ok && c->p.treeDepth == 2 && c->opt.cascadeTiles;
 }
 
 // the float pyramid -> threshold-rank cells (levels whose kernels did not emit them): the one k_rank launch
-static int launchRankCells(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int nF, int nChns)
+static int launchRankCells(acf_hip_ctx* c, const CascState& cs, const float* pyr, int64_t pyr_fs, int nF, int nChns)
 {
-    const CascState& cs = c->cs;
     const size_t ldsR = size_t(cs.rankMaxRec) * sizeof(RankRec);
     int rc;
     if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_rank), ldsR)))
@@ -132,10 +137,9 @@ static int launchRankCells(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
         return rc;
     }
     prof(c, "k_rank");
-    hipLaunchKernelGGL(k_rank, dim3(cdiv(cs.rankMaxWP, RANK_CHUNK_COLS), int(c->plan.levels.size()) * nChns, nF), dim3(256), ldsR, c->stream, pyr, pyr_fs,
+    hipLaunchKernelGGL(k_rank, dim3(cdiv(cs.rankMaxWP, RANK_CHUNK_COLS), cs.nLevels * nChns, nF), dim3(256), ldsR, c->stream, pyr, pyr_fs,
         cs.d_pyrR, cs.pyrRCells, (const RankJob*)cs.d_rankJobs, nChns, (const RankChan*)cs.d_rankChan, (const RankRec*)cs.d_rankRec);
     LAUNCHCHK(c, "k_rank");
-    c->ranksValid = true;
     return ACF_HIP_OK;
 }
 
@@ -168,14 +172,13 @@ static void setTiles(TileArgs& a, const TileSet& ts)
     a.aTB = ts.aTB;
 }
 
-static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int nF, int nChns)
+static int runCascadeTiled(acf_hip_ctx* c, const CascState& cs, const float* pyr, int64_t pyr_fs, int nF, int nChns, bool* ranks)
 {
     const acf_hip_params& p = c->p;
-    const CascState& cs = c->cs;
     const TileGeom& g = cs.tiles.g;
-    if (!c->countersZeroed)
+    if (!(ranks && c->countersZeroed))
     {
-        HIPCHK(c, hipMemsetAsync(cs.d_qcounts, 0, sizeof(int32_t) * (2 * size_t(c->maxBatch) + 8), c->stream));
+        HIPCHK(c, hipMemsetAsync(cs.d_qcounts, 0, sizeof(int32_t) * (2 * size_t(cs.batch) + 8), c->stream));
     }
     TileArgs a{};
     setTiles(a, cs.tiles);
@@ -184,19 +187,19 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
     a.levels = cs.d_cascLevels;
     a.nFrames = nF;
     a.nChns = nChns;
-    a.mH = p.modelDsPad_h / p.shrink;
-    a.mW = p.modelDsPad_w / p.shrink;
+    a.mH = p.modelDsPad_h / cs.cell;
+    a.mW = p.modelDsPad_w / cs.cell;
     a.nTrees = p.nTrees;
     a.tailNodes = cs.d_tailNodes;
     a.cascThr = float(p.cascThr); // DetectionParams::cascThr is a float (acfDetect1.cpp:63,323)
     a.q = cs.d_queue[0];
     a.qcount = cs.d_qcounts;
-    a.qhead = cs.d_qcounts + c->maxBatch;
-    a.tileNext = cs.d_qcounts + 2 * size_t(c->maxBatch);
+    a.qhead = cs.d_qcounts + cs.batch;
+    a.tileNext = cs.d_qcounts + 2 * size_t(cs.batch);
     a.qcap = cs.qcap;
     a.hits = cs.d_hits;
     a.counts = cs.d_counts;
-    a.maxHits = c->maxHits;
+    a.maxHits = cs.maxHits;
     a.tailScratch = cs.d_tailScratch;
     a.tailPad = cs.tailPad;
     a.tailSlab = cs.tailSlab;
@@ -216,11 +219,15 @@ static int runCascadeTiled(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int
         HIPCHK(c, hipMalloc(&a.stamps, size_t((total + 7) / 8 * 8) * 8 * sizeof(long long)));
         HIPCHK(c, hipMemsetAsync(a.stamps, 0, size_t((total + 7) / 8 * 8) * 8 * sizeof(long long), c->stream));
     }
-    const bool rank = rankCellsOn(c) && pyr == c->d_pyr;
+    const bool rank = ranks && rankCellsOn(c, cs);
     int rc = 0;
-    if (rank && !c->ranksValid && (rc = launchRankCells(c, pyr, pyr_fs, nF, nChns)))
+    if (rank && !*ranks)
     {
-        return rc;
+        if ((rc = launchRankCells(c, cs, pyr, pyr_fs, nF, nChns)))
+        {
+            return rc;
+        }
+        *ranks = true;
     }
     if (cs.tiles.nTiles > 0)
     {
@@ -336,22 +343,23 @@ static void fillNmsArgs(NmsArgs& a, const acf_hip_nms_params& q)
     a.pruneRatio = q.pruneRatio;
 }
 
-// bbNms + prune of every frame's detections (k_nms, one workgroup per frame)
+// bbNms + prune of every frame's detections of the plan's batch (k_nms, one workgroup per frame)
 static int launchNms(acf_hip_ctx* c, int nF)
 {
+    const CascState& cs = c->cs;
     int rc;
     if (!c->d_nmsKeep)
     {
-        if ((rc = devAlloc(c, &c->d_nmsKeep, size_t(c->maxBatch) * NMS_CAP)) || (rc = devAlloc(c, &c->d_nmsN, size_t(c->maxBatch))) ||
-            (rc = devAlloc(c, &c->d_nmsCounts, size_t(c->maxBatch))) || (rc = devAlloc(c, &c->d_nmsDets, size_t(c->maxBatch) * c->maxHits)))
+        if ((rc = devAlloc(c, &c->d_nmsKeep, size_t(cs.batch) * NMS_CAP)) || (rc = devAlloc(c, &c->d_nmsN, size_t(cs.batch))) ||
+            (rc = devAlloc(c, &c->d_nmsCounts, size_t(cs.batch))) || (rc = devAlloc(c, &c->d_nmsDets, size_t(cs.batch) * cs.maxHits)))
         {
             return rc;
         }
     }
     NmsArgs a{};
-    a.dets = c->cs.d_dets;
-    a.counts = c->cs.d_counts;
-    a.maxHits = c->maxHits;
+    a.dets = cs.d_dets;
+    a.counts = cs.d_counts;
+    a.maxHits = cs.maxHits;
     fillNmsArgs(a, c->nms);
     a.keep = c->d_nmsKeep;
     a.nKeep = c->d_nmsN;
@@ -376,11 +384,11 @@ static inline bool nmsActive(const acf_hip_ctx* c)
 // the tail's leaf codes from its stage E; k_cascade_tileD: trees [0, t1D)) instead of the staged path's first per-lane gathers
 // from the pyramid.  Its survivors enter the queue of the stage that ends at `end`.  firstStage: the first stage the staged path
 // still runs (0 when no stage ends there: the tile kernel does not run); pooledTail: the tile kernel has written the tail's leaf codes.
-static int runTileStageD(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int nF, int nChns, const std::vector<int>& bounds, int& firstStage, bool& pooledTail)
+static int runTileStageD(acf_hip_ctx* c, const CascState& cs, const float* pyr, int64_t pyr_fs, int nF, int nChns, bool* ranks, const std::vector<int>& bounds,
+    int& firstStage, bool& pooledTail)
 {
     const acf_hip_params& p = c->p;
-    const CascState& cs = c->cs;
-    const bool rank = rankCellsOn(c) && pyr == c->d_pyr;
+    const bool rank = ranks && rankCellsOn(c, cs);
     const TileSet& ts = rank ? cs.tilesR : cs.tiles; // (the rank set is always pooled)
     const int end = ts.g.pooled ? ts.g.b[4] : ts.t1D; // last tree the tile kernel evaluates
     const int nStages = int(bounds.size());
@@ -410,19 +418,20 @@ static int runTileStageD(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int n
     at.cascThr = float(p.cascThr);
     at.last = sD == nStages - 1;
     at.qout = cs.d_queue[sD & 1];
-    at.qoutCount = cs.d_qcounts + size_t(sD) * c->maxBatch;
+    at.qoutCount = cs.d_qcounts + size_t(sD) * cs.batch;
     at.qcap = cs.qcap;
     at.hits = cs.d_hits;
     at.counts = cs.d_counts;
-    at.maxHits = c->maxHits;
+    at.maxHits = cs.maxHits;
     const int64_t total = int64_t(ts.nTiles) * nF;
     int rc = 0;
-    if (rank && !c->ranksValid)
+    if (rank && !*ranks)
     {
-        if ((rc = launchRankCells(c, pyr, pyr_fs, nF, nChns)))
+        if ((rc = launchRankCells(c, cs, pyr, pyr_fs, nF, nChns)))
         {
             return rc;
         }
+        *ranks = true;
         prof(c, "k_cascade");
     }
     // k_cascade_tile3D on a pooled set (persistent workgroups where option tile_persist says so), else k_cascade_tileD
@@ -449,7 +458,7 @@ static int runTileStageD(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int n
         lds = pooledTileLds(ts.g, rank ? 2 : 4, size_t(128) * 4 << p.treeDepth);
         tg = tileGrid(c, lds, total);
         // (the staged path's counters [stage][frame] start at d_qcounts; the tile counters sit behind them)
-        at.tileNext = tg.persist ? cs.d_qcounts + size_t(8) * c->maxBatch : nullptr;
+        at.tileNext = tg.persist ? cs.d_qcounts + size_t(8) * cs.batch : nullptr;
         if (tg.persist)
         {
             HIPCHK(c, hipMemsetAsync(at.tileNext, 0, sizeof(int32_t) * 8, c->stream));
@@ -470,26 +479,19 @@ static int runTileStageD(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, int n
     return ACF_HIP_OK;
 }
 
-static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const BoxLevel* d_box, int nF, int nChns)
+static int runCascade(acf_hip_ctx* c, const CascState& cs, const float* pyr, int64_t pyr_fs, const BoxLevel* d_box, int nF, int nChns, bool* ranks = nullptr)
 {
     const acf_hip_params& p = c->p;
-    const CascState& cs = c->cs;
     const int blocksPerFrame = cs.blocksPerFrame;
     prof(c, "k_cascade");
-    const bool rankPath = wholeCascadeTiled(c) && rankCellsOn(c);
-    if (pyr == c->d_pyr && !c->floatPyramid && !(rankPath && c->ranksValid))
-    {
-        // (options changed between acf_hip_pyramid and acf_hip_detect: the float cells this path reads were never written)
-        return fail(c, ACF_HIP_E_INVALID, "detect: the float pyramid of this batch was not written (keep_pyramid = 0) and the selected cascade reads floats");
-    }
-    if (!c->countersZeroed)
+    if (!(ranks && c->countersZeroed))
     {
         HIPCHK(c, hipMemsetAsync(cs.d_counts, 0, sizeof(int32_t) * nF, c->stream));
     }
     int rc = 0;
-    if (wholeCascadeTiled(c))
+    if (wholeCascadeTiled(c, cs))
     {
-        if ((rc = runCascadeTiled(c, pyr, pyr_fs, nF, nChns)))
+        if ((rc = runCascadeTiled(c, cs, pyr, pyr_fs, nF, nChns, ranks)))
         {
             return rc;
         }
@@ -507,7 +509,7 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
         }
         bounds.push_back(p.nTrees);
         const int nStages = int(bounds.size());
-        HIPCHK(c, hipMemsetAsync(cs.d_qcounts, 0, sizeof(int32_t) * size_t(nStages) * c->maxBatch, c->stream));
+        HIPCHK(c, hipMemsetAsync(cs.d_qcounts, 0, sizeof(int32_t) * size_t(nStages) * cs.batch, c->stream));
         CascArgs a{};
         a.pyr = pyr;
         a.pyr_fs = pyr_fs;
@@ -515,15 +517,15 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
         a.blockLevel = cs.d_blockLevel;
         a.blocksPerFrame = blocksPerFrame;
         a.nFrames = nF;
-        a.mH = p.modelDsPad_h / p.shrink;
-        a.mW = p.modelDsPad_w / p.shrink;
+        a.mH = p.modelDsPad_h / cs.cell;
+        a.mW = p.modelDsPad_w / cs.cell;
         a.nChns = nChns;
         a.fids = cs.d_fids;
         a.nTrees = p.nTrees;
         a.nTreeNodes = p.nTreeNodes;
         a.treeDepth = p.treeDepth;
-        a.stride = cs.dedupQ > 1 ? p.shrink : p.stride; // (the grid of distinct offsets: its windows are one cell apart)
-        a.shrink = p.shrink;
+        a.stride = cs.dedupQ > 1 ? cs.cell : p.stride; // (the grid of distinct offsets: its windows are one cell apart)
+        a.shrink = cs.cell;
         a.cascThr = float(p.cascThr); // DetectionParams::cascThr is a float (acfDetect1.cpp:63,323)
         a.cidAll = cs.d_cidAll;
         a.thrs = cs.d_thrs;
@@ -533,13 +535,13 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
         a.qcap = cs.qcap;
         a.hits = cs.d_hits;
         a.counts = cs.d_counts;
-        a.maxHits = c->maxHits;
+        a.maxHits = cs.maxHits;
         const int mode = p.treeDepth == 2 ? 2 : (p.treeDepth > 0 ? 1 : 0);
         // later stages see a shrinking survivor set; grid-stride loops cover any count
         const int qGrid[3] = { std::max(1, blocksPerFrame / 2), std::max(1, blocksPerFrame / 8), std::max(1, std::min(blocksPerFrame, 64)) };
         int firstStage = 0;
         bool pooledTail = false; // k_cascade_tile3D has written the tail's leaf codes: no k_tail_codesD
-        if (cs.tiles.ok && p.treeDepth != 2 && c->opt.cascadeTiles && (rc = runTileStageD(c, pyr, pyr_fs, nF, nChns, bounds, firstStage, pooledTail)))
+        if (cs.tiles.ok && p.treeDepth != 2 && c->opt.cascadeTiles && (rc = runTileStageD(c, cs, pyr, pyr_fs, nF, nChns, ranks, bounds, firstStage, pooledTail)))
         {
             return rc;
         }
@@ -549,9 +551,9 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
             a.t1 = bounds[sidx];
             a.last = sidx == nStages - 1;
             a.qin = sidx > 0 ? cs.d_queue[(sidx - 1) & 1] : nullptr;
-            a.qinCount = sidx > 0 ? cs.d_qcounts + size_t(sidx - 1) * c->maxBatch : nullptr;
+            a.qinCount = sidx > 0 ? cs.d_qcounts + size_t(sidx - 1) * cs.batch : nullptr;
             a.qout = cs.d_queue[sidx & 1];
-            a.qoutCount = cs.d_qcounts + size_t(sidx) * c->maxBatch;
+            a.qoutCount = cs.d_qcounts + size_t(sidx) * cs.batch;
             dim3 block(256);
             const size_t winBytes = sizeof(float) * size_t(nChns) * a.mH * a.mW;
             const bool tail = a.last && sidx > 0 && a.t0 >= 128 && winBytes <= 64 * 1024;
@@ -647,20 +649,51 @@ static int runCascade(acf_hip_ctx* c, const float* pyr, int64_t pyr_fs, const Bo
         {
             return fail(c, ACF_HIP_E_INVALID, "detect: no buffer for the windows that share an offset (stride < shrink)");
         }
-        hipLaunchKernelGGL(k_expand_hits, dim3(nF), dim3(256), 0, c->stream, (const acf_hip_hit*)cs.d_hits, cs.d_counts, cs.d_hitsX, c->maxHits,
+        hipLaunchKernelGGL(k_expand_hits, dim3(nF), dim3(256), 0, c->stream, (const acf_hip_hit*)cs.d_hits, cs.d_counts, cs.d_hitsX, cs.maxHits,
             (const int2*)cs.d_realWin, cs.dedupQ);
         LAUNCHCHK(c, "k_expand_hits");
         hitsForSort = cs.d_hitsX;
     }
     prof(c, "k_sort_map");
-    hipLaunchKernelGGL(k_sort_map, dim3(SM_BLOCKS, nF), dim3(256), 0, c->stream, hitsForSort, (const int32_t*)cs.d_counts, c->maxHits,
+    hipLaunchKernelGGL(k_sort_map, dim3(SM_BLOCKS, nF), dim3(256), 0, c->stream, hitsForSort, (const int32_t*)cs.d_counts, cs.maxHits,
         d_box, p.stride, shift_h, shift_w, cs.d_sorted, cs.d_dets);
     LAUNCHCHK(c, "k_sort_map");
-    if (c->nmsOn && c->nms.type != 0 && (rc = launchNms(c, nF)))
+    return ACF_HIP_OK;
+}
+
+// LDCF: every level of the batch's pyramid filtered (k 5x5 filters per channel) and halved into the LDCF pyramid, on which the
+// cascade then runs with cells of 2*shrink pixels (include/acf_hip.h, acf_hip_params::ldcfK)
+static int runLdcf(acf_hip_ctx* c, int nF)
+{
+    const Plan& pl = c->plan;
+    const LdcfStage& L = c->ldcf;
+    const ResampleDesc* descs = c->d_descs + L.descBase;
+    if (L.tiles > 0)
     {
-        return rc;
+        // filters + half resample in one kernel: the filtered full-resolution planes stay in LDS
+        prof(c, "k_ldcf_tile");
+        const int xoT = 16;
+        const size_t ldsB = ldcfTileLdsFloats(L.tileRows, L.tileCols, xoT) * sizeof(float);
+        auto kern = &k_ldcf_tile<8, 4>;
+        int rc;
+        if ((rc = allowLds(c, reinterpret_cast<const void*>(kern), ldsB)))
+        {
+            return rc;
+        }
+        hipLaunchKernelGGL(kern, dim3(L.tiles, pl.nChns, nF), dim3(256), ldsB, c->stream, (const float*)c->d_pyr, L.d_pyr, (const float*)L.d_filt,
+            (const LdcfTileJob*)L.d_tileJobs, (const LdcfJob*)L.d_jobs, descs, (const int32_t*)c->d_it, (const float*)c->d_ft, L.tileRows, L.tileCols, xoT,
+            c->p.ldcfK, pl.nChns, pl.pyr_floats);
+        LAUNCHCHK(c, "k_ldcf_tile");
+        return ACF_HIP_OK;
     }
-    prof(c, "(end)");
-    c->countsFetched = false;
+    const int nL = int(pl.levels.size());
+    prof(c, "k_ldcf_conv");
+    hipLaunchKernelGGL(k_ldcf_conv, dim3(cdiv(L.maxCells, 256), pl.nChns * c->p.ldcfK, nF * nL), dim3(256), 0, c->stream, (const float*)c->d_pyr, L.d_tmp,
+        (const float*)L.d_filt, (const LdcfJob*)L.d_jobs, nL, pl.nChns, pl.pyr_floats, L.tmpFloats);
+    LAUNCHCHK(c, "k_ldcf_conv");
+    prof(c, "k_resample(ldcf)");
+    hipLaunchKernelGGL(k_resample, dim3(L.maxBlocks, nL, nF), dim3(64, 4), 0, c->stream, (const float*)L.d_tmp, L.d_pyr, descs, (const int32_t*)c->d_it,
+        (const float*)c->d_ft, RS_XT);
+    LAUNCHCHK(c, "k_resample(ldcf)");
     return ACF_HIP_OK;
 }

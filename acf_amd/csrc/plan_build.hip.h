@@ -398,139 +398,123 @@ int PlanBuild::levelJobs()
 int PlanBuild::ldcf()
 {
     int rc = ACF_HIP_OK;
-    (void)rc;
     // ---- LDCF post-stage (acf_hip_params::ldcfK): level table of the filtered, halved pyramid + one resample per level
-    c->ldcfLevels.clear();
-    c->ldcfFloats = c->ldcfTmpFloats = 0;
-    if (p.ldcfK > 0)
+    LdcfStage& L = c->ldcf;
+    if (p.ldcfK <= 0)
     {
-        const int shrink2 = 2 * p.shrink, nCk = pl.nChns * p.ldcfK;
-        c->ldcfDescBase = int(c->h_descs.size());
-        c->ldcfMaxCells = c->ldcfMaxBlocks = 0;
-        std::vector<LdcfJob> ldcfJobs;
-        int64_t off = 0;
-        for (size_t i = 0; i < pl.levels.size(); i++)
+        return ACF_HIP_OK;
+    }
+    const int shrink2 = 2 * p.shrink, nCk = pl.nChns * p.ldcfK;
+    L.descBase = int(c->h_descs.size());
+    L.tmpFloats = int64_t(p.ldcfK) * pl.pyr_floats;
+    std::vector<LdcfJob> jobs;
+    for (size_t i = 0; i < pl.levels.size(); i++)
+    {
+        acf_hip_level l = pl.levels[i];
+        const acf_hip_level& s0 = pl.levels[i];
+        l.hP = l.hC = int(std::floor(0.5 * s0.hP + 0.5)); // imResample(C, .5): round(.5 * size)
+        l.wP = l.wC = int(std::floor(0.5 * s0.wP + 0.5));
+        if (l.hP < 1 || l.wP < 1)
         {
-            acf_hip_level l = pl.levels[i];
-            const acf_hip_level& s0 = pl.levels[i];
-            l.hP = l.hC = int(std::floor(0.5 * s0.hP + 0.5)); // imResample(C, .5): round(.5 * size)
-            l.wP = l.wC = int(std::floor(0.5 * s0.wP + 0.5));
-            if (l.hP < 1 || l.wP < 1)
-            {
-                return fail(c, ACF_HIP_E_UNSUPPORTED, "plan: LDCF level smaller than one cell");
-            }
-            l.nWinR = std::max(0, int(std::ceil(float(l.hP * shrink2 - p.modelDsPad_h + 1) / p.stride)));
-            l.nWinC = std::max(0, int(std::ceil(float(l.wP * shrink2 - p.modelDsPad_w + 1) / p.stride)));
-            l.offset = off;
-            off += int64_t(nCk) * l.hP * l.wP;
-            c->ldcfLevels.push_back(l);
-            ResampleDesc dd;
-            if ((rc = buildResample(s0.hP, s0.wP, l.hP, l.wP, dd, arena)))
-            {
-                return fail(c, rc, "plan: degenerate LDCF resample geometry");
-            }
-            const double one[3] = { 1.0, 1.0, 1.0 };
-            setResampleGain(dd, one, nCk, nCk);
-            dd.nplanes = nCk;
-            dd.src_off = int64_t(p.ldcfK) * s0.offset; // the filtered scratch holds every level: k planes per channel plane
-            dd.dst_off = l.offset;
-            c->h_descs.push_back(dd);
-            LdcfJob j{};
-            j.h = s0.hP;
-            j.w = s0.wP;
-            j.inOff = s0.offset;
-            j.outOff = int64_t(p.ldcfK) * s0.offset;
-            ldcfJobs.push_back(j);
-            c->ldcfMaxCells = std::max(c->ldcfMaxCells, s0.hP * s0.wP);
-            c->ldcfMaxBlocks = std::max(c->ldcfMaxBlocks, resampleBlocks(dd));
+            return fail(c, ACF_HIP_E_UNSUPPORTED, "plan: LDCF level smaller than one cell");
         }
-        c->ldcfTmpFloats = int64_t(p.ldcfK) * pl.pyr_floats;
-        c->ldcfFloats = off;
+        l.nWinR = std::max(0, int(std::ceil(float(l.hP * shrink2 - p.modelDsPad_h + 1) / p.stride)));
+        l.nWinC = std::max(0, int(std::ceil(float(l.wP * shrink2 - p.modelDsPad_w + 1) / p.stride)));
+        l.offset = L.floats;
+        L.floats += int64_t(nCk) * l.hP * l.wP;
+        L.levels.push_back(l);
+        ResampleDesc dd;
+        if ((rc = buildResample(s0.hP, s0.wP, l.hP, l.wP, dd, arena)))
         {
-            // fused path: every level tiled for k_resample_tile's passes with 16 output columns per tile
-            std::vector<LdcfTileJob> tj;
-            int maxR = 0, maxC = 0;
-            bool ok = !fallbackForced(FB_LDCF_UNFUSED);
-            const int xoMax = 16; // output columns per tile at most (source tile: twice as many columns)
-            for (size_t i = 0; i < c->ldcfLevels.size() && ok; i++)
+            return fail(c, rc, "plan: degenerate LDCF resample geometry");
+        }
+        const double one[3] = { 1.0, 1.0, 1.0 };
+        setResampleGain(dd, one, nCk, nCk);
+        dd.nplanes = nCk;
+        dd.src_off = int64_t(p.ldcfK) * s0.offset; // the filtered scratch holds every level: k planes per channel plane
+        dd.dst_off = l.offset;
+        dd.src_frame_stride = L.tmpFloats;
+        c->h_descs.push_back(dd);
+        LdcfJob j{};
+        j.h = s0.hP;
+        j.w = s0.wP;
+        j.inOff = s0.offset;
+        j.outOff = int64_t(p.ldcfK) * s0.offset;
+        jobs.push_back(j);
+        L.maxCells = std::max(L.maxCells, s0.hP * s0.wP);
+        L.maxBlocks = std::max(L.maxBlocks, resampleBlocks(dd));
+    }
+    for (size_t i = 0; i < L.levels.size(); i++)
+    {
+        c->h_descs[size_t(L.descBase) + i].dst_frame_stride = L.floats;
+    }
+    // fused path: every level tiled for k_resample_tile's passes with 16 output columns per tile
+    std::vector<LdcfTileJob> tj;
+    bool ok = !fallbackForced(FB_LDCF_UNFUSED);
+    const int xoMax = 16; // output columns per tile at most (source tile: twice as many columns)
+    // tile sizes (outputs y, x) of at most 64 x 16 outputs, the largest first
+    std::vector<std::pair<int, int>> cand;
+    for (int y = RT_YO; y >= 32; y--)
+    {
+        for (int x = xoMax; x >= xoMax / 2; x--)
+        {
+            cand.push_back({ y, x });
+        }
+    }
+    std::stable_sort(cand.begin(), cand.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first * a.second > b.first * b.second; });
+    for (size_t i = 0; i < L.levels.size() && ok; i++)
+    {
+        const ResampleDesc& dd = c->h_descs[size_t(L.descBase) + i];
+        // the largest tile whose source tile is at most 128 rows x 32 columns: the filter stage then has exactly two tile rows
+        // per lane and eight column quads (k_ldcf_tile)
+        ResampleTiling tl;
+        int yo = 0, xo = 0;
+        for (const auto& yx : cand)
+        {
+            tl = resampleTilePlan(dd, arena, yx.second, int64_t(40) * 1024, yx.first, 128, 2 * xoMax);
+            if (tl.rows > 0)
             {
-                const ResampleDesc& dd = c->h_descs[size_t(c->ldcfDescBase) + i];
-                // the largest tile of at most 64 x 16 outputs whose source tile is at most 128 rows x 32 columns: the filter
-                // stage then has exactly two tile rows per lane and eight column quads (k_ldcf_tile)
-                ResampleTiling tl;
-                int yo = 0, xo = 0;
-                {
-                    std::vector<std::pair<int, int>> cand;
-                    for (int y = RT_YO; y >= 32; y--)
-                    {
-                        for (int x = xoMax; x >= xoMax / 2; x--)
-                        {
-                            cand.push_back({ y, x });
-                        }
-                    }
-                    std::stable_sort(cand.begin(), cand.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first * a.second > b.first * b.second; });
-                    for (const auto& yx : cand)
-                    {
-                        tl = resampleTilePlan(dd, arena, yx.second, int64_t(40) * 1024, yx.first, 128, 2 * xoMax);
-                        if (tl.rows > 0)
-                        {
-                            yo = yx.first;
-                            xo = yx.second;
-                            break;
-                        }
-                    }
-                }
-                if (tl.rows <= 0)
-                {
-                    ok = false;
-                    break;
-                }
-                maxR = std::max(maxR, tl.rows);
-                maxC = std::max(maxC, tl.cols);
-                const int ntY = cdiv(dd.hb, yo), ntX = cdiv(dd.wb, xo);
-                for (int x = 0; x < ntX; x++)
-                {
-                    for (int y = 0; y < ntY; y++)
-                    {
-                        LdcfTileJob j{};
-                        j.level = int(i);
-                        j.ytile = y;
-                        j.xtile = x;
-                        j.tile_y = tl.tile_y;
-                        j.tile_x = tl.tile_x;
-                        j.yo = yo;
-                        j.xo = xo;
-                        tj.push_back(j);
-                    }
-                }
-            }
-            c->ldcfTiles = 0;
-            if (ok && !tj.empty())
-            {
-                c->ldcfTiles = int(tj.size());
-                c->ldcfTileRows = maxR;
-                c->ldcfTileCols = maxC;
-                if ((rc = devUpload(c, &c->d_ldcfTileJobs, tj)))
-                {
-                    return rc;
-                }
+                yo = yx.first;
+                xo = yx.second;
+                break;
             }
         }
-        for (size_t i = 0; i < c->ldcfLevels.size(); i++)
+        if (tl.rows <= 0)
         {
-            ResampleDesc& dd = c->h_descs[size_t(c->ldcfDescBase) + i];
-            dd.src_frame_stride = c->ldcfTmpFloats;
-            dd.dst_frame_stride = c->ldcfFloats;
+            ok = false;
+            break;
         }
-        if ((rc = devUpload(c, &c->d_ldcfJobs, ldcfJobs)))
+        L.tileRows = std::max(L.tileRows, tl.rows);
+        L.tileCols = std::max(L.tileCols, tl.cols);
+        const int ntY = cdiv(dd.hb, yo), ntX = cdiv(dd.wb, xo);
+        for (int x = 0; x < ntX; x++)
+        {
+            for (int y = 0; y < ntY; y++)
+            {
+                LdcfTileJob j{};
+                j.level = int(i);
+                j.ytile = y;
+                j.xtile = x;
+                j.tile_y = tl.tile_y;
+                j.tile_x = tl.tile_x;
+                j.yo = yo;
+                j.xo = xo;
+                tj.push_back(j);
+            }
+        }
+    }
+    if (ok && !tj.empty())
+    {
+        L.tiles = int(tj.size());
+        if ((rc = devUpload(c, &L.d_tileJobs, tj)))
         {
             return rc;
         }
-        if ((rc = devUpload(c, &c->d_ldcfFilt, c->ldcfFilters)) || (c->ldcfTiles == 0 && (rc = devAlloc(c, &c->d_ldcfTmp, size_t(B) * c->ldcfTmpFloats + 64))) ||
-            (rc = devAlloc(c, &c->d_ldcfPyr, size_t(B) * c->ldcfFloats + 64)))
-        {
-            return rc;
-        }
+    }
+    if ((rc = devUpload(c, &L.d_jobs, jobs)) || (rc = devUpload(c, &L.d_filt, L.filters)) ||
+        (L.tiles == 0 && (rc = devAlloc(c, &L.d_tmp, size_t(B) * L.tmpFloats + 64))) || (rc = devAlloc(c, &L.d_pyr, size_t(B) * L.floats + 64)))
+    {
+        return rc;
     }
     return ACF_HIP_OK;
 }
@@ -583,19 +567,11 @@ int PlanBuild::uploadAndScratch()
 int PlanBuild::cascade()
 {
     int rc = ACF_HIP_OK;
-    (void)rc;
-    // cascade
-    // with LDCF the cascade runs on the filtered pyramid: its tables are built for those levels, nChns*k channels, shrink*2
-    const std::vector<acf_hip_level>& cascLevels = p.ldcfK > 0 ? c->ldcfLevels : pl.levels;
-    {
-        ShrinkScope ss(c, p.ldcfK > 0 ? 2 : 1);
-        if ((rc = buildCascadeTables(c, cascLevels, pl.nChns * std::max(p.ldcfK, 1), c->cs, p.ldcfK <= 0)))
-        {
-            return rc;
-        }
-    }
-    if ((rc = devUpload(c, &c->cs.d_thrs, c->thrs)) || (rc = devUpload(c, &c->cs.d_hs, c->hs)) || (rc = devUpload(c, &c->cs.d_child, c->child)) ||
-        (rc = devUpload(c, &c->cs.d_fids, c->fids)))
+    // with LDCF the cascade runs on the filtered pyramid: its tables are built for those levels, nChns*k channels, cells of 2*shrink pixels
+    const bool ldcf = p.ldcfK > 0;
+    const std::vector<acf_hip_level>& cascLevels = ldcf ? c->ldcf.levels : pl.levels;
+    if ((rc = buildCascadeTables(c, cascLevels, pl.nChns * std::max(p.ldcfK, 1), p.shrink * (ldcf ? 2 : 1), B, c->thrs, c->cs, !ldcf)) ||
+        (rc = allocCascadeRun(c, c->cs, cascLevels, c->thrs, max_hits)))
     {
         return rc;
     }
@@ -608,32 +584,6 @@ int PlanBuild::cascade()
         box[i].bh = int(std::lrint(double(p.modelDs_h) / pl.levels[i].scale));
         box[i].bw = int(std::lrint(double(p.modelDs_w) / pl.levels[i].scale));
     }
-    if ((rc = devUpload(c, &c->d_boxLevels, box)))
-    {
-        return rc;
-    }
-    if (c->cs.dedupQ > 1 && (rc = devAlloc(c, &c->cs.d_hitsX, size_t(B) * max_hits)))
-    {
-        return rc;
-    }
-    if ((rc = devAlloc(c, &c->cs.d_hits, size_t(B) * max_hits)) || (rc = devAlloc(c, &c->cs.d_sorted, size_t(B) * max_hits)) ||
-        (rc = devAlloc(c, &c->cs.d_dets, size_t(B) * max_hits)) || (rc = devAlloc(c, &c->cs.d_counts, size_t(B))))
-    {
-        return rc;
-    }
-    {
-        int64_t nWinTotal = 0;
-        for (const auto& l : cascLevels)
-        {
-            nWinTotal += int64_t(l.nWinR) * l.nWinC;
-        }
-        c->cs.qcap = int(std::max<int64_t>(nWinTotal, 1));
-        if ((rc = devAlloc(c, &c->cs.d_queue[0], size_t(B) * c->cs.qcap)) || (rc = devAlloc(c, &c->cs.d_queue[1], size_t(B) * c->cs.qcap)) ||
-            (rc = devAlloc(c, &c->cs.d_qcounts, size_t(8) * B + 8))) // (+ 8: k_cascade_tile3's tile counters, one per XCD)
-        {
-            return rc;
-        }
-    }
-    return ACF_HIP_OK;
+    return devUpload(c, &c->d_boxLevels, box);
 }
 } // namespace

@@ -763,7 +763,7 @@ int PyramidRun::levels(int f0, int nLF)
         // what the levels leave as: floats (always, unless the caller has declared the float pyramid unneeded), and the
         // cascade's 16-bit rank cells when every level goes through this one launch
         // (the rank cells have one reader, the tile kernel: a plan or option that routes the cascade elsewhere keeps floats)
-        const bool emitRank = fused && c->levelsEmitRank && rankCellsOn(c) && !c->opt.taps && c->opt.cascadeTiles;
+        const bool emitRank = fused && c->levelsEmitRank && rankCellsOn(c, c->cs) && !c->opt.taps && c->opt.cascadeTiles;
         // (depths other than 2 keep the floats: their queue's overflow path reads them)
         const bool emitF32 = !(emitRank && !c->opt.keepPyramid && !c->autoLambdas) || (c->cs.tilesR.ok && c->p.treeDepth != 2);
         wroteRank = emitRank;

@@ -231,10 +231,10 @@ def test_acf_detect1(dev, oracle, depth, nTrees, tiles):
     assert np.array_equal(bits(got["score"]), bits(want["score"]))
 
 
-def _detect1_case(dev, oracle, depth, nTrees, tiles, cascThr, hs_range, seed=0):
+def _detect1_case(dev, oracle, depth, nTrees, tiles, cascThr, hs_range, seed=0, **model_kw):
     nC, wP, hP = 10, 60, 44
     chns = rnd(99 + depth + seed, (nC, wP, hP), 0.0, 0.6)
-    m = synth.make_model(seed=11 + depth, name="TINY", nTrees=nTrees, cascThr=cascThr, treeDepth=depth)
+    m = synth.make_model(seed=11 + depth, name="TINY", nTrees=nTrees, cascThr=cascThr, treeDepth=depth, **model_kw)
     m["thrs"] = rnd(5, m["thrs"].shape, 0.1, 0.5)
     m["hs"] = rnd(6, m["hs"].shape, *hs_range)
     m["fids"] = (synth.uniform(7, m["fids"].size, 1) * (nC * 16)).astype(np.uint32).reshape(m["fids"].shape)
@@ -319,6 +319,126 @@ def test_acf_detect1_u8(dev, oracle, depth, explicit_thrs):
     for k in ("scale", "c", "r"):
         assert np.array_equal(got[k], want[k]), k
     assert np.array_equal(bits(got["score"]), bits(want["score"]))
+
+
+@pytest.mark.parametrize("depth", [2, 3])
+def test_acf_detect1_ldcf_model_keeps_shrink_cells(dev, oracle, depth):
+    """acf_hip_op_acf_detect1 on a context whose model has ldcfK > 0: the caller's buffer is a plain channel buffer, so
+    its cells are shrink pixels wide (acfDetect1's own geometry, which acfo_acf_detect1 restates) — the 2 * shrink cells
+    belong to acf_hip_detect's LDCF pyramid alone.  With doubled cells the model window would be 2 x 2 cells and the
+    feature ids below (up to nC * 16) out of range."""
+    _detect1_case(dev, oracle, depth, 128, 1, -1.0, (-0.25, 0.2), ldcfK=2)
+
+
+def _oracle_detect1(oracle, m, chns, thrs_u8=None):
+    """acfo_acf_detect1 on [nC][wP][hP] float planes, or on byte planes with byte thresholds."""
+    nC, wP, hP = chns.shape
+    params, keep = capi.make_params(m)
+    thrs = keep["thrs"] if thrs_u8 is None else thrs_u8
+    want = np.zeros(1 << 16, dtype=capi.HIT_DTYPE)
+    n = oracle.lib().acfo_acf_detect1(chns.ctypes.data_as(C.c_void_p), 0 if thrs_u8 is None else 1, thrs.ctypes.data_as(C.c_void_p), hP, wP, nC,
+                                      C.byref(params), want.ctypes.data_as(C.POINTER(capi.Hit)), 1 << 16, 0)
+    return want[:n]
+
+
+def _assert_hits_equal(got, want):
+    assert len(got) == len(want)
+    for k in ("scale", "c", "r"):
+        assert np.array_equal(got[k], want[k]), k
+    assert np.array_equal(bits(got["score"]), bits(want["score"]))
+
+
+# A small planned pipeline with the device NMS on, and a channel buffer that has nothing to do with its frames.
+_RES_H, _RES_W, _RES_FRAMES, _RES_MAX_HITS = 240, 320, 3, 1 << 14
+
+
+def _resident_model():
+    return synth.make_model(seed=3, name="TINY", nTrees=96, cascThr=-2.0)
+
+
+def _resident_nms():
+    return capi.make_nms(type="maxg", overlap=0.65, ovrDnm="min", prune=True, maxCount=40, pruneRatio=0.1)
+
+
+def _resident_results(det):
+    """Per frame: (detections, hits, raw detections), what acf_hip_get_detections / _get_hits / _get_raw_detections return."""
+    out = []
+    for f in range(_RES_FRAMES):
+        d, h = det.detections(f)
+        out.append((d, h, det.raw_detections(f)))
+    return out
+
+
+def _assert_results_equal(a, b):
+    for f, (x, y) in enumerate(zip(a, b)):
+        for k, (u, v) in enumerate(zip(x, y)):
+            assert len(u) == len(v), (f, k, len(u), len(v))
+            assert np.array_equal(u.view(np.uint32), v.view(np.uint32)), (f, k)
+
+
+def test_acf_detect1_leaves_resident_results(oracle):
+    """acf_hip_op_acf_detect1{,_u8} run a cascade of their own over the caller's buffer: the batch's detections (the device
+    NMS's survivors), hits and raw detections that are resident in the context are afterwards what they were before, for
+    every frame, and the op's hits are the oracle's."""
+    import torch
+    from acf_amd.detector import HipDetector
+    m = _resident_model()
+    frames = np.stack([synth.make_frame(70 + i, _RES_H, _RES_W, "luv") for i in range(_RES_FRAMES)])
+    chns = rnd(123, (10, 60, 44), 0.0, 0.6)
+    chns8 = (rnd(124, (10, 60, 44), 0.0, 0.6) * 255.0).astype(np.uint8)
+    tu = oracle.thrs_u8(m["thrs"])
+    want, want8 = _oracle_detect1(oracle, m, chns), _oracle_detect1(oracle, m, chns8, tu)
+    # (fewer hits than the plan's max_hits and than the device NMS takes: whatever the op's cascade hands on stays inside one
+    # frame's slice of any buffer of the plan)
+    assert 0 < len(want) < 2048 and 0 < len(want8) < 2048, (len(want), len(want8))
+    det = HipDetector(m, _RES_H, _RES_W, 3, max_batch=_RES_FRAMES, max_hits=_RES_MAX_HITS)
+    try:
+        det.set_nms(_resident_nms())
+        det.run(torch.from_numpy(frames).cuda())
+        before = _resident_results(det)
+        assert all(1 <= len(d) < len(raw) and len(h) == len(d) for d, h, raw in before), [(len(d), len(raw)) for d, _, raw in before]
+        got = det.op_acf_detect1(chns)
+        print("op_acf_detect1: %d hits (oracle %d)" % (len(got), len(want)))
+        after = _resident_results(det)
+        got8 = det.op_acf_detect1_u8(chns8)
+        print("op_acf_detect1_u8: %d hits (oracle %d)" % (len(got8), len(want8)))
+        after8 = _resident_results(det)
+        for f in range(_RES_FRAMES):
+            print("frame %d: detections %d -> %d -> %d, raw %d -> %d -> %d" % (f, len(before[f][0]), len(after[f][0]), len(after8[f][0]),
+                                                                              len(before[f][2]), len(after[f][2]), len(after8[f][2])))
+        _assert_hits_equal(got, want)
+        _assert_hits_equal(got8, want8)
+        _assert_results_equal(before, after)
+        _assert_results_equal(before, after8)
+    finally:
+        det.close()
+
+
+def test_acf_detect1_before_the_first_run(oracle):
+    """acf_hip_op_acf_detect1 between acf_hip_plan and the first acf_hip_run of a context with the device NMS on: the batch
+    then gives what it gives on a context that never called the op (the op allocates nothing that the plan keeps)."""
+    import torch
+    from acf_amd.detector import HipDetector
+    m = _resident_model()
+    frames = torch.from_numpy(np.stack([synth.make_frame(70 + i, _RES_H, _RES_W, "luv") for i in range(_RES_FRAMES)])).cuda()
+    chns = rnd(123, (10, 60, 44), 0.0, 0.6)
+    want = _oracle_detect1(oracle, m, chns)
+    assert 0 < len(want) < 2048, len(want)
+    results = []
+    for with_op in (True, False):
+        det = HipDetector()
+        try:
+            det.set_model(m)
+            det.set_nms(_resident_nms())
+            det.plan(_RES_H, _RES_W, 3, max_batch=_RES_FRAMES, max_hits=_RES_MAX_HITS)
+            if with_op:
+                _assert_hits_equal(det.op_acf_detect1(chns), want)
+            det.run(frames)
+            results.append(_resident_results(det))
+        finally:
+            det.close()
+    assert all(1 <= len(d) < len(raw) for d, _, raw in results[1])
+    _assert_results_equal(results[0], results[1])
 
 
 @pytest.mark.parametrize("case", ["stride8", "wide_model", "tall_plane", "one_window", "permissive", "stride2", "stride1", "stride2_odd", "stride3"])
