@@ -9,6 +9,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace acfhip;
@@ -75,6 +76,25 @@ struct LeafCodes
     int cap = 0, pitch = 0;
 };
 
+// The cascade's counters in d_qcounts, int32 each, for a state of B frames: the ONE statement of their layout.
+//   staged path:        the count of stage s's queue [frame] at s * B (at most 4 stages); the tile counters of the tile kernel in front
+//                       (depths 1, 3, 4) at 8 * B
+//   depth-2 tiled path: the tail queue's count [frame] at 0, its head [frame] at B, k_cascade_tile3's tile counters at 2 * B
+struct QueueCounters
+{
+    static constexpr size_t TILE_COUNTERS = 8; // the persistent tile kernels' next tile, one per XCD
+    int32_t* d;
+    size_t B;
+    static size_t allocCount(size_t B) { return 8 * B + TILE_COUNTERS; }
+    int32_t* stage(int s) const { return d + size_t(s) * B; }
+    size_t stagedCount(int nStages) const { return size_t(nStages) * B; } // what the staged path clears from d on
+    int32_t* tileNextD() const { return d + 8 * B; }                      // (cleared on its own, when the workgroups are persistent)
+    int32_t* queueCount() const { return d; }
+    int32_t* queueHead() const { return d + B; }
+    int32_t* tileNext2() const { return d + 2 * B; }
+    size_t tiled2Count() const { return 2 * B + TILE_COUNTERS; }          // what the depth-2 tiled path clears from d on
+};
+
 // Everything the cascade launch needs on the device, and what it was built for.
 struct CascState
 {
@@ -98,7 +118,8 @@ struct CascState
     acf_hip_detection* d_dets = nullptr;
     int32_t* d_counts = nullptr;
     uint2* d_queue[2] = { nullptr, nullptr }; // survivor queues between cascade stages
-    int32_t* d_qcounts = nullptr;             // [stage][frame]
+    int32_t* d_qcounts = nullptr;             // see QueueCounters
+    QueueCounters counters() const { return { d_qcounts, size_t(batch) }; }
     int qcap = 0;
     // LDS-tiled path (stride a multiple of shrink): the tile sets over float cells and over threshold-rank cells (host_plan.h).
     // Depth 2: k_cascade_tile3 + the tail; depths 1, 3, 4: the staged path's first stages (k_cascade_tile3D if g.pooled, else
@@ -2004,7 +2025,7 @@ int acf_hip_op_resize_u8(acf_hip_ctx* c, const uint8_t* src, int rows, int cols,
     return rc;
 }
 
-#include "cascade_run.hip.h"    // allowLds, wholeCascadeTiled, runCascadeTiled, runTileStageD, launchNms, runCascade
+#include "cascade_run.hip.h"    // allowLds, wholeCascadeTiled, planCascadeCall, clearCounters, runCascade, launchNms, runLdcf
 
 int acf_hip_detect(acf_hip_ctx* c)
 {
@@ -2032,16 +2053,14 @@ int acf_hip_detect(acf_hip_ctx* c)
     HIPCHK(c, hipSetDevice(c->device));
     const bool ldcf = c->p.ldcfK > 0;
     const int nF = c->lastBatch;
-    if (!ldcf && !c->floatPyramid && !(wholeCascadeTiled(c, c->cs) && rankCellsOn(c, c->cs) && c->ranksValid))
+    const CascInput in = { ldcf ? c->ldcf.d_pyr : c->d_pyr, ldcf ? c->ldcf.floats : c->plan.pyr_floats, nF, c->plan.nChns * std::max(c->p.ldcfK, 1) };
+    if (!ldcf && !c->floatPyramid && planCascadeCall(c, c->cs, in, true).readsFloats(c->ranksValid))
     {
         // (options changed between acf_hip_pyramid and acf_hip_detect: the float cells this path reads were never written)
         return fail(c, ACF_HIP_E_INVALID, "detect: the float pyramid of this batch was not written (keep_pyramid = 0) and the selected cascade reads floats");
     }
     int rc;
-    if ((ldcf && (rc = runLdcf(c, nF))) ||
-        (rc = runCascade(c, c->cs, ldcf ? c->ldcf.d_pyr : c->d_pyr, ldcf ? c->ldcf.floats : c->plan.pyr_floats, c->d_boxLevels, nF,
-             c->plan.nChns * std::max(c->p.ldcfK, 1), &c->ranksValid)) ||
-        (c->nmsOn && c->nms.type != 0 && (rc = launchNms(c, nF))))
+    if ((ldcf && (rc = runLdcf(c, nF))) || (rc = runCascade(c, c->cs, in, c->d_boxLevels, &c->ranksValid)) || (nmsRequested(c) && (rc = launchNms(c, nF))))
     {
         return rc;
     }
@@ -2063,7 +2082,7 @@ static void graphRunState(acf_hip_ctx* c, const acf_hip_ctx::GraphSlot& gs)
 
 // acf_hip_run knows that the cascade follows the pyramid: the tiled cascade's counters (hit counts; its queue's count and head and the
 // tile counters) are cleared in front of the pyramid's launches instead of between the level kernel and the cascade, where a single
-// frame waits for every node of the chain (runCascade / runCascadeTiled then skip their own memsets)
+// frame waits for every node of the chain (runCascade then skips clearCounters: CascadeCall::countersCleared)
 static int preZeroCounters(acf_hip_ctx* c, int nF)
 {
     if (!c || !c->hasPlan || !c->kids.empty() || !wholeCascadeTiled(c, c->cs) || c->p.ldcfK > 0 || !c->cs.d_counts || !c->cs.d_qcounts || nF <= 0 ||
@@ -2072,10 +2091,28 @@ static int preZeroCounters(acf_hip_ctx* c, int nF)
         return ACF_HIP_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemsetAsync(c->cs.d_counts, 0, sizeof(int32_t) * nF, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->cs.d_qcounts, 0, sizeof(int32_t) * (2 * size_t(c->maxBatch) + 8), c->stream));
-    c->countersZeroed = true;
-    return ACF_HIP_OK;
+    const int rc = clearCounters(c, c->cs, planCascadeCall(c, c->cs, { c->d_pyr, c->plan.pyr_floats, nF, c->plan.nChns }, true));
+    c->countersZeroed = !rc;
+    return rc;
+}
+
+// acf_hip_run's work: the pyramid, then the cascade with its counters cleared early
+static int pyramidThenDetect(acf_hip_ctx* c, const float* frames, int nF)
+{
+    int rc = preZeroCounters(c, nF);
+    if (!rc)
+    {
+        rc = acf_hip_pyramid(c, frames, nF);
+    }
+    if (!rc)
+    {
+        rc = acf_hip_detect(c);
+    }
+    if (c)
+    {
+        c->countersZeroed = false;
+    }
+    return rc;
 }
 
 int acf_hip_run(acf_hip_ctx* c, const float* frames, int nF)
@@ -2128,16 +2165,7 @@ int acf_hip_run(acf_hip_ctx* c, const float* frames, int nF)
         int rcc = ACF_HIP_OK;
         if (ok)
         {
-            rcc = preZeroCounters(c, nF);
-            if (!rcc)
-            {
-                rcc = acf_hip_pyramid(c, frames, nF);
-            }
-            if (!rcc)
-            {
-                rcc = acf_hip_detect(c);
-            }
-            c->countersZeroed = false;
+            rcc = pyramidThenDetect(c, frames, nF);
             ok = hipStreamEndCapture(c->stream, &g) == hipSuccess && g != nullptr && !rcc;
         }
         if (ok)
@@ -2163,21 +2191,7 @@ int acf_hip_run(acf_hip_ctx* c, const float* frames, int nF)
         gs = acf_hip_ctx::GraphSlot();
         c->graphBroken = 1; // (fall through: the plain path below does the work)
     }
-    int rc = preZeroCounters(c, nF);
-    if (!rc)
-    {
-        rc = acf_hip_pyramid(c, frames, nF);
-    }
-    if (rc)
-    {
-        if (c)
-        {
-            c->countersZeroed = false;
-        }
-        return rc;
-    }
-    rc = acf_hip_detect(c);
-    c->countersZeroed = false;
+    const int rc = pyramidThenDetect(c, frames, nF);
     if (!rc && c)
     {
         c->plainRuns++;
@@ -3651,7 +3665,7 @@ static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::ve
             return fail(c, ACF_HIP_E_HIP, "launch k_widen_u8");
         }
     }
-    if ((rc = runCascade(c, cs, dChn, 0, dBox, 1, nChns)))
+    if ((rc = runCascade(c, cs, { dChn, 0, 1, nChns }, dBox)))
     {
         return rc;
     }

@@ -699,7 +699,7 @@ static int allocCascadeRun(acf_hip_ctx* c, CascState& cs, const std::vector<acf_
         (rc = devUpload(c, &cs.d_fids, c->fids)) || (cs.dedupQ > 1 && (rc = devAlloc(c, &cs.d_hitsX, B * max_hits))) ||
         (rc = devAlloc(c, &cs.d_hits, B * max_hits)) || (rc = devAlloc(c, &cs.d_sorted, B * max_hits)) || (rc = devAlloc(c, &cs.d_dets, B * max_hits)) ||
         (rc = devAlloc(c, &cs.d_counts, B)) || (rc = devAlloc(c, &cs.d_queue[0], B * cs.qcap)) || (rc = devAlloc(c, &cs.d_queue[1], B * cs.qcap)) ||
-        (rc = devAlloc(c, &cs.d_qcounts, 8 * B + 8))) // (+ 8: k_cascade_tile3's tile counters, one per XCD)
+        (rc = devAlloc(c, &cs.d_qcounts, QueueCounters::allocCount(B))))
     {
         return rc;
     }
