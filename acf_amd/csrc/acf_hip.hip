@@ -349,6 +349,7 @@ struct acf_hip_ctx
     std::vector<StreamSlot> slots;
     hipStream_t copyStream = nullptr;
     int stPix = 0, stStride = 0, stCap = 0, nextTicket = 0, nextCollect = 0;
+    int64_t stFrameBytes = 0; // bytes between the frames of a submitted batch
     // the plan's cascade (tables, model arrays, work queues, outputs); acf_hip_op_acf_detect1 builds and runs a state of its own
     CascState cs;
     BoxLevel* d_boxLevels = nullptr;
@@ -369,6 +370,13 @@ struct acf_hip_ctx
         int32_t *d_xlin = nullptr, *d_ylin = nullptr, *d_xrun = nullptr, *d_yrun = nullptr, *d_xtap = nullptr, *d_ytap = nullptr;
         uint8_t* d_out = nullptr; // [maxBatch][plan.H][plan.W][4]
     } rz;
+    // acf_hip_set_yuv_layout: where an NV12 / NV21 frame's chroma plane starts and how far frames are apart (0 = tight)
+    struct YuvLayout
+    {
+        int64_t chromaOff = 0, frameStride = 0;
+    } yuv;
+    uint8_t* d_yuvRgb = nullptr; // k_yuv420_to_rgb8's tight RGB frames (in front of the input resize; fallback yuv_unfused)
+    size_t yuvRgbBytes = 0;
 };
 
 // the ONE statement of "the cascade state has rank cells and option rank_cells is on"; each reader adds its own terms
@@ -422,6 +430,7 @@ enum : uint32_t
     FB_TAIL3 = 1u << 10,            // every tail window through k_cascade_tail3
     FB_TILED_STAGED = 1u << 11,     // depths 1, 3, 4: the staged queue instead of the pooled tile kernel
     FB_TILED_POOLED1 = 1u << 12,    // depth 1 on float cells: the pooled tile kernel instead of the staged queue
+    FB_YUV_UNFUSED = 1u << 13,      // NV12 / NV21 as k_yuv420_to_rgb8 + k_ingest_u8 instead of k_ingest_yuv420
 };
 uint32_t fallbackMask()
 {
@@ -430,7 +439,8 @@ uint32_t fallbackMask()
             { "triy_unfused", FB_TRIY_UNFUSED }, { "mou_plain", FB_MOU_PLAIN }, { "resample_no_strip", FB_RESAMPLE_NO_STRIP },
             { "resample_no_pair", FB_RESAMPLE_NO_PAIR }, { "resample_no_up", FB_RESAMPLE_NO_UP }, { "resample_generic", FB_RESAMPLE_GENERIC },
             { "level_groups", FB_LEVEL_GROUPS }, { "ldcf_unfused", FB_LDCF_UNFUSED }, { "no_dedup", FB_NO_DEDUP }, { "no_tail_codes", FB_NO_TAIL_CODES },
-            { "tail3", FB_TAIL3 }, { "tiled_staged", FB_TILED_STAGED }, { "tiled_pooled1", FB_TILED_POOLED1 } };
+            { "tail3", FB_TAIL3 }, { "tiled_staged", FB_TILED_STAGED }, { "tiled_pooled1", FB_TILED_POOLED1 },
+            { "yuv_unfused", FB_YUV_UNFUSED } };
         uint32_t m = 0;
         const char* e = getenv("ACF_HIP_FORCE_FALLBACK");
         std::string s = e ? e : "";
@@ -562,6 +572,9 @@ void freeAll(acf_hip_ctx* c)
     c->levelSegFrames = 0;
     c->d_color = c->d_stage = c->d_chns = c->d_pyr = nullptr; // a re-plan must not see the previous plan's buffers
     c->rz = acf_hip_ctx::InputResize();
+    c->yuv = acf_hip_ctx::YuvLayout();
+    c->d_yuvRgb = nullptr;
+    c->yuvRgbBytes = 0;
     c->ldcf = LdcfStage{ std::move(c->ldcf.filters) }; // (the model's filters stay where acf_hip_params::ldcfFilters points)
     c->d_nmsKeep = c->d_nmsN = c->d_nmsCounts = nullptr;
     c->d_nmsDets = nullptr;
@@ -1712,6 +1725,7 @@ int acf_hip_pyramid(acf_hip_ctx* c, const float* frames, int nF)
 namespace
 {
 using IngestKernel = void (*)(IngestArgs);
+using YuvIngestKernel = void (*)(IngestArgs, YuvSrc);
 
 static IngestKernel ingestKernel(int mode, bool aligned)
 {
@@ -1724,10 +1738,125 @@ static IngestKernel ingestKernel(int mode, bool aligned)
     }
 }
 
+// (no IG_LUV: a YUV 4:2:0 frame has even H and W, so H * W % 4 == 0 and rgbConvert takes the vector body, rgbConvertMex.cpp:92,343)
+static YuvIngestKernel yuvIngestKernel(int mode, bool aligned)
+{
+    switch (mode)
+    {
+        case IG_LUV_VEC: return aligned ? k_ingest_yuv420<IG_LUV_VEC, true> : k_ingest_yuv420<IG_LUV_VEC, false>;
+        case IG_GRAY: return aligned ? k_ingest_yuv420<IG_GRAY, true> : k_ingest_yuv420<IG_GRAY, false>;
+        default: return aligned ? k_ingest_yuv420<IG_PLANAR, true> : k_ingest_yuv420<IG_PLANAR, false>;
+    }
+}
+
+static bool pixIsYuv(int pix)
+{
+    return pix == ACF_HIP_PIX_NV12 || pix == ACF_HIP_PIX_NV21;
+}
+
+// Where the bytes of a batch of 8-bit frames of rows x cols lie — the ONE place that knows (acf_hip_u8_frame_bytes, the ingest, the
+// input resize, the stream's buffers).  rowStride 0 = tight.  NV12 / NV21: cpp = 1 (the luma plane); chromaOff / frameStride are
+// acf_hip_set_yuv_layout's (0 = tight: chroma behind the luma rows, frames stride * rows * 3 / 2 apart).  The packed layouts have
+// no such freedom: frames are stride * rows apart.  Returns what is wrong, or null.
+struct U8Geom
+{
+    int cpp, stride;
+    int ro, go, bo; // byte offsets of r, g, b inside a packed pixel
+    bool yuv;
+    int64_t chromaOff, frameStride;
+};
+static const char* u8Geom(int pix, int rows, int cols, int rowStride, int64_t chromaOff, int64_t frameStride, U8Geom& g)
+{
+    g = U8Geom{};
+    switch (pix)
+    {
+        case ACF_HIP_PIX_RGB: g.cpp = 3, g.ro = 0, g.go = 1, g.bo = 2; break;
+        case ACF_HIP_PIX_BGR: g.cpp = 3, g.ro = 2, g.go = 1, g.bo = 0; break;
+        case ACF_HIP_PIX_RGBA: g.cpp = 4, g.ro = 0, g.go = 1, g.bo = 2; break;
+        case ACF_HIP_PIX_BGRA: g.cpp = 4, g.ro = 2, g.go = 1, g.bo = 0; break;
+        case ACF_HIP_PIX_GRAY: g.cpp = 1; break;
+        case ACF_HIP_PIX_NV12:
+        case ACF_HIP_PIX_NV21: g.cpp = 1, g.yuv = true; break;
+        default: return "pixel layout";
+    }
+    if (rows < 1 || cols < 1 || rowStride < 0)
+    {
+        return "frame size";
+    }
+    if (int64_t(cols) * g.cpp > INT32_MAX)
+    {
+        return "frame size";
+    }
+    g.stride = rowStride > 0 ? rowStride : cols * g.cpp;
+    if (g.stride < cols * g.cpp)
+    {
+        return "row stride smaller than a row";
+    }
+    const int64_t plane = int64_t(g.stride) * rows;
+    if (!g.yuv)
+    {
+        g.frameStride = plane;
+        return nullptr;
+    }
+    if (rows % 2 || cols % 2)
+    {
+        return "NV12 / NV21 frames have even rows and columns";
+    }
+    g.chromaOff = chromaOff > 0 ? chromaOff : plane;
+    if (g.chromaOff < plane)
+    {
+        return "chroma offset inside the luma plane";
+    }
+    g.frameStride = frameStride > 0 ? frameStride : g.chromaOff + plane / 2;
+    if (g.frameStride < g.chromaOff + plane / 2)
+    {
+        return "frame stride smaller than a frame (frames would overlap)";
+    }
+    return nullptr;
+}
+
+// the plan's input planes against the layout: 1 for GRAY, 3 for the colour layouts — NV12 / NV21 included: the luma plane is limited
+// range, not the grey cvtColor gives, so a 1-plane plan does not take it
+static bool u8PlanesOk(const U8Geom& g, int d_in)
+{
+    return (g.cpp == 1 && !g.yuv) == (d_in == 1);
+}
+
+static YuvSrc yuvSrc(const uint8_t* frames, int pix, int rows, int cols, const U8Geom& g)
+{
+    YuvSrc s{};
+    s.in = frames;
+    s.H = rows;
+    s.W = cols;
+    s.rowStride = g.stride;
+    s.vFirst = pix == ACF_HIP_PIX_NV21;
+    s.chromaOff = g.chromaOff;
+    s.in_fs = g.frameStride;
+    return s;
+}
+
+// k_yuv420_to_rgb8 over a batch: NV12 / NV21 frames of rows x cols -> tight RGB frames at dst
+static int launchYuvToRgb(acf_hip_ctx* c, const YuvSrc& s, int nF, uint8_t* dst)
+{
+    prof(c, "k_yuv420_to_rgb8");
+    hipLaunchKernelGGL(k_yuv420_to_rgb8, dim3(cdiv(s.W / 2, 64), cdiv(s.H / 2, 4), nF), dim3(256), 0, c->stream, s, dst);
+    LAUNCHCHK(c, "k_yuv420_to_rgb8");
+    return ACF_HIP_OK;
+}
+
 int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t out_fs, bool convert)
 {
     const acf_hip_params& p = c->p;
     const Plan& pl = c->plan;
+    U8Geom g;
+    if (const char* bad = u8Geom(u.pix, pl.H, pl.W, u.rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_u8: ") + bad);
+    }
+    if (!u8PlanesOk(g, pl.d_in))
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY");
+    }
     IngestArgs a{};
     a.in = u.frames;
     a.out = dst;
@@ -1739,28 +1868,15 @@ int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t
     a.mb = kGray.b;
     a.H = pl.H;
     a.W = pl.W;
-    switch (u.pix)
-    {
-        case ACF_HIP_PIX_RGB: a.cpp = 3, a.ro = 0, a.go = 1, a.bo = 2; break;
-        case ACF_HIP_PIX_BGR: a.cpp = 3, a.ro = 2, a.go = 1, a.bo = 0; break;
-        case ACF_HIP_PIX_RGBA: a.cpp = 4, a.ro = 0, a.go = 1, a.bo = 2; break;
-        case ACF_HIP_PIX_BGRA: a.cpp = 4, a.ro = 2, a.go = 1, a.bo = 0; break;
-        case ACF_HIP_PIX_GRAY: a.cpp = 1, a.ro = 0, a.go = 0, a.bo = 0; break;
-        default: return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: pixel layout");
-    }
-    if ((a.cpp == 1) != (pl.d_in == 1))
-    {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: the plan's input planes (d) must be 3 for colour layouts and 1 for GRAY");
-    }
-    a.rowStride = u.rowStride > 0 ? u.rowStride : pl.W * a.cpp;
-    if (a.rowStride < pl.W * a.cpp)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: row stride smaller than a row");
-    }
-    a.in_fs = int64_t(a.rowStride) * pl.H;
+    a.cpp = g.cpp;
+    a.ro = g.ro;
+    a.go = g.go;
+    a.bo = g.bo;
+    a.rowStride = g.stride;
+    a.in_fs = g.frameStride;
     a.out_fs = out_fs;
     a.vecStore = (pl.H % 4 == 0) && (out_fs % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0);
-    const bool aligned = (reinterpret_cast<uintptr_t>(u.frames) % 4 == 0) && (a.rowStride % 4 == 0);
+    bool aligned = (reinterpret_cast<uintptr_t>(u.frames) % 4 == 0) && (a.rowStride % 4 == 0);
     const int64_t np0 = int64_t(pl.H) * pl.W;
     int mode = IG_PLANAR;
     a.nOut = pl.d_in;
@@ -1779,7 +1895,15 @@ int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t
             a.nOut = 3; // ORIG / RGB with a 1-plane input: replicate (chnsPyramid.cpp:242-243)
         }
     }
-    hipLaunchKernelGGL(ingestKernel(mode, aligned), dim3(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF), dim3(256), 0, c->stream, a);
+    const dim3 grid(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF);
+    if (g.yuv)
+    {
+        aligned = aligned && g.chromaOff % 4 == 0 && g.frameStride % 4 == 0;
+        hipLaunchKernelGGL(yuvIngestKernel(mode, aligned), grid, dim3(256), 0, c->stream, a, yuvSrc(u.frames, u.pix, pl.H, pl.W, g));
+        LAUNCHCHK(c, "k_ingest_yuv420");
+        return ACF_HIP_OK;
+    }
+    hipLaunchKernelGGL(ingestKernel(mode, aligned), grid, dim3(256), 0, c->stream, a);
     LAUNCHCHK(c, "k_ingest_u8");
     return ACF_HIP_OK;
 }
@@ -1808,11 +1932,6 @@ static void launchColour(acf_hip_ctx* c, const float* in, float* out, int64_t n,
     {
         hipLaunchKernelGGL(k_replicate3, grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs);
     }
-}
-
-static int pixCpp(int pix)
-{
-    return pix == ACF_HIP_PIX_GRAY ? 1 : ((pix == ACF_HIP_PIX_RGBA || pix == ACF_HIP_PIX_BGRA) ? 4 : 3);
 }
 
 // k_resize_u8 over a batch: `src` frames of t.rows x t.cols (row stride `stride` bytes) -> tight t.drows x t.dcols frames at dst
@@ -1895,6 +2014,70 @@ int acf_hip_pyramid_u8(acf_hip_ctx* c, const uint8_t* frames, int nF, int pix, i
     }
     PackedSrc u{ frames, pix, rowStride };
     return pyramidImpl(c, nullptr, &u, nF);
+}
+
+int acf_hip_u8_frame_bytes(int pix, int rows, int cols, int rowStride, int64_t* out)
+{
+    U8Geom g;
+    if (!out || u8Geom(pix, rows, cols, rowStride, 0, 0, g))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    *out = g.frameStride;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_set_yuv_layout(acf_hip_ctx* c, int64_t chromaOff, int64_t frameStride)
+{
+    if (!c || !c->hasPlan)
+    {
+        return c ? fail(c, ACF_HIP_E_NOPLAN, "set_yuv_layout: plan first") : ACF_HIP_E_INVALID;
+    }
+    if (!c->kids.empty() || !c->slots.empty())
+    {
+        return fail(c, ACF_HIP_E_UNSUPPORTED, "set_yuv_layout: not with option \"streams\" > 1; before acf_hip_stream_open");
+    }
+    if (chromaOff < 0 || frameStride < 0)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "set_yuv_layout: negative offset or stride");
+    }
+    dropGraph(c);
+    c->yuv.chromaOff = chromaOff; // (held against the frames' row stride where that is known: the run / open call)
+    c->yuv.frameStride = frameStride;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_op_yuv420_to_rgb(acf_hip_ctx* c, const uint8_t* src, int rows, int cols, int pix, int rowStride, int64_t chromaOff, uint8_t* dst)
+{
+    if (!c || !src || !dst || !pixIsYuv(pix) || chromaOff < 0)
+    {
+        return c ? fail(c, ACF_HIP_E_INVALID, "op_yuv420_to_rgb: arguments (pix: ACF_HIP_PIX_NV12 or _NV21)") : ACF_HIP_E_INVALID;
+    }
+    U8Geom g;
+    if (const char* bad = u8Geom(pix, rows, cols, rowStride, chromaOff, 0, g))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("op_yuv420_to_rgb: ") + bad);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // one-off buffers (an operator entry, not the hot path)
+    uint8_t *dS = nullptr, *dD = nullptr;
+    const size_t nS = size_t(g.frameStride), nD = size_t(rows) * cols * 3;
+    bool ok = hipMalloc(reinterpret_cast<void**>(&dS), nS) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&dD), nD) == hipSuccess &&
+        hipMemcpy(dS, src, nS, hipMemcpyHostToDevice) == hipSuccess;
+    int rc = ACF_HIP_OK;
+    if (ok)
+    {
+        rc = launchYuvToRgb(c, yuvSrc(dS, pix, rows, cols, g), 1, dD);
+        ok = !rc && hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(dst, dD, nD, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(dS);
+    (void)hipFree(dD);
+    if (!ok && !rc)
+    {
+        (void)hipGetLastError();
+        return fail(c, ACF_HIP_E_HIP, "op_yuv420_to_rgb: device allocation or copy failed");
+    }
+    return rc;
 }
 
 int acf_hip_resize_dims(int rows, int cols, double scale, int* out_rows, int* out_cols)
@@ -2308,31 +2491,31 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, "stream_open: not available with option \"streams\" > 1");
     }
-    if (depth < 2 || depth > 8 || cap <= 0 || pix < ACF_HIP_PIX_RGB || pix > ACF_HIP_PIX_GRAY)
+    if (depth < 2 || depth > 8 || cap <= 0)
     {
-        return fail(c, ACF_HIP_E_INVALID, "stream_open: depth must be 2..8, cap > 0, pix one of ACF_HIP_PIX_*");
-    }
-    const int cpp = (pix == ACF_HIP_PIX_GRAY) ? 1 : (pix == ACF_HIP_PIX_RGBA || pix == ACF_HIP_PIX_BGRA) ? 4 : 3;
-    if ((cpp == 1) != (c->plan.d_in == 1))
-    {
-        return fail(c, ACF_HIP_E_INVALID, "stream_open: the plan's input planes (d) must be 3 for colour layouts and 1 for GRAY");
+        return fail(c, ACF_HIP_E_INVALID, "stream_open: depth must be 2..8, cap > 0");
     }
     // (with acf_hip_set_input_resize the submitted frames are the unreduced ones)
     const int inRows = c->rz.on ? c->rz.rows : c->plan.H, inCols = c->rz.on ? c->rz.cols : c->plan.W;
-    const int stride = rowStride > 0 ? rowStride : inCols * cpp;
-    if (stride < inCols * cpp)
+    U8Geom g;
+    if (const char* bad = u8Geom(pix, inRows, inCols, rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
     {
-        return fail(c, ACF_HIP_E_INVALID, "stream_open: row stride smaller than a row");
+        return fail(c, ACF_HIP_E_INVALID, std::string("stream_open: ") + bad);
+    }
+    if (!u8PlanesOk(g, c->plan.d_in))
+    {
+        return fail(c, ACF_HIP_E_INVALID, "stream_open: the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY");
     }
     acf_hip_stream_close(c);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
     c->stPix = pix;
-    c->stStride = stride;
+    c->stStride = g.stride;
+    c->stFrameBytes = g.frameStride;
     c->stCap = cap;
     c->nextTicket = c->nextCollect = 0;
     c->slots.resize(size_t(depth));
-    const size_t inBytes = size_t(c->maxBatch) * stride * inRows;
+    const size_t inBytes = size_t(c->maxBatch) * size_t(g.frameStride);
     const size_t recBytes = size_t(c->maxBatch) * (1 + 6 * size_t(cap)) * sizeof(int32_t);
     for (auto& s : c->slots)
     {
@@ -2364,7 +2547,7 @@ int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, in
     HIPCHK(c, hipSetDevice(c->device));
     acf_hip_ctx::StreamSlot& s = c->slots[size_t(c->nextTicket % depth)];
     // The slot's previous batch was collected (checked above), so its device input and host records are free.
-    const size_t bytes = size_t(nF) * c->stStride * (c->rz.on ? c->rz.rows : c->plan.H);
+    const size_t bytes = size_t(nF) * size_t(c->stFrameBytes);
     HIPCHK(c, hipMemcpyAsync(s.d_in, frames_host, bytes, hipMemcpyHostToDevice, c->copyStream));
     HIPCHK(c, hipEventRecord(s.evH2D, c->copyStream));
     HIPCHK(c, hipStreamWaitEvent(c->stream, s.evH2D, 0));

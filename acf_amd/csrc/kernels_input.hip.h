@@ -204,6 +204,56 @@ struct IngestArgs
 constexpr int IG_T = 64;
 constexpr int IG_PITCH = 260; // bytes; 65 dwords
 
+// One pixel of a lane's four (r, g, b already * 1/255) through the model's colour conversion, into column j of the planes' quads.
+template <int MODE>
+__device__ __forceinline__ void ingest_convert(const IngestArgs& a, float r, float g, float b, float (&o)[3][4], int j)
+{
+    if (MODE == IG_PLANAR)
+    {
+        o[0][j] = r;
+        o[1][j] = g;
+        o[2][j] = b;
+    }
+    else if (MODE == IG_GRAY)
+    {
+        o[0][j] = r * a.mr + g * a.mg + b * a.mb; // rgbConvertMex.cpp:241-252
+    }
+    else
+    {
+        luv_px<MODE == IG_LUV_VEC>(r, g, b, a.lTable, a.k, o[0][j], o[1][j], o[2][j], a.x86);
+    }
+}
+
+// A lane's four consecutive image-y of every output plane: one float4 a plane, or the `left` (< 4) rows the tile still has.
+template <int MODE>
+__device__ __forceinline__ void ingest_store(const IngestArgs& a, const float (&o)[3][4], float* at, int64_t np, int left)
+{
+    const int nPl = (MODE == IG_PLANAR) ? a.nOut : (MODE == IG_GRAY ? 1 : 3);
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+    {
+        if (c < nPl)
+        {
+            float* d = at + c * np;
+            if (a.vecStore && left > 3)
+            {
+                *reinterpret_cast<float4*>(d) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+            }
+            else
+            {
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                {
+                    if (j < left)
+                    {
+                        d[j] = o[c][j];
+                    }
+                }
+            }
+        }
+    }
+}
+
 template <int MODE, bool ALIGNED>
 __global__ void __launch_bounds__(256) k_ingest_u8(IngestArgs a)
 {
@@ -266,46 +316,160 @@ __global__ void __launch_bounds__(256) k_ingest_u8(IngestArgs a)
             const int yy = min(yq + j, IG_T - 1);
             const uint8_t* px = tile + yy * IG_PITCH + xx * a.cpp;
             const float r = float(px[a.ro]) * sc, g = float(px[a.go]) * sc, b = float(px[a.bo]) * sc;
-            if (MODE == IG_PLANAR)
-            {
-                o[0][j] = r;
-                o[1][j] = g;
-                o[2][j] = b;
-            }
-            else if (MODE == IG_GRAY)
-            {
-                o[0][j] = r * a.mr + g * a.mg + b * a.mb; // rgbConvertMex.cpp:241-252
-            }
-            else
-            {
-                luv_px<MODE == IG_LUV_VEC>(r, g, b, a.lTable, a.k, o[0][j], o[1][j], o[2][j], a.x86);
-            }
+            ingest_convert<MODE>(a, r, g, b, o, j);
         }
-        const int nPl = (MODE == IG_PLANAR) ? a.nOut : (MODE == IG_GRAY ? 1 : 3);
-        const int64_t at = int64_t(x0 + xx) * a.H + y0 + yq;
+        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
+    }
+}
+
+// ------------------------------------------------------------------------
+// YUV 4:2:0 video frames (NV12 / NV21) -> 8-bit R, G, B: cvtColor(COLOR_YUV2RGB_NV12 / _NV21), the call the apps make before
+// Detector::operator()(const cv::Mat&).  OpenCV is not part of the reference tree: this is the published algorithm of
+// imgproc/src/color_yuv.simd.hpp restated (BT.601 limited range, 20-bit fixed point, int32, arithmetic shift; the chroma pair of a
+// 2 x 2 block shared by its four pixels, no interpolation) — PARITY UNPINNED.
+// Frame: H rows of W luma bytes, rowStride apart; at chromaOff H / 2 rows of W / 2 byte pairs (U, V; vFirst: V, U), same stride.
+// ------------------------------------------------------------------------
+struct YuvChroma
+{
+    int ruv, guv, buv;
+};
+__device__ __forceinline__ YuvChroma yuv_chroma(int u, int v)
+{
+    u -= 128;
+    v -= 128;
+    return { (1 << 19) + 1673527 * v, (1 << 19) - 852492 * v - 409993 * u, (1 << 19) + 2116026 * u };
+}
+__device__ __forceinline__ void yuv_rgb8(int Y, const YuvChroma& c, int& r, int& g, int& b)
+{
+    const int y = max(0, Y - 16) * 1220542;
+    r = min(max((y + c.ruv) >> 20, 0), 255);
+    g = min(max((y + c.guv) >> 20, 0), 255);
+    b = min(max((y + c.buv) >> 20, 0), 255);
+}
+
+struct YuvSrc
+{
+    const uint8_t* in;
+    int H, W;          // even
+    int rowStride;     // bytes between rows, luma and chroma alike
+    int vFirst;        // NV21
+    int64_t chromaOff; // bytes from a frame's first luma byte to its first chroma byte
+    int64_t in_fs;     // bytes between frames
+};
+
+// The unfused form: tight packed RGB bytes [H][W][3] per frame (in front of k_resize_u8, acf_hip_op_yuv420_to_rgb, and the
+// fallback yuv_unfused of k_ingest_yuv420).  One thread per 2 x 2 block; byte accesses, so any base and stride.
+__global__ void __launch_bounds__(256) k_yuv420_to_rgb8(YuvSrc s, uint8_t* __restrict__ dst)
+{
+    const int bx = blockIdx.x * 64 + (threadIdx.x & 63), by = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (2 * bx >= s.W || 2 * by >= s.H)
+    {
+        return;
+    }
+    const uint8_t* __restrict__ F = s.in + int64_t(blockIdx.z) * s.in_fs;
+    const uint8_t* __restrict__ C = F + s.chromaOff + int64_t(by) * s.rowStride + 2 * bx;
+    const YuvChroma c = yuv_chroma(C[s.vFirst], C[1 - s.vFirst]);
+    uint8_t* __restrict__ D = dst + int64_t(blockIdx.z) * s.H * s.W * 3;
 #pragma unroll
-        for (int c = 0; c < 3; c++)
+    for (int j = 0; j < 2; j++)
+    {
+        const uint8_t* __restrict__ L = F + int64_t(2 * by + j) * s.rowStride + 2 * bx;
+        uint8_t* __restrict__ d = D + (int64_t(2 * by + j) * s.W + 2 * bx) * 3;
+#pragma unroll
+        for (int i = 0; i < 2; i++)
         {
-            if (c < nPl)
+            int r, g, b;
+            yuv_rgb8(L[i], c, r, g, b);
+            d[3 * i] = uint8_t(r);
+            d[3 * i + 1] = uint8_t(g);
+            d[3 * i + 2] = uint8_t(b);
+        }
+    }
+}
+
+// The hot path: NV12 / NV21 -> transposed planar f32, the model's colour conversion in registers: k_ingest_u8's tile and lane
+// assignment (a workgroup owns 64 x 64 pixels; a lane takes four consecutive image-y of one image-x and stores one float4 a
+// plane), with the 8-bit R, G, B of the integer formula in between, times float(1 / 255.0) as there — so the planes are those of
+// k_ingest_u8 on the converted RGB frame, bit for bit.  a.in / cpp / ro / go / bo / rowStride / in_fs of IngestArgs are not read.
+//
+// LDS: 64 luma rows and 32 chroma rows of 16 dwords.  In the convert phase a 32-lane half (the unit bank conflicts count in;
+// 32 banks for byte reads and dword writes) is 16 row-quads x 2 adjacent image-x, which share a dword: 16 addresses, luma rows
+// 4k + j and chroma rows 2k + i, k = 0 .. 15.  At any plain pitch p those are 4kp (2kp) dwords apart: at most 8 (16) banks.  So
+// the rows are stored regrouped — luma row r in slot (r & 3) * 16 + (r >> 2), chroma row r in slot (r & 1) * 16 + (r >> 1) —
+// at a pitch of 17 dwords: the 16 rows of one read are then 17 dwords apart, 17k mod 32 = k (k even), 16 + k (k odd): 16
+// distinct banks.  In the load phase a half writes 16 dwords of each of two adjacent rows r, r + 1 (r even), 16 slots =
+// 272 = 16 (mod 32) dwords apart: 32 distinct banks.  (96 x 17 dwords = 6528 bytes.)
+constexpr int YG_PITCH = 68; // bytes; 17 dwords
+__device__ __forceinline__ int yg_luma_slot(int r)
+{
+    return (r & 3) * 16 + (r >> 2);
+}
+__device__ __forceinline__ int yg_chroma_slot(int r)
+{
+    return IG_T + (r & 1) * 16 + (r >> 1);
+}
+
+template <int MODE, bool ALIGNED>
+__global__ void __launch_bounds__(256) k_ingest_yuv420(IngestArgs a, YuvSrc s)
+{
+    __shared__ uint32_t tileW[(IG_T + IG_T / 2) * YG_PITCH / 4];
+    uint8_t* tile = reinterpret_cast<uint8_t*>(tileW);
+    const int x0 = blockIdx.x * IG_T, y0 = blockIdx.y * IG_T;
+    const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0); // both even
+    const uint8_t* luma = s.in + int64_t(blockIdx.z) * s.in_fs + int64_t(y0) * s.rowStride + x0;
+    const uint8_t* chroma = s.in + int64_t(blockIdx.z) * s.in_fs + s.chromaOff + int64_t(y0 >> 1) * s.rowStride + x0;
+    const int nRows = ny + (ny >> 1); // luma rows, then chroma rows: nx bytes each
+    if (ALIGNED)
+    {
+        // base, row stride, chroma offset and frame stride are multiples of 4 (host-checked) and x0 is a multiple of 64;
+        // a row's last dword is whole or holds one byte pair (nx is even): that pair is read as 16 bits, nothing beyond the row
+        for (int i = threadIdx.x; i < nRows * 16; i += 256)
+        {
+            const int row = i >> 4, j = i & 15;
+            if (4 * j < nx)
             {
-                float* d = outF + c * np + at;
-                if (a.vecStore && yq + 3 < ny)
-                {
-                    *reinterpret_cast<float4*>(d) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
-                }
-                else
-                {
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                    {
-                        if (yq + j < ny)
-                        {
-                            d[j] = o[c][j];
-                        }
-                    }
-                }
+                const uint8_t* rp = (row < ny ? luma + int64_t(row) * s.rowStride : chroma + int64_t(row - ny) * s.rowStride) + 4 * j;
+                const uint32_t v = (4 * j + 4 <= nx) ? *reinterpret_cast<const uint32_t*>(rp) : uint32_t(*reinterpret_cast<const uint16_t*>(rp));
+                tileW[(row < ny ? yg_luma_slot(row) : yg_chroma_slot(row - ny)) * (YG_PITCH / 4) + j] = v;
             }
         }
+    }
+    else
+    {
+        for (int i = threadIdx.x; i < nRows * 64; i += 256)
+        {
+            const int row = i >> 6, j = i & 63;
+            if (j < nx)
+            {
+                const uint8_t* rp = row < ny ? luma + int64_t(row) * s.rowStride : chroma + int64_t(row - ny) * s.rowStride;
+                tile[(row < ny ? yg_luma_slot(row) : yg_chroma_slot(row - ny)) * YG_PITCH + j] = rp[j];
+            }
+        }
+    }
+    __syncthreads();
+    const int yq = (threadIdx.x & 15) * 4;
+    const float sc = float(1.0 / 255.0);
+    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
+    const int64_t np = int64_t(a.H) * a.W;
+    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
+    {
+        float o[3][4];
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+        {
+            // rows beyond the tile (yq + 2i >= ny) convert whatever the LDS holds: never stored
+            const uint8_t* cp = tile + yg_chroma_slot((yq >> 1) + i) * YG_PITCH + (xx & ~1);
+            const YuvChroma c = yuv_chroma(cp[s.vFirst], cp[1 - s.vFirst]);
+#pragma unroll
+            for (int jj = 0; jj < 2; jj++)
+            {
+                const int j = 2 * i + jj;
+                int r, g, b;
+                yuv_rgb8(tile[yg_luma_slot(yq + j) * YG_PITCH + xx], c, r, g, b);
+                ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
+            }
+        }
+        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
     }
 }
 

@@ -147,7 +147,7 @@ struct PyramidRun
     bool scalePar = false;                        // the real scales on their own streams
     hipStream_t mainStream;
     bool wroteRank = false, wroteF32 = true;      // what the level kernels left: 16-bit rank cells, floats
-    PackedSrc reduced{};
+    PackedSrc reduced{}, converted{};
 
     PyramidRun(acf_hip_ctx* ctx, const float* frames_, int nF_)
         : c(ctx), p(ctx->p), pl(ctx->plan), nF(nF_), H(pl.H), W(pl.W), d(pl.d), d_in(pl.d_in), shrink(ctx->p.shrink), np0(int64_t(pl.H) * pl.W), frames(frames_),
@@ -176,16 +176,48 @@ int PyramidRun::ingest(const PackedSrc* u8, bool& ingestConverted)
     {
         return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: a plan for five input planes (image + M, O) takes float frames");
     }
+    const int inRows = c->rz.on ? c->rz.rows : H, inCols = c->rz.on ? c->rz.cols : W; // the caller's frames
+    const bool fusedYuv = u8 && pixIsYuv(u8->pix) && !c->rz.on && !fallbackForced(FB_YUV_UNFUSED);
+    if (u8 && pixIsYuv(u8->pix) && !fusedYuv)
+    {
+        // cvtColor first, as the apps do: in front of their Resizer (convert -> resize -> ingest), and as k_ingest_yuv420's fallback
+        U8Geom g;
+        if (const char* bad = u8Geom(u8->pix, inRows, inCols, u8->rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
+        {
+            return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_u8: ") + bad);
+        }
+        if (!u8PlanesOk(g, d_in))
+        {
+            return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: the plan's input planes (d) must be 3 for NV12 / NV21");
+        }
+        const size_t need = size_t(c->maxBatch) * inRows * inCols * 3;
+        if (c->yuvRgbBytes < need)
+        {
+            HIPCHK(c, hipStreamSynchronize(c->stream)); // (a batch in flight may still read the smaller buffer)
+            devRelease(c, c->d_yuvRgb);
+            c->yuvRgbBytes = 0;
+            if ((rc = devAlloc(c, &c->d_yuvRgb, need)))
+            {
+                return rc;
+            }
+            c->yuvRgbBytes = need;
+        }
+        if ((rc = launchYuvToRgb(c, yuvSrc(u8->frames, u8->pix, inRows, inCols, g), nF, c->d_yuvRgb)))
+        {
+            return rc;
+        }
+        converted = PackedSrc{ c->d_yuvRgb, ACF_HIP_PIX_RGB, 0 };
+        u8 = &converted;
+    }
     if (u8 && c->rz.on)
     {
         // the apps' Resizer (acf.cpp:117-148) in front of the ingest: the caller's frames are rz.rows x rz.cols
-        const int cpp = pixCpp(u8->pix);
-        const int stride = u8->rowStride > 0 ? u8->rowStride : c->rz.cols * cpp;
-        if (stride < c->rz.cols * cpp)
+        U8Geom g;
+        if (const char* bad = u8Geom(u8->pix, inRows, inCols, u8->rowStride, 0, 0, g))
         {
-            return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: row stride smaller than a row of the unreduced frame");
+            return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_u8 (the unreduced frame): ") + bad);
         }
-        if ((rc = launchResizeU8(c, c->rz, u8->frames, cpp, stride, nF, c->rz.d_out)))
+        if ((rc = launchResizeU8(c, c->rz, u8->frames, g.cpp, g.stride, nF, c->rz.d_out)))
         {
             return rc;
         }
@@ -195,7 +227,7 @@ int PyramidRun::ingest(const PackedSrc* u8, bool& ingestConverted)
     if (u8)
     {
         // 8-bit ingest (ACF.cpp:114-119,137; MatP.cpp:51-73), fused with the colour conversion below when there is one
-        prof(c, "k_ingest_u8");
+        prof(c, fusedYuv ? "k_ingest_yuv420" : "k_ingest_u8");
         ingestConverted = c->d_color && p.colorSpace != ACF_HIP_CS_HSV; // (hsv: planar ingest, then k_rgb2hsv like a float frame)
         if (ingestConverted)
         {

@@ -131,13 +131,38 @@ class HipDetector:
         self._chk(self.lib.acf_hip_run_host(self.ctx, capi.fptr(frames), frames.shape[0]))
 
     def pyramid_u8(self, frames, pix=capi.PIX_RGB, row_stride=0, n=None):
-        """frames: torch uint8 CUDA tensor [n][H][W][cpp] (upright, packed) or a raw device pointer."""
+        """frames: torch uint8 CUDA tensor [n][H][W][cpp] (upright, packed; PIX_NV12 / PIX_NV21: [n][frame bytes], see
+        u8_frame_bytes and set_yuv_layout) or a raw device pointer."""
         n = n if n is not None else frames.shape[0]
         self._chk(self.lib.acf_hip_pyramid_u8(self.ctx, C.c_void_p(_dev_ptr_u8(frames)), n, pix, row_stride))
 
     def run_u8(self, frames, pix=capi.PIX_RGB, row_stride=0, n=None):
         n = n if n is not None else frames.shape[0]
         self._chk(self.lib.acf_hip_run_u8(self.ctx, C.c_void_p(_dev_ptr_u8(frames)), n, pix, row_stride))
+
+    # ---- YUV 4:2:0 video frames (PIX_NV12 / PIX_NV21) in the 8-bit entries
+    @staticmethod
+    def u8_frame_bytes(pix, rows, cols, row_stride=0):
+        """Bytes from one tight frame of layout `pix` to the next (host arithmetic: no context, no GPU)."""
+        out = C.c_int64()
+        rc = capi.load().acf_hip_u8_frame_bytes(pix, rows, cols, row_stride, C.byref(out))
+        if rc:
+            raise HipError(rc, "acf_hip_u8_frame_bytes(pix=%d, %d x %d, stride %d)" % (pix, rows, cols, row_stride))
+        return out.value
+
+    def set_yuv_layout(self, chroma_offset=0, frame_stride=0):
+        """Where an NV12 / NV21 frame's chroma plane starts and how far frames are apart, in bytes (0, 0 = tight); until the next plan."""
+        self._chk(self.lib.acf_hip_set_yuv_layout(self.ctx, chroma_offset, frame_stride))
+
+    def yuv420_to_rgb(self, frame, rows, cols, pix=capi.PIX_NV12, row_stride=0, chroma_offset=0):
+        """frame: the bytes of one NV12 / NV21 frame (host, uint8) -> uint8 [rows][cols][3] R, G, B (cvtColor COLOR_YUV2RGB_NV12 / _NV21)."""
+        frame = np.ascontiguousarray(frame, dtype=np.uint8)
+        stride = row_stride or cols
+        if rows > 0 and cols > 0 and frame.size < (chroma_offset or stride * rows) + stride * (rows // 2):
+            raise HipError(capi.E_INVALID, "yuv420_to_rgb: frame buffer smaller than the frame")
+        out = np.zeros((max(rows, 0), max(cols, 0), 3), dtype=np.uint8)
+        self._chk(self.lib.acf_hip_op_yuv420_to_rgb(self.ctx, frame.ctypes.data, rows, cols, pix, row_stride, chroma_offset, out.ctypes.data))
+        return out
 
     # ---- the apps' resize to a minimum object width (acf.cpp:117-148 Resizer) in front of the 8-bit entries
     @staticmethod

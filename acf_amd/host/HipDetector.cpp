@@ -516,15 +516,13 @@ int HipDetector::operator()(const uint8_t* packed, int rows, int cols, int pix, 
     {
         throw Exception(ACF_HIP_E_UNSUPPORTED, "operator()(packed): 8-bit input must be upright (setIsTranspose(false))");
     }
-    const int cpp = pix == ACF_HIP_PIX_GRAY ? 1 : (pix == ACF_HIP_PIX_RGBA || pix == ACF_HIP_PIX_BGRA) ? 4 : 3;
-    const int stride = rowStrideBytes > 0 ? rowStrideBytes : cols * cpp;
+    const size_t bytes = u8FrameBytes(pix, rows, cols, rowStrideBytes); // (refuses an unknown layout, a short stride, odd NV12 / NV21 sizes)
     // one-frame stream: H2D on the copy stream, ingest + pyramid + cascade on the context's stream
-    if (m_streamCap == 0 || m_srcRows != rows || m_srcCols != cols || m_planD != (cpp == 1 ? 1 : 3) || m_dirty || pix != m_streamPix ||
-        stride != m_streamStride)
+    if (m_streamCap == 0 || m_srcRows != rows || m_srcCols != cols || m_planD != (pix == ACF_HIP_PIX_GRAY ? 1 : 3) || m_dirty || pix != m_streamPix ||
+        rowStrideBytes != m_streamStride)
     {
-        streamOpen(rows, cols, pix, stride, std::max(1, m_planBatch), 2);
+        streamOpen(rows, cols, pix, rowStrideBytes, std::max(1, m_planBatch), 2);
     }
-    const size_t bytes = size_t(stride) * rows;
     if (bytes > m_pinBytes)
     {
         pinnedFree(m_pin);
@@ -581,7 +579,17 @@ void HipDetector::streamOpen(int rows, int cols, int pix, int rowStrideBytes, in
     check(m_api->acf_hip_stream_open(m_ctx, pix, rowStrideBytes, maxDetectionsPerFrame, depth), "acf_hip_stream_open");
     m_streamCap = maxDetectionsPerFrame;
     m_streamPix = pix;
-    m_streamStride = rowStrideBytes > 0 ? rowStrideBytes : cols * (pix == ACF_HIP_PIX_GRAY ? 1 : (pix == ACF_HIP_PIX_RGBA || pix == ACF_HIP_PIX_BGRA) ? 4 : 3);
+    m_streamStride = rowStrideBytes;
+}
+
+size_t HipDetector::u8FrameBytes(int pix, int rows, int cols, int rowStrideBytes)
+{
+    int64_t n = 0;
+    if (hip::load().acf_hip_u8_frame_bytes(pix, rows, cols, rowStrideBytes, &n))
+    {
+        throw Exception(ACF_HIP_E_INVALID, "u8FrameBytes: unknown layout, empty frame, row stride smaller than a row, or odd NV12 / NV21 size");
+    }
+    return size_t(n);
 }
 
 int HipDetector::streamSubmit(const uint8_t* frames, int nFrames)

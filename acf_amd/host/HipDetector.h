@@ -275,7 +275,9 @@ public:
     int operator()(const float* rgbInterleaved, int rows, int cols, RectVec& objects, RealVec* scores = nullptr);
     // Packed 8-bit image (CV_8UC3 RGB / CV_8UC4 / CV_8UC1 of the reference's cv::Mat entry, ACF.cpp:135-141), upright
     // rows x cols, `pix` = ACF_HIP_PIX_*, `rowStrideBytes` 0 = tight.  /255, transpose, plane split and the colour
-    // conversion all happen on the device (acf_hip_run_u8).
+    // conversion all happen on the device (acf_hip_run_u8).  ACF_HIP_PIX_NV12 / _NV21: a YUV 4:2:0 video frame (rows x cols luma
+    // bytes, then rows / 2 rows of interleaved chroma pairs at the same stride; rows and cols even), converted as
+    // cvtColor(COLOR_YUV2RGB_NV12 / _NV21) does, on the device as well (include/acf_hip.h "YUV 4:2:0 input").
     int operator()(const uint8_t* packed, int rows, int cols, int pix, int rowStrideBytes, RectVec& objects, RealVec* scores = nullptr);
     // Multi-scale search on a pyramid (ACF.cpp:268-367).
     int operator()(const Pyramid& P, RectVec& objects, RealVec* scores = nullptr);
@@ -291,6 +293,8 @@ public:
     // reference's order, before NMS/prune are applied exactly as in operator().
     void streamOpen(int rows, int cols, int pix, int rowStrideBytes, int maxBatch, int depth = 2, int maxDetectionsPerFrame = 4096);
     int streamSubmit(const uint8_t* frames, int nFrames);
+    // bytes from one tight frame of layout `pix` to the next: what a batch for streamSubmit / a frame for operator()(packed) holds
+    static size_t u8FrameBytes(int pix, int rows, int cols, int rowStrideBytes = 0);
     void streamCollect(int ticket, std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
     void streamClose();
     static void* pinnedAlloc(size_t bytes);

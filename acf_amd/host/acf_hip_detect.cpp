@@ -3,8 +3,8 @@
 //
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N
 //                  [--luv] [--nms] [--batch] [--via-pyramid] [--max-count K] [--prune-ratio R]
-//   acf_hip_detect --model m.acfm --frames f.u8 --u8 rgb|bgr|rgba|bgra|gray --rows H --cols W --count N [--stream B] [--min-width M] ...
-//                  packed 8-bit upright frames; --stream B: batches of B frames through streamSubmit/streamCollect
+//   acf_hip_detect --model m.acfm --frames f.u8 --u8 rgb|bgr|rgba|bgra|gray|nv12|nv21 --rows H --cols W --count N [--stream B] [--min-width M] ...
+//                  packed 8-bit upright frames (nv12 / nv21: tight YUV 4:2:0 video frames); --stream B: batches of B frames through streamSubmit/streamCollect
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
@@ -196,11 +196,10 @@ int main(int argc, char** argv)
         if (a.count("u8"))
         {
             static const std::map<std::string, int> kPix = { { "rgb", ACF_HIP_PIX_RGB }, { "bgr", ACF_HIP_PIX_BGR }, { "rgba", ACF_HIP_PIX_RGBA },
-                { "bgra", ACF_HIP_PIX_BGRA }, { "gray", ACF_HIP_PIX_GRAY } };
+                { "bgra", ACF_HIP_PIX_BGRA }, { "gray", ACF_HIP_PIX_GRAY }, { "nv12", ACF_HIP_PIX_NV12 }, { "nv21", ACF_HIP_PIX_NV21 } };
             const int pix = kPix.at(a["u8"]);
-            const int cpp = pix == ACF_HIP_PIX_GRAY ? 1 : (pix == ACF_HIP_PIX_RGBA || pix == ACF_HIP_PIX_BGRA) ? 4 : 3;
             const int H = std::stoi(a.at("rows")), W = std::stoi(a.at("cols")), cnt = std::stoi(a.at("count"));
-            const size_t per = size_t(H) * W * cpp;
+            const size_t per = HipDetector::u8FrameBytes(pix, H, W);
             std::vector<uint8_t> frames(per * size_t(cnt));
             std::ifstream is(a.at("frames"), std::ios::binary);
             is.read(reinterpret_cast<char*>(frames.data()), std::streamsize(frames.size()));

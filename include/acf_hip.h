@@ -345,7 +345,11 @@ enum {
     ACF_HIP_PIX_BGR = 1,
     ACF_HIP_PIX_RGBA = 2,
     ACF_HIP_PIX_BGRA = 3,
-    ACF_HIP_PIX_GRAY = 4
+    ACF_HIP_PIX_GRAY = 4,
+    /* YUV 4:2:0 video frames as decoders hand them out (semi-planar: a luma plane, then one plane of interleaved chroma
+     * pairs, U,V for NV12 and V,U for NV21); see "YUV 4:2:0 input" below */
+    ACF_HIP_PIX_NV12 = 5,
+    ACF_HIP_PIX_NV21 = 6
 };
 
 /* The image entry for 8-bit input: cvt8UC3To32FC3 = convertTo(CV_32F, 1/255)
@@ -357,6 +361,41 @@ enum {
  * apart).  The plan's `d` must be 3 for the colour layouts and 1 for GRAY. */
 ACF_HIP_API int acf_hip_pyramid_u8(acf_hip_ctx* ctx, const uint8_t* frames_dev, int n_frames, int pix, int row_stride_bytes);
 ACF_HIP_API int acf_hip_run_u8(acf_hip_ctx* ctx, const uint8_t* frames_dev, int n_frames, int pix, int row_stride_bytes);
+
+/* YUV 4:2:0 input (ACF_HIP_PIX_NV12 / _NV21) in the 8-bit entries (acf_hip_pyramid_u8 / run_u8 / stream_*).
+ * Semantics: cvtColor(frame, COLOR_YUV2RGB_NV12 / _NV21) — the call a user of Detector::operator()(const cv::Mat&) makes on
+ * decoded video — followed by the image entry above: BT.601 limited range in 20-bit fixed point, the chroma pair of a 2 x 2
+ * block shared by its four pixels with no interpolation; all int32, >> arithmetic (floor):
+ *     CY = 1220542, CVR = 1673527, CVG = -852492, CUG = -409993, CUB = 2116026
+ *     y   = max(0, Y - 16) * CY
+ *     ruv = (1 << 19) + CVR * (V - 128)
+ *     guv = (1 << 19) + CVG * (V - 128) + CUG * (U - 128)
+ *     buv = (1 << 19) + CUB * (U - 128)
+ *     R = clamp((y + ruv) >> 20, 0, 255)   G = clamp((y + guv) >> 20, 0, 255)   B = clamp((y + buv) >> 20, 0, 255)
+ * cvtColor is OpenCV's (not part of the reference tree): the published algorithm of its imgproc/src/color_yuv.simd.hpp is
+ * restated; PARITY UNPINNED (DESIGN.md 7 says what was checked: within one code value of the rounded real BT.601 matrix on
+ * every (Y, U, V)).  One kernel takes the frames to the converted planar f32 image (k_ingest_yuv420); the planes are bit for
+ * bit those of the RGB layout fed with the R, G, B bytes above.
+ * Frame layout: h rows of w luma bytes, `row_stride_bytes` apart (0 = w); then h / 2 rows of w / 2 chroma pairs at the same
+ * row stride.  h and w must be even (of the plan, or of the unreduced frame with acf_hip_set_input_resize, where the order is
+ * convert, resize, ingest as in the apps); the plan's `d` must be 3 (the luma plane is limited range, not the grey cvtColor
+ * gives: a d = 1 plan is ACF_HIP_E_INVALID).
+ *  acf_hip_set_yuv_layout    decoder surfaces pad the luma plane to an aligned height and the frame to an aligned size:
+ *                            the chroma plane starts `chroma_offset_bytes` after a frame's first luma byte and frames are
+ *                            `frame_stride_bytes` apart; 0, 0 = tight (chroma at stride * h, frames stride * h * 3 / 2
+ *                            apart).  After acf_hip_plan, before acf_hip_stream_open; sticky until the next plan; the packed
+ *                            layouts ignore it.  A chroma offset inside the luma plane or a frame stride that lets frames
+ *                            overlap is refused by the run / open call, where the row stride is known
+ *  acf_hip_op_yuv420_to_rgb  the conversion alone, host buffers: src one frame of chroma_offset_bytes (0 = tight) +
+ *                            stride * rows / 2 bytes, dst rows x cols x 3 tight R, G, B
+ *  acf_hip_u8_frame_bytes    host arithmetic, no context, no GPU: the bytes from one tight frame of layout `pix` to the next
+ *                            (stride * rows for the packed layouts, stride * rows * 3 / 2 for NV12 / NV21; row_stride_bytes
+ *                            0 = tight rows).  ACF_HIP_E_INVALID for an unknown layout, sizes < 1, a stride smaller than a
+ *                            row, odd NV12 / NV21 sizes */
+ACF_HIP_API int acf_hip_set_yuv_layout(acf_hip_ctx* ctx, int64_t chroma_offset_bytes, int64_t frame_stride_bytes);
+ACF_HIP_API int acf_hip_op_yuv420_to_rgb(acf_hip_ctx* ctx, const uint8_t* src_host, int rows, int cols, int pix, int row_stride_bytes,
+    int64_t chroma_offset_bytes, uint8_t* dst_host);
+ACF_HIP_API int acf_hip_u8_frame_bytes(int pix, int rows, int cols, int row_stride_bytes, int64_t* out);
 
 /* The apps' resize to a minimum object width (src/app/acf/acf.cpp:117-148 `Resizer`,
  * GPUDetectionPipeline.cpp:250-266 computeDetectionWidth): scale = float(winSize.width) /
