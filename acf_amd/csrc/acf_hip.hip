@@ -1,6 +1,8 @@
 // acf_hip.hip — implementation of the C ABI in include/acf_hip.h: context,
 // planning, buffer ownership and kernel launches.  All device work is
 // enqueued on the context's stream; nothing here falls back to the CPU.
+// This file holds the context, the guards and helpers every entry shares, and the plan / run / stream entries; the stages'
+// logic, the read-back entries and the single-operator entries are textual parts (*.hip.h), included in the order of their use.
 #include "kernels.hip.h"
 
 #include <algorithm>
@@ -481,6 +483,30 @@ int fail(const acf_hip_ctx* c, int code, const std::string& msg)
     return code;
 }
 
+// The entry guards: 0, or the code the entry returns at once (a null context has nowhere to leave a text).  An entry calls one
+// through `if (int rc = needPlan(c, "detect")) return rc;`.
+int needCtx(const acf_hip_ctx* c)
+{
+    return c ? ACF_HIP_OK : ACF_HIP_E_INVALID;
+}
+int needPlan(const acf_hip_ctx* c, const char* who, const char* hint = "")
+{
+    return !c ? ACF_HIP_E_INVALID : c->hasPlan ? ACF_HIP_OK : fail(c, ACF_HIP_E_NOPLAN, std::string(who) + ": plan first" + hint);
+}
+// (the read-back entries have always answered a null context with E_NOPLAN)
+int needPlanRead(const acf_hip_ctx* c, const char* who)
+{
+    return c ? needPlan(c, who) : ACF_HIP_E_NOPLAN;
+}
+int needModel(const acf_hip_ctx* c, const char* who)
+{
+    return !c ? ACF_HIP_E_INVALID : c->hasModel ? ACF_HIP_OK : fail(c, ACF_HIP_E_NOMODEL, std::string(who) + ": set_model first");
+}
+int needStream(const acf_hip_ctx* c, const char* who)
+{
+    return !c ? ACF_HIP_E_INVALID : !c->slots.empty() ? ACF_HIP_OK : fail(c, ACF_HIP_E_INVALID, std::string(who) + ": stream_open first");
+}
+
 // Profile marker: an event recorded on the stream before the launch named
 // `name`; a kernel's time is the span to the next marker.
 // the CPU tables the three approximate sites evaluate (option "arith" = 1), or null: exact arithmetic
@@ -553,6 +579,64 @@ void devRelease(acf_hip_ctx* c, T*& p)
     }
     p = nullptr;
 }
+
+// Whatever devAlloc / devUpload add to the context's list while the mark lives is freed when it goes.  For acf_hip_op_acf_detect1:
+// its buffers come from buildCascadeTables / allocCascadeRun, which allocate into the context — so they cannot be a Scratch's.
+struct AllocMark
+{
+    acf_hip_ctx* c;
+    size_t mark;
+    ~AllocMark()
+    {
+        for (size_t i = mark; i < c->allocs.size(); i++)
+        {
+            (void)hipFree(c->allocs[i]);
+        }
+        c->allocs.resize(mark);
+    }
+};
+
+// The one-off device buffers of an operator entry (not the hot path): freed when the entry returns, whichever way.
+struct Scratch
+{
+    std::vector<void*> ptrs;
+    ~Scratch()
+    {
+        for (void* p : ptrs)
+        {
+            (void)hipFree(p);
+        }
+    }
+    template <class T>
+    T* alloc(size_t n)
+    {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess)
+        {
+            return nullptr;
+        }
+        ptrs.push_back(p);
+        return reinterpret_cast<T*>(p);
+    }
+    template <class T>
+    T* upload(const T* h, size_t n)
+    {
+        T* d = alloc<T>(n);
+        if (d && n && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+        {
+            return nullptr;
+        }
+        return d;
+    }
+    // an operator's tail: n elements of what the context's stream computed, on the host
+    template <class T>
+    static int download(acf_hip_ctx* c, const char* who, T* host, const T* dev, size_t n)
+    {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        e = e ? e : hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost);
+        return e ? fail(c, ACF_HIP_E_HIP, std::string(who) + ": " + hipGetErrorString(e)) : ACF_HIP_OK;
+    }
+};
 
 void freeAll(acf_hip_ctx* c)
 {
@@ -672,6 +756,14 @@ int ensureConstTables(acf_hip_ctx* c)
     return devAlloc(c, &c->d_dump, 1024);
 }
 
+// what every single-operator entry starts with: a context, its device current, the constant tables
+int opBegin(acf_hip_ctx* c)
+{
+    if (int rc = needCtx(c)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return ensureConstTables(c);
+}
+
 // rank pyramid: cells between the columns of a level (every column starts on 16 bytes)
 inline int rankPitch(int hP)
 {
@@ -685,6 +777,16 @@ inline int cdiv(int64_t a, int64_t b)
 
 // ---- kernel launch helpers (shared by the pyramid and the op_* entry points) ----
 // (A picker returns the instantiation a launch takes; each names its instantiations in the order the code object lists them.)
+
+// a kernel that takes more than 64 KiB of dynamic LDS asks for it first
+int allowLds(acf_hip_ctx* c, const void* kernel, size_t bytes)
+{
+    if (bytes > 64 * 1024)
+    {
+        HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
+    }
+    return ACF_HIP_OK;
+}
 
 using SmoothTri1Kernel = void (*)(const float*, float*, const SmoothJob*, int64_t, int64_t, float, int, float*);
 
@@ -902,42 +1004,6 @@ static bool colourPassthrough(const acf_hip_params& p, int nIn)
 
 } // namespace
 
-namespace
-{
-struct Scratch
-{
-    std::vector<void*> ptrs;
-    ~Scratch()
-    {
-        for (void* p : ptrs)
-        {
-            (void)hipFree(p);
-        }
-    }
-    template <class T>
-    T* alloc(size_t n)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess)
-        {
-            return nullptr;
-        }
-        ptrs.push_back(p);
-        return reinterpret_cast<T*>(p);
-    }
-    template <class T>
-    T* upload(const T* h, size_t n)
-    {
-        T* d = alloc<T>(n);
-        if (d && n && hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-        {
-            return nullptr;
-        }
-        return d;
-    }
-};
-} // namespace
-
 // gradMagNorm as a stand-alone kernel (only the op_gradient_mag entry point
 // needs it; the pyramid fuses it into k_chns).  toolbox/gradientMex.cpp:254-275.
 __global__ void __launch_bounds__(256) k_norm(float* __restrict__ M, const float* __restrict__ S, int n, float norm, const uint32_t* __restrict__ x86)
@@ -1028,7 +1094,25 @@ int onFrameOwner(acf_hip_ctx* c, int frame, const char* outOfRange, Fn fn)
     }
     acf_hip_ctx* k = c->kids[size_t(frame / c->kidChunk)];
     const int rc = fn(k, frame % c->kidChunk);
-    return rc ? fail(c, rc, k->err) : rc;
+    return rc == ACF_HIP_OK ? rc : fail(c, rc, k->err);
+}
+// A whole run of nF frames on a context with children: run(kid, the kid's first frame, its count) on every child's share; then the
+// parent holds the batch (`who` names the entry in the text for a bad nF)
+template <class Run>
+int runOnKids(acf_hip_ctx* c, const char* who, const float* frames, int nF, Run run)
+{
+    if (!frames || nF <= 0 || nF > c->maxBatch)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": n_frames out of range");
+    }
+    const size_t per = size_t(c->plan.d_in) * c->plan.H * c->plan.W;
+    const int rc = forEachKid(c, nF, [&](acf_hip_ctx* k, int first, int n) { return run(k, frames + first * per, n); });
+    if (!rc)
+    {
+        c->lastBatch = nF;
+        c->pyramidValid = c->detectValid = true;
+    }
+    return rc;
 }
 } // namespace
 
@@ -1506,15 +1590,8 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
 
 int acf_hip_plan(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_hits)
 {
-    if (!c)
-    {
-        return ACF_HIP_E_INVALID;
-    }
     dropGraph(c);
-    if (!c->hasModel)
-    {
-        return fail(c, ACF_HIP_E_NOMODEL, "plan: set_model first");
-    }
+    if (int rc = needModel(c, "plan")) return rc;
     if (max_batch <= 0 || max_hits <= 0)
     {
         return fail(c, ACF_HIP_E_INVALID, "plan: max_batch/max_hits");
@@ -1595,10 +1672,7 @@ int acf_hip_plan(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_
 
 int acf_hip_num_levels(const acf_hip_ctx* c, int* nScales, int* nChns)
 {
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
+    if (int rc = needPlanRead(c, "num_levels")) return rc;
     if (nScales)
     {
         *nScales = int(c->plan.levels.size());
@@ -1612,10 +1686,7 @@ int acf_hip_num_levels(const acf_hip_ctx* c, int* nScales, int* nChns)
 
 int acf_hip_get_levels(const acf_hip_ctx* c, acf_hip_level* out, int cap)
 {
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
+    if (int rc = needPlanRead(c, "get_levels")) return rc;
     if (!out || cap < int(c->plan.levels.size()))
     {
         return fail(c, ACF_HIP_E_INVALID, "get_levels: capacity");
@@ -1642,10 +1713,7 @@ int acf_hip_get_ldcf_levels(const acf_hip_ctx* c, acf_hip_level* out, int cap)
 
 int acf_hip_pyramid_floats(const acf_hip_ctx* c, int64_t* n)
 {
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
+    if (int rc = needPlanRead(c, "pyramid_floats")) return rc;
     *n = c->plan.pyr_floats;
     return ACF_HIP_OK;
 }
@@ -1690,8 +1758,6 @@ int acf_hip_get_lambdas(acf_hip_ctx* c, int frame, double out[3])
     });
 }
 
-static int allowLds(acf_hip_ctx* c, const void* kernel, size_t bytes);
-
 // A/B knob: ACF_HIP_RESAMPLE_GENERIC forces the gather kernel for the image resamples (read once)
 static bool resampleGenericOnly()
 {
@@ -1714,16 +1780,7 @@ struct PackedSrc
     const uint8_t* frames;
     int pix, rowStride;
 };
-int pyramidImpl(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF);
-} // namespace
 
-int acf_hip_pyramid(acf_hip_ctx* c, const float* frames, int nF)
-{
-    return pyramidImpl(c, frames, nullptr, nF);
-}
-
-namespace
-{
 using IngestKernel = void (*)(IngestArgs);
 using YuvIngestKernel = void (*)(IngestArgs, YuvSrc);
 
@@ -1990,9 +2047,11 @@ static void clearRepairFlags(acf_hip_ctx* c)
     }
 }
 
-int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF);
+} // namespace
 
-int pyramidImpl(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF)
+#include "pyramid_run.hip.h" // PyramidRun (acf_hip_pyramid's stages), pyramidBody
+
+static int pyramidImpl(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF)
 {
     const int rc = pyramidBody(c, frames, u8, nF);
     if (rc && c && c->hasPlan && c->kids.empty())
@@ -2002,16 +2061,14 @@ int pyramidImpl(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
     return rc;
 }
 
-} // namespace
-
-#include "pyramid_run.hip.h"
+int acf_hip_pyramid(acf_hip_ctx* c, const float* frames, int nF)
+{
+    return pyramidImpl(c, frames, nullptr, nF);
+}
 
 int acf_hip_pyramid_u8(acf_hip_ctx* c, const uint8_t* frames, int nF, int pix, int rowStride)
 {
-    if (!c)
-    {
-        return ACF_HIP_E_INVALID;
-    }
+    if (int rc = needCtx(c)) return rc;
     PackedSrc u{ frames, pix, rowStride };
     return pyramidImpl(c, nullptr, &u, nF);
 }
@@ -2029,10 +2086,7 @@ int acf_hip_u8_frame_bytes(int pix, int rows, int cols, int rowStride, int64_t* 
 
 int acf_hip_set_yuv_layout(acf_hip_ctx* c, int64_t chromaOff, int64_t frameStride)
 {
-    if (!c || !c->hasPlan)
-    {
-        return c ? fail(c, ACF_HIP_E_NOPLAN, "set_yuv_layout: plan first") : ACF_HIP_E_INVALID;
-    }
+    if (int rc = needPlan(c, "set_yuv_layout")) return rc;
     if (!c->kids.empty() || !c->slots.empty())
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, "set_yuv_layout: not with option \"streams\" > 1; before acf_hip_stream_open");
@@ -2047,39 +2101,6 @@ int acf_hip_set_yuv_layout(acf_hip_ctx* c, int64_t chromaOff, int64_t frameStrid
     return ACF_HIP_OK;
 }
 
-int acf_hip_op_yuv420_to_rgb(acf_hip_ctx* c, const uint8_t* src, int rows, int cols, int pix, int rowStride, int64_t chromaOff, uint8_t* dst)
-{
-    if (!c || !src || !dst || !pixIsYuv(pix) || chromaOff < 0)
-    {
-        return c ? fail(c, ACF_HIP_E_INVALID, "op_yuv420_to_rgb: arguments (pix: ACF_HIP_PIX_NV12 or _NV21)") : ACF_HIP_E_INVALID;
-    }
-    U8Geom g;
-    if (const char* bad = u8Geom(pix, rows, cols, rowStride, chromaOff, 0, g))
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string("op_yuv420_to_rgb: ") + bad);
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    // one-off buffers (an operator entry, not the hot path)
-    uint8_t *dS = nullptr, *dD = nullptr;
-    const size_t nS = size_t(g.frameStride), nD = size_t(rows) * cols * 3;
-    bool ok = hipMalloc(reinterpret_cast<void**>(&dS), nS) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&dD), nD) == hipSuccess &&
-        hipMemcpy(dS, src, nS, hipMemcpyHostToDevice) == hipSuccess;
-    int rc = ACF_HIP_OK;
-    if (ok)
-    {
-        rc = launchYuvToRgb(c, yuvSrc(dS, pix, rows, cols, g), 1, dD);
-        ok = !rc && hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(dst, dD, nD, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    (void)hipFree(dS);
-    (void)hipFree(dD);
-    if (!ok && !rc)
-    {
-        (void)hipGetLastError();
-        return fail(c, ACF_HIP_E_HIP, "op_yuv420_to_rgb: device allocation or copy failed");
-    }
-    return rc;
-}
-
 int acf_hip_resize_dims(int rows, int cols, double scale, int* out_rows, int* out_cols)
 {
     if (!out_rows || !out_cols || rows < 1 || cols < 1 || !(scale > 0))
@@ -2092,10 +2113,7 @@ int acf_hip_resize_dims(int rows, int cols, double scale, int* out_rows, int* ou
 
 int acf_hip_set_input_resize(acf_hip_ctx* c, int srcRows, int srcCols, double scale)
 {
-    if (!c || !c->hasPlan)
-    {
-        return c ? fail(c, ACF_HIP_E_NOPLAN, "set_input_resize: plan first (for the reduced size, acf_hip_resize_dims)") : ACF_HIP_E_INVALID;
-    }
+    if (int rc = needPlan(c, "set_input_resize", " (for the reduced size, acf_hip_resize_dims)")) return rc;
     if (!c->kids.empty() || !c->slots.empty())
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, "set_input_resize: not with option \"streams\" > 1; before acf_hip_stream_open");
@@ -2144,71 +2162,7 @@ int acf_hip_set_input_resize(acf_hip_ctx* c, int srcRows, int srcCols, double sc
     return ACF_HIP_OK;
 }
 
-int acf_hip_op_resize_u8(acf_hip_ctx* c, const uint8_t* src, int rows, int cols, int cpp, int rowStride, double scale, uint8_t* dst, int dstRows, int dstCols)
-{
-    if (!c || !src || !dst || cpp < 1 || cpp > 4)
-    {
-        return c ? fail(c, ACF_HIP_E_INVALID, "op_resize_u8: arguments") : ACF_HIP_E_INVALID;
-    }
-    if (cpp == 2)
-    {
-        // OpenCV's 2 x 2 area path rounds two-channel pixels with saturate_cast(sum * 0.25f) (half to even), not (sum + 2) >> 2 as for
-        // 1, 3 and 4 channels; no pixel format of the path has two channels (ACF_HIP_PIX_*), so the form is not restated
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "op_resize_u8: two-channel images are not supported (1, 3 or 4 bytes per pixel)");
-    }
-    acf_hip_ctx::InputResize rz;
-    if (buildResizeTables(rows, cols, scale, rz.t) || rz.t.drows != dstRows || rz.t.dcols != dstCols)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "op_resize_u8: dst size must be acf_hip_resize_dims(rows, cols, scale)");
-    }
-    const int stride = rowStride > 0 ? rowStride : cols * cpp;
-    if (stride < cols * cpp)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "op_resize_u8: row stride smaller than a row");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    // one-off buffers (an operator entry, not the hot path)
-    uint8_t *dS = nullptr, *dD = nullptr;
-    const size_t nS = size_t(stride) * rows, nD = size_t(dstRows) * dstCols * cpp;
-    std::vector<void*> tmp;
-    auto up = [&](int32_t** d, const std::vector<int32_t>& v) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(v.size(), 1) * 4) != hipSuccess)
-        {
-            return false;
-        }
-        tmp.push_back(p);
-        *d = static_cast<int32_t*>(p);
-        return v.empty() || hipMemcpy(p, v.data(), v.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    bool ok = hipMalloc(reinterpret_cast<void**>(&dS), nS) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&dD), nD) == hipSuccess;
-    ok = ok && up(&rz.d_xlin, rz.t.xlin) && up(&rz.d_ylin, rz.t.ylin) && up(&rz.d_xrun, rz.t.xrun) && up(&rz.d_yrun, rz.t.yrun) && up(&rz.d_xtap, rz.t.xtap) &&
-        up(&rz.d_ytap, rz.t.ytap);
-    int rc = ACF_HIP_OK;
-    if (ok)
-    {
-        ok = hipMemcpy(dS, src, nS, hipMemcpyHostToDevice) == hipSuccess;
-        if (ok)
-        {
-            rc = launchResizeU8(c, rz, dS, cpp, stride, 1, dD);
-        }
-        ok = ok && !rc && hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(dst, dD, nD, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    for (void* p : tmp)
-    {
-        (void)hipFree(p);
-    }
-    (void)hipFree(dS);
-    (void)hipFree(dD);
-    if (!ok && !rc)
-    {
-        (void)hipGetLastError();
-        return fail(c, ACF_HIP_E_HIP, "op_resize_u8: device allocation or copy failed");
-    }
-    return rc;
-}
-
-#include "cascade_run.hip.h"    // allowLds, wholeCascadeTiled, planCascadeCall, clearCounters, runCascade, launchNms, runLdcf
+#include "cascade_run.hip.h"    // wholeCascadeTiled, planCascadeCall, clearCounters, runCascade, launchNms, runLdcf
 
 int acf_hip_detect(acf_hip_ctx* c)
 {
@@ -2225,10 +2179,7 @@ int acf_hip_detect(acf_hip_ctx* c)
         }
         return rc;
     }
-    if (!c || !c->hasPlan)
-    {
-        return c ? fail(c, ACF_HIP_E_NOPLAN, "detect: plan first") : ACF_HIP_E_INVALID;
-    }
+    if (int rc = needPlan(c, "detect")) return rc;
     if (!c->pyramidValid)
     {
         return fail(c, ACF_HIP_E_INVALID, "detect: no pyramid (call acf_hip_pyramid)");
@@ -2302,18 +2253,7 @@ int acf_hip_run(acf_hip_ctx* c, const float* frames, int nF)
 {
     if (c && !c->kids.empty())
     {
-        if (!frames || nF <= 0 || nF > c->maxBatch)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "run: n_frames out of range");
-        }
-        const size_t per = size_t(c->plan.d_in) * c->plan.H * c->plan.W;
-        const int rc = forEachKid(c, nF, [&](acf_hip_ctx* k, int first, int n) { return acf_hip_run(k, frames + first * per, n); });
-        if (!rc)
-        {
-            c->lastBatch = nF;
-            c->pyramidValid = c->detectValid = true;
-        }
-        return rc;
+        return runOnKids(c, "run", frames, nF, acf_hip_run);
     }
     // option "graph": the launches of this call — same frames pointer, same batch size, nothing in the path that reads back or
     // records events of its own — as one captured graph.  The first calls run plainly (they may allocate); a capture that the
@@ -2386,23 +2326,9 @@ int acf_hip_run_host(acf_hip_ctx* c, const float* frames_host, int nF)
 {
     if (c && !c->kids.empty())
     {
-        if (!frames_host || nF <= 0 || nF > c->maxBatch)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "run_host: n_frames out of range");
-        }
-        const size_t per = size_t(c->plan.d_in) * c->plan.H * c->plan.W;
-        const int rc = forEachKid(c, nF, [&](acf_hip_ctx* k, int first, int n) { return acf_hip_run_host(k, frames_host + first * per, n); });
-        if (!rc)
-        {
-            c->lastBatch = nF;
-            c->pyramidValid = c->detectValid = true;
-        }
-        return rc;
+        return runOnKids(c, "run_host", frames_host, nF, acf_hip_run_host);
     }
-    if (!c || !c->hasPlan)
-    {
-        return c ? fail(c, ACF_HIP_E_NOPLAN, "run_host: plan first") : ACF_HIP_E_INVALID;
-    }
+    if (int rc = needPlan(c, "run_host")) return rc;
     if (!frames_host || nF <= 0 || nF > c->maxBatch)
     {
         return fail(c, ACF_HIP_E_INVALID, "run_host: n_frames out of range");
@@ -2483,10 +2409,7 @@ int acf_hip_stream_close(acf_hip_ctx* c)
 
 int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int depth)
 {
-    if (!c || !c->hasPlan)
-    {
-        return c ? fail(c, ACF_HIP_E_NOPLAN, "stream_open: plan first") : ACF_HIP_E_INVALID;
-    }
+    if (int rc = needPlan(c, "stream_open")) return rc;
     if (!c->kids.empty())
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, "stream_open: not available with option \"streams\" > 1");
@@ -2531,10 +2454,7 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
 
 int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, int* ticket)
 {
-    if (!c || c->slots.empty())
-    {
-        return c ? fail(c, ACF_HIP_E_INVALID, "stream_submit: stream_open first") : ACF_HIP_E_INVALID;
-    }
+    if (int rc = needStream(c, "stream_submit")) return rc;
     if (!frames_host || nF <= 0 || nF > c->maxBatch)
     {
         return fail(c, ACF_HIP_E_INVALID, "stream_submit: n_frames out of range");
@@ -2574,10 +2494,7 @@ int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, in
 
 int acf_hip_stream_collect(acf_hip_ctx* c, int ticket, const int32_t** records, int* nFrames)
 {
-    if (!c || c->slots.empty())
-    {
-        return c ? fail(c, ACF_HIP_E_INVALID, "stream_collect: stream_open first") : ACF_HIP_E_INVALID;
-    }
+    if (int rc = needStream(c, "stream_collect")) return rc;
     if (ticket != c->nextCollect || ticket >= c->nextTicket)
     {
         return fail(c, ACF_HIP_E_INVALID, "stream_collect: tickets are collected in submission order");
@@ -2625,128 +2542,6 @@ int acf_hip_synchronize(acf_hip_ctx* c)
     return ACF_HIP_OK;
 }
 
-int acf_hip_profile_get(acf_hip_ctx* c, int* n, const char** names, float* ms, int* launches, int cap)
-{
-    if (!c || !n)
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    if (!c->kids.empty())
-    {
-        // sum over the sub-batch contexts (their kernels overlap in time: the sum exceeds the wall clock)
-        std::vector<const char*> nm;
-        std::vector<float> tot;
-        std::vector<int> cnt;
-        for (acf_hip_ctx* k : c->kids)
-        {
-            int kn = 0;
-            const char* knames[64];
-            float kms[64];
-            int kl[64];
-            int rc = acf_hip_profile_get(k, &kn, knames, kms, kl, 64);
-            if (rc)
-            {
-                return fail(c, rc, k->err);
-            }
-            for (int i = 0; i < std::min(kn, 64); i++)
-            {
-                size_t j = 0;
-                for (; j < nm.size() && strcmp(nm[j], knames[i]); j++)
-                {
-                }
-                if (j == nm.size())
-                {
-                    nm.push_back(knames[i]);
-                    tot.push_back(0.f);
-                    cnt.push_back(0);
-                }
-                tot[j] += kms[i];
-                cnt[j] += kl[i];
-            }
-        }
-        *n = int(nm.size());
-        for (int i = 0; i < std::min(*n, cap); i++)
-        {
-            if (names) names[i] = nm[size_t(i)];
-            if (ms) ms[i] = tot[size_t(i)];
-            if (launches) launches[i] = cnt[size_t(i)];
-        }
-        return ACF_HIP_OK;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the side streams were joined into it)
-    std::vector<const char*> nm;
-    std::vector<float> tot;
-    std::vector<int> cnt;
-    for (size_t i = 0; i + 1 < c->evUsed; i++)
-    {
-        const char* name = c->evName[i];
-        if (!strcmp(name, "(end)"))
-        {
-            continue;
-        }
-        // the kernel ends where the next event of the same stream was recorded (real scales run on their own streams)
-        size_t j = i + 1;
-        while (j < c->evUsed && c->evStream[j] != c->evStream[i])
-        {
-            j++;
-        }
-        float dt = 0;
-        if (j >= c->evUsed || hipEventElapsedTime(&dt, c->evPool[i], c->evPool[j]) != hipSuccess)
-        {
-            continue;
-        }
-        size_t k = 0;
-        for (; k < nm.size(); k++)
-        {
-            if (!strcmp(nm[k], name))
-            {
-                break;
-            }
-        }
-        if (k == nm.size())
-        {
-            nm.push_back(name);
-            tot.push_back(0.f);
-            cnt.push_back(0);
-        }
-        tot[k] += dt;
-        cnt[k]++;
-    }
-    c->evUsed = 0;
-    *n = int(nm.size());
-    for (int k = 0; k < *n && k < cap; k++)
-    {
-        if (names)
-        {
-            names[k] = nm[k];
-        }
-        if (ms)
-        {
-            ms[k] = tot[k];
-        }
-        if (launches)
-        {
-            launches[k] = cnt[k];
-        }
-    }
-    return ACF_HIP_OK;
-}
-
-static int fetchCounts(acf_hip_ctx* c)
-{
-    if (!c->detectValid)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "no detections (call acf_hip_detect)");
-    }
-    if (!c->countsFetched)
-    {
-        HIPCHK(c, hipMemcpyAsync(c->h_counts.data(), nmsActive(c) ? c->d_nmsCounts : c->cs.d_counts, sizeof(int32_t) * c->lastBatch, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->countsFetched = true;
-    }
-    return ACF_HIP_OK;
-}
-
 static int checkNmsParams(acf_hip_ctx* c, const acf_hip_nms_params* q)
 {
     if (q->type < 0 || q->type > 2 || !(q->overlap == q->overlap) || (q->prune && q->maxCount < 0))
@@ -2784,1120 +2579,8 @@ int acf_hip_set_nms(acf_hip_ctx* c, const acf_hip_nms_params* q)
     return ACF_HIP_OK;
 }
 
-int acf_hip_op_nms(acf_hip_ctx* c, const int32_t* boxes, const double* scores, int n, const acf_hip_nms_params* q, int32_t* keep_idx, int* count)
-{
-    if (!c || !q || !count || n < 0 || (n > 0 && (!boxes || !scores || !keep_idx)))
-    {
-        return c ? fail(c, ACF_HIP_E_INVALID, "op_nms: arguments") : ACF_HIP_E_INVALID;
-    }
-    int rc = checkNmsParams(c, q);
-    if (rc)
-    {
-        return rc;
-    }
-    if (n == 0 || q->type == 0)
-    {
-        // bbNms returns its input for an empty list and for type "none" (bbNms.cpp:262-273); prune still applies to the caller
-        for (int i = 0; i < n; i++)
-        {
-            keep_idx[i] = i;
-        }
-        *count = n;
-        return ACF_HIP_OK;
-    }
-    if (n > NMS_CAP)
-    {
-        return fail(c, ACF_HIP_E_CAPACITY, "op_nms: more than ACF_HIP_NMS_CAP boxes");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    // one allocation, freed on every exit: boxes [n][4] int32 | scores [n] f64 | keep [NMS_CAP] int32 | count
-    const size_t offSc = (size_t(n) * 16 + 7) / 8 * 8, offKeep = offSc + size_t(n) * 8, offN = offKeep + size_t(NMS_CAP) * 4;
-    char* d_all = nullptr;
-    HIPCHK(c, hipMalloc(&d_all, offN + 4));
-    int32_t *d_box = reinterpret_cast<int32_t*>(d_all), *d_keep = reinterpret_cast<int32_t*>(d_all + offKeep), *d_n = reinterpret_cast<int32_t*>(d_all + offN);
-    double* d_sc = reinterpret_cast<double*>(d_all + offSc);
-    auto cleanup = [&]() { (void)hipFree(d_all); };
-    NmsArgs a{};
-    a.boxes = d_box;
-    a.scores = d_sc;
-    a.nOp = n;
-    fillNmsArgs(a, *q);
-    a.keep = d_keep;
-    a.nKeep = d_n;
-    hipError_t e = hipMemcpyAsync(d_box, boxes, size_t(n) * 16, hipMemcpyHostToDevice, c->stream);
-    e = e ? e : hipMemcpyAsync(d_sc, scores, size_t(n) * 8, hipMemcpyHostToDevice, c->stream);
-    if (!e && (rc = allowLds(c, reinterpret_cast<const void*>(&k_nms), kNmsLds)))
-    {
-        cleanup();
-        return rc;
-    }
-    int32_t m = 0;
-    if (!e)
-    {
-        hipLaunchKernelGGL(k_nms, dim3(1), dim3(1024), kNmsLds, c->stream, a);
-        e = hipGetLastError();
-    }
-    e = e ? e : hipMemcpyAsync(&m, d_n, 4, hipMemcpyDeviceToHost, c->stream);
-    e = e ? e : hipStreamSynchronize(c->stream);
-    if (!e && m > 0)
-    {
-        e = hipMemcpy(keep_idx, d_keep, size_t(m) * 4, hipMemcpyDeviceToHost);
-    }
-    cleanup();
-    if (e)
-    {
-        c->err = std::string("op_nms: ") + hipGetErrorString(e);
-        return ACF_HIP_E_HIP;
-    }
-    *count = m;
-    return ACF_HIP_OK;
-}
+#include "readback.hip.h" // fetchCounts, readRecords and the get_* entries, export_detections, read_level / _rank_level / _tap, profile_get
 
-// raw (pre-NMS) count of one frame of the last batch
-static int rawCount(acf_hip_ctx* c, int frame, int* n)
-{
-    if (!nmsActive(c))
-    {
-        *n = c->h_counts[frame];
-        return ACF_HIP_OK;
-    }
-    int32_t v = 0;
-    HIPCHK(c, hipMemcpyAsync(&v, c->cs.d_counts + frame, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *n = v;
-    return ACF_HIP_OK;
-}
-
-enum RecordList
-{
-    REC_DETECTIONS, // the detections, after the device NMS when it is on
-    REC_RAW,        // the detections before the device NMS
-    REC_HITS        // the hits behind REC_DETECTIONS, one per detection
-};
-
-// One frame's list of the last batch: *count = its length, at most min(cap, max_hits) records into out
-static int readRecords(acf_hip_ctx* c, int frame, RecordList which, void* out, int cap, int* count)
-{
-    static const char* const frameText[] = { "get_detections: frame index", "get_raw_detections: frame index", "get_hits: frame index" };
-    return onFrameOwner(c, frame, frameText[which], [&](acf_hip_ctx* c, int frame) -> int {
-        if (!c || !c->hasPlan)
-        {
-            return ACF_HIP_E_NOPLAN;
-        }
-        int rc = fetchCounts(c);
-        if (rc)
-        {
-            return rc;
-        }
-        if (frame < 0 || frame >= c->lastBatch)
-        {
-            return fail(c, ACF_HIP_E_INVALID, frameText[which]);
-        }
-        int n = c->h_counts[frame];
-        if (which == REC_RAW && (rc = rawCount(c, frame, &n)))
-        {
-            return rc;
-        }
-        if (n < 0) // (k_nms's count for a frame with more than NMS_CAP detections; a raw count is never negative)
-        {
-            return fail(c, ACF_HIP_E_CAPACITY, "more than ACF_HIP_NMS_CAP detections into the device NMS: take the raw list (acf_hip_get_raw_detections) and suppress it on the host");
-        }
-        if (which == REC_HITS && nmsActive(c))
-        {
-            // hit i belongs to detection i of acf_hip_get_detections: the survivors' entries of the raw list, through k_nms's keep indices
-            if (n > c->maxHits)
-            {
-                return fail(c, ACF_HIP_E_CAPACITY, "more hits than max_hits; re-plan with a larger capacity");
-            }
-            if (count)
-            {
-                *count = n;
-            }
-            const int m = std::min(n, cap);
-            if (m > 0 && out)
-            {
-                int nRaw = 0;
-                if ((rc = rawCount(c, frame, &nRaw)))
-                {
-                    return rc;
-                }
-                nRaw = std::min(nRaw, c->maxHits);
-                std::vector<int32_t> keep(static_cast<size_t>(m));
-                std::vector<acf_hip_hit> raw(static_cast<size_t>(std::max(nRaw, 1)));
-                HIPCHK(c, hipMemcpy(keep.data(), c->d_nmsKeep + size_t(frame) * NMS_CAP, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
-                HIPCHK(c, hipMemcpy(raw.data(), c->cs.d_sorted + size_t(frame) * c->maxHits, sizeof(acf_hip_hit) * nRaw, hipMemcpyDeviceToHost));
-                for (int i = 0; i < m; i++)
-                {
-                    if (keep[size_t(i)] < 0 || keep[size_t(i)] >= nRaw)
-                    {
-                        return fail(c, ACF_HIP_E_INVALID, "get_hits: survivor index outside the raw list");
-                    }
-                    static_cast<acf_hip_hit*>(out)[i] = raw[size_t(keep[size_t(i)])];
-                }
-            }
-            return ACF_HIP_OK;
-        }
-        if (count)
-        {
-            *count = n;
-        }
-        const int m = std::min(std::min(n, c->maxHits), cap);
-        if (m > 0 && out)
-        {
-            const size_t at = size_t(frame) * c->maxHits, rec = which == REC_HITS ? sizeof(acf_hip_hit) : sizeof(acf_hip_detection);
-            const void* src = which == REC_HITS ? static_cast<const void*>(c->cs.d_sorted + at)
-                                                : (which == REC_DETECTIONS && nmsActive(c) ? c->d_nmsDets : c->cs.d_dets) + at;
-            HIPCHK(c, hipMemcpy(out, src, rec * m, hipMemcpyDeviceToHost));
-        }
-        if (n > c->maxHits)
-        {
-            return fail(c, ACF_HIP_E_CAPACITY, "more hits than max_hits; re-plan with a larger capacity");
-        }
-        return ACF_HIP_OK;
-    });
-}
-
-int acf_hip_get_detections(acf_hip_ctx* c, int frame, acf_hip_detection* out, int cap, int* count)
-{
-    return readRecords(c, frame, REC_DETECTIONS, out, cap, count);
-}
-
-int acf_hip_get_raw_detections(acf_hip_ctx* c, int frame, acf_hip_detection* out, int cap, int* count)
-{
-    return readRecords(c, frame, REC_RAW, out, cap, count);
-}
-
-int acf_hip_get_hits(acf_hip_ctx* c, int frame, acf_hip_hit* out, int cap, int* count)
-{
-    return readRecords(c, frame, REC_HITS, out, cap, count);
-}
-
-int acf_hip_export_detections(acf_hip_ctx* c, int32_t* dst_dev, int cap)
-{
-    if (c && !c->kids.empty())
-    {
-        if (!c->detectValid || !dst_dev || cap <= 0)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "export_detections: nothing to export");
-        }
-        return forEachKid(c, c->lastBatch,
-            [&](acf_hip_ctx* k, int first, int) { return acf_hip_export_detections(k, dst_dev + first * (1 + 6 * size_t(cap)), cap); });
-    }
-    if (!c || !c->hasPlan)
-    {
-        return ACF_HIP_E_NOPLAN;
-    }
-    if (!c->detectValid || !dst_dev || cap <= 0)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "export_detections: nothing to export");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_export, dim3(cdiv(cap, 256), c->lastBatch), dim3(256), 0, c->stream,
-        (const acf_hip_detection*)(nmsActive(c) ? c->d_nmsDets : c->cs.d_dets), (const int32_t*)(nmsActive(c) ? c->d_nmsCounts : c->cs.d_counts), c->maxHits, cap, dst_dev);
-    LAUNCHCHK(c, "k_export");
-    return ACF_HIP_OK;
-}
-
-int acf_hip_read_level(acf_hip_ctx* c, int frame, int level, float* host_out)
-{
-    return onFrameOwner(c, frame, "read_level: arguments", [&](acf_hip_ctx* c, int frame) -> int {
-        if (!c || !c->hasPlan)
-        {
-            return ACF_HIP_E_NOPLAN;
-        }
-        if (!c->pyramidValid || frame < 0 || frame >= c->lastBatch || level < 0 || level >= int(c->plan.levels.size()) || !host_out)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "read_level: arguments");
-        }
-        if (!c->floatPyramid)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "read_level: the float pyramid was not kept (option keep_pyramid = 0: the levels left as rank cells only)");
-        }
-        const acf_hip_level& l = c->plan.levels[level];
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(host_out, c->d_pyr + size_t(frame) * c->plan.pyr_floats + l.offset, sizeof(float) * c->plan.nChns * l.hP * l.wP, hipMemcpyDeviceToHost));
-        return ACF_HIP_OK;
-    });
-}
-
-int acf_hip_read_rank_level(acf_hip_ctx* c, int frame, int level, uint16_t* host_out)
-{
-    return onFrameOwner(c, frame, "read_rank_level: arguments, or no detect since the last pyramid", [&](acf_hip_ctx* c, int frame) -> int {
-        if (!c || !c->hasPlan)
-        {
-            return ACF_HIP_E_NOPLAN;
-        }
-        if (!rankCellsOn(c, c->cs))
-        {
-            return fail(c, ACF_HIP_E_UNSUPPORTED, "read_rank_level: the plan has no rank cells (model not depth 2 / thresholds too dense / option rank_cells off / LDCF)");
-        }
-        if (!c->pyramidValid || !c->ranksValid || frame < 0 || frame >= c->lastBatch || level < 0 || level >= int(c->plan.levels.size()) || !host_out)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "read_rank_level: arguments, or no detect since the last pyramid");
-        }
-        const acf_hip_level& l = c->plan.levels[level];
-        const int pitch = rankPitch(l.hP);
-        int64_t off = 0;
-        for (int i = 0; i < level; i++)
-        {
-            off += int64_t(c->plan.nChns) * rankPitch(c->plan.levels[i].hP) * c->plan.levels[i].wP;
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy2D(host_out, size_t(l.hP) * 2, c->cs.d_pyrR + size_t(frame) * c->cs.pyrRCells + off, size_t(pitch) * 2, size_t(l.hP) * 2,
-            size_t(c->plan.nChns) * l.wP, hipMemcpyDeviceToHost));
-        return ACF_HIP_OK;
-    });
-}
-
-int acf_hip_rank_cells_host(const acf_hip_params* p, int nChns, int chn, const float* v, int n, uint16_t* cells_out, uint32_t* thr_index_out, int32_t* info)
-{
-    if (!p || !p->fids || !p->thrs || nChns <= 0 || chn < 0 || chn >= nChns || n < 0 || (n > 0 && !v) || p->treeDepth <= 0 || p->shrink <= 0)
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    const int mH = p->modelDsPad_h / p->shrink, mW = p->modelDsPad_w / p->shrink;
-    if (mH <= 0 || mW <= 0)
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    const size_t nNodes = size_t(p->nTrees) * p->nTreeNodes;
-    std::vector<int32_t> chnOfNode(nNodes, -1);
-    for (int t = 0; t < p->nTrees; t++)
-    {
-        for (int k = 0; k < (1 << p->treeDepth) - 1 && k < p->nTreeNodes; k++)
-        {
-            const size_t q = size_t(t) * p->nTreeNodes + k;
-            chnOfNode[q] = int32_t(p->fids[q] / uint32_t(mW * mH));
-        }
-    }
-    RankTables rt;
-    buildRankTables(p->thrs, chnOfNode.data(), nNodes, nChns, rt);
-    if (info)
-    {
-        info[0] = rt.ok ? 1 : 0;
-        info[1] = rt.ok ? rt.chan[size_t(chn)].shift : 0;
-        info[2] = rt.ok ? rt.chan[size_t(chn)].nb : 0;
-        info[3] = rt.ok ? rt.chan[size_t(chn)].nThr : 0;
-    }
-    if (!rt.ok)
-    {
-        return ACF_HIP_E_UNSUPPORTED;
-    }
-    for (int i = 0; i < n && cells_out; i++)
-    {
-        cells_out[i] = uint16_t(rt.rankOfCell(chn, v[i]));
-    }
-    for (size_t q = 0; q < nNodes && thr_index_out; q++)
-    {
-        thr_index_out[q] = chnOfNode[q] >= 0 ? rt.rankOfThreshold(chnOfNode[q], p->thrs[q]) : 0u;
-    }
-    return ACF_HIP_OK;
-}
-
-int acf_hip_read_tap(acf_hip_ctx* c, int frame, int tap, int index, float* host_out, int64_t cap)
-{
-    return onFrameOwner(c, frame, "read_tap: arguments", [&](acf_hip_ctx* c, int frame) -> int {
-        if (!c || !c->hasPlan)
-        {
-            return ACF_HIP_E_NOPLAN;
-        }
-        if (!c->pyramidValid || frame < 0 || frame >= c->lastBatch || !host_out)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "read_tap: arguments");
-        }
-        const Plan& pl = c->plan;
-        const float* src = nullptr;
-        int64_t n = 0;
-        if (tap == ACF_HIP_TAP_LDCF)
-        {
-            if (c->p.ldcfK <= 0 || !c->detectValid || index < 0 || index >= int(c->ldcf.levels.size()))
-            {
-                return fail(c, ACF_HIP_E_INVALID, "read_tap: LDCF levels exist after acf_hip_detect on a model with ldcfK > 0");
-            }
-            const acf_hip_level& l = c->ldcf.levels[size_t(index)];
-            n = int64_t(pl.nChns) * c->p.ldcfK * l.hP * l.wP;
-            src = c->ldcf.d_pyr + size_t(frame) * c->ldcf.floats + l.offset;
-        }
-        else if (tap == ACF_HIP_TAP_CHNS)
-        {
-            if (index < 0 || index >= int(pl.levels.size()))
-            {
-                return fail(c, ACF_HIP_E_INVALID, "read_tap: level");
-            }
-            const acf_hip_level& l = pl.levels[index];
-            n = int64_t(pl.nChns) * l.hC * l.wC;
-            src = c->d_chns + size_t(frame) * pl.raw_floats + pl.raw_off[index];
-        }
-        else
-        {
-            if (index < 0 || index >= int(c->real.size()))
-            {
-                return fail(c, ACF_HIP_E_INVALID, "read_tap: real-scale ordinal");
-            }
-            const RealScale& rs = c->real[index];
-            const int64_t np = int64_t(rs.h) * rs.w;
-            if (pl.d_in == 5 && index == 0 && (tap == ACF_HIP_TAP_M || tap == ACF_HIP_TAP_O || tap == ACF_HIP_TAP_S || tap == ACF_HIP_TAP_MNORM))
-            {
-                // chnsCompute.cpp:265-269: M and O came with the frame; nothing was computed here, and the reference logs none of them
-                return fail(c, ACF_HIP_E_INVALID, "read_tap: M, O, S and Mnorm of the first real scale came with the five-plane frame (none computed)");
-            }
-            switch (tap)
-            {
-                case ACF_HIP_TAP_IMAGE:
-                    n = np * pl.d;
-                    if (rs.resampled)
-                    {
-                        src = rs.img + size_t(frame) * n;
-                    }
-                    else if (c->d_color)
-                    {
-                        src = c->d_color + size_t(frame) * n;
-                    }
-                    else
-                    {
-                        src = c->lastFrames + size_t(frame) * pl.d_in * np; // (the caller's frames: d_in planes a frame, M and O behind the image's)
-                    }
-                    break;
-                case ACF_HIP_TAP_SMOOTHED:
-                    n = np * pl.d;
-                    src = rs.sm + size_t(frame) * n;
-                    break;
-                case ACF_HIP_TAP_M:
-                    n = np;
-                    src = rs.M ? rs.M + size_t(frame) * n : nullptr;
-                    break;
-                case ACF_HIP_TAP_O:
-                    n = np;
-                    src = rs.O ? rs.O + size_t(frame) * n : nullptr;
-                    break;
-                case ACF_HIP_TAP_S:
-                    n = np;
-                    src = rs.S ? rs.S + size_t(frame) * n : nullptr;
-                    break;
-                case ACF_HIP_TAP_MNORM:
-                    n = np;
-                    src = rs.Mn ? rs.Mn + size_t(frame) * n : nullptr;
-                    break;
-                default:
-                    return fail(c, ACF_HIP_E_INVALID, "read_tap: unknown tap");
-            }
-            if (!src)
-            {
-                return fail(c, ACF_HIP_E_INVALID, "read_tap: tap not kept (set option \"taps\" before acf_hip_plan)");
-            }
-        }
-        if (cap < n)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "read_tap: capacity");
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(host_out, src, sizeof(float) * n, hipMemcpyDeviceToHost));
-        return ACF_HIP_OK;
-    });
-}
-
-/* ---- single operators on host planes ---------------------------------- */
-
-
-#define OP_PROLOGUE(c)                      \
-    if (!(c))                               \
-    {                                       \
-        return ACF_HIP_E_INVALID;           \
-    }                                       \
-    HIPCHK(c, hipSetDevice((c)->device));   \
-    {                                       \
-        int rc0_ = ensureConstTables(c);    \
-        if (rc0_)                           \
-        {                                   \
-            return rc0_;                    \
-        }                                   \
-    }
-
-int acf_hip_op_rgb_convert(acf_hip_ctx* c, const float* in, float* out, int h, int w, int flag)
-{
-    OP_PROLOGUE(c);
-    if (!in || !out || h <= 0 || w <= 0)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "op_rgb_convert: arguments");
-    }
-    const int n = h * w;
-    Scratch s;
-    float* di = s.upload(in, size_t(3) * n);
-    const int dOut = flag == ACF_HIP_CS_GRAY ? 1 : 3;
-    float* dout = s.alloc<float>(size_t(dOut) * n);
-    if (!di || !dout)
-    {
-        return fail(c, ACF_HIP_E_HIP, "op_rgb_convert: allocation");
-    }
-    if (flag != ACF_HIP_CS_LUV && flag != ACF_HIP_CS_GRAY && flag != ACF_HIP_CS_HSV)
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "op_rgb_convert: flag");
-    }
-    launchColour(c, di, dout, n, 1, 0, 0, flag, 3);
-    LAUNCHCHK(c, "op_rgb_convert");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, dout, sizeof(float) * dOut * n, hipMemcpyDeviceToHost));
-    return ACF_HIP_OK;
-}
-
-namespace
-{
-// convTri with a radius <= 1 (k_smooth_tri1) of the d planes of ONE h x w frame, tight, through a one-job SmoothJob; `who` prefixes the
-// error texts
-int smoothOne(acf_hip_ctx* c, Scratch& s, const char* who, const float* in, float* out, int h, int w, int d, int64_t fs, float p, bool aliased)
-{
-    SmoothJob j{};
-    j.h = h;
-    j.w = w;
-    j.nplanes = d;
-    j.out_cs = h;
-    j.in_ps = int64_t(h) * w;
-    j.out_ps = int64_t(h) * w;
-    SmoothJob* dj = s.upload(&j, 1);
-    if (!dj)
-    {
-        return fail(c, ACF_HIP_E_HIP, std::string(who) + ": allocation");
-    }
-    return launchSmooth(c, in, out, dj, 1, d, h, fs, fs, 1, p, aliased);
-}
-
-// gradMag of ONE h x w plane I into M and O (k_grad_mag_strip), then convTri(M, normRad) into S through U when normRad > 0; `who`
-// prefixes the launch's error text, normRadErr is the text for a normRad the plane is too small for
-int gradMagOne(acf_hip_ctx* c, const char* who, const char* normRadErr, const float* I, float* M, float* O, float* U, float* S, int h, int w, int full,
-    int normRad)
-{
-    hipLaunchKernelGGL(k_grad_mag_strip, dim3(cdiv(h, GM_ROWS), 1, 1), dim3(GM_ROWS), 0, c->stream, I, M, O, (const float*)c->d_acos, h, w, full, int64_t(0),
-        int64_t(0), cdiv(w, GM_XT), x86T(c));
-    LAUNCHCHK(c, std::string(who) + ": k_grad_mag");
-    if (!normRad)
-    {
-        return ACF_HIP_OK;
-    }
-    if (std::min(h, w) < 4 || 2 * normRad + 1 >= std::min(h, w) || normRad < 2)
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, normRadErr);
-    }
-    return launchTri(c, M, U, S, h, w, normRad, int64_t(h) * w, 1);
-}
-} // namespace
-
-int acf_hip_op_conv_tri(acf_hip_ctx* c, const float* in, float* out, int h, int w, int d, double r, int aliased)
-{
-    OP_PROLOGUE(c);
-    if (!in || !out || h <= 0 || w <= 0 || d <= 0)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "op_conv_tri: arguments");
-    }
-    const int m = std::min(h, w);
-    if (m < 4 || (2 * r + 1) >= m)
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "op_conv_tri: plane too small (sepFilter2D fallback, convTri.cpp:224-251)");
-    }
-    const int64_t np = int64_t(h) * w;
-    Scratch s;
-    float* di = s.upload(in, size_t(np) * d);
-    float* dout = s.alloc<float>(size_t(np) * d);
-    if (!di || !dout)
-    {
-        return fail(c, ACF_HIP_E_HIP, "op_conv_tri: allocation");
-    }
-    int rc;
-    if (r > 0 && r <= 1.0)
-    {
-        if ((rc = smoothOne(c, s, "op_conv_tri", di, dout, h, w, d, 0, float(12.0 / r / (r + 2.0) - 2.0), aliased != 0)))
-        {
-            return rc;
-        }
-    }
-    else if (r > 1)
-    {
-        const int ri = int(std::round(float(r)));
-        if (ri >= m / 2)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "op_conv_tri: mask larger than image (convTri.cpp:166-169)");
-        }
-        float* dU = s.alloc<float>(size_t(np) * d);
-        if (!dU)
-        {
-            return fail(c, ACF_HIP_E_HIP, "op_conv_tri: allocation");
-        }
-        if ((rc = launchTri(c, di, dU, dout, h, w, ri, np, d)))
-        {
-            return rc;
-        }
-    }
-    else
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "op_conv_tri: radius");
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, dout, sizeof(float) * np * d, hipMemcpyDeviceToHost));
-    return ACF_HIP_OK;
-}
-
-// the device's table functions on the host (kernels.hip.h: x86_rcp_bits), for the composed table of gm_inv_x86g
-static uint32_t hostX86RcpBits(uint32_t u, const uint32_t* rcp4096)
-{
-    const uint32_t s = u & 0x80000000u, e = (u >> 23) & 0xffu, m = u & 0x7fffffu;
-    if (e == 0xffu)
-    {
-        return m ? (u | 0x400000u) : s;
-    }
-    if (e == 0)
-    {
-        return s | 0x7f800000u;
-    }
-    const uint32_t t = rcp4096[m >> 11];
-    const int re = int((t >> 23) & 0xffu) + 127 - int(e);
-    return re <= 0 ? s : (s | (uint32_t(re) << 23) | (t & 0x7fffffu));
-}
-
-int acf_hip_set_x86_tables(acf_hip_ctx* c, const uint32_t* rcp4096, const uint32_t* rsqrt8192)
-{
-    OP_PROLOGUE(c);
-    if (!rcp4096 || !rsqrt8192)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "set_x86_tables: null table");
-    }
-    dropGraph(c);
-    if (!c->d_x86)
-    {
-        // (not one of the plan's buffers: it outlives a re-plan; freed by acf_hip_destroy)
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->d_x86), X86_BUF_N * sizeof(uint32_t)));
-        c->x86Owned = true;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // (a run in flight may be reading the previous tables)
-    // [rcp 4096][rsqrt 8192][gradMag's pairs {RSQ[i], rcp(RSQ[i])} x 8192][rcp(1e10)] (kernels_channels.hip.h: gm_inv_x86g)
-    std::vector<uint32_t> buf(X86_BUF_N, 0u);
-    memcpy(buf.data(), rcp4096, 4096 * sizeof(uint32_t));
-    memcpy(buf.data() + 4096, rsqrt8192, 8192 * sizeof(uint32_t));
-    for (int i = 0; i < X86_GM_N; i++)
-    {
-        buf[size_t(X86_TABLE_N) + 2 * size_t(i)] = rsqrt8192[i];
-        buf[size_t(X86_TABLE_N) + 2 * size_t(i) + 1] = hostX86RcpBits(rsqrt8192[i], rcp4096);
-    }
-    {
-        const float big = 1e10f;
-        uint32_t bb;
-        memcpy(&bb, &big, 4);
-        buf[size_t(X86_TABLE_N) + 2 * size_t(X86_GM_N)] = hostX86RcpBits(bb, rcp4096);
-    }
-    HIPCHK(c, hipMemcpy(c->d_x86, buf.data(), buf.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    for (acf_hip_ctx* k : c->kids)
-    {
-        k->d_x86 = c->d_x86;
-    }
-    return ACF_HIP_OK;
-}
-
-int acf_hip_selftest_x86(acf_hip_ctx* c, uint32_t first_bits, uint64_t count, uint32_t stride, uint64_t digest[3])
-{
-    OP_PROLOGUE(c);
-    if (!digest || !c->d_x86)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "selftest_x86: install tables first (acf_hip_set_x86_tables)");
-    }
-    Scratch s;
-    unsigned long long* d = s.alloc<unsigned long long>(3);
-    if (!d)
-    {
-        return fail(c, ACF_HIP_E_HIP, "selftest_x86: allocation");
-    }
-    HIPCHK(c, hipMemset(d, 0, 3 * sizeof(unsigned long long)));
-    hipLaunchKernelGGL(k_x86_digest, dim3(4096), dim3(256), 0, c->stream, (const uint32_t*)c->d_x86, first_bits, (unsigned long long)count, stride, d);
-    LAUNCHCHK(c, "k_x86_digest");
-    // ... and gradMag's one-read form against the two table functions over the same patterns (negative non-NaN ones skipped)
-    hipLaunchKernelGGL(k_gm_x86_selftest, dim3(4096), dim3(256), 0, c->stream, (const uint32_t*)c->d_x86, first_bits, (unsigned long long)count, stride, d + 2);
-    LAUNCHCHK(c, "k_gm_x86_selftest");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    unsigned long long out[3];
-    HIPCHK(c, hipMemcpy(out, d, sizeof(out), hipMemcpyDeviceToHost));
-    digest[0] = out[0];
-    digest[1] = out[1];
-    digest[2] = out[2];
-    return ACF_HIP_OK;
-}
-
-int acf_hip_selftest_gradmag(acf_hip_ctx* c, uint32_t first_bits, uint32_t last_bits, uint64_t* mismatches, uint32_t* first_bad_bits)
-{
-    OP_PROLOGUE(c);
-    if (!mismatches || last_bits < first_bits)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "selftest_gradmag: arguments");
-    }
-    Scratch s;
-    unsigned long long* d = s.alloc<unsigned long long>(2);
-    if (!d)
-    {
-        return fail(c, ACF_HIP_E_HIP, "selftest_gradmag: allocation");
-    }
-    const unsigned long long init[2] = { 0ull, ~0ull };
-    HIPCHK(c, hipMemcpy(d, init, sizeof(init), hipMemcpyHostToDevice));
-    const unsigned long long count = (unsigned long long)(last_bits - first_bits) + 1ull;
-    hipLaunchKernelGGL(k_gm_inv_selftest, dim3(4096), dim3(256), 0, c->stream, first_bits, count, d);
-    LAUNCHCHK(c, "k_gm_inv_selftest");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    unsigned long long out[2];
-    HIPCHK(c, hipMemcpy(out, d, sizeof(out), hipMemcpyDeviceToHost));
-    *mismatches = out[0];
-    if (first_bad_bits)
-    {
-        *first_bad_bits = uint32_t(out[1]);
-    }
-    return ACF_HIP_OK;
-}
-
-int acf_hip_op_gradient_mag(acf_hip_ctx* c, const float* in, float* M, float* O, float* S_out, int h, int w, int normRad, double normConst, int full)
-{
-    OP_PROLOGUE(c);
-    if (!in || !M || !O || h < 2 || w < 2)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "op_gradient_mag: arguments");
-    }
-    const int64_t np = int64_t(h) * w;
-    Scratch s;
-    float* di = s.upload(in, size_t(np));
-    float *dM = s.alloc<float>(np), *dO = s.alloc<float>(np), *dU = s.alloc<float>(np), *dS = s.alloc<float>(np);
-    if (!di || !dM || !dO || !dU || !dS)
-    {
-        return fail(c, ACF_HIP_E_HIP, "op_gradient_mag: allocation");
-    }
-    if (int rc = gradMagOne(c, "op_gradient_mag", "op_gradient_mag: normRad", di, dM, dO, dU, dS, h, w, full, normRad))
-    {
-        return rc;
-    }
-    if (normRad)
-    {
-        hipLaunchKernelGGL(k_norm, dim3(cdiv(np, 256)), dim3(256), 0, c->stream, dM, (const float*)dS, int(np), float(normConst), x86T(c));
-        LAUNCHCHK(c, "k_norm");
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(M, dM, sizeof(float) * np, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(O, dO, sizeof(float) * np, hipMemcpyDeviceToHost));
-    if (S_out && normRad)
-    {
-        HIPCHK(c, hipMemcpy(S_out, dS, sizeof(float) * np, hipMemcpyDeviceToHost));
-    }
-    return ACF_HIP_OK;
-}
-
-// Detector::chnsCompute (ACF.h:342-349, chnsCompute.cpp:146-338): the channels of ONE image at its own scale, no pyramid plan.
-int acf_hip_chns_compute(acf_hip_ctx* c, const acf_hip_params* pIn, const float* in, int h, int w, int d, float* out, int64_t cap, int* nChnsOut, int* hCOut,
-    int* wCOut)
-{
-    OP_PROLOGUE(c);
-    const acf_hip_params* pp = pIn ? pIn : (c->hasModel ? &c->p : nullptr);
-    if (!pp)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "chns_compute: no parameters (pass them, or set a model first)");
-    }
-    acf_hip_params p = *pp;
-    if (!in || h <= 0 || w <= 0 || (d != 1 && d != 3 && d != 5)) // (5: the image's own M, O planes behind three image planes, chnsCompute.cpp:219-226)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "chns_compute: arguments");
-    }
-    {
-        std::string err;
-        const int rcc = checkChnsParams(p, d, err); // (the checks acf_hip_plan makes on the same fields)
-        if (rcc)
-        {
-            return fail(c, rcc, "chns_compute: " + err);
-        }
-    }
-    if (p.nOrients < 1 || p.nOrients > 12)
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "chns_compute: nOrients must be 1..12");
-    }
-    if (d == 1 && p.colorChn != 0)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "chns_compute: colorChn of a 1-plane image must be 0 (gradientMag reads I[colorChn], chnsCompute.cpp:278-282)");
-    }
-    const int shrink = p.shrink;
-    const int hc = h - h % shrink, wc = w - w % shrink; // crop so divisible by shrink (chnsCompute.cpp:203-217)
-    // a 1-plane image is its own colour plane for gray and orig alike (rgbConvert.cpp:129-148); replicating it is chnsPyramid's rule only
-    // (chnsPyramid.cpp:234-244)
-    const int dcol = d == 1 ? 1 : colorPlanes(p), nC = numChannels(p, dcol);
-    const int hs = hc / shrink, ws = wc / shrink;
-    if (nChnsOut)
-    {
-        *nChnsOut = nC;
-    }
-    if (hCOut)
-    {
-        *hCOut = hs;
-    }
-    if (wCOut)
-    {
-        *wCOut = ws;
-    }
-    if (!out)
-    {
-        return ACF_HIP_OK; // (a size query)
-    }
-    if (hc < 2 || wc < 2 || hs < 1 || ws < 1)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "chns_compute: image smaller than a cell");
-    }
-    if (cap < int64_t(nC) * hs * ws)
-    {
-        return fail(c, ACF_HIP_E_CAPACITY, "chns_compute: output buffer too small");
-    }
-    const int64_t np = int64_t(hc) * wc;
-    Scratch s;
-    // the cropped planes, tight: [d][wc][hc]
-    std::vector<float> crop;
-    const float* src = in;
-    if (hc != h || wc != w)
-    {
-        crop.resize(size_t(d) * np);
-        for (int z = 0; z < d; z++)
-        {
-            for (int x = 0; x < wc; x++)
-            {
-                memcpy(&crop[(size_t(z) * wc + x) * hc], in + (size_t(z) * w + x) * h, sizeof(float) * hc);
-            }
-        }
-        src = crop.data();
-    }
-    float* dI = s.upload(src, size_t(d) * np);
-    float* dCol = s.alloc<float>(size_t(dcol) * np);
-    float *dM = s.alloc<float>(np), *dO = s.alloc<float>(np), *dU = s.alloc<float>(np), *dS = s.alloc<float>(np);
-    float* dOut = s.alloc<float>(size_t(nC) * hs * ws);
-    if (!dI || !dCol || !dM || !dO || !dU || !dS || !dOut)
-    {
-        return fail(c, ACF_HIP_E_HIP, "chns_compute: allocation");
-    }
-    // rgbConvert(I, I, colorSpace, true, isLuv) (chnsCompute.cpp:235; rgbConvert.cpp:101-170)
-    if (d == 1 || colourPassthrough(p, d))
-    {
-        HIPCHK(c, hipMemcpyAsync(dCol, dI, sizeof(float) * dcol * np, hipMemcpyDeviceToDevice, c->stream));
-    }
-    else
-    {
-        launchColour(c, dI, dCol, np, 1, 0, 0, p.colorSpace, d);
-        LAUNCHCHK(c, "chns_compute: colour conversion");
-    }
-    // convTri(I, I, pColor.smooth, 1) in place (chnsCompute.cpp:239)
-    if (p.colorSmooth > 0)
-    {
-        if (p.colorSmooth > 1)
-        {
-            return fail(c, ACF_HIP_E_UNSUPPORTED, "chns_compute: pColor.smooth > 1 (convTri with a radius) is not built for the colour planes");
-        }
-        const float pColor = float(12.0 / p.colorSmooth / (p.colorSmooth + 2.0) - 2.0);
-        if (int rc = smoothOne(c, s, "chns_compute", dCol, dCol, hc, wc, dcol, int64_t(dcol) * np, pColor, true))
-        {
-            return rc;
-        }
-    }
-    ChnsArgs a{};
-    a.sm = dCol;
-    a.M = dM;
-    a.S = dS;
-    a.O = dO;
-    a.chns = dOut;
-    a.sm_fs = int64_t(dcol) * np;
-    a.m_fs = np;
-    a.chns_fs = int64_t(nC) * hs * ws;
-    a.h = hc;
-    a.w = wc;
-    a.d = dcol;
-    a.colorEnabled = p.colorEnabled;
-    a.magEnabled = p.gradMagEnabled;
-    a.histEnabled = p.gradHistEnabled;
-    a.nOrients = p.nOrients;
-    a.doNorm = p.normRad != 0;
-    a.full = p.full;
-    a.hardBin = p.softBin < 0;
-    a.normConst = float(p.normConst);
-    a.rq_y = shrinkGainY(shrink);
-    a.x86 = x86T(c);
-    if (d == 5)
-    {
-        // M = MO[0], O = MO[1] (chnsCompute.cpp:265-269): no gradientMag, no normalisation
-        a.M = dI + 3 * np;
-        a.O = dI + 4 * np;
-        a.doNorm = 0;
-    }
-    else if (p.gradMagEnabled || p.gradHistEnabled)
-    {
-        if (int rc = gradMagOne(c, "chns_compute", "chns_compute: normRad against the image size", dCol + int64_t(p.colorChn) * np, dM, dO, dU, dS, hc, wc,
-                p.full, p.normRad))
-        {
-            return rc;
-        }
-    }
-    int rc = launchChns(c, a, shrink, 1);
-    if (rc)
-    {
-        return rc;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, dOut, sizeof(float) * size_t(nC) * hs * ws, hipMemcpyDeviceToHost));
-    return ACF_HIP_OK;
-}
-
-int acf_hip_op_gradient_hist(acf_hip_ctx* c, const float* M, const float* O, float* H, int h, int w, int bin, int nOrients, int softBin, int full)
-{
-    OP_PROLOGUE(c);
-    if (!M || !O || !H || h <= 0 || w <= 0 || nOrients < 1 || nOrients > 12)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "op_gradient_hist: arguments");
-    }
-    if (softBin % 2 != 0)
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "op_gradient_hist: odd softBin (trilinear spatial binning) is not built");
-    }
-    if ((bin != 2 && bin != 4) || h % bin || w % bin)
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "op_gradient_hist: bin must be 2 or 4 and divide h, w");
-    }
-    const int64_t np = int64_t(h) * w, nc = np / (bin * bin);
-    Scratch s;
-    float *dM = s.upload(M, np), *dO = s.upload(O, np), *dH = s.alloc<float>(nc * nOrients);
-    if (!dM || !dO || !dH)
-    {
-        return fail(c, ACF_HIP_E_HIP, "op_gradient_hist: allocation");
-    }
-    ChnsArgs a{};
-    a.M = dM;
-    a.S = dM;
-    a.O = dO;
-    a.chns = dH;
-    a.h = h;
-    a.w = w;
-    a.d = 0;
-    a.histEnabled = 1;
-    a.nOrients = nOrients;
-    a.full = full;
-    a.hardBin = softBin < 0;
-    a.rq_y = shrinkGainY(bin);
-    int rc = launchChns(c, a, bin, 1);
-    if (rc)
-    {
-        return rc;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(H, dH, sizeof(float) * nc * nOrients, hipMemcpyDeviceToHost));
-    return ACF_HIP_OK;
-}
-
-int acf_hip_op_im_resample(acf_hip_ctx* c, const float* in, float* out, int ha, int wa, int hb, int wb, int d, double nrm)
-{
-    OP_PROLOGUE(c);
-    if (!in || !out || ha <= 0 || wa <= 0 || hb <= 0 || wb <= 0 || d <= 0)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "op_im_resample: arguments");
-    }
-    TableArena arena;
-    ResampleDesc dd;
-    int rc = buildResample(ha, wa, hb, wb, dd, arena);
-    if (rc)
-    {
-        return fail(c, rc, "op_im_resample: degenerate geometry");
-    }
-    const double ratio[3] = { nrm, nrm, nrm };
-    setResampleGain(dd, ratio, d, d);
-    dd.nplanes = d;
-    Scratch s;
-    float* di = s.upload(in, size_t(d) * ha * wa);
-    float* dout = s.alloc<float>(size_t(d) * hb * wb);
-    dd.src_frame_stride = int64_t(d) * ha * wa;
-    dd.dst_frame_stride = int64_t(d) * hb * wb;
-    const StripPlan sp = stripPlan(dd, nullptr, arena); // appends its tile ranges to the int arena
-    ResampleDesc* ddesc = s.upload(&dd, 1);
-    int32_t* dit = s.upload(arena.ints.data(), arena.ints.size());
-    float* dft = s.upload(arena.floats.data(), arena.floats.size());
-    if (!di || !dout || !ddesc || !dit || !dft)
-    {
-        return fail(c, ACF_HIP_E_HIP, "op_im_resample: allocation");
-    }
-    if (sp.ok && !resampleGenericOnly() && (rc = ensureConstTables(c)) == 0)
-    {
-        // the strip march the pyramid uses for its down-sampled real scales
-        launchStrip(c, sp, ddesc, 0, -1, d, di, dout, nullptr, dit, dft, 1);
-    }
-    else if (resampleUpOk(dd) && !resampleGenericOnly())
-    {
-        hipLaunchKernelGGL(k_resample_up, dim3(cdiv(d * cdiv(hb, 256) * cdiv(wb, RSU_XC), 4), 1, 1), dim3(256), 0, c->stream, (const float*)di, dout,
-            (const ResampleDesc*)ddesc, (const int32_t*)dit, (const float*)dft);
-    }
-    else
-    {
-        hipLaunchKernelGGL(k_resample, dim3(resampleBlocks(dd), 1, 1), dim3(64, 4), 0, c->stream, (const float*)di, dout,
-            (const ResampleDesc*)ddesc, (const int32_t*)dit, (const float*)dft, RS_XT);
-    }
-    LAUNCHCHK(c, "k_resample");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, dout, sizeof(float) * d * hb * wb, hipMemcpyDeviceToHost));
-    return ACF_HIP_OK;
-}
-
-// thrs.convertTo(thrsU8, CV_8UC1, 255.0f) (ACFIOArchive.h:96-99): OpenCV's 32f->8u cvtScale works in f32 and rounds
-// with cvRound (to nearest even), then saturates.
-int acf_hip_thrs_u8(const float* thrs, int n, uint8_t* out)
-{
-    if (!thrs || !out || n < 0)
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    for (int i = 0; i < n; i++)
-    {
-        const float v = thrs[i] * 255.0f;
-        // cvRound is cvtss2si: half to even; NaN and |v| >= 2^31 convert to INT_MIN, which saturate_cast<uchar> maps to 0
-        const bool inRange = v > -2147483648.0f && v < 2147483648.0f;
-        const float r = inRange ? std::nearbyint(v) : -1.0f;
-        out[i] = uint8_t(r < 0.f ? 0 : (r > 255.f ? 255 : int(r)));
-    }
-    return ACF_HIP_OK;
-}
-
-static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::vector<float>* thrs, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count);
-
-int acf_hip_op_acf_detect1(acf_hip_ctx* c, const float* chns, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count)
-{
-    return opAcfDetect1(c, chns, false, nullptr, hP, wP, nChns, out, cap, count);
-}
-
-// The uint8_t body of acfDetect1 (acfDetect1.cpp:157-166,187-192): features and thresholds are bytes, compared after
-// promotion to float (`float ftr = chns1[...]; ftr < thrs[k]`).  Bytes widen to f32 exactly, so the planes are widened
-// on the device and the f32 cascade runs on them with the widened thresholds: same comparisons, same sums.
-int acf_hip_op_acf_detect1_u8(acf_hip_ctx* c, const uint8_t* chns, int hP, int wP, int nChns, const uint8_t* thrsU8, acf_hip_hit* out, int cap, int* count)
-{
-    if (!c || !c->hasModel)
-    {
-        return c ? fail(c, ACF_HIP_E_NOMODEL, "op_acf_detect1_u8: set_model first") : ACF_HIP_E_INVALID;
-    }
-    std::vector<uint8_t> derived;
-    if (!thrsU8)
-    {
-        derived.resize(c->thrs.size());
-        acf_hip_thrs_u8(c->thrs.data(), int(c->thrs.size()), derived.data());
-        thrsU8 = derived.data();
-    }
-    std::vector<float> wide(c->thrs.size());
-    for (size_t i = 0; i < wide.size(); i++)
-    {
-        wide[i] = float(thrsU8[i]);
-    }
-    return opAcfDetect1(c, chns, true, &wide, hP, wP, nChns, out, cap, count);
-}
-
-// acfDetect1 on one caller's channel buffer: a cascade state of its own (one level, one frame, cap hits), built, run and freed
-// here.  The plan's state, its batch and its resident results are not touched.  thrs == nullptr: the model's thresholds.
-static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::vector<float>* thrs, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count)
-{
-    OP_PROLOGUE(c);
-    if (!c->hasModel)
-    {
-        return fail(c, ACF_HIP_E_NOMODEL, "op_acf_detect1: set_model first");
-    }
-    if (!chns || hP <= 0 || wP <= 0 || nChns <= 0 || cap <= 0 || !count)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "op_acf_detect1: arguments");
-    }
-    const acf_hip_params& p = c->p;
-    std::vector<acf_hip_level> lv(1);
-    lv[0] = acf_hip_level{};
-    lv[0].scale = 1.0;
-    lv[0].scalehw_h = lv[0].scalehw_w = 1.0;
-    lv[0].hP = lv[0].hC = hP;
-    lv[0].wP = lv[0].wC = wP;
-    lv[0].nWinR = std::max(0, int(std::ceil(float(hP * p.shrink - p.modelDsPad_h + 1) / p.stride)));
-    lv[0].nWinC = std::max(0, int(std::ceil(float(wP * p.shrink - p.modelDsPad_w + 1) / p.stride)));
-    lv[0].offset = 0;
-    std::vector<BoxLevel> box(1);
-    box[0].shw_h = box[0].shw_w = 1.0;
-    box[0].bw = p.modelDs_w;
-    box[0].bh = p.modelDs_h;
-    // the temporary buffers are in the context's allocation list for the duration of this call only
-    struct Temporaries
-    {
-        acf_hip_ctx* c;
-        size_t mark;
-        ~Temporaries()
-        {
-            for (size_t i = mark; i < c->allocs.size(); i++)
-            {
-                (void)hipFree(c->allocs[i]);
-            }
-            c->allocs.resize(mark);
-        }
-    } temporaries{ c, c->allocs.size() };
-    const std::vector<float>& th = thrs ? *thrs : c->thrs;
-    const size_t n = size_t(nChns) * hP * wP;
-    CascState cs;
-    BoxLevel* dBox = nullptr;
-    float* dChn = nullptr;
-    uint8_t* dBytes = nullptr;
-    int rc;
-    if ((rc = buildCascadeTables(c, lv, nChns, p.shrink, 1, th, cs)) || (rc = allocCascadeRun(c, cs, lv, th, cap)) || (rc = devUpload(c, &dBox, box)) ||
-        (rc = devAlloc(c, &dChn, n + 64)) || (u8 && (rc = devAlloc(c, &dBytes, n))))
-    {
-        return rc;
-    }
-    if (hipMemcpy(u8 ? static_cast<void*>(dBytes) : dChn, chns, n * (u8 ? 1 : sizeof(float)), hipMemcpyHostToDevice) != hipSuccess)
-    {
-        return fail(c, ACF_HIP_E_HIP, u8 ? "op_acf_detect1_u8: upload" : "op_acf_detect1: upload");
-    }
-    if (u8)
-    {
-        hipLaunchKernelGGL(k_widen_u8, dim3(cdiv(int64_t(n), 256)), dim3(256), 0, c->stream, (const uint8_t*)dBytes, dChn, int64_t(n));
-        if (hipGetLastError() != hipSuccess)
-        {
-            return fail(c, ACF_HIP_E_HIP, "launch k_widen_u8");
-        }
-    }
-    if ((rc = runCascade(c, cs, { dChn, 0, 1, nChns }, dBox)))
-    {
-        return rc;
-    }
-    prof(c, "(end)");
-    int nHits = 0;
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&nHits, cs.d_counts, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-    {
-        return fail(c, ACF_HIP_E_HIP, "op_acf_detect1: sync");
-    }
-    *count = nHits;
-    const int m = std::min(nHits, cap);
-    if (m > 0 && out && hipMemcpy(out, cs.d_sorted, sizeof(acf_hip_hit) * m, hipMemcpyDeviceToHost) != hipSuccess)
-    {
-        return fail(c, ACF_HIP_E_HIP, "op_acf_detect1: download");
-    }
-    return nHits > cap ? fail(c, ACF_HIP_E_CAPACITY, "op_acf_detect1: more hits than cap") : ACF_HIP_OK;
-}
-
-int acf_hip_op_evaluate(acf_hip_ctx* c, const float* chns, int hP, int wP, int nChns, double cascThr, float* score)
-{
-    OP_PROLOGUE(c);
-    if (!c->hasModel)
-    {
-        return fail(c, ACF_HIP_E_NOMODEL, "op_evaluate: set_model first");
-    }
-    const acf_hip_params& p = c->p;
-    const int mH = p.modelDsPad_h / p.shrink, mW = p.modelDsPad_w / p.shrink;
-    if (!chns || !score || nChns <= 0 || hP < mH || wP < mW)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "op_evaluate: the buffer must hold at least one window");
-    }
-    Scratch s;
-    const size_t n = size_t(nChns) * hP * wP;
-    float* dC = s.upload(chns, n);
-    uint32_t* dF = s.upload(c->fids.data(), c->fids.size());
-    float* dT = s.upload(c->thrs.data(), c->thrs.size());
-    float* dH = s.upload(c->hs.data(), c->hs.size());
-    uint32_t* dCh = c->child.empty() ? nullptr : s.upload(c->child.data(), c->child.size());
-    float* dS = s.alloc<float>(1);
-    if (!dC || !dF || !dT || !dH || !dS || (p.treeDepth == 0 && !dCh))
-    {
-        return fail(c, ACF_HIP_E_HIP, "op_evaluate: allocation");
-    }
-    hipLaunchKernelGGL(k_evaluate_window, dim3(1), dim3(64), 0, c->stream, (const float*)dC, hP, wP, mH, mW, (const uint32_t*)dF, (const float*)dT,
-        (const float*)dH, (const uint32_t*)dCh, p.nTrees, p.nTreeNodes, p.treeDepth, float(cascThr), dS);
-    LAUNCHCHK(c, "k_evaluate_window");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(score, dS, sizeof(float), hipMemcpyDeviceToHost));
-    return ACF_HIP_OK;
-}
+#include "ops.hip.h"      // the single-operator entries (acf_hip_op_*, acf_hip_chns_compute), the x86 tables and the self-tests
 
 } // extern "C"

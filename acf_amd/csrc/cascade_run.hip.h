@@ -14,15 +14,6 @@
 // the counters already.
 #pragma once
 
-static int allowLds(acf_hip_ctx* c, const void* kernel, size_t bytes)
-{
-    if (bytes > 64 * 1024)
-    {
-        HIPCHK(c, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)));
-    }
-    return ACF_HIP_OK;
-}
-
 extern "C++" // (this file is included inside acf_hip.hip's extern "C" block)
 {
 // allowLds + the launch of a kernel that takes its arguments as one struct

@@ -1020,10 +1020,7 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
         }
         return rc;
     }
-    if (!c || !c->hasPlan)
-    {
-        return c ? fail(c, ACF_HIP_E_NOPLAN, "pyramid: plan first") : ACF_HIP_E_INVALID;
-    }
+    if (int rc = needPlan(c, "pyramid")) return rc;
     if ((!frames && !u8) || (u8 && !u8->frames) || nF <= 0 || nF > c->maxBatch)
     {
         return fail(c, ACF_HIP_E_INVALID, "pyramid: n_frames out of range");

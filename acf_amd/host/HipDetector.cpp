@@ -207,12 +207,17 @@ int HipDetector::acfModify(const Modify& params)
     return 0;
 }
 
-void HipDetector::ensurePlan(int imgH, int imgW, int d, int batch)
+void HipDetector::ensureContext(int device)
 {
-    if (!m_good)
+    if (!m_ctx)
     {
-        throw Exception(ACF_HIP_E_NOMODEL, "HipDetector: no model");
+        m_api = &hip::load();
+        check(m_api->acf_hip_create(device, nullptr, &m_ctx), "acf_hip_create");
     }
+}
+
+void HipDetector::ensureModel()
+{
     if (m_dirty)
     {
         acf_hip_params p;
@@ -221,6 +226,55 @@ void HipDetector::ensurePlan(int imgH, int imgW, int d, int batch)
         m_dirty = false;
         m_planH = 0;
     }
+}
+
+// channels of a level: the colour planes, the gradient magnitude, the orientation bins — each if enabled
+int HipDetector::numChannels() const
+{
+    const auto& ch = opts.pPyramid.pChns;
+    const int nColor = ch.pColor.enabled ? (ch.pColor.colorSpace == "gray" ? 1 : 3) : 0;
+    return nColor + (ch.pGradMag.enabled ? 1 : 0) + (ch.pGradHist.enabled ? ch.pGradHist.nOrients : 0);
+}
+
+// the logger's tag of a plane (HipDetector.h, MatLoggerType)
+std::string HipDetector::planeTag(const char* name, int cols, int rows)
+{
+    return std::string(name) + ":" + std::to_string(cols) + "x" + std::to_string(rows);
+}
+
+// the d colour planes of an H x W image ([W rows][H cols] each), one by one: "L", "U", "V", or "L" alone
+void HipDetector::logColourPlanes(const MatLoggerType& logger, MatP& planes, int d, int H, int W)
+{
+    static const char* luv[3] = { "L", "U", "V" };
+    for (int z = 0; z < d; z++)
+    {
+        MatP plane(W, H, 1, planes[z]);
+        logger(plane, planeTag(d == 3 ? luv[z] : "L", H, W));
+    }
+}
+
+// cv::hconcat of the nOrients histogram planes (chnsCompute.cpp:322-329): planes firstPlane... of src ([wC rows][hC cols] each)
+// side by side, [wC rows][nOrients * hC cols]
+MatP HipDetector::hconcatHist(const float* src, int firstPlane, int nOrients, int hC, int wC)
+{
+    MatP cat(wC, nOrients * hC, 1);
+    for (int b = 0; b < nOrients; b++)
+    {
+        for (int r = 0; r < wC; r++)
+        {
+            std::memcpy(cat.data() + (size_t(r) * nOrients + b) * hC, src + (size_t(firstPlane + b) * wC + r) * hC, sizeof(float) * hC);
+        }
+    }
+    return cat;
+}
+
+void HipDetector::ensurePlan(int imgH, int imgW, int d, int batch)
+{
+    if (!m_good)
+    {
+        throw Exception(ACF_HIP_E_NOMODEL, "HipDetector: no model");
+    }
+    ensureModel();
     if (imgH != m_planH || imgW != m_planW || d != m_planD || batch > m_planBatch)
     {
         check(m_api->acf_hip_plan(m_ctx, imgH, imgW, d, batch, 1 << 16), "acf_hip_plan");
@@ -746,10 +800,8 @@ int HipDetector::chnsPyramid(const MatP& I, const Options::Pyramid* pPyramid, Py
     {
         const auto& ch = opts.pPyramid.pChns;
         const int d = ch.pColor.colorSpace == "gray" ? 1 : 3;
-        const int nColor = ch.pColor.enabled ? d : 0;
         const int shrink = ch.shrink;
         int ordinal = 0;
-        auto tag = [](const char* name, int cols, int rows) { return std::string(name) + ":" + std::to_string(cols) + "x" + std::to_string(rows); };
         for (size_t i = 0; i < m_levels.size(); i++)
         {
             const acf_hip_level& l = m_levels[i];
@@ -760,37 +812,22 @@ int HipDetector::chnsPyramid(const MatP& I, const Options::Pyramid* pPyramid, Py
             const int h1 = l.hC * shrink, w1 = l.wC * shrink; // the real scale's image: planes are [w1 rows][h1 cols]
             MatP sm(w1, h1, d), one(w1, h1, 1);
             check(m_api->acf_hip_read_tap(m_ctx, 0, ACF_HIP_TAP_SMOOTHED, ordinal, sm.data(), int64_t(sm.numel())), "acf_hip_read_tap");
-            static const char* luv[3] = { "L", "U", "V" };
-            for (int z = 0; z < d; z++)
-            {
-                MatP plane(w1, h1, 1, sm[z]);
-                logger(plane, tag(d == 3 ? luv[z] : "L", h1, w1));
-            }
+            logColourPlanes(logger, sm, d, h1, w1);
             // (five planes: the first real scale's M and O came with the image; the reference logs none of them, chnsCompute.cpp:265-269)
             if ((ch.pGradMag.enabled || ch.pGradHist.enabled) && !(I.channels() == 5 && ordinal == 0))
             {
                 for (const auto& t : { std::make_pair(int(ACF_HIP_TAP_M), "M"), std::make_pair(int(ACF_HIP_TAP_MNORM), "Mnorm"), std::make_pair(int(ACF_HIP_TAP_O), "O") })
                 {
                     check(m_api->acf_hip_read_tap(m_ctx, 0, t.first, ordinal, one.data(), int64_t(one.numel())), "acf_hip_read_tap");
-                    logger(one, tag(t.second, h1, w1));
+                    logger(one, planeTag(t.second, h1, w1));
                 }
             }
             if (ch.pGradHist.enabled)
             {
-                // cv::hconcat of the nOrients histogram planes (chnsCompute.cpp:322-329): [wC rows][nOrients * hC cols]
-                const int nO = ch.pGradHist.nOrients;
+                const int nO = ch.pGradHist.nOrients; // (the bins are a level's last channels)
                 MatP raw(l.wC * m_nChns, l.hC, 1);
                 check(m_api->acf_hip_read_tap(m_ctx, 0, ACF_HIP_TAP_CHNS, int(i), raw.data(), int64_t(raw.numel())), "acf_hip_read_tap");
-                const int first = nColor + (ch.pGradMag.enabled ? 1 : 0);
-                MatP hc(l.wC, nO * l.hC, 1);
-                for (int b = 0; b < nO; b++)
-                {
-                    for (int r = 0; r < l.wC; r++)
-                    {
-                        std::memcpy(hc.data() + (size_t(r) * nO + b) * l.hC, raw.data() + (size_t(first + b) * l.wC + r) * l.hC, sizeof(float) * l.hC);
-                    }
-                }
-                logger(hc, tag("H", nO * l.hC, l.wC));
+                logger(hconcatHist(raw.data(), numChannels() - nO, nO, l.hC, l.wC), planeTag("H", nO * l.hC, l.wC));
             }
             ordinal++;
         }
@@ -914,17 +951,8 @@ void HipDetector::detect1(const float* f32, const uint8_t* u8, int rows, int col
     {
         throw Exception(ACF_HIP_E_NOMODEL, "acfDetect1: no model");
     }
-    if (m_dirty)
-    {
-        acf_hip_params p;
-        fillParams(p);
-        check(m_api->acf_hip_set_model(m_ctx, &p), "acf_hip_set_model");
-        m_dirty = false;
-        m_planH = 0;
-    }
-    const auto& ch = opts.pPyramid.pChns;
-    const int nColor = ch.pColor.enabled ? (ch.pColor.colorSpace == "gray" ? 1 : 3) : 0;
-    const int nC = nColor + (ch.pGradMag.enabled ? 1 : 0) + (ch.pGradHist.enabled ? ch.pGradHist.nOrients : 0);
+    ensureModel();
+    const int nC = numChannels();
     const int wP = rows / nC, hP = cols;
     const int cap = std::max(1, wP * hP);
     std::vector<acf_hip_hit> hits(static_cast<size_t>(cap));
@@ -959,17 +987,8 @@ float HipDetector::evaluate(const MatP& chns, int, const Size&, int)
     {
         throw Exception(ACF_HIP_E_NOMODEL, "evaluate: no model");
     }
-    if (m_dirty)
-    {
-        acf_hip_params p;
-        fillParams(p);
-        check(m_api->acf_hip_set_model(m_ctx, &p), "acf_hip_set_model");
-        m_dirty = false;
-        m_planH = 0;
-    }
-    const auto& ch = opts.pPyramid.pChns;
-    const int nColor = ch.pColor.enabled ? (ch.pColor.colorSpace == "gray" ? 1 : 3) : 0;
-    const int nC = nColor + (ch.pGradMag.enabled ? 1 : 0) + (ch.pGradHist.enabled ? ch.pGradHist.nOrients : 0);
+    ensureModel();
+    const int nC = numChannels();
     float score = 0.f;
     check(m_api->acf_hip_op_evaluate(m_ctx, chns.data(), chns.cols(), chns.rows() / nC, nC, 0.0, &score), "acf_hip_op_evaluate");
     return score;
@@ -998,11 +1017,7 @@ void HipDetector::getScales(int nPerOct, int nOctUp, const Size& minDs, int shri
 int HipDetector::rgbConvert(const MatP& I, MatP& J, const std::string& colorSpace)
 {
     const int flag = colorSpaceFlag(colorSpace);
-    if (!m_ctx)
-    {
-        m_api = &hip::load();
-        check(m_api->acf_hip_create(0, nullptr, &m_ctx), "acf_hip_create");
-    }
+    ensureContext();
     J.create(I.rows(), I.cols(), flag == ACF_HIP_CS_GRAY ? 1 : 3);
     check(m_api->acf_hip_op_rgb_convert(m_ctx, I.data(), J.data(), I.cols(), I.rows(), flag), "acf_hip_op_rgb_convert");
     return 0;
@@ -1010,11 +1025,7 @@ int HipDetector::rgbConvert(const MatP& I, MatP& J, const std::string& colorSpac
 
 int HipDetector::convTri(const MatP& I, MatP& J, double r, bool inPlaceSemantics)
 {
-    if (!m_ctx)
-    {
-        m_api = &hip::load();
-        check(m_api->acf_hip_create(0, nullptr, &m_ctx), "acf_hip_create");
-    }
+    ensureContext();
     J.create(I.rows(), I.cols(), I.channels());
     check(m_api->acf_hip_op_conv_tri(m_ctx, I.data(), J.data(), I.cols(), I.rows(), I.channels(), r, inPlaceSemantics ? 1 : 0), "acf_hip_op_conv_tri");
     return 0;
@@ -1022,11 +1033,7 @@ int HipDetector::convTri(const MatP& I, MatP& J, double r, bool inPlaceSemantics
 
 int HipDetector::gradientMag(const MatP& I, MatP& M, MatP& O, int normRad, double normConst, int full)
 {
-    if (!m_ctx)
-    {
-        m_api = &hip::load();
-        check(m_api->acf_hip_create(0, nullptr, &m_ctx), "acf_hip_create");
-    }
+    ensureContext();
     M.create(I.rows(), I.cols(), 1);
     O.create(I.rows(), I.cols(), 1);
     check(m_api->acf_hip_op_gradient_mag(m_ctx, I.data(), M.data(), O.data(), nullptr, I.cols(), I.rows(), normRad, normConst, full), "acf_hip_op_gradient_mag");
@@ -1035,11 +1042,7 @@ int HipDetector::gradientMag(const MatP& I, MatP& M, MatP& O, int normRad, doubl
 
 int HipDetector::gradientHist(const MatP& M, const MatP& O, MatP& H, int binSize, int nOrients, int full, int softBin)
 {
-    if (!m_ctx)
-    {
-        m_api = &hip::load();
-        check(m_api->acf_hip_create(0, nullptr, &m_ctx), "acf_hip_create");
-    }
+    ensureContext();
     H.create(M.rows() / binSize, M.cols() / binSize, nOrients);
     check(m_api->acf_hip_op_gradient_hist(m_ctx, M.data(), O.data(), H.data(), M.cols(), M.rows(), binSize, nOrients, softBin, full), "acf_hip_op_gradient_hist");
     return 0;
@@ -1105,10 +1108,6 @@ void chnsParams(const HipDetector::Options::Pyramid::Chns& ch, acf_hip_params& p
     p.softBin = ch.pGradHist.softBin;
     p.isLuv = ch.isLuv ? 1 : 0;
 }
-std::string planeTag(const char* name, int cols, int rows)
-{
-    return std::string(name) + ":" + std::to_string(cols) + "x" + std::to_string(rows);
-}
 } // namespace
 
 int HipDetector::chnsCompute(const MatP& IIn, const Options::Pyramid::Chns& pChns, Channels& chns, bool isInit, const MatLoggerType& pLogger, int device)
@@ -1164,12 +1163,7 @@ int HipDetector::chnsCompute(const MatP& IIn, const Options::Pyramid::Chns& pChn
             utilCheck(api, c, api.acf_hip_op_conv_tri(c, col.data(), sm.data(), H, W, dcol, p.colorSmooth, 1), "acf_hip_op_conv_tri");
             col = sm;
         }
-        static const char* luv[3] = { "L", "U", "V" };
-        for (int z = 0; z < dcol; z++)
-        {
-            MatP plane(W, H, 1, col[z]);
-            pLogger(plane, planeTag(dcol == 3 ? luv[z] : "L", H, W));
-        }
+        logColourPlanes(pLogger, col, dcol, H, W);
         float* o = all.data();
         if (p.colorEnabled)
         {
@@ -1201,15 +1195,7 @@ int HipDetector::chnsCompute(const MatP& IIn, const Options::Pyramid::Chns& pChn
             if (p.gradHistEnabled)
             {
                 utilCheck(api, c, api.acf_hip_op_gradient_hist(c, Mn.data(), On.data(), o, H, W, shrink, p.nOrients, p.softBin, p.full), "acf_hip_op_gradient_hist");
-                MatP hcat(wc, p.nOrients * hc, 1); // cv::hconcat of the planes (:322-329)
-                for (int b = 0; b < p.nOrients; b++)
-                {
-                    for (int r = 0; r < wc; r++)
-                    {
-                        std::memcpy(hcat.data() + (size_t(r) * p.nOrients + b) * hc, o + (size_t(b) * wc + r) * hc, sizeof(float) * hc);
-                    }
-                }
-                pLogger(hcat, planeTag("H", p.nOrients * hc, wc));
+                pLogger(hconcatHist(o, 0, p.nOrients, hc, wc), planeTag("H", p.nOrients * hc, wc));
             }
         }
     }
@@ -1370,11 +1356,7 @@ bool HipDetector::probeHostArithmetic(std::vector<uint32_t>& rcp, std::vector<ui
 
 void HipDetector::setReferenceArithmetic(const uint32_t* rcp4096, const uint32_t* rsqrt8192)
 {
-    if (!m_ctx)
-    {
-        m_api = &hip::load();
-        check(m_api->acf_hip_create(0, nullptr, &m_ctx), "acf_hip_create");
-    }
+    ensureContext();
     check(m_api->acf_hip_set_x86_tables(m_ctx, rcp4096, rsqrt8192), "acf_hip_set_x86_tables");
     check(m_api->acf_hip_set_option(m_ctx, "arith", 1), "acf_hip_set_option(arith)");
 }

@@ -359,7 +359,14 @@ public:
 private:
     void check(int rc, const char* what) const;
     void fillParams(acf_hip_params& p) const;
+    void ensureContext(int device = 0); // the context, created at its first use
+    void ensureModel();                 // the model on the context, pushed again after a change (m_dirty)
     void ensurePlan(int imgH, int imgW, int d, int batch);
+    int numChannels() const;            // of a level, from opts.pPyramid.pChns
+    // what the loggers of chnsPyramid and chnsCompute share
+    static std::string planeTag(const char* name, int cols, int rows);
+    static void logColourPlanes(const MatLoggerType& logger, MatP& planes, int d, int H, int W);
+    static MatP hconcatHist(const float* src, int firstPlane, int nOrients, int hC, int wC);
     void fetch(int frame, RectVec& objects, RealVec* scores);
     void detect1(const float* f32, const uint8_t* u8, int rows, int cols, DetectionVec& objects);
     void finish(DetectionVec& bbs, RectVec& objects, RealVec* scores, bool forceHostNms = false) const; // ACF.cpp:332-364
