@@ -228,7 +228,7 @@ struct Options
 struct acf_hip_ctx
 {
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr; // the caller's stream: assigned in acf_hip_create and nowhere else (a stage that enqueues elsewhere is told its stream)
     bool ownStream = false;
     // side streams: independent launches of one stage (the level groups) run concurrently, forked from and
     // joined back into `stream` with events, so the stage costs its longest launch instead of their sum
@@ -507,15 +507,15 @@ int needStream(const acf_hip_ctx* c, const char* who)
     return !c ? ACF_HIP_E_INVALID : !c->slots.empty() ? ACF_HIP_OK : fail(c, ACF_HIP_E_INVALID, std::string(who) + ": stream_open first");
 }
 
-// Profile marker: an event recorded on the stream before the launch named
-// `name`; a kernel's time is the span to the next marker.
 // the CPU tables the three approximate sites evaluate (option "arith" = 1), or null: exact arithmetic
 inline const uint32_t* x86T(const acf_hip_ctx* c)
 {
     return c->opt.arith ? c->d_x86 : nullptr;
 }
 
-void prof(acf_hip_ctx* c, const char* name)
+// Profile marker: an event recorded on the stream before the launch named
+// `name`; a kernel's time is the span to the next marker.
+void prof(acf_hip_ctx* c, hipStream_t st, const char* name)
 {
     if (!c->opt.profile)
     {
@@ -530,11 +530,11 @@ void prof(acf_hip_ctx* c, const char* name)
         }
         c->evPool.push_back(e);
         c->evName.push_back(name);
-        c->evStream.push_back(c->stream);
+        c->evStream.push_back(st);
     }
     c->evName[c->evUsed] = name;
-    c->evStream[c->evUsed] = c->stream;
-    (void)hipEventRecord(c->evPool[c->evUsed], c->stream);
+    c->evStream[c->evUsed] = st;
+    (void)hipEventRecord(c->evPool[c->evUsed], st);
     c->evUsed++;
 }
 
@@ -801,7 +801,7 @@ static SmoothTri1Kernel smoothTri1Kernel(int R, bool aliased)
     }
 }
 
-int launchSmooth(acf_hip_ctx* c, const float* in, float* out, const SmoothJob* d_jobs, int nJobs, int maxPlanes, int maxH,
+int launchSmooth(acf_hip_ctx* c, hipStream_t st, const float* in, float* out, const SmoothJob* d_jobs, int nJobs, int maxPlanes, int maxH,
     int64_t in_fs, int64_t out_fs, int nFrames, float p, bool aliased)
 {
     // threads along y, R interleaved rows per thread: the (nt, R) with the fewest idle row slots (every slot
@@ -823,9 +823,9 @@ int launchSmooth(acf_hip_ctx* c, const float* in, float* out, const SmoothJob* d
         return fail(c, ACF_HIP_E_UNSUPPORTED, "smooth: plane taller than 4096 rows");
     }
     const int ldsStride = maxH + 1;
-    prof(c, nJobs > 1 ? "k_smooth_tri1(levels)" : "k_smooth_tri1(image)");
+    prof(c, st, nJobs > 1 ? "k_smooth_tri1(levels)" : "k_smooth_tri1(image)");
     const size_t lds = 2 * size_t(ldsStride) * sizeof(float);
-    hipLaunchKernelGGL(smoothTri1Kernel(R, aliased), dim3(maxPlanes, nJobs, nFrames), dim3(nt), lds, c->stream, in, out, d_jobs, in_fs, out_fs, p, ldsStride,
+    hipLaunchKernelGGL(smoothTri1Kernel(R, aliased), dim3(maxPlanes, nJobs, nFrames), dim3(nt), lds, st, in, out, d_jobs, in_fs, out_fs, p, ldsStride,
         c->d_dump);
     LAUNCHCHK(c, "k_smooth_tri1");
     return ACF_HIP_OK;
@@ -893,7 +893,7 @@ static TriyChnsKernel triyChnsKernel(bool maxO6, bool ut, bool x86)
 // uCapacity / moCapacity: floats per frame the U and the M, O buffers hold (>= fs); blocked: M and O ARE in the blocked layout
 // (the caller ran k_grad_mag_vec<true> after asking triPlan)
 // xDone: U is there already (k_smooth_grad_tri wrote it, blocked)
-int launchTri(acf_hip_ctx* c, const float* in, float* U, float* S, int h, int w, int rad, int64_t fs, int nFrames, ChnsArgs* fuse = nullptr,
+int launchTri(acf_hip_ctx* c, hipStream_t st, const float* in, float* U, float* S, int h, int w, int rad, int64_t fs, int nFrames, ChnsArgs* fuse = nullptr,
     bool* fused = nullptr, int64_t uCapacity = 0, int64_t moCapacity = 0, bool blocked = false, bool xDone = false)
 {
     if (rad > 15)
@@ -917,15 +917,15 @@ int launchTri(acf_hip_ctx* c, const float* in, float* U, float* S, int h, int w,
     }
     else
     {
-        prof(c, "k_tri_x");
+        prof(c, st, "k_tri_x");
         if (vecX)
         {
-            hipLaunchKernelGGL(triX5Kernel(ut), dim3(cdiv(h / 4, 64), 1, nFrames), dim3(64), 0, c->stream, in, U, h, w,
+            hipLaunchKernelGGL(triX5Kernel(ut), dim3(cdiv(h / 4, 64), 1, nFrames), dim3(64), 0, st, in, U, h, w,
                 ut ? mfs : fs, ut ? ufs : fs, ut ? nyb : 0, ut ? nybM : 0);
         }
         else
         {
-            hipLaunchKernelGGL(k_tri_x, dim3(cdiv(h, 256), 1, nFrames), dim3(256), 0, c->stream, in, U, h, w, rad, fs);
+            hipLaunchKernelGGL(k_tri_x, dim3(cdiv(h, 256), 1, nFrames), dim3(256), 0, st, in, U, h, w, rad, fs);
         }
         LAUNCHCHK(c, "k_tri_x");
     }
@@ -935,26 +935,26 @@ int launchTri(acf_hip_ctx* c, const float* in, float* U, float* S, int h, int w,
     }
     if (doFuse)
     {
-        prof(c, "k_triy_chns");
+        prof(c, st, "k_triy_chns");
         if (ut)
         {
             fuse->m_fs = mfs;
             fuse->nybM = nybM;
         }
-        hipLaunchKernelGGL(triyChnsKernel(fuse->nOrients <= 6, ut, fuse->x86 != nullptr), dim3(cdiv(w, 256), 1, nFrames), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(triyChnsKernel(fuse->nOrients <= 6, ut, fuse->x86 != nullptr), dim3(cdiv(w, 256), 1, nFrames), dim3(256), 0, st,
             (const float*)U, *fuse, ut ? ufs : fs, ut ? nyb : 0);
         LAUNCHCHK(c, "k_triy_chns");
         *fused = true;
         return ACF_HIP_OK;
     }
-    prof(c, "k_tri_y");
+    prof(c, st, "k_tri_y");
     if (rad == 5 && h % 4 == 0 && h >= 48 && fs % 4 == 0 && ((uintptr_t(U) | uintptr_t(S)) & 15) == 0)
     {
-        hipLaunchKernelGGL(k_tri_y5s, dim3(cdiv(w, 256), 1, nFrames), dim3(256), 0, c->stream, (const float*)U, S, h, w, fs);
+        hipLaunchKernelGGL(k_tri_y5s, dim3(cdiv(w, 256), 1, nFrames), dim3(256), 0, st, (const float*)U, S, h, w, fs);
     }
     else
     {
-        hipLaunchKernelGGL(k_tri_y, dim3(cdiv(w, 64), 1, nFrames), dim3(64), 0, c->stream, (const float*)U, S, h, w, rad, fs);
+        hipLaunchKernelGGL(k_tri_y, dim3(cdiv(w, 64), 1, nFrames), dim3(64), 0, st, (const float*)U, S, h, w, rad, fs);
     }
     LAUNCHCHK(c, "k_tri_y");
     return ACF_HIP_OK;
@@ -980,11 +980,11 @@ static ChnsKernel chnsKernel(int shrink, bool maxO6)
     return maxO6 ? k_chns<2, 6> : k_chns<2, 12>;
 }
 
-int launchChns(acf_hip_ctx* c, const ChnsArgs& a, int shrink, int nFrames)
+int launchChns(acf_hip_ctx* c, hipStream_t st, const ChnsArgs& a, int shrink, int nFrames)
 {
     const int hc = a.h / shrink, wc = a.w / shrink;
-    prof(c, "k_chns");
-    hipLaunchKernelGGL(chnsKernel(shrink, a.nOrients <= 6), dim3(cdiv(int64_t(hc) * wc, 256), 1, nFrames), dim3(256), 0, c->stream, a);
+    prof(c, st, "k_chns");
+    hipLaunchKernelGGL(chnsKernel(shrink, a.nOrients <= 6), dim3(cdiv(int64_t(hc) * wc, 256), 1, nFrames), dim3(256), 0, st, a);
     LAUNCHCHK(c, "k_chns");
     return ACF_HIP_OK;
 }
@@ -1045,23 +1045,35 @@ __global__ void __launch_bounds__(256) k_copy_planes(const float* __restrict__ i
 
 namespace
 {
-int kidsFork(acf_hip_ctx* c)
+// Fork: `ev` recorded on `from`, then each of the n streams streamAt(0 .. n - 1) waits for it.
+template <class StreamAt>
+int forkStreams(acf_hip_ctx* c, hipStream_t from, hipEvent_t ev, size_t n, StreamAt streamAt)
 {
-    HIPCHK(c, hipEventRecord(c->evFork, c->stream));
-    for (acf_hip_ctx* k : c->kids)
+    HIPCHK(c, hipEventRecord(ev, from));
+    for (size_t i = 0; i < n; i++)
     {
-        HIPCHK(c, hipStreamWaitEvent(k->stream, c->evFork, 0));
+        HIPCHK(c, hipStreamWaitEvent(streamAt(i), ev, 0));
     }
     return ACF_HIP_OK;
 }
-int kidsJoin(acf_hip_ctx* c)
+// Join: c->evJoin[i] recorded on streamAt(i) and `to` waiting for it, stream by stream.
+template <class StreamAt>
+int joinStreams(acf_hip_ctx* c, size_t n, StreamAt streamAt, hipStream_t to)
 {
-    for (size_t i = 0; i < c->kids.size(); i++)
+    for (size_t i = 0; i < n; i++)
     {
-        HIPCHK(c, hipEventRecord(c->evJoin[i], c->kids[i]->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->evJoin[i], 0));
+        HIPCHK(c, hipEventRecord(c->evJoin[i], streamAt(i)));
+        HIPCHK(c, hipStreamWaitEvent(to, c->evJoin[i], 0));
     }
     return ACF_HIP_OK;
+}
+int kidsFork(acf_hip_ctx* c)
+{
+    return forkStreams(c, c->stream, c->evFork, c->kids.size(), [c](size_t i) { return c->kids[i]->stream; });
+}
+int kidsJoin(acf_hip_ctx* c)
+{
+    return joinStreams(c, c->kids.size(), [c](size_t i) { return c->kids[i]->stream; }, c->stream);
 }
 // fn(kid, first, n) for every child that owns frames of a batch of nF (child i: [i * chunk, min(nF, (i+1) * chunk))), forked from
 // and joined into c's stream; the first failure returns its code with the child's text on c
@@ -1122,6 +1134,7 @@ namespace
 std::mutex g_turnMu;
 hipEvent_t g_turnLast[2][64] = {};
 // which: 0 = the tile kernel, 1 = the level kernel; chain: whose turns it takes (0 / 1)
+// (on c->stream: the levels and the cascade always run on the context's own stream)
 int turnBegin(acf_hip_ctx* c, int which, int chain)
 {
     if (c->device < 0 || c->device >= 64)
@@ -1895,7 +1908,7 @@ static YuvSrc yuvSrc(const uint8_t* frames, int pix, int rows, int cols, const U
 // k_yuv420_to_rgb8 over a batch: NV12 / NV21 frames of rows x cols -> tight RGB frames at dst
 static int launchYuvToRgb(acf_hip_ctx* c, const YuvSrc& s, int nF, uint8_t* dst)
 {
-    prof(c, "k_yuv420_to_rgb8");
+    prof(c, c->stream, "k_yuv420_to_rgb8");
     hipLaunchKernelGGL(k_yuv420_to_rgb8, dim3(cdiv(s.W / 2, 64), cdiv(s.H / 2, 4), nF), dim3(256), 0, c->stream, s, dst);
     LAUNCHCHK(c, "k_yuv420_to_rgb8");
     return ACF_HIP_OK;
@@ -2015,7 +2028,7 @@ static int launchResizeU8(acf_hip_ctx* c, const acf_hip_ctx::InputResize& rz, co
     a.yrun = reinterpret_cast<const int2*>(rz.d_yrun);
     a.xtap = reinterpret_cast<const int2*>(rz.d_xtap);
     a.ytap = reinterpret_cast<const int2*>(rz.d_ytap);
-    prof(c, "k_resize_u8");
+    prof(c, c->stream, "k_resize_u8");
     hipLaunchKernelGGL(k_resize_u8, dim3(cdiv(t.dcols, 64), cdiv(t.drows, 4), nF), dim3(256), 0, c->stream, a);
     LAUNCHCHK(c, "k_resize_u8");
     return ACF_HIP_OK;
@@ -2198,7 +2211,7 @@ int acf_hip_detect(acf_hip_ctx* c)
     {
         return rc;
     }
-    prof(c, "(end)");
+    prof(c, c->stream, "(end)");
     c->countsFetched = false;
     c->detectValid = true;
     return ACF_HIP_OK;

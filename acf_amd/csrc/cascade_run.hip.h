@@ -345,14 +345,14 @@ static int ensureRankCells(acf_hip_ctx* c, const CascState& cs, const CascadeCal
     {
         return rc;
     }
-    prof(c, "k_rank");
+    prof(c, c->stream, "k_rank");
     hipLaunchKernelGGL(k_rank, dim3(cdiv(cs.rankMaxWP, RANK_CHUNK_COLS), cs.nLevels * call.in.nChns, call.in.nF), dim3(256), ldsR, c->stream, call.in.pyr,
         call.in.pyr_fs, cs.d_pyrR, cs.pyrRCells, (const RankJob*)cs.d_rankJobs, call.in.nChns, (const RankChan*)cs.d_rankChan, (const RankRec*)cs.d_rankRec);
     LAUNCHCHK(c, "k_rank");
     *ranks = true;
     if (call.path == CascPath::Staged)
     {
-        prof(c, "k_cascade"); // (what follows is the staged cascade's time again)
+        prof(c, c->stream, "k_cascade"); // (what follows is the staged cascade's time again)
     }
     return ACF_HIP_OK;
 }
@@ -480,7 +480,7 @@ static int launchTiled2Tails(acf_hip_ctx* c, const CascState& cs, const CascadeC
     {
         // the first codeCap queue entries of every frame carry leaf codes (stage E of the tile kernel): the ordered scan
         const size_t ldsS = size_t(c->p.nTrees - cs.tiles.g.b[4]) * 16;
-        prof(c, "k_tail_scan");
+        prof(c, c->stream, "k_tail_scan");
         if ((rc = launchLds(c, &k_tail_scan, dim3(nF * ((cs.codes.cap + 255) / 256)), dim3(256), ldsS, a)))
         {
             return rc;
@@ -493,7 +493,7 @@ static int launchTiled2Tails(acf_hip_ctx* c, const CascState& cs, const CascadeC
     }
     // queue entries without codes (beyond codeCap): a wave per entry; the blocks leave at once when k_tail_scan has taken the
     // whole queue
-    prof(c, "k_cascade_tail3");
+    prof(c, c->stream, "k_cascade_tail3");
     if (call.rank)
     {
         hipLaunchKernelGGL(k_cascade_tail_rank, dim3(std::max(1, 1024 / nF) * nF), dim3(64), 0, c->stream, at, (const TreeNode*)cs.d_tailNodesR);
@@ -539,7 +539,7 @@ static int launchTiled2(acf_hip_ctx* c, const CascState& cs, const CascadeCall& 
     {
         return rc;
     }
-    prof(c, "k_cascade_tile");
+    prof(c, c->stream, "k_cascade_tile");
     if ((rc = launchLds(c, call.tile3, dim3(call.grid.blocks), dim3(at.g.NW * 64), call.tileLds, at)))
     {
         return rc;
@@ -589,7 +589,7 @@ static int launchTileStageD(acf_hip_ctx* c, const CascState& cs, const CascadeCa
         at.codeCap = call.pooledTail ? cs.codes.cap : 0;
         at.codePitch = cs.codes.pitch;
         at.tileNext = call.grid.persist ? cs.counters().tileNextD() : nullptr;
-        prof(c, "k_cascade_tile");
+        prof(c, c->stream, "k_cascade_tile");
     }
     int rc;
     if ((rc = launchLds(c, call.tileD, dim3(call.grid.blocks), dim3(ts.g.NW * 64), call.tileLds, at)))
@@ -599,7 +599,7 @@ static int launchTileStageD(acf_hip_ctx* c, const CascState& cs, const CascadeCa
     LAUNCHCHK(c, (ts.g.pooled ? "k_cascade_tile3D" : "k_cascade_tileD"));
     if (ts.g.pooled)
     {
-        prof(c, "k_cascade");
+        prof(c, c->stream, "k_cascade");
     }
     return ACF_HIP_OK;
 }
@@ -708,7 +708,7 @@ static int sortHits(acf_hip_ctx* c, const CascState& cs, const CascadeCall& call
         LAUNCHCHK(c, "k_expand_hits");
         hitsForSort = cs.d_hitsX;
     }
-    prof(c, "k_sort_map");
+    prof(c, c->stream, "k_sort_map");
     hipLaunchKernelGGL(k_sort_map, dim3(SM_BLOCKS, nF), dim3(256), 0, c->stream, hitsForSort, (const int32_t*)cs.d_counts, cs.maxHits,
         d_box, p.stride, shift_h, shift_w, cs.d_sorted, cs.d_dets);
     LAUNCHCHK(c, "k_sort_map");
@@ -718,7 +718,7 @@ static int sortHits(acf_hip_ctx* c, const CascState& cs, const CascadeCall& call
 static int runCascade(acf_hip_ctx* c, const CascState& cs, const CascInput& in, const BoxLevel* d_box, bool* ranks = nullptr)
 {
     const CascadeCall call = planCascadeCall(c, cs, in, ranks != nullptr);
-    prof(c, "k_cascade");
+    prof(c, c->stream, "k_cascade");
     int rc;
     if ((!call.countersCleared && (rc = clearCounters(c, cs, call))) || (rc = ensureRankCells(c, cs, call, ranks)))
     {
@@ -774,7 +774,7 @@ static int launchNms(acf_hip_ctx* c, int nF)
     {
         return rc;
     }
-    prof(c, "k_nms");
+    prof(c, c->stream, "k_nms");
     hipLaunchKernelGGL(k_nms, dim3(nF), dim3(1024), kNmsLds, c->stream, a);
     LAUNCHCHK(c, "k_nms");
     return ACF_HIP_OK;
@@ -802,7 +802,7 @@ static int runLdcf(acf_hip_ctx* c, int nF)
     if (L.tiles > 0)
     {
         // filters + half resample in one kernel: the filtered full-resolution planes stay in LDS
-        prof(c, "k_ldcf_tile");
+        prof(c, c->stream, "k_ldcf_tile");
         const int xoT = 16;
         const size_t ldsB = ldcfTileLdsFloats(L.tileRows, L.tileCols, xoT) * sizeof(float);
         auto kern = &k_ldcf_tile<8, 4>;
@@ -818,11 +818,11 @@ static int runLdcf(acf_hip_ctx* c, int nF)
         return ACF_HIP_OK;
     }
     const int nL = int(pl.levels.size());
-    prof(c, "k_ldcf_conv");
+    prof(c, c->stream, "k_ldcf_conv");
     hipLaunchKernelGGL(k_ldcf_conv, dim3(cdiv(L.maxCells, 256), pl.nChns * c->p.ldcfK, nF * nL), dim3(256), 0, c->stream, (const float*)c->d_pyr, L.d_tmp,
         (const float*)L.d_filt, (const LdcfJob*)L.d_jobs, nL, pl.nChns, pl.pyr_floats, L.tmpFloats);
     LAUNCHCHK(c, "k_ldcf_conv");
-    prof(c, "k_resample(ldcf)");
+    prof(c, c->stream, "k_resample(ldcf)");
     hipLaunchKernelGGL(k_resample, dim3(L.maxBlocks, nL, nF), dim3(64, 4), 0, c->stream, (const float*)L.d_tmp, L.d_pyr, descs, (const int32_t*)c->d_it,
         (const float*)c->d_ft, RS_XT);
     LAUNCHCHK(c, "k_resample(ldcf)");

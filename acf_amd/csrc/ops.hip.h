@@ -179,7 +179,7 @@ int smoothOne(acf_hip_ctx* c, Scratch& s, const char* who, const float* in, floa
     {
         return fail(c, ACF_HIP_E_HIP, std::string(who) + ": allocation");
     }
-    return launchSmooth(c, in, out, dj, 1, d, h, fs, fs, 1, p, aliased);
+    return launchSmooth(c, c->stream, in, out, dj, 1, d, h, fs, fs, 1, p, aliased);
 }
 
 // gradMag of ONE h x w plane I into M and O (k_grad_mag_strip), then convTri(M, normRad) into S through U when normRad > 0; `who`
@@ -198,7 +198,7 @@ int gradMagOne(acf_hip_ctx* c, const char* who, const char* normRadErr, const fl
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, normRadErr);
     }
-    return launchTri(c, M, U, S, h, w, normRad, int64_t(h) * w, 1);
+    return launchTri(c, c->stream, M, U, S, h, w, normRad, int64_t(h) * w, 1);
 }
 } // namespace
 
@@ -242,7 +242,7 @@ int acf_hip_op_conv_tri(acf_hip_ctx* c, const float* in, float* out, int h, int 
         {
             return fail(c, ACF_HIP_E_HIP, "op_conv_tri: allocation");
         }
-        if ((rc = launchTri(c, di, dU, dout, h, w, ri, np, d)))
+        if ((rc = launchTri(c, c->stream, di, dU, dout, h, w, ri, np, d)))
         {
             return rc;
         }
@@ -548,7 +548,7 @@ int acf_hip_chns_compute(acf_hip_ctx* c, const acf_hip_params* pIn, const float*
             return rc;
         }
     }
-    int rc = launchChns(c, a, shrink, 1);
+    int rc = launchChns(c, c->stream, a, shrink, 1);
     if (rc)
     {
         return rc;
@@ -591,7 +591,7 @@ int acf_hip_op_gradient_hist(acf_hip_ctx* c, const float* M, const float* O, flo
     a.full = full;
     a.hardBin = softBin < 0;
     a.rq_y = shrinkGainY(bin);
-    int rc = launchChns(c, a, bin, 1);
+    int rc = launchChns(c, c->stream, a, bin, 1);
     if (rc)
     {
         return rc;
@@ -632,7 +632,7 @@ int acf_hip_op_im_resample(acf_hip_ctx* c, const float* in, float* out, int ha, 
     if (sp.ok && !resampleGenericOnly() && (rc = ensureConstTables(c)) == 0)
     {
         // the strip march the pyramid uses for its down-sampled real scales
-        launchStrip(c, sp, ddesc, 0, -1, d, di, dout, nullptr, dit, dft, 1);
+        launchStrip(c, c->stream, sp, ddesc, 0, -1, d, di, dout, nullptr, dit, dft, 1);
     }
     else if (resampleUpOk(dd) && !resampleGenericOnly())
     {
@@ -720,7 +720,7 @@ static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::ve
     {
         return rc;
     }
-    prof(c, "(end)");
+    prof(c, c->stream, "(end)");
     int nHits = 0;
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&nHits, cs.d_counts, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
     {

@@ -1,6 +1,8 @@
 // pyramid_run.hip.h — part of acf_hip.hip (included there and nowhere else): acf_hip_pyramid's launch logic, one function per stage of
 // Detector::chnsPyramid (chnsPyramid.cpp:160-456) in the order the reference runs them.  PyramidRun holds what the stages of ONE call
-// share; every stage enqueues on the context's stream(s) and returns an ACF_HIP_* status.
+// share; every stage returns an ACF_HIP_* status.  The real scales' stages enqueue on PyramidRun::st and hand it to the launch helpers they
+// call: the context's stream, or the scale's own between realScale and joinScales (option scale_streams).  c->stream itself is never reassigned;
+// ingest and colour run on it before any scale has a stream of its own, the levels after joinScales has set st back to it.
 //
 //   ingest()            packed 8-bit frames -> planar f32 (ACF.cpp:114-119,137), the apps' Resizer in front of it
 //   colour()            rgbConvert once at full resolution (chnsPyramid.cpp:230-263)
@@ -8,7 +10,8 @@
 //   realScale(k)        imageResample(k) -> planScale(k) -> smoothImage(k) -> gradientChannels(k): chnsCompute at a real scale (:297-338,
 //                       chnsCompute.cpp:146-338)
 //   joinScales()
-//   levels(f0, n)       the approximated levels + final smoothing + padding of frames [f0, f0 + n) (:385-435)
+//   levels(f0, n)       the approximated levels + final smoothing + padding of frames [f0, f0 + n) (:385-435): planLevels decides the forms
+//                       (LevelsCall), launchLevels runs them for a frame offset
 //   levelsWithImageLambdas()   the same behind the per-image lambda estimate (:341-374)
 #pragma once
 
@@ -39,6 +42,37 @@ using LevelAllKernel = void (*)(const float*, float*, float*, const LevelJob*, c
     float*, int, LevelRankArgs, LevelSegArgs);
 using LevelKernel = void (*)(const float*, float*, float*, const LevelJob*, const ResampleDesc*, const int32_t*, const float*, int, int64_t, int64_t, float,
     float*, int);
+
+// How the levels stage runs, decided once per call (PyramidRun::planLevels); launchLevels and its launchers only read it
+enum LevelsPath
+{
+    LV_FUSED,       // k_level_all + k_level groups resample, smooth and place every level
+    LV_WAVE_SMOOTH, // the same kernels smooth and place what a separate k_resample approximated
+    LV_SMOOTH_JOBS, // launchSmooth over the final jobs
+    LV_COPY         // no smoothing: plane copies
+};
+struct LevelsCall
+{
+    LevelsPath path = LV_COPY;
+    int nLF = 0;               // frames per launch
+    bool approxFirst = false;  // the approximated levels come from a k_resample launch of their own
+    bool pad = false;          // k_pad_reflect runs
+    float pS = 0.f;            // convTri1's p of the final smoothing
+    int64_t copyElems = 0;     // LV_COPY: the largest level's elements
+    // LV_FUSED / LV_WAVE_SMOOTH
+    const LevelJob* jobs = nullptr;                   // the leading nAll go to k_level_all, the rest to k_level in groups
+    const std::vector<acf_hip_ctx::LevelGroup>* groups = nullptr;
+    int nAll = 0;
+    size_t nSide = 0;          // side streams the groups fan out to (0: they follow on the stage's stream)
+    bool rawOut = false;       // option taps: the approximated levels' raw channels are written back too
+    bool emitRank = false, emitF32 = true; // what the levels leave: the cascade's 16-bit rank cells, floats
+    LevelRankArgs ra{};        // (without the frame's output pointer)
+    LevelSegArgs lsa{};        // column segments (nSeg, warm-up) of k_level_all's first launch
+    size_t ldsL = 0;
+    LevelAllKernel allKernel = nullptr;
+    bool lvTurns = false;      // option cascade_turns: k_level_all takes turns with the other contexts' (chain lvChain)
+    int lvChain = 1;
+};
 
 static SmoothVecKernel smoothGradKernel(bool tri, bool half, bool x86)
 {
@@ -112,15 +146,15 @@ static LevelKernel levelKernel(int R, int mode)
 }
 
 // option count_repairs: the n planes a verify kernel judged (its flags at d_flags) into c->repairs[slot], those it flagged into [slot + 1]
-static int countRepairs(acf_hip_ctx* c, const int32_t* d_flags, size_t n, int slot)
+static int countRepairs(acf_hip_ctx* c, hipStream_t st, const int32_t* d_flags, size_t n, int slot)
 {
     if (!c->opt.countRepairs)
     {
         return ACF_HIP_OK;
     }
     std::vector<int32_t> fl(n);
-    HIPCHK(c, hipMemcpyAsync(fl.data(), d_flags, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(fl.data(), d_flags, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
     c->repairs[slot] += int64_t(n);
     for (int32_t v : fl)
     {
@@ -145,16 +179,15 @@ struct PyramidRun
     std::vector<int> srcIdx;                      // per real scale: the real scale whose smoothed image it is resampled from (-1: the frame)
     std::vector<char> halfDone, pairDone;         // the scale's image was produced already (by the previous scale's smoothing / its strip pair)
     bool scalePar = false;                        // the real scales on their own streams
-    hipStream_t mainStream;
-    bool wroteRank = false, wroteF32 = true;      // what the level kernels left: 16-bit rank cells, floats
+    hipStream_t st;                               // the stream the current stage enqueues on: the context's, but a real scale's own between realScale and joinScales
+    LevelsCall lv;                                // the levels stage of this call (planLevels)
     PackedSrc reduced{}, converted{};
 
     PyramidRun(acf_hip_ctx* ctx, const float* frames_, int nF_)
         : c(ctx), p(ctx->p), pl(ctx->plan), nF(nF_), H(pl.H), W(pl.W), d(pl.d), d_in(pl.d_in), shrink(ctx->p.shrink), np0(int64_t(pl.H) * pl.W), frames(frames_),
-          mainStream(ctx->stream)
+          st(ctx->stream)
     {
     }
-    ~PyramidRun() { c->stream = mainStream; } // (the launch helpers all use c->stream: realScale points it at the scale's stream; back on every way out)
 
     int ingest(const PackedSrc* u8, bool& ingestConverted);
     int colour(bool ingestConverted);
@@ -165,7 +198,12 @@ struct PyramidRun
     int smoothImage(size_t k, const float* img, int64_t img_fs, const ScalePlan& sp);
     int gradientChannels(size_t k, const ScalePlan& sp);
     int joinScales();
+    int planLevels(int nLF);
     int levels(int f0, int nLF);
+    int launchLevels(const LevelsCall& lc, int f0);
+    int launchLevelAll(const LevelsCall& lc, int f0);
+    int launchLevelGroups(const LevelsCall& lc, int f0);
+    int padLevels(const LevelsCall& lc, int f0);
     int levelsWithImageLambdas();
 };
 
@@ -227,7 +265,7 @@ int PyramidRun::ingest(const PackedSrc* u8, bool& ingestConverted)
     if (u8)
     {
         // 8-bit ingest (ACF.cpp:114-119,137; MatP.cpp:51-73), fused with the colour conversion below when there is one
-        prof(c, fusedYuv ? "k_ingest_yuv420" : "k_ingest_u8");
+        prof(c, c->stream, fusedYuv ? "k_ingest_yuv420" : "k_ingest_u8");
         ingestConverted = c->d_color && p.colorSpace != ACF_HIP_CS_HSV; // (hsv: planar ingest, then k_rgb2hsv like a float frame)
         if (ingestConverted)
         {
@@ -267,7 +305,7 @@ int PyramidRun::colour(bool ingestConverted)
     }
     else if (c->d_color)
     {
-        prof(c, "k_colour");
+        prof(c, c->stream, "k_colour");
         const int64_t out_fs = int64_t(d) * np0;
         launchColour(c, frames, c->d_color, np0, nF, cur_fs, out_fs, p.colorSpace, d_in); // (hsv: d_in == 3, the plan checked)
         LAUNCHCHK(c, "colour conversion");
@@ -325,12 +363,12 @@ int PyramidRun::realScale(size_t k)
     {
         if (k > 0)
         {
-            prof(c, "(end)"); // closes the previous scale's last kernel on its stream
+            prof(c, st, "(end)"); // closes the previous scale's last kernel on its stream
         }
-        c->stream = k == 0 ? mainStream : c->side[k - 1];
+        st = k == 0 ? c->stream : c->side[k - 1];
         if (k > 0)
         {
-            HIPCHK(c, hipStreamWaitEvent(c->stream, c->evScale[k - 1], 0));
+            HIPCHK(c, hipStreamWaitEvent(st, c->evScale[k - 1], 0));
         }
     }
     const float* img = cur;
@@ -346,7 +384,7 @@ int PyramidRun::realScale(size_t k)
     }
     if (scalePar)
     {
-        HIPCHK(c, hipEventRecord(c->evScale[k], c->stream));
+        HIPCHK(c, hipEventRecord(c->evScale[k], st));
     }
     if (rs.adoptAsI)
     {
@@ -371,7 +409,7 @@ int PyramidRun::imageResample(size_t k, const float*& img, int64_t& img_fs)
     {
         return fail(c, ACF_HIP_E_INVALID, "pyramid: internal frame-stride mismatch");
     }
-    prof(c, "k_resample(image)");
+    prof(c, st, "k_resample(image)");
     const ResampleDesc& hd = c->h_descs[rs.descIndex];
     const bool exactHalf = hd.xmode == RS_EXACT && hd.ymode == RS_EXACT && hd.xk == 2 && hd.yk == 2 && hd.ha % 4 == 0 && hd.hb % 2 == 0 &&
         hd.src_frame_stride % 4 == 0 && hd.dst_frame_stride % 2 == 0 && hd.src_off % 4 == 0 && hd.dst_off % 2 == 0 &&
@@ -388,27 +426,27 @@ int PyramidRun::imageResample(size_t k, const float*& img, int64_t& img_fs)
         {
             pairDone[k + 1] = 1;
         }
-        launchStrip(c, pair ? rs.stripPair : rs.strip, c->d_descs, rs.descIndex, pair ? c->real[k + 1].descIndex : -1, hd.nplanes, cur, rs.img,
+        launchStrip(c, st, pair ? rs.stripPair : rs.strip, c->d_descs, rs.descIndex, pair ? c->real[k + 1].descIndex : -1, hd.nplanes, cur, rs.img,
             pair ? c->real[k + 1].img : nullptr, c->d_it, c->d_ft, nF);
     }
     else if (exactHalf)
     {
         const int64_t items = int64_t(hd.hb / 2) * hd.wb * hd.nplanes;
-        hipLaunchKernelGGL(k_resample_half, dim3(cdiv(items, 256), 1, nF), dim3(256), 0, c->stream, cur, rs.img,
+        hipLaunchKernelGGL(k_resample_half, dim3(cdiv(items, 256), 1, nF), dim3(256), 0, st, cur, rs.img,
             (const ResampleDesc*)(c->d_descs + rs.descIndex));
     }
     else if (resampleUpOk(hd) && !resampleGenericOnly() && (uintptr_t(rs.img) & 15) == 0)
     {
         // nOctUp > 0: the frame up-sampled (cfg 4)
         const int nw = hd.nplanes * cdiv(hd.hb, 256) * cdiv(hd.wb, RSU_XC);
-        hipLaunchKernelGGL(k_resample_up, dim3(cdiv(nw, 4), 1, nF), dim3(256), 0, c->stream, cur, rs.img,
+        hipLaunchKernelGGL(k_resample_up, dim3(cdiv(nw, 4), 1, nF), dim3(256), 0, st, cur, rs.img,
             (const ResampleDesc*)(c->d_descs + rs.descIndex), (const int32_t*)c->d_it, (const float*)c->d_ft);
     }
     else
     {
         // small planes: fewer columns per wave, more waves
         const int xt = int64_t(resampleBlocks(hd)) * nF < 4096 ? 2 : RS_XT;
-        hipLaunchKernelGGL(k_resample, dim3(resampleBlocks(hd, xt), 1, nF), dim3(64, 4), 0, c->stream, cur, rs.img,
+        hipLaunchKernelGGL(k_resample, dim3(resampleBlocks(hd, xt), 1, nF), dim3(64, 4), 0, st, cur, rs.img,
             (const ResampleDesc*)(c->d_descs + rs.descIndex), (const int32_t*)c->d_it, (const float*)c->d_ft, xt);
     }
     LAUNCHCHK(c, "k_resample(image)");
@@ -552,9 +590,9 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, const Sc
     {
         if (p.colorSmooth > 0)
         {
-            return launchSmooth(c, img, rs.sm, c->d_realJobs + k, 1, d, rs.h, img_fs, int64_t(d) * np, nF, pColor, true);
+            return launchSmooth(c, st, img, rs.sm, c->d_realJobs + k, 1, d, rs.h, img_fs, int64_t(d) * np, nF, pColor, true);
         }
-        hipLaunchKernelGGL(k_copy_planes, dim3(cdiv(np * d, 256), 1, nF), dim3(256), 0, c->stream, img, rs.sm, (const SmoothJob*)(c->d_realJobs + k), img_fs,
+        hipLaunchKernelGGL(k_copy_planes, dim3(cdiv(np * d, 256), 1, nF), dim3(256), 0, st, img, rs.sm, (const SmoothJob*)(c->d_realJobs + k), img_fs,
             int64_t(d) * np);
         LAUNCHCHK(c, "k_copy_planes");
         return ACF_HIP_OK;
@@ -630,13 +668,13 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, const Sc
         {
             return rc;
         }
-        prof(c, gradName);
-        hipLaunchKernelGGL(gradKernel, dim3(1, sp.nSegG, nF), dim3(sp.nt), sp.ldsG, c->stream, gradArgs(sp.segWG, sp.nSegG), sp.fullMask);
+        prof(c, st, gradName);
+        hipLaunchKernelGGL(gradKernel, dim3(1, sp.nSegG, nF), dim3(sp.nt), sp.ldsG, st, gradArgs(sp.segWG, sp.nSegG), sp.fullMask);
     }
     if (nVec > 0)
     {
-        prof(c, "k_smooth_vec");
-        hipLaunchKernelGGL(vecKernel, dim3(nVec, sp.nSeg, nF), dim3(sp.nt), sp.ldsB, c->stream, sa, sp.fullMask);
+        prof(c, st, "k_smooth_vec");
+        hipLaunchKernelGGL(vecKernel, dim3(nVec, sp.nSeg, nF), dim3(sp.nt), sp.ldsB, st, sa, sp.fullMask);
     }
     LAUNCHCHK(c, "k_smooth_vec");
     if (sp.segStride == 1)
@@ -644,10 +682,10 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, const Sc
         return ACF_HIP_OK;
     }
     // the segments' hand-overs, bit for bit; planes with a difference are recomputed as one chain
-    hipLaunchKernelGGL(k_smooth_verify, dim3(sp.segStride - 1, d, nF), dim3(256), 0, c->stream, (const float*)c->d_specState, (const float*)c->d_trueState,
+    hipLaunchKernelGGL(k_smooth_verify, dim3(sp.segStride - 1, d, nF), dim3(256), 0, st, (const float*)c->d_specState, (const float*)c->d_trueState,
         rs.h, sp.segStride, d, c->d_redo, c->opt.smoothForceRedo, sp.nSeg, sp.wantGrad ? p.colorChn : -1, sp.nSegG);
     LAUNCHCHK(c, "k_smooth_verify");
-    if ((rc = countRepairs(c, c->d_redo, size_t(nF) * d, 0)))
+    if ((rc = countRepairs(c, st, c->d_redo, size_t(nF) * d, 0)))
     {
         return rc;
     }
@@ -657,16 +695,16 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, const Sc
     sa.redo = c->d_redo;
     if (sp.wantGrad)
     {
-        prof(c, gradName);
+        prof(c, st, gradName);
         if (sp.nSegG > 1) // (else nothing to repair: the plane was one chain)
         {
-            hipLaunchKernelGGL(gradKernel, dim3(1, 1, nF), dim3(sp.nt), sp.ldsG, c->stream, gradArgs(rs.w, 1), sp.fullMask);
+            hipLaunchKernelGGL(gradKernel, dim3(1, 1, nF), dim3(sp.nt), sp.ldsG, st, gradArgs(rs.w, 1), sp.fullMask);
         }
     }
     if (nVec > 0)
     {
-        prof(c, "k_smooth_vec");
-        hipLaunchKernelGGL(vecKernel, dim3(nVec, 1, nF), dim3(sp.nt), sp.ldsB, c->stream, sa, sp.fullMask);
+        prof(c, st, "k_smooth_vec");
+        hipLaunchKernelGGL(vecKernel, dim3(nVec, 1, nF), dim3(sp.nt), sp.ldsB, st, sa, sp.fullMask);
     }
     LAUNCHCHK(c, "k_smooth_vec(repair)");
     return ACF_HIP_OK;
@@ -689,19 +727,19 @@ int PyramidRun::gradientChannels(size_t k, const ScalePlan& sp)
         a.Mn = nullptr;
         a.m_fs = int64_t(d_in) * np0;
         a.doNorm = 0;
-        return launchChns(c, a, shrink, nF);
+        return launchChns(c, st, a, shrink, nF);
     }
     a.x86 = x86T(c);
     if ((p.gradMagEnabled || p.gradHistEnabled) && !sp.wantGrad) // (with it, M and O are there already)
     {
-        prof(c, "k_grad_mag");
+        prof(c, st, "k_grad_mag");
         if (rs.h % 4 == 0 && np % 4 == 0)
         {
             // 16 bytes per lane, persistent grid (one 16-wave workgroup per CU around the 80 KB LDS table), grid-stride over (frame, strip, row quad)
             const int64_t items = int64_t(cdiv(rs.w, GMV_XT)) * (rs.h / 4) * nF;
             const int gmvMax = 256;
             const int blocks = int(std::min<int64_t>(gmvMax, (items + GMV_BLOCK - 1) / GMV_BLOCK));
-            hipLaunchKernelGGL(gradMagVecKernel(sp.blocked, a.x86 != nullptr), dim3(blocks), dim3(GMV_BLOCK), 0, c->stream,
+            hipLaunchKernelGGL(gradMagVecKernel(sp.blocked, a.x86 != nullptr), dim3(blocks), dim3(GMV_BLOCK), 0, st,
                 (const float*)(rs.sm + int64_t(p.colorChn) * np), rs.M, rs.O, (const float*)c->d_acos, rs.h, rs.w, p.full, int64_t(d) * np,
                 sp.blocked ? moBlockedFloats(rs.h, rs.w) : np, nF, sp.blocked ? (rs.h + 15) / 16 : 0, a.x86);
         }
@@ -711,7 +749,7 @@ int PyramidRun::gradientChannels(size_t k, const ScalePlan& sp)
             const int rowBlocks = cdiv(rs.h, GM_ROWS), nStrips = cdiv(rs.w, GM_XT);
             const int want = std::max(1, cdiv(1024, rowBlocks * nF));
             const int spb = std::max(8, cdiv(nStrips, want));
-            hipLaunchKernelGGL(k_grad_mag_strip, dim3(rowBlocks, cdiv(nStrips, spb), nF), dim3(GM_ROWS), 0, c->stream,
+            hipLaunchKernelGGL(k_grad_mag_strip, dim3(rowBlocks, cdiv(nStrips, spb), nF), dim3(GM_ROWS), 0, st,
                 (const float*)(rs.sm + int64_t(p.colorChn) * np), rs.M, rs.O, (const float*)c->d_acos, rs.h, rs.w, p.full, int64_t(d) * np, np, spb, x86T(c));
         }
         LAUNCHCHK(c, "k_grad_mag");
@@ -721,202 +759,229 @@ int PyramidRun::gradientChannels(size_t k, const ScalePlan& sp)
     {
         // convTri(M, normRad): x running sums, then the y pass — fused with the channel cells when the level allows it
         // (S then never reaches HBM), else S is written for k_chns
-        if ((rc = launchTri(c, rs.M, rs.U, rs.S, rs.h, rs.w, p.normRad, np, nF, sp.fuseCells ? &a : nullptr, &cellsDone, rs.uFloats, rs.moFloats,
+        if ((rc = launchTri(c, st, rs.M, rs.U, rs.S, rs.h, rs.w, p.normRad, np, nF, sp.fuseCells ? &a : nullptr, &cellsDone, rs.uFloats, rs.moFloats,
                  sp.blocked, sp.triXFused)))
         {
             return rc;
         }
     }
-    return cellsDone ? ACF_HIP_OK : launchChns(c, a, shrink, nF);
+    return cellsDone ? ACF_HIP_OK : launchChns(c, st, a, shrink, nF);
 }
 
 int PyramidRun::joinScales()
 {
     if (scalePar)
     {
-        prof(c, "(end)");
-        c->stream = mainStream;
-        for (size_t k = 1; k < c->real.size(); k++)
-        {
-            HIPCHK(c, hipEventRecord(c->evJoin[k - 1], c->side[k - 1]));
-            HIPCHK(c, hipStreamWaitEvent(mainStream, c->evJoin[k - 1], 0));
-        }
+        prof(c, st, "(end)");
+        st = c->stream;
+        return joinStreams(c, c->real.size() - 1, [this](size_t i) { return c->side[i]; }, st);
     }
     return ACF_HIP_OK;
 }
 
 // ---- approximated levels, smoothing and padding of frames [f0, f0 + nLF) of the batch (chnsPyramid.cpp:385-435)
+// The stage's forms, decided once per call; what depends on the frame offset (the channels, the pyramid, the rank cells' frame) is the launchers'
+int PyramidRun::planLevels(int nLF)
+{
+    LevelsCall& lc = lv;
+    lc = LevelsCall{};
+    lc.nLF = nLF;
+    const bool waveSmooth = p.smooth > 0 && c->finalMaxH <= 64 * LEVEL_MAX_R_REAL && c->opt.fusedLevels != 0;
+    const bool fused = waveSmooth && c->fusedOk && c->opt.fusedLevels == 1;
+    lc.path = fused ? LV_FUSED : waveSmooth ? LV_WAVE_SMOOTH : p.smooth > 0 ? LV_SMOOTH_JOBS : LV_COPY;
+    lc.approxFirst = !fused && c->nApproxDescs > 0;
+    lc.pad = p.pad_h / shrink > 0 || p.pad_w / shrink > 0;
+    lc.pS = p.smooth > 0 ? float(12.0 / p.smooth / (p.smooth + 2.0) - 2.0) : 0.f;
+    if (!waveSmooth)
+    {
+        for (const auto& l : pl.levels)
+        {
+            lc.copyElems = std::max<int64_t>(lc.copyElems, int64_t(pl.nChns) * l.hC * l.wC); // (LV_COPY's grid)
+        }
+        return ACF_HIP_OK;
+    }
+    lc.rawOut = fused && c->opt.taps;
+    lc.jobs = fused ? c->d_levelJobs : c->d_levelJobsRaw;
+    lc.groups = fused ? &c->levelGroups : &c->levelGroupsRaw;
+    lc.nAll = fused ? c->nAllJobs : c->nAllJobsRaw;
+    lc.lvChain = (c->opt.cascadeTurns & 4) ? 0 : 1;
+    lc.lvTurns = (c->opt.cascadeTurns & 6) && fused && c->nAllJobs > 0;
+    // every group is an independent launch (disjoint outputs): on the side streams, forked from st
+    if (!lc.groups->empty())
+    {
+        ensureSide(c);
+        lc.nSide = c->evFork ? c->side.size() : 0;
+    }
+    for (const auto& g : *lc.groups)
+    {
+        if (!levelKernel(g.R, g.mode))
+        {
+            return fail(c, ACF_HIP_E_UNSUPPORTED, "pyramid: level taller than the level kernels' rows per lane");
+        }
+    }
+    // what the levels leave as: floats (always, unless the caller has declared the float pyramid unneeded), and the
+    // cascade's 16-bit rank cells when every level goes through this one launch
+    // (the rank cells have one reader, the tile kernel: a plan or option that routes the cascade elsewhere keeps floats)
+    lc.emitRank = fused && c->levelsEmitRank && rankCellsOn(c, c->cs) && !c->opt.taps && c->opt.cascadeTiles;
+    // (depths other than 2 keep the floats: their queue's overflow path reads them)
+    lc.emitF32 = !(lc.emitRank && !c->opt.keepPyramid && !c->autoLambdas) || (c->cs.tilesR.ok && c->p.treeDepth != 2);
+    if (lc.nAll == 0)
+    {
+        return ACF_HIP_OK;
+    }
+    lc.ldsL = size_t(LEVEL_WAVES) * (lc.emitRank ? LEVEL_ALL_WF_RANK : LEVEL_ALL_WF) * sizeof(float);
+    if (lc.emitRank)
+    {
+        lc.ra.fs = c->cs.pyrRCells;
+        lc.ra.chan = c->cs.d_rankChan;
+        lc.ra.rec = c->cs.d_rankRec;
+        lc.ldsL += size_t(c->cs.rankMaxRec) * sizeof(RankRec);
+    }
+    // column segments for small batches (a level's chain of up to wC column steps is then the launch's duration):
+    // as many as give the launch ~4 waves per SIMD, at most levelSegCap; every hand-over verified on the device
+    int nSegL = 1;
+    if (fused && !c->opt.taps && nLF <= c->levelSegFrames && c->opt.levelSegments != 1 && !c->autoLambdas)
+    {
+        const int64_t wavesL = int64_t(lc.nAll) * pl.nChns * nLF;
+        nSegL = c->opt.levelSegments > 1 ? c->opt.levelSegments : int((4 * 1024 + wavesL - 1) / wavesL); // 0: ~4 waves per SIMD
+        nSegL = std::max(1, std::min(nSegL, c->levelSegCap));
+    }
+    lc.lsa.nSeg = nSegL;
+    lc.lsa.warm = std::max(4, c->opt.levelWarm / 4 * 4);
+    lc.lsa.hMax = c->levelHMax;
+    lc.lsa.nJobs = lc.nAll;
+    lc.lsa.spec = c->d_lvSpec;
+    lc.lsa.tru = c->d_lvTrue;
+    lc.lsa.redo = nullptr;
+    lc.allKernel = levelAllKernel(lc.emitF32, lc.emitRank, nSegL > 1);
+    return allowLds(c, reinterpret_cast<const void*>(lc.allKernel), lc.ldsL);
+}
+
 int PyramidRun::levels(int f0, int nLF)
+{
+    const int rc = planLevels(nLF);
+    return rc ? rc : launchLevels(lv, f0);
+}
+
+int PyramidRun::launchLevels(const LevelsCall& lc, int f0)
 {
     int rc;
     float* const chnsF = c->d_chns + int64_t(f0) * pl.raw_floats;
     float* const pyrF = c->d_pyr + int64_t(f0) * pl.pyr_floats;
     const int nL = int(pl.levels.size());
-    const bool waveSmooth = p.smooth > 0 && c->finalMaxH <= 64 * LEVEL_MAX_R_REAL && c->opt.fusedLevels != 0;
-    const bool fused = waveSmooth && c->fusedOk && c->opt.fusedLevels == 1;
-    if (!fused && c->nApproxDescs > 0)
+    if (lc.approxFirst)
     {
         // ---- approximated levels: one launch, blockIdx.y = level (chnsPyramid.cpp:385-397)
-        prof(c, "k_resample(approx)");
-        hipLaunchKernelGGL(k_resample, dim3(c->approxMaxBlocks, c->nApproxDescs, nLF), dim3(64, 4), 0, c->stream,
+        prof(c, st, "k_resample(approx)");
+        hipLaunchKernelGGL(k_resample, dim3(c->approxMaxBlocks, c->nApproxDescs, lc.nLF), dim3(64, 4), 0, st,
             (const float*)chnsF, chnsF, (const ResampleDesc*)(c->d_descs + c->nImgDescs), (const int32_t*)c->d_it, (const float*)c->d_ft, RS_XT);
         LAUNCHCHK(c, "k_resample(approx)");
     }
-    if (waveSmooth)
+    if (lc.path == LV_FUSED || lc.path == LV_WAVE_SMOOTH)
     {
         // ---- (approximated-scale resample +) smoothing + placement in the padded pyramid: one wave per plane (k_level)
-        const float pS = float(12.0 / p.smooth / (p.smooth + 2.0) - 2.0);
-        float* rawOut = (fused && c->opt.taps) ? chnsF : nullptr;
-        const LevelJob* ljobs = fused ? c->d_levelJobs : c->d_levelJobsRaw;
-        const auto& groups = fused ? c->levelGroups : c->levelGroupsRaw;
-        const ResampleDesc* dd = c->d_descs + c->nImgDescs;
-        const int lvChain = (c->opt.cascadeTurns & 4) ? 0 : 1;
-        const bool lvTurns = (c->opt.cascadeTurns & 6) && fused && c->nAllJobs > 0;
-        if (lvTurns && (rc = turnBegin(c, 1, lvChain)))
+        if (lc.lvTurns && (rc = turnBegin(c, 1, lc.lvChain)))
         {
             return rc;
         }
-        prof(c, fused ? "k_level(fused)" : "k_level(smooth)");
-        // fork: every group is an independent launch (disjoint outputs); biggest planes first
-        if (!groups.empty())
+        prof(c, st, lc.path == LV_FUSED ? "k_level(fused)" : "k_level(smooth)");
+        // the groups' streams fork here: their launches run beside k_level_all; biggest planes first
+        if (lc.nSide && (rc = forkStreams(c, st, c->evFork, lc.nSide, [this](size_t i) { return c->side[i]; })))
         {
-            ensureSide(c);
+            return rc;
         }
-        const size_t nSide = groups.empty() ? 0 : c->side.size();
-        if (nSide && c->evFork)
+        if ((rc = launchLevelAll(lc, f0)) || (rc = launchLevelGroups(lc, f0)))
         {
-            HIPCHK(c, hipEventRecord(c->evFork, c->stream));
-            for (size_t k = 0; k < nSide; k++)
-            {
-                HIPCHK(c, hipStreamWaitEvent(c->side[k], c->evFork, 0));
-            }
-        }
-        const int nAll = fused ? c->nAllJobs : c->nAllJobsRaw;
-        // what the levels leave as: floats (always, unless the caller has declared the float pyramid unneeded), and the
-        // cascade's 16-bit rank cells when every level goes through this one launch
-        // (the rank cells have one reader, the tile kernel: a plan or option that routes the cascade elsewhere keeps floats)
-        const bool emitRank = fused && c->levelsEmitRank && rankCellsOn(c, c->cs) && !c->opt.taps && c->opt.cascadeTiles;
-        // (depths other than 2 keep the floats: their queue's overflow path reads them)
-        const bool emitF32 = !(emitRank && !c->opt.keepPyramid && !c->autoLambdas) || (c->cs.tilesR.ok && c->p.treeDepth != 2);
-        wroteRank = emitRank;
-        wroteF32 = emitF32;
-        if (nAll > 0)
-        {
-            LevelRankArgs ra{};
-            size_t ldsL = size_t(LEVEL_WAVES) * (emitRank ? LEVEL_ALL_WF_RANK : LEVEL_ALL_WF) * sizeof(float);
-            if (emitRank)
-            {
-                ra.out = c->cs.d_pyrR + int64_t(f0) * c->cs.pyrRCells;
-                ra.fs = c->cs.pyrRCells;
-                ra.chan = c->cs.d_rankChan;
-                ra.rec = c->cs.d_rankRec;
-                ldsL += size_t(c->cs.rankMaxRec) * sizeof(RankRec);
-            }
-            // column segments for small batches (a level's chain of up to wC column steps is then the launch's duration):
-            // as many as give the launch ~4 waves per SIMD, at most levelSegCap; every hand-over verified on the device
-            int nSegL = 1;
-            const int warmL = std::max(4, c->opt.levelWarm / 4 * 4);
-            if (fused && !c->opt.taps && nLF <= c->levelSegFrames && c->opt.levelSegments != 1 && !c->autoLambdas)
-            {
-                const int64_t wavesL = int64_t(nAll) * pl.nChns * nLF;
-                nSegL = c->opt.levelSegments > 1 ? c->opt.levelSegments : int((4 * 1024 + wavesL - 1) / wavesL); // 0: ~4 waves per SIMD
-                nSegL = std::max(1, std::min(nSegL, c->levelSegCap));
-            }
-            LevelSegArgs lsa{};
-            lsa.nSeg = nSegL;
-            lsa.warm = warmL;
-            lsa.hMax = c->levelHMax;
-            lsa.nJobs = nAll;
-            lsa.spec = c->d_lvSpec;
-            lsa.tru = c->d_lvTrue;
-            lsa.redo = nullptr;
-            const LevelAllKernel lk = levelAllKernel(emitF32, emitRank, nSegL > 1);
-            if ((rc = allowLds(c, reinterpret_cast<const void*>(lk), ldsL)))
-            {
-                return rc;
-            }
-            auto launchAll = [&](int nz) {
-                hipLaunchKernelGGL(lk, dim3(pl.nChns, cdiv(nLF, LEVEL_WAVES), nz), dim3(64 * LEVEL_WAVES), ldsL, c->stream, (const float*)chnsF, pyrF, rawOut,
-                    ljobs, dd, (const int32_t*)c->d_it, (const float*)c->d_ft, pl.nChns, pl.raw_floats, pl.pyr_floats, pS, c->d_dump, nLF, ra, lsa);
-            };
-            launchAll(nAll * nSegL);
-            if (nSegL > 1)
-            {
-                // the segments' hand-overs, bit for bit; level planes with a difference are recomputed as one chain
-                hipLaunchKernelGGL(k_level_verify, dim3(nAll * nSegL, pl.nChns, nLF), dim3(64), 0, c->stream, (const float*)c->d_lvSpec,
-                    (const float*)c->d_lvTrue, ljobs, lsa, pl.nChns, c->d_lvRedo, c->opt.smoothForceRedo);
-                if ((rc = countRepairs(c, c->d_lvRedo, size_t(nLF) * nAll * pl.nChns, 2)))
-                {
-                    return rc;
-                }
-                lsa.nSeg = 1;
-                lsa.redo = c->d_lvRedo;
-                launchAll(nAll);
-            }
-            LAUNCHCHK(c, "k_level_all");
-            if (lvTurns && (rc = turnEnd(c, 1, lvChain)))
-            {
-                return rc;
-            }
-        }
-        size_t gi = 0;
-        for (auto git = groups.rbegin(); git != groups.rend(); ++git, ++gi)
-        {
-            const auto& g = *git;
-            hipStream_t lst = (nSide && c->evFork) ? c->side[gi % nSide] : c->stream;
-            dim3 grid(pl.nChns, g.count, cdiv(nLF, LEVEL_WAVES)), block(64 * LEVEL_WAVES);
-            const LevelKernel lk = levelKernel(g.R, g.mode);
-            if (!lk)
-            {
-                return fail(c, ACF_HIP_E_UNSUPPORTED, "pyramid: level taller than the level kernels' rows per lane");
-            }
-            hipLaunchKernelGGL(lk, grid, block, 0, lst, (const float*)chnsF, pyrF, rawOut, ljobs + g.first, dd, (const int32_t*)c->d_it, (const float*)c->d_ft,
-                pl.nChns, pl.raw_floats, pl.pyr_floats, pS, c->d_dump, nLF);
-            LAUNCHCHK(c, "k_level");
-        }
-        if (nSide && c->evFork)
-        {
-            for (size_t k = 0; k < std::min(nSide, groups.size()); k++)
-            {
-                HIPCHK(c, hipEventRecord(c->evJoin[k], c->side[k]));
-                HIPCHK(c, hipStreamWaitEvent(c->stream, c->evJoin[k], 0));
-            }
+            return rc;
         }
     }
-    else if (p.smooth > 0)
+    else if (lc.path == LV_SMOOTH_JOBS)
     {
         // ---- smooth every plane of every level into the fused, padded pyramid (chnsPyramid.cpp:399-435)
-        const float pS = float(12.0 / p.smooth / (p.smooth + 2.0) - 2.0);
-        if ((rc = launchSmooth(c, chnsF, pyrF, c->d_finalJobs, nL, pl.nChns, c->finalMaxH, pl.raw_floats, pl.pyr_floats, nLF, pS, true)))
+        if ((rc = launchSmooth(c, st, chnsF, pyrF, c->d_finalJobs, nL, pl.nChns, c->finalMaxH, pl.raw_floats, pl.pyr_floats, lc.nLF, lc.pS, true)))
         {
             return rc;
         }
     }
     else
     {
-        int64_t maxE = 0;
-        for (const auto& l : pl.levels)
-        {
-            maxE = std::max<int64_t>(maxE, int64_t(pl.nChns) * l.hC * l.wC);
-        }
-        hipLaunchKernelGGL(k_copy_planes, dim3(cdiv(maxE, 256), nL, nLF), dim3(256), 0, c->stream, (const float*)chnsF, pyrF,
+        hipLaunchKernelGGL(k_copy_planes, dim3(cdiv(lc.copyElems, 256), nL, lc.nLF), dim3(256), 0, st, (const float*)chnsF, pyrF,
             (const SmoothJob*)c->d_finalJobs, pl.raw_floats, pl.pyr_floats);
         LAUNCHCHK(c, "k_copy_planes(final)");
     }
-    if (p.pad_h / shrink > 0 || p.pad_w / shrink > 0)
+    return lc.pad ? padLevels(lc, f0) : ACF_HIP_OK;
+}
+
+// the leading nAll jobs in one launch (k_level_all); in column segments: launch, verify, repair
+int PyramidRun::launchLevelAll(const LevelsCall& lc, int f0)
+{
+    int rc;
+    if (lc.nAll == 0)
     {
-        prof(c, "k_pad_reflect");
-        if (wroteF32)
-        {
-            hipLaunchKernelGGL(k_pad_reflect<float>, dim3(cdiv(c->padMaxElems, 256), nL, nLF), dim3(256), 0, c->stream, pyrF, (const PadJob*)c->d_padJobs, pl.pyr_floats);
-        }
-        if (wroteRank)
-        {
-            hipLaunchKernelGGL(k_pad_reflect<uint16_t>, dim3(cdiv(c->padMaxElems, 256), nL, nLF), dim3(256), 0, c->stream,
-                c->cs.d_pyrR + int64_t(f0) * c->cs.pyrRCells, (const PadJob*)c->d_padJobsR, c->cs.pyrRCells);
-        }
-        LAUNCHCHK(c, "k_pad_reflect");
+        return ACF_HIP_OK;
     }
+    float* const chnsF = c->d_chns + int64_t(f0) * pl.raw_floats;
+    LevelRankArgs ra = lc.ra;
+    if (lc.emitRank)
+    {
+        ra.out = c->cs.d_pyrR + int64_t(f0) * c->cs.pyrRCells;
+    }
+    LevelSegArgs lsa = lc.lsa;
+    auto launchAll = [&](int nz) {
+        hipLaunchKernelGGL(lc.allKernel, dim3(pl.nChns, cdiv(lc.nLF, LEVEL_WAVES), nz), dim3(64 * LEVEL_WAVES), lc.ldsL, st, (const float*)chnsF,
+            c->d_pyr + int64_t(f0) * pl.pyr_floats, lc.rawOut ? chnsF : nullptr, lc.jobs, (const ResampleDesc*)(c->d_descs + c->nImgDescs),
+            (const int32_t*)c->d_it, (const float*)c->d_ft, pl.nChns, pl.raw_floats, pl.pyr_floats, lc.pS, c->d_dump, lc.nLF, ra, lsa);
+    };
+    launchAll(lc.nAll * lsa.nSeg);
+    if (lsa.nSeg > 1)
+    {
+        // the segments' hand-overs, bit for bit; level planes with a difference are recomputed as one chain
+        hipLaunchKernelGGL(k_level_verify, dim3(lc.nAll * lsa.nSeg, pl.nChns, lc.nLF), dim3(64), 0, st, (const float*)c->d_lvSpec,
+            (const float*)c->d_lvTrue, lc.jobs, lsa, pl.nChns, c->d_lvRedo, c->opt.smoothForceRedo);
+        if ((rc = countRepairs(c, st, c->d_lvRedo, size_t(lc.nLF) * lc.nAll * pl.nChns, 2)))
+        {
+            return rc;
+        }
+        lsa.nSeg = 1;
+        lsa.redo = c->d_lvRedo;
+        launchAll(lc.nAll);
+    }
+    LAUNCHCHK(c, "k_level_all");
+    return lc.lvTurns ? turnEnd(c, 1, lc.lvChain) : ACF_HIP_OK;
+}
+
+// the other jobs in groups of equal (rows per lane, mode), one launch each (k_level): round-robin over the forked streams, then joined
+int PyramidRun::launchLevelGroups(const LevelsCall& lc, int f0)
+{
+    float* const chnsF = c->d_chns + int64_t(f0) * pl.raw_floats;
+    size_t gi = 0;
+    for (auto git = lc.groups->rbegin(); git != lc.groups->rend(); ++git, ++gi)
+    {
+        const auto& g = *git;
+        hipStream_t lst = lc.nSide ? c->side[gi % lc.nSide] : st;
+        dim3 grid(pl.nChns, g.count, cdiv(lc.nLF, LEVEL_WAVES)), block(64 * LEVEL_WAVES);
+        hipLaunchKernelGGL(levelKernel(g.R, g.mode), grid, block, 0, lst, (const float*)chnsF, c->d_pyr + int64_t(f0) * pl.pyr_floats,
+            lc.rawOut ? chnsF : nullptr, lc.jobs + g.first, (const ResampleDesc*)(c->d_descs + c->nImgDescs), (const int32_t*)c->d_it, (const float*)c->d_ft,
+            pl.nChns, pl.raw_floats, pl.pyr_floats, lc.pS, c->d_dump, lc.nLF);
+        LAUNCHCHK(c, "k_level");
+    }
+    return joinStreams(c, std::min(lc.nSide, lc.groups->size()), [this](size_t i) { return c->side[i]; }, st);
+}
+
+int PyramidRun::padLevels(const LevelsCall& lc, int f0)
+{
+    const dim3 grid(cdiv(c->padMaxElems, 256), int(pl.levels.size()), lc.nLF);
+    prof(c, st, "k_pad_reflect");
+    if (lc.emitF32)
+    {
+        hipLaunchKernelGGL(k_pad_reflect<float>, grid, dim3(256), 0, st, c->d_pyr + int64_t(f0) * pl.pyr_floats, (const PadJob*)c->d_padJobs, pl.pyr_floats);
+    }
+    if (lc.emitRank)
+    {
+        hipLaunchKernelGGL(k_pad_reflect<uint16_t>, grid, dim3(256), 0, st, c->cs.d_pyrR + int64_t(f0) * c->cs.pyrRCells, (const PadJob*)c->d_padJobsR,
+            c->cs.pyrRCells);
+    }
+    LAUNCHCHK(c, "k_pad_reflect");
     return ACF_HIP_OK;
 }
 
@@ -929,15 +994,19 @@ int PyramidRun::levelsWithImageLambdas()
     // oracle uses, then the approximated levels frame by frame with that frame's gains written into the descriptors
     // (stream-ordered copies).  A fallback path for models that ship without lambdas: correctness first — it
     // synchronises once per batch and launches per frame.
-    prof(c, "k_plane_sums");
+    if ((rc = planLevels(1))) // (one plan serves every frame's launches)
+    {
+        return rc;
+    }
+    prof(c, st, "k_plane_sums");
     const int lv0 = pl.lambdaLevel[0], lv1 = pl.lambdaLevel[1];
     SumJob j0{ pl.raw_off[size_t(lv0)], pl.levels[size_t(lv0)].hC * pl.levels[size_t(lv0)].wC, 0 };
     SumJob j1{ pl.raw_off[size_t(lv1)], pl.levels[size_t(lv1)].hC * pl.levels[size_t(lv1)].wC, 0 };
-    hipLaunchKernelGGL(k_plane_sums, dim3(pl.nChns, 2, nF), dim3(256), 0, c->stream, (const float*)c->d_chns, pl.raw_floats, j0, j1, pl.nChns, c->d_planeSums);
+    hipLaunchKernelGGL(k_plane_sums, dim3(pl.nChns, 2, nF), dim3(256), 0, st, (const float*)c->d_chns, pl.raw_floats, j0, j1, pl.nChns, c->d_planeSums);
     LAUNCHCHK(c, "k_plane_sums");
     std::vector<double> sums(size_t(nF) * 2 * pl.nChns);
-    HIPCHK(c, hipMemcpyAsync(sums.data(), c->d_planeSums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(sums.data(), c->d_planeSums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
     const int nColorL = p.colorEnabled ? d : 0, nMagL = p.gradMagEnabled ? 1 : 0, nHistL = p.gradHistEnabled ? p.nOrients : 0;
     const int nTypeCh[3] = { nColorL, nMagL, nHistL };
     // one copy of the approximated levels' descriptors per frame: each stays untouched until its stream-ordered upload is done
@@ -987,14 +1056,14 @@ int PyramidRun::levelsWithImageLambdas()
         }
         if (!descs.empty())
         {
-            HIPCHK(c, hipMemcpyAsync(c->d_descs + c->nImgDescs, descs.data(), descs.size() * sizeof(ResampleDesc), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->d_descs + c->nImgDescs, descs.data(), descs.size() * sizeof(ResampleDesc), hipMemcpyHostToDevice, st));
         }
-        if ((rc = levels(f, 1)))
+        if ((rc = launchLevels(lv, f)))
         {
             return rc;
         }
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // descsAll is read by the uploads above
+    HIPCHK(c, hipStreamSynchronize(st)); // descsAll is read by the uploads above
     return ACF_HIP_OK;
 }
 
@@ -1067,11 +1136,11 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
     {
         return rc;
     }
-    prof(c, "(end)");
+    prof(c, c->stream, "(end)");
     c->lastBatch = nF;
     c->pyramidValid = true;
-    c->ranksValid = run.wroteRank;   // else the cascade converts the float pyramid first (k_rank)
-    c->floatPyramid = run.wroteF32;
+    c->ranksValid = run.lv.emitRank;   // else the cascade converts the float pyramid first (k_rank)
+    c->floatPyramid = run.lv.emitF32;
     return ACF_HIP_OK;
 }
 } // namespace

@@ -173,7 +173,7 @@ static StripPlan stripPlan(const ResampleDesc& da, const ResampleDesc* db, Table
 }
 
 // k_resample_strip for one output (descB < 0) or two outputs of one source
-static void launchStrip(acf_hip_ctx* c, const StripPlan& sp, const ResampleDesc* d_descs, int descA, int descB, int nplanes, const float* src, float* dstA,
+static void launchStrip(acf_hip_ctx* c, hipStream_t st, const StripPlan& sp, const ResampleDesc* d_descs, int descA, int descB, int nplanes, const float* src, float* dstA,
     float* dstB, const int32_t* d_it, const float* d_ft, int nF)
 {
     const bool pair = descB >= 0;
@@ -220,19 +220,19 @@ static void launchStrip(acf_hip_ctx* c, const StripPlan& sp, const ResampleDesc*
     const bool slow = sp.slowRows > 0;
     if (pair && slow)
     {
-        hipLaunchKernelGGL((k_resample_strip<true, true>), sgrid, dim3(RS_NT), ldsS, c->stream, sa);
+        hipLaunchKernelGGL((k_resample_strip<true, true>), sgrid, dim3(RS_NT), ldsS, st, sa);
     }
     else if (pair)
     {
-        hipLaunchKernelGGL((k_resample_strip<true, false>), sgrid, dim3(RS_NT), ldsS, c->stream, sa);
+        hipLaunchKernelGGL((k_resample_strip<true, false>), sgrid, dim3(RS_NT), ldsS, st, sa);
     }
     else if (slow)
     {
-        hipLaunchKernelGGL((k_resample_strip<false, true>), sgrid, dim3(RS_NT), ldsS, c->stream, sa);
+        hipLaunchKernelGGL((k_resample_strip<false, true>), sgrid, dim3(RS_NT), ldsS, st, sa);
     }
     else
     {
-        hipLaunchKernelGGL((k_resample_strip<false, false>), sgrid, dim3(RS_NT), ldsS, c->stream, sa);
+        hipLaunchKernelGGL((k_resample_strip<false, false>), sgrid, dim3(RS_NT), ldsS, st, sa);
     }
 }
 

@@ -466,6 +466,34 @@ def test_graph_replay_matches_plain_launches(oracle, scale_streams):
     det.close()
 
 
+def test_profile_markers_follow_their_scale_streams():
+    """Option profile: a marker is recorded on the stream its launch goes to, and a kernel's time is the span to the next marker of that
+    stream.  With the real scales on their own streams (scale_streams=1) every marker must still find its successor: the same kernel
+    names with the same launch counts as on one stream, every time finite and not negative, and the same detections."""
+    import math
+    import torch
+    from acf_amd.detector import HipDetector
+    H, W = 480, 640
+    model = synth.make_model(seed=3, name="FACE80", nTrees=256)
+    frames = np.stack([synth.make_frame(301 + i, H, W, "luv") for i in range(2)])
+    dev = torch.from_numpy(frames).cuda()
+    seen = {}
+    for scale_streams in (1, 0):
+        det = HipDetector(model, H, W, 3, max_batch=2, max_hits=1 << 14)
+        det.set_option("scale_streams", scale_streams)
+        det.set_option("profile", 1)
+        det.run(dev)
+        prof = det.profile()
+        print(scale_streams, prof)
+        assert prof, scale_streams
+        for name, (ms, launches) in prof.items():
+            assert math.isfinite(ms) and ms >= 0 and launches > 0, (scale_streams, name, ms, launches)
+        seen[scale_streams] = ({k: v[1] for k, v in prof.items()}, [tuple(a.tobytes() for a in det.detections(f)) for f in range(2)])
+        det.close()
+    assert seen[1][0] == seen[0][0]
+    assert seen[1][1] == seen[0][1] and sum(len(d[0]) for d in seen[0][1]) > 0
+
+
 def test_graph_replay_sees_new_content_in_the_same_buffer(oracle):
     """The documented use of option graph: new frame content copied into the SAME device buffer between replays.  Frames with
     different detection counts, detections() after every run (which caches the counts on the host): a replay must not hand out
