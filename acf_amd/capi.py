@@ -231,6 +231,8 @@ def load():
         "acf_hip_op_acf_detect1_u8": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(Hit), C.c_int, C.POINTER(C.c_int)], C.c_int),
         "acf_hip_thrs_u8": ([fp, C.c_int, C.c_void_p], C.c_int),
         "acf_hip_op_evaluate": ([ctx, fp, C.c_int, C.c_int, C.c_int, C.c_double, fp], C.c_int),
+        "acf_hip_evaluate_crops": ([ctx, C.POINTER(Params), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p], C.c_int),
+        "acf_hip_evaluate_crops_u8": ([ctx, C.POINTER(Params), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p], C.c_int),
     }
     for name, (argtypes, restype) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -251,6 +253,7 @@ DECLARED_SYMBOLS = [
     "acf_hip_export_detections", "acf_hip_synchronize", "acf_hip_get_repairs", "acf_hip_profile_get", "acf_hip_read_level", "acf_hip_read_rank_level", "acf_hip_rank_cells_host", "acf_hip_read_tap",
     "acf_hip_op_rgb_convert", "acf_hip_op_conv_tri", "acf_hip_op_gradient_mag", "acf_hip_selftest_gradmag", "acf_hip_set_x86_tables", "acf_hip_selftest_x86", "acf_hip_chns_compute", "acf_hip_op_gradient_hist",
     "acf_hip_op_im_resample", "acf_hip_op_acf_detect1", "acf_hip_op_acf_detect1_u8", "acf_hip_thrs_u8", "acf_hip_op_evaluate",
+    "acf_hip_evaluate_crops", "acf_hip_evaluate_crops_u8",
 ]
 
 

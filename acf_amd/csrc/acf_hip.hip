@@ -379,6 +379,15 @@ struct acf_hip_ctx
     } yuv;
     uint8_t* d_yuvRgb = nullptr; // k_yuv420_to_rgb8's tight RGB frames (in front of the input resize; fallback yuv_unfused)
     size_t yuvRgbBytes = 0;
+    // acf_hip_evaluate_crops: the classifier on the device without a plan (not one of the plan's buffers: uploaded at the first call
+    // after acf_hip_set_model, freed by the next one and by acf_hip_destroy); fidMax: the largest feature id a tree walk can read
+    struct CropModel
+    {
+        uint32_t *fids = nullptr, *child = nullptr;
+        float *thrs = nullptr, *hs = nullptr;
+        uint32_t fidMax = 0;
+        bool valid = false;
+    } crop;
 };
 
 // the ONE statement of "the cascade state has rank cells and option rank_cells is on"; each reader adds its own terms
@@ -1321,9 +1330,30 @@ static void dropGraph(acf_hip_ctx* c)
     c->plainRuns = 0; // the next run is a plain one again (it may allocate: NMS buffers, side streams)
 }
 
+// acf_hip_evaluate_crops' copy of the classifier (crops_run.hip.h: ensureCropModel) goes with the model it was made from
+static void dropCropModel(acf_hip_ctx* c)
+{
+    if (!c)
+    {
+        return;
+    }
+    auto& m = c->crop;
+    if (m.fids || m.thrs || m.hs || m.child)
+    {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream); // (a call in flight may be reading it)
+        (void)hipFree(m.fids);
+        (void)hipFree(m.thrs);
+        (void)hipFree(m.hs);
+        (void)hipFree(m.child);
+    }
+    m = acf_hip_ctx::CropModel();
+}
+
 int acf_hip_destroy(acf_hip_ctx* c)
 {
     dropGraph(c);
+    dropCropModel(c);
     if (c)
     {
         for (acf_hip_ctx* k : c->kids)
@@ -1518,6 +1548,7 @@ int acf_hip_plan_levels(const acf_hip_params* p, int h, int w, int d, acf_hip_le
 int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
 {
     dropGraph(c);
+    dropCropModel(c);
     if (c)
     {
         for (acf_hip_ctx* k : c->kids)
@@ -2595,5 +2626,7 @@ int acf_hip_set_nms(acf_hip_ctx* c, const acf_hip_nms_params* q)
 #include "readback.hip.h" // fetchCounts, readRecords and the get_* entries, export_detections, read_level / _rank_level / _tap, profile_get
 
 #include "ops.hip.h"      // the single-operator entries (acf_hip_op_*, acf_hip_chns_compute), the x86 tables and the self-tests
+
+#include "crops_run.hip.h" // acf_hip_evaluate_crops / _u8: Detector::evaluate(const cv::Mat&) for a batch (k_crop_score, or staged)
 
 } // extern "C"

@@ -2541,9 +2541,42 @@ __global__ void __launch_bounds__(256) k_tail_scan(TileArgs a)
     }
 }
 
+// The leaf tree t of the classifier reaches for the window at (0, 0) of a channel buffer [..][wP][hP] (area = hP * wP): evaluate(),
+// acfDetect1.cpp:113-138, with getChild (:100-107) or, depth 0, the child-pointer walk (:146-155).  Returns the node index into hs[].
+__device__ __forceinline__ uint32_t tree_leaf(const float* chns, int area, int hP, int mH, int mW, const uint32_t* __restrict__ fids,
+    const float* __restrict__ thrs, const uint32_t* __restrict__ child, int nTreeNodes, int depth, int t)
+{
+    const uint32_t offset = uint32_t(t) * uint32_t(nTreeNodes);
+    uint32_t k = offset, k0 = depth == 0 ? k : 0u;
+    if (depth > 0)
+    {
+        for (int i = 0; i < depth; i++)
+        {
+            const uint32_t f = fids[k];
+            const uint32_t z = f / uint32_t(mW * mH), cc = (f / uint32_t(mH)) % uint32_t(mW), rr = f % uint32_t(mH); // cids[], :390-406
+            const float ftr = chns[z * uint32_t(area) + cc * uint32_t(hP) + rr];
+            k = (ftr < thrs[k]) ? 1u : 2u;
+            k0 = k += k0 * 2u;
+            k += offset;
+        }
+    }
+    else
+    {
+        while (child[k])
+        {
+            const uint32_t f = fids[k];
+            const uint32_t z = f / uint32_t(mW * mH), cc = (f / uint32_t(mH)) % uint32_t(mW), rr = f % uint32_t(mH);
+            const float ftr = chns[z * uint32_t(area) + cc * uint32_t(hP) + rr];
+            k = (ftr < thrs[k]) ? 1u : 0u;
+            k0 = k = child[k0] - k + offset;
+        }
+    }
+    return k;
+}
+
 // Detector::evaluate(const MatP&, ...) (acfDetect1.cpp:337-342): the score of the single window at (0, 0), trees added in
-// order until h <= cascThr (the reference sets cascThr = 0 for this call) — evaluate(), :113-138, with getChild (:100-107) or
-// the child-pointer walk (:146-155).  One thread: this is a probe, not a hot path.
+// order until h <= cascThr (the reference sets cascThr = 0 for this call).  One thread: this is a probe, not a hot path (the
+// batched forms are k_evaluate_windows and k_crop_score, kernels_crops.hip.h).
 __global__ void k_evaluate_window(const float* __restrict__ chns, int hP, int wP, int mH, int mW, const uint32_t* __restrict__ fids,
     const float* __restrict__ thrs, const float* __restrict__ hs, const uint32_t* __restrict__ child, int nTrees, int nTreeNodes, int depth,
     float cascThr, float* __restrict__ score)
@@ -2552,36 +2585,10 @@ __global__ void k_evaluate_window(const float* __restrict__ chns, int hP, int wP
     {
         return;
     }
-    const int area = hP * wP;
     float h = 0.f;
     for (int t = 0; t < nTrees; t++)
     {
-        const uint32_t offset = uint32_t(t) * uint32_t(nTreeNodes);
-        uint32_t k = offset, k0 = depth == 0 ? k : 0u;
-        if (depth > 0)
-        {
-            for (int i = 0; i < depth; i++)
-            {
-                const uint32_t f = fids[k];
-                const uint32_t z = f / uint32_t(mW * mH), cc = (f / uint32_t(mH)) % uint32_t(mW), rr = f % uint32_t(mH); // cids[], :390-406
-                const float ftr = chns[z * uint32_t(area) + cc * uint32_t(hP) + rr];
-                k = (ftr < thrs[k]) ? 1u : 2u;
-                k0 = k += k0 * 2u;
-                k += offset;
-            }
-        }
-        else
-        {
-            while (child[k])
-            {
-                const uint32_t f = fids[k];
-                const uint32_t z = f / uint32_t(mW * mH), cc = (f / uint32_t(mH)) % uint32_t(mW), rr = f % uint32_t(mH);
-                const float ftr = chns[z * uint32_t(area) + cc * uint32_t(hP) + rr];
-                k = (ftr < thrs[k]) ? 1u : 0u;
-                k0 = k = child[k0] - k + offset;
-            }
-        }
-        h += hs[k];
+        h += hs[tree_leaf(chns, hP * wP, hP, mH, mW, fids, thrs, child, nTreeNodes, depth, t)];
         if (h <= cascThr)
         {
             break;

@@ -87,18 +87,9 @@ __global__ void __launch_bounds__(256) k_rgb2gray(const float* __restrict__ in, 
 }
 
 // Replicate one plane to three (chnsPyramid.cpp:242-243), colorSpace "orig".
-// rgb2hsv (toolbox/rgbConvertMex.cpp:194-238), nrm = 1: three planes in, H, S, V out.  IEEE divisions; h * float(1 / 6.0).
-__global__ void __launch_bounds__(256) k_rgb2hsv(const float* __restrict__ in, float* __restrict__ out, int n, int64_t in_fs, int64_t out_fs)
+// rgb2hsv (toolbox/rgbConvertMex.cpp:194-238), nrm = 1: one pixel.  IEEE divisions; h * float(1 / 6.0).
+__device__ __forceinline__ void hsv_px(float r, float g, float b, float& h, float& s, float& v)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n)
-    {
-        return;
-    }
-    const float* I = in + int64_t(blockIdx.z) * in_fs;
-    float* J = out + int64_t(blockIdx.z) * out_fs;
-    const float r = I[i], g = I[n + i], b = I[2 * int64_t(n) + i];
-    float h, s, v;
     if (r == g && g == b)
     {
         h = 0.f;
@@ -134,6 +125,21 @@ __global__ void __launch_bounds__(256) k_rgb2hsv(const float* __restrict__ in, f
         s = 1 - minv / maxv;
         v = maxv * 1.0f;
     }
+}
+
+// three planes in, H, S, V out
+__global__ void __launch_bounds__(256) k_rgb2hsv(const float* __restrict__ in, float* __restrict__ out, int n, int64_t in_fs, int64_t out_fs)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+    {
+        return;
+    }
+    const float* I = in + int64_t(blockIdx.z) * in_fs;
+    float* J = out + int64_t(blockIdx.z) * out_fs;
+    const float r = I[i], g = I[n + i], b = I[2 * int64_t(n) + i];
+    float h, s, v;
+    hsv_px(r, g, b, h, s, v);
     J[i] = h;
     J[n + i] = s;
     J[2 * int64_t(n) + i] = v;

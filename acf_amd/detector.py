@@ -400,6 +400,47 @@ class HipDetector:
         self._chk(self.lib.acf_hip_op_evaluate(self.ctx, capi.fptr(chns), hP, wP, nC, float(cascThr), capi.fptr(out)))
         return out[0]
 
+    # ---- Detector::evaluate(const cv::Mat&) for a batch of crops (device in, device out; no plan)
+    def _params_of(self, chns):
+        if chns is None:
+            return None, None
+        prm, keep = capi.make_params(chns)
+        return C.byref(prm), (prm, keep)
+
+    @staticmethod
+    def _to_device(x, dtype):
+        import torch
+        if isinstance(x, np.ndarray):
+            return torch.from_numpy(np.array(x, dtype=dtype, order="C")).cuda()
+        return x
+
+    def evaluate_crops(self, crops, chns=None, cascThr=0.0):
+        """crops: float32 [n][d][w][h] (numpy, or a torch CUDA tensor), d = 1 or 3; chns: a dict like synth.make_model's whose Chns
+        fields are read, or None for the context's model.  Returns the scores, float32 [n] (acf_hip_evaluate_crops)."""
+        import torch
+        t = self._to_device(crops, np.float32)
+        n, d, w, h = t.shape
+        out = torch.empty(max(n, 1), dtype=torch.float32, device=t.device)
+        pp, keep = self._params_of(chns)
+        self._chk(self.lib.acf_hip_evaluate_crops(self.ctx, pp, C.c_void_p(_dev_ptr(t) if n else 0), n, h, w, d, float(cascThr), C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return out[:n].cpu().numpy()
+
+    def evaluate_crops_u8(self, crops, pix, row_stride=0, chns=None, cascThr=0.0, h=None, w=None):
+        """crops: uint8 [n][h][w][cpp] ([n][h][w] for PIX_GRAY), or — with padded rows — [n][h * row_stride] with h and w given; numpy
+        or a torch CUDA tensor.  Returns the scores, float32 [n] (acf_hip_evaluate_crops_u8)."""
+        import torch
+        t = self._to_device(crops, np.uint8)
+        n = t.shape[0]
+        if h is None or w is None:
+            h, w = t.shape[1], t.shape[2]
+        out = torch.empty(max(n, 1), dtype=torch.float32, device=t.device)
+        pp, keep = self._params_of(chns)
+        self._chk(self.lib.acf_hip_evaluate_crops_u8(self.ctx, pp, C.c_void_p(_dev_ptr_u8(t) if n else 0), n, h, w, pix, row_stride, float(cascThr),
+                                                     C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return out[:n].cpu().numpy()
+
 
 class DetectorPool:
     """N detector contexts on one GPU, each with its own HIP stream, plan and buffers; batches are handed to them in turn.

@@ -1253,6 +1253,88 @@ void HipDetector::computeChannels(const MatP& Ip, MatP& Ip2, const MatLoggerType
     }
 }
 
+// ---- Detector::evaluate(const cv::Mat&) (ACF.cpp:123-133)
+std::vector<float> HipDetector::evaluateCrops(const std::vector<MatP>& crops, const Options::Pyramid::Chns* pChns, double cascThr)
+{
+    if (!m_good)
+    {
+        throw Exception(ACF_HIP_E_NOMODEL, "evaluate: no model");
+    }
+    ensureModel();
+    const int n = int(crops.size());
+    if (n == 0)
+    {
+        return {};
+    }
+    const int w = crops[0].rows(), h = crops[0].cols(), d = crops[0].channels();
+    const size_t per = size_t(d) * w * h, bytes = (per + 1) * size_t(n) * sizeof(float);
+    // page-locked memory is the device's to read and write: the crops and their scores go through the detector's pinned scratch
+    if (bytes > m_pinBytes)
+    {
+        pinnedFree(m_pin);
+        m_pin = pinnedAlloc(bytes);
+        m_pinBytes = bytes;
+    }
+    float* in = static_cast<float*>(m_pin);
+    float* out = in + per * size_t(n);
+    for (int i = 0; i < n; i++)
+    {
+        if (crops[size_t(i)].rows() != w || crops[size_t(i)].cols() != h || crops[size_t(i)].channels() != d)
+        {
+            throw Exception(ACF_HIP_E_INVALID, "evaluate: the crops of a batch must have one size");
+        }
+        std::memcpy(in + per * size_t(i), crops[size_t(i)].data(), per * sizeof(float));
+    }
+    acf_hip_params p;
+    if (pChns)
+    {
+        chnsParams(*pChns, p);
+    }
+    check(m_api->acf_hip_evaluate_crops(m_ctx, pChns ? &p : nullptr, in, n, h, w, d, cascThr, out), "acf_hip_evaluate_crops");
+    check(m_api->acf_hip_synchronize(m_ctx), "acf_hip_synchronize");
+    return std::vector<float>(out, out + n);
+}
+
+std::vector<float> HipDetector::evaluate(const std::vector<MatP>& crops)
+{
+    const Options::Pyramid::Chns dfs; // ACF.cpp:185-232: the toolbox defaults (computeChannels)
+    return evaluateCrops(crops, &dfs, 0.0);
+}
+
+float HipDetector::evaluate(const MatP& Ip)
+{
+    return evaluate(std::vector<MatP>(1, Ip))[0];
+}
+
+std::vector<float> HipDetector::evaluate(const std::vector<const float*>& rgb, int rows, int cols)
+{
+    // ACF.cpp:135-141: transpose unless the caller already did, split interleaved -> planar (MatP.cpp:18-34)
+    const int W = m_isTranspose ? rows : cols, H = m_isTranspose ? cols : rows;
+    std::vector<MatP> crops;
+    for (const float* I : rgb)
+    {
+        MatP Ip(W, H, 3);
+        for (int z = 0; z < 3; z++)
+        {
+            float* P = Ip[z];
+            for (int r = 0; r < rows; r++)
+            {
+                for (int c = 0; c < cols; c++)
+                {
+                    P[m_isTranspose ? size_t(r) * cols + c : size_t(c) * rows + r] = I[(size_t(r) * cols + c) * 3 + z];
+                }
+            }
+        }
+        crops.push_back(Ip);
+    }
+    return evaluate(crops);
+}
+
+float HipDetector::evaluate(const float* rgb, int rows, int cols)
+{
+    return evaluate(std::vector<const float*>(1, rgb), rows, cols)[0];
+}
+
 // ---- the reference's arithmetic (option "arith")
 namespace
 {

@@ -344,6 +344,16 @@ public:
     // Detector::evaluate (ACF.h:543-544, acfDetect1.cpp:337-342): score of the window at (0,0) of a fused channel buffer, trees added
     // until the score drops to 0 or below (the reference fixes cascThr = 0 for this probe)
     float evaluate(const MatP& chns, int shrink, const Size& modelDsPad, int stride);
+    // float Detector::evaluate(const cv::Mat& I) const (ACF.h:543, ACF.cpp:123-133): the score of an image of the window's size —
+    // computeChannels' toolbox-default channels whatever the model's Chns say, then the window at (0, 0) with cascThr 0 — on the
+    // device in one call (acf_hip_evaluate_crops).  The image types operator() takes: a transposed planar MatP, or interleaved RGB
+    // f32, upright unless setIsTranspose(true).  The vector forms score a batch of equally sized crops.
+    float evaluate(const MatP& IpTranspose);
+    float evaluate(const float* rgbInterleaved, int rows, int cols);
+    std::vector<float> evaluate(const std::vector<MatP>& cropsTranspose);
+    std::vector<float> evaluate(const std::vector<const float*>& rgbInterleaved, int rows, int cols);
+    // ... with the channel options and cascThr of the caller's choice (pChns null: the model's own): the C entry's full argument list
+    std::vector<float> evaluateCrops(const std::vector<MatP>& cropsTranspose, const Options::Pyramid::Chns* pChns, double cascThr);
     // bbNms.cpp:229-304 (max / maxg / none), ObjectDetector.cpp:28-44
     static int bbNms(const DetectionVec& bbsIn, const Options::Nms& pNms, DetectionVec& bbs);
     void prune(RectVec& objects, RealVec& scores) const;

@@ -8,6 +8,10 @@
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
+//   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --score-crops [--defaults] [--luv]
+//                  Detector::evaluate(const cv::Mat&) on the frames as one batch of crops: a "crop i score scorebits" line each
+//                  (--defaults: the toolbox-default channels, as the reference; else the model's).  Without --score-crops a frame
+//                  of exactly the window's size is scored the same way instead of searched (acf.cpp:350-355)
 //   ... --ref-arith host|tables.bin   the reference's rcpps / rsqrtps bits (probed from this CPU, or 4096 + 8192 uint32 from a file)
 //   ... --log-levels                  Detector::setLogger: a "level <tag> <hash>" line per pyramid level
 //   acf_hip_detect --convert in.acfm|in.cpb --out out.cpb                                  (model file conversion, no GPU)
@@ -308,6 +312,26 @@ int main(int argc, char** argv)
             }
             return os ? 0 : 2;
         }
+        if (a.count("score-crops"))
+        {
+            // Detector::evaluate(const cv::Mat&) on every frame as ONE batch (--defaults: computeChannels' toolbox defaults, the
+            // reference's method; else the model's own Chns; both with cascThr 0)
+            std::vector<acf::MatP> crops;
+            for (int f = 0; f < cnt; f++)
+            {
+                crops.emplace_back(rows, cols, ch, frames.data() + per * size_t(f));
+            }
+            HipDetector::Options::Pyramid::Chns pc = det.opts.pPyramid.pChns;
+            pc.isLuv = a.count("luv") != 0;
+            const std::vector<float> sc = a.count("defaults") ? det.evaluate(crops) : det.evaluateCrops(crops, &pc, 0.0);
+            for (int f = 0; f < cnt; f++)
+            {
+                uint32_t b;
+                std::memcpy(&b, &sc[size_t(f)], 4);
+                std::printf("crop %d %.9g %08x\n", f, sc[size_t(f)], b);
+            }
+            return 0;
+        }
         if (a.count("pool"))
         {
             // acf::HipDetectorPool: one detector per visible device ("--pool N": the first N devices, several times the same
@@ -410,6 +434,12 @@ int main(int argc, char** argv)
                         det(other, o2, nullptr);
                     }
                     det(P, objs, &scores);
+                }
+                else if (cols == det.getWindowSize().height && rows == det.getWindowSize().width)
+                {
+                    // acf.cpp:350-355: an image of exactly the window's size is scored, not searched
+                    scores.push_back(det.evaluate(Ip));
+                    objs.push_back(acf::Rect(0, 0, rows, cols));
                 }
                 else
                 {

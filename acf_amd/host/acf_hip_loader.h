@@ -76,6 +76,8 @@ struct Api
     ACF_HIP_FN(acf_hip_op_acf_detect1_u8)
     ACF_HIP_FN(acf_hip_thrs_u8)
     ACF_HIP_FN(acf_hip_op_evaluate)
+    ACF_HIP_FN(acf_hip_evaluate_crops)
+    ACF_HIP_FN(acf_hip_evaluate_crops_u8)
 #undef ACF_HIP_FN
 };
 

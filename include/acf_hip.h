@@ -560,6 +560,30 @@ ACF_HIP_API int acf_hip_op_acf_detect1_u8(acf_hip_ctx* ctx, const uint8_t* chns,
  * window at (0,0) of one host channel buffer [nChns][wP][hP]; trees are added until the score is <= cascThr (the reference
  * passes 0 here) and the score reached is returned, whether or not the window would be a detection. */
 ACF_HIP_API int acf_hip_op_evaluate(acf_hip_ctx* ctx, const float* chns, int hP, int wP, int nChns, double cascThr, float* score);
+/* Detector::evaluate(const cv::Mat&) for a BATCH of crops (ACF.h:543, ACF.cpp:123-133 = computeChannels + evaluate(MatP),
+ * acfDetect1.cpp:337-342) — how the reference's CLI classifies images of exactly the window's size (acf.cpp:350-355).  Hot path:
+ * DEVICE pointers, on the context's stream, a model but no plan.  scores_dev[i] receives exactly the bits acf_hip_chns_compute(ctx,
+ * chns, crop i, ..) followed by acf_hip_op_evaluate(ctx, channels, hC, wC, nChns, cascThr, ..) returns: the crop cut to a multiple
+ * of shrink, rgbConvert with the same pass-through rules, the in-place convTri1 colour smoothing, gradientMag with its
+ * normalisation, gradientHist, addChn's shrink, then the window at (0, 0), trees in order until the score is <= cascThr (the
+ * reference passes 0).  Every tree depth 0..8; option "arith" is honoured.
+ *   chns       the Options::Pyramid::Chns fields are read, as in acf_hip_chns_compute; NULL: the context's model.  (The reference's
+ *              overload always computes the toolbox-default channels of computeChannels, ACF.cpp:183-236: pass those to mirror it.)
+ *   crops_dev  n crops back to back, each [d][w][h] transposed planar f32, d = 1 or 3
+ *   _u8        n upright packed images of h rows x w pixels in layout pix (ACF_HIP_PIX_RGB / BGR / RGBA / BGRA / GRAY; NV12 / NV21 are
+ *              refused), row_stride_bytes apart (0 = tight), crops stride * h bytes apart; the bytes become planes by the 8-bit entries'
+ *              arithmetic, float(v) * float(1 / 255.0)
+ * Two forms, chosen by the crop's size alone, identical in every bit: crops whose planes fit one workgroup's LDS (80 x 80 x 3 and
+ * 128 x 64 x 3 do) are scored by ONE kernel, k_crop_score, asynchronously and without allocating; bigger crops go as a batch of
+ * frames through the kernels acf_hip_chns_compute launches and k_evaluate_windows — that form allocates its planes per call and
+ * SYNCHRONISES the stream before it returns.  With option "profile" the form that ran reports under those two names.
+ * ACF_HIP_E_NOMODEL without a model; ACF_HIP_E_INVALID for null pointers, n < 1, d not 1 or 3, a cropped image smaller than
+ * modelDsPad on either axis, a model whose feature ids reach beyond nChns(chns) x the window's cells, NV12 / NV21 or unknown pix;
+ * what acf_hip_chns_compute refuses with its code (odd softBin, pColor.smooth > 1, ...); ACF_HIP_E_UNSUPPORTED for an LDCF model. */
+ACF_HIP_API int acf_hip_evaluate_crops(acf_hip_ctx* ctx, const acf_hip_params* chns, const float* crops_dev, int n, int h, int w, int d,
+    double cascThr, float* scores_dev);
+ACF_HIP_API int acf_hip_evaluate_crops_u8(acf_hip_ctx* ctx, const acf_hip_params* chns, const uint8_t* crops_dev, int n, int h, int w, int pix,
+    int row_stride_bytes, double cascThr, float* scores_dev);
 /* thrs.convertTo(thrsU8, CV_8UC1, 255.0f) (ACFIOArchive.h:96-99): host only, no context. */
 ACF_HIP_API int acf_hip_thrs_u8(const float* thrs, int n, uint8_t* out);
 
