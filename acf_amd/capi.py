@@ -149,6 +149,16 @@ PIX_RGB, PIX_BGR, PIX_RGBA, PIX_BGRA, PIX_GRAY = range(5)
 PIX_CPP = {PIX_RGB: 3, PIX_BGR: 3, PIX_RGBA: 4, PIX_BGRA: 4, PIX_GRAY: 1}
 PIX_NV12, PIX_NV21 = 5, 6  # YUV 4:2:0 (a luma plane, then interleaved chroma pairs): no bytes per pixel; sizes from acf_hip_u8_frame_bytes
 
+T_U8, T_F16, T_BF16, T_F32 = range(4)  # ACF_HIP_T_*: element types of the image entry (acf_hip_pyramid_image / run_image)
+
+
+class ImageDesc(C.Structure):
+    """struct acf_hip_image_desc: strides in elements of an image indexed [n][c][y][x] (torch.Tensor.stride() of [n, c, H, W])."""
+
+    _fields_ = [("dtype", C.c_int32), ("channels", C.c_int32),
+                ("stride_n", C.c_int64), ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64)]
+
+
 _lib = None
 
 
@@ -193,6 +203,9 @@ def load():
         "acf_hip_run_host": ([ctx, fp, C.c_int], C.c_int),
         "acf_hip_pyramid_u8": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int], C.c_int),
         "acf_hip_run_u8": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int], C.c_int),
+        "acf_hip_pyramid_image": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc)], C.c_int),
+        "acf_hip_run_image": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc)], C.c_int),
+        "acf_hip_image_extent": ([C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
         "acf_hip_u8_frame_bytes": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)], C.c_int),
@@ -254,6 +267,7 @@ DECLARED_SYMBOLS = [
     "acf_hip_op_rgb_convert", "acf_hip_op_conv_tri", "acf_hip_op_gradient_mag", "acf_hip_selftest_gradmag", "acf_hip_set_x86_tables", "acf_hip_selftest_x86", "acf_hip_chns_compute", "acf_hip_op_gradient_hist",
     "acf_hip_op_im_resample", "acf_hip_op_acf_detect1", "acf_hip_op_acf_detect1_u8", "acf_hip_thrs_u8", "acf_hip_op_evaluate",
     "acf_hip_evaluate_crops", "acf_hip_evaluate_crops_u8",
+    "acf_hip_pyramid_image", "acf_hip_run_image", "acf_hip_image_extent",
 ]
 
 

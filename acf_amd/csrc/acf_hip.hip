@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -1825,7 +1826,28 @@ struct PackedSrc
     int pix, rowStride;
 };
 
+// an upright image of any element strides (acf_hip_pyramid_image)
+struct ImageSrc
+{
+    const void* frames;
+    acf_hip_image_desc d;
+};
+
 using IngestKernel = void (*)(IngestArgs);
+using ImageKernel = void (*)(IngestArgs, ImageArgs);
+
+// k_ingest_image<element type, conversion>: [ACF_HIP_T_*][IG_*]
+static ImageKernel imageKernel(int dtype, int mode)
+{
+    static const ImageKernel table[4][4] = {
+        { k_ingest_image<IM_U8, IG_PLANAR>, k_ingest_image<IM_U8, IG_LUV_VEC>, k_ingest_image<IM_U8, IG_LUV>, k_ingest_image<IM_U8, IG_GRAY> },
+        { k_ingest_image<IM_F16, IG_PLANAR>, k_ingest_image<IM_F16, IG_LUV_VEC>, k_ingest_image<IM_F16, IG_LUV>, k_ingest_image<IM_F16, IG_GRAY> },
+        { k_ingest_image<IM_BF16, IG_PLANAR>, k_ingest_image<IM_BF16, IG_LUV_VEC>, k_ingest_image<IM_BF16, IG_LUV>, k_ingest_image<IM_BF16, IG_GRAY> },
+        { k_ingest_image<IM_F32, IG_PLANAR>, k_ingest_image<IM_F32, IG_LUV_VEC>, k_ingest_image<IM_F32, IG_LUV>, k_ingest_image<IM_F32, IG_GRAY> },
+    };
+    return table[dtype][mode];
+}
+
 using YuvIngestKernel = void (*)(IngestArgs, YuvSrc);
 
 static IngestKernel ingestKernel(int mode, bool aligned)
@@ -1945,21 +1967,12 @@ static int launchYuvToRgb(acf_hip_ctx* c, const YuvSrc& s, int nF, uint8_t* dst)
     return ACF_HIP_OK;
 }
 
-int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t out_fs, bool convert)
+// What every ingest kernel is told, whatever it reads: the destination planes, the constants of the model's colour conversion and
+// the conversion itself (the return value: IG_*).  convert: to the converted colour planes; else planar, the input's own planes.
+static int ingestShared(acf_hip_ctx* c, float* dst, int64_t out_fs, bool convert, IngestArgs& a)
 {
     const acf_hip_params& p = c->p;
     const Plan& pl = c->plan;
-    U8Geom g;
-    if (const char* bad = u8Geom(u.pix, pl.H, pl.W, u.rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_u8: ") + bad);
-    }
-    if (!u8PlanesOk(g, pl.d_in))
-    {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY");
-    }
-    IngestArgs a{};
-    a.in = u.frames;
     a.out = dst;
     a.lTable = c->d_lTable;
     a.k = makeLuvConsts();
@@ -1969,15 +1982,8 @@ int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t
     a.mb = kGray.b;
     a.H = pl.H;
     a.W = pl.W;
-    a.cpp = g.cpp;
-    a.ro = g.ro;
-    a.go = g.go;
-    a.bo = g.bo;
-    a.rowStride = g.stride;
-    a.in_fs = g.frameStride;
     a.out_fs = out_fs;
     a.vecStore = (pl.H % 4 == 0) && (out_fs % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0);
-    bool aligned = (reinterpret_cast<uintptr_t>(u.frames) % 4 == 0) && (a.rowStride % 4 == 0);
     const int64_t np0 = int64_t(pl.H) * pl.W;
     int mode = IG_PLANAR;
     a.nOut = pl.d_in;
@@ -1996,6 +2002,31 @@ int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t
             a.nOut = 3; // ORIG / RGB with a 1-plane input: replicate (chnsPyramid.cpp:242-243)
         }
     }
+    return mode;
+}
+
+int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t out_fs, bool convert)
+{
+    const Plan& pl = c->plan;
+    U8Geom g;
+    if (const char* bad = u8Geom(u.pix, pl.H, pl.W, u.rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_u8: ") + bad);
+    }
+    if (!u8PlanesOk(g, pl.d_in))
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY");
+    }
+    IngestArgs a{};
+    const int mode = ingestShared(c, dst, out_fs, convert, a);
+    a.in = u.frames;
+    a.cpp = g.cpp;
+    a.ro = g.ro;
+    a.go = g.go;
+    a.bo = g.bo;
+    a.rowStride = g.stride;
+    a.in_fs = g.frameStride;
+    bool aligned = (reinterpret_cast<uintptr_t>(u.frames) % 4 == 0) && (a.rowStride % 4 == 0);
     const dim3 grid(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF);
     if (g.yuv)
     {
@@ -2006,6 +2037,78 @@ int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t
     }
     hipLaunchKernelGGL(ingestKernel(mode, aligned), grid, dim3(256), 0, c->stream, a);
     LAUNCHCHK(c, "k_ingest_u8");
+    return ACF_HIP_OK;
+}
+
+// What is wrong with an image description by itself (acf_hip_image_extent and the image entries), or null
+static const char* imageDescBad(const acf_hip_image_desc* d)
+{
+    if (!d)
+    {
+        return "null description";
+    }
+    if (d->dtype < ACF_HIP_T_U8 || d->dtype > ACF_HIP_T_F32)
+    {
+        return "unknown dtype";
+    }
+    if (d->channels != 1 && d->channels != 3)
+    {
+        return "channels must be 1 or 3";
+    }
+    if (d->stride_x < 1 || d->stride_y < 1)
+    {
+        return "stride_x and stride_y must be positive";
+    }
+    if (d->stride_n < 0)
+    {
+        return "negative stride_n";
+    }
+    return nullptr;
+}
+
+static int imageElemBytes(int dtype)
+{
+    return dtype == ACF_HIP_T_U8 ? 1 : (dtype == ACF_HIP_T_F32 ? 4 : 2);
+}
+
+// The load form of k_ingest_image for a description and a pointer: the vector forms where their conditions hold (kernels_input.hip.h),
+// else the element-wise one, which is right for every description.
+static int imageLoadForm(const ImageSrc& im)
+{
+    const acf_hip_image_desc& d = im.d;
+    const uintptr_t at = reinterpret_cast<uintptr_t>(im.frames);
+    const int es = imageElemBytes(d.dtype);
+    if (at % es)
+    {
+        return IM_GENERIC;
+    }
+    if (d.stride_x == 1 && at % (4 * es) == 0 && d.stride_n % 4 == 0 && d.stride_y % 4 == 0 && (d.channels == 1 || d.stride_c % 4 == 0))
+    {
+        return IM_ROWVEC;
+    }
+    if (d.channels == 3 && (d.stride_c == 1 || d.stride_c == -1) && (d.stride_x == 3 || d.stride_x == 4))
+    {
+        return IM_PACKED;
+    }
+    return IM_GENERIC;
+}
+
+// k_ingest_image over a batch: the image entry's frames -> planar f32 at dst, converted (to c->d_color) or as they are (to c->d_stage)
+int launchIngestImage(acf_hip_ctx* c, const ImageSrc& im, int nF, float* dst, int64_t out_fs, bool convert)
+{
+    const Plan& pl = c->plan;
+    IngestArgs a{};
+    const int mode = ingestShared(c, dst, out_fs, convert, a);
+    ImageArgs s{};
+    s.in = im.frames;
+    s.sn = im.d.stride_n;
+    s.sc = im.d.stride_c;
+    s.sy = im.d.stride_y;
+    s.sx = im.d.stride_x;
+    s.nIn = im.d.channels;
+    s.form = imageLoadForm(im);
+    hipLaunchKernelGGL(imageKernel(im.d.dtype, mode), dim3(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF), dim3(256), 0, c->stream, a, s);
+    LAUNCHCHK(c, "k_ingest_image");
     return ACF_HIP_OK;
 }
 
@@ -2095,9 +2198,9 @@ static void clearRepairFlags(acf_hip_ctx* c)
 
 #include "pyramid_run.hip.h" // PyramidRun (acf_hip_pyramid's stages), pyramidBody
 
-static int pyramidImpl(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF)
+static int pyramidImpl(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF, const ImageSrc* img = nullptr)
 {
-    const int rc = pyramidBody(c, frames, u8, nF);
+    const int rc = pyramidBody(c, frames, u8, nF, img);
     if (rc && c && c->hasPlan && c->kids.empty())
     {
         clearRepairFlags(c);
@@ -2115,6 +2218,44 @@ int acf_hip_pyramid_u8(acf_hip_ctx* c, const uint8_t* frames, int nF, int pix, i
     if (int rc = needCtx(c)) return rc;
     PackedSrc u{ frames, pix, rowStride };
     return pyramidImpl(c, nullptr, &u, nF);
+}
+
+int acf_hip_pyramid_image(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc)
+{
+    if (int rc = needCtx(c)) return rc;
+    if (!frames || !desc)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_image: null frames or description");
+    }
+    ImageSrc im{ frames, *desc };
+    return pyramidImpl(c, nullptr, nullptr, nF, &im);
+}
+
+int acf_hip_run_image(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc)
+{
+    int rc = acf_hip_pyramid_image(c, frames, nF, desc);
+    if (rc)
+    {
+        return rc;
+    }
+    return acf_hip_detect(c);
+}
+
+int acf_hip_image_extent(const acf_hip_image_desc* d, int h, int w, int nF, int64_t* first, int64_t* last)
+{
+    if (!first || !last || imageDescBad(d) || h < 1 || w < 1 || nF < 1)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    int64_t lo = 0, hi = 0;
+    const int64_t span[4] = { (nF - 1) * d->stride_n, (d->channels - 1) * d->stride_c, (h - 1) * d->stride_y, (w - 1) * d->stride_x };
+    for (int64_t v : span)
+    {
+        (v < 0 ? lo : hi) += v;
+    }
+    *first = lo;
+    *last = hi;
+    return ACF_HIP_OK;
 }
 
 int acf_hip_u8_frame_bytes(int pix, int rows, int cols, int rowStride, int64_t* out)

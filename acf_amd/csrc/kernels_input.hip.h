@@ -329,6 +329,258 @@ __global__ void __launch_bounds__(256) k_ingest_u8(IngestArgs a)
 }
 
 // ------------------------------------------------------------------------
+// Upright images of any element strides (u8 / f16 / bf16 / f32) -> transposed planar f32: the image entry for CV_32FC3 as well as
+// CV_8UC3 (ACF.cpp:135-141: I.t(), then the MatP split, MatP.cpp:51-73) on what a tensor library holds — element (n, c, y, x) at
+// in[n * sn + c * sc + y * sy + x * sx].  k_ingest_u8's shape: a workgroup owns 64 x 64 pixels; the load phase runs lanes along
+// image-x, widens every element to f32 as it arrives (u8: float(v) * float(1 / 255.0) as k_ingest_u8; f16 / bf16: exact) and
+// stores it to an LDS tile of floats; the store phase is k_ingest_u8's (four consecutive image-y of one image-x a lane, the
+// model's colour conversion in registers, one float4 a plane).
+//
+// Load forms (ImageArgs::form, chosen on the host from the strides and the pointer; all give the same planes):
+//   IM_GENERIC  one element a lane, any strides: the baseline
+//   IM_ROWVEC   sx == 1, every row start a multiple of four elements: four elements a lane in one load (4 / 8 / 16 bytes); the
+//               nx % 4 elements at a row's end one by one
+//   IM_PACKED   sc == +-1, sx == 3 or 4 (interleaved pixels, alpha skipped, channels forwards or backwards): the row's addressed
+//               span [first element of pixel x0, last element of pixel x0 + nx - 1] is read as aligned dwords by consecutive
+//               lanes (4 / 2 / 1 elements) and every element goes to its plane; the dwords that straddle the span's ends one
+//               element at a time
+// No load covers an address outside [first, last] element the same row of the same plane set addresses, so a view that ends
+// with its allocation is safe.
+//
+// LDS: plane c at c * IM_PLANE floats, image row r in slot (r & 3) * 16 + (r >> 2) at a pitch of 66 dwords (the regrouping of
+// k_ingest_yuv420).  Bank = dword address % 32, counted per 32-lane half (ds_read_b32 / ds_write_b32):
+//   store phase (reads)  a half is 16 row-quads x 2 adjacent image-x; read j takes rows 4k + j = slots 16j + k, k = 0 .. 15:
+//                        addresses 66k + {0, 1} -> banks 2k + {0, 1}: 32 distinct banks, conflict-free, for each plane's read
+//   IM_GENERIC (writes)  a half writes 32 consecutive image-x of one row and plane: 32 distinct banks, conflict-free
+//   IM_ROWVEC (writes)   a lane holds 4 consecutive dwords, a half two rows 16 slots = 1056 = 0 (mod 32) dwords apart: one
+//                        ds_write_b32 of element i puts lanes at 4q + i, q = 0 .. 15, twice: 8 banks, 4-way (as b32; the
+//                        slot pitch is 8-byte aligned, so the compiler may pair them into ds_write_b64)
+//   IM_PACKED (writes)   a wave takes one row, its lanes the row's dwords: 32 consecutive elements of a row are ~11 pixels in all
+//                        three planes; the planes are 64 * 66 + 11 dwords apart, so channel c of pixel x lands on bank
+//                        x + 11c + const.  Enumerated over every lane group and row alignment: f32 (one element a lane)
+//                        conflict-free; f16 / bf16 (element t of consecutive lanes' dwords: every 2nd element) 2-way; u8 (every
+//                        4th) 4-way at stride_x 3, conflict-free at 4
+// (degrees computed from the address maps above with the bank rule; the SQ_LDS_BANK_CONFLICT counter was not read:
+// profiles/image_entry.md)
+// 3 x (64 x 66 + 11) floats = 50820 bytes: three workgroups a CU.
+// ------------------------------------------------------------------------
+enum
+{
+    IM_U8 = 0, // = ACF_HIP_T_*
+    IM_F16 = 1,
+    IM_BF16 = 2,
+    IM_F32 = 3
+};
+enum
+{
+    IM_GENERIC = 0,
+    IM_ROWVEC = 1,
+    IM_PACKED = 2
+};
+
+struct ImageArgs
+{
+    const void* in;
+    int64_t sn, sc, sy, sx; // strides in elements: frames, channels, image rows, image columns
+    int nIn;                // planes read: 1 (r = g = b = the plane) or 3
+    int form;               // IM_GENERIC / IM_ROWVEC / IM_PACKED
+};
+
+template <int DT>
+struct ImgElem;
+template <>
+struct ImgElem<IM_U8>
+{
+    using raw = uint8_t;
+    static __device__ __forceinline__ float cvt(raw v)
+    {
+        return float(v) * float(1.0 / 255.0);
+    }
+};
+template <>
+struct ImgElem<IM_F16>
+{
+    using raw = uint16_t;
+    static __device__ __forceinline__ float cvt(raw v)
+    {
+        return float(__builtin_bit_cast(_Float16, v));
+    }
+};
+template <>
+struct ImgElem<IM_BF16>
+{
+    using raw = uint16_t;
+    static __device__ __forceinline__ float cvt(raw v)
+    {
+        return __uint_as_float(uint32_t(v) << 16);
+    }
+};
+template <>
+struct ImgElem<IM_F32>
+{
+    using raw = uint32_t;
+    static __device__ __forceinline__ float cvt(raw v)
+    {
+        return __uint_as_float(v);
+    }
+};
+
+constexpr int IM_PITCH = 66;                     // dwords
+constexpr int IM_PLANE = IG_T * IM_PITCH + 11;   // dwords
+__device__ __forceinline__ int im_slot(int r)
+{
+    return (r & 3) * 16 + (r >> 2);
+}
+
+template <int DT, int MODE>
+__global__ void __launch_bounds__(256) k_ingest_image(IngestArgs a, ImageArgs s)
+{
+    using E = ImgElem<DT>;
+    using raw = typename E::raw;
+    __shared__ float tile[3 * IM_PLANE];
+    const int x0 = blockIdx.x * IG_T, y0 = blockIdx.y * IG_T;
+    const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0);
+    const raw* src = static_cast<const raw*>(s.in) + int64_t(blockIdx.z) * s.sn + int64_t(y0) * s.sy + int64_t(x0) * s.sx;
+    if (s.form == IM_ROWVEC)
+    {
+        // sx == 1; the base and sn, sc, sy are multiples of four elements (host-checked) and x0 is a multiple of 64
+        struct alignas(4 * sizeof(raw)) Quad
+        {
+            raw v[4];
+        };
+        const int nq = nx >> 2;
+        // (constant trip counts, so that the loads of all the passes are in flight together)
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+        {
+            if (c < s.nIn)
+            {
+                const raw* pc = src + int64_t(c) * s.sc;
+                float* tc = tile + c * IM_PLANE;
+#pragma unroll
+                for (int pass = 0; pass < IG_T * 16 / 256; pass++)
+                {
+                    const int i = threadIdx.x + pass * 256;
+                    const int yy = i >> 4, q = i & 15;
+                    const raw* rp = pc + int64_t(yy) * s.sy + 4 * q;
+                    float* t = tc + im_slot(yy) * IM_PITCH + 4 * q;
+                    if (yy < ny && q < nq)
+                    {
+                        const Quad v = *reinterpret_cast<const Quad*>(rp);
+#pragma unroll
+                        for (int j = 0; j < 4; j++)
+                        {
+                            t[j] = E::cvt(v.v[j]);
+                        }
+                    }
+                    else if (yy < ny && q == nq)
+                    {
+                        for (int j = 0; 4 * q + j < nx; j++) // the row's tail: element by element
+                        {
+                            t[j] = E::cvt(rp[j]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    else if (s.form == IM_PACKED)
+    {
+        // sc == +-1, sx == 3 or 4, three planes; the base is a multiple of the element size (host-checked)
+        constexpr int PER = 4 / int(sizeof(raw)); // elements a dword
+        const int rev = s.sc < 0, sx = int(s.sx);
+        const int L = (nx - 1) * sx + 3;          // elements the row addresses in this tile: [0, L) from `span`
+        const raw* span = src - (rev ? 2 : 0);
+        const int ndMax = (L * int(sizeof(raw)) + 6) >> 2; // dwords that can hold a piece of it, whatever the row's alignment
+        // a wave takes a row, its lanes the row's dwords in turn (four rows a pass; two passes' loads in flight)
+#pragma unroll 2
+        for (int yy = threadIdx.x >> 6; yy < ny; yy += 4)
+        {
+            const raw* rp = span + int64_t(yy) * s.sy;
+            const int mis = int(reinterpret_cast<uintptr_t>(rp) & 3) / int(sizeof(raw)); // elements of rp's dword in front of rp
+            float* trow = tile + im_slot(yy) * IM_PITCH;
+            for (int j = threadIdx.x & 63; j < ndMax; j += 64)
+            {
+                const int e0 = j * PER - mis; // span index of dword j's first element
+                if (e0 >= L)
+                {
+                    continue;
+                }
+                raw v[PER];
+                if (e0 >= 0 && e0 + PER <= L)
+                {
+                    const uint32_t w = *reinterpret_cast<const uint32_t*>(rp + e0);
+#pragma unroll
+                    for (int t = 0; t < PER; t++)
+                    {
+                        v[t] = raw(w >> (8 * int(sizeof(raw)) * t));
+                    }
+                }
+                else
+                {
+#pragma unroll
+                    for (int t = 0; t < PER; t++) // a dword over one end of the span: only the elements inside it
+                    {
+                        const int e = e0 + t;
+                        v[t] = (e >= 0 && e < L) ? rp[e] : raw(0);
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < PER; t++)
+                {
+                    const int e = e0 + t;
+                    if (e >= 0 && e < L)
+                    {
+                        const int x = sx == 4 ? e >> 2 : e / 3, m = e - x * sx;
+                        if (m < 3) // (m == 3: the skipped fourth element)
+                        {
+                            trow[(rev ? 2 - m : m) * IM_PLANE + x] = E::cvt(v[t]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    else
+    {
+        for (int c = 0; c < s.nIn; c++)
+        {
+            const raw* pc = src + int64_t(c) * s.sc;
+            float* tc = tile + c * IM_PLANE;
+#pragma unroll 8
+            for (int pass = 0; pass < IG_T * IG_T / 256; pass++)
+            {
+                const int i = threadIdx.x + pass * 256;
+                const int yy = i >> 6, xx = i & 63;
+                if (yy < ny && xx < nx)
+                {
+                    tc[im_slot(yy) * IM_PITCH + xx] = E::cvt(pc[int64_t(yy) * s.sy + int64_t(xx) * s.sx]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int k16 = threadIdx.x & 15, yq = k16 * 4;
+    const int p1 = s.nIn == 3 ? IM_PLANE : 0, p2 = 2 * p1; // one plane: r = g = b (chnsPyramid.cpp:234-244)
+    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
+    const int64_t np = int64_t(a.H) * a.W;
+    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
+    {
+        float o[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            // rows beyond the tile convert zeros (the LDS there was never written; rgb2luv indexes a table): never stored
+            const float* t = tile + (j * 16 + k16) * IM_PITCH + xx;
+            const bool in = yq + j < ny;
+            const float r = in ? t[0] : 0.f, g = in ? t[p1] : 0.f, b = in ? t[p2] : 0.f;
+            ingest_convert<MODE>(a, r, g, b, o, j);
+        }
+        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
+    }
+}
+
+// ------------------------------------------------------------------------
 // YUV 4:2:0 video frames (NV12 / NV21) -> 8-bit R, G, B: cvtColor(COLOR_YUV2RGB_NV12 / _NV21), the call the apps make before
 // Detector::operator()(const cv::Mat&).  OpenCV is not part of the reference tree: this is the published algorithm of
 // imgproc/src/color_yuv.simd.hpp restated (BT.601 limited range, 20-bit fixed point, int32, arithmetic shift; the chroma pair of a

@@ -190,6 +190,9 @@ struct PyramidRun
     }
 
     int ingest(const PackedSrc* u8, bool& ingestConverted);
+    int ingestImage(const ImageSrc& im, bool& ingestConverted);
+    using IngestLaunch = std::function<int(float* dst, int64_t out_fs, bool convert)>;
+    int ingestPlanes(const char* kernel, bool& ingestConverted, const IngestLaunch& launch);
     int colour(bool ingestConverted);
     int prepareScales();
     int realScale(size_t k);
@@ -265,30 +268,63 @@ int PyramidRun::ingest(const PackedSrc* u8, bool& ingestConverted)
     if (u8)
     {
         // 8-bit ingest (ACF.cpp:114-119,137; MatP.cpp:51-73), fused with the colour conversion below when there is one
-        prof(c, c->stream, fusedYuv ? "k_ingest_yuv420" : "k_ingest_u8");
-        ingestConverted = c->d_color && p.colorSpace != ACF_HIP_CS_HSV; // (hsv: planar ingest, then k_rgb2hsv like a float frame)
-        if (ingestConverted)
-        {
-            if ((rc = launchIngest(c, *u8, nF, c->d_color, int64_t(d) * np0, true)))
-            {
-                return rc;
-            }
-            frames = nullptr;
-        }
-        else
-        {
-            if (!c->d_stage && (rc = devAlloc(c, &c->d_stage, size_t(c->maxBatch) * d_in * np0)))
-            {
-                return rc;
-            }
-            if ((rc = launchIngest(c, *u8, nF, c->d_stage, int64_t(d_in) * np0, false)))
-            {
-                return rc;
-            }
-            frames = c->d_stage;
-        }
+        return ingestPlanes(fusedYuv ? "k_ingest_yuv420" : "k_ingest_u8", ingestConverted,
+            [&](float* dst, int64_t out_fs, bool convert) { return launchIngest(c, *u8, nF, dst, out_fs, convert); });
     }
     return ACF_HIP_OK;
+}
+
+// An ingest kernel in front of the pyramid: to the converted colour planes where the model converts (every colour space but hsv),
+// else to planar planes in d_stage (hsv: k_rgb2hsv follows like on a float frame; orig / isLuv: the pyramid reads them as they are).
+int PyramidRun::ingestPlanes(const char* kernel, bool& ingestConverted, const IngestLaunch& launch)
+{
+    int rc;
+    prof(c, c->stream, kernel);
+    ingestConverted = c->d_color && p.colorSpace != ACF_HIP_CS_HSV;
+    if (ingestConverted)
+    {
+        if ((rc = launch(c->d_color, int64_t(d) * np0, true)))
+        {
+            return rc;
+        }
+        frames = nullptr;
+    }
+    else
+    {
+        if (!c->d_stage && (rc = devAlloc(c, &c->d_stage, size_t(c->maxBatch) * d_in * np0)))
+        {
+            return rc;
+        }
+        if ((rc = launch(c->d_stage, int64_t(d_in) * np0, false)))
+        {
+            return rc;
+        }
+        frames = c->d_stage;
+    }
+    return ACF_HIP_OK;
+}
+
+// The image entry for upright images of any strides and element type (ACF.cpp:135-141 for CV_32FC3 and CV_8UC3; MatP.cpp:51-73)
+int PyramidRun::ingestImage(const ImageSrc& im, bool& ingestConverted)
+{
+    if (const char* bad = imageDescBad(&im.d))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_image: ") + bad);
+    }
+    if (d_in == 5)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_image: a plan for five input planes (image + M, O) takes planar float frames");
+    }
+    if (im.d.channels != d_in)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_image: channels must be the plan's input planes (d)");
+    }
+    if (c->rz.on)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_image: not with acf_hip_set_input_resize (the resize takes packed 8-bit frames)");
+    }
+    return ingestPlanes("k_ingest_image", ingestConverted,
+        [&](float* dst, int64_t out_fs, bool convert) { return launchIngestImage(c, im, nF, dst, out_fs, convert); });
 }
 
 // ---- colour conversion, once at full resolution (chnsPyramid.cpp:230-263)
@@ -1067,13 +1103,13 @@ int PyramidRun::levelsWithImageLambdas()
     return ACF_HIP_OK;
 }
 
-int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF)
+int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF, const ImageSrc* img)
 {
     if (c && !c->kids.empty())
     {
-        if (u8)
+        if (u8 || img)
         {
-            return fail(c, ACF_HIP_E_UNSUPPORTED, "pyramid_u8: not available with option \"streams\" > 1");
+            return fail(c, ACF_HIP_E_UNSUPPORTED, std::string(img ? "pyramid_image" : "pyramid_u8") + ": not available with option \"streams\" > 1");
         }
         if (!frames || nF <= 0 || nF > c->maxBatch)
         {
@@ -1090,7 +1126,7 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
         return rc;
     }
     if (int rc = needPlan(c, "pyramid")) return rc;
-    if ((!frames && !u8) || (u8 && !u8->frames) || nF <= 0 || nF > c->maxBatch)
+    if ((!frames && !u8 && !img) || (u8 && !u8->frames) || (img && !img->frames) || nF <= 0 || nF > c->maxBatch)
     {
         return fail(c, ACF_HIP_E_INVALID, "pyramid: n_frames out of range");
     }
@@ -1099,7 +1135,7 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
     int rc;
     PyramidRun run(c, frames, nF);
     bool ingestConverted = false; // the 8-bit ingest wrote the converted colour planes itself
-    if (u8 && (rc = run.ingest(u8, ingestConverted)))
+    if ((u8 && (rc = run.ingest(u8, ingestConverted))) || (img && (rc = run.ingestImage(*img, ingestConverted))))
     {
         return rc;
     }

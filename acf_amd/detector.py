@@ -140,6 +140,55 @@ class HipDetector:
         n = n if n is not None else frames.shape[0]
         self._chk(self.lib.acf_hip_run_u8(self.ctx, C.c_void_p(_dev_ptr_u8(frames)), n, pix, row_stride))
 
+    # ---- upright device tensors of any strides: uint8 / float16 / bfloat16 / float32 (acf_hip_pyramid_image / run_image)
+    @staticmethod
+    def _torch_dtype_code(t):
+        import torch
+        codes = {torch.uint8: capi.T_U8, torch.float16: capi.T_F16, torch.bfloat16: capi.T_BF16, torch.float32: capi.T_F32}
+        if t.dtype not in codes:
+            raise HipError(capi.E_INVALID, "tensor entry: dtype must be uint8, float16, bfloat16 or float32, not %s" % t.dtype)
+        return codes[t.dtype]
+
+    def _image_of(self, t, layout):
+        """(device pointer, n, capi.ImageDesc) of a device tensor [n, c, H, W] (layout "nchw") or [n, H, W, c] ("nhwc", taken as the
+        permuted view); the strides are the tensor's own: nothing is copied or made contiguous."""
+        if layout not in ("nchw", "nhwc"):
+            raise HipError(capi.E_INVALID, "tensor entry: layout must be \"nchw\" or \"nhwc\"")
+        if t.dim() != 4 or not t.is_cuda:
+            raise HipError(capi.E_INVALID, "tensor entry: a device tensor of four dimensions")
+        if layout == "nhwc":
+            t = t.permute(0, 3, 1, 2)
+        n, ch, h, w = t.shape
+        if (h, w, ch) != (self.H, self.W, self.d_in):
+            raise HipError(capi.E_INVALID, "tensor entry: the tensor is c = %d, H = %d, W = %d; the plan is for %d, %d, %d" % (ch, h, w, self.d_in, self.H, self.W))
+        sn, sc, sy, sx = t.stride()
+        return t.data_ptr(), n, capi.ImageDesc(self._torch_dtype_code(t), ch, sn, sc, sy, sx)
+
+    def pyramid_tensor(self, t, layout="nchw"):
+        """t: device tensor [n, c, H, W] of any strides (or [n, H, W, c] with layout="nhwc"), uint8 / float16 / bfloat16 / float32."""
+        ptr, n, desc = self._image_of(t, layout)
+        self._chk(self.lib.acf_hip_pyramid_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+
+    def run_tensor(self, t, layout="nchw"):
+        ptr, n, desc = self._image_of(t, layout)
+        self._chk(self.lib.acf_hip_run_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+
+    def pyramid_image(self, ptr, n, desc):
+        """The raw entry: a device pointer (int) and a capi.ImageDesc."""
+        self._chk(self.lib.acf_hip_pyramid_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+
+    def run_image(self, ptr, n, desc):
+        self._chk(self.lib.acf_hip_run_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+
+    @staticmethod
+    def image_extent(desc, h, w, n):
+        """(lowest, highest) element offset from the frames pointer that a call with this capi.ImageDesc reads (host arithmetic)."""
+        lo, hi = C.c_int64(), C.c_int64()
+        rc = capi.load().acf_hip_image_extent(C.byref(desc), h, w, n, C.byref(lo), C.byref(hi))
+        if rc:
+            raise HipError(rc, "acf_hip_image_extent")
+        return lo.value, hi.value
+
     # ---- YUV 4:2:0 video frames (PIX_NV12 / PIX_NV21) in the 8-bit entries
     @staticmethod
     def u8_frame_bytes(pix, rows, cols, row_stride=0):

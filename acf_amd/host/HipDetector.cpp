@@ -535,29 +535,56 @@ void HipDetector::logPyramid()
 
 int HipDetector::operator()(const float* rgb, int rows, int cols, RectVec& objects, RealVec* scores)
 {
-    // ACF.cpp:135-141: transpose unless the caller already did, split interleaved -> planar (MatP.cpp:18-34)
-    const int W = m_isTranspose ? rows : cols, H = m_isTranspose ? cols : rows;
-    MatP Ip(W, H, 3);
-    for (int z = 0; z < 3; z++)
+    // ACF.cpp:135-141: transpose unless the caller already did, split interleaved -> planar (MatP.cpp:18-34) — on the device
+    // (acf_hip_run_image): the interleaved image goes to page-locked memory as it is, which the device reads, and the strides say
+    // which index is the image row.  setIsTranspose(true): the array's rows are image columns.
+    if (!rgb || rows <= 0 || cols <= 0)
     {
-        float* P = Ip[z];
-        for (int r = 0; r < rows; r++)
-        {
-            for (int c = 0; c < cols; c++)
-            {
-                const float v = rgb[(size_t(r) * cols + c) * 3 + z];
-                if (m_isTranspose)
-                {
-                    P[size_t(r) * cols + c] = v; // already [W][H]
-                }
-                else
-                {
-                    P[size_t(c) * rows + r] = v;
-                }
-            }
-        }
+        throw Exception(ACF_HIP_E_INVALID, "operator()(interleaved): empty image");
     }
-    return (*this)(Ip, objects, scores);
+    const int W = m_isTranspose ? rows : cols, H = m_isTranspose ? cols : rows;
+    const size_t bytes = size_t(rows) * cols * 3 * sizeof(float);
+    if (bytes > m_pinBytes)
+    {
+        pinnedFree(m_pin);
+        m_pin = pinnedAlloc(bytes);
+        m_pinBytes = bytes;
+    }
+    std::memcpy(m_pin, rgb, bytes);
+    acf_hip_image_desc d;
+    d.dtype = ACF_HIP_T_F32;
+    d.channels = 3;
+    d.stride_n = int64_t(rows) * cols * 3;
+    d.stride_c = 1;
+    d.stride_y = m_isTranspose ? 3 : int64_t(cols) * 3;
+    d.stride_x = m_isTranspose ? int64_t(cols) * 3 : 3;
+    ensurePlan(H, W, 3, 1);
+    syncNms();
+    check(m_api->acf_hip_run_image(m_ctx, m_pin, 1, &d), "acf_hip_run_image");
+    if (m_logger)
+    {
+        logPyramid();
+    }
+    fetch(0, objects, scores);
+    return 0;
+}
+
+int HipDetector::detectImages(const void* framesDev, int nFrames, int rows, int cols, const acf_hip_image_desc& desc,
+    std::vector<RectVec>& objects, std::vector<RealVec>* scores)
+{
+    ensurePlan(rows, cols, desc.channels, nFrames);
+    syncNms();
+    check(m_api->acf_hip_run_image(m_ctx, framesDev, nFrames, &desc), "acf_hip_run_image");
+    objects.assign(size_t(nFrames), RectVec());
+    if (scores)
+    {
+        scores->assign(size_t(nFrames), RealVec());
+    }
+    for (int f = 0; f < nFrames; f++)
+    {
+        fetch(f, objects[size_t(f)], scores ? &(*scores)[size_t(f)] : nullptr);
+    }
+    return 0;
 }
 
 int HipDetector::operator()(const uint8_t* packed, int rows, int cols, int pix, int rowStrideBytes, RectVec& objects, RealVec* scores)

@@ -271,7 +271,12 @@ public:
     // Detection: planar f32 transposed image (RGB in [0,1], or LUV after setIsLuv(true)); ACF.cpp:246-265.
     // Returns 0, APPENDS to objects; scores appended (no NMS) or assigned (NMS) exactly like ACF.cpp:332-364.
     int operator()(const MatP& IpTranspose, RectVec& objects, RealVec* scores = nullptr);
-    // Packed interleaved RGB f32 in [0,1], upright rows x cols x 3 unless setIsTranspose(true) (ACF.cpp:135-141).
+    // Packed interleaved RGB f32 in [0,1], upright rows x cols x 3 unless setIsTranspose(true) (ACF.cpp:135-141).  The image is
+    // copied as it is into the detector's page-locked scratch, which the device reads in place through acf_hip_run_image (this
+    // library holds no HIP calls of its own, so there is no separate copy into device memory): transpose and plane split happen in
+    // the ingest kernel, one pass over the host link.  With setIsTranspose(true) image rows are the array's columns and the kernel
+    // takes its element-wise load form across lines of host memory: correct, but the slow way in; callers who care about speed
+    // hand over upright frames, or device memory through detectImages.
     int operator()(const float* rgbInterleaved, int rows, int cols, RectVec& objects, RealVec* scores = nullptr);
     // Packed 8-bit image (CV_8UC3 RGB / CV_8UC4 / CV_8UC1 of the reference's cv::Mat entry, ACF.cpp:135-141), upright
     // rows x cols, `pix` = ACF_HIP_PIX_*, `rowStrideBytes` 0 = tight.  /255, transpose, plane split and the colour
@@ -283,6 +288,11 @@ public:
     int operator()(const Pyramid& P, RectVec& objects, RealVec* scores = nullptr);
     // Batch of frames (no reference precedent; frames are independent): per-frame outputs.
     int detectBatch(const float* framesTransposedPlanar, int nFrames, int rows, int cols, int channels,
+        std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
+
+    // Batch of upright images in memory the device reads (device memory, or page-locked memory from pinnedAlloc), of any element
+    // strides and element type: include/acf_hip.h, acf_hip_run_image.  rows x cols = the image's size; NMS / prune as detectBatch.
+    int detectImages(const void* framesDev, int nFrames, int rows, int cols, const acf_hip_image_desc& desc,
         std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
 
     // Streaming front end (the role of GPUDetectionPipeline::runFast's two-frame FIFO, GPUDetectionPipeline.cpp:357-437):

@@ -12,6 +12,9 @@
 //                  Detector::evaluate(const cv::Mat&) on the frames as one batch of crops: a "crop i score scorebits" line each
 //                  (--defaults: the toolbox-default channels, as the reference; else the model's).  Without --score-crops a frame
 //                  of exactly the window's size is scored the same way instead of searched (acf.cpp:350-355)
+//   ... --via-images                  the same frames through detectImages: the planes described as upright images by their strides
+//   ... --interleaved [--transposed]  the same frames as interleaved upright [H][W][3] images through operator()(const float*, rows, cols)
+//                                     (--transposed: [W][H][3] after setIsTranspose(true))
 //   ... --ref-arith host|tables.bin   the reference's rcpps / rsqrtps bits (probed from this CPU, or 4096 + 8192 uint32 from a file)
 //   ... --log-levels                  Detector::setLogger: a "level <tag> <hash>" line per pyramid level
 //   acf_hip_detect --convert in.acfm|in.cpb --out out.cpb                                  (model file conversion, no GPU)
@@ -357,6 +360,65 @@ int main(int argc, char** argv)
             for (int f = 0; f < cnt; f++)
             {
                 printFrame(f, objs[size_t(f)], scores[size_t(f)]);
+            }
+        }
+        else if (a.count("via-images") || a.count("interleaved"))
+        {
+            if (ch != 3)
+            {
+                std::fprintf(stderr, "--via-images / --interleaved take three planes\n");
+                return 2;
+            }
+            // the same frames as upright images: W = rows, H = cols of the transposed planes
+            const int W = rows, H = cols;
+            if (a.count("via-images"))
+            {
+                // detectImages on the planes where they lie (in page-locked memory, which the device reads): element (c, y, x) of an
+                // upright image at c * W * H + x * H + y — an image description with stride_y = 1
+                float* pin = static_cast<float*>(HipDetector::pinnedAlloc(frames.size() * sizeof(float)));
+                std::memcpy(pin, frames.data(), frames.size() * sizeof(float));
+                acf_hip_image_desc d;
+                d.dtype = ACF_HIP_T_F32;
+                d.channels = 3;
+                d.stride_n = int64_t(per);
+                d.stride_c = int64_t(W) * H;
+                d.stride_y = 1;
+                d.stride_x = H;
+                std::vector<HipDetector::RectVec> objs;
+                std::vector<HipDetector::RealVec> scores;
+                det.detectImages(pin, cnt, H, W, d, objs, &scores);
+                HipDetector::pinnedFree(pin);
+                for (int f = 0; f < cnt; f++)
+                {
+                    printFrame(f, objs[size_t(f)], scores[size_t(f)]);
+                }
+            }
+            else
+            {
+                // operator()(const float* rgbInterleaved): the interleaved upright image [H][W][3] (--transposed: [W][H][3] after
+                // setIsTranspose(true)) built from the planes
+                const bool tr = a.count("transposed") != 0;
+                det.setIsTranspose(tr);
+                std::vector<float> img(per);
+                for (int f = 0; f < cnt; f++)
+                {
+                    const float* P = frames.data() + per * size_t(f);
+                    for (int z = 0; z < 3; z++)
+                    {
+                        for (int x = 0; x < W; x++)
+                        {
+                            for (int y = 0; y < H; y++)
+                            {
+                                const size_t px = tr ? size_t(x) * H + y : size_t(y) * W + x;
+                                img[px * 3 + z] = P[(size_t(z) * W + x) * H + y];
+                            }
+                        }
+                    }
+                    HipDetector::RectVec objs;
+                    HipDetector::RealVec scores;
+                    det(img.data(), tr ? W : H, tr ? H : W, objs, &scores);
+                    printFrame(f, objs, scores);
+                }
             }
         }
         else if (a.count("batch"))

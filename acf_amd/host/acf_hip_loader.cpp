@@ -58,6 +58,9 @@ static void doLoad(const std::string& path)
     ACF_HIP_FN(acf_hip_pyramid_u8)
     ACF_HIP_FN(acf_hip_run_u8)
     ACF_HIP_FN(acf_hip_u8_frame_bytes)
+    ACF_HIP_FN(acf_hip_pyramid_image)
+    ACF_HIP_FN(acf_hip_run_image)
+    ACF_HIP_FN(acf_hip_image_extent)
     ACF_HIP_FN(acf_hip_resize_dims)
     ACF_HIP_FN(acf_hip_set_input_resize)
     ACF_HIP_FN(acf_hip_op_resize_u8)

@@ -397,6 +397,42 @@ ACF_HIP_API int acf_hip_op_yuv420_to_rgb(acf_hip_ctx* ctx, const uint8_t* src_ho
     int64_t chroma_offset_bytes, uint8_t* dst_host);
 ACF_HIP_API int acf_hip_u8_frame_bytes(int pix, int rows, int cols, int row_stride_bytes, int64_t* out);
 
+/* The image entry for upright device images of any element strides: what a tensor library holds ([n, c, H, W] in NCHW or
+ * channels_last memory, packed RGB / BGR / RGBA, padded rows, a rectangular view into a larger surface) in uint8, float16,
+ * bfloat16 or float32 — Detector::operator()(const cv::Mat&) for CV_32FC3 as well as CV_8UC3 (ACF.cpp:135-141: I.t(), then the
+ * MatP split, MatP.cpp:51-73), with no transposed copy in front of it.
+ *     plane[c][x][y] = value(frames_dev[n * stride_n + c * stride_c + y * stride_y + x * stride_x])     at the plan's h x w
+ *     value: u8 float(v) * float(1 / 255.0) (as acf_hip_pyramid_u8); f16, bf16 the exact widening to f32; f32 the value itself
+ * and then exactly acf_hip_pyramid / acf_hip_run on those planes: every level, hit, score bit and box is what the planar entry
+ * gives for the same values (option "arith" = 1 included).  One kernel (k_ingest_image, so named under option "profile"), fused
+ * with the colour conversion of chnsPyramid.cpp:230-263 when the model asks for LUV / grey; a 1-plane image is replicated as
+ * chnsPyramid.cpp:234-244 says.
+ * Strides are in ELEMENTS — what torch.Tensor.stride() reports for an [n, c, H, W] tensor or view.  stride_x >= 1, stride_y >= 1;
+ * stride_n >= 0 (0 repeats one frame); stride_c any value: negative reads the channels backwards (packed BGR: frames_dev + 2
+ * with stride_c = -1), 0 replicates one plane.  RGBA with the alpha skipped is stride_x = 4, channels = 3.  frames_dev is a
+ * multiple of the element size.  Only addressed elements are read: a view may end with its allocation.
+ * Asynchronous on the context's stream; nothing is allocated after the first call.  The calls always run plainly and leave a
+ * captured graph of acf_hip_run (option "graph") valid; ACF_HIP_TAP_IMAGE behaves as after acf_hip_pyramid_u8.
+ * ACF_HIP_E_INVALID: null pointers, n_frames outside 1 .. max_batch, an unknown dtype, channels other than the plan's d, a
+ * five-plane plan, stride_x < 1, stride_y < 1, stride_n < 0, an active acf_hip_set_input_resize (8-bit packed only);
+ * ACF_HIP_E_UNSUPPORTED with option "streams" > 1; ACF_HIP_E_NOPLAN without a plan.
+ *  acf_hip_image_extent      host arithmetic, no context, no GPU: the lowest and the highest element offset from frames_dev that a
+ *                            call with these arguments reads (first_elem <= 0 <= last_elem), to check a buffer or a view against */
+enum {
+    ACF_HIP_T_U8 = 0,
+    ACF_HIP_T_F16 = 1,
+    ACF_HIP_T_BF16 = 2,
+    ACF_HIP_T_F32 = 3
+};
+typedef struct acf_hip_image_desc {
+    int32_t dtype;    /* ACF_HIP_T_* */
+    int32_t channels; /* 1 or 3: the plan's d */
+    int64_t stride_n, stride_c, stride_y, stride_x; /* in elements, of an image indexed [n][c][y][x] (y = image row, x = image column) */
+} acf_hip_image_desc;
+ACF_HIP_API int acf_hip_pyramid_image(acf_hip_ctx* ctx, const void* frames_dev, int n_frames, const acf_hip_image_desc* desc);
+ACF_HIP_API int acf_hip_run_image(acf_hip_ctx* ctx, const void* frames_dev, int n_frames, const acf_hip_image_desc* desc);
+ACF_HIP_API int acf_hip_image_extent(const acf_hip_image_desc* desc, int h, int w, int n_frames, int64_t* first_elem, int64_t* last_elem);
+
 /* The apps' resize to a minimum object width (src/app/acf/acf.cpp:117-148 `Resizer`,
  * GPUDetectionPipeline.cpp:250-266 computeDetectionWidth): scale = float(winSize.width) /
  * float(minWidth); cv::resize(image, reduced, {}, scale, scale, scale < 1 ? INTER_AREA :
