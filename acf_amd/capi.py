@@ -159,6 +159,24 @@ class ImageDesc(C.Structure):
                 ("stride_n", C.c_int64), ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64)]
 
 
+# ACF_HIP_YUV_*: the named layouts acf_hip_yuv_layout builds descriptors for (not PIX_*)
+YUV_NV12, YUV_NV21, YUV_I420, YUV_YV12, YUV_I422, YUV_I444, YUV_YUYV, YUV_UYVY, YUV_YVYU = range(9)
+YUV_NAMES = {"nv12": YUV_NV12, "nv21": YUV_NV21, "i420": YUV_I420, "yv12": YUV_YV12, "i422": YUV_I422, "i444": YUV_I444,
+             "yuyv": YUV_YUYV, "uyvy": YUV_UYVY, "yvyu": YUV_YVYU}
+
+
+class YuvPlane(C.Structure):
+    """struct acf_hip_yuv_plane: where one plane's samples lie, in bytes from the base pointer."""
+
+    _fields_ = [("offset", C.c_int64), ("stride_n", C.c_int64), ("stride_row", C.c_int64), ("stride_px", C.c_int64)]
+
+
+class YuvDesc(C.Structure):
+    """struct acf_hip_yuv_desc: the Y, U and V planes of a video frame; sub_x / sub_y = log2 of the chroma subsampling (0 or 1)."""
+
+    _fields_ = [("y", YuvPlane), ("u", YuvPlane), ("v", YuvPlane), ("sub_x", C.c_int32), ("sub_y", C.c_int32)]
+
+
 _lib = None
 
 
@@ -206,6 +224,12 @@ def load():
         "acf_hip_pyramid_image": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc)], C.c_int),
         "acf_hip_run_image": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc)], C.c_int),
         "acf_hip_image_extent": ([C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+        "acf_hip_pyramid_yuv": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc)], C.c_int),
+        "acf_hip_run_yuv": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc)], C.c_int),
+        "acf_hip_yuv_to_rgb8": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(YuvDesc), C.c_void_p], C.c_int),
+        "acf_hip_yuv_extent": ([C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+        "acf_hip_yuv_layout": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(YuvDesc), C.POINTER(C.c_int64)], C.c_int),
+        "acf_hip_stream_open_yuv": ([ctx, C.POINTER(YuvDesc), C.c_int64, C.c_int, C.c_int], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
         "acf_hip_u8_frame_bytes": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)], C.c_int),
@@ -268,6 +292,7 @@ DECLARED_SYMBOLS = [
     "acf_hip_op_im_resample", "acf_hip_op_acf_detect1", "acf_hip_op_acf_detect1_u8", "acf_hip_thrs_u8", "acf_hip_op_evaluate",
     "acf_hip_evaluate_crops", "acf_hip_evaluate_crops_u8",
     "acf_hip_pyramid_image", "acf_hip_run_image", "acf_hip_image_extent",
+    "acf_hip_pyramid_yuv", "acf_hip_run_yuv", "acf_hip_yuv_to_rgb8", "acf_hip_yuv_extent", "acf_hip_yuv_layout", "acf_hip_stream_open_yuv",
 ]
 
 

@@ -353,6 +353,8 @@ struct acf_hip_ctx
     hipStream_t copyStream = nullptr;
     int stPix = 0, stStride = 0, stCap = 0, nextTicket = 0, nextCollect = 0;
     int64_t stFrameBytes = 0; // bytes between the frames of a submitted batch
+    bool stYuv = false;       // opened by acf_hip_stream_open_yuv: a batch runs through acf_hip_run_yuv with stYuvDesc
+    acf_hip_yuv_desc stYuvDesc{};
     // the plan's cascade (tables, model arrays, work queues, outputs); acf_hip_op_acf_detect1 builds and runs a state of its own
     CascState cs;
     BoxLevel* d_boxLevels = nullptr;
@@ -1833,8 +1835,27 @@ struct ImageSrc
     acf_hip_image_desc d;
 };
 
+// a YUV frame of three planes described by offsets and byte strides (acf_hip_pyramid_yuv)
+struct YuvFrames
+{
+    const uint8_t* base;
+    acf_hip_yuv_desc d;
+};
+
 using IngestKernel = void (*)(IngestArgs);
 using ImageKernel = void (*)(IngestArgs, ImageArgs);
+using YuvDescKernel = void (*)(IngestArgs, YuvDescSrc);
+
+// k_ingest_yuv<conversion, load form>: [YD_*][IG_*]
+static YuvDescKernel yuvDescKernel(int form, int mode)
+{
+    static const YuvDescKernel table[3][4] = {
+        { k_ingest_yuv<IG_PLANAR, YD_GENERIC>, k_ingest_yuv<IG_LUV_VEC, YD_GENERIC>, k_ingest_yuv<IG_LUV, YD_GENERIC>, k_ingest_yuv<IG_GRAY, YD_GENERIC> },
+        { k_ingest_yuv<IG_PLANAR, YD_PLANAR>, k_ingest_yuv<IG_LUV_VEC, YD_PLANAR>, k_ingest_yuv<IG_LUV, YD_PLANAR>, k_ingest_yuv<IG_GRAY, YD_PLANAR> },
+        { k_ingest_yuv<IG_PLANAR, YD_PACKED422>, k_ingest_yuv<IG_LUV_VEC, YD_PACKED422>, k_ingest_yuv<IG_LUV, YD_PACKED422>, k_ingest_yuv<IG_GRAY, YD_PACKED422> },
+    };
+    return table[form][mode];
+}
 
 // k_ingest_image<element type, conversion>: [ACF_HIP_T_*][IG_*]
 static ImageKernel imageKernel(int dtype, int mode)
@@ -2112,6 +2133,142 @@ int launchIngestImage(acf_hip_ctx* c, const ImageSrc& im, int nF, float* dst, in
     return ACF_HIP_OK;
 }
 
+// What is wrong with a YUV description by itself (acf_hip_yuv_extent, the YUV entries), or null
+static const char* yuvDescBad(const acf_hip_yuv_desc* d)
+{
+    if (!d)
+    {
+        return "null description";
+    }
+    if (d->sub_x < 0 || d->sub_x > 1 || d->sub_y < 0 || d->sub_y > 1)
+    {
+        return "sub_x and sub_y must be 0 or 1";
+    }
+    for (const acf_hip_yuv_plane* p : { &d->y, &d->u, &d->v })
+    {
+        if (p->stride_px < 1 || p->stride_row < 1)
+        {
+            return "stride_px and stride_row must be positive";
+        }
+        if (p->stride_n < 0)
+        {
+            return "negative stride_n";
+        }
+    }
+    return nullptr;
+}
+
+// first / last byte offset plane by plane (Y, U, V) that nF frames of h x w address
+static void yuvExtent(const acf_hip_yuv_desc& d, int h, int w, int nF, int64_t first[3], int64_t last[3])
+{
+    const acf_hip_yuv_plane* pl[3] = { &d.y, &d.u, &d.v };
+    for (int i = 0; i < 3; i++)
+    {
+        const int rows = i ? (h + d.sub_y) >> d.sub_y : h, cols = i ? (w + d.sub_x) >> d.sub_x : w;
+        first[i] = pl[i]->offset; // (no stride is negative)
+        last[i] = pl[i]->offset + int64_t(nF - 1) * pl[i]->stride_n + int64_t(rows - 1) * pl[i]->stride_row + int64_t(cols - 1) * pl[i]->stride_px;
+    }
+}
+
+static YuvDescSrc yuvDescSrc(const YuvFrames& f)
+{
+    YuvDescSrc s{};
+    s.base = f.base;
+    s.y = YuvPlane{ f.d.y.offset, f.d.y.stride_n, f.d.y.stride_row, f.d.y.stride_px };
+    s.u = YuvPlane{ f.d.u.offset, f.d.u.stride_n, f.d.u.stride_row, f.d.u.stride_px };
+    s.v = YuvPlane{ f.d.v.offset, f.d.v.stride_n, f.d.v.stride_row, f.d.v.stride_px };
+    s.subX = f.d.sub_x;
+    s.subY = f.d.sub_y;
+    return s;
+}
+
+// The load form of k_ingest_yuv for a description and a pointer: the vector forms where their conditions hold (kernels_input.hip.h),
+// else the byte form, which is right for every description.  YD_PACKED422 also fills in the macropixel's byte order.
+static int yuvLoadForm(YuvDescSrc& s)
+{
+    const uintptr_t at = reinterpret_cast<uintptr_t>(s.base);
+    const auto aligned = [&](const YuvPlane& p) { return (at + uintptr_t(p.off)) % 4 == 0 && p.sr % 4 == 0 && p.sn % 4 == 0; };
+    if (s.y.sp == 1 && s.u.sp == 1 && s.v.sp == 1 && aligned(s.y) && aligned(s.u) && aligned(s.v))
+    {
+        return YD_PLANAR;
+    }
+    if (s.subX == 1 && s.subY == 0 && s.y.sp == 2 && s.u.sp == 4 && s.v.sp == 4 && s.y.sr == s.u.sr && s.y.sr == s.v.sr && s.y.sn == s.u.sn &&
+        s.y.sn == s.v.sn)
+    {
+        const int64_t mp = std::min(s.y.off, std::min(s.u.off, s.v.off));
+        const int64_t yp = s.y.off - mp, up = s.u.off - mp, vp = s.v.off - mp;
+        // Y0, Y1, U, V take the four bytes of one aligned macropixel
+        if (yp <= 1 && up <= 3 && vp <= 3 && ((1 << yp) | (1 << (yp + 2)) | (1 << up) | (1 << vp)) == 15 && (at + uintptr_t(mp)) % 4 == 0 && s.y.sr % 4 == 0 &&
+            s.y.sn % 4 == 0)
+        {
+            s.mp = mp;
+            s.yPos = int(yp);
+            s.uPos = int(up);
+            s.vPos = int(vp);
+            return YD_PACKED422;
+        }
+    }
+    return YD_GENERIC;
+}
+
+// A description of an NV12 / NV21 frame as the 8-bit entry takes it (one row stride, interleaved chroma pairs, even sizes): the
+// YuvSrc of k_ingest_yuv420, which then runs it — the same kernel, so the same bits as acf_hip_run_u8(ACF_HIP_PIX_NV12 / _NV21)
+static bool yuvIsSemiPlanar(const YuvFrames& f, int H, int W, YuvSrc& out)
+{
+    const acf_hip_yuv_desc& d = f.d;
+    const int64_t c0 = std::min(d.u.offset, d.v.offset);
+    if (!(d.sub_x == 1 && d.sub_y == 1 && H % 2 == 0 && W % 2 == 0 && d.y.stride_px == 1 && d.u.stride_px == 2 && d.v.stride_px == 2 &&
+            std::max(d.u.offset, d.v.offset) == c0 + 1 && d.u.stride_row == d.y.stride_row && d.v.stride_row == d.y.stride_row && d.y.stride_row <= INT32_MAX &&
+            d.u.stride_n == d.y.stride_n && d.v.stride_n == d.y.stride_n))
+    {
+        return false;
+    }
+    out = YuvSrc{};
+    out.in = f.base + d.y.offset;
+    out.H = H;
+    out.W = W;
+    out.rowStride = int(d.y.stride_row);
+    out.vFirst = d.v.offset < d.u.offset;
+    out.chromaOff = c0 - d.y.offset;
+    out.in_fs = d.y.stride_n;
+    return true;
+}
+
+// The profile name of the kernel a YUV description runs with this base pointer (static strings: prof keeps the pointer)
+static const char* yuvKernelName(const YuvFrames& f, int H, int W)
+{
+    static const char* const names[3] = { "k_ingest_yuv_generic", "k_ingest_yuv_planar", "k_ingest_yuv_packed422" };
+    YuvSrc semi;
+    if (yuvIsSemiPlanar(f, H, W, semi))
+    {
+        return "k_ingest_yuv420";
+    }
+    YuvDescSrc s = yuvDescSrc(f);
+    return names[yuvLoadForm(s)];
+}
+
+// k_ingest_yuv (k_ingest_yuv420 for an NV12 / NV21-shaped description) over a batch: the YUV entry's frames -> planar f32 at dst
+int launchIngestYuv(acf_hip_ctx* c, const YuvFrames& f, int nF, float* dst, int64_t out_fs, bool convert)
+{
+    const Plan& pl = c->plan;
+    IngestArgs a{};
+    const int mode = ingestShared(c, dst, out_fs, convert, a);
+    const dim3 grid(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF);
+    YuvSrc semi;
+    if (yuvIsSemiPlanar(f, pl.H, pl.W, semi))
+    {
+        const bool aligned = reinterpret_cast<uintptr_t>(semi.in) % 4 == 0 && semi.rowStride % 4 == 0 && semi.chromaOff % 4 == 0 && semi.in_fs % 4 == 0;
+        hipLaunchKernelGGL(yuvIngestKernel(mode, aligned), grid, dim3(256), 0, c->stream, a, semi); // (even sizes: never IG_LUV)
+        LAUNCHCHK(c, "k_ingest_yuv420");
+        return ACF_HIP_OK;
+    }
+    YuvDescSrc s = yuvDescSrc(f);
+    const int form = yuvLoadForm(s);
+    hipLaunchKernelGGL(yuvDescKernel(form, mode), grid, dim3(256), 0, c->stream, a, s);
+    LAUNCHCHK(c, "k_ingest_yuv");
+    return ACF_HIP_OK;
+}
+
 // rgbConvert of nF frames of n pixels: `in` holds nIn planes a frame (frame stride in_fs), `out` the converted planes (out_fs).  LUV takes
 // the vector body iff n % 4 == 0 (rgbConvertMex.cpp:92,343); a 1-plane input is replicated first (chnsPyramid.cpp:234-244): gray from
 // it is k_rgb2gray<true>, ORIG / RGB k_replicate3.  The caller checks the launch.
@@ -2198,9 +2355,9 @@ static void clearRepairFlags(acf_hip_ctx* c)
 
 #include "pyramid_run.hip.h" // PyramidRun (acf_hip_pyramid's stages), pyramidBody
 
-static int pyramidImpl(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF, const ImageSrc* img = nullptr)
+static int pyramidImpl(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF, const ImageSrc* img = nullptr, const YuvFrames* yuv = nullptr)
 {
-    const int rc = pyramidBody(c, frames, u8, nF, img);
+    const int rc = pyramidBody(c, frames, u8, nF, img, yuv);
     if (rc && c && c->hasPlan && c->kids.empty())
     {
         clearRepairFlags(c);
@@ -2255,6 +2412,110 @@ int acf_hip_image_extent(const acf_hip_image_desc* d, int h, int w, int nF, int6
     }
     *first = lo;
     *last = hi;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_pyramid_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
+{
+    if (int rc = needCtx(c)) return rc;
+    if (!base || !desc)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv: null base or description");
+    }
+    YuvFrames f{ base, *desc };
+    return pyramidImpl(c, nullptr, nullptr, nF, nullptr, &f);
+}
+
+int acf_hip_run_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
+{
+    int rc = acf_hip_pyramid_yuv(c, base, nF, desc);
+    if (rc)
+    {
+        return rc;
+    }
+    return acf_hip_detect(c);
+}
+
+int acf_hip_yuv_to_rgb8(acf_hip_ctx* c, const uint8_t* base, int nF, int rows, int cols, const acf_hip_yuv_desc* desc, uint8_t* dst)
+{
+    if (int rc = needCtx(c)) return rc;
+    if (!base || !desc || !dst)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "yuv_to_rgb8: null base, description or destination");
+    }
+    if (const char* bad = yuvDescBad(desc))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("yuv_to_rgb8: ") + bad);
+    }
+    if (nF < 1 || nF > 65535 || rows < 1 || cols < 1)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "yuv_to_rgb8: n_frames 1 .. 65535, rows and cols >= 1");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    prof(c, c->stream, "k_yuv_to_rgb8");
+    hipLaunchKernelGGL(k_yuv_to_rgb8, dim3(cdiv(cols, 64), cdiv(rows, 4), nF), dim3(256), 0, c->stream, yuvDescSrc(YuvFrames{ base, *desc }), rows, cols, dst);
+    LAUNCHCHK(c, "k_yuv_to_rgb8");
+    return ACF_HIP_OK;
+}
+
+int acf_hip_yuv_extent(const acf_hip_yuv_desc* d, int h, int w, int nF, int64_t* first, int64_t* last)
+{
+    if (!first || !last || yuvDescBad(d) || h < 1 || w < 1 || nF < 1)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    yuvExtent(*d, h, w, nF, first, last);
+    return ACF_HIP_OK;
+}
+
+int acf_hip_yuv_layout(int layout, int h, int w, int rowStride, acf_hip_yuv_desc* out, int64_t* frameBytes)
+{
+    if (!out || !frameBytes || h < 1 || w < 1 || rowStride < 0 || layout < ACF_HIP_YUV_NV12 || layout > ACF_HIP_YUV_YVYU)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    const bool packed = layout >= ACF_HIP_YUV_YUYV, semi = layout <= ACF_HIP_YUV_NV21;
+    const int subX = layout == ACF_HIP_YUV_I444 ? 0 : 1, subY = (semi || layout == ACF_HIP_YUV_I420 || layout == ACF_HIP_YUV_YV12) ? 1 : 0;
+    const int64_t rowBytes = packed ? 2 * int64_t(w) : w;
+    const int64_t stride = rowStride > 0 ? rowStride : rowBytes;
+    if (stride < rowBytes || (subX && w % 2) || (subY && h % 2) || (!packed && !semi && stride % 2))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    acf_hip_yuv_desc d{};
+    d.sub_x = subX;
+    d.sub_y = subY;
+    int64_t fb;
+    if (packed)
+    {
+        // macropixels of four bytes: Y0 U Y1 V / U Y0 V Y1 / Y0 V Y1 U
+        const int yp = layout == ACF_HIP_YUV_UYVY ? 1 : 0, up = layout == ACF_HIP_YUV_YUYV ? 1 : (layout == ACF_HIP_YUV_UYVY ? 0 : 3),
+                  vp = layout == ACF_HIP_YUV_YUYV ? 3 : (layout == ACF_HIP_YUV_UYVY ? 2 : 1);
+        fb = stride * h;
+        d.y = acf_hip_yuv_plane{ yp, fb, stride, 2 };
+        d.u = acf_hip_yuv_plane{ up, fb, stride, 4 };
+        d.v = acf_hip_yuv_plane{ vp, fb, stride, 4 };
+    }
+    else if (semi)
+    {
+        const int64_t chroma = stride * h; // the tight rule of the 8-bit entry (u8Geom)
+        fb = chroma + stride * (h / 2);
+        const int vFirst = layout == ACF_HIP_YUV_NV21;
+        d.y = acf_hip_yuv_plane{ 0, fb, stride, 1 };
+        d.u = acf_hip_yuv_plane{ chroma + vFirst, fb, stride, 2 };
+        d.v = acf_hip_yuv_plane{ chroma + 1 - vFirst, fb, stride, 2 };
+    }
+    else
+    {
+        const int64_t cs = stride >> subX, plane = cs * (h >> subY), first = stride * h;
+        fb = first + 2 * plane;
+        const bool vFirst = layout == ACF_HIP_YUV_YV12;
+        d.y = acf_hip_yuv_plane{ 0, fb, stride, 1 };
+        d.u = acf_hip_yuv_plane{ first + (vFirst ? plane : 0), fb, cs, 1 };
+        d.v = acf_hip_yuv_plane{ first + (vFirst ? 0 : plane), fb, cs, 1 };
+    }
+    *out = d;
+    *frameBytes = fb;
     return ACF_HIP_OK;
 }
 
@@ -2592,6 +2853,31 @@ int acf_hip_stream_close(acf_hip_ctx* c)
     return ACF_HIP_OK;
 }
 
+// The slots of a stream (device input, device and pinned records, events) for batches of up to max_batch frames of frameBytes each;
+// replaces an open stream
+static int streamSlots(acf_hip_ctx* c, int64_t frameBytes, int cap, int depth)
+{
+    acf_hip_stream_close(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
+    c->stFrameBytes = frameBytes;
+    c->stCap = cap;
+    c->nextTicket = c->nextCollect = 0;
+    c->slots.resize(size_t(depth));
+    const size_t inBytes = size_t(c->maxBatch) * size_t(frameBytes);
+    const size_t recBytes = size_t(c->maxBatch) * (1 + 6 * size_t(cap)) * sizeof(int32_t);
+    for (auto& s : c->slots)
+    {
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.d_in), inBytes));
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.d_rec), recBytes));
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.h_rec), recBytes, hipHostMallocDefault));
+        HIPCHK(c, hipEventCreateWithFlags(&s.evH2D, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&s.evDone, hipEventDisableTiming));
+        s.ticket = -1;
+    }
+    return ACF_HIP_OK;
+}
+
 int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int depth)
 {
     if (int rc = needPlan(c, "stream_open")) return rc;
@@ -2614,27 +2900,47 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
     {
         return fail(c, ACF_HIP_E_INVALID, "stream_open: the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY");
     }
-    acf_hip_stream_close(c);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
+    c->stYuv = false;
     c->stPix = pix;
     c->stStride = g.stride;
-    c->stFrameBytes = g.frameStride;
-    c->stCap = cap;
-    c->nextTicket = c->nextCollect = 0;
-    c->slots.resize(size_t(depth));
-    const size_t inBytes = size_t(c->maxBatch) * size_t(g.frameStride);
-    const size_t recBytes = size_t(c->maxBatch) * (1 + 6 * size_t(cap)) * sizeof(int32_t);
-    for (auto& s : c->slots)
+    return streamSlots(c, g.frameStride, cap, depth);
+}
+
+int acf_hip_stream_open_yuv(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int cap, int depth)
+{
+    if (int rc = needPlan(c, "stream_open_yuv")) return rc;
+    if (!c->kids.empty())
     {
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.d_in), inBytes));
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s.d_rec), recBytes));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.h_rec), recBytes, hipHostMallocDefault));
-        HIPCHK(c, hipEventCreateWithFlags(&s.evH2D, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&s.evDone, hipEventDisableTiming));
-        s.ticket = -1;
+        return fail(c, ACF_HIP_E_UNSUPPORTED, "stream_open_yuv: not available with option \"streams\" > 1");
     }
-    return ACF_HIP_OK;
+    if (depth < 2 || depth > 8 || cap <= 0)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv: depth must be 2..8, cap > 0");
+    }
+    if (const char* bad = yuvDescBad(desc))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("stream_open_yuv: ") + bad);
+    }
+    if (c->plan.d_in != 3 || c->rz.on)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv: the plan's input planes (d) must be 3, and not with acf_hip_set_input_resize");
+    }
+    int64_t first[3], last[3];
+    yuvExtent(*desc, c->plan.H, c->plan.W, 1, first, last);
+    for (int i = 0; i < 3; i++)
+    {
+        if (first[i] < 0 || last[i] >= frameBytes)
+        {
+            return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv: every plane of a frame must lie in [0, frame_bytes)");
+        }
+    }
+    if (desc->y.stride_n != frameBytes || desc->u.stride_n != frameBytes || desc->v.stride_n != frameBytes)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv: stride_n of every plane must be frame_bytes");
+    }
+    c->stYuv = true;
+    c->stYuvDesc = *desc;
+    return streamSlots(c, frameBytes, cap, depth);
 }
 
 int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, int* ticket)
@@ -2656,7 +2962,7 @@ int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, in
     HIPCHK(c, hipMemcpyAsync(s.d_in, frames_host, bytes, hipMemcpyHostToDevice, c->copyStream));
     HIPCHK(c, hipEventRecord(s.evH2D, c->copyStream));
     HIPCHK(c, hipStreamWaitEvent(c->stream, s.evH2D, 0));
-    int rc = acf_hip_run_u8(c, s.d_in, nF, c->stPix, c->stStride);
+    int rc = c->stYuv ? acf_hip_run_yuv(c, s.d_in, nF, &c->stYuvDesc) : acf_hip_run_u8(c, s.d_in, nF, c->stPix, c->stStride);
     if (rc)
     {
         return rc;

@@ -732,6 +732,226 @@ __global__ void __launch_bounds__(256) k_ingest_yuv420(IngestArgs a, YuvSrc s)
 }
 
 // ------------------------------------------------------------------------
+// YUV frames of three planes, each with its own offset and byte strides (acf_hip_yuv_desc: I420 / YV12 / I422 / I444 planar, YUYV /
+// UYVY / YVYU packed 4:2:2, NV12 / NV21, separately allocated planes, odd sizes) -> 8-bit R, G, B by yuv_chroma / yuv_rgb8 above.
+// Pixel (r, c) of frame n: Y at y.off + n * y.sn + r * y.sr + c * y.sp, U and V likewise at (r >> subY, c >> subX): no interpolation.
+// The cvtColor codes for I420 / YV12 / YUY2 / UYVY / YVYU share the fixed-point helpers of NV12 / NV21 in OpenCV's published
+// imgproc/src/color_yuv.simd.hpp; I422 / I444 are the same per-pixel formula — PARITY UNPINNED.
+// ------------------------------------------------------------------------
+struct YuvPlane
+{
+    int64_t off, sn, sr, sp; // bytes: first sample, between frames, between the plane's rows, between its samples
+};
+struct YuvDescSrc
+{
+    const uint8_t* base;
+    YuvPlane y, u, v;
+    int subX, subY;        // 0 or 1
+    int yPos, uPos, vPos;  // YD_PACKED422: byte of Y0 (Y1 two further), U, V inside the macropixel at `mp`
+    int64_t mp;            // YD_PACKED422: offset of the first macropixel (4-aligned with base)
+};
+enum
+{
+    YD_GENERIC = 0,   // byte loads, any strides
+    YD_PLANAR = 1,    // all three sp == 1; base + off, sr, sn multiples of 4: dword loads
+    YD_PACKED422 = 2  // 4:2:2 macropixels of four bytes; base + mp, sr, sn multiples of 4: one dword = two pixels
+};
+
+// The descriptor form of k_yuv420_to_rgb8: tight packed RGB bytes [rows][cols][3] per frame.  One thread per pixel; byte accesses.
+__global__ void __launch_bounds__(256) k_yuv_to_rgb8(YuvDescSrc s, int rows, int cols, uint8_t* __restrict__ dst)
+{
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), r = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= cols || r >= rows)
+    {
+        return;
+    }
+    const int64_t n = blockIdx.z;
+    const int cr = r >> s.subY, cc = c >> s.subX;
+    const uint8_t* __restrict__ B = s.base;
+    const int Y = B[s.y.off + n * s.y.sn + int64_t(r) * s.y.sr + int64_t(c) * s.y.sp];
+    const int U = B[s.u.off + n * s.u.sn + int64_t(cr) * s.u.sr + int64_t(cc) * s.u.sp];
+    const int V = B[s.v.off + n * s.v.sn + int64_t(cr) * s.v.sr + int64_t(cc) * s.v.sp];
+    int R, G, Bl;
+    yuv_rgb8(Y, yuv_chroma(U, V), R, G, Bl);
+    uint8_t* d = dst + ((n * rows + r) * cols + c) * 3;
+    d[0] = uint8_t(R);
+    d[1] = uint8_t(G);
+    d[2] = uint8_t(Bl);
+}
+
+// The hot path: k_ingest_yuv420's shape (a workgroup owns 64 x 64 pixels; the load phase runs lanes along the rows of each plane into
+// LDS byte tiles; then a lane takes four consecutive image-y of one image-x, converts and stores one float4 a plane through
+// ingest_convert / ingest_store) for any acf_hip_yuv_desc, so the planes are those of k_ingest_u8 on the converted RGB frame, bit
+// for bit.  Sizes may be odd (IG_LUV, the scalar rgb2luv body, is reachable here): the tile then has ceil(ny / 2^subY) chroma
+// rows of ceil(nx / 2^subX) samples.  a.in / cpp / ro / go / bo / rowStride / in_fs of IngestArgs are not read.
+//
+// Load forms (FORM, chosen on the host from the descriptor and the base's alignment alone; all give the same tiles):
+//   YD_PLANAR     every plane's rows as dwords by consecutive lanes; the nb % 4 bytes at a row's end one by one
+//   YD_PACKED422  a lane's dword is one macropixel = two pixels: Y0, Y1 to the luma tile, U and V to theirs; the half macropixel
+//                 at an odd row end byte by byte
+//   YD_GENERIC    one sample a lane, any strides
+// No load covers a byte outside the span the same row of the same plane addresses (YD_PACKED422: of the macropixels the row
+// addresses), so a plane may end with its allocation.
+//
+// LDS: three byte tiles (Y, U, V) of 64 slots x 17 dwords; luma row r in slot (r & 3) * 16 + (r >> 2) as k_ingest_yuv420, chroma
+// row r in the same slot when subY == 0, in (r & 1) * 16 + (r >> 1) when subY == 1.  Bank = dword address % 32 per 32-lane half:
+//   convert phase (byte reads)  a half is 16 row-quads x 2 adjacent image-x, which share a dword of each tile (columns xx or
+//                               xx >> 1): read j takes luma rows 4k + j = slots 16j + k and chroma rows (4k + j) >> subY = slots
+//                               16j + k or 16(j >> 1) + k, k = 0 .. 15: 17k mod 32: 16 distinct banks, conflict-free, for each tile
+//   YD_PLANAR (dword writes)    luma, and chroma with subX == 0: a half writes the 16 dwords of rows r, r + 1 (r even), 16 slots =
+//                               272 = 16 (mod 32) dwords apart: 32 distinct banks.  Chroma with subX == 1: the 8 dwords of rows
+//                               r .. r + 3: slots 0, 16, 1, 17 (subY == 1) or 0, 16, 32, 48 (subY == 0) -> bank offsets 0, 16, 17,
+//                               1 or 0, 16, 0, 16: 2-way (no extra cycles on ds_write_b32)
+//   YD_PACKED422                a half is the 32 macropixels of one row: 16-bit luma writes two lanes a dword, chroma byte writes
+//                               four lanes a dword, over 16 and 8 distinct banks
+//   YD_GENERIC (byte writes)    a half writes 32 consecutive samples of one row: four lanes a dword, 8 distinct banks
+// (degrees derived from the address maps above with the bank rule; whether sub-dword writes of several lanes to one dword
+// serialise, and the SQ_LDS_BANK_CONFLICT counter: not measured.)  3 x 64 x 17 dwords = 13056 bytes.
+// ------------------------------------------------------------------------
+constexpr int YD_TILE = IG_T * YG_PITCH; // bytes between the Y, U and V tiles
+
+__device__ __forceinline__ int yd_slot(int r, int subY)
+{
+    return subY ? (r & 1) * 16 + (r >> 1) : (r & 3) * 16 + (r >> 2);
+}
+
+// YD_PLANAR: rows x nb bytes of one plane (first byte p, sr apart) to a tile; 1 << lg dwords a tile row, PASSES * 256 >= rows << lg
+// (constant trip counts, so that the loads of all the passes are in flight together)
+template <int PASSES>
+__device__ __forceinline__ void yd_load_rows_vec(const uint8_t* __restrict__ p, int64_t sr, int rows, int nb, int lg, int slotSubY, uint32_t* tileW)
+{
+#pragma unroll
+    for (int pass = 0; pass < PASSES; pass++)
+    {
+        const int i = threadIdx.x + pass * 256;
+        const int row = i >> lg, j = i & ((1 << lg) - 1);
+        if (row < rows && 4 * j < nb)
+        {
+            const uint8_t* rp = p + int64_t(row) * sr + 4 * j;
+            uint32_t v;
+            if (4 * j + 4 <= nb)
+            {
+                v = *reinterpret_cast<const uint32_t*>(rp);
+            }
+            else
+            {
+                v = 0;
+                for (int b = 0; b < nb - 4 * j; b++) // the row's tail: byte by byte
+                {
+                    v |= uint32_t(rp[b]) << (8 * b);
+                }
+            }
+            tileW[yd_slot(row, slotSubY) * (YG_PITCH / 4) + j] = v;
+        }
+    }
+}
+
+// YD_GENERIC: rows x cols samples of one plane (sp apart in a row); 1 << lg lanes a tile row
+__device__ __forceinline__ void yd_load_rows_generic(const uint8_t* __restrict__ p, int64_t sr, int64_t sp, int rows, int cols, int lg, int slotSubY, uint8_t* tile)
+{
+    for (int i = threadIdx.x; i < (rows << lg); i += 256)
+    {
+        const int row = i >> lg, col = i & ((1 << lg) - 1);
+        if (col < cols)
+        {
+            tile[yd_slot(row, slotSubY) * YG_PITCH + col] = p[int64_t(row) * sr + int64_t(col) * sp];
+        }
+    }
+}
+
+template <int MODE, int FORM>
+__global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
+{
+    __shared__ uint32_t tileW[3 * YD_TILE / 4];
+    uint8_t* tile = reinterpret_cast<uint8_t*>(tileW);
+    const int x0 = blockIdx.x * IG_T, y0 = blockIdx.y * IG_T;
+    const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0);
+    const int subX = s.subX, subY = s.subY;
+    const int cnx = (nx + subX) >> subX, cny = (ny + subY) >> subY; // chroma samples a tile row, chroma rows (x0, y0 are even)
+    const int64_t n = blockIdx.z;
+    if (FORM == YD_PACKED422)
+    {
+        // subX == 1, subY == 0; the three planes share sr and sn; base + mp, sr, sn are multiples of 4 (host-checked) and x0 * 2 is
+        const uint8_t* src = s.base + s.mp + n * s.y.sn + int64_t(y0) * s.y.sr + int64_t(x0) * 2;
+        const int sy0 = 8 * s.yPos, su = 8 * s.uPos, sv = 8 * s.vPos;
+        uint16_t* tile16 = reinterpret_cast<uint16_t*>(tile);
+#pragma unroll 4
+        for (int pass = 0; pass < IG_T * 32 / 256; pass++)
+        {
+            const int i = threadIdx.x + pass * 256;
+            const int row = i >> 5, q = i & 31;
+            if (row < ny && 2 * q < nx)
+            {
+                const uint8_t* rp = src + int64_t(row) * s.y.sr + 4 * q;
+                uint32_t Y0, Y1, U, V;
+                if (2 * q + 1 < nx)
+                {
+                    const uint32_t w = *reinterpret_cast<const uint32_t*>(rp);
+                    Y0 = (w >> sy0) & 255;
+                    Y1 = (w >> (sy0 + 16)) & 255;
+                    U = (w >> su) & 255;
+                    V = (w >> sv) & 255;
+                }
+                else
+                {
+                    Y0 = rp[s.yPos]; // an odd row's last pixel: its three bytes only
+                    Y1 = 0;
+                    U = rp[s.uPos];
+                    V = rp[s.vPos];
+                }
+                const int at = yd_slot(row, 0) * YG_PITCH;
+                tile16[(at >> 1) + q] = uint16_t(Y0 | (Y1 << 8));
+                tile[YD_TILE + at + q] = uint8_t(U);
+                tile[2 * YD_TILE + at + q] = uint8_t(V);
+            }
+        }
+    }
+    else
+    {
+        const uint8_t* py = s.base + s.y.off + n * s.y.sn + int64_t(y0) * s.y.sr + int64_t(x0) * s.y.sp;
+        const uint8_t* pu = s.base + s.u.off + n * s.u.sn + int64_t(y0 >> subY) * s.u.sr + int64_t(x0 >> subX) * s.u.sp;
+        const uint8_t* pv = s.base + s.v.off + n * s.v.sn + int64_t(y0 >> subY) * s.v.sr + int64_t(x0 >> subX) * s.v.sp;
+        if (FORM == YD_PLANAR)
+        {
+            // sp == 1; base + off, sr, sn of every plane are multiples of 4 (host-checked) and x0 >> subX is a multiple of 32
+            yd_load_rows_vec<4>(py, s.y.sr, ny, nx, 4, 0, tileW);
+            yd_load_rows_vec<4>(pu, s.u.sr, cny, cnx, 4 - subX, subY, tileW + YD_TILE / 4);
+            yd_load_rows_vec<4>(pv, s.v.sr, cny, cnx, 4 - subX, subY, tileW + 2 * YD_TILE / 4);
+        }
+        else
+        {
+            yd_load_rows_generic(py, s.y.sr, s.y.sp, ny, nx, 6, 0, tile);
+            yd_load_rows_generic(pu, s.u.sr, s.u.sp, cny, cnx, 6 - subX, subY, tile + YD_TILE);
+            yd_load_rows_generic(pv, s.v.sr, s.v.sp, cny, cnx, 6 - subX, subY, tile + 2 * YD_TILE);
+        }
+    }
+    __syncthreads();
+    const int yq = (threadIdx.x & 15) * 4;
+    const float sc = float(1.0 / 255.0);
+    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
+    const int64_t np = int64_t(a.H) * a.W;
+    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
+    {
+        float o[3][4];
+        YuvChroma c{};
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            // rows beyond the tile (yq + j >= ny) convert whatever the LDS holds (8-bit R, G, B whatever it is): never stored
+            if (j == 0 || (j >> subY) != ((j - 1) >> subY)) // a new chroma row (uniform: subY is)
+            {
+                const int at = yd_slot((yq + j) >> subY, subY) * YG_PITCH + (xx >> subX);
+                c = yuv_chroma(tile[YD_TILE + at], tile[2 * YD_TILE + at]);
+            }
+            int r, g, b;
+            yuv_rgb8(tile[yd_slot(yq + j, 0) * YG_PITCH + xx], c, r, g, b);
+            ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
+        }
+        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
+    }
+}
+
+// ------------------------------------------------------------------------
 // convTri1 with the pyramid's in-place aliasing (toolbox/convConst.cpp:445-525;
 // chnsCompute.cpp:239, chnsPyramid.cpp:404).
 //

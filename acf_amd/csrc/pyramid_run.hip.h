@@ -191,6 +191,7 @@ struct PyramidRun
 
     int ingest(const PackedSrc* u8, bool& ingestConverted);
     int ingestImage(const ImageSrc& im, bool& ingestConverted);
+    int ingestYuv(const YuvFrames& yf, bool& ingestConverted);
     using IngestLaunch = std::function<int(float* dst, int64_t out_fs, bool convert)>;
     int ingestPlanes(const char* kernel, bool& ingestConverted, const IngestLaunch& launch);
     int colour(bool ingestConverted);
@@ -325,6 +326,26 @@ int PyramidRun::ingestImage(const ImageSrc& im, bool& ingestConverted)
     }
     return ingestPlanes("k_ingest_image", ingestConverted,
         [&](float* dst, int64_t out_fs, bool convert) { return launchIngestImage(c, im, nF, dst, out_fs, convert); });
+}
+
+// The video frame entry for three-plane YUV descriptions: cvtColor's BT.601 integer conversion (restated, kernels_input.hip.h), then
+// the 8-bit image entry (ACF.cpp:114-119,135-141; MatP.cpp:51-73), in one kernel
+int PyramidRun::ingestYuv(const YuvFrames& yf, bool& ingestConverted)
+{
+    if (const char* bad = yuvDescBad(&yf.d))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_yuv: ") + bad);
+    }
+    if (d_in != 3)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv: the plan's input planes (d) must be 3");
+    }
+    if (c->rz.on)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv: not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)");
+    }
+    return ingestPlanes(yuvKernelName(yf, H, W), ingestConverted,
+        [&](float* dst, int64_t out_fs, bool convert) { return launchIngestYuv(c, yf, nF, dst, out_fs, convert); });
 }
 
 // ---- colour conversion, once at full resolution (chnsPyramid.cpp:230-263)
@@ -1103,13 +1124,13 @@ int PyramidRun::levelsWithImageLambdas()
     return ACF_HIP_OK;
 }
 
-int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF, const ImageSrc* img)
+int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF, const ImageSrc* img, const YuvFrames* yuv)
 {
     if (c && !c->kids.empty())
     {
-        if (u8 || img)
+        if (u8 || img || yuv)
         {
-            return fail(c, ACF_HIP_E_UNSUPPORTED, std::string(img ? "pyramid_image" : "pyramid_u8") + ": not available with option \"streams\" > 1");
+            return fail(c, ACF_HIP_E_UNSUPPORTED, std::string(yuv ? "pyramid_yuv" : (img ? "pyramid_image" : "pyramid_u8")) + ": not available with option \"streams\" > 1");
         }
         if (!frames || nF <= 0 || nF > c->maxBatch)
         {
@@ -1126,7 +1147,7 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
         return rc;
     }
     if (int rc = needPlan(c, "pyramid")) return rc;
-    if ((!frames && !u8 && !img) || (u8 && !u8->frames) || (img && !img->frames) || nF <= 0 || nF > c->maxBatch)
+    if ((!frames && !u8 && !img && !yuv) || (u8 && !u8->frames) || (img && !img->frames) || (yuv && !yuv->base) || nF <= 0 || nF > c->maxBatch)
     {
         return fail(c, ACF_HIP_E_INVALID, "pyramid: n_frames out of range");
     }
@@ -1135,7 +1156,8 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
     int rc;
     PyramidRun run(c, frames, nF);
     bool ingestConverted = false; // the 8-bit ingest wrote the converted colour planes itself
-    if ((u8 && (rc = run.ingest(u8, ingestConverted))) || (img && (rc = run.ingestImage(*img, ingestConverted))))
+    if ((u8 && (rc = run.ingest(u8, ingestConverted))) || (img && (rc = run.ingestImage(*img, ingestConverted))) ||
+        (yuv && (rc = run.ingestYuv(*yuv, ingestConverted))))
     {
         return rc;
     }

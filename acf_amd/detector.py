@@ -213,6 +213,70 @@ class HipDetector:
         self._chk(self.lib.acf_hip_op_yuv420_to_rgb(self.ctx, frame.ctypes.data, rows, cols, pix, row_stride, chroma_offset, out.ctypes.data))
         return out
 
+    # ---- YUV frames of three planes described by offsets and byte strides (acf_hip_pyramid_yuv / run_yuv): I420 / YV12 / I422 /
+    # I444, packed 4:2:2, NV12 / NV21, separately allocated planes
+    @staticmethod
+    def yuv_desc(layout, H, W, row_stride=0):
+        """(capi.YuvDesc, frame bytes) of a named layout: capi.YUV_* or its name ("i420", "yuyv", ...); host arithmetic."""
+        code = capi.YUV_NAMES.get(layout.lower(), -1) if isinstance(layout, str) else layout
+        desc, fb = capi.YuvDesc(), C.c_int64()
+        rc = capi.load().acf_hip_yuv_layout(code, H, W, row_stride, C.byref(desc), C.byref(fb))
+        if rc:
+            raise HipError(rc, "acf_hip_yuv_layout(%r, %d x %d, stride %d)" % (layout, H, W, row_stride))
+        return desc, fb.value
+
+    @staticmethod
+    def yuv_extent(desc, h, w, n):
+        """([first Y, U, V], [last Y, U, V]): the lowest and highest byte offset from the base a call reads of each plane."""
+        lo, hi = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        rc = capi.load().acf_hip_yuv_extent(C.byref(desc), h, w, n, lo, hi)
+        if rc:
+            raise HipError(rc, "acf_hip_yuv_extent")
+        return list(lo), list(hi)
+
+    def pyramid_yuv(self, base, n, desc):
+        """base: a torch uint8 CUDA tensor (its first byte is the base; it need not be contiguous) or a device pointer."""
+        self._chk(self.lib.acf_hip_pyramid_yuv(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, C.byref(desc)))
+
+    def run_yuv(self, base, n, desc):
+        self._chk(self.lib.acf_hip_run_yuv(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, C.byref(desc)))
+
+    @staticmethod
+    def yuv_planes_desc(y, u, v, sub_x, sub_y):
+        """(base pointer, n, capi.YuvDesc) of three torch uint8 device tensors [n, rows, cols] (or [rows, cols]) wherever they lie:
+        Y is the base, U and V are described by their distance from it (which may be negative) and their own strides."""
+        def plane(t):
+            if t.dim() == 2:
+                t = t[None]
+            if t.dim() != 3 or not t.is_cuda or t.element_size() != 1:
+                raise HipError(capi.E_INVALID, "run_yuv_planes: uint8 device tensors [n, rows, cols]")
+            return t
+        y, u, v = plane(y), plane(u), plane(v)
+        if not (y.shape[0] == u.shape[0] == v.shape[0]):
+            raise HipError(capi.E_INVALID, "run_yuv_planes: the planes hold different numbers of frames")
+        base = y.data_ptr()
+        mk = lambda t: capi.YuvPlane(t.data_ptr() - base, t.stride(0) if t.shape[0] > 1 else 0, t.stride(1), t.stride(2))
+        return base, y.shape[0], capi.YuvDesc(mk(y), mk(u), mk(v), sub_x, sub_y)
+
+    def run_yuv_planes(self, y, u, v, sub_x=1, sub_y=1):
+        """Three separately allocated planes (a software decoder's frame): y [n, H, W], u and v [n, ceil(H / 2^sub_y), ceil(W / 2^sub_x)]."""
+        base, n, desc = self.yuv_planes_desc(y, u, v, sub_x, sub_y)
+        self.run_yuv(base, n, desc)
+
+    def yuv_to_rgb8(self, base, n, rows, cols, desc):
+        """The conversion alone on the device -> torch uint8 CUDA tensor [n][rows][cols][3] (acf_hip_yuv_to_rgb8; no model or plan)."""
+        import torch
+        out = torch.empty((n, rows, cols, 3), dtype=torch.uint8, device="cuda")
+        self._chk(self.lib.acf_hip_yuv_to_rgb8(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, rows, cols, C.byref(desc),
+                                               C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return out
+
+    def stream_open_yuv(self, desc, frame_bytes, cap=1024, depth=2):
+        """The streaming front end for host frames of frame_bytes each, described by desc (stride_n == frame_bytes)."""
+        self._chk(self.lib.acf_hip_stream_open_yuv(self.ctx, C.byref(desc), frame_bytes, cap, depth))
+        self._stream_cap = cap
+
     # ---- the apps' resize to a minimum object width (acf.cpp:117-148 Resizer) in front of the 8-bit entries
     @staticmethod
     def resize_scale(win_width, min_width):

@@ -587,6 +587,39 @@ int HipDetector::detectImages(const void* framesDev, int nFrames, int rows, int 
     return 0;
 }
 
+int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc& desc, std::vector<RectVec>& objects,
+    std::vector<RealVec>* scores)
+{
+    ensurePlan(rows, cols, 3, nFrames);
+    syncNms();
+    check(m_api->acf_hip_run_yuv(m_ctx, baseDev, nFrames, &desc), "acf_hip_run_yuv");
+    objects.assign(size_t(nFrames), RectVec());
+    if (scores)
+    {
+        scores->assign(size_t(nFrames), RealVec());
+    }
+    for (int f = 0; f < nFrames; f++)
+    {
+        fetch(f, objects[size_t(f)], scores ? &(*scores)[size_t(f)] : nullptr);
+    }
+    return 0;
+}
+
+acf_hip_yuv_desc HipDetector::yuvLayout(int layout, int rows, int cols, int rowStrideBytes, size_t* frameBytes)
+{
+    acf_hip_yuv_desc d;
+    int64_t n = 0;
+    if (hip::load().acf_hip_yuv_layout(layout, rows, cols, rowStrideBytes, &d, &n))
+    {
+        throw Exception(ACF_HIP_E_INVALID, "yuvLayout: unknown layout, empty frame, row stride smaller than a row or odd for a planar layout, or an odd subsampled size");
+    }
+    if (frameBytes)
+    {
+        *frameBytes = size_t(n);
+    }
+    return d;
+}
+
 int HipDetector::operator()(const uint8_t* packed, int rows, int cols, int pix, int rowStrideBytes, RectVec& objects, RealVec* scores)
 {
     if (!packed || rows <= 0 || cols <= 0)
@@ -661,6 +694,23 @@ void HipDetector::streamOpen(int rows, int cols, int pix, int rowStrideBytes, in
     m_streamCap = maxDetectionsPerFrame;
     m_streamPix = pix;
     m_streamStride = rowStrideBytes;
+}
+
+void HipDetector::streamOpenYuv(int rows, int cols, const acf_hip_yuv_desc& desc, size_t frameBytes, int maxBatch, int depth, int maxDetectionsPerFrame)
+{
+    if (m_minObjectWidth >= 0 && inputScale() != 1.f)
+    {
+        throw Exception(ACF_HIP_E_UNSUPPORTED, "streamOpenYuv: not with setMinObjectWidth (the input resize takes the packed 8-bit entries' frames)");
+    }
+    ensurePlan(rows, cols, 3, maxBatch);
+    (void)m_api->acf_hip_stream_close(m_ctx);
+    check(m_api->acf_hip_set_input_resize(m_ctx, 0, 0, 1.0), "acf_hip_set_input_resize");
+    m_srcRows = rows;
+    m_srcCols = cols;
+    check(m_api->acf_hip_stream_open_yuv(m_ctx, &desc, int64_t(frameBytes), maxDetectionsPerFrame, depth), "acf_hip_stream_open_yuv");
+    m_streamCap = maxDetectionsPerFrame;
+    m_streamPix = -1; // (operator()(packed) reopens its own stream)
+    m_streamStride = 0;
 }
 
 size_t HipDetector::u8FrameBytes(int pix, int rows, int cols, int rowStrideBytes)

@@ -295,6 +295,14 @@ public:
     int detectImages(const void* framesDev, int nFrames, int rows, int cols, const acf_hip_image_desc& desc,
         std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
 
+    // Batch of YUV video frames of three planes in memory the device reads, each plane described by its own offset and byte strides
+    // (I420 / YV12 / I422 / I444, packed 4:2:2, NV12 / NV21, three separately allocated planes): include/acf_hip.h, acf_hip_run_yuv.
+    // The conversion is cvtColor's BT.601 integer formula (restated, parity unpinned), on the device, fused into the ingest.
+    int detectYuv(const uint8_t* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc& desc,
+        std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
+    // the descriptor of a named layout (ACF_HIP_YUV_*) of rows x cols; *frameBytes = the distance to the next frame
+    static acf_hip_yuv_desc yuvLayout(int layout, int rows, int cols, int rowStrideBytes = 0, size_t* frameBytes = nullptr);
+
     // Streaming front end (the role of GPUDetectionPipeline::runFast's two-frame FIFO, GPUDetectionPipeline.cpp:357-437):
     // batches of packed 8-bit frames are copied to the device while the previous batch computes.
     //   streamOpen(rows, cols, pix, stride, maxBatch, depth); t = streamSubmit(frames, n); streamCollect(t, objects, &scores);
@@ -302,6 +310,8 @@ public:
     // collected in submission order.  At most maxDetectionsPerFrame (streamOpen) boxes per frame come back, in the
     // reference's order, before NMS/prune are applied exactly as in operator().
     void streamOpen(int rows, int cols, int pix, int rowStrideBytes, int maxBatch, int depth = 2, int maxDetectionsPerFrame = 4096);
+    // the same for host frames of frameBytes each described by a YUV descriptor (acf_hip_stream_open_yuv); submit / collect as above
+    void streamOpenYuv(int rows, int cols, const acf_hip_yuv_desc& desc, size_t frameBytes, int maxBatch, int depth = 2, int maxDetectionsPerFrame = 4096);
     int streamSubmit(const uint8_t* frames, int nFrames);
     // bytes from one tight frame of layout `pix` to the next: what a batch for streamSubmit / a frame for operator()(packed) holds
     static size_t u8FrameBytes(int pix, int rows, int cols, int rowStrideBytes = 0);

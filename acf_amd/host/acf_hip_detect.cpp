@@ -5,6 +5,9 @@
 //                  [--luv] [--nms] [--batch] [--via-pyramid] [--max-count K] [--prune-ratio R]
 //   acf_hip_detect --model m.acfm --frames f.u8 --u8 rgb|bgr|rgba|bgra|gray|nv12|nv21 --rows H --cols W --count N [--stream B] [--min-width M] ...
 //                  packed 8-bit upright frames (nv12 / nv21: tight YUV 4:2:0 video frames); --stream B: batches of B frames through streamSubmit/streamCollect
+//   acf_hip_detect --model m.acfm --frames f.yuv --yuv i420|yv12|i422|i444|yuyv|uyvy|yvyu|nv12|nv21 --rows H --cols W --count N [--stream B]
+//                  tight YUV video frames of the named layout through detectYuv (one batch; the frames in page-locked memory, which the
+//                  device reads), or --stream B through streamOpenYuv / streamSubmit / streamCollect
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
@@ -199,6 +202,68 @@ int main(int argc, char** argv)
                 std::printf("level %s %dx%d %016llx\n", t.c_str(), m.cols(), m.rows(), static_cast<unsigned long long>(fnv(m)));
                 return 0;
             });
+        }
+        if (a.count("yuv"))
+        {
+            static const std::map<std::string, int> kYuv = { { "nv12", ACF_HIP_YUV_NV12 }, { "nv21", ACF_HIP_YUV_NV21 }, { "i420", ACF_HIP_YUV_I420 },
+                { "yv12", ACF_HIP_YUV_YV12 }, { "i422", ACF_HIP_YUV_I422 }, { "i444", ACF_HIP_YUV_I444 }, { "yuyv", ACF_HIP_YUV_YUYV }, { "uyvy", ACF_HIP_YUV_UYVY },
+                { "yvyu", ACF_HIP_YUV_YVYU } };
+            const int H = std::stoi(a.at("rows")), W = std::stoi(a.at("cols")), cnt = std::stoi(a.at("count"));
+            size_t per = 0;
+            const acf_hip_yuv_desc desc = HipDetector::yuvLayout(kYuv.at(a["yuv"]), H, W, 0, &per);
+            const int B = a.count("stream") ? std::stoi(a["stream"]) : cnt, depth = 2;
+            uint8_t* pin[2] = { static_cast<uint8_t*>(HipDetector::pinnedAlloc(per * size_t(B))), static_cast<uint8_t*>(HipDetector::pinnedAlloc(per * size_t(B))) };
+            std::ifstream is(a.at("frames"), std::ios::binary);
+            auto readBatch = [&](uint8_t* dst, int n) {
+                is.read(reinterpret_cast<char*>(dst), std::streamsize(per * size_t(n)));
+                if (!is)
+                {
+                    throw std::runtime_error("short frames file");
+                }
+            };
+            std::vector<HipDetector::RectVec> objs;
+            std::vector<HipDetector::RealVec> scores;
+            if (a.count("stream"))
+            {
+                det.streamOpenYuv(H, W, desc, per, B, depth, 8192);
+                std::vector<std::pair<int, int>> inflight; // ticket, first frame
+                auto drain = [&]() {
+                    det.streamCollect(inflight.front().first, objs, &scores);
+                    for (size_t f = 0; f < objs.size(); f++)
+                    {
+                        printFrame(inflight.front().second + int(f), objs[f], scores[f]);
+                    }
+                    inflight.erase(inflight.begin());
+                };
+                int k = 0;
+                for (int f0 = 0; f0 < cnt; f0 += B, k++)
+                {
+                    if (int(inflight.size()) == depth)
+                    {
+                        drain();
+                    }
+                    const int n = std::min(B, cnt - f0);
+                    readBatch(pin[k % 2], n);
+                    inflight.emplace_back(det.streamSubmit(pin[k % 2], n), f0);
+                }
+                while (!inflight.empty())
+                {
+                    drain();
+                }
+                det.streamClose();
+            }
+            else
+            {
+                readBatch(pin[0], cnt);
+                det.detectYuv(pin[0], cnt, H, W, desc, objs, &scores);
+                for (int f = 0; f < cnt; f++)
+                {
+                    printFrame(f, objs[size_t(f)], scores[size_t(f)]);
+                }
+            }
+            HipDetector::pinnedFree(pin[0]);
+            HipDetector::pinnedFree(pin[1]);
+            return 0;
         }
         if (a.count("u8"))
         {

@@ -45,6 +45,12 @@ struct Api
     ACF_HIP_FN(acf_hip_pyramid_image)
     ACF_HIP_FN(acf_hip_run_image)
     ACF_HIP_FN(acf_hip_image_extent)
+    ACF_HIP_FN(acf_hip_pyramid_yuv)
+    ACF_HIP_FN(acf_hip_run_yuv)
+    ACF_HIP_FN(acf_hip_yuv_to_rgb8)
+    ACF_HIP_FN(acf_hip_yuv_extent)
+    ACF_HIP_FN(acf_hip_yuv_layout)
+    ACF_HIP_FN(acf_hip_stream_open_yuv)
     ACF_HIP_FN(acf_hip_resize_dims)
     ACF_HIP_FN(acf_hip_set_input_resize)
     ACF_HIP_FN(acf_hip_op_resize_u8)

@@ -433,6 +433,78 @@ ACF_HIP_API int acf_hip_pyramid_image(acf_hip_ctx* ctx, const void* frames_dev, 
 ACF_HIP_API int acf_hip_run_image(acf_hip_ctx* ctx, const void* frames_dev, int n_frames, const acf_hip_image_desc* desc);
 ACF_HIP_API int acf_hip_image_extent(const acf_hip_image_desc* desc, int h, int w, int n_frames, int64_t* first_elem, int64_t* last_elem);
 
+/* The video frame entry for YUV frames of three planes, each described by its own offset and byte strides: what a software
+ * decoder hands out (yuv420p = I420: three planes, often three allocations, each with its own line size), a capture device's
+ * packed 4:2:2 (YUYV / UYVY / YVYU), the 4:2:2 and 4:4:4 planar surfaces of professional video, and NV12 / NV21 again.  For
+ * pixel (row r, column c) of frame n at the plan's h x w, all offsets and strides in BYTES from base_dev:
+ *     Y = base_dev[y.offset + n * y.stride_n + r * y.stride_row + c * y.stride_px]
+ *     U = base_dev[u.offset + n * u.stride_n + (r >> sub_y) * u.stride_row + (c >> sub_x) * u.stride_px]
+ *     V = base_dev[v.offset + n * v.stride_n + (r >> sub_y) * v.stride_row + (c >> sub_x) * v.stride_px]
+ * (no chroma interpolation: a chroma sample is shared by the 1, 2 or 4 pixels above it), then R, G, B by the formula under
+ * "YUV 4:2:0 input" above, and from there on exactly acf_hip_pyramid_u8 / run_u8(ACF_HIP_PIX_RGB) on those bytes: every plane,
+ * level, hit, score bit and box is what the packed RGB entry gives for the converted frame (option "arith" = 1 included).  A
+ * descriptor that describes an NV12 / NV21 frame gives what acf_hip_run_u8(ACF_HIP_PIX_NV12 / _NV21) gives, bit for bit.
+ * cvtColor counterparts: COLOR_YUV2RGB_NV12 / _NV21 / _I420 / _YV12 / _YUY2 (YUYV) / _UYVY / _YVYU, which share the BT.601
+ * fixed-point helpers in OpenCV's imgproc/src/color_yuv.simd.hpp; I422 and I444 have no cvtColor code with this arithmetic: they
+ * are this library's extension of the same per-pixel formula.  OpenCV is not part of the reference tree: its published
+ * algorithm is restated; PARITY UNPINNED.
+ * h and w may be odd: a chroma plane then has ceil(h / 2^sub_y) rows of ceil(w / 2^sub_x) samples.  Offsets may be negative
+ * (three separately allocated planes: base_dev is one of them, the others lie where they lie); stride_px >= 1, stride_row >= 1,
+ * stride_n >= 0 (0 repeats one frame).  Only addressed bytes are ever read, so a plane may end with its allocation;
+ * acf_hip_yuv_extent gives the byte range of each plane to check against.  The plan's d must be 3.
+ * One kernel (k_ingest_yuv) with three load forms chosen from the descriptor and base_dev's alignment alone, all giving the same
+ * bits; under option "profile" it reports as k_ingest_yuv_planar (all three stride_px = 1; every plane's first byte, stride_row
+ * and stride_n multiples of 4: dword loads), k_ingest_yuv_packed422 (4:2:2 macropixels of four bytes, 4-aligned: one dword holds
+ * two pixels) or k_ingest_yuv_generic (byte loads, any strides); an NV12 / NV21-shaped descriptor of even h, w runs
+ * k_ingest_yuv420, the kernel of the 8-bit entry.
+ * Asynchronous on the context's stream; nothing is allocated after the first call.  The calls always run plainly and leave a
+ * captured graph of acf_hip_run (option "graph") valid; ACF_HIP_TAP_IMAGE behaves as after acf_hip_pyramid_u8.
+ * ACF_HIP_E_INVALID: null pointers, n_frames outside 1 .. max_batch, sub_x / sub_y outside {0, 1}, stride_px < 1, stride_row < 1,
+ * stride_n < 0, a plan of 1 or 5 input planes, an active acf_hip_set_input_resize; ACF_HIP_E_UNSUPPORTED with option "streams"
+ * > 1; ACF_HIP_E_NOPLAN without a plan.
+ *  acf_hip_yuv_to_rgb8       the conversion alone (k_yuv_to_rgb8), device buffers, no model, no plan: tight [n_frames][rows][cols][3]
+ *                            R, G, B at dst_dev, asynchronously on the context's stream
+ *  acf_hip_yuv_extent        host arithmetic, no context, no GPU: first[p] / last[p] = the lowest / highest byte offset from
+ *                            base_dev a call with these arguments reads of plane p (0 = Y, 1 = U, 2 = V)
+ *  acf_hip_yuv_layout        host arithmetic: the descriptor of a named layout (ACF_HIP_YUV_*, NOT ACF_HIP_PIX_*) of h x w with
+ *                            row_stride_bytes between luma rows (0 = tight: w, or 2 * w for the packed names); *frame_bytes = the
+ *                            distance to the next frame = stride_n of every plane.  NV12 / NV21: the tight rule of the 8-bit
+ *                            entry.  I420 / YV12 / I422 / I444: the luma plane, then the two chroma planes tight behind one
+ *                            another at row stride (row_stride_bytes >> sub_x), U then V (YV12: V then U).  YUYV / UYVY / YVYU:
+ *                            macropixels of four bytes in the named order (Y0 U Y1 V / U Y0 V Y1 / Y0 V Y1 U).  The 4:2:0 names
+ *                            need even h and w, the 4:2:2 names even w; the planar names an even luma stride; a stride shorter than a
+ *                            row, an unknown name, sizes < 1 and null outputs are ACF_HIP_E_INVALID.  Odd sizes are for hand-built
+ *                            descriptors only
+ *  acf_hip_stream_open_yuv   the streaming front end (below) for host frames of frame_bytes each: every plane's one-frame extent
+ *                            must lie in [0, frame_bytes) and stride_n == frame_bytes; acf_hip_stream_submit then copies
+ *                            n_frames * frame_bytes and runs acf_hip_run_yuv on the slot; submit / collect / close are unchanged,
+ *                            and a later acf_hip_stream_open replaces it (and the other way round) */
+enum {
+    ACF_HIP_YUV_NV12 = 0, /* Y plane; U, V interleaved */
+    ACF_HIP_YUV_NV21 = 1, /* Y plane; V, U interleaved */
+    ACF_HIP_YUV_I420 = 2, /* 4:2:0 planar Y, U, V (yuv420p) */
+    ACF_HIP_YUV_YV12 = 3, /* 4:2:0 planar Y, V, U */
+    ACF_HIP_YUV_I422 = 4, /* 4:2:2 planar Y, U, V */
+    ACF_HIP_YUV_I444 = 5, /* 4:4:4 planar Y, U, V */
+    ACF_HIP_YUV_YUYV = 6, /* 4:2:2 packed Y0 U Y1 V (YUY2) */
+    ACF_HIP_YUV_UYVY = 7, /* 4:2:2 packed U Y0 V Y1 */
+    ACF_HIP_YUV_YVYU = 8  /* 4:2:2 packed Y0 V Y1 U */
+};
+typedef struct acf_hip_yuv_plane {
+    int64_t offset, stride_n, stride_row, stride_px; /* bytes */
+} acf_hip_yuv_plane;
+typedef struct acf_hip_yuv_desc {
+    acf_hip_yuv_plane y, u, v;
+    int32_t sub_x, sub_y; /* 0 or 1: log2 of the chroma subsampling along image-x / image-y */
+} acf_hip_yuv_desc;
+ACF_HIP_API int acf_hip_pyramid_yuv(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc);
+ACF_HIP_API int acf_hip_run_yuv(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc);
+ACF_HIP_API int acf_hip_yuv_to_rgb8(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, int rows, int cols, const acf_hip_yuv_desc* desc,
+    uint8_t* dst_dev);
+ACF_HIP_API int acf_hip_yuv_extent(const acf_hip_yuv_desc* desc, int h, int w, int n_frames, int64_t first[3], int64_t last[3]);
+ACF_HIP_API int acf_hip_yuv_layout(int layout, int h, int w, int row_stride_bytes, acf_hip_yuv_desc* out, int64_t* frame_bytes);
+ACF_HIP_API int acf_hip_stream_open_yuv(acf_hip_ctx* ctx, const acf_hip_yuv_desc* desc, int64_t frame_bytes, int cap, int depth);
+
 /* The apps' resize to a minimum object width (src/app/acf/acf.cpp:117-148 `Resizer`,
  * GPUDetectionPipeline.cpp:250-266 computeDetectionWidth): scale = float(winSize.width) /
  * float(minWidth); cv::resize(image, reduced, {}, scale, scale, scale < 1 ? INTER_AREA :
