@@ -5,7 +5,9 @@ sys.path.insert(0, os.getcwd())
 from acf_amd import synth
 from acf_amd.detector import HipDetector
 from oracle import binding as ob
-rng = np.random.RandomState(int(sys.argv[1]) if len(sys.argv) > 1 else 7)
+SEED = int(sys.argv[1]) if len(sys.argv) > 1 else 7
+rng = np.random.RandomState(SEED)
+rng_chn = np.random.RandomState(SEED + 1000003)  # the channel parameters draw from a stream of their own: the fields above them keep their values per seed
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 bad = 0
 ran = 0
@@ -21,6 +23,9 @@ for it in range(N):
               softBin=int(rng.choice([0, 0, 0, -2, 2])), stride=int(rng.choice([4, 4, 4, 4, 8, 2, 1])))  # (stride < shrink: one evaluation per distinct offset)
     if kw["nApprox"] < 0:
         kw["nApprox"] = kw["nPerOct"] - 1
+    # the channel parameters the planned pipeline's forms fork on (generic-radius normalisation, k_triy_chns<12>, no smoothing = plain copies)
+    kw.update(normRad=int(rng_chn.choice([0, 3, 5, 5, 7])), nOrients=int(rng_chn.choice([4, 6, 6, 9, 12])),
+              smooth=float(rng_chn.choice([0, 0.5, 1, 1])), colorSmooth=float(rng_chn.choice([0, 0.5, 1, 1])))
     kind = "rgb" if rng.rand() < 0.3 else "luv"   # RGB frames go through rgbConvert (k_rgb2luv) first
     kw["isLuv"] = int(kind == "luv")
     arith = int(rng.rand() < 0.25)                # the reference's rcpps / rsqrtps bits (option arith; oracle: acfo_set_approx(3))

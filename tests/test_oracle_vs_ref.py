@@ -148,6 +148,76 @@ def test_grad_hist_bit_exact(oracle, refk, h, w, full, softBin):
     assert H_r.sum() > 0
 
 
+# ---- the parameters tests/channel_params_case.py leaves the defaults with: the oracle is the yardstick of the GPU cases there, so it is
+# pinned to the reference's compiled kernels at those values first
+
+@pytest.mark.parametrize("h,w", [(64, 48), (63, 50), (37, 41), (120, 160)])
+@pytest.mark.parametrize("softBin", [0, -2])
+@pytest.mark.parametrize("full", [0, 1])
+@pytest.mark.parametrize("bin_", [4, 2])
+@pytest.mark.parametrize("nOrients", [1, 2, 4, 5, 7, 9, 12])
+def test_grad_hist_orients_and_bins_bit_exact(oracle, refk, nOrients, bin_, full, softBin, h, w):
+    """gradHist away from bin 4 / nOrients 6: 1 .. 12 orientations (one bin takes everything; odd counts; the most the planned
+    pipeline's kernels take), cells of 2 (shrink 2), both even-softBin branches, orientation over pi and 2 pi."""
+    M = oracle.aligned_copy(rnd(h * w + 5 + nOrients, (w, h), 0.0, 0.6))
+    hi = 2 * np.pi if full else np.pi
+    O = oracle.aligned_copy(rnd(h * w + 6 + nOrients, (w, h), 0.0, float(hi) - 1e-6))
+    hb, wb = h // bin_, w // bin_
+    H_r, H_o = oracle.aligned((nOrients, wb, hb)), oracle.aligned((nOrients, wb, hb))
+    refk.ref_gradHist(oracle.F(M), oracle.F(O), oracle.F(H_r), h, w, bin_, nOrients, softBin, full)
+    assert oracle.lib().acfo_grad_hist(oracle.F(M), oracle.F(O), oracle.F(H_o), h, w, bin_, nOrients, softBin, full) == 0
+    assert np.array_equal(H_r.view(np.uint32), H_o.view(np.uint32))
+    assert H_r.sum() > 0
+
+
+@pytest.mark.parametrize("h,w,r", [(h, w, r) for r in (4, 6, 7, 10, 15) for h, w in SIZES if 2 * r + 1 < min(h, w)])
+def test_conv_tri_other_radii_bit_exact(oracle, refk, h, w, r):
+    """convTri at the normalisation radii other than 5, up to the largest the plan accepts, wherever the plane holds the filter."""
+    a =oracle.aligned_copy(rnd(h * 31 + w * 7 + r, (1, w, h)))
+    out_r = oracle.aligned((1, w, h))
+    out_o = oracle.aligned((1, w, h))
+    refk.ref_convTri(oracle.F(a), oracle.F(out_r), h, w, 1, r, 1)
+    assert oracle.lib().acfo_conv_tri(oracle.F(a), oracle.F(out_o), h, w, 1, r, 1) == 0
+    assert np.array_equal(out_r.view(np.uint32), out_o.view(np.uint32))
+
+
+def tri1_p(r):
+    """convTri's p for a radius below 1, as the pyramid derives it from smooth / colorSmooth (convTri.cpp: 12 / r / (r + 2) - 2)."""
+    return float(12.0 / r / (r + 2.0) - 2.0)
+
+
+@pytest.mark.parametrize("h,w", SIZES)
+@pytest.mark.parametrize("r", [0.5, 0.25, 0.8])
+@pytest.mark.parametrize("aliased", [0, 1])
+def test_conv_tri1_other_radii_bit_exact(oracle, refk, h, w, r, aliased):
+    """convTri1 with the p of smooth / colorSmooth 0.5, 0.25 and 0.8, out of place and in place (O == I, as the pyramid calls it)."""
+    p = tri1_p(r)
+    src = rnd(h * 77 + w + int(r * 100), (3, w, h))
+    a_r, a_o = oracle.aligned_copy(src), oracle.aligned_copy(src)
+    out_r = a_r if aliased else oracle.aligned((3, w, h))
+    out_o = a_o if aliased else oracle.aligned((3, w, h))
+    refk.ref_convTri1(oracle.F(a_r), oracle.F(out_r), h, w, 3, p, 1)
+    assert oracle.lib().acfo_conv_tri1(oracle.F(a_o), oracle.F(out_o), h, w, 3, p, 1) == 0
+    assert np.array_equal(out_r.view(np.uint32), out_o.view(np.uint32))
+    assert not np.array_equal(out_r, src)
+
+
+@pytest.mark.parametrize("h,w", SIZES)
+@pytest.mark.parametrize("normConst", [0.02, 0.0005])
+def test_grad_mag_norm_other_constants_within_rcp_bound(oracle, refk, h, w, normConst):
+    M0 = rnd(h * w + 1, (w, h), 0.0, 0.5)
+    S = oracle.aligned_copy(rnd(h * w + 2, (w, h), 0.0, 0.3))
+    M_r, M_o = oracle.aligned_copy(M0), oracle.aligned_copy(M0)
+    refk.ref_gradMagNorm(oracle.F(M_r), oracle.F(S), h, w, normConst)
+    oracle.lib().acfo_grad_mag_norm(oracle.F(M_o), oracle.F(S), h, w, normConst)
+    rel = np.abs(M_r - M_o) / np.maximum(np.abs(M_o), 1e-20)
+    assert rel.max() <= 1.1 * RCP_EPS
+    assert not np.array_equal(M_o, M0)
+    n = h * w
+    if n % 4:  # scalar tail divides exactly in both
+        assert np.array_equal(M_r.ravel()[n - n % 4:].view(np.uint32), M_o.ravel()[n - n % 4:].view(np.uint32))
+
+
 def test_grad_hist_odd_soft_bin_is_refused(oracle):
     """Odd softBin is the trilinear form with its 8/7 boundary normalisation (gradientMex.cpp:511-662): refused by the restatement
     (and by the library), not approximated."""
