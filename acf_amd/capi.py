@@ -230,6 +230,11 @@ def load():
         "acf_hip_yuv_extent": ([C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
         "acf_hip_yuv_layout": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(YuvDesc), C.POINTER(C.c_int64)], C.c_int),
         "acf_hip_stream_open_yuv": ([ctx, C.POINTER(YuvDesc), C.c_int64, C.c_int, C.c_int], C.c_int),
+        "acf_hip_pyramid_yuv_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_run_yuv_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_pyramid_image_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_run_image_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_stream_open_yuv_resized": ([ctx, C.POINTER(YuvDesc), C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
         "acf_hip_u8_frame_bytes": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)], C.c_int),
@@ -293,6 +298,8 @@ DECLARED_SYMBOLS = [
     "acf_hip_evaluate_crops", "acf_hip_evaluate_crops_u8",
     "acf_hip_pyramid_image", "acf_hip_run_image", "acf_hip_image_extent",
     "acf_hip_pyramid_yuv", "acf_hip_run_yuv", "acf_hip_yuv_to_rgb8", "acf_hip_yuv_extent", "acf_hip_yuv_layout", "acf_hip_stream_open_yuv",
+    "acf_hip_pyramid_yuv_resized", "acf_hip_run_yuv_resized", "acf_hip_pyramid_image_resized", "acf_hip_run_image_resized",
+    "acf_hip_stream_open_yuv_resized",
 ]
 
 

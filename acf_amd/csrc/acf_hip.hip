@@ -355,6 +355,8 @@ struct acf_hip_ctx
     int64_t stFrameBytes = 0; // bytes between the frames of a submitted batch
     bool stYuv = false;       // opened by acf_hip_stream_open_yuv: a batch runs through acf_hip_run_yuv with stYuvDesc
     acf_hip_yuv_desc stYuvDesc{};
+    int stSrcRows = 0, stSrcCols = 0; // > 0: opened by acf_hip_stream_open_yuv_resized: acf_hip_run_yuv_resized with these and stScale
+    double stScale = 1;
     // the plan's cascade (tables, model arrays, work queues, outputs); acf_hip_op_acf_detect1 builds and runs a state of its own
     CascState cs;
     BoxLevel* d_boxLevels = nullptr;
@@ -375,6 +377,10 @@ struct acf_hip_ctx
         int32_t *d_xlin = nullptr, *d_ylin = nullptr, *d_xrun = nullptr, *d_yrun = nullptr, *d_xtap = nullptr, *d_ytap = nullptr;
         uint8_t* d_out = nullptr; // [maxBatch][plan.H][plan.W][4]
     } rz;
+    // the resized tensor / YUV entries (acf_hip_pyramid_image_resized / _yuv_resized): the tap tables of the last (rows, cols, scale),
+    // uploaded at the first call with a new key and kept until another key or acf_hip_plan (d_out is not used: k_ingest_resized
+    // leaves no reduced 8-bit image)
+    InputResize rzIn;
     // acf_hip_set_yuv_layout: where an NV12 / NV21 frame's chroma plane starts and how far frames are apart (0 = tight)
     struct YuvLayout
     {
@@ -668,6 +674,7 @@ void freeAll(acf_hip_ctx* c)
     c->levelSegFrames = 0;
     c->d_color = c->d_stage = c->d_chns = c->d_pyr = nullptr; // a re-plan must not see the previous plan's buffers
     c->rz = acf_hip_ctx::InputResize();
+    c->rzIn = acf_hip_ctx::InputResize();
     c->yuv = acf_hip_ctx::YuvLayout();
     c->d_yuvRgb = nullptr;
     c->yuvRgbBytes = 0;
@@ -1833,6 +1840,9 @@ struct ImageSrc
 {
     const void* frames;
     acf_hip_image_desc d;
+    bool resized = false;         // the resized entry: frames of srcRows x srcCols, reduced by `scale` to the plan's size
+    int srcRows = 0, srcCols = 0;
+    double scale = 1;
 };
 
 // a YUV frame of three planes described by offsets and byte strides (acf_hip_pyramid_yuv)
@@ -1840,7 +1850,22 @@ struct YuvFrames
 {
     const uint8_t* base;
     acf_hip_yuv_desc d;
+    bool resized = false;         // the resized entry: frames of srcRows x srcCols, reduced by `scale` to the plan's size
+    int srcRows = 0, srcCols = 0;
+    double scale = 1;
 };
+
+using ResizedKernel = void (*)(IngestArgs, ResizedSrc);
+
+// k_ingest_resized<source, conversion>: [RS_*][IG_*]
+static ResizedKernel resizedKernel(int src, int mode)
+{
+    static const ResizedKernel table[2][4] = {
+        { k_ingest_resized<RS_IMAGE, IG_PLANAR>, k_ingest_resized<RS_IMAGE, IG_LUV_VEC>, k_ingest_resized<RS_IMAGE, IG_LUV>, k_ingest_resized<RS_IMAGE, IG_GRAY> },
+        { k_ingest_resized<RS_YUV, IG_PLANAR>, k_ingest_resized<RS_YUV, IG_LUV_VEC>, k_ingest_resized<RS_YUV, IG_LUV>, k_ingest_resized<RS_YUV, IG_GRAY> },
+    };
+    return table[src][mode];
+}
 
 using IngestKernel = void (*)(IngestArgs);
 using ImageKernel = void (*)(IngestArgs, ImageArgs);
@@ -2295,6 +2320,24 @@ static void launchColour(acf_hip_ctx* c, const float* in, float* out, int64_t n,
     }
 }
 
+// what rz_pixel reads besides the source: the tables on the device and the source size
+static ResizeTaps resizeTaps(const acf_hip_ctx::InputResize& rz)
+{
+    ResizeTaps t{};
+    t.rows = rz.t.rows;
+    t.cols = rz.t.cols;
+    t.mode = rz.t.mode;
+    t.isx = rz.t.isx;
+    t.isy = rz.t.isy;
+    t.xlin = reinterpret_cast<const int4*>(rz.d_xlin);
+    t.ylin = reinterpret_cast<const int4*>(rz.d_ylin);
+    t.xrun = reinterpret_cast<const int2*>(rz.d_xrun);
+    t.yrun = reinterpret_cast<const int2*>(rz.d_yrun);
+    t.xtap = reinterpret_cast<const int2*>(rz.d_xtap);
+    t.ytap = reinterpret_cast<const int2*>(rz.d_ytap);
+    return t;
+}
+
 // k_resize_u8 over a batch: `src` frames of t.rows x t.cols (row stride `stride` bytes) -> tight t.drows x t.dcols frames at dst
 static int launchResizeU8(acf_hip_ctx* c, const acf_hip_ctx::InputResize& rz, const uint8_t* src, int cpp, int stride, int nF, uint8_t* dst)
 {
@@ -2302,23 +2345,13 @@ static int launchResizeU8(acf_hip_ctx* c, const acf_hip_ctx::InputResize& rz, co
     ResizeArgs a{};
     a.src = src;
     a.dst = dst;
-    a.rows = t.rows;
-    a.cols = t.cols;
     a.cn = cpp;
     a.stride = stride;
     a.drows = t.drows;
     a.dcols = t.dcols;
     a.src_fs = int64_t(stride) * t.rows;
     a.dst_fs = int64_t(t.drows) * t.dcols * cpp;
-    a.mode = t.mode;
-    a.isx = t.isx;
-    a.isy = t.isy;
-    a.xlin = reinterpret_cast<const int4*>(rz.d_xlin);
-    a.ylin = reinterpret_cast<const int4*>(rz.d_ylin);
-    a.xrun = reinterpret_cast<const int2*>(rz.d_xrun);
-    a.yrun = reinterpret_cast<const int2*>(rz.d_yrun);
-    a.xtap = reinterpret_cast<const int2*>(rz.d_xtap);
-    a.ytap = reinterpret_cast<const int2*>(rz.d_ytap);
+    a.t = resizeTaps(rz);
     prof(c, c->stream, "k_resize_u8");
     hipLaunchKernelGGL(k_resize_u8, dim3(cdiv(t.dcols, 64), cdiv(t.drows, 4), nF), dim3(256), 0, c->stream, a);
     LAUNCHCHK(c, "k_resize_u8");
@@ -2333,6 +2366,81 @@ static int uploadResizeTables(acf_hip_ctx* c, acf_hip_ctx::InputResize& rz)
     {
         return rc;
     }
+    return ACF_HIP_OK;
+}
+
+static void releaseResize(acf_hip_ctx* c, acf_hip_ctx::InputResize& r)
+{
+    devRelease(c, r.d_xlin);
+    devRelease(c, r.d_ylin);
+    devRelease(c, r.d_xrun);
+    devRelease(c, r.d_yrun);
+    devRelease(c, r.d_xtap);
+    devRelease(c, r.d_ytap);
+    devRelease(c, r.d_out);
+}
+
+// What the resized entries refuse about (src_rows, src_cols, scale) and the plan, then their tap tables on the device: those of the
+// context's key (rows, cols, scale) as they are, else built and uploaded (the stream is synchronised before the old ones go)
+static int resizedTables(acf_hip_ctx* c, const char* who, int srcRows, int srcCols, double scale)
+{
+    if (srcRows < 1 || srcCols < 1 || !(scale > 0) || !std::isfinite(scale))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": src_rows and src_cols >= 1, scale a positive finite number");
+    }
+    if (c->rz.on)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": not with acf_hip_set_input_resize (the entry resizes by itself)");
+    }
+    acf_hip_ctx::InputResize& cur = c->rzIn;
+    if (cur.on && cur.rows == srcRows && cur.cols == srcCols && cur.scale == scale)
+    {
+        return ACF_HIP_OK; // (built against this plan: acf_hip_plan drops them)
+    }
+    acf_hip_ctx::InputResize rz;
+    if (buildResizeTables(srcRows, srcCols, scale, rz.t) || rz.t.drows != c->plan.H || rz.t.dcols != c->plan.W)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": the plan must be for the reduced size (acf_hip_resize_dims of the frame size and scale)");
+    }
+    rz.rows = srcRows;
+    rz.cols = srcCols;
+    rz.scale = scale;
+    if (int rc = uploadResizeTables(c, rz))
+    {
+        releaseResize(c, rz); // (what was uploaded before the failure)
+        return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // the previous key's tables: a batch in flight may still read them
+    releaseResize(c, cur);
+    rz.on = true;
+    cur = rz;
+    return ACF_HIP_OK;
+}
+
+// k_ingest_resized over a batch: the resized entries' frames (an image's strides or a YUV description, at the source size) -> planar
+// f32 at the plan's size at dst
+int launchIngestResized(acf_hip_ctx* c, const ImageSrc* im, const YuvFrames* yf, int nF, float* dst, int64_t out_fs, bool convert)
+{
+    const Plan& pl = c->plan;
+    IngestArgs a{};
+    const int mode = ingestShared(c, dst, out_fs, convert, a);
+    ResizedSrc s{};
+    s.t = resizeTaps(c->rzIn);
+    if (im)
+    {
+        s.im.in = im->frames;
+        s.im.sn = im->d.stride_n;
+        s.im.sc = im->d.stride_c;
+        s.im.sy = im->d.stride_y;
+        s.im.sx = im->d.stride_x;
+        s.im.nIn = im->d.channels;
+    }
+    else
+    {
+        s.yuv = yuvDescSrc(*yf);
+    }
+    hipLaunchKernelGGL(resizedKernel(im ? RS_IMAGE : RS_YUV, mode), dim3(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF), dim3(256), 0, c->stream, a, s);
+    LAUNCHCHK(c, "k_ingest_resized");
     return ACF_HIP_OK;
 }
 
@@ -2429,6 +2537,48 @@ int acf_hip_pyramid_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_h
 int acf_hip_run_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
 {
     int rc = acf_hip_pyramid_yuv(c, base, nF, desc);
+    if (rc)
+    {
+        return rc;
+    }
+    return acf_hip_detect(c);
+}
+
+int acf_hip_pyramid_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
+{
+    if (int rc = needCtx(c)) return rc;
+    if (!base || !desc)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv_resized: null base or description");
+    }
+    YuvFrames f{ base, *desc, true, srcRows, srcCols, scale };
+    return pyramidImpl(c, nullptr, nullptr, nF, nullptr, &f);
+}
+
+int acf_hip_run_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
+{
+    int rc = acf_hip_pyramid_yuv_resized(c, base, nF, desc, srcRows, srcCols, scale);
+    if (rc)
+    {
+        return rc;
+    }
+    return acf_hip_detect(c);
+}
+
+int acf_hip_pyramid_image_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, double scale)
+{
+    if (int rc = needCtx(c)) return rc;
+    if (!frames || !desc)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "pyramid_image_resized: null frames or description");
+    }
+    ImageSrc im{ frames, *desc, true, srcRows, srcCols, scale };
+    return pyramidImpl(c, nullptr, nullptr, nF, &im);
+}
+
+int acf_hip_run_image_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, double scale)
+{
+    int rc = acf_hip_pyramid_image_resized(c, frames, nF, desc, srcRows, srcCols, scale);
     if (rc)
     {
         return rc;
@@ -2584,25 +2734,16 @@ int acf_hip_set_input_resize(acf_hip_ctx* c, int srcRows, int srcCols, double sc
     rz.cols = srcCols;
     rz.scale = scale;
     HIPCHK(c, hipSetDevice(c->device));
-    auto release = [&](acf_hip_ctx::InputResize& r) {
-        devRelease(c, r.d_xlin);
-        devRelease(c, r.d_ylin);
-        devRelease(c, r.d_xrun);
-        devRelease(c, r.d_yrun);
-        devRelease(c, r.d_xtap);
-        devRelease(c, r.d_ytap);
-        devRelease(c, r.d_out);
-    };
     int rc;
     if ((rc = uploadResizeTables(c, rz)) || (rc = devAlloc(c, &rz.d_out, size_t(c->maxBatch) * c->plan.H * c->plan.W * 4)))
     {
-        release(rz); // (what was uploaded before the failure)
+        releaseResize(c, rz); // (what was uploaded before the failure)
         return rc;
     }
     // the previous geometry's tables: a batch in flight may still read them
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->rz.on = false;
-    release(c->rz);
+    releaseResize(c, c->rz);
     rz.on = true;
     c->rz = rz;
     return ACF_HIP_OK;
@@ -2906,41 +3047,62 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
     return streamSlots(c, g.frameStride, cap, depth);
 }
 
-int acf_hip_stream_open_yuv(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int cap, int depth)
+// acf_hip_stream_open_yuv and acf_hip_stream_open_yuv_resized (resized: frames of srcRows x srcCols, reduced by scale)
+static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc* desc, int64_t frameBytes, bool resized, int srcRows, int srcCols, double scale,
+    int cap, int depth)
 {
-    if (int rc = needPlan(c, "stream_open_yuv")) return rc;
+    const std::string w = std::string(who) + ": ";
+    if (int rc = needPlan(c, who)) return rc;
     if (!c->kids.empty())
     {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "stream_open_yuv: not available with option \"streams\" > 1");
+        return fail(c, ACF_HIP_E_UNSUPPORTED, w + "not available with option \"streams\" > 1");
     }
     if (depth < 2 || depth > 8 || cap <= 0)
     {
-        return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv: depth must be 2..8, cap > 0");
+        return fail(c, ACF_HIP_E_INVALID, w + "depth must be 2..8, cap > 0");
     }
     if (const char* bad = yuvDescBad(desc))
     {
-        return fail(c, ACF_HIP_E_INVALID, std::string("stream_open_yuv: ") + bad);
+        return fail(c, ACF_HIP_E_INVALID, w + bad);
     }
     if (c->plan.d_in != 3 || c->rz.on)
     {
-        return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv: the plan's input planes (d) must be 3, and not with acf_hip_set_input_resize");
+        return fail(c, ACF_HIP_E_INVALID, w + "the plan's input planes (d) must be 3, and not with acf_hip_set_input_resize");
+    }
+    if (resized)
+    {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = resizedTables(c, who, srcRows, srcCols, scale)) return rc;
     }
     int64_t first[3], last[3];
-    yuvExtent(*desc, c->plan.H, c->plan.W, 1, first, last);
+    yuvExtent(*desc, resized ? srcRows : c->plan.H, resized ? srcCols : c->plan.W, 1, first, last);
     for (int i = 0; i < 3; i++)
     {
         if (first[i] < 0 || last[i] >= frameBytes)
         {
-            return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv: every plane of a frame must lie in [0, frame_bytes)");
+            return fail(c, ACF_HIP_E_INVALID, w + "every plane of a frame must lie in [0, frame_bytes)");
         }
     }
     if (desc->y.stride_n != frameBytes || desc->u.stride_n != frameBytes || desc->v.stride_n != frameBytes)
     {
-        return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv: stride_n of every plane must be frame_bytes");
+        return fail(c, ACF_HIP_E_INVALID, w + "stride_n of every plane must be frame_bytes");
     }
     c->stYuv = true;
     c->stYuvDesc = *desc;
+    c->stSrcRows = resized ? srcRows : 0;
+    c->stSrcCols = resized ? srcCols : 0;
+    c->stScale = scale;
     return streamSlots(c, frameBytes, cap, depth);
+}
+
+int acf_hip_stream_open_yuv(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int cap, int depth)
+{
+    return streamOpenYuv(c, "stream_open_yuv", desc, frameBytes, false, 0, 0, 1.0, cap, depth);
+}
+
+int acf_hip_stream_open_yuv_resized(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, double scale, int cap, int depth)
+{
+    return streamOpenYuv(c, "stream_open_yuv_resized", desc, frameBytes, true, srcRows, srcCols, scale, cap, depth);
 }
 
 int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, int* ticket)
@@ -2962,7 +3124,9 @@ int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, in
     HIPCHK(c, hipMemcpyAsync(s.d_in, frames_host, bytes, hipMemcpyHostToDevice, c->copyStream));
     HIPCHK(c, hipEventRecord(s.evH2D, c->copyStream));
     HIPCHK(c, hipStreamWaitEvent(c->stream, s.evH2D, 0));
-    int rc = c->stYuv ? acf_hip_run_yuv(c, s.d_in, nF, &c->stYuvDesc) : acf_hip_run_u8(c, s.d_in, nF, c->stPix, c->stStride);
+    int rc = !c->stYuv        ? acf_hip_run_u8(c, s.d_in, nF, c->stPix, c->stStride)
+        : c->stSrcRows > 0 ? acf_hip_run_yuv_resized(c, s.d_in, nF, &c->stYuvDesc, c->stSrcRows, c->stSrcCols, c->stScale)
+                           : acf_hip_run_yuv(c, s.d_in, nF, &c->stYuvDesc);
     if (rc)
     {
         return rc;

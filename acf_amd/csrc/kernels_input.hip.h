@@ -1,6 +1,7 @@
 // kernels_input.hip.h — part of kernels.hip.h (included from there, in its order, and nowhere else: the parts share kernels.hip.h's
 // includes, its layout / arithmetic contract and the helpers of the parts before them).
-// rgbConvert (LUV / gray / HSV), the packed 8-bit ingest, the apps' resize to a minimum object width, and the plain convTri1 (k_smooth_tri1: the fallback of the vector smoothing).
+// rgbConvert (LUV / gray / HSV), the packed 8-bit ingest, the apps' resize to a minimum object width (alone: k_resize_u8; inside the tensor / YUV
+// entries: k_ingest_resized), and the plain convTri1 (k_smooth_tri1: the fallback of the vector smoothing).
 #pragma once
 
 namespace acfhip
@@ -260,6 +261,31 @@ __device__ __forceinline__ void ingest_store(const IngestArgs& a, const float (&
     }
 }
 
+// The store phase of a 64 x 64 tile of packed bytes in LDS (pitch IG_PITCH; r, g, b at ro, go, bo of a pixel's cpp bytes): a lane takes
+// four consecutive image-y of one image-x through the model's colour conversion and writes one float4 a plane.  k_ingest_u8's, and
+// k_ingest_resized's behind its resize.  (Rows beyond the tile convert whatever the LDS holds — bytes, so in range: never stored.)
+template <int MODE>
+__device__ __forceinline__ void ingest_store_tile(const IngestArgs& a, const uint8_t* tile, int cpp, int ro, int go, int bo, int x0, int y0, int nx, int ny)
+{
+    const int yq = (threadIdx.x & 15) * 4;
+    const float sc = float(1.0 / 255.0);
+    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
+    const int64_t np = int64_t(a.H) * a.W;
+    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
+    {
+        float o[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            const int yy = min(yq + j, IG_T - 1);
+            const uint8_t* px = tile + yy * IG_PITCH + xx * cpp;
+            const float r = float(px[ro]) * sc, g = float(px[go]) * sc, b = float(px[bo]) * sc;
+            ingest_convert<MODE>(a, r, g, b, o, j);
+        }
+        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
+    }
+}
+
 template <int MODE, bool ALIGNED>
 __global__ void __launch_bounds__(256) k_ingest_u8(IngestArgs a)
 {
@@ -309,23 +335,7 @@ __global__ void __launch_bounds__(256) k_ingest_u8(IngestArgs a)
         }
     }
     __syncthreads();
-    const int yq = (threadIdx.x & 15) * 4;
-    const float sc = float(1.0 / 255.0);
-    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
-    const int64_t np = int64_t(a.H) * a.W;
-    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
-    {
-        float o[3][4];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-        {
-            const int yy = min(yq + j, IG_T - 1);
-            const uint8_t* px = tile + yy * IG_PITCH + xx * a.cpp;
-            const float r = float(px[a.ro]) * sc, g = float(px[a.go]) * sc, b = float(px[a.bo]) * sc;
-            ingest_convert<MODE>(a, r, g, b, o, j);
-        }
-        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
-    }
+    ingest_store_tile<MODE>(a, tile, a.cpp, a.ro, a.go, a.bo, x0, y0, nx, ny);
 }
 
 // ------------------------------------------------------------------------
@@ -985,12 +995,10 @@ enum
     RZ_AREA = 1,
     RZ_AREA_INT = 2
 };
-struct ResizeArgs
+// The tap tables and source size of one resize: what the per-pixel arithmetic reads besides the source
+struct ResizeTaps
 {
-    const uint8_t* src;
-    uint8_t* dst;
-    int32_t rows, cols, cn, stride, drows, dcols;
-    int64_t src_fs, dst_fs; // bytes per frame
+    int32_t rows, cols;  // source size
     int32_t mode, isx, isy;
     const int4* xlin;   // RZ_LINEAR [dcols]
     const int4* ylin;   // RZ_LINEAR [drows]
@@ -999,32 +1007,61 @@ struct ResizeArgs
     const int2* xtap;   // RZ_AREA {source column, float bits}
     const int2* ytap;
 };
+struct ResizeArgs
+{
+    const uint8_t* src;
+    uint8_t* dst;
+    int32_t cn, stride, drows, dcols;
+    int64_t src_fs, dst_fs; // bytes per frame
+    ResizeTaps t;
+};
 __device__ __forceinline__ uint8_t rz_sat_u8(float v)
 {
     const int i = __float2int_rn(v); // cvRound: round half to even
     return uint8_t(min(max(i, 0), 255));
 }
-__global__ void __launch_bounds__(256) k_resize_u8(ResizeArgs a)
+
+// Source accessors of rz_pixel: px(y, x, v) gives the cn (<= 4) channels of source pixel (y, x) as ints 0 .. 255, all at once.
+// A packed 8-bit frame: cn interleaved bytes a pixel
+struct RzPackedSrc
 {
-    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= a.dcols || dy >= a.drows)
+    const uint8_t* S; // the frame
+    int stride, cn;
+    __device__ __forceinline__ void px(int y, int x, int (&v)[4]) const
     {
-        return;
+        const uint8_t* p = S + int64_t(y) * stride + x * cn;
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+        {
+            v[c] = c < cn ? p[c] : 0;
+        }
     }
-    const uint8_t* __restrict__ S = a.src + int64_t(blockIdx.z) * a.src_fs;
-    uint8_t* __restrict__ D = a.dst + int64_t(blockIdx.z) * a.dst_fs + (int64_t(dy) * a.dcols + dx) * a.cn;
-    const int cn = a.cn;
+};
+
+// One output pixel (dx, dy) of the resize, every channel: the ONE statement of the three forms' arithmetic (k_resize_u8 on a packed
+// frame, k_ingest_resized on an image's strides or a YUV description).  Channels are independent, so reading a source pixel once for
+// all of them changes no bit.
+template <class SRC>
+__device__ __forceinline__ void rz_pixel(const SRC& s, const ResizeTaps& a, int dx, int dy, uint8_t (&out)[4])
+{
+    int v[4];
     if (a.mode == RZ_LINEAR)
     {
         const int4 X = a.xlin[dx], Y = a.ylin[dy];
-        const uint8_t* S0 = S + int64_t(Y.x) * a.stride + X.x * cn;
-        const uint8_t* S1 = S + int64_t(Y.y) * a.stride + X.x * cn;
-        const int nx = X.w ? cn : 0; // (beyond xmax the second tap is not read: S[sx] * 2048)
-        for (int c = 0; c < cn; c++)
+        int p0[4], p1[4], q0[4] = { 0, 0, 0, 0 }, q1[4] = { 0, 0, 0, 0 };
+        s.px(Y.x, X.x, p0);
+        s.px(Y.y, X.x, p1);
+        if (X.w) // (beyond xmax the second tap is not read: S[sx] * 2048)
         {
-            const int h0 = X.w ? S0[c] * X.y + S0[nx + c] * X.z : S0[c] * 2048;
-            const int h1 = X.w ? S1[c] * X.y + S1[nx + c] * X.z : S1[c] * 2048;
-            D[c] = uint8_t((((Y.z * (h0 >> 4)) >> 16) + ((Y.w * (h1 >> 4)) >> 16) + 2) >> 2);
+            s.px(Y.x, X.x + 1, q0);
+            s.px(Y.y, X.x + 1, q1);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+        {
+            const int h0 = X.w ? p0[c] * X.y + q0[c] * X.z : p0[c] * 2048;
+            const int h1 = X.w ? p1[c] * X.y + q1[c] * X.z : p1[c] * 2048;
+            out[c] = uint8_t((((Y.z * (h0 >> 4)) >> 16) + ((Y.w * (h1 >> 4)) >> 16) + 2) >> 2);
         }
         return;
     }
@@ -1034,47 +1071,179 @@ __global__ void __launch_bounds__(256) k_resize_u8(ResizeArgs a)
         const bool partial = sy0 + a.isy > a.rows || sx0 + a.isx > a.cols;
         const int ny = min(a.isy, a.rows - sy0), nx = min(a.isx, a.cols - sx0);
         const float sc = 1.f / float(a.isx * a.isy);
-        for (int c = 0; c < cn; c++)
+        int sum[4] = { 0, 0, 0, 0 };
+        for (int y = 0; y < ny; y++)
         {
-            int sum = 0;
-            for (int y = 0; y < ny; y++)
+            for (int x = 0; x < nx; x++)
             {
-                for (int x = 0; x < nx; x++)
+                s.px(sy0 + y, sx0 + x, v);
+#pragma unroll
+                for (int c = 0; c < 4; c++)
                 {
-                    sum += S[int64_t(sy0 + y) * a.stride + (sx0 + x) * cn + c];
+                    sum[c] += v[c];
                 }
             }
-            const int count = max(ny, 0) * max(nx, 0);
+        }
+        const int count = max(ny, 0) * max(nx, 0);
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+        {
             if (partial)
             {
-                D[c] = count > 0 ? rz_sat_u8(float(sum) / float(count)) : uint8_t(0);
+                out[c] = count > 0 ? rz_sat_u8(float(sum[c]) / float(count)) : uint8_t(0);
             }
             else
             {
-                D[c] = (a.isx == 2 && a.isy == 2) ? uint8_t((sum + 2) >> 2) : rz_sat_u8(float(sum) * sc);
+                out[c] = (a.isx == 2 && a.isy == 2) ? uint8_t((sum[c] + 2) >> 2) : rz_sat_u8(float(sum[c]) * sc);
             }
         }
         return;
     }
     const int2 xr = a.xrun[dx], yr = a.yrun[dy];
-    for (int c = 0; c < cn; c++)
+    float sum[4] = { 0.f, 0.f, 0.f, 0.f };
+    for (int j = 0; j < yr.y; j++)
     {
-        float sum = 0.f;
-        for (int j = 0; j < yr.y; j++)
+        const int2 ty = a.ytap[yr.x + j];
+        float buf[4] = { 0.f, 0.f, 0.f, 0.f };
+        for (int k = 0; k < xr.y; k++)
         {
-            const int2 ty = a.ytap[yr.x + j];
-            const uint8_t* Sr = S + int64_t(ty.x) * a.stride + c;
-            float buf = 0.f;
-            for (int k = 0; k < xr.y; k++)
+            const int2 tx = a.xtap[xr.x + k];
+            s.px(ty.x, tx.x, v);
+#pragma unroll
+            for (int c = 0; c < 4; c++)
             {
-                const int2 tx = a.xtap[xr.x + k];
-                buf = buf + float(Sr[tx.x * cn]) * __int_as_float(tx.y);
+                buf[c] = buf[c] + float(v[c]) * __int_as_float(tx.y);
             }
-            const float t = __int_as_float(ty.y) * buf;
-            sum = j == 0 ? t : sum + t;
         }
-        D[c] = rz_sat_u8(sum);
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+        {
+            const float t = __int_as_float(ty.y) * buf[c];
+            sum[c] = j == 0 ? t : sum[c] + t;
+        }
     }
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+    {
+        out[c] = rz_sat_u8(sum[c]);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_resize_u8(ResizeArgs a)
+{
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= a.dcols || dy >= a.drows)
+    {
+        return;
+    }
+    const RzPackedSrc s{ a.src + int64_t(blockIdx.z) * a.src_fs, a.stride, a.cn };
+    uint8_t* __restrict__ D = a.dst + int64_t(blockIdx.z) * a.dst_fs + (int64_t(dy) * a.dcols + dx) * a.cn;
+    uint8_t o[4];
+    rz_pixel(s, a.t, dx, dy, o);
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+    {
+        if (c < a.cn)
+        {
+            D[c] = o[c];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------
+// The apps' resize inside the tensor and YUV entries (acf_hip_pyramid_image_resized / _yuv_resized): the caller's bytes -> the
+// converted planar f32 image at the reduced size in one kernel, defined as the existing entries composed — acf_hip_yuv_to_rgb8 (or the
+// addressed bytes as an interleaved image), k_resize_u8's arithmetic (rz_pixel), k_ingest_u8 — bit for bit.  cvtColor and cv::resize
+// stay restated: PARITY UNPINNED.
+//
+// k_ingest_u8's shape: a workgroup of 256 threads owns a 64 x 64 tile of the REDUCED image.
+//   phase 1  lanes run along reduced-image x (a wave = one tile row, 16 rows a wave): rz_pixel over a source accessor (the image's
+//            n / c / y / x element strides; or Y at (r, c), U and V at (r >> sub_y, c >> sub_x) through yuv_chroma / yuv_rgb8, once per
+//            source pixel for its three channels), the bytes into k_ingest_u8's LDS byte tile (pitch 260; r, g, b at 0, 1, 2 of 3)
+//   phase 2  ingest_store_tile: k_ingest_u8's store phase
+// No load touches a byte outside what the description addresses at the source size: rz_pixel reads source pixels inside
+// [0, rows) x [0, cols) only (RZ_LINEAR's second tap only where the table's fourth field says so; partial area cells clamp).
+//
+// LDS (bank = dword address % 32, per 32-lane half): phase 1 writes bytes 3 * xx + c of one row: a half covers 24 dwords, up to two
+// lanes a dword for one c (byte writes of several lanes to one dword: whether they serialise was not measured); phase 2 reads as
+// k_ingest_u8 does (16 row-quads a half at a pitch of 65 dwords: 16 distinct banks).  64 x 260 = 16640 bytes.
+// ------------------------------------------------------------------------
+struct RzImageSrc
+{
+    const uint8_t* in; // frame n's element (0, 0, 0)
+    int64_t sc, sy, sx;
+    int nIn;
+    __device__ __forceinline__ void px(int y, int x, int (&v)[4]) const
+    {
+        const uint8_t* p = in + int64_t(y) * sy + int64_t(x) * sx;
+        v[0] = p[0];
+        v[1] = nIn == 3 ? p[sc] : 0;
+        v[2] = nIn == 3 ? p[2 * sc] : 0;
+        v[3] = 0;
+    }
+};
+struct RzYuvSrc
+{
+    const uint8_t *py, *pu, *pv; // frame n's first sample of each plane
+    int64_t ysr, ysp, usr, usp, vsr, vsp;
+    int subX, subY;
+    __device__ __forceinline__ void px(int y, int x, int (&v)[4]) const
+    {
+        const int cr = y >> subY, cc = x >> subX;
+        const int Y = py[int64_t(y) * ysr + int64_t(x) * ysp];
+        const int U = pu[int64_t(cr) * usr + int64_t(cc) * usp];
+        const int V = pv[int64_t(cr) * vsr + int64_t(cc) * vsp];
+        yuv_rgb8(Y, yuv_chroma(U, V), v[0], v[1], v[2]);
+        v[3] = 0;
+    }
+};
+enum
+{
+    RS_IMAGE = 0,
+    RS_YUV = 1
+};
+struct ResizedSrc
+{
+    ImageArgs im;   // RS_IMAGE (u8 elements; form is not read)
+    YuvDescSrc yuv; // RS_YUV
+    ResizeTaps t;
+};
+
+template <int SRC, int MODE>
+__global__ void __launch_bounds__(256) k_ingest_resized(IngestArgs a, ResizedSrc s)
+{
+    __shared__ uint32_t tileW[IG_T * IG_PITCH / 4];
+    uint8_t* tile = reinterpret_cast<uint8_t*>(tileW);
+    const int x0 = blockIdx.x * IG_T, y0 = blockIdx.y * IG_T;
+    const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0);
+    const int64_t n = blockIdx.z;
+    const int xx = threadIdx.x & 63;
+    if (xx < nx)
+    {
+        const int cn = SRC == RS_YUV ? 3 : s.im.nIn;
+        for (int yy = threadIdx.x >> 6; yy < ny; yy += 4)
+        {
+            uint8_t o[4];
+            if (SRC == RS_YUV)
+            {
+                const YuvDescSrc& d = s.yuv;
+                const RzYuvSrc src{ d.base + d.y.off + n * d.y.sn, d.base + d.u.off + n * d.u.sn, d.base + d.v.off + n * d.v.sn, d.y.sr, d.y.sp, d.u.sr,
+                    d.u.sp, d.v.sr, d.v.sp, d.subX, d.subY };
+                rz_pixel(src, s.t, x0 + xx, y0 + yy, o);
+            }
+            else
+            {
+                const RzImageSrc src{ static_cast<const uint8_t*>(s.im.in) + n * s.im.sn, s.im.sc, s.im.sy, s.im.sx, s.im.nIn };
+                rz_pixel(src, s.t, x0 + xx, y0 + yy, o);
+            }
+            uint8_t* t = tile + yy * IG_PITCH + 3 * xx;
+            t[0] = o[0];
+            t[1] = cn == 3 ? o[1] : o[0]; // one plane: r = g = b (chnsPyramid.cpp:234-244), as k_ingest_u8 reads a 1-byte pixel
+            t[2] = cn == 3 ? o[2] : o[0];
+        }
+    }
+    __syncthreads();
+    ingest_store_tile<MODE>(a, tile, 3, 0, 1, 2, x0, y0, nx, ny);
 }
 
 struct SmoothJob

@@ -5,6 +5,7 @@
 // ingest and colour run on it before any scale has a stream of its own, the levels after joinScales has set st back to it.
 //
 //   ingest()            packed 8-bit frames -> planar f32 (ACF.cpp:114-119,137), the apps' Resizer in front of it
+//   ingestImage() / ingestYuv()   the tensor and YUV entries; their resized forms run the Resizer inside the ingest kernel
 //   colour()            rgbConvert once at full resolution (chnsPyramid.cpp:230-263)
 //   prepareScales()     which image every real scale is resampled from (the I = I1 adoption, :313-316), the scales' streams
 //   realScale(k)        imageResample(k) -> planScale(k) -> smoothImage(k) -> gradientChannels(k): chnsCompute at a real scale (:297-338,
@@ -305,47 +306,75 @@ int PyramidRun::ingestPlanes(const char* kernel, bool& ingestConverted, const In
     return ACF_HIP_OK;
 }
 
-// The image entry for upright images of any strides and element type (ACF.cpp:135-141 for CV_32FC3 and CV_8UC3; MatP.cpp:51-73)
+// The image entry for upright images of any strides and element type (ACF.cpp:135-141 for CV_32FC3 and CV_8UC3; MatP.cpp:51-73); the
+// resized entry (im.resized): the apps' Resizer on the addressed bytes first, in the same kernel (k_ingest_resized)
 int PyramidRun::ingestImage(const ImageSrc& im, bool& ingestConverted)
 {
+    const bool resized = im.resized;
+    const std::string who = resized ? "pyramid_image_resized: " : "pyramid_image: ";
     if (const char* bad = imageDescBad(&im.d))
     {
-        return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_image: ") + bad);
+        return fail(c, ACF_HIP_E_INVALID, who + bad);
     }
     if (d_in == 5)
     {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_image: a plan for five input planes (image + M, O) takes planar float frames");
+        return fail(c, ACF_HIP_E_INVALID, who + "a plan for five input planes (image + M, O) takes planar float frames");
     }
     if (im.d.channels != d_in)
     {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_image: channels must be the plan's input planes (d)");
+        return fail(c, ACF_HIP_E_INVALID, who + "channels must be the plan's input planes (d)");
     }
-    if (c->rz.on)
+    if (!resized)
     {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_image: not with acf_hip_set_input_resize (the resize takes packed 8-bit frames)");
+        if (c->rz.on)
+        {
+            return fail(c, ACF_HIP_E_INVALID, "pyramid_image: not with acf_hip_set_input_resize (the resize takes packed 8-bit frames)");
+        }
+        return ingestPlanes("k_ingest_image", ingestConverted,
+            [&](float* dst, int64_t out_fs, bool convert) { return launchIngestImage(c, im, nF, dst, out_fs, convert); });
     }
-    return ingestPlanes("k_ingest_image", ingestConverted,
-        [&](float* dst, int64_t out_fs, bool convert) { return launchIngestImage(c, im, nF, dst, out_fs, convert); });
+    if (im.d.dtype != ACF_HIP_T_U8)
+    {
+        return fail(c, ACF_HIP_E_UNSUPPORTED, who + "dtype must be ACF_HIP_T_U8 (cv::resize's CV_32F arithmetic is not restated)");
+    }
+    if (int rc = resizedTables(c, "pyramid_image_resized", im.srcRows, im.srcCols, im.scale))
+    {
+        return rc;
+    }
+    return ingestPlanes("k_ingest_resized_image", ingestConverted,
+        [&](float* dst, int64_t out_fs, bool convert) { return launchIngestResized(c, &im, nullptr, nF, dst, out_fs, convert); });
 }
 
 // The video frame entry for three-plane YUV descriptions: cvtColor's BT.601 integer conversion (restated, kernels_input.hip.h), then
-// the 8-bit image entry (ACF.cpp:114-119,135-141; MatP.cpp:51-73), in one kernel
+// the 8-bit image entry (ACF.cpp:114-119,135-141; MatP.cpp:51-73), in one kernel; the resized entry (yf.resized): the apps'
+// Resizer between the two, still one kernel (k_ingest_resized)
 int PyramidRun::ingestYuv(const YuvFrames& yf, bool& ingestConverted)
 {
+    const bool resized = yf.resized;
+    const std::string who = resized ? "pyramid_yuv_resized: " : "pyramid_yuv: ";
     if (const char* bad = yuvDescBad(&yf.d))
     {
-        return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_yuv: ") + bad);
+        return fail(c, ACF_HIP_E_INVALID, who + bad);
     }
     if (d_in != 3)
     {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv: the plan's input planes (d) must be 3");
+        return fail(c, ACF_HIP_E_INVALID, who + "the plan's input planes (d) must be 3");
     }
-    if (c->rz.on)
+    if (!resized)
     {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv: not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)");
+        if (c->rz.on)
+        {
+            return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv: not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)");
+        }
+        return ingestPlanes(yuvKernelName(yf, H, W), ingestConverted,
+            [&](float* dst, int64_t out_fs, bool convert) { return launchIngestYuv(c, yf, nF, dst, out_fs, convert); });
     }
-    return ingestPlanes(yuvKernelName(yf, H, W), ingestConverted,
-        [&](float* dst, int64_t out_fs, bool convert) { return launchIngestYuv(c, yf, nF, dst, out_fs, convert); });
+    if (int rc = resizedTables(c, "pyramid_yuv_resized", yf.srcRows, yf.srcCols, yf.scale))
+    {
+        return rc;
+    }
+    return ingestPlanes("k_ingest_resized_yuv", ingestConverted,
+        [&](float* dst, int64_t out_fs, bool convert) { return launchIngestResized(c, nullptr, &yf, nF, dst, out_fs, convert); });
 }
 
 // ---- colour conversion, once at full resolution (chnsPyramid.cpp:230-263)
@@ -1130,7 +1159,8 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
     {
         if (u8 || img || yuv)
         {
-            return fail(c, ACF_HIP_E_UNSUPPORTED, std::string(yuv ? "pyramid_yuv" : (img ? "pyramid_image" : "pyramid_u8")) + ": not available with option \"streams\" > 1");
+            return fail(c, ACF_HIP_E_UNSUPPORTED, std::string(yuv ? "pyramid_yuv" : (img ? "pyramid_image" : "pyramid_u8")) + ((yuv && yuv->resized) || (img && img->resized) ? "_resized" : "") +
+                ": not available with option \"streams\" > 1");
         }
         if (!frames || nF <= 0 || nF > c->maxBatch)
         {

@@ -149,9 +149,10 @@ class HipDetector:
             raise HipError(capi.E_INVALID, "tensor entry: dtype must be uint8, float16, bfloat16 or float32, not %s" % t.dtype)
         return codes[t.dtype]
 
-    def _image_of(self, t, layout):
+    def _image_of(self, t, layout, scale=None):
         """(device pointer, n, capi.ImageDesc) of a device tensor [n, c, H, W] (layout "nchw") or [n, H, W, c] ("nhwc", taken as the
-        permuted view); the strides are the tensor's own: nothing is copied or made contiguous."""
+        permuted view); the strides are the tensor's own: nothing is copied or made contiguous.  scale: the resized entries — the
+        tensor is the unreduced frame, the plan is for resize_dims of its size."""
         if layout not in ("nchw", "nhwc"):
             raise HipError(capi.E_INVALID, "tensor entry: layout must be \"nchw\" or \"nhwc\"")
         if t.dim() != 4 or not t.is_cuda:
@@ -159,7 +160,12 @@ class HipDetector:
         if layout == "nhwc":
             t = t.permute(0, 3, 1, 2)
         n, ch, h, w = t.shape
-        if (h, w, ch) != (self.H, self.W, self.d_in):
+        if scale is not None:
+            if self._torch_dtype_code(t) != capi.T_U8:
+                raise HipError(capi.E_UNSUPPORTED, "resized tensor entry: uint8 only, not %s" % t.dtype)
+            if ch != self.d_in:
+                raise HipError(capi.E_INVALID, "resized tensor entry: the tensor has c = %d, the plan %d" % (ch, self.d_in))
+        elif (h, w, ch) != (self.H, self.W, self.d_in):
             raise HipError(capi.E_INVALID, "tensor entry: the tensor is c = %d, H = %d, W = %d; the plan is for %d, %d, %d" % (ch, h, w, self.d_in, self.H, self.W))
         sn, sc, sy, sx = t.stride()
         return t.data_ptr(), n, capi.ImageDesc(self._torch_dtype_code(t), ch, sn, sc, sy, sx)
@@ -173,12 +179,31 @@ class HipDetector:
         ptr, n, desc = self._image_of(t, layout)
         self._chk(self.lib.acf_hip_run_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
 
+    def pyramid_tensor_resized(self, t, scale, layout="nchw"):
+        """t: uint8 device tensor of the UNREDUCED frames [n, c, rows, cols] of any strides; the plan is for resize_dims(rows, cols,
+        scale).  The apps' resize and the ingest in one kernel; detections are in the reduced frame (unscale_boxes maps them back)."""
+        ptr, n, desc = self._image_of(t, layout, scale)
+        rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
+        self._chk(self.lib.acf_hip_pyramid_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), rows, cols, float(scale)))
+
+    def run_tensor_resized(self, t, scale, layout="nchw"):
+        ptr, n, desc = self._image_of(t, layout, scale)
+        rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
+        self._chk(self.lib.acf_hip_run_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), rows, cols, float(scale)))
+
     def pyramid_image(self, ptr, n, desc):
         """The raw entry: a device pointer (int) and a capi.ImageDesc."""
         self._chk(self.lib.acf_hip_pyramid_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
 
     def run_image(self, ptr, n, desc):
         self._chk(self.lib.acf_hip_run_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+
+    def pyramid_image_resized(self, ptr, n, desc, src_rows, src_cols, scale):
+        """The raw resized entry: desc (uint8) describes frames of src_rows x src_cols; the plan is for resize_dims of them."""
+        self._chk(self.lib.acf_hip_pyramid_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, float(scale)))
+
+    def run_image_resized(self, ptr, n, desc, src_rows, src_cols, scale):
+        self._chk(self.lib.acf_hip_run_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, float(scale)))
 
     @staticmethod
     def image_extent(desc, h, w, n):
@@ -241,6 +266,16 @@ class HipDetector:
     def run_yuv(self, base, n, desc):
         self._chk(self.lib.acf_hip_run_yuv(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, C.byref(desc)))
 
+    def pyramid_yuv_resized(self, base, n, desc, src_rows, src_cols, scale):
+        """desc describes frames of src_rows x src_cols; the plan is for resize_dims(src_rows, src_cols, scale).  Conversion, the apps'
+        resize and the ingest in one kernel; detections are in the reduced frame (unscale_boxes maps them back)."""
+        self._chk(self.lib.acf_hip_pyramid_yuv_resized(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, C.byref(desc),
+                                                       src_rows, src_cols, float(scale)))
+
+    def run_yuv_resized(self, base, n, desc, src_rows, src_cols, scale):
+        self._chk(self.lib.acf_hip_run_yuv_resized(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, C.byref(desc),
+                                                   src_rows, src_cols, float(scale)))
+
     @staticmethod
     def yuv_planes_desc(y, u, v, sub_x, sub_y):
         """(base pointer, n, capi.YuvDesc) of three torch uint8 device tensors [n, rows, cols] (or [rows, cols]) wherever they lie:
@@ -258,10 +293,14 @@ class HipDetector:
         mk = lambda t: capi.YuvPlane(t.data_ptr() - base, t.stride(0) if t.shape[0] > 1 else 0, t.stride(1), t.stride(2))
         return base, y.shape[0], capi.YuvDesc(mk(y), mk(u), mk(v), sub_x, sub_y)
 
-    def run_yuv_planes(self, y, u, v, sub_x=1, sub_y=1):
-        """Three separately allocated planes (a software decoder's frame): y [n, H, W], u and v [n, ceil(H / 2^sub_y), ceil(W / 2^sub_x)]."""
+    def run_yuv_planes(self, y, u, v, sub_x=1, sub_y=1, scale=None):
+        """Three separately allocated planes (a software decoder's frame): y [n, H, W], u and v [n, ceil(H / 2^sub_y), ceil(W / 2^sub_x)].
+        scale: the planes are the unreduced frame (run_yuv_resized; the plan is for resize_dims of y's size)."""
         base, n, desc = self.yuv_planes_desc(y, u, v, sub_x, sub_y)
-        self.run_yuv(base, n, desc)
+        if scale is None:
+            self.run_yuv(base, n, desc)
+        else:
+            self.run_yuv_resized(base, n, desc, y.shape[-2], y.shape[-1], scale)
 
     def yuv_to_rgb8(self, base, n, rows, cols, desc):
         """The conversion alone on the device -> torch uint8 CUDA tensor [n][rows][cols][3] (acf_hip_yuv_to_rgb8; no model or plan)."""
@@ -275,6 +314,11 @@ class HipDetector:
     def stream_open_yuv(self, desc, frame_bytes, cap=1024, depth=2):
         """The streaming front end for host frames of frame_bytes each, described by desc (stride_n == frame_bytes)."""
         self._chk(self.lib.acf_hip_stream_open_yuv(self.ctx, C.byref(desc), frame_bytes, cap, depth))
+        self._stream_cap = cap
+
+    def stream_open_yuv_resized(self, desc, frame_bytes, src_rows, src_cols, scale, cap=1024, depth=2):
+        """stream_open_yuv for unreduced frames of src_rows x src_cols: every submit runs run_yuv_resized on its slot."""
+        self._chk(self.lib.acf_hip_stream_open_yuv_resized(self.ctx, C.byref(desc), frame_bytes, src_rows, src_cols, float(scale), cap, depth))
         self._stream_cap = cap
 
     # ---- the apps' resize to a minimum object width (acf.cpp:117-148 Resizer) in front of the 8-bit entries

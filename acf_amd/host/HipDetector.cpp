@@ -569,12 +569,22 @@ int HipDetector::operator()(const float* rgb, int rows, int cols, RectVec& objec
     return 0;
 }
 
-int HipDetector::detectImages(const void* framesDev, int nFrames, int rows, int cols, const acf_hip_image_desc& desc,
-    std::vector<RectVec>& objects, std::vector<RealVec>* scores)
+// setMinObjectWidth in the tensor and YUV entries: the plan's size for frames of rows x cols (acf_hip_resize_dims); false: no resize
+bool HipDetector::resizedPlan(int rows, int cols, int& planRows, int& planCols) const
 {
-    ensurePlan(rows, cols, desc.channels, nFrames);
-    syncNms();
-    check(m_api->acf_hip_run_image(m_ctx, framesDev, nFrames, &desc), "acf_hip_run_image");
+    planRows = rows;
+    planCols = cols;
+    if (m_minObjectWidth < 0 || inputScale() == 1.f)
+    {
+        return false;
+    }
+    check(m_api->acf_hip_resize_dims(rows, cols, double(inputScale()), &planRows, &planCols), "acf_hip_resize_dims");
+    return true;
+}
+
+// every frame's detections of the batch just run; resized: mapped back as operator()(packed) does (Resizer::operator()(objects))
+void HipDetector::fetchBatch(int nFrames, bool resized, std::vector<RectVec>& objects, std::vector<RealVec>* scores)
+{
     objects.assign(size_t(nFrames), RectVec());
     if (scores)
     {
@@ -583,25 +593,55 @@ int HipDetector::detectImages(const void* framesDev, int nFrames, int rows, int 
     for (int f = 0; f < nFrames; f++)
     {
         fetch(f, objects[size_t(f)], scores ? &(*scores)[size_t(f)] : nullptr);
+        if (resized)
+        {
+            for (Rect& o : objects[size_t(f)])
+            {
+                o = unscale(o, inputScale());
+            }
+        }
     }
+}
+
+int HipDetector::detectImages(const void* framesDev, int nFrames, int rows, int cols, const acf_hip_image_desc& desc,
+    std::vector<RectVec>& objects, std::vector<RealVec>* scores)
+{
+    int planRows, planCols;
+    const bool resized = resizedPlan(rows, cols, planRows, planCols);
+    if (resized && desc.dtype != ACF_HIP_T_U8)
+    {
+        throw Exception(ACF_HIP_E_UNSUPPORTED, "detectImages: setMinObjectWidth takes 8-bit images (cv::resize's CV_32F arithmetic is not restated)");
+    }
+    ensurePlan(planRows, planCols, desc.channels, nFrames);
+    syncNms();
+    if (resized)
+    {
+        check(m_api->acf_hip_run_image_resized(m_ctx, framesDev, nFrames, &desc, rows, cols, double(inputScale())), "acf_hip_run_image_resized");
+    }
+    else
+    {
+        check(m_api->acf_hip_run_image(m_ctx, framesDev, nFrames, &desc), "acf_hip_run_image");
+    }
+    fetchBatch(nFrames, resized, objects, scores);
     return 0;
 }
 
 int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc& desc, std::vector<RectVec>& objects,
     std::vector<RealVec>* scores)
 {
-    ensurePlan(rows, cols, 3, nFrames);
+    int planRows, planCols;
+    const bool resized = resizedPlan(rows, cols, planRows, planCols);
+    ensurePlan(planRows, planCols, 3, nFrames);
     syncNms();
-    check(m_api->acf_hip_run_yuv(m_ctx, baseDev, nFrames, &desc), "acf_hip_run_yuv");
-    objects.assign(size_t(nFrames), RectVec());
-    if (scores)
+    if (resized)
     {
-        scores->assign(size_t(nFrames), RealVec());
+        check(m_api->acf_hip_run_yuv_resized(m_ctx, baseDev, nFrames, &desc, rows, cols, double(inputScale())), "acf_hip_run_yuv_resized");
     }
-    for (int f = 0; f < nFrames; f++)
+    else
     {
-        fetch(f, objects[size_t(f)], scores ? &(*scores)[size_t(f)] : nullptr);
+        check(m_api->acf_hip_run_yuv(m_ctx, baseDev, nFrames, &desc), "acf_hip_run_yuv");
     }
+    fetchBatch(nFrames, resized, objects, scores);
     return 0;
 }
 
@@ -698,16 +738,22 @@ void HipDetector::streamOpen(int rows, int cols, int pix, int rowStrideBytes, in
 
 void HipDetector::streamOpenYuv(int rows, int cols, const acf_hip_yuv_desc& desc, size_t frameBytes, int maxBatch, int depth, int maxDetectionsPerFrame)
 {
-    if (m_minObjectWidth >= 0 && inputScale() != 1.f)
-    {
-        throw Exception(ACF_HIP_E_UNSUPPORTED, "streamOpenYuv: not with setMinObjectWidth (the input resize takes the packed 8-bit entries' frames)");
-    }
-    ensurePlan(rows, cols, 3, maxBatch);
+    int planRows, planCols;
+    const bool resized = resizedPlan(rows, cols, planRows, planCols);
+    ensurePlan(planRows, planCols, 3, maxBatch);
     (void)m_api->acf_hip_stream_close(m_ctx);
     check(m_api->acf_hip_set_input_resize(m_ctx, 0, 0, 1.0), "acf_hip_set_input_resize");
     m_srcRows = rows;
     m_srcCols = cols;
-    check(m_api->acf_hip_stream_open_yuv(m_ctx, &desc, int64_t(frameBytes), maxDetectionsPerFrame, depth), "acf_hip_stream_open_yuv");
+    if (resized) // (streamCollect maps the boxes back)
+    {
+        check(m_api->acf_hip_stream_open_yuv_resized(m_ctx, &desc, int64_t(frameBytes), rows, cols, double(inputScale()), maxDetectionsPerFrame, depth),
+            "acf_hip_stream_open_yuv_resized");
+    }
+    else
+    {
+        check(m_api->acf_hip_stream_open_yuv(m_ctx, &desc, int64_t(frameBytes), maxDetectionsPerFrame, depth), "acf_hip_stream_open_yuv");
+    }
     m_streamCap = maxDetectionsPerFrame;
     m_streamPix = -1; // (operator()(packed) reopens its own stream)
     m_streamStride = 0;

@@ -292,12 +292,16 @@ public:
 
     // Batch of upright images in memory the device reads (device memory, or page-locked memory from pinnedAlloc), of any element
     // strides and element type: include/acf_hip.h, acf_hip_run_image.  rows x cols = the image's size; NMS / prune as detectBatch.
+    // With setMinObjectWidth (inputScale() != 1) an ACF_HIP_T_U8 image is reduced first, in the same kernel (acf_hip_run_image_resized),
+    // and the boxes are mapped back as operator()(packed) does; a float image then throws ACF_HIP_E_UNSUPPORTED.
     int detectImages(const void* framesDev, int nFrames, int rows, int cols, const acf_hip_image_desc& desc,
         std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
 
     // Batch of YUV video frames of three planes in memory the device reads, each plane described by its own offset and byte strides
     // (I420 / YV12 / I422 / I444, packed 4:2:2, NV12 / NV21, three separately allocated planes): include/acf_hip.h, acf_hip_run_yuv.
     // The conversion is cvtColor's BT.601 integer formula (restated, parity unpinned), on the device, fused into the ingest.
+    // With setMinObjectWidth (inputScale() != 1): converted, reduced and ingested in one kernel (acf_hip_run_yuv_resized), the boxes
+    // mapped back as operator()(packed) does.
     int detectYuv(const uint8_t* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc& desc,
         std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
     // the descriptor of a named layout (ACF_HIP_YUV_*) of rows x cols; *frameBytes = the distance to the next frame
@@ -310,7 +314,8 @@ public:
     // collected in submission order.  At most maxDetectionsPerFrame (streamOpen) boxes per frame come back, in the
     // reference's order, before NMS/prune are applied exactly as in operator().
     void streamOpen(int rows, int cols, int pix, int rowStrideBytes, int maxBatch, int depth = 2, int maxDetectionsPerFrame = 4096);
-    // the same for host frames of frameBytes each described by a YUV descriptor (acf_hip_stream_open_yuv); submit / collect as above
+    // the same for host frames of frameBytes each described by a YUV descriptor (acf_hip_stream_open_yuv; with setMinObjectWidth
+    // acf_hip_stream_open_yuv_resized: streamCollect maps the boxes back); submit / collect as above
     void streamOpenYuv(int rows, int cols, const acf_hip_yuv_desc& desc, size_t frameBytes, int maxBatch, int depth = 2, int maxDetectionsPerFrame = 4096);
     int streamSubmit(const uint8_t* frames, int nFrames);
     // bytes from one tight frame of layout `pix` to the next: what a batch for streamSubmit / a frame for operator()(packed) holds
@@ -398,6 +403,8 @@ private:
     static void logColourPlanes(const MatLoggerType& logger, MatP& planes, int d, int H, int W);
     static MatP hconcatHist(const float* src, int firstPlane, int nOrients, int hC, int wC);
     void fetch(int frame, RectVec& objects, RealVec* scores);
+    bool resizedPlan(int rows, int cols, int& planRows, int& planCols) const;
+    void fetchBatch(int nFrames, bool resized, std::vector<RectVec>& objects, std::vector<RealVec>* scores);
     void detect1(const float* f32, const uint8_t* u8, int rows, int cols, DetectionVec& objects);
     void finish(DetectionVec& bbs, RectVec& objects, RealVec* scores, bool forceHostNms = false) const; // ACF.cpp:332-364
     void logPyramid(); // ACF.cpp:252-262

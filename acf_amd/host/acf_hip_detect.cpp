@@ -5,9 +5,10 @@
 //                  [--luv] [--nms] [--batch] [--via-pyramid] [--max-count K] [--prune-ratio R]
 //   acf_hip_detect --model m.acfm --frames f.u8 --u8 rgb|bgr|rgba|bgra|gray|nv12|nv21 --rows H --cols W --count N [--stream B] [--min-width M] ...
 //                  packed 8-bit upright frames (nv12 / nv21: tight YUV 4:2:0 video frames); --stream B: batches of B frames through streamSubmit/streamCollect
-//   acf_hip_detect --model m.acfm --frames f.yuv --yuv i420|yv12|i422|i444|yuyv|uyvy|yvyu|nv12|nv21 --rows H --cols W --count N [--stream B]
+//   acf_hip_detect --model m.acfm --frames f.yuv --yuv i420|yv12|i422|i444|yuyv|uyvy|yvyu|nv12|nv21 --rows H --cols W --count N [--stream B] [--min-width M]
 //                  tight YUV video frames of the named layout through detectYuv (one batch; the frames in page-locked memory, which the
-//                  device reads), or --stream B through streamOpenYuv / streamSubmit / streamCollect
+//                  device reads), or --stream B through streamOpenYuv / streamSubmit / streamCollect; --min-width M: reduced on the device
+//                  first, in the ingest kernel (acf_hip_run_yuv_resized), the boxes mapped back
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
@@ -164,7 +165,7 @@ int main(int argc, char** argv)
         det.setDoNonMaximaSuppression(a.count("nms") != 0);
         if (a.count("max-count")) det.setMaxDetectionCount(size_t(std::stoul(a["max-count"])));
         if (a.count("prune-ratio")) det.setDetectionScorePruneRatio(std::stod(a["prune-ratio"]));
-        if (a.count("min-width")) det.setMinObjectWidth(std::stoi(a["min-width"])); // the apps' Resizer (acf.cpp:117-148), 8-bit entries
+        if (a.count("min-width")) det.setMinObjectWidth(std::stoi(a["min-width"])); // the apps' Resizer (acf.cpp:117-148): 8-bit and YUV entries
         if (a.count("casc-cal"))
         {
             HipDetector::Modify m;

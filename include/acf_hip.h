@@ -523,6 +523,39 @@ ACF_HIP_API int acf_hip_set_input_resize(acf_hip_ctx* ctx, int src_rows, int src
 ACF_HIP_API int acf_hip_op_resize_u8(acf_hip_ctx* ctx, const uint8_t* src_host, int rows, int cols, int cpp, int row_stride_bytes, double scale,
     uint8_t* dst_host, int dst_rows, int dst_cols);
 
+/* The same resize inside the tensor and YUV entries: frames of src_rows x src_cols as the descriptor describes them (acf_hip_image_desc
+ * / acf_hip_yuv_desc above; acf_hip_image_extent / acf_hip_yuv_extent called with src_rows x src_cols give exactly the bytes that are
+ * read), reduced by `scale` and ingested in ONE kernel (k_ingest_resized; option "profile": k_ingest_resized_image /
+ * k_ingest_resized_yuv) — no converted or reduced 8-bit image goes to device memory.  The plan must be for
+ * acf_hip_resize_dims(src_rows, src_cols, scale).
+ * Definition: the existing entries composed, bit for bit —
+ *   YUV    acf_hip_yuv_to_rgb8 on the source frames, acf_hip_op_resize_u8's arithmetic with 3 bytes a pixel, acf_hip_pyramid_u8 / run_u8
+ *          (ACF_HIP_PIX_RGB)
+ *   image  the addressed bytes as an upright interleaved image of `channels` bytes a pixel, the same resize with cpp = channels, run_u8
+ *          with ACF_HIP_PIX_RGB or ACF_HIP_PIX_GRAY
+ * every plane, level, hit, score bit and box, option "arith" = 1 included.  Detections are in the reduced frame's coordinates, as with
+ * acf_hip_set_input_resize: cv::Rect2f(o) * (1.f / scale) maps them back.  cv::resize and cvtColor are OpenCV's (not part of the
+ * reference tree): their published arithmetic is restated; PARITY UNPINNED.
+ * The tap tables of (src_rows, src_cols, scale) are built and uploaded at the first call with a new triple (which waits for the
+ * context's stream before the previous triple's tables go) and kept: nothing is allocated on later calls with the same triple; a new
+ * plan drops them.  Asynchronous on the context's stream; the calls always run plainly and leave a captured graph of acf_hip_run
+ * (option "graph") valid; ACF_HIP_TAP_IMAGE behaves as after acf_hip_pyramid_u8.
+ * ACF_HIP_E_INVALID: what the un-resized entry refuses; src_rows / src_cols < 1; a scale that is not a positive finite number; a plan
+ * of other dimensions; an active acf_hip_set_input_resize.  ACF_HIP_E_UNSUPPORTED: option "streams" > 1; an image dtype other than
+ * ACF_HIP_T_U8 (cv::resize's CV_32F arithmetic is not restated).  ACF_HIP_E_NOPLAN without a plan.
+ *  acf_hip_stream_open_yuv_resized   acf_hip_stream_open_yuv's rules with the one-frame extents taken at src_rows x src_cols; every
+ *                                    submit runs acf_hip_run_yuv_resized on its slot; submit / collect / close are unchanged */
+ACF_HIP_API int acf_hip_pyramid_yuv_resized(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc, int src_rows,
+    int src_cols, double scale);
+ACF_HIP_API int acf_hip_run_yuv_resized(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc, int src_rows, int src_cols,
+    double scale);
+ACF_HIP_API int acf_hip_pyramid_image_resized(acf_hip_ctx* ctx, const void* frames_dev, int n_frames, const acf_hip_image_desc* desc, int src_rows,
+    int src_cols, double scale);
+ACF_HIP_API int acf_hip_run_image_resized(acf_hip_ctx* ctx, const void* frames_dev, int n_frames, const acf_hip_image_desc* desc, int src_rows, int src_cols,
+    double scale);
+ACF_HIP_API int acf_hip_stream_open_yuv_resized(acf_hip_ctx* ctx, const acf_hip_yuv_desc* desc, int64_t frame_bytes, int src_rows, int src_cols,
+    double scale, int cap, int depth);
+
 /* ---- streaming front end ---------------------------------------------
  * The overlap of transfer and compute that GPUDetectionPipeline::runFast gets
  * from its two-frame texture FIFO (GPUDetectionPipeline.cpp:357-437), expressed
