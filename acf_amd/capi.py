@@ -209,6 +209,7 @@ def load():
         "acf_hip_set_model": ([ctx, C.POINTER(Params)], C.c_int),
         "acf_hip_get_scales": ([C.c_int] * 7 + [C.POINTER(C.c_double)] * 3 + [C.c_int, C.POINTER(C.c_int)], C.c_int),
         "acf_hip_plan_levels": ([C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.POINTER(Level), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_check_model": ([C.POINTER(Params), C.c_int, C.c_char_p, C.c_int], C.c_int),
         "acf_hip_plan": ([ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
         "acf_hip_num_levels": ([ctx, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
         "acf_hip_get_levels": ([ctx, C.POINTER(Level), C.c_int], C.c_int),
@@ -287,7 +288,7 @@ def load():
 
 DECLARED_SYMBOLS = [
     "acf_hip_create", "acf_hip_device_count", "acf_hip_destroy", "acf_hip_abi_version", "acf_hip_last_error", "acf_hip_set_option",
-    "acf_hip_set_model", "acf_hip_get_scales", "acf_hip_plan_levels",
+    "acf_hip_set_model", "acf_hip_get_scales", "acf_hip_plan_levels", "acf_hip_check_model",
     "acf_hip_plan", "acf_hip_num_levels", "acf_hip_get_levels", "acf_hip_get_ldcf_levels", "acf_hip_pyramid_floats", "acf_hip_get_lambdas", "acf_hip_pyramid",
     "acf_hip_detect", "acf_hip_run", "acf_hip_run_host", "acf_hip_set_nms", "acf_hip_op_nms", "acf_hip_get_detections", "acf_hip_get_hits", "acf_hip_get_raw_detections",
     "acf_hip_pyramid_u8", "acf_hip_run_u8", "acf_hip_set_yuv_layout", "acf_hip_op_yuv420_to_rgb", "acf_hip_u8_frame_bytes", "acf_hip_resize_dims", "acf_hip_set_input_resize", "acf_hip_op_resize_u8", "acf_hip_stream_open", "acf_hip_stream_submit", "acf_hip_stream_collect",

@@ -1555,6 +1555,84 @@ int acf_hip_plan_levels(const acf_hip_params* p, int h, int w, int d, acf_hip_le
     return ACF_HIP_OK;
 }
 
+// What a classifier must satisfy before a walk is launched on it (include/acf_hip.h, acf_hip_params::child).  Only the nodes that carry a
+// feature test are looked at: the first 2^depth - 1 of a fixed-depth tree, the nodes with child != 0 of a variable-depth one; leaves
+// and unused slots may hold anything.  nChns > 0: every test's feature id against nChns planes of the model window in cells of `cell`
+// pixels (cids[], acfDetect1.cpp:390-406).
+static int checkModel(const acf_hip_params& p, int nChns, int cell, std::string& why)
+{
+    if (p.nTrees <= 0 || p.nTreeNodes <= 0 || !p.fids || !p.thrs || !p.hs)
+    {
+        why = "empty classifier";
+        return ACF_HIP_E_INVALID;
+    }
+    if (p.treeDepth < 0 || p.treeDepth > 8)
+    {
+        why = "treeDepth must be 0..8 (acfDetect1.cpp:204-226)";
+        return ACF_HIP_E_INVALID;
+    }
+    if (p.treeDepth == 0 && !p.child)
+    {
+        why = "treeDepth 0 needs child[]";
+        return ACF_HIP_E_INVALID;
+    }
+    if (p.treeDepth > 0 && p.nTreeNodes < (1 << (p.treeDepth + 1)) - 1)
+    {
+        why = "nTreeNodes too small for treeDepth";
+        return ACF_HIP_E_INVALID;
+    }
+    if (p.stride <= 0 || p.shrink <= 0 || cell <= 0 || p.modelDsPad_h % p.shrink || p.modelDsPad_w % p.shrink)
+    {
+        why = "stride/shrink/modelDsPad";
+        return ACF_HIP_E_INVALID;
+    }
+    const uint64_t nF = nChns > 0 ? uint64_t(nChns) * uint64_t(p.modelDsPad_h / cell) * uint64_t(p.modelDsPad_w / cell) : 0;
+    const int nInternal = p.treeDepth > 0 ? (1 << p.treeDepth) - 1 : 0;
+    for (int t = 0; t < p.nTrees; t++)
+    {
+        for (int k = 0; k < p.nTreeNodes; k++)
+        {
+            const size_t q = size_t(t) * p.nTreeNodes + k;
+            const bool test = p.treeDepth > 0 ? k < nInternal : p.child[q] != 0;
+            // next node = child[k] - (ftr < thr), in 0-based terms child[k] - 1 or child[k] (acfDetect1.cpp:146-155): both must stay
+            // inside the tree AND lie after k — trees are stored parent-first, and a backward or self reference in an untrusted
+            // model file would make the walk `while (child[k])` spin forever on the GPU
+            if (p.treeDepth == 0 && test && (p.child[q] >= uint32_t(p.nTreeNodes) || p.child[q] - 1 <= uint32_t(k)))
+            {
+                why = "child[] of tree " + std::to_string(t) + ", node " + std::to_string(k) + " is " + std::to_string(p.child[q]) +
+                    ": the pair child - 1, child must lie after its parent and inside the tree's " + std::to_string(p.nTreeNodes) + " nodes";
+                return ACF_HIP_E_INVALID;
+            }
+            if (nChns > 0 && test && p.fids[q] >= nF)
+            {
+                why = "feature id out of range for modelDsPad/shrink/channels (tree " + std::to_string(t) + ", node " + std::to_string(k) + ": " +
+                    std::to_string(p.fids[q]) + " of " + std::to_string(nF) + ")";
+                return ACF_HIP_E_INVALID;
+            }
+        }
+    }
+    return ACF_HIP_OK;
+}
+
+int acf_hip_check_model(const acf_hip_params* p, int nChns, char* why, int cap)
+{
+    std::string err;
+    int rc = ACF_HIP_E_INVALID;
+    if (!p || nChns < 0)
+    {
+        err = "check_model: arguments";
+    }
+    else
+    {
+        rc = checkModel(*p, nChns, p->shrink, err);
+    }
+    if (why && cap > 0)
+    {
+        std::snprintf(why, size_t(cap), "%s", err.c_str());
+    }
+    return rc;
+}
+
 int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
 {
     dropGraph(c);
@@ -1571,25 +1649,14 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
     {
         return ACF_HIP_E_INVALID;
     }
-    if (p->nTrees <= 0 || p->nTreeNodes <= 0 || !p->fids || !p->thrs || !p->hs)
     {
-        return fail(c, ACF_HIP_E_INVALID, "set_model: empty classifier");
-    }
-    if (p->treeDepth < 0 || p->treeDepth > 8)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "set_model: treeDepth must be 0..8 (acfDetect1.cpp:204-226)");
-    }
-    if (p->treeDepth == 0 && !p->child)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "set_model: treeDepth 0 needs child[]");
-    }
-    if (p->treeDepth > 0 && p->nTreeNodes < (1 << (p->treeDepth + 1)) - 1)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "set_model: nTreeNodes too small for treeDepth");
-    }
-    if (p->stride <= 0 || p->shrink <= 0 || p->modelDsPad_h % p->shrink || p->modelDsPad_w % p->shrink)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "set_model: stride/shrink/modelDsPad");
+        // the structure alone (nChns = 0: the channels a call scores on are not known yet): no entry launches a walk on a model
+        // that did not pass here
+        std::string why;
+        if (const int rc = checkModel(*p, 0, p->shrink, why))
+        {
+            return fail(c, rc, "set_model: " + why);
+        }
     }
     if (p->nOrients < 1 || p->nOrients > 12)
     {

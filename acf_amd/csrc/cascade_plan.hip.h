@@ -369,13 +369,20 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
     cs.nLevels = int(lv.size());
     const acf_hip_params& p = c->p;
     const int mH = p.modelDsPad_h / cell, mW = p.modelDsPad_w / cell;
-    const uint32_t nF = uint32_t(nChns) * mH * mW;
     const size_t nNodes = size_t(p.nTrees) * p.nTreeNodes;
     const bool packed = p.treeDepth == 2;
     std::vector<CascLevel> cl(lv.size());
     std::vector<int32_t> bl;
     std::vector<uint32_t> cidAll;
     std::vector<CascNode2> nodes2;
+    // the tests' feature ids against these channels and cells (child[] itself passed at acf_hip_set_model; checkModel looks again)
+    {
+        std::string why;
+        if (const int rc = checkModel(p, nChns, cell, why))
+        {
+            return fail(c, rc, "model: " + why);
+        }
+    }
     // which nodes carry a feature test
     std::vector<uint8_t> internal(nNodes, 0);
     for (int t = 0; t < p.nTrees; t++)
@@ -384,20 +391,6 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
         {
             const size_t q = size_t(t) * p.nTreeNodes + k;
             internal[q] = p.treeDepth > 0 ? (k < (1 << p.treeDepth) - 1) : (c->child[q] != 0);
-            if (internal[q] && c->fids[q] >= nF)
-            {
-                return fail(c, ACF_HIP_E_INVALID, "model: feature id out of range for modelDsPad/shrink/channels");
-            }
-            if (p.treeDepth == 0 && c->child[q] != 0)
-            {
-                // next node = child[k] - (ftr < thr) in 0-based terms child[k] - 1 or child[k] (acfDetect1.cpp:146-155): both must
-                // stay inside the tree AND lie after k — trees are stored parent-first, and a backward or self reference in
-                // an untrusted model file would make the walk `while (child[k])` spin forever on the GPU
-                if (c->child[q] >= uint32_t(p.nTreeNodes) || c->child[q] - 1 <= uint32_t(k))
-                {
-                    return fail(c, ACF_HIP_E_INVALID, "model: child index out of range or not after its parent");
-                }
-            }
         }
     }
     int block = 0;

@@ -72,11 +72,13 @@ int ensureCropModel(acf_hip_ctx* c)
         dropCropModel(c);
         return fail(c, ACF_HIP_E_HIP, "evaluate_crops: uploading the classifier failed");
     }
-    // the largest feature id a walk can read: every node's for fixed depths, the inner nodes' for the child-pointer walk
+    // the largest feature id a walk can read (checkModel's rule, kept as one number so that a call compares once): the first
+    // 2^depth - 1 nodes of a fixed-depth tree, the nodes with a child of the child-pointer walk; child[] itself passed at acf_hip_set_model
     m.fidMax = 0;
+    const size_t nInternal = c->p.treeDepth > 0 ? (size_t(1) << c->p.treeDepth) - 1 : 0;
     for (size_t i = 0; i < c->fids.size(); i++)
     {
-        if (c->p.treeDepth > 0 || c->child[i])
+        if (c->p.treeDepth > 0 ? i % size_t(c->p.nTreeNodes) < nInternal : c->child[i] != 0)
         {
             m.fidMax = std::max(m.fidMax, c->fids[i]);
         }

@@ -771,6 +771,14 @@ int acf_hip_op_evaluate(acf_hip_ctx* c, const float* chns, int hP, int wP, int n
     {
         return fail(c, ACF_HIP_E_INVALID, "op_evaluate: the buffer must hold at least one window");
     }
+    {
+        // before anything is allocated or launched: every test's feature id lies inside the nChns planes of the window
+        std::string why;
+        if (const int rc = checkModel(p, nChns, p.shrink, why))
+        {
+            return fail(c, rc, "op_evaluate: " + why);
+        }
+    }
     Scratch s;
     const size_t n = size_t(nChns) * hP * wP;
     float* dC = s.upload(chns, n);

@@ -44,6 +44,7 @@ static void doLoad(const std::string& path)
     ACF_HIP_FN(acf_hip_set_option)
     ACF_HIP_FN(acf_hip_get_scales)
     ACF_HIP_FN(acf_hip_plan_levels)
+    ACF_HIP_FN(acf_hip_check_model)
     ACF_HIP_FN(acf_hip_set_model)
     ACF_HIP_FN(acf_hip_plan)
     ACF_HIP_FN(acf_hip_num_levels)

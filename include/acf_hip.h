@@ -75,7 +75,12 @@ typedef struct acf_hip_params
     const uint32_t* fids;
     const float* thrs;
     const float* hs;
-    const uint32_t* child; /* may be NULL when treeDepth > 0 */
+    /* treeDepth 0 (may be NULL when treeDepth > 0): child[k] == 0 marks a leaf; otherwise node k carries a test and the walk goes on
+     * at node child[k] - (ftr < thr) of the same tree, i.e. the pair sits at child[k] - 1 and child[k] (acfDetect1.cpp:146-155).
+     * Contract, checked by acf_hip_check_model and refused by acf_hip_set_model: child[k] < nTreeNodes and child[k] - 1 > k (trees
+     * are stored parent-first, so every walk ends after at most nTreeNodes / 2 steps).  Only nodes with a test are read: fids, thrs
+     * and child of a leaf, hs of a node with a test, and every array of a slot no walk reaches may hold anything. */
+    const uint32_t* child;
 
     /* Options: modelDs, modelDsPad, stride, cascThr (ACF.h:204-211) */
     int32_t modelDs_h, modelDs_w;
@@ -289,7 +294,15 @@ ACF_HIP_API int acf_hip_get_scales(int nPerOct, int nOctUp, int minDs_h, int min
  * acfDetect1.cpp:258-259, yield). */
 ACF_HIP_API int acf_hip_plan_levels(const acf_hip_params* p, int h, int w, int d, acf_hip_level* out, int cap, int* nScales, int* nChns);
 
-/* Upload classifier + options.  Replaces Detector::deserialize*() filling
+/* Is this classifier one the device may walk?  Host only, no context.  Always: the checks of acf_hip_set_model on nTrees, nTreeNodes,
+ * treeDepth, the arrays, stride, shrink and modelDsPad, and for treeDepth 0 the child[] contract (acf_hip_params::child).  nChns > 0:
+ * also every test's feature id < nChns * (modelDsPad_h / shrink) * (modelDsPad_w / shrink), the index space of cids[]
+ * (acfDetect1.cpp:390-406); nChns = 0: structure only.  Leaves and unused slots are not inspected.  Returns ACF_HIP_OK or
+ * ACF_HIP_E_INVALID; `why` (may be NULL) receives the reason, at most cap bytes with the terminator. */
+ACF_HIP_API int acf_hip_check_model(const acf_hip_params* p, int nChns, char* why, int cap);
+
+/* Upload classifier + options.  Refuses what acf_hip_check_model(p, 0, ..) refuses, so that no later entry launches a walk over a
+ * child[] that does not end.  Replaces Detector::deserialize*() filling
  * `clf` and `opts` (ACF.h:277,312) and acfModify's effects (acfModify.cpp:139-143),
  * which the caller applies to the struct before the call. */
 ACF_HIP_API int acf_hip_set_model(acf_hip_ctx* ctx, const acf_hip_params* p);

@@ -1,4 +1,4 @@
-"""A fixed-seed slice of tests/fuzz_parity.py: random frame sizes, model shapes (depth 1-4, trees, scales per octave,
+"""A fixed-seed slice of tests/fuzz_parity.py: random frame sizes, model shapes (depth 1-4 or variable-depth trees of a random shape, trees, scales per octave,
 pads, gradient plane, full orientation) and option sets (fused_grad, segments, streams, rank cells, graph, tiles) against the
 oracle — pyramid bits, hits and boxes.  (Five seeds x 60 cases ran clean when this was added; the slice keeps that alive.)"""
 import os
