@@ -2,14 +2,14 @@
 // planning, buffer ownership and kernel launches.  All device work is
 // enqueued on the context's stream; nothing here falls back to the CPU.
 // This file holds the context, the guards and helpers every entry shares, and the plan / run / stream entries; the stages'
-// logic, the read-back entries and the single-operator entries are textual parts (*.hip.h), included in the order of their use.
+// logic, the input entries (input_run.hip.h), the read-back entries and the single-operator entries are textual parts (*.hip.h), included
+// in the order of their use.
 #include "kernels.hip.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -51,6 +51,28 @@ struct RealScale
     StripPlan strip, stripPair;     // k_resample_strip: this scale's image alone / together with the next real scale's (stripPair.ok)
     float *img = nullptr, *sm = nullptr, *M = nullptr, *O = nullptr, *U = nullptr, *S = nullptr, *Mn = nullptr;
     int64_t uFloats = 0, moFloats = 0; // floats per frame of U and of M, O (room for the blocked layouts' padding)
+};
+
+// Where the frames of a call come from: what every entry that takes frames hands to pyramidBody (input_run.hip.h holds the rest of
+// the input path; the type stands here because the context keeps the one its stream was opened with)
+enum SourceKind
+{
+    SRC_F32,   // planar float planes, the pyramid's own layout
+    SRC_U8,    // packed 8-bit frames: pix (ACF_HIP_PIX_*, NV12 / NV21 included), rowStride
+    SRC_IMAGE, // an upright image of any element strides: img
+    SRC_YUV    // three planes described by offsets and byte strides: yuv
+};
+struct FrameSource
+{
+    SourceKind kind = SRC_F32;
+    const void* base = nullptr;
+    const char* who = "pyramid";  // the entry's name in messages
+    int pix = 0, rowStride = 0;
+    acf_hip_image_desc img{};
+    acf_hip_yuv_desc yuv{};
+    bool resized = false;         // the resized entries: frames of srcRows x srcCols, reduced by `scale` to the plan's size
+    int srcRows = 0, srcCols = 0;
+    double scale = 1;
 };
 
 } // namespace
@@ -351,12 +373,9 @@ struct acf_hip_ctx
     };
     std::vector<StreamSlot> slots;
     hipStream_t copyStream = nullptr;
-    int stPix = 0, stStride = 0, stCap = 0, nextTicket = 0, nextCollect = 0;
+    int stCap = 0, nextTicket = 0, nextCollect = 0;
     int64_t stFrameBytes = 0; // bytes between the frames of a submitted batch
-    bool stYuv = false;       // opened by acf_hip_stream_open_yuv: a batch runs through acf_hip_run_yuv with stYuvDesc
-    acf_hip_yuv_desc stYuvDesc{};
-    int stSrcRows = 0, stSrcCols = 0; // > 0: opened by acf_hip_stream_open_yuv_resized: acf_hip_run_yuv_resized with these and stScale
-    double stScale = 1;
+    FrameSource stSrc;        // what the stream was opened for: a batch runs as this source at its slot's device buffer
     // the plan's cascade (tables, model arrays, work queues, outputs); acf_hip_op_acf_detect1 builds and runs a state of its own
     CascState cs;
     BoxLevel* d_boxLevels = nullptr;
@@ -1895,622 +1914,6 @@ static bool resampleUpOk(const ResampleDesc& d)
 
 namespace
 {
-// packed 8-bit source of a batch (acf_hip_pyramid_u8)
-struct PackedSrc
-{
-    const uint8_t* frames;
-    int pix, rowStride;
-};
-
-// an upright image of any element strides (acf_hip_pyramid_image)
-struct ImageSrc
-{
-    const void* frames;
-    acf_hip_image_desc d;
-    bool resized = false;         // the resized entry: frames of srcRows x srcCols, reduced by `scale` to the plan's size
-    int srcRows = 0, srcCols = 0;
-    double scale = 1;
-};
-
-// a YUV frame of three planes described by offsets and byte strides (acf_hip_pyramid_yuv)
-struct YuvFrames
-{
-    const uint8_t* base;
-    acf_hip_yuv_desc d;
-    bool resized = false;         // the resized entry: frames of srcRows x srcCols, reduced by `scale` to the plan's size
-    int srcRows = 0, srcCols = 0;
-    double scale = 1;
-};
-
-using ResizedKernel = void (*)(IngestArgs, ResizedSrc);
-
-// k_ingest_resized<source, conversion>: [RS_*][IG_*]
-static ResizedKernel resizedKernel(int src, int mode)
-{
-    static const ResizedKernel table[2][4] = {
-        { k_ingest_resized<RS_IMAGE, IG_PLANAR>, k_ingest_resized<RS_IMAGE, IG_LUV_VEC>, k_ingest_resized<RS_IMAGE, IG_LUV>, k_ingest_resized<RS_IMAGE, IG_GRAY> },
-        { k_ingest_resized<RS_YUV, IG_PLANAR>, k_ingest_resized<RS_YUV, IG_LUV_VEC>, k_ingest_resized<RS_YUV, IG_LUV>, k_ingest_resized<RS_YUV, IG_GRAY> },
-    };
-    return table[src][mode];
-}
-
-using IngestKernel = void (*)(IngestArgs);
-using ImageKernel = void (*)(IngestArgs, ImageArgs);
-using YuvDescKernel = void (*)(IngestArgs, YuvDescSrc);
-
-// k_ingest_yuv<conversion, load form>: [YD_*][IG_*]
-static YuvDescKernel yuvDescKernel(int form, int mode)
-{
-    static const YuvDescKernel table[3][4] = {
-        { k_ingest_yuv<IG_PLANAR, YD_GENERIC>, k_ingest_yuv<IG_LUV_VEC, YD_GENERIC>, k_ingest_yuv<IG_LUV, YD_GENERIC>, k_ingest_yuv<IG_GRAY, YD_GENERIC> },
-        { k_ingest_yuv<IG_PLANAR, YD_PLANAR>, k_ingest_yuv<IG_LUV_VEC, YD_PLANAR>, k_ingest_yuv<IG_LUV, YD_PLANAR>, k_ingest_yuv<IG_GRAY, YD_PLANAR> },
-        { k_ingest_yuv<IG_PLANAR, YD_PACKED422>, k_ingest_yuv<IG_LUV_VEC, YD_PACKED422>, k_ingest_yuv<IG_LUV, YD_PACKED422>, k_ingest_yuv<IG_GRAY, YD_PACKED422> },
-    };
-    return table[form][mode];
-}
-
-// k_ingest_image<element type, conversion>: [ACF_HIP_T_*][IG_*]
-static ImageKernel imageKernel(int dtype, int mode)
-{
-    static const ImageKernel table[4][4] = {
-        { k_ingest_image<IM_U8, IG_PLANAR>, k_ingest_image<IM_U8, IG_LUV_VEC>, k_ingest_image<IM_U8, IG_LUV>, k_ingest_image<IM_U8, IG_GRAY> },
-        { k_ingest_image<IM_F16, IG_PLANAR>, k_ingest_image<IM_F16, IG_LUV_VEC>, k_ingest_image<IM_F16, IG_LUV>, k_ingest_image<IM_F16, IG_GRAY> },
-        { k_ingest_image<IM_BF16, IG_PLANAR>, k_ingest_image<IM_BF16, IG_LUV_VEC>, k_ingest_image<IM_BF16, IG_LUV>, k_ingest_image<IM_BF16, IG_GRAY> },
-        { k_ingest_image<IM_F32, IG_PLANAR>, k_ingest_image<IM_F32, IG_LUV_VEC>, k_ingest_image<IM_F32, IG_LUV>, k_ingest_image<IM_F32, IG_GRAY> },
-    };
-    return table[dtype][mode];
-}
-
-using YuvIngestKernel = void (*)(IngestArgs, YuvSrc);
-
-static IngestKernel ingestKernel(int mode, bool aligned)
-{
-    switch (mode)
-    {
-        case IG_LUV_VEC: return aligned ? k_ingest_u8<IG_LUV_VEC, true> : k_ingest_u8<IG_LUV_VEC, false>;
-        case IG_LUV: return aligned ? k_ingest_u8<IG_LUV, true> : k_ingest_u8<IG_LUV, false>;
-        case IG_GRAY: return aligned ? k_ingest_u8<IG_GRAY, true> : k_ingest_u8<IG_GRAY, false>;
-        default: return aligned ? k_ingest_u8<IG_PLANAR, true> : k_ingest_u8<IG_PLANAR, false>;
-    }
-}
-
-// (no IG_LUV: a YUV 4:2:0 frame has even H and W, so H * W % 4 == 0 and rgbConvert takes the vector body, rgbConvertMex.cpp:92,343)
-static YuvIngestKernel yuvIngestKernel(int mode, bool aligned)
-{
-    switch (mode)
-    {
-        case IG_LUV_VEC: return aligned ? k_ingest_yuv420<IG_LUV_VEC, true> : k_ingest_yuv420<IG_LUV_VEC, false>;
-        case IG_GRAY: return aligned ? k_ingest_yuv420<IG_GRAY, true> : k_ingest_yuv420<IG_GRAY, false>;
-        default: return aligned ? k_ingest_yuv420<IG_PLANAR, true> : k_ingest_yuv420<IG_PLANAR, false>;
-    }
-}
-
-static bool pixIsYuv(int pix)
-{
-    return pix == ACF_HIP_PIX_NV12 || pix == ACF_HIP_PIX_NV21;
-}
-
-// Where the bytes of a batch of 8-bit frames of rows x cols lie — the ONE place that knows (acf_hip_u8_frame_bytes, the ingest, the
-// input resize, the stream's buffers).  rowStride 0 = tight.  NV12 / NV21: cpp = 1 (the luma plane); chromaOff / frameStride are
-// acf_hip_set_yuv_layout's (0 = tight: chroma behind the luma rows, frames stride * rows * 3 / 2 apart).  The packed layouts have
-// no such freedom: frames are stride * rows apart.  Returns what is wrong, or null.
-struct U8Geom
-{
-    int cpp, stride;
-    int ro, go, bo; // byte offsets of r, g, b inside a packed pixel
-    bool yuv;
-    int64_t chromaOff, frameStride;
-};
-static const char* u8Geom(int pix, int rows, int cols, int rowStride, int64_t chromaOff, int64_t frameStride, U8Geom& g)
-{
-    g = U8Geom{};
-    switch (pix)
-    {
-        case ACF_HIP_PIX_RGB: g.cpp = 3, g.ro = 0, g.go = 1, g.bo = 2; break;
-        case ACF_HIP_PIX_BGR: g.cpp = 3, g.ro = 2, g.go = 1, g.bo = 0; break;
-        case ACF_HIP_PIX_RGBA: g.cpp = 4, g.ro = 0, g.go = 1, g.bo = 2; break;
-        case ACF_HIP_PIX_BGRA: g.cpp = 4, g.ro = 2, g.go = 1, g.bo = 0; break;
-        case ACF_HIP_PIX_GRAY: g.cpp = 1; break;
-        case ACF_HIP_PIX_NV12:
-        case ACF_HIP_PIX_NV21: g.cpp = 1, g.yuv = true; break;
-        default: return "pixel layout";
-    }
-    if (rows < 1 || cols < 1 || rowStride < 0)
-    {
-        return "frame size";
-    }
-    if (int64_t(cols) * g.cpp > INT32_MAX)
-    {
-        return "frame size";
-    }
-    g.stride = rowStride > 0 ? rowStride : cols * g.cpp;
-    if (g.stride < cols * g.cpp)
-    {
-        return "row stride smaller than a row";
-    }
-    const int64_t plane = int64_t(g.stride) * rows;
-    if (!g.yuv)
-    {
-        g.frameStride = plane;
-        return nullptr;
-    }
-    if (rows % 2 || cols % 2)
-    {
-        return "NV12 / NV21 frames have even rows and columns";
-    }
-    g.chromaOff = chromaOff > 0 ? chromaOff : plane;
-    if (g.chromaOff < plane)
-    {
-        return "chroma offset inside the luma plane";
-    }
-    g.frameStride = frameStride > 0 ? frameStride : g.chromaOff + plane / 2;
-    if (g.frameStride < g.chromaOff + plane / 2)
-    {
-        return "frame stride smaller than a frame (frames would overlap)";
-    }
-    return nullptr;
-}
-
-// the plan's input planes against the layout: 1 for GRAY, 3 for the colour layouts — NV12 / NV21 included: the luma plane is limited
-// range, not the grey cvtColor gives, so a 1-plane plan does not take it
-static bool u8PlanesOk(const U8Geom& g, int d_in)
-{
-    return (g.cpp == 1 && !g.yuv) == (d_in == 1);
-}
-
-static YuvSrc yuvSrc(const uint8_t* frames, int pix, int rows, int cols, const U8Geom& g)
-{
-    YuvSrc s{};
-    s.in = frames;
-    s.H = rows;
-    s.W = cols;
-    s.rowStride = g.stride;
-    s.vFirst = pix == ACF_HIP_PIX_NV21;
-    s.chromaOff = g.chromaOff;
-    s.in_fs = g.frameStride;
-    return s;
-}
-
-// k_yuv420_to_rgb8 over a batch: NV12 / NV21 frames of rows x cols -> tight RGB frames at dst
-static int launchYuvToRgb(acf_hip_ctx* c, const YuvSrc& s, int nF, uint8_t* dst)
-{
-    prof(c, c->stream, "k_yuv420_to_rgb8");
-    hipLaunchKernelGGL(k_yuv420_to_rgb8, dim3(cdiv(s.W / 2, 64), cdiv(s.H / 2, 4), nF), dim3(256), 0, c->stream, s, dst);
-    LAUNCHCHK(c, "k_yuv420_to_rgb8");
-    return ACF_HIP_OK;
-}
-
-// What every ingest kernel is told, whatever it reads: the destination planes, the constants of the model's colour conversion and
-// the conversion itself (the return value: IG_*).  convert: to the converted colour planes; else planar, the input's own planes.
-static int ingestShared(acf_hip_ctx* c, float* dst, int64_t out_fs, bool convert, IngestArgs& a)
-{
-    const acf_hip_params& p = c->p;
-    const Plan& pl = c->plan;
-    a.out = dst;
-    a.lTable = c->d_lTable;
-    a.k = makeLuvConsts();
-    a.x86 = x86T(c);
-    a.mr = kGray.r;
-    a.mg = kGray.g;
-    a.mb = kGray.b;
-    a.H = pl.H;
-    a.W = pl.W;
-    a.out_fs = out_fs;
-    a.vecStore = (pl.H % 4 == 0) && (out_fs % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0);
-    const int64_t np0 = int64_t(pl.H) * pl.W;
-    int mode = IG_PLANAR;
-    a.nOut = pl.d_in;
-    if (convert)
-    {
-        if (p.colorSpace == ACF_HIP_CS_LUV)
-        {
-            mode = (np0 % 4 == 0) ? IG_LUV_VEC : IG_LUV; // rgbConvertMex.cpp:92,343
-        }
-        else if (p.colorSpace == ACF_HIP_CS_GRAY)
-        {
-            mode = IG_GRAY; // a 1-plane input is replicated first (chnsPyramid.cpp:234-244): r == g == b
-        }
-        else
-        {
-            a.nOut = 3; // ORIG / RGB with a 1-plane input: replicate (chnsPyramid.cpp:242-243)
-        }
-    }
-    return mode;
-}
-
-int launchIngest(acf_hip_ctx* c, const PackedSrc& u, int nF, float* dst, int64_t out_fs, bool convert)
-{
-    const Plan& pl = c->plan;
-    U8Geom g;
-    if (const char* bad = u8Geom(u.pix, pl.H, pl.W, u.rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_u8: ") + bad);
-    }
-    if (!u8PlanesOk(g, pl.d_in))
-    {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY");
-    }
-    IngestArgs a{};
-    const int mode = ingestShared(c, dst, out_fs, convert, a);
-    a.in = u.frames;
-    a.cpp = g.cpp;
-    a.ro = g.ro;
-    a.go = g.go;
-    a.bo = g.bo;
-    a.rowStride = g.stride;
-    a.in_fs = g.frameStride;
-    bool aligned = (reinterpret_cast<uintptr_t>(u.frames) % 4 == 0) && (a.rowStride % 4 == 0);
-    const dim3 grid(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF);
-    if (g.yuv)
-    {
-        aligned = aligned && g.chromaOff % 4 == 0 && g.frameStride % 4 == 0;
-        hipLaunchKernelGGL(yuvIngestKernel(mode, aligned), grid, dim3(256), 0, c->stream, a, yuvSrc(u.frames, u.pix, pl.H, pl.W, g));
-        LAUNCHCHK(c, "k_ingest_yuv420");
-        return ACF_HIP_OK;
-    }
-    hipLaunchKernelGGL(ingestKernel(mode, aligned), grid, dim3(256), 0, c->stream, a);
-    LAUNCHCHK(c, "k_ingest_u8");
-    return ACF_HIP_OK;
-}
-
-// What is wrong with an image description by itself (acf_hip_image_extent and the image entries), or null
-static const char* imageDescBad(const acf_hip_image_desc* d)
-{
-    if (!d)
-    {
-        return "null description";
-    }
-    if (d->dtype < ACF_HIP_T_U8 || d->dtype > ACF_HIP_T_F32)
-    {
-        return "unknown dtype";
-    }
-    if (d->channels != 1 && d->channels != 3)
-    {
-        return "channels must be 1 or 3";
-    }
-    if (d->stride_x < 1 || d->stride_y < 1)
-    {
-        return "stride_x and stride_y must be positive";
-    }
-    if (d->stride_n < 0)
-    {
-        return "negative stride_n";
-    }
-    return nullptr;
-}
-
-static int imageElemBytes(int dtype)
-{
-    return dtype == ACF_HIP_T_U8 ? 1 : (dtype == ACF_HIP_T_F32 ? 4 : 2);
-}
-
-// The load form of k_ingest_image for a description and a pointer: the vector forms where their conditions hold (kernels_input.hip.h),
-// else the element-wise one, which is right for every description.
-static int imageLoadForm(const ImageSrc& im)
-{
-    const acf_hip_image_desc& d = im.d;
-    const uintptr_t at = reinterpret_cast<uintptr_t>(im.frames);
-    const int es = imageElemBytes(d.dtype);
-    if (at % es)
-    {
-        return IM_GENERIC;
-    }
-    if (d.stride_x == 1 && at % (4 * es) == 0 && d.stride_n % 4 == 0 && d.stride_y % 4 == 0 && (d.channels == 1 || d.stride_c % 4 == 0))
-    {
-        return IM_ROWVEC;
-    }
-    if (d.channels == 3 && (d.stride_c == 1 || d.stride_c == -1) && (d.stride_x == 3 || d.stride_x == 4))
-    {
-        return IM_PACKED;
-    }
-    return IM_GENERIC;
-}
-
-// k_ingest_image over a batch: the image entry's frames -> planar f32 at dst, converted (to c->d_color) or as they are (to c->d_stage)
-int launchIngestImage(acf_hip_ctx* c, const ImageSrc& im, int nF, float* dst, int64_t out_fs, bool convert)
-{
-    const Plan& pl = c->plan;
-    IngestArgs a{};
-    const int mode = ingestShared(c, dst, out_fs, convert, a);
-    ImageArgs s{};
-    s.in = im.frames;
-    s.sn = im.d.stride_n;
-    s.sc = im.d.stride_c;
-    s.sy = im.d.stride_y;
-    s.sx = im.d.stride_x;
-    s.nIn = im.d.channels;
-    s.form = imageLoadForm(im);
-    hipLaunchKernelGGL(imageKernel(im.d.dtype, mode), dim3(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF), dim3(256), 0, c->stream, a, s);
-    LAUNCHCHK(c, "k_ingest_image");
-    return ACF_HIP_OK;
-}
-
-// What is wrong with a YUV description by itself (acf_hip_yuv_extent, the YUV entries), or null
-static const char* yuvDescBad(const acf_hip_yuv_desc* d)
-{
-    if (!d)
-    {
-        return "null description";
-    }
-    if (d->sub_x < 0 || d->sub_x > 1 || d->sub_y < 0 || d->sub_y > 1)
-    {
-        return "sub_x and sub_y must be 0 or 1";
-    }
-    for (const acf_hip_yuv_plane* p : { &d->y, &d->u, &d->v })
-    {
-        if (p->stride_px < 1 || p->stride_row < 1)
-        {
-            return "stride_px and stride_row must be positive";
-        }
-        if (p->stride_n < 0)
-        {
-            return "negative stride_n";
-        }
-    }
-    return nullptr;
-}
-
-// first / last byte offset plane by plane (Y, U, V) that nF frames of h x w address
-static void yuvExtent(const acf_hip_yuv_desc& d, int h, int w, int nF, int64_t first[3], int64_t last[3])
-{
-    const acf_hip_yuv_plane* pl[3] = { &d.y, &d.u, &d.v };
-    for (int i = 0; i < 3; i++)
-    {
-        const int rows = i ? (h + d.sub_y) >> d.sub_y : h, cols = i ? (w + d.sub_x) >> d.sub_x : w;
-        first[i] = pl[i]->offset; // (no stride is negative)
-        last[i] = pl[i]->offset + int64_t(nF - 1) * pl[i]->stride_n + int64_t(rows - 1) * pl[i]->stride_row + int64_t(cols - 1) * pl[i]->stride_px;
-    }
-}
-
-static YuvDescSrc yuvDescSrc(const YuvFrames& f)
-{
-    YuvDescSrc s{};
-    s.base = f.base;
-    s.y = YuvPlane{ f.d.y.offset, f.d.y.stride_n, f.d.y.stride_row, f.d.y.stride_px };
-    s.u = YuvPlane{ f.d.u.offset, f.d.u.stride_n, f.d.u.stride_row, f.d.u.stride_px };
-    s.v = YuvPlane{ f.d.v.offset, f.d.v.stride_n, f.d.v.stride_row, f.d.v.stride_px };
-    s.subX = f.d.sub_x;
-    s.subY = f.d.sub_y;
-    return s;
-}
-
-// The load form of k_ingest_yuv for a description and a pointer: the vector forms where their conditions hold (kernels_input.hip.h),
-// else the byte form, which is right for every description.  YD_PACKED422 also fills in the macropixel's byte order.
-static int yuvLoadForm(YuvDescSrc& s)
-{
-    const uintptr_t at = reinterpret_cast<uintptr_t>(s.base);
-    const auto aligned = [&](const YuvPlane& p) { return (at + uintptr_t(p.off)) % 4 == 0 && p.sr % 4 == 0 && p.sn % 4 == 0; };
-    if (s.y.sp == 1 && s.u.sp == 1 && s.v.sp == 1 && aligned(s.y) && aligned(s.u) && aligned(s.v))
-    {
-        return YD_PLANAR;
-    }
-    if (s.subX == 1 && s.subY == 0 && s.y.sp == 2 && s.u.sp == 4 && s.v.sp == 4 && s.y.sr == s.u.sr && s.y.sr == s.v.sr && s.y.sn == s.u.sn &&
-        s.y.sn == s.v.sn)
-    {
-        const int64_t mp = std::min(s.y.off, std::min(s.u.off, s.v.off));
-        const int64_t yp = s.y.off - mp, up = s.u.off - mp, vp = s.v.off - mp;
-        // Y0, Y1, U, V take the four bytes of one aligned macropixel
-        if (yp <= 1 && up <= 3 && vp <= 3 && ((1 << yp) | (1 << (yp + 2)) | (1 << up) | (1 << vp)) == 15 && (at + uintptr_t(mp)) % 4 == 0 && s.y.sr % 4 == 0 &&
-            s.y.sn % 4 == 0)
-        {
-            s.mp = mp;
-            s.yPos = int(yp);
-            s.uPos = int(up);
-            s.vPos = int(vp);
-            return YD_PACKED422;
-        }
-    }
-    return YD_GENERIC;
-}
-
-// A description of an NV12 / NV21 frame as the 8-bit entry takes it (one row stride, interleaved chroma pairs, even sizes): the
-// YuvSrc of k_ingest_yuv420, which then runs it — the same kernel, so the same bits as acf_hip_run_u8(ACF_HIP_PIX_NV12 / _NV21)
-static bool yuvIsSemiPlanar(const YuvFrames& f, int H, int W, YuvSrc& out)
-{
-    const acf_hip_yuv_desc& d = f.d;
-    const int64_t c0 = std::min(d.u.offset, d.v.offset);
-    if (!(d.sub_x == 1 && d.sub_y == 1 && H % 2 == 0 && W % 2 == 0 && d.y.stride_px == 1 && d.u.stride_px == 2 && d.v.stride_px == 2 &&
-            std::max(d.u.offset, d.v.offset) == c0 + 1 && d.u.stride_row == d.y.stride_row && d.v.stride_row == d.y.stride_row && d.y.stride_row <= INT32_MAX &&
-            d.u.stride_n == d.y.stride_n && d.v.stride_n == d.y.stride_n))
-    {
-        return false;
-    }
-    out = YuvSrc{};
-    out.in = f.base + d.y.offset;
-    out.H = H;
-    out.W = W;
-    out.rowStride = int(d.y.stride_row);
-    out.vFirst = d.v.offset < d.u.offset;
-    out.chromaOff = c0 - d.y.offset;
-    out.in_fs = d.y.stride_n;
-    return true;
-}
-
-// The profile name of the kernel a YUV description runs with this base pointer (static strings: prof keeps the pointer)
-static const char* yuvKernelName(const YuvFrames& f, int H, int W)
-{
-    static const char* const names[3] = { "k_ingest_yuv_generic", "k_ingest_yuv_planar", "k_ingest_yuv_packed422" };
-    YuvSrc semi;
-    if (yuvIsSemiPlanar(f, H, W, semi))
-    {
-        return "k_ingest_yuv420";
-    }
-    YuvDescSrc s = yuvDescSrc(f);
-    return names[yuvLoadForm(s)];
-}
-
-// k_ingest_yuv (k_ingest_yuv420 for an NV12 / NV21-shaped description) over a batch: the YUV entry's frames -> planar f32 at dst
-int launchIngestYuv(acf_hip_ctx* c, const YuvFrames& f, int nF, float* dst, int64_t out_fs, bool convert)
-{
-    const Plan& pl = c->plan;
-    IngestArgs a{};
-    const int mode = ingestShared(c, dst, out_fs, convert, a);
-    const dim3 grid(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF);
-    YuvSrc semi;
-    if (yuvIsSemiPlanar(f, pl.H, pl.W, semi))
-    {
-        const bool aligned = reinterpret_cast<uintptr_t>(semi.in) % 4 == 0 && semi.rowStride % 4 == 0 && semi.chromaOff % 4 == 0 && semi.in_fs % 4 == 0;
-        hipLaunchKernelGGL(yuvIngestKernel(mode, aligned), grid, dim3(256), 0, c->stream, a, semi); // (even sizes: never IG_LUV)
-        LAUNCHCHK(c, "k_ingest_yuv420");
-        return ACF_HIP_OK;
-    }
-    YuvDescSrc s = yuvDescSrc(f);
-    const int form = yuvLoadForm(s);
-    hipLaunchKernelGGL(yuvDescKernel(form, mode), grid, dim3(256), 0, c->stream, a, s);
-    LAUNCHCHK(c, "k_ingest_yuv");
-    return ACF_HIP_OK;
-}
-
-// rgbConvert of nF frames of n pixels: `in` holds nIn planes a frame (frame stride in_fs), `out` the converted planes (out_fs).  LUV takes
-// the vector body iff n % 4 == 0 (rgbConvertMex.cpp:92,343); a 1-plane input is replicated first (chnsPyramid.cpp:234-244): gray from
-// it is k_rgb2gray<true>, ORIG / RGB k_replicate3.  The caller checks the launch.
-static void launchColour(acf_hip_ctx* c, const float* in, float* out, int64_t n, int nF, int64_t in_fs, int64_t out_fs, int colorSpace, int nIn)
-{
-    const dim3 grid(cdiv(n, 256), 1, nF), block(256);
-    if (colorSpace == ACF_HIP_CS_LUV)
-    {
-        hipLaunchKernelGGL((n % 4 == 0 ? k_rgb2luv<true> : k_rgb2luv<false>), grid, block, 0, c->stream, in, out, (const float*)c->d_lTable, makeLuvConsts(),
-            int(n), in_fs, out_fs, x86T(c));
-    }
-    else if (colorSpace == ACF_HIP_CS_GRAY)
-    {
-        hipLaunchKernelGGL((nIn == 1 ? k_rgb2gray<true> : k_rgb2gray<false>), grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs, kGray.r, kGray.g,
-            kGray.b);
-    }
-    else if (colorSpace == ACF_HIP_CS_HSV)
-    {
-        hipLaunchKernelGGL(k_rgb2hsv, grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs);
-    }
-    else
-    {
-        hipLaunchKernelGGL(k_replicate3, grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs);
-    }
-}
-
-// what rz_pixel reads besides the source: the tables on the device and the source size
-static ResizeTaps resizeTaps(const acf_hip_ctx::InputResize& rz)
-{
-    ResizeTaps t{};
-    t.rows = rz.t.rows;
-    t.cols = rz.t.cols;
-    t.mode = rz.t.mode;
-    t.isx = rz.t.isx;
-    t.isy = rz.t.isy;
-    t.xlin = reinterpret_cast<const int4*>(rz.d_xlin);
-    t.ylin = reinterpret_cast<const int4*>(rz.d_ylin);
-    t.xrun = reinterpret_cast<const int2*>(rz.d_xrun);
-    t.yrun = reinterpret_cast<const int2*>(rz.d_yrun);
-    t.xtap = reinterpret_cast<const int2*>(rz.d_xtap);
-    t.ytap = reinterpret_cast<const int2*>(rz.d_ytap);
-    return t;
-}
-
-// k_resize_u8 over a batch: `src` frames of t.rows x t.cols (row stride `stride` bytes) -> tight t.drows x t.dcols frames at dst
-static int launchResizeU8(acf_hip_ctx* c, const acf_hip_ctx::InputResize& rz, const uint8_t* src, int cpp, int stride, int nF, uint8_t* dst)
-{
-    const ResizeTables& t = rz.t;
-    ResizeArgs a{};
-    a.src = src;
-    a.dst = dst;
-    a.cn = cpp;
-    a.stride = stride;
-    a.drows = t.drows;
-    a.dcols = t.dcols;
-    a.src_fs = int64_t(stride) * t.rows;
-    a.dst_fs = int64_t(t.drows) * t.dcols * cpp;
-    a.t = resizeTaps(rz);
-    prof(c, c->stream, "k_resize_u8");
-    hipLaunchKernelGGL(k_resize_u8, dim3(cdiv(t.dcols, 64), cdiv(t.drows, 4), nF), dim3(256), 0, c->stream, a);
-    LAUNCHCHK(c, "k_resize_u8");
-    return ACF_HIP_OK;
-}
-
-static int uploadResizeTables(acf_hip_ctx* c, acf_hip_ctx::InputResize& rz)
-{
-    int rc;
-    if ((rc = devUpload(c, &rz.d_xlin, rz.t.xlin)) || (rc = devUpload(c, &rz.d_ylin, rz.t.ylin)) || (rc = devUpload(c, &rz.d_xrun, rz.t.xrun)) ||
-        (rc = devUpload(c, &rz.d_yrun, rz.t.yrun)) || (rc = devUpload(c, &rz.d_xtap, rz.t.xtap)) || (rc = devUpload(c, &rz.d_ytap, rz.t.ytap)))
-    {
-        return rc;
-    }
-    return ACF_HIP_OK;
-}
-
-static void releaseResize(acf_hip_ctx* c, acf_hip_ctx::InputResize& r)
-{
-    devRelease(c, r.d_xlin);
-    devRelease(c, r.d_ylin);
-    devRelease(c, r.d_xrun);
-    devRelease(c, r.d_yrun);
-    devRelease(c, r.d_xtap);
-    devRelease(c, r.d_ytap);
-    devRelease(c, r.d_out);
-}
-
-// What the resized entries refuse about (src_rows, src_cols, scale) and the plan, then their tap tables on the device: those of the
-// context's key (rows, cols, scale) as they are, else built and uploaded (the stream is synchronised before the old ones go)
-static int resizedTables(acf_hip_ctx* c, const char* who, int srcRows, int srcCols, double scale)
-{
-    if (srcRows < 1 || srcCols < 1 || !(scale > 0) || !std::isfinite(scale))
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": src_rows and src_cols >= 1, scale a positive finite number");
-    }
-    if (c->rz.on)
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": not with acf_hip_set_input_resize (the entry resizes by itself)");
-    }
-    acf_hip_ctx::InputResize& cur = c->rzIn;
-    if (cur.on && cur.rows == srcRows && cur.cols == srcCols && cur.scale == scale)
-    {
-        return ACF_HIP_OK; // (built against this plan: acf_hip_plan drops them)
-    }
-    acf_hip_ctx::InputResize rz;
-    if (buildResizeTables(srcRows, srcCols, scale, rz.t) || rz.t.drows != c->plan.H || rz.t.dcols != c->plan.W)
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": the plan must be for the reduced size (acf_hip_resize_dims of the frame size and scale)");
-    }
-    rz.rows = srcRows;
-    rz.cols = srcCols;
-    rz.scale = scale;
-    if (int rc = uploadResizeTables(c, rz))
-    {
-        releaseResize(c, rz); // (what was uploaded before the failure)
-        return rc;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream)); // the previous key's tables: a batch in flight may still read them
-    releaseResize(c, cur);
-    rz.on = true;
-    cur = rz;
-    return ACF_HIP_OK;
-}
-
-// k_ingest_resized over a batch: the resized entries' frames (an image's strides or a YUV description, at the source size) -> planar
-// f32 at the plan's size at dst
-int launchIngestResized(acf_hip_ctx* c, const ImageSrc* im, const YuvFrames* yf, int nF, float* dst, int64_t out_fs, bool convert)
-{
-    const Plan& pl = c->plan;
-    IngestArgs a{};
-    const int mode = ingestShared(c, dst, out_fs, convert, a);
-    ResizedSrc s{};
-    s.t = resizeTaps(c->rzIn);
-    if (im)
-    {
-        s.im.in = im->frames;
-        s.im.sn = im->d.stride_n;
-        s.im.sc = im->d.stride_c;
-        s.im.sy = im->d.stride_y;
-        s.im.sx = im->d.stride_x;
-        s.im.nIn = im->d.channels;
-    }
-    else
-    {
-        s.yuv = yuvDescSrc(*yf);
-    }
-    hipLaunchKernelGGL(resizedKernel(im ? RS_IMAGE : RS_YUV, mode), dim3(cdiv(pl.W, IG_T), cdiv(pl.H, IG_T), nF), dim3(256), 0, c->stream, a, s);
-    LAUNCHCHK(c, "k_ingest_resized");
-    return ACF_HIP_OK;
-}
-
 // A call that fails between a verify launch and its repair launch (a launch error, the count_repairs read-back) would leave
 // repair flags set for the next call — harmless for results (a flagged plane is recomputed as one chain), but counted by
 // count_repairs and paid for.  Every failing pyramid call therefore takes the flags down again.
@@ -2528,292 +1931,26 @@ static void clearRepairFlags(acf_hip_ctx* c)
 
 } // namespace
 
+#include "input_run.hip.h"   // u8Geom and the description checks, planIngest (IngestPlan), launchColour, the resize tables, the input entries
+
 #include "pyramid_run.hip.h" // PyramidRun (acf_hip_pyramid's stages), pyramidBody
 
-static int pyramidImpl(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF, const ImageSrc* img = nullptr, const YuvFrames* yuv = nullptr)
+namespace
 {
-    const int rc = pyramidBody(c, frames, u8, nF, img, yuv);
+int pyramidImpl(acf_hip_ctx* c, const FrameSource& src, int nF)
+{
+    const int rc = pyramidBody(c, src, nF);
     if (rc && c && c->hasPlan && c->kids.empty())
     {
         clearRepairFlags(c);
     }
     return rc;
 }
+} // namespace
 
 int acf_hip_pyramid(acf_hip_ctx* c, const float* frames, int nF)
 {
-    return pyramidImpl(c, frames, nullptr, nF);
-}
-
-int acf_hip_pyramid_u8(acf_hip_ctx* c, const uint8_t* frames, int nF, int pix, int rowStride)
-{
-    if (int rc = needCtx(c)) return rc;
-    PackedSrc u{ frames, pix, rowStride };
-    return pyramidImpl(c, nullptr, &u, nF);
-}
-
-int acf_hip_pyramid_image(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc)
-{
-    if (int rc = needCtx(c)) return rc;
-    if (!frames || !desc)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_image: null frames or description");
-    }
-    ImageSrc im{ frames, *desc };
-    return pyramidImpl(c, nullptr, nullptr, nF, &im);
-}
-
-int acf_hip_run_image(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc)
-{
-    int rc = acf_hip_pyramid_image(c, frames, nF, desc);
-    if (rc)
-    {
-        return rc;
-    }
-    return acf_hip_detect(c);
-}
-
-int acf_hip_image_extent(const acf_hip_image_desc* d, int h, int w, int nF, int64_t* first, int64_t* last)
-{
-    if (!first || !last || imageDescBad(d) || h < 1 || w < 1 || nF < 1)
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    int64_t lo = 0, hi = 0;
-    const int64_t span[4] = { (nF - 1) * d->stride_n, (d->channels - 1) * d->stride_c, (h - 1) * d->stride_y, (w - 1) * d->stride_x };
-    for (int64_t v : span)
-    {
-        (v < 0 ? lo : hi) += v;
-    }
-    *first = lo;
-    *last = hi;
-    return ACF_HIP_OK;
-}
-
-int acf_hip_pyramid_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
-{
-    if (int rc = needCtx(c)) return rc;
-    if (!base || !desc)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv: null base or description");
-    }
-    YuvFrames f{ base, *desc };
-    return pyramidImpl(c, nullptr, nullptr, nF, nullptr, &f);
-}
-
-int acf_hip_run_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
-{
-    int rc = acf_hip_pyramid_yuv(c, base, nF, desc);
-    if (rc)
-    {
-        return rc;
-    }
-    return acf_hip_detect(c);
-}
-
-int acf_hip_pyramid_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
-{
-    if (int rc = needCtx(c)) return rc;
-    if (!base || !desc)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv_resized: null base or description");
-    }
-    YuvFrames f{ base, *desc, true, srcRows, srcCols, scale };
-    return pyramidImpl(c, nullptr, nullptr, nF, nullptr, &f);
-}
-
-int acf_hip_run_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
-{
-    int rc = acf_hip_pyramid_yuv_resized(c, base, nF, desc, srcRows, srcCols, scale);
-    if (rc)
-    {
-        return rc;
-    }
-    return acf_hip_detect(c);
-}
-
-int acf_hip_pyramid_image_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, double scale)
-{
-    if (int rc = needCtx(c)) return rc;
-    if (!frames || !desc)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_image_resized: null frames or description");
-    }
-    ImageSrc im{ frames, *desc, true, srcRows, srcCols, scale };
-    return pyramidImpl(c, nullptr, nullptr, nF, &im);
-}
-
-int acf_hip_run_image_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, double scale)
-{
-    int rc = acf_hip_pyramid_image_resized(c, frames, nF, desc, srcRows, srcCols, scale);
-    if (rc)
-    {
-        return rc;
-    }
-    return acf_hip_detect(c);
-}
-
-int acf_hip_yuv_to_rgb8(acf_hip_ctx* c, const uint8_t* base, int nF, int rows, int cols, const acf_hip_yuv_desc* desc, uint8_t* dst)
-{
-    if (int rc = needCtx(c)) return rc;
-    if (!base || !desc || !dst)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "yuv_to_rgb8: null base, description or destination");
-    }
-    if (const char* bad = yuvDescBad(desc))
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string("yuv_to_rgb8: ") + bad);
-    }
-    if (nF < 1 || nF > 65535 || rows < 1 || cols < 1)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "yuv_to_rgb8: n_frames 1 .. 65535, rows and cols >= 1");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    prof(c, c->stream, "k_yuv_to_rgb8");
-    hipLaunchKernelGGL(k_yuv_to_rgb8, dim3(cdiv(cols, 64), cdiv(rows, 4), nF), dim3(256), 0, c->stream, yuvDescSrc(YuvFrames{ base, *desc }), rows, cols, dst);
-    LAUNCHCHK(c, "k_yuv_to_rgb8");
-    return ACF_HIP_OK;
-}
-
-int acf_hip_yuv_extent(const acf_hip_yuv_desc* d, int h, int w, int nF, int64_t* first, int64_t* last)
-{
-    if (!first || !last || yuvDescBad(d) || h < 1 || w < 1 || nF < 1)
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    yuvExtent(*d, h, w, nF, first, last);
-    return ACF_HIP_OK;
-}
-
-int acf_hip_yuv_layout(int layout, int h, int w, int rowStride, acf_hip_yuv_desc* out, int64_t* frameBytes)
-{
-    if (!out || !frameBytes || h < 1 || w < 1 || rowStride < 0 || layout < ACF_HIP_YUV_NV12 || layout > ACF_HIP_YUV_YVYU)
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    const bool packed = layout >= ACF_HIP_YUV_YUYV, semi = layout <= ACF_HIP_YUV_NV21;
-    const int subX = layout == ACF_HIP_YUV_I444 ? 0 : 1, subY = (semi || layout == ACF_HIP_YUV_I420 || layout == ACF_HIP_YUV_YV12) ? 1 : 0;
-    const int64_t rowBytes = packed ? 2 * int64_t(w) : w;
-    const int64_t stride = rowStride > 0 ? rowStride : rowBytes;
-    if (stride < rowBytes || (subX && w % 2) || (subY && h % 2) || (!packed && !semi && stride % 2))
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    acf_hip_yuv_desc d{};
-    d.sub_x = subX;
-    d.sub_y = subY;
-    int64_t fb;
-    if (packed)
-    {
-        // macropixels of four bytes: Y0 U Y1 V / U Y0 V Y1 / Y0 V Y1 U
-        const int yp = layout == ACF_HIP_YUV_UYVY ? 1 : 0, up = layout == ACF_HIP_YUV_YUYV ? 1 : (layout == ACF_HIP_YUV_UYVY ? 0 : 3),
-                  vp = layout == ACF_HIP_YUV_YUYV ? 3 : (layout == ACF_HIP_YUV_UYVY ? 2 : 1);
-        fb = stride * h;
-        d.y = acf_hip_yuv_plane{ yp, fb, stride, 2 };
-        d.u = acf_hip_yuv_plane{ up, fb, stride, 4 };
-        d.v = acf_hip_yuv_plane{ vp, fb, stride, 4 };
-    }
-    else if (semi)
-    {
-        const int64_t chroma = stride * h; // the tight rule of the 8-bit entry (u8Geom)
-        fb = chroma + stride * (h / 2);
-        const int vFirst = layout == ACF_HIP_YUV_NV21;
-        d.y = acf_hip_yuv_plane{ 0, fb, stride, 1 };
-        d.u = acf_hip_yuv_plane{ chroma + vFirst, fb, stride, 2 };
-        d.v = acf_hip_yuv_plane{ chroma + 1 - vFirst, fb, stride, 2 };
-    }
-    else
-    {
-        const int64_t cs = stride >> subX, plane = cs * (h >> subY), first = stride * h;
-        fb = first + 2 * plane;
-        const bool vFirst = layout == ACF_HIP_YUV_YV12;
-        d.y = acf_hip_yuv_plane{ 0, fb, stride, 1 };
-        d.u = acf_hip_yuv_plane{ first + (vFirst ? plane : 0), fb, cs, 1 };
-        d.v = acf_hip_yuv_plane{ first + (vFirst ? 0 : plane), fb, cs, 1 };
-    }
-    *out = d;
-    *frameBytes = fb;
-    return ACF_HIP_OK;
-}
-
-int acf_hip_u8_frame_bytes(int pix, int rows, int cols, int rowStride, int64_t* out)
-{
-    U8Geom g;
-    if (!out || u8Geom(pix, rows, cols, rowStride, 0, 0, g))
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    *out = g.frameStride;
-    return ACF_HIP_OK;
-}
-
-int acf_hip_set_yuv_layout(acf_hip_ctx* c, int64_t chromaOff, int64_t frameStride)
-{
-    if (int rc = needPlan(c, "set_yuv_layout")) return rc;
-    if (!c->kids.empty() || !c->slots.empty())
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "set_yuv_layout: not with option \"streams\" > 1; before acf_hip_stream_open");
-    }
-    if (chromaOff < 0 || frameStride < 0)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "set_yuv_layout: negative offset or stride");
-    }
-    dropGraph(c);
-    c->yuv.chromaOff = chromaOff; // (held against the frames' row stride where that is known: the run / open call)
-    c->yuv.frameStride = frameStride;
-    return ACF_HIP_OK;
-}
-
-int acf_hip_resize_dims(int rows, int cols, double scale, int* out_rows, int* out_cols)
-{
-    if (!out_rows || !out_cols || rows < 1 || cols < 1 || !(scale > 0))
-    {
-        return ACF_HIP_E_INVALID;
-    }
-    resizeDims(rows, cols, scale, *out_rows, *out_cols);
-    return (*out_rows >= 1 && *out_cols >= 1) ? ACF_HIP_OK : ACF_HIP_E_INVALID;
-}
-
-int acf_hip_set_input_resize(acf_hip_ctx* c, int srcRows, int srcCols, double scale)
-{
-    if (int rc = needPlan(c, "set_input_resize", " (for the reduced size, acf_hip_resize_dims)")) return rc;
-    if (!c->kids.empty() || !c->slots.empty())
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "set_input_resize: not with option \"streams\" > 1; before acf_hip_stream_open");
-    }
-    dropGraph(c);
-    if (srcRows <= 0 || srcCols <= 0)
-    {
-        c->rz.on = false;
-        return ACF_HIP_OK;
-    }
-    if (c->rz.d_out && c->rz.rows == srcRows && c->rz.cols == srcCols && c->rz.scale == scale)
-    {
-        c->rz.on = true; // same geometry as the tables already on the device (a re-opened stream): nothing to build
-        return ACF_HIP_OK;
-    }
-    acf_hip_ctx::InputResize rz;
-    if (buildResizeTables(srcRows, srcCols, scale, rz.t) || rz.t.drows != c->plan.H || rz.t.dcols != c->plan.W)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "set_input_resize: the plan must be for the reduced size (acf_hip_resize_dims of the frame size and scale)");
-    }
-    rz.rows = srcRows;
-    rz.cols = srcCols;
-    rz.scale = scale;
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = uploadResizeTables(c, rz)) || (rc = devAlloc(c, &rz.d_out, size_t(c->maxBatch) * c->plan.H * c->plan.W * 4)))
-    {
-        releaseResize(c, rz); // (what was uploaded before the failure)
-        return rc;
-    }
-    // the previous geometry's tables: a batch in flight may still read them
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->rz.on = false;
-    releaseResize(c, c->rz);
-    rz.on = true;
-    c->rz = rz;
-    return ACF_HIP_OK;
+    return pyramidImpl(c, FrameSource{ SRC_F32, frames }, nF);
 }
 
 #include "cascade_run.hip.h"    // wholeCascadeTiled, planCascadeCall, clearCounters, runCascade, launchNms, runLdcf
@@ -3001,16 +2138,6 @@ int acf_hip_run_host(acf_hip_ctx* c, const float* frames_host, int nF)
     return acf_hip_run(c, c->d_stage, nF);
 }
 
-int acf_hip_run_u8(acf_hip_ctx* c, const uint8_t* frames, int nF, int pix, int rowStride)
-{
-    int rc = acf_hip_pyramid_u8(c, frames, nF, pix, rowStride);
-    if (rc)
-    {
-        return rc;
-    }
-    return acf_hip_detect(c);
-}
-
 // ---------------------------------------------------------------------------
 // streaming front end: copy stream + per-slot events; see include/acf_hip.h
 // ---------------------------------------------------------------------------
@@ -3108,9 +2235,7 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
     {
         return fail(c, ACF_HIP_E_INVALID, "stream_open: the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY");
     }
-    c->stYuv = false;
-    c->stPix = pix;
-    c->stStride = g.stride;
+    c->stSrc = FrameSource{ SRC_U8, nullptr, "pyramid_u8", pix, g.stride };
     return streamSlots(c, g.frameStride, cap, depth);
 }
 
@@ -3154,11 +2279,7 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     {
         return fail(c, ACF_HIP_E_INVALID, w + "stride_n of every plane must be frame_bytes");
     }
-    c->stYuv = true;
-    c->stYuvDesc = *desc;
-    c->stSrcRows = resized ? srcRows : 0;
-    c->stSrcCols = resized ? srcCols : 0;
-    c->stScale = scale;
+    c->stSrc = FrameSource{ SRC_YUV, nullptr, resized ? "pyramid_yuv_resized" : "pyramid_yuv", 0, 0, {}, *desc, resized, srcRows, srcCols, scale };
     return streamSlots(c, frameBytes, cap, depth);
 }
 
@@ -3191,9 +2312,9 @@ int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, in
     HIPCHK(c, hipMemcpyAsync(s.d_in, frames_host, bytes, hipMemcpyHostToDevice, c->copyStream));
     HIPCHK(c, hipEventRecord(s.evH2D, c->copyStream));
     HIPCHK(c, hipStreamWaitEvent(c->stream, s.evH2D, 0));
-    int rc = !c->stYuv        ? acf_hip_run_u8(c, s.d_in, nF, c->stPix, c->stStride)
-        : c->stSrcRows > 0 ? acf_hip_run_yuv_resized(c, s.d_in, nF, &c->stYuvDesc, c->stSrcRows, c->stSrcCols, c->stScale)
-                           : acf_hip_run_yuv(c, s.d_in, nF, &c->stYuvDesc);
+    FrameSource src = c->stSrc;
+    src.base = s.d_in;
+    int rc = runSource(c, src, nF);
     if (rc)
     {
         return rc;

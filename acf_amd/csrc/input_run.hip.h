@@ -1,0 +1,949 @@
+// input_run.hip.h — part of acf_hip.hip (included there and nowhere else): where a call's frames come from.  Every entry that takes frames
+// describes them as ONE FrameSource (acf_hip.hip, beside the context, whose stream keeps the one it was opened with); planIngest checks
+// the source against the plan and decides the call's ingest once (IngestPlan: the preludes, the kernel, its arguments, its names), and
+// PyramidRun::ingest (pyramid_run.hip.h) launches that plan straight-line.  A new kind of input is one more SourceKind.
+//
+//   u8Geom, imageDescBad, yuvDescBad, yuvExtent      what a layout or a description is, by itself
+//   the kernel tables and form choosers              ingestKernel .. resizedKernel, imageLoadForm, yuvLoadForm, yuvIsSemiPlanar
+//   launchYuvToRgb, launchResizeU8, launchColour     the preludes and the colour conversion (ops.hip.h and crops_run.hip.h call them too)
+//   installResizeTables, resizedTables               the tap tables of acf_hip_set_input_resize (c->rz) and of the resized entries (c->rzIn)
+//   planIngest                                       FrameSource -> IngestPlan, or the refusal
+//   the entries that are only about input            acf_hip_pyramid_u8 / _image / _yuv / *_resized and their run_ twins, the extents
+//                                                    and layouts, acf_hip_set_yuv_layout, acf_hip_set_input_resize, acf_hip_yuv_to_rgb8
+#pragma once
+
+namespace
+{
+int pyramidImpl(acf_hip_ctx* c, const FrameSource& src, int nF); // (acf_hip.hip, behind pyramid_run.hip.h)
+
+using IngestKernel = void (*)(IngestArgs);
+using YuvIngestKernel = void (*)(IngestArgs, YuvSrc);
+using ImageKernel = void (*)(IngestArgs, ImageArgs);
+using YuvDescKernel = void (*)(IngestArgs, YuvDescSrc);
+using ResizedKernel = void (*)(IngestArgs, ResizedSrc);
+
+static IngestKernel ingestKernel(int mode, bool aligned)
+{
+    switch (mode)
+    {
+        case IG_LUV_VEC: return aligned ? k_ingest_u8<IG_LUV_VEC, true> : k_ingest_u8<IG_LUV_VEC, false>;
+        case IG_LUV: return aligned ? k_ingest_u8<IG_LUV, true> : k_ingest_u8<IG_LUV, false>;
+        case IG_GRAY: return aligned ? k_ingest_u8<IG_GRAY, true> : k_ingest_u8<IG_GRAY, false>;
+        default: return aligned ? k_ingest_u8<IG_PLANAR, true> : k_ingest_u8<IG_PLANAR, false>;
+    }
+}
+
+// (no IG_LUV: a YUV 4:2:0 frame has even H and W, so H * W % 4 == 0 and rgbConvert takes the vector body, rgbConvertMex.cpp:92,343)
+static YuvIngestKernel yuvIngestKernel(int mode, bool aligned)
+{
+    switch (mode)
+    {
+        case IG_LUV_VEC: return aligned ? k_ingest_yuv420<IG_LUV_VEC, true> : k_ingest_yuv420<IG_LUV_VEC, false>;
+        case IG_GRAY: return aligned ? k_ingest_yuv420<IG_GRAY, true> : k_ingest_yuv420<IG_GRAY, false>;
+        default: return aligned ? k_ingest_yuv420<IG_PLANAR, true> : k_ingest_yuv420<IG_PLANAR, false>;
+    }
+}
+
+// k_ingest_image<element type, conversion>: [ACF_HIP_T_*][IG_*]
+static ImageKernel imageKernel(int dtype, int mode)
+{
+    static const ImageKernel table[4][4] = {
+        { k_ingest_image<IM_U8, IG_PLANAR>, k_ingest_image<IM_U8, IG_LUV_VEC>, k_ingest_image<IM_U8, IG_LUV>, k_ingest_image<IM_U8, IG_GRAY> },
+        { k_ingest_image<IM_F16, IG_PLANAR>, k_ingest_image<IM_F16, IG_LUV_VEC>, k_ingest_image<IM_F16, IG_LUV>, k_ingest_image<IM_F16, IG_GRAY> },
+        { k_ingest_image<IM_BF16, IG_PLANAR>, k_ingest_image<IM_BF16, IG_LUV_VEC>, k_ingest_image<IM_BF16, IG_LUV>, k_ingest_image<IM_BF16, IG_GRAY> },
+        { k_ingest_image<IM_F32, IG_PLANAR>, k_ingest_image<IM_F32, IG_LUV_VEC>, k_ingest_image<IM_F32, IG_LUV>, k_ingest_image<IM_F32, IG_GRAY> },
+    };
+    return table[dtype][mode];
+}
+
+// k_ingest_yuv<conversion, load form>: [YD_*][IG_*]
+static YuvDescKernel yuvDescKernel(int form, int mode)
+{
+    static const YuvDescKernel table[3][4] = {
+        { k_ingest_yuv<IG_PLANAR, YD_GENERIC>, k_ingest_yuv<IG_LUV_VEC, YD_GENERIC>, k_ingest_yuv<IG_LUV, YD_GENERIC>, k_ingest_yuv<IG_GRAY, YD_GENERIC> },
+        { k_ingest_yuv<IG_PLANAR, YD_PLANAR>, k_ingest_yuv<IG_LUV_VEC, YD_PLANAR>, k_ingest_yuv<IG_LUV, YD_PLANAR>, k_ingest_yuv<IG_GRAY, YD_PLANAR> },
+        { k_ingest_yuv<IG_PLANAR, YD_PACKED422>, k_ingest_yuv<IG_LUV_VEC, YD_PACKED422>, k_ingest_yuv<IG_LUV, YD_PACKED422>, k_ingest_yuv<IG_GRAY, YD_PACKED422> },
+    };
+    return table[form][mode];
+}
+
+// k_ingest_resized<source, conversion>: [RS_*][IG_*]
+static ResizedKernel resizedKernel(int src, int mode)
+{
+    static const ResizedKernel table[2][4] = {
+        { k_ingest_resized<RS_IMAGE, IG_PLANAR>, k_ingest_resized<RS_IMAGE, IG_LUV_VEC>, k_ingest_resized<RS_IMAGE, IG_LUV>, k_ingest_resized<RS_IMAGE, IG_GRAY> },
+        { k_ingest_resized<RS_YUV, IG_PLANAR>, k_ingest_resized<RS_YUV, IG_LUV_VEC>, k_ingest_resized<RS_YUV, IG_LUV>, k_ingest_resized<RS_YUV, IG_GRAY> },
+    };
+    return table[src][mode];
+}
+
+static bool pixIsYuv(int pix)
+{
+    return pix == ACF_HIP_PIX_NV12 || pix == ACF_HIP_PIX_NV21;
+}
+
+// Where the bytes of a batch of 8-bit frames of rows x cols lie — the ONE place that knows (acf_hip_u8_frame_bytes, the ingest, the
+// input resize, the stream's buffers).  rowStride 0 = tight.  NV12 / NV21: cpp = 1 (the luma plane); chromaOff / frameStride are
+// acf_hip_set_yuv_layout's (0 = tight: chroma behind the luma rows, frames stride * rows * 3 / 2 apart).  The packed layouts have
+// no such freedom: frames are stride * rows apart.  Returns what is wrong, or null.
+struct U8Geom
+{
+    int cpp, stride;
+    int ro, go, bo; // byte offsets of r, g, b inside a packed pixel
+    bool yuv;
+    int64_t chromaOff, frameStride;
+};
+static const char* u8Geom(int pix, int rows, int cols, int rowStride, int64_t chromaOff, int64_t frameStride, U8Geom& g)
+{
+    g = U8Geom{};
+    switch (pix)
+    {
+        case ACF_HIP_PIX_RGB: g.cpp = 3, g.ro = 0, g.go = 1, g.bo = 2; break;
+        case ACF_HIP_PIX_BGR: g.cpp = 3, g.ro = 2, g.go = 1, g.bo = 0; break;
+        case ACF_HIP_PIX_RGBA: g.cpp = 4, g.ro = 0, g.go = 1, g.bo = 2; break;
+        case ACF_HIP_PIX_BGRA: g.cpp = 4, g.ro = 2, g.go = 1, g.bo = 0; break;
+        case ACF_HIP_PIX_GRAY: g.cpp = 1; break;
+        case ACF_HIP_PIX_NV12:
+        case ACF_HIP_PIX_NV21: g.cpp = 1, g.yuv = true; break;
+        default: return "pixel layout";
+    }
+    if (rows < 1 || cols < 1 || rowStride < 0)
+    {
+        return "frame size";
+    }
+    if (int64_t(cols) * g.cpp > INT32_MAX)
+    {
+        return "frame size";
+    }
+    g.stride = rowStride > 0 ? rowStride : cols * g.cpp;
+    if (g.stride < cols * g.cpp)
+    {
+        return "row stride smaller than a row";
+    }
+    const int64_t plane = int64_t(g.stride) * rows;
+    if (!g.yuv)
+    {
+        g.frameStride = plane;
+        return nullptr;
+    }
+    if (rows % 2 || cols % 2)
+    {
+        return "NV12 / NV21 frames have even rows and columns";
+    }
+    g.chromaOff = chromaOff > 0 ? chromaOff : plane;
+    if (g.chromaOff < plane)
+    {
+        return "chroma offset inside the luma plane";
+    }
+    g.frameStride = frameStride > 0 ? frameStride : g.chromaOff + plane / 2;
+    if (g.frameStride < g.chromaOff + plane / 2)
+    {
+        return "frame stride smaller than a frame (frames would overlap)";
+    }
+    return nullptr;
+}
+
+// the plan's input planes against the layout: 1 for GRAY, 3 for the colour layouts — NV12 / NV21 included: the luma plane is limited
+// range, not the grey cvtColor gives, so a 1-plane plan does not take it
+static bool u8PlanesOk(const U8Geom& g, int d_in)
+{
+    return (g.cpp == 1 && !g.yuv) == (d_in == 1);
+}
+
+static YuvSrc yuvSrc(const uint8_t* frames, int pix, int rows, int cols, const U8Geom& g)
+{
+    YuvSrc s{};
+    s.in = frames;
+    s.H = rows;
+    s.W = cols;
+    s.rowStride = g.stride;
+    s.vFirst = pix == ACF_HIP_PIX_NV21;
+    s.chromaOff = g.chromaOff;
+    s.in_fs = g.frameStride;
+    return s;
+}
+
+// k_yuv420_to_rgb8 over a batch: NV12 / NV21 frames of rows x cols -> tight RGB frames at dst
+static int launchYuvToRgb(acf_hip_ctx* c, const YuvSrc& s, int nF, uint8_t* dst)
+{
+    prof(c, c->stream, "k_yuv420_to_rgb8");
+    hipLaunchKernelGGL(k_yuv420_to_rgb8, dim3(cdiv(s.W / 2, 64), cdiv(s.H / 2, 4), nF), dim3(256), 0, c->stream, s, dst);
+    LAUNCHCHK(c, "k_yuv420_to_rgb8");
+    return ACF_HIP_OK;
+}
+
+// The conversion an ingest kernel does on its way (IG_*).  convert: to the converted colour planes; else planar, the input's own planes.
+static int ingestMode(const acf_hip_ctx* c, bool convert)
+{
+    if (convert && c->p.colorSpace == ACF_HIP_CS_LUV)
+    {
+        return (int64_t(c->plan.H) * c->plan.W % 4 == 0) ? IG_LUV_VEC : IG_LUV; // rgbConvertMex.cpp:92,343
+    }
+    if (convert && c->p.colorSpace == ACF_HIP_CS_GRAY)
+    {
+        return IG_GRAY; // a 1-plane input is replicated first (chnsPyramid.cpp:234-244): r == g == b
+    }
+    return IG_PLANAR;
+}
+
+// What every ingest kernel is told, whatever it reads: the nOut destination planes and the constants of the model's colour conversion
+static void ingestShared(acf_hip_ctx* c, float* dst, int64_t out_fs, int nOut, IngestArgs& a)
+{
+    const Plan& pl = c->plan;
+    a.out = dst;
+    a.nOut = nOut;
+    a.lTable = c->d_lTable;
+    a.k = makeLuvConsts();
+    a.x86 = x86T(c);
+    a.mr = kGray.r;
+    a.mg = kGray.g;
+    a.mb = kGray.b;
+    a.H = pl.H;
+    a.W = pl.W;
+    a.out_fs = out_fs;
+    a.vecStore = (pl.H % 4 == 0) && (out_fs % 4 == 0) && (reinterpret_cast<uintptr_t>(dst) % 16 == 0);
+}
+
+// What is wrong with an image description by itself (acf_hip_image_extent and the image entries), or null
+static const char* imageDescBad(const acf_hip_image_desc* d)
+{
+    if (!d)
+    {
+        return "null description";
+    }
+    if (d->dtype < ACF_HIP_T_U8 || d->dtype > ACF_HIP_T_F32)
+    {
+        return "unknown dtype";
+    }
+    if (d->channels != 1 && d->channels != 3)
+    {
+        return "channels must be 1 or 3";
+    }
+    if (d->stride_x < 1 || d->stride_y < 1)
+    {
+        return "stride_x and stride_y must be positive";
+    }
+    if (d->stride_n < 0)
+    {
+        return "negative stride_n";
+    }
+    return nullptr;
+}
+
+static int imageElemBytes(int dtype)
+{
+    return dtype == ACF_HIP_T_U8 ? 1 : (dtype == ACF_HIP_T_F32 ? 4 : 2);
+}
+
+// an image description as the kernels take it (without the load form)
+static ImageArgs imageArgs(const void* frames, const acf_hip_image_desc& d)
+{
+    ImageArgs s{};
+    s.in = frames;
+    s.sn = d.stride_n;
+    s.sc = d.stride_c;
+    s.sy = d.stride_y;
+    s.sx = d.stride_x;
+    s.nIn = d.channels;
+    return s;
+}
+
+// The load form of k_ingest_image for a description and a pointer: the vector forms where their conditions hold (kernels_input.hip.h),
+// else the element-wise one, which is right for every description.
+static int imageLoadForm(const void* frames, const acf_hip_image_desc& d)
+{
+    const uintptr_t at = reinterpret_cast<uintptr_t>(frames);
+    const int es = imageElemBytes(d.dtype);
+    if (at % es)
+    {
+        return IM_GENERIC;
+    }
+    if (d.stride_x == 1 && at % (4 * es) == 0 && d.stride_n % 4 == 0 && d.stride_y % 4 == 0 && (d.channels == 1 || d.stride_c % 4 == 0))
+    {
+        return IM_ROWVEC;
+    }
+    if (d.channels == 3 && (d.stride_c == 1 || d.stride_c == -1) && (d.stride_x == 3 || d.stride_x == 4))
+    {
+        return IM_PACKED;
+    }
+    return IM_GENERIC;
+}
+
+// What is wrong with a YUV description by itself (acf_hip_yuv_extent, the YUV entries), or null
+static const char* yuvDescBad(const acf_hip_yuv_desc* d)
+{
+    if (!d)
+    {
+        return "null description";
+    }
+    if (d->sub_x < 0 || d->sub_x > 1 || d->sub_y < 0 || d->sub_y > 1)
+    {
+        return "sub_x and sub_y must be 0 or 1";
+    }
+    for (const acf_hip_yuv_plane* p : { &d->y, &d->u, &d->v })
+    {
+        if (p->stride_px < 1 || p->stride_row < 1)
+        {
+            return "stride_px and stride_row must be positive";
+        }
+        if (p->stride_n < 0)
+        {
+            return "negative stride_n";
+        }
+    }
+    return nullptr;
+}
+
+// first / last byte offset plane by plane (Y, U, V) that nF frames of h x w address
+static void yuvExtent(const acf_hip_yuv_desc& d, int h, int w, int nF, int64_t first[3], int64_t last[3])
+{
+    const acf_hip_yuv_plane* pl[3] = { &d.y, &d.u, &d.v };
+    for (int i = 0; i < 3; i++)
+    {
+        const int rows = i ? (h + d.sub_y) >> d.sub_y : h, cols = i ? (w + d.sub_x) >> d.sub_x : w;
+        first[i] = pl[i]->offset; // (no stride is negative)
+        last[i] = pl[i]->offset + int64_t(nF - 1) * pl[i]->stride_n + int64_t(rows - 1) * pl[i]->stride_row + int64_t(cols - 1) * pl[i]->stride_px;
+    }
+}
+
+static YuvDescSrc yuvDescSrc(const uint8_t* base, const acf_hip_yuv_desc& d)
+{
+    YuvDescSrc s{};
+    s.base = base;
+    s.y = YuvPlane{ d.y.offset, d.y.stride_n, d.y.stride_row, d.y.stride_px };
+    s.u = YuvPlane{ d.u.offset, d.u.stride_n, d.u.stride_row, d.u.stride_px };
+    s.v = YuvPlane{ d.v.offset, d.v.stride_n, d.v.stride_row, d.v.stride_px };
+    s.subX = d.sub_x;
+    s.subY = d.sub_y;
+    return s;
+}
+
+// The load form of k_ingest_yuv for a description and a pointer: the vector forms where their conditions hold (kernels_input.hip.h),
+// else the byte form, which is right for every description.  YD_PACKED422 also fills in the macropixel's byte order.
+static int yuvLoadForm(YuvDescSrc& s)
+{
+    const uintptr_t at = reinterpret_cast<uintptr_t>(s.base);
+    const auto aligned = [&](const YuvPlane& p) { return (at + uintptr_t(p.off)) % 4 == 0 && p.sr % 4 == 0 && p.sn % 4 == 0; };
+    if (s.y.sp == 1 && s.u.sp == 1 && s.v.sp == 1 && aligned(s.y) && aligned(s.u) && aligned(s.v))
+    {
+        return YD_PLANAR;
+    }
+    if (s.subX == 1 && s.subY == 0 && s.y.sp == 2 && s.u.sp == 4 && s.v.sp == 4 && s.y.sr == s.u.sr && s.y.sr == s.v.sr && s.y.sn == s.u.sn &&
+        s.y.sn == s.v.sn)
+    {
+        const int64_t mp = std::min(s.y.off, std::min(s.u.off, s.v.off));
+        const int64_t yp = s.y.off - mp, up = s.u.off - mp, vp = s.v.off - mp;
+        // Y0, Y1, U, V take the four bytes of one aligned macropixel
+        if (yp <= 1 && up <= 3 && vp <= 3 && ((1 << yp) | (1 << (yp + 2)) | (1 << up) | (1 << vp)) == 15 && (at + uintptr_t(mp)) % 4 == 0 && s.y.sr % 4 == 0 &&
+            s.y.sn % 4 == 0)
+        {
+            s.mp = mp;
+            s.yPos = int(yp);
+            s.uPos = int(up);
+            s.vPos = int(vp);
+            return YD_PACKED422;
+        }
+    }
+    return YD_GENERIC;
+}
+
+// A description of an NV12 / NV21 frame as the 8-bit entry takes it (one row stride, interleaved chroma pairs, even sizes): the
+// YuvSrc of k_ingest_yuv420, which then runs it — the same kernel, so the same bits as acf_hip_run_u8(ACF_HIP_PIX_NV12 / _NV21)
+static bool yuvIsSemiPlanar(const uint8_t* base, const acf_hip_yuv_desc& d, int H, int W, YuvSrc& out)
+{
+    const int64_t c0 = std::min(d.u.offset, d.v.offset);
+    if (!(d.sub_x == 1 && d.sub_y == 1 && H % 2 == 0 && W % 2 == 0 && d.y.stride_px == 1 && d.u.stride_px == 2 && d.v.stride_px == 2 &&
+            std::max(d.u.offset, d.v.offset) == c0 + 1 && d.u.stride_row == d.y.stride_row && d.v.stride_row == d.y.stride_row && d.y.stride_row <= INT32_MAX &&
+            d.u.stride_n == d.y.stride_n && d.v.stride_n == d.y.stride_n))
+    {
+        return false;
+    }
+    out = YuvSrc{};
+    out.in = base + d.y.offset;
+    out.H = H;
+    out.W = W;
+    out.rowStride = int(d.y.stride_row);
+    out.vFirst = d.v.offset < d.u.offset;
+    out.chromaOff = c0 - d.y.offset;
+    out.in_fs = d.y.stride_n;
+    return true;
+}
+
+// rgbConvert of nF frames of n pixels: `in` holds nIn planes a frame (frame stride in_fs), `out` the converted planes (out_fs).  LUV takes
+// the vector body iff n % 4 == 0 (rgbConvertMex.cpp:92,343); a 1-plane input is replicated first (chnsPyramid.cpp:234-244): gray from
+// it is k_rgb2gray<true>, ORIG / RGB k_replicate3.  The caller checks the launch.
+static void launchColour(acf_hip_ctx* c, const float* in, float* out, int64_t n, int nF, int64_t in_fs, int64_t out_fs, int colorSpace, int nIn)
+{
+    const dim3 grid(cdiv(n, 256), 1, nF), block(256);
+    if (colorSpace == ACF_HIP_CS_LUV)
+    {
+        hipLaunchKernelGGL((n % 4 == 0 ? k_rgb2luv<true> : k_rgb2luv<false>), grid, block, 0, c->stream, in, out, (const float*)c->d_lTable, makeLuvConsts(),
+            int(n), in_fs, out_fs, x86T(c));
+    }
+    else if (colorSpace == ACF_HIP_CS_GRAY)
+    {
+        hipLaunchKernelGGL((nIn == 1 ? k_rgb2gray<true> : k_rgb2gray<false>), grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs, kGray.r, kGray.g,
+            kGray.b);
+    }
+    else if (colorSpace == ACF_HIP_CS_HSV)
+    {
+        hipLaunchKernelGGL(k_rgb2hsv, grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs);
+    }
+    else
+    {
+        hipLaunchKernelGGL(k_replicate3, grid, block, 0, c->stream, in, out, int(n), in_fs, out_fs);
+    }
+}
+
+// what rz_pixel reads besides the source: the tables on the device and the source size
+static ResizeTaps resizeTaps(const acf_hip_ctx::InputResize& rz)
+{
+    ResizeTaps t{};
+    t.rows = rz.t.rows;
+    t.cols = rz.t.cols;
+    t.mode = rz.t.mode;
+    t.isx = rz.t.isx;
+    t.isy = rz.t.isy;
+    t.xlin = reinterpret_cast<const int4*>(rz.d_xlin);
+    t.ylin = reinterpret_cast<const int4*>(rz.d_ylin);
+    t.xrun = reinterpret_cast<const int2*>(rz.d_xrun);
+    t.yrun = reinterpret_cast<const int2*>(rz.d_yrun);
+    t.xtap = reinterpret_cast<const int2*>(rz.d_xtap);
+    t.ytap = reinterpret_cast<const int2*>(rz.d_ytap);
+    return t;
+}
+
+// k_resize_u8 over a batch: `src` frames of t.rows x t.cols (row stride `stride` bytes) -> tight t.drows x t.dcols frames at dst
+static int launchResizeU8(acf_hip_ctx* c, const acf_hip_ctx::InputResize& rz, const uint8_t* src, int cpp, int stride, int nF, uint8_t* dst)
+{
+    const ResizeTables& t = rz.t;
+    ResizeArgs a{};
+    a.src = src;
+    a.dst = dst;
+    a.cn = cpp;
+    a.stride = stride;
+    a.drows = t.drows;
+    a.dcols = t.dcols;
+    a.src_fs = int64_t(stride) * t.rows;
+    a.dst_fs = int64_t(t.drows) * t.dcols * cpp;
+    a.t = resizeTaps(rz);
+    prof(c, c->stream, "k_resize_u8");
+    hipLaunchKernelGGL(k_resize_u8, dim3(cdiv(t.dcols, 64), cdiv(t.drows, 4), nF), dim3(256), 0, c->stream, a);
+    LAUNCHCHK(c, "k_resize_u8");
+    return ACF_HIP_OK;
+}
+
+static int uploadResizeTables(acf_hip_ctx* c, acf_hip_ctx::InputResize& rz)
+{
+    int rc;
+    if ((rc = devUpload(c, &rz.d_xlin, rz.t.xlin)) || (rc = devUpload(c, &rz.d_ylin, rz.t.ylin)) || (rc = devUpload(c, &rz.d_xrun, rz.t.xrun)) ||
+        (rc = devUpload(c, &rz.d_yrun, rz.t.yrun)) || (rc = devUpload(c, &rz.d_xtap, rz.t.xtap)) || (rc = devUpload(c, &rz.d_ytap, rz.t.ytap)))
+    {
+        return rc;
+    }
+    return ACF_HIP_OK;
+}
+
+static void releaseResize(acf_hip_ctx* c, acf_hip_ctx::InputResize& r)
+{
+    devRelease(c, r.d_xlin);
+    devRelease(c, r.d_ylin);
+    devRelease(c, r.d_xrun);
+    devRelease(c, r.d_yrun);
+    devRelease(c, r.d_xtap);
+    devRelease(c, r.d_ytap);
+    devRelease(c, r.d_out);
+}
+
+// The tap tables of (srcRows, srcCols, scale) into `slot` (c->rz or c->rzIn) in place of the ones it holds: built, held against the
+// plan, uploaded — with the reduced 8-bit frames' buffer where k_resize_u8 is to run (withOut) — and installed switched on
+static int installResizeTables(acf_hip_ctx* c, const char* who, acf_hip_ctx::InputResize& slot, int srcRows, int srcCols, double scale, bool withOut)
+{
+    acf_hip_ctx::InputResize rz;
+    if (buildResizeTables(srcRows, srcCols, scale, rz.t) || rz.t.drows != c->plan.H || rz.t.dcols != c->plan.W)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": the plan must be for the reduced size (acf_hip_resize_dims of the frame size and scale)");
+    }
+    rz.rows = srcRows;
+    rz.cols = srcCols;
+    rz.scale = scale;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = uploadResizeTables(c, rz)) || (withOut && (rc = devAlloc(c, &rz.d_out, size_t(c->maxBatch) * c->plan.H * c->plan.W * 4))))
+    {
+        releaseResize(c, rz); // (what was uploaded before the failure)
+        return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // the previous tables: a batch in flight may still read them
+    releaseResize(c, slot);
+    rz.on = true;
+    slot = rz;
+    return ACF_HIP_OK;
+}
+
+// What the resized entries refuse about (src_rows, src_cols, scale) and the plan, then their tap tables on the device: those of the
+// context's key (rows, cols, scale) as they are, else new ones
+static int resizedTables(acf_hip_ctx* c, const char* who, int srcRows, int srcCols, double scale)
+{
+    if (srcRows < 1 || srcCols < 1 || !(scale > 0) || !std::isfinite(scale))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": src_rows and src_cols >= 1, scale a positive finite number");
+    }
+    if (c->rz.on)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": not with acf_hip_set_input_resize (the entry resizes by itself)");
+    }
+    const acf_hip_ctx::InputResize& cur = c->rzIn;
+    if (cur.on && cur.rows == srcRows && cur.cols == srcCols && cur.scale == scale)
+    {
+        return ACF_HIP_OK; // (built against this plan: acf_hip_plan drops them)
+    }
+    return installResizeTables(c, who, c->rzIn, srcRows, srcCols, scale, false);
+}
+
+// One call's ingest, decided once (planIngest); PyramidRun::ingest only reads it
+struct IngestPlan
+{
+    // the preludes, in this order: cvtColor first, as the apps do, in front of their Resizer (convert -> resize -> ingest)
+    bool toRgb = false;        // k_yuv420_to_rgb8: the caller's NV12 / NV21 frames -> tight RGB in c->d_yuvRgb
+    YuvSrc toRgbSrc{};
+    bool resize = false;       // k_resize_u8 (the apps' Resizer, acf.cpp:117-148): frames of rz.rows x rz.cols -> c->rz.d_out
+    const uint8_t* resizeSrc = nullptr;
+    int resizeCpp = 0, resizeStride = 0;
+    // the ingest kernel
+    bool convert = false;      // it writes the converted colour planes (c->d_color), else planar ones (c->d_stage)
+    int nOut = 0;              // ... this many a frame
+    const uint8_t* in = nullptr; // the 8-bit kinds: the packed frames it reads and their layout
+    U8Geom g{};
+    const void* kernel = nullptr;
+    union Second               // the kernel's second argument (k_ingest_u8 has none)
+    {
+        ResizedSrc resized;
+        YuvSrc yuv420;
+        ImageArgs image;
+        YuvDescSrc yuv;
+    } second{};
+    const char* profName = nullptr;   // (static strings: prof keeps the pointer)
+    const char* launchName = nullptr;
+
+    // (a kernel goes in together with the argument of its own type)
+    void set(IngestKernel k) { kernel = reinterpret_cast<const void*>(k); }
+    void set(YuvIngestKernel k, const YuvSrc& s) { kernel = reinterpret_cast<const void*>(k); second.yuv420 = s; }
+    void set(ImageKernel k, const ImageArgs& s) { kernel = reinterpret_cast<const void*>(k); second.image = s; }
+    void set(YuvDescKernel k, const YuvDescSrc& s) { kernel = reinterpret_cast<const void*>(k); second.yuv = s; }
+    void set(ResizedKernel k, const ResizedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.resized = s; }
+};
+
+// The ingest of one call: the source held against the plan and the context's settings (what is refused, in the order the entries
+// have always checked), then the kernel form, its arguments and its names.  The ONE place that decides them.
+static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
+{
+    const int H = c->plan.H, W = c->plan.W, d_in = c->plan.d_in;
+    const std::string who = std::string(src.who) + ": ";
+    ip = IngestPlan{};
+    // to the converted colour planes where the model converts (every colour space but hsv), else to planar planes in d_stage (hsv:
+    // k_rgb2hsv follows like on a float frame; orig / isLuv: the pyramid reads them as they are)
+    ip.convert = c->d_color && c->p.colorSpace != ACF_HIP_CS_HSV;
+    const int mode = ingestMode(c, ip.convert);
+    ip.nOut = (ip.convert && mode == IG_PLANAR) ? 3 : d_in; // ORIG / RGB with a 1-plane input: replicate (chnsPyramid.cpp:242-243)
+    if (src.kind == SRC_U8)
+    {
+        // 8-bit ingest (ACF.cpp:114-119,137; MatP.cpp:51-73), fused with the colour conversion when there is one
+        if (d_in == 5)
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + "a plan for five input planes (image + M, O) takes float frames");
+        }
+        const bool rz = c->rz.on, yuv = pixIsYuv(src.pix), fused = yuv && !rz && !fallbackForced(FB_YUV_UNFUSED);
+        int rows = rz ? c->rz.rows : H, cols = rz ? c->rz.cols : W; // the caller's frames
+        U8Geom& g = ip.g;
+        if (const char* bad = u8Geom(src.pix, rows, cols, src.rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
+        {
+            return fail(c, ACF_HIP_E_INVALID, std::string(src.who) + (rz && !yuv ? " (the unreduced frame): " : ": ") + bad);
+        }
+        if (!u8PlanesOk(g, d_in))
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + (yuv && !fused ? "the plan's input planes (d) must be 3 for NV12 / NV21"
+                                                                  : "the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY"));
+        }
+        ip.in = static_cast<const uint8_t*>(src.base);
+        // a prelude leaves tight frames of the same pixel layout
+        const auto tight = [&](const uint8_t* at) {
+            ip.in = at;
+            g.stride = cols * g.cpp;
+            g.frameStride = int64_t(g.stride) * rows;
+        };
+        if (yuv && !fused)
+        {
+            const size_t need = size_t(c->maxBatch) * rows * cols * 3;
+            if (c->yuvRgbBytes < need)
+            {
+                HIPCHK(c, hipStreamSynchronize(c->stream)); // (a batch in flight may still read the smaller buffer)
+                devRelease(c, c->d_yuvRgb);
+                c->yuvRgbBytes = 0;
+                if (int rc = devAlloc(c, &c->d_yuvRgb, need))
+                {
+                    return rc;
+                }
+                c->yuvRgbBytes = need;
+            }
+            ip.toRgb = true;
+            ip.toRgbSrc = yuvSrc(ip.in, src.pix, rows, cols, g);
+            g = U8Geom{ 3, 0, 0, 1, 2, false, 0, 0 };
+            tight(c->d_yuvRgb);
+        }
+        if (rz)
+        {
+            ip.resize = true;
+            ip.resizeSrc = ip.in;
+            ip.resizeCpp = g.cpp;
+            ip.resizeStride = g.stride;
+            rows = H;
+            cols = W;
+            tight(c->rz.d_out);
+        }
+        bool aligned = (reinterpret_cast<uintptr_t>(ip.in) % 4 == 0) && (g.stride % 4 == 0);
+        if (fused)
+        {
+            aligned = aligned && g.chromaOff % 4 == 0 && g.frameStride % 4 == 0;
+            ip.set(yuvIngestKernel(mode, aligned), yuvSrc(ip.in, src.pix, H, W, g));
+        }
+        else
+        {
+            ip.set(ingestKernel(mode, aligned));
+        }
+        ip.profName = ip.launchName = fused ? "k_ingest_yuv420" : "k_ingest_u8";
+        return ACF_HIP_OK;
+    }
+    if (src.kind == SRC_IMAGE)
+    {
+        // The image entry for upright images of any strides and element type (ACF.cpp:135-141 for CV_32FC3 and CV_8UC3; MatP.cpp:51-73);
+        // the resized entry: the apps' Resizer on the addressed bytes first, in the same kernel (k_ingest_resized)
+        if (const char* bad = imageDescBad(&src.img))
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + bad);
+        }
+        if (d_in == 5)
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + "a plan for five input planes (image + M, O) takes planar float frames");
+        }
+        if (src.img.channels != d_in)
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + "channels must be the plan's input planes (d)");
+        }
+        ImageArgs s = imageArgs(src.base, src.img);
+        if (!src.resized)
+        {
+            if (c->rz.on)
+            {
+                return fail(c, ACF_HIP_E_INVALID, who + "not with acf_hip_set_input_resize (the resize takes packed 8-bit frames)");
+            }
+            s.form = imageLoadForm(src.base, src.img);
+            ip.set(imageKernel(src.img.dtype, mode), s);
+            ip.profName = ip.launchName = "k_ingest_image";
+            return ACF_HIP_OK;
+        }
+        if (src.img.dtype != ACF_HIP_T_U8)
+        {
+            return fail(c, ACF_HIP_E_UNSUPPORTED, who + "dtype must be ACF_HIP_T_U8 (cv::resize's CV_32F arithmetic is not restated)");
+        }
+        if (int rc = resizedTables(c, src.who, src.srcRows, src.srcCols, src.scale))
+        {
+            return rc;
+        }
+        ResizedSrc r{};
+        r.t = resizeTaps(c->rzIn);
+        r.im = s;
+        ip.set(resizedKernel(RS_IMAGE, mode), r);
+        ip.profName = "k_ingest_resized_image";
+        ip.launchName = "k_ingest_resized";
+        return ACF_HIP_OK;
+    }
+    // The video frame entry for three-plane YUV descriptions: cvtColor's BT.601 integer conversion (restated, kernels_input.hip.h), then
+    // the 8-bit image entry (ACF.cpp:114-119,135-141; MatP.cpp:51-73), in one kernel; the resized entry: the apps' Resizer between the
+    // two, still one kernel (k_ingest_resized)
+    if (const char* bad = yuvDescBad(&src.yuv))
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + bad);
+    }
+    if (d_in != 3)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "the plan's input planes (d) must be 3");
+    }
+    const uint8_t* base = static_cast<const uint8_t*>(src.base);
+    YuvDescSrc s = yuvDescSrc(base, src.yuv);
+    if (src.resized)
+    {
+        if (int rc = resizedTables(c, src.who, src.srcRows, src.srcCols, src.scale))
+        {
+            return rc;
+        }
+        ResizedSrc r{};
+        r.t = resizeTaps(c->rzIn);
+        r.yuv = s;
+        ip.set(resizedKernel(RS_YUV, mode), r);
+        ip.profName = "k_ingest_resized_yuv";
+        ip.launchName = "k_ingest_resized";
+        return ACF_HIP_OK;
+    }
+    if (c->rz.on)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)");
+    }
+    YuvSrc semi;
+    if (yuvIsSemiPlanar(base, src.yuv, H, W, semi))
+    {
+        const bool aligned = reinterpret_cast<uintptr_t>(semi.in) % 4 == 0 && semi.rowStride % 4 == 0 && semi.chromaOff % 4 == 0 && semi.in_fs % 4 == 0;
+        ip.set(yuvIngestKernel(mode, aligned), semi); // (even sizes: never IG_LUV)
+        ip.profName = ip.launchName = "k_ingest_yuv420";
+        return ACF_HIP_OK;
+    }
+    static const char* const names[3] = { "k_ingest_yuv_generic", "k_ingest_yuv_planar", "k_ingest_yuv_packed422" };
+    const int form = yuvLoadForm(s);
+    ip.set(yuvDescKernel(form, mode), s);
+    ip.profName = names[form];
+    ip.launchName = "k_ingest_yuv";
+    return ACF_HIP_OK;
+}
+
+// the pyramid of a source, then the cascade on it: the run_ entries of every kind but planar float frames, and the stream
+static int runSource(acf_hip_ctx* c, const FrameSource& src, int nF)
+{
+    const int rc = pyramidImpl(c, src, nF);
+    return rc ? rc : acf_hip_detect(c);
+}
+
+// the image and the YUV entries, plain and resized: the pyramid alone, or the whole run (detect)
+static int imageEntry(acf_hip_ctx* c, bool detect, const char* who, const void* frames, int nF, const acf_hip_image_desc* desc, bool resized = false, int srcRows = 0,
+    int srcCols = 0, double scale = 1)
+{
+    if (int rc = needCtx(c)) return rc;
+    if (!frames || !desc)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": null frames or description");
+    }
+    const FrameSource src{ SRC_IMAGE, frames, who, 0, 0, *desc, {}, resized, srcRows, srcCols, scale };
+    return detect ? runSource(c, src, nF) : pyramidImpl(c, src, nF);
+}
+static int yuvEntry(acf_hip_ctx* c, bool detect, const char* who, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, bool resized = false, int srcRows = 0,
+    int srcCols = 0, double scale = 1)
+{
+    if (int rc = needCtx(c)) return rc;
+    if (!base || !desc)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": null base or description");
+    }
+    const FrameSource src{ SRC_YUV, base, who, 0, 0, {}, *desc, resized, srcRows, srcCols, scale };
+    return detect ? runSource(c, src, nF) : pyramidImpl(c, src, nF);
+}
+} // namespace
+
+int acf_hip_pyramid_u8(acf_hip_ctx* c, const uint8_t* frames, int nF, int pix, int rowStride)
+{
+    if (int rc = needCtx(c)) return rc;
+    return pyramidImpl(c, FrameSource{ SRC_U8, frames, "pyramid_u8", pix, rowStride }, nF);
+}
+
+int acf_hip_run_u8(acf_hip_ctx* c, const uint8_t* frames, int nF, int pix, int rowStride)
+{
+    if (int rc = needCtx(c)) return rc;
+    return runSource(c, FrameSource{ SRC_U8, frames, "pyramid_u8", pix, rowStride }, nF);
+}
+
+int acf_hip_pyramid_image(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc)
+{
+    return imageEntry(c, false, "pyramid_image", frames, nF, desc);
+}
+
+int acf_hip_run_image(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc)
+{
+    return imageEntry(c, true, "pyramid_image", frames, nF, desc);
+}
+
+int acf_hip_pyramid_image_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, double scale)
+{
+    return imageEntry(c, false, "pyramid_image_resized", frames, nF, desc, true, srcRows, srcCols, scale);
+}
+
+int acf_hip_run_image_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, double scale)
+{
+    return imageEntry(c, true, "pyramid_image_resized", frames, nF, desc, true, srcRows, srcCols, scale);
+}
+
+int acf_hip_pyramid_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
+{
+    return yuvEntry(c, false, "pyramid_yuv", base, nF, desc);
+}
+
+int acf_hip_run_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
+{
+    return yuvEntry(c, true, "pyramid_yuv", base, nF, desc);
+}
+
+int acf_hip_pyramid_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
+{
+    return yuvEntry(c, false, "pyramid_yuv_resized", base, nF, desc, true, srcRows, srcCols, scale);
+}
+
+int acf_hip_run_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
+{
+    return yuvEntry(c, true, "pyramid_yuv_resized", base, nF, desc, true, srcRows, srcCols, scale);
+}
+
+int acf_hip_image_extent(const acf_hip_image_desc* d, int h, int w, int nF, int64_t* first, int64_t* last)
+{
+    if (!first || !last || imageDescBad(d) || h < 1 || w < 1 || nF < 1)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    int64_t lo = 0, hi = 0;
+    const int64_t span[4] = { (nF - 1) * d->stride_n, (d->channels - 1) * d->stride_c, (h - 1) * d->stride_y, (w - 1) * d->stride_x };
+    for (int64_t v : span)
+    {
+        (v < 0 ? lo : hi) += v;
+    }
+    *first = lo;
+    *last = hi;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_yuv_to_rgb8(acf_hip_ctx* c, const uint8_t* base, int nF, int rows, int cols, const acf_hip_yuv_desc* desc, uint8_t* dst)
+{
+    if (int rc = needCtx(c)) return rc;
+    if (!base || !desc || !dst)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "yuv_to_rgb8: null base, description or destination");
+    }
+    if (const char* bad = yuvDescBad(desc))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("yuv_to_rgb8: ") + bad);
+    }
+    if (nF < 1 || nF > 65535 || rows < 1 || cols < 1)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "yuv_to_rgb8: n_frames 1 .. 65535, rows and cols >= 1");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    prof(c, c->stream, "k_yuv_to_rgb8");
+    hipLaunchKernelGGL(k_yuv_to_rgb8, dim3(cdiv(cols, 64), cdiv(rows, 4), nF), dim3(256), 0, c->stream, yuvDescSrc(base, *desc), rows, cols, dst);
+    LAUNCHCHK(c, "k_yuv_to_rgb8");
+    return ACF_HIP_OK;
+}
+
+int acf_hip_yuv_extent(const acf_hip_yuv_desc* d, int h, int w, int nF, int64_t* first, int64_t* last)
+{
+    if (!first || !last || yuvDescBad(d) || h < 1 || w < 1 || nF < 1)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    yuvExtent(*d, h, w, nF, first, last);
+    return ACF_HIP_OK;
+}
+
+int acf_hip_yuv_layout(int layout, int h, int w, int rowStride, acf_hip_yuv_desc* out, int64_t* frameBytes)
+{
+    if (!out || !frameBytes || h < 1 || w < 1 || rowStride < 0 || layout < ACF_HIP_YUV_NV12 || layout > ACF_HIP_YUV_YVYU)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    const bool packed = layout >= ACF_HIP_YUV_YUYV, semi = layout <= ACF_HIP_YUV_NV21;
+    const int subX = layout == ACF_HIP_YUV_I444 ? 0 : 1, subY = (semi || layout == ACF_HIP_YUV_I420 || layout == ACF_HIP_YUV_YV12) ? 1 : 0;
+    const int64_t rowBytes = packed ? 2 * int64_t(w) : w;
+    const int64_t stride = rowStride > 0 ? rowStride : rowBytes;
+    if (stride < rowBytes || (subX && w % 2) || (subY && h % 2) || (!packed && !semi && stride % 2))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    acf_hip_yuv_desc d{};
+    d.sub_x = subX;
+    d.sub_y = subY;
+    int64_t fb;
+    if (packed)
+    {
+        // macropixels of four bytes: Y0 U Y1 V / U Y0 V Y1 / Y0 V Y1 U
+        const int yp = layout == ACF_HIP_YUV_UYVY ? 1 : 0, up = layout == ACF_HIP_YUV_YUYV ? 1 : (layout == ACF_HIP_YUV_UYVY ? 0 : 3),
+                  vp = layout == ACF_HIP_YUV_YUYV ? 3 : (layout == ACF_HIP_YUV_UYVY ? 2 : 1);
+        fb = stride * h;
+        d.y = acf_hip_yuv_plane{ yp, fb, stride, 2 };
+        d.u = acf_hip_yuv_plane{ up, fb, stride, 4 };
+        d.v = acf_hip_yuv_plane{ vp, fb, stride, 4 };
+    }
+    else if (semi)
+    {
+        const int64_t chroma = stride * h; // the tight rule of the 8-bit entry (u8Geom)
+        fb = chroma + stride * (h / 2);
+        const int vFirst = layout == ACF_HIP_YUV_NV21;
+        d.y = acf_hip_yuv_plane{ 0, fb, stride, 1 };
+        d.u = acf_hip_yuv_plane{ chroma + vFirst, fb, stride, 2 };
+        d.v = acf_hip_yuv_plane{ chroma + 1 - vFirst, fb, stride, 2 };
+    }
+    else
+    {
+        const int64_t cs = stride >> subX, plane = cs * (h >> subY), first = stride * h;
+        fb = first + 2 * plane;
+        const bool vFirst = layout == ACF_HIP_YUV_YV12;
+        d.y = acf_hip_yuv_plane{ 0, fb, stride, 1 };
+        d.u = acf_hip_yuv_plane{ first + (vFirst ? plane : 0), fb, cs, 1 };
+        d.v = acf_hip_yuv_plane{ first + (vFirst ? 0 : plane), fb, cs, 1 };
+    }
+    *out = d;
+    *frameBytes = fb;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_u8_frame_bytes(int pix, int rows, int cols, int rowStride, int64_t* out)
+{
+    U8Geom g;
+    if (!out || u8Geom(pix, rows, cols, rowStride, 0, 0, g))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    *out = g.frameStride;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_set_yuv_layout(acf_hip_ctx* c, int64_t chromaOff, int64_t frameStride)
+{
+    if (int rc = needPlan(c, "set_yuv_layout")) return rc;
+    if (!c->kids.empty() || !c->slots.empty())
+    {
+        return fail(c, ACF_HIP_E_UNSUPPORTED, "set_yuv_layout: not with option \"streams\" > 1; before acf_hip_stream_open");
+    }
+    if (chromaOff < 0 || frameStride < 0)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "set_yuv_layout: negative offset or stride");
+    }
+    dropGraph(c);
+    c->yuv.chromaOff = chromaOff; // (held against the frames' row stride where that is known: the run / open call)
+    c->yuv.frameStride = frameStride;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_resize_dims(int rows, int cols, double scale, int* out_rows, int* out_cols)
+{
+    if (!out_rows || !out_cols || rows < 1 || cols < 1 || !(scale > 0))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    resizeDims(rows, cols, scale, *out_rows, *out_cols);
+    return (*out_rows >= 1 && *out_cols >= 1) ? ACF_HIP_OK : ACF_HIP_E_INVALID;
+}
+
+int acf_hip_set_input_resize(acf_hip_ctx* c, int srcRows, int srcCols, double scale)
+{
+    if (int rc = needPlan(c, "set_input_resize", " (for the reduced size, acf_hip_resize_dims)")) return rc;
+    if (!c->kids.empty() || !c->slots.empty())
+    {
+        return fail(c, ACF_HIP_E_UNSUPPORTED, "set_input_resize: not with option \"streams\" > 1; before acf_hip_stream_open");
+    }
+    dropGraph(c);
+    if (srcRows <= 0 || srcCols <= 0)
+    {
+        c->rz.on = false;
+        return ACF_HIP_OK;
+    }
+    if (c->rz.d_out && c->rz.rows == srcRows && c->rz.cols == srcCols && c->rz.scale == scale)
+    {
+        c->rz.on = true; // same geometry as the tables already on the device (a re-opened stream): nothing to build
+        return ACF_HIP_OK;
+    }
+    return installResizeTables(c, "set_input_resize", c->rz, srcRows, srcCols, scale, true);
+}

@@ -4,8 +4,7 @@
 // call: the context's stream, or the scale's own between realScale and joinScales (option scale_streams).  c->stream itself is never reassigned;
 // ingest and colour run on it before any scale has a stream of its own, the levels after joinScales has set st back to it.
 //
-//   ingest()            packed 8-bit frames -> planar f32 (ACF.cpp:114-119,137), the apps' Resizer in front of it
-//   ingestImage() / ingestYuv()   the tensor and YUV entries; their resized forms run the Resizer inside the ingest kernel
+//   ingest(plan)        the call's frames -> planar f32 as planIngest decided (input_run.hip.h): the preludes, then the ingest kernel
 //   colour()            rgbConvert once at full resolution (chnsPyramid.cpp:230-263)
 //   prepareScales()     which image every real scale is resampled from (the I = I1 adoption, :313-316), the scales' streams
 //   realScale(k)        imageResample(k) -> planScale(k) -> smoothImage(k) -> gradientChannels(k): chnsCompute at a real scale (:297-338,
@@ -182,7 +181,6 @@ struct PyramidRun
     bool scalePar = false;                        // the real scales on their own streams
     hipStream_t st;                               // the stream the current stage enqueues on: the context's, but a real scale's own between realScale and joinScales
     LevelsCall lv;                                // the levels stage of this call (planLevels)
-    PackedSrc reduced{}, converted{};
 
     PyramidRun(acf_hip_ctx* ctx, const float* frames_, int nF_)
         : c(ctx), p(ctx->p), pl(ctx->plan), nF(nF_), H(pl.H), W(pl.W), d(pl.d), d_in(pl.d_in), shrink(ctx->p.shrink), np0(int64_t(pl.H) * pl.W), frames(frames_),
@@ -190,11 +188,7 @@ struct PyramidRun
     {
     }
 
-    int ingest(const PackedSrc* u8, bool& ingestConverted);
-    int ingestImage(const ImageSrc& im, bool& ingestConverted);
-    int ingestYuv(const YuvFrames& yf, bool& ingestConverted);
-    using IngestLaunch = std::function<int(float* dst, int64_t out_fs, bool convert)>;
-    int ingestPlanes(const char* kernel, bool& ingestConverted, const IngestLaunch& launch);
+    int ingest(const IngestPlan& ip);
     int colour(bool ingestConverted);
     int prepareScales();
     int realScale(size_t k);
@@ -212,169 +206,34 @@ struct PyramidRun
     int levelsWithImageLambdas();
 };
 
-int PyramidRun::ingest(const PackedSrc* u8, bool& ingestConverted)
+// ---- the ingest planIngest decided: its preludes, then the kernel, to the destination the plan names
+int PyramidRun::ingest(const IngestPlan& ip)
 {
     int rc;
-    if (d_in == 5)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: a plan for five input planes (image + M, O) takes float frames");
-    }
-    const int inRows = c->rz.on ? c->rz.rows : H, inCols = c->rz.on ? c->rz.cols : W; // the caller's frames
-    const bool fusedYuv = u8 && pixIsYuv(u8->pix) && !c->rz.on && !fallbackForced(FB_YUV_UNFUSED);
-    if (u8 && pixIsYuv(u8->pix) && !fusedYuv)
-    {
-        // cvtColor first, as the apps do: in front of their Resizer (convert -> resize -> ingest), and as k_ingest_yuv420's fallback
-        U8Geom g;
-        if (const char* bad = u8Geom(u8->pix, inRows, inCols, u8->rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
-        {
-            return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_u8: ") + bad);
-        }
-        if (!u8PlanesOk(g, d_in))
-        {
-            return fail(c, ACF_HIP_E_INVALID, "pyramid_u8: the plan's input planes (d) must be 3 for NV12 / NV21");
-        }
-        const size_t need = size_t(c->maxBatch) * inRows * inCols * 3;
-        if (c->yuvRgbBytes < need)
-        {
-            HIPCHK(c, hipStreamSynchronize(c->stream)); // (a batch in flight may still read the smaller buffer)
-            devRelease(c, c->d_yuvRgb);
-            c->yuvRgbBytes = 0;
-            if ((rc = devAlloc(c, &c->d_yuvRgb, need)))
-            {
-                return rc;
-            }
-            c->yuvRgbBytes = need;
-        }
-        if ((rc = launchYuvToRgb(c, yuvSrc(u8->frames, u8->pix, inRows, inCols, g), nF, c->d_yuvRgb)))
-        {
-            return rc;
-        }
-        converted = PackedSrc{ c->d_yuvRgb, ACF_HIP_PIX_RGB, 0 };
-        u8 = &converted;
-    }
-    if (u8 && c->rz.on)
-    {
-        // the apps' Resizer (acf.cpp:117-148) in front of the ingest: the caller's frames are rz.rows x rz.cols
-        U8Geom g;
-        if (const char* bad = u8Geom(u8->pix, inRows, inCols, u8->rowStride, 0, 0, g))
-        {
-            return fail(c, ACF_HIP_E_INVALID, std::string("pyramid_u8 (the unreduced frame): ") + bad);
-        }
-        if ((rc = launchResizeU8(c, c->rz, u8->frames, g.cpp, g.stride, nF, c->rz.d_out)))
-        {
-            return rc;
-        }
-        reduced = PackedSrc{ c->rz.d_out, u8->pix, 0 };
-        u8 = &reduced;
-    }
-    if (u8)
-    {
-        // 8-bit ingest (ACF.cpp:114-119,137; MatP.cpp:51-73), fused with the colour conversion below when there is one
-        return ingestPlanes(fusedYuv ? "k_ingest_yuv420" : "k_ingest_u8", ingestConverted,
-            [&](float* dst, int64_t out_fs, bool convert) { return launchIngest(c, *u8, nF, dst, out_fs, convert); });
-    }
-    return ACF_HIP_OK;
-}
-
-// An ingest kernel in front of the pyramid: to the converted colour planes where the model converts (every colour space but hsv),
-// else to planar planes in d_stage (hsv: k_rgb2hsv follows like on a float frame; orig / isLuv: the pyramid reads them as they are).
-int PyramidRun::ingestPlanes(const char* kernel, bool& ingestConverted, const IngestLaunch& launch)
-{
-    int rc;
-    prof(c, c->stream, kernel);
-    ingestConverted = c->d_color && p.colorSpace != ACF_HIP_CS_HSV;
-    if (ingestConverted)
-    {
-        if ((rc = launch(c->d_color, int64_t(d) * np0, true)))
-        {
-            return rc;
-        }
-        frames = nullptr;
-    }
-    else
-    {
-        if (!c->d_stage && (rc = devAlloc(c, &c->d_stage, size_t(c->maxBatch) * d_in * np0)))
-        {
-            return rc;
-        }
-        if ((rc = launch(c->d_stage, int64_t(d_in) * np0, false)))
-        {
-            return rc;
-        }
-        frames = c->d_stage;
-    }
-    return ACF_HIP_OK;
-}
-
-// The image entry for upright images of any strides and element type (ACF.cpp:135-141 for CV_32FC3 and CV_8UC3; MatP.cpp:51-73); the
-// resized entry (im.resized): the apps' Resizer on the addressed bytes first, in the same kernel (k_ingest_resized)
-int PyramidRun::ingestImage(const ImageSrc& im, bool& ingestConverted)
-{
-    const bool resized = im.resized;
-    const std::string who = resized ? "pyramid_image_resized: " : "pyramid_image: ";
-    if (const char* bad = imageDescBad(&im.d))
-    {
-        return fail(c, ACF_HIP_E_INVALID, who + bad);
-    }
-    if (d_in == 5)
-    {
-        return fail(c, ACF_HIP_E_INVALID, who + "a plan for five input planes (image + M, O) takes planar float frames");
-    }
-    if (im.d.channels != d_in)
-    {
-        return fail(c, ACF_HIP_E_INVALID, who + "channels must be the plan's input planes (d)");
-    }
-    if (!resized)
-    {
-        if (c->rz.on)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "pyramid_image: not with acf_hip_set_input_resize (the resize takes packed 8-bit frames)");
-        }
-        return ingestPlanes("k_ingest_image", ingestConverted,
-            [&](float* dst, int64_t out_fs, bool convert) { return launchIngestImage(c, im, nF, dst, out_fs, convert); });
-    }
-    if (im.d.dtype != ACF_HIP_T_U8)
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, who + "dtype must be ACF_HIP_T_U8 (cv::resize's CV_32F arithmetic is not restated)");
-    }
-    if (int rc = resizedTables(c, "pyramid_image_resized", im.srcRows, im.srcCols, im.scale))
+    if ((ip.toRgb && (rc = launchYuvToRgb(c, ip.toRgbSrc, nF, c->d_yuvRgb))) ||
+        (ip.resize && (rc = launchResizeU8(c, c->rz, ip.resizeSrc, ip.resizeCpp, ip.resizeStride, nF, c->rz.d_out))))
     {
         return rc;
     }
-    return ingestPlanes("k_ingest_resized_image", ingestConverted,
-        [&](float* dst, int64_t out_fs, bool convert) { return launchIngestResized(c, &im, nullptr, nF, dst, out_fs, convert); });
-}
-
-// The video frame entry for three-plane YUV descriptions: cvtColor's BT.601 integer conversion (restated, kernels_input.hip.h), then
-// the 8-bit image entry (ACF.cpp:114-119,135-141; MatP.cpp:51-73), in one kernel; the resized entry (yf.resized): the apps'
-// Resizer between the two, still one kernel (k_ingest_resized)
-int PyramidRun::ingestYuv(const YuvFrames& yf, bool& ingestConverted)
-{
-    const bool resized = yf.resized;
-    const std::string who = resized ? "pyramid_yuv_resized: " : "pyramid_yuv: ";
-    if (const char* bad = yuvDescBad(&yf.d))
-    {
-        return fail(c, ACF_HIP_E_INVALID, who + bad);
-    }
-    if (d_in != 3)
-    {
-        return fail(c, ACF_HIP_E_INVALID, who + "the plan's input planes (d) must be 3");
-    }
-    if (!resized)
-    {
-        if (c->rz.on)
-        {
-            return fail(c, ACF_HIP_E_INVALID, "pyramid_yuv: not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)");
-        }
-        return ingestPlanes(yuvKernelName(yf, H, W), ingestConverted,
-            [&](float* dst, int64_t out_fs, bool convert) { return launchIngestYuv(c, yf, nF, dst, out_fs, convert); });
-    }
-    if (int rc = resizedTables(c, "pyramid_yuv_resized", yf.srcRows, yf.srcCols, yf.scale))
+    prof(c, c->stream, ip.profName);
+    if (!ip.convert && !c->d_stage && (rc = devAlloc(c, &c->d_stage, size_t(c->maxBatch) * d_in * np0)))
     {
         return rc;
     }
-    return ingestPlanes("k_ingest_resized_yuv", ingestConverted,
-        [&](float* dst, int64_t out_fs, bool convert) { return launchIngestResized(c, nullptr, &yf, nF, dst, out_fs, convert); });
+    IngestArgs a{};
+    ingestShared(c, ip.convert ? c->d_color : c->d_stage, int64_t(ip.convert ? d : d_in) * np0, ip.nOut, a);
+    a.in = ip.in;
+    a.cpp = ip.g.cpp;
+    a.ro = ip.g.ro;
+    a.go = ip.g.go;
+    a.bo = ip.g.bo;
+    a.rowStride = ip.g.stride;
+    a.in_fs = ip.g.frameStride;
+    void* args[] = { &a, const_cast<IngestPlan::Second*>(&ip.second) };
+    (void)hipLaunchKernel(ip.kernel, dim3(cdiv(W, IG_T), cdiv(H, IG_T), nF), dim3(256), args, 0, c->stream);
+    LAUNCHCHK(c, ip.launchName);
+    frames = ip.convert ? nullptr : c->d_stage; // (converted: the pyramid starts from d_color)
+    return ACF_HIP_OK;
 }
 
 // ---- colour conversion, once at full resolution (chnsPyramid.cpp:230-263)
@@ -1153,14 +1012,14 @@ int PyramidRun::levelsWithImageLambdas()
     return ACF_HIP_OK;
 }
 
-int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF, const ImageSrc* img, const YuvFrames* yuv)
+int pyramidBody(acf_hip_ctx* c, const FrameSource& src, int nF)
 {
+    const float* const frames = src.kind == SRC_F32 ? static_cast<const float*>(src.base) : nullptr;
     if (c && !c->kids.empty())
     {
-        if (u8 || img || yuv)
+        if (src.kind != SRC_F32)
         {
-            return fail(c, ACF_HIP_E_UNSUPPORTED, std::string(yuv ? "pyramid_yuv" : (img ? "pyramid_image" : "pyramid_u8")) + ((yuv && yuv->resized) || (img && img->resized) ? "_resized" : "") +
-                ": not available with option \"streams\" > 1");
+            return fail(c, ACF_HIP_E_UNSUPPORTED, std::string(src.who) + ": not available with option \"streams\" > 1");
         }
         if (!frames || nF <= 0 || nF > c->maxBatch)
         {
@@ -1177,7 +1036,7 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
         return rc;
     }
     if (int rc = needPlan(c, "pyramid")) return rc;
-    if ((!frames && !u8 && !img && !yuv) || (u8 && !u8->frames) || (img && !img->frames) || (yuv && !yuv->base) || nF <= 0 || nF > c->maxBatch)
+    if (!src.base || nF <= 0 || nF > c->maxBatch)
     {
         return fail(c, ACF_HIP_E_INVALID, "pyramid: n_frames out of range");
     }
@@ -1185,14 +1044,13 @@ int pyramidBody(acf_hip_ctx* c, const float* frames, const PackedSrc* u8, int nF
     c->pyramidValid = c->detectValid = false;
     int rc;
     PyramidRun run(c, frames, nF);
-    bool ingestConverted = false; // the 8-bit ingest wrote the converted colour planes itself
-    if ((u8 && (rc = run.ingest(u8, ingestConverted))) || (img && (rc = run.ingestImage(*img, ingestConverted))) ||
-        (yuv && (rc = run.ingestYuv(*yuv, ingestConverted))))
+    IngestPlan ip; // (planar float frames: none; convert stays false)
+    if (src.kind != SRC_F32 && ((rc = planIngest(c, src, ip)) || (rc = run.ingest(ip))))
     {
         return rc;
     }
     c->lastFrames = run.frames;
-    if ((rc = run.colour(ingestConverted)) || (rc = run.prepareScales()))
+    if ((rc = run.colour(ip.convert)) || (rc = run.prepareScales()))
     {
         return rc;
     }

@@ -1,0 +1,90 @@
+"""Every kind of input on ONE context, in turn, forwards and then backwards: each call must leave exactly what a fresh context leaves
+for that call alone — the pyramid and the raw detections of both frames, bit for bit.  This is independence from history (the
+resized entries' tap tables, the planar staging buffer, the NV12 conversion buffer and its growth, the input resize's switch, the
+destination the ingest chooses), not correctness: the per-entry suites hold every entry against the reference.
+
+Once with a model whose colour conversion the ingest does itself (LUV), once with one it stages planar for (HSV)."""
+import numpy as np
+import pytest
+
+import resized_entry_case as rc
+import yuv_desc_ref as ydr
+from acf_amd import capi, synth
+
+pytestmark = pytest.mark.gpu
+
+PH, PW = 96, 128                  # the plan
+SH, SW, SCALE = 192, 256, 0.5     # the unreduced frames of the resized kinds
+NF = 2
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def steps():
+    """[(name, call(det))]: the device buffers are made once and shared by the fresh contexts and the sequence."""
+    import torch
+    from acf_amd.detector import HipDetector
+    assert HipDetector.resize_dims(SH, SW, SCALE) == (PH, PW)
+    f32 = dev(np.stack([synth.make_frame(11 + f, PH, PW, "rgb") for f in range(NF)]))
+    rgb = dev(np.stack([rc.rgb_u8(21 + f, PH, PW) for f in range(NF)]))
+    nv12 = dev(np.concatenate([ydr.pack("nv12", *rc.yuv_planes(31 + f, PH, PW, 1, 1)) for f in range(NF)]))
+    f16 = dev(np.stack([rc.rgb_u8(41 + f, PH, PW) for f in range(NF)])).permute(0, 3, 1, 2).contiguous().to(torch.float16) / 255
+    i420 = dev(np.concatenate([ydr.pack("i420", *rc.yuv_planes(51 + f, PH, PW, 1, 1)) for f in range(NF)]))
+    nv12b = dev(np.concatenate([ydr.pack("nv12", *rc.yuv_planes(61 + f, PH, PW, 1, 1)) for f in range(NF)]))
+    i420S = dev(np.concatenate([ydr.pack("i420", *rc.yuv_planes(71 + f, SH, SW, 1, 1)) for f in range(NF)]))
+    nchwS = dev(np.stack([rc.rgb_u8(81 + f, SH, SW) for f in range(NF)]).transpose(0, 3, 1, 2))
+    rgbS = dev(np.stack([rc.rgb_u8(91 + f, SH, SW) for f in range(NF)]))
+    d_i420, _ = HipDetector.yuv_desc("i420", PH, PW)
+    d_nv12, _ = HipDetector.yuv_desc("nv12", PH, PW)
+    d_i420S, _ = HipDetector.yuv_desc("i420", SH, SW)
+
+    def resized_u8(det):
+        det.set_input_resize(SH, SW, SCALE)
+        try:
+            det.run_u8(rgbS, capi.PIX_RGB, 0, n=NF)
+        finally:
+            det.set_input_resize(0, 0, 1.0)
+    return [
+        ("run_f32", lambda det: det.run(f32, NF)),
+        ("run_u8_rgb", lambda det: det.run_u8(rgb, capi.PIX_RGB, 0, n=NF)),
+        ("run_u8_nv12", lambda det: det.run_u8(nv12, capi.PIX_NV12, 0, n=NF)),
+        ("run_tensor_f16", lambda det: det.run_tensor(f16)),
+        ("run_yuv_i420", lambda det: det.run_yuv(i420, NF, d_i420)),
+        ("run_yuv_nv12_description", lambda det: det.run_yuv(nv12b, NF, d_nv12)),
+        ("run_yuv_resized_i420", lambda det: det.run_yuv_resized(i420S, NF, d_i420S, SH, SW, SCALE)),
+        ("run_tensor_resized", lambda det: det.run_tensor_resized(nchwS, SCALE)),
+        ("input_resize_run_u8", resized_u8),
+    ]
+
+
+def snapshot(det):
+    return [(det.read_pyramid(f).view(np.uint32).copy(), det.raw_detections(f).tobytes()) for f in range(NF)]
+
+
+@pytest.mark.parametrize("space", ["luv", "hsv"])
+def test_each_kind_leaves_what_a_fresh_context_leaves(space):
+    from acf_amd.detector import HipDetector
+    over = dict(isLuv=0) if space == "luv" else dict(isLuv=0, colorSpace=capi.CS_HSV)   # luv: the ingest converts; hsv: it stages planar
+    model = synth.make_model(seed=3, name="TINY", nTrees=16, **over)
+
+    def fresh():
+        return HipDetector(model, PH, PW, 3, max_batch=NF, max_hits=1 << 15)
+    seq = steps()
+    want = {}
+    for name, call in seq:
+        det = fresh()
+        call(det)
+        want[name] = snapshot(det)
+        det.close()
+    assert sum(len(d) for snap in want.values() for _, d in snap) > 0
+    assert len({snap[0][0].tobytes() for snap in want.values()}) == len(seq), "every step has frames of its own"
+    det = fresh()
+    for name, call in seq + seq[::-1]:
+        call(det)
+        for f, ((gp, gd), (wp, wd)) in enumerate(zip(snapshot(det), want[name])):
+            assert np.array_equal(gp, wp), (space, name, f, "pyramid")
+            assert gd == wd, (space, name, f, "detections")
+    det.close()
