@@ -51,6 +51,11 @@ struct RealScale
     StripPlan strip, stripPair;     // k_resample_strip: this scale's image alone / together with the next real scale's (stripPair.ok)
     float *img = nullptr, *sm = nullptr, *M = nullptr, *O = nullptr, *U = nullptr, *S = nullptr, *Mn = nullptr;
     int64_t uFloats = 0, moFloats = 0; // floats per frame of U and of M, O (room for the blocked layouts' padding)
+    // convTri's x pass as checkpoints (host_plan.h triCkIndex): where that form runs U is not needed, so U is allocated only when a
+    // call first takes a form that reads it (PyramidRun::realScale).  triForm: what the last pyramid call ran (acf_hip_get_tri_forms)
+    float* Ck = nullptr;
+    int64_t ckFloats = 0;
+    int triForm = 0;
 };
 
 // Where the frames of a call come from: what every entry that takes frames hands to pyramidBody (input_run.hip.h holds the rest of
@@ -470,6 +475,7 @@ enum : uint32_t
     FB_TILED_STAGED = 1u << 11,     // depths 1, 3, 4: the staged queue instead of the pooled tile kernel
     FB_TILED_POOLED1 = 1u << 12,    // depth 1 on float cells: the pooled tile kernel instead of the staged queue
     FB_YUV_UNFUSED = 1u << 13,      // NV12 / NV21 as k_yuv420_to_rgb8 + k_ingest_u8 instead of k_ingest_yuv420
+    FB_TRIY_STORED_U = 1u << 14,    // convTri's x pass writes the blocked plane U (instead of checkpoints replayed by k_triy_chns)
 };
 uint32_t fallbackMask()
 {
@@ -479,7 +485,7 @@ uint32_t fallbackMask()
             { "resample_no_pair", FB_RESAMPLE_NO_PAIR }, { "resample_no_up", FB_RESAMPLE_NO_UP }, { "resample_generic", FB_RESAMPLE_GENERIC },
             { "level_groups", FB_LEVEL_GROUPS }, { "ldcf_unfused", FB_LDCF_UNFUSED }, { "no_dedup", FB_NO_DEDUP }, { "no_tail_codes", FB_NO_TAIL_CODES },
             { "tail3", FB_TAIL3 }, { "tiled_staged", FB_TILED_STAGED }, { "tiled_pooled1", FB_TILED_POOLED1 },
-            { "yuv_unfused", FB_YUV_UNFUSED } };
+            { "yuv_unfused", FB_YUV_UNFUSED }, { "triy_stored_u", FB_TRIY_STORED_U } };
         uint32_t m = 0;
         const char* e = getenv("ACF_HIP_FORCE_FALLBACK");
         std::string s = e ? e : "";
@@ -583,6 +589,12 @@ int devAlloc(acf_hip_ctx* c, T** out, size_t count)
     c->allocs.push_back(p);
     *out = reinterpret_cast<T*>(p);
     return ACF_HIP_OK;
+}
+
+// convTri's plane U of a real scale, for `batch` frames (at plan time, or when a call first takes a form that reads it)
+int allocU(acf_hip_ctx* c, RealScale& rs, int batch)
+{
+    return devAlloc(c, &rs.U, size_t(batch) * size_t(rs.uFloats));
 }
 
 template <class T>
@@ -884,35 +896,51 @@ static int64_t moBlockedFloats(int h, int w)
 
 struct TriPlan
 {
-    bool vecX, doFuse, blocked;
+    bool vecX, doFuse, blocked, ck;
 };
 
 // Which forms convTri(M) + the channel cells of a level take: the vector x pass, the fused y pass + cells, and the blocked
 // layout of M, O and U (kernels.hip.h, k_tri_x5v) — possible when gradMag, the x pass and the fused y pass are all the vector
 // forms and the buffers have room for the blocks' padding (A/B: ACF_HIP_MOU_PLAIN).  gradVec: k_grad_mag_vec writes M and O.
+// ck: the x pass leaves checkpoints and k_triy_chns replays it (M and O blocked as before, no U) — wherever the blocked forms apply
+// and the checkpoint buffer has room; otherwise blocked needs a U buffer that holds the blocks (a null U holds nothing).
 static TriPlan triPlan(const float* in, const float* U, int h, int w, int rad, int64_t fs, const ChnsArgs* fuse, int64_t uCapacity, int64_t moCapacity,
-    bool gradVec)
+    bool gradVec, const float* Ck = nullptr, int64_t ckCapacity = 0)
 {
-    const bool noFuse = fallbackForced(FB_TRIY_UNFUSED), plain = fallbackForced(FB_MOU_PLAIN);
+    const bool noFuse = fallbackForced(FB_TRIY_UNFUSED), plain = fallbackForced(FB_MOU_PLAIN), storedU = fallbackForced(FB_TRIY_STORED_U);
     TriPlan t;
     t.vecX = rad == 5 && h % 4 == 0 && w >= 48 && fs % 4 == 0 && ((uintptr_t(in) | uintptr_t(U)) & 15) == 0;
     t.doFuse = fuse && !noFuse && rad == 5 && h % 4 == 0 && h >= 48 && w % 4 == 0 && fs % 4 == 0 && (uintptr_t(U) & 15) == 0 && fuse->doNorm &&
         !fuse->Mn && (fuse->colorDone || !fuse->colorEnabled) && (fuse->magEnabled || fuse->histEnabled) && fuse->nOrients <= 12 &&
         ((uintptr_t(fuse->M) | uintptr_t(fuse->O)) & 15) == 0;
-    t.blocked = t.vecX && t.doFuse && gradVec && !plain && uCapacity >= uBlockedFloats(h, w) && moCapacity >= moBlockedFloats(h, w);
+    const bool blockedMO = t.vecX && t.doFuse && gradVec && !plain && moCapacity >= moBlockedFloats(h, w);
+    t.ck = blockedMO && !storedU && Ck && (uintptr_t(Ck) & 15) == 0 && ckCapacity >= triCkFloats(h, w);
+    t.blocked = t.ck || (blockedMO && U && uCapacity >= uBlockedFloats(h, w));
     return t;
 }
 
 using TriX5Kernel = void (*)(const float*, float*, int, int, int64_t, int64_t, int, int);
 using TriyChnsKernel = void (*)(const float*, ChnsArgs, int64_t, int);
 
-static TriX5Kernel triX5Kernel(bool ut)
+static TriX5Kernel triX5Kernel(bool ut, bool ck)
 {
+    if (ck)
+    {
+        return k_tri_x5v<true, true>;
+    }
     return ut ? k_tri_x5v<true> : k_tri_x5v<false>;
 }
 
-static TriyChnsKernel triyChnsKernel(bool maxO6, bool ut, bool x86)
+static TriyChnsKernel triyChnsKernel(bool maxO6, bool ut, bool x86, bool ck)
 {
+    if (ck)
+    {
+        if (maxO6)
+        {
+            return x86 ? k_triy_chns<6, true, true, true> : k_triy_chns<6, true, false, true>;
+        }
+        return x86 ? k_triy_chns<12, true, true, true> : k_triy_chns<12, true, false, true>;
+    }
     if (maxO6)
     {
         if (ut)
@@ -931,21 +959,28 @@ static TriyChnsKernel triyChnsKernel(bool maxO6, bool ut, bool x86)
 // uCapacity / moCapacity: floats per frame the U and the M, O buffers hold (>= fs); blocked: M and O ARE in the blocked layout
 // (the caller ran k_grad_mag_vec<true> after asking triPlan)
 // xDone: U is there already (k_smooth_grad_tri wrote it, blocked)
+// ck: the checkpoint form (Ck, ckCapacity: its buffer); the caller asked triPlan with the same arguments
 int launchTri(acf_hip_ctx* c, hipStream_t st, const float* in, float* U, float* S, int h, int w, int rad, int64_t fs, int nFrames, ChnsArgs* fuse = nullptr,
-    bool* fused = nullptr, int64_t uCapacity = 0, int64_t moCapacity = 0, bool blocked = false, bool xDone = false)
+    bool* fused = nullptr, int64_t uCapacity = 0, int64_t moCapacity = 0, bool blocked = false, bool xDone = false, float* Ck = nullptr,
+    int64_t ckCapacity = 0, bool ck = false)
 {
     if (rad > 15)
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, "convTri: radius > 15");
     }
-    const TriPlan tp = triPlan(in, U, h, w, rad, fs, fuse, uCapacity, moCapacity, blocked);
-    if (blocked && !tp.blocked)
+    const TriPlan tp = triPlan(in, U, h, w, rad, fs, fuse, uCapacity, moCapacity, blocked, Ck, ckCapacity);
+    if ((blocked && !tp.blocked) || ck != (blocked && tp.ck))
     {
         return fail(c, ACF_HIP_E_INVALID, "convTri: blocked M/O without the kernels that read them");
     }
+    if (!ck && !U)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "convTri: no U buffer for the stored form");
+    }
     const bool vecX = tp.vecX, doFuse = tp.doFuse, ut = blocked;
-    const int nyb = (h + 8 + 15) / 16, nybM = (h + 15) / 16;
-    const int64_t ufs = uBlockedFloats(h, w), mfs = moBlockedFloats(h, w);
+    const int nyb = triCkBlockRows(h), nybM = (h + 15) / 16; // (U's blocks and the checkpoints' have the same rows)
+    const int64_t ufs = ck ? triCkFloats(h, w) : uBlockedFloats(h, w), mfs = moBlockedFloats(h, w);
+    float* const xOut = ck ? Ck : U; // what the x pass leaves and the y pass takes
     if (xDone)
     {
         if (!ut || !doFuse)
@@ -958,7 +993,7 @@ int launchTri(acf_hip_ctx* c, hipStream_t st, const float* in, float* U, float* 
         prof(c, st, "k_tri_x");
         if (vecX)
         {
-            hipLaunchKernelGGL(triX5Kernel(ut), dim3(cdiv(h / 4, 64), 1, nFrames), dim3(64), 0, st, in, U, h, w,
+            hipLaunchKernelGGL(triX5Kernel(ut, ck), dim3(cdiv(h / 4, 64), 1, nFrames), dim3(64), 0, st, in, xOut, h, w,
                 ut ? mfs : fs, ut ? ufs : fs, ut ? nyb : 0, ut ? nybM : 0);
         }
         else
@@ -979,8 +1014,8 @@ int launchTri(acf_hip_ctx* c, hipStream_t st, const float* in, float* U, float* 
             fuse->m_fs = mfs;
             fuse->nybM = nybM;
         }
-        hipLaunchKernelGGL(triyChnsKernel(fuse->nOrients <= 6, ut, fuse->x86 != nullptr), dim3(cdiv(w, 256), 1, nFrames), dim3(256), 0, st,
-            (const float*)U, *fuse, ut ? ufs : fs, ut ? nyb : 0);
+        hipLaunchKernelGGL(triyChnsKernel(fuse->nOrients <= 6, ut, fuse->x86 != nullptr, ck), dim3(cdiv(w, 256), 1, nFrames), dim3(256), 0, st,
+            (const float*)xOut, *fuse, ut ? ufs : fs, ut ? nyb : 0);
         LAUNCHCHK(c, "k_triy_chns");
         *fused = true;
         return ACF_HIP_OK;
@@ -1872,6 +1907,33 @@ int acf_hip_get_repairs(acf_hip_ctx* c, int64_t out[4])
             out[i] += k->repairs[i];
         }
     }
+    return ACF_HIP_OK;
+}
+
+int acf_hip_get_tri_forms(const acf_hip_ctx* c, int32_t* out, int cap, int* n)
+{
+    if (int rc = needPlanRead(c, "get_tri_forms")) return rc;
+    if (!n || (cap > 0 && !out))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    const acf_hip_ctx* s = c->kids.empty() ? c : c->kids[0]; // (sub-batch children hold the buffers; they all run the same forms)
+    *n = int(s->real.size());
+    for (int i = 0; i < *n && i < cap; i++)
+    {
+        out[i] = s->real[size_t(i)].triForm;
+    }
+    return ACF_HIP_OK;
+}
+
+int acf_hip_tri_ck_layout(int h, int w, int x, int y, int64_t out[2])
+{
+    if (!out || h <= 0 || w <= 0 || x < 0 || x >= w || y < 0 || y >= h)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    out[0] = triCkIndex(x, y, triCkBlockRows(h));
+    out[1] = triCkFloats(h, w);
     return ACF_HIP_OK;
 }
 

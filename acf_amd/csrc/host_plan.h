@@ -170,6 +170,31 @@ struct ResizeTables
 void resizeDims(int rows, int cols, double scale, int& drows, int& dcols);
 int buildResizeTables(int rows, int cols, double scale, ResizeTables& t);
 
+// ---- convTri's x pass as checkpoints (k_tri_x5v<true, true>, k_smooth_grad_tri<.., CK>, k_triy_chns<.., CK>) --------------------
+// Instead of the plane U the x pass leaves its running sums (T, U) once per row and 16-column segment: the state the segment's
+// replay in the y kernel starts from (after column (x & ~15) - 1; segment 0: after column 0).  Per frame
+//     [x >> 6][(y + 8) >> 4][(x >> 4) & 3][(y + 8) & 15][2]
+// so that the 16 rows x 4 segments a wave of the y kernel takes per step (rows J + 8 .. J + 23 of its 64 columns) are 512
+// contiguous bytes.  nyb = triCkBlockRows(h); the index is the sum of its column part (y = -8) and its row part (x = 0).
+#if defined(__HIPCC__)
+#define ACF_PLAN_HD __host__ __device__
+#else
+#define ACF_PLAN_HD
+#endif
+ACF_PLAN_HD constexpr int triCkBlockRows(int h)
+{
+    return (h + 8 + 15) / 16;
+}
+ACF_PLAN_HD constexpr int64_t triCkIndex(int x, int y, int nyb)
+{
+    return ((int64_t(x >> 6) * nyb + ((y + 8) >> 4)) * 4 + ((x >> 4) & 3)) * 32 + ((y + 8) & 15) * 2;
+}
+// floats per frame
+ACF_PLAN_HD constexpr int64_t triCkFloats(int h, int w)
+{
+    return int64_t((w + 63) / 64) * triCkBlockRows(h) * 128;
+}
+
 int colorPlanes(const acf_hip_params& p);
 int numChannels(const acf_hip_params& p);
 int numChannels(const acf_hip_params& p, int dcol); // (dcol colour planes: acf_hip_chns_compute's 1-plane image keeps one)

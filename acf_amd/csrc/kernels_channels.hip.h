@@ -219,7 +219,7 @@ __global__ void __launch_bounds__(256) k_gm_inv_selftest(uint32_t first, unsigne
         atomicMin(&bad[1], lo);
     }
 }
-template <bool FULL, bool HALF, bool SHRINK, bool GRAD = false, bool TRIX = false, bool ARITH = false>
+template <bool FULL, bool HALF, bool SHRINK, bool GRAD = false, bool TRIX = false, bool ARITH = false, bool CK = false>
 __device__ __forceinline__ void smooth_vec_body(const SmoothVecArgs& a, float* lds, int z, const float* acosT = nullptr, const uint2* x86G = nullptr, float x86K = 0.f)
 {
     const int h = a.h, w = a.w, nq = h >> 2;
@@ -271,10 +271,19 @@ __device__ __forceinline__ void smooth_vec_body(const SmoothVecArgs& a, float* l
         {
             ring[m] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        tUq = a.tU + f * a.u_fs + int64_t(((uint32_t(4 * qc + 8) >> 4) << 10) + (uint32_t(4 * qc + 8) & 15u));
+        // CK: tU is the checkpoint buffer (k_tri_x5v<true, true>: the state after column 16 S - 1 is segment S's entry, segment 0's the
+        // state after column 0) — a (T, U) store on every 16th column instead of a U store on each
+        tUq = CK ? a.tU + f * a.u_fs + acfhip::triCkIndex(0, 4 * qc, a.nybU)
+                 : a.tU + f * a.u_fs + int64_t(((uint32_t(4 * qc + 8) >> 4) << 10) + (uint32_t(4 * qc + 8) & 15u));
+    }
+#define SV_TRI_CK_ST(OK_, COL1_)                                                                  \
+    {                                                                                             \
+        float* p_ = (OK_) ? tUq + acfhip::triCkIndex((COL1_), -8, a.nybU) : a.dump + 4 * lane;    \
+        *reinterpret_cast<float4*>(p_) = make_float4(tT[0], tUu[0], tT[1], tUu[1]);               \
+        *reinterpret_cast<float4*>((OK_) ? p_ + 4 : p_) = make_float4(tT[2], tUu[2], tT[3], tUu[3]); \
     }
 #define SV_TRI_ADDR(col) (tUq + int64_t((((uint32_t(col) >> 6) * uint32_t(a.nybU)) << 10) + ((uint32_t(col) & 63u) << 4)))
-#define SV_TRI_STEP(A_, B_, C_, J_, OKJ_)                                                          \
+#define SV_TRI_STEP(A_, B_, C_, J_, OKJ_, CKJ_)                                                    \
     {                                                                                             \
         const float a4_[4] = { A_.x, A_.y, A_.z, A_.w };                                          \
         const float b4_[4] = { B_.x, B_.y, B_.z, B_.w };                                          \
@@ -284,7 +293,14 @@ __device__ __forceinline__ void smooth_vec_body(const SmoothVecArgs& a, float* l
             tT[k] += a4_[k] + b4_[k] - 2 * c4_[k];                                                \
             tUu[k] += triN * tT[k];                                                               \
         }                                                                                         \
-        *reinterpret_cast<float4*>((valid && (OKJ_)) ? SV_TRI_ADDR(J_) : a.dump + 4 * lane) = make_float4(tUu[0], tUu[1], tUu[2], tUu[3]); \
+        if (!CK)                                                                                  \
+        {                                                                                         \
+            *reinterpret_cast<float4*>((valid && (OKJ_)) ? SV_TRI_ADDR(J_) : a.dump + 4 * lane) = make_float4(tUu[0], tUu[1], tUu[2], tUu[3]); \
+        }                                                                                         \
+        else if (CKJ_) /* column J_ ends a segment */                                             \
+        {                                                                                         \
+            SV_TRI_CK_ST(valid && (OKJ_) && (J_) + 1 < w, (J_) + 1)                               \
+        }                                                                                         \
     }
     // M's column x_ (slot SLOT = x_ & 15, compile-time) has just been computed
 #define SV_TRI_PUSH(SLOT, x_, mo)                                                                 \
@@ -293,7 +309,7 @@ __device__ __forceinline__ void smooth_vec_body(const SmoothVecArgs& a, float* l
         const float4 mv_ = make_float4(mo[0], mo[1], mo[2], mo[3]);                               \
         ring[s_] = mv_;                                                                           \
         /* (slots <= 5 and 15 are also those of the chain's first columns, where there is no output column yet) */ \
-        SV_TRI_STEP(ring[(s_ - 12) & 15], mv_, ring[(s_ - 6) & 15], (x_) - 5, (s_ <= 5 || s_ == 15) ? (x_) >= 6 : true) \
+        SV_TRI_STEP(ring[(s_ - 12) & 15], mv_, ring[(s_ - 6) & 15], (x_) - 5, (s_ <= 5 || s_ == 15) ? (x_) >= 6 : true, s_ == 4) \
         if (s_ == 5 && (x_) == 5)                                                                 \
         {                                                                                         \
             const float4 e0_ = ring[0];                                                           \
@@ -312,7 +328,14 @@ __device__ __forceinline__ void smooth_vec_body(const SmoothVecArgs& a, float* l
                 tUu[k] = triN * (2 * tUu[k] - tT[k]);                                             \
                 tT[k] = 0;                                                                        \
             }                                                                                     \
-            *reinterpret_cast<float4*>(valid ? SV_TRI_ADDR(0) : a.dump + 4 * lane) = make_float4(tUu[0], tUu[1], tUu[2], tUu[3]); \
+            if (CK)                                                                               \
+            {                                                                                     \
+                SV_TRI_CK_ST(valid, 0)                                                            \
+            }                                                                                     \
+            else                                                                                  \
+            {                                                                                     \
+                *reinterpret_cast<float4*>(valid ? SV_TRI_ADDR(0) : a.dump + 4 * lane) = make_float4(tUu[0], tUu[1], tUu[2], tUu[3]); \
+            }                                                                                     \
             _Pragma("unroll") for (int m_ = 0; m_ < 6; m_++)                                      \
             {                                                                                     \
                 ring[10 + m_] = ring[5 - m_];                                                     \
@@ -525,7 +548,7 @@ __device__ __forceinline__ void smooth_vec_body(const SmoothVecArgs& a, float* l
                 for (int j = w - 6; j < w; j++)
                 {
                     const float4 ta = SV_TRI_LD(j - 7), tc = SV_TRI_LD(j - 1), tb = SV_TRI_LD(j > w - 6 ? 2 * w - 6 - j : j + 5);
-                    SV_TRI_STEP(ta, tb, tc, j, true)
+                    SV_TRI_STEP(ta, tb, tc, j, true, (j & 15) == 15)
                 }
 #undef SV_TRI_LD
             }
@@ -553,6 +576,7 @@ __device__ __forceinline__ void smooth_vec_body(const SmoothVecArgs& a, float* l
 #undef SV_GRAD
 #undef SV_TRI_PUSH
 #undef SV_TRI_STEP
+#undef SV_TRI_CK_ST
 #undef SV_TRI_ADDR
 #undef SV_LOAD
 #undef SV_COL
@@ -649,7 +673,8 @@ __global__ void __launch_bounds__(64 * SV_MAXW) k_smooth_grad(SmoothVecArgs a, u
 // k_smooth_grad with convTri's x pass over M on the same chain (smooth_vec_body's TRIX): M is written once and not read back by a
 // separate x pass (8.3 MB per 1080p frame and one launch less per scale).  One segment per plane; up to 8 waves (1920 rows): the
 // ring of sixteen M columns costs 64 registers, which a workgroup of ten waves cannot have.
-template <bool HALF, bool ARITH = false>
+// CK: the x pass leaves checkpoints, not U (smooth_vec_body, k_tri_x5v).
+template <bool HALF, bool ARITH = false, bool CK = false>
 __global__ void __launch_bounds__(512) k_smooth_grad_tri(SmoothVecArgs a, uint32_t fullMask)
 {
     extern __shared__ float lds[]; // (k_smooth_grad's)
@@ -673,11 +698,11 @@ __global__ void __launch_bounds__(512) k_smooth_grad_tri(SmoothVecArgs a, uint32
     __syncthreads();
     if ((fullMask >> z) & 1u)
     {
-        smooth_vec_body<true, HALF, true, true, true, ARITH>(a, lds, z, acosL + 10010, x86G, x86K);
+        smooth_vec_body<true, HALF, true, true, true, ARITH, CK>(a, lds, z, acosL + 10010, x86G, x86K);
     }
     else
     {
-        smooth_vec_body<false, HALF, true, true, true, ARITH>(a, lds, z, acosL + 10010, x86G, x86K);
+        smooth_vec_body<false, HALF, true, true, true, ARITH, CK>(a, lds, z, acosL + 10010, x86G, x86K);
     }
 }
 
@@ -1101,9 +1126,18 @@ __global__ void __launch_bounds__(256) k_tri_x(const float* __restrict__ in, flo
 // next column's pieces complete the lines in L2.  ufs: frame stride of U in floats, nyb = (h + 8 + 15) / 16.
 // With UT the INPUT is blocked too (unshifted: [x >> 6][y >> 4][x & 63][y & 15], frame stride fs, nybM = ceil(h / 16)), as
 // k_grad_mag_vec<true> writes it: k_triy_chns's cells then take a block's M and O in one step as well.
-template <bool UT>
+//
+// CK (with UT): U does not leave at all.  The recurrence is exactly resumable — from (T, U) after column c the same operations
+// on the same M give the same bits at c + 1, c + 2, ... — so only CHECKPOINTS leave, one per row and 16-column segment, and
+// k_triy_chns<.., CK> re-runs a segment's column steps over the M blocks it reads anyway.  Uo is then the checkpoint buffer
+// (triCkIndex, host_plan.h: per frame [x >> 6][(y + 8) >> 4][(x >> 4) & 3][(y + 8) & 15][2] = (T, U); ufs = its frame stride): the entry of
+// segment x >> 4 is the state its replay STARTS from — after column (x & ~15) - 1, and for segment 0 after column 0 (T = 0,
+// U = the head's value: the replay takes column 0 as it is and steps through columns 1 .. 15, reflected left taps included).
+// A lane's four rows are 32 contiguous bytes of an entry block.
+template <bool UT, bool CK = false>
 __global__ void __launch_bounds__(64) k_tri_x5v(const float* __restrict__ in, float* __restrict__ Uo, int h, int w, int64_t fs, int64_t ufs, int nyb, int nybM)
 {
+    static_assert(!CK || UT, "checkpoints go with the blocked layout");
     const int h4 = h >> 2;
     const int q = blockIdx.x * 64 + threadIdx.x;
     if (q >= h4)
@@ -1112,15 +1146,30 @@ __global__ void __launch_bounds__(64) k_tri_x5v(const float* __restrict__ in, fl
     }
     const float* __restrict__ I = UT ? in + int64_t(blockIdx.z) * fs + ((uint32_t(4 * q) >> 4) << 10) + (uint32_t(4 * q) & 15u)
                                      : in + int64_t(blockIdx.z) * fs + 4 * q;
-    float* __restrict__ Uc = UT ? Uo + int64_t(blockIdx.z) * ufs + ((uint32_t(4 * q + 8) >> 4) << 10) + (uint32_t(4 * q + 8) & 15u)
+    float* __restrict__ Uc = CK ? Uo + int64_t(blockIdx.z) * ufs + acfhip::triCkIndex(0, 4 * q, nyb)
+                           : UT ? Uo + int64_t(blockIdx.z) * ufs + ((uint32_t(4 * q + 8) >> 4) << 10) + (uint32_t(4 * q + 8) & 15u)
                                 : Uo + int64_t(blockIdx.z) * fs + 4 * q;
     constexpr int r = 6;
     const float nrm = 1.0f / (r * r * r * r);
 #define TXV_LD(col)                                                                                                                 \
     (*reinterpret_cast<const float4*>(UT ? I + (((uint32_t(col) >> 6) * uint32_t(nybM)) << 10) + ((uint32_t(col) & 63u) << 4) : I + int64_t(col) * h))
-#define TXV_ST(col, v)                                                                                                              \
-    (*reinterpret_cast<float4*>(UT ? Uc + (((uint32_t(col) >> 6) * uint32_t(nyb)) << 10) + ((uint32_t(col) & 63u) << 4) : Uc + int64_t(col) * h) = (v))
     float T[4], U[4];
+    // CK: the state after column col is the entry of the segment that starts at col + 1 (and of segment 0 after column 0)
+#define TXV_ST(col, v)                                                                                                              \
+    if (CK)                                                                                                                         \
+    {                                                                                                                               \
+        const int c_ = (col);                                                                                                       \
+        if (c_ == 0 || ((c_ & 15) == 15 && c_ + 1 < w))                                                                             \
+        {                                                                                                                           \
+            float* p_ = Uc + acfhip::triCkIndex(c_ + 1, -8, nyb);                                                                        \
+            *reinterpret_cast<float4*>(p_) = make_float4(T[0], U[0], T[1], U[1]);                                                   \
+            *reinterpret_cast<float4*>(p_ + 4) = make_float4(T[2], U[2], T[3], U[3]);                                               \
+        }                                                                                                                           \
+    }                                                                                                                               \
+    else                                                                                                                            \
+    {                                                                                                                               \
+        *reinterpret_cast<float4*>(UT ? Uc + (((uint32_t(col) >> 6) * uint32_t(nyb)) << 10) + ((uint32_t(col) & 63u) << 4) : Uc + int64_t(col) * h) = (v); \
+    }
     {
         const float4 v0 = TXV_LD(0);
         U[0] = T[0] = v0.x, U[1] = T[1] = v0.y, U[2] = T[2] = v0.z, U[3] = T[3] = v0.w;
@@ -1555,10 +1604,29 @@ __device__ __forceinline__ void chns_load_vec(const float* __restrict__ p, float
 // ------------------------------------------------------------------------
 // UT: U comes in k_tri_x5v<true>'s blocked layout (ufs, nyb as there): a step's rows are four 16-byte loads per lane from one
 // contiguous 4 KB block, already in the lane that owns the column.
-template <int MAXO, bool UT, bool ARITH = false>
+//
+// CK (with UT): U does not come from memory at all.  Ui holds the x pass's CHECKPOINTS (host_plan.h triCkIndex; ufs = their frame
+// stride, nyb as for U) and the wave re-runs convTri's x pass for the 16 rows x 64 columns of a step itself (TY_REPLAY):
+//   * lane = (row rl = lane & 15, segment sg = lane >> 4): the lane takes (T, U) of its row at the segment's start — the wave's
+//     64 entries are 512 contiguous bytes — and runs the segment's 16 column steps, k_tri_x5v's operations in its order:
+//     column i from M[i - 7] (i <= 6: the reflected M[6 - i]), M[i - 1] and M[i + 5] (i > w - 6: the reflected M[2 w - 6 - i]);
+//     column 0 is the checkpoint's U itself.  Same operations on the same M from the same state: the same bits as the plane held.
+//   * M for that: rows R0 .. R0 + 15 of columns x0 - 7 .. x0 + 72 (clamped into the plane; 76 of them are used), five 16-byte
+//     loads per lane requested a step ahead like U's were, staged in the wave's LDS slot with pitch 17 (a lane's reads are
+//     conflict-free: bank = 16 sg + rl + const).  Rows outside the plane (the head's block starts at row -8, the tail's ends
+//     past h) are clamped quads: their results are never used.
+//   * hand-over: the lanes hold all M they need in registers, then the SAME slot takes the 64 x 16 results as [column][row]
+//     (pitch TY_PITCH, plus 16 floats per segment so that the four segments' stores fall into different banks) and lane =
+//     column reads its 16 rows back as four 16-byte loads — what TY_FETCH / TY_TAKE gave.
+// The head (rows 0 .. 20) and the tail take their rows from replayed blocks in registers instead of from memory.
+// LDS: the slot grows from 64 * TY_PITCH to 80 * 17 floats per wave (57,600 B per workgroup at MAXO = 6).
+template <int MAXO, bool UT, bool ARITH = false, bool CK = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_triy_chns(const float* __restrict__ Ui, ChnsArgs ca, int64_t ufs, int nyb)
 {
-    __shared__ float ty_lds[4][UT ? 1 : 2][64 * TY_PITCH];
+    static_assert(!CK || UT, "checkpoints go with the blocked layout");
+    constexpr int MT_P = 17, MT_W = 80; // the replay's M tile: row pitch of a column, columns
+    static_assert(MT_W * MT_P >= 64 * TY_PITCH + 48, "the hand-over shares the tile's slot");
+    __shared__ float ty_lds[4][UT ? 1 : 2][CK ? MT_W * MT_P : 64 * TY_PITCH];
     // STG: the cells of FOUR steps (16 cell rows of the wave's 16 cell columns, per channel) are collected in LDS and leave as 64
     // contiguous bytes per cell column and channel — a step alone writes 16-byte pieces, which L2 evicts before the next steps
     // complete their lines: 14.7 MB written per 1080p frame for 4.8 MB of cells (WRITE_SIZE, profiles/r05_ab/triy_nt_level_fm.txt)
@@ -1600,6 +1668,114 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     constexpr int r = 6, r0 = 5, r1 = 7, h0 = 7;
     const int r2 = 2 * h - r, h1 = h - r + 1;
     float t, u;
+    // ---- CK: the replay -------------------------------------------------------------------------------------------------------
+    // tile column ci = e >> 2 of load e = 64 q + lane is image column x0 - 7 + ci (clamped), its quad e & 3 rows R0 + 4 (e & 3) ..
+    uint32_t mtOff[5];
+    int mtRq[5];
+    const float* __restrict__ ckL = U0 + acfhip::triCkIndex(x0 + 16 * cl, rl - 8, nyb); // the lane's entry in block row 0
+    const float* __restrict__ MfR = ca.M + int64_t(blockIdx.z) * fs;
+    const float nrmX = 1.0f / (6 * 6 * 6 * 6);
+    if (CK)
+    {
+#pragma unroll
+        for (int q = 0; q < 5; q++)
+        {
+            const int e = 64 * q + lane;
+            const int X = min(max(x0 - 7 + (e >> 2), 0), w - 1);
+            mtOff[q] = (((uint32_t(X) >> 6) * uint32_t(ca.nybM)) << 10) + ((uint32_t(X) & 63u) << 4);
+            mtRq[q] = 4 * (e & 3);
+        }
+    }
+    float4 mt[5];
+    float2 ckv;
+    // request rows R0 .. R0 + 15 (R0 % 16 == 8): the M tile and the lane's checkpoint
+#define TY_REPLAY_REQ(R0)                                                                                   \
+    {                                                                                                       \
+        _Pragma("unroll") for (int q = 0; q < 5; q++)                                                       \
+        {                                                                                                   \
+            const int yq_ = min(max((R0) + mtRq[q], 0), h - 4);                                             \
+            mt[q] = *reinterpret_cast<const float4*>(MfR + mtOff[q] + ((uint32_t(yq_) >> 4) << 10) + (uint32_t(yq_) & 15u)); \
+        }                                                                                                   \
+        /* (h % 16 == 8: the tail's block starts at row h, one block row past the buffer — none of its rows is used) */ \
+        ckv = *reinterpret_cast<const float2*>(ckL + min(uint32_t((R0) + 8) >> 4, uint32_t(nyb - 1)) * 128u); \
+    }
+    // ... and run them: N[q] = rows R0 + 4q .. R0 + 4q + 3 of this lane's column (lane = column again)
+#define TY_REPLAY_RUN(N)                                                                                    \
+    {                                                                                                       \
+        _Pragma("unroll") for (int q = 0; q < 5; q++)                                                       \
+        {                                                                                                   \
+            float* d_ = inb + ((64 * q + lane) >> 2) * MT_P + mtRq[q];                                      \
+            d_[0] = mt[q].x, d_[1] = mt[q].y, d_[2] = mt[q].z, d_[3] = mt[q].w;                             \
+        }                                                                                                   \
+        __builtin_amdgcn_wave_barrier();                                                                    \
+        float m_[28], av_[7], bv_[16];                                                                      \
+        _Pragma("unroll") for (int j = 0; j < 28; j++)                                                      \
+        {                                                                                                   \
+            m_[j] = inb[(16 * cl + j) * MT_P + rl]; /* image column x0 + 16 cl + j - 7 */                   \
+        }                                                                                                   \
+        _Pragma("unroll") for (int k = 0; k < 7; k++)                                                       \
+        {                                                                                                   \
+            av_[k] = m_[k];                                                                                 \
+        }                                                                                                   \
+        if (x0 == 0) /* wave-uniform: columns 1 .. 6 take the reflected left tap M[6 - i] (tile column 13 - i) */ \
+        {                                                                                                   \
+            _Pragma("unroll") for (int k = 1; k < 7; k++)                                                   \
+            {                                                                                               \
+                const float v_ = inb[(13 - k) * MT_P + rl];                                                 \
+                av_[k] = cl == 0 ? v_ : av_[k];                                                             \
+            }                                                                                               \
+        }                                                                                                   \
+        _Pragma("unroll") for (int k = 0; k < 16; k++)                                                      \
+        {                                                                                                   \
+            bv_[k] = m_[k + 12];                                                                            \
+        }                                                                                                   \
+        if (x0 + 63 > w - 6) /* wave-uniform: columns i > w - 6 take the reflected right tap M[2 w - 6 - i] */ \
+        {                                                                                                   \
+            _Pragma("unroll") for (int k = 0; k < 16; k++)                                                  \
+            {                                                                                               \
+                const int i_ = x0 + 16 * cl + k;                                                            \
+                const int ci_ = min(max(2 * w + 1 - i_ - x0, 0), MT_W - 1); /* (columns >= w: anything inside the tile) */ \
+                const float v_ = inb[ci_ * MT_P + rl];                                                      \
+                bv_[k] = i_ > w - 6 ? v_ : bv_[k];                                                          \
+            }                                                                                               \
+        }                                                                                                   \
+        __builtin_amdgcn_wave_barrier();                                                                    \
+        float tx_ = ckv.x, ux_ = ckv.y;                                                                     \
+        float* ho_ = inb + (16 * cl) * TY_PITCH + 16 * cl + rl;                                             \
+        _Pragma("unroll") for (int k = 0; k < 16; k++)                                                      \
+        {                                                                                                   \
+            const float a_ = k < 7 ? av_[k < 7 ? k : 0] : m_[k];                                            \
+            const float tn_ = tx_ + ((a_ + bv_[k]) - 2 * m_[k + 6]);                                        \
+            const float un_ = ux_ + nrmX * tn_;                                                             \
+            const bool col0_ = k == 0 && x0 == 0 && cl == 0; /* column 0 is the checkpoint itself */        \
+            tx_ = col0_ ? tx_ : tn_;                                                                        \
+            ux_ = col0_ ? ux_ : un_;                                                                        \
+            ho_[k * TY_PITCH] = ux_;                                                                        \
+        }                                                                                                   \
+        __builtin_amdgcn_wave_barrier();                                                                    \
+        _Pragma("unroll") for (int q = 0; q < 4; q++)                                                       \
+        {                                                                                                   \
+            N[q] = *reinterpret_cast<const float4*>(inb + lane * TY_PITCH + 16 * cl + 4 * q);               \
+        }                                                                                                   \
+        __builtin_amdgcn_wave_barrier();                                                                    \
+    }
+    float uh[32]; // CK: rows -8 .. 23 of the lane's column (rows < 0: unused)
+    if (CK)
+    {
+        float4 n0[4], n1[4];
+        TY_REPLAY_REQ(-8);
+        TY_REPLAY_RUN(n0);
+        TY_REPLAY_REQ(8);
+        TY_REPLAY_RUN(n1);
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+        {
+            uh[4 * q] = n0[q].x, uh[4 * q + 1] = n0[q].y, uh[4 * q + 2] = n0[q].z, uh[4 * q + 3] = n0[q].w;
+            uh[16 + 4 * q] = n1[q].x, uh[17 + 4 * q] = n1[q].y, uh[18 + 4 * q] = n1[q].z, uh[19 + 4 * q] = n1[q].w;
+        }
+    }
+#undef TY_U
+#define TY_U(j) (CK ? uh[(j) + 8] : UT ? colT[((uint32_t((j) + 8) >> 4) << 10) + (uint32_t((j) + 8) & 15u)] : colP[(j)])
     // rows 0..15: the reference's head (reflected taps), straight from memory
     u = t = TY_U(0);
 #pragma unroll
@@ -1838,8 +2014,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     float4 g4[4];
     float4 nx[4];
     {
-        TY_FETCH(g, g4, 8);
-        TY_TAKE(g, g4, nx); // rows 8..23
+        if (CK)
+        {
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+            {
+                nx[q] = make_float4(uh[16 + 4 * q], uh[17 + 4 * q], uh[18 + 4 * q], uh[19 + 4 * q]);
+            }
+        }
+        else
+        {
+            TY_FETCH(g, g4, 8);
+            TY_TAKE(g, g4, nx); // rows 8..23
+        }
         ring[8] = nx[0].x, ring[9] = nx[0].y, ring[10] = nx[0].z, ring[11] = nx[0].w;
         ring[12] = nx[1].x, ring[13] = nx[1].y, ring[14] = nx[1].z, ring[15] = nx[1].w;
         ring[0] = nx[2].x, ring[1] = nx[2].y, ring[2] = nx[2].z, ring[3] = nx[2].w;
@@ -1849,8 +2036,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int lastFast = h - 24; // J + 23 <= h - 1 and every j <= J + 15 < h1
     if (J <= lastFast)
     {
-        TY_FETCH(g, g4, J + 8);
-        TY_TAKE(g, g4, nx); // rows J+8 .. J+23
+        if (CK)
+        {
+            TY_REPLAY_REQ(J + 8);
+            TY_REPLAY_RUN(nx);
+        }
+        else
+        {
+            TY_FETCH(g, g4, J + 8);
+            TY_TAKE(g, g4, nx); // rows J+8 .. J+23
+        }
     }
 #define TY_ITER(CO, NO)                                                                             \
     {                                                                                                       \
@@ -1858,7 +2053,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         TY_O_FETCH(NO, J + 16); /* the NEXT block's orientations */                                         \
         if (more)                                                                                           \
         {                                                                                                   \
-            TY_FETCH(g, g4, J + 24); /* next iteration's rows, in flight during this iteration's recurrence */  \
+            if (CK)                                                                                         \
+            {                                                                                               \
+                TY_REPLAY_REQ(J + 24);                                                                      \
+            }                                                                                               \
+            else                                                                                            \
+            {                                                                                               \
+                TY_FETCH(g, g4, J + 24); /* next iteration's rows, in flight during this iteration's recurrence */  \
+            }                                                                                               \
         }                                                                                                   \
         _Pragma("unroll") for (int q = 0; q < 4; q++)                                                       \
         {                                                                                                   \
@@ -1884,7 +2086,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         TY_CELLS(CO, J, 16, J + 16);                                                                         \
         if (more)                                                                                           \
         {                                                                                                   \
-            TY_TAKE(g, g4, nx);                                                                                 \
+            if (CK)                                                                                         \
+            {                                                                                               \
+                TY_REPLAY_RUN(nx);                                                                          \
+            }                                                                                               \
+            else                                                                                            \
+            {                                                                                               \
+                TY_TAKE(g, g4, nx);                                                                         \
+            }                                                                                               \
         }                                                                                                   \
         J += 16;                                                                                            \
     }
@@ -1913,28 +2122,81 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 #undef TY_TAKE
     // remaining rows (the reflected tail, 8 .. 23 of them), from memory, 16 at a time through the same cell step; the first
     // group's M and O are already in set A
-    for (bool firstTail = true; J < h; J += 16, firstTail = false)
+    if (CK)
     {
-        const int nr = min(16, h - J); // a multiple of 4
-        if (!firstTail)
+        // the rows of the tail's steps, relative to J: -8 .. 7 are in the ring (slot = row & 15, J % 16 == 0), 8 .. 23 are one more
+        // replayed block (rows past h: clamped, unused).  h - J is 8, 12, 16 or 20: row j takes rows j - 7, j - 1 and j + 5, or, from
+        // j = h - 5 on, the reflected 2 h - 6 - j — one of four compile-time rows by h - J.
+        float tb[32];
+        float4 nt[4];
+        TY_REPLAY_REQ(J + 8);
+        TY_REPLAY_RUN(nt);
+#pragma unroll
+        for (int q = 0; q < 16; q++)
         {
-            TY_O_FETCH(oqA, J); // (M was requested by the previous group's cell step)
+            tb[q] = ring[(q + 8) & 15];
         }
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+        {
+            tb[16 + 4 * q] = nt[q].x, tb[17 + 4 * q] = nt[q].y, tb[18 + 4 * q] = nt[q].z, tb[19 + 4 * q] = nt[q].w;
+        }
+        const int rem = h - J;
+#define TY_TAIL_B(jj, REM) tb[8 + ((jj) >= (REM) ? 0 : (jj) < (REM) - 5 ? (jj) + 5 : 2 * (REM) - 6 - (jj))]
+#define TY_TAIL_STEP(jj)                                                                                    \
+    if ((jj) < rem) /* wave-uniform */                                                                      \
+    {                                                                                                       \
+        const float b_ = rem == 8 ? TY_TAIL_B(jj, 8) : rem == 12 ? TY_TAIL_B(jj, 12) : rem == 16 ? TY_TAIL_B(jj, 16) : TY_TAIL_B(jj, 20); \
+        t += tb[8 + (jj) - 7] + b_ - 2 * tb[8 + (jj) - 1];                                                  \
+        u += t;                                                                                             \
+        o[(jj) & 15] = u;                                                                                   \
+    }
 #pragma unroll
         for (int jj = 0; jj < 16; jj++)
         {
-            const int j = J + jj;
-            if (jj < nr) // wave-uniform
-            {
-                const float a_ = TY_U(j - r1);
-                const float b_ = (j < h1) ? TY_U(r0 + j) : TY_U(r2 - j);
-                t += a_ + b_ - 2 * TY_U(j - 1);
-                u += t;
-                o[jj] = u;
-            }
+            TY_TAIL_STEP(jj);
         }
-        TY_CELLS(oqA, J, nr, J + 16);
+        TY_CELLS(oqA, J, min(16, rem), J + 16);
+        if (rem > 16)
+        {
+            TY_O_FETCH(oqA, J + 16); // (M was requested by the previous group's cell step)
+#pragma unroll
+            for (int jj = 16; jj < 20; jj++)
+            {
+                TY_TAIL_STEP(jj);
+            }
+            TY_CELLS(oqA, J + 16, rem - 16, J + 32);
+        }
+#undef TY_TAIL_STEP
+#undef TY_TAIL_B
     }
+    else
+    {
+        for (bool firstTail = true; J < h; J += 16, firstTail = false)
+        {
+            const int nr = min(16, h - J); // a multiple of 4
+            if (!firstTail)
+            {
+                TY_O_FETCH(oqA, J); // (M was requested by the previous group's cell step)
+            }
+#pragma unroll
+            for (int jj = 0; jj < 16; jj++)
+            {
+                const int j = J + jj;
+                if (jj < nr) // wave-uniform
+                {
+                    const float a_ = TY_U(j - r1);
+                    const float b_ = (j < h1) ? TY_U(r0 + j) : TY_U(r2 - j);
+                    t += a_ + b_ - 2 * TY_U(j - 1);
+                    u += t;
+                    o[jj] = u;
+                }
+            }
+            TY_CELLS(oqA, J, nr, J + 16);
+        }
+    }
+#undef TY_REPLAY_REQ
+#undef TY_REPLAY_RUN
     if (STG && cs > 0)
     {
         TY_FLUSH();

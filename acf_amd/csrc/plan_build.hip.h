@@ -126,8 +126,25 @@ int PlanBuild::realScales()
             }
             if (p.normRad)
             {
+                // U: a plane (with room for the blocks' padding) — or, where convTri's x pass can leave checkpoints instead (triPlan's
+                // ck; its shape conditions are stated here, the rest is decided per call), an eighth of one and NO plane: U is then
+                // allocated by the first call that takes a form which reads it (PyramidRun::realScale -> allocU)
                 rs.uFloats = std::max<int64_t>(np, uBlockedFloats(rs.h, rs.w));
-                if ((rc = devAlloc(c, &rs.U, size_t(B) * size_t(rs.uFloats))) || (rc = devAlloc(c, &rs.S, size_t(B) * np)))
+                const bool ckShape = p.normRad == 5 && p.shrink == 4 && rs.h % 4 == 0 && rs.w % 4 == 0 && rs.h >= 48 && rs.w >= 48 &&
+                    !c->opt.taps && !fallbackForced(FB_TRIY_STORED_U);
+                if (ckShape)
+                {
+                    rs.ckFloats = triCkFloats(rs.h, rs.w);
+                    if ((rc = devAlloc(c, &rs.Ck, size_t(B) * size_t(rs.ckFloats))))
+                    {
+                        return rc;
+                    }
+                }
+                else if ((rc = allocU(c, rs, B)))
+                {
+                    return rc;
+                }
+                if ((rc = devAlloc(c, &rs.S, size_t(B) * np)))
                 {
                     return rc;
                 }

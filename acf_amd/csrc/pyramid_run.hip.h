@@ -27,6 +27,8 @@ struct ScalePlan
     bool triXFused = false;   // ... and convTri's x pass: U (k_smooth_grad_tri)
     bool fuseCells = false;   // convTri's y pass may write the channel cells (k_triy_chns); else S is written and k_chns normalises
     bool blocked = false;     // M, O and U in 64 x 16 blocks (triPlan)
+    bool ck = false;          // ... and no U: the x pass leaves checkpoints, k_triy_chns replays it (triPlan)
+    bool needU = false;       // convTri runs in a form that reads the plane U
     ChnsArgs a{};             // the level's channel arguments (without the arith tables)
     int nt = 0, warm = 0;     // k_smooth_vec's threads, warm-up columns
     int nSeg = 1, segW = 0;   // column segments of the other planes' launch (and their width)
@@ -74,8 +76,16 @@ struct LevelsCall
     int lvChain = 1;
 };
 
-static SmoothVecKernel smoothGradKernel(bool tri, bool half, bool x86)
+static SmoothVecKernel smoothGradKernel(bool tri, bool half, bool x86, bool ck)
 {
+    if (tri && ck)
+    {
+        if (!x86)
+        {
+            return half ? k_smooth_grad_tri<true, false, true> : k_smooth_grad_tri<false, false, true>;
+        }
+        return half ? k_smooth_grad_tri<true, true, true> : k_smooth_grad_tri<false, true, true>;
+    }
     if (!x86)
     {
         if (!tri)
@@ -322,7 +332,17 @@ int PyramidRun::realScale(size_t k)
     {
         return rc;
     }
-    const ScalePlan sp = planScale(k, img, img_fs);
+    ScalePlan sp = planScale(k, img, img_fs);
+    if (sp.needU && !rs.U)
+    {
+        // the first call that takes a form which reads U where the plan expected checkpoints (a form switch set after the plan)
+        if ((rc = allocU(c, rs, c->maxBatch)))
+        {
+            return rc;
+        }
+        sp = planScale(k, img, img_fs);
+    }
+    rs.triForm = (sp.ck ? 1 : 0) | (rs.U ? 2 : 0);
     if ((rc = smoothImage(k, img, img_fs, sp)))
     {
         return rc;
@@ -436,8 +456,13 @@ ScalePlan PyramidRun::planScale(size_t k, const float* img, int64_t img_fs)
     // M, O and U of this scale in 64 x 16 blocks when every kernel that touches them is the vector form
     const bool gradVec = rs.h % 4 == 0 && np % 4 == 0;
     sp.fuseCells = shrink == 4 && !c->opt.taps;
-    sp.blocked = grad && p.normRad && !moWithImage &&
-        triPlan(rs.M, rs.U, rs.h, rs.w, p.normRad, np, sp.fuseCells ? &a : nullptr, rs.uFloats, rs.moFloats, gradVec).blocked;
+    if (grad && p.normRad && !moWithImage)
+    {
+        const TriPlan tp = triPlan(rs.M, rs.U, rs.h, rs.w, p.normRad, np, sp.fuseCells ? &a : nullptr, rs.uFloats, rs.moFloats, gradVec, rs.Ck, rs.ckFloats);
+        sp.blocked = tp.blocked;
+        sp.ck = tp.ck;
+        sp.needU = !tp.ck;
+    }
     if (!sp.fuseSm)
     {
         return sp;
@@ -587,9 +612,9 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, const Sc
         sa.full = p.full;
         if (sp.triXFused)
         {
-            sa.tU = rs.U;
-            sa.u_fs = uBlockedFloats(rs.h, rs.w);
-            sa.nybU = (rs.h + 8 + 15) / 16;
+            sa.tU = sp.ck ? rs.Ck : rs.U;
+            sa.u_fs = sp.ck ? triCkFloats(rs.h, rs.w) : uBlockedFloats(rs.h, rs.w);
+            sa.nybU = triCkBlockRows(rs.h);
         }
     }
     // the gradient plane's launch (with convTri's x pass on the chain or without, the next scale's half image or not, exact reciprocals
@@ -603,7 +628,7 @@ int PyramidRun::smoothImage(size_t k, const float* img, int64_t img_fs, const Sc
         g.x86 = x86T(c);
         return g;
     };
-    const SmoothVecKernel gradKernel = smoothGradKernel(sp.triXFused, sp.halfNext, x86T(c) != nullptr), vecKernel = smoothVecKernel(sp.halfNext);
+    const SmoothVecKernel gradKernel = smoothGradKernel(sp.triXFused, sp.halfNext, x86T(c) != nullptr, sp.ck), vecKernel = smoothVecKernel(sp.halfNext);
     const char* gradName = sp.triXFused ? "k_smooth_grad_tri" : "k_smooth_grad";
     const int nVec = sp.wantGrad ? d - 1 : d;
     // (the repair flags are zero here: set by k_smooth_verify, taken down by the repair launch that reads them)
@@ -705,7 +730,7 @@ int PyramidRun::gradientChannels(size_t k, const ScalePlan& sp)
         // convTri(M, normRad): x running sums, then the y pass — fused with the channel cells when the level allows it
         // (S then never reaches HBM), else S is written for k_chns
         if ((rc = launchTri(c, st, rs.M, rs.U, rs.S, rs.h, rs.w, p.normRad, np, nF, sp.fuseCells ? &a : nullptr, &cellsDone, rs.uFloats, rs.moFloats,
-                 sp.blocked, sp.triXFused)))
+                 sp.blocked, sp.triXFused, rs.Ck, rs.ckFloats, sp.ck)))
         {
             return rc;
         }

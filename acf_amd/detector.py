@@ -387,6 +387,15 @@ class HipDetector:
         self._chk(self.lib.acf_hip_get_repairs(self.ctx, out))
         return tuple(int(x) for x in out)
 
+    def tri_forms(self):
+        """Per real scale, the form convTri(M, normRad) took in the last call (acf_hip_get_tri_forms): bit 0 = checkpoints replayed by the
+        y kernel, bit 1 = a plane U is held."""
+        cap = 64
+        n = C.c_int()
+        out = (C.c_int32 * cap)()
+        self._chk(self.lib.acf_hip_get_tri_forms(self.ctx, out, cap, C.byref(n)))
+        return [int(out[i]) for i in range(min(n.value, cap))]
+
     def set_option(self, key, value):
         self._chk(self.lib.acf_hip_set_option(self.ctx, key.encode(), int(value)))
 

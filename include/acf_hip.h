@@ -261,7 +261,13 @@ ACF_HIP_API const char* acf_hip_last_error(const acf_hip_ctx* ctx);
  * in its count as always, but WHICH of its hits are retained is unspecified (slots are
  * reserved in thread order; a q x q group may be partly written).  "keep_pyramid" = 0 has no
  * effect for LDCF models, for stride < shrink and for tree depths 1, 3 and 4 on rank cells:
- * those paths read the float pyramid (their overflow queues do), so it is always written. */
+ * those paths read the float pyramid (their overflow queues do), so it is always written.
+ *
+ * Environment, read once per process: ACF_HIP_FORCE_FALLBACK=name[,name...] makes the named stages run their fallback form where
+ * the default form would (identical results; the tests hold every form against the oracle that way; DESIGN.md §8 lists the names;
+ * an unknown name aborts).  `triy_stored_u`: convTri's x pass (normRad 5) writes the blocked plane U and the fused y pass reads it
+ * back, instead of the default — (T, U) checkpoints every 16 columns, an eighth of the plane, from which the y pass re-runs the
+ * x pass over the M blocks (acf_hip_get_tri_forms reports which form a call took). */
 ACF_HIP_API int acf_hip_set_option(acf_hip_ctx* ctx, const char* key, int value);
 
 /* The reference's arithmetic at its three approximate sites (option "arith" = 1).  _mm_rcp_ps and _mm_rsqrt_ps
@@ -621,6 +627,16 @@ ACF_HIP_API int acf_hip_synchronize(acf_hip_ctx* ctx);
  * smoothing segments were checked, of those recomputed as one chain, level planes checked, recomputed} since the context
  * was created — how often the speculative column segments (options smooth_segments / smooth_warm / level_warm) miss. */
 ACF_HIP_API int acf_hip_get_repairs(acf_hip_ctx* ctx, int64_t out[4]);
+/* Read-only: the form convTri(M, normRad) took at every real scale in the last acf_hip_pyramid / acf_hip_run* call (0 before the
+ * first).  out[i] for real scale i (at most `cap`; *n = their number): bit 0 = the x pass left checkpoints which the y kernel
+ * replayed (no plane U travels through memory), bit 1 = the context holds a plane U for that scale (it is allocated only when a
+ * call first takes a form that reads it).  Additive: ACF_HIP_ABI_VERSION stays. */
+ACF_HIP_API int acf_hip_get_tri_forms(const acf_hip_ctx* ctx, int32_t* out, int cap, int* n);
+/* Host only (tests): the checkpoint buffer of an h x w plane — out[0] = float index of the (T, U) pair that row y's replay of the
+ * 16-column segment holding column x starts from, out[1] = floats per frame.  Per frame
+ * [x >> 6][(y + 8) >> 4][(x >> 4) & 3][(y + 8) & 15][2]: the 16 rows x 4 segments a wave of the y kernel takes per step are 512
+ * contiguous bytes; the state is the one after column (x & ~15) - 1, for segment 0 the one after column 0. */
+ACF_HIP_API int acf_hip_tri_ck_layout(int h, int w, int x, int y, int64_t out[2]);
 
 /* Per-kernel timing with HIP events recorded on the context's stream (option
  * "profile" = 1): the counterpart of the reference's ScopeTimeLogger stage
