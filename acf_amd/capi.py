@@ -160,6 +160,9 @@ class ImageDesc(C.Structure):
 
 
 # ACF_HIP_YUV_*: the named layouts acf_hip_yuv_layout builds descriptors for (not PIX_*)
+# ACF_HIP_ORIENT_*: rot + 4 * mirror; the upright frame is np.rot90(S[:, ::-1] if mirror else S, k=-rot)
+(ORIENT_UPRIGHT, ORIENT_ROT90, ORIENT_ROT180, ORIENT_ROT270, ORIENT_MIRROR, ORIENT_MIRROR_ROT90, ORIENT_MIRROR_ROT180,
+ ORIENT_MIRROR_ROT270) = range(8)
 YUV_NV12, YUV_NV21, YUV_I420, YUV_YV12, YUV_I422, YUV_I444, YUV_YUYV, YUV_UYVY, YUV_YVYU = range(9)
 YUV_NAMES = {"nv12": YUV_NV12, "nv21": YUV_NV21, "i420": YUV_I420, "yv12": YUV_YV12, "i422": YUV_I422, "i444": YUV_I444,
              "yuyv": YUV_YUYV, "uyvy": YUV_UYVY, "yvyu": YUV_YVYU}
@@ -236,6 +239,13 @@ def load():
         "acf_hip_pyramid_image_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_double], C.c_int),
         "acf_hip_run_image_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_double], C.c_int),
         "acf_hip_stream_open_yuv_resized": ([ctx, C.POINTER(YuvDesc), C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int], C.c_int),
+        "acf_hip_pyramid_image_oriented": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int], C.c_int),
+        "acf_hip_run_image_oriented": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int], C.c_int),
+        "acf_hip_pyramid_yuv_oriented": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_int], C.c_int),
+        "acf_hip_run_yuv_oriented": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_int], C.c_int),
+        "acf_hip_stream_open_yuv_oriented": ([ctx, C.POINTER(YuvDesc), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
+        "acf_hip_oriented_dims": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_unorient_rect": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
         "acf_hip_u8_frame_bytes": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)], C.c_int),
@@ -303,6 +313,8 @@ DECLARED_SYMBOLS = [
     "acf_hip_pyramid_yuv", "acf_hip_run_yuv", "acf_hip_yuv_to_rgb8", "acf_hip_yuv_extent", "acf_hip_yuv_layout", "acf_hip_stream_open_yuv",
     "acf_hip_pyramid_yuv_resized", "acf_hip_run_yuv_resized", "acf_hip_pyramid_image_resized", "acf_hip_run_image_resized",
     "acf_hip_stream_open_yuv_resized",
+    "acf_hip_pyramid_image_oriented", "acf_hip_run_image_oriented", "acf_hip_pyramid_yuv_oriented", "acf_hip_run_yuv_oriented",
+    "acf_hip_stream_open_yuv_oriented", "acf_hip_oriented_dims", "acf_hip_unorient_rect",
 ]
 
 

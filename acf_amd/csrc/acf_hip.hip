@@ -78,6 +78,7 @@ struct FrameSource
     bool resized = false;         // the resized entries: frames of srcRows x srcCols, reduced by `scale` to the plan's size
     int srcRows = 0, srcCols = 0;
     double scale = 1;
+    int orient = 0;               // the oriented entries (ACF_HIP_ORIENT_*, image and YUV kinds): frames of srcRows x srcCols, turned to the plan's size
 };
 
 } // namespace
@@ -2301,9 +2302,10 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
     return streamSlots(c, g.frameStride, cap, depth);
 }
 
-// acf_hip_stream_open_yuv and acf_hip_stream_open_yuv_resized (resized: frames of srcRows x srcCols, reduced by scale)
+// acf_hip_stream_open_yuv, acf_hip_stream_open_yuv_resized (resized: frames of srcRows x srcCols, reduced by scale) and
+// acf_hip_stream_open_yuv_oriented (orient: frames of srcRows x srcCols turned to the plan's size; the entry has checked them)
 static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc* desc, int64_t frameBytes, bool resized, int srcRows, int srcCols, double scale,
-    int cap, int depth)
+    int cap, int depth, int orient = 0)
 {
     const std::string w = std::string(who) + ": ";
     if (int rc = needPlan(c, who)) return rc;
@@ -2328,8 +2330,9 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
         HIPCHK(c, hipSetDevice(c->device));
         if (int rc = resizedTables(c, who, srcRows, srcCols, scale)) return rc;
     }
+    const bool ownSize = resized || orient; // the frames are srcRows x srcCols, not the plan's size
     int64_t first[3], last[3];
-    yuvExtent(*desc, resized ? srcRows : c->plan.H, resized ? srcCols : c->plan.W, 1, first, last);
+    yuvExtent(*desc, ownSize ? srcRows : c->plan.H, ownSize ? srcCols : c->plan.W, 1, first, last);
     for (int i = 0; i < 3; i++)
     {
         if (first[i] < 0 || last[i] >= frameBytes)
@@ -2341,7 +2344,8 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     {
         return fail(c, ACF_HIP_E_INVALID, w + "stride_n of every plane must be frame_bytes");
     }
-    c->stSrc = FrameSource{ SRC_YUV, nullptr, resized ? "pyramid_yuv_resized" : "pyramid_yuv", 0, 0, {}, *desc, resized, srcRows, srcCols, scale };
+    c->stSrc = FrameSource{ SRC_YUV, nullptr, resized ? "pyramid_yuv_resized" : (orient ? "pyramid_yuv_oriented" : "pyramid_yuv"), 0, 0, {}, *desc, resized, srcRows,
+        srcCols, scale, orient };
     return streamSlots(c, frameBytes, cap, depth);
 }
 
@@ -2353,6 +2357,13 @@ int acf_hip_stream_open_yuv(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_
 int acf_hip_stream_open_yuv_resized(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, double scale, int cap, int depth)
 {
     return streamOpenYuv(c, "stream_open_yuv_resized", desc, frameBytes, true, srcRows, srcCols, scale, cap, depth);
+}
+
+int acf_hip_stream_open_yuv_oriented(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, int orient, int cap, int depth)
+{
+    if (int rc = needPlan(c, "stream_open_yuv_oriented")) return rc;
+    if (int rc = orientedBad(c, "stream_open_yuv_oriented: ", srcRows, srcCols, orient)) return rc; // (code 0 too: the frame size is the plan's)
+    return streamOpenYuv(c, "stream_open_yuv_oriented", desc, frameBytes, false, srcRows, srcCols, 1.0, cap, depth, orient);
 }
 
 int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, int* ticket)

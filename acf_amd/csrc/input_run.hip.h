@@ -4,11 +4,12 @@
 // PyramidRun::ingest (pyramid_run.hip.h) launches that plan straight-line.  A new kind of input is one more SourceKind.
 //
 //   u8Geom, imageDescBad, yuvDescBad, yuvExtent      what a layout or a description is, by itself
-//   the kernel tables and form choosers              ingestKernel .. resizedKernel, imageLoadForm, yuvLoadForm, yuvIsSemiPlanar
+//   the kernel tables and form choosers              ingestKernel .. resizedKernel, imageLoadForm, yuvLoadForm, yuvIsSemiPlanar; the oriented
+//                                                    entries: imageOrientedKernel, yuvOrientedKernel, orientSrc, orientedBad, yuvIsAlignedPairs
 //   launchYuvToRgb, launchResizeU8, launchColour     the preludes and the colour conversion (ops.hip.h and crops_run.hip.h call them too)
 //   installResizeTables, resizedTables               the tap tables of acf_hip_set_input_resize (c->rz) and of the resized entries (c->rzIn)
 //   planIngest                                       FrameSource -> IngestPlan, or the refusal
-//   the entries that are only about input            acf_hip_pyramid_u8 / _image / _yuv / *_resized and their run_ twins, the extents
+//   the entries that are only about input            acf_hip_pyramid_u8 / _image / _yuv / *_resized / *_oriented and their run_ twins, the extents
 //                                                    and layouts, acf_hip_set_yuv_layout, acf_hip_set_input_resize, acf_hip_yuv_to_rgb8
 #pragma once
 
@@ -21,6 +22,8 @@ using YuvIngestKernel = void (*)(IngestArgs, YuvSrc);
 using ImageKernel = void (*)(IngestArgs, ImageArgs);
 using YuvDescKernel = void (*)(IngestArgs, YuvDescSrc);
 using ResizedKernel = void (*)(IngestArgs, ResizedSrc);
+using ImageOrientedKernel = void (*)(IngestArgs, ImageOrientedSrc);
+using YuvOrientedKernel = void (*)(IngestArgs, YuvOrientedSrc);
 
 static IngestKernel ingestKernel(int mode, bool aligned)
 {
@@ -75,6 +78,30 @@ static ResizedKernel resizedKernel(int src, int mode)
         { k_ingest_resized<RS_YUV, IG_PLANAR>, k_ingest_resized<RS_YUV, IG_LUV_VEC>, k_ingest_resized<RS_YUV, IG_LUV>, k_ingest_resized<RS_YUV, IG_GRAY> },
     };
     return table[src][mode];
+}
+
+// k_ingest_image_oriented<element type, conversion>: [ACF_HIP_T_*][IG_*] (the load form and the orientation are arguments)
+static ImageOrientedKernel imageOrientedKernel(int dtype, int mode)
+{
+    static const ImageOrientedKernel table[4][4] = {
+        { k_ingest_image_oriented<IM_U8, IG_PLANAR>, k_ingest_image_oriented<IM_U8, IG_LUV_VEC>, k_ingest_image_oriented<IM_U8, IG_LUV>,
+            k_ingest_image_oriented<IM_U8, IG_GRAY> },
+        { k_ingest_image_oriented<IM_F16, IG_PLANAR>, k_ingest_image_oriented<IM_F16, IG_LUV_VEC>, k_ingest_image_oriented<IM_F16, IG_LUV>,
+            k_ingest_image_oriented<IM_F16, IG_GRAY> },
+        { k_ingest_image_oriented<IM_BF16, IG_PLANAR>, k_ingest_image_oriented<IM_BF16, IG_LUV_VEC>, k_ingest_image_oriented<IM_BF16, IG_LUV>,
+            k_ingest_image_oriented<IM_BF16, IG_GRAY> },
+        { k_ingest_image_oriented<IM_F32, IG_PLANAR>, k_ingest_image_oriented<IM_F32, IG_LUV_VEC>, k_ingest_image_oriented<IM_F32, IG_LUV>,
+            k_ingest_image_oriented<IM_F32, IG_GRAY> },
+    };
+    return table[dtype][mode];
+}
+
+// k_ingest_yuv_oriented<conversion>: [IG_*]
+static YuvOrientedKernel yuvOrientedKernel(int mode)
+{
+    static const YuvOrientedKernel table[4] = { k_ingest_yuv_oriented<IG_PLANAR>, k_ingest_yuv_oriented<IG_LUV_VEC>, k_ingest_yuv_oriented<IG_LUV>,
+        k_ingest_yuv_oriented<IG_GRAY> };
+    return table[mode];
 }
 
 static bool pixIsYuv(int pix)
@@ -501,6 +528,46 @@ static int resizedTables(acf_hip_ctx* c, const char* who, int srcRows, int srcCo
     return installResizeTables(c, who, c->rzIn, srcRows, srcCols, scale, false);
 }
 
+// An orientation code (ACF_HIP_ORIENT_*: rot + 4 * mirror) as the map from upright to source indices that the kernels and
+// acf_hip_unorient_rect take (kernels_input.hip.h): rot 1: swap, revR; rot 2: revR, revC; rot 3: swap, revC; mirror flips revC
+static OrientSrc orientSrc(int code, int srcRows, int srcCols)
+{
+    const int rot = code & 3, mirror = (code >> 2) & 1;
+    OrientSrc o{};
+    o.Hs = srcRows;
+    o.Ws = srcCols;
+    o.swap = rot & 1;
+    o.revR = rot == 1 || rot == 2;
+    o.revC = (rot >= 2) != (mirror != 0);
+    return o;
+}
+
+// What the oriented entries refuse about (src_rows, src_cols, orient) and the plan
+static int orientedBad(acf_hip_ctx* c, const std::string& who, int srcRows, int srcCols, int orient)
+{
+    if (orient < 0 || orient > 7 || srcRows < 1 || srcCols < 1)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
+    }
+    const bool swap = orient & 1;
+    if (c->plan.H != (swap ? srcCols : srcRows) || c->plan.W != (swap ? srcRows : srcCols))
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "the plan must be for the upright size (acf_hip_oriented_dims of the frame size and orientation)");
+    }
+    return ACF_HIP_OK;
+}
+
+// The wide load form of k_ingest_yuv_oriented for NV12 / NV21-like descriptions of any size: luma samples 1 apart, chroma one plane
+// of byte pairs, all of it four-aligned with the pointer
+static bool yuvIsAlignedPairs(const YuvDescSrc& s, int& vFirst)
+{
+    const uintptr_t at = reinterpret_cast<uintptr_t>(s.base);
+    const int64_t c0 = std::min(s.u.off, s.v.off);
+    vFirst = s.v.off < s.u.off;
+    return s.subX == 1 && s.y.sp == 1 && s.u.sp == 2 && s.v.sp == 2 && std::max(s.u.off, s.v.off) == c0 + 1 && s.u.sr == s.v.sr && s.u.sn == s.v.sn &&
+           (at + uintptr_t(s.y.off)) % 4 == 0 && s.y.sr % 4 == 0 && s.y.sn % 4 == 0 && (at + uintptr_t(c0)) % 4 == 0 && s.u.sr % 4 == 0 && s.u.sn % 4 == 0;
+}
+
 // One call's ingest, decided once (planIngest); PyramidRun::ingest only reads it
 struct IngestPlan
 {
@@ -522,6 +589,8 @@ struct IngestPlan
         YuvSrc yuv420;
         ImageArgs image;
         YuvDescSrc yuv;
+        ImageOrientedSrc imageOriented;
+        YuvOrientedSrc yuvOriented;
     } second{};
     const char* profName = nullptr;   // (static strings: prof keeps the pointer)
     const char* launchName = nullptr;
@@ -532,6 +601,8 @@ struct IngestPlan
     void set(ImageKernel k, const ImageArgs& s) { kernel = reinterpret_cast<const void*>(k); second.image = s; }
     void set(YuvDescKernel k, const YuvDescSrc& s) { kernel = reinterpret_cast<const void*>(k); second.yuv = s; }
     void set(ResizedKernel k, const ResizedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.resized = s; }
+    void set(ImageOrientedKernel k, const ImageOrientedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.imageOriented = s; }
+    void set(YuvOrientedKernel k, const YuvOrientedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.yuvOriented = s; }
 };
 
 // The ingest of one call: the source held against the plan and the context's settings (what is refused, in the order the entries
@@ -638,6 +709,19 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
                 return fail(c, ACF_HIP_E_INVALID, who + "not with acf_hip_set_input_resize (the resize takes packed 8-bit frames)");
             }
             s.form = imageLoadForm(src.base, src.img);
+            if (src.orient)
+            {
+                // a turned frame: the same description and load forms at srcRows x srcCols, placed upright (k_ingest_image_oriented)
+                if (int rc = orientedBad(c, who, src.srcRows, src.srcCols, src.orient))
+                {
+                    return rc;
+                }
+                const OrientSrc o = orientSrc(src.orient, src.srcRows, src.srcCols);
+                ip.set(imageOrientedKernel(src.img.dtype, mode), ImageOrientedSrc{ s, o });
+                ip.profName = s.form == IM_GENERIC ? "k_ingest_image_oriented_generic" : (o.swap ? "k_ingest_image_oriented_cols" : "k_ingest_image_oriented_rows");
+                ip.launchName = "k_ingest_image_oriented";
+                return ACF_HIP_OK;
+            }
             ip.set(imageKernel(src.img.dtype, mode), s);
             ip.profName = ip.launchName = "k_ingest_image";
             return ACF_HIP_OK;
@@ -689,6 +773,26 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
     {
         return fail(c, ACF_HIP_E_INVALID, who + "not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)");
     }
+    if (src.orient)
+    {
+        // a turned frame: the description at srcRows x srcCols, the chroma sample chosen there, placed upright (k_ingest_yuv_oriented)
+        if (int rc = orientedBad(c, who, src.srcRows, src.srcCols, src.orient))
+        {
+            return rc;
+        }
+        YuvOrientedSrc y{};
+        y.o = orientSrc(src.orient, src.srcRows, src.srcCols);
+        y.form = yuvLoadForm(s);
+        if (y.form == YD_GENERIC && yuvIsAlignedPairs(s, y.vFirst))
+        {
+            y.form = YO_SEMI;
+        }
+        y.yuv = s;
+        ip.set(yuvOrientedKernel(mode), y);
+        ip.profName = y.form == YD_GENERIC ? "k_ingest_yuv_oriented_generic" : (y.o.swap ? "k_ingest_yuv_oriented_cols" : "k_ingest_yuv_oriented_rows");
+        ip.launchName = "k_ingest_yuv_oriented";
+        return ACF_HIP_OK;
+    }
     YuvSrc semi;
     if (yuvIsSemiPlanar(base, src.yuv, H, W, semi))
     {
@@ -714,26 +818,47 @@ static int runSource(acf_hip_ctx* c, const FrameSource& src, int nF)
 
 // the image and the YUV entries, plain and resized: the pyramid alone, or the whole run (detect)
 static int imageEntry(acf_hip_ctx* c, bool detect, const char* who, const void* frames, int nF, const acf_hip_image_desc* desc, bool resized = false, int srcRows = 0,
-    int srcCols = 0, double scale = 1)
+    int srcCols = 0, double scale = 1, int orient = 0)
 {
     if (int rc = needCtx(c)) return rc;
     if (!frames || !desc)
     {
         return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": null frames or description");
     }
-    const FrameSource src{ SRC_IMAGE, frames, who, 0, 0, *desc, {}, resized, srcRows, srcCols, scale };
+    const FrameSource src{ SRC_IMAGE, frames, who, 0, 0, *desc, {}, resized, srcRows, srcCols, scale, orient };
     return detect ? runSource(c, src, nF) : pyramidImpl(c, src, nF);
 }
 static int yuvEntry(acf_hip_ctx* c, bool detect, const char* who, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, bool resized = false, int srcRows = 0,
-    int srcCols = 0, double scale = 1)
+    int srcCols = 0, double scale = 1, int orient = 0)
 {
     if (int rc = needCtx(c)) return rc;
     if (!base || !desc)
     {
         return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": null base or description");
     }
-    const FrameSource src{ SRC_YUV, base, who, 0, 0, {}, *desc, resized, srcRows, srcCols, scale };
+    const FrameSource src{ SRC_YUV, base, who, 0, 0, {}, *desc, resized, srcRows, srcCols, scale, orient };
     return detect ? runSource(c, src, nF) : pyramidImpl(c, src, nF);
+}
+
+// The oriented entries' own checks in front of imageEntry / yuvEntry.  Code 0 is the un-oriented entry itself (forward: true), once
+// the frame size is the plan's.
+static int orientedEntry(acf_hip_ctx* c, const char* who, int srcRows, int srcCols, int orient, bool& forward)
+{
+    forward = false;
+    if (int rc = needCtx(c)) return rc;
+    if (orient < 0 || orient > 7 || srcRows < 1 || srcCols < 1)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
+    }
+    if (orient == 0)
+    {
+        if (c->hasPlan && c->kids.empty())
+        {
+            if (int rc = orientedBad(c, std::string(who) + ": ", srcRows, srcCols, 0)) return rc;
+        }
+        forward = true;
+    }
+    return ACF_HIP_OK;
 }
 } // namespace
 
@@ -787,6 +912,63 @@ int acf_hip_pyramid_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, con
 int acf_hip_run_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
 {
     return yuvEntry(c, true, "pyramid_yuv_resized", base, nF, desc, true, srcRows, srcCols, scale);
+}
+
+int acf_hip_pyramid_image_oriented(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, int orient)
+{
+    bool forward;
+    if (int rc = orientedEntry(c, "pyramid_image_oriented", srcRows, srcCols, orient, forward)) return rc;
+    return forward ? acf_hip_pyramid_image(c, frames, nF, desc) : imageEntry(c, false, "pyramid_image_oriented", frames, nF, desc, false, srcRows, srcCols, 1, orient);
+}
+
+int acf_hip_run_image_oriented(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, int orient)
+{
+    bool forward;
+    if (int rc = orientedEntry(c, "pyramid_image_oriented", srcRows, srcCols, orient, forward)) return rc;
+    return forward ? acf_hip_run_image(c, frames, nF, desc) : imageEntry(c, true, "pyramid_image_oriented", frames, nF, desc, false, srcRows, srcCols, 1, orient);
+}
+
+int acf_hip_pyramid_yuv_oriented(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient)
+{
+    bool forward;
+    if (int rc = orientedEntry(c, "pyramid_yuv_oriented", srcRows, srcCols, orient, forward)) return rc;
+    return forward ? acf_hip_pyramid_yuv(c, base, nF, desc) : yuvEntry(c, false, "pyramid_yuv_oriented", base, nF, desc, false, srcRows, srcCols, 1, orient);
+}
+
+int acf_hip_run_yuv_oriented(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient)
+{
+    bool forward;
+    if (int rc = orientedEntry(c, "pyramid_yuv_oriented", srcRows, srcCols, orient, forward)) return rc;
+    return forward ? acf_hip_run_yuv(c, base, nF, desc) : yuvEntry(c, true, "pyramid_yuv_oriented", base, nF, desc, false, srcRows, srcCols, 1, orient);
+}
+
+int acf_hip_oriented_dims(int srcRows, int srcCols, int orient, int* h, int* w)
+{
+    if (!h || !w || srcRows < 1 || srcCols < 1 || orient < 0 || orient > 7)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    *h = (orient & 1) ? srcCols : srcRows;
+    *w = (orient & 1) ? srcRows : srcCols;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_unorient_rect(int orient, int srcRows, int srcCols, const int32_t in[4], int32_t out[4])
+{
+    if (!in || !out || srcRows < 1 || srcCols < 1 || orient < 0 || orient > 7)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    // upright columns [x, x + w) and rows [y, y + h): the source index an upright index follows runs with it or against it
+    const OrientSrc o = orientSrc(orient, srcRows, srcCols);
+    const int32_t x = in[0], y = in[1], w = in[2], h = in[3];
+    const int32_t r0 = o.swap ? x : y, nr = o.swap ? w : h; // along the source rows
+    const int32_t c0 = o.swap ? y : x, nc = o.swap ? h : w; // along the source columns
+    out[0] = o.revC ? srcCols - c0 - nc : c0;
+    out[1] = o.revR ? srcRows - r0 - nr : r0;
+    out[2] = nc;
+    out[3] = nr;
+    return ACF_HIP_OK;
 }
 
 int acf_hip_image_extent(const acf_hip_image_desc* d, int h, int w, int nF, int64_t* first, int64_t* last)

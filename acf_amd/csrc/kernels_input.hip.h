@@ -1,6 +1,7 @@
 // kernels_input.hip.h — part of kernels.hip.h (included from there, in its order, and nowhere else: the parts share kernels.hip.h's
 // includes, its layout / arithmetic contract and the helpers of the parts before them).
-// rgbConvert (LUV / gray / HSV), the packed 8-bit ingest, the apps' resize to a minimum object width (alone: k_resize_u8; inside the tensor / YUV
+// rgbConvert (LUV / gray / HSV), the packed 8-bit ingest, the tensor and YUV ingests (upright: k_ingest_image / k_ingest_yuv; rotated and mirrored
+// frames: k_ingest_image_oriented / k_ingest_yuv_oriented), the apps' resize to a minimum object width (alone: k_resize_u8; inside the tensor / YUV
 // entries: k_ingest_resized), and the plain convTri1 (k_smooth_tri1: the fallback of the vector smoothing).
 #pragma once
 
@@ -955,6 +956,477 @@ __global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
             }
             int r, g, b;
             yuv_rgb8(tile[yd_slot(yq + j, 0) * YG_PITCH + xx], c, r, g, b);
+            ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
+        }
+        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
+    }
+}
+
+// ------------------------------------------------------------------------
+// Rotated and mirrored frames (acf_hip_*_oriented, orientation codes 1 .. 7; code 0 runs the kernels above): the source frame S of
+// Hs x Ws pixels is read where it lies and the planes are those of the upright frame U = np.rot90(S[:, ::-1] if mirror else S, -rot).
+// Upright pixel (r, c) is source pixel (rs, cs):
+//     swap == 0 (rot 0 / 2):  rs = revR ? Hs - 1 - r : r,  cs = revC ? Ws - 1 - c : c
+//     swap == 1 (rot 1 / 3):  rs = revR ? Hs - 1 - c : c,  cs = revC ? Ws - 1 - r : r
+// (rot 1: swap, revR; rot 2: revR, revC; rot 3: swap, revC; mirror flips revC.)  All three are runtime arguments.
+//
+// A workgroup owns 64 x 64 UPRIGHT pixels, as every ingest kernel; they are one 64 x 64 (ragged: nsr x nsc) rectangle of the source,
+// whose first row / column is anywhere (Hs - y0 - ny ...), not on a multiple of 64.  Both kernels work the same way:
+//   load phase   lanes run along the SOURCE rows of that rectangle, whichever way the frame is turned, with the wide loads of the
+//                un-oriented kernels (below), so the loads are coalesced in every orientation;
+//   placement    every element goes to the LDS tile at its UPRIGHT position (orient_up): the reversals and, for swap, the transpose
+//                happen here, and the chroma sample of a subsampled plane is chosen here, in source coordinates, and written to
+//                each of the (up to four) pixels of the rectangle that take it;
+//   store phase  the shared one, on a tile that holds the upright pixels: a lane takes four consecutive image-y of one image-x through
+//                the model's colour conversion and stores one float4 a plane (coalesced along image-y).
+// Profile names: *_oriented_rows (swap == 0) and *_oriented_cols (swap == 1) with a wide load form, *_oriented_generic with the
+// element-wise one.  For swap the four image-y a lane stores ARE four neighbouring source pixels of one source row, so planar sources
+// could go from registers to the float4 store without LDS; the tile is kept for them too — one placement and one store phase for every
+// layout (packed pixels, macropixels and subsampled chroma need the stage anyway), and LDS traffic is not what bounds a kernel that
+// moves 1 .. 12 bytes in and 4 .. 12 bytes out per pixel through HBM (profiles/oriented_entry.md holds what was measured).
+//
+// Because the rectangle starts anywhere, a row's wide loads are the ALIGNED words that hold a piece of it (at most 17 quads / dwords
+// for 64 elements); a word is loaded whole only when all of it lies inside the rectangle, else its elements inside the rectangle one by
+// one.  So no load covers an address outside the [first, last] span the same row of the same plane addresses.
+//
+// LDS banks (bank = dword address % 32, per 32-lane half), the image kernel (float tile of k_ingest_image: row r in slot
+// (r & 3) * 16 + (r >> 2), pitch 66 dwords, planes 64 * 66 + 11 apart):
+//   store phase (reads)      k_ingest_image's: conflict-free
+//   rows, IM_ROWVEC writes   a lane's element t of quad q goes to upright x = +-(4q + t) + const of one slot; a half is 17 quads of
+//                            one row then 15 of the next (another slot: a multiple of 66 dwords away): stride-4 columns -> 8 banks a
+//                            row, 4-way, as k_ingest_image's IM_ROWVEC
+//   cols, IM_ROWVEC writes   element t of quad q goes to upright row 4q' + t' (the quads of the rectangle are not those of the
+//                            upright rows unless Ws % 4 == 0), column = the source row: per ds_write the lanes of one source row
+//                            write slots 16 t' + q', 66 dwords apart -> banks 2q' + const, 16 or 17 distinct; the second source row
+//                            of the half is one column (one bank) further: 2-way at worst
+//   IM_PACKED / IM_GENERIC   rows: as k_ingest_image.  cols: consecutive pixels of a source row go down one tile column, rows
+//                            r, r + 1, .. -> slots 16 apart = 1056 = 0 (mod 32) dwords for r & 3 = 0 .. 2, then + 66: the pixels of
+//                            one lane group fall on 8 .. 9 banks, up to 4-way for f32 (one pixel a lane), less for the narrower
+//                            types whose lanes share pixels.
+// The YUV kernel (three byte tiles Y, U, V at the UPRIGHT resolution, each 64 slots x 17 dwords as k_ingest_yuv's luma tile):
+//   store phase (byte reads) the luma pattern of k_ingest_yuv for all three tiles: 16 distinct banks, conflict-free
+//   rows, dword loads        four bytes of a lane go to four adjacent bytes of one slot (forwards or backwards): one dword or two
+//   cols, dword loads        four bytes of a lane go to four slots 16 apart (272 = 16 (mod 32) dwords): 2 banks a lane; the lanes
+//                            of a source row walk 17 dwords a quad: conflict degree <= 4 on byte writes
+// (degrees derived from the address maps with the bank rule; SQ_LDS_BANK_CONFLICT was not read.)
+// ------------------------------------------------------------------------
+struct OrientSrc
+{
+    int Hs, Ws;           // source rows, columns
+    int swap, revR, revC; // the map above
+};
+
+// The source rectangle of a workgroup's upright tile, and where its elements go
+struct OrientTile
+{
+    int rs0, cs0, nsr, nsc; // first source row / column, rows, columns
+    int swap, revR, revC;
+    // upright tile position (yy, xx) of the rectangle's element (i, j)
+    __device__ __forceinline__ void up(int i, int j, int& yy, int& xx) const
+    {
+        const int p = revR ? nsr - 1 - i : i, q = revC ? nsc - 1 - j : j;
+        yy = swap ? q : p;
+        xx = swap ? p : q;
+    }
+};
+__device__ __forceinline__ OrientTile orient_tile(const OrientSrc& o, int x0, int y0, int nx, int ny)
+{
+    OrientTile t;
+    t.swap = o.swap;
+    t.revR = o.revR;
+    t.revC = o.revC;
+    t.nsr = o.swap ? nx : ny;
+    t.nsc = o.swap ? ny : nx;
+    const int r0 = o.swap ? x0 : y0, c0 = o.swap ? y0 : x0;
+    t.rs0 = o.revR ? o.Hs - r0 - t.nsr : r0;
+    t.cs0 = o.revC ? o.Ws - c0 - t.nsc : c0;
+    return t;
+}
+
+constexpr int OR_WORDS = 17; // aligned 4-element words that can hold a piece of 64 consecutive elements
+
+struct ImageOrientedSrc
+{
+    ImageArgs im; // the description at Hs x Ws; form: the load form, by imageLoadForm's conditions
+    OrientSrc o;
+};
+
+template <int DT, int MODE>
+__global__ void __launch_bounds__(256) k_ingest_image_oriented(IngestArgs a, ImageOrientedSrc S)
+{
+    using E = ImgElem<DT>;
+    using raw = typename E::raw;
+    __shared__ float tile[3 * IM_PLANE];
+    const ImageArgs& s = S.im;
+    const int x0 = blockIdx.x * IG_T, y0 = blockIdx.y * IG_T;
+    const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0);
+    const OrientTile T = orient_tile(S.o, x0, y0, nx, ny);
+    const auto place = [&](int c, int i, int j, raw v) {
+        int yy, xx;
+        T.up(i, j, yy, xx);
+        tile[c * IM_PLANE + im_slot(yy) * IM_PITCH + xx] = E::cvt(v);
+    };
+    // the frame's row T.rs0, column 0 (the row starts keep the alignment the host checked)
+    const raw* rows = static_cast<const raw*>(s.in) + int64_t(blockIdx.z) * s.sn + int64_t(T.rs0) * s.sy;
+    if (s.form == IM_ROWVEC)
+    {
+        // sx == 1; the base and sn, sc, sy are multiples of four elements (host-checked)
+        struct alignas(4 * sizeof(raw)) Quad
+        {
+            raw v[4];
+        };
+        const int e0 = T.cs0 & ~3, e1 = T.cs0 + T.nsc; // the first quad's first column; one past the last column
+        for (int c = 0; c < s.nIn; c++)
+        {
+            const raw* pc = rows + int64_t(c) * s.sc;
+#pragma unroll 2
+            for (int idx = threadIdx.x; idx < T.nsr * OR_WORDS; idx += 256)
+            {
+                const int i = idx / OR_WORDS, col = e0 + 4 * (idx - i * OR_WORDS);
+                if (col >= e1)
+                {
+                    continue;
+                }
+                const raw* rp = pc + int64_t(i) * s.sy + col;
+                if (col >= T.cs0 && col + 4 <= e1)
+                {
+                    const Quad v = *reinterpret_cast<const Quad*>(rp);
+#pragma unroll
+                    for (int t = 0; t < 4; t++)
+                    {
+                        place(c, i, col + t - T.cs0, v.v[t]);
+                    }
+                }
+                else
+                {
+                    for (int t = 0; t < 4; t++) // a quad over one end of the rectangle: only the elements inside it
+                    {
+                        if (col + t >= T.cs0 && col + t < e1)
+                        {
+                            place(c, i, col + t - T.cs0, rp[t]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    else if (s.form == IM_PACKED)
+    {
+        // sc == +-1, sx == 3 or 4, three planes; the base is a multiple of the element size (host-checked): k_ingest_image's IM_PACKED
+        // on the rectangle's rows
+        constexpr int PER = 4 / int(sizeof(raw)); // elements a dword
+        const int rev = s.sc < 0, sx = int(s.sx);
+        const int L = (T.nsc - 1) * sx + 3;       // elements a row of the rectangle addresses: [0, L) from `span`
+        const raw* span = rows + int64_t(T.cs0) * sx - (rev ? 2 : 0);
+        const int ndMax = (L * int(sizeof(raw)) + 6) >> 2; // dwords that can hold a piece of it, whatever the row's alignment
+#pragma unroll 2
+        for (int i = threadIdx.x >> 6; i < T.nsr; i += 4)
+        {
+            const raw* rp = span + int64_t(i) * s.sy;
+            const int mis = int(reinterpret_cast<uintptr_t>(rp) & 3) / int(sizeof(raw)); // elements of rp's dword in front of rp
+            for (int d = threadIdx.x & 63; d < ndMax; d += 64)
+            {
+                const int f0 = d * PER - mis; // span index of dword d's first element
+                if (f0 >= L)
+                {
+                    continue;
+                }
+                raw v[PER];
+                if (f0 >= 0 && f0 + PER <= L)
+                {
+                    const uint32_t w = *reinterpret_cast<const uint32_t*>(rp + f0);
+#pragma unroll
+                    for (int t = 0; t < PER; t++)
+                    {
+                        v[t] = raw(w >> (8 * int(sizeof(raw)) * t));
+                    }
+                }
+                else
+                {
+#pragma unroll
+                    for (int t = 0; t < PER; t++) // a dword over one end of the span: only the elements inside it
+                    {
+                        const int e = f0 + t;
+                        v[t] = (e >= 0 && e < L) ? rp[e] : raw(0);
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < PER; t++)
+                {
+                    const int e = f0 + t;
+                    if (e >= 0 && e < L)
+                    {
+                        const int x = sx == 4 ? e >> 2 : e / 3, m = e - x * sx;
+                        if (m < 3) // (m == 3: the skipped fourth element)
+                        {
+                            place(rev ? 2 - m : m, i, x, v[t]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    else
+    {
+        // one element a lane, lanes along the source row, any strides
+        for (int c = 0; c < s.nIn; c++)
+        {
+            const raw* pc = rows + int64_t(c) * s.sc + int64_t(T.cs0) * s.sx;
+#pragma unroll 4
+            for (int idx = threadIdx.x; idx < T.nsr * IG_T; idx += 256)
+            {
+                const int i = idx >> 6, j = idx & 63;
+                if (j < T.nsc)
+                {
+                    place(c, i, j, pc[int64_t(i) * s.sy + int64_t(j) * s.sx]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // k_ingest_image's store phase
+    const int k16 = threadIdx.x & 15, yq = k16 * 4;
+    const int p1 = s.nIn == 3 ? IM_PLANE : 0, p2 = 2 * p1; // one plane: r = g = b (chnsPyramid.cpp:234-244)
+    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
+    const int64_t np = int64_t(a.H) * a.W;
+    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
+    {
+        float o[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            // rows beyond the tile convert zeros (the LDS there was never written; rgb2luv indexes a table): never stored
+            const float* t = tile + (j * 16 + k16) * IM_PITCH + xx;
+            const bool in = yq + j < ny;
+            const float r = in ? t[0] : 0.f, g = in ? t[p1] : 0.f, b = in ? t[p2] : 0.f;
+            ingest_convert<MODE>(a, r, g, b, o, j);
+        }
+        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
+    }
+}
+
+// The YUV twin.  Load forms (YuvOrientedSrc::form, chosen on the host from the description and the base's alignment alone; all give
+// the same tiles):
+//   YD_PLANAR     (yuvLoadForm's conditions) every plane's rows as aligned dwords by consecutive lanes
+//   YD_PACKED422  (yuvLoadForm's conditions) a lane's dword is one macropixel = two source pixels; the rectangle may start or end on
+//                 half a macropixel: the dword is still inside the row's macropixels, and only the pixels inside the rectangle are placed
+//   YO_SEMI       luma rows as YD_PLANAR; chroma is one plane of byte pairs (U, V or V, U: NV12 / NV21 of any size and strides, 4-aligned):
+//                 a lane's dword is two chroma samples
+//   YD_GENERIC    one sample a lane, any strides
+constexpr int YO_SEMI = 3;
+
+struct YuvOrientedSrc
+{
+    YuvDescSrc yuv; // the description at Hs x Ws (yPos .. mp as yuvLoadForm fills them)
+    OrientSrc o;
+    int form;
+    int vFirst;     // YO_SEMI: the pair is V, U
+};
+
+// one sample v of plane `tile` (plane row pr, plane column pc; lsy, lsx: the plane's subsampling shifts) to every pixel of the
+// rectangle that takes it
+__device__ __forceinline__ void yo_spread(const OrientTile& T, uint8_t* tile, int pr, int pc, int lsy, int lsx, uint8_t v)
+{
+    for (int dy = 0; dy <= lsy; dy++)
+    {
+        const int i = (pr << lsy) + dy - T.rs0;
+        if (i < 0 || i >= T.nsr)
+        {
+            continue;
+        }
+        for (int dx = 0; dx <= lsx; dx++)
+        {
+            const int j = (pc << lsx) + dx - T.cs0;
+            if (j >= 0 && j < T.nsc)
+            {
+                int yy, xx;
+                T.up(i, j, yy, xx);
+                tile[yd_slot(yy, 0) * YG_PITCH + xx] = v;
+            }
+        }
+    }
+}
+
+// YD_GENERIC: the samples of one plane that the rectangle takes, one a lane
+__device__ __forceinline__ void yo_load_generic(const OrientTile& T, const uint8_t* __restrict__ frame, const YuvPlane& p, int lsy, int lsx, uint8_t* tile)
+{
+    const int pr0 = T.rs0 >> lsy, nPr = ((T.rs0 + T.nsr - 1) >> lsy) - pr0 + 1;
+    const int pc0 = T.cs0 >> lsx, nPc = ((T.cs0 + T.nsc - 1) >> lsx) - pc0 + 1;
+    for (int idx = threadIdx.x; idx < nPr * IG_T; idx += 256)
+    {
+        const int pr = pr0 + (idx >> 6), pc = pc0 + (idx & 63);
+        if (pc < pc0 + nPc)
+        {
+            yo_spread(T, tile, pr, pc, lsy, lsx, frame[int64_t(pr) * p.sr + int64_t(pc) * p.sp]);
+        }
+    }
+}
+
+// YD_PLANAR: the same with the aligned dwords of each plane row (sp == 1; frame + row starts are multiples of 4)
+__device__ __forceinline__ void yo_load_vec(const OrientTile& T, const uint8_t* __restrict__ frame, const YuvPlane& p, int lsy, int lsx, uint8_t* tile)
+{
+    const int pr0 = T.rs0 >> lsy, nPr = ((T.rs0 + T.nsr - 1) >> lsy) - pr0 + 1;
+    const int pc0 = T.cs0 >> lsx, pc1 = ((T.cs0 + T.nsc - 1) >> lsx) + 1; // [pc0, pc1)
+    const int e0 = pc0 & ~3;
+#pragma unroll 2
+    for (int idx = threadIdx.x; idx < nPr * OR_WORDS; idx += 256)
+    {
+        const int r = idx / OR_WORDS, col = e0 + 4 * (idx - r * OR_WORDS), pr = pr0 + r;
+        if (col >= pc1)
+        {
+            continue;
+        }
+        const uint8_t* rp = frame + int64_t(pr) * p.sr + col;
+        if (col >= pc0 && col + 4 <= pc1)
+        {
+            const uint32_t w = *reinterpret_cast<const uint32_t*>(rp);
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+            {
+                yo_spread(T, tile, pr, col + t, lsy, lsx, uint8_t(w >> (8 * t)));
+            }
+        }
+        else
+        {
+            for (int t = 0; t < 4; t++) // a dword over one end of the rectangle's samples: only those inside
+            {
+                if (col + t >= pc0 && col + t < pc1)
+                {
+                    yo_spread(T, tile, pr, col + t, lsy, lsx, rp[t]);
+                }
+            }
+        }
+    }
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) k_ingest_yuv_oriented(IngestArgs a, YuvOrientedSrc S)
+{
+    __shared__ uint32_t tileW[3 * YD_TILE / 4];
+    uint8_t* tile = reinterpret_cast<uint8_t*>(tileW);
+    const YuvDescSrc& s = S.yuv;
+    const int x0 = blockIdx.x * IG_T, y0 = blockIdx.y * IG_T;
+    const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0);
+    const OrientTile T = orient_tile(S.o, x0, y0, nx, ny);
+    const int subX = s.subX, subY = s.subY;
+    const int64_t n = blockIdx.z;
+    const uint8_t* fy = s.base + s.y.off + n * s.y.sn;
+    const uint8_t* fu = s.base + s.u.off + n * s.u.sn;
+    const uint8_t* fv = s.base + s.v.off + n * s.v.sn;
+    if (S.form == YD_PACKED422)
+    {
+        // subX == 1, subY == 0; the three planes share sr and sn; base + mp, sr, sn are multiples of 4 (host-checked)
+        const uint8_t* src = s.base + s.mp + n * s.y.sn + int64_t(T.rs0) * s.y.sr;
+        const int sy0 = 8 * s.yPos, su = 8 * s.uPos, sv = 8 * s.vPos;
+        const int m0 = T.cs0 >> 1, nm = ((T.cs0 + T.nsc - 1) >> 1) - m0 + 1; // the macropixels a row of the rectangle touches: <= 33
+#pragma unroll 2
+        for (int idx = threadIdx.x; idx < T.nsr * IG_T; idx += 256)
+        {
+            const int i = idx >> 6, q = idx & 63;
+            if (q >= nm)
+            {
+                continue;
+            }
+            const int m = m0 + q;
+            const uint8_t* rp = src + int64_t(i) * s.y.sr + 4 * int64_t(m);
+            uint32_t Y[2], U, V;
+            if (2 * m + 1 < S.o.Ws)
+            {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(rp);
+                Y[0] = (w >> sy0) & 255;
+                Y[1] = (w >> (sy0 + 16)) & 255;
+                U = (w >> su) & 255;
+                V = (w >> sv) & 255;
+            }
+            else
+            {
+                Y[0] = rp[s.yPos]; // an odd row's last pixel: its three bytes only
+                Y[1] = 0;
+                U = rp[s.uPos];
+                V = rp[s.vPos];
+            }
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+            {
+                const int j = 2 * m + t - T.cs0;
+                if (j >= 0 && j < T.nsc)
+                {
+                    int yy, xx;
+                    T.up(i, j, yy, xx);
+                    const int at = yd_slot(yy, 0) * YG_PITCH + xx;
+                    tile[at] = uint8_t(Y[t]);
+                    tile[YD_TILE + at] = uint8_t(U);
+                    tile[2 * YD_TILE + at] = uint8_t(V);
+                }
+            }
+        }
+    }
+    else if (S.form == YD_PLANAR)
+    {
+        yo_load_vec(T, fy, s.y, 0, 0, tile);
+        yo_load_vec(T, fu, s.u, subY, subX, tile + YD_TILE);
+        yo_load_vec(T, fv, s.v, subY, subX, tile + 2 * YD_TILE);
+    }
+    else if (S.form == YO_SEMI)
+    {
+        // subX == 1; y.sp == 1; the chroma pairs are four-aligned with their rows, as the luma rows (host-checked)
+        yo_load_vec(T, fy, s.y, 0, 0, tile);
+        const uint8_t* fc = S.vFirst ? fv : fu; // the pair's first byte
+        const int uAt = 8 * S.vFirst, vAt = 8 - uAt;
+        const int pr0 = T.rs0 >> subY, nPr = ((T.rs0 + T.nsr - 1) >> subY) - pr0 + 1;
+        const int pc0 = T.cs0 >> 1, pc1 = ((T.cs0 + T.nsc - 1) >> 1) + 1; // pairs [pc0, pc1)
+        const int e0 = pc0 & ~1;
+#pragma unroll 2
+        for (int idx = threadIdx.x; idx < nPr * OR_WORDS; idx += 256)
+        {
+            const int r = idx / OR_WORDS, col = e0 + 2 * (idx - r * OR_WORDS), pr = pr0 + r;
+            if (col >= pc1)
+            {
+                continue;
+            }
+            const uint8_t* rp = fc + int64_t(pr) * s.u.sr + 2 * col;
+            uint32_t w;
+            if (col >= pc0 && col + 2 <= pc1)
+            {
+                w = *reinterpret_cast<const uint32_t*>(rp);
+            }
+            else
+            {
+                const int t = col >= pc0 ? 0 : 1; // the one pair inside
+                w = (uint32_t(rp[2 * t]) | (uint32_t(rp[2 * t + 1]) << 8)) << (16 * t);
+            }
+#pragma unroll
+            for (int t = 0; t < 2; t++)
+            {
+                if (col + t >= pc0 && col + t < pc1)
+                {
+                    yo_spread(T, tile + YD_TILE, pr, col + t, subY, 1, uint8_t(w >> (16 * t + uAt)));
+                    yo_spread(T, tile + 2 * YD_TILE, pr, col + t, subY, 1, uint8_t(w >> (16 * t + vAt)));
+                }
+            }
+        }
+    }
+    else
+    {
+        yo_load_generic(T, fy, s.y, 0, 0, tile);
+        yo_load_generic(T, fu, s.u, subY, subX, tile + YD_TILE);
+        yo_load_generic(T, fv, s.v, subY, subX, tile + 2 * YD_TILE);
+    }
+    __syncthreads();
+    const int yq = (threadIdx.x & 15) * 4;
+    const float sc = float(1.0 / 255.0);
+    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
+    const int64_t np = int64_t(a.H) * a.W;
+    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
+    {
+        float o[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            // rows beyond the tile (yq + j >= ny) convert whatever the LDS holds (8-bit R, G, B whatever it is): never stored
+            const int at = yd_slot(yq + j, 0) * YG_PITCH + xx;
+            int r, g, b;
+            yuv_rgb8(tile[at], yuv_chroma(tile[YD_TILE + at], tile[2 * YD_TILE + at]), r, g, b);
             ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
         }
         ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);

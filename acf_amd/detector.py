@@ -149,10 +149,11 @@ class HipDetector:
             raise HipError(capi.E_INVALID, "tensor entry: dtype must be uint8, float16, bfloat16 or float32, not %s" % t.dtype)
         return codes[t.dtype]
 
-    def _image_of(self, t, layout, scale=None):
+    def _image_of(self, t, layout, scale=None, orient=0):
         """(device pointer, n, capi.ImageDesc) of a device tensor [n, c, H, W] (layout "nchw") or [n, H, W, c] ("nhwc", taken as the
         permuted view); the strides are the tensor's own: nothing is copied or made contiguous.  scale: the resized entries — the
-        tensor is the unreduced frame, the plan is for resize_dims of its size."""
+        tensor is the unreduced frame, the plan is for resize_dims of its size.  orient: the oriented entries — the tensor is the
+        frame as stored, the plan is for oriented_dims of its size."""
         if layout not in ("nchw", "nhwc"):
             raise HipError(capi.E_INVALID, "tensor entry: layout must be \"nchw\" or \"nhwc\"")
         if t.dim() != 4 or not t.is_cuda:
@@ -165,19 +166,39 @@ class HipDetector:
                 raise HipError(capi.E_UNSUPPORTED, "resized tensor entry: uint8 only, not %s" % t.dtype)
             if ch != self.d_in:
                 raise HipError(capi.E_INVALID, "resized tensor entry: the tensor has c = %d, the plan %d" % (ch, self.d_in))
+        elif orient:
+            if ch != self.d_in:
+                raise HipError(capi.E_INVALID, "oriented tensor entry: the tensor has c = %d, the plan %d" % (ch, self.d_in))
         elif (h, w, ch) != (self.H, self.W, self.d_in):
             raise HipError(capi.E_INVALID, "tensor entry: the tensor is c = %d, H = %d, W = %d; the plan is for %d, %d, %d" % (ch, h, w, self.d_in, self.H, self.W))
         sn, sc, sy, sx = t.stride()
         return t.data_ptr(), n, capi.ImageDesc(self._torch_dtype_code(t), ch, sn, sc, sy, sx)
 
-    def pyramid_tensor(self, t, layout="nchw"):
-        """t: device tensor [n, c, H, W] of any strides (or [n, H, W, c] with layout="nhwc"), uint8 / float16 / bfloat16 / float32."""
-        ptr, n, desc = self._image_of(t, layout)
-        self._chk(self.lib.acf_hip_pyramid_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+    def pyramid_tensor(self, t, layout="nchw", orient=0):
+        """t: device tensor [n, c, H, W] of any strides (or [n, H, W, c] with layout="nhwc"), uint8 / float16 / bfloat16 / float32.
+        orient (capi.ORIENT_*, rot + 4 * mirror): t is the frame as stored, [n, c, Hs, Ws]; the plan is for oriented_dims(Hs, Ws, orient)
+        and detections are in the upright frame (unorient_boxes maps them back).  0 takes the un-oriented entry."""
+        ptr, n, desc = self._image_of(t, layout, orient=orient)
+        if not orient:
+            self._chk(self.lib.acf_hip_pyramid_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+            return
+        rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
+        self._chk(self.lib.acf_hip_pyramid_image_oriented(self.ctx, C.c_void_p(ptr), n, C.byref(desc), rows, cols, orient))
 
-    def run_tensor(self, t, layout="nchw"):
-        ptr, n, desc = self._image_of(t, layout)
-        self._chk(self.lib.acf_hip_run_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+    def run_tensor(self, t, layout="nchw", orient=0):
+        ptr, n, desc = self._image_of(t, layout, orient=orient)
+        if not orient:
+            self._chk(self.lib.acf_hip_run_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+            return
+        rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
+        self._chk(self.lib.acf_hip_run_image_oriented(self.ctx, C.c_void_p(ptr), n, C.byref(desc), rows, cols, orient))
+
+    def pyramid_image_oriented(self, ptr, n, desc, src_rows, src_cols, orient):
+        """The raw oriented entry: desc describes frames of src_rows x src_cols; the plan is for oriented_dims of them."""
+        self._chk(self.lib.acf_hip_pyramid_image_oriented(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, orient))
+
+    def run_image_oriented(self, ptr, n, desc, src_rows, src_cols, orient):
+        self._chk(self.lib.acf_hip_run_image_oriented(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, orient))
 
     def pyramid_tensor_resized(self, t, scale, layout="nchw"):
         """t: uint8 device tensor of the UNREDUCED frames [n, c, rows, cols] of any strides; the plan is for resize_dims(rows, cols,
@@ -259,12 +280,27 @@ class HipDetector:
             raise HipError(rc, "acf_hip_yuv_extent")
         return list(lo), list(hi)
 
-    def pyramid_yuv(self, base, n, desc):
-        """base: a torch uint8 CUDA tensor (its first byte is the base; it need not be contiguous) or a device pointer."""
-        self._chk(self.lib.acf_hip_pyramid_yuv(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, C.byref(desc)))
+    def pyramid_yuv(self, base, n, desc, orient=0, src_rows=None, src_cols=None):
+        """base: a torch uint8 CUDA tensor (its first byte is the base; it need not be contiguous) or a device pointer.
+        orient (capi.ORIENT_*): desc describes the frame as stored, src_rows x src_cols; the plan is for oriented_dims of that."""
+        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
+        if not orient and src_rows is None:
+            self._chk(self.lib.acf_hip_pyramid_yuv(self.ctx, ptr, n, C.byref(desc)))
+        else:
+            self._chk(self.lib.acf_hip_pyramid_yuv_oriented(self.ctx, ptr, n, C.byref(desc), *self._src_size(orient, src_rows, src_cols), orient))
 
-    def run_yuv(self, base, n, desc):
-        self._chk(self.lib.acf_hip_run_yuv(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, C.byref(desc)))
+    def run_yuv(self, base, n, desc, orient=0, src_rows=None, src_cols=None):
+        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
+        if not orient and src_rows is None:
+            self._chk(self.lib.acf_hip_run_yuv(self.ctx, ptr, n, C.byref(desc)))
+        else:
+            self._chk(self.lib.acf_hip_run_yuv_oriented(self.ctx, ptr, n, C.byref(desc), *self._src_size(orient, src_rows, src_cols), orient))
+
+    def _src_size(self, orient, src_rows, src_cols):
+        """The stored frame's size where the caller left it out: the plan's, turned back (odd rot swaps rows and columns)."""
+        if src_rows is not None and src_cols is not None:
+            return src_rows, src_cols
+        return (self.W, self.H) if orient & 1 else (self.H, self.W)
 
     def pyramid_yuv_resized(self, base, n, desc, src_rows, src_cols, scale):
         """desc describes frames of src_rows x src_cols; the plan is for resize_dims(src_rows, src_cols, scale).  Conversion, the apps'
@@ -293,11 +329,15 @@ class HipDetector:
         mk = lambda t: capi.YuvPlane(t.data_ptr() - base, t.stride(0) if t.shape[0] > 1 else 0, t.stride(1), t.stride(2))
         return base, y.shape[0], capi.YuvDesc(mk(y), mk(u), mk(v), sub_x, sub_y)
 
-    def run_yuv_planes(self, y, u, v, sub_x=1, sub_y=1, scale=None):
+    def run_yuv_planes(self, y, u, v, sub_x=1, sub_y=1, scale=None, orient=0):
         """Three separately allocated planes (a software decoder's frame): y [n, H, W], u and v [n, ceil(H / 2^sub_y), ceil(W / 2^sub_x)].
         scale: the planes are the unreduced frame (run_yuv_resized; the plan is for resize_dims of y's size)."""
         base, n, desc = self.yuv_planes_desc(y, u, v, sub_x, sub_y)
-        if scale is None:
+        if orient:
+            if scale is not None:
+                raise HipError(capi.E_UNSUPPORTED, "run_yuv_planes: orient and scale together (the resized entries are not oriented)")
+            self.run_yuv(base, n, desc, orient, y.shape[-2], y.shape[-1])
+        elif scale is None:
             self.run_yuv(base, n, desc)
         else:
             self.run_yuv_resized(base, n, desc, y.shape[-2], y.shape[-1], scale)
@@ -311,9 +351,13 @@ class HipDetector:
         self.synchronize()
         return out
 
-    def stream_open_yuv(self, desc, frame_bytes, cap=1024, depth=2):
-        """The streaming front end for host frames of frame_bytes each, described by desc (stride_n == frame_bytes)."""
-        self._chk(self.lib.acf_hip_stream_open_yuv(self.ctx, C.byref(desc), frame_bytes, cap, depth))
+    def stream_open_yuv(self, desc, frame_bytes, cap=1024, depth=2, orient=0, src_rows=None, src_cols=None):
+        """The streaming front end for host frames of frame_bytes each, described by desc (stride_n == frame_bytes).
+        orient: frames as stored, src_rows x src_cols; every submit runs run_yuv(..., orient) on its slot."""
+        if not orient and src_rows is None:
+            self._chk(self.lib.acf_hip_stream_open_yuv(self.ctx, C.byref(desc), frame_bytes, cap, depth))
+        else:
+            self._chk(self.lib.acf_hip_stream_open_yuv_oriented(self.ctx, C.byref(desc), frame_bytes, *self._src_size(orient, src_rows, src_cols), orient, cap, depth))
         self._stream_cap = cap
 
     def stream_open_yuv_resized(self, desc, frame_bytes, src_rows, src_cols, scale, cap=1024, depth=2):
@@ -355,6 +399,31 @@ class HipDetector:
         inv = np.float32(1.0) / np.float32(scale)
         for k in ("x", "y", "w", "h"):
             out[k] = np.rint((dets[k].astype(np.float32) * inv).astype(np.float64)).astype(out[k].dtype)
+        return out
+
+    # ---- rotated and mirrored frames (the oriented entries): host arithmetic
+    @staticmethod
+    def oriented_dims(src_rows, src_cols, orient):
+        """(h, w) of the upright frame of a stored src_rows x src_cols frame: what the plan must be for."""
+        h, w = C.c_int(), C.c_int()
+        rc = capi.load().acf_hip_oriented_dims(src_rows, src_cols, orient, C.byref(h), C.byref(w))
+        if rc:
+            raise HipError(rc, "acf_hip_oriented_dims")
+        return h.value, w.value
+
+    @staticmethod
+    def unorient_boxes(dets, orient, src_rows, src_cols):
+        """Boxes of the upright frame -> the boxes covering the same pixels in the stored frame (acf_hip_unorient_rect); dets: DET_DTYPE array."""
+        out = dets.copy()
+        lib = capi.load()
+        a, b = (C.c_int32 * 4)(), (C.c_int32 * 4)()
+        for i in range(len(dets)):
+            a[:] = [int(dets[k][i]) for k in ("x", "y", "w", "h")]
+            rc = lib.acf_hip_unorient_rect(orient, src_rows, src_cols, a, b)
+            if rc:
+                raise HipError(rc, "acf_hip_unorient_rect")
+            for j, k in enumerate(("x", "y", "w", "h")):
+                out[k][i] = b[j]
         return out
 
     # ---- streaming front end (pinned host frames in, pinned host records out)

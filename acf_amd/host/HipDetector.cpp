@@ -582,6 +582,32 @@ bool HipDetector::resizedPlan(int rows, int cols, int& planRows, int& planCols) 
     return true;
 }
 
+// setInputOrientation in the tensor and YUV entries: the plan's size for stored frames of rows x cols (acf_hip_oriented_dims); false: upright
+bool HipDetector::orientedPlan(int rows, int cols, bool resized, int& planRows, int& planCols) const
+{
+    if (m_orient == 0)
+    {
+        return false;
+    }
+    if (resized)
+    {
+        throw Exception(ACF_HIP_E_UNSUPPORTED, "setInputOrientation and setMinObjectWidth together: the resized entries are not oriented");
+    }
+    check(m_api->acf_hip_oriented_dims(rows, cols, m_orient, &planRows, &planCols), "acf_hip_oriented_dims");
+    return true;
+}
+
+Rect HipDetector::unorientRect(const Rect& o, int orient, int srcRows, int srcCols)
+{
+    const int32_t in[4] = { o.x, o.y, o.width, o.height };
+    int32_t out[4];
+    if (hip::load().acf_hip_unorient_rect(orient, srcRows, srcCols, in, out))
+    {
+        throw Exception(ACF_HIP_E_INVALID, "unorientRect: orient must be 0 .. 7, srcRows and srcCols >= 1");
+    }
+    return Rect(out[0], out[1], out[2], out[3]);
+}
+
 // every frame's detections of the batch just run; resized: mapped back as operator()(packed) does (Resizer::operator()(objects))
 void HipDetector::fetchBatch(int nFrames, bool resized, std::vector<RectVec>& objects, std::vector<RealVec>* scores)
 {
@@ -612,9 +638,14 @@ int HipDetector::detectImages(const void* framesDev, int nFrames, int rows, int 
     {
         throw Exception(ACF_HIP_E_UNSUPPORTED, "detectImages: setMinObjectWidth takes 8-bit images (cv::resize's CV_32F arithmetic is not restated)");
     }
+    const bool oriented = orientedPlan(rows, cols, resized, planRows, planCols);
     ensurePlan(planRows, planCols, desc.channels, nFrames);
     syncNms();
-    if (resized)
+    if (oriented) // (boxes in the upright frame)
+    {
+        check(m_api->acf_hip_run_image_oriented(m_ctx, framesDev, nFrames, &desc, rows, cols, m_orient), "acf_hip_run_image_oriented");
+    }
+    else if (resized)
     {
         check(m_api->acf_hip_run_image_resized(m_ctx, framesDev, nFrames, &desc, rows, cols, double(inputScale())), "acf_hip_run_image_resized");
     }
@@ -631,9 +662,14 @@ int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int co
 {
     int planRows, planCols;
     const bool resized = resizedPlan(rows, cols, planRows, planCols);
+    const bool oriented = orientedPlan(rows, cols, resized, planRows, planCols);
     ensurePlan(planRows, planCols, 3, nFrames);
     syncNms();
-    if (resized)
+    if (oriented) // (boxes in the upright frame)
+    {
+        check(m_api->acf_hip_run_yuv_oriented(m_ctx, baseDev, nFrames, &desc, rows, cols, m_orient), "acf_hip_run_yuv_oriented");
+    }
+    else if (resized)
     {
         check(m_api->acf_hip_run_yuv_resized(m_ctx, baseDev, nFrames, &desc, rows, cols, double(inputScale())), "acf_hip_run_yuv_resized");
     }
@@ -740,12 +776,18 @@ void HipDetector::streamOpenYuv(int rows, int cols, const acf_hip_yuv_desc& desc
 {
     int planRows, planCols;
     const bool resized = resizedPlan(rows, cols, planRows, planCols);
+    const bool oriented = orientedPlan(rows, cols, resized, planRows, planCols);
     ensurePlan(planRows, planCols, 3, maxBatch);
     (void)m_api->acf_hip_stream_close(m_ctx);
     check(m_api->acf_hip_set_input_resize(m_ctx, 0, 0, 1.0), "acf_hip_set_input_resize");
     m_srcRows = rows;
     m_srcCols = cols;
-    if (resized) // (streamCollect maps the boxes back)
+    if (oriented) // (streamCollect returns boxes in the upright frame)
+    {
+        check(m_api->acf_hip_stream_open_yuv_oriented(m_ctx, &desc, int64_t(frameBytes), rows, cols, m_orient, maxDetectionsPerFrame, depth),
+            "acf_hip_stream_open_yuv_oriented");
+    }
+    else if (resized) // (streamCollect maps the boxes back)
     {
         check(m_api->acf_hip_stream_open_yuv_resized(m_ctx, &desc, int64_t(frameBytes), rows, cols, double(inputScale()), maxDetectionsPerFrame, depth),
             "acf_hip_stream_open_yuv_resized");

@@ -266,6 +266,15 @@ public:
     int getMinObjectWidth() const { return m_minObjectWidth; }
     float inputScale() const { return m_minObjectWidth >= 0 ? float(getWindowSize().width) / float(m_minObjectWidth) : 1.f; }
     static Rect unscale(const Rect& o, float scale); // Resizer::operator()(objects) for one box
+    // Rotated and mirrored frames (a decoder's rotation tag, a mirroring front camera): detectImages, detectYuv and streamOpenYuv take
+    // the frames as they are stored, rows x cols, in orientation `orient` (ACF_HIP_ORIENT_*: rot + 4 * mirror; the upright frame is
+    // the stored one mirrored left-right first, then turned rot quarter turns clockwise) and search the upright frame — the ingest
+    // kernel reads the stored frame where it lies (include/acf_hip.h, acf_hip_run_image_oriented / acf_hip_run_yuv_oriented).  Boxes
+    // come back in the UPRIGHT frame's coordinates; unorientRect maps one to the stored frame.  0 (default): off.  Not together with
+    // setMinObjectWidth (ACF_HIP_E_UNSUPPORTED: the resized entries are not oriented).
+    void setInputOrientation(int orient) { m_orient = orient; }
+    int getInputOrientation() const { return m_orient; }
+    static Rect unorientRect(const Rect& o, int orient, int srcRows, int srcCols); // acf_hip_unorient_rect
     int acfModify(const Modify& params); // acfModify.cpp:83-152
 
     // Detection: planar f32 transposed image (RGB in [0,1], or LUV after setIsLuv(true)); ACF.cpp:246-265.
@@ -404,6 +413,7 @@ private:
     static MatP hconcatHist(const float* src, int firstPlane, int nOrients, int hC, int wC);
     void fetch(int frame, RectVec& objects, RealVec* scores);
     bool resizedPlan(int rows, int cols, int& planRows, int& planCols) const;
+    bool orientedPlan(int rows, int cols, bool resized, int& planRows, int& planCols) const;
     void fetchBatch(int nFrames, bool resized, std::vector<RectVec>& objects, std::vector<RealVec>* scores);
     void detect1(const float* f32, const uint8_t* u8, int rows, int cols, DetectionVec& objects);
     void finish(DetectionVec& bbs, RectVec& objects, RealVec* scores, bool forceHostNms = false) const; // ACF.cpp:332-364
@@ -423,6 +433,7 @@ private:
     int m_nChns = 0;
     std::vector<float> m_upright; // scratch for operator()(interleaved)
     int m_streamCap = 0, m_streamPix = -1, m_streamStride = 0;
+    int m_orient = 0; // setInputOrientation
     int m_minObjectWidth = -1, m_srcRows = 0, m_srcCols = 0; // frame size handed to the 8-bit entries (== the plan's without a resize)
     MatLoggerType m_logger;
     StreamLoggerType m_streamLogger;

@@ -6,9 +6,12 @@
 //   acf_hip_detect --model m.acfm --frames f.u8 --u8 rgb|bgr|rgba|bgra|gray|nv12|nv21 --rows H --cols W --count N [--stream B] [--min-width M] ...
 //                  packed 8-bit upright frames (nv12 / nv21: tight YUV 4:2:0 video frames); --stream B: batches of B frames through streamSubmit/streamCollect
 //   acf_hip_detect --model m.acfm --frames f.yuv --yuv i420|yv12|i422|i444|yuyv|uyvy|yvyu|nv12|nv21 --rows H --cols W --count N [--stream B] [--min-width M]
+//                  [--orient K]
 //                  tight YUV video frames of the named layout through detectYuv (one batch; the frames in page-locked memory, which the
 //                  device reads), or --stream B through streamOpenYuv / streamSubmit / streamCollect; --min-width M: reduced on the device
-//                  first, in the ingest kernel (acf_hip_run_yuv_resized), the boxes mapped back
+//                  first, in the ingest kernel (acf_hip_run_yuv_resized), the boxes mapped back; --orient K (0 .. 7 = rot + 4 * mirror:
+//                  the frames are stored mirrored / turned; H x W is the STORED size): the upright frame is searched
+//                  (setInputOrientation), the boxes are printed in the UPRIGHT frame's coordinates and every "frame" line says so
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
@@ -59,9 +62,9 @@ static uint64_t fnv(const acf::MatP& m)
     return hsh;
 }
 
-static void printFrame(int f, const HipDetector::RectVec& objs, const HipDetector::RealVec& scores)
+static void printFrame(int f, const HipDetector::RectVec& objs, const HipDetector::RealVec& scores, const std::string& note = "")
 {
-    std::printf("frame %d %zu\n", f, objs.size());
+    std::printf("frame %d %zu%s\n", f, objs.size(), note.c_str());
     for (size_t i = 0; i < objs.size(); i++)
     {
         const float s = float(scores[i]);
@@ -212,6 +215,13 @@ int main(int argc, char** argv)
             const int H = std::stoi(a.at("rows")), W = std::stoi(a.at("cols")), cnt = std::stoi(a.at("count"));
             size_t per = 0;
             const acf_hip_yuv_desc desc = HipDetector::yuvLayout(kYuv.at(a["yuv"]), H, W, 0, &per);
+            const int orient = a.count("orient") ? std::stoi(a["orient"]) : 0;
+            std::string note; // what the boxes' coordinates are, when they are not the stored frame's
+            if (orient)
+            {
+                det.setInputOrientation(orient);
+                note = " upright " + std::to_string(orient & 1 ? W : H) + "x" + std::to_string(orient & 1 ? H : W) + " orient " + std::to_string(orient);
+            }
             const int B = a.count("stream") ? std::stoi(a["stream"]) : cnt, depth = 2;
             uint8_t* pin[2] = { static_cast<uint8_t*>(HipDetector::pinnedAlloc(per * size_t(B))), static_cast<uint8_t*>(HipDetector::pinnedAlloc(per * size_t(B))) };
             std::ifstream is(a.at("frames"), std::ios::binary);
@@ -232,7 +242,7 @@ int main(int argc, char** argv)
                     det.streamCollect(inflight.front().first, objs, &scores);
                     for (size_t f = 0; f < objs.size(); f++)
                     {
-                        printFrame(inflight.front().second + int(f), objs[f], scores[f]);
+                        printFrame(inflight.front().second + int(f), objs[f], scores[f], note);
                     }
                     inflight.erase(inflight.begin());
                 };
@@ -259,7 +269,7 @@ int main(int argc, char** argv)
                 det.detectYuv(pin[0], cnt, H, W, desc, objs, &scores);
                 for (int f = 0; f < cnt; f++)
                 {
-                    printFrame(f, objs[size_t(f)], scores[size_t(f)]);
+                    printFrame(f, objs[size_t(f)], scores[size_t(f)], note);
                 }
             }
             HipDetector::pinnedFree(pin[0]);

@@ -57,6 +57,13 @@ struct Api
     ACF_HIP_FN(acf_hip_pyramid_image_resized)
     ACF_HIP_FN(acf_hip_run_image_resized)
     ACF_HIP_FN(acf_hip_stream_open_yuv_resized)
+    ACF_HIP_FN(acf_hip_pyramid_image_oriented)
+    ACF_HIP_FN(acf_hip_run_image_oriented)
+    ACF_HIP_FN(acf_hip_pyramid_yuv_oriented)
+    ACF_HIP_FN(acf_hip_run_yuv_oriented)
+    ACF_HIP_FN(acf_hip_stream_open_yuv_oriented)
+    ACF_HIP_FN(acf_hip_oriented_dims)
+    ACF_HIP_FN(acf_hip_unorient_rect)
     ACF_HIP_FN(acf_hip_resize_dims)
     ACF_HIP_FN(acf_hip_set_input_resize)
     ACF_HIP_FN(acf_hip_op_resize_u8)

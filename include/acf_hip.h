@@ -575,6 +575,65 @@ ACF_HIP_API int acf_hip_run_image_resized(acf_hip_ctx* ctx, const void* frames_d
 ACF_HIP_API int acf_hip_stream_open_yuv_resized(acf_hip_ctx* ctx, const acf_hip_yuv_desc* desc, int64_t frame_bytes, int src_rows, int src_cols,
     double scale, int cap, int depth);
 
+/* ---- rotated and mirrored frames in the tensor and YUV entries ---------
+ * Video is stored in sensor orientation with a rotation tag, and front cameras mirror; the cascade only finds upright objects.  The
+ * oriented entries read the frame where it lies, as the descriptor describes it at src_rows x src_cols (Hs x Ws), and detect on the
+ * upright frame — no rotated copy goes to device memory.  An orientation code is rot + 4 * mirror; the upright frame U of source S is
+ *     U = np.rot90(S[:, ::-1] if mirror else S, k=-rot)     (mirror left-right first, then rot quarter turns CLOCKWISE)
+ * so upright pixel (r, c) is source pixel (rs, cs):
+ *     rot 0: (r, c)   rot 1: (Hs-1-c, r)   rot 2: (Hs-1-r, Ws-1-c)   rot 3: (c, Ws-1-r);   mirror: cs becomes Ws-1-cs
+ * The plan must be for the upright size, acf_hip_oriented_dims(src_rows, src_cols, orient): Ws x Hs for odd rot.
+ * Definition: the existing entries composed, bit for bit —
+ *   image  the addressed elements of the descriptor at Hs x Ws re-arranged into U, then acf_hip_pyramid_image / run_image on a tight
+ *          upright image holding U (every dtype, channels 1 or 3, stride_c of any sign)
+ *   YUV    acf_hip_yuv_to_rgb8's R, G, B of the source frame (the chroma sample of source pixel (rs, cs) at (rs >> sub_y, cs >> sub_x):
+ *          chosen in SOURCE coordinates) re-arranged into U, then acf_hip_pyramid_u8 / run_u8 (ACF_HIP_PIX_RGB)
+ * every plane, level, hit, score bit and box, option "arith" = 1 included.  Detections are in U's coordinates; acf_hip_unorient_rect
+ * maps a box back to the source frame.  ACF_HIP_ORIENT_UPRIGHT is the un-oriented entry itself: the call forwards to it.
+ * acf_hip_image_extent / acf_hip_yuv_extent called with src_rows x src_cols give exactly the elements and bytes an oriented call
+ * reads (an orientation permutes the same pixel set), and no load covers an address outside the [first, last] span of the row and
+ * plane it belongs to.
+ * Option "profile": k_ingest_image_oriented_rows / k_ingest_yuv_oriented_rows (rot 0 / 2) and k_ingest_image_oriented_cols /
+ * k_ingest_yuv_oriented_cols (rot 1 / 3) with wide loads along the source rows — under the conditions of the un-oriented entries'
+ * vector forms, and for NV12 / NV21-like descriptions whose planes, row and frame strides are 4-aligned — else
+ * k_ingest_image_oriented_generic / k_ingest_yuv_oriented_generic (one element a lane, any description).
+ * Asynchronous on the context's stream; nothing is allocated after the first call; the calls always run plainly and leave a captured
+ * graph of acf_hip_run (option "graph") valid; ACF_HIP_TAP_IMAGE behaves as after acf_hip_pyramid_u8.
+ * ACF_HIP_E_INVALID: what the un-oriented entry refuses; orient outside 0 .. 7; src_rows / src_cols < 1; a plan whose h x w is not
+ * acf_hip_oriented_dims(...); an active acf_hip_set_input_resize; a five-plane plan.  ACF_HIP_E_UNSUPPORTED: option "streams" > 1.
+ * ACF_HIP_E_NOPLAN without a plan.
+ *  acf_hip_stream_open_yuv_oriented   acf_hip_stream_open_yuv's rules with the one-frame extents taken at src_rows x src_cols; every
+ *                                     submit runs acf_hip_run_yuv_oriented on its slot; submit / collect / close are unchanged
+ *  acf_hip_oriented_dims              host arithmetic: the upright h x w; ACF_HIP_E_INVALID for a bad code, size or null pointer
+ *  acf_hip_unorient_rect              host arithmetic, exact: the upright box {x, y, w, h} -> the box covering the same pixels in the
+ *                                     source frame: {x', y', w', h'} with, for even rot, x' = x or Ws - x - w, y' = y or Hs - y - h,
+ *                                     w' = w, h' = h, and for odd rot x' = y or Ws - y - h, y' = x or Hs - x - w, w' = h, h' = w (the
+ *                                     second form where that source index runs against the upright one); defined by the same
+ *                                     formula for boxes that reach outside the frame, as padded detections do */
+enum
+{
+    ACF_HIP_ORIENT_UPRIGHT = 0,        /* U = S */
+    ACF_HIP_ORIENT_ROT90 = 1,          /* S turned a quarter turn clockwise */
+    ACF_HIP_ORIENT_ROT180 = 2,
+    ACF_HIP_ORIENT_ROT270 = 3,         /* a quarter turn anticlockwise */
+    ACF_HIP_ORIENT_MIRROR = 4,         /* S[:, ::-1] */
+    ACF_HIP_ORIENT_MIRROR_ROT90 = 5,   /* the anti-transpose S[::-1, ::-1].T */
+    ACF_HIP_ORIENT_MIRROR_ROT180 = 6,  /* S[::-1, :] */
+    ACF_HIP_ORIENT_MIRROR_ROT270 = 7   /* the transpose S.T */
+};
+ACF_HIP_API int acf_hip_pyramid_image_oriented(acf_hip_ctx* ctx, const void* frames_dev, int n_frames, const acf_hip_image_desc* desc, int src_rows,
+    int src_cols, int orient);
+ACF_HIP_API int acf_hip_run_image_oriented(acf_hip_ctx* ctx, const void* frames_dev, int n_frames, const acf_hip_image_desc* desc, int src_rows, int src_cols,
+    int orient);
+ACF_HIP_API int acf_hip_pyramid_yuv_oriented(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc, int src_rows,
+    int src_cols, int orient);
+ACF_HIP_API int acf_hip_run_yuv_oriented(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc, int src_rows, int src_cols,
+    int orient);
+ACF_HIP_API int acf_hip_stream_open_yuv_oriented(acf_hip_ctx* ctx, const acf_hip_yuv_desc* desc, int64_t frame_bytes, int src_rows, int src_cols,
+    int orient, int cap, int depth);
+ACF_HIP_API int acf_hip_oriented_dims(int src_rows, int src_cols, int orient, int* h, int* w);
+ACF_HIP_API int acf_hip_unorient_rect(int orient, int src_rows, int src_cols, const int32_t in[4], int32_t out[4]);
+
 /* ---- streaming front end ---------------------------------------------
  * The overlap of transfer and compute that GPUDetectionPipeline::runFast gets
  * from its two-frame texture FIFO (GPUDetectionPipeline.cpp:357-437), expressed
