@@ -245,6 +245,12 @@ def load():
         "acf_hip_run_yuv_oriented": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_int], C.c_int),
         "acf_hip_stream_open_yuv_oriented": ([ctx, C.POINTER(YuvDesc), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int], C.c_int),
         "acf_hip_oriented_dims": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_pyramid_image_oriented_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_run_image_oriented_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_pyramid_yuv_oriented_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_run_yuv_oriented_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_stream_open_yuv_oriented_resized": ([ctx, C.POINTER(YuvDesc), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int], C.c_int),
+        "acf_hip_oriented_resized_dims": ([C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
         "acf_hip_unorient_rect": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
@@ -315,6 +321,8 @@ DECLARED_SYMBOLS = [
     "acf_hip_stream_open_yuv_resized",
     "acf_hip_pyramid_image_oriented", "acf_hip_run_image_oriented", "acf_hip_pyramid_yuv_oriented", "acf_hip_run_yuv_oriented",
     "acf_hip_stream_open_yuv_oriented", "acf_hip_oriented_dims", "acf_hip_unorient_rect",
+    "acf_hip_pyramid_image_oriented_resized", "acf_hip_run_image_oriented_resized", "acf_hip_pyramid_yuv_oriented_resized",
+    "acf_hip_run_yuv_oriented_resized", "acf_hip_stream_open_yuv_oriented_resized", "acf_hip_oriented_resized_dims",
 ]
 
 

@@ -401,6 +401,7 @@ struct acf_hip_ctx
         ResizeTables t;
         int32_t *d_xlin = nullptr, *d_ylin = nullptr, *d_xrun = nullptr, *d_yrun = nullptr, *d_xtap = nullptr, *d_ytap = nullptr;
         uint8_t* d_out = nullptr; // [maxBatch][plan.H][plan.W][4]
+        int osBand[2] = { -1, -1 }; // the oriented resized entries: reduced rows a band for rot 0 / 2 and rot 1 / 3 (orientedResizedBand; -1: not yet)
     } rz;
     // the resized tensor / YUV entries (acf_hip_pyramid_image_resized / _yuv_resized): the tap tables of the last (rows, cols, scale),
     // uploaded at the first call with a new key and kept until another key or acf_hip_plan (d_out is not used: k_ingest_resized
@@ -477,6 +478,7 @@ enum : uint32_t
     FB_TILED_POOLED1 = 1u << 12,    // depth 1 on float cells: the pooled tile kernel instead of the staged queue
     FB_YUV_UNFUSED = 1u << 13,      // NV12 / NV21 as k_yuv420_to_rgb8 + k_ingest_u8 instead of k_ingest_yuv420
     FB_TRIY_STORED_U = 1u << 14,    // convTri's x pass writes the blocked plane U (instead of checkpoints replayed by k_triy_chns)
+    FB_ORIENTED_RESIZED_GENERIC = 1u << 15, // the oriented resized entries gather from global memory (instead of staging the footprint in LDS)
 };
 uint32_t fallbackMask()
 {
@@ -486,7 +488,8 @@ uint32_t fallbackMask()
             { "resample_no_pair", FB_RESAMPLE_NO_PAIR }, { "resample_no_up", FB_RESAMPLE_NO_UP }, { "resample_generic", FB_RESAMPLE_GENERIC },
             { "level_groups", FB_LEVEL_GROUPS }, { "ldcf_unfused", FB_LDCF_UNFUSED }, { "no_dedup", FB_NO_DEDUP }, { "no_tail_codes", FB_NO_TAIL_CODES },
             { "tail3", FB_TAIL3 }, { "tiled_staged", FB_TILED_STAGED }, { "tiled_pooled1", FB_TILED_POOLED1 },
-            { "yuv_unfused", FB_YUV_UNFUSED }, { "triy_stored_u", FB_TRIY_STORED_U } };
+            { "yuv_unfused", FB_YUV_UNFUSED }, { "triy_stored_u", FB_TRIY_STORED_U },
+            { "oriented_resized_generic", FB_ORIENTED_RESIZED_GENERIC } };
         uint32_t m = 0;
         const char* e = getenv("ACF_HIP_FORCE_FALLBACK");
         std::string s = e ? e : "";
@@ -2303,7 +2306,8 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
 }
 
 // acf_hip_stream_open_yuv, acf_hip_stream_open_yuv_resized (resized: frames of srcRows x srcCols, reduced by scale) and
-// acf_hip_stream_open_yuv_oriented (orient: frames of srcRows x srcCols turned to the plan's size; the entry has checked them)
+// acf_hip_stream_open_yuv_oriented (orient: frames of srcRows x srcCols turned to the plan's size; the entry has checked them);
+// acf_hip_stream_open_yuv_oriented_resized: both (turned, then reduced)
 static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc* desc, int64_t frameBytes, bool resized, int srcRows, int srcCols, double scale,
     int cap, int depth, int orient = 0)
 {
@@ -2327,8 +2331,9 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     }
     if (resized)
     {
+        // (resized and oriented: the tables and the plan are for the upright size)
         HIPCHK(c, hipSetDevice(c->device));
-        if (int rc = resizedTables(c, who, srcRows, srcCols, scale)) return rc;
+        if (int rc = resizedTables(c, who, (orient & 1) ? srcCols : srcRows, (orient & 1) ? srcRows : srcCols, scale)) return rc;
     }
     const bool ownSize = resized || orient; // the frames are srcRows x srcCols, not the plan's size
     int64_t first[3], last[3];
@@ -2344,7 +2349,8 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     {
         return fail(c, ACF_HIP_E_INVALID, w + "stride_n of every plane must be frame_bytes");
     }
-    c->stSrc = FrameSource{ SRC_YUV, nullptr, resized ? "pyramid_yuv_resized" : (orient ? "pyramid_yuv_oriented" : "pyramid_yuv"), 0, 0, {}, *desc, resized, srcRows,
+    c->stSrc = FrameSource{ SRC_YUV, nullptr,
+        resized ? (orient ? "pyramid_yuv_oriented_resized" : "pyramid_yuv_resized") : (orient ? "pyramid_yuv_oriented" : "pyramid_yuv"), 0, 0, {}, *desc, resized, srcRows,
         srcCols, scale, orient };
     return streamSlots(c, frameBytes, cap, depth);
 }
@@ -2357,6 +2363,21 @@ int acf_hip_stream_open_yuv(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_
 int acf_hip_stream_open_yuv_resized(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, double scale, int cap, int depth)
 {
     return streamOpenYuv(c, "stream_open_yuv_resized", desc, frameBytes, true, srcRows, srcCols, scale, cap, depth);
+}
+
+int acf_hip_stream_open_yuv_oriented_resized(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, int orient, double scale,
+    int cap, int depth)
+{
+    if (int rc = needPlan(c, "stream_open_yuv_oriented_resized")) return rc;
+    if (orient < 0 || orient > 7 || srcRows < 1 || srcCols < 1)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv_oriented_resized: orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
+    }
+    if (orient == 0)
+    {
+        return acf_hip_stream_open_yuv_resized(c, desc, frameBytes, srcRows, srcCols, scale, cap, depth);
+    }
+    return streamOpenYuv(c, "stream_open_yuv_oriented_resized", desc, frameBytes, true, srcRows, srcCols, scale, cap, depth, orient);
 }
 
 int acf_hip_stream_open_yuv_oriented(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, int orient, int cap, int depth)

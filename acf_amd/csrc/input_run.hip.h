@@ -5,11 +5,12 @@
 //
 //   u8Geom, imageDescBad, yuvDescBad, yuvExtent      what a layout or a description is, by itself
 //   the kernel tables and form choosers              ingestKernel .. resizedKernel, imageLoadForm, yuvLoadForm, yuvIsSemiPlanar; the oriented
-//                                                    entries: imageOrientedKernel, yuvOrientedKernel, orientSrc, orientedBad, yuvIsAlignedPairs
+//                                                    entries: imageOrientedKernel, yuvOrientedKernel, orientSrc, orientedBad, yuvIsAlignedPairs;
+//                                                    the oriented resized entries: orientedResizedKernel, orientedResizedBand, planOrientedResized
 //   launchYuvToRgb, launchResizeU8, launchColour     the preludes and the colour conversion (ops.hip.h and crops_run.hip.h call them too)
 //   installResizeTables, resizedTables               the tap tables of acf_hip_set_input_resize (c->rz) and of the resized entries (c->rzIn)
 //   planIngest                                       FrameSource -> IngestPlan, or the refusal
-//   the entries that are only about input            acf_hip_pyramid_u8 / _image / _yuv / *_resized / *_oriented and their run_ twins, the extents
+//   the entries that are only about input            acf_hip_pyramid_u8 / _image / _yuv / *_resized / *_oriented / *_oriented_resized and their run_ twins, the extents
 //                                                    and layouts, acf_hip_set_yuv_layout, acf_hip_set_input_resize, acf_hip_yuv_to_rgb8
 #pragma once
 
@@ -24,6 +25,7 @@ using YuvDescKernel = void (*)(IngestArgs, YuvDescSrc);
 using ResizedKernel = void (*)(IngestArgs, ResizedSrc);
 using ImageOrientedKernel = void (*)(IngestArgs, ImageOrientedSrc);
 using YuvOrientedKernel = void (*)(IngestArgs, YuvOrientedSrc);
+using OrientedResizedKernel = void (*)(IngestArgs, OrientedResizedSrc);
 
 static IngestKernel ingestKernel(int mode, bool aligned)
 {
@@ -102,6 +104,16 @@ static YuvOrientedKernel yuvOrientedKernel(int mode)
     static const YuvOrientedKernel table[4] = { k_ingest_yuv_oriented<IG_PLANAR>, k_ingest_yuv_oriented<IG_LUV_VEC>, k_ingest_yuv_oriented<IG_LUV>,
         k_ingest_yuv_oriented<IG_GRAY> };
     return table[mode];
+}
+
+// k_ingest_oriented_resized<source, conversion, staged>: [RS_*][IG_*], the LDS-staged form or the global gather
+static OrientedResizedKernel orientedResizedKernel(int src, int mode, bool staged)
+{
+#define ORK(SRC, ST) { k_ingest_oriented_resized<SRC, IG_PLANAR, ST>, k_ingest_oriented_resized<SRC, IG_LUV_VEC, ST>, k_ingest_oriented_resized<SRC, IG_LUV, ST>, \
+                       k_ingest_oriented_resized<SRC, IG_GRAY, ST> }
+    static const OrientedResizedKernel table[2][2][4] = { { ORK(RS_IMAGE, false), ORK(RS_YUV, false) }, { ORK(RS_IMAGE, true), ORK(RS_YUV, true) } };
+#undef ORK
+    return table[staged][src][mode];
 }
 
 static bool pixIsYuv(int pix)
@@ -568,6 +580,42 @@ static bool yuvIsAlignedPairs(const YuvDescSrc& s, int& vFirst)
            (at + uintptr_t(s.y.off)) % 4 == 0 && s.y.sr % 4 == 0 && s.y.sn % 4 == 0 && (at + uintptr_t(c0)) % 4 == 0 && s.u.sr % 4 == 0 && s.u.sn % 4 == 0;
 }
 
+// The staged form of k_ingest_oriented_resized marches a 64 x 64 reduced tile in bands of reduced rows; the band for tables t: the tile
+// split into the fewest equal bands (64, 32, 22, 16, 13, 11, 10, 8 rows) such that the footprint of every band of every tile (rz_span,
+// the kernel's own arithmetic) fits OS_STAGE dwords at the kernel's pitch (stored columns | 1; quarter turns: the band's rows are the
+// stored columns).  0: not even bands of OS_MIN_BAND rows fit (scales under 1 / 4): the generic form.
+static int orientedResizedBand(const ResizeTables& t, bool swap)
+{
+    const auto span = [&](bool y, int d0, int d1) {
+        int f, l;
+        rz_span(t.mode, y ? t.isy : t.isx, y ? t.rows : t.cols, (y ? t.ylin : t.xlin).data(), (y ? t.yrun : t.xrun).data(), (y ? t.ytap : t.xtap).data(), y, d0, d1, f, l);
+        return l - f + 1;
+    };
+    int fw = 1;
+    for (int x0 = 0; x0 < t.dcols; x0 += IG_T)
+    {
+        fw = std::max(fw, span(false, x0, std::min(x0 + IG_T, t.dcols) - 1));
+    }
+    for (int nb = 1; nb <= IG_T / OS_MIN_BAND; nb++)
+    {
+        const int b = cdiv(IG_T, nb);
+        int fh = 1;
+        for (int y0 = 0; y0 < t.drows; y0 += IG_T)
+        {
+            const int ny = std::min(IG_T, t.drows - y0);
+            for (int yb = 0; yb < ny; yb += b)
+            {
+                fh = std::max(fh, span(true, y0 + yb, y0 + std::min(yb + b, ny) - 1));
+            }
+        }
+        if ((swap ? int64_t(fw) * (fh | 1) : int64_t(fh) * (fw | 1)) <= OS_STAGE)
+        {
+            return b;
+        }
+    }
+    return 0;
+}
+
 // One call's ingest, decided once (planIngest); PyramidRun::ingest only reads it
 struct IngestPlan
 {
@@ -591,6 +639,7 @@ struct IngestPlan
         YuvDescSrc yuv;
         ImageOrientedSrc imageOriented;
         YuvOrientedSrc yuvOriented;
+        OrientedResizedSrc orientedResized;
     } second{};
     const char* profName = nullptr;   // (static strings: prof keeps the pointer)
     const char* launchName = nullptr;
@@ -603,7 +652,48 @@ struct IngestPlan
     void set(ResizedKernel k, const ResizedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.resized = s; }
     void set(ImageOrientedKernel k, const ImageOrientedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.imageOriented = s; }
     void set(YuvOrientedKernel k, const YuvOrientedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.yuvOriented = s; }
+    void set(OrientedResizedKernel k, const OrientedResizedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.orientedResized = s; }
 };
+
+// The upright size of a source that is both oriented and resized — what its tap tables and its plan are for — or the refusal
+static int orientedResizedUpright(acf_hip_ctx* c, const std::string& who, const FrameSource& src, int& rows, int& cols)
+{
+    rows = src.srcRows;
+    cols = src.srcCols;
+    if (src.orient < 0 || src.orient > 7)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "orient must be 0 .. 7 (ACF_HIP_ORIENT_*)");
+    }
+    if (src.orient & 1)
+    {
+        std::swap(rows, cols);
+    }
+    return ACF_HIP_OK;
+}
+
+// A source that is both resized and oriented (r.r.im or r.r.yuv filled in; c->rzIn holds the tables of the upright size): the form of
+// k_ingest_oriented_resized, by what was measured (profiles/oriented_resized_entry.md).  Staged for quarter turns where the footprint fits
+// (orientedResizedBand): there the generic form's lanes each read another stored row (3.2 x / 5.2 x slower at scale 1 / 2 and 80 / 150).
+// Generic for rot 0 / 2 — its lanes already run along the stored rows, forwards or backwards, and the stage did not beat it (1.03 against
+// 0.74 ms at 1 / 2, 1.74 against 1.70 ms at 80 / 150) —, for footprints that do not fit, and when forced.
+static void planOrientedResized(acf_hip_ctx* c, int kind, int mode, bool vec, OrientedResizedSrc s, const FrameSource& src, IngestPlan& ip)
+{
+    static const char* const names[2][2] = { { "k_ingest_oriented_resized_image_generic", "k_ingest_oriented_resized_yuv_generic" },
+        { "k_ingest_oriented_resized_image", "k_ingest_oriented_resized_yuv" } };
+    s.r.t = resizeTaps(c->rzIn);
+    s.o = orientSrc(src.orient, src.srcRows, src.srcCols);
+    int& band = c->rzIn.osBand[s.o.swap];
+    if (band < 0)
+    {
+        band = orientedResizedBand(c->rzIn.t, s.o.swap != 0);
+    }
+    const bool staged = s.o.swap && band > 0 && !fallbackForced(FB_ORIENTED_RESIZED_GENERIC);
+    s.band = band;
+    s.vec = vec;
+    ip.set(orientedResizedKernel(kind, mode, staged), s);
+    ip.profName = names[staged][kind];
+    ip.launchName = "k_ingest_oriented_resized";
+}
 
 // The ingest of one call: the source held against the plan and the context's settings (what is refused, in the order the entries
 // have always checked), then the kernel form, its arguments and its names.  The ONE place that decides them.
@@ -730,9 +820,18 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
         {
             return fail(c, ACF_HIP_E_UNSUPPORTED, who + "dtype must be ACF_HIP_T_U8 (cv::resize's CV_32F arithmetic is not restated)");
         }
-        if (int rc = resizedTables(c, src.who, src.srcRows, src.srcCols, src.scale))
+        // (a turned unreduced frame: the tables and the plan are for the upright size: orient first, then resize)
+        int uprightRows, uprightCols, rc;
+        if ((rc = orientedResizedUpright(c, who, src, uprightRows, uprightCols)) || (rc = resizedTables(c, src.who, uprightRows, uprightCols, src.scale)))
         {
             return rc;
+        }
+        if (src.orient)
+        {
+            OrientedResizedSrc o{};
+            o.r.im = s;
+            planOrientedResized(c, RS_IMAGE, mode, imageLoadForm(src.base, src.img) == IM_ROWVEC, o, src, ip);
+            return ACF_HIP_OK;
         }
         ResizedSrc r{};
         r.t = resizeTaps(c->rzIn);
@@ -757,9 +856,18 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
     YuvDescSrc s = yuvDescSrc(base, src.yuv);
     if (src.resized)
     {
-        if (int rc = resizedTables(c, src.who, src.srcRows, src.srcCols, src.scale))
+        int uprightRows, uprightCols, rc;
+        if ((rc = orientedResizedUpright(c, who, src, uprightRows, uprightCols)) || (rc = resizedTables(c, src.who, uprightRows, uprightCols, src.scale)))
         {
             return rc;
+        }
+        if (src.orient)
+        {
+            OrientedResizedSrc o{};
+            const bool vec = yuvLoadForm(s) == YD_PLANAR;
+            o.r.yuv = s;
+            planOrientedResized(c, RS_YUV, mode, vec, o, src, ip);
+            return ACF_HIP_OK;
         }
         ResizedSrc r{};
         r.t = resizeTaps(c->rzIn);
@@ -940,6 +1048,61 @@ int acf_hip_run_yuv_oriented(acf_hip_ctx* c, const uint8_t* base, int nF, const 
     bool forward;
     if (int rc = orientedEntry(c, "pyramid_yuv_oriented", srcRows, srcCols, orient, forward)) return rc;
     return forward ? acf_hip_run_yuv(c, base, nF, desc) : yuvEntry(c, true, "pyramid_yuv_oriented", base, nF, desc, false, srcRows, srcCols, 1, orient);
+}
+
+// The oriented resized entries' own checks in front of imageEntry / yuvEntry.  Code 0 is the resized entry itself (forward: true).
+static int orientedResizedEntry(acf_hip_ctx* c, const char* who, int srcRows, int srcCols, int orient, bool& forward)
+{
+    forward = false;
+    if (int rc = needCtx(c)) return rc;
+    if (orient < 0 || orient > 7 || srcRows < 1 || srcCols < 1)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
+    }
+    forward = orient == 0;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_pyramid_image_oriented_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, int orient, double scale)
+{
+    bool forward;
+    if (int rc = orientedResizedEntry(c, "pyramid_image_oriented_resized", srcRows, srcCols, orient, forward)) return rc;
+    return forward ? acf_hip_pyramid_image_resized(c, frames, nF, desc, srcRows, srcCols, scale)
+                   : imageEntry(c, false, "pyramid_image_oriented_resized", frames, nF, desc, true, srcRows, srcCols, scale, orient);
+}
+
+int acf_hip_run_image_oriented_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, int orient, double scale)
+{
+    bool forward;
+    if (int rc = orientedResizedEntry(c, "pyramid_image_oriented_resized", srcRows, srcCols, orient, forward)) return rc;
+    return forward ? acf_hip_run_image_resized(c, frames, nF, desc, srcRows, srcCols, scale)
+                   : imageEntry(c, true, "pyramid_image_oriented_resized", frames, nF, desc, true, srcRows, srcCols, scale, orient);
+}
+
+int acf_hip_pyramid_yuv_oriented_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient, double scale)
+{
+    bool forward;
+    if (int rc = orientedResizedEntry(c, "pyramid_yuv_oriented_resized", srcRows, srcCols, orient, forward)) return rc;
+    return forward ? acf_hip_pyramid_yuv_resized(c, base, nF, desc, srcRows, srcCols, scale)
+                   : yuvEntry(c, false, "pyramid_yuv_oriented_resized", base, nF, desc, true, srcRows, srcCols, scale, orient);
+}
+
+int acf_hip_run_yuv_oriented_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient, double scale)
+{
+    bool forward;
+    if (int rc = orientedResizedEntry(c, "pyramid_yuv_oriented_resized", srcRows, srcCols, orient, forward)) return rc;
+    return forward ? acf_hip_run_yuv_resized(c, base, nF, desc, srcRows, srcCols, scale)
+                   : yuvEntry(c, true, "pyramid_yuv_oriented_resized", base, nF, desc, true, srcRows, srcCols, scale, orient);
+}
+
+int acf_hip_oriented_resized_dims(int srcRows, int srcCols, int orient, double scale, int* h, int* w)
+{
+    int uh, uw;
+    if (!h || !w || !std::isfinite(scale) || acf_hip_oriented_dims(srcRows, srcCols, orient, &uh, &uw))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    return acf_hip_resize_dims(uh, uw, scale, h, w);
 }
 
 int acf_hip_oriented_dims(int srcRows, int srcCols, int orient, int* h, int* w)

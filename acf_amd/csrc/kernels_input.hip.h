@@ -2,7 +2,7 @@
 // includes, its layout / arithmetic contract and the helpers of the parts before them).
 // rgbConvert (LUV / gray / HSV), the packed 8-bit ingest, the tensor and YUV ingests (upright: k_ingest_image / k_ingest_yuv; rotated and mirrored
 // frames: k_ingest_image_oriented / k_ingest_yuv_oriented), the apps' resize to a minimum object width (alone: k_resize_u8; inside the tensor / YUV
-// entries: k_ingest_resized), and the plain convTri1 (k_smooth_tri1: the fallback of the vector smoothing).
+// entries: k_ingest_resized; on rotated and mirrored frames: k_ingest_oriented_resized), and the plain convTri1 (k_smooth_tri1: the fallback of the vector smoothing).
 #pragma once
 
 namespace acfhip
@@ -1712,6 +1712,339 @@ __global__ void __launch_bounds__(256) k_ingest_resized(IngestArgs a, ResizedSrc
             t[0] = o[0];
             t[1] = cn == 3 ? o[1] : o[0]; // one plane: r = g = b (chnsPyramid.cpp:234-244), as k_ingest_u8 reads a 1-byte pixel
             t[2] = cn == 3 ? o[2] : o[0];
+        }
+    }
+    __syncthreads();
+    ingest_store_tile<MODE>(a, tile, 3, 0, 1, 2, x0, y0, nx, ny);
+}
+
+// ------------------------------------------------------------------------
+// The apps' resize on rotated and mirrored frames (acf_hip_pyramid_image_oriented_resized / _yuv_oriented_resized, codes 1 .. 7; code 0
+// runs k_ingest_resized): the stored frame S of Hs x Ws is read where it lies, and the planes are those of k_ingest_resized on a tight
+// upright u8 image holding U = np.rot90(S[:, ::-1] if mirror else S, -rot) — orient FIRST, then rz_pixel with the tap tables of U's size,
+// as the reference's GL front end does (GPUACF.cpp: rotate -> smooth -> reduce) — bit for bit.  cvtColor and cv::resize stay restated:
+// PARITY UNPINNED.  The chroma sample of a subsampled plane is chosen in SOURCE coordinates, as the oriented entries do.
+//
+// STAGED (k_ingest_oriented_resized_image / _yuv; taken for quarter turns, see planOrientedResized).  k_ingest_resized gathers per output pixel from global memory with lanes along
+// reduced-image x; with a quarter turn every lane of a wave would read another stored row.  Here a workgroup of 256 threads owns a
+// 64 x 64 tile of the REDUCED upright image and marches it in bands of `band` reduced rows (chosen on the host, orientedResizedBand, so
+// that every band's footprint fits the stage; 64 = one band):
+//   footprint  rz_span: the first and last tap of the band's first and last row and of the tile's first and last column (xlin / ylin,
+//              xrun / xtap, dx * isx), clipped to U; orient_tile maps that rectangle of U to a rectangle of S (nsr x nsc from rs0, cs0)
+//   load       lanes run along the STORED rows of the rectangle, whichever way the frame is turned: with S.vec (imageLoadForm's
+//              IM_ROWVEC / yuvLoadForm's YD_PLANAR conditions) a lane takes the aligned quad of source columns 4q .. 4q + 3: one dword a
+//              plane (a 2 x-subsampled chroma plane: one 16-bit load); else one pixel a lane, byte loads.  A word is loaded whole only
+//              when all of it lies inside the row of its plane ([0, Ws), chroma [0, ceil(Ws / 2))), else its bytes inside one by one:
+//              no load covers an address outside the [first, last] span of the row and plane it belongs to.  YUV goes through
+//              yuv_chroma / yuv_rgb8 here, once per source pixel (chroma at (rs >> subY, cs >> subX))
+//   stage      pixel (i, j) of the rectangle is ONE dword r | g << 8 | b << 16 (one plane: the byte) at i * pitch + j, pitch = nsc | 1
+//   resize     rz_pixel, unchanged, over RzStageSrc, which applies the orientation in its index arithmetic (base + y * ay + x * ax:
+//              ay, ax are +-pitch and +-1, swapped for quarter turns); lanes along reduced-image x, a wave a row, the bytes into
+//              k_ingest_u8's LDS byte tile as k_ingest_resized writes them
+//   store      ingest_store_tile, once the last band is in
+// LDS: stage OS_STAGE = 8448 dwords (33792 bytes: a 64 x 64 tile at scale 1 / 2 is 64 + 64 rows of 129 dwords = two bands; at 1 / 4 a band
+// of 8 reduced rows is 32 rows of 257) + the byte tile 16640 = 50432 bytes a workgroup: three workgroups a CU of 160 KiB.  A band
+// below OS_MIN_BAND = 8 rows (scales under 1 / 4: two barriers for less than two rows a wave) takes the generic form instead.
+// By the compiler's resource report (-Rpass-analysis=kernel-resource-usage, gfx950): staged 52 VGPRs (image) / 63 (YUV), 106 SGPRs, no
+// scratch, 50432 bytes of LDS, occupancy 3 waves a SIMD (LDS-bound); generic 48 / 62 VGPRs, 16640 bytes, 8 waves a SIMD.
+// Banks (bank = dword address % 32, per 32-lane half; derived from the address maps.  Not measured: SQ_LDS_BANK_CONFLICT, whether byte
+// writes of several lanes to one dword of the byte tile serialise, the byte load form's time, scales other than 1 / 2 and 80 / 150,
+// image sources; profiles/oriented_resized_entry.md holds what was):
+//   stage writes, vec    a lane's element t goes to dword 4q + t + const of one row: a half is 32 quads, stride 4 -> 8 banks, 4-way (as
+//                        IM_ROWVEC's); the rows of one half are `pitch` apart, which only shifts the pattern
+//   stage writes, bytes  a half writes 32 consecutive dwords of a row (or the end of one row and the start of the next, pitch apart):
+//                        conflict-free, or 2-way where the two runs overlap mod 32
+//   rz_pixel reads       one tap of 32 consecutive reduced x.  rot 0 / 2 (ax = +-1): the taps are 1 / scale dwords apart on average:
+//                        scale 1 / 2: stride 2, 2-way; 1 / 4: stride 4, 4-way; 80 / 150: stride 1.875, 30 + distinct dwords over 60: at
+//                        most 2-way; enlarging: neighbours share a dword (broadcast).  rot 1 / 3 (ax = +-pitch, odd): stride pitch / scale:
+//                        an odd pitch times 2 (4): the same 2-way (4-way); fractional: as rot 0 / 2.  The mirror only changes signs.
+//   byte tile            as k_ingest_resized
+// GENERIC (k_ingest_oriented_resized_image_generic / _yuv_generic; STAGED = false; taken for rot 0 / 2, where its lanes run along the stored
+// rows already and the stage was measured slower, and for scales under 1 / 4): k_ingest_resized's phase 1 with the orientation map in
+// front of the global accessors (RzOrientedSrc over RzImageSrc / RzYuvSrc): every lane gathers its own pixels, any description, any scale;
+// 16640 bytes of LDS.  Both forms run the same rz_pixel on the same bytes: identical bits.
+// ------------------------------------------------------------------------
+constexpr int OS_STAGE = 8448;  // dwords
+constexpr int OS_MIN_BAND = 8;  // reduced rows
+
+// The first and last source index that reduced indices d0 .. d1 of one axis read (y: rows, else columns), clipped to [0, ssize): the
+// kernel's footprint and the host's band choice (orientedResizedBand) from the same tables.  lin: {sx, a0, a1, two} / {r0, r1, b0, b1};
+// run: {first tap, count}; tap: {source index, weight}; is: RZ_AREA_INT's cell.
+__host__ __device__ inline void rz_span(int mode, int is, int ssize, const int32_t* lin, const int32_t* run, const int32_t* tap, bool y, int d0, int d1, int& first,
+    int& last)
+{
+    if (mode == RZ_LINEAR)
+    {
+        first = lin[4 * d0];
+        last = y ? lin[4 * d1 + 1] : lin[4 * d1] + (lin[4 * d1 + 3] ? 1 : 0);
+    }
+    else if (mode == RZ_AREA_INT)
+    {
+        first = d0 * is;
+        last = (d1 + 1) * is - 1;
+    }
+    else
+    {
+        first = tap[2 * run[2 * d0]];
+        last = tap[2 * (run[2 * d1] + (run[2 * d1 + 1] > 0 ? run[2 * d1 + 1] - 1 : 0))];
+    }
+    first = first < 0 ? 0 : (first > ssize - 1 ? ssize - 1 : first);
+    last = last > ssize - 1 ? ssize - 1 : (last < first ? first : last);
+}
+
+// rz_pixel's accessor on the stage: upright pixel (y, x) of U is the dword at base + y * ay + x * ax
+struct RzStageSrc
+{
+    const uint32_t* st;
+    int base, ay, ax;
+    __device__ __forceinline__ void px(int y, int x, int (&v)[4]) const
+    {
+        const uint32_t w = st[base + y * ay + x * ax];
+        v[0] = int(w & 255);
+        v[1] = int((w >> 8) & 255);
+        v[2] = int((w >> 16) & 255);
+        v[3] = 0;
+    }
+};
+
+// rz_pixel's global accessors behind the orientation map: upright pixel (y, x) of U is source pixel (rs, cs) of S
+template <class IN>
+struct RzOrientedSrc
+{
+    IN in;
+    OrientSrc o;
+    __device__ __forceinline__ void px(int y, int x, int (&v)[4]) const
+    {
+        const int p = o.swap ? x : y, q = o.swap ? y : x;
+        in.px(o.revR ? o.Hs - 1 - p : p, o.revC ? o.Ws - 1 - q : q, v);
+    }
+};
+
+struct OrientedResizedSrc
+{
+    ResizedSrc r;  // the description at Hs x Ws; the tap tables of U's size
+    OrientSrc o;
+    int band;      // STAGED: reduced rows a band
+    int vec;       // STAGED: the wide load form
+};
+
+// n (1 .. 3) bytes at p as the low bytes of a dword
+__device__ __forceinline__ uint32_t os_bytes(const uint8_t* p, int n)
+{
+    uint32_t v = 0;
+    for (int b = 0; b < n; b++)
+    {
+        v |= uint32_t(p[b]) << (8 * b);
+    }
+    return v;
+}
+
+// STAGED load phase, an image of u8 elements: the rectangle T of frame `in` (element (0, 0, 0)) to the stage
+__device__ __forceinline__ void os_stage_image(const ImageArgs& s, const uint8_t* in, const OrientTile& T, int Ws, int pitch, int vec, uint32_t* stage)
+{
+    const int nIn = s.nIn;
+    if (vec)
+    {
+        // sx == 1; the base and sn, sc, sy are multiples of four (host-checked): every row start is
+        const int q0 = T.cs0 >> 2, nq = ((T.cs0 + T.nsc - 1) >> 2) - q0 + 1;
+#pragma unroll 2
+        for (int idx = threadIdx.x; idx < T.nsr * nq; idx += 256)
+        {
+            const int i = idx / nq, col = 4 * (q0 + idx - i * nq);
+            const uint8_t* rp = in + int64_t(T.rs0 + i) * s.sy + col;
+            const bool whole = col + 4 <= Ws;
+            uint32_t w[3] = { 0, 0, 0 };
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+            {
+                if (c < nIn)
+                {
+                    const uint8_t* pc = rp + int64_t(c) * s.sc;
+                    w[c] = whole ? *reinterpret_cast<const uint32_t*>(pc) : os_bytes(pc, Ws - col);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+            {
+                const int j = col + t - T.cs0;
+                if (j >= 0 && j < T.nsc)
+                {
+                    stage[i * pitch + j] = ((w[0] >> (8 * t)) & 255) | (((w[1] >> (8 * t)) & 255) << 8) | (((w[2] >> (8 * t)) & 255) << 16);
+                }
+            }
+        }
+    }
+    else
+    {
+#pragma unroll 2
+        for (int idx = threadIdx.x; idx < T.nsr * T.nsc; idx += 256)
+        {
+            const int i = idx / T.nsc, j = idx - i * T.nsc;
+            const uint8_t* p = in + int64_t(T.rs0 + i) * s.sy + int64_t(T.cs0 + j) * s.sx;
+            uint32_t w = p[0];
+            if (nIn == 3)
+            {
+                w |= (uint32_t(p[s.sc]) << 8) | (uint32_t(p[2 * s.sc]) << 16);
+            }
+            stage[i * pitch + j] = w;
+        }
+    }
+}
+
+// STAGED load phase, a YUV description: the rectangle T of frame n, converted once per source pixel, to the stage
+__device__ __forceinline__ void os_stage_yuv(const YuvDescSrc& s, int64_t n, const OrientTile& T, int Ws, int pitch, int vec, uint32_t* stage)
+{
+    const uint8_t* fy = s.base + s.y.off + n * s.y.sn;
+    const uint8_t* fu = s.base + s.u.off + n * s.u.sn;
+    const uint8_t* fv = s.base + s.v.off + n * s.v.sn;
+    const int subX = s.subX, subY = s.subY;
+    if (vec)
+    {
+        // sp == 1; base + off, sr, sn of every plane are multiples of 4 (host-checked): every plane row start is
+        const int cW = (Ws + subX) >> subX; // chroma samples a row
+        const int q0 = T.cs0 >> 2, nq = ((T.cs0 + T.nsc - 1) >> 2) - q0 + 1;
+#pragma unroll 2
+        for (int idx = threadIdx.x; idx < T.nsr * nq; idx += 256)
+        {
+            const int i = idx / nq, col = 4 * (q0 + idx - i * nq), rs = T.rs0 + i, cr = rs >> subY;
+            const uint8_t* yp = fy + int64_t(rs) * s.y.sr + col;
+            const uint32_t Y = col + 4 <= Ws ? *reinterpret_cast<const uint32_t*>(yp) : os_bytes(yp, Ws - col);
+            uint32_t U, V;
+            if (subX)
+            {
+                const int cc = col >> 1; // even: the pair (cc, cc + 1) is 2-aligned
+                const uint8_t* up = fu + int64_t(cr) * s.u.sr + cc;
+                const uint8_t* vp = fv + int64_t(cr) * s.v.sr + cc;
+                const bool whole = cc + 2 <= cW;
+                U = whole ? uint32_t(*reinterpret_cast<const uint16_t*>(up)) : uint32_t(up[0]);
+                V = whole ? uint32_t(*reinterpret_cast<const uint16_t*>(vp)) : uint32_t(vp[0]);
+            }
+            else
+            {
+                const uint8_t* up = fu + int64_t(cr) * s.u.sr + col;
+                const uint8_t* vp = fv + int64_t(cr) * s.v.sr + col;
+                const bool whole = col + 4 <= Ws;
+                U = whole ? *reinterpret_cast<const uint32_t*>(up) : os_bytes(up, Ws - col);
+                V = whole ? *reinterpret_cast<const uint32_t*>(vp) : os_bytes(vp, Ws - col);
+            }
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+            {
+                const int j = col + t - T.cs0;
+                if (j >= 0 && j < T.nsc)
+                {
+                    const int ct = 8 * (t >> subX);
+                    int r, g, b;
+                    yuv_rgb8(int((Y >> (8 * t)) & 255), yuv_chroma(int((U >> ct) & 255), int((V >> ct) & 255)), r, g, b);
+                    stage[i * pitch + j] = uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(b) << 16);
+                }
+            }
+        }
+    }
+    else
+    {
+#pragma unroll 2
+        for (int idx = threadIdx.x; idx < T.nsr * T.nsc; idx += 256)
+        {
+            const int i = idx / T.nsc, j = idx - i * T.nsc, rs = T.rs0 + i, cs = T.cs0 + j;
+            const int cr = rs >> subY, cc = cs >> subX;
+            const int Y = fy[int64_t(rs) * s.y.sr + int64_t(cs) * s.y.sp];
+            const int U = fu[int64_t(cr) * s.u.sr + int64_t(cc) * s.u.sp];
+            const int V = fv[int64_t(cr) * s.v.sr + int64_t(cc) * s.v.sp];
+            int r, g, b;
+            yuv_rgb8(Y, yuv_chroma(U, V), r, g, b);
+            stage[i * pitch + j] = uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(b) << 16);
+        }
+    }
+}
+
+template <int SRC, int MODE, bool STAGED>
+__global__ void __launch_bounds__(256) k_ingest_oriented_resized(IngestArgs a, OrientedResizedSrc S)
+{
+    __shared__ uint32_t tileW[IG_T * IG_PITCH / 4];
+    __shared__ uint32_t stage[STAGED ? OS_STAGE : 1];
+    uint8_t* tile = reinterpret_cast<uint8_t*>(tileW);
+    const ResizeTaps& tp = S.r.t; // of U: tp.rows x tp.cols
+    const int x0 = blockIdx.x * IG_T, y0 = blockIdx.y * IG_T;
+    const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0);
+    const int64_t n = blockIdx.z;
+    const int xx = threadIdx.x & 63;
+    const int cn = SRC == RS_YUV ? 3 : S.r.im.nIn;
+    const auto put = [&](int yy, const uint8_t (&o)[4]) {
+        uint8_t* t = tile + yy * IG_PITCH + 3 * xx;
+        t[0] = o[0];
+        t[1] = cn == 3 ? o[1] : o[0]; // one plane: r = g = b, as k_ingest_resized
+        t[2] = cn == 3 ? o[2] : o[0];
+    };
+    if (!STAGED)
+    {
+        if (xx < nx)
+        {
+            for (int yy = threadIdx.x >> 6; yy < ny; yy += 4)
+            {
+                uint8_t o[4];
+                if (SRC == RS_YUV)
+                {
+                    const YuvDescSrc& d = S.r.yuv;
+                    const RzOrientedSrc<RzYuvSrc> src{ { d.base + d.y.off + n * d.y.sn, d.base + d.u.off + n * d.u.sn, d.base + d.v.off + n * d.v.sn, d.y.sr, d.y.sp,
+                                                          d.u.sr, d.u.sp, d.v.sr, d.v.sp, d.subX, d.subY },
+                        S.o };
+                    rz_pixel(src, tp, x0 + xx, y0 + yy, o);
+                }
+                else
+                {
+                    const ImageArgs& im = S.r.im;
+                    const RzOrientedSrc<RzImageSrc> src{ { static_cast<const uint8_t*>(im.in) + n * im.sn, im.sc, im.sy, im.sx, im.nIn }, S.o };
+                    rz_pixel(src, tp, x0 + xx, y0 + yy, o);
+                }
+                put(yy, o);
+            }
+        }
+    }
+    else
+    {
+        const int32_t* xlin = reinterpret_cast<const int32_t*>(tp.xlin);
+        const int32_t* ylin = reinterpret_cast<const int32_t*>(tp.ylin);
+        const int32_t* xrun = reinterpret_cast<const int32_t*>(tp.xrun);
+        const int32_t* yrun = reinterpret_cast<const int32_t*>(tp.yrun);
+        const int32_t* xtap = reinterpret_cast<const int32_t*>(tp.xtap);
+        const int32_t* ytap = reinterpret_cast<const int32_t*>(tp.ytap);
+        int fx0, fx1;
+        rz_span(tp.mode, tp.isx, tp.cols, xlin, xrun, xtap, false, x0, x0 + nx - 1, fx0, fx1);
+        for (int yb = 0; yb < ny; yb += S.band)
+        {
+            const int nb = min(S.band, ny - yb);
+            int fy0, fy1;
+            rz_span(tp.mode, tp.isy, tp.rows, ylin, yrun, ytap, true, y0 + yb, y0 + yb + nb - 1, fy0, fy1);
+            const OrientTile T = orient_tile(S.o, fx0, fy0, fx1 - fx0 + 1, fy1 - fy0 + 1);
+            const int pitch = T.nsc | 1;
+            if (yb)
+            {
+                __syncthreads(); // the band before is read
+            }
+            if (SRC == RS_YUV)
+            {
+                os_stage_yuv(S.r.yuv, n, T, S.o.Ws, pitch, S.vec, stage);
+            }
+            else
+            {
+                os_stage_image(S.r.im, static_cast<const uint8_t*>(S.r.im.in) + n * S.r.im.sn, T, S.o.Ws, pitch, S.vec, stage);
+            }
+            __syncthreads();
+            // rectangle element (i, j) of upright (y, x): p = (swap ? x - fx0 : y - fy0), q = the other; i = revR ? nsr - 1 - p : p, j likewise
+            const int sR = T.revR ? -1 : 1, sC = T.revC ? -1 : 1;
+            const int pOff = T.swap ? fx0 : fy0, qOff = T.swap ? fy0 : fx0;
+            const int base = ((T.revR ? T.nsr - 1 : 0) - sR * pOff) * pitch + (T.revC ? T.nsc - 1 : 0) - sC * qOff;
+            const RzStageSrc src{ stage, base, T.swap ? sC : sR * pitch, T.swap ? sR * pitch : sC };
+            if (xx < nx)
+            {
+                for (int yy = yb + (threadIdx.x >> 6); yy < yb + nb; yy += 4)
+                {
+                    uint8_t o[4];
+                    rz_pixel(src, tp, x0 + xx, y0 + yy, o);
+                    put(yy, o);
+                }
+            }
         }
     }
     __syncthreads();

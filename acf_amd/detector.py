@@ -200,17 +200,19 @@ class HipDetector:
     def run_image_oriented(self, ptr, n, desc, src_rows, src_cols, orient):
         self._chk(self.lib.acf_hip_run_image_oriented(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, orient))
 
-    def pyramid_tensor_resized(self, t, scale, layout="nchw"):
+    def pyramid_tensor_resized(self, t, scale, layout="nchw", orient=0):
         """t: uint8 device tensor of the UNREDUCED frames [n, c, rows, cols] of any strides; the plan is for resize_dims(rows, cols,
-        scale).  The apps' resize and the ingest in one kernel; detections are in the reduced frame (unscale_boxes maps them back)."""
+        scale).  The apps' resize and the ingest in one kernel; detections are in the reduced frame (unscale_boxes maps them back).
+        orient (capi.ORIENT_*): t is the unreduced frame AS STORED; it is turned upright, then reduced: the plan is for
+        oriented_resized_dims(rows, cols, orient, scale), and unscale_boxes, then unorient_boxes map detections back."""
         ptr, n, desc = self._image_of(t, layout, scale)
         rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
-        self._chk(self.lib.acf_hip_pyramid_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), rows, cols, float(scale)))
+        self.pyramid_image_resized(ptr, n, desc, rows, cols, scale, orient)
 
-    def run_tensor_resized(self, t, scale, layout="nchw"):
+    def run_tensor_resized(self, t, scale, layout="nchw", orient=0):
         ptr, n, desc = self._image_of(t, layout, scale)
         rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
-        self._chk(self.lib.acf_hip_run_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), rows, cols, float(scale)))
+        self.run_image_resized(ptr, n, desc, rows, cols, scale, orient)
 
     def pyramid_image(self, ptr, n, desc):
         """The raw entry: a device pointer (int) and a capi.ImageDesc."""
@@ -219,12 +221,19 @@ class HipDetector:
     def run_image(self, ptr, n, desc):
         self._chk(self.lib.acf_hip_run_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
 
-    def pyramid_image_resized(self, ptr, n, desc, src_rows, src_cols, scale):
-        """The raw resized entry: desc (uint8) describes frames of src_rows x src_cols; the plan is for resize_dims of them."""
-        self._chk(self.lib.acf_hip_pyramid_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, float(scale)))
+    def pyramid_image_resized(self, ptr, n, desc, src_rows, src_cols, scale, orient=0):
+        """The raw resized entry: desc (uint8) describes frames of src_rows x src_cols; the plan is for resize_dims of them — with
+        orient, for oriented_resized_dims (the frame is turned upright first, then reduced)."""
+        if not orient:
+            self._chk(self.lib.acf_hip_pyramid_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, float(scale)))
+        else:
+            self._chk(self.lib.acf_hip_pyramid_image_oriented_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, orient, float(scale)))
 
-    def run_image_resized(self, ptr, n, desc, src_rows, src_cols, scale):
-        self._chk(self.lib.acf_hip_run_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, float(scale)))
+    def run_image_resized(self, ptr, n, desc, src_rows, src_cols, scale, orient=0):
+        if not orient:
+            self._chk(self.lib.acf_hip_run_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, float(scale)))
+        else:
+            self._chk(self.lib.acf_hip_run_image_oriented_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, orient, float(scale)))
 
     @staticmethod
     def image_extent(desc, h, w, n):
@@ -302,15 +311,23 @@ class HipDetector:
             return src_rows, src_cols
         return (self.W, self.H) if orient & 1 else (self.H, self.W)
 
-    def pyramid_yuv_resized(self, base, n, desc, src_rows, src_cols, scale):
+    def pyramid_yuv_resized(self, base, n, desc, src_rows, src_cols, scale, orient=0):
         """desc describes frames of src_rows x src_cols; the plan is for resize_dims(src_rows, src_cols, scale).  Conversion, the apps'
-        resize and the ingest in one kernel; detections are in the reduced frame (unscale_boxes maps them back)."""
-        self._chk(self.lib.acf_hip_pyramid_yuv_resized(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, C.byref(desc),
-                                                       src_rows, src_cols, float(scale)))
+        resize and the ingest in one kernel; detections are in the reduced frame (unscale_boxes maps them back).
+        orient (capi.ORIENT_*): the frames as stored; turned upright, then reduced: the plan is for oriented_resized_dims(src_rows,
+        src_cols, orient, scale); unscale_boxes, then unorient_boxes map detections back."""
+        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
+        if not orient:
+            self._chk(self.lib.acf_hip_pyramid_yuv_resized(self.ctx, ptr, n, C.byref(desc), src_rows, src_cols, float(scale)))
+        else:
+            self._chk(self.lib.acf_hip_pyramid_yuv_oriented_resized(self.ctx, ptr, n, C.byref(desc), src_rows, src_cols, orient, float(scale)))
 
-    def run_yuv_resized(self, base, n, desc, src_rows, src_cols, scale):
-        self._chk(self.lib.acf_hip_run_yuv_resized(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, C.byref(desc),
-                                                   src_rows, src_cols, float(scale)))
+    def run_yuv_resized(self, base, n, desc, src_rows, src_cols, scale, orient=0):
+        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
+        if not orient:
+            self._chk(self.lib.acf_hip_run_yuv_resized(self.ctx, ptr, n, C.byref(desc), src_rows, src_cols, float(scale)))
+        else:
+            self._chk(self.lib.acf_hip_run_yuv_oriented_resized(self.ctx, ptr, n, C.byref(desc), src_rows, src_cols, orient, float(scale)))
 
     @staticmethod
     def yuv_planes_desc(y, u, v, sub_x, sub_y):
@@ -331,16 +348,15 @@ class HipDetector:
 
     def run_yuv_planes(self, y, u, v, sub_x=1, sub_y=1, scale=None, orient=0):
         """Three separately allocated planes (a software decoder's frame): y [n, H, W], u and v [n, ceil(H / 2^sub_y), ceil(W / 2^sub_x)].
-        scale: the planes are the unreduced frame (run_yuv_resized; the plan is for resize_dims of y's size)."""
+        scale: the planes are the unreduced frame (run_yuv_resized; the plan is for resize_dims of y's size).  orient: the planes as
+        stored (the plan is for oriented_dims of y's size); with both, turned upright and then reduced (oriented_resized_dims)."""
         base, n, desc = self.yuv_planes_desc(y, u, v, sub_x, sub_y)
-        if orient:
-            if scale is not None:
-                raise HipError(capi.E_UNSUPPORTED, "run_yuv_planes: orient and scale together (the resized entries are not oriented)")
+        if scale is not None:
+            self.run_yuv_resized(base, n, desc, y.shape[-2], y.shape[-1], scale, orient)
+        elif orient:
             self.run_yuv(base, n, desc, orient, y.shape[-2], y.shape[-1])
-        elif scale is None:
-            self.run_yuv(base, n, desc)
         else:
-            self.run_yuv_resized(base, n, desc, y.shape[-2], y.shape[-1], scale)
+            self.run_yuv(base, n, desc)
 
     def yuv_to_rgb8(self, base, n, rows, cols, desc):
         """The conversion alone on the device -> torch uint8 CUDA tensor [n][rows][cols][3] (acf_hip_yuv_to_rgb8; no model or plan)."""
@@ -360,9 +376,12 @@ class HipDetector:
             self._chk(self.lib.acf_hip_stream_open_yuv_oriented(self.ctx, C.byref(desc), frame_bytes, *self._src_size(orient, src_rows, src_cols), orient, cap, depth))
         self._stream_cap = cap
 
-    def stream_open_yuv_resized(self, desc, frame_bytes, src_rows, src_cols, scale, cap=1024, depth=2):
-        """stream_open_yuv for unreduced frames of src_rows x src_cols: every submit runs run_yuv_resized on its slot."""
-        self._chk(self.lib.acf_hip_stream_open_yuv_resized(self.ctx, C.byref(desc), frame_bytes, src_rows, src_cols, float(scale), cap, depth))
+    def stream_open_yuv_resized(self, desc, frame_bytes, src_rows, src_cols, scale, cap=1024, depth=2, orient=0):
+        """stream_open_yuv for unreduced frames of src_rows x src_cols: every submit runs run_yuv_resized(..., orient) on its slot."""
+        if not orient:
+            self._chk(self.lib.acf_hip_stream_open_yuv_resized(self.ctx, C.byref(desc), frame_bytes, src_rows, src_cols, float(scale), cap, depth))
+        else:
+            self._chk(self.lib.acf_hip_stream_open_yuv_oriented_resized(self.ctx, C.byref(desc), frame_bytes, src_rows, src_cols, orient, float(scale), cap, depth))
         self._stream_cap = cap
 
     # ---- the apps' resize to a minimum object width (acf.cpp:117-148 Resizer) in front of the 8-bit entries
@@ -409,6 +428,15 @@ class HipDetector:
         rc = capi.load().acf_hip_oriented_dims(src_rows, src_cols, orient, C.byref(h), C.byref(w))
         if rc:
             raise HipError(rc, "acf_hip_oriented_dims")
+        return h.value, w.value
+
+    @staticmethod
+    def oriented_resized_dims(src_rows, src_cols, orient, scale):
+        """(h, w) of the reduced upright frame of a stored src_rows x src_cols frame: resize_dims(oriented_dims(...), scale)."""
+        h, w = C.c_int(), C.c_int()
+        rc = capi.load().acf_hip_oriented_resized_dims(src_rows, src_cols, orient, float(scale), C.byref(h), C.byref(w))
+        if rc:
+            raise HipError(rc, "acf_hip_oriented_resized_dims")
         return h.value, w.value
 
     @staticmethod

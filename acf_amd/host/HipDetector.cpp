@@ -582,7 +582,8 @@ bool HipDetector::resizedPlan(int rows, int cols, int& planRows, int& planCols) 
     return true;
 }
 
-// setInputOrientation in the tensor and YUV entries: the plan's size for stored frames of rows x cols (acf_hip_oriented_dims); false: upright
+// setInputOrientation in the tensor and YUV entries: the plan's size for stored frames of rows x cols (acf_hip_oriented_dims; with
+// setMinObjectWidth too the frame is turned upright first and then reduced: acf_hip_oriented_resized_dims); false: upright
 bool HipDetector::orientedPlan(int rows, int cols, bool resized, int& planRows, int& planCols) const
 {
     if (m_orient == 0)
@@ -591,7 +592,8 @@ bool HipDetector::orientedPlan(int rows, int cols, bool resized, int& planRows, 
     }
     if (resized)
     {
-        throw Exception(ACF_HIP_E_UNSUPPORTED, "setInputOrientation and setMinObjectWidth together: the resized entries are not oriented");
+        check(m_api->acf_hip_oriented_resized_dims(rows, cols, m_orient, double(inputScale()), &planRows, &planCols), "acf_hip_oriented_resized_dims");
+        return true;
     }
     check(m_api->acf_hip_oriented_dims(rows, cols, m_orient, &planRows, &planCols), "acf_hip_oriented_dims");
     return true;
@@ -641,7 +643,12 @@ int HipDetector::detectImages(const void* framesDev, int nFrames, int rows, int 
     const bool oriented = orientedPlan(rows, cols, resized, planRows, planCols);
     ensurePlan(planRows, planCols, desc.channels, nFrames);
     syncNms();
-    if (oriented) // (boxes in the upright frame)
+    if (oriented && resized) // (fetchBatch unscales: boxes in the upright full-size frame)
+    {
+        check(m_api->acf_hip_run_image_oriented_resized(m_ctx, framesDev, nFrames, &desc, rows, cols, m_orient, double(inputScale())),
+            "acf_hip_run_image_oriented_resized");
+    }
+    else if (oriented) // (boxes in the upright frame)
     {
         check(m_api->acf_hip_run_image_oriented(m_ctx, framesDev, nFrames, &desc, rows, cols, m_orient), "acf_hip_run_image_oriented");
     }
@@ -665,7 +672,12 @@ int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int co
     const bool oriented = orientedPlan(rows, cols, resized, planRows, planCols);
     ensurePlan(planRows, planCols, 3, nFrames);
     syncNms();
-    if (oriented) // (boxes in the upright frame)
+    if (oriented && resized) // (fetchBatch unscales: boxes in the upright full-size frame)
+    {
+        check(m_api->acf_hip_run_yuv_oriented_resized(m_ctx, baseDev, nFrames, &desc, rows, cols, m_orient, double(inputScale())),
+            "acf_hip_run_yuv_oriented_resized");
+    }
+    else if (oriented) // (boxes in the upright frame)
     {
         check(m_api->acf_hip_run_yuv_oriented(m_ctx, baseDev, nFrames, &desc, rows, cols, m_orient), "acf_hip_run_yuv_oriented");
     }
@@ -782,7 +794,13 @@ void HipDetector::streamOpenYuv(int rows, int cols, const acf_hip_yuv_desc& desc
     check(m_api->acf_hip_set_input_resize(m_ctx, 0, 0, 1.0), "acf_hip_set_input_resize");
     m_srcRows = rows;
     m_srcCols = cols;
-    if (oriented) // (streamCollect returns boxes in the upright frame)
+    if (oriented && resized) // (streamCollect maps the boxes back to the upright full-size frame)
+    {
+        check(m_api->acf_hip_stream_open_yuv_oriented_resized(m_ctx, &desc, int64_t(frameBytes), rows, cols, m_orient, double(inputScale()), maxDetectionsPerFrame,
+                  depth),
+            "acf_hip_stream_open_yuv_oriented_resized");
+    }
+    else if (oriented) // (streamCollect returns boxes in the upright frame)
     {
         check(m_api->acf_hip_stream_open_yuv_oriented(m_ctx, &desc, int64_t(frameBytes), rows, cols, m_orient, maxDetectionsPerFrame, depth),
             "acf_hip_stream_open_yuv_oriented");

@@ -270,8 +270,9 @@ public:
     // the frames as they are stored, rows x cols, in orientation `orient` (ACF_HIP_ORIENT_*: rot + 4 * mirror; the upright frame is
     // the stored one mirrored left-right first, then turned rot quarter turns clockwise) and search the upright frame — the ingest
     // kernel reads the stored frame where it lies (include/acf_hip.h, acf_hip_run_image_oriented / acf_hip_run_yuv_oriented).  Boxes
-    // come back in the UPRIGHT frame's coordinates; unorientRect maps one to the stored frame.  0 (default): off.  Not together with
-    // setMinObjectWidth (ACF_HIP_E_UNSUPPORTED: the resized entries are not oriented).
+    // come back in the UPRIGHT frame's coordinates; unorientRect maps one to the stored frame.  0 (default): off.  Together with
+    // setMinObjectWidth the frame is turned upright first and then reduced, still in one kernel (acf_hip_run_image_oriented_resized /
+    // acf_hip_run_yuv_oriented_resized); the boxes are unscaled as always, so they are in the upright FULL-SIZE frame.
     void setInputOrientation(int orient) { m_orient = orient; }
     int getInputOrientation() const { return m_orient; }
     static Rect unorientRect(const Rect& o, int orient, int srcRows, int srcCols); // acf_hip_unorient_rect

@@ -11,7 +11,9 @@
 //                  device reads), or --stream B through streamOpenYuv / streamSubmit / streamCollect; --min-width M: reduced on the device
 //                  first, in the ingest kernel (acf_hip_run_yuv_resized), the boxes mapped back; --orient K (0 .. 7 = rot + 4 * mirror:
 //                  the frames are stored mirrored / turned; H x W is the STORED size): the upright frame is searched
-//                  (setInputOrientation), the boxes are printed in the UPRIGHT frame's coordinates and every "frame" line says so
+//                  (setInputOrientation), the boxes are printed in the UPRIGHT frame's coordinates and every "frame" line says so;
+//                  --orient K --min-width M together: turned upright, then reduced, in one kernel (acf_hip_run_yuv_oriented_resized); the
+//                  boxes are mapped back to the upright full-size frame and the "frame" line also names the reduced size
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
@@ -221,6 +223,14 @@ int main(int argc, char** argv)
             {
                 det.setInputOrientation(orient);
                 note = " upright " + std::to_string(orient & 1 ? W : H) + "x" + std::to_string(orient & 1 ? H : W) + " orient " + std::to_string(orient);
+                if (det.getMinObjectWidth() >= 0 && det.inputScale() != 1.f)
+                {
+                    int rh = 0, rw = 0;
+                    if (acf::hip::load().acf_hip_oriented_resized_dims(H, W, orient, double(det.inputScale()), &rh, &rw) == 0)
+                    {
+                        note += " reduced " + std::to_string(rh) + "x" + std::to_string(rw);
+                    }
+                }
             }
             const int B = a.count("stream") ? std::stoi(a["stream"]) : cnt, depth = 2;
             uint8_t* pin[2] = { static_cast<uint8_t*>(HipDetector::pinnedAlloc(per * size_t(B))), static_cast<uint8_t*>(HipDetector::pinnedAlloc(per * size_t(B))) };

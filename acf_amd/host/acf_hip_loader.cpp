@@ -79,6 +79,12 @@ static void doLoad(const std::string& path)
     ACF_HIP_FN(acf_hip_run_yuv_oriented)
     ACF_HIP_FN(acf_hip_stream_open_yuv_oriented)
     ACF_HIP_FN(acf_hip_oriented_dims)
+    ACF_HIP_FN(acf_hip_pyramid_image_oriented_resized)
+    ACF_HIP_FN(acf_hip_run_image_oriented_resized)
+    ACF_HIP_FN(acf_hip_pyramid_yuv_oriented_resized)
+    ACF_HIP_FN(acf_hip_run_yuv_oriented_resized)
+    ACF_HIP_FN(acf_hip_stream_open_yuv_oriented_resized)
+    ACF_HIP_FN(acf_hip_oriented_resized_dims)
     ACF_HIP_FN(acf_hip_unorient_rect)
     ACF_HIP_FN(acf_hip_resize_dims)
     ACF_HIP_FN(acf_hip_set_input_resize)

@@ -634,6 +634,51 @@ ACF_HIP_API int acf_hip_stream_open_yuv_oriented(acf_hip_ctx* ctx, const acf_hip
 ACF_HIP_API int acf_hip_oriented_dims(int src_rows, int src_cols, int orient, int* h, int* w);
 ACF_HIP_API int acf_hip_unorient_rect(int orient, int src_rows, int src_cols, const int32_t in[4], int32_t out[4]);
 
+/* ---- rotated and mirrored frames, reduced to a minimum object width ----
+ * The two families above joined: the frame as stored (src_rows x src_cols = Hs x Ws, an orientation code) is turned upright and THEN
+ * reduced by `scale`, in ONE kernel — the order of the reference's GL front end (GPUACF.cpp: rotate -> smooth -> reduce).  No rotated,
+ * converted or reduced 8-bit image goes to device memory.
+ * Definition: the existing entries composed, bit for bit —
+ *   1. the bytes of S: the addressed u8 elements at the descriptor's strides (image), or acf_hip_yuv_to_rgb8's R, G, B with the chroma
+ *      sample chosen in SOURCE coordinates (YUV), exactly as the oriented entries define it
+ *   2. U = np.rot90(S[:, ::-1] if mirror else S, k=-rot), the upright frame of the oriented entries
+ *   3. acf_hip_op_resize_u8's arithmetic on U as a tight interleaved image of `channels` bytes a pixel (3 for YUV), with the tap tables
+ *      of (upright rows, upright cols, scale)
+ *   4. acf_hip_pyramid_u8 / run_u8 (ACF_HIP_PIX_RGB or ACF_HIP_PIX_GRAY)
+ * i.e. acf_hip_run_image_resized on a tight upright u8 image holding U: every plane, level, hit, score bit and box, option "arith" = 1
+ * included.  Orient-then-resize and resize-then-orient give different bytes (cvRound of the sizes, asymmetric area taps): orient first.
+ * The plan must be for acf_hip_oriented_resized_dims(src_rows, src_cols, orient, scale) = acf_hip_resize_dims(acf_hip_oriented_dims(...)).
+ * Detections are in the reduced upright frame: cv::Rect2f(o) * (1.f / scale) first, then acf_hip_unorient_rect.  cv::resize and cvtColor
+ * are OpenCV's (not part of the reference tree): their published arithmetic is restated; PARITY UNPINNED.
+ * ACF_HIP_ORIENT_UPRIGHT forwards to the *_resized entry.  acf_hip_image_extent / acf_hip_yuv_extent at src_rows x src_cols give the
+ * bytes that may be read, and no load covers an address outside the [first, last] span of the row and plane it belongs to.
+ * Option "profile": k_ingest_oriented_resized_image / k_ingest_oriented_resized_yuv for quarter turns (odd rot) at scales >= 1 / 4 — the
+ * tile's footprint in the stored frame is read along the stored rows into LDS (dword loads for descriptions that meet the un-oriented
+ * entries' row-vector / planar conditions, else bytes) and resampled from there — and the same names with _generic (each lane gathers
+ * its own pixels from device memory) for rot 0 / 2, where the lanes run along the stored rows anyway, for smaller scales, and under
+ * ACF_HIP_FORCE_FALLBACK=oriented_resized_generic.  Both forms give the same bits.
+ * Asynchronous on the context's stream; the tap tables are those of the resized entries (built at the first call with a new upright
+ * size and scale, kept; nothing is allocated on later calls); the calls always run plainly and leave a captured graph of acf_hip_run
+ * (option "graph") valid; ACF_HIP_TAP_IMAGE behaves as after acf_hip_pyramid_u8.
+ * ACF_HIP_E_INVALID: what either family refuses; orient outside 0 .. 7; a plan of other dimensions; an active
+ * acf_hip_set_input_resize; a five-plane plan; a scale that is not a positive finite number.  ACF_HIP_E_UNSUPPORTED: option "streams"
+ * > 1; an image dtype other than ACF_HIP_T_U8.  ACF_HIP_E_NOPLAN without a plan.
+ *  acf_hip_stream_open_yuv_oriented_resized   acf_hip_stream_open_yuv's rules with the one-frame extents taken at src_rows x src_cols;
+ *                                             every submit runs acf_hip_run_yuv_oriented_resized on its slot
+ *  acf_hip_oriented_resized_dims              host arithmetic, no context: the reduced upright h x w; ACF_HIP_E_INVALID for a bad code,
+ *                                             size, scale or null pointer */
+ACF_HIP_API int acf_hip_pyramid_image_oriented_resized(acf_hip_ctx* ctx, const void* frames_dev, int n_frames, const acf_hip_image_desc* desc, int src_rows,
+    int src_cols, int orient, double scale);
+ACF_HIP_API int acf_hip_run_image_oriented_resized(acf_hip_ctx* ctx, const void* frames_dev, int n_frames, const acf_hip_image_desc* desc, int src_rows,
+    int src_cols, int orient, double scale);
+ACF_HIP_API int acf_hip_pyramid_yuv_oriented_resized(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc, int src_rows,
+    int src_cols, int orient, double scale);
+ACF_HIP_API int acf_hip_run_yuv_oriented_resized(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc, int src_rows,
+    int src_cols, int orient, double scale);
+ACF_HIP_API int acf_hip_stream_open_yuv_oriented_resized(acf_hip_ctx* ctx, const acf_hip_yuv_desc* desc, int64_t frame_bytes, int src_rows, int src_cols,
+    int orient, double scale, int cap, int depth);
+ACF_HIP_API int acf_hip_oriented_resized_dims(int src_rows, int src_cols, int orient, double scale, int* h, int* w);
+
 /* ---- streaming front end ---------------------------------------------
  * The overlap of transfer and compute that GPUDetectionPipeline::runFast gets
  * from its two-frame texture FIFO (GPUDetectionPipeline.cpp:357-437), expressed
