@@ -180,6 +180,18 @@ class YuvDesc(C.Structure):
     _fields_ = [("y", YuvPlane), ("u", YuvPlane), ("v", YuvPlane), ("sub_x", C.c_int32), ("sub_y", C.c_int32)]
 
 
+# ACF_HIP_YUV_MATRIX_*
+YUV_MATRIX_BT601, YUV_MATRIX_BT709, YUV_MATRIX_BT2020 = range(3)
+YUV_MATRIX_NAMES = {"bt601": YUV_MATRIX_BT601, "bt709": YUV_MATRIX_BT709, "bt2020": YUV_MATRIX_BT2020}
+
+
+class YuvFormat(C.Structure):
+    """struct acf_hip_yuv_format: sample width (8: bytes; 9 .. 16: little-endian 16-bit words, sample = (word >> shift) & mask),
+    matrix (YUV_MATRIX_*) and range of a video frame.  {8, 0, BT601, 0} is the arithmetic of the YUV entries."""
+
+    _fields_ = [("bits", C.c_int32), ("shift", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32)]
+
+
 _lib = None
 
 
@@ -251,6 +263,13 @@ def load():
         "acf_hip_run_yuv_oriented_resized": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.c_int, C.c_int, C.c_int, C.c_double], C.c_int),
         "acf_hip_stream_open_yuv_oriented_resized": ([ctx, C.POINTER(YuvDesc), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int], C.c_int),
         "acf_hip_oriented_resized_dims": ([C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_pyramid_video": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.POINTER(YuvFormat), C.c_int, C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_run_video": ([ctx, C.c_void_p, C.c_int, C.POINTER(YuvDesc), C.POINTER(YuvFormat), C.c_int, C.c_int, C.c_int, C.c_double], C.c_int),
+        "acf_hip_stream_open_video": ([ctx, C.POINTER(YuvDesc), C.POINTER(YuvFormat), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int], C.c_int),
+        "acf_hip_video_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(YuvDesc), C.POINTER(YuvFormat), C.c_void_p], C.c_int),
+        "acf_hip_video_extent": ([C.POINTER(YuvDesc), C.POINTER(YuvFormat), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
+        "acf_hip_video_layout": ([C.c_int, C.POINTER(YuvFormat), C.c_int, C.c_int, C.c_int, C.POINTER(YuvDesc), C.POINTER(C.c_int64)], C.c_int),
+        "acf_hip_yuv_coeffs": ([C.POINTER(YuvFormat), C.POINTER(C.c_int64)], C.c_int),
         "acf_hip_unorient_rect": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
@@ -323,6 +342,8 @@ DECLARED_SYMBOLS = [
     "acf_hip_stream_open_yuv_oriented", "acf_hip_oriented_dims", "acf_hip_unorient_rect",
     "acf_hip_pyramid_image_oriented_resized", "acf_hip_run_image_oriented_resized", "acf_hip_pyramid_yuv_oriented_resized",
     "acf_hip_run_yuv_oriented_resized", "acf_hip_stream_open_yuv_oriented_resized", "acf_hip_oriented_resized_dims",
+    "acf_hip_pyramid_video", "acf_hip_run_video", "acf_hip_stream_open_video", "acf_hip_video_to_rgb", "acf_hip_video_extent",
+    "acf_hip_video_layout", "acf_hip_yuv_coeffs",
 ]
 
 

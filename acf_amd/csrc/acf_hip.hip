@@ -79,6 +79,7 @@ struct FrameSource
     int srcRows = 0, srcCols = 0;
     double scale = 1;
     int orient = 0;               // the oriented entries (ACF_HIP_ORIENT_*, image and YUV kinds): frames of srcRows x srcCols, turned to the plan's size
+    acf_hip_yuv_format fmt{ 8, 0, ACF_HIP_YUV_MATRIX_BT601, 0 }; // the video entries (SRC_YUV): sample width, matrix and range; this is the default
 };
 
 } // namespace
@@ -2309,7 +2310,7 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
 // acf_hip_stream_open_yuv_oriented (orient: frames of srcRows x srcCols turned to the plan's size; the entry has checked them);
 // acf_hip_stream_open_yuv_oriented_resized: both (turned, then reduced)
 static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc* desc, int64_t frameBytes, bool resized, int srcRows, int srcCols, double scale,
-    int cap, int depth, int orient = 0)
+    int cap, int depth, int orient = 0, const acf_hip_yuv_format& fmt = kDefaultVideoFormat)
 {
     const std::string w = std::string(who) + ": ";
     if (int rc = needPlan(c, who)) return rc;
@@ -2340,7 +2341,7 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     yuvExtent(*desc, ownSize ? srcRows : c->plan.H, ownSize ? srcCols : c->plan.W, 1, first, last);
     for (int i = 0; i < 3; i++)
     {
-        if (first[i] < 0 || last[i] >= frameBytes)
+        if (first[i] < 0 || last[i] + (fmt.bits > 8 ? 1 : 0) >= frameBytes) // (16-bit words: the last byte is the word's high byte)
         {
             return fail(c, ACF_HIP_E_INVALID, w + "every plane of a frame must lie in [0, frame_bytes)");
         }
@@ -2351,7 +2352,7 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     }
     c->stSrc = FrameSource{ SRC_YUV, nullptr,
         resized ? (orient ? "pyramid_yuv_oriented_resized" : "pyramid_yuv_resized") : (orient ? "pyramid_yuv_oriented" : "pyramid_yuv"), 0, 0, {}, *desc, resized, srcRows,
-        srcCols, scale, orient };
+        srcCols, scale, orient, fmt };
     return streamSlots(c, frameBytes, cap, depth);
 }
 
@@ -2385,6 +2386,60 @@ int acf_hip_stream_open_yuv_oriented(acf_hip_ctx* c, const acf_hip_yuv_desc* des
     if (int rc = needPlan(c, "stream_open_yuv_oriented")) return rc;
     if (int rc = orientedBad(c, "stream_open_yuv_oriented: ", srcRows, srcCols, orient)) return rc; // (code 0 too: the frame size is the plan's)
     return streamOpenYuv(c, "stream_open_yuv_oriented", desc, frameBytes, false, srcRows, srcCols, 1.0, cap, depth, orient);
+}
+
+// The video entries' stream: the default format is the existing open call of the family; any other format is the same stream with
+// the format in its FrameSource
+int acf_hip_stream_open_video(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmtIn, int64_t frameBytes, int srcRows, int srcCols, int orient,
+    double scale, int cap, int depth)
+{
+    if (int rc = needPlan(c, "stream_open_video")) return rc;
+    const acf_hip_yuv_format fmt = fmtIn ? *fmtIn : kDefaultVideoFormat;
+    if (const char* bad = videoFormatBad(fmt))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("stream_open_video: ") + bad);
+    }
+    if (!(scale >= 0) || !std::isfinite(scale))
+    {
+        return fail(c, ACF_HIP_E_INVALID, "stream_open_video: scale must be 0 (no resize) or a positive finite number");
+    }
+    const bool plain = orient == 0 && scale == 0 && srcRows == 0 && srcCols == 0;
+    if (videoFormatIsDefault(fmt))
+    {
+        if (plain)
+        {
+            return acf_hip_stream_open_yuv(c, desc, frameBytes, cap, depth);
+        }
+        return scale == 0 ? acf_hip_stream_open_yuv_oriented(c, desc, frameBytes, srcRows, srcCols, orient, cap, depth)
+                          : acf_hip_stream_open_yuv_oriented_resized(c, desc, frameBytes, srcRows, srcCols, orient, scale, cap, depth);
+    }
+    if (!c->kids.empty())
+    {
+        return fail(c, ACF_HIP_E_UNSUPPORTED, "stream_open_video: not available with option \"streams\" > 1");
+    }
+    if (orient < 0 || orient > 7 || (!plain && (srcRows < 1 || srcCols < 1)))
+    {
+        return fail(c, ACF_HIP_E_INVALID, "stream_open_video: orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
+    }
+    if (fmt.bits > 8)
+    {
+        if (orient != 0 || scale != 0)
+        {
+            return fail(c, ACF_HIP_E_UNSUPPORTED, "stream_open_video: more than 8 bits a sample: upright and unreduced frames only (orient 0, scale 0)");
+        }
+        if (desc && !yuvDescBad(desc))
+        {
+            if (const char* bad = video16DescBad(nullptr, *desc))
+            {
+                return fail(c, ACF_HIP_E_INVALID, std::string("stream_open_video: ") + bad);
+            }
+        }
+    }
+    if (scale == 0 && !plain)
+    {
+        if (int rc = orientedBad(c, "stream_open_video: ", srcRows, srcCols, orient)) return rc;
+    }
+    return streamOpenYuv(c, "stream_open_video", desc, frameBytes, scale != 0, srcRows, srcCols, scale == 0 ? 1.0 : scale, cap, depth, orient, fmt);
 }
 
 int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, int* ticket)

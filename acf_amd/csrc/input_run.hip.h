@@ -4,14 +4,16 @@
 // PyramidRun::ingest (pyramid_run.hip.h) launches that plan straight-line.  A new kind of input is one more SourceKind.
 //
 //   u8Geom, imageDescBad, yuvDescBad, yuvExtent      what a layout or a description is, by itself
-//   the kernel tables and form choosers              ingestKernel .. resizedKernel, imageLoadForm, yuvLoadForm, yuvIsSemiPlanar; the oriented
+//   videoFormatBad, video16DescBad, yuvCoef          what an acf_hip_yuv_format is, by itself: its checks and the conversion's constants
+//   the kernel tables and form choosers              ingestKernel .. resizedKernel, yuv16Kernel, imageLoadForm, yuvLoadForm, yuv16LoadForm, yuvIsSemiPlanar; the oriented
 //                                                    entries: imageOrientedKernel, yuvOrientedKernel, orientSrc, orientedBad, yuvIsAlignedPairs;
 //                                                    the oriented resized entries: orientedResizedKernel, orientedResizedBand, planOrientedResized
 //   launchYuvToRgb, launchResizeU8, launchColour     the preludes and the colour conversion (ops.hip.h and crops_run.hip.h call them too)
 //   installResizeTables, resizedTables               the tap tables of acf_hip_set_input_resize (c->rz) and of the resized entries (c->rzIn)
 //   planIngest                                       FrameSource -> IngestPlan, or the refusal
 //   the entries that are only about input            acf_hip_pyramid_u8 / _image / _yuv / *_resized / *_oriented / *_oriented_resized and their run_ twins, the extents
-//                                                    and layouts, acf_hip_set_yuv_layout, acf_hip_set_input_resize, acf_hip_yuv_to_rgb8
+//                                                    and layouts, acf_hip_set_yuv_layout, acf_hip_set_input_resize, acf_hip_yuv_to_rgb8; the video
+//                                                    entries (acf_hip_pyramid_video / run_video / video_to_rgb / video_extent / video_layout / yuv_coeffs)
 #pragma once
 
 namespace
@@ -26,6 +28,7 @@ using ResizedKernel = void (*)(IngestArgs, ResizedSrc);
 using ImageOrientedKernel = void (*)(IngestArgs, ImageOrientedSrc);
 using YuvOrientedKernel = void (*)(IngestArgs, YuvOrientedSrc);
 using OrientedResizedKernel = void (*)(IngestArgs, OrientedResizedSrc);
+using Yuv16Kernel = void (*)(IngestArgs, Yuv16Src);
 
 static IngestKernel ingestKernel(int mode, bool aligned)
 {
@@ -39,8 +42,17 @@ static IngestKernel ingestKernel(int mode, bool aligned)
 }
 
 // (no IG_LUV: a YUV 4:2:0 frame has even H and W, so H * W % 4 == 0 and rgbConvert takes the vector body, rgbConvertMex.cpp:92,343)
-static YuvIngestKernel yuvIngestKernel(int mode, bool aligned)
+static YuvIngestKernel yuvIngestKernel(int mode, bool aligned, bool cf = false)
 {
+    if (cf) // a format other than the default: the constants from YuvSrc::k
+    {
+        switch (mode)
+        {
+            case IG_LUV_VEC: return aligned ? k_ingest_yuv420<IG_LUV_VEC, true, true> : k_ingest_yuv420<IG_LUV_VEC, false, true>;
+            case IG_GRAY: return aligned ? k_ingest_yuv420<IG_GRAY, true, true> : k_ingest_yuv420<IG_GRAY, false, true>;
+            default: return aligned ? k_ingest_yuv420<IG_PLANAR, true, true> : k_ingest_yuv420<IG_PLANAR, false, true>;
+        }
+    }
     switch (mode)
     {
         case IG_LUV_VEC: return aligned ? k_ingest_yuv420<IG_LUV_VEC, true> : k_ingest_yuv420<IG_LUV_VEC, false>;
@@ -61,23 +73,32 @@ static ImageKernel imageKernel(int dtype, int mode)
     return table[dtype][mode];
 }
 
-// k_ingest_yuv<conversion, load form>: [YD_*][IG_*]
-static YuvDescKernel yuvDescKernel(int form, int mode)
+// k_ingest_yuv<conversion, load form, constants as an argument>: [cf][YD_*][IG_*]
+static YuvDescKernel yuvDescKernel(int form, int mode, bool cf = false)
 {
-    static const YuvDescKernel table[3][4] = {
-        { k_ingest_yuv<IG_PLANAR, YD_GENERIC>, k_ingest_yuv<IG_LUV_VEC, YD_GENERIC>, k_ingest_yuv<IG_LUV, YD_GENERIC>, k_ingest_yuv<IG_GRAY, YD_GENERIC> },
-        { k_ingest_yuv<IG_PLANAR, YD_PLANAR>, k_ingest_yuv<IG_LUV_VEC, YD_PLANAR>, k_ingest_yuv<IG_LUV, YD_PLANAR>, k_ingest_yuv<IG_GRAY, YD_PLANAR> },
-        { k_ingest_yuv<IG_PLANAR, YD_PACKED422>, k_ingest_yuv<IG_LUV_VEC, YD_PACKED422>, k_ingest_yuv<IG_LUV, YD_PACKED422>, k_ingest_yuv<IG_GRAY, YD_PACKED422> },
-    };
+#define YDK(FORM, CF) { k_ingest_yuv<IG_PLANAR, FORM, CF>, k_ingest_yuv<IG_LUV_VEC, FORM, CF>, k_ingest_yuv<IG_LUV, FORM, CF>, k_ingest_yuv<IG_GRAY, FORM, CF> }
+    static const YuvDescKernel table[2][3][4] = { { YDK(YD_GENERIC, false), YDK(YD_PLANAR, false), YDK(YD_PACKED422, false) },
+        { YDK(YD_GENERIC, true), YDK(YD_PLANAR, true), YDK(YD_PACKED422, true) } };
+#undef YDK
+    return table[cf][form][mode];
+}
+
+// k_ingest_yuv16<conversion, load form>: [YD16_*][IG_*]
+static Yuv16Kernel yuv16Kernel(int form, int mode)
+{
+#define Y16K(FORM) { k_ingest_yuv16<IG_PLANAR, FORM>, k_ingest_yuv16<IG_LUV_VEC, FORM>, k_ingest_yuv16<IG_LUV, FORM>, k_ingest_yuv16<IG_GRAY, FORM> }
+    static const Yuv16Kernel table[3][4] = { Y16K(YD16_GENERIC), Y16K(YD16_PLANAR), Y16K(YD16_PAIRS) };
+#undef Y16K
     return table[form][mode];
 }
 
 // k_ingest_resized<source, conversion>: [RS_*][IG_*]
 static ResizedKernel resizedKernel(int src, int mode)
 {
-    static const ResizedKernel table[2][4] = {
+    static const ResizedKernel table[3][4] = {
         { k_ingest_resized<RS_IMAGE, IG_PLANAR>, k_ingest_resized<RS_IMAGE, IG_LUV_VEC>, k_ingest_resized<RS_IMAGE, IG_LUV>, k_ingest_resized<RS_IMAGE, IG_GRAY> },
         { k_ingest_resized<RS_YUV, IG_PLANAR>, k_ingest_resized<RS_YUV, IG_LUV_VEC>, k_ingest_resized<RS_YUV, IG_LUV>, k_ingest_resized<RS_YUV, IG_GRAY> },
+        { k_ingest_resized<RS_YUV_CF, IG_PLANAR>, k_ingest_resized<RS_YUV_CF, IG_LUV_VEC>, k_ingest_resized<RS_YUV_CF, IG_LUV>, k_ingest_resized<RS_YUV_CF, IG_GRAY> },
     };
     return table[src][mode];
 }
@@ -98,12 +119,13 @@ static ImageOrientedKernel imageOrientedKernel(int dtype, int mode)
     return table[dtype][mode];
 }
 
-// k_ingest_yuv_oriented<conversion>: [IG_*]
-static YuvOrientedKernel yuvOrientedKernel(int mode)
+// k_ingest_yuv_oriented<conversion, constants as an argument>: [cf][IG_*]
+static YuvOrientedKernel yuvOrientedKernel(int mode, bool cf = false)
 {
-    static const YuvOrientedKernel table[4] = { k_ingest_yuv_oriented<IG_PLANAR>, k_ingest_yuv_oriented<IG_LUV_VEC>, k_ingest_yuv_oriented<IG_LUV>,
-        k_ingest_yuv_oriented<IG_GRAY> };
-    return table[mode];
+    static const YuvOrientedKernel table[2][4] = { { k_ingest_yuv_oriented<IG_PLANAR>, k_ingest_yuv_oriented<IG_LUV_VEC>, k_ingest_yuv_oriented<IG_LUV>,
+                                                       k_ingest_yuv_oriented<IG_GRAY> },
+        { k_ingest_yuv_oriented<IG_PLANAR, true>, k_ingest_yuv_oriented<IG_LUV_VEC, true>, k_ingest_yuv_oriented<IG_LUV, true>, k_ingest_yuv_oriented<IG_GRAY, true> } };
+    return table[cf][mode];
 }
 
 // k_ingest_oriented_resized<source, conversion, staged>: [RS_*][IG_*], the LDS-staged form or the global gather
@@ -111,7 +133,8 @@ static OrientedResizedKernel orientedResizedKernel(int src, int mode, bool stage
 {
 #define ORK(SRC, ST) { k_ingest_oriented_resized<SRC, IG_PLANAR, ST>, k_ingest_oriented_resized<SRC, IG_LUV_VEC, ST>, k_ingest_oriented_resized<SRC, IG_LUV, ST>, \
                        k_ingest_oriented_resized<SRC, IG_GRAY, ST> }
-    static const OrientedResizedKernel table[2][2][4] = { { ORK(RS_IMAGE, false), ORK(RS_YUV, false) }, { ORK(RS_IMAGE, true), ORK(RS_YUV, true) } };
+    static const OrientedResizedKernel table[2][3][4] = { { ORK(RS_IMAGE, false), ORK(RS_YUV, false), ORK(RS_YUV_CF, false) },
+        { ORK(RS_IMAGE, true), ORK(RS_YUV, true), ORK(RS_YUV_CF, true) } };
 #undef ORK
     return table[staged][src][mode];
 }
@@ -345,6 +368,76 @@ static void yuvExtent(const acf_hip_yuv_desc& d, int h, int w, int nF, int64_t f
     }
 }
 
+// The default format: the arithmetic of the YUV entries ({8, 0, BT601, 0}; a null format is it)
+static const acf_hip_yuv_format kDefaultVideoFormat{ 8, 0, ACF_HIP_YUV_MATRIX_BT601, 0 };
+static bool videoFormatIsDefault(const acf_hip_yuv_format& f)
+{
+    return f.bits == 8 && f.shift == 0 && f.matrix == ACF_HIP_YUV_MATRIX_BT601 && f.full_range == 0;
+}
+
+// What is wrong with a format by itself, or null
+static const char* videoFormatBad(const acf_hip_yuv_format& f)
+{
+    if (f.bits < 8 || f.bits > 16)
+    {
+        return "bits must be 8 .. 16";
+    }
+    if (f.shift < 0 || (f.bits == 8 && f.shift != 0) || f.shift + f.bits > 16)
+    {
+        return "shift must be 0 for 8 bits, and shift + bits <= 16";
+    }
+    if (f.matrix < ACF_HIP_YUV_MATRIX_BT601 || f.matrix > ACF_HIP_YUV_MATRIX_BT2020)
+    {
+        return "unknown matrix (ACF_HIP_YUV_MATRIX_*)";
+    }
+    if (f.full_range != 0 && f.full_range != 1)
+    {
+        return "full_range must be 0 or 1";
+    }
+    return nullptr;
+}
+
+// 16-bit words: what is wrong with the description (and the pointer, when there is one) for them, or null
+static const char* video16DescBad(const void* base, const acf_hip_yuv_desc& d)
+{
+    if (reinterpret_cast<uintptr_t>(base) % 2)
+    {
+        return "16-bit samples need an even base";
+    }
+    for (const acf_hip_yuv_plane* p : { &d.y, &d.u, &d.v })
+    {
+        if (p->offset % 2 || p->stride_n % 2 || p->stride_row % 2 || p->stride_px % 2)
+        {
+            return "16-bit samples need even offsets and strides";
+        }
+    }
+    return nullptr;
+}
+
+// The constants of a (checked) format: round(2^20 * q), half away from zero, q the exact rational from Kr / Kb with the luma gain
+// 255 / 219 and the chroma gain 255 / 224 for limited range (tests/video_format_ref.py derives them again with fractions.Fraction);
+// BT.601 limited keeps cvtColor's (from coefficients rounded to three decimals): yuv_chroma / yuv_rgb8's own
+static YuvCoef yuvCoef(const acf_hip_yuv_format& f)
+{
+    static const int table[3][2][5] = {
+        { { 1220542, 1673527, -852492, -409993, 2116026 }, { 1048576, 1470104, -748826, -360853, 1858077 } },
+        { { 1220945, 1879825, -558796, -223607, 2215014 }, { 1048576, 1651297, -490864, -196424, 1945738 } },
+        { { 1220945, 1760217, -682019, -196426, 2245811 }, { 1048576, 1546230, -599107, -172546, 1972791 } },
+    };
+    const int* t = table[f.matrix][f.full_range];
+    YuvCoef k{};
+    k.yoff = f.full_range ? 0 : 16 << (f.bits - 8);
+    k.cmid = 1 << (f.bits - 1);
+    k.omax = f.full_range ? (1 << f.bits) - 1 : 255 << (f.bits - 8);
+    k.cy = t[0];
+    k.cvr = t[1];
+    k.cvg = t[2];
+    k.cug = t[3];
+    k.cub = t[4];
+    k.sc = float(1.0 / double(k.omax));
+    return k;
+}
+
 static YuvDescSrc yuvDescSrc(const uint8_t* base, const acf_hip_yuv_desc& d)
 {
     YuvDescSrc s{};
@@ -384,6 +477,29 @@ static int yuvLoadForm(YuvDescSrc& s)
         }
     }
     return YD_GENERIC;
+}
+
+// The load form of k_ingest_yuv16 for a (checked: all even) description and a pointer; YD16_PAIRS also says which word comes first
+static int yuv16LoadForm(const YuvDescSrc& s, int& vFirst)
+{
+    const uintptr_t at = reinterpret_cast<uintptr_t>(s.base);
+    const auto aligned = [&](const YuvPlane& p) { return (at + uintptr_t(p.off)) % 4 == 0 && p.sr % 4 == 0 && p.sn % 4 == 0; };
+    vFirst = 0;
+    if (s.y.sp != 2 || !aligned(s.y))
+    {
+        return YD16_GENERIC;
+    }
+    if (s.u.sp == 2 && s.v.sp == 2 && aligned(s.u) && aligned(s.v))
+    {
+        return YD16_PLANAR;
+    }
+    const YuvPlane& lo = s.v.off < s.u.off ? s.v : s.u;
+    if (s.u.sp == 4 && s.v.sp == 4 && std::max(s.u.off, s.v.off) == lo.off + 2 && s.u.sr == s.v.sr && s.u.sn == s.v.sn && aligned(lo))
+    {
+        vFirst = s.v.off < s.u.off;
+        return YD16_PAIRS;
+    }
+    return YD16_GENERIC;
 }
 
 // A description of an NV12 / NV21 frame as the 8-bit entry takes it (one row stride, interleaved chroma pairs, even sizes): the
@@ -640,6 +756,7 @@ struct IngestPlan
         ImageOrientedSrc imageOriented;
         YuvOrientedSrc yuvOriented;
         OrientedResizedSrc orientedResized;
+        Yuv16Src yuv16;
     } second{};
     const char* profName = nullptr;   // (static strings: prof keeps the pointer)
     const char* launchName = nullptr;
@@ -653,6 +770,7 @@ struct IngestPlan
     void set(ImageOrientedKernel k, const ImageOrientedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.imageOriented = s; }
     void set(YuvOrientedKernel k, const YuvOrientedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.yuvOriented = s; }
     void set(OrientedResizedKernel k, const OrientedResizedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.orientedResized = s; }
+    void set(Yuv16Kernel k, const Yuv16Src& s) { kernel = reinterpret_cast<const void*>(k); second.yuv16 = s; }
 };
 
 // The upright size of a source that is both oriented and resized — what its tap tables and its plan are for — or the refusal
@@ -678,8 +796,8 @@ static int orientedResizedUpright(acf_hip_ctx* c, const std::string& who, const 
 // 0.74 ms at 1 / 2, 1.74 against 1.70 ms at 80 / 150) —, for footprints that do not fit, and when forced.
 static void planOrientedResized(acf_hip_ctx* c, int kind, int mode, bool vec, OrientedResizedSrc s, const FrameSource& src, IngestPlan& ip)
 {
-    static const char* const names[2][2] = { { "k_ingest_oriented_resized_image_generic", "k_ingest_oriented_resized_yuv_generic" },
-        { "k_ingest_oriented_resized_image", "k_ingest_oriented_resized_yuv" } };
+    static const char* const names[2][3] = { { "k_ingest_oriented_resized_image_generic", "k_ingest_oriented_resized_yuv_generic", "k_ingest_oriented_resized_yuv_generic" },
+        { "k_ingest_oriented_resized_image", "k_ingest_oriented_resized_yuv", "k_ingest_oriented_resized_yuv" } };
     s.r.t = resizeTaps(c->rzIn);
     s.o = orientSrc(src.orient, src.srcRows, src.srcCols);
     int& band = c->rzIn.osBand[s.o.swap];
@@ -852,8 +970,45 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
     {
         return fail(c, ACF_HIP_E_INVALID, who + "the plan's input planes (d) must be 3");
     }
+    // the video entries' format: another matrix or range runs the same 8-bit kernels with the constants as an argument (cf; the profile
+    // names stay); more than 8 bits is k_ingest_yuv16, upright and unreduced only
+    if (const char* bad = videoFormatBad(src.fmt))
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + bad);
+    }
+    const bool cf = !videoFormatIsDefault(src.fmt);
     const uint8_t* base = static_cast<const uint8_t*>(src.base);
+    if (src.fmt.bits > 8)
+    {
+        if (const char* bad = video16DescBad(base, src.yuv))
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + bad);
+        }
+        if (src.orient || src.resized)
+        {
+            return fail(c, ACF_HIP_E_UNSUPPORTED, who + "more than 8 bits a sample: upright and unreduced frames only (orient 0, scale 0)");
+        }
+        if (c->rz.on)
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + "not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)");
+        }
+        static const char* const names16[3] = { "k_ingest_yuv16_generic", "k_ingest_yuv16_planar", "k_ingest_yuv16_pairs" };
+        Yuv16Src y{};
+        y.yuv = yuvDescSrc(base, src.yuv);
+        y.yuv.k = yuvCoef(src.fmt);
+        y.shift = src.fmt.shift;
+        y.mask = (1 << src.fmt.bits) - 1;
+        const int form = yuv16LoadForm(y.yuv, y.vFirst);
+        ip.set(yuv16Kernel(form, mode), y);
+        ip.profName = names16[form];
+        ip.launchName = "k_ingest_yuv16";
+        return ACF_HIP_OK;
+    }
     YuvDescSrc s = yuvDescSrc(base, src.yuv);
+    if (cf)
+    {
+        s.k = yuvCoef(src.fmt);
+    }
     if (src.resized)
     {
         int uprightRows, uprightCols, rc;
@@ -866,13 +1021,13 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
             OrientedResizedSrc o{};
             const bool vec = yuvLoadForm(s) == YD_PLANAR;
             o.r.yuv = s;
-            planOrientedResized(c, RS_YUV, mode, vec, o, src, ip);
+            planOrientedResized(c, cf ? RS_YUV_CF : RS_YUV, mode, vec, o, src, ip);
             return ACF_HIP_OK;
         }
         ResizedSrc r{};
         r.t = resizeTaps(c->rzIn);
         r.yuv = s;
-        ip.set(resizedKernel(RS_YUV, mode), r);
+        ip.set(resizedKernel(cf ? RS_YUV_CF : RS_YUV, mode), r);
         ip.profName = "k_ingest_resized_yuv";
         ip.launchName = "k_ingest_resized";
         return ACF_HIP_OK;
@@ -896,7 +1051,7 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
             y.form = YO_SEMI;
         }
         y.yuv = s;
-        ip.set(yuvOrientedKernel(mode), y);
+        ip.set(yuvOrientedKernel(mode, cf), y);
         ip.profName = y.form == YD_GENERIC ? "k_ingest_yuv_oriented_generic" : (y.o.swap ? "k_ingest_yuv_oriented_cols" : "k_ingest_yuv_oriented_rows");
         ip.launchName = "k_ingest_yuv_oriented";
         return ACF_HIP_OK;
@@ -905,13 +1060,14 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
     if (yuvIsSemiPlanar(base, src.yuv, H, W, semi))
     {
         const bool aligned = reinterpret_cast<uintptr_t>(semi.in) % 4 == 0 && semi.rowStride % 4 == 0 && semi.chromaOff % 4 == 0 && semi.in_fs % 4 == 0;
-        ip.set(yuvIngestKernel(mode, aligned), semi); // (even sizes: never IG_LUV)
+        semi.k = s.k;
+        ip.set(yuvIngestKernel(mode, aligned, cf), semi); // (even sizes: never IG_LUV)
         ip.profName = ip.launchName = "k_ingest_yuv420";
         return ACF_HIP_OK;
     }
     static const char* const names[3] = { "k_ingest_yuv_generic", "k_ingest_yuv_planar", "k_ingest_yuv_packed422" };
     const int form = yuvLoadForm(s);
-    ip.set(yuvDescKernel(form, mode), s);
+    ip.set(yuvDescKernel(form, mode, cf), s);
     ip.profName = names[form];
     ip.launchName = "k_ingest_yuv";
     return ACF_HIP_OK;
@@ -937,14 +1093,14 @@ static int imageEntry(acf_hip_ctx* c, bool detect, const char* who, const void* 
     return detect ? runSource(c, src, nF) : pyramidImpl(c, src, nF);
 }
 static int yuvEntry(acf_hip_ctx* c, bool detect, const char* who, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, bool resized = false, int srcRows = 0,
-    int srcCols = 0, double scale = 1, int orient = 0)
+    int srcCols = 0, double scale = 1, int orient = 0, const acf_hip_yuv_format& fmt = kDefaultVideoFormat)
 {
     if (int rc = needCtx(c)) return rc;
     if (!base || !desc)
     {
         return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": null base or description");
     }
-    const FrameSource src{ SRC_YUV, base, who, 0, 0, {}, *desc, resized, srcRows, srcCols, scale, orient };
+    const FrameSource src{ SRC_YUV, base, who, 0, 0, {}, *desc, resized, srcRows, srcCols, scale, orient, fmt };
     return detect ? runSource(c, src, nF) : pyramidImpl(c, src, nF);
 }
 
@@ -1231,6 +1387,182 @@ int acf_hip_yuv_layout(int layout, int h, int w, int rowStride, acf_hip_yuv_desc
     }
     *out = d;
     *frameBytes = fb;
+    return ACF_HIP_OK;
+}
+
+// ---- the video entries: acf_hip_yuv_format beside the descriptor (the header's "video formats" section) ----
+
+// The default format forwards to the existing entry of the call's family — the same kernels under the same names; any other format
+// goes through the family's own checks (orientedEntry / orientedResizedEntry) and then yuvEntry with the format in the FrameSource.
+static int videoEntry(acf_hip_ctx* c, bool detect, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmtIn, int srcRows, int srcCols,
+    int orient, double scale)
+{
+    if (int rc = needCtx(c)) return rc;
+    const acf_hip_yuv_format fmt = fmtIn ? *fmtIn : kDefaultVideoFormat;
+    const std::string who = detect ? "run_video: " : "pyramid_video: ";
+    if (const char* bad = videoFormatBad(fmt))
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + bad);
+    }
+    if (!(scale >= 0) || !std::isfinite(scale))
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "scale must be 0 (no resize) or a positive finite number");
+    }
+    const bool plain = orient == 0 && scale == 0 && srcRows == 0 && srcCols == 0; // the plan's size
+    if (videoFormatIsDefault(fmt))
+    {
+        if (plain)
+        {
+            return detect ? acf_hip_run_yuv(c, base, nF, desc) : acf_hip_pyramid_yuv(c, base, nF, desc);
+        }
+        if (scale == 0)
+        {
+            return detect ? acf_hip_run_yuv_oriented(c, base, nF, desc, srcRows, srcCols, orient) : acf_hip_pyramid_yuv_oriented(c, base, nF, desc, srcRows, srcCols, orient);
+        }
+        return detect ? acf_hip_run_yuv_oriented_resized(c, base, nF, desc, srcRows, srcCols, orient, scale)
+                      : acf_hip_pyramid_yuv_oriented_resized(c, base, nF, desc, srcRows, srcCols, orient, scale);
+    }
+    if (fmt.bits > 8 && (orient != 0 || scale != 0))
+    {
+        return fail(c, ACF_HIP_E_UNSUPPORTED, who + "more than 8 bits a sample: upright and unreduced frames only (orient 0, scale 0)");
+    }
+    if (plain)
+    {
+        return yuvEntry(c, detect, "pyramid_video", base, nF, desc, false, 0, 0, 1, 0, fmt);
+    }
+    bool forward;
+    if (scale == 0)
+    {
+        if (int rc = orientedEntry(c, "pyramid_video", srcRows, srcCols, orient, forward)) return rc;
+        return yuvEntry(c, detect, "pyramid_video", base, nF, desc, false, srcRows, srcCols, 1, orient, fmt);
+    }
+    if (int rc = orientedResizedEntry(c, "pyramid_video", srcRows, srcCols, orient, forward)) return rc;
+    return yuvEntry(c, detect, "pyramid_video", base, nF, desc, true, srcRows, srcCols, scale, orient, fmt);
+}
+
+int acf_hip_pyramid_video(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, int srcRows, int srcCols, int orient,
+    double scale)
+{
+    return videoEntry(c, false, base, nF, desc, fmt, srcRows, srcCols, orient, scale);
+}
+
+int acf_hip_run_video(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, int srcRows, int srcCols, int orient,
+    double scale)
+{
+    return videoEntry(c, true, base, nF, desc, fmt, srcRows, srcCols, orient, scale);
+}
+
+int acf_hip_video_to_rgb(acf_hip_ctx* c, const uint8_t* base, int nF, int rows, int cols, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmtIn, void* dst)
+{
+    if (int rc = needCtx(c)) return rc;
+    const acf_hip_yuv_format fmt = fmtIn ? *fmtIn : kDefaultVideoFormat;
+    if (const char* bad = videoFormatBad(fmt))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("video_to_rgb: ") + bad);
+    }
+    if (videoFormatIsDefault(fmt))
+    {
+        return acf_hip_yuv_to_rgb8(c, base, nF, rows, cols, desc, static_cast<uint8_t*>(dst));
+    }
+    if (!base || !desc || !dst)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "video_to_rgb: null base, description or destination");
+    }
+    if (const char* bad = yuvDescBad(desc))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("video_to_rgb: ") + bad);
+    }
+    if (nF < 1 || nF > 65535 || rows < 1 || cols < 1)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "video_to_rgb: n_frames 1 .. 65535, rows and cols >= 1");
+    }
+    const dim3 grid(cdiv(cols, 64), cdiv(rows, 4), nF);
+    if (fmt.bits == 8)
+    {
+        YuvDescSrc s = yuvDescSrc(base, *desc);
+        s.k = yuvCoef(fmt);
+        HIPCHK(c, hipSetDevice(c->device));
+        prof(c, c->stream, "k_yuv_to_rgb8");
+        hipLaunchKernelGGL(k_yuv_to_rgb8<true>, grid, dim3(256), 0, c->stream, s, rows, cols, static_cast<uint8_t*>(dst));
+        LAUNCHCHK(c, "k_yuv_to_rgb8");
+        return ACF_HIP_OK;
+    }
+    const char* bad = video16DescBad(base, *desc);
+    if (bad || reinterpret_cast<uintptr_t>(dst) % 2)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string("video_to_rgb: ") + (bad ? bad : "16-bit samples need an even destination"));
+    }
+    Yuv16Src y{};
+    y.yuv = yuvDescSrc(base, *desc);
+    y.yuv.k = yuvCoef(fmt);
+    y.shift = fmt.shift;
+    y.mask = (1 << fmt.bits) - 1;
+    HIPCHK(c, hipSetDevice(c->device));
+    prof(c, c->stream, "k_video_to_rgb16");
+    hipLaunchKernelGGL(k_video_to_rgb16, grid, dim3(256), 0, c->stream, y, rows, cols, static_cast<uint16_t*>(dst));
+    LAUNCHCHK(c, "k_video_to_rgb16");
+    return ACF_HIP_OK;
+}
+
+int acf_hip_video_extent(const acf_hip_yuv_desc* d, const acf_hip_yuv_format* fmtIn, int h, int w, int nF, int64_t* first, int64_t* last)
+{
+    const acf_hip_yuv_format fmt = fmtIn ? *fmtIn : kDefaultVideoFormat;
+    if (!first || !last || yuvDescBad(d) || videoFormatBad(fmt) || h < 1 || w < 1 || nF < 1 || (fmt.bits > 8 && video16DescBad(nullptr, *d)))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    yuvExtent(*d, h, w, nF, first, last);
+    if (fmt.bits > 8)
+    {
+        for (int i = 0; i < 3; i++)
+        {
+            last[i] += 1; // the high byte of the last word
+        }
+    }
+    return ACF_HIP_OK;
+}
+
+int acf_hip_video_layout(int layout, const acf_hip_yuv_format* fmtIn, int h, int w, int rowStride, acf_hip_yuv_desc* out, int64_t* frameBytes)
+{
+    const acf_hip_yuv_format fmt = fmtIn ? *fmtIn : kDefaultVideoFormat;
+    if (videoFormatBad(fmt))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    if (fmt.bits == 8)
+    {
+        return acf_hip_yuv_layout(layout, h, w, rowStride, out, frameBytes);
+    }
+    // two bytes a sample: the layout of w 16-bit words is the 8-bit layout of a row stride counted in words, every byte quantity doubled
+    if (!out || !frameBytes || rowStride < 0 || rowStride % 2)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    acf_hip_yuv_desc d{};
+    int64_t fb = 0;
+    if (int rc = acf_hip_yuv_layout(layout, h, w, rowStride / 2, &d, &fb)) return rc;
+    for (acf_hip_yuv_plane* p : { &d.y, &d.u, &d.v })
+    {
+        p->offset *= 2;
+        p->stride_n *= 2;
+        p->stride_row *= 2;
+        p->stride_px *= 2;
+    }
+    *out = d;
+    *frameBytes = 2 * fb;
+    return ACF_HIP_OK;
+}
+
+int acf_hip_yuv_coeffs(const acf_hip_yuv_format* fmtIn, int64_t* out)
+{
+    const acf_hip_yuv_format fmt = fmtIn ? *fmtIn : kDefaultVideoFormat;
+    if (!out || videoFormatBad(fmt))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    const YuvCoef k = yuvCoef(fmt);
+    const int64_t v[8] = { k.yoff, k.cmid, k.omax, k.cy, k.cvr, k.cvg, k.cug, k.cub };
+    std::copy(v, v + 8, out);
     return ACF_HIP_OK;
 }
 

@@ -616,6 +616,40 @@ __device__ __forceinline__ void yuv_rgb8(int Y, const YuvChroma& c, int& r, int&
     b = min(max((y + c.buv) >> 20, 0), 255);
 }
 
+// The same conversion for any acf_hip_yuv_format (the video entries): the constants of acf_hip_yuv_coeffs as an argument.  CF == false is
+// the default format, {8, 0, BT601, 0}: the two functions above with their constants inline, so every default instantiation is the kernel
+// it was.  8 bits: int32 holds every sum for all six matrix / range rows (|219 * CY| + 2^19 + |CUB| * 128 < 2^31).
+struct YuvCoef
+{
+    int yoff, cmid, omax;
+    int cy, cvr, cvg, cug, cub;
+    float sc; // float(1.0 / omax): a sample as a plane value
+};
+template <bool CF>
+__device__ __forceinline__ YuvChroma yuv_chroma(int u, int v, const YuvCoef& k)
+{
+    if (!CF)
+    {
+        return yuv_chroma(u, v);
+    }
+    u -= k.cmid;
+    v -= k.cmid;
+    return { (1 << 19) + k.cvr * v, (1 << 19) + k.cvg * v + k.cug * u, (1 << 19) + k.cub * u };
+}
+template <bool CF>
+__device__ __forceinline__ void yuv_rgb8(int Y, const YuvChroma& c, const YuvCoef& k, int& r, int& g, int& b)
+{
+    if (!CF)
+    {
+        yuv_rgb8(Y, c, r, g, b);
+        return;
+    }
+    const int y = max(0, Y - k.yoff) * k.cy;
+    r = min(max((y + c.ruv) >> 20, 0), k.omax);
+    g = min(max((y + c.guv) >> 20, 0), k.omax);
+    b = min(max((y + c.buv) >> 20, 0), k.omax);
+}
+
 struct YuvSrc
 {
     const uint8_t* in;
@@ -624,6 +658,7 @@ struct YuvSrc
     int vFirst;        // NV21
     int64_t chromaOff; // bytes from a frame's first luma byte to its first chroma byte
     int64_t in_fs;     // bytes between frames
+    YuvCoef k;         // CF instantiations only (a format other than the default)
 };
 
 // The unfused form: tight packed RGB bytes [H][W][3] per frame (in front of k_resize_u8, acf_hip_op_yuv420_to_rgb, and the
@@ -678,7 +713,7 @@ __device__ __forceinline__ int yg_chroma_slot(int r)
     return IG_T + (r & 1) * 16 + (r >> 1);
 }
 
-template <int MODE, bool ALIGNED>
+template <int MODE, bool ALIGNED, bool CF = false>
 __global__ void __launch_bounds__(256) k_ingest_yuv420(IngestArgs a, YuvSrc s)
 {
     __shared__ uint32_t tileW[(IG_T + IG_T / 2) * YG_PITCH / 4];
@@ -728,13 +763,13 @@ __global__ void __launch_bounds__(256) k_ingest_yuv420(IngestArgs a, YuvSrc s)
         {
             // rows beyond the tile (yq + 2i >= ny) convert whatever the LDS holds: never stored
             const uint8_t* cp = tile + yg_chroma_slot((yq >> 1) + i) * YG_PITCH + (xx & ~1);
-            const YuvChroma c = yuv_chroma(cp[s.vFirst], cp[1 - s.vFirst]);
+            const YuvChroma c = yuv_chroma<CF>(cp[s.vFirst], cp[1 - s.vFirst], s.k);
 #pragma unroll
             for (int jj = 0; jj < 2; jj++)
             {
                 const int j = 2 * i + jj;
                 int r, g, b;
-                yuv_rgb8(tile[yg_luma_slot(yq + j) * YG_PITCH + xx], c, r, g, b);
+                yuv_rgb8<CF>(tile[yg_luma_slot(yq + j) * YG_PITCH + xx], c, s.k, r, g, b);
                 ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
             }
         }
@@ -760,6 +795,7 @@ struct YuvDescSrc
     int subX, subY;        // 0 or 1
     int yPos, uPos, vPos;  // YD_PACKED422: byte of Y0 (Y1 two further), U, V inside the macropixel at `mp`
     int64_t mp;            // YD_PACKED422: offset of the first macropixel (4-aligned with base)
+    YuvCoef k;             // CF instantiations only (a format other than the default)
 };
 enum
 {
@@ -769,6 +805,7 @@ enum
 };
 
 // The descriptor form of k_yuv420_to_rgb8: tight packed RGB bytes [rows][cols][3] per frame.  One thread per pixel; byte accesses.
+template <bool CF = false>
 __global__ void __launch_bounds__(256) k_yuv_to_rgb8(YuvDescSrc s, int rows, int cols, uint8_t* __restrict__ dst)
 {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), r = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -783,7 +820,7 @@ __global__ void __launch_bounds__(256) k_yuv_to_rgb8(YuvDescSrc s, int rows, int
     const int U = B[s.u.off + n * s.u.sn + int64_t(cr) * s.u.sr + int64_t(cc) * s.u.sp];
     const int V = B[s.v.off + n * s.v.sn + int64_t(cr) * s.v.sr + int64_t(cc) * s.v.sp];
     int R, G, Bl;
-    yuv_rgb8(Y, yuv_chroma(U, V), R, G, Bl);
+    yuv_rgb8<CF>(Y, yuv_chroma<CF>(U, V, s.k), s.k, R, G, Bl);
     uint8_t* d = dst + ((n * rows + r) * cols + c) * 3;
     d[0] = uint8_t(R);
     d[1] = uint8_t(G);
@@ -870,7 +907,7 @@ __device__ __forceinline__ void yd_load_rows_generic(const uint8_t* __restrict__
     }
 }
 
-template <int MODE, int FORM>
+template <int MODE, int FORM, bool CF = false>
 __global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
 {
     __shared__ uint32_t tileW[3 * YD_TILE / 4];
@@ -952,10 +989,214 @@ __global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
             if (j == 0 || (j >> subY) != ((j - 1) >> subY)) // a new chroma row (uniform: subY is)
             {
                 const int at = yd_slot((yq + j) >> subY, subY) * YG_PITCH + (xx >> subX);
-                c = yuv_chroma(tile[YD_TILE + at], tile[2 * YD_TILE + at]);
+                c = yuv_chroma<CF>(tile[YD_TILE + at], tile[2 * YD_TILE + at], s.k);
             }
             int r, g, b;
-            yuv_rgb8(tile[yd_slot(yq + j, 0) * YG_PITCH + xx], c, r, g, b);
+            yuv_rgb8<CF>(tile[yd_slot(yq + j, 0) * YG_PITCH + xx], c, s.k, r, g, b);
+            ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
+        }
+        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
+    }
+}
+
+// ------------------------------------------------------------------------
+// YUV frames of 9 .. 16-bit samples (acf_hip_yuv_format with bits > 8: P010 / P012 / P016, yuv420p10le, I210, I410, Y210 ...): every
+// sample is one little-endian 16-bit word at the descriptor's BYTE offsets and strides, sample = (word >> shift) & ((1 << bits) - 1).
+// R, G, B in [0, omax] by the formula of acf_hip_yuv_coeffs in exact integers: 20 fractional bits and 16-bit samples do not fit
+// int32 ((1023 - 64) * CY + CUB * 512 > 2^31), so the sums are int64 (a v_mad_i64_i32 for the luma term, 64-bit adds and shifts behind
+// it); plane value = float(R) * float(1.0 / omax), so the planes are those of k_ingest_image on a tight packed float32 RGB image
+// holding these values, bit for bit.  H.273 gives the matrices; there is no OpenCV counterpart — PARITY UNPINNED.
+// ------------------------------------------------------------------------
+struct YuvChroma64
+{
+    int64_t ruv, guv, buv;
+};
+__device__ __forceinline__ YuvChroma64 yuv16_chroma(int u, int v, const YuvCoef& k)
+{
+    u -= k.cmid;
+    v -= k.cmid;
+    return { (1 << 19) + int64_t(k.cvr) * v, (1 << 19) + int64_t(k.cvg) * v + int64_t(k.cug) * u, (1 << 19) + int64_t(k.cub) * u };
+}
+__device__ __forceinline__ void yuv16_rgb(int Y, const YuvChroma64& c, const YuvCoef& k, int& r, int& g, int& b)
+{
+    // |sum| < 2^38 (16-bit samples, constants below 2^22), so sum >> 20 fits int32: the clamp is a 32-bit one on the same integers
+    const int64_t y = int64_t(max(0, Y - k.yoff)) * k.cy;
+    r = min(max(int((y + c.ruv) >> 20), 0), k.omax);
+    g = min(max(int((y + c.guv) >> 20), 0), k.omax);
+    b = min(max(int((y + c.buv) >> 20), 0), k.omax);
+}
+
+struct Yuv16Src
+{
+    YuvDescSrc yuv;    // byte offsets and strides, all even (host-checked); yuv.k: the format's constants
+    int shift, mask;   // sample = (word >> shift) & mask
+    int vFirst;        // YD16_PAIRS: a chroma dword is (V, U)
+};
+enum
+{
+    YD16_GENERIC = 0, // 16-bit loads, any even offsets and strides
+    YD16_PLANAR = 1,  // all three sp == 2; base + off, sr, sn of every plane multiples of 4: a dword holds two samples
+    YD16_PAIRS = 2    // luma as YD16_PLANAR; U and V interleaved 16-bit pairs, 4-aligned: a chroma dword is one (U, V) or (V, U) pair
+};
+
+// The conversion alone for more than 8 bits: tight packed [rows][cols][3] per frame, uint16 samples in [0, omax].  One thread a pixel.
+__global__ void __launch_bounds__(256) k_video_to_rgb16(Yuv16Src S, int rows, int cols, uint16_t* __restrict__ dst)
+{
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), r = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (c >= cols || r >= rows)
+    {
+        return;
+    }
+    const YuvDescSrc& s = S.yuv;
+    const int64_t n = blockIdx.z;
+    const int cr = r >> s.subY, cc = c >> s.subX;
+    const uint8_t* __restrict__ B = s.base;
+    const auto at = [&](const YuvPlane& p, int pr, int pc) {
+        return (int(*reinterpret_cast<const uint16_t*>(B + p.off + n * p.sn + int64_t(pr) * p.sr + int64_t(pc) * p.sp)) >> S.shift) & S.mask;
+    };
+    int R, G, Bl;
+    yuv16_rgb(at(s.y, r, c), yuv16_chroma(at(s.u, cr, cc), at(s.v, cr, cc), s.k), s.k, R, G, Bl);
+    uint16_t* d = dst + ((n * rows + r) * cols + c) * 3;
+    d[0] = uint16_t(R);
+    d[1] = uint16_t(G);
+    d[2] = uint16_t(Bl);
+}
+
+// The hot path: k_ingest_yuv's shape for 16-bit words.  A workgroup owns 64 x 64 pixels; the load phase runs lanes along the rows of
+// each plane into three LDS tiles of 16-bit samples, masked and shifted on the way in; then the shared store phase: a lane takes four
+// consecutive image-y of one image-x through ingest_convert / ingest_store, one float4 a plane.  Sizes may be odd (IG_LUV is reachable):
+// ceil(ny / 2^subY) chroma rows of ceil(nx / 2^subX) samples.  a.in / cpp / ro / go / bo / rowStride / in_fs of IngestArgs are not read.
+//
+// Load forms (FORM, chosen on the host from the descriptor and the base's alignment alone; all give the same tiles):
+//   YD16_PLANAR   every plane's rows as dwords (two samples) by consecutive lanes; an odd row's last sample as one 16-bit load
+//   YD16_PAIRS    luma as YD16_PLANAR; a lane's chroma dword is one pair: one sample to the U tile, one to the V tile
+//   YD16_GENERIC  one 16-bit load a lane and sample, any even strides (packed 4:2:2 of words — Y210 — runs here)
+// No load covers a byte outside the [first, last] span the same row of the same plane addresses (YD16_PAIRS: of the pairs the row
+// addresses), so a plane may end with its allocation.
+//
+// LDS: three tiles (Y, U, V) of 64 slots x 33 dwords (66 samples, 64 used); row r of a plane in slot yd_slot(r, its subY): luma
+// (r & 3) * 16 + (r >> 2), chroma the same when subY == 0, (r & 1) * 16 + (r >> 1) when subY == 1.  Bank = dword address % 32 per
+// 32-lane half (MI355X LDS rule for 4-byte and narrower accesses); 16 slots are 16 * 33 = 528 = 16 (mod 32) dwords apart, one slot 1:
+//   store phase (16-bit reads)  a half is 16 row-quads x 2 adjacent image-x (xx even, xx + 1), which share a dword of the luma tile
+//                               (column xx >> 1) and a dword or a sample of the chroma tiles: read j takes luma rows 4k + j = slots
+//                               16j + k and chroma rows (4k + j) >> subY = slots 16j + k or 16(j >> 1) + k, k = 0 .. 15: banks
+//                               16j + k + const (mod 32): 16 distinct banks, conflict-free, for each tile
+//   YD16_PLANAR (dword writes)  luma, and chroma with subX == 0: a half writes the 32 dwords of one row: 32 distinct banks.  Chroma
+//                               with subX == 1: the 16 dwords of rows r, r + 1 (r even): 16 slots apart with either row order =
+//                               16 (mod 32) dwords: 32 distinct banks
+//   YD16_PAIRS chroma           a half is the 32 pairs of one row: 16-bit writes, two lanes a dword, 16 distinct banks a tile
+//   YD16_GENERIC                a half writes 32 consecutive samples of one row: two lanes a dword, 16 distinct banks
+// (degrees derived from the address maps with the bank rule; whether 16-bit writes of two lanes to one dword serialise, and the
+// SQ_LDS_BANK_CONFLICT counter: not measured.)  3 x 64 x 33 dwords = 25344 bytes: six workgroups a CU by LDS.  By the compiler's resource
+// report (-Rpass-analysis=kernel-resource-usage, gfx950; all twelve instantiations): 35 .. 44 VGPRs, 63 .. 88 SGPRs, no scratch, 6 waves a SIMD.
+constexpr int Y16_PITCH = 66;                // samples; 33 dwords
+constexpr int Y16_TILE = IG_T * Y16_PITCH;   // samples between the Y, U and V tiles
+
+// YD16_PLANAR: rows x ns samples of one plane (first byte p, sr bytes apart) to a tile; 1 << lg dwords a tile row; PASSES * 256 >=
+// rows << lg (constant trip counts, so that the loads of all the passes are in flight together)
+template <int PASSES>
+__device__ __forceinline__ void y16_load_rows_vec(const uint8_t* __restrict__ p, int64_t sr, int rows, int ns, int lg, int slotSubY, int shift, uint32_t mask,
+    uint32_t* tileW)
+{
+#pragma unroll
+    for (int pass = 0; pass < PASSES; pass++)
+    {
+        const int i = threadIdx.x + pass * 256;
+        const int row = i >> lg, j = i & ((1 << lg) - 1);
+        if (row < rows && 2 * j < ns)
+        {
+            const uint8_t* rp = p + int64_t(row) * sr + 4 * j;
+            // the row's last sample when ns is odd: its 16 bits only
+            const uint32_t w = (2 * j + 2 <= ns) ? *reinterpret_cast<const uint32_t*>(rp) : uint32_t(*reinterpret_cast<const uint16_t*>(rp));
+            tileW[yd_slot(row, slotSubY) * (Y16_PITCH / 2) + j] = (((w & 0xffffu) >> shift) & mask) | ((((w >> 16) >> shift) & mask) << 16);
+        }
+    }
+}
+
+// YD16_GENERIC: rows x cols samples of one plane (sp bytes apart in a row); 1 << lg lanes a tile row
+__device__ __forceinline__ void y16_load_rows_generic(const uint8_t* __restrict__ p, int64_t sr, int64_t sp, int rows, int cols, int lg, int slotSubY, int shift,
+    int mask, uint16_t* tile)
+{
+#pragma unroll 4
+    for (int i = threadIdx.x; i < (rows << lg); i += 256)
+    {
+        const int row = i >> lg, col = i & ((1 << lg) - 1);
+        if (col < cols)
+        {
+            const int w = *reinterpret_cast<const uint16_t*>(p + int64_t(row) * sr + int64_t(col) * sp);
+            tile[yd_slot(row, slotSubY) * Y16_PITCH + col] = uint16_t((w >> shift) & mask);
+        }
+    }
+}
+
+template <int MODE, int FORM>
+__global__ void __launch_bounds__(256) k_ingest_yuv16(IngestArgs a, Yuv16Src S)
+{
+    __shared__ uint32_t tileW[3 * Y16_TILE / 2];
+    uint16_t* tile = reinterpret_cast<uint16_t*>(tileW);
+    const YuvDescSrc& s = S.yuv;
+    const int x0 = blockIdx.x * IG_T, y0 = blockIdx.y * IG_T;
+    const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0);
+    const int subX = s.subX, subY = s.subY;
+    const int cnx = (nx + subX) >> subX, cny = (ny + subY) >> subY; // chroma samples a tile row, chroma rows (x0, y0 are even)
+    const int64_t n = blockIdx.z;
+    const int shift = S.shift, mask = S.mask;
+    const uint8_t* py = s.base + s.y.off + n * s.y.sn + int64_t(y0) * s.y.sr + int64_t(x0) * s.y.sp;
+    const uint8_t* pu = s.base + s.u.off + n * s.u.sn + int64_t(y0 >> subY) * s.u.sr + int64_t(x0 >> subX) * s.u.sp;
+    const uint8_t* pv = s.base + s.v.off + n * s.v.sn + int64_t(y0 >> subY) * s.v.sr + int64_t(x0 >> subX) * s.v.sp;
+    if (FORM == YD16_PLANAR)
+    {
+        // sp == 2; base + off, sr, sn of every plane are multiples of 4 (host-checked) and (x0 >> subX) * 2 is
+        y16_load_rows_vec<8>(py, s.y.sr, ny, nx, 5, 0, shift, uint32_t(mask), tileW);
+        y16_load_rows_vec<8>(pu, s.u.sr, cny, cnx, 5 - subX, subY, shift, uint32_t(mask), tileW + Y16_TILE / 2);
+        y16_load_rows_vec<8>(pv, s.v.sr, cny, cnx, 5 - subX, subY, shift, uint32_t(mask), tileW + 2 * (Y16_TILE / 2));
+    }
+    else if (FORM == YD16_PAIRS)
+    {
+        // luma as planar; chroma: u.sp == v.sp == 4, the two planes 2 bytes apart with one sr and sn, the lower one 4-aligned with base
+        y16_load_rows_vec<8>(py, s.y.sr, ny, nx, 5, 0, shift, uint32_t(mask), tileW);
+        const uint8_t* pc = S.vFirst ? pv : pu; // the pair's first word
+        const int lg = 6 - subX;
+#pragma unroll 4
+        for (int i = threadIdx.x; i < (cny << lg); i += 256)
+        {
+            const int row = i >> lg, col = i & ((1 << lg) - 1);
+            if (col < cnx)
+            {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(pc + int64_t(row) * s.u.sr + 4 * col);
+                const uint32_t lo = ((w & 0xffffu) >> shift) & uint32_t(mask), hi = ((w >> 16) >> shift) & uint32_t(mask);
+                const int at = yd_slot(row, subY) * Y16_PITCH + col;
+                tile[Y16_TILE + at] = uint16_t(S.vFirst ? hi : lo);
+                tile[2 * Y16_TILE + at] = uint16_t(S.vFirst ? lo : hi);
+            }
+        }
+    }
+    else
+    {
+        y16_load_rows_generic(py, s.y.sr, s.y.sp, ny, nx, 6, 0, shift, mask, tile);
+        y16_load_rows_generic(pu, s.u.sr, s.u.sp, cny, cnx, 6 - subX, subY, shift, mask, tile + Y16_TILE);
+        y16_load_rows_generic(pv, s.v.sr, s.v.sp, cny, cnx, 6 - subX, subY, shift, mask, tile + 2 * Y16_TILE);
+    }
+    __syncthreads();
+    const int yq = (threadIdx.x & 15) * 4;
+    const float sc = s.k.sc;
+    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
+    const int64_t np = int64_t(a.H) * a.W;
+    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
+    {
+        float o[3][4];
+        YuvChroma64 c{};
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            // rows beyond the tile (yq + j >= ny) convert whatever the LDS holds: R, G, B are clamped to [0, omax] whatever it is: never stored
+            if (j == 0 || (j >> subY) != ((j - 1) >> subY)) // a new chroma row (uniform: subY is)
+            {
+                const int at = yd_slot((yq + j) >> subY, subY) * Y16_PITCH + (xx >> subX);
+                c = yuv16_chroma(tile[Y16_TILE + at], tile[2 * Y16_TILE + at], s.k);
+            }
+            int r, g, b;
+            yuv16_rgb(tile[yd_slot(yq + j, 0) * Y16_PITCH + xx], c, s.k, r, g, b);
             ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
         }
         ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
@@ -1299,12 +1540,32 @@ __device__ __forceinline__ void yo_load_vec(const OrientTile& T, const uint8_t* 
     }
 }
 
-template <int MODE>
+// CF: the conversion's constants go through LDS (36 bytes, written first, read behind the barrier into vector registers): the load
+// phase runs at the scalar register limit, and nine more live scalars spilled to scratch
+template <bool CF>
+__device__ __forceinline__ YuvCoef* yo_coef_lds()
+{
+    if constexpr (CF)
+    {
+        __shared__ YuvCoef kS;
+        return &kS;
+    }
+    else
+    {
+        return nullptr;
+    }
+}
+
+template <int MODE, bool CF = false>
 __global__ void __launch_bounds__(256) k_ingest_yuv_oriented(IngestArgs a, YuvOrientedSrc S)
 {
     __shared__ uint32_t tileW[3 * YD_TILE / 4];
     uint8_t* tile = reinterpret_cast<uint8_t*>(tileW);
     const YuvDescSrc& s = S.yuv;
+    if (CF && threadIdx.x == 0)
+    {
+        *yo_coef_lds<CF>() = s.k;
+    }
     const int x0 = blockIdx.x * IG_T, y0 = blockIdx.y * IG_T;
     const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0);
     const OrientTile T = orient_tile(S.o, x0, y0, nx, ny);
@@ -1417,6 +1678,7 @@ __global__ void __launch_bounds__(256) k_ingest_yuv_oriented(IngestArgs a, YuvOr
     const float sc = float(1.0 / 255.0);
     float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
     const int64_t np = int64_t(a.H) * a.W;
+    const YuvCoef k = CF ? *yo_coef_lds<CF>() : YuvCoef{};
     for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
     {
         float o[3][4];
@@ -1426,7 +1688,7 @@ __global__ void __launch_bounds__(256) k_ingest_yuv_oriented(IngestArgs a, YuvOr
             // rows beyond the tile (yq + j >= ny) convert whatever the LDS holds (8-bit R, G, B whatever it is): never stored
             const int at = yd_slot(yq + j, 0) * YG_PITCH + xx;
             int r, g, b;
-            yuv_rgb8(tile[at], yuv_chroma(tile[YD_TILE + at], tile[2 * YD_TILE + at]), r, g, b);
+            yuv_rgb8<CF>(tile[at], yuv_chroma<CF>(tile[YD_TILE + at], tile[2 * YD_TILE + at], k), k, r, g, b);
             ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
         }
         ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
@@ -1654,25 +1916,29 @@ struct RzImageSrc
         v[3] = 0;
     }
 };
-struct RzYuvSrc
+template <bool CF>
+struct RzYuvSrcT
 {
     const uint8_t *py, *pu, *pv; // frame n's first sample of each plane
     int64_t ysr, ysp, usr, usp, vsr, vsp;
     int subX, subY;
+    YuvCoef k; // CF only
     __device__ __forceinline__ void px(int y, int x, int (&v)[4]) const
     {
         const int cr = y >> subY, cc = x >> subX;
         const int Y = py[int64_t(y) * ysr + int64_t(x) * ysp];
         const int U = pu[int64_t(cr) * usr + int64_t(cc) * usp];
         const int V = pv[int64_t(cr) * vsr + int64_t(cc) * vsp];
-        yuv_rgb8(Y, yuv_chroma(U, V), v[0], v[1], v[2]);
+        yuv_rgb8<CF>(Y, yuv_chroma<CF>(U, V, k), k, v[0], v[1], v[2]);
         v[3] = 0;
     }
 };
+using RzYuvSrc = RzYuvSrcT<false>;
 enum
 {
     RS_IMAGE = 0,
-    RS_YUV = 1
+    RS_YUV = 1,
+    RS_YUV_CF = 2 // RS_YUV with the conversion's constants from yuv.k (a format other than the default)
 };
 struct ResizedSrc
 {
@@ -1692,15 +1958,15 @@ __global__ void __launch_bounds__(256) k_ingest_resized(IngestArgs a, ResizedSrc
     const int xx = threadIdx.x & 63;
     if (xx < nx)
     {
-        const int cn = SRC == RS_YUV ? 3 : s.im.nIn;
+        const int cn = SRC != RS_IMAGE ? 3 : s.im.nIn;
         for (int yy = threadIdx.x >> 6; yy < ny; yy += 4)
         {
             uint8_t o[4];
-            if (SRC == RS_YUV)
+            if (SRC != RS_IMAGE)
             {
                 const YuvDescSrc& d = s.yuv;
-                const RzYuvSrc src{ d.base + d.y.off + n * d.y.sn, d.base + d.u.off + n * d.u.sn, d.base + d.v.off + n * d.v.sn, d.y.sr, d.y.sp, d.u.sr,
-                    d.u.sp, d.v.sr, d.v.sp, d.subX, d.subY };
+                const RzYuvSrcT<SRC == RS_YUV_CF> src{ d.base + d.y.off + n * d.y.sn, d.base + d.u.off + n * d.u.sn, d.base + d.v.off + n * d.v.sn, d.y.sr, d.y.sp, d.u.sr,
+                    d.u.sp, d.v.sr, d.v.sp, d.subX, d.subY, d.k };
                 rz_pixel(src, s.t, x0 + xx, y0 + yy, o);
             }
             else
@@ -1892,6 +2158,7 @@ __device__ __forceinline__ void os_stage_image(const ImageArgs& s, const uint8_t
 }
 
 // STAGED load phase, a YUV description: the rectangle T of frame n, converted once per source pixel, to the stage
+template <bool CF>
 __device__ __forceinline__ void os_stage_yuv(const YuvDescSrc& s, int64_t n, const OrientTile& T, int Ws, int pitch, int vec, uint32_t* stage)
 {
     const uint8_t* fy = s.base + s.y.off + n * s.y.sn;
@@ -1935,7 +2202,7 @@ __device__ __forceinline__ void os_stage_yuv(const YuvDescSrc& s, int64_t n, con
                 {
                     const int ct = 8 * (t >> subX);
                     int r, g, b;
-                    yuv_rgb8(int((Y >> (8 * t)) & 255), yuv_chroma(int((U >> ct) & 255), int((V >> ct) & 255)), r, g, b);
+                    yuv_rgb8<CF>(int((Y >> (8 * t)) & 255), yuv_chroma<CF>(int((U >> ct) & 255), int((V >> ct) & 255), s.k), s.k, r, g, b);
                     stage[i * pitch + j] = uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(b) << 16);
                 }
             }
@@ -1952,7 +2219,7 @@ __device__ __forceinline__ void os_stage_yuv(const YuvDescSrc& s, int64_t n, con
             const int U = fu[int64_t(cr) * s.u.sr + int64_t(cc) * s.u.sp];
             const int V = fv[int64_t(cr) * s.v.sr + int64_t(cc) * s.v.sp];
             int r, g, b;
-            yuv_rgb8(Y, yuv_chroma(U, V), r, g, b);
+            yuv_rgb8<CF>(Y, yuv_chroma<CF>(U, V, s.k), s.k, r, g, b);
             stage[i * pitch + j] = uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(b) << 16);
         }
     }
@@ -1969,7 +2236,7 @@ __global__ void __launch_bounds__(256) k_ingest_oriented_resized(IngestArgs a, O
     const int nx = min(IG_T, a.W - x0), ny = min(IG_T, a.H - y0);
     const int64_t n = blockIdx.z;
     const int xx = threadIdx.x & 63;
-    const int cn = SRC == RS_YUV ? 3 : S.r.im.nIn;
+    const int cn = SRC != RS_IMAGE ? 3 : S.r.im.nIn;
     const auto put = [&](int yy, const uint8_t (&o)[4]) {
         uint8_t* t = tile + yy * IG_PITCH + 3 * xx;
         t[0] = o[0];
@@ -1983,11 +2250,11 @@ __global__ void __launch_bounds__(256) k_ingest_oriented_resized(IngestArgs a, O
             for (int yy = threadIdx.x >> 6; yy < ny; yy += 4)
             {
                 uint8_t o[4];
-                if (SRC == RS_YUV)
+                if (SRC != RS_IMAGE)
                 {
                     const YuvDescSrc& d = S.r.yuv;
-                    const RzOrientedSrc<RzYuvSrc> src{ { d.base + d.y.off + n * d.y.sn, d.base + d.u.off + n * d.u.sn, d.base + d.v.off + n * d.v.sn, d.y.sr, d.y.sp,
-                                                          d.u.sr, d.u.sp, d.v.sr, d.v.sp, d.subX, d.subY },
+                    const RzOrientedSrc<RzYuvSrcT<SRC == RS_YUV_CF>> src{ { d.base + d.y.off + n * d.y.sn, d.base + d.u.off + n * d.u.sn, d.base + d.v.off + n * d.v.sn, d.y.sr,
+                                                                             d.y.sp, d.u.sr, d.u.sp, d.v.sr, d.v.sp, d.subX, d.subY, d.k },
                         S.o };
                     rz_pixel(src, tp, x0 + xx, y0 + yy, o);
                 }
@@ -2022,9 +2289,9 @@ __global__ void __launch_bounds__(256) k_ingest_oriented_resized(IngestArgs a, O
             {
                 __syncthreads(); // the band before is read
             }
-            if (SRC == RS_YUV)
+            if (SRC != RS_IMAGE)
             {
-                os_stage_yuv(S.r.yuv, n, T, S.o.Ws, pitch, S.vec, stage);
+                os_stage_yuv<SRC == RS_YUV_CF>(S.r.yuv, n, T, S.o.Ws, pitch, S.vec, stage);
             }
             else
             {

@@ -384,6 +384,98 @@ class HipDetector:
             self._chk(self.lib.acf_hip_stream_open_yuv_oriented_resized(self.ctx, C.byref(desc), frame_bytes, src_rows, src_cols, orient, float(scale), cap, depth))
         self._stream_cap = cap
 
+    # ---- video formats (acf_hip_yuv_format): 9 .. 16-bit samples, BT.709 / BT.2020, full range, beside the same descriptors
+    @staticmethod
+    def video_format(bits=8, shift=0, matrix="bt601", full_range=False):
+        """capi.YuvFormat: bits 8 (bytes) or 9 .. 16 (little-endian words, sample = (word >> shift) & mask; P010: bits 10, shift 6),
+        matrix "bt601" / "bt709" / "bt2020" or capi.YUV_MATRIX_*, full_range False = limited ("video")."""
+        code = capi.YUV_MATRIX_NAMES.get(matrix.lower(), -1) if isinstance(matrix, str) else int(matrix)
+        return capi.YuvFormat(int(bits), int(shift), code, int(full_range))
+
+    @staticmethod
+    def video_desc(layout, H, W, fmt=None, row_stride=0):
+        """(capi.YuvDesc, frame bytes) of a named layout with the format's 1 or 2 bytes a sample (row_stride in bytes; 0 = tight)."""
+        code = capi.YUV_NAMES.get(layout.lower(), -1) if isinstance(layout, str) else layout
+        desc, fb = capi.YuvDesc(), C.c_int64()
+        rc = capi.load().acf_hip_video_layout(code, C.byref(fmt) if fmt is not None else None, H, W, row_stride, C.byref(desc), C.byref(fb))
+        if rc:
+            raise HipError(rc, "acf_hip_video_layout(%r, %d x %d, stride %d)" % (layout, H, W, row_stride))
+        return desc, fb.value
+
+    @staticmethod
+    def video_extent(desc, fmt, h, w, n):
+        """([first Y, U, V], [last Y, U, V]): the lowest and highest BYTE offset from the base a call reads of each plane."""
+        lo, hi = (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        rc = capi.load().acf_hip_video_extent(C.byref(desc), C.byref(fmt) if fmt is not None else None, h, w, n, lo, hi)
+        if rc:
+            raise HipError(rc, "acf_hip_video_extent")
+        return list(lo), list(hi)
+
+    @staticmethod
+    def yuv_coeffs(fmt=None):
+        """[yoff, cmid, out_max, CY, CVR, CVG, CUG, CUB] of a format (host arithmetic)."""
+        out = (C.c_int64 * 8)()
+        rc = capi.load().acf_hip_yuv_coeffs(C.byref(fmt) if fmt is not None else None, out)
+        if rc:
+            raise HipError(rc, "acf_hip_yuv_coeffs")
+        return list(out)
+
+    def _video_args(self, fmt, src_rows, src_cols, orient, scale):
+        """(format pointer, src_rows, src_cols, orient, scale) as the C entries take them: scale None = 0 = no resize; a size left
+        out is the plan's, turned back, when the frame is turned, and 0 x 0 (the plain entry) otherwise."""
+        if src_rows is None or src_cols is None:
+            src_rows, src_cols = self._src_size(orient, None, None) if orient else (0, 0)
+        return (C.byref(fmt) if fmt is not None else None), src_rows, src_cols, orient, float(scale) if scale is not None else 0.0
+
+    def pyramid_video(self, base, n, desc, fmt=None, src_rows=None, src_cols=None, orient=0, scale=None):
+        """pyramid_yuv / _oriented / _resized for frames of any capi.YuvFormat (fmt None: the default, which forwards to them).
+        base: a torch device tensor (its first byte is the base) or a device pointer.  More than 8 bits: orient 0 and no scale."""
+        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
+        self._chk(self.lib.acf_hip_pyramid_video(self.ctx, ptr, n, C.byref(desc), *self._video_args(fmt, src_rows, src_cols, orient, scale)))
+
+    def run_video(self, base, n, desc, fmt=None, src_rows=None, src_cols=None, orient=0, scale=None):
+        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
+        self._chk(self.lib.acf_hip_run_video(self.ctx, ptr, n, C.byref(desc), *self._video_args(fmt, src_rows, src_cols, orient, scale)))
+
+    def video_to_rgb(self, base, n, rows, cols, desc, fmt=None):
+        """The conversion alone on the device -> torch CUDA tensor [n][rows][cols][3] of R, G, B in [0, out_max]: uint8 for 8 bits,
+        else 16-bit words (int16 storage: view them as uint16 on the host) (acf_hip_video_to_rgb; no model or plan)."""
+        import torch
+        wide = fmt is not None and fmt.bits > 8
+        out = torch.empty((n, rows, cols, 3), dtype=torch.int16 if wide else torch.uint8, device="cuda")
+        self._chk(self.lib.acf_hip_video_to_rgb(self.ctx, C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, rows, cols, C.byref(desc),
+                                                C.byref(fmt) if fmt is not None else None, C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return out
+
+    def stream_open_video(self, desc, fmt, frame_bytes, cap=1024, depth=2, src_rows=None, src_cols=None, orient=0, scale=None):
+        """The streaming front end for host frames of frame_bytes each in any format: every submit runs run_video on its slot."""
+        f, sr, sc, o, s = self._video_args(fmt, src_rows, src_cols, orient, scale)
+        self._chk(self.lib.acf_hip_stream_open_video(self.ctx, C.byref(desc), f, frame_bytes, sr, sc, o, s, cap, depth))
+        self._stream_cap = cap
+
+    @staticmethod
+    def video_planes_desc(y, u, v, sub_x, sub_y):
+        """yuv_planes_desc for uint8 or 16-bit (int16 / uint16) torch device tensors [n, rows, cols]: strides in bytes."""
+        def plane(t):
+            if t.dim() == 2:
+                t = t[None]
+            if t.dim() != 3 or not t.is_cuda or t.element_size() != y.element_size() or t.element_size() > 2 or t.is_floating_point():
+                raise HipError(capi.E_INVALID, "run_video_planes: uint8 or 16-bit integer device tensors [n, rows, cols] of one type")
+            return t
+        y, u, v = plane(y), plane(u), plane(v)
+        if not (y.shape[0] == u.shape[0] == v.shape[0]):
+            raise HipError(capi.E_INVALID, "run_video_planes: the planes hold different numbers of frames")
+        base, es = y.data_ptr(), y.element_size()
+        mk = lambda t: capi.YuvPlane(t.data_ptr() - base, es * t.stride(0) if t.shape[0] > 1 else 0, es * t.stride(1), es * t.stride(2))
+        return base, y.shape[0], capi.YuvDesc(mk(y), mk(u), mk(v), sub_x, sub_y)
+
+    def run_video_planes(self, y, u, v, sub_x=1, sub_y=1, fmt=None, scale=None, orient=0):
+        """run_yuv_planes for any format: uint8 planes, or 16-bit planes with fmt.bits > 8 (upright and unreduced only)."""
+        base, n, desc = self.video_planes_desc(y, u, v, sub_x, sub_y)
+        own = scale is not None or orient
+        self.run_video(base, n, desc, fmt, y.shape[-2] if own else None, y.shape[-1] if own else None, orient, scale)
+
     # ---- the apps' resize to a minimum object width (acf.cpp:117-148 Resizer) in front of the 8-bit entries
     @staticmethod
     def resize_scale(win_width, min_width):

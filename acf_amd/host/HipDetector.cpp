@@ -664,6 +664,11 @@ int HipDetector::detectImages(const void* framesDev, int nFrames, int rows, int 
     return 0;
 }
 
+static bool isDefaultVideoFormat(const acf_hip_yuv_format& f)
+{
+    return f.bits == 8 && f.shift == 0 && f.matrix == ACF_HIP_YUV_MATRIX_BT601 && f.full_range == 0;
+}
+
 int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc& desc, std::vector<RectVec>& objects,
     std::vector<RealVec>* scores)
 {
@@ -672,7 +677,13 @@ int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int co
     const bool oriented = orientedPlan(rows, cols, resized, planRows, planCols);
     ensurePlan(planRows, planCols, 3, nFrames);
     syncNms();
-    if (oriented && resized) // (fetchBatch unscales: boxes in the upright full-size frame)
+    if (!isDefaultVideoFormat(m_videoFormat)) // (the default format takes the entries below: acf_hip_run_video would forward to them)
+    {
+        check(m_api->acf_hip_run_video(m_ctx, baseDev, nFrames, &desc, &m_videoFormat, (oriented || resized) ? rows : 0, (oriented || resized) ? cols : 0,
+                  oriented ? m_orient : 0, resized ? double(inputScale()) : 0.0),
+            "acf_hip_run_video");
+    }
+    else if (oriented && resized) // (fetchBatch unscales: boxes in the upright full-size frame)
     {
         check(m_api->acf_hip_run_yuv_oriented_resized(m_ctx, baseDev, nFrames, &desc, rows, cols, m_orient, double(inputScale())),
             "acf_hip_run_yuv_oriented_resized");
@@ -691,6 +702,21 @@ int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int co
     }
     fetchBatch(nFrames, resized, objects, scores);
     return 0;
+}
+
+acf_hip_yuv_desc HipDetector::videoLayout(int layout, const acf_hip_yuv_format& fmt, int rows, int cols, int rowStrideBytes, size_t* frameBytes)
+{
+    acf_hip_yuv_desc d;
+    int64_t n = 0;
+    if (hip::load().acf_hip_video_layout(layout, &fmt, rows, cols, rowStrideBytes, &d, &n))
+    {
+        throw Exception(ACF_HIP_E_INVALID, "videoLayout: a bad format, or what yuvLayout refuses (sizes and strides in samples of 1 or 2 bytes)");
+    }
+    if (frameBytes)
+    {
+        *frameBytes = size_t(n);
+    }
+    return d;
 }
 
 acf_hip_yuv_desc HipDetector::yuvLayout(int layout, int rows, int cols, int rowStrideBytes, size_t* frameBytes)
@@ -794,7 +820,13 @@ void HipDetector::streamOpenYuv(int rows, int cols, const acf_hip_yuv_desc& desc
     check(m_api->acf_hip_set_input_resize(m_ctx, 0, 0, 1.0), "acf_hip_set_input_resize");
     m_srcRows = rows;
     m_srcCols = cols;
-    if (oriented && resized) // (streamCollect maps the boxes back to the upright full-size frame)
+    if (!isDefaultVideoFormat(m_videoFormat))
+    {
+        check(m_api->acf_hip_stream_open_video(m_ctx, &desc, &m_videoFormat, int64_t(frameBytes), (oriented || resized) ? rows : 0, (oriented || resized) ? cols : 0,
+                  oriented ? m_orient : 0, resized ? double(inputScale()) : 0.0, maxDetectionsPerFrame, depth),
+            "acf_hip_stream_open_video");
+    }
+    else if (oriented && resized) // (streamCollect maps the boxes back to the upright full-size frame)
     {
         check(m_api->acf_hip_stream_open_yuv_oriented_resized(m_ctx, &desc, int64_t(frameBytes), rows, cols, m_orient, double(inputScale()), maxDetectionsPerFrame,
                   depth),

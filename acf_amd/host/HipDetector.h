@@ -275,6 +275,13 @@ public:
     // acf_hip_run_yuv_oriented_resized); the boxes are unscaled as always, so they are in the upright FULL-SIZE frame.
     void setInputOrientation(int orient) { m_orient = orient; }
     int getInputOrientation() const { return m_orient; }
+
+    // The sample width, matrix and range of the frames detectYuv and streamOpenYuv take (include/acf_hip.h, acf_hip_yuv_format: 8 bits
+    // or 9 .. 16-bit little-endian words, BT.601 / BT.709 / BT.2020, limited or full range); the default {8, 0, BT601, 0} is cvtColor's
+    // arithmetic.  Honoured together with setInputOrientation and setMinObjectWidth (acf_hip_run_video / acf_hip_stream_open_video);
+    // what the library refuses — a bad format, more than 8 bits with an orientation or a reduction — is thrown with its code.
+    void setVideoFormat(const acf_hip_yuv_format& fmt) { m_videoFormat = fmt; }
+    const acf_hip_yuv_format& getVideoFormat() const { return m_videoFormat; }
     static Rect unorientRect(const Rect& o, int orient, int srcRows, int srcCols); // acf_hip_unorient_rect
     int acfModify(const Modify& params); // acfModify.cpp:83-152
 
@@ -316,6 +323,8 @@ public:
         std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
     // the descriptor of a named layout (ACF_HIP_YUV_*) of rows x cols; *frameBytes = the distance to the next frame
     static acf_hip_yuv_desc yuvLayout(int layout, int rows, int cols, int rowStrideBytes = 0, size_t* frameBytes = nullptr);
+    // the same with the format's 1 or 2 bytes a sample (acf_hip_video_layout; P010 is ACF_HIP_YUV_NV12 with bits 10, shift 6)
+    static acf_hip_yuv_desc videoLayout(int layout, const acf_hip_yuv_format& fmt, int rows, int cols, int rowStrideBytes = 0, size_t* frameBytes = nullptr);
 
     // Streaming front end (the role of GPUDetectionPipeline::runFast's two-frame FIFO, GPUDetectionPipeline.cpp:357-437):
     // batches of packed 8-bit frames are copied to the device while the previous batch computes.
@@ -435,6 +444,7 @@ private:
     std::vector<float> m_upright; // scratch for operator()(interleaved)
     int m_streamCap = 0, m_streamPix = -1, m_streamStride = 0;
     int m_orient = 0; // setInputOrientation
+    acf_hip_yuv_format m_videoFormat{ 8, 0, ACF_HIP_YUV_MATRIX_BT601, 0 }; // setVideoFormat
     int m_minObjectWidth = -1, m_srcRows = 0, m_srcCols = 0; // frame size handed to the 8-bit entries (== the plan's without a resize)
     MatLoggerType m_logger;
     StreamLoggerType m_streamLogger;

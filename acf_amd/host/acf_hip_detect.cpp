@@ -6,6 +6,7 @@
 //   acf_hip_detect --model m.acfm --frames f.u8 --u8 rgb|bgr|rgba|bgra|gray|nv12|nv21 --rows H --cols W --count N [--stream B] [--min-width M] ...
 //                  packed 8-bit upright frames (nv12 / nv21: tight YUV 4:2:0 video frames); --stream B: batches of B frames through streamSubmit/streamCollect
 //   acf_hip_detect --model m.acfm --frames f.yuv --yuv i420|yv12|i422|i444|yuyv|uyvy|yvyu|nv12|nv21 --rows H --cols W --count N [--stream B] [--min-width M]
+//                  [--bits N --shift S --matrix bt601|bt709|bt2020 --range limited|full]
 //                  [--orient K]
 //                  tight YUV video frames of the named layout through detectYuv (one batch; the frames in page-locked memory, which the
 //                  device reads), or --stream B through streamOpenYuv / streamSubmit / streamCollect; --min-width M: reduced on the device
@@ -216,7 +217,14 @@ int main(int argc, char** argv)
                 { "yvyu", ACF_HIP_YUV_YVYU } };
             const int H = std::stoi(a.at("rows")), W = std::stoi(a.at("cols")), cnt = std::stoi(a.at("count"));
             size_t per = 0;
-            const acf_hip_yuv_desc desc = HipDetector::yuvLayout(kYuv.at(a["yuv"]), H, W, 0, &per);
+            // --bits N --shift S --matrix bt601|bt709|bt2020 --range limited|full: the frames' acf_hip_yuv_format (setVideoFormat)
+            static const std::map<std::string, int> kMatrix = { { "bt601", ACF_HIP_YUV_MATRIX_BT601 }, { "bt709", ACF_HIP_YUV_MATRIX_BT709 },
+                { "bt2020", ACF_HIP_YUV_MATRIX_BT2020 } };
+            static const std::map<std::string, int> kRange = { { "limited", 0 }, { "full", 1 } };
+            const acf_hip_yuv_format fmt{ a.count("bits") ? std::stoi(a["bits"]) : 8, a.count("shift") ? std::stoi(a["shift"]) : 0,
+                a.count("matrix") ? kMatrix.at(a["matrix"]) : ACF_HIP_YUV_MATRIX_BT601, a.count("range") ? kRange.at(a["range"]) : 0 };
+            det.setVideoFormat(fmt);
+            const acf_hip_yuv_desc desc = HipDetector::videoLayout(kYuv.at(a["yuv"]), fmt, H, W, 0, &per);
             const int orient = a.count("orient") ? std::stoi(a["orient"]) : 0;
             std::string note; // what the boxes' coordinates are, when they are not the stored frame's
             if (orient)

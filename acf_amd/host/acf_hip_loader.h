@@ -69,6 +69,13 @@ struct Api
     ACF_HIP_FN(acf_hip_run_yuv_oriented_resized)
     ACF_HIP_FN(acf_hip_stream_open_yuv_oriented_resized)
     ACF_HIP_FN(acf_hip_oriented_resized_dims)
+    ACF_HIP_FN(acf_hip_pyramid_video)
+    ACF_HIP_FN(acf_hip_run_video)
+    ACF_HIP_FN(acf_hip_stream_open_video)
+    ACF_HIP_FN(acf_hip_video_to_rgb)
+    ACF_HIP_FN(acf_hip_video_extent)
+    ACF_HIP_FN(acf_hip_video_layout)
+    ACF_HIP_FN(acf_hip_yuv_coeffs)
     ACF_HIP_FN(acf_hip_unorient_rect)
     ACF_HIP_FN(acf_hip_resize_dims)
     ACF_HIP_FN(acf_hip_set_input_resize)

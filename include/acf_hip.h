@@ -679,6 +679,86 @@ ACF_HIP_API int acf_hip_stream_open_yuv_oriented_resized(acf_hip_ctx* ctx, const
     int orient, double scale, int cap, int depth);
 ACF_HIP_API int acf_hip_oriented_resized_dims(int src_rows, int src_cols, int orient, double scale, int* h, int* w);
 
+/* ---- video formats: 9 .. 16-bit samples, BT.709 / BT.2020, full range ---
+ * The YUV entries above convert with one arithmetic: 8-bit samples, BT.601, limited range.  The video entries take the same
+ * descriptor (acf_hip_yuv_desc keeps its meaning: all offsets and strides in BYTES) together with an acf_hip_yuv_format:
+ *   bits        8: one byte a sample.  9 .. 16: one little-endian 16-bit word a sample, sample = (word >> shift) & ((1 << bits) - 1);
+ *               a planar 16-bit plane has stride_px 2, P010's chroma stride_px 4 with V two bytes behind U
+ *   shift       P010 = 6, P012 = 4, P016 / yuv420p10le = 0; must be 0 for 8 bits; shift + bits <= 16
+ *   matrix      ACF_HIP_YUV_MATRIX_BT601 / _BT709 / _BT2020 (Rec. ITU-T H.273 MatrixCoefficients 5 / 6, 1, 9)
+ *   full_range  0 limited ("video"), 1 full ("pc" / JPEG)
+ * A null format is the default {8, 0, BT601, 0}.
+ * Arithmetic, in exact integers (N = bits; >> is floor; an implementation may use any width that gives the same integers):
+ *     yoff = full_range ? 0 : 16 << (N - 8);   cmid = 1 << (N - 1);   out_max = full_range ? (1 << N) - 1 : 255 << (N - 8)
+ *     y = max(0, Y - yoff) * CY
+ *     R = clamp((y + (1 << 19) + CVR * (V - cmid)) >> 20, 0, out_max)
+ *     G = clamp((y + (1 << 19) + CVG * (V - cmid) + CUG * (U - cmid)) >> 20, 0, out_max)
+ *     B = clamp((y + (1 << 19) + CUB * (U - cmid)) >> 20, 0, out_max)
+ *     plane value = float(R) * float(1.0 / out_max)          (8 bits: float(1 / 255.0), as every 8-bit entry)
+ * N-bit limited-range codes are read as the 8-bit codes times 2^(N - 8), as H.273 defines them, so the constants do not depend on N.
+ * Full range follows H.273 / JFIF: luma gain 1, the chroma excursion half the RGB range.  The constants are round(2^20 * q), half
+ * away from zero, q the exact rational from Kr / Kb (0.299 / 0.114, 0.2126 / 0.0722, 0.2627 / 0.0593); limited range: luma gain
+ * 255 / 219, chroma gain 255 / 224.  BT.601 limited is the exception: it KEEPS cvtColor's constants (from coefficients rounded to three
+ * decimals), so that the default format is the arithmetic of the entries above.
+ *     matrix, range     CY       CVR      CVG      CUG      CUB
+ *     BT601 limited     1220542  1673527  -852492  -409993  2116026
+ *     BT601 full        1048576  1470104  -748826  -360853  1858077
+ *     BT709 limited     1220945  1879825  -558796  -223607  2215014
+ *     BT709 full        1048576  1651297  -490864  -196424  1945738
+ *     BT2020 limited    1220945  1760217  -682019  -196426  2245811
+ *     BT2020 full       1048576  1546230  -599107  -172546  1972791
+ * The chroma sample of pixel (r, c) is the one at (r >> sub_y, c >> sub_x) in SOURCE coordinates, no interpolation, as above.
+ * Definition of the entries, composed from what exists, bit for bit (every plane, level, hit, score bit and box, option "arith" = 1
+ * included):
+ *   8 bits, any matrix or range   acf_hip_run_u8(ACF_HIP_PIX_RGB) on the R, G, B bytes above; with orient / scale the bytes of the
+ *                                 stored frame go through the oriented, resized or oriented-then-resized definitions above, unchanged
+ *   more than 8 bits              acf_hip_run_image on a tight packed float32 RGB image holding float(R) * float(1.0 / out_max)
+ * OpenCV has no counterpart beyond BT.601 8-bit: PARITY UNPINNED; the matrices are H.273's.
+ *  acf_hip_pyramid_video / run_video   scale 0: no resize, the plan is for acf_hip_oriented_dims(src_rows, src_cols, orient); otherwise
+ *                            for acf_hip_oriented_resized_dims(...).  orient 0 with scale 0 is the plain entry (src_rows = src_cols = 0:
+ *                            the plan's size).  With the default format the call FORWARDS to the existing entry of its family
+ *                            (acf_hip_run_yuv, _oriented, _resized, _oriented_resized): the same kernels under the same profile names.
+ *                            Other 8-bit formats run the same kernels with the constants as an argument (the profile names stay; an
+ *                            NV12 / NV21-shaped descriptor still runs k_ingest_yuv420).  More than 8 bits: k_ingest_yuv16, one kernel with
+ *                            three load forms chosen from the descriptor and base_dev's alignment alone, all giving the same bits:
+ *                            k_ingest_yuv16_planar (every stride_px 2; every plane's first byte, stride_row and stride_n multiples of 4),
+ *                            k_ingest_yuv16_pairs (P010-like: luma as planar; U and V interleaved 16-bit pairs, 4-aligned) and
+ *                            k_ingest_yuv16_generic (16-bit loads, any even offsets and strides; Y210 runs here).  Only addressed
+ *                            words are read.
+ *  acf_hip_stream_open_video the streaming front end with acf_hip_stream_open_yuv's rules (extents in BYTES, acf_hip_video_extent)
+ *  acf_hip_video_to_rgb      the conversion alone, device buffers, no model, no plan: dst_dev is tight [n_frames][rows][cols][3] of
+ *                            uint8 (8 bits) or uint16 (more) holding R, G, B in [0, out_max]
+ *  acf_hip_video_extent      host arithmetic: as acf_hip_yuv_extent, with last[p] the last BYTE read (the high byte of the last word)
+ *  acf_hip_video_layout      host arithmetic: the nine ACF_HIP_YUV_* names with 1 or 2 bytes a sample (acf_hip_yuv_layout's rules with
+ *                            every size in bytes doubled for bits > 8; row_stride_bytes 0 = tight).  P010 is (ACF_HIP_YUV_NV12, bits
+ *                            10, shift 6), yuv420p10le (ACF_HIP_YUV_I420, bits 10), Y210 (ACF_HIP_YUV_YUYV, bits 10, shift 6)
+ *  acf_hip_yuv_coeffs        host only: {yoff, cmid, out_max, CY, CVR, CVG, CUG, CUB}
+ * ACF_HIP_E_INVALID: what the family's existing entry refuses; bits outside 8 .. 16; shift != 0 with bits 8; shift + bits > 16; an
+ * unknown matrix; full_range outside {0, 1}; with bits > 8 an odd base, offset or stride.  ACF_HIP_E_UNSUPPORTED: option "streams"
+ * > 1; bits > 8 together with orient != 0 or scale != 0 — cv::resize's 16-bit arithmetic is not restated, and a 16-bit oriented kernel
+ * is deliberately left for later.  Not covered: chroma siting and interpolation, transfer functions (PQ / HLG), tone mapping,
+ * big-endian words. */
+enum { ACF_HIP_YUV_MATRIX_BT601 = 0, ACF_HIP_YUV_MATRIX_BT709 = 1, ACF_HIP_YUV_MATRIX_BT2020 = 2 };
+typedef struct acf_hip_yuv_format {
+    int32_t bits;       /* 8: one byte a sample.  9..16: one little-endian 16-bit word a sample */
+    int32_t shift;      /* bits > 8: sample = (word >> shift) & ((1 << bits) - 1).  P010 = 6, P012 = 4, P016 / yuv420p10le = 0 */
+    int32_t matrix;     /* ACF_HIP_YUV_MATRIX_* */
+    int32_t full_range; /* 0 limited ("video"), 1 full ("pc" / JPEG) */
+} acf_hip_yuv_format;   /* 16 bytes.  {8, 0, BT601, 0} is the arithmetic of the YUV entries above */
+ACF_HIP_API int acf_hip_pyramid_video(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt,
+    int src_rows, int src_cols, int orient, double scale);
+ACF_HIP_API int acf_hip_run_video(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt,
+    int src_rows, int src_cols, int orient, double scale);
+ACF_HIP_API int acf_hip_stream_open_video(acf_hip_ctx* ctx, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, int64_t frame_bytes, int src_rows,
+    int src_cols, int orient, double scale, int cap, int depth);
+ACF_HIP_API int acf_hip_video_to_rgb(acf_hip_ctx* ctx, const uint8_t* base_dev, int n_frames, int rows, int cols, const acf_hip_yuv_desc* desc,
+    const acf_hip_yuv_format* fmt, void* dst_dev);
+ACF_HIP_API int acf_hip_video_extent(const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, int h, int w, int n_frames, int64_t first[3],
+    int64_t last[3]);
+ACF_HIP_API int acf_hip_video_layout(int layout, const acf_hip_yuv_format* fmt, int h, int w, int row_stride_bytes, acf_hip_yuv_desc* out,
+    int64_t* frame_bytes);
+ACF_HIP_API int acf_hip_yuv_coeffs(const acf_hip_yuv_format* fmt, int64_t out[8]);
+
 /* ---- streaming front end ---------------------------------------------
  * The overlap of transfer and compute that GPUDetectionPipeline::runFast gets
  * from its two-frame texture FIFO (GPUDetectionPipeline.cpp:357-437), expressed
