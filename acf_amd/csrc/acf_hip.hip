@@ -2306,14 +2306,20 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
     return streamSlots(c, g.frameStride, cap, depth);
 }
 
-// acf_hip_stream_open_yuv, acf_hip_stream_open_yuv_resized (resized: frames of srcRows x srcCols, reduced by scale) and
-// acf_hip_stream_open_yuv_oriented (orient: frames of srcRows x srcCols turned to the plan's size; the entry has checked them);
-// acf_hip_stream_open_yuv_oriented_resized: both (turned, then reduced)
-static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc* desc, int64_t frameBytes, bool resized, int srcRows, int srcCols, double scale,
-    int cap, int depth, int orient = 0, const acf_hip_yuv_format& fmt = kDefaultVideoFormat)
+// The general open for frames described by three planes: every exported stream_open_yuv* / _video call is one call of it that fills in
+// what it states (st), as the pyramid entries do (input_run.hip.h).  The call's own arguments first (sourceArgsBad) and, for unreduced
+// frames, their size against the plan; then the context and the description; a reduced source's tables where the plan's planes are known.
+static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc* desc, int64_t frameBytes, Stated st, int srcRows, int srcCols, int orient, double scale,
+    const acf_hip_yuv_format* fmt, int cap, int depth)
 {
     const std::string w = std::string(who) + ": ";
     if (int rc = needPlan(c, who)) return rc;
+    FrameSource src{ SRC_YUV, nullptr, who, 0, 0, {}, {}, false, srcRows, srcCols, scale, orient, fmt ? *fmt : kDefaultVideoFormat };
+    if (int rc = sourceArgsBad(c, who, st, src, true)) return rc;
+    if (!src.resized)
+    {
+        if (int rc = sourceAgainstPlan(c, src)) return rc;
+    }
     if (!c->kids.empty())
     {
         return fail(c, ACF_HIP_E_UNSUPPORTED, w + "not available with option \"streams\" > 1");
@@ -2322,7 +2328,12 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     {
         return fail(c, ACF_HIP_E_INVALID, w + "depth must be 2..8, cap > 0");
     }
-    if (const char* bad = yuvDescBad(desc))
+    const char* bad = yuvDescBad(desc);
+    if (!bad && src.fmt.bits > 8)
+    {
+        bad = video16DescBad(nullptr, *desc);
+    }
+    if (bad)
     {
         return fail(c, ACF_HIP_E_INVALID, w + bad);
     }
@@ -2330,18 +2341,17 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     {
         return fail(c, ACF_HIP_E_INVALID, w + "the plan's input planes (d) must be 3, and not with acf_hip_set_input_resize");
     }
-    if (resized)
+    if (src.resized)
     {
-        // (resized and oriented: the tables and the plan are for the upright size)
         HIPCHK(c, hipSetDevice(c->device));
-        if (int rc = resizedTables(c, who, (orient & 1) ? srcCols : srcRows, (orient & 1) ? srcRows : srcCols, scale)) return rc;
+        if (int rc = sourceAgainstPlan(c, src)) return rc;
     }
-    const bool ownSize = resized || orient; // the frames are srcRows x srcCols, not the plan's size
+    const bool ownSize = srcRows || srcCols; // the frames are srcRows x srcCols, not the plan's size
     int64_t first[3], last[3];
     yuvExtent(*desc, ownSize ? srcRows : c->plan.H, ownSize ? srcCols : c->plan.W, 1, first, last);
     for (int i = 0; i < 3; i++)
     {
-        if (first[i] < 0 || last[i] + (fmt.bits > 8 ? 1 : 0) >= frameBytes) // (16-bit words: the last byte is the word's high byte)
+        if (first[i] < 0 || last[i] + (src.fmt.bits > 8 ? 1 : 0) >= frameBytes) // (16-bit words: the last byte is the word's high byte)
         {
             return fail(c, ACF_HIP_E_INVALID, w + "every plane of a frame must lie in [0, frame_bytes)");
         }
@@ -2350,96 +2360,38 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     {
         return fail(c, ACF_HIP_E_INVALID, w + "stride_n of every plane must be frame_bytes");
     }
-    c->stSrc = FrameSource{ SRC_YUV, nullptr,
-        resized ? (orient ? "pyramid_yuv_oriented_resized" : "pyramid_yuv_resized") : (orient ? "pyramid_yuv_oriented" : "pyramid_yuv"), 0, 0, {}, *desc, resized, srcRows,
-        srcCols, scale, orient, fmt };
+    // (a batch runs under the name of the pyramid entry of its geometry)
+    src.who = src.resized ? (orient ? "pyramid_yuv_oriented_resized" : "pyramid_yuv_resized") : (orient ? "pyramid_yuv_oriented" : "pyramid_yuv");
+    src.yuv = *desc;
+    c->stSrc = src;
     return streamSlots(c, frameBytes, cap, depth);
 }
 
 int acf_hip_stream_open_yuv(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int cap, int depth)
 {
-    return streamOpenYuv(c, "stream_open_yuv", desc, frameBytes, false, 0, 0, 1.0, cap, depth);
+    return streamOpenYuv(c, "stream_open_yuv", desc, frameBytes, ST_PLAN, 0, 0, 0, 0, nullptr, cap, depth);
 }
 
 int acf_hip_stream_open_yuv_resized(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, double scale, int cap, int depth)
 {
-    return streamOpenYuv(c, "stream_open_yuv_resized", desc, frameBytes, true, srcRows, srcCols, scale, cap, depth);
+    return streamOpenYuv(c, "stream_open_yuv_resized", desc, frameBytes, ST_REDUCED, srcRows, srcCols, 0, scale, nullptr, cap, depth);
+}
+
+int acf_hip_stream_open_yuv_oriented(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, int orient, int cap, int depth)
+{
+    return streamOpenYuv(c, "stream_open_yuv_oriented", desc, frameBytes, ST_TURNED, srcRows, srcCols, orient, 0, nullptr, cap, depth);
 }
 
 int acf_hip_stream_open_yuv_oriented_resized(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, int orient, double scale,
     int cap, int depth)
 {
-    if (int rc = needPlan(c, "stream_open_yuv_oriented_resized")) return rc;
-    if (orient < 0 || orient > 7 || srcRows < 1 || srcCols < 1)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "stream_open_yuv_oriented_resized: orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
-    }
-    if (orient == 0)
-    {
-        return acf_hip_stream_open_yuv_resized(c, desc, frameBytes, srcRows, srcCols, scale, cap, depth);
-    }
-    return streamOpenYuv(c, "stream_open_yuv_oriented_resized", desc, frameBytes, true, srcRows, srcCols, scale, cap, depth, orient);
+    return streamOpenYuv(c, "stream_open_yuv_oriented_resized", desc, frameBytes, ST_TURNED_REDUCED, srcRows, srcCols, orient, scale, nullptr, cap, depth);
 }
 
-int acf_hip_stream_open_yuv_oriented(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int srcRows, int srcCols, int orient, int cap, int depth)
-{
-    if (int rc = needPlan(c, "stream_open_yuv_oriented")) return rc;
-    if (int rc = orientedBad(c, "stream_open_yuv_oriented: ", srcRows, srcCols, orient)) return rc; // (code 0 too: the frame size is the plan's)
-    return streamOpenYuv(c, "stream_open_yuv_oriented", desc, frameBytes, false, srcRows, srcCols, 1.0, cap, depth, orient);
-}
-
-// The video entries' stream: the default format is the existing open call of the family; any other format is the same stream with
-// the format in its FrameSource
-int acf_hip_stream_open_video(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmtIn, int64_t frameBytes, int srcRows, int srcCols, int orient,
+int acf_hip_stream_open_video(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, int64_t frameBytes, int srcRows, int srcCols, int orient,
     double scale, int cap, int depth)
 {
-    if (int rc = needPlan(c, "stream_open_video")) return rc;
-    const acf_hip_yuv_format fmt = fmtIn ? *fmtIn : kDefaultVideoFormat;
-    if (const char* bad = videoFormatBad(fmt))
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string("stream_open_video: ") + bad);
-    }
-    if (!(scale >= 0) || !std::isfinite(scale))
-    {
-        return fail(c, ACF_HIP_E_INVALID, "stream_open_video: scale must be 0 (no resize) or a positive finite number");
-    }
-    const bool plain = orient == 0 && scale == 0 && srcRows == 0 && srcCols == 0;
-    if (videoFormatIsDefault(fmt))
-    {
-        if (plain)
-        {
-            return acf_hip_stream_open_yuv(c, desc, frameBytes, cap, depth);
-        }
-        return scale == 0 ? acf_hip_stream_open_yuv_oriented(c, desc, frameBytes, srcRows, srcCols, orient, cap, depth)
-                          : acf_hip_stream_open_yuv_oriented_resized(c, desc, frameBytes, srcRows, srcCols, orient, scale, cap, depth);
-    }
-    if (!c->kids.empty())
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, "stream_open_video: not available with option \"streams\" > 1");
-    }
-    if (orient < 0 || orient > 7 || (!plain && (srcRows < 1 || srcCols < 1)))
-    {
-        return fail(c, ACF_HIP_E_INVALID, "stream_open_video: orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
-    }
-    if (fmt.bits > 8)
-    {
-        if (orient != 0 || scale != 0)
-        {
-            return fail(c, ACF_HIP_E_UNSUPPORTED, "stream_open_video: more than 8 bits a sample: upright and unreduced frames only (orient 0, scale 0)");
-        }
-        if (desc && !yuvDescBad(desc))
-        {
-            if (const char* bad = video16DescBad(nullptr, *desc))
-            {
-                return fail(c, ACF_HIP_E_INVALID, std::string("stream_open_video: ") + bad);
-            }
-        }
-    }
-    if (scale == 0 && !plain)
-    {
-        if (int rc = orientedBad(c, "stream_open_video: ", srcRows, srcCols, orient)) return rc;
-    }
-    return streamOpenYuv(c, "stream_open_video", desc, frameBytes, scale != 0, srcRows, srcCols, scale == 0 ? 1.0 : scale, cap, depth, orient, fmt);
+    return streamOpenYuv(c, "stream_open_video", desc, frameBytes, ST_VIDEO, srcRows, srcCols, orient, scale, fmt, cap, depth);
 }
 
 int acf_hip_stream_submit(acf_hip_ctx* c, const uint8_t* frames_host, int nF, int* ticket)

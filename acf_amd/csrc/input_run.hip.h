@@ -1,19 +1,22 @@
 // input_run.hip.h — part of acf_hip.hip (included there and nowhere else): where a call's frames come from.  Every entry that takes frames
-// describes them as ONE FrameSource (acf_hip.hip, beside the context, whose stream keeps the one it was opened with); planIngest checks
-// the source against the plan and decides the call's ingest once (IngestPlan: the preludes, the kernel, its arguments, its names), and
-// PyramidRun::ingest (pyramid_run.hip.h) launches that plan straight-line.  A new kind of input is one more SourceKind.
+// describes them as ONE FrameSource (acf_hip.hip, beside the context, whose stream keeps the one it was opened with).  Every exported
+// image / YUV entry is a one-line call of the general entry of its kind (imageEntry, yuvEntry; the streams: streamOpenYuv in acf_hip.hip)
+// that fills in what it states; no exported entry calls another.  The checks stand once, in two layers: sourceArgsBad (what the call
+// states, whatever the context) and sourceAgainstPlan (what the plan must be for).  planIngest decides the call's ingest once
+// (IngestPlan: the preludes, the kernel, its arguments, its names) from the FrameSource's fields alone — so orient 0, scale 0 and the
+// default format are the plain kernels under the plain names through whichever entry they came — and PyramidRun::ingest
+// (pyramid_run.hip.h) launches that plan straight-line.  A new kind of input is one more SourceKind.
 //
 //   u8Geom, imageDescBad, yuvDescBad, yuvExtent      what a layout or a description is, by itself
 //   videoFormatBad, video16DescBad, yuvCoef          what an acf_hip_yuv_format is, by itself: its checks and the conversion's constants
-//   the kernel tables and form choosers              ingestKernel .. resizedKernel, yuv16Kernel, imageLoadForm, yuvLoadForm, yuv16LoadForm, yuvIsSemiPlanar; the oriented
-//                                                    entries: imageOrientedKernel, yuvOrientedKernel, orientSrc, orientedBad, yuvIsAlignedPairs;
-//                                                    the oriented resized entries: orientedResizedKernel, orientedResizedBand, planOrientedResized
+//   the kernel tables and form choosers              ingestKernel .. orientedResizedKernel, yuv16Kernel, imageLoadForm, yuvLoadForm, yuv16LoadForm, yuvIsSemiPlanar,
+//                                                    yuvIsAlignedPairs, orientSrc, orientedResizedBand
 //   launchYuvToRgb, launchResizeU8, launchColour     the preludes and the colour conversion (ops.hip.h and crops_run.hip.h call them too)
-//   installResizeTables, resizedTables               the tap tables of acf_hip_set_input_resize (c->rz) and of the resized entries (c->rzIn)
-//   planIngest                                       FrameSource -> IngestPlan, or the refusal
-//   the entries that are only about input            acf_hip_pyramid_u8 / _image / _yuv / *_resized / *_oriented / *_oriented_resized and their run_ twins, the extents
-//                                                    and layouts, acf_hip_set_yuv_layout, acf_hip_set_input_resize, acf_hip_yuv_to_rgb8; the video
-//                                                    entries (acf_hip_pyramid_video / run_video / video_to_rgb / video_extent / video_layout / yuv_coeffs)
+//   installResizeTables, resizedTables               the tap tables of acf_hip_set_input_resize (c->rz) and of the reduced sources (c->rzIn)
+//   sourceArgsBad, sourceAgainstPlan                 the two layers of the checks
+//   planIngest                                       FrameSource -> IngestPlan, or the refusal: planU8, planImage, planYuv; planReduced, planOrientedResized
+//   imageEntry, yuvEntry and the exported entries    acf_hip_pyramid_u8 / _image* / _yuv* / _video and their run_ twins, the extents and layouts,
+//                                                    acf_hip_set_yuv_layout, acf_hip_set_input_resize, acf_hip_yuv_to_rgb8 / video_to_rgb (videoToRgb)
 #pragma once
 
 namespace
@@ -636,6 +639,12 @@ static int installResizeTables(acf_hip_ctx* c, const char* who, acf_hip_ctx::Inp
     return ACF_HIP_OK;
 }
 
+// every entry but the 8-bit one, while acf_hip_set_input_resize is switched on
+static int inputResizeRefused(acf_hip_ctx* c, const char* who, const char* why)
+{
+    return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": not with acf_hip_set_input_resize (" + why + ")");
+}
+
 // What the resized entries refuse about (src_rows, src_cols, scale) and the plan, then their tap tables on the device: those of the
 // context's key (rows, cols, scale) as they are, else new ones
 static int resizedTables(acf_hip_ctx* c, const char* who, int srcRows, int srcCols, double scale)
@@ -646,7 +655,7 @@ static int resizedTables(acf_hip_ctx* c, const char* who, int srcRows, int srcCo
     }
     if (c->rz.on)
     {
-        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": not with acf_hip_set_input_resize (the entry resizes by itself)");
+        return inputResizeRefused(c, who, "the entry resizes by itself");
     }
     const acf_hip_ctx::InputResize& cur = c->rzIn;
     if (cur.on && cur.rows == srcRows && cur.cols == srcCols && cur.scale == scale)
@@ -670,17 +679,82 @@ static OrientSrc orientSrc(int code, int srcRows, int srcCols)
     return o;
 }
 
-// What the oriented entries refuse about (src_rows, src_cols, orient) and the plan
-static int orientedBad(acf_hip_ctx* c, const std::string& who, int srcRows, int srcCols, int orient)
+// a stored frame size and an orientation code, by themselves (acf_hip_oriented_dims, acf_hip_unorient_rect and the entries that state them)
+static bool orientedArgsBad(int srcRows, int srcCols, int orient)
 {
-    if (orient < 0 || orient > 7 || srcRows < 1 || srcCols < 1)
+    return orient < 0 || orient > 7 || srcRows < 1 || srcCols < 1;
+}
+
+// Which of (srcRows, srcCols, orient, scale) a call states beside its description: what its exported entry takes
+enum Stated
+{
+    ST_PLAN,           // none: upright frames of the plan's size
+    ST_REDUCED,        // the size and the scale; both are held together with the tap tables (resizedTables), after the description and the planes
+    ST_TURNED,         // the size and the orientation
+    ST_TURNED_REDUCED, // all four; the scale is held with the tap tables
+    ST_VIDEO           // all four and a format, 0 meaning "none": scale 0 = no resize, everything 0 = ST_PLAN
+};
+
+// What is wrong with what a call states about its frames, whatever the context is — the first layer of the checks: the refusal, or OK
+// with src.resized decided.  src holds the call's arguments (who, fmt, srcRows, srcCols, orient, scale); `who` names the entry where
+// the format, the scale and the sample width are refused (run_video says its own name there, pyramid_video's everywhere else).
+// open: the call is a stream's open, which has always kept an order of its own in two places (below), so that a call that is wrong
+// in two ways keeps its error code.
+static int sourceArgsBad(acf_hip_ctx* c, const char* who, Stated st, FrameSource& src, bool open = false)
+{
+    const std::string w = std::string(who) + ": ";
+    bool sized = st == ST_TURNED || st == ST_TURNED_REDUCED, wide = false;
+    src.resized = st == ST_REDUCED || st == ST_TURNED_REDUCED;
+    if (st == ST_VIDEO)
     {
-        return fail(c, ACF_HIP_E_INVALID, who + "orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
+        if (const char* bad = videoFormatBad(src.fmt))
+        {
+            return fail(c, ACF_HIP_E_INVALID, w + bad);
+        }
+        if (!(src.scale >= 0) || !std::isfinite(src.scale))
+        {
+            return fail(c, ACF_HIP_E_INVALID, w + "scale must be 0 (no resize) or a positive finite number");
+        }
+        // (the one check of the context in here: the open of another format refuses sub-batch streams before the geometry, every
+        // other open after it and after the size against the plan — streamOpenYuv)
+        if (open && !videoFormatIsDefault(src.fmt) && !c->kids.empty())
+        {
+            return fail(c, ACF_HIP_E_UNSUPPORTED, w + "not available with option \"streams\" > 1");
+        }
+        sized = src.orient != 0 || src.scale != 0 || src.srcRows != 0 || src.srcCols != 0;
+        wide = src.fmt.bits > 8 && (src.orient != 0 || src.scale != 0);
+        src.resized = src.scale != 0;
     }
-    const bool swap = orient & 1;
-    if (c->plan.H != (swap ? srcCols : srcRows) || c->plan.W != (swap ? srcRows : srcCols))
+    const bool turnedBad = sized && orientedArgsBad(src.srcRows, src.srcCols, src.orient);
+    // (the pyramid entries refuse the sample width before the orient range and the size, a stream's open after them)
+    if (wide && !(open && turnedBad))
     {
-        return fail(c, ACF_HIP_E_INVALID, who + "the plan must be for the upright size (acf_hip_oriented_dims of the frame size and orientation)");
+        return fail(c, ACF_HIP_E_UNSUPPORTED, w + "more than 8 bits a sample: upright and unreduced frames only (orient 0, scale 0)");
+    }
+    if (turnedBad)
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(src.who) + ": orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
+    }
+    return ACF_HIP_OK;
+}
+
+// What the plan must be for — the second layer, for a source that passed the first: the upright size of an unreduced source is the
+// plan's (a source that states no size has the plan's); a reduced source needs the tap tables of its upright size, which are built
+// against the plan (resizedTables).  The ONE place that holds a frame size against the plan (planIngest and streamOpenYuv call it).
+static int sourceAgainstPlan(acf_hip_ctx* c, const FrameSource& src)
+{
+    int rows = src.srcRows, cols = src.srcCols; // (a turned frame: orient first, then resize)
+    if (src.orient & 1)
+    {
+        std::swap(rows, cols);
+    }
+    if (src.resized)
+    {
+        return resizedTables(c, src.who, rows, cols, src.scale);
+    }
+    if ((rows || cols) && (c->plan.H != rows || c->plan.W != cols))
+    {
+        return fail(c, ACF_HIP_E_INVALID, std::string(src.who) + ": the plan must be for the upright size (acf_hip_oriented_dims of the frame size and orientation)");
     }
     return ACF_HIP_OK;
 }
@@ -773,26 +847,10 @@ struct IngestPlan
     void set(Yuv16Kernel k, const Yuv16Src& s) { kernel = reinterpret_cast<const void*>(k); second.yuv16 = s; }
 };
 
-// The upright size of a source that is both oriented and resized — what its tap tables and its plan are for — or the refusal
-static int orientedResizedUpright(acf_hip_ctx* c, const std::string& who, const FrameSource& src, int& rows, int& cols)
-{
-    rows = src.srcRows;
-    cols = src.srcCols;
-    if (src.orient < 0 || src.orient > 7)
-    {
-        return fail(c, ACF_HIP_E_INVALID, who + "orient must be 0 .. 7 (ACF_HIP_ORIENT_*)");
-    }
-    if (src.orient & 1)
-    {
-        std::swap(rows, cols);
-    }
-    return ACF_HIP_OK;
-}
-
 // A source that is both resized and oriented (r.r.im or r.r.yuv filled in; c->rzIn holds the tables of the upright size): the form of
 // k_ingest_oriented_resized, by what was measured (profiles/oriented_resized_entry.md).  Staged for quarter turns where the footprint fits
 // (orientedResizedBand): there the generic form's lanes each read another stored row (3.2 x / 5.2 x slower at scale 1 / 2 and 80 / 150).
-// Generic for rot 0 / 2 — its lanes already run along the stored rows, forwards or backwards, and the stage did not beat it (1.03 against
+// Generic for rot 0 / 2 — its lanes already run along the stored rows, in either direction, and the stage did not beat it (1.03 against
 // 0.74 ms at 1 / 2, 1.74 against 1.70 ms at 80 / 150) —, for footprints that do not fit, and when forced.
 static void planOrientedResized(acf_hip_ctx* c, int kind, int mode, bool vec, OrientedResizedSrc s, const FrameSource& src, IngestPlan& ip)
 {
@@ -813,168 +871,166 @@ static void planOrientedResized(acf_hip_ctx* c, int kind, int mode, bool vec, Or
     ip.launchName = "k_ingest_oriented_resized";
 }
 
-// The ingest of one call: the source held against the plan and the context's settings (what is refused, in the order the entries
-// have always checked), then the kernel form, its arguments and its names.  The ONE place that decides them.
-static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
+// The reduced sources of both kinds (r.im or r.yuv filled in; kind: RS_*): the source against the plan, which leaves the tables of
+// the upright size in c->rzIn, then the apps' Resizer on the addressed bytes in the ingest kernel itself — k_ingest_resized, or for a
+// turned frame k_ingest_oriented_resized (vec: its wide load form holds)
+static int planReduced(acf_hip_ctx* c, const FrameSource& src, int kind, int mode, bool vec, ResizedSrc r, IngestPlan& ip)
+{
+    if (int rc = sourceAgainstPlan(c, src))
+    {
+        return rc;
+    }
+    if (src.orient)
+    {
+        OrientedResizedSrc o{};
+        o.r = r;
+        planOrientedResized(c, kind, mode, vec, o, src, ip);
+        return ACF_HIP_OK;
+    }
+    r.t = resizeTaps(c->rzIn);
+    ip.set(resizedKernel(kind, mode), r);
+    ip.profName = kind == RS_IMAGE ? "k_ingest_resized_image" : "k_ingest_resized_yuv";
+    ip.launchName = "k_ingest_resized";
+    return ACF_HIP_OK;
+}
+
+// 8-bit ingest (ACF.cpp:114-119,137; MatP.cpp:51-73), fused with the colour conversion when there is one
+static int planU8(acf_hip_ctx* c, const FrameSource& src, int mode, IngestPlan& ip)
 {
     const int H = c->plan.H, W = c->plan.W, d_in = c->plan.d_in;
     const std::string who = std::string(src.who) + ": ";
-    ip = IngestPlan{};
-    // to the converted colour planes where the model converts (every colour space but hsv), else to planar planes in d_stage (hsv:
-    // k_rgb2hsv follows like on a float frame; orig / isLuv: the pyramid reads them as they are)
-    ip.convert = c->d_color && c->p.colorSpace != ACF_HIP_CS_HSV;
-    const int mode = ingestMode(c, ip.convert);
-    ip.nOut = (ip.convert && mode == IG_PLANAR) ? 3 : d_in; // ORIG / RGB with a 1-plane input: replicate (chnsPyramid.cpp:242-243)
-    if (src.kind == SRC_U8)
+    if (d_in == 5)
     {
-        // 8-bit ingest (ACF.cpp:114-119,137; MatP.cpp:51-73), fused with the colour conversion when there is one
-        if (d_in == 5)
-        {
-            return fail(c, ACF_HIP_E_INVALID, who + "a plan for five input planes (image + M, O) takes float frames");
-        }
-        const bool rz = c->rz.on, yuv = pixIsYuv(src.pix), fused = yuv && !rz && !fallbackForced(FB_YUV_UNFUSED);
-        int rows = rz ? c->rz.rows : H, cols = rz ? c->rz.cols : W; // the caller's frames
-        U8Geom& g = ip.g;
-        if (const char* bad = u8Geom(src.pix, rows, cols, src.rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
-        {
-            return fail(c, ACF_HIP_E_INVALID, std::string(src.who) + (rz && !yuv ? " (the unreduced frame): " : ": ") + bad);
-        }
-        if (!u8PlanesOk(g, d_in))
-        {
-            return fail(c, ACF_HIP_E_INVALID, who + (yuv && !fused ? "the plan's input planes (d) must be 3 for NV12 / NV21"
-                                                                  : "the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY"));
-        }
-        ip.in = static_cast<const uint8_t*>(src.base);
-        // a prelude leaves tight frames of the same pixel layout
-        const auto tight = [&](const uint8_t* at) {
-            ip.in = at;
-            g.stride = cols * g.cpp;
-            g.frameStride = int64_t(g.stride) * rows;
-        };
-        if (yuv && !fused)
-        {
-            const size_t need = size_t(c->maxBatch) * rows * cols * 3;
-            if (c->yuvRgbBytes < need)
-            {
-                HIPCHK(c, hipStreamSynchronize(c->stream)); // (a batch in flight may still read the smaller buffer)
-                devRelease(c, c->d_yuvRgb);
-                c->yuvRgbBytes = 0;
-                if (int rc = devAlloc(c, &c->d_yuvRgb, need))
-                {
-                    return rc;
-                }
-                c->yuvRgbBytes = need;
-            }
-            ip.toRgb = true;
-            ip.toRgbSrc = yuvSrc(ip.in, src.pix, rows, cols, g);
-            g = U8Geom{ 3, 0, 0, 1, 2, false, 0, 0 };
-            tight(c->d_yuvRgb);
-        }
-        if (rz)
-        {
-            ip.resize = true;
-            ip.resizeSrc = ip.in;
-            ip.resizeCpp = g.cpp;
-            ip.resizeStride = g.stride;
-            rows = H;
-            cols = W;
-            tight(c->rz.d_out);
-        }
-        bool aligned = (reinterpret_cast<uintptr_t>(ip.in) % 4 == 0) && (g.stride % 4 == 0);
-        if (fused)
-        {
-            aligned = aligned && g.chromaOff % 4 == 0 && g.frameStride % 4 == 0;
-            ip.set(yuvIngestKernel(mode, aligned), yuvSrc(ip.in, src.pix, H, W, g));
-        }
-        else
-        {
-            ip.set(ingestKernel(mode, aligned));
-        }
-        ip.profName = ip.launchName = fused ? "k_ingest_yuv420" : "k_ingest_u8";
-        return ACF_HIP_OK;
+        return fail(c, ACF_HIP_E_INVALID, who + "a plan for five input planes (image + M, O) takes float frames");
     }
-    if (src.kind == SRC_IMAGE)
+    const bool rz = c->rz.on, yuv = pixIsYuv(src.pix), fused = yuv && !rz && !fallbackForced(FB_YUV_UNFUSED);
+    int rows = rz ? c->rz.rows : H, cols = rz ? c->rz.cols : W; // the caller's frames
+    U8Geom& g = ip.g;
+    if (const char* bad = u8Geom(src.pix, rows, cols, src.rowStride, c->yuv.chromaOff, c->yuv.frameStride, g))
     {
-        // The image entry for upright images of any strides and element type (ACF.cpp:135-141 for CV_32FC3 and CV_8UC3; MatP.cpp:51-73);
-        // the resized entry: the apps' Resizer on the addressed bytes first, in the same kernel (k_ingest_resized)
-        if (const char* bad = imageDescBad(&src.img))
+        return fail(c, ACF_HIP_E_INVALID, std::string(src.who) + (rz && !yuv ? " (the unreduced frame): " : ": ") + bad);
+    }
+    if (!u8PlanesOk(g, d_in))
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + (yuv && !fused ? "the plan's input planes (d) must be 3 for NV12 / NV21"
+                                                              : "the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY"));
+    }
+    ip.in = static_cast<const uint8_t*>(src.base);
+    // a prelude leaves tight frames of the same pixel layout
+    const auto tight = [&](const uint8_t* at) {
+        ip.in = at;
+        g.stride = cols * g.cpp;
+        g.frameStride = int64_t(g.stride) * rows;
+    };
+    if (yuv && !fused)
+    {
+        const size_t need = size_t(c->maxBatch) * rows * cols * 3;
+        if (c->yuvRgbBytes < need)
         {
-            return fail(c, ACF_HIP_E_INVALID, who + bad);
-        }
-        if (d_in == 5)
-        {
-            return fail(c, ACF_HIP_E_INVALID, who + "a plan for five input planes (image + M, O) takes planar float frames");
-        }
-        if (src.img.channels != d_in)
-        {
-            return fail(c, ACF_HIP_E_INVALID, who + "channels must be the plan's input planes (d)");
-        }
-        ImageArgs s = imageArgs(src.base, src.img);
-        if (!src.resized)
-        {
-            if (c->rz.on)
+            HIPCHK(c, hipStreamSynchronize(c->stream)); // (a batch in flight may still read the smaller buffer)
+            devRelease(c, c->d_yuvRgb);
+            c->yuvRgbBytes = 0;
+            if (int rc = devAlloc(c, &c->d_yuvRgb, need))
             {
-                return fail(c, ACF_HIP_E_INVALID, who + "not with acf_hip_set_input_resize (the resize takes packed 8-bit frames)");
+                return rc;
             }
-            s.form = imageLoadForm(src.base, src.img);
-            if (src.orient)
-            {
-                // a turned frame: the same description and load forms at srcRows x srcCols, placed upright (k_ingest_image_oriented)
-                if (int rc = orientedBad(c, who, src.srcRows, src.srcCols, src.orient))
-                {
-                    return rc;
-                }
-                const OrientSrc o = orientSrc(src.orient, src.srcRows, src.srcCols);
-                ip.set(imageOrientedKernel(src.img.dtype, mode), ImageOrientedSrc{ s, o });
-                ip.profName = s.form == IM_GENERIC ? "k_ingest_image_oriented_generic" : (o.swap ? "k_ingest_image_oriented_cols" : "k_ingest_image_oriented_rows");
-                ip.launchName = "k_ingest_image_oriented";
-                return ACF_HIP_OK;
-            }
-            ip.set(imageKernel(src.img.dtype, mode), s);
-            ip.profName = ip.launchName = "k_ingest_image";
-            return ACF_HIP_OK;
+            c->yuvRgbBytes = need;
         }
+        ip.toRgb = true;
+        ip.toRgbSrc = yuvSrc(ip.in, src.pix, rows, cols, g);
+        g = U8Geom{ 3, 0, 0, 1, 2, false, 0, 0 };
+        tight(c->d_yuvRgb);
+    }
+    if (rz)
+    {
+        ip.resize = true;
+        ip.resizeSrc = ip.in;
+        ip.resizeCpp = g.cpp;
+        ip.resizeStride = g.stride;
+        rows = H;
+        cols = W;
+        tight(c->rz.d_out);
+    }
+    bool aligned = (reinterpret_cast<uintptr_t>(ip.in) % 4 == 0) && (g.stride % 4 == 0);
+    if (fused)
+    {
+        aligned = aligned && g.chromaOff % 4 == 0 && g.frameStride % 4 == 0;
+        ip.set(yuvIngestKernel(mode, aligned), yuvSrc(ip.in, src.pix, H, W, g));
+    }
+    else
+    {
+        ip.set(ingestKernel(mode, aligned));
+    }
+    ip.profName = ip.launchName = fused ? "k_ingest_yuv420" : "k_ingest_u8";
+    return ACF_HIP_OK;
+}
+
+// The image kind: images of any strides and element type (ACF.cpp:135-141 for CV_32FC3 and CV_8UC3; MatP.cpp:51-73), upright
+// (k_ingest_image) or turned — the same description and load forms at srcRows x srcCols, placed upright (k_ingest_image_oriented);
+// reduced: planReduced
+static int planImage(acf_hip_ctx* c, const FrameSource& src, int mode, IngestPlan& ip)
+{
+    const int d_in = c->plan.d_in;
+    const std::string who = std::string(src.who) + ": ";
+    if (const char* bad = imageDescBad(&src.img))
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + bad);
+    }
+    if (d_in == 5)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "a plan for five input planes (image + M, O) takes planar float frames");
+    }
+    if (src.img.channels != d_in)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "channels must be the plan's input planes (d)");
+    }
+    ImageArgs s = imageArgs(src.base, src.img);
+    if (src.resized)
+    {
         if (src.img.dtype != ACF_HIP_T_U8)
         {
             return fail(c, ACF_HIP_E_UNSUPPORTED, who + "dtype must be ACF_HIP_T_U8 (cv::resize's CV_32F arithmetic is not restated)");
         }
-        // (a turned unreduced frame: the tables and the plan are for the upright size: orient first, then resize)
-        int uprightRows, uprightCols, rc;
-        if ((rc = orientedResizedUpright(c, who, src, uprightRows, uprightCols)) || (rc = resizedTables(c, src.who, uprightRows, uprightCols, src.scale)))
-        {
-            return rc;
-        }
-        if (src.orient)
-        {
-            OrientedResizedSrc o{};
-            o.r.im = s;
-            planOrientedResized(c, RS_IMAGE, mode, imageLoadForm(src.base, src.img) == IM_ROWVEC, o, src, ip);
-            return ACF_HIP_OK;
-        }
         ResizedSrc r{};
-        r.t = resizeTaps(c->rzIn);
         r.im = s;
-        ip.set(resizedKernel(RS_IMAGE, mode), r);
-        ip.profName = "k_ingest_resized_image";
-        ip.launchName = "k_ingest_resized";
+        return planReduced(c, src, RS_IMAGE, mode, imageLoadForm(src.base, src.img) == IM_ROWVEC, r, ip);
+    }
+    if (c->rz.on)
+    {
+        return inputResizeRefused(c, src.who, "the resize takes packed 8-bit frames");
+    }
+    if (int rc = sourceAgainstPlan(c, src))
+    {
+        return rc;
+    }
+    s.form = imageLoadForm(src.base, src.img);
+    if (src.orient)
+    {
+        const OrientSrc o = orientSrc(src.orient, src.srcRows, src.srcCols);
+        ip.set(imageOrientedKernel(src.img.dtype, mode), ImageOrientedSrc{ s, o });
+        ip.profName = s.form == IM_GENERIC ? "k_ingest_image_oriented_generic" : (o.swap ? "k_ingest_image_oriented_cols" : "k_ingest_image_oriented_rows");
+        ip.launchName = "k_ingest_image_oriented";
         return ACF_HIP_OK;
     }
-    // The video frame entry for three-plane YUV descriptions: cvtColor's BT.601 integer conversion (restated, kernels_input.hip.h), then
-    // the 8-bit image entry (ACF.cpp:114-119,135-141; MatP.cpp:51-73), in one kernel; the resized entry: the apps' Resizer between the
-    // two, still one kernel (k_ingest_resized)
+    ip.set(imageKernel(src.img.dtype, mode), s);
+    ip.profName = ip.launchName = "k_ingest_image";
+    return ACF_HIP_OK;
+}
+
+// The YUV kind, three planes described by offsets and byte strides: cvtColor's BT.601 integer conversion (restated, kernels_input.hip.h),
+// then the 8-bit image entry (ACF.cpp:114-119,135-141; MatP.cpp:51-73), in one kernel.  A format other than the default (cf) runs the
+// same 8-bit kernels with the constants as an argument, under the same profile names; more than 8 bits is k_ingest_yuv16 (upright
+// and unreduced: sourceArgsBad).  The format itself was checked where the call or the stream's open stated it.
+static int planYuv(acf_hip_ctx* c, const FrameSource& src, int mode, IngestPlan& ip)
+{
+    const std::string who = std::string(src.who) + ": ";
     if (const char* bad = yuvDescBad(&src.yuv))
     {
         return fail(c, ACF_HIP_E_INVALID, who + bad);
     }
-    if (d_in != 3)
+    if (c->plan.d_in != 3)
     {
         return fail(c, ACF_HIP_E_INVALID, who + "the plan's input planes (d) must be 3");
-    }
-    // the video entries' format: another matrix or range runs the same 8-bit kernels with the constants as an argument (cf; the profile
-    // names stay); more than 8 bits is k_ingest_yuv16, upright and unreduced only
-    if (const char* bad = videoFormatBad(src.fmt))
-    {
-        return fail(c, ACF_HIP_E_INVALID, who + bad);
     }
     const bool cf = !videoFormatIsDefault(src.fmt);
     const uint8_t* base = static_cast<const uint8_t*>(src.base);
@@ -984,13 +1040,13 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
         {
             return fail(c, ACF_HIP_E_INVALID, who + bad);
         }
-        if (src.orient || src.resized)
-        {
-            return fail(c, ACF_HIP_E_UNSUPPORTED, who + "more than 8 bits a sample: upright and unreduced frames only (orient 0, scale 0)");
-        }
         if (c->rz.on)
         {
-            return fail(c, ACF_HIP_E_INVALID, who + "not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)");
+            return inputResizeRefused(c, src.who, "the resize takes the 8-bit entries' frames");
+        }
+        if (int rc = sourceAgainstPlan(c, src))
+        {
+            return rc;
         }
         static const char* const names16[3] = { "k_ingest_yuv16_generic", "k_ingest_yuv16_planar", "k_ingest_yuv16_pairs" };
         Yuv16Src y{};
@@ -1011,38 +1067,22 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
     }
     if (src.resized)
     {
-        int uprightRows, uprightCols, rc;
-        if ((rc = orientedResizedUpright(c, who, src, uprightRows, uprightCols)) || (rc = resizedTables(c, src.who, uprightRows, uprightCols, src.scale)))
-        {
-            return rc;
-        }
-        if (src.orient)
-        {
-            OrientedResizedSrc o{};
-            const bool vec = yuvLoadForm(s) == YD_PLANAR;
-            o.r.yuv = s;
-            planOrientedResized(c, cf ? RS_YUV_CF : RS_YUV, mode, vec, o, src, ip);
-            return ACF_HIP_OK;
-        }
+        const bool vec = src.orient && yuvLoadForm(s) == YD_PLANAR; // (the turned form's; yuvLoadForm leaves its findings in s)
         ResizedSrc r{};
-        r.t = resizeTaps(c->rzIn);
         r.yuv = s;
-        ip.set(resizedKernel(cf ? RS_YUV_CF : RS_YUV, mode), r);
-        ip.profName = "k_ingest_resized_yuv";
-        ip.launchName = "k_ingest_resized";
-        return ACF_HIP_OK;
+        return planReduced(c, src, cf ? RS_YUV_CF : RS_YUV, mode, vec, r, ip);
     }
     if (c->rz.on)
     {
-        return fail(c, ACF_HIP_E_INVALID, who + "not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)");
+        return inputResizeRefused(c, src.who, "the resize takes the 8-bit entries' frames");
+    }
+    if (int rc = sourceAgainstPlan(c, src))
+    {
+        return rc;
     }
     if (src.orient)
     {
         // a turned frame: the description at srcRows x srcCols, the chroma sample chosen there, placed upright (k_ingest_yuv_oriented)
-        if (int rc = orientedBad(c, who, src.srcRows, src.srcCols, src.orient))
-        {
-            return rc;
-        }
         YuvOrientedSrc y{};
         y.o = orientSrc(src.orient, src.srcRows, src.srcCols);
         y.form = yuvLoadForm(s);
@@ -1057,7 +1097,7 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
         return ACF_HIP_OK;
     }
     YuvSrc semi;
-    if (yuvIsSemiPlanar(base, src.yuv, H, W, semi))
+    if (yuvIsSemiPlanar(base, src.yuv, c->plan.H, c->plan.W, semi))
     {
         const bool aligned = reinterpret_cast<uintptr_t>(semi.in) % 4 == 0 && semi.rowStride % 4 == 0 && semi.chromaOff % 4 == 0 && semi.in_fs % 4 == 0;
         semi.k = s.k;
@@ -1073,6 +1113,19 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
     return ACF_HIP_OK;
 }
 
+// The ingest of one call: the source held against the plan and the context's settings (what is refused, in the order the entries
+// have always checked), then the kernel form, its arguments and its names.  The ONE place that decides them.
+static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
+{
+    ip = IngestPlan{};
+    // to the converted colour planes where the model converts (every colour space but hsv), else to planar planes in d_stage (hsv:
+    // k_rgb2hsv follows like on a float frame; orig / isLuv: the pyramid reads them as they are)
+    ip.convert = c->d_color && c->p.colorSpace != ACF_HIP_CS_HSV;
+    const int mode = ingestMode(c, ip.convert);
+    ip.nOut = (ip.convert && mode == IG_PLANAR) ? 3 : c->plan.d_in; // ORIG / RGB with a 1-plane input: replicate (chnsPyramid.cpp:242-243)
+    return src.kind == SRC_U8 ? planU8(c, src, mode, ip) : src.kind == SRC_IMAGE ? planImage(c, src, mode, ip) : planYuv(c, src, mode, ip);
+}
+
 // the pyramid of a source, then the cascade on it: the run_ entries of every kind but planar float frames, and the stream
 static int runSource(acf_hip_ctx* c, const FrameSource& src, int nF)
 {
@@ -1080,49 +1133,37 @@ static int runSource(acf_hip_ctx* c, const FrameSource& src, int nF)
     return rc ? rc : acf_hip_detect(c);
 }
 
-// the image and the YUV entries, plain and resized: the pyramid alone, or the whole run (detect)
-static int imageEntry(acf_hip_ctx* c, bool detect, const char* who, const void* frames, int nF, const acf_hip_image_desc* desc, bool resized = false, int srcRows = 0,
-    int srcCols = 0, double scale = 1, int orient = 0)
+// The two general entries, image and YUV: every exported entry of their kinds is one call of them that fills in what it states (st)
+// and leaves the rest 0 — srcRows == srcCols == 0: the plan's size, orient 0: upright, scale 0: no resize, no format: the default.
+// The pyramid alone, or the whole run (detect).  The order of the refusals is the entries' own: what the call states (sourceArgsBad),
+// the pointers, then pyramidBody's (streams, plan, n_frames) and planIngest's.
+static int imageEntry(acf_hip_ctx* c, bool detect, const char* who, const void* frames, int nF, const acf_hip_image_desc* desc, Stated st, int srcRows, int srcCols,
+    int orient, double scale)
 {
     if (int rc = needCtx(c)) return rc;
+    FrameSource src{ SRC_IMAGE, frames, who, 0, 0, {}, {}, false, srcRows, srcCols, scale, orient };
+    if (int rc = sourceArgsBad(c, who, st, src)) return rc;
     if (!frames || !desc)
     {
         return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": null frames or description");
     }
-    const FrameSource src{ SRC_IMAGE, frames, who, 0, 0, *desc, {}, resized, srcRows, srcCols, scale, orient };
+    src.img = *desc;
     return detect ? runSource(c, src, nF) : pyramidImpl(c, src, nF);
 }
-static int yuvEntry(acf_hip_ctx* c, bool detect, const char* who, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, bool resized = false, int srcRows = 0,
-    int srcCols = 0, double scale = 1, int orient = 0, const acf_hip_yuv_format& fmt = kDefaultVideoFormat)
+static int yuvEntry(acf_hip_ctx* c, bool detect, const char* who, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, Stated st, int srcRows, int srcCols,
+    int orient, double scale, const acf_hip_yuv_format* fmt = nullptr)
 {
     if (int rc = needCtx(c)) return rc;
+    FrameSource src{ SRC_YUV, base, who, 0, 0, {}, {}, false, srcRows, srcCols, scale, orient, fmt ? *fmt : kDefaultVideoFormat };
+    // (acf_hip_run_video alone among the run_ entries names itself, and only where its format, scale and sample width are refused;
+    // everywhere else it says pyramid_video, as every run_ entry says its pyramid_ twin's name)
+    if (int rc = sourceArgsBad(c, st == ST_VIDEO && detect ? "run_video" : who, st, src)) return rc;
     if (!base || !desc)
     {
         return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": null base or description");
     }
-    const FrameSource src{ SRC_YUV, base, who, 0, 0, {}, *desc, resized, srcRows, srcCols, scale, orient, fmt };
+    src.yuv = *desc;
     return detect ? runSource(c, src, nF) : pyramidImpl(c, src, nF);
-}
-
-// The oriented entries' own checks in front of imageEntry / yuvEntry.  Code 0 is the un-oriented entry itself (forward: true), once
-// the frame size is the plan's.
-static int orientedEntry(acf_hip_ctx* c, const char* who, int srcRows, int srcCols, int orient, bool& forward)
-{
-    forward = false;
-    if (int rc = needCtx(c)) return rc;
-    if (orient < 0 || orient > 7 || srcRows < 1 || srcCols < 1)
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
-    }
-    if (orient == 0)
-    {
-        if (c->hasPlan && c->kids.empty())
-        {
-            if (int rc = orientedBad(c, std::string(who) + ": ", srcRows, srcCols, 0)) return rc;
-        }
-        forward = true;
-    }
-    return ACF_HIP_OK;
 }
 } // namespace
 
@@ -1140,115 +1181,94 @@ int acf_hip_run_u8(acf_hip_ctx* c, const uint8_t* frames, int nF, int pix, int r
 
 int acf_hip_pyramid_image(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc)
 {
-    return imageEntry(c, false, "pyramid_image", frames, nF, desc);
+    return imageEntry(c, false, "pyramid_image", frames, nF, desc, ST_PLAN, 0, 0, 0, 0);
 }
 
 int acf_hip_run_image(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc)
 {
-    return imageEntry(c, true, "pyramid_image", frames, nF, desc);
+    return imageEntry(c, true, "pyramid_image", frames, nF, desc, ST_PLAN, 0, 0, 0, 0);
 }
 
 int acf_hip_pyramid_image_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, double scale)
 {
-    return imageEntry(c, false, "pyramid_image_resized", frames, nF, desc, true, srcRows, srcCols, scale);
+    return imageEntry(c, false, "pyramid_image_resized", frames, nF, desc, ST_REDUCED, srcRows, srcCols, 0, scale);
 }
 
 int acf_hip_run_image_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, double scale)
 {
-    return imageEntry(c, true, "pyramid_image_resized", frames, nF, desc, true, srcRows, srcCols, scale);
-}
-
-int acf_hip_pyramid_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
-{
-    return yuvEntry(c, false, "pyramid_yuv", base, nF, desc);
-}
-
-int acf_hip_run_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
-{
-    return yuvEntry(c, true, "pyramid_yuv", base, nF, desc);
-}
-
-int acf_hip_pyramid_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
-{
-    return yuvEntry(c, false, "pyramid_yuv_resized", base, nF, desc, true, srcRows, srcCols, scale);
-}
-
-int acf_hip_run_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
-{
-    return yuvEntry(c, true, "pyramid_yuv_resized", base, nF, desc, true, srcRows, srcCols, scale);
+    return imageEntry(c, true, "pyramid_image_resized", frames, nF, desc, ST_REDUCED, srcRows, srcCols, 0, scale);
 }
 
 int acf_hip_pyramid_image_oriented(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, int orient)
 {
-    bool forward;
-    if (int rc = orientedEntry(c, "pyramid_image_oriented", srcRows, srcCols, orient, forward)) return rc;
-    return forward ? acf_hip_pyramid_image(c, frames, nF, desc) : imageEntry(c, false, "pyramid_image_oriented", frames, nF, desc, false, srcRows, srcCols, 1, orient);
+    return imageEntry(c, false, "pyramid_image_oriented", frames, nF, desc, ST_TURNED, srcRows, srcCols, orient, 0);
 }
 
 int acf_hip_run_image_oriented(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, int orient)
 {
-    bool forward;
-    if (int rc = orientedEntry(c, "pyramid_image_oriented", srcRows, srcCols, orient, forward)) return rc;
-    return forward ? acf_hip_run_image(c, frames, nF, desc) : imageEntry(c, true, "pyramid_image_oriented", frames, nF, desc, false, srcRows, srcCols, 1, orient);
-}
-
-int acf_hip_pyramid_yuv_oriented(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient)
-{
-    bool forward;
-    if (int rc = orientedEntry(c, "pyramid_yuv_oriented", srcRows, srcCols, orient, forward)) return rc;
-    return forward ? acf_hip_pyramid_yuv(c, base, nF, desc) : yuvEntry(c, false, "pyramid_yuv_oriented", base, nF, desc, false, srcRows, srcCols, 1, orient);
-}
-
-int acf_hip_run_yuv_oriented(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient)
-{
-    bool forward;
-    if (int rc = orientedEntry(c, "pyramid_yuv_oriented", srcRows, srcCols, orient, forward)) return rc;
-    return forward ? acf_hip_run_yuv(c, base, nF, desc) : yuvEntry(c, true, "pyramid_yuv_oriented", base, nF, desc, false, srcRows, srcCols, 1, orient);
-}
-
-// The oriented resized entries' own checks in front of imageEntry / yuvEntry.  Code 0 is the resized entry itself (forward: true).
-static int orientedResizedEntry(acf_hip_ctx* c, const char* who, int srcRows, int srcCols, int orient, bool& forward)
-{
-    forward = false;
-    if (int rc = needCtx(c)) return rc;
-    if (orient < 0 || orient > 7 || srcRows < 1 || srcCols < 1)
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string(who) + ": orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1");
-    }
-    forward = orient == 0;
-    return ACF_HIP_OK;
+    return imageEntry(c, true, "pyramid_image_oriented", frames, nF, desc, ST_TURNED, srcRows, srcCols, orient, 0);
 }
 
 int acf_hip_pyramid_image_oriented_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, int orient, double scale)
 {
-    bool forward;
-    if (int rc = orientedResizedEntry(c, "pyramid_image_oriented_resized", srcRows, srcCols, orient, forward)) return rc;
-    return forward ? acf_hip_pyramid_image_resized(c, frames, nF, desc, srcRows, srcCols, scale)
-                   : imageEntry(c, false, "pyramid_image_oriented_resized", frames, nF, desc, true, srcRows, srcCols, scale, orient);
+    return imageEntry(c, false, "pyramid_image_oriented_resized", frames, nF, desc, ST_TURNED_REDUCED, srcRows, srcCols, orient, scale);
 }
 
 int acf_hip_run_image_oriented_resized(acf_hip_ctx* c, const void* frames, int nF, const acf_hip_image_desc* desc, int srcRows, int srcCols, int orient, double scale)
 {
-    bool forward;
-    if (int rc = orientedResizedEntry(c, "pyramid_image_oriented_resized", srcRows, srcCols, orient, forward)) return rc;
-    return forward ? acf_hip_run_image_resized(c, frames, nF, desc, srcRows, srcCols, scale)
-                   : imageEntry(c, true, "pyramid_image_oriented_resized", frames, nF, desc, true, srcRows, srcCols, scale, orient);
+    return imageEntry(c, true, "pyramid_image_oriented_resized", frames, nF, desc, ST_TURNED_REDUCED, srcRows, srcCols, orient, scale);
+}
+
+int acf_hip_pyramid_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
+{
+    return yuvEntry(c, false, "pyramid_yuv", base, nF, desc, ST_PLAN, 0, 0, 0, 0);
+}
+
+int acf_hip_run_yuv(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc)
+{
+    return yuvEntry(c, true, "pyramid_yuv", base, nF, desc, ST_PLAN, 0, 0, 0, 0);
+}
+
+int acf_hip_pyramid_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
+{
+    return yuvEntry(c, false, "pyramid_yuv_resized", base, nF, desc, ST_REDUCED, srcRows, srcCols, 0, scale);
+}
+
+int acf_hip_run_yuv_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, double scale)
+{
+    return yuvEntry(c, true, "pyramid_yuv_resized", base, nF, desc, ST_REDUCED, srcRows, srcCols, 0, scale);
+}
+
+int acf_hip_pyramid_yuv_oriented(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient)
+{
+    return yuvEntry(c, false, "pyramid_yuv_oriented", base, nF, desc, ST_TURNED, srcRows, srcCols, orient, 0);
+}
+
+int acf_hip_run_yuv_oriented(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient)
+{
+    return yuvEntry(c, true, "pyramid_yuv_oriented", base, nF, desc, ST_TURNED, srcRows, srcCols, orient, 0);
 }
 
 int acf_hip_pyramid_yuv_oriented_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient, double scale)
 {
-    bool forward;
-    if (int rc = orientedResizedEntry(c, "pyramid_yuv_oriented_resized", srcRows, srcCols, orient, forward)) return rc;
-    return forward ? acf_hip_pyramid_yuv_resized(c, base, nF, desc, srcRows, srcCols, scale)
-                   : yuvEntry(c, false, "pyramid_yuv_oriented_resized", base, nF, desc, true, srcRows, srcCols, scale, orient);
+    return yuvEntry(c, false, "pyramid_yuv_oriented_resized", base, nF, desc, ST_TURNED_REDUCED, srcRows, srcCols, orient, scale);
 }
 
 int acf_hip_run_yuv_oriented_resized(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, int srcRows, int srcCols, int orient, double scale)
 {
-    bool forward;
-    if (int rc = orientedResizedEntry(c, "pyramid_yuv_oriented_resized", srcRows, srcCols, orient, forward)) return rc;
-    return forward ? acf_hip_run_yuv_resized(c, base, nF, desc, srcRows, srcCols, scale)
-                   : yuvEntry(c, true, "pyramid_yuv_oriented_resized", base, nF, desc, true, srcRows, srcCols, scale, orient);
+    return yuvEntry(c, true, "pyramid_yuv_oriented_resized", base, nF, desc, ST_TURNED_REDUCED, srcRows, srcCols, orient, scale);
+}
+
+int acf_hip_pyramid_video(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, int srcRows, int srcCols, int orient,
+    double scale)
+{
+    return yuvEntry(c, false, "pyramid_video", base, nF, desc, ST_VIDEO, srcRows, srcCols, orient, scale, fmt);
+}
+
+int acf_hip_run_video(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, int srcRows, int srcCols, int orient,
+    double scale)
+{
+    return yuvEntry(c, true, "pyramid_video", base, nF, desc, ST_VIDEO, srcRows, srcCols, orient, scale, fmt);
 }
 
 int acf_hip_oriented_resized_dims(int srcRows, int srcCols, int orient, double scale, int* h, int* w)
@@ -1263,7 +1283,7 @@ int acf_hip_oriented_resized_dims(int srcRows, int srcCols, int orient, double s
 
 int acf_hip_oriented_dims(int srcRows, int srcCols, int orient, int* h, int* w)
 {
-    if (!h || !w || srcRows < 1 || srcCols < 1 || orient < 0 || orient > 7)
+    if (!h || !w || orientedArgsBad(srcRows, srcCols, orient))
     {
         return ACF_HIP_E_INVALID;
     }
@@ -1274,7 +1294,7 @@ int acf_hip_oriented_dims(int srcRows, int srcCols, int orient, int* h, int* w)
 
 int acf_hip_unorient_rect(int orient, int srcRows, int srcCols, const int32_t in[4], int32_t out[4])
 {
-    if (!in || !out || srcRows < 1 || srcCols < 1 || orient < 0 || orient > 7)
+    if (!in || !out || orientedArgsBad(srcRows, srcCols, orient))
     {
         return ACF_HIP_E_INVALID;
     }
@@ -1304,28 +1324,6 @@ int acf_hip_image_extent(const acf_hip_image_desc* d, int h, int w, int nF, int6
     }
     *first = lo;
     *last = hi;
-    return ACF_HIP_OK;
-}
-
-int acf_hip_yuv_to_rgb8(acf_hip_ctx* c, const uint8_t* base, int nF, int rows, int cols, const acf_hip_yuv_desc* desc, uint8_t* dst)
-{
-    if (int rc = needCtx(c)) return rc;
-    if (!base || !desc || !dst)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "yuv_to_rgb8: null base, description or destination");
-    }
-    if (const char* bad = yuvDescBad(desc))
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string("yuv_to_rgb8: ") + bad);
-    }
-    if (nF < 1 || nF > 65535 || rows < 1 || cols < 1)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "yuv_to_rgb8: n_frames 1 .. 65535, rows and cols >= 1");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    prof(c, c->stream, "k_yuv_to_rgb8");
-    hipLaunchKernelGGL(k_yuv_to_rgb8, dim3(cdiv(cols, 64), cdiv(rows, 4), nF), dim3(256), 0, c->stream, yuvDescSrc(base, *desc), rows, cols, dst);
-    LAUNCHCHK(c, "k_yuv_to_rgb8");
     return ACF_HIP_OK;
 }
 
@@ -1390,107 +1388,48 @@ int acf_hip_yuv_layout(int layout, int h, int w, int rowStride, acf_hip_yuv_desc
     return ACF_HIP_OK;
 }
 
-// ---- the video entries: acf_hip_yuv_format beside the descriptor (the header's "video formats" section) ----
+// ---- what else takes an acf_hip_yuv_format beside the descriptor (the header's "video formats" section) ----
 
-// The default format forwards to the existing entry of the call's family — the same kernels under the same names; any other format
-// goes through the family's own checks (orientedEntry / orientedResizedEntry) and then yuvEntry with the format in the FrameSource.
-static int videoEntry(acf_hip_ctx* c, bool detect, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmtIn, int srcRows, int srcCols,
-    int orient, double scale)
+// The conversion alone, of any format, under the name of the entry that was called
+static int videoToRgb(acf_hip_ctx* c, const std::string& who, const uint8_t* base, int nF, int rows, int cols, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format& fmt,
+    void* dst)
 {
     if (int rc = needCtx(c)) return rc;
-    const acf_hip_yuv_format fmt = fmtIn ? *fmtIn : kDefaultVideoFormat;
-    const std::string who = detect ? "run_video: " : "pyramid_video: ";
     if (const char* bad = videoFormatBad(fmt))
     {
         return fail(c, ACF_HIP_E_INVALID, who + bad);
     }
-    if (!(scale >= 0) || !std::isfinite(scale))
-    {
-        return fail(c, ACF_HIP_E_INVALID, who + "scale must be 0 (no resize) or a positive finite number");
-    }
-    const bool plain = orient == 0 && scale == 0 && srcRows == 0 && srcCols == 0; // the plan's size
-    if (videoFormatIsDefault(fmt))
-    {
-        if (plain)
-        {
-            return detect ? acf_hip_run_yuv(c, base, nF, desc) : acf_hip_pyramid_yuv(c, base, nF, desc);
-        }
-        if (scale == 0)
-        {
-            return detect ? acf_hip_run_yuv_oriented(c, base, nF, desc, srcRows, srcCols, orient) : acf_hip_pyramid_yuv_oriented(c, base, nF, desc, srcRows, srcCols, orient);
-        }
-        return detect ? acf_hip_run_yuv_oriented_resized(c, base, nF, desc, srcRows, srcCols, orient, scale)
-                      : acf_hip_pyramid_yuv_oriented_resized(c, base, nF, desc, srcRows, srcCols, orient, scale);
-    }
-    if (fmt.bits > 8 && (orient != 0 || scale != 0))
-    {
-        return fail(c, ACF_HIP_E_UNSUPPORTED, who + "more than 8 bits a sample: upright and unreduced frames only (orient 0, scale 0)");
-    }
-    if (plain)
-    {
-        return yuvEntry(c, detect, "pyramid_video", base, nF, desc, false, 0, 0, 1, 0, fmt);
-    }
-    bool forward;
-    if (scale == 0)
-    {
-        if (int rc = orientedEntry(c, "pyramid_video", srcRows, srcCols, orient, forward)) return rc;
-        return yuvEntry(c, detect, "pyramid_video", base, nF, desc, false, srcRows, srcCols, 1, orient, fmt);
-    }
-    if (int rc = orientedResizedEntry(c, "pyramid_video", srcRows, srcCols, orient, forward)) return rc;
-    return yuvEntry(c, detect, "pyramid_video", base, nF, desc, true, srcRows, srcCols, scale, orient, fmt);
-}
-
-int acf_hip_pyramid_video(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, int srcRows, int srcCols, int orient,
-    double scale)
-{
-    return videoEntry(c, false, base, nF, desc, fmt, srcRows, srcCols, orient, scale);
-}
-
-int acf_hip_run_video(acf_hip_ctx* c, const uint8_t* base, int nF, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, int srcRows, int srcCols, int orient,
-    double scale)
-{
-    return videoEntry(c, true, base, nF, desc, fmt, srcRows, srcCols, orient, scale);
-}
-
-int acf_hip_video_to_rgb(acf_hip_ctx* c, const uint8_t* base, int nF, int rows, int cols, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmtIn, void* dst)
-{
-    if (int rc = needCtx(c)) return rc;
-    const acf_hip_yuv_format fmt = fmtIn ? *fmtIn : kDefaultVideoFormat;
-    if (const char* bad = videoFormatBad(fmt))
-    {
-        return fail(c, ACF_HIP_E_INVALID, std::string("video_to_rgb: ") + bad);
-    }
-    if (videoFormatIsDefault(fmt))
-    {
-        return acf_hip_yuv_to_rgb8(c, base, nF, rows, cols, desc, static_cast<uint8_t*>(dst));
-    }
     if (!base || !desc || !dst)
     {
-        return fail(c, ACF_HIP_E_INVALID, "video_to_rgb: null base, description or destination");
+        return fail(c, ACF_HIP_E_INVALID, who + "null base, description or destination");
     }
     if (const char* bad = yuvDescBad(desc))
     {
-        return fail(c, ACF_HIP_E_INVALID, std::string("video_to_rgb: ") + bad);
+        return fail(c, ACF_HIP_E_INVALID, who + bad);
     }
     if (nF < 1 || nF > 65535 || rows < 1 || cols < 1)
     {
-        return fail(c, ACF_HIP_E_INVALID, "video_to_rgb: n_frames 1 .. 65535, rows and cols >= 1");
+        return fail(c, ACF_HIP_E_INVALID, who + "n_frames 1 .. 65535, rows and cols >= 1");
     }
     const dim3 grid(cdiv(cols, 64), cdiv(rows, 4), nF);
     if (fmt.bits == 8)
     {
+        const bool cf = !videoFormatIsDefault(fmt);
         YuvDescSrc s = yuvDescSrc(base, *desc);
-        s.k = yuvCoef(fmt);
+        if (cf)
+        {
+            s.k = yuvCoef(fmt);
+        }
         HIPCHK(c, hipSetDevice(c->device));
         prof(c, c->stream, "k_yuv_to_rgb8");
-        hipLaunchKernelGGL(k_yuv_to_rgb8<true>, grid, dim3(256), 0, c->stream, s, rows, cols, static_cast<uint8_t*>(dst));
+        hipLaunchKernelGGL((!cf ? k_yuv_to_rgb8<false> : k_yuv_to_rgb8<true>), grid, dim3(256), 0, c->stream, s, rows, cols, static_cast<uint8_t*>(dst));
         LAUNCHCHK(c, "k_yuv_to_rgb8");
         return ACF_HIP_OK;
     }
     const char* bad = video16DescBad(base, *desc);
     if (bad || reinterpret_cast<uintptr_t>(dst) % 2)
     {
-        return fail(c, ACF_HIP_E_INVALID, std::string("video_to_rgb: ") + (bad ? bad : "16-bit samples need an even destination"));
+        return fail(c, ACF_HIP_E_INVALID, who + (bad ? bad : "16-bit samples need an even destination"));
     }
     Yuv16Src y{};
     y.yuv = yuvDescSrc(base, *desc);
@@ -1502,6 +1441,16 @@ int acf_hip_video_to_rgb(acf_hip_ctx* c, const uint8_t* base, int nF, int rows, 
     hipLaunchKernelGGL(k_video_to_rgb16, grid, dim3(256), 0, c->stream, y, rows, cols, static_cast<uint16_t*>(dst));
     LAUNCHCHK(c, "k_video_to_rgb16");
     return ACF_HIP_OK;
+}
+
+int acf_hip_yuv_to_rgb8(acf_hip_ctx* c, const uint8_t* base, int nF, int rows, int cols, const acf_hip_yuv_desc* desc, uint8_t* dst)
+{
+    return videoToRgb(c, "yuv_to_rgb8: ", base, nF, rows, cols, desc, kDefaultVideoFormat, dst);
+}
+
+int acf_hip_video_to_rgb(acf_hip_ctx* c, const uint8_t* base, int nF, int rows, int cols, const acf_hip_yuv_desc* desc, const acf_hip_yuv_format* fmt, void* dst)
+{
+    return videoToRgb(c, "video_to_rgb: ", base, nF, rows, cols, desc, fmt ? *fmt : kDefaultVideoFormat, dst);
 }
 
 int acf_hip_video_extent(const acf_hip_yuv_desc* d, const acf_hip_yuv_format* fmtIn, int h, int w, int nF, int64_t* first, int64_t* last)

@@ -174,66 +174,74 @@ class HipDetector:
         sn, sc, sy, sx = t.stride()
         return t.data_ptr(), n, capi.ImageDesc(self._torch_dtype_code(t), ch, sn, sc, sy, sx)
 
+    def _entry_for(self, src_rows, src_cols, orient, scale):
+        """(name suffix, further arguments) of the most specific entry for what the caller states about the frames — a size, an
+        orientation, a scale — pyramid, run and stream_open alike; the library takes all of them through one general entry.  Code 0
+        beside a scale is the resized entry, beside a size alone the oriented one."""
+        if scale is not None and not orient:
+            return "_resized", (src_rows, src_cols, float(scale))
+        if scale is not None:
+            return "_oriented_resized", (src_rows, src_cols, orient, float(scale))
+        if orient or src_rows is not None:
+            return "_oriented", (*self._src_size(orient, src_rows, src_cols), orient)
+        return "", ()
+
+    def _source_call(self, stem, ptr, n, desc, src_rows=None, src_cols=None, orient=0, scale=None):
+        suffix, args = self._entry_for(src_rows, src_cols, orient, scale)
+        self._chk(getattr(self.lib, "acf_hip_" + stem + suffix)(self.ctx, ptr, n, C.byref(desc), *args))
+
+    def _image_call(self, run, ptr, n, desc, *geometry):
+        self._source_call("run_image" if run else "pyramid_image", C.c_void_p(ptr), n, desc, *geometry)
+
+    def _yuv_call(self, run, base, n, desc, *geometry):
+        self._source_call("run_yuv" if run else "pyramid_yuv", C.c_void_p(base if isinstance(base, int) else base.data_ptr()), n, desc, *geometry)
+
+    def _tensor_call(self, run, t, layout, orient, scale=None):
+        ptr, n, desc = self._image_of(t, layout, scale, orient)
+        rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
+        own = orient or scale is not None   # (else the plan's size, which _image_of has held the tensor against: the plain entry)
+        self._image_call(run, ptr, n, desc, rows if own else None, cols if own else None, orient, scale)
+
     def pyramid_tensor(self, t, layout="nchw", orient=0):
         """t: device tensor [n, c, H, W] of any strides (or [n, H, W, c] with layout="nhwc"), uint8 / float16 / bfloat16 / float32.
         orient (capi.ORIENT_*, rot + 4 * mirror): t is the frame as stored, [n, c, Hs, Ws]; the plan is for oriented_dims(Hs, Ws, orient)
         and detections are in the upright frame (unorient_boxes maps them back).  0 takes the un-oriented entry."""
-        ptr, n, desc = self._image_of(t, layout, orient=orient)
-        if not orient:
-            self._chk(self.lib.acf_hip_pyramid_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
-            return
-        rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
-        self._chk(self.lib.acf_hip_pyramid_image_oriented(self.ctx, C.c_void_p(ptr), n, C.byref(desc), rows, cols, orient))
+        self._tensor_call(False, t, layout, orient)
 
     def run_tensor(self, t, layout="nchw", orient=0):
-        ptr, n, desc = self._image_of(t, layout, orient=orient)
-        if not orient:
-            self._chk(self.lib.acf_hip_run_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
-            return
-        rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
-        self._chk(self.lib.acf_hip_run_image_oriented(self.ctx, C.c_void_p(ptr), n, C.byref(desc), rows, cols, orient))
+        self._tensor_call(True, t, layout, orient)
 
     def pyramid_image_oriented(self, ptr, n, desc, src_rows, src_cols, orient):
         """The raw oriented entry: desc describes frames of src_rows x src_cols; the plan is for oriented_dims of them."""
-        self._chk(self.lib.acf_hip_pyramid_image_oriented(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, orient))
+        self._image_call(False, ptr, n, desc, src_rows, src_cols, orient)
 
     def run_image_oriented(self, ptr, n, desc, src_rows, src_cols, orient):
-        self._chk(self.lib.acf_hip_run_image_oriented(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, orient))
+        self._image_call(True, ptr, n, desc, src_rows, src_cols, orient)
 
     def pyramid_tensor_resized(self, t, scale, layout="nchw", orient=0):
         """t: uint8 device tensor of the UNREDUCED frames [n, c, rows, cols] of any strides; the plan is for resize_dims(rows, cols,
         scale).  The apps' resize and the ingest in one kernel; detections are in the reduced frame (unscale_boxes maps them back).
         orient (capi.ORIENT_*): t is the unreduced frame AS STORED; it is turned upright, then reduced: the plan is for
         oriented_resized_dims(rows, cols, orient, scale), and unscale_boxes, then unorient_boxes map detections back."""
-        ptr, n, desc = self._image_of(t, layout, scale)
-        rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
-        self.pyramid_image_resized(ptr, n, desc, rows, cols, scale, orient)
+        self._tensor_call(False, t, layout, orient, scale)
 
     def run_tensor_resized(self, t, scale, layout="nchw", orient=0):
-        ptr, n, desc = self._image_of(t, layout, scale)
-        rows, cols = (t.shape[2], t.shape[3]) if layout == "nchw" else (t.shape[1], t.shape[2])
-        self.run_image_resized(ptr, n, desc, rows, cols, scale, orient)
+        self._tensor_call(True, t, layout, orient, scale)
 
     def pyramid_image(self, ptr, n, desc):
         """The raw entry: a device pointer (int) and a capi.ImageDesc."""
-        self._chk(self.lib.acf_hip_pyramid_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+        self._image_call(False, ptr, n, desc)
 
     def run_image(self, ptr, n, desc):
-        self._chk(self.lib.acf_hip_run_image(self.ctx, C.c_void_p(ptr), n, C.byref(desc)))
+        self._image_call(True, ptr, n, desc)
 
     def pyramid_image_resized(self, ptr, n, desc, src_rows, src_cols, scale, orient=0):
         """The raw resized entry: desc (uint8) describes frames of src_rows x src_cols; the plan is for resize_dims of them — with
         orient, for oriented_resized_dims (the frame is turned upright first, then reduced)."""
-        if not orient:
-            self._chk(self.lib.acf_hip_pyramid_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, float(scale)))
-        else:
-            self._chk(self.lib.acf_hip_pyramid_image_oriented_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, orient, float(scale)))
+        self._image_call(False, ptr, n, desc, src_rows, src_cols, orient, scale)
 
     def run_image_resized(self, ptr, n, desc, src_rows, src_cols, scale, orient=0):
-        if not orient:
-            self._chk(self.lib.acf_hip_run_image_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, float(scale)))
-        else:
-            self._chk(self.lib.acf_hip_run_image_oriented_resized(self.ctx, C.c_void_p(ptr), n, C.byref(desc), src_rows, src_cols, orient, float(scale)))
+        self._image_call(True, ptr, n, desc, src_rows, src_cols, orient, scale)
 
     @staticmethod
     def image_extent(desc, h, w, n):
@@ -292,18 +300,10 @@ class HipDetector:
     def pyramid_yuv(self, base, n, desc, orient=0, src_rows=None, src_cols=None):
         """base: a torch uint8 CUDA tensor (its first byte is the base; it need not be contiguous) or a device pointer.
         orient (capi.ORIENT_*): desc describes the frame as stored, src_rows x src_cols; the plan is for oriented_dims of that."""
-        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
-        if not orient and src_rows is None:
-            self._chk(self.lib.acf_hip_pyramid_yuv(self.ctx, ptr, n, C.byref(desc)))
-        else:
-            self._chk(self.lib.acf_hip_pyramid_yuv_oriented(self.ctx, ptr, n, C.byref(desc), *self._src_size(orient, src_rows, src_cols), orient))
+        self._yuv_call(False, base, n, desc, src_rows, src_cols, orient)
 
     def run_yuv(self, base, n, desc, orient=0, src_rows=None, src_cols=None):
-        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
-        if not orient and src_rows is None:
-            self._chk(self.lib.acf_hip_run_yuv(self.ctx, ptr, n, C.byref(desc)))
-        else:
-            self._chk(self.lib.acf_hip_run_yuv_oriented(self.ctx, ptr, n, C.byref(desc), *self._src_size(orient, src_rows, src_cols), orient))
+        self._yuv_call(True, base, n, desc, src_rows, src_cols, orient)
 
     def _src_size(self, orient, src_rows, src_cols):
         """The stored frame's size where the caller left it out: the plan's, turned back (odd rot swaps rows and columns)."""
@@ -316,18 +316,10 @@ class HipDetector:
         resize and the ingest in one kernel; detections are in the reduced frame (unscale_boxes maps them back).
         orient (capi.ORIENT_*): the frames as stored; turned upright, then reduced: the plan is for oriented_resized_dims(src_rows,
         src_cols, orient, scale); unscale_boxes, then unorient_boxes map detections back."""
-        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
-        if not orient:
-            self._chk(self.lib.acf_hip_pyramid_yuv_resized(self.ctx, ptr, n, C.byref(desc), src_rows, src_cols, float(scale)))
-        else:
-            self._chk(self.lib.acf_hip_pyramid_yuv_oriented_resized(self.ctx, ptr, n, C.byref(desc), src_rows, src_cols, orient, float(scale)))
+        self._yuv_call(False, base, n, desc, src_rows, src_cols, orient, scale)
 
     def run_yuv_resized(self, base, n, desc, src_rows, src_cols, scale, orient=0):
-        ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
-        if not orient:
-            self._chk(self.lib.acf_hip_run_yuv_resized(self.ctx, ptr, n, C.byref(desc), src_rows, src_cols, float(scale)))
-        else:
-            self._chk(self.lib.acf_hip_run_yuv_oriented_resized(self.ctx, ptr, n, C.byref(desc), src_rows, src_cols, orient, float(scale)))
+        self._yuv_call(True, base, n, desc, src_rows, src_cols, orient, scale)
 
     @staticmethod
     def yuv_planes_desc(y, u, v, sub_x, sub_y):
@@ -351,12 +343,8 @@ class HipDetector:
         scale: the planes are the unreduced frame (run_yuv_resized; the plan is for resize_dims of y's size).  orient: the planes as
         stored (the plan is for oriented_dims of y's size); with both, turned upright and then reduced (oriented_resized_dims)."""
         base, n, desc = self.yuv_planes_desc(y, u, v, sub_x, sub_y)
-        if scale is not None:
-            self.run_yuv_resized(base, n, desc, y.shape[-2], y.shape[-1], scale, orient)
-        elif orient:
-            self.run_yuv(base, n, desc, orient, y.shape[-2], y.shape[-1])
-        else:
-            self.run_yuv(base, n, desc)
+        own = scale is not None or orient
+        self._yuv_call(True, base, n, desc, y.shape[-2] if own else None, y.shape[-1] if own else None, orient, scale)
 
     def yuv_to_rgb8(self, base, n, rows, cols, desc):
         """The conversion alone on the device -> torch uint8 CUDA tensor [n][rows][cols][3] (acf_hip_yuv_to_rgb8; no model or plan)."""
@@ -370,18 +358,15 @@ class HipDetector:
     def stream_open_yuv(self, desc, frame_bytes, cap=1024, depth=2, orient=0, src_rows=None, src_cols=None):
         """The streaming front end for host frames of frame_bytes each, described by desc (stride_n == frame_bytes).
         orient: frames as stored, src_rows x src_cols; every submit runs run_yuv(..., orient) on its slot."""
-        if not orient and src_rows is None:
-            self._chk(self.lib.acf_hip_stream_open_yuv(self.ctx, C.byref(desc), frame_bytes, cap, depth))
-        else:
-            self._chk(self.lib.acf_hip_stream_open_yuv_oriented(self.ctx, C.byref(desc), frame_bytes, *self._src_size(orient, src_rows, src_cols), orient, cap, depth))
-        self._stream_cap = cap
+        self._yuv_open(desc, frame_bytes, cap, depth, src_rows, src_cols, orient)
 
     def stream_open_yuv_resized(self, desc, frame_bytes, src_rows, src_cols, scale, cap=1024, depth=2, orient=0):
         """stream_open_yuv for unreduced frames of src_rows x src_cols: every submit runs run_yuv_resized(..., orient) on its slot."""
-        if not orient:
-            self._chk(self.lib.acf_hip_stream_open_yuv_resized(self.ctx, C.byref(desc), frame_bytes, src_rows, src_cols, float(scale), cap, depth))
-        else:
-            self._chk(self.lib.acf_hip_stream_open_yuv_oriented_resized(self.ctx, C.byref(desc), frame_bytes, src_rows, src_cols, orient, float(scale), cap, depth))
+        self._yuv_open(desc, frame_bytes, cap, depth, src_rows, src_cols, orient, scale)
+
+    def _yuv_open(self, desc, frame_bytes, cap, depth, src_rows=None, src_cols=None, orient=0, scale=None):
+        suffix, args = self._entry_for(src_rows, src_cols, orient, scale)
+        self._chk(getattr(self.lib, "acf_hip_stream_open_yuv" + suffix)(self.ctx, C.byref(desc), frame_bytes, *args, cap, depth))
         self._stream_cap = cap
 
     # ---- video formats (acf_hip_yuv_format): 9 .. 16-bit samples, BT.709 / BT.2020, full range, beside the same descriptors
@@ -428,7 +413,7 @@ class HipDetector:
         return (C.byref(fmt) if fmt is not None else None), src_rows, src_cols, orient, float(scale) if scale is not None else 0.0
 
     def pyramid_video(self, base, n, desc, fmt=None, src_rows=None, src_cols=None, orient=0, scale=None):
-        """pyramid_yuv / _oriented / _resized for frames of any capi.YuvFormat (fmt None: the default, which forwards to them).
+        """pyramid_yuv / _oriented / _resized for frames of any capi.YuvFormat (fmt None: the default, the arithmetic of those entries).
         base: a torch device tensor (its first byte is the base) or a device pointer.  More than 8 bits: orient 0 and no scale."""
         ptr = C.c_void_p(base if isinstance(base, int) else base.data_ptr())
         self._chk(self.lib.acf_hip_pyramid_video(self.ctx, ptr, n, C.byref(desc), *self._video_args(fmt, src_rows, src_cols, orient, scale)))

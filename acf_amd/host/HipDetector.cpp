@@ -640,33 +640,21 @@ int HipDetector::detectImages(const void* framesDev, int nFrames, int rows, int 
     {
         throw Exception(ACF_HIP_E_UNSUPPORTED, "detectImages: setMinObjectWidth takes 8-bit images (cv::resize's CV_32F arithmetic is not restated)");
     }
-    const bool oriented = orientedPlan(rows, cols, resized, planRows, planCols);
+    orientedPlan(rows, cols, resized, planRows, planCols);
     ensurePlan(planRows, planCols, desc.channels, nFrames);
     syncNms();
-    if (oriented && resized) // (fetchBatch unscales: boxes in the upright full-size frame)
+    // (code 0 included: the un-oriented entry's kernels; boxes in the upright frame, which fetchBatch unscales to the full size)
+    if (resized)
     {
         check(m_api->acf_hip_run_image_oriented_resized(m_ctx, framesDev, nFrames, &desc, rows, cols, m_orient, double(inputScale())),
             "acf_hip_run_image_oriented_resized");
     }
-    else if (oriented) // (boxes in the upright frame)
+    else
     {
         check(m_api->acf_hip_run_image_oriented(m_ctx, framesDev, nFrames, &desc, rows, cols, m_orient), "acf_hip_run_image_oriented");
     }
-    else if (resized)
-    {
-        check(m_api->acf_hip_run_image_resized(m_ctx, framesDev, nFrames, &desc, rows, cols, double(inputScale())), "acf_hip_run_image_resized");
-    }
-    else
-    {
-        check(m_api->acf_hip_run_image(m_ctx, framesDev, nFrames, &desc), "acf_hip_run_image");
-    }
     fetchBatch(nFrames, resized, objects, scores);
     return 0;
-}
-
-static bool isDefaultVideoFormat(const acf_hip_yuv_format& f)
-{
-    return f.bits == 8 && f.shift == 0 && f.matrix == ACF_HIP_YUV_MATRIX_BT601 && f.full_range == 0;
 }
 
 int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc& desc, std::vector<RectVec>& objects,
@@ -677,29 +665,10 @@ int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int co
     const bool oriented = orientedPlan(rows, cols, resized, planRows, planCols);
     ensurePlan(planRows, planCols, 3, nFrames);
     syncNms();
-    if (!isDefaultVideoFormat(m_videoFormat)) // (the default format takes the entries below: acf_hip_run_video would forward to them)
-    {
-        check(m_api->acf_hip_run_video(m_ctx, baseDev, nFrames, &desc, &m_videoFormat, (oriented || resized) ? rows : 0, (oriented || resized) ? cols : 0,
-                  oriented ? m_orient : 0, resized ? double(inputScale()) : 0.0),
-            "acf_hip_run_video");
-    }
-    else if (oriented && resized) // (fetchBatch unscales: boxes in the upright full-size frame)
-    {
-        check(m_api->acf_hip_run_yuv_oriented_resized(m_ctx, baseDev, nFrames, &desc, rows, cols, m_orient, double(inputScale())),
-            "acf_hip_run_yuv_oriented_resized");
-    }
-    else if (oriented) // (boxes in the upright frame)
-    {
-        check(m_api->acf_hip_run_yuv_oriented(m_ctx, baseDev, nFrames, &desc, rows, cols, m_orient), "acf_hip_run_yuv_oriented");
-    }
-    else if (resized)
-    {
-        check(m_api->acf_hip_run_yuv_resized(m_ctx, baseDev, nFrames, &desc, rows, cols, double(inputScale())), "acf_hip_run_yuv_resized");
-    }
-    else
-    {
-        check(m_api->acf_hip_run_yuv(m_ctx, baseDev, nFrames, &desc), "acf_hip_run_yuv");
-    }
+    // the general entry: 0 sizes for upright frames of the plan's size, scale 0 for no resize (boxes in the upright frame; fetchBatch unscales)
+    check(m_api->acf_hip_run_video(m_ctx, baseDev, nFrames, &desc, &m_videoFormat, (oriented || resized) ? rows : 0, (oriented || resized) ? cols : 0,
+              oriented ? m_orient : 0, resized ? double(inputScale()) : 0.0),
+        "acf_hip_run_video");
     fetchBatch(nFrames, resized, objects, scores);
     return 0;
 }
@@ -820,32 +789,10 @@ void HipDetector::streamOpenYuv(int rows, int cols, const acf_hip_yuv_desc& desc
     check(m_api->acf_hip_set_input_resize(m_ctx, 0, 0, 1.0), "acf_hip_set_input_resize");
     m_srcRows = rows;
     m_srcCols = cols;
-    if (!isDefaultVideoFormat(m_videoFormat))
-    {
-        check(m_api->acf_hip_stream_open_video(m_ctx, &desc, &m_videoFormat, int64_t(frameBytes), (oriented || resized) ? rows : 0, (oriented || resized) ? cols : 0,
-                  oriented ? m_orient : 0, resized ? double(inputScale()) : 0.0, maxDetectionsPerFrame, depth),
-            "acf_hip_stream_open_video");
-    }
-    else if (oriented && resized) // (streamCollect maps the boxes back to the upright full-size frame)
-    {
-        check(m_api->acf_hip_stream_open_yuv_oriented_resized(m_ctx, &desc, int64_t(frameBytes), rows, cols, m_orient, double(inputScale()), maxDetectionsPerFrame,
-                  depth),
-            "acf_hip_stream_open_yuv_oriented_resized");
-    }
-    else if (oriented) // (streamCollect returns boxes in the upright frame)
-    {
-        check(m_api->acf_hip_stream_open_yuv_oriented(m_ctx, &desc, int64_t(frameBytes), rows, cols, m_orient, maxDetectionsPerFrame, depth),
-            "acf_hip_stream_open_yuv_oriented");
-    }
-    else if (resized) // (streamCollect maps the boxes back)
-    {
-        check(m_api->acf_hip_stream_open_yuv_resized(m_ctx, &desc, int64_t(frameBytes), rows, cols, double(inputScale()), maxDetectionsPerFrame, depth),
-            "acf_hip_stream_open_yuv_resized");
-    }
-    else
-    {
-        check(m_api->acf_hip_stream_open_yuv(m_ctx, &desc, int64_t(frameBytes), maxDetectionsPerFrame, depth), "acf_hip_stream_open_yuv");
-    }
+    // (streamCollect maps the boxes back to the upright full-size frame)
+    check(m_api->acf_hip_stream_open_video(m_ctx, &desc, &m_videoFormat, int64_t(frameBytes), (oriented || resized) ? rows : 0, (oriented || resized) ? cols : 0,
+              oriented ? m_orient : 0, resized ? double(inputScale()) : 0.0, maxDetectionsPerFrame, depth),
+        "acf_hip_stream_open_video");
     m_streamCap = maxDetectionsPerFrame;
     m_streamPix = -1; // (operator()(packed) reopens its own stream)
     m_streamStride = 0;

@@ -589,7 +589,8 @@ ACF_HIP_API int acf_hip_stream_open_yuv_resized(acf_hip_ctx* ctx, const acf_hip_
  *   YUV    acf_hip_yuv_to_rgb8's R, G, B of the source frame (the chroma sample of source pixel (rs, cs) at (rs >> sub_y, cs >> sub_x):
  *          chosen in SOURCE coordinates) re-arranged into U, then acf_hip_pyramid_u8 / run_u8 (ACF_HIP_PIX_RGB)
  * every plane, level, hit, score bit and box, option "arith" = 1 included.  Detections are in U's coordinates; acf_hip_unorient_rect
- * maps a box back to the source frame.  ACF_HIP_ORIENT_UPRIGHT is the un-oriented entry itself: the call forwards to it.
+ * maps a box back to the source frame.  ACF_HIP_ORIENT_UPRIGHT is the un-oriented entry's call: the same kernels under the same profile
+ * names (every entry of a kind is one call of the library's general entry of that kind; none calls another).
  * acf_hip_image_extent / acf_hip_yuv_extent called with src_rows x src_cols give exactly the elements and bytes an oriented call
  * reads (an orientation permutes the same pixel set), and no load covers an address outside the [first, last] span of the row and
  * plane it belongs to.
@@ -650,7 +651,7 @@ ACF_HIP_API int acf_hip_unorient_rect(int orient, int src_rows, int src_cols, co
  * The plan must be for acf_hip_oriented_resized_dims(src_rows, src_cols, orient, scale) = acf_hip_resize_dims(acf_hip_oriented_dims(...)).
  * Detections are in the reduced upright frame: cv::Rect2f(o) * (1.f / scale) first, then acf_hip_unorient_rect.  cv::resize and cvtColor
  * are OpenCV's (not part of the reference tree): their published arithmetic is restated; PARITY UNPINNED.
- * ACF_HIP_ORIENT_UPRIGHT forwards to the *_resized entry.  acf_hip_image_extent / acf_hip_yuv_extent at src_rows x src_cols give the
+ * ACF_HIP_ORIENT_UPRIGHT is the *_resized entry's call.  acf_hip_image_extent / acf_hip_yuv_extent at src_rows x src_cols give the
  * bytes that may be read, and no load covers an address outside the [first, last] span of the row and plane it belongs to.
  * Option "profile": k_ingest_oriented_resized_image / k_ingest_oriented_resized_yuv for quarter turns (odd rot) at scales >= 1 / 4 — the
  * tile's footprint in the stored frame is read along the stored rows into LDS (dword loads for descriptions that meet the un-oriented
@@ -716,8 +717,9 @@ ACF_HIP_API int acf_hip_oriented_resized_dims(int src_rows, int src_cols, int or
  * OpenCV has no counterpart beyond BT.601 8-bit: PARITY UNPINNED; the matrices are H.273's.
  *  acf_hip_pyramid_video / run_video   scale 0: no resize, the plan is for acf_hip_oriented_dims(src_rows, src_cols, orient); otherwise
  *                            for acf_hip_oriented_resized_dims(...).  orient 0 with scale 0 is the plain entry (src_rows = src_cols = 0:
- *                            the plan's size).  With the default format the call FORWARDS to the existing entry of its family
- *                            (acf_hip_run_yuv, _oriented, _resized, _oriented_resized): the same kernels under the same profile names.
+ *                            the plan's size).  This is the general YUV entry: acf_hip_run_yuv, _oriented, _resized and _oriented_resized
+ *                            are this call with the default format and what they do not state left 0, so the default format runs
+ *                            the same kernels under the same profile names as they do.
  *                            Other 8-bit formats run the same kernels with the constants as an argument (the profile names stay; an
  *                            NV12 / NV21-shaped descriptor still runs k_ingest_yuv420).  More than 8 bits: k_ingest_yuv16, one kernel with
  *                            three load forms chosen from the descriptor and base_dev's alignment alone, all giving the same bits:

@@ -1,5 +1,6 @@
 """What the input entries refuse, entry by entry: the 8-bit, tensor and YUV entries, their resized forms, the three stream_open calls
-and the settings in front of them (set_input_resize, set_yuv_layout, yuv_to_rgb8).
+and the settings in front of them (set_input_resize, set_yuv_layout, yuv_to_rgb8); then the oriented, the oriented resized and the video
+entries and their three stream_open calls (FAMILY_ROWS), which are called by their C names so that a row says which entry it enters.
 
 One table.  A row is a bad call, the error code it returns and a piece of the message it leaves: the entry's name and the reason, as
 the library words them.  A call that is wrong in two ways names the check that comes first.  Nothing is launched for a refused call;
@@ -19,7 +20,8 @@ NAN, INF = float("nan"), float("inf")
 
 
 class Ctxs:
-    """The contexts of the table, made once: three-plane, one-plane, five-plane, an odd-sized plan, sub-batch streams."""
+    """The contexts of the table, made once: three-plane, one-plane, five-plane, an odd-sized plan, sub-batch streams, and a three-plane
+    one whose plan is the quarter turn of the others' (128 x 96)."""
 
     def __init__(self):
         import torch
@@ -36,10 +38,13 @@ class Ctxs:
         self.five = HipDetector(self.tiny, PH, PW, 5, max_batch=2)
         self.odd = HipDetector(self.tiny, PH + 1, PW, 3, max_batch=2)
         self.multi = HipDetector(self.tiny, PH, PW, 3, max_batch=4, streams=2)
+        self.turn = HipDetector(self.tiny, PW, PH, 3, max_batch=2)
         self.yuv, self.fb = HipDetector.yuv_desc("i420", PH, PW)
         self.yuvS, self.fbS = HipDetector.yuv_desc("i420", SH, SW)
         self.img = capi.ImageDesc(capi.T_U8, 3, 3 * PH * PW, PH * PW, PW, 1)
         self.imgS = capi.ImageDesc(capi.T_U8, 3, 3 * SH * SW, SH * SW, SW, 1)
+        self.f709, self.f10 = capi.YuvFormat(8, 0, capi.YUV_MATRIX_BT709, 0), capi.YuvFormat(10, 6, capi.YUV_MATRIX_BT2020, 0)
+        self.yuv10, self.fb10 = HipDetector.video_desc("nv12", PH, PW, self.f10)
 
     def bare(self):
         return self.D(self.tiny)
@@ -55,7 +60,7 @@ class Ctxs:
         det.synchronize()
 
     def close(self):
-        for d in (self.three, self.one, self.five, self.odd, self.multi):
+        for d in (self.three, self.one, self.five, self.odd, self.multi, self.turn):
             d.close()
 
 
@@ -315,6 +320,377 @@ ROWS = [
     ("stream_yuv_resized_stride_n", "three", lambda k, d: d.stream_open_yuv_resized(yuv(k.yuvS, v_stride_n=k.fbS + 4), k.fbS, SH, SW, SCALE, 64, 2), INV,
      "stream_open_yuv_resized: stride_n of every plane must be frame_bytes", None),
 ]
+
+
+# ---- the oriented, the oriented resized and the video families, by their C names.  An argument is a value or a function of the contexts.
+def ent(fn, *args):
+    return lambda k, d: raw(d, "acf_hip_" + fn, *[a(k) if callable(a) else a for a in args])
+
+
+PTR = lambda k: P(k.ptr)
+ODD = lambda k: P(k.ptr + 1)
+I, IS = (lambda k: C.byref(k.img)), (lambda k: C.byref(k.imgS))
+Y, YS, Y10 = (lambda k: C.byref(k.yuv)), (lambda k: C.byref(k.yuvS)), (lambda k: C.byref(k.yuv10))
+FB, FBS, FB10 = (lambda k: k.fb), (lambda k: k.fbS), (lambda k: k.fb10)
+F709, F10 = (lambda k: C.byref(k.f709)), (lambda k: C.byref(k.f10))
+
+
+def ydesc(which, **kw):
+    return lambda k: C.byref(yuv(getattr(k, which), **{f: (v(k) if callable(v) else v) for f, v in kw.items()}))
+
+
+def idesc(which, **kw):
+    return lambda k: C.byref(image(getattr(k, which), **kw))
+
+
+def fmt(*v):
+    return lambda k: C.byref(capi.YuvFormat(*(list(v) + [0, 0, 0])[:4]))
+
+
+ORIENT = "orient must be 0 .. 7 (ACF_HIP_ORIENT_*), src_rows and src_cols >= 1"
+UPRIGHT = "the plan must be for the upright size (acf_hip_oriented_dims of the frame size and orientation)"
+REDUCED = "the plan must be for the reduced size (acf_hip_resize_dims of the frame size and scale)"
+SIZE_SCALE = "src_rows and src_cols >= 1, scale a positive finite number"
+VSCALE = "scale must be 0 (no resize) or a positive finite number"
+WIDE = "more than 8 bits a sample: upright and unreduced frames only (orient 0, scale 0)"
+STREAMS = "not available with option \"streams\" > 1"
+FRAMES = "pyramid: n_frames out of range"
+RZ_YUV = "not with acf_hip_set_input_resize (the resize takes the 8-bit entries' frames)"
+RZ_IMAGE = "not with acf_hip_set_input_resize (the resize takes packed 8-bit frames)"
+RZ_SELF = "not with acf_hip_set_input_resize (the entry resizes by itself)"
+YUV_PLANES = "the plan's input planes (d) must be 3"
+OPEN_PLANES = "the plan's input planes (d) must be 3, and not with acf_hip_set_input_resize"
+IMAGE_FIVE = "a plan for five input planes (image + M, O) takes planar float frames"
+CHANNELS = "channels must be the plan's input planes (d)"
+DEPTH = "depth must be 2..8, cap > 0"
+INSIDE = "every plane of a frame must lie in [0, frame_bytes)"
+STRIDE_N = "stride_n of every plane must be frame_bytes"
+EVEN = "16-bit samples need even offsets and strides"
+BAD_FORMATS = [((7,), "bits must be 8 .. 16"), ((17,), "bits must be 8 .. 16"), ((8, 1), "shift must be 0 for 8 bits, and shift + bits <= 16"),
+               ((10, 7), "shift must be 0 for 8 bits, and shift + bits <= 16"), ((16, 1), "shift must be 0 for 8 bits, and shift + bits <= 16"),
+               ((8, 0, 3), "unknown matrix (ACF_HIP_YUV_MATRIX_*)"), ((8, 0, 0, 2), "full_range must be 0 or 1")]
+RZ = (rz_on, rz_off)
+FAMILY_ROWS = []
+
+
+def fam(prefix, who, rows):
+    """rows of (id, context, call, code, reason, around): the piece is `who: reason`, or the reason alone where who is None or the reason
+    names its entry itself (a forwarded call; "pyramid: ...")."""
+    for rid, ctx, call, code, reason, around in rows:
+        own = who is not None and not reason.startswith("pyramid: ")
+        FAMILY_ROWS.append((prefix + "_" + rid, ctx, call, code, (who + ": " + reason) if own else reason, around))
+
+
+def oriented(kind, fn, FR, D, dvar, null, planes_one, planes_five, rz_text, bad_desc, bad_text):
+    """acf_hip_run_<kind>_oriented(ctx, frames, n, desc, src_rows, src_cols, orient); FR: the frames, D: the description of 96 x 128 frames"""
+    e = lambda *a: ent(fn, *a)
+    who = "pyramid_%s_oriented" % kind
+    fam(kind + "_oriented", who, [
+        ("null_frames", "three", e(None, 1, D, PH, PW, 2), INV, null, None),
+        ("null_description", "three", ent(fn.replace("run_", "pyramid_"), FR, 1, None, PH, PW, 2), INV, null, None),
+        ("orient_below", "three", e(FR, 1, D, PH, PW, -1), INV, ORIENT, None),
+        ("orient_above", "three", e(FR, 1, D, PH, PW, 8), INV, ORIENT, None),
+        ("no_rows", "three", e(FR, 1, D, 0, PW, 2), INV, ORIENT, None),
+        ("negative_cols", "three", e(FR, 1, D, PH, -1, 2), INV, ORIENT, None),
+        ("size_code_1", "three", e(FR, 1, D, PH, PW, 1), INV, UPRIGHT, None),
+        ("size_code_2", "three", e(FR, 1, D, PH + 2, PW, 2), INV, UPRIGHT, None),
+        ("size_code_5_quarter_turn", "turn", e(FR, 1, D, PH, PW + 2, 5), INV, UPRIGHT, None),
+        ("one_plane", "one", e(FR, 1, D, PH, PW, 2), INV, planes_one, None),
+        ("five_planes", "five", e(FR, 1, D, PH, PW, 2), INV, planes_five, None),
+        ("with_input_resize", "three", e(FR, 1, D, PH, PW, 2), INV, rz_text, RZ),
+        ("streams", "multi", e(FR, 2, D, PH, PW, 2), UNS, STREAMS, None),
+        ("no_plan", "bare", e(FR, 1, D, PH, PW, 2), NOPLAN, "pyramid: plan first", None),
+        ("no_frames", "three", e(FR, 0, D, PH, PW, 2), INV, FRAMES, None),
+        ("too_many_frames", "turn", e(FR, 3, D, PH, PW, 1), INV, FRAMES, None),
+        ("orient_before_plan_first", "bare", e(FR, 1, D, PH, PW, 8), INV, ORIENT, None),
+        ("orient_before_null", "three", e(None, 1, D, PH, PW, -1), INV, ORIENT, None),
+        ("null_before_streams", "multi", e(None, 1, D, PH, PW, 2), INV, null, None),
+        ("streams_before_frames", "multi", e(FR, 0, D, PH, PW, 2), UNS, STREAMS, None),
+        ("frames_before_description", "three", e(FR, 3, bad_desc, PH, PW, 2), INV, FRAMES, None),
+        ("description_before_planes", "five", e(FR, 1, bad_desc, PH, PW, 2), INV, bad_text, None),
+        ("planes_before_input_resize", "one", e(FR, 1, D, PH, PW, 2), INV, planes_one, RZ),
+        ("input_resize_before_size", "three", e(FR, 1, D, PH + 2, PW, 2), INV, rz_text, RZ),
+    ])
+    fam(kind + "_oriented_code_0", None, [   # (code 0 is the un-oriented entry, whichever name the message carries)
+        ("size", "three", e(FR, 1, D, PH + 2, PW, 0), INV, UPRIGHT, None),
+        ("one_plane", "one", e(FR, 1, D, PH, PW, 0), INV, planes_one, None),
+        ("with_input_resize", "three", e(FR, 1, D, PH, PW, 0), INV, rz_text, RZ),
+    ])
+
+
+def oriented_resized(kind, fn, FR, D, dvar, null, planes_one, planes_five, bad_desc, bad_text):
+    """acf_hip_run_<kind>_oriented_resized(ctx, frames, n, desc, src_rows, src_cols, orient, scale); D: the description of 192 x 256 frames"""
+    e = lambda *a: ent(fn, *a)
+    who = "pyramid_%s_oriented_resized" % kind
+    fam(kind + "_oriented_resized", who, [
+        ("null_frames", "three", e(None, 1, D, SH, SW, 2, SCALE), INV, null, None),
+        ("null_description", "three", ent(fn.replace("run_", "pyramid_"), FR, 1, None, SH, SW, 2, SCALE), INV, null, None),
+        ("orient_below", "three", e(FR, 1, D, SH, SW, -1, SCALE), INV, ORIENT, None),
+        ("orient_above", "three", e(FR, 1, D, SH, SW, 8, SCALE), INV, ORIENT, None),
+        ("no_rows", "three", e(FR, 1, D, 0, SW, 2, SCALE), INV, ORIENT, None),
+        ("negative_cols", "three", e(FR, 1, D, SH, -1, 2, SCALE), INV, ORIENT, None),
+        ("size_code_1", "three", e(FR, 1, D, SH, SW, 1, SCALE), INV, REDUCED, None),
+        ("size_code_2", "three", e(FR, 1, D, SH + 2, SW, 2, SCALE), INV, REDUCED, None),
+        ("size_code_7_quarter_turn", "turn", e(FR, 1, D, SH, SW + 2, 7, SCALE), INV, REDUCED, None),
+        ("nan_scale", "three", e(FR, 1, D, SH, SW, 2, NAN), INV, SIZE_SCALE, None),
+        ("negative_scale", "three", e(FR, 1, D, SH, SW, 2, -0.5), INV, SIZE_SCALE, None),
+        ("zero_scale", "three", e(FR, 1, D, SH, SW, 2, 0.0), INV, SIZE_SCALE, None),
+        ("other_plan", "three", e(FR, 1, D, SH, SW, 2, 0.75), INV, REDUCED, None),
+        ("one_plane", "one", e(FR, 1, D, SH, SW, 2, SCALE), INV, planes_one, None),
+        ("five_planes", "five", e(FR, 1, D, SH, SW, 2, SCALE), INV, planes_five, None),
+        ("with_input_resize", "three", e(FR, 1, D, SH, SW, 2, SCALE), INV, RZ_SELF, RZ),
+        ("streams", "multi", e(FR, 2, D, SH, SW, 2, SCALE), UNS, STREAMS, None),
+        ("no_plan", "bare", e(FR, 1, D, SH, SW, 2, SCALE), NOPLAN, "pyramid: plan first", None),
+        ("no_frames", "three", e(FR, 0, D, SH, SW, 2, SCALE), INV, FRAMES, None),
+        ("too_many_frames", "turn", e(FR, 3, D, SH, SW, 1, SCALE), INV, FRAMES, None),
+        ("orient_before_plan_first", "bare", e(FR, 1, D, SH, SW, 8, SCALE), INV, ORIENT, None),
+        ("orient_before_null", "three", e(None, 1, D, SH, SW, -1, SCALE), INV, ORIENT, None),
+        ("null_before_streams", "multi", e(None, 1, D, SH, SW, 2, SCALE), INV, null, None),
+        ("frames_before_description", "three", e(FR, 3, bad_desc, SH, SW, 2, SCALE), INV, FRAMES, None),
+        ("description_before_planes", "five", e(FR, 1, bad_desc, SH, SW, 2, SCALE), INV, bad_text, None),
+        ("planes_before_scale", "one", e(FR, 1, D, SH, SW, 2, NAN), INV, planes_one, None),
+        ("scale_before_input_resize", "three", e(FR, 1, D, SH, SW, 2, NAN), INV, SIZE_SCALE, RZ),
+        ("input_resize_before_the_plan", "three", e(FR, 1, D, SH + 2, SW, 2, SCALE), INV, RZ_SELF, RZ),
+    ])
+    fam(kind + "_oriented_resized_code_0", None, [   # (code 0 is the resized entry)
+        ("size", "three", e(FR, 1, D, SH + 2, SW, 0, SCALE), INV, REDUCED, None),
+        ("nan_scale", "three", e(FR, 1, D, SH, SW, 0, NAN), INV, SIZE_SCALE, None),
+        ("one_plane", "one", e(FR, 1, D, SH, SW, 0, SCALE), INV, planes_one, None),
+        ("with_input_resize", "three", e(FR, 1, D, SH, SW, 0, SCALE), INV, RZ_SELF, RZ),
+    ])
+
+
+NULL_IMAGE, NULL_YUV = "null frames or description", "null base or description"
+oriented("image", "run_image_oriented", PTR, I, "img", NULL_IMAGE, CHANNELS, IMAGE_FIVE, RZ_IMAGE, idesc("img", stride_y=-3), "stride_x and stride_y must be positive")
+oriented("yuv", "run_yuv_oriented", PTR, Y, "yuv", NULL_YUV, YUV_PLANES, YUV_PLANES, RZ_YUV, ydesc("yuv", sub_y=-1), "sub_x and sub_y must be 0 or 1")
+oriented_resized("image", "run_image_oriented_resized", PTR, IS, "imgS", NULL_IMAGE, CHANNELS, IMAGE_FIVE, idesc("imgS", stride_y=-3),
+                 "stride_x and stride_y must be positive")
+oriented_resized("yuv", "run_yuv_oriented_resized", PTR, YS, "yuvS", NULL_YUV, YUV_PLANES, YUV_PLANES, ydesc("yuvS", sub_y=-1), "sub_x and sub_y must be 0 or 1")
+DTYPE = "dtype must be ACF_HIP_T_U8 (cv::resize's CV_32F arithmetic is not restated)"
+fam("image_oriented_resized", "pyramid_image_oriented_resized", [
+    ("f16", "three", ent("run_image_oriented_resized", PTR, 1, idesc("imgS", dtype=capi.T_F16), SH, SW, 2, SCALE), UNS, DTYPE, None),
+    ("channels_before_dtype", "one", ent("run_image_oriented_resized", PTR, 1, idesc("imgS", dtype=capi.T_F16), SH, SW, 2, SCALE), INV, CHANNELS, None),
+    ("dtype_before_scale", "three", ent("pyramid_image_oriented_resized", PTR, 1, idesc("imgS", dtype=capi.T_F32), SH, SW, 2, NAN), UNS, DTYPE, None),
+    ("orient_before_dtype", "three", ent("run_image_oriented_resized", PTR, 1, idesc("imgS", dtype=capi.T_F32), SH, SW, 9, SCALE), INV, ORIENT, None),
+])
+
+
+def video(tag, FM, D, FR):
+    """acf_hip_pyramid_video / run_video(ctx, base, n, desc, fmt, src_rows, src_cols, orient, scale) with a format other than the default:
+    the rows the 8-bit and the 10-bit format share.  Plain: sizes 0, orient 0, scale 0."""
+    e = lambda *a: ent("run_video", *a)
+    p = lambda *a: ent("pyramid_video", *a)
+    fam("video_" + tag, "pyramid_video", [
+        ("null_base", "three", e(None, 1, D, FM, 0, 0, 0, 0.0), INV, NULL_YUV, None),
+        ("null_description", "three", p(FR, 1, None, FM, 0, 0, 0, 0.0), INV, NULL_YUV, None),
+        ("no_rows", "three", e(FR, 1, D, FM, 0, PW, 0, 0.0), INV, ORIENT, None),
+        ("negative_cols", "three", e(FR, 1, D, FM, PH, -1, 0, 0.0), INV, ORIENT, None),
+        ("size_code_0", "three", e(FR, 1, D, FM, PH + 2, PW, 0, 0.0), INV, UPRIGHT, None),
+        ("nan_scale", "three", p(FR, 1, D, FM, SH, SW, 0, NAN), INV, VSCALE, None),
+        ("negative_scale", "three", p(FR, 1, D, FM, SH, SW, 0, -0.5), INV, VSCALE, None),
+        ("inf_scale", "three", p(FR, 1, D, FM, 0, 0, 0, INF), INV, VSCALE, None),
+        ("one_plane", "one", e(FR, 1, D, FM, 0, 0, 0, 0.0), INV, YUV_PLANES, None),
+        ("five_planes", "five", e(FR, 1, D, FM, 0, 0, 0, 0.0), INV, YUV_PLANES, None),
+        ("with_input_resize", "three", e(FR, 1, D, FM, 0, 0, 0, 0.0), INV, RZ_YUV, RZ),
+        ("streams", "multi", e(FR, 2, D, FM, 0, 0, 0, 0.0), UNS, STREAMS, None),
+        ("no_plan", "bare", e(FR, 1, D, FM, 0, 0, 0, 0.0), NOPLAN, "pyramid: plan first", None),
+        ("no_frames", "three", e(FR, 0, D, FM, 0, 0, 0, 0.0), INV, FRAMES, None),
+        ("too_many_frames", "three", p(FR, 3, D, FM, PH, PW, 0, 0.0), INV, FRAMES, None),
+        ("scale_before_orient", "three", p(FR, 1, D, FM, PH, PW, 8, NAN), INV, VSCALE, None),
+        ("orient_before_null", "three", e(None, 1, D, FM, 0, PW, 0, 0.0), INV, ORIENT, None),
+        ("scale_before_plan_first", "bare", p(FR, 1, D, FM, 0, 0, 0, -1.0), INV, VSCALE, None),
+        ("null_before_streams", "multi", e(None, 1, D, FM, 0, 0, 0, 0.0), INV, NULL_YUV, None),
+        ("frames_before_description", "three", e(FR, 3, ydesc("yuv", sub_x=2), FM, 0, 0, 0, 0.0), INV, FRAMES, None),
+        ("description_before_planes", "five", e(FR, 1, ydesc("yuv", sub_x=2), FM, 0, 0, 0, 0.0), INV, "sub_x and sub_y must be 0 or 1", None),
+        ("planes_before_input_resize", "one", e(FR, 1, D, FM, 0, 0, 0, 0.0), INV, YUV_PLANES, RZ),
+    ])
+    fam("video_" + tag, "run_video", [   # (what run_video checks before it goes the way of pyramid_video names itself)
+        ("run_nan_scale", "three", e(FR, 1, D, FM, 0, 0, 0, NAN), INV, VSCALE, None),
+    ])
+
+
+video("bt709", F709, Y, PTR)
+video("10_bits", F10, Y10, PTR)
+fam("video_bt709", "pyramid_video", [
+    ("orient_below", "three", ent("run_video", PTR, 1, Y, F709, PH, PW, -1, 0.0), INV, ORIENT, None),
+    ("orient_above", "three", ent("run_video", PTR, 1, Y, F709, PH, PW, 8, 0.0), INV, ORIENT, None),
+    ("orient_above_reduced", "three", ent("run_video", PTR, 1, YS, F709, SH, SW, 8, SCALE), INV, ORIENT, None),
+    ("no_rows_reduced", "three", ent("run_video", PTR, 1, YS, F709, 0, SW, 0, SCALE), INV, ORIENT, None),
+    ("size_code_1", "three", ent("run_video", PTR, 1, Y, F709, PH, PW, 1, 0.0), INV, UPRIGHT, None),
+    ("size_code_2", "three", ent("run_video", PTR, 1, Y, F709, PH + 2, PW, 2, 0.0), INV, UPRIGHT, None),
+    ("size_code_3_quarter_turn", "turn", ent("run_video", PTR, 1, Y, F709, PH, PW + 2, 3, 0.0), INV, UPRIGHT, None),
+    ("other_plan", "three", ent("run_video", PTR, 1, YS, F709, SH, SW, 0, 0.75), INV, REDUCED, None),
+    ("other_plan_code_1", "three", ent("run_video", PTR, 1, YS, F709, SH, SW, 1, SCALE), INV, REDUCED, None),
+    ("reduced_with_input_resize", "three", ent("run_video", PTR, 1, YS, F709, SH, SW, 2, SCALE), INV, RZ_SELF, RZ),
+    ("turned_with_input_resize", "three", ent("run_video", PTR, 1, Y, F709, PH, PW, 2, 0.0), INV, RZ_YUV, RZ),
+    ("input_resize_before_size", "three", ent("run_video", PTR, 1, Y, F709, PH + 2, PW, 2, 0.0), INV, RZ_YUV, RZ),
+    ("orient_before_plan_first", "bare", ent("run_video", PTR, 1, Y, F709, PH, PW, 8, 0.0), INV, ORIENT, None),
+    ("planes_before_size", "one", ent("run_video", PTR, 1, Y, F709, PH + 2, PW, 2, 0.0), INV, YUV_PLANES, None),
+    ("planes_before_scale_tables", "one", ent("run_video", PTR, 1, YS, F709, SH, SW, 2, 0.75), INV, YUV_PLANES, None),
+] + [("format_%d" % i, "three", ent("pyramid_video", PTR, 1, Y, fmt(*f), 0, 0, 0, 0.0), INV, why, None) for i, (f, why) in enumerate(BAD_FORMATS)] + [
+    ("format_before_null", "three", ent("pyramid_video", None, 1, Y, fmt(7), 0, 0, 0, 0.0), INV, "bits must be 8 .. 16", None),
+    ("format_before_scale", "three", ent("pyramid_video", PTR, 1, Y, fmt(8, 0, 3), 0, 0, 0, NAN), INV, "unknown matrix (ACF_HIP_YUV_MATRIX_*)", None),
+    ("format_before_plan_first", "bare", ent("pyramid_video", PTR, 1, Y, fmt(17), 0, 0, 0, 0.0), INV, "bits must be 8 .. 16", None),
+])
+fam("video_bt709", "run_video", [("run_format", "three", ent("run_video", PTR, 1, Y, fmt(16, 1), 0, 0, 0, 0.0), INV, "shift must be 0 for 8 bits, and shift + bits <= 16", None)])
+fam("video_10_bits", "pyramid_video", [
+    ("odd_base", "three", ent("run_video", ODD, 1, Y10, F10, 0, 0, 0, 0.0), INV, "16-bit samples need an even base", None),
+    ("odd_offset", "three", ent("run_video", PTR, 1, ydesc("yuv10", y_offset=1), F10, 0, 0, 0, 0.0), INV, EVEN, None),
+    ("odd_stride_row", "three", ent("run_video", PTR, 1, ydesc("yuv10", u_stride_row=2 * PW + 1), F10, 0, 0, 0, 0.0), INV, EVEN, None),
+    ("odd_stride_n", "three", ent("pyramid_video", PTR, 1, ydesc("yuv10", v_stride_n=lambda k: k.fb10 + 1), F10, PH, PW, 0, 0.0), INV, EVEN, None),
+    ("odd_stride_px", "three", ent("run_video", PTR, 1, ydesc("yuv10", u_stride_px=3), F10, 0, 0, 0, 0.0), INV, EVEN, None),
+    ("turned", "turn", ent("pyramid_video", PTR, 1, Y10, F10, PH, PW, 1, 0.0), UNS, WIDE, None),
+    ("turned_half", "three", ent("pyramid_video", PTR, 1, Y10, F10, PH, PW, 2, 0.0), UNS, WIDE, None),
+    ("reduced", "three", ent("pyramid_video", PTR, 1, Y10, F10, SH, SW, 0, SCALE), UNS, WIDE, None),
+    ("orient_below", "three", ent("pyramid_video", PTR, 1, Y10, F10, PH, PW, -1, 0.0), UNS, WIDE, None),
+    ("orient_above", "three", ent("pyramid_video", PTR, 1, Y10, F10, PH, PW, 8, 0.0), UNS, WIDE, None),
+    ("other_plan", "three", ent("pyramid_video", PTR, 1, Y10, F10, SH, SW, 0, 0.75), UNS, WIDE, None),
+    ("turned_before_the_size", "three", ent("pyramid_video", PTR, 1, Y10, F10, 0, PW, 2, 0.0), UNS, WIDE, None),
+    ("turned_before_plan_first", "bare", ent("pyramid_video", PTR, 1, Y10, F10, PH, PW, 2, 0.0), UNS, WIDE, None),
+    ("scale_before_turned", "three", ent("pyramid_video", PTR, 1, Y10, F10, PH, PW, 1, NAN), INV, VSCALE, None),
+    ("planes_before_even", "one", ent("run_video", PTR, 1, ydesc("yuv10", y_offset=1), F10, 0, 0, 0, 0.0), INV, YUV_PLANES, None),
+    ("description_before_even", "three", ent("run_video", PTR, 1, ydesc("yuv10", y_offset=1, sub_x=2), F10, 0, 0, 0, 0.0), INV, "sub_x and sub_y must be 0 or 1", None),
+    ("even_before_input_resize", "three", ent("run_video", PTR, 1, ydesc("yuv10", y_offset=1), F10, 0, 0, 0, 0.0), INV, EVEN, RZ),
+])
+fam("video_default_format", None, [   # (the default format is the YUV entry of the call's family)
+    ("orient_above", "three", ent("run_video", PTR, 1, Y, None, PH, PW, 8, 0.0), INV, ORIENT, None),
+    ("size", "three", ent("run_video", PTR, 1, Y, None, PH + 2, PW, 0, 0.0), INV, UPRIGHT, None),
+    ("one_plane", "one", ent("run_video", PTR, 1, Y, None, 0, 0, 0, 0.0), INV, YUV_PLANES, None),
+    ("reduced_nan_scale", "three", ent("pyramid_video", PTR, 1, YS, None, SH, SW, 0, NAN), INV, VSCALE, None),
+    ("other_plan", "three", ent("run_video", PTR, 1, YS, None, SH, SW, 2, 0.75), INV, REDUCED, None),
+])
+
+
+def opens(tag, who, o, D, DV, fbytes, rows, cols, resized):
+    """The rows the three stream_open calls of these families share.  o(desc, frame_bytes, rows, cols, orient, cap, depth): the call;
+    D / DV: the description and its name in the contexts; rows x cols: the frames."""
+    size_text = REDUCED if resized else UPRIGHT
+    fam(tag, who, [
+        ("null_description", "three", o(None, fbytes, rows, cols, 2, 64, 2), INV, "null description", None),
+        ("orient_below", "three", o(D, fbytes, rows, cols, -1, 64, 2), INV, ORIENT, None),
+        ("orient_above", "three", o(D, fbytes, rows, cols, 8, 64, 2), INV, ORIENT, None),
+        ("no_rows", "three", o(D, fbytes, 0, cols, 2, 64, 2), INV, ORIENT, None),
+        ("negative_cols", "three", o(D, fbytes, rows, -1, 2, 64, 2), INV, ORIENT, None),
+        ("size_code_1", "three", o(D, fbytes, rows, cols, 1, 64, 2), INV, size_text, None),
+        ("size_code_2", "three", o(D, fbytes, rows + 2, cols, 2, 64, 2), INV, size_text, None),
+        ("size_code_1_quarter_turn", "turn", o(D, fbytes, rows, cols + 2, 1, 64, 2), INV, size_text, None),
+        ("one_plane", "one", o(D, fbytes, rows, cols, 2, 64, 2), INV, OPEN_PLANES, None),
+        ("five_planes", "five", o(D, fbytes, rows, cols, 2, 64, 2), INV, OPEN_PLANES, None),
+        ("with_input_resize", "three", o(D, fbytes, rows, cols, 2, 64, 2), INV, OPEN_PLANES, RZ),
+        ("streams", "multi", o(D, fbytes, rows, cols, 2, 64, 2), UNS, STREAMS, None),
+        ("no_plan", "bare", o(D, fbytes, rows, cols, 2, 64, 2), NOPLAN, "plan first", None),
+        ("depth", "three", o(D, fbytes, rows, cols, 2, 64, 9), INV, DEPTH, None),
+        ("cap", "three", o(D, fbytes, rows, cols, 2, 0, 2), INV, DEPTH, None),
+        ("plane_outside", "three", o(D, lambda k: fbytes(k) - 1, rows, cols, 2, 64, 2), INV, INSIDE, None),
+        ("plane_below", "three", o(ydesc(DV, v_offset=-8), fbytes, rows, cols, 2, 64, 2), INV, INSIDE, None),
+        ("stride_n", "three", o(ydesc(DV, y_stride_n=lambda k: fbytes(k) + 4), fbytes, rows, cols, 2, 64, 2), INV, STRIDE_N, None),
+        ("plan_first_before_orient", "bare", o(D, fbytes, rows, cols, 8, 64, 2), NOPLAN, "plan first", None),
+        ("streams_before_depth", "multi", o(D, fbytes, rows, cols, 2, 64, 9), UNS, STREAMS, None),
+        ("depth_before_description", "three", o(ydesc(DV, sub_x=2), fbytes, rows, cols, 2, 0, 2), INV, DEPTH, None),
+        ("description_before_planes", "five", o(ydesc(DV, sub_x=2), fbytes, rows, cols, 2, 64, 2), INV, "sub_x and sub_y must be 0 or 1", None),
+        ("planes_before_extent", "one", o(D, lambda k: fbytes(k) - 1, rows, cols, 2, 64, 2), INV, OPEN_PLANES, None),
+        ("extent_before_stride_n", "three", o(ydesc(DV, u_stride_n=lambda k: fbytes(k) + 4, v_offset=fbytes), fbytes, rows, cols, 2, 64, 2), INV, INSIDE, None),
+    ])
+
+
+o_oriented = lambda d, fb, r, c, o, cap, depth: ent("stream_open_yuv_oriented", d, fb, r, c, o, cap, depth)
+o_oriented_resized = lambda d, fb, r, c, o, cap, depth, s=SCALE: ent("stream_open_yuv_oriented_resized", d, fb, r, c, o, s, cap, depth)
+o_video = lambda d, fb, r, c, o, cap, depth, f=F709, s=0.0: ent("stream_open_video", d, f, fb, r, c, o, s, cap, depth)
+o_video_reduced = lambda d, fb, r, c, o, cap, depth: o_video(d, fb, r, c, o, cap, depth, F709, SCALE)
+opens("stream_open_yuv_oriented", "stream_open_yuv_oriented", o_oriented, Y, "yuv", FB, PH, PW, False)
+opens("stream_open_yuv_oriented_resized", "stream_open_yuv_oriented_resized", o_oriented_resized, YS, "yuvS", FBS, SH, SW, True)
+opens("stream_open_video_bt709", "stream_open_video", o_video, Y, "yuv", FB, PH, PW, False)
+opens("stream_open_video_bt709_reduced", "stream_open_video", o_video_reduced, YS, "yuvS", FBS, SH, SW, True)
+W_O, W_OR, W_V = "stream_open_yuv_oriented", "stream_open_yuv_oriented_resized", "stream_open_video"
+fam(W_O, W_O, [
+    ("size_code_0", "three", o_oriented(Y, FB, PH + 2, PW, 0, 64, 2), INV, UPRIGHT, None),
+    ("orient_before_streams", "multi", o_oriented(Y, FB, PH, PW, 8, 64, 2), INV, ORIENT, None),
+    ("size_before_streams", "multi", o_oriented(Y, FB, PH + 2, PW, 2, 64, 2), INV, UPRIGHT, None),
+    ("size_before_depth", "three", o_oriented(Y, FB, PH + 2, PW, 2, 64, 9), INV, UPRIGHT, None),
+])
+fam(W_OR, W_OR, [
+    ("nan_scale", "three", o_oriented_resized(YS, FBS, SH, SW, 2, 64, 2, NAN), INV, SIZE_SCALE, None),
+    ("negative_scale", "three", o_oriented_resized(YS, FBS, SH, SW, 2, 64, 2, -0.5), INV, SIZE_SCALE, None),
+    ("zero_scale", "three", o_oriented_resized(YS, FBS, SH, SW, 2, 64, 2, 0.0), INV, SIZE_SCALE, None),
+    ("other_plan", "three", o_oriented_resized(YS, FBS, SH, SW, 2, 64, 2, 0.75), INV, REDUCED, None),
+    ("orient_before_streams", "multi", o_oriented_resized(YS, FBS, SH, SW, 8, 64, 2), INV, ORIENT, None),
+    ("planes_before_scale", "one", o_oriented_resized(YS, FBS, SH, SW, 2, 64, 2, NAN), INV, OPEN_PLANES, None),
+    ("plan_before_the_extent", "three", o_oriented_resized(YS, lambda k: k.fbS - 1, SH + 2, SW, 2, 64, 2), INV, REDUCED, None),
+    ("room_for_the_plan_size_only", "three",
+     o_oriented_resized(ydesc("yuvS", y_stride_n=FB, u_stride_n=FB, v_stride_n=FB), FB, SH, SW, 2, 64, 2), INV, INSIDE, None),
+])
+fam(W_OR + "_code_0", None, [   # (code 0 is stream_open_yuv_resized)
+    ("size", "three", o_oriented_resized(YS, FBS, SH + 2, SW, 0, 64, 2), INV, REDUCED, None),
+    ("nan_scale", "three", o_oriented_resized(YS, FBS, SH, SW, 0, 64, 2, NAN), INV, SIZE_SCALE, None),
+    ("one_plane", "one", o_oriented_resized(YS, FBS, SH, SW, 0, 64, 2), INV, OPEN_PLANES, None),
+    ("plane_outside", "three", o_oriented_resized(YS, lambda k: k.fbS - 1, SH, SW, 0, 64, 2), INV, INSIDE, None),
+])
+fam(W_V + "_bt709", W_V, [
+    ("null_description_plain", "three", o_video(None, FB, 0, 0, 0, 64, 2), INV, "null description", None),
+    ("size_code_0", "three", o_video(Y, FB, PH + 2, PW, 0, 64, 2), INV, UPRIGHT, None),
+    ("nan_scale", "three", o_video(YS, FBS, SH, SW, 0, 64, 2, F709, NAN), INV, VSCALE, None),
+    ("negative_scale", "three", o_video(YS, FBS, SH, SW, 0, 64, 2, F709, -0.5), INV, VSCALE, None),
+    ("other_plan", "three", o_video(YS, FBS, SH, SW, 0, 64, 2, F709, 0.75), INV, REDUCED, None),
+    ("plain_one_plane", "one", o_video(Y, FB, 0, 0, 0, 64, 2), INV, OPEN_PLANES, None),
+    ("plain_streams", "multi", o_video(Y, FB, 0, 0, 0, 64, 2), UNS, STREAMS, None),
+    ("plain_plane_outside", "three", o_video(Y, lambda k: k.fb - 1, 0, 0, 0, 64, 2), INV, INSIDE, None),
+    ("plain_stride_n", "three", o_video(ydesc("yuv", v_stride_n=lambda k: k.fb + 4), FB, 0, 0, 0, 64, 2), INV, STRIDE_N, None),
+    ("plan_first_before_format", "bare", o_video(Y, FB, 0, 0, 0, 64, 2, fmt(7)), NOPLAN, "plan first", None),
+    ("format_before_scale", "three", o_video(Y, FB, 0, 0, 0, 64, 2, fmt(8, 0, 0, 2), NAN), INV, "full_range must be 0 or 1", None),
+    ("format_before_streams", "multi", o_video(Y, FB, 0, 0, 0, 64, 2, fmt(17)), INV, "bits must be 8 .. 16", None),
+    ("scale_before_streams", "multi", o_video(Y, FB, 0, 0, 0, 64, 2, F709, NAN), INV, VSCALE, None),
+    ("scale_before_orient", "three", o_video(Y, FB, PH, PW, 8, 64, 2, F709, -1.0), INV, VSCALE, None),
+    ("size_before_depth", "three", o_video(Y, FB, PH + 2, PW, 2, 64, 9), INV, UPRIGHT, None),
+    ("planes_before_scale_tables", "one", o_video(YS, FBS, SH, SW, 2, 64, 2, F709, 0.75), INV, OPEN_PLANES, None),
+    ("streams_before_orient", "multi", o_video(Y, FB, PH, PW, 8, 64, 2), UNS, STREAMS, None),
+    ("streams_before_orient_below", "multi", o_video(Y, FB, PH, PW, -1, 64, 2), UNS, STREAMS, None),
+    ("streams_before_no_rows", "multi", o_video(Y, FB, 0, PW, 2, 64, 2), UNS, STREAMS, None),
+    ("streams_before_size", "multi", o_video(Y, FB, PH + 2, PW, 2, 64, 2), UNS, STREAMS, None),
+    ("streams_before_size_code_0", "multi", o_video(Y, FB, PH + 2, PW, 0, 64, 2), UNS, STREAMS, None),
+    ("streams_before_orient_reduced", "multi", o_video(YS, FBS, SH, SW, 8, 64, 2, F709, SCALE), UNS, STREAMS, None),
+] + [("format_%d" % i, "three", o_video(Y, FB, 0, 0, 0, 64, 2, fmt(*f)), INV, why, None) for i, (f, why) in enumerate(BAD_FORMATS)])
+fam(W_V + "_10_bits", W_V, [
+    ("null_description", "three", o_video(None, FB10, 0, 0, 0, 64, 2, F10), INV, "null description", None),
+    ("no_rows", "three", o_video(Y10, FB10, 0, PW, 0, 64, 2, F10), INV, ORIENT, None),
+    ("negative_cols", "three", o_video(Y10, FB10, PH, -1, 0, 64, 2, F10), INV, ORIENT, None),
+    ("size_code_0", "three", o_video(Y10, FB10, PH + 2, PW, 0, 64, 2, F10), INV, UPRIGHT, None),
+    ("nan_scale", "three", o_video(Y10, FB10, 0, 0, 0, 64, 2, F10, NAN), INV, VSCALE, None),
+    ("one_plane", "one", o_video(Y10, FB10, 0, 0, 0, 64, 2, F10), INV, OPEN_PLANES, None),
+    ("five_planes", "five", o_video(Y10, FB10, 0, 0, 0, 64, 2, F10), INV, OPEN_PLANES, None),
+    ("with_input_resize", "three", o_video(Y10, FB10, 0, 0, 0, 64, 2, F10), INV, OPEN_PLANES, RZ),
+    ("streams", "multi", o_video(Y10, FB10, 0, 0, 0, 64, 2, F10), UNS, STREAMS, None),
+    ("no_plan", "bare", o_video(Y10, FB10, 0, 0, 0, 64, 2, F10), NOPLAN, "plan first", None),
+    ("depth", "three", o_video(Y10, FB10, 0, 0, 0, 64, 1, F10), INV, DEPTH, None),
+    ("odd_offset", "three", o_video(ydesc("yuv10", y_offset=1), FB10, 0, 0, 0, 64, 2, F10), INV, EVEN, None),
+    ("odd_stride_row", "three", o_video(ydesc("yuv10", u_stride_row=2 * PW + 1), FB10, 0, 0, 0, 64, 2, F10), INV, EVEN, None),
+    ("odd_stride_n", "three", o_video(ydesc("yuv10", v_stride_n=lambda k: k.fb10 + 1), FB10, 0, 0, 0, 64, 2, F10), INV, EVEN, None),
+    ("turned", "turn", o_video(Y10, FB10, PH, PW, 1, 64, 2, F10), UNS, WIDE, None),
+    ("turned_half", "three", o_video(Y10, FB10, PH, PW, 2, 64, 2, F10), UNS, WIDE, None),
+    ("reduced", "three", o_video(Y10, FB10, SH, SW, 0, 64, 2, F10, SCALE), UNS, WIDE, None),
+    ("orient_below", "three", o_video(Y10, FB10, PH, PW, -1, 64, 2, F10), INV, ORIENT, None),
+    ("orient_above", "three", o_video(Y10, FB10, PH, PW, 8, 64, 2, F10), INV, ORIENT, None),
+    ("orient_before_reduced", "three", o_video(Y10, FB10, SH, SW, 8, 64, 2, F10, SCALE), INV, ORIENT, None),
+    ("no_rows_before_turned", "three", o_video(Y10, FB10, 0, PW, 2, 64, 2, F10), INV, ORIENT, None),
+    ("streams_before_orient", "multi", o_video(Y10, FB10, PH, PW, 8, 64, 2, F10), UNS, STREAMS, None),
+    ("streams_before_turned", "multi", o_video(Y10, FB10, PH, PW, 2, 64, 2, F10), UNS, STREAMS, None),
+    ("last_word_high_byte_outside", "three", o_video(Y10, lambda k: k.fb10 - 1, 0, 0, 0, 64, 2, F10), INV, INSIDE, None),
+    ("last_word_outside", "three", o_video(Y10, lambda k: k.fb10 - 2, 0, 0, 0, 64, 2, F10), INV, INSIDE, None),
+    ("stride_n", "three", o_video(ydesc("yuv10", y_stride_n=lambda k: k.fb10 + 4), FB10, 0, 0, 0, 64, 2, F10), INV, STRIDE_N, None),
+    ("scale_before_turned", "three", o_video(Y10, FB10, PH, PW, 1, 64, 2, F10, NAN), INV, VSCALE, None),
+    ("description_before_planes", "five", o_video(ydesc("yuv10", sub_y=2), FB10, 0, 0, 0, 64, 2, F10), INV, "sub_x and sub_y must be 0 or 1", None),
+    ("extent_before_stride_n", "three", o_video(ydesc("yuv10", u_stride_n=lambda k: k.fb10 + 4), lambda k: k.fb10 - 1, 0, 0, 0, 64, 2, F10), INV, INSIDE, None),
+])
+fam(W_V + "_default_format", None, [   # (the default format is the open call of the family)
+    ("orient_above", "three", o_video(Y, FB, PH, PW, 8, 64, 2, None), INV, ORIENT, None),
+    ("size", "three", o_video(Y, FB, PH + 2, PW, 0, 64, 2, None), INV, UPRIGHT, None),
+    ("one_plane", "one", o_video(Y, FB, 0, 0, 0, 64, 2, None), INV, OPEN_PLANES, None),
+    ("plane_outside", "three", o_video(Y, lambda k: k.fb - 1, 0, 0, 0, 64, 2, None), INV, INSIDE, None),
+    ("reduced_other_plan", "three", o_video(YS, FBS, SH, SW, 2, 64, 2, None, 0.75), INV, REDUCED, None),
+    ("orient_before_streams", "multi", o_video(Y, FB, PH, PW, 8, 64, 2, None), INV, ORIENT, None),
+    ("size_before_streams", "multi", o_video(Y, FB, PH + 2, PW, 2, 64, 2, None), INV, UPRIGHT, None),
+])
+ROWS += FAMILY_ROWS
+
 IDS = [r[0] for r in ROWS]
 assert len(set(IDS)) == len(IDS)
 
@@ -327,7 +703,7 @@ def ctxs():
 
 
 def test_every_context_takes_its_good_call(ctxs):
-    for name in ("three", "one", "five", "odd", "multi"):
+    for name in ("three", "one", "five", "odd", "multi", "turn"):
         ctxs.good(name, getattr(ctxs, name))
     d = ctxs.three
     d.run_yuv_resized(ctxs.x, 2, ctxs.yuvS, SH, SW, SCALE)
