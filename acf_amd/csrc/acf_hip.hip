@@ -333,6 +333,10 @@ struct acf_hip_ctx
     PadJob* d_padJobs = nullptr;
     PadJob* d_padJobsR = nullptr; // the same borders in the rank pyramid's layout
     bool levelsEmitRank = false;  // every level goes through k_level_all: the level kernels can write the rank cells themselves
+    // acf_hip_get_level_forms: per level the word levelJobs wrote while it decided (ACF_HIP_LF_*; the job in the fused list and in the
+    // raw list), and the call-wide words the last pyramid call's planLevels left
+    std::vector<int32_t> levelFormFused, levelFormRaw;
+    int32_t levelCallForm[ACF_HIP_LF_HEAD] = { 0, 0, 0, 0, 0, 0 };
     // k_smooth_vec's speculative column segments (kernels.hip.h): state of the segments' hand-overs, planes to repair
     float *d_specState = nullptr, *d_trueState = nullptr;
     bool countersZeroed = false; // acf_hip_run has cleared the tiled cascade's counters in front of the pyramid's launches
@@ -1927,6 +1931,30 @@ int acf_hip_get_tri_forms(const acf_hip_ctx* c, int32_t* out, int cap, int* n)
     for (int i = 0; i < *n && i < cap; i++)
     {
         out[i] = s->real[size_t(i)].triForm;
+    }
+    return ACF_HIP_OK;
+}
+
+int acf_hip_get_level_forms(const acf_hip_ctx* c, int32_t* out, int cap, int* n)
+{
+    if (int rc = needPlanRead(c, "get_level_forms")) return rc;
+    if (!n || (cap > 0 && !out))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    const acf_hip_ctx* s = c->kids.empty() ? c : c->kids[0]; // (sub-batch children hold the plan's job lists; they all run the same forms)
+    const int nL = int(s->levelFormFused.size());
+    *n = ACF_HIP_LF_HEAD + nL;
+    for (int i = 0; i < ACF_HIP_LF_HEAD && i < cap; i++)
+    {
+        out[i] = s->levelCallForm[i];
+    }
+    const int path = s->levelCallForm[0];
+    const int32_t form = 0xffff, why = ~form, taker = 3 << 12;
+    for (int i = 0; i < nL && ACF_HIP_LF_HEAD + i < cap; i++)
+    {
+        const int32_t f = s->levelFormFused[size_t(i)], r = s->levelFormRaw[size_t(i)];
+        out[ACF_HIP_LF_HEAD + i] = (f & why) | (path == ACF_HIP_LV_WAVE_SMOOTH ? r & form : path == ACF_HIP_LV_FUSED ? f & form : f & form & ~taker);
     }
     return ACF_HIP_OK;
 }

@@ -305,9 +305,18 @@ int PlanBuild::levelJobs()
         {
             int key;
             LevelJob j;
+            int level;
         };
         std::vector<Keyed> fusedJobs, rawJobs;
-        c->fusedOk = p.smooth > 0 && c->finalMaxH <= 64 * LEVEL_MAX_R_REAL;
+        c->fusedOk = p.smooth > 0;
+        // acf_hip_get_level_forms' words: every decision below leaves its bit on the level it was made for
+        c->levelFormFused.assign(pl.levels.size(), 0);
+        c->levelFormRaw.assign(pl.levels.size(), 0);
+        std::fill(c->levelCallForm, c->levelCallForm + ACF_HIP_LF_HEAD, 0);
+        auto notFused = [&](size_t level, int32_t why) {
+            c->fusedOk = false;
+            c->levelFormFused[level] |= why;
+        };
         int ai = 0;
         for (size_t i = 0; i < pl.levels.size(); i++)
         {
@@ -327,37 +336,47 @@ int PlanBuild::levelJobs()
             j.desc = -1;
             const int R = (l.hC + 63) / 64;
             int mode = LM_REAL;
-            rawJobs.push_back({ R * 8 + LM_REAL, j });
+            rawJobs.push_back({ R * 8 + LM_REAL, j, int(i) });
+            if (l.hC > 64 * LEVEL_MAX_R_REAL)
+            {
+                notFused(i, ACF_HIP_LF_WHY_TALL); // (finalMaxH: no level kernel takes it, planLevels leaves the wave-per-plane paths)
+            }
             if (!l.isReal)
             {
                 j.desc = ai;
                 const ResampleDesc& dd = c->h_descs[size_t(c->nImgDescs + ai)];
-                if ((dd.ymode == RS_DOWN && dd.ybd0 > 3) || (dd.xmode == RS_DOWN && dd.xbd0 > 3) || dd.ymode == RS_EXACT || dd.xmode == RS_EXACT)
+                if ((dd.ymode == RS_DOWN && dd.ybd0 > 3) || (dd.xmode == RS_DOWN && dd.xbd0 > 3))
                 {
-                    c->fusedOk = false; // more than three taps on an axis or an exact 1/k ratio: separate launches
+                    notFused(i, ACF_HIP_LF_WHY_TAPS); // more than three taps on an axis: separate launches
+                }
+                if (dd.ymode == RS_EXACT || dd.xmode == RS_EXACT)
+                {
+                    notFused(i, ACF_HIP_LF_WHY_EXACT); // an exact 1/k ratio: separate launches
                 }
                 mode = dd.xmode == RS_DOWN ? (dd.ymode == RS_DOWN ? LM_DD : LM_DU) : (dd.ymode == RS_DOWN ? LM_UD : LM_UU);
                 if (R > 8)
                 {
-                    c->fusedOk = false; // (only copies of real levels are instantiated beyond eight rows per lane)
+                    notFused(i, ACF_HIP_LF_WHY_ROWS); // (only copies of real levels are instantiated beyond eight rows per lane)
                 }
                 if (dd.ha >= 64 * (dd.ymode == RS_DOWN ? (3 * R + 1) / 2 : R))
                 {
                     // more source rows than LevelWindow's registers hold (ratio beyond 2^(1/2)), or no row left in the
                     // column buffer for the zeros that taps beyond the source's last row read (level_column)
-                    c->fusedOk = false;
+                    notFused(i, ACF_HIP_LF_WHY_WINDOW);
                 }
                 if (mode == LM_DU || mode == LM_UD)
                 {
                     // one axis up, the other down: cannot happen with getScales' isotropic scales (an exhaustive scan of
-                    // 64..330 x 64..330 frames finds none), so the fused kernel is not instantiated for it
-                    c->fusedOk = false;
+                    // 64..330 x 64..330 frames finds none), so the fused kernel is not instantiated for it.  (An exact axis is "not
+                    // down" above, so an exact x beside a down y lands here as well — tests/level_forms_case.py has such levels —
+                    // after the exact ratio has ruled the fused path out already.)
+                    notFused(i, ACF_HIP_LF_WHY_MIXED);
                 }
                 ai++;
             }
-            fusedJobs.push_back({ R * 8 + mode, j });
+            fusedJobs.push_back({ R * 8 + mode, j, int(i) });
         }
-        auto pack = [&](std::vector<Keyed>& v, std::vector<acf_hip_ctx::LevelGroup>& groups, LevelJob** dst, int* nAll) {
+        auto pack = [&](std::vector<Keyed>& v, std::vector<acf_hip_ctx::LevelGroup>& groups, LevelJob** dst, int* nAll, std::vector<int32_t>& form) {
             auto jobCost = [](const Keyed& k) {
                 // one wave walks wC column steps; a step costs ~R row registers x (1 for a copy, 3 for a resampled column) + the recursion
                 const int R = k.key / 8, mode = k.key % 8;
@@ -373,7 +392,9 @@ int PlanBuild::levelJobs()
             for (const auto& k : v)
             {
                 const int R = k.key / 8, mode = k.key % 8;
-                ((R <= 4 || (mode == LM_REAL && R <= 8)) && !fallbackForced(FB_LEVEL_GROUPS) ? all : rest).push_back(k);
+                const bool toAll = (R <= 4 || (mode == LM_REAL && R <= 8)) && !fallbackForced(FB_LEVEL_GROUPS);
+                (toAll ? all : rest).push_back(k);
+                form[size_t(k.level)] |= R | mode << 8 | (toAll ? ACF_HIP_LF_BY_ALL : ACF_HIP_LF_BY_GROUP) << 12;
             }
             std::stable_sort(all.begin(), all.end(), [&](const Keyed& a, const Keyed& b) { return jobCost(a) > jobCost(b); });
             std::stable_sort(rest.begin(), rest.end(), [](const Keyed& a, const Keyed& b) { return a.key < b.key; });
@@ -396,7 +417,8 @@ int PlanBuild::levelJobs()
             }
             return devUpload(c, dst, flat);
         };
-        if ((rc = pack(fusedJobs, c->levelGroups, &c->d_levelJobs, &c->nAllJobs)) || (rc = pack(rawJobs, c->levelGroupsRaw, &c->d_levelJobsRaw, &c->nAllJobsRaw)))
+        if ((rc = pack(fusedJobs, c->levelGroups, &c->d_levelJobs, &c->nAllJobs, c->levelFormFused)) ||
+            (rc = pack(rawJobs, c->levelGroupsRaw, &c->d_levelJobsRaw, &c->nAllJobsRaw, c->levelFormRaw)))
         {
             return rc;
         }

@@ -208,6 +208,7 @@ struct PyramidRun
     int gradientChannels(size_t k, const ScalePlan& sp);
     int joinScales();
     int planLevels(int nLF);
+    void noteLevelForms();
     int levels(int f0, int nLF);
     int launchLevels(const LevelsCall& lc, int f0);
     int launchLevelAll(const LevelsCall& lc, int f0);
@@ -829,8 +830,22 @@ int PyramidRun::planLevels(int nLF)
 
 int PyramidRun::levels(int f0, int nLF)
 {
-    const int rc = planLevels(nLF);
-    return rc ? rc : launchLevels(lv, f0);
+    if (int rc = planLevels(nLF))
+    {
+        return rc;
+    }
+    noteLevelForms();
+    return launchLevels(lv, f0);
+}
+
+// acf_hip_get_level_forms' call-wide words: what planLevels decided, as launchLevels reads it
+void PyramidRun::noteLevelForms()
+{
+    static_assert(LV_FUSED == ACF_HIP_LV_FUSED && LV_WAVE_SMOOTH == ACF_HIP_LV_WAVE_SMOOTH && LV_SMOOTH_JOBS == ACF_HIP_LV_SMOOTH_JOBS && LV_COPY == ACF_HIP_LV_COPY, "");
+    const bool wave = lv.path == LV_FUSED || lv.path == LV_WAVE_SMOOTH;
+    const int32_t w[ACF_HIP_LF_HEAD] = { int32_t(lv.path), wave && lv.emitRank, !wave || lv.emitF32, wave && lv.nAll > 0 ? lv.lsa.nSeg : 0, lv.approxFirst,
+        int32_t(pl.levels.size()) };
+    std::copy(w, w + ACF_HIP_LF_HEAD, c->levelCallForm);
 }
 
 int PyramidRun::launchLevels(const LevelsCall& lc, int f0)
@@ -968,6 +983,7 @@ int PyramidRun::levelsWithImageLambdas()
     {
         return rc;
     }
+    noteLevelForms();
     prof(c, st, "k_plane_sums");
     const int lv0 = pl.lambdaLevel[0], lv1 = pl.lambdaLevel[1];
     SumJob j0{ pl.raw_off[size_t(lv0)], pl.levels[size_t(lv0)].hC * pl.levels[size_t(lv0)].wC, 0 };

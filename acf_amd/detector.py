@@ -570,6 +570,28 @@ class HipDetector:
         self._chk(self.lib.acf_hip_get_tri_forms(self.ctx, out, cap, C.byref(n)))
         return [int(out[i]) for i in range(min(n.value, cap))]
 
+    LEVEL_PATHS = ("fused", "wave_smooth", "smooth_jobs", "copy")
+    LEVEL_MODES = ("real", "dd", "du", "ud", "uu")
+    LEVEL_TAKERS = (None, "all", "group")
+    LEVEL_WHY = ("taps", "exact", "rows", "window", "tall", "mixed")
+
+    def level_forms(self):
+        """What the level stage decided (acf_hip_get_level_forms): dict(path, emit_rank, emit_f32, segments, approx_first, levels), of the
+        last pyramid call (before the first: the call-wide entries are zero / "fused" / False and the levels are the plan's fused list); levels[i] = dict(R, mode, by = "all" (k_level_all) / "group" (a k_level<R, mode> launch) / None, why = the
+        reasons level i gives the plan not to fuse, a tuple of LEVEL_WHY names)."""
+        cap = capi.LF_HEAD + 256
+        n = C.c_int()
+        out = (C.c_int32 * cap)()
+        self._chk(self.lib.acf_hip_get_level_forms(self.ctx, out, cap, C.byref(n)))
+        levels = []
+        for i in range(capi.LF_HEAD, min(n.value, cap)):
+            w = int(out[i])
+            levels.append(dict(R=w & 255, mode=self.LEVEL_MODES[w >> 8 & 7], by=self.LEVEL_TAKERS[w >> 12 & 3],
+                               why=tuple(name for b, name in enumerate(self.LEVEL_WHY) if w >> (16 + b) & 1)))
+        assert out[5] in (0, len(levels))   # (the call-wide words are zero before the first pyramid call)
+        return dict(path=self.LEVEL_PATHS[out[0]], emit_rank=bool(out[1]), emit_f32=bool(out[2]), segments=int(out[3]),
+                    approx_first=bool(out[4]), levels=levels)
+
     def set_option(self, key, value):
         self._chk(self.lib.acf_hip_set_option(self.ctx, key.encode(), int(value)))
 

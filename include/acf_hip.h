@@ -818,6 +818,31 @@ ACF_HIP_API int acf_hip_get_repairs(acf_hip_ctx* ctx, int64_t out[4]);
  * replayed (no plane U travels through memory), bit 1 = the context holds a plane U for that scale (it is allocated only when a
  * call first takes a form that reads it).  Additive: ACF_HIP_ABI_VERSION stays. */
 ACF_HIP_API int acf_hip_get_tri_forms(const acf_hip_ctx* ctx, int32_t* out, int cap, int* n);
+/* Read-only: what the level stage (approximated levels, final smoothing, placement, rank cells) decided, written down where the plan
+ * and the last acf_hip_pyramid / acf_hip_run* call decided it.  *n = ACF_HIP_LF_HEAD + number of levels; at most `cap` words are
+ * written.  Call-wide, of the last call (zeros before the first): out[0] = path (ACF_HIP_LV_*), out[1] = the level kernels wrote the
+ * rank cells, out[2] = they wrote floats, out[3] = column segments of k_level_all's first launch (0: it did not run), out[4] =
+ * k_resample(approx) ran first, out[5] = number of levels.  out[ACF_HIP_LF_HEAD + i], level i, of the job list that path reads (the
+ * plan's fused list before the first call and on the paths that run no level kernel): bits 0-7 rows per lane R, bits 8-10 the mode
+ * (0 real, 1 x and y down, 2 x down y up, 3 x up y down, 4 x and y up), bits 12-13 who takes the level (ACF_HIP_LF_BY_*), and from bit
+ * 16 the reasons this level gives the plan not to fuse (ACF_HIP_LF_WHY_*; all clear on every level: the plan can).  With a batch
+ * that the call cut into launches of their own (image-specific lambdas) the words are those of the launches: they all share one
+ * plan.  Additive: ACF_HIP_ABI_VERSION stays. */
+#define ACF_HIP_LF_HEAD 6
+#define ACF_HIP_LV_FUSED 0       /* k_level_all + k_level groups resample, smooth and place every level */
+#define ACF_HIP_LV_WAVE_SMOOTH 1 /* the same kernels smooth and place what a separate k_resample approximated */
+#define ACF_HIP_LV_SMOOTH_JOBS 2 /* the tiled smoothing kernels over every level */
+#define ACF_HIP_LV_COPY 3        /* no smoothing: plane copies */
+#define ACF_HIP_LF_BY_NONE 0     /* no level kernel (paths 2 and 3) */
+#define ACF_HIP_LF_BY_ALL 1      /* k_level_all */
+#define ACF_HIP_LF_BY_GROUP 2    /* a k_level<R, mode> group launch */
+#define ACF_HIP_LF_WHY_TAPS (1 << 16)   /* more than three taps on an axis */
+#define ACF_HIP_LF_WHY_EXACT (1 << 17)  /* an exact 1/k ratio on an axis */
+#define ACF_HIP_LF_WHY_ROWS (1 << 18)   /* an approximated level of more than 8 rows per lane */
+#define ACF_HIP_LF_WHY_WINDOW (1 << 19) /* more source rows than the level kernel's window holds */
+#define ACF_HIP_LF_WHY_TALL (1 << 20)   /* taller than the tallest level kernel */
+#define ACF_HIP_LF_WHY_MIXED (1 << 21)  /* one axis up, the other down */
+ACF_HIP_API int acf_hip_get_level_forms(const acf_hip_ctx* ctx, int32_t* out, int cap, int* n);
 /* Host only (tests): the checkpoint buffer of an h x w plane — out[0] = float index of the (T, U) pair that row y's replay of the
  * 16-column segment holding column x starts from, out[1] = floats per frame.  Per frame
  * [x >> 6][(y + 8) >> 4][(x >> 4) & 3][(y + 8) & 15][2]: the 16 rows x 4 segments a wave of the y kernel takes per step are 512
