@@ -180,7 +180,6 @@ struct CascState
 // channel) and halved into the LDCF pyramid, on which the cascade then runs.
 struct LdcfStage
 {
-    std::vector<float> filters;        // the model's (acf_hip_set_model): they outlive a plan
     std::vector<acf_hip_level> levels; // level table of the LDCF pyramid
     int descBase = 0;                  // the levels' resample descriptors in h_descs / d_descs
     int64_t floats = 0, tmpFloats = 0; // floats per frame of the LDCF pyramid and of the filtered scratch
@@ -255,58 +254,54 @@ struct Options
     int keepPyramid = 1;
 };
 
-struct acf_hip_ctx
-{
-    int device = 0;
-    hipStream_t stream = nullptr; // the caller's stream: assigned in acf_hip_create and nowhere else (a stage that enqueues elsewhere is told its stream)
-    bool ownStream = false;
-    // side streams: independent launches of one stage (the level groups) run concurrently, forked from and
-    // joined back into `stream` with events, so the stage costs its longest launch instead of their sum
-    std::vector<hipStream_t> side;
-    // Sub-batch contexts (option "streams" = K > 1): the batch is cut into K contiguous chunks, each run by a child
-    // context with its own buffers and stream, forked from / joined into `stream` by events.  The path is a chain of
-    // kernels several of which are latency-bound inside a frame (column recursions, per-tile dependency chains):
-    // chunks at different stages of the chain fill each other's idle issue slots and memory time.
-    std::vector<acf_hip_ctx*> kids;
-    int nStreams = 1, kidChunk = 0;
-    hipEvent_t evFork = nullptr;
-    std::vector<hipEvent_t> evJoin;
-    mutable std::string err;
-    bool hasModel = false, hasPlan = false;
-    Options opt; // acf_hip_set_option's settings (sub-batch children hold the parent's)
-    bool x86Owned = false;
-    uint32_t* d_x86 = nullptr; // [X86_BUF_N]: rcp over [1, 2) by m >> 11 (4096), rsqrt over [1, 4) by parity and m >> 11 (2 x 4096), then gradMag's composed pairs
-    // the device as hipGetDeviceProperties describes it (acf_hip_create): the persistent grids are sized from these.  The
-    // counters the persistent workgroups draw tiles from are eight (blockIdx.x & 7: one per XCD of an MI355X, whose
-    // dispatcher deals consecutive workgroups to consecutive XCDs); on a part with another XCD count the ranges still
-    // cover every tile, only their locality is lost.
-    int numCus = 256;
-    size_t ldsPerCu = size_t(160) * 1024;
-    bool ranksValid = false; // the rank pyramid of the last batch has been written (by the level kernels or by k_rank)
-    bool floatPyramid = true; // the float pyramid of the last batch exists (option keep_pyramid = 0: it may not)
-    std::vector<hipEvent_t> evPool;
-    std::vector<const char*> evName;
-    size_t evUsed = 0;
-    std::vector<hipStream_t> evStream; // the stream each profile event was recorded on (a kernel ends at the next event of ITS stream)
-    std::vector<hipEvent_t> evScale;   // pyramid: "real scale k has been smoothed" (the next real scale starts from it on its own stream)
-    hipEvent_t evTurn[2] = { nullptr, nullptr }; // [0] tile kernel, [1] level kernel (bit 1 of the option: own turns; bit 2: the tile kernels' turns)
+// The context's state is grouped by lifetime.  Each group is a base of acf_hip_ctx, so its fields are reached as c->field, and a
+// lifetime's reset is the assignment of a default-constructed group: no function keeps a list of fields to clear.
 
+// ---- acf_hip_set_model's: the classifier and the channel parameters (they survive acf_hip_plan)
+struct ModelState
+{
+    bool hasModel = false;
     acf_hip_params p{};
     std::vector<uint32_t> fids, child;
     std::vector<float> thrs, hs;
-    LdcfStage ldcf;
+    std::vector<float> ldcfFilters; // where p.ldcfFilters points: the filters outlive a plan, the LDCF stage built from them does not
+    // acf_hip_evaluate_crops: the classifier on the device without a plan (not one of the plan's buffers: uploaded at the first call
+    // after acf_hip_set_model, freed by the next one and by acf_hip_destroy); fidMax: the largest feature id a tree walk can read
+    struct CropModel
+    {
+        uint32_t *fids = nullptr, *child = nullptr;
+        float *thrs = nullptr, *hs = nullptr;
+        uint32_t fidMax = 0;
+        bool valid = false;
+    } crop;
+};
 
+// ---- what the last pyramid / detect call left (part of the plan's state: a new plan starts without a batch; a replayed graph
+// restores what its captured host code left, GraphSlot::after)
+struct LastRun
+{
+    int lastBatch = 0;
+    bool pyramidValid = false, detectValid = false;
+    bool ranksValid = false;   // the rank pyramid of the last batch has been written (by the level kernels or by k_rank)
+    bool floatPyramid = true;  // the float pyramid of the last batch exists (option keep_pyramid = 0: it may not)
+    bool countsFetched = false; // h_counts holds the last batch's counts
+    const float* lastFrames = nullptr;
+};
+
+// ---- acf_hip_plan's: everything the plan builds, and what runs allocate lazily under it.  dropPlan frees `allocs` and assigns a
+// fresh PlanState, so a pointer declared here never outlives the memory it names.
+struct PlanState : LastRun
+{
+    bool hasPlan = false;
     Plan plan;
+    int maxBatch = 0, maxHits = 0;
+    std::vector<void*> allocs; // every device buffer of this struct (devAlloc / devUpload)
     // image-specific lambdas (model without lambdas, chnsPyramid.cpp:341-374): per-frame plane sums of two real levels on
     // the device, the lambdas of every frame of the last batch on the host
     bool autoLambdas = false;
     double* d_planeSums = nullptr;     // [maxBatch][2][nChns]
     std::vector<double> h_lambdas;     // [maxBatch][3]
-    int maxBatch = 0, maxHits = 0, lastBatch = 0;
-    bool pyramidValid = false, detectValid = false;
-
-    std::vector<void*> allocs;
-    // constant tables
+    // constant tables (ensureConstTables: also built without a plan, for the single-operator entries)
     float* d_lTable = nullptr;
     float* d_acos = nullptr;
     // planning tables
@@ -339,64 +334,30 @@ struct acf_hip_ctx
     int32_t levelCallForm[ACF_HIP_LF_HEAD] = { 0, 0, 0, 0, 0, 0 };
     // k_smooth_vec's speculative column segments (kernels.hip.h): state of the segments' hand-overs, planes to repair
     float *d_specState = nullptr, *d_trueState = nullptr;
-    bool countersZeroed = false; // acf_hip_run has cleared the tiled cascade's counters in front of the pyramid's launches
     int32_t* d_redo = nullptr;
     size_t redoInts = 0, lvRedoInts = 0; // their sizes (clearRepairFlags)
     // the same for the level chains (k_level_all<OUT, 1>), for batches of at most levelSegFrames frames
     float *d_lvSpec = nullptr, *d_lvTrue = nullptr;
     int32_t* d_lvRedo = nullptr;
     int levelSegFrames = 0, levelSegCap = 0, levelHMax = 0;
-    // option "graph": acf_hip_run replays a HIP graph captured from its own launches (same frames pointer, same batch size):
-    // one host call instead of ~45 launches per frame — what a single frame's latency is made of when the kernels take 20 us
-    int useGraph = 0;
-    // option "graph": captured runs keyed by (input pointer, batch size); a caller that alternates between a few input buffers
-    // (double / triple buffering) replays one graph per buffer instead of re-capturing on every call
-    struct GraphSlot
-    {
-        hipGraphExec_t exec = nullptr;
-        const float* frames = nullptr;
-        int n = 0;
-        bool ranksValid = false, floatPyramid = true; // what the captured host code left behind
-    };
-    static constexpr int GRAPH_SLOTS = 4;
-    GraphSlot graphs[GRAPH_SLOTS];
-    int graphNext = 0; // slot the next capture replaces (round robin)
-    int plainRuns = 0, graphBroken = 0;
-    int64_t repairs[4] = { 0, 0, 0, 0 }; // {smoothing planes checked, redone, level planes checked, redone}
     int segCap = 0;               // segments the state buffers hold per plane
     int finalMaxH = 0;
     int approxMaxBlocks = 0;
     int64_t padMaxElems = 0;
+    LdcfStage ldcf;
     // frame buffers
     float* d_color = nullptr; // colour-converted full-resolution image (if a conversion is needed)
     float* d_chns = nullptr;
     float* d_pyr = nullptr;
-    const float* lastFrames = nullptr;
-    float* d_stage = nullptr; // H2D staging for run_host; planar f32 target of the 8-bit ingest when no colour conversion follows
-    // streaming front end (acf_hip_stream_*)
-    struct StreamSlot
-    {
-        uint8_t* d_in = nullptr;   // device copy of the packed 8-bit batch
-        int32_t* d_rec = nullptr;  // device records (acf_hip_export_detections layout)
-        int32_t* h_rec = nullptr;  // pinned host records
-        hipEvent_t evH2D = nullptr, evDone = nullptr;
-        int ticket = -1, nFrames = 0;
-    };
-    std::vector<StreamSlot> slots;
-    hipStream_t copyStream = nullptr;
-    int stCap = 0, nextTicket = 0, nextCollect = 0;
-    int64_t stFrameBytes = 0; // bytes between the frames of a submitted batch
-    FrameSource stSrc;        // what the stream was opened for: a batch runs as this source at its slot's device buffer
     // the plan's cascade (tables, model arrays, work queues, outputs); acf_hip_op_acf_detect1 builds and runs a state of its own
     CascState cs;
     BoxLevel* d_boxLevels = nullptr;
-    // device bbNms + prune (acf_hip_set_nms): survivors of every frame, what get_detections / export then return
-    bool nmsOn = false;
-    acf_hip_nms_params nms{};
+    // -- allocated by the first run that needs them --
+    float* d_stage = nullptr; // H2D staging for run_host; planar f32 target of the 8-bit ingest when no colour conversion follows
+    // device bbNms + prune: survivors of every frame, what get_detections / export then return (the settings are the context's: nmsOn, nms)
     int32_t *d_nmsKeep = nullptr, *d_nmsN = nullptr, *d_nmsCounts = nullptr;
     acf_hip_detection* d_nmsDets = nullptr;
     std::vector<int32_t> h_counts;
-    bool countsFetched = false;
     // acf_hip_set_input_resize: the apps' resize to a minimum object width in front of the 8-bit entries (k_resize_u8)
     struct InputResize
     {
@@ -419,15 +380,85 @@ struct acf_hip_ctx
     } yuv;
     uint8_t* d_yuvRgb = nullptr; // k_yuv420_to_rgb8's tight RGB frames (in front of the input resize; fallback yuv_unfused)
     size_t yuvRgbBytes = 0;
-    // acf_hip_evaluate_crops: the classifier on the device without a plan (not one of the plan's buffers: uploaded at the first call
-    // after acf_hip_set_model, freed by the next one and by acf_hip_destroy); fidMax: the largest feature id a tree walk can read
-    struct CropModel
+};
+
+// ---- an open stream's (acf_hip_stream_open* .. acf_hip_stream_close; acf_hip_plan closes it: its slots are sized by the plan)
+struct StreamFront
+{
+    struct StreamSlot
     {
-        uint32_t *fids = nullptr, *child = nullptr;
-        float *thrs = nullptr, *hs = nullptr;
-        uint32_t fidMax = 0;
-        bool valid = false;
-    } crop;
+        uint8_t* d_in = nullptr;   // device copy of the packed 8-bit batch
+        int32_t* d_rec = nullptr;  // device records (acf_hip_export_detections layout)
+        int32_t* h_rec = nullptr;  // pinned host records
+        hipEvent_t evH2D = nullptr, evDone = nullptr;
+        int ticket = -1, nFrames = 0;
+    };
+    std::vector<StreamSlot> slots;
+    hipStream_t copyStream = nullptr;
+    int stCap = 0, nextTicket = 0, nextCollect = 0;
+    int64_t stFrameBytes = 0; // bytes between the frames of a submitted batch
+    FrameSource stSrc;        // what the stream was opened for: a batch runs as this source at its slot's device buffer
+};
+
+// ---- create .. destroy, and the settings that survive acf_hip_plan (options, NMS, the x86 tables, the counted repairs)
+struct acf_hip_ctx : ModelState, PlanState, StreamFront
+{
+    int device = 0;
+    hipStream_t stream = nullptr; // the caller's stream: assigned in acf_hip_create and nowhere else (a stage that enqueues elsewhere is told its stream)
+    bool ownStream = false;
+    // side streams: independent launches of one stage (the level groups) run concurrently, forked from and
+    // joined back into `stream` with events, so the stage costs its longest launch instead of their sum
+    std::vector<hipStream_t> side;
+    hipEvent_t evFork = nullptr;
+    std::vector<hipEvent_t> evJoin;
+    std::vector<hipEvent_t> evScale;   // pyramid: "real scale k has been smoothed" (the next real scale starts from it on its own stream)
+    hipEvent_t evTurn[2] = { nullptr, nullptr }; // [0] tile kernel, [1] level kernel (bit 1 of the option: own turns; bit 2: the tile kernels' turns)
+    // the device as hipGetDeviceProperties describes it (acf_hip_create): the persistent grids are sized from these.  The
+    // counters the persistent workgroups draw tiles from are eight (blockIdx.x & 7: one per XCD of an MI355X, whose
+    // dispatcher deals consecutive workgroups to consecutive XCDs); on a part with another XCD count the ranges still
+    // cover every tile, only their locality is lost.
+    int numCus = 256;
+    size_t ldsPerCu = size_t(160) * 1024;
+    mutable std::string err;
+    Options opt; // acf_hip_set_option's settings (sub-batch children hold the parent's)
+    bool x86Owned = false;
+    uint32_t* d_x86 = nullptr; // [X86_BUF_N]: rcp over [1, 2) by m >> 11 (4096), rsqrt over [1, 4) by parity and m >> 11 (2 x 4096), then gradMag's composed pairs
+    // acf_hip_set_nms: device bbNms + prune after the cascade (its buffers are the plan's)
+    bool nmsOn = false;
+    acf_hip_nms_params nms{};
+    int64_t repairs[4] = { 0, 0, 0, 0 }; // {smoothing planes checked, redone, level planes checked, redone}
+    bool countersZeroed = false; // for the length of one acf_hip_run: it has cleared the tiled cascade's counters in front of the pyramid's launches
+    // Sub-batch contexts (option "streams" = K > 1): the batch is cut into K contiguous chunks, each run by a child
+    // context with its own buffers and stream, forked from / joined into `stream` by events.  The path is a chain of
+    // kernels several of which are latency-bound inside a frame (column recursions, per-tile dependency chains):
+    // chunks at different stages of the chain fill each other's idle issue slots and memory time.  They hold the plan's buffers
+    // in this context's place, so they go with the plan (dropPlan).
+    std::vector<acf_hip_ctx*> kids;
+    int nStreams = 1, kidChunk = 0;
+    // option "graph": acf_hip_run replays a HIP graph captured from its own launches (same frames pointer, same batch size):
+    // one host call instead of ~45 launches per frame — what a single frame's latency is made of when the kernels take 20 us
+    int useGraph = 0;
+    // option "graph": captured runs keyed by (input pointer, batch size); a caller that alternates between a few input buffers
+    // (double / triple buffering) replays one graph per buffer instead of re-capturing on every call
+    struct GraphSlot
+    {
+        hipGraphExec_t exec = nullptr;
+        const float* frames = nullptr;
+        LastRun after; // what the captured host code left behind (after.lastBatch: the batch size)
+    };
+    static constexpr int GRAPH_SLOTS = 4;
+    GraphSlot graphs[GRAPH_SLOTS];
+    int graphNext = 0; // slot the next capture replaces (round robin)
+    int plainRuns = 0, graphBroken = 0;
+    // option "profile": a pool of markers, the first evUsed of them recorded since the last acf_hip_profile_get
+    struct ProfMark
+    {
+        hipEvent_t ev;
+        const char* name;
+        hipStream_t stream; // the stream it was recorded on (a kernel ends at the next marker of ITS stream)
+    };
+    std::vector<ProfMark> evPool;
+    size_t evUsed = 0;
 };
 
 // the ONE statement of "the cascade state has rank cells and option rank_cells is on"; each reader adds its own terms
@@ -580,14 +611,12 @@ void prof(acf_hip_ctx* c, hipStream_t st, const char* name)
         {
             return;
         }
-        c->evPool.push_back(e);
-        c->evName.push_back(name);
-        c->evStream.push_back(st);
+        c->evPool.push_back({ e, name, st });
     }
-    c->evName[c->evUsed] = name;
-    c->evStream[c->evUsed] = st;
-    (void)hipEventRecord(c->evPool[c->evUsed], st);
-    c->evUsed++;
+    acf_hip_ctx::ProfMark& m = c->evPool[c->evUsed++];
+    m.name = name;
+    m.stream = st;
+    (void)hipEventRecord(m.ev, st);
 }
 
 template <class T>
@@ -696,33 +725,20 @@ struct Scratch
     }
 };
 
-void freeAll(acf_hip_ctx* c)
+// The plan goes: its buffers, every pointer to them and everything computed for it — and the sub-batch children, which hold a
+// plan's buffers in their parent's place.  (The caller has made sure nothing in flight reads the buffers.)
+void dropPlan(acf_hip_ctx* c)
 {
+    for (acf_hip_ctx* k : c->kids)
+    {
+        (void)acf_hip_destroy(k);
+    }
+    c->kids.clear();
     for (void* p : c->allocs)
     {
         (void)hipFree(p);
     }
-    c->allocs.clear();
-    c->hasPlan = false;
-    c->d_lTable = c->d_acos = nullptr;
-    c->d_dump = nullptr;
-    c->d_specState = c->d_trueState = nullptr;
-    c->d_redo = nullptr;
-    c->segCap = 0;
-    c->d_lvSpec = c->d_lvTrue = nullptr;
-    c->d_lvRedo = nullptr;
-    c->levelSegFrames = 0;
-    c->d_color = c->d_stage = c->d_chns = c->d_pyr = nullptr; // a re-plan must not see the previous plan's buffers
-    c->rz = acf_hip_ctx::InputResize();
-    c->rzIn = acf_hip_ctx::InputResize();
-    c->yuv = acf_hip_ctx::YuvLayout();
-    c->d_yuvRgb = nullptr;
-    c->yuvRgbBytes = 0;
-    c->ldcf = LdcfStage{ std::move(c->ldcf.filters) }; // (the model's filters stay where acf_hip_params::ldcfFilters points)
-    c->d_nmsKeep = c->d_nmsN = c->d_nmsCounts = nullptr;
-    c->d_nmsDets = nullptr;
-    c->lastFrames = nullptr;
-    c->pyramidValid = c->detectValid = false;
+    static_cast<PlanState&>(*c) = PlanState{};
 }
 
 // rgb2luv_setup's table (toolbox/rgbConvertMex.cpp:39-58)
@@ -1427,14 +1443,6 @@ int acf_hip_destroy(acf_hip_ctx* c)
 {
     dropGraph(c);
     dropCropModel(c);
-    if (c)
-    {
-        for (acf_hip_ctx* k : c->kids)
-        {
-            (void)acf_hip_destroy(k);
-        }
-        c->kids.clear();
-    }
     if (!c)
     {
         return ACF_HIP_E_INVALID;
@@ -1443,14 +1451,14 @@ int acf_hip_destroy(acf_hip_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     (void)acf_hip_stream_close(c);
     cascTurnForget(c);
-    freeAll(c);
+    dropPlan(c);
     if (c->d_x86 && c->x86Owned)
     {
         (void)hipFree(c->d_x86);
     }
-    for (hipEvent_t e : c->evPool)
+    for (const auto& m : c->evPool)
     {
-        (void)hipEventDestroy(e);
+        (void)hipEventDestroy(m.ev);
     }
     for (hipStream_t st : c->side)
     {
@@ -1700,14 +1708,6 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
 {
     dropGraph(c);
     dropCropModel(c);
-    if (c)
-    {
-        for (acf_hip_ctx* k : c->kids)
-        {
-            (void)acf_hip_destroy(k);
-        }
-        c->kids.clear();
-    }
     if (!c || !p)
     {
         return ACF_HIP_E_INVALID;
@@ -1732,15 +1732,15 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
     }
     const size_t n = size_t(p->nTrees) * p->nTreeNodes;
     c->p = *p;
-    c->ldcf.filters.clear();
+    c->ldcfFilters.clear();
     c->p.ldcfK = ldcf ? p->ldcfK : 0;
     c->p.ldcfFilters = nullptr;
     if (ldcf)
     {
         const int dcol = p->colorSpace == ACF_HIP_CS_GRAY ? 1 : 3;
         const int nC = (p->colorEnabled ? dcol : 0) + (p->gradMagEnabled ? 1 : 0) + (p->gradHistEnabled ? p->nOrients : 0);
-        c->ldcf.filters.assign(p->ldcfFilters, p->ldcfFilters + size_t(p->ldcfK) * nC * 25);
-        c->p.ldcfFilters = c->ldcf.filters.data();
+        c->ldcfFilters.assign(p->ldcfFilters, p->ldcfFilters + size_t(p->ldcfK) * nC * 25);
+        c->p.ldcfFilters = c->ldcfFilters.data();
     }
     c->fids.assign(p->fids, p->fids + n);
     c->thrs.assign(p->thrs, p->thrs + n);
@@ -1761,7 +1761,7 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
     if (c->hasPlan)
     {
         (void)hipStreamSynchronize(c->stream);
-        freeAll(c);
+        dropPlan(c); // (built for the previous model; a refused model, above, leaves it and the children as they were)
     }
     return ACF_HIP_OK;
 }
@@ -1772,29 +1772,17 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
 
 #include "plan_build.hip.h" // acf_hip_plan's stages (PlanBuild), after the helpers they call
 
-int acf_hip_plan(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_hits)
+// acf_hip_plan's work on a context that dropPlan has just left without a plan
+static int planFresh(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_hits)
 {
-    dropGraph(c);
-    if (int rc = needModel(c, "plan")) return rc;
-    if (max_batch <= 0 || max_hits <= 0)
-    {
-        return fail(c, ACF_HIP_E_INVALID, "plan: max_batch/max_hits");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)acf_hip_stream_close(c); // its slots are sized by the plan
-    freeAll(c);
     const acf_hip_params& p = c->p;
     int rc = buildPlan(p, H, W, d_in, c->plan, c->err);
     if (rc)
     {
         return rc;
     }
-    for (acf_hip_ctx* k : c->kids)
-    {
-        (void)acf_hip_destroy(k);
-    }
-    c->kids.clear();
+    c->maxBatch = max_batch;
+    c->maxHits = max_hits;
     if (c->nStreams > 1 && max_batch >= 2 * c->nStreams && c->evFork && int(c->evJoin.size()) >= c->nStreams)
     {
         // sub-batch contexts: this context keeps only the plan's geometry; every device buffer lives in a child
@@ -1816,11 +1804,6 @@ int acf_hip_plan(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_
                 return fail(c, rc, k->err);
             }
         }
-        c->maxBatch = max_batch;
-        c->maxHits = max_hits;
-        c->hasPlan = true;
-        c->pyramidValid = c->detectValid = false;
-        c->lastBatch = 0;
         return ACF_HIP_OK;
     }
     // smoothing radii the recursion kernel implements (convTri.cpp:215-218)
@@ -1839,8 +1822,6 @@ int acf_hip_plan(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_
     {
         return rc;
     }
-    c->maxBatch = max_batch;
-    c->maxHits = max_hits;
     PlanBuild b(c, H, W, d_in, max_batch, max_hits);
     if ((rc = b.colourBuffer()) || (rc = b.realScales()) || (rc = b.imageStrips()) || (rc = b.approxLevels()) || (rc = b.finalJobs()) || (rc = b.levelJobs()) ||
         (rc = b.ldcf()) || (rc = b.uploadAndScratch()) || (rc = b.cascade()))
@@ -1848,9 +1829,28 @@ int acf_hip_plan(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_
         return rc;
     }
     c->h_counts.assign(size_t(max_batch), 0);
+    return ACF_HIP_OK;
+}
+
+int acf_hip_plan(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_hits)
+{
+    dropGraph(c);
+    if (int rc = needModel(c, "plan")) return rc;
+    if (max_batch <= 0 || max_hits <= 0)
+    {
+        return fail(c, ACF_HIP_E_INVALID, "plan: max_batch/max_hits");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    (void)acf_hip_stream_close(c); // its slots are sized by the plan
+    dropPlan(c);
+    // (a plan refused from here on leaves none: what it had built goes at once)
+    if (const int rc = planFresh(c, H, W, d_in, max_batch, max_hits))
+    {
+        dropPlan(c);
+        return rc;
+    }
     c->hasPlan = true;
-    c->pyramidValid = c->detectValid = false;
-    c->lastBatch = 0;
     return ACF_HIP_OK;
 }
 
@@ -2090,14 +2090,13 @@ int acf_hip_detect(acf_hip_ctx* c)
     return ACF_HIP_OK;
 }
 
-// Host-side state after a replayed (or just captured) run: what runPyramid / runCascade's host code would have left.
-static void graphRunState(acf_hip_ctx* c, const acf_hip_ctx::GraphSlot& gs)
+// A captured run replayed: the launches, then the host-side state that pyramidBody / acf_hip_detect's host code left at the capture
+// (the batch and both results valid, which pyramids were written, the counts on the host not this run's)
+static int graphReplay(acf_hip_ctx* c, const acf_hip_ctx::GraphSlot& gs)
 {
-    c->lastBatch = gs.n;
-    c->pyramidValid = c->detectValid = true;
-    c->ranksValid = gs.ranksValid;
-    c->floatPyramid = gs.floatPyramid;
-    c->countsFetched = false; // the counts on the host are the previous run's
+    HIPCHK(c, hipGraphLaunch(gs.exec, c->stream));
+    static_cast<LastRun&>(*c) = gs.after;
+    return ACF_HIP_OK;
 }
 
 // acf_hip_run knows that the cascade follows the pyramid: the tiled cascade's counters (hit counts; its queue's count and head and the
@@ -2150,12 +2149,10 @@ int acf_hip_run(acf_hip_ctx* c, const float* frames, int nF)
     {
         for (auto& gs : c->graphs)
         {
-            if (gs.exec && gs.frames == frames && gs.n == nF)
+            if (gs.exec && gs.frames == frames && gs.after.lastBatch == nF)
             {
                 HIPCHK(c, hipSetDevice(c->device));
-                HIPCHK(c, hipGraphLaunch(gs.exec, c->stream));
-                graphRunState(c, gs);
-                return ACF_HIP_OK;
+                return graphReplay(c, gs);
             }
         }
     }
@@ -2188,13 +2185,9 @@ int acf_hip_run(acf_hip_ctx* c, const float* frames, int nF)
         if (ok)
         {
             gs.frames = frames;
-            gs.n = nF;
-            gs.ranksValid = c->ranksValid;
-            gs.floatPyramid = c->floatPyramid;
+            gs.after = static_cast<const LastRun&>(*c);
             c->graphNext = (c->graphNext + 1) % acf_hip_ctx::GRAPH_SLOTS;
-            HIPCHK(c, hipGraphLaunch(gs.exec, c->stream));
-            graphRunState(c, gs);
-            return ACF_HIP_OK;
+            return graphReplay(c, gs);
         }
         (void)hipGetLastError();
         gs = acf_hip_ctx::GraphSlot();
@@ -2274,25 +2267,24 @@ int acf_hip_stream_close(acf_hip_ctx* c)
             (void)hipEventDestroy(s.evDone);
         }
     }
-    c->slots.clear();
     if (c->copyStream)
     {
         (void)hipStreamDestroy(c->copyStream);
-        c->copyStream = nullptr;
     }
+    static_cast<StreamFront&>(*c) = StreamFront{};
     return ACF_HIP_OK;
 }
 
-// The slots of a stream (device input, device and pinned records, events) for batches of up to max_batch frames of frameBytes each;
-// replaces an open stream
-static int streamSlots(acf_hip_ctx* c, int64_t frameBytes, int cap, int depth)
+// A stream for batches of `src`: its slots (device input, device and pinned records, events) for up to max_batch frames of frameBytes
+// each; replaces an open stream
+static int streamSlots(acf_hip_ctx* c, const FrameSource& src, int64_t frameBytes, int cap, int depth)
 {
     acf_hip_stream_close(c);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
+    c->stSrc = src;
     c->stFrameBytes = frameBytes;
     c->stCap = cap;
-    c->nextTicket = c->nextCollect = 0;
     c->slots.resize(size_t(depth));
     const size_t inBytes = size_t(c->maxBatch) * size_t(frameBytes);
     const size_t recBytes = size_t(c->maxBatch) * (1 + 6 * size_t(cap)) * sizeof(int32_t);
@@ -2303,7 +2295,6 @@ static int streamSlots(acf_hip_ctx* c, int64_t frameBytes, int cap, int depth)
         HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.h_rec), recBytes, hipHostMallocDefault));
         HIPCHK(c, hipEventCreateWithFlags(&s.evH2D, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&s.evDone, hipEventDisableTiming));
-        s.ticket = -1;
     }
     return ACF_HIP_OK;
 }
@@ -2330,8 +2321,7 @@ int acf_hip_stream_open(acf_hip_ctx* c, int pix, int rowStride, int cap, int dep
     {
         return fail(c, ACF_HIP_E_INVALID, "stream_open: the plan's input planes (d) must be 3 for colour layouts (NV12 / NV21 included) and 1 for GRAY");
     }
-    c->stSrc = FrameSource{ SRC_U8, nullptr, "pyramid_u8", pix, g.stride };
-    return streamSlots(c, g.frameStride, cap, depth);
+    return streamSlots(c, FrameSource{ SRC_U8, nullptr, "pyramid_u8", pix, g.stride }, g.frameStride, cap, depth);
 }
 
 // The general open for frames described by three planes: every exported stream_open_yuv* / _video call is one call of it that fills in
@@ -2391,8 +2381,7 @@ static int streamOpenYuv(acf_hip_ctx* c, const char* who, const acf_hip_yuv_desc
     // (a batch runs under the name of the pyramid entry of its geometry)
     src.who = src.resized ? (orient ? "pyramid_yuv_oriented_resized" : "pyramid_yuv_resized") : (orient ? "pyramid_yuv_oriented" : "pyramid_yuv");
     src.yuv = *desc;
-    c->stSrc = src;
-    return streamSlots(c, frameBytes, cap, depth);
+    return streamSlots(c, src, frameBytes, cap, depth);
 }
 
 int acf_hip_stream_open_yuv(acf_hip_ctx* c, const acf_hip_yuv_desc* desc, int64_t frameBytes, int cap, int depth)

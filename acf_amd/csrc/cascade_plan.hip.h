@@ -491,10 +491,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
     {
         return rc;
     }
-    // ---- LDS-tiled path (kernels.hip.h): a tile set is kept only where its kernels take it
-    cs.tiles = TileSet{};
-    cs.tilesR = TileSet{};
-    cs.codes = LeafCodes{};
+    // ---- LDS-tiled path (kernels.hip.h): a tile set is kept only where its kernels take it (the caller's state is a fresh one: none yet)
     const bool tiled = p.treeDepth >= 1 && p.treeDepth <= 4 && p.stride % cell == 0 && p.stride >= cell;
     if (!packed && p.treeDepth >= 1 && p.treeDepth <= 4 && p.nTrees > 128 && !fallbackForced(FB_NO_TAIL_CODES))
     {

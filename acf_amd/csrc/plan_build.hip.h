@@ -66,8 +66,6 @@ int PlanBuild::realScales()
     int rc = ACF_HIP_OK;
     (void)rc;
     // real scales: mirror the reference's shallow-copy bookkeeping (chnsPyramid.cpp:297-338)
-    c->h_descs.clear();
-    c->real.clear();
     int curH = H, curW = W;
     for (size_t k = 0; k < pl.real.size(); k++)
     {
@@ -210,7 +208,6 @@ int PlanBuild::approxLevels()
     // approximated levels (chnsPyramid.cpp:385-397)
     const int nColor = p.colorEnabled ? d : 0;
     const int nMag = p.gradMagEnabled ? 1 : 0;
-    c->approxMaxBlocks = 0;
     for (size_t i = 0; i < pl.levels.size(); i++)
     {
         const acf_hip_level& l = pl.levels[i];
@@ -255,8 +252,6 @@ int PlanBuild::finalJobs()
     (void)rc;
     // final smoothing + padding jobs (chnsPyramid.cpp:399-435)
     int64_t rankOff = 0; // the rank pyramid's layout (rankPitch): levels in order, nChns planes [wP][pitch] each
-    c->finalMaxH = 0;
-    c->padMaxElems = 0;
     py = p.pad_h / shrink;
     px = p.pad_w / shrink;
     for (size_t i = 0; i < pl.levels.size(); i++)
@@ -312,7 +307,6 @@ int PlanBuild::levelJobs()
         // acf_hip_get_level_forms' words: every decision below leaves its bit on the level it was made for
         c->levelFormFused.assign(pl.levels.size(), 0);
         c->levelFormRaw.assign(pl.levels.size(), 0);
-        std::fill(c->levelCallForm, c->levelCallForm + ACF_HIP_LF_HEAD, 0);
         auto notFused = [&](size_t level, int32_t why) {
             c->fusedOk = false;
             c->levelFormFused[level] |= why;
@@ -404,7 +398,6 @@ int PlanBuild::levelJobs()
                 flat.push_back(k.j);
             }
             *nAll = int(all.size());
-            groups.clear();
             for (const auto& k : rest)
             {
                 if (groups.empty() || groups.back().R * 8 + groups.back().mode != k.key)
@@ -550,7 +543,7 @@ int PlanBuild::ldcf()
             return rc;
         }
     }
-    if ((rc = devUpload(c, &L.d_jobs, jobs)) || (rc = devUpload(c, &L.d_filt, L.filters)) ||
+    if ((rc = devUpload(c, &L.d_jobs, jobs)) || (rc = devUpload(c, &L.d_filt, c->ldcfFilters)) ||
         (L.tiles == 0 && (rc = devAlloc(c, &L.d_tmp, size_t(B) * L.tmpFloats + 64))) || (rc = devAlloc(c, &L.d_pyr, size_t(B) * L.floats + 64)))
     {
         return rc;

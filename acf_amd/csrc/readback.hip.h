@@ -422,21 +422,21 @@ int acf_hip_profile_get(acf_hip_ctx* c, int* n, const char** names, float* ms, i
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the side streams were joined into it)
     for (size_t i = 0; i + 1 < c->evUsed; i++)
     {
-        const char* name = c->evName[i];
-        if (!strcmp(name, "(end)"))
+        const acf_hip_ctx::ProfMark& m = c->evPool[i];
+        if (!strcmp(m.name, "(end)"))
         {
             continue;
         }
         // the kernel ends where the next event of the same stream was recorded (real scales run on their own streams)
         size_t j = i + 1;
-        while (j < c->evUsed && c->evStream[j] != c->evStream[i])
+        while (j < c->evUsed && c->evPool[j].stream != m.stream)
         {
             j++;
         }
         float dt = 0;
-        if (j < c->evUsed && hipEventElapsedTime(&dt, c->evPool[i], c->evPool[j]) == hipSuccess)
+        if (j < c->evUsed && hipEventElapsedTime(&dt, m.ev, c->evPool[j].ev) == hipSuccess)
         {
-            tot.add(name, dt, 1);
+            tot.add(m.name, dt, 1);
         }
     }
     c->evUsed = 0;
