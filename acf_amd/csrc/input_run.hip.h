@@ -419,7 +419,7 @@ static const char* video16DescBad(const void* base, const acf_hip_yuv_desc& d)
 
 // The constants of a (checked) format: round(2^20 * q), half away from zero, q the exact rational from Kr / Kb with the luma gain
 // 255 / 219 and the chroma gain 255 / 224 for limited range (tests/video_format_ref.py derives them again with fractions.Fraction);
-// BT.601 limited keeps cvtColor's (from coefficients rounded to three decimals): yuv_chroma / yuv_rgb8's own
+// BT.601 limited keeps cvtColor's (from coefficients rounded to three decimals): yuv_chroma / yuv_rgb's own
 static YuvCoef yuvCoef(const acf_hip_yuv_format& f)
 {
     static const int table[3][2][5] = {

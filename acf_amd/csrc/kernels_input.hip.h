@@ -262,14 +262,17 @@ __device__ __forceinline__ void ingest_store(const IngestArgs& a, const float (&
     }
 }
 
-// The store phase of a 64 x 64 tile of packed bytes in LDS (pitch IG_PITCH; r, g, b at ro, go, bo of a pixel's cpp bytes): a lane takes
-// four consecutive image-y of one image-x through the model's colour conversion and writes one float4 a plane.  k_ingest_u8's, and
-// k_ingest_resized's behind its resize.  (Rows beyond the tile convert whatever the LDS holds — bytes, so in range: never stored.)
-template <int MODE>
-__device__ __forceinline__ void ingest_store_tile(const IngestArgs& a, const uint8_t* tile, int cpp, int ro, int go, int bo, int x0, int y0, int nx, int ny)
+// The store phase every ingest kernel ends in, behind the barrier that closes its load phase: of the workgroup's 64 x 64 tile (nx x ny
+// at the frame's edges) a lane takes four consecutive image-y, yq .. yq + 3, of one image-x, xx, through the model's colour conversion
+// and writes one float4 a plane (coalesced along image-y).  px(xx, yq, j, r, g, b) yields the already-scaled f32 r, g, b of tile pixel
+// (yq + j, xx); it is called with j = 0 .. 3 in turn for one xx, so a kernel's functor may carry state from one j to the next (the
+// chroma sample of a subsampled row pair).  Rows >= ny of the last quad are converted like the others and never stored, so px must
+// yield something the conversion takes there too (rgb2luv indexes a table): bytes and clamped integers are in range whatever the LDS
+// holds; a float tile yields zeros.
+template <int MODE, class PX>
+__device__ __forceinline__ void ingest_store_phase(const IngestArgs& a, int x0, int y0, int nx, int ny, PX&& px)
 {
     const int yq = (threadIdx.x & 15) * 4;
-    const float sc = float(1.0 / 255.0);
     float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
     const int64_t np = int64_t(a.H) * a.W;
     for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
@@ -278,13 +281,26 @@ __device__ __forceinline__ void ingest_store_tile(const IngestArgs& a, const uin
 #pragma unroll
         for (int j = 0; j < 4; j++)
         {
-            const int yy = min(yq + j, IG_T - 1);
-            const uint8_t* px = tile + yy * IG_PITCH + xx * cpp;
-            const float r = float(px[ro]) * sc, g = float(px[go]) * sc, b = float(px[bo]) * sc;
+            float r, g, b;
+            px(xx, yq, j, r, g, b);
             ingest_convert<MODE>(a, r, g, b, o, j);
         }
         ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
     }
+}
+
+// The store phase on a 64 x 64 tile of packed bytes in LDS (pitch IG_PITCH; r, g, b at ro, go, bo of a pixel's cpp bytes): k_ingest_u8's,
+// and the resized kernels' behind their resize.
+template <int MODE>
+__device__ __forceinline__ void ingest_store_tile(const IngestArgs& a, const uint8_t* tile, int cpp, int ro, int go, int bo, int x0, int y0, int nx, int ny)
+{
+    ingest_store_phase<MODE>(a, x0, y0, nx, ny, [&](int xx, int yq, int j, float& r, float& g, float& b) {
+        const float sc = float(1.0 / 255.0);
+        const uint8_t* p = tile + min(yq + j, IG_T - 1) * IG_PITCH + xx * cpp;
+        r = float(p[ro]) * sc;
+        g = float(p[go]) * sc;
+        b = float(p[bo]) * sc;
+    });
 }
 
 template <int MODE, bool ALIGNED>
@@ -443,6 +459,79 @@ __device__ __forceinline__ int im_slot(int r)
     return (r & 3) * 16 + (r >> 2);
 }
 
+// IM_PACKED: `rows` rows (sy elements apart) of npx interleaved pixels of sx (3 or 4) elements, r, g, b at 0, 1, 2 of a pixel (rev:
+// at 2, 1, 0), the first row's first addressed element at `span`.  A row's addressed span [0, L) is read as the aligned dwords that
+// hold a piece of it — a wave takes a row, its lanes the row's dwords in turn (four rows a pass; two passes' loads in flight); a dword
+// over one end of the span element by element — and every element goes to place(plane, row, pixel, raw element).
+template <int DT, class PLACE>
+__device__ __forceinline__ void im_load_packed(const typename ImgElem<DT>::raw* span, int64_t sy, int npx, int sx, int rev, int rows, PLACE&& place)
+{
+    using raw = typename ImgElem<DT>::raw;
+    constexpr int PER = 4 / int(sizeof(raw));          // elements a dword
+    const int L = (npx - 1) * sx + 3;                  // elements a row addresses
+    const int ndMax = (L * int(sizeof(raw)) + 6) >> 2; // dwords that can hold a piece of it, whatever the row's alignment
+#pragma unroll 2
+    for (int i = threadIdx.x >> 6; i < rows; i += 4)
+    {
+        const raw* rp = span + int64_t(i) * sy;
+        const int mis = int(reinterpret_cast<uintptr_t>(rp) & 3) / int(sizeof(raw)); // elements of rp's dword in front of rp
+        for (int d = threadIdx.x & 63; d < ndMax; d += 64)
+        {
+            const int e0 = d * PER - mis; // span index of dword d's first element
+            if (e0 >= L)
+            {
+                continue;
+            }
+            raw v[PER];
+            if (e0 >= 0 && e0 + PER <= L)
+            {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(rp + e0);
+#pragma unroll
+                for (int t = 0; t < PER; t++)
+                {
+                    v[t] = raw(w >> (8 * int(sizeof(raw)) * t));
+                }
+            }
+            else
+            {
+#pragma unroll
+                for (int t = 0; t < PER; t++) // a dword over one end of the span: only the elements inside it
+                {
+                    const int e = e0 + t;
+                    v[t] = (e >= 0 && e < L) ? rp[e] : raw(0);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < PER; t++)
+            {
+                const int e = e0 + t;
+                if (e >= 0 && e < L)
+                {
+                    const int x = sx == 4 ? e >> 2 : e / 3, m = e - x * sx;
+                    if (m < 3) // (m == 3: the skipped fourth element)
+                    {
+                        place(rev ? 2 - m : m, i, x, v[t]);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The store phase on the float tile (both image kernels; the reads' banks are derived above)
+template <int MODE>
+__device__ __forceinline__ void im_store_phase(const IngestArgs& a, const float* tile, int nIn, int x0, int y0, int nx, int ny)
+{
+    const int p1 = nIn == 3 ? IM_PLANE : 0, p2 = 2 * p1; // one plane: r = g = b (chnsPyramid.cpp:234-244)
+    ingest_store_phase<MODE>(a, x0, y0, nx, ny, [&](int xx, int yq, int j, float& r, float& g, float& b) {
+        const float* t = tile + im_slot(yq + j) * IM_PITCH + xx;
+        const bool in = yq + j < ny; // (the LDS of rows beyond the tile was never written)
+        r = in ? t[0] : 0.f;
+        g = in ? t[p1] : 0.f;
+        b = in ? t[p2] : 0.f;
+    });
+}
+
 template <int DT, int MODE>
 __global__ void __launch_bounds__(256) k_ingest_image(IngestArgs a, ImageArgs s)
 {
@@ -498,59 +587,9 @@ __global__ void __launch_bounds__(256) k_ingest_image(IngestArgs a, ImageArgs s)
     else if (s.form == IM_PACKED)
     {
         // sc == +-1, sx == 3 or 4, three planes; the base is a multiple of the element size (host-checked)
-        constexpr int PER = 4 / int(sizeof(raw)); // elements a dword
-        const int rev = s.sc < 0, sx = int(s.sx);
-        const int L = (nx - 1) * sx + 3;          // elements the row addresses in this tile: [0, L) from `span`
-        const raw* span = src - (rev ? 2 : 0);
-        const int ndMax = (L * int(sizeof(raw)) + 6) >> 2; // dwords that can hold a piece of it, whatever the row's alignment
-        // a wave takes a row, its lanes the row's dwords in turn (four rows a pass; two passes' loads in flight)
-#pragma unroll 2
-        for (int yy = threadIdx.x >> 6; yy < ny; yy += 4)
-        {
-            const raw* rp = span + int64_t(yy) * s.sy;
-            const int mis = int(reinterpret_cast<uintptr_t>(rp) & 3) / int(sizeof(raw)); // elements of rp's dword in front of rp
-            float* trow = tile + im_slot(yy) * IM_PITCH;
-            for (int j = threadIdx.x & 63; j < ndMax; j += 64)
-            {
-                const int e0 = j * PER - mis; // span index of dword j's first element
-                if (e0 >= L)
-                {
-                    continue;
-                }
-                raw v[PER];
-                if (e0 >= 0 && e0 + PER <= L)
-                {
-                    const uint32_t w = *reinterpret_cast<const uint32_t*>(rp + e0);
-#pragma unroll
-                    for (int t = 0; t < PER; t++)
-                    {
-                        v[t] = raw(w >> (8 * int(sizeof(raw)) * t));
-                    }
-                }
-                else
-                {
-#pragma unroll
-                    for (int t = 0; t < PER; t++) // a dword over one end of the span: only the elements inside it
-                    {
-                        const int e = e0 + t;
-                        v[t] = (e >= 0 && e < L) ? rp[e] : raw(0);
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < PER; t++)
-                {
-                    const int e = e0 + t;
-                    if (e >= 0 && e < L)
-                    {
-                        const int x = sx == 4 ? e >> 2 : e / 3, m = e - x * sx;
-                        if (m < 3) // (m == 3: the skipped fourth element)
-                        {
-                            trow[(rev ? 2 - m : m) * IM_PLANE + x] = E::cvt(v[t]);
-                        }
-                    }
-                }
-            }
-        }
+        const int rev = s.sc < 0;
+        im_load_packed<DT>(src - (rev ? 2 : 0), s.sy, nx, int(s.sx), rev, ny,
+            [&](int c, int i, int x, raw v) { tile[c * IM_PLANE + im_slot(i) * IM_PITCH + x] = E::cvt(v); });
     }
     else
     {
@@ -571,24 +610,7 @@ __global__ void __launch_bounds__(256) k_ingest_image(IngestArgs a, ImageArgs s)
         }
     }
     __syncthreads();
-    const int k16 = threadIdx.x & 15, yq = k16 * 4;
-    const int p1 = s.nIn == 3 ? IM_PLANE : 0, p2 = 2 * p1; // one plane: r = g = b (chnsPyramid.cpp:234-244)
-    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
-    const int64_t np = int64_t(a.H) * a.W;
-    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
-    {
-        float o[3][4];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-        {
-            // rows beyond the tile convert zeros (the LDS there was never written; rgb2luv indexes a table): never stored
-            const float* t = tile + (j * 16 + k16) * IM_PITCH + xx;
-            const bool in = yq + j < ny;
-            const float r = in ? t[0] : 0.f, g = in ? t[p1] : 0.f, b = in ? t[p2] : 0.f;
-            ingest_convert<MODE>(a, r, g, b, o, j);
-        }
-        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
-    }
+    im_store_phase<MODE>(a, tile, s.nIn, x0, y0, nx, ny);
 }
 
 // ------------------------------------------------------------------------
@@ -597,57 +619,55 @@ __global__ void __launch_bounds__(256) k_ingest_image(IngestArgs a, ImageArgs s)
 // imgproc/src/color_yuv.simd.hpp restated (BT.601 limited range, 20-bit fixed point, int32, arithmetic shift; the chroma pair of a
 // 2 x 2 block shared by its four pixels, no interpolation) — PARITY UNPINNED.
 // Frame: H rows of W luma bytes, rowStride apart; at chromaOff H / 2 rows of W / 2 byte pairs (U, V; vFirst: V, U), same stride.
+//
+// The ONE statement of that formula, for every acf_hip_yuv_format (the video entries) and sample width:
+//   CF   false: the default format, {8, 0, BT601, 0}, with cvtColor's constants inline — immediates, so every default instantiation is
+//        the kernel it was before there were formats; true: the constants of acf_hip_yuv_coeffs, an argument (YuvCoef)
+//   ACC  int for 8-bit samples: int32 holds every sum for all six matrix / range rows (|219 * CY| + 2^19 + |CUB| * 128 < 2^31);
+//        int64_t above: 20 fractional bits and 16-bit samples do not fit int32 ((1023 - 64) * CY + CUB * 512 > 2^31), so the sums are
+//        64-bit (a v_mad_i64_i32 for the luma term, 64-bit adds and shifts behind it)
 // ------------------------------------------------------------------------
-struct YuvChroma
-{
-    int ruv, guv, buv;
-};
-__device__ __forceinline__ YuvChroma yuv_chroma(int u, int v)
-{
-    u -= 128;
-    v -= 128;
-    return { (1 << 19) + 1673527 * v, (1 << 19) - 852492 * v - 409993 * u, (1 << 19) + 2116026 * u };
-}
-__device__ __forceinline__ void yuv_rgb8(int Y, const YuvChroma& c, int& r, int& g, int& b)
-{
-    const int y = max(0, Y - 16) * 1220542;
-    r = min(max((y + c.ruv) >> 20, 0), 255);
-    g = min(max((y + c.guv) >> 20, 0), 255);
-    b = min(max((y + c.buv) >> 20, 0), 255);
-}
-
-// The same conversion for any acf_hip_yuv_format (the video entries): the constants of acf_hip_yuv_coeffs as an argument.  CF == false is
-// the default format, {8, 0, BT601, 0}: the two functions above with their constants inline, so every default instantiation is the kernel
-// it was.  8 bits: int32 holds every sum for all six matrix / range rows (|219 * CY| + 2^19 + |CUB| * 128 < 2^31).
 struct YuvCoef
 {
     int yoff, cmid, omax;
     int cy, cvr, cvg, cug, cub;
     float sc; // float(1.0 / omax): a sample as a plane value
 };
-template <bool CF>
-__device__ __forceinline__ YuvChroma yuv_chroma(int u, int v, const YuvCoef& k)
+template <class ACC>
+struct YuvChromaT
 {
-    if (!CF)
-    {
-        return yuv_chroma(u, v);
-    }
-    u -= k.cmid;
-    v -= k.cmid;
-    return { (1 << 19) + k.cvr * v, (1 << 19) + k.cvg * v + k.cug * u, (1 << 19) + k.cub * u };
+    ACC ruv, guv, buv;
+};
+using YuvChroma = YuvChromaT<int>;
+template <class T>
+using YuvAcc = std::conditional_t<sizeof(T) == 1, int, int64_t>; // by sample type
+template <bool CF, class ACC = int>
+__device__ __forceinline__ YuvChromaT<ACC> yuv_chroma(int u, int v, const YuvCoef& k)
+{
+    const ACC cvr = CF ? k.cvr : 1673527, cvg = CF ? k.cvg : -852492, cug = CF ? k.cug : -409993, cub = CF ? k.cub : 2116026;
+    u -= CF ? k.cmid : 128;
+    v -= CF ? k.cmid : 128;
+    return { (1 << 19) + cvr * v, (1 << 19) + cvg * v + cug * u, (1 << 19) + cub * u };
 }
-template <bool CF>
-__device__ __forceinline__ void yuv_rgb8(int Y, const YuvChroma& c, const YuvCoef& k, int& r, int& g, int& b)
+// R, G, B in [0, omax].  |sum| < 2^38 (16-bit samples, constants below 2^22), so sum >> 20 fits int32: the clamp is a 32-bit one
+template <bool CF, class ACC>
+__device__ __forceinline__ void yuv_rgb(int Y, const YuvChromaT<ACC>& c, const YuvCoef& k, int& r, int& g, int& b)
 {
-    if (!CF)
-    {
-        yuv_rgb8(Y, c, r, g, b);
-        return;
-    }
-    const int y = max(0, Y - k.yoff) * k.cy;
-    r = min(max((y + c.ruv) >> 20, 0), k.omax);
-    g = min(max((y + c.guv) >> 20, 0), k.omax);
-    b = min(max((y + c.buv) >> 20, 0), k.omax);
+    const int omax = CF ? k.omax : 255;
+    const ACC y = ACC(max(0, Y - (CF ? k.yoff : 16))) * (CF ? k.cy : 1220542);
+    r = min(max(int((y + c.ruv) >> 20), 0), omax);
+    g = min(max(int((y + c.guv) >> 20), 0), omax);
+    b = min(max(int((y + c.buv) >> 20), 0), omax);
+}
+// ... as the plane values a store phase's px yields: the integers times sc = float(1.0 / omax)
+template <bool CF, class ACC>
+__device__ __forceinline__ void yuv_px(int Y, const YuvChromaT<ACC>& c, const YuvCoef& k, float sc, float& r, float& g, float& b)
+{
+    int R, G, B;
+    yuv_rgb<CF>(Y, c, k, R, G, B);
+    r = float(R) * sc;
+    g = float(G) * sc;
+    b = float(B) * sc;
 }
 
 struct YuvSrc
@@ -672,7 +692,7 @@ __global__ void __launch_bounds__(256) k_yuv420_to_rgb8(YuvSrc s, uint8_t* __res
     }
     const uint8_t* __restrict__ F = s.in + int64_t(blockIdx.z) * s.in_fs;
     const uint8_t* __restrict__ C = F + s.chromaOff + int64_t(by) * s.rowStride + 2 * bx;
-    const YuvChroma c = yuv_chroma(C[s.vFirst], C[1 - s.vFirst]);
+    const YuvChroma c = yuv_chroma<false>(C[s.vFirst], C[1 - s.vFirst], s.k);
     uint8_t* __restrict__ D = dst + int64_t(blockIdx.z) * s.H * s.W * 3;
 #pragma unroll
     for (int j = 0; j < 2; j++)
@@ -683,7 +703,7 @@ __global__ void __launch_bounds__(256) k_yuv420_to_rgb8(YuvSrc s, uint8_t* __res
         for (int i = 0; i < 2; i++)
         {
             int r, g, b;
-            yuv_rgb8(L[i], c, r, g, b);
+            yuv_rgb<false>(L[i], c, s.k, r, g, b);
             d[3 * i] = uint8_t(r);
             d[3 * i + 1] = uint8_t(g);
             d[3 * i + 2] = uint8_t(b);
@@ -751,6 +771,8 @@ __global__ void __launch_bounds__(256) k_ingest_yuv420(IngestArgs a, YuvSrc s)
         }
     }
     __syncthreads();
+    // ingest_store_phase written out for this kernel (kept apart deliberately: profiles/ingest_refactor.md): the chroma pair of a 2 x 2
+    // block once for its two rows
     const int yq = (threadIdx.x & 15) * 4;
     const float sc = float(1.0 / 255.0);
     float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
@@ -761,7 +783,6 @@ __global__ void __launch_bounds__(256) k_ingest_yuv420(IngestArgs a, YuvSrc s)
 #pragma unroll
         for (int i = 0; i < 2; i++)
         {
-            // rows beyond the tile (yq + 2i >= ny) convert whatever the LDS holds: never stored
             const uint8_t* cp = tile + yg_chroma_slot((yq >> 1) + i) * YG_PITCH + (xx & ~1);
             const YuvChroma c = yuv_chroma<CF>(cp[s.vFirst], cp[1 - s.vFirst], s.k);
 #pragma unroll
@@ -769,7 +790,7 @@ __global__ void __launch_bounds__(256) k_ingest_yuv420(IngestArgs a, YuvSrc s)
             {
                 const int j = 2 * i + jj;
                 int r, g, b;
-                yuv_rgb8<CF>(tile[yg_luma_slot(yq + j) * YG_PITCH + xx], c, s.k, r, g, b);
+                yuv_rgb<CF>(tile[yg_luma_slot(yq + j) * YG_PITCH + xx], c, s.k, r, g, b);
                 ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
             }
         }
@@ -779,7 +800,7 @@ __global__ void __launch_bounds__(256) k_ingest_yuv420(IngestArgs a, YuvSrc s)
 
 // ------------------------------------------------------------------------
 // YUV frames of three planes, each with its own offset and byte strides (acf_hip_yuv_desc: I420 / YV12 / I422 / I444 planar, YUYV /
-// UYVY / YVYU packed 4:2:2, NV12 / NV21, separately allocated planes, odd sizes) -> 8-bit R, G, B by yuv_chroma / yuv_rgb8 above.
+// UYVY / YVYU packed 4:2:2, NV12 / NV21, separately allocated planes, odd sizes) -> 8-bit R, G, B by yuv_chroma / yuv_rgb above.
 // Pixel (r, c) of frame n: Y at y.off + n * y.sn + r * y.sr + c * y.sp, U and V likewise at (r >> subY, c >> subX): no interpolation.
 // The cvtColor codes for I420 / YV12 / YUY2 / UYVY / YVYU share the fixed-point helpers of NV12 / NV21 in OpenCV's published
 // imgproc/src/color_yuv.simd.hpp; I422 / I444 are the same per-pixel formula — PARITY UNPINNED.
@@ -820,7 +841,7 @@ __global__ void __launch_bounds__(256) k_yuv_to_rgb8(YuvDescSrc s, int rows, int
     const int U = B[s.u.off + n * s.u.sn + int64_t(cr) * s.u.sr + int64_t(cc) * s.u.sp];
     const int V = B[s.v.off + n * s.v.sn + int64_t(cr) * s.v.sr + int64_t(cc) * s.v.sp];
     int R, G, Bl;
-    yuv_rgb8<CF>(Y, yuv_chroma<CF>(U, V, s.k), s.k, R, G, Bl);
+    yuv_rgb<CF>(Y, yuv_chroma<CF>(U, V, s.k), s.k, R, G, Bl);
     uint8_t* d = dst + ((n * rows + r) * cols + c) * 3;
     d[0] = uint8_t(R);
     d[1] = uint8_t(G);
@@ -857,39 +878,61 @@ __global__ void __launch_bounds__(256) k_yuv_to_rgb8(YuvDescSrc s, int rows, int
 // serialise, and the SQ_LDS_BANK_CONFLICT counter: not measured.)  3 x 64 x 17 dwords = 13056 bytes.
 // ------------------------------------------------------------------------
 constexpr int YD_TILE = IG_T * YG_PITCH; // bytes between the Y, U and V tiles
+constexpr int Y16_PITCH = 66;               // k_ingest_yuv16's tiles (their layout is derived there): samples; 33 dwords
+constexpr int Y16_TILE = IG_T * Y16_PITCH;  // samples between the Y, U and V tiles
+// The tiles by sample type: T = uint8_t (k_ingest_yuv) or uint16_t (k_ingest_yuv16)
+template <class T>
+struct YdTile
+{
+    static constexpr int PER = 4 / int(sizeof(T));                      // samples a dword
+    static constexpr int PITCH = sizeof(T) == 1 ? YG_PITCH : Y16_PITCH; // samples
+    static constexpr int TILE = IG_T * PITCH;                           // samples between the Y, U and V tiles
+};
 
 __device__ __forceinline__ int yd_slot(int r, int subY)
 {
     return subY ? (r & 1) * 16 + (r >> 1) : (r & 3) * 16 + (r >> 2);
 }
 
-// YD_PLANAR: rows x nb bytes of one plane (first byte p, sr apart) to a tile; 1 << lg dwords a tile row, PASSES * 256 >= rows << lg
-// (constant trip counts, so that the loads of all the passes are in flight together)
-template <int PASSES>
-__device__ __forceinline__ void yd_load_rows_vec(const uint8_t* __restrict__ p, int64_t sr, int rows, int nb, int lg, int slotSubY, uint32_t* tileW)
+// YD_PLANAR / YD16_PLANAR: rows x ns samples of one plane (first byte p, sr bytes apart) to a tile of T; 1 << lg dwords a tile row,
+// PASSES * 256 >= rows << lg (constant trip counts, so that the loads of all the passes are in flight together).  The samples behind a
+// row's last whole dword: bytes one by one; of 16-bit words there is one, read as one 16-bit load.  16-bit words are shifted and masked
+// on the way in (shift, mask: not read for bytes).
+template <class T, int PASSES>
+__device__ __forceinline__ void yd_load_rows_vec(const uint8_t* __restrict__ p, int64_t sr, int rows, int ns, int lg, int slotSubY, int shift, uint32_t mask,
+    uint32_t* tileW)
 {
+    constexpr int PER = YdTile<T>::PER;
 #pragma unroll
     for (int pass = 0; pass < PASSES; pass++)
     {
         const int i = threadIdx.x + pass * 256;
         const int row = i >> lg, j = i & ((1 << lg) - 1);
-        if (row < rows && 4 * j < nb)
+        if (row < rows && PER * j < ns)
         {
             const uint8_t* rp = p + int64_t(row) * sr + 4 * j;
             uint32_t v;
-            if (4 * j + 4 <= nb)
+            if (PER * j + PER <= ns)
             {
                 v = *reinterpret_cast<const uint32_t*>(rp);
+            }
+            else if constexpr (sizeof(T) == 2)
+            {
+                v = uint32_t(*reinterpret_cast<const uint16_t*>(rp));
             }
             else
             {
                 v = 0;
-                for (int b = 0; b < nb - 4 * j; b++) // the row's tail: byte by byte
+                for (int b = 0; b < ns - 4 * j; b++)
                 {
                     v |= uint32_t(rp[b]) << (8 * b);
                 }
             }
-            tileW[yd_slot(row, slotSubY) * (YG_PITCH / 4) + j] = v;
+            if constexpr (sizeof(T) == 2)
+            {
+                v = (((v & 0xffffu) >> shift) & mask) | ((((v >> 16) >> shift) & mask) << 16);
+            }
+            tileW[yd_slot(row, slotSubY) * (YdTile<T>::PITCH / PER) + j] = v;
         }
     }
 }
@@ -907,6 +950,44 @@ __device__ __forceinline__ void yd_load_rows_generic(const uint8_t* __restrict__
     }
 }
 
+// YD_PACKED422: the macropixel at rp (four bytes: Y0 at yPos, Y1 two further, U and V at uPos, vPos) as one dword when `whole`; else
+// — an odd row's last pixel — the three bytes of its first half only (Y1 = 0)
+__device__ __forceinline__ void yd_macropixel(const uint8_t* rp, bool whole, const YuvDescSrc& s, uint32_t& Y0, uint32_t& Y1, uint32_t& U, uint32_t& V)
+{
+    if (whole)
+    {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(rp);
+        Y0 = (w >> (8 * s.yPos)) & 255;
+        Y1 = (w >> (8 * s.yPos + 16)) & 255;
+        U = (w >> (8 * s.uPos)) & 255;
+        V = (w >> (8 * s.vPos)) & 255;
+    }
+    else
+    {
+        Y0 = rp[s.yPos];
+        Y1 = 0;
+        U = rp[s.uPos];
+        V = rp[s.vPos];
+    }
+}
+
+// The store phase on three tiles (Y, U, V) of T, chroma at the planes' own resolution: k_ingest_yuv's and k_ingest_yuv16's.  sc: float(1.0 / omax)
+template <int MODE, bool CF, class T>
+__device__ __forceinline__ void yd_store_phase(const IngestArgs& a, const YuvDescSrc& s, const T* tile, float sc, int x0, int y0, int nx, int ny)
+{
+    constexpr int PITCH = YdTile<T>::PITCH, TILE = YdTile<T>::TILE;
+    const int subX = s.subX, subY = s.subY;
+    YuvChromaT<YuvAcc<T>> c{}; // of the chroma row that tile row yq + j lies in: kept from one j to the next
+    ingest_store_phase<MODE>(a, x0, y0, nx, ny, [&](int xx, int yq, int j, float& r, float& g, float& b) {
+        if (j == 0 || (j >> subY) != ((j - 1) >> subY)) // a new chroma row (uniform: subY is)
+        {
+            const int at = yd_slot((yq + j) >> subY, subY) * PITCH + (xx >> subX);
+            c = yuv_chroma<CF, YuvAcc<T>>(tile[TILE + at], tile[2 * TILE + at], s.k);
+        }
+        yuv_px<CF>(tile[yd_slot(yq + j, 0) * PITCH + xx], c, s.k, sc, r, g, b);
+    });
+}
+
 template <int MODE, int FORM, bool CF = false>
 __global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
 {
@@ -921,7 +1002,6 @@ __global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
     {
         // subX == 1, subY == 0; the three planes share sr and sn; base + mp, sr, sn are multiples of 4 (host-checked) and x0 * 2 is
         const uint8_t* src = s.base + s.mp + n * s.y.sn + int64_t(y0) * s.y.sr + int64_t(x0) * 2;
-        const int sy0 = 8 * s.yPos, su = 8 * s.uPos, sv = 8 * s.vPos;
         uint16_t* tile16 = reinterpret_cast<uint16_t*>(tile);
 #pragma unroll 4
         for (int pass = 0; pass < IG_T * 32 / 256; pass++)
@@ -932,21 +1012,7 @@ __global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
             {
                 const uint8_t* rp = src + int64_t(row) * s.y.sr + 4 * q;
                 uint32_t Y0, Y1, U, V;
-                if (2 * q + 1 < nx)
-                {
-                    const uint32_t w = *reinterpret_cast<const uint32_t*>(rp);
-                    Y0 = (w >> sy0) & 255;
-                    Y1 = (w >> (sy0 + 16)) & 255;
-                    U = (w >> su) & 255;
-                    V = (w >> sv) & 255;
-                }
-                else
-                {
-                    Y0 = rp[s.yPos]; // an odd row's last pixel: its three bytes only
-                    Y1 = 0;
-                    U = rp[s.uPos];
-                    V = rp[s.vPos];
-                }
+                yd_macropixel(rp, 2 * q + 1 < nx, s, Y0, Y1, U, V);
                 const int at = yd_slot(row, 0) * YG_PITCH;
                 tile16[(at >> 1) + q] = uint16_t(Y0 | (Y1 << 8));
                 tile[YD_TILE + at + q] = uint8_t(U);
@@ -962,9 +1028,9 @@ __global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
         if (FORM == YD_PLANAR)
         {
             // sp == 1; base + off, sr, sn of every plane are multiples of 4 (host-checked) and x0 >> subX is a multiple of 32
-            yd_load_rows_vec<4>(py, s.y.sr, ny, nx, 4, 0, tileW);
-            yd_load_rows_vec<4>(pu, s.u.sr, cny, cnx, 4 - subX, subY, tileW + YD_TILE / 4);
-            yd_load_rows_vec<4>(pv, s.v.sr, cny, cnx, 4 - subX, subY, tileW + 2 * YD_TILE / 4);
+            yd_load_rows_vec<uint8_t, 4>(py, s.y.sr, ny, nx, 4, 0, 0, 0, tileW);
+            yd_load_rows_vec<uint8_t, 4>(pu, s.u.sr, cny, cnx, 4 - subX, subY, 0, 0, tileW + YD_TILE / 4);
+            yd_load_rows_vec<uint8_t, 4>(pv, s.v.sr, cny, cnx, 4 - subX, subY, 0, 0, tileW + 2 * YD_TILE / 4);
         }
         else
         {
@@ -974,29 +1040,7 @@ __global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
         }
     }
     __syncthreads();
-    const int yq = (threadIdx.x & 15) * 4;
-    const float sc = float(1.0 / 255.0);
-    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
-    const int64_t np = int64_t(a.H) * a.W;
-    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
-    {
-        float o[3][4];
-        YuvChroma c{};
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-        {
-            // rows beyond the tile (yq + j >= ny) convert whatever the LDS holds (8-bit R, G, B whatever it is): never stored
-            if (j == 0 || (j >> subY) != ((j - 1) >> subY)) // a new chroma row (uniform: subY is)
-            {
-                const int at = yd_slot((yq + j) >> subY, subY) * YG_PITCH + (xx >> subX);
-                c = yuv_chroma<CF>(tile[YD_TILE + at], tile[2 * YD_TILE + at], s.k);
-            }
-            int r, g, b;
-            yuv_rgb8<CF>(tile[yd_slot(yq + j, 0) * YG_PITCH + xx], c, s.k, r, g, b);
-            ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
-        }
-        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
-    }
+    yd_store_phase<MODE, CF>(a, s, tile, float(1.0 / 255.0), x0, y0, nx, ny);
 }
 
 // ------------------------------------------------------------------------
@@ -1007,25 +1051,6 @@ __global__ void __launch_bounds__(256) k_ingest_yuv(IngestArgs a, YuvDescSrc s)
 // it); plane value = float(R) * float(1.0 / omax), so the planes are those of k_ingest_image on a tight packed float32 RGB image
 // holding these values, bit for bit.  H.273 gives the matrices; there is no OpenCV counterpart — PARITY UNPINNED.
 // ------------------------------------------------------------------------
-struct YuvChroma64
-{
-    int64_t ruv, guv, buv;
-};
-__device__ __forceinline__ YuvChroma64 yuv16_chroma(int u, int v, const YuvCoef& k)
-{
-    u -= k.cmid;
-    v -= k.cmid;
-    return { (1 << 19) + int64_t(k.cvr) * v, (1 << 19) + int64_t(k.cvg) * v + int64_t(k.cug) * u, (1 << 19) + int64_t(k.cub) * u };
-}
-__device__ __forceinline__ void yuv16_rgb(int Y, const YuvChroma64& c, const YuvCoef& k, int& r, int& g, int& b)
-{
-    // |sum| < 2^38 (16-bit samples, constants below 2^22), so sum >> 20 fits int32: the clamp is a 32-bit one on the same integers
-    const int64_t y = int64_t(max(0, Y - k.yoff)) * k.cy;
-    r = min(max(int((y + c.ruv) >> 20), 0), k.omax);
-    g = min(max(int((y + c.guv) >> 20), 0), k.omax);
-    b = min(max(int((y + c.buv) >> 20), 0), k.omax);
-}
-
 struct Yuv16Src
 {
     YuvDescSrc yuv;    // byte offsets and strides, all even (host-checked); yuv.k: the format's constants
@@ -1040,6 +1065,7 @@ enum
 };
 
 // The conversion alone for more than 8 bits: tight packed [rows][cols][3] per frame, uint16 samples in [0, omax].  One thread a pixel.
+// (k_yuv_to_rgb8 with 16-bit words and the 64-bit accumulator; the two are kept apart deliberately: profiles/ingest_refactor.md)
 __global__ void __launch_bounds__(256) k_video_to_rgb16(Yuv16Src S, int rows, int cols, uint16_t* __restrict__ dst)
 {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), r = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -1055,7 +1081,7 @@ __global__ void __launch_bounds__(256) k_video_to_rgb16(Yuv16Src S, int rows, in
         return (int(*reinterpret_cast<const uint16_t*>(B + p.off + n * p.sn + int64_t(pr) * p.sr + int64_t(pc) * p.sp)) >> S.shift) & S.mask;
     };
     int R, G, Bl;
-    yuv16_rgb(at(s.y, r, c), yuv16_chroma(at(s.u, cr, cc), at(s.v, cr, cc), s.k), s.k, R, G, Bl);
+    yuv_rgb<true>(at(s.y, r, c), yuv_chroma<true, int64_t>(at(s.u, cr, cc), at(s.v, cr, cc), s.k), s.k, R, G, Bl);
     uint16_t* d = dst + ((n * rows + r) * cols + c) * 3;
     d[0] = uint16_t(R);
     d[1] = uint16_t(G);
@@ -1089,30 +1115,6 @@ __global__ void __launch_bounds__(256) k_video_to_rgb16(Yuv16Src S, int rows, in
 // (degrees derived from the address maps with the bank rule; whether 16-bit writes of two lanes to one dword serialise, and the
 // SQ_LDS_BANK_CONFLICT counter: not measured.)  3 x 64 x 33 dwords = 25344 bytes: six workgroups a CU by LDS.  By the compiler's resource
 // report (-Rpass-analysis=kernel-resource-usage, gfx950; all twelve instantiations): 35 .. 44 VGPRs, 63 .. 88 SGPRs, no scratch, 6 waves a SIMD.
-constexpr int Y16_PITCH = 66;                // samples; 33 dwords
-constexpr int Y16_TILE = IG_T * Y16_PITCH;   // samples between the Y, U and V tiles
-
-// YD16_PLANAR: rows x ns samples of one plane (first byte p, sr bytes apart) to a tile; 1 << lg dwords a tile row; PASSES * 256 >=
-// rows << lg (constant trip counts, so that the loads of all the passes are in flight together)
-template <int PASSES>
-__device__ __forceinline__ void y16_load_rows_vec(const uint8_t* __restrict__ p, int64_t sr, int rows, int ns, int lg, int slotSubY, int shift, uint32_t mask,
-    uint32_t* tileW)
-{
-#pragma unroll
-    for (int pass = 0; pass < PASSES; pass++)
-    {
-        const int i = threadIdx.x + pass * 256;
-        const int row = i >> lg, j = i & ((1 << lg) - 1);
-        if (row < rows && 2 * j < ns)
-        {
-            const uint8_t* rp = p + int64_t(row) * sr + 4 * j;
-            // the row's last sample when ns is odd: its 16 bits only
-            const uint32_t w = (2 * j + 2 <= ns) ? *reinterpret_cast<const uint32_t*>(rp) : uint32_t(*reinterpret_cast<const uint16_t*>(rp));
-            tileW[yd_slot(row, slotSubY) * (Y16_PITCH / 2) + j] = (((w & 0xffffu) >> shift) & mask) | ((((w >> 16) >> shift) & mask) << 16);
-        }
-    }
-}
-
 // YD16_GENERIC: rows x cols samples of one plane (sp bytes apart in a row); 1 << lg lanes a tile row
 __device__ __forceinline__ void y16_load_rows_generic(const uint8_t* __restrict__ p, int64_t sr, int64_t sp, int rows, int cols, int lg, int slotSubY, int shift,
     int mask, uint16_t* tile)
@@ -1147,14 +1149,14 @@ __global__ void __launch_bounds__(256) k_ingest_yuv16(IngestArgs a, Yuv16Src S)
     if (FORM == YD16_PLANAR)
     {
         // sp == 2; base + off, sr, sn of every plane are multiples of 4 (host-checked) and (x0 >> subX) * 2 is
-        y16_load_rows_vec<8>(py, s.y.sr, ny, nx, 5, 0, shift, uint32_t(mask), tileW);
-        y16_load_rows_vec<8>(pu, s.u.sr, cny, cnx, 5 - subX, subY, shift, uint32_t(mask), tileW + Y16_TILE / 2);
-        y16_load_rows_vec<8>(pv, s.v.sr, cny, cnx, 5 - subX, subY, shift, uint32_t(mask), tileW + 2 * (Y16_TILE / 2));
+        yd_load_rows_vec<uint16_t, 8>(py, s.y.sr, ny, nx, 5, 0, shift, uint32_t(mask), tileW);
+        yd_load_rows_vec<uint16_t, 8>(pu, s.u.sr, cny, cnx, 5 - subX, subY, shift, uint32_t(mask), tileW + Y16_TILE / 2);
+        yd_load_rows_vec<uint16_t, 8>(pv, s.v.sr, cny, cnx, 5 - subX, subY, shift, uint32_t(mask), tileW + 2 * (Y16_TILE / 2));
     }
     else if (FORM == YD16_PAIRS)
     {
         // luma as planar; chroma: u.sp == v.sp == 4, the two planes 2 bytes apart with one sr and sn, the lower one 4-aligned with base
-        y16_load_rows_vec<8>(py, s.y.sr, ny, nx, 5, 0, shift, uint32_t(mask), tileW);
+        yd_load_rows_vec<uint16_t, 8>(py, s.y.sr, ny, nx, 5, 0, shift, uint32_t(mask), tileW);
         const uint8_t* pc = S.vFirst ? pv : pu; // the pair's first word
         const int lg = 6 - subX;
 #pragma unroll 4
@@ -1178,29 +1180,7 @@ __global__ void __launch_bounds__(256) k_ingest_yuv16(IngestArgs a, Yuv16Src S)
         y16_load_rows_generic(pv, s.v.sr, s.v.sp, cny, cnx, 6 - subX, subY, shift, mask, tile + 2 * Y16_TILE);
     }
     __syncthreads();
-    const int yq = (threadIdx.x & 15) * 4;
-    const float sc = s.k.sc;
-    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
-    const int64_t np = int64_t(a.H) * a.W;
-    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
-    {
-        float o[3][4];
-        YuvChroma64 c{};
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-        {
-            // rows beyond the tile (yq + j >= ny) convert whatever the LDS holds: R, G, B are clamped to [0, omax] whatever it is: never stored
-            if (j == 0 || (j >> subY) != ((j - 1) >> subY)) // a new chroma row (uniform: subY is)
-            {
-                const int at = yd_slot((yq + j) >> subY, subY) * Y16_PITCH + (xx >> subX);
-                c = yuv16_chroma(tile[Y16_TILE + at], tile[2 * Y16_TILE + at], s.k);
-            }
-            int r, g, b;
-            yuv16_rgb(tile[yd_slot(yq + j, 0) * Y16_PITCH + xx], c, s.k, r, g, b);
-            ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
-        }
-        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
-    }
+    yd_store_phase<MODE, true>(a, s, tile, s.k.sc, x0, y0, nx, ny);
 }
 
 // ------------------------------------------------------------------------
@@ -1353,59 +1333,9 @@ __global__ void __launch_bounds__(256) k_ingest_image_oriented(IngestArgs a, Ima
     }
     else if (s.form == IM_PACKED)
     {
-        // sc == +-1, sx == 3 or 4, three planes; the base is a multiple of the element size (host-checked): k_ingest_image's IM_PACKED
-        // on the rectangle's rows
-        constexpr int PER = 4 / int(sizeof(raw)); // elements a dword
-        const int rev = s.sc < 0, sx = int(s.sx);
-        const int L = (T.nsc - 1) * sx + 3;       // elements a row of the rectangle addresses: [0, L) from `span`
-        const raw* span = rows + int64_t(T.cs0) * sx - (rev ? 2 : 0);
-        const int ndMax = (L * int(sizeof(raw)) + 6) >> 2; // dwords that can hold a piece of it, whatever the row's alignment
-#pragma unroll 2
-        for (int i = threadIdx.x >> 6; i < T.nsr; i += 4)
-        {
-            const raw* rp = span + int64_t(i) * s.sy;
-            const int mis = int(reinterpret_cast<uintptr_t>(rp) & 3) / int(sizeof(raw)); // elements of rp's dword in front of rp
-            for (int d = threadIdx.x & 63; d < ndMax; d += 64)
-            {
-                const int f0 = d * PER - mis; // span index of dword d's first element
-                if (f0 >= L)
-                {
-                    continue;
-                }
-                raw v[PER];
-                if (f0 >= 0 && f0 + PER <= L)
-                {
-                    const uint32_t w = *reinterpret_cast<const uint32_t*>(rp + f0);
-#pragma unroll
-                    for (int t = 0; t < PER; t++)
-                    {
-                        v[t] = raw(w >> (8 * int(sizeof(raw)) * t));
-                    }
-                }
-                else
-                {
-#pragma unroll
-                    for (int t = 0; t < PER; t++) // a dword over one end of the span: only the elements inside it
-                    {
-                        const int e = f0 + t;
-                        v[t] = (e >= 0 && e < L) ? rp[e] : raw(0);
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < PER; t++)
-                {
-                    const int e = f0 + t;
-                    if (e >= 0 && e < L)
-                    {
-                        const int x = sx == 4 ? e >> 2 : e / 3, m = e - x * sx;
-                        if (m < 3) // (m == 3: the skipped fourth element)
-                        {
-                            place(rev ? 2 - m : m, i, x, v[t]);
-                        }
-                    }
-                }
-            }
-        }
+        // k_ingest_image's IM_PACKED on the rectangle's rows
+        const int rev = s.sc < 0;
+        im_load_packed<DT>(rows + int64_t(T.cs0) * s.sx - (rev ? 2 : 0), s.sy, T.nsc, int(s.sx), rev, T.nsr, place);
     }
     else
     {
@@ -1425,25 +1355,7 @@ __global__ void __launch_bounds__(256) k_ingest_image_oriented(IngestArgs a, Ima
         }
     }
     __syncthreads();
-    // k_ingest_image's store phase
-    const int k16 = threadIdx.x & 15, yq = k16 * 4;
-    const int p1 = s.nIn == 3 ? IM_PLANE : 0, p2 = 2 * p1; // one plane: r = g = b (chnsPyramid.cpp:234-244)
-    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
-    const int64_t np = int64_t(a.H) * a.W;
-    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
-    {
-        float o[3][4];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-        {
-            // rows beyond the tile convert zeros (the LDS there was never written; rgb2luv indexes a table): never stored
-            const float* t = tile + (j * 16 + k16) * IM_PITCH + xx;
-            const bool in = yq + j < ny;
-            const float r = in ? t[0] : 0.f, g = in ? t[p1] : 0.f, b = in ? t[p2] : 0.f;
-            ingest_convert<MODE>(a, r, g, b, o, j);
-        }
-        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
-    }
+    im_store_phase<MODE>(a, tile, s.nIn, x0, y0, nx, ny);
 }
 
 // The YUV twin.  Load forms (YuvOrientedSrc::form, chosen on the host from the description and the base's alignment alone; all give
@@ -1578,7 +1490,6 @@ __global__ void __launch_bounds__(256) k_ingest_yuv_oriented(IngestArgs a, YuvOr
     {
         // subX == 1, subY == 0; the three planes share sr and sn; base + mp, sr, sn are multiples of 4 (host-checked)
         const uint8_t* src = s.base + s.mp + n * s.y.sn + int64_t(T.rs0) * s.y.sr;
-        const int sy0 = 8 * s.yPos, su = 8 * s.uPos, sv = 8 * s.vPos;
         const int m0 = T.cs0 >> 1, nm = ((T.cs0 + T.nsc - 1) >> 1) - m0 + 1; // the macropixels a row of the rectangle touches: <= 33
 #pragma unroll 2
         for (int idx = threadIdx.x; idx < T.nsr * IG_T; idx += 256)
@@ -1591,21 +1502,7 @@ __global__ void __launch_bounds__(256) k_ingest_yuv_oriented(IngestArgs a, YuvOr
             const int m = m0 + q;
             const uint8_t* rp = src + int64_t(i) * s.y.sr + 4 * int64_t(m);
             uint32_t Y[2], U, V;
-            if (2 * m + 1 < S.o.Ws)
-            {
-                const uint32_t w = *reinterpret_cast<const uint32_t*>(rp);
-                Y[0] = (w >> sy0) & 255;
-                Y[1] = (w >> (sy0 + 16)) & 255;
-                U = (w >> su) & 255;
-                V = (w >> sv) & 255;
-            }
-            else
-            {
-                Y[0] = rp[s.yPos]; // an odd row's last pixel: its three bytes only
-                Y[1] = 0;
-                U = rp[s.uPos];
-                V = rp[s.vPos];
-            }
+            yd_macropixel(rp, 2 * m + 1 < S.o.Ws, s, Y[0], Y[1], U, V);
 #pragma unroll
             for (int t = 0; t < 2; t++)
             {
@@ -1674,42 +1571,13 @@ __global__ void __launch_bounds__(256) k_ingest_yuv_oriented(IngestArgs a, YuvOr
         yo_load_generic(T, fv, s.v, subY, subX, tile + 2 * YD_TILE);
     }
     __syncthreads();
-    const int yq = (threadIdx.x & 15) * 4;
-    const float sc = float(1.0 / 255.0);
-    float* outF = a.out + int64_t(blockIdx.z) * a.out_fs;
-    const int64_t np = int64_t(a.H) * a.W;
     const YuvCoef k = CF ? *yo_coef_lds<CF>() : YuvCoef{};
-    for (int xx = threadIdx.x >> 4; xx < nx; xx += 16)
-    {
-        float o[3][4];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-        {
-            // rows beyond the tile (yq + j >= ny) convert whatever the LDS holds (8-bit R, G, B whatever it is): never stored
-            const int at = yd_slot(yq + j, 0) * YG_PITCH + xx;
-            int r, g, b;
-            yuv_rgb8<CF>(tile[at], yuv_chroma<CF>(tile[YD_TILE + at], tile[2 * YD_TILE + at], k), k, r, g, b);
-            ingest_convert<MODE>(a, float(r) * sc, float(g) * sc, float(b) * sc, o, j);
-        }
-        ingest_store<MODE>(a, o, outF + int64_t(x0 + xx) * a.H + y0 + yq, np, ny - yq);
-    }
+    ingest_store_phase<MODE>(a, x0, y0, nx, ny, [&](int xx, int yq, int j, float& r, float& g, float& b) {
+        const int at = yd_slot(yq + j, 0) * YG_PITCH + xx; // all three tiles are at the upright resolution
+        yuv_px<CF>(tile[at], yuv_chroma<CF>(tile[YD_TILE + at], tile[2 * YD_TILE + at], k), k, float(1.0 / 255.0), r, g, b);
+    });
 }
 
-// ------------------------------------------------------------------------
-// convTri1 with the pyramid's in-place aliasing (toolbox/convConst.cpp:445-525;
-// chnsCompute.cpp:239, chnsPyramid.cpp:404).
-//
-// Because source and destination are the same buffer in the reference, the
-// x tap of column i reads the OUTPUT of column i-1:
-//     T_i[y] = nrm*((O_{i-1}[y] + p*I_i[y]) + I_{i+1}[y])      (O_{-1} := I_0)
-//     O_i[y] = (T_i[y-1] + p*T_i[y]) + T_i[y+1]                (edges: (1+p)*T)
-// a recursion along image-x with a 3-tap exchange along image-y every step.
-// It cannot be tiled along x without changing bits, so one workgroup owns a
-// whole plane: threads run along y (R interleaved rows each), the previous
-// output column stays in registers (the kernel is out-of-place: it never
-// re-reads what it wrote), and the y exchange goes through a double-buffered
-// LDS column with one barrier per image column.
-// ------------------------------------------------------------------------
 // ------------------------------------------------------------------------
 // The apps' resize to a minimum object width (src/app/acf/acf.cpp:117-148 `Resizer`, GPUDetectionPipeline.cpp:250-266):
 // cv::resize of the packed 8-bit image by scale = winSize.width / minWidth, INTER_AREA when reducing, INTER_LINEAR else.
@@ -1892,7 +1760,7 @@ __global__ void __launch_bounds__(256) k_resize_u8(ResizeArgs a)
 //
 // k_ingest_u8's shape: a workgroup of 256 threads owns a 64 x 64 tile of the REDUCED image.
 //   phase 1  lanes run along reduced-image x (a wave = one tile row, 16 rows a wave): rz_pixel over a source accessor (the image's
-//            n / c / y / x element strides; or Y at (r, c), U and V at (r >> sub_y, c >> sub_x) through yuv_chroma / yuv_rgb8, once per
+//            n / c / y / x element strides; or Y at (r, c), U and V at (r >> sub_y, c >> sub_x) through yuv_chroma / yuv_rgb, once per
 //            source pixel for its three channels), the bytes into k_ingest_u8's LDS byte tile (pitch 260; r, g, b at 0, 1, 2 of 3)
 //   phase 2  ingest_store_tile: k_ingest_u8's store phase
 // No load touches a byte outside what the description addresses at the source size: rz_pixel reads source pixels inside
@@ -1929,7 +1797,7 @@ struct RzYuvSrcT
         const int Y = py[int64_t(y) * ysr + int64_t(x) * ysp];
         const int U = pu[int64_t(cr) * usr + int64_t(cc) * usp];
         const int V = pv[int64_t(cr) * vsr + int64_t(cc) * vsp];
-        yuv_rgb8<CF>(Y, yuv_chroma<CF>(U, V, k), k, v[0], v[1], v[2]);
+        yuv_rgb<CF>(Y, yuv_chroma<CF>(U, V, k), k, v[0], v[1], v[2]);
         v[3] = 0;
     }
 };
@@ -1946,6 +1814,38 @@ struct ResizedSrc
     YuvDescSrc yuv; // RS_YUV
     ResizeTaps t;
 };
+// rz_pixel's global accessor of frame n for SRC: of the image description, or of the YUV one
+template <int SRC>
+__device__ __forceinline__ auto rz_global_src(const ResizedSrc& s, int64_t n)
+{
+    if constexpr (SRC == RS_IMAGE)
+    {
+        return RzImageSrc{ static_cast<const uint8_t*>(s.im.in) + n * s.im.sn, s.im.sc, s.im.sy, s.im.sx, s.im.nIn };
+    }
+    else
+    {
+        const YuvDescSrc& d = s.yuv;
+        return RzYuvSrcT<SRC == RS_YUV_CF>{ d.base + d.y.off + n * d.y.sn, d.base + d.u.off + n * d.u.sn, d.base + d.v.off + n * d.v.sn, d.y.sr, d.y.sp, d.u.sr, d.u.sp,
+            d.v.sr, d.v.sp, d.subX, d.subY, d.k };
+    }
+}
+// Phase 1 of k_ingest_oriented_resized's two forms, for a lane with a tile column (lanes run along reduced-image x, a wave a tile row: xx = threadIdx.x & 63
+// < nx, which the caller checks before it builds `src`: with that check in here, by the compiler's resource report, the kernels took
+// 14 .. 18 more scalar registers and some lost a wave of occupancy): rz_pixel over `src` for rows yFirst, yFirst + 4, .. < yEnd of
+// column xx, the bytes into k_ingest_u8's byte tile as r, g, b at 0, 1, 2 of 3
+template <class SRC>
+__device__ __forceinline__ void rz_fill_tile(const SRC& src, const ResizeTaps& t, int cn, int x0, int y0, int xx, int yFirst, int yEnd, uint8_t* tile)
+{
+    for (int yy = yFirst; yy < yEnd; yy += 4)
+    {
+        uint8_t o[4];
+        rz_pixel(src, t, x0 + xx, y0 + yy, o);
+        uint8_t* p = tile + yy * IG_PITCH + 3 * xx;
+        p[0] = o[0];
+        p[1] = cn == 3 ? o[1] : o[0]; // one plane: r = g = b (chnsPyramid.cpp:234-244), as k_ingest_u8 reads a 1-byte pixel
+        p[2] = cn == 3 ? o[2] : o[0];
+    }
+}
 
 template <int SRC, int MODE>
 __global__ void __launch_bounds__(256) k_ingest_resized(IngestArgs a, ResizedSrc s)
@@ -1958,25 +1858,15 @@ __global__ void __launch_bounds__(256) k_ingest_resized(IngestArgs a, ResizedSrc
     const int xx = threadIdx.x & 63;
     if (xx < nx)
     {
+        // rz_fill_tile's loop written out, the accessor built inside it (kept apart deliberately: profiles/ingest_refactor.md)
         const int cn = SRC != RS_IMAGE ? 3 : s.im.nIn;
         for (int yy = threadIdx.x >> 6; yy < ny; yy += 4)
         {
             uint8_t o[4];
-            if (SRC != RS_IMAGE)
-            {
-                const YuvDescSrc& d = s.yuv;
-                const RzYuvSrcT<SRC == RS_YUV_CF> src{ d.base + d.y.off + n * d.y.sn, d.base + d.u.off + n * d.u.sn, d.base + d.v.off + n * d.v.sn, d.y.sr, d.y.sp, d.u.sr,
-                    d.u.sp, d.v.sr, d.v.sp, d.subX, d.subY, d.k };
-                rz_pixel(src, s.t, x0 + xx, y0 + yy, o);
-            }
-            else
-            {
-                const RzImageSrc src{ static_cast<const uint8_t*>(s.im.in) + n * s.im.sn, s.im.sc, s.im.sy, s.im.sx, s.im.nIn };
-                rz_pixel(src, s.t, x0 + xx, y0 + yy, o);
-            }
+            rz_pixel(rz_global_src<SRC>(s, n), s.t, x0 + xx, y0 + yy, o);
             uint8_t* t = tile + yy * IG_PITCH + 3 * xx;
             t[0] = o[0];
-            t[1] = cn == 3 ? o[1] : o[0]; // one plane: r = g = b (chnsPyramid.cpp:234-244), as k_ingest_u8 reads a 1-byte pixel
+            t[1] = cn == 3 ? o[1] : o[0]; // one plane: r = g = b, as rz_fill_tile
             t[2] = cn == 3 ? o[2] : o[0];
         }
     }
@@ -2002,7 +1892,7 @@ __global__ void __launch_bounds__(256) k_ingest_resized(IngestArgs a, ResizedSrc
 //              plane (a 2 x-subsampled chroma plane: one 16-bit load); else one pixel a lane, byte loads.  A word is loaded whole only
 //              when all of it lies inside the row of its plane ([0, Ws), chroma [0, ceil(Ws / 2))), else its bytes inside one by one:
 //              no load covers an address outside the [first, last] span of the row and plane it belongs to.  YUV goes through
-//              yuv_chroma / yuv_rgb8 here, once per source pixel (chroma at (rs >> subY, cs >> subX))
+//              yuv_chroma / yuv_rgb here, once per source pixel (chroma at (rs >> subY, cs >> subX))
 //   stage      pixel (i, j) of the rectangle is ONE dword r | g << 8 | b << 16 (one plane: the byte) at i * pitch + j, pitch = nsc | 1
 //   resize     rz_pixel, unchanged, over RzStageSrc, which applies the orientation in its index arithmetic (base + y * ay + x * ax:
 //              ay, ax are +-pitch and +-1, swapped for quarter turns); lanes along reduced-image x, a wave a row, the bytes into
@@ -2202,7 +2092,7 @@ __device__ __forceinline__ void os_stage_yuv(const YuvDescSrc& s, int64_t n, con
                 {
                     const int ct = 8 * (t >> subX);
                     int r, g, b;
-                    yuv_rgb8<CF>(int((Y >> (8 * t)) & 255), yuv_chroma<CF>(int((U >> ct) & 255), int((V >> ct) & 255), s.k), s.k, r, g, b);
+                    yuv_rgb<CF>(int((Y >> (8 * t)) & 255), yuv_chroma<CF>(int((U >> ct) & 255), int((V >> ct) & 255), s.k), s.k, r, g, b);
                     stage[i * pitch + j] = uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(b) << 16);
                 }
             }
@@ -2219,7 +2109,7 @@ __device__ __forceinline__ void os_stage_yuv(const YuvDescSrc& s, int64_t n, con
             const int U = fu[int64_t(cr) * s.u.sr + int64_t(cc) * s.u.sp];
             const int V = fv[int64_t(cr) * s.v.sr + int64_t(cc) * s.v.sp];
             int r, g, b;
-            yuv_rgb8<CF>(Y, yuv_chroma<CF>(U, V, s.k), s.k, r, g, b);
+            yuv_rgb<CF>(Y, yuv_chroma<CF>(U, V, s.k), s.k, r, g, b);
             stage[i * pitch + j] = uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(b) << 16);
         }
     }
@@ -2237,35 +2127,12 @@ __global__ void __launch_bounds__(256) k_ingest_oriented_resized(IngestArgs a, O
     const int64_t n = blockIdx.z;
     const int xx = threadIdx.x & 63;
     const int cn = SRC != RS_IMAGE ? 3 : S.r.im.nIn;
-    const auto put = [&](int yy, const uint8_t (&o)[4]) {
-        uint8_t* t = tile + yy * IG_PITCH + 3 * xx;
-        t[0] = o[0];
-        t[1] = cn == 3 ? o[1] : o[0]; // one plane: r = g = b, as k_ingest_resized
-        t[2] = cn == 3 ? o[2] : o[0];
-    };
     if (!STAGED)
     {
         if (xx < nx)
         {
-            for (int yy = threadIdx.x >> 6; yy < ny; yy += 4)
-            {
-                uint8_t o[4];
-                if (SRC != RS_IMAGE)
-                {
-                    const YuvDescSrc& d = S.r.yuv;
-                    const RzOrientedSrc<RzYuvSrcT<SRC == RS_YUV_CF>> src{ { d.base + d.y.off + n * d.y.sn, d.base + d.u.off + n * d.u.sn, d.base + d.v.off + n * d.v.sn, d.y.sr,
-                                                                             d.y.sp, d.u.sr, d.u.sp, d.v.sr, d.v.sp, d.subX, d.subY, d.k },
-                        S.o };
-                    rz_pixel(src, tp, x0 + xx, y0 + yy, o);
-                }
-                else
-                {
-                    const ImageArgs& im = S.r.im;
-                    const RzOrientedSrc<RzImageSrc> src{ { static_cast<const uint8_t*>(im.in) + n * im.sn, im.sc, im.sy, im.sx, im.nIn }, S.o };
-                    rz_pixel(src, tp, x0 + xx, y0 + yy, o);
-                }
-                put(yy, o);
-            }
+            const RzOrientedSrc<decltype(rz_global_src<SRC>(S.r, n))> src{ rz_global_src<SRC>(S.r, n), S.o };
+            rz_fill_tile(src, tp, cn, x0, y0, xx, threadIdx.x >> 6, ny, tile);
         }
     }
     else
@@ -2305,12 +2172,7 @@ __global__ void __launch_bounds__(256) k_ingest_oriented_resized(IngestArgs a, O
             const RzStageSrc src{ stage, base, T.swap ? sC : sR * pitch, T.swap ? sR * pitch : sC };
             if (xx < nx)
             {
-                for (int yy = yb + (threadIdx.x >> 6); yy < yb + nb; yy += 4)
-                {
-                    uint8_t o[4];
-                    rz_pixel(src, tp, x0 + xx, y0 + yy, o);
-                    put(yy, o);
-                }
+                rz_fill_tile(src, tp, cn, x0, y0, xx, yb + (threadIdx.x >> 6), yb + nb, tile);
             }
         }
     }
@@ -2318,6 +2180,21 @@ __global__ void __launch_bounds__(256) k_ingest_oriented_resized(IngestArgs a, O
     ingest_store_tile<MODE>(a, tile, 3, 0, 1, 2, x0, y0, nx, ny);
 }
 
+// ------------------------------------------------------------------------
+// convTri1 with the pyramid's in-place aliasing (toolbox/convConst.cpp:445-525;
+// chnsCompute.cpp:239, chnsPyramid.cpp:404).
+//
+// Because source and destination are the same buffer in the reference, the
+// x tap of column i reads the OUTPUT of column i-1:
+//     T_i[y] = nrm*((O_{i-1}[y] + p*I_i[y]) + I_{i+1}[y])      (O_{-1} := I_0)
+//     O_i[y] = (T_i[y-1] + p*T_i[y]) + T_i[y+1]                (edges: (1+p)*T)
+// a recursion along image-x with a 3-tap exchange along image-y every step.
+// It cannot be tiled along x without changing bits, so one workgroup owns a
+// whole plane: threads run along y (R interleaved rows each), the previous
+// output column stays in registers (the kernel is out-of-place: it never
+// re-reads what it wrote), and the y exchange goes through a double-buffered
+// LDS column with one barrier per image column.
+// ------------------------------------------------------------------------
 struct SmoothJob
 {
     int32_t h, w, nplanes, out_cs; // out_cs: destination column stride (hP)

@@ -42,6 +42,19 @@ def _cases():
     add("u8_nchw_hsv", 120, 160, capi.T_U8, 3, "rgb", dict(name="INRIA", nTrees=64, nOctUp=0, colorSpace=capi.CS_HSV, cascThr=-3.0), _nchw(3, 120, 160))
     # packed BGR: the pointer at the R of the first pixel, channels backwards
     add("bgr_negative_stride", 96, 128, capi.T_F32, 3, "luv", _TINY, (96 * 128 * 3, -1, 128 * 3, 3), base=2)
+    # 3 x 3 ragged tiles with a ragged width of 6 (not a multiple of 16), through conversions and load forms the rows above do not pair:
+    # packed bytes into the vector rgb2luv body (H % 4 == 0: float4 stores); every second f16 element of a row (the element-wise form)
+    # into rgb2gray (H % 4 == 2: scalar stores, a last quad of two rows)
+    add("u8_nhwc_luv_vec_ragged", 132, 134, capi.T_U8, 3, "rgb", dict(name="INRIA", nTrees=64, nOctUp=0, cascThr=-2.5), (132 * 134 * 3, 1, 134 * 3, 3))
+    add("f16_stride2_gray_ragged", 130, 134, capi.T_F16, 3, "rgb", dict(name="FACE64", nTrees=128, minDs_h=32, minDs_w=32, cascThr=-4.0),
+        (3 * 130 * 134 * 2, 130 * 134 * 2, 134 * 2, 2))
+    # the element type x conversion pairs no row above takes: element-wise and packed at 132 x 134, then the row-vector form on rows of 136
+    # (four-element aligned, a ragged width of 8)
+    add("bf16_stride2_luv_vec_ragged", 132, 134, capi.T_BF16, 3, "rgb", dict(name="INRIA", nTrees=64, nOctUp=0, cascThr=-2.5),
+        (3 * 132 * 134 * 2, 132 * 134 * 2, 134 * 2, 2))
+    add("f16_nhwc_luv_vec_ragged", 132, 134, capi.T_F16, 3, "rgb", dict(name="INRIA", nTrees=64, nOctUp=0, cascThr=-2.5), (132 * 134 * 3, 1, 134 * 3, 3))
+    add("f32_nchw_gray_ragged", 130, 136, capi.T_F32, 3, "rgb", dict(name="FACE64", nTrees=128, minDs_h=32, minDs_w=32, cascThr=-4.0), _nchw(3, 130, 136))
+    add("bf16_nchw_isluv_ragged", 130, 136, capi.T_BF16, 3, "luv", _TINY, _nchw(3, 130, 136))
     return out
 
 

@@ -19,12 +19,15 @@ MODELS = {
 TILES3 = (130, 174)   # three tiles each way, ragged edges, H % 4 == 2
 ODD = (131, 175)      # H * W % 4 == 1: the scalar rgb2luv body; ceil-sized chroma planes
 THIN = (40, 203)      # one tile or less along an axis
+VEC3 = (132, 136)     # three tiles each way, ragged edges of 4 and 8, H % 4 == 0 in every orientation: float4 stores
 SUB_NAME = {(1, 1): "i420", (1, 0): "i422", (0, 0): "i444"}
 
 # (model, source size, class) of every reference the GPU tests take: class = (sub_x, sub_y) for RGB from YUV planes of that
 # subsampling, "gray" for one plane, "f16" / "bf16" for the 4:4:4 RGB as rounded float elements
 USED = [("inria", TILES3, (1, 1)), ("inria", TILES3, (1, 0)), ("inria", TILES3, (0, 0)), ("face64", TILES3, "gray"), ("inria", TILES3, "f16"),
-        ("inria", TILES3, "bf16"), ("inria", ODD, (1, 1)), ("inria", ODD, (1, 0)), ("inria", ODD, (0, 0)), ("tiny", THIN, (1, 1)), ("tiny", THIN, (0, 0))]
+        ("inria", TILES3, "bf16"), ("inria", ODD, (1, 1)), ("inria", ODD, (1, 0)), ("inria", ODD, (0, 0)), ("tiny", THIN, (1, 1)), ("tiny", THIN, (0, 0)),
+        ("tiny", TILES3, "f16"), ("face64", TILES3, "bf16"), ("face64", ODD, (1, 1)), ("face64", ODD, (1, 0)),
+        ("tiny", THIN, (1, 0)), ("tiny", VEC3, "f16"), ("face64", VEC3, "bf16"), ("face64", VEC3, (1, 1))]
 
 
 @functools.lru_cache(maxsize=None)

@@ -33,6 +33,9 @@ CASES = [
     ("bgr_packed_half", 240, 320, 120, 160, 0.5, "area_int", "bgr", FACE80, 3),              # stride_c -1, stride_x 3, base + 2
     ("rgba_linear_up_hsv", 240, 320, 300, 400, S64, "linear", "rgba", FACE80_HSV, 3),       # alpha skipped; the d_stage route
     ("gray_064", 240, 320, 154, 205, 0.64, "area", "gray", FACE64, 1),
+    # (both reduce to two whole 64-pixel tiles and a ragged one on each axis)
+    ("i420_gray_frac", 246, 326, 131, 174, S150, "area", "i420", FACE64, 3),                # rgb2gray on a YUV frame's R, G, B
+    ("nchw_odd_037", 353, 359, 131, 133, 0.37, "area", "nchw", FACE80_RGB, 3),              # an image into the scalar rgb2luv, no float4
 ]
 IDS = [c[0] for c in CASES]
 YUV_INPUTS = ("i420", "nv12", "yuyv_padded", "i444_odd", "three_planes")

@@ -144,6 +144,7 @@ def test_stream_matches_blocking_calls(oracle, depth):
     for x in batches:
         det.run_u8(torch.from_numpy(x).cuda(), pix)
         dst = torch.zeros((x.shape[0], 1 + 6 * cap), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                                          # (torch fills dst on its own stream: before the export writes it)
         det.export_detections(dst, cap)
         det.synchronize()
         want.append(dst.cpu().numpy())

@@ -150,11 +150,15 @@ def _layouts(size):
         "window_unaligned_f32": ("inria", capi.T_F32, _float_src(size, capi.T_F32), (3 * (R + 8) * (P + 24), (R + 8) * (P + 24), P + 24, 1), 3 * (P + 24) + 1,
                                  N * 3 * (R + 8) * (P + 24), False, capi.T_F32),
         "gray_one_plane_u8": ("face64", capi.T_U8, u8[:, 1:2], (R * P, 0, P, 1), 0, None, True, "gray"),
+        # the store phase's other two conversions behind load forms the rows above do not take them through: packed f16 pixels into a
+        # model that takes its planes as they are; every second bf16 element of a row (element-wise loads) into rgb2gray on three planes
+        "packed_f16_isluv": ("tiny", capi.T_F16, _float_src(size, capi.T_F16), (R * Cc * 3, 1, Cc * 3, 3), 0, None, True, capi.T_F16),
+        "stride2_bf16_gray": ("face64", capi.T_BF16, _float_src(size, capi.T_BF16), (3 * R * Cc * 2, R * Cc * 2, Cc * 2, 2), 0, None, False, capi.T_BF16),
     }
 
 
 LAYOUT_IDS = ["nchw_f32", "channels_last_u8", "packed_bgr_u8", "rgba_alpha_skipped_u8", "f16_padded_rows", "bf16_padded_rows", "window_unaligned_f32",
-              "gray_one_plane_u8"]
+              "gray_one_plane_u8", "packed_f16_isluv", "stride2_bf16_gray"]
 
 
 def _run_layout(dets, size, lid, code, entry="run"):
@@ -210,6 +214,16 @@ def test_run_tensor_orient_keyword(dets):
 def test_tensor_odd_source_size(dets, lid, code):
     """131 x 175: H * W % 4 == 1 (the scalar rgb2luv body), a row tail of three elements, scalar plane stores."""
     det, want, names, form = _run_layout(dets, oc.ODD, lid, code)
+    same(snapshot(det), want, (lid, code))
+    if code:
+        assert ingest_names(names) == [form], (names, form)
+
+
+@pytest.mark.parametrize("code", CODES)
+@pytest.mark.parametrize("lid", ["packed_f16_isluv", "stride2_bf16_gray"])
+def test_tensor_layouts_with_float4_stores(dets, lid, code):
+    """132 x 136: the pass-through and grey layouts of the table again where H % 4 == 0 in every orientation."""
+    det, want, names, form = _run_layout(dets, oc.VEC3, lid, code)
     same(snapshot(det), want, (lid, code))
     if code:
         assert ingest_names(names) == [form], (names, form)
@@ -301,6 +315,11 @@ ODD_CASES = {
     "i422_dword_loads": ((1, 0), lambda p: oc.planar_buffer(p, 176, 88, (1, 0)), True),
     "yuyv_half_macropixel": ((1, 0), lambda p: oc.yuyv_buffer(p, 352), True),
     "yuyv_from_an_odd_base": ((1, 0), lambda p: oc.yuyv_buffer(p, 352, lead=1), False),
+    # a fourth field: the model, where it is not "inria" — rgb2gray behind a wide and behind the element-wise load form
+    "i420_gray_dword_loads": ((1, 1), lambda p: oc.planar_buffer(p, 176, 88, (1, 1)), True, "face64"),
+    "yuyv_gray_from_an_odd_base": ((1, 0), lambda p: oc.yuyv_buffer(p, 352, lead=1), False, "face64"),
+    # a fifth field: the source size, where it is not 131 x 175 — the grey model with float4 stores
+    "i420_gray_float4_stores": ((1, 1), lambda p: oc.planar_buffer(p, 136, 68, (1, 1)), True, "face64", oc.VEC3),
 }
 
 
@@ -308,12 +327,13 @@ ODD_CASES = {
 def test_yuv_odd_source_size(dets, case):
     """131 x 175 with 66 x 88 (4:2:0) and 131 x 88 (4:2:2) chroma planes: the chroma sample of a reversed odd axis is
     (Hs - 1 - c) >> 1, which no strided view of the upright frame gives; H * W % 4 == 1: the scalar rgb2luv body."""
-    sub, build, fast = ODD_CASES[case]
-    size = oc.ODD
+    sub, build, fast = ODD_CASES[case][:3]
+    mkey = (ODD_CASES[case] + ("inria",))[3]
+    size = ODD_CASES[case][4] if len(ODD_CASES[case]) > 4 else oc.ODD
     buf, d, fb = build(oc.yuv_planes(size, sub))
     lead = 1 if case.endswith("odd_base") else 0
     for code in CODES:
-        det, want, names = _run_yuv(dets, "inria", size, sub, buf, d, code, lead)
+        det, want, names = _run_yuv(dets, mkey, size, sub, buf, d, code, lead)
         same(snapshot(det), want, (case, code))
         if code:
             assert ingest_names(names) == [form_name("yuv", fast, code)], (case, code, names)
@@ -326,6 +346,17 @@ def test_one_tile_or_less_along_an_axis(dets, code):
     buf, d, fb = oc.planar_buffer(oc.yuv_planes(size, (1, 1)), 204, 104, (1, 1))
     det, want, names = _run_yuv(dets, "tiny", size, (1, 1), buf, d, code)
     same(snapshot(det), want, ("i420", code))
+    if code:
+        assert ingest_names(names) == [form_name("yuv", True, code)], names
+    # the same model behind the other two load forms: tight odd strides (byte loads), hand-packed YUYV with half a macropixel at the row end
+    buf, d, fb = oc.planar_buffer(oc.yuv_planes(size, (1, 1)), 203, 102, (1, 1))
+    det, want, names = _run_yuv(dets, "tiny", size, (1, 1), buf, d, code)
+    same(snapshot(det), want, ("i420 bytes", code))
+    if code:
+        assert ingest_names(names) == [form_name("yuv", False, code)], names
+    buf, d, fb = oc.yuyv_buffer(oc.yuv_planes(size, (1, 0)), 408)
+    det, want, names = _run_yuv(dets, "tiny", size, (1, 0), buf, d, code)
+    same(snapshot(det), want, ("yuyv", code))
     if code:
         assert ingest_names(names) == [form_name("yuv", True, code)], names
     x = dev(oc.rgb_source(size, (0, 0)))
@@ -428,6 +459,7 @@ def test_stream_of_oriented_frames_matches_blocking_calls(code):
         xd = dev(x)
         det.run_yuv(xd, N, d, code, size[0], size[1])
         dst = torch.zeros((N, 1 + 6 * cap), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                                          # (torch fills dst on its own stream: before the export writes it)
         det.export_detections(dst, cap)
         det.synchronize()
         want.append(dst.cpu().numpy())

@@ -149,6 +149,7 @@ def test_stream_matches_blocking_calls(code):
         xd = orc.dev(x)
         det.run_yuv_resized(xd, x.shape[0], d, H, W, scale, code)
         dst = torch.zeros((x.shape[0], 1 + 6 * cap), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                                          # (torch fills dst on its own stream: before the export writes it)
         det.export_detections(dst, cap)
         det.synchronize()
         want.append(dst.cpu().numpy())

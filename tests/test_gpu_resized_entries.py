@@ -244,6 +244,7 @@ def test_stream_of_unreduced_i420_frames_matches_blocking_calls():
         xd = dev(x)                                                       # (alive until the synchronise: the call is asynchronous)
         det.run_yuv_resized(xd, x.shape[0], d, H, W, scale)
         dst = torch.zeros((x.shape[0], 1 + 6 * cap), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                                          # (torch fills dst on its own stream: before the export writes it)
         det.export_detections(dst, cap)
         det.synchronize()
         want.append(dst.cpu().numpy())

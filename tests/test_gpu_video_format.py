@@ -15,6 +15,7 @@ import pytest
 
 import orient_ref as orf
 import video_format_ref as vr
+import oriented_case as oc
 import yuv_desc_ref as ydr
 from acf_amd import capi, synth
 from test_gpu_yuv_desc import INRIA, batch, dev, rgb_expect, same, snapshot
@@ -260,21 +261,28 @@ def test_8_bit_formats_equal_the_rgb_entry(det130, name, fmt):
     assert expect in names and not any(n.startswith("k_ingest") and n != expect for n in names), names
 
 
-COMPOSED = [(1, None), (6, None), (0, 0.6), (0, 1.5), (3, 0.6)]
+FACE64_32 = dict(name="FACE64", nTrees=128, cascThr=-4.0, minDs_h=32, minDs_w=32)
+TINY_96 = dict(name="TINY", nTrees=96, cascThr=-3.0)
+# orientation code, scale, model (none: INRIA): rgb2luv_sse, then rgb2gray and the planes as they are behind the turned, the reduced and the
+# turned and reduced (staged: code 3; generic: code 6) entries
+COMPOSED = [(1, None), (6, None), (0, 0.6), (0, 1.5), (3, 0.6),
+            (1, None, FACE64_32), (6, None, TINY_96), (0, 0.6, FACE64_32), (0, 0.6, TINY_96), (3, 0.6, FACE64_32), (6, 0.6, TINY_96)]
 
 
-@pytest.mark.parametrize("case", COMPOSED, ids=["orient1", "orient6", "scale06", "scale15", "orient3_scale06"])
+@pytest.mark.parametrize("case", COMPOSED, ids=["orient1", "orient6", "scale06", "scale15", "orient3_scale06", "orient1_gray", "orient6_isluv", "scale06_gray",
+                                                "scale06_isluv", "orient3_scale06_gray", "orient6_scale06_isluv"])
 def test_bt709_turned_and_reduced_matches_its_composed_definition(case):
     """numpy's R, G, B of the stored frame, turned upright by numpy, then run_u8(PIX_RGB) — through the image entry's resize (the
     apps' Resizer on tight upright bytes) where the call reduces."""
     from acf_amd.detector import HipDetector
-    orient, scale = case
+    orient, scale = case[:2]
+    model = case[2] if len(case) > 2 else INRIA
     fmt = F(8, 0, capi.YUV_MATRIX_BT709, 0)
     sr, sc = (H, W) if not scale else ((216, 290) if scale < 1 else (88, 116))
     if orient & 1:
         sr, sc = sc, sr
     ph, pw = HipDetector.oriented_resized_dims(sr, sc, orient, scale) if scale else HipDetector.oriented_dims(sr, sc, orient)
-    det = HipDetector(synth.make_model(seed=3, **INRIA), ph, pw, 3, max_batch=2, max_hits=1 << 16)
+    det = HipDetector(synth.make_model(seed=3, **model), ph, pw, 3, max_batch=2, max_hits=1 << 16)
     planes = [video_planes(320 + f, sr, sc, 1, 1) for f in range(2)]
     buf, d, fb = batch("nv12" if orient != 6 else "i420", planes)
     rgb = vr.desc_to_rgb(buf, d, sr, sc, tup(fmt), 2)
@@ -374,26 +382,58 @@ def test_the_three_load_forms_give_identical_pyramids_and_report_their_names(det
     same(e, a, "pairs, V first, against planar")
 
 
-@pytest.mark.parametrize("ystride,cstride", [(2 * 175, 2 * 89), (352, 176)], ids=["odd_word_stride_generic", "dword_loads_with_tails"])
-def test_odd_sizes_reach_the_scalar_luv_body(ystride, cstride):
-    """131 x 175 (h * w % 4 == 1: IG_LUV) as hand-built 4:2:0 planar words with ceil-sized 66 x 88 chroma planes."""
+def _pairs16(planes, stride, shift):
+    """Hand-packed P010-like frames of any size: Y words, then rows of (U, V) word pairs, `stride` bytes a row -> (buffer, descriptor)."""
+    h, w = planes[0][0].shape
+    ch, cw = planes[0][1].shape
+    assert stride % 4 == 0 and stride >= 2 * w and stride >= 4 * cw
+    fb = stride * (h + ch)
+    buf = np.full(fb * len(planes), 0x5A, np.uint8)
+    for f, (Y, U, V) in enumerate(planes):
+        fr = buf[f * fb:(f + 1) * fb]
+        fr[:stride * h].reshape(h, stride)[:, :2 * w] = (Y.astype(np.uint16) << shift).view(np.uint8).reshape(h, 2 * w)
+        uv = (np.stack([U, V], axis=-1).astype(np.uint16) << shift).reshape(ch, 2 * cw)
+        fr[stride * h:].reshape(ch, stride)[:, :4 * cw] = uv.view(np.uint8).reshape(ch, 4 * cw)
+    d = capi.YuvDesc(capi.YuvPlane(0, fb, stride, 2), capi.YuvPlane(stride * h, fb, stride, 4), capi.YuvPlane(stride * h + 2, fb, stride, 4), 1, 1)
+    return buf, d
+
+
+ODD_FORMS = [
+    # id, builder(planes) -> (buffer, descriptor), format, the kernel it must reach
+    ("odd_word_stride_generic", lambda p: _planar16(p, 2 * 175, 2 * 89, 0, 0), F(10, 0, capi.YUV_MATRIX_BT709, 0), "k_ingest_yuv16_generic"),
+    ("dword_loads_with_tails", lambda p: _planar16(p, 352, 176, 0, 0), F(10, 0, capi.YUV_MATRIX_BT709, 0), "k_ingest_yuv16_planar"),
+    ("p010_pairs", lambda p: _pairs16(p, 352, 6), F(10, 6, capi.YUV_MATRIX_BT2020, 0), "k_ingest_yuv16_pairs"),
+    # 8 bits, not the default format: the scalar rgb2luv behind the kernels that take the constants as an argument
+    ("bt709_planar_8", lambda p: oc.planar_buffer(p, 176, 88, (1, 1))[:2], F(8, 0, capi.YUV_MATRIX_BT709, 0), "k_ingest_yuv_planar"),
+    ("bt709_bytes_8", lambda p: oc.planar_buffer(p, 175, 89, (1, 1))[:2], F(8, 0, capi.YUV_MATRIX_BT709, 0), "k_ingest_yuv_generic"),
+    ("bt2020_full_yuyv_8", lambda p: oc.yuyv_buffer(p, 352)[:2], F(8, 0, capi.YUV_MATRIX_BT2020, 1), "k_ingest_yuv_packed422"),
+]
+
+
+@pytest.mark.parametrize("case", ODD_FORMS, ids=[c[0] for c in ODD_FORMS])
+def test_odd_sizes_reach_the_scalar_luv_body(case):
+    """131 x 175 (h * w % 4 == 1: IG_LUV) as hand-built frames with ceil-sized chroma planes (66 x 88; packed 4:2:2: 131 x 88)."""
     from acf_amd.detector import HipDetector
+    tag, build, fmt, kernel = case
     h, w, nF = 131, 175, 2
-    fmt = F(10, 0, capi.YUV_MATRIX_BT709, 0)
+    ch = h if "yuyv" in tag else 66
+    top = 1 << fmt.bits
     det = HipDetector(synth.make_model(seed=3, name="INRIA", nTrees=64, cascThr=-2.5, nOctUp=0), h, w, 3, max_batch=nF, max_hits=1 << 16)
     rng = np.random.RandomState(19)
-    planes = [(rng.randint(0, 1024, (h, w)), rng.randint(0, 1024, (66, 88)), rng.randint(0, 1024, (66, 88))) for _ in range(nF)]
-    buf, d = _planar16(planes, ystride, cstride, 0, 0)
-    assert (d.sub_x, d.sub_y) == (1, 1)
+    planes = [(rng.randint(0, top, (h, w)), rng.randint(0, top, (ch, 88)), rng.randint(0, top, (ch, 88))) for _ in range(nF)]
+    buf, d = build(planes)
+    assert (d.sub_x, d.sub_y) == (1, 1 if ch == 66 else 0)
     rgb = vr.desc_to_rgb(buf, d, h, w, tup(fmt), nF)
-    assert np.array_equal(rgb, np.stack([vr.to_rgb(Y, ydr.upsample(U, h, w, 1, 1), ydr.upsample(V, h, w, 1, 1), 10, 1, 0) for Y, U, V in planes]))
-    want = nonvacuous(f32_expect(det, rgb, fmt), "odd")
+    assert np.array_equal(rgb, np.stack([vr.to_rgb(Y, ydr.upsample(U, h, w, 1, d.sub_y), ydr.upsample(V, h, w, 1, d.sub_y), fmt.bits, fmt.matrix, fmt.full_range)
+                                         for Y, U, V in planes]))
+    want = nonvacuous(f32_expect(det, rgb, fmt) if fmt.bits > 8 else rgb_expect(det, rgb.astype(np.uint8)), tag)
     x = dev(buf)
-    assert np.array_equal(det.video_to_rgb(x, nF, h, w, d, fmt).cpu().numpy().view(np.uint16), rgb)
+    got = det.video_to_rgb(x, nF, h, w, d, fmt).cpu().numpy()
+    assert np.array_equal(got.view(np.uint16) if fmt.bits > 8 else got, rgb)
     det.set_option("profile", 1)
     names = names_of(det, lambda: det.run_video(x, nF, d, fmt))
-    assert ("k_ingest_yuv16_generic" if ystride % 4 else "k_ingest_yuv16_planar") in names, names
-    same(snapshot(det, nF), want, (ystride, cstride))
+    assert kernel in names, names
+    same(snapshot(det, nF), want, tag)
     det.close()
 
 
@@ -436,6 +476,12 @@ def test_stride_n_zero_repeats_one_frame(det130):
 MODE_CASES = [
     ("face64_gray", 120, 160, dict(name="FACE64", nTrees=128, cascThr=-4.0, minDs_h=32, minDs_w=32)),   # IG_GRAY
     ("tiny_isluv", 96, 128, dict(name="TINY", nTrees=96, cascThr=-3.0)),                                # planes taken as they are
+    # the same two on 3 x 3 ragged tiles (a ragged width of 6: not a multiple of 16); tight rows of 134 samples put the first layout on the
+    # element-wise load form.  H % 4 == 2: scalar stores, a last quad of two rows; H % 4 == 0: float4 stores
+    ("face64_gray_ragged", 130, 134, dict(name="FACE64", nTrees=128, cascThr=-4.0, minDs_h=32, minDs_w=32)),
+    ("face64_gray_ragged_vec", 132, 134, dict(name="FACE64", nTrees=128, cascThr=-4.0, minDs_h=32, minDs_w=32)),
+    ("tiny_isluv_ragged", 130, 134, dict(name="TINY", nTrees=96, cascThr=-3.0)),
+    ("tiny_isluv_ragged_vec", 132, 134, dict(name="TINY", nTrees=96, cascThr=-3.0)),
 ]
 
 
@@ -445,15 +491,25 @@ def test_grey_and_pass_through_models(case):
     tag, h, w, kw = case
     det = HipDetector(synth.make_model(seed=3, **kw), h, w, 3, max_batch=2, max_hits=1 << 16)
     total = 0
-    for name, fmt in (("nv12", F(10, 6, 2, 0)), ("i422", F(12, 0, 1, 1))):
+    # (tight rows of w samples: the wide forms need every plane's rows four-aligned)
+    layouts = (("nv12", F(10, 6, 2, 0), "k_ingest_yuv16_pairs"), ("i422", F(12, 0, 1, 1), "k_ingest_yuv16_planar" if w % 4 == 0 else "k_ingest_yuv16_generic"),
+               # 8 bits, not the default format: the instantiations that take the constants as an argument
+               ("nv12", F(8, 0, 1, 0), "k_ingest_yuv420"), ("i420", F(8, 0, 1, 0), "k_ingest_yuv_planar" if w % 8 == 0 else "k_ingest_yuv_generic"),
+               ("yuyv", F(8, 0, 2, 1), "k_ingest_yuv_packed422"))
+    for name, fmt, kernel in layouts:
         sx, sy = ydr.SUB[name]
         planes = [video_planes(40 + f, h, w, sx, sy, fmt.bits) for f in range(2)]
-        buf, d, fb = batch16(name, planes, fmt)
+        buf, d, fb = batch16(name, planes, fmt) if fmt.bits > 8 else batch(name, planes)
         rgb = vr.desc_to_rgb(buf, d, h, w, tup(fmt), 2)
-        want = f32_expect(det, rgb, fmt)
+        want = f32_expect(det, rgb, fmt) if fmt.bits > 8 else rgb_expect(det, rgb.astype(np.uint8))
         x = dev(buf)
-        det.run_video(x, 2, d, fmt)
-        same(snapshot(det, 2), want, (tag, name))
+        det.set_option("profile", 1)
+        try:
+            names = names_of(det, lambda: det.run_video(x, 2, d, fmt))
+        finally:
+            det.set_option("profile", 0)
+        assert kernel in names and not any(n.startswith("k_ingest") and n != kernel for n in names), (tag, name, names)
+        same(snapshot(det, 2), want, (tag, name, tup(fmt)))
         total += sum(len(s[1]) for s in want)
     assert total > 0, "no detections: the cascade comparison would be vacuous"
     det.close()
@@ -507,6 +563,7 @@ def test_stream_matches_blocking_calls(kind):
         xd = dev(x)                                                       # (alive until the synchronise: the call is asynchronous)
         det.run_video(xd, x.shape[0], d, fmt)
         dst = torch.zeros((x.shape[0], 1 + 6 * cap), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                                          # (torch fills dst on its own stream: before the export writes it)
         det.export_detections(dst, cap)
         det.synchronize()
         want.append(dst.cpu().numpy())

@@ -90,6 +90,11 @@ YUV_CASES = [
     ("byte_loads", 130, 174, False, 175, 175 * 130 + 3, 0, 1, dict(name="INRIA", nTrees=64, cascThr=-3.0, nOctUp=0), 0),  # odd stride, odd base
     ("nv21", 240, 320, True, 0, 0, 0, 0, dict(name="INRIA", nTrees=128, cascThr=-2.5), 0),
     ("nv21_padded", 130, 174, True, 176, 176 * 132, 0, 0, dict(name="INRIA", nTrees=64, cascThr=-3.0, nOctUp=0), 0),
+    # the other two conversions of the shared store phase on 3 x 3 ragged tiles (a ragged width of 6: not a multiple of 16), through both load forms
+    ("gray_bytes_ragged", 130, 134, False, 135, 135 * 130 + 3, 0, 1, dict(name="FACE64", nTrees=128, cascThr=-4.0, minDs_h=32, minDs_w=32), 0),  # H % 4 == 2
+    ("isluv_bytes_ragged", 132, 134, False, 135, 135 * 132 + 3, 0, 1, dict(name="TINY", nTrees=96, cascThr=-3.0), 0),       # H % 4 == 0: float4 stores
+    ("gray_dwords_ragged", 132, 134, False, 136, 0, 0, 0, dict(name="FACE64", nTrees=128, cascThr=-4.0, minDs_h=32, minDs_w=32), 0),
+    ("isluv_dwords_ragged", 130, 134, False, 136, 0, 0, 0, dict(name="TINY", nTrees=96, cascThr=-3.0), 0),
 ]
 
 
@@ -164,6 +169,7 @@ def test_yuv_and_restated_rgb_give_the_same_records_through_the_library():
     for pix, batch in ((capi.PIX_NV12, np.stack(frames)), (capi.PIX_RGB, np.stack([yr.nv_to_rgb(fr, H, W) for fr in frames]))):
         det.run_u8(torch.from_numpy(batch).cuda(), pix)
         dst = torch.zeros((nF, 1 + 6 * cap), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                                          # (torch fills dst on its own stream: before the export writes it)
         det.export_detections(dst, cap)
         det.synchronize()
         recs.append((dst.cpu().numpy(), [det.read_pyramid(f) for f in range(nF)]))
@@ -252,6 +258,7 @@ def test_stream_of_yuv_frames_matches_blocking_calls(oracle, depth):
     for x in batches:
         det.run_u8(torch.from_numpy(x).cuda(), pix)
         dst = torch.zeros((x.shape[0], 1 + 6 * cap), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                                          # (torch fills dst on its own stream: before the export writes it)
         det.export_detections(dst, cap)
         det.synchronize()
         want.append(dst.cpu().numpy())

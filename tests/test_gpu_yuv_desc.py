@@ -127,26 +127,24 @@ def test_named_layouts_equal_the_rgb_entry(det130, name, padded):
 
 # ---------------------------------------------------------------- odd sizes: ceil-sized chroma planes, the scalar rgb2luv body
 
-@pytest.mark.parametrize("ystride,cstride", [(175, 88), (176, 88)], ids=["byte_loads", "dword_loads_with_tails"])
-def test_odd_sizes_reach_the_scalar_luv_body(ystride, cstride):
-    """131 x 175 (h * w % 4 == 1: IG_LUV) as hand-built 4:2:0 planar with 66 x 88 chroma planes."""
+@pytest.mark.parametrize("layout,ystride,cstride", [("planar", 175, 88), ("planar", 176, 88), ("yuyv", 352, 0)],
+                         ids=["byte_loads", "dword_loads_with_tails", "yuyv_half_macropixel"])
+def test_odd_sizes_reach_the_scalar_luv_body(layout, ystride, cstride):
+    """131 x 175 (h * w % 4 == 1: IG_LUV) as hand-built 4:2:0 planar with 66 x 88 chroma planes, and as hand-packed YUYV (131 x 88 chroma
+    samples: every row ends on half a macropixel)."""
+    import oriented_case as oc
     from acf_amd.detector import HipDetector
     h, w, nF = 131, 175, 2
-    ch, cw = 66, 88
+    ch, cw = (66, 88) if layout == "planar" else (131, 88)
+    sy = 1 if layout == "planar" else 0
     det = HipDetector(synth.make_model(seed=3, name="INRIA", nTrees=64, cascThr=-2.5, nOctUp=0), h, w, 3, max_batch=nF, max_hits=1 << 16)
     rng = np.random.RandomState(9)
-    fb = ystride * h + 2 * cstride * ch
-    buf = np.full(nF * fb, 0x5A, np.uint8)
-    rgbs = []
-    for f in range(nF):
-        Y, U, V = rng.randint(0, 256, (h, w)), rng.randint(0, 256, (ch, cw)), rng.randint(0, 256, (ch, cw))
-        fr = buf[f * fb:(f + 1) * fb]
-        fr[:ystride * h].reshape(h, ystride)[:, :w] = Y
-        fr[ystride * h:ystride * h + cstride * ch].reshape(ch, cstride)[:, :cw] = U
-        fr[ystride * h + cstride * ch:].reshape(ch, cstride)[:, :cw] = V
-        rgbs.append(ydr.planes_to_rgb(Y, U, V, 1, 1))
-    d = capi.YuvDesc(capi.YuvPlane(0, fb, ystride, 1), capi.YuvPlane(ystride * h, fb, cstride, 1), capi.YuvPlane(ystride * h + cstride * ch, fb, cstride, 1), 1, 1)
-    rgb = np.stack(rgbs)
+    planes = [(rng.randint(0, 256, (h, w)), rng.randint(0, 256, (ch, cw)), rng.randint(0, 256, (ch, cw))) for f in range(nF)]
+    rgb = np.stack([ydr.planes_to_rgb(Y, U, V, 1, sy) for Y, U, V in planes])
+    if layout == "planar":
+        buf, d, fb = oc.planar_buffer(planes, ystride, cstride, (1, 1))
+    else:
+        buf, d, fb = oc.yuyv_buffer(planes, ystride)
     assert np.array_equal(ydr.desc_to_rgb(buf, d, h, w, nF), rgb)
     want = rgb_expect(det, rgb)
     assert sum(len(x[1]) for x in want) > 0
@@ -156,8 +154,8 @@ def test_odd_sizes_reach_the_scalar_luv_body(ystride, cstride):
     det.profile()
     det.run_yuv(x, nF, d)
     names = set(det.profile())
-    assert ("k_ingest_yuv_generic" if ystride % 4 else "k_ingest_yuv_planar") in names, names
-    same(snapshot(det, nF), want, (ystride, cstride))
+    assert ("k_ingest_yuv_packed422" if layout == "yuyv" else "k_ingest_yuv_generic" if ystride % 4 else "k_ingest_yuv_planar") in names, names
+    same(snapshot(det, nF), want, (layout, ystride, cstride))
     det.close()
 
 
@@ -262,6 +260,12 @@ def test_views_repeat_a_frame_and_end_with_the_allocation(det130):
 MODE_CASES = [
     ("face64_gray", 120, 160, dict(name="FACE64", nTrees=128, cascThr=-4.0, minDs_h=32, minDs_w=32)),   # IG_GRAY
     ("tiny_isluv", 96, 128, dict(name="TINY", nTrees=96, cascThr=-3.0)),                                # planes taken as they are
+    # the same two on 3 x 3 ragged tiles (a ragged width of 6: not a multiple of 16); tight rows of 134 samples put the first layout on the
+    # element-wise load form.  H % 4 == 2: scalar stores, a last quad of two rows; H % 4 == 0: float4 stores
+    ("face64_gray_ragged", 130, 134, dict(name="FACE64", nTrees=128, cascThr=-4.0, minDs_h=32, minDs_w=32)),
+    ("face64_gray_ragged_vec", 132, 134, dict(name="FACE64", nTrees=128, cascThr=-4.0, minDs_h=32, minDs_w=32)),
+    ("tiny_isluv_ragged", 130, 134, dict(name="TINY", nTrees=96, cascThr=-3.0)),
+    ("tiny_isluv_ragged_vec", 132, 134, dict(name="TINY", nTrees=96, cascThr=-3.0)),
 ]
 
 
@@ -283,7 +287,13 @@ def test_grey_and_pass_through_models(case):
         want = rgb_expect(det, rgb)
         buf, d, fb = batch(name, planes)
         x = dev(buf)
+        det.set_option("profile", 1)
+        det.profile()
         det.run_yuv(x, 2, d)
+        names = set(det.profile())
+        det.set_option("profile", 0)
+        # tight rows of w samples: the planar form needs w and w / 2 four-aligned, else the element-wise form; uyvy rows of 2 w bytes are
+        assert ("k_ingest_yuv_packed422" if name == "uyvy" else "k_ingest_yuv_planar" if w % 8 == 0 else "k_ingest_yuv_generic") in names, (tag, name, names)
         same(snapshot(det, 2), want, (tag, name))
         total += sum(len(x[1]) for x in want)
     assert total > 0, "no detections: the cascade comparison would be vacuous"
@@ -313,6 +323,7 @@ def test_stream_of_i420_frames_matches_blocking_calls():
         xd = dev(x)                                                       # (alive until the synchronise: the call is asynchronous)
         det.run_yuv(xd, x.shape[0], d)
         dst = torch.zeros((x.shape[0], 1 + 6 * cap), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                                          # (torch fills dst on its own stream: before the export writes it)
         det.export_detections(dst, cap)
         det.synchronize()
         want.append(dst.cpu().numpy())

@@ -32,7 +32,7 @@ def test_entries_are_declared_and_bound_and_the_abi_stays():
 
 
 def test_case_table_is_self_consistent(oracle):
-    assert len(rc.CASES) == 9 and len(set(rc.IDS)) == 9
+    assert len(rc.CASES) == 11 and len(set(rc.IDS)) == 11
     assert rc.form_of(rc.S150) == "area" and rc.form_of(rc.S64) == "linear" and rc.S64 == 1.25
     for case in rc.CASES:
         name, H, W, dr, dc, scale, form, inp, model, d_in = case
