@@ -193,6 +193,21 @@ class YuvFormat(C.Structure):
     _fields_ = [("bits", C.c_int32), ("shift", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32)]
 
 
+class CropSource(C.Structure):
+    """struct acf_hip_crop_source: the frames as stored (exactly one of image / yuv is set), their size and orientation code."""
+
+    _fields_ = [("base_dev", C.c_void_p), ("n_frames", C.c_int32), ("image", C.POINTER(ImageDesc)), ("yuv", C.POINTER(YuvDesc)),
+                ("fmt", C.POINTER(YuvFormat)), ("src_rows", C.c_int32), ("src_cols", C.c_int32), ("orient", C.c_int32)]
+
+
+class CropSpec(C.Structure):
+    """struct acf_hip_crop_spec: the crops' size, samples per output pixel (s x s), dtype (T_*), layout (0 planar, 1 packed) and, for
+    cut_detections, crops per frame and the box's growth."""
+
+    _fields_ = [("out_h", C.c_int32), ("out_w", C.c_int32), ("samples", C.c_int32), ("dtype", C.c_int32), ("layout", C.c_int32),
+                ("max_per_frame", C.c_int32), ("grow", C.c_float), ("reserved", C.c_int32)]
+
+
 _lib = None
 
 
@@ -271,6 +286,11 @@ def load():
         "acf_hip_video_extent": ([C.POINTER(YuvDesc), C.POINTER(YuvFormat), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], C.c_int),
         "acf_hip_video_layout": ([C.c_int, C.POINTER(YuvFormat), C.c_int, C.c_int, C.c_int, C.POINTER(YuvDesc), C.POINTER(C.c_int64)], C.c_int),
         "acf_hip_yuv_coeffs": ([C.POINTER(YuvFormat), C.POINTER(C.c_int64)], C.c_int),
+        "acf_hip_cut_crops": ([ctx, C.POINTER(CropSource), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CropSpec), C.c_void_p], C.c_int),
+        "acf_hip_cut_detections": ([ctx, C.POINTER(CropSource), C.c_double, C.POINTER(CropSpec), C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+        "acf_hip_crop_box": ([C.POINTER(C.c_int32), C.c_double, C.c_float, fp], C.c_int),
+        "acf_hip_crop_bytes": ([C.POINTER(CropSpec), C.c_int, C.POINTER(C.c_int64)], C.c_int),
+        "acf_hip_crop_form": ([C.POINTER(CropSpec), fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
         "acf_hip_unorient_rect": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
@@ -346,6 +366,7 @@ DECLARED_SYMBOLS = [
     "acf_hip_run_yuv_oriented_resized", "acf_hip_stream_open_yuv_oriented_resized", "acf_hip_oriented_resized_dims",
     "acf_hip_pyramid_video", "acf_hip_run_video", "acf_hip_stream_open_video", "acf_hip_video_to_rgb", "acf_hip_video_extent",
     "acf_hip_video_layout", "acf_hip_yuv_coeffs",
+    "acf_hip_cut_crops", "acf_hip_cut_detections", "acf_hip_crop_box", "acf_hip_crop_bytes", "acf_hip_crop_form",
 ]
 
 

@@ -2546,4 +2546,6 @@ int acf_hip_set_nms(acf_hip_ctx* c, const acf_hip_nms_params* q)
 
 #include "crops_run.hip.h" // acf_hip_evaluate_crops / _u8: Detector::evaluate(const cv::Mat&) for a batch (k_crop_score, or staged)
 
+#include "cut_run.hip.h"   // acf_hip_cut_crops / _cut_detections: crops of the stored frame under boxes or the last batch's detections (k_cut_crops)
+
 } // extern "C"

@@ -531,6 +531,127 @@ class HipDetector:
                 out[k][i] = b[j]
         return out
 
+    # ---- crops of the stored frame under boxes or the last batch's detections (acf_hip_cut_crops / acf_hip_cut_detections)
+    @staticmethod
+    def _crop_source(ptr, n, image, yuv, fmt, src_rows, src_cols, orient, keep):
+        src = capi.CropSource(C.c_void_p(ptr), n, C.pointer(image) if image is not None else None, C.pointer(yuv) if yuv is not None else None,
+                              C.pointer(fmt) if fmt is not None else None, src_rows, src_cols, orient)
+        src.keep = (image, yuv, fmt, keep)    # what the pointers point at lives as long as the source
+        src.channels = int(image.channels) if image is not None else 3
+        bits = int(fmt.bits) if fmt is not None else 8
+        src.sample_bytes = {capi.T_F16: 2, capi.T_BF16: 2, capi.T_F32: 4}.get(int(image.dtype), 1) if image is not None else (1 if bits == 8 else 2)
+        src.floating = image is not None and int(image.dtype) != capi.T_U8
+        return src
+
+    def crop_source_tensor(self, t, layout="nchw", orient=0):
+        """capi.CropSource of a device tensor [n, c, Hs, Ws] ("nhwc": [n, Hs, Ws, c]) of any strides holding the frames AS STORED,
+        uint8 / float16 / bfloat16 / float32; orient: capi.ORIENT_*.  Nothing is copied."""
+        if layout not in ("nchw", "nhwc") or t.dim() != 4 or not t.is_cuda:
+            raise HipError(capi.E_INVALID, "crop_source_tensor: a device tensor of four dimensions, layout \"nchw\" or \"nhwc\"")
+        if layout == "nhwc":
+            t = t.permute(0, 3, 1, 2)
+        n, ch, h, w = t.shape
+        sn, sc, sy, sx = t.stride()
+        return self._crop_source(t.data_ptr(), n, capi.ImageDesc(self._torch_dtype_code(t), ch, sn, sc, sy, sx), None, None, h, w, orient, t)
+
+    def crop_source_image(self, ptr, n, desc, src_rows, src_cols, orient=0):
+        """capi.CropSource of a raw device pointer and a capi.ImageDesc (what no torch view expresses: a negative channel stride)."""
+        return self._crop_source(ptr, n, desc, None, None, src_rows, src_cols, orient, None)
+
+    def crop_source_yuv(self, base, n, desc, fmt=None, src_rows=None, src_cols=None, orient=0):
+        """capi.CropSource of video frames as run_video reads them: base a torch device tensor (its first byte is the base) or a
+        device pointer, desc a capi.YuvDesc at src_rows x src_cols (the stored size), fmt a capi.YuvFormat or None (the default)."""
+        ptr = base if isinstance(base, int) else base.data_ptr()
+        return self._crop_source(ptr, n, None, desc, fmt, src_rows, src_cols, orient, base)
+
+    @staticmethod
+    def crop_spec(out_size, samples=1, dtype=None, layout="planar", k=1, grow=1.0):
+        """capi.CropSpec: out_size (h, w) or one number; dtype a torch dtype, capi.T_* or None (float32); layout "planar" [C][h][w] or
+        "packed" [h][w][C]."""
+        oh, ow = (out_size, out_size) if isinstance(out_size, int) else out_size
+        if dtype is None:
+            dtype = capi.T_F32
+        elif not isinstance(dtype, int):
+            import torch
+            dtype = {torch.uint8: capi.T_U8, torch.float16: capi.T_F16, torch.bfloat16: capi.T_BF16, torch.float32: capi.T_F32}.get(dtype, -1)
+        lay = {"planar": 0, "packed": 1}.get(layout, -1) if isinstance(layout, str) else int(layout)
+        return capi.CropSpec(int(oh), int(ow), int(samples), dtype, lay, int(k), float(grow), 0)
+
+    @staticmethod
+    def _crop_tensor(spec, channels, lead):
+        import torch
+        dt = {capi.T_U8: torch.uint8, capi.T_F16: torch.float16, capi.T_BF16: torch.bfloat16, capi.T_F32: torch.float32}.get(int(spec.dtype), torch.float32)
+        shape = (spec.out_h, spec.out_w, channels) if spec.layout == 1 else (channels, spec.out_h, spec.out_w)
+        return torch.empty(tuple(lead) + tuple(max(int(v), 0) for v in shape), dtype=dt, device="cuda")
+
+    def cut_crops(self, source, boxes, frame_index, out_size, samples=1, dtype=None, layout="planar", out=None):
+        """Crop i of box boxes[i] = (x, y, w, h) in the upright frame of stored frame frame_index[i] of `source` -> torch device tensor
+        [n, C, oh, ow] (layout "packed": [n, oh, ow, C]).  boxes float32 [n, 4], frame_index int32 [n]: device tensors (host arrays
+        are copied over first).  Asynchronous on the context's stream; no model or plan.  out: a tensor to write into."""
+        import torch
+        spec = self.crop_spec(out_size, samples, dtype, layout)
+        if not torch.is_tensor(boxes):
+            boxes = torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.float32)).cuda()
+        if not torch.is_tensor(frame_index):
+            frame_index = torch.from_numpy(np.ascontiguousarray(frame_index, dtype=np.int32)).cuda()
+        n = int(frame_index.shape[0])
+        if boxes.dtype != torch.float32 or frame_index.dtype != torch.int32 or tuple(boxes.shape) != (n, 4) or not boxes.is_contiguous() \
+                or not frame_index.is_contiguous() or not boxes.is_cuda or not frame_index.is_cuda:
+            raise HipError(capi.E_INVALID, "cut_crops: boxes float32 [n, 4] and frame_index int32 [n], contiguous device tensors")
+        if out is None:
+            out = self._crop_tensor(spec, source.channels, (n,))
+        self._chk(self.lib.acf_hip_cut_crops(self.ctx, C.byref(source), C.c_void_p(boxes.data_ptr()), C.c_void_p(frame_index.data_ptr()), n, C.byref(spec),
+                                             C.c_void_p(out.data_ptr())))
+        return out
+
+    def cut_detections(self, source, out_size, k, det_scale=None, grow=1.0, samples=1, dtype=None, layout="planar", out=None, boxes_out=None,
+                       counts_out=None):
+        """The first k detections of every frame of the last detect / run* call, cropped out of `source` (the frames that call read,
+        as stored) -> (crops [nF, k, C, oh, ow] (or [nF, k, oh, ow, C]), boxes float32 [nF, k, 4] in the upright frame, counts int32
+        [nF]), all on the device, nothing synchronised; slots at and beyond a frame's count are not written.  det_scale: the scale
+        the frames were reduced by (None: none); grow: the box grown about its centre."""
+        import torch
+        spec = self.crop_spec(out_size, samples, dtype, layout, k, grow)
+        nF = int(source.n_frames)
+        if out is None:
+            out = self._crop_tensor(spec, source.channels, (nF, max(int(k), 0)))
+        if boxes_out is None:
+            boxes_out = torch.empty((nF, max(int(k), 0), 4), dtype=torch.float32, device="cuda")
+        if counts_out is None:
+            counts_out = torch.empty((nF,), dtype=torch.int32, device="cuda")
+        self._chk(self.lib.acf_hip_cut_detections(self.ctx, C.byref(source), float(det_scale) if det_scale is not None else 0.0, C.byref(spec),
+                                                  C.c_void_p(out.data_ptr()), C.c_void_p(boxes_out.data_ptr()), C.c_void_p(counts_out.data_ptr())))
+        return out, boxes_out, counts_out
+
+    @staticmethod
+    def crop_box(det, det_scale=None, grow=1.0):
+        """A detection (x, y, w, h) of the reduced frame -> float32 [4], its box in the upright frame grown about its centre
+        (acf_hip_crop_box: cv::Rect2f(o) * (1.f / scale), as the apps map boxes back)."""
+        a = (C.c_int32 * 4)(*[int(v) for v in det])
+        out = np.zeros(4, dtype=np.float32)
+        rc = capi.load().acf_hip_crop_box(a, float(det_scale) if det_scale is not None else 0.0, float(grow), capi.fptr(out))
+        if rc:
+            raise HipError(rc, "acf_hip_crop_box")
+        return out
+
+    @staticmethod
+    def crop_bytes(spec, channels):
+        out = C.c_int64()
+        rc = capi.load().acf_hip_crop_bytes(C.byref(spec), channels, C.byref(out))
+        if rc:
+            raise HipError(rc, "acf_hip_crop_bytes")
+        return out.value
+
+    @staticmethod
+    def crop_form(spec, box, Hu, Wu, channels, sample_bytes):
+        """0 staged, 1 gather: the form k_cut_crops takes for this box (host arithmetic)."""
+        b = np.ascontiguousarray(box, dtype=np.float32)
+        out = C.c_int()
+        rc = capi.load().acf_hip_crop_form(C.byref(spec), capi.fptr(b), Hu, Wu, channels, sample_bytes, C.byref(out))
+        if rc:
+            raise HipError(rc, "acf_hip_crop_form")
+        return out.value
+
     # ---- streaming front end (pinned host frames in, pinned host records out)
     def stream_open(self, pix=capi.PIX_RGB, row_stride=0, cap=1024, depth=2):
         self._chk(self.lib.acf_hip_stream_open(self.ctx, pix, row_stride, cap, depth))

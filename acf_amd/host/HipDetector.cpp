@@ -673,6 +673,38 @@ int HipDetector::detectYuv(const uint8_t* baseDev, int nFrames, int rows, int co
     return 0;
 }
 
+int HipDetector::cutDetections(const void* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc* yuv, const acf_hip_image_desc* image,
+    const acf_hip_crop_spec& spec, void* dstDev, float* boxesDev, int32_t* countsDev)
+{
+    if (!m_ctx)
+    {
+        throw Exception(ACF_HIP_E_INVALID, "cutDetections: detectYuv or detectImages first");
+    }
+    int planRows, planCols;
+    const bool resized = resizedPlan(rows, cols, planRows, planCols);
+    acf_hip_crop_source src{};
+    src.base_dev = baseDev;
+    src.n_frames = nFrames;
+    src.image = image;
+    src.yuv = yuv;
+    src.fmt = yuv ? &m_videoFormat : nullptr;
+    src.src_rows = rows;
+    src.src_cols = cols;
+    src.orient = m_orient;
+    check(m_api->acf_hip_cut_detections(m_ctx, &src, resized ? double(inputScale()) : 0.0, &spec, dstDev, boxesDev, countsDev), "acf_hip_cut_detections");
+    return 0;
+}
+
+size_t HipDetector::cropBytes(const acf_hip_crop_spec& spec, int channels)
+{
+    int64_t n = 0;
+    if (hip::load().acf_hip_crop_bytes(&spec, channels, &n))
+    {
+        throw Exception(ACF_HIP_E_INVALID, "cropBytes: a spec out of range, or channels other than 1 or 3");
+    }
+    return size_t(n);
+}
+
 acf_hip_yuv_desc HipDetector::videoLayout(int layout, const acf_hip_yuv_format& fmt, int rows, int cols, int rowStrideBytes, size_t* frameBytes)
 {
     acf_hip_yuv_desc d;

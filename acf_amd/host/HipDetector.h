@@ -321,6 +321,17 @@ public:
     // mapped back as operator()(packed) does.
     int detectYuv(const uint8_t* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc& desc,
         std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
+    // After detectYuv / detectImages: the first spec.max_per_frame detections of every frame of that call, cropped out of the same
+    // frames as they are stored, upright, at spec.out_h x out_w, on the device (include/acf_hip.h, acf_hip_cut_detections; kernel
+    // k_cut_crops) — with the orientation, minimum object width and video format set on this object, which that call used too.
+    // Exactly one of yuv / image describes the frames.  dstDev [nFrames][K][crop], boxesDev [nFrames][K][4] floats (may be null) and
+    // countsDev [nFrames] int32 are device memory; the call is asynchronous and leaves them on the device: slot i of frame f is
+    // detection i of the DEVICE-side list (the survivors in score order when the NMS runs on the device; a frame with more than
+    // ACF_HIP_NMS_CAP detections, which detectYuv suppresses on the host, has count -1 and no crops), its box the one cv::Rect2f(o) *
+    // (1.f / inputScale()) gives, in floats, grown by spec.grow.  Slots at and beyond a frame's count are not written.
+    int cutDetections(const void* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc* yuv, const acf_hip_image_desc* image,
+        const acf_hip_crop_spec& spec, void* dstDev, float* boxesDev, int32_t* countsDev);
+    static size_t cropBytes(const acf_hip_crop_spec& spec, int channels); // acf_hip_crop_bytes
     // the descriptor of a named layout (ACF_HIP_YUV_*) of rows x cols; *frameBytes = the distance to the next frame
     static acf_hip_yuv_desc yuvLayout(int layout, int rows, int cols, int rowStrideBytes = 0, size_t* frameBytes = nullptr);
     // the same with the format's 1 or 2 bytes a sample (acf_hip_video_layout; P010 is ACF_HIP_YUV_NV12 with bits 10, shift 6)

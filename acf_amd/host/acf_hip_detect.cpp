@@ -14,7 +14,9 @@
 //                  the frames are stored mirrored / turned; H x W is the STORED size): the upright frame is searched
 //                  (setInputOrientation), the boxes are printed in the UPRIGHT frame's coordinates and every "frame" line says so;
 //                  --orient K --min-width M together: turned upright, then reduced, in one kernel (acf_hip_run_yuv_oriented_resized); the
-//                  boxes are mapped back to the upright full-size frame and the "frame" line also names the reduced size
+//                  boxes are mapped back to the upright full-size frame and the "frame" line also names the reduced size;
+//                  --cut WxH[:K] --cut-prefix P (without --stream): the first K detections of every frame cropped out of the stored
+//                  frames on the device, upright, W x H (cutDetections), written as P_<frame>_<i>.ppm, and a "crops f n" line a frame
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
@@ -288,6 +290,38 @@ int main(int argc, char** argv)
                 for (int f = 0; f < cnt; f++)
                 {
                     printFrame(f, objs[size_t(f)], scores[size_t(f)], note);
+                }
+                if (a.count("cut"))
+                {
+                    // --cut WxH[:K] --cut-prefix P: the first K (default 1) detections of every frame cropped out of the stored frames on the
+                    // device (cutDetections: upright, W x H, 8-bit packed R, G, B), written as P_<frame>_<i>.ppm; a "crops f n" line a frame
+                    int cw = 0, ch = 0, K = 1;
+                    if (std::sscanf(a["cut"].c_str(), "%dx%d:%d", &cw, &ch, &K) < 2)
+                    {
+                        throw std::runtime_error("--cut takes WxH or WxH:K");
+                    }
+                    const acf_hip_crop_spec spec{ ch, cw, 1, ACF_HIP_T_U8, 1, K, 1.f, 0 };
+                    const size_t cb = HipDetector::cropBytes(spec, 3);
+                    uint8_t* crops = static_cast<uint8_t*>(HipDetector::pinnedAlloc(cb * size_t(K) * size_t(cnt)));
+                    int32_t* counts = static_cast<int32_t*>(HipDetector::pinnedAlloc(sizeof(int32_t) * size_t(cnt)));
+                    det.cutDetections(pin[0], cnt, H, W, &desc, nullptr, spec, crops, nullptr, counts);
+                    if (acf::hip::load().acf_hip_synchronize(det.context()))
+                    {
+                        throw std::runtime_error("acf_hip_synchronize");
+                    }
+                    const std::string prefix = a.count("cut-prefix") ? a["cut-prefix"] : "crop";
+                    for (int f = 0; f < cnt; f++)
+                    {
+                        std::printf("crops %d %d\n", f, counts[f]);
+                        for (int i = 0; i < counts[f]; i++)
+                        {
+                            std::ofstream os(prefix + "_" + std::to_string(f) + "_" + std::to_string(i) + ".ppm", std::ios::binary);
+                            os << "P6\n" << cw << " " << ch << "\n255\n";
+                            os.write(reinterpret_cast<const char*>(crops + cb * (size_t(f) * size_t(K) + size_t(i))), std::streamsize(cb));
+                        }
+                    }
+                    HipDetector::pinnedFree(crops);
+                    HipDetector::pinnedFree(counts);
                 }
             }
             HipDetector::pinnedFree(pin[0]);

@@ -76,6 +76,11 @@ struct Api
     ACF_HIP_FN(acf_hip_video_extent)
     ACF_HIP_FN(acf_hip_video_layout)
     ACF_HIP_FN(acf_hip_yuv_coeffs)
+    ACF_HIP_FN(acf_hip_cut_crops)
+    ACF_HIP_FN(acf_hip_cut_detections)
+    ACF_HIP_FN(acf_hip_crop_box)
+    ACF_HIP_FN(acf_hip_crop_bytes)
+    ACF_HIP_FN(acf_hip_crop_form)
     ACF_HIP_FN(acf_hip_unorient_rect)
     ACF_HIP_FN(acf_hip_resize_dims)
     ACF_HIP_FN(acf_hip_set_input_resize)

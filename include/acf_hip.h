@@ -761,6 +761,84 @@ ACF_HIP_API int acf_hip_video_layout(int layout, const acf_hip_yuv_format* fmt, 
     int64_t* frame_bytes);
 ACF_HIP_API int acf_hip_yuv_coeffs(const acf_hip_yuv_format* fmt, int64_t out[8]);
 
+/* ---- crops of the stored frame: the stage behind the detections ---------
+ * What nearly every caller does with a detector's boxes is crop them and hand the crops to a second model (landmarks, recognition, a
+ * verifier such as acf_hip_evaluate_crops).  These entries read only the pixels under the boxes from the frame AS STORED — the
+ * descriptors, formats and orientation codes of the entries above — and write upright crops of one fixed size into one device tensor,
+ * in the order of the boxes; no box goes through the host, no converted or turned frame goes to device memory.  No reference
+ * counterpart: the definition below is this library's own.
+ *
+ * The upright frame U.  Hu x Wu = acf_hip_oriented_dims(src_rows, src_cols, orient); upright pixel (r, c) is the stored pixel of the
+ * orientation mapping above ("rotated and mirrored frames").  Its C values are exact floats:
+ *   image source   C = channels; the addressed element: u8 as float(v), f16 / bf16 / f32 widened
+ *   YUV source     C = 3; the integer R, G, B of the format's arithmetic at the stored pixel, chroma chosen in SOURCE coordinates: what
+ *                  acf_hip_video_to_rgb writes
+ * Sampling.  A box is (bx, by, bw, bh) = x, y, w, h in U's coordinates (pixel centres at integers + 0.5 of a unit grid: pixel c covers
+ * [c, c + 1)); s = samples.  Every operation is an f32 operation rounded once, none fused:
+ *     stepx = bw / float(out_w * s)            stepy = bh / float(out_h * s)
+ *     v(m)  = (bx + (float(m) + 0.5f) * stepx) - 0.5f,   m = j * s + b,   clamped to [0, float(Wu - 1)]   (rows alike with by, stepy, Hu)
+ *     c0 = int(floorf(v)), c1 = min(c0 + 1, Wu - 1), fx = v - float(c0)
+ *     top = p00 + fx * (p01 - p00);  bot = p10 + fx * (p11 - p10);  sample = top + fy * (bot - top)
+ *     acc = 0; for a < s: for b < s: acc = acc + sample(i * s + a, j * s + b);      val = acc * float(1.0 / (s * s))
+ * Clamping the coordinate is border replication: a box may reach outside the frame, as padded detections do.
+ * Output.  unit = float(1 / 255.0) for 8-bit codes (u8 images, 8-bit video), float(1.0 / out_max) for video of more than 8 bits, 1 for
+ * floating images.  ACF_HIP_T_F32: val * unit; F16 / BF16: that value narrowed round-to-nearest-even; U8 (8-bit code sources only):
+ * uint8(clamp(rint(val), 0, 255)), val unscaled.  layout 0: a crop is [C][out_h][out_w], 1: [out_h][out_w][C]; crops lie back to back,
+ * acf_hip_crop_bytes apart.
+ * Bad boxes.  A box with a non-finite member or bw <= 0 / bh <= 0, and a frame index outside [0, n_frames), give a crop of zeros.
+ * Nothing in boxes_dev makes the kernel read outside the addressed elements: acf_hip_image_extent / acf_hip_video_extent at src_rows x
+ * src_cols stay the bound.
+ *  acf_hip_cut_crops        a context, no model, no plan (like acf_hip_video_to_rgb): crop i of box boxes_dev[i] in frame frame_dev[i]
+ *                           into slot i of dst_dev.  n = 0 launches nothing (boxes_dev and frame_dev may then be null)
+ *  acf_hip_cut_detections   on the detections of the context's last acf_hip_detect / acf_hip_run*: for frame f, n_f = the device-side
+ *                           count (after the device NMS when it is on); n_f = -1 (over ACF_HIP_NMS_CAP): counts_out[f] = -1 and no crop;
+ *                           else counts_out[f] = min(n_f, K, max_hits), and slot f * K + i of dst_dev (and of boxes_out_dev) is detection
+ *                           i in acf_hip_get_detections' order with the box acf_hip_crop_box gives (the same f32 operations, on the
+ *                           device).  Slots at and beyond the count are not written.  det_scale: the scale the frames were reduced by
+ *                           (0: none); the plan's h x w must be acf_hip_oriented_resized_dims(src_rows, src_cols, orient, det_scale),
+ *                           or acf_hip_oriented_dims(...) for det_scale 0, and n_frames the last batch
+ *  acf_hip_crop_box         host only: a detection {x, y, w, h} of the reduced frame as a box in U — the apps' cv::Rect2f(o) * (1.f / scale)
+ *                           (src/app/acf/acf.cpp:548-551): inv = det_scale == 0 ? 1.f : 1.f / float(det_scale); each of x, y, w, h is
+ *                           float(int) * inv; then cx = x + w * 0.5f, w' = w * grow, x' = cx - w' * 0.5f, and y alike
+ *  acf_hip_crop_bytes       host only: bytes of one crop, out_h * out_w * channels * the element size
+ *  acf_hip_crop_form        host only: the form k_cut_crops takes for this box (Hu x Wu, channels and bytes of a staged code value: 1 for
+ *                           8-bit codes, 2 for wider video and f16 / bf16 images, 4 for f32 images): 0 staged, 1 gather
+ * One kernel, k_cut_crops (so named under option "profile"), one workgroup a crop slot, two forms chosen per crop, both giving the same
+ * bits: staged — bands of output rows whose clamped footprint in U is loaded once along the stored rows into LDS as code values (YUV
+ * converted once per stored pixel) and sampled from there — and gather — every sample fetches its four neighbours through the source's
+ * accessor: right for strong reductions, where a footprint holds far more pixels than are sampled.  The rule (acf_hip_crop_form): gather
+ * when the crop's footprint holds more than four pixels a sample, or when the footprint of one output row does not fit the stage.
+ * Both entries are asynchronous on the context's stream, allocate nothing, never wait for the device, always run plainly and leave a
+ * captured graph of acf_hip_run (option "graph") valid.
+ * ACF_HIP_E_INVALID: null pointers; both or neither of image / yuv; what the oriented image / video entry refuses about the
+ * description and the format; orient outside 0 .. 7; sizes < 1; out sizes, samples, dtype, layout, max_per_frame or reserved out of
+ * range; grow not positive finite; n < 0; cut_detections without valid detections, with n_frames other than the last batch, with a
+ * det_scale that is not 0 or a positive finite number, or with a plan of other dimensions.  ACF_HIP_E_UNSUPPORTED: U8 output from a
+ * floating image or from video of more than 8 bits; option "streams" > 1.  Not covered: area-exact reduction (samples is the
+ * anti-aliasing), rotated boxes, chroma interpolation, five-plane frames. */
+typedef struct acf_hip_crop_source {          /* the frames as stored: exactly one of image / yuv is non-NULL */
+    const void* base_dev; int32_t n_frames;
+    const acf_hip_image_desc* image;          /* as acf_hip_run_image_oriented reads it */
+    const acf_hip_yuv_desc* yuv; const acf_hip_yuv_format* fmt;   /* as acf_hip_run_video reads it; fmt NULL = default */
+    int32_t src_rows, src_cols, orient;       /* stored size (Hs x Ws) and ACF_HIP_ORIENT_* */
+} acf_hip_crop_source;
+typedef struct acf_hip_crop_spec {
+    int32_t out_h, out_w;      /* 1 .. 512 */
+    int32_t samples;           /* s: s x s bilinear samples averaged per output pixel, 1 .. 4 */
+    int32_t dtype;             /* ACF_HIP_T_U8 / F16 / BF16 / F32 */
+    int32_t layout;            /* 0 planar [C][out_h][out_w], 1 packed [out_h][out_w][C] */
+    int32_t max_per_frame;     /* K, 1 .. ACF_HIP_NMS_CAP; cut_detections only */
+    float grow;                /* box grown about its centre by this factor (1 = the box); cut_detections only */
+    int32_t reserved;          /* 0 */
+} acf_hip_crop_spec;
+ACF_HIP_API int acf_hip_cut_crops(acf_hip_ctx* ctx, const acf_hip_crop_source* src, const float* boxes_dev /* [n][4] x, y, w, h in U */,
+    const int32_t* frame_dev /* [n] */, int n, const acf_hip_crop_spec* spec, void* dst_dev);
+ACF_HIP_API int acf_hip_cut_detections(acf_hip_ctx* ctx, const acf_hip_crop_source* src, double det_scale, const acf_hip_crop_spec* spec, void* dst_dev,
+    float* boxes_out_dev /* [n_frames][K][4], may be NULL */, int32_t* counts_out_dev /* [n_frames] */);
+ACF_HIP_API int acf_hip_crop_box(const int32_t det[4], double det_scale, float grow, float out[4]);
+ACF_HIP_API int acf_hip_crop_bytes(const acf_hip_crop_spec* spec, int channels, int64_t* bytes_per_crop);
+ACF_HIP_API int acf_hip_crop_form(const acf_hip_crop_spec* spec, const float box[4], int Hu, int Wu, int channels, int sample_bytes, int* form);
+
 /* ---- streaming front end ---------------------------------------------
  * The overlap of transfer and compute that GPUDetectionPipeline::runFast gets
  * from its two-frame texture FIFO (GPUDetectionPipeline.cpp:357-437), expressed
