@@ -291,6 +291,12 @@ def load():
         "acf_hip_crop_box": ([C.POINTER(C.c_int32), C.c_double, C.c_float, fp], C.c_int),
         "acf_hip_crop_bytes": ([C.POINTER(CropSpec), C.c_int, C.POINTER(C.c_int64)], C.c_int),
         "acf_hip_crop_form": ([C.POINTER(CropSpec), fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_pyramid_view": ([ctx, C.POINTER(CropSource), C.c_void_p, C.c_void_p, C.c_int, C.c_int], C.c_int),
+        "acf_hip_run_view": ([ctx, C.POINTER(CropSource), C.c_void_p, C.c_void_p, C.c_int, C.c_int], C.c_int),
+        "acf_hip_view_from_box": ([fp, C.c_double, C.c_int, C.c_int, fp], C.c_int),
+        "acf_hip_view_quad": ([fp, C.POINTER(C.c_int32), fp], C.c_int),
+        "acf_hip_view_box": ([fp, C.POINTER(C.c_int32), fp], C.c_int),
+        "acf_hip_view_form": ([fp] + [C.c_int] * 9 + [C.POINTER(C.c_int)], C.c_int),
         "acf_hip_unorient_rect": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
@@ -367,6 +373,7 @@ DECLARED_SYMBOLS = [
     "acf_hip_pyramid_video", "acf_hip_run_video", "acf_hip_stream_open_video", "acf_hip_video_to_rgb", "acf_hip_video_extent",
     "acf_hip_video_layout", "acf_hip_yuv_coeffs",
     "acf_hip_cut_crops", "acf_hip_cut_detections", "acf_hip_crop_box", "acf_hip_crop_bytes", "acf_hip_crop_form",
+    "acf_hip_pyramid_view", "acf_hip_run_view", "acf_hip_view_from_box", "acf_hip_view_quad", "acf_hip_view_box", "acf_hip_view_form",
 ]
 
 

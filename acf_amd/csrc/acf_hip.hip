@@ -65,7 +65,8 @@ enum SourceKind
     SRC_F32,   // planar float planes, the pyramid's own layout
     SRC_U8,    // packed 8-bit frames: pix (ACF_HIP_PIX_*, NV12 / NV21 included), rowStride
     SRC_IMAGE, // an upright image of any element strides: img
-    SRC_YUV    // three planes described by offsets and byte strides: yuv
+    SRC_YUV,   // three planes described by offsets and byte strides: yuv
+    SRC_VIEW   // affine views of stored frames (acf_hip_pyramid_view): img or yuv (viewYuv) + fmt at srcRows x srcCols, orient; views, viewFrames
 };
 struct FrameSource
 {
@@ -80,6 +81,11 @@ struct FrameSource
     double scale = 1;
     int orient = 0;               // the oriented entries (ACF_HIP_ORIENT_*, image and YUV kinds): frames of srcRows x srcCols, turned to the plan's size
     acf_hip_yuv_format fmt{ 8, 0, ACF_HIP_YUV_MATRIX_BT601, 0 }; // the video entries (SRC_YUV): sample width, matrix and range; this is the default
+    // the view entries (SRC_VIEW): frame i of the batch is view views[i] of stored frame viewFrames[i] (null: i) of nStored, samples x samples a pixel
+    bool viewYuv = false;
+    const float* views = nullptr;
+    const int32_t* viewFrames = nullptr;
+    int nStored = 0, samples = 1;
 };
 
 } // namespace
@@ -286,6 +292,7 @@ struct LastRun
     bool floatPyramid = true;  // the float pyramid of the last batch exists (option keep_pyramid = 0: it may not)
     bool countsFetched = false; // h_counts holds the last batch's counts
     const float* lastFrames = nullptr;
+    bool viewRun = false;      // the last batch's frames were views (acf_hip_pyramid_view): its boxes are in view coordinates
 };
 
 // ---- acf_hip_plan's: everything the plan builds, and what runs allocate lazily under it.  dropPlan frees `allocs` and assigns a
@@ -1221,6 +1228,7 @@ int runOnKids(acf_hip_ctx* c, const char* who, const float* frames, int nF, Run 
     {
         c->lastBatch = nF;
         c->pyramidValid = c->detectValid = true;
+        c->viewRun = false;
     }
     return rc;
 }

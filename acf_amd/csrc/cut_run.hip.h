@@ -204,6 +204,10 @@ int acf_hip_cut_detections(acf_hip_ctx* c, const acf_hip_crop_source* src, doubl
     {
         return fail(c, ACF_HIP_E_INVALID, who + "no detections (call acf_hip_detect or acf_hip_run* first)");
     }
+    if (c->viewRun)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "the last run was a view (its boxes are in view coordinates: acf_hip_view_box, then acf_hip_cut_crops)");
+    }
     if (src->n_frames != c->lastBatch)
     {
         return fail(c, ACF_HIP_E_INVALID, who + "n_frames must be the last batch's");

@@ -14,9 +14,11 @@
 //   launchYuvToRgb, launchResizeU8, launchColour     the preludes and the colour conversion (ops.hip.h and crops_run.hip.h call them too)
 //   installResizeTables, resizedTables               the tap tables of acf_hip_set_input_resize (c->rz) and of the reduced sources (c->rzIn)
 //   sourceArgsBad, sourceAgainstPlan                 the two layers of the checks
-//   planIngest                                       FrameSource -> IngestPlan, or the refusal: planU8, planImage, planYuv; planReduced, planOrientedResized
+//   planIngest                                       FrameSource -> IngestPlan, or the refusal: planU8, planImage, planYuv, planView; planReduced, planOrientedResized
 //   imageEntry, yuvEntry and the exported entries    acf_hip_pyramid_u8 / _image* / _yuv* / _video and their run_ twins, the extents and layouts,
 //                                                    acf_hip_set_yuv_layout, acf_hip_set_input_resize, acf_hip_yuv_to_rgb8 / video_to_rgb (videoToRgb)
+//   viewEntry and the view entries                   acf_hip_pyramid_view / acf_hip_run_view (SRC_VIEW: affine views of stored frames, k_ingest_view) and their host
+//                                                    arithmetic acf_hip_view_from_box / _view_quad / _view_box / _view_form
 #pragma once
 
 namespace
@@ -32,6 +34,7 @@ using ImageOrientedKernel = void (*)(IngestArgs, ImageOrientedSrc);
 using YuvOrientedKernel = void (*)(IngestArgs, YuvOrientedSrc);
 using OrientedResizedKernel = void (*)(IngestArgs, OrientedResizedSrc);
 using Yuv16Kernel = void (*)(IngestArgs, Yuv16Src);
+using ViewKernel = void (*)(IngestArgs, ViewSrc);
 
 static IngestKernel ingestKernel(int mode, bool aligned)
 {
@@ -140,6 +143,15 @@ static OrientedResizedKernel orientedResizedKernel(int src, int mode, bool stage
         { ORK(RS_IMAGE, true), ORK(RS_YUV, true), ORK(RS_YUV_CF, true) } };
 #undef ORK
     return table[staged][src][mode];
+}
+
+// k_ingest_view<source kind, conversion>: [CUT_*][IG_*] (the form is decided per tile, in the kernel)
+static ViewKernel viewKernel(int kind, int mode)
+{
+#define VK(KIND) { k_ingest_view<KIND, IG_PLANAR>, k_ingest_view<KIND, IG_LUV_VEC>, k_ingest_view<KIND, IG_LUV>, k_ingest_view<KIND, IG_GRAY> }
+    static const ViewKernel table[7][4] = { VK(CUT_IMG_U8), VK(CUT_IMG_F16), VK(CUT_IMG_BF16), VK(CUT_IMG_F32), VK(CUT_YUV8), VK(CUT_YUV8_CF), VK(CUT_YUV16) };
+#undef VK
+    return table[kind][mode];
 }
 
 static bool pixIsYuv(int pix)
@@ -831,6 +843,7 @@ struct IngestPlan
         YuvOrientedSrc yuvOriented;
         OrientedResizedSrc orientedResized;
         Yuv16Src yuv16;
+        ViewSrc view;
     } second{};
     const char* profName = nullptr;   // (static strings: prof keeps the pointer)
     const char* launchName = nullptr;
@@ -845,6 +858,7 @@ struct IngestPlan
     void set(YuvOrientedKernel k, const YuvOrientedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.yuvOriented = s; }
     void set(OrientedResizedKernel k, const OrientedResizedSrc& s) { kernel = reinterpret_cast<const void*>(k); second.orientedResized = s; }
     void set(Yuv16Kernel k, const Yuv16Src& s) { kernel = reinterpret_cast<const void*>(k); second.yuv16 = s; }
+    void set(ViewKernel k, const ViewSrc& s) { kernel = reinterpret_cast<const void*>(k); second.view = s; }
 };
 
 // A source that is both resized and oriented (r.r.im or r.r.yuv filled in; c->rzIn holds the tables of the upright size): the form of
@@ -1113,6 +1127,62 @@ static int planYuv(acf_hip_ctx* c, const FrameSource& src, int mode, IngestPlan&
     return ACF_HIP_OK;
 }
 
+// The view kind (the header's "affine views of the stored frame"): frame i of the batch is the view views[i] of stored frame
+// viewFrames[i], sampled from the frames as the description (image or YUV + format) and the orientation code state them, in
+// k_ingest_view.  The checks are those of the oriented image / video entries about the description, and cut_crops' source's; the
+// stored size is free of the plan's (the view maps one into the other).
+static int planView(acf_hip_ctx* c, const FrameSource& src, int mode, IngestPlan& ip)
+{
+    const std::string who = std::string(src.who) + ": ";
+    if (c->plan.d_in == 5)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "a plan for five input planes (image + M, O) takes planar float frames");
+    }
+    if (c->rz.on)
+    {
+        return inputResizeRefused(c, src.who, "a view scales by itself");
+    }
+    ViewSrc v{};
+    int kind;
+    if (!src.viewYuv)
+    {
+        if (src.img.channels != c->plan.d_in)
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + "channels must be the plan's input planes (d)");
+        }
+        v.S.im = imageArgs(src.base, src.img);
+        kind = src.img.dtype; // CUT_IMG_* = ACF_HIP_T_*
+        v.C = src.img.channels;
+        v.unit = src.img.dtype == ACF_HIP_T_U8 ? float(1.0 / 255.0) : 1.f;
+    }
+    else
+    {
+        if (c->plan.d_in != 3)
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + "the plan's input planes (d) must be 3");
+        }
+        Yuv16Src& y = v.S.yuv;
+        y.yuv = yuvDescSrc(static_cast<const uint8_t*>(src.base), src.yuv);
+        y.yuv.k = yuvCoef(src.fmt);
+        y.shift = src.fmt.shift;
+        y.mask = (1 << src.fmt.bits) - 1;
+        kind = src.fmt.bits > 8 ? CUT_YUV16 : (videoFormatIsDefault(src.fmt) ? CUT_YUV8 : CUT_YUV8_CF);
+        v.C = 3;
+        v.unit = src.fmt.bits == 8 ? float(1.0 / 255.0) : y.yuv.k.sc;
+    }
+    v.views = src.views;
+    v.frames = src.viewFrames;
+    v.nFrames = src.nStored;
+    v.o = orientSrc(src.orient, src.srcRows, src.srcCols);
+    v.Hu = v.o.swap ? src.srcCols : src.srcRows;
+    v.Wu = v.o.swap ? src.srcRows : src.srcCols;
+    v.s = src.samples;
+    ip.set(viewKernel(kind, mode), v);
+    ip.profName = src.viewYuv ? "k_ingest_view_yuv" : "k_ingest_view_image";
+    ip.launchName = "k_ingest_view";
+    return ACF_HIP_OK;
+}
+
 // The ingest of one call: the source held against the plan and the context's settings (what is refused, in the order the entries
 // have always checked), then the kernel form, its arguments and its names.  The ONE place that decides them.
 static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
@@ -1123,7 +1193,10 @@ static int planIngest(acf_hip_ctx* c, const FrameSource& src, IngestPlan& ip)
     ip.convert = c->d_color && c->p.colorSpace != ACF_HIP_CS_HSV;
     const int mode = ingestMode(c, ip.convert);
     ip.nOut = (ip.convert && mode == IG_PLANAR) ? 3 : c->plan.d_in; // ORIG / RGB with a 1-plane input: replicate (chnsPyramid.cpp:242-243)
-    return src.kind == SRC_U8 ? planU8(c, src, mode, ip) : src.kind == SRC_IMAGE ? planImage(c, src, mode, ip) : planYuv(c, src, mode, ip);
+    return src.kind == SRC_U8      ? planU8(c, src, mode, ip)
+           : src.kind == SRC_IMAGE ? planImage(c, src, mode, ip)
+           : src.kind == SRC_VIEW  ? planView(c, src, mode, ip)
+                                   : planYuv(c, src, mode, ip);
 }
 
 // the pyramid of a source, then the cascade on it: the run_ entries of every kind but planar float frames, and the stream
@@ -1165,7 +1238,163 @@ static int yuvEntry(acf_hip_ctx* c, bool detect, const char* who, const uint8_t*
     src.yuv = *desc;
     return detect ? runSource(c, src, nF) : pyramidImpl(c, src, nF);
 }
+
+// The general view entry: what the call states about its source (cut_crops' checks of an acf_hip_crop_source), its views and its
+// samples, whatever the context; then pyramidBody's (streams, plan, n_views) and planView's.  A view call always runs plainly.
+static int viewEntry(acf_hip_ctx* c, bool detect, const acf_hip_crop_source* s, const float* views, const int32_t* frames, int nViews, int samples)
+{
+    if (int rc = needCtx(c)) return rc;
+    const char* const name = "pyramid_view";
+    const std::string who = "pyramid_view: ";
+    if (!s || !views || !s->base_dev)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "null source, base or views");
+    }
+    if ((s->image != nullptr) == (s->yuv != nullptr))
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "exactly one of image and yuv describes the frames");
+    }
+    if (samples < 1 || samples > 4)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "samples must be 1 .. 4");
+    }
+    if (s->n_frames < 1 || orientedArgsBad(s->src_rows, s->src_cols, s->orient))
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "orient must be 0 .. 7 (ACF_HIP_ORIENT_*), n_frames, src_rows and src_cols >= 1");
+    }
+    FrameSource src{ SRC_VIEW, s->base_dev, name };
+    src.srcRows = s->src_rows;
+    src.srcCols = s->src_cols;
+    src.orient = s->orient;
+    src.views = views;
+    src.viewFrames = frames;
+    src.nStored = s->n_frames;
+    src.samples = samples;
+    if (s->image)
+    {
+        if (const char* bad = imageDescBad(s->image))
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + bad);
+        }
+        if (reinterpret_cast<uintptr_t>(s->base_dev) % imageElemBytes(s->image->dtype))
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + "base_dev must be a multiple of the element size");
+        }
+        src.img = *s->image;
+    }
+    else
+    {
+        src.viewYuv = true;
+        src.fmt = s->fmt ? *s->fmt : kDefaultVideoFormat;
+        if (const char* bad = videoFormatBad(src.fmt))
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + bad);
+        }
+        if (const char* bad = yuvDescBad(s->yuv))
+        {
+            return fail(c, ACF_HIP_E_INVALID, who + bad);
+        }
+        if (src.fmt.bits > 8)
+        {
+            if (const char* bad = video16DescBad(s->base_dev, *s->yuv))
+            {
+                return fail(c, ACF_HIP_E_INVALID, who + bad);
+            }
+        }
+        src.yuv = *s->yuv;
+    }
+    if (!frames && nViews > s->n_frames)
+    {
+        return fail(c, ACF_HIP_E_INVALID, who + "without frame indices view i reads stored frame i: n_views must not exceed n_frames");
+    }
+    return detect ? runSource(c, src, nViews) : pyramidImpl(c, src, nViews);
+}
 } // namespace
+
+int acf_hip_pyramid_view(acf_hip_ctx* c, const acf_hip_crop_source* src, const float* views, const int32_t* frames, int nViews, int samples)
+{
+    return viewEntry(c, false, src, views, frames, nViews, samples);
+}
+
+int acf_hip_run_view(acf_hip_ctx* c, const acf_hip_crop_source* src, const float* views, const int32_t* frames, int nViews, int samples)
+{
+    return viewEntry(c, true, src, views, frames, nViews, samples);
+}
+
+// ---- the views' host arithmetic: in double from the float inputs, results rounded to float
+int acf_hip_view_from_box(const float box[4], double angle, int h, int w, float m[6])
+{
+    if (!box || !m || h < 1 || w < 1)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    const double bx = box[0], by = box[1], bw = box[2], bh = box[3];
+    const double sx = bw / w, sy = bh / h, ca = std::cos(angle), sa = std::sin(angle);
+    const double m0 = sx * ca, m1 = -sy * sa, m3 = sx * sa, m4 = sy * ca;
+    const double cx = bx + bw / 2, cy = by + bh / 2;
+    const double out[6] = { m0, m1, cx - (m0 * w + m1 * h) / 2, m3, m4, cy - (m3 * w + m4 * h) / 2 };
+    for (int k = 0; k < 6; k++)
+    {
+        m[k] = float(out[k]);
+    }
+    return ACF_HIP_OK;
+}
+
+int acf_hip_view_quad(const float m[6], const int32_t det[4], float quad[8])
+{
+    if (!m || !det || !quad)
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    const double x0 = det[0], y0 = det[1], x1 = double(det[0]) + det[2], y1 = double(det[1]) + det[3];
+    const double xs[4] = { x0, x1, x1, x0 }, ys[4] = { y0, y0, y1, y1 }; // TL, TR, BR, BL
+    for (int k = 0; k < 4; k++)
+    {
+        quad[2 * k] = float(double(m[0]) * xs[k] + double(m[1]) * ys[k] + double(m[2]));
+        quad[2 * k + 1] = float(double(m[3]) * xs[k] + double(m[4]) * ys[k] + double(m[5]));
+    }
+    return ACF_HIP_OK;
+}
+
+int acf_hip_view_box(const float m[6], const int32_t det[4], float box[4])
+{
+    float q[8];
+    if (!box || acf_hip_view_quad(m, det, q))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    // (the corners in double once more: the box's extent is the difference of the unrounded extremes)
+    const double x0 = det[0], y0 = det[1], x1 = double(det[0]) + det[2], y1 = double(det[1]) + det[3];
+    const double xs[4] = { x0, x1, x1, x0 }, ys[4] = { y0, y0, y1, y1 };
+    double lo[2] = { 0, 0 }, hi[2] = { 0, 0 };
+    for (int k = 0; k < 4; k++)
+    {
+        const double p[2] = { double(m[0]) * xs[k] + double(m[1]) * ys[k] + double(m[2]), double(m[3]) * xs[k] + double(m[4]) * ys[k] + double(m[5]) };
+        for (int d = 0; d < 2; d++)
+        {
+            lo[d] = k == 0 || p[d] < lo[d] ? p[d] : lo[d];
+            hi[d] = k == 0 || p[d] > hi[d] ? p[d] : hi[d];
+        }
+    }
+    box[0] = float(lo[0]);
+    box[1] = float(lo[1]);
+    box[2] = float(hi[0] - lo[0]);
+    box[3] = float(hi[1] - lo[1]);
+    return ACF_HIP_OK;
+}
+
+int acf_hip_view_form(const float m[6], int samples, int tileX, int tileY, int h, int w, int Hu, int Wu, int channels, int sampleBytes, int* form)
+{
+    if (!m || !form || samples < 1 || samples > 4 || h < 1 || w < 1 || Hu < 1 || Wu < 1 || (channels != 1 && channels != 3) ||
+        (sampleBytes != 1 && sampleBytes != 2 && sampleBytes != 4) || tileX < 0 || tileY < 0 || tileX >= cdiv(w, IG_T) || tileY >= cdiv(h, IG_T))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    const ViewGrid g = view_grid(m, samples, Hu, Wu);
+    const int x0 = tileX * IG_T, y0 = tileY * IG_T, nx = std::min(IG_T, w - x0), ny = std::min(IG_T, h - y0);
+    *form = view_form(g, view_rect(g, x0, y0, nx, ny), nx, ny, channels, sampleBytes);
+    return ACF_HIP_OK;
+}
 
 int acf_hip_pyramid_u8(acf_hip_ctx* c, const uint8_t* frames, int nF, int pix, int rowStride)
 {

@@ -1073,6 +1073,7 @@ int pyramidBody(acf_hip_ctx* c, const FrameSource& src, int nF)
             c->lastBatch = nF;
             c->pyramidValid = true;
             c->detectValid = false;
+            c->viewRun = false;
         }
         return rc;
     }
@@ -1083,6 +1084,7 @@ int pyramidBody(acf_hip_ctx* c, const FrameSource& src, int nF)
     }
     HIPCHK(c, hipSetDevice(c->device));
     c->pyramidValid = c->detectValid = false;
+    c->viewRun = src.kind == SRC_VIEW; // (every other run clears it)
     int rc;
     PyramidRun run(c, frames, nF);
     IngestPlan ip; // (planar float frames: none; convert stays false)

@@ -652,6 +652,69 @@ class HipDetector:
             raise HipError(rc, "acf_hip_crop_form")
         return out.value
 
+    # ---- affine views of the stored frame as the batch's frames (acf_hip_pyramid_view / acf_hip_run_view)
+    def _view_call(self, detect, source, views, frames, samples):
+        import torch
+        if not torch.is_tensor(views):
+            views = torch.from_numpy(np.ascontiguousarray(views, dtype=np.float32).reshape(-1, 6)).cuda()
+        if frames is not None and not torch.is_tensor(frames):
+            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.int32)).cuda()
+        n = int(views.shape[0])
+        if views.dtype != torch.float32 or views.dim() != 2 or views.shape[1] != 6 or not views.is_contiguous() or not views.is_cuda:
+            raise HipError(capi.E_INVALID, "run_view: views float32 [n, 6], a contiguous device tensor")
+        if frames is not None and (frames.dtype != torch.int32 or tuple(frames.shape) != (n,) or not frames.is_contiguous() or not frames.is_cuda):
+            raise HipError(capi.E_INVALID, "run_view: frames int32 [n], a contiguous device tensor")
+        fn = self.lib.acf_hip_run_view if detect else self.lib.acf_hip_pyramid_view
+        self._chk(fn(self.ctx, C.byref(source), C.c_void_p(views.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, n, int(samples)))
+        self._view_keep = (views, frames)     # the call is asynchronous: what it reads lives until the next one
+
+    def pyramid_view(self, source, views, frames=None, samples=1):
+        """The pyramid of views of stored frames: frame i of the batch is the affine view views[i] (six floats: xu = m0 x + m1 y + m2,
+        yu = m3 x + m4 y + m5 from the plan's frame into the upright stored frame) of stored frame frames[i] (None: frame i) of
+        `source` (crop_source_tensor / crop_source_yuv), samples x samples bilinear samples a pixel.  views, frames: numpy arrays
+        (copied over first) or device tensors."""
+        self._view_call(False, source, views, frames, samples)
+
+    def run_view(self, source, views, frames=None, samples=1):
+        """pyramid_view, then the cascade.  The detections are in VIEW coordinates: view_quad / view_box map them back."""
+        self._view_call(True, source, views, frames, samples)
+
+    @staticmethod
+    def view_from_box(box, angle_rad, h, w):
+        """float32 [6]: the view whose h x w frame is the box (x, y, w, h in the upright stored frame) turned by angle_rad about its centre."""
+        b, m = np.ascontiguousarray(box, dtype=np.float32), np.zeros(6, dtype=np.float32)
+        rc = capi.load().acf_hip_view_from_box(capi.fptr(b), float(angle_rad), int(h), int(w), capi.fptr(m))
+        if rc:
+            raise HipError(rc, "acf_hip_view_from_box")
+        return m
+
+    @staticmethod
+    def view_quad(m, det):
+        """A detection (x, y, w, h) of the view's frame -> float32 [4, 2]: its corners TL, TR, BR, BL (x, y) in the upright stored frame."""
+        mm, q = np.ascontiguousarray(m, dtype=np.float32), np.zeros(8, dtype=np.float32)
+        rc = capi.load().acf_hip_view_quad(capi.fptr(mm), (C.c_int32 * 4)(*[int(v) for v in det]), capi.fptr(q))
+        if rc:
+            raise HipError(rc, "acf_hip_view_quad")
+        return q.reshape(4, 2)
+
+    @staticmethod
+    def view_box(m, det):
+        """A detection of the view's frame -> float32 [4]: the bounding box (x, y, w, h) of view_quad, what cut_crops takes."""
+        mm, b = np.ascontiguousarray(m, dtype=np.float32), np.zeros(4, dtype=np.float32)
+        rc = capi.load().acf_hip_view_box(capi.fptr(mm), (C.c_int32 * 4)(*[int(v) for v in det]), capi.fptr(b))
+        if rc:
+            raise HipError(rc, "acf_hip_view_box")
+        return b
+
+    @staticmethod
+    def view_form(m, samples, tile_x, tile_y, h, w, Hu, Wu, channels, sample_bytes):
+        """0 staged, 1 gather: the form k_ingest_view takes for a 64 x 64 tile of the h x w frame (host arithmetic)."""
+        mm, out = np.ascontiguousarray(m, dtype=np.float32), C.c_int()
+        rc = capi.load().acf_hip_view_form(capi.fptr(mm), samples, tile_x, tile_y, h, w, Hu, Wu, channels, sample_bytes, C.byref(out))
+        if rc:
+            raise HipError(rc, "acf_hip_view_form")
+        return out.value
+
     # ---- streaming front end (pinned host frames in, pinned host records out)
     def stream_open(self, pix=capi.PIX_RGB, row_stride=0, cap=1024, depth=2):
         self._chk(self.lib.acf_hip_stream_open(self.ctx, pix, row_stride, cap, depth))

@@ -695,6 +695,79 @@ int HipDetector::cutDetections(const void* baseDev, int nFrames, int rows, int c
     return 0;
 }
 
+int HipDetector::detectViews(const acf_hip_crop_source& src, const std::vector<std::array<float, 6>>& views, const std::vector<int>& frames, int samples, int h,
+    int w, std::vector<RectVec>& objects, std::vector<RealVec>* scores)
+{
+    const int n = int(views.size());
+    if (n < 1 || (!frames.empty() && frames.size() != views.size()))
+    {
+        throw Exception(ACF_HIP_E_INVALID, "detectViews: at least one view, and a frame index for every view or none");
+    }
+    ensurePlan(h, w, src.image ? src.image->channels : 3, n);
+    syncNms();
+    // page-locked memory is the device's to read: the views and the indices go through the detector's pinned scratch
+    const size_t vBytes = size_t(n) * 6 * sizeof(float), bytes = vBytes + size_t(n) * sizeof(int32_t);
+    if (bytes > m_pinBytes)
+    {
+        pinnedFree(m_pin);
+        m_pin = pinnedAlloc(bytes);
+        m_pinBytes = bytes;
+    }
+    float* v = static_cast<float*>(m_pin);
+    int32_t* f = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(m_pin) + vBytes);
+    for (int i = 0; i < n; i++)
+    {
+        std::copy(views[size_t(i)].begin(), views[size_t(i)].end(), v + size_t(i) * 6);
+        if (!frames.empty())
+        {
+            f[i] = frames[size_t(i)];
+        }
+    }
+    check(m_api->acf_hip_run_view(m_ctx, &src, v, frames.empty() ? nullptr : f, n, samples), "acf_hip_run_view");
+    fetchBatch(n, false, objects, scores); // (waits for the device: the scratch is free again)
+    return 0;
+}
+
+int HipDetector::detectViews(const acf_hip_crop_source& src, const std::vector<std::array<float, 6>>& views, const std::vector<int>& frames, int samples,
+    std::vector<RectVec>& objects, std::vector<RealVec>* scores)
+{
+    int h = m_viewH, w = m_viewW;
+    if (h < 1 || w < 1)
+    {
+        if (hip::load().acf_hip_oriented_dims(src.src_rows, src.src_cols, src.orient, &h, &w))
+        {
+            throw Exception(ACF_HIP_E_INVALID, "detectViews: orient must be 0 .. 7, src_rows and src_cols >= 1");
+        }
+    }
+    return detectViews(src, views, frames, samples, h, w, objects, scores);
+}
+
+std::array<float, 6> HipDetector::viewFromBox(const std::array<float, 4>& box, double angleRad, int h, int w)
+{
+    std::array<float, 6> m{};
+    if (hip::load().acf_hip_view_from_box(box.data(), angleRad, h, w, m.data()))
+    {
+        throw Exception(ACF_HIP_E_INVALID, "viewFromBox: h and w >= 1");
+    }
+    return m;
+}
+
+std::array<float, 8> HipDetector::viewQuad(const std::array<float, 6>& m, const Rect& o)
+{
+    const int32_t det[4] = { o.x, o.y, o.width, o.height };
+    std::array<float, 8> q{};
+    (void)hip::load().acf_hip_view_quad(m.data(), det, q.data());
+    return q;
+}
+
+std::array<float, 4> HipDetector::viewBox(const std::array<float, 6>& m, const Rect& o)
+{
+    const int32_t det[4] = { o.x, o.y, o.width, o.height };
+    std::array<float, 4> b{};
+    (void)hip::load().acf_hip_view_box(m.data(), det, b.data());
+    return b;
+}
+
 size_t HipDetector::cropBytes(const acf_hip_crop_spec& spec, int channels)
 {
     int64_t n = 0;

@@ -20,6 +20,7 @@
 
 #include "acf_hip_loader.h"
 
+#include <array>
 #include <cstdint>
 #include <functional>
 #include <stdexcept>
@@ -332,6 +333,21 @@ public:
     int cutDetections(const void* baseDev, int nFrames, int rows, int cols, const acf_hip_yuv_desc* yuv, const acf_hip_image_desc* image,
         const acf_hip_crop_spec& spec, void* dstDev, float* boxesDev, int32_t* countsDev);
     static size_t cropBytes(const acf_hip_crop_spec& spec, int channels); // acf_hip_crop_bytes
+    // Affine views of stored frames as the batch (include/acf_hip.h, acf_hip_run_view; kernel k_ingest_view): frame i of the batch is
+    // the view views[i] (six floats: xu = m0 x + m1 y + m2, yu = m3 x + m4 y + m5 from the h x w frame searched into the upright stored
+    // frame) of stored frame frames[i] (frames empty: frame i) of src, samples x samples bilinear samples a pixel — one frame at a few
+    // roll angles, a tracker's neighbourhood magnified, several windows of one frame.  h x w: the size searched (the plan's).  src
+    // describes memory the device reads; the views and indices go through the detector's page-locked scratch.  Boxes come back in
+    // VIEW coordinates: viewQuad / viewBox map one to the upright stored frame (viewBox is what acf_hip_cut_crops takes).
+    int detectViews(const acf_hip_crop_source& src, const std::vector<std::array<float, 6>>& views, const std::vector<int>& frames, int samples, int h, int w,
+        std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
+    // ... searched at the size setViewSize names, or without one at the upright stored size (acf_hip_oriented_dims of src)
+    int detectViews(const acf_hip_crop_source& src, const std::vector<std::array<float, 6>>& views, const std::vector<int>& frames, int samples,
+        std::vector<RectVec>& objects, std::vector<RealVec>* scores = nullptr);
+    void setViewSize(int h, int w) { m_viewH = h; m_viewW = w; }
+    static std::array<float, 6> viewFromBox(const std::array<float, 4>& box, double angleRad, int h, int w); // acf_hip_view_from_box
+    static std::array<float, 8> viewQuad(const std::array<float, 6>& m, const Rect& o);                      // acf_hip_view_quad: TL, TR, BR, BL
+    static std::array<float, 4> viewBox(const std::array<float, 6>& m, const Rect& o);                       // acf_hip_view_box
     // the descriptor of a named layout (ACF_HIP_YUV_*) of rows x cols; *frameBytes = the distance to the next frame
     static acf_hip_yuv_desc yuvLayout(int layout, int rows, int cols, int rowStrideBytes = 0, size_t* frameBytes = nullptr);
     // the same with the format's 1 or 2 bytes a sample (acf_hip_video_layout; P010 is ACF_HIP_YUV_NV12 with bits 10, shift 6)
@@ -455,6 +471,7 @@ private:
     std::vector<float> m_upright; // scratch for operator()(interleaved)
     int m_streamCap = 0, m_streamPix = -1, m_streamStride = 0;
     int m_orient = 0; // setInputOrientation
+    int m_viewH = 0, m_viewW = 0; // setViewSize
     acf_hip_yuv_format m_videoFormat{ 8, 0, ACF_HIP_YUV_MATRIX_BT601, 0 }; // setVideoFormat
     int m_minObjectWidth = -1, m_srcRows = 0, m_srcCols = 0; // frame size handed to the 8-bit entries (== the plan's without a resize)
     MatLoggerType m_logger;

@@ -16,7 +16,10 @@
 //                  --orient K --min-width M together: turned upright, then reduced, in one kernel (acf_hip_run_yuv_oriented_resized); the
 //                  boxes are mapped back to the upright full-size frame and the "frame" line also names the reduced size;
 //                  --cut WxH[:K] --cut-prefix P (without --stream): the first K detections of every frame cropped out of the stored
-//                  frames on the device, upright, W x H (cutDetections), written as P_<frame>_<i>.ppm, and a "crops f n" line a frame
+//                  frames on the device, upright, W x H (cutDetections), written as P_<frame>_<i>.ppm, and a "crops f n" line a frame;
+//                  --view x,y,w,h[,deg[,frame]] (repeatable, without --stream) [--view-size HxW] [--view-samples s]: every view is one
+//                  frame of the batch, the box of the upright stored frame turned by deg about its centre (detectViews); "view i n",
+//                  then a line "x0 y0 x1 y1 x2 y2 x3 y3 score scorebits" a detection: its corners in the upright stored frame
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
@@ -82,6 +85,7 @@ static void printFrame(int f, const HipDetector::RectVec& objs, const HipDetecto
 int main(int argc, char** argv)
 {
     std::map<std::string, std::string> a;
+    std::vector<std::string> viewArgs; // every --view, in order
     for (int i = 1; i < argc; i++)
     {
         std::string k = argv[i];
@@ -89,6 +93,10 @@ int main(int argc, char** argv)
         {
             if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0)
             {
+                if (k == "--view")
+                {
+                    viewArgs.push_back(argv[i + 1]);
+                }
                 a[k.substr(2)] = argv[++i];
             }
             else
@@ -254,7 +262,56 @@ int main(int argc, char** argv)
             };
             std::vector<HipDetector::RectVec> objs;
             std::vector<HipDetector::RealVec> scores;
-            if (a.count("stream"))
+            if (!viewArgs.empty())
+            {
+                // --view x,y,w,h[,deg[,frame]] (repeatable; without --stream): every view is one frame of the batch — the box of the
+                // upright stored frame `frame` (default 0) turned by deg about its centre, searched at --view-size HxW (default: the
+                // upright stored size) with --view-samples s (default 1) samples a pixel each way (detectViews).  Output: "view i n",
+                // then n lines "x0 y0 x1 y1 x2 y2 x3 y3 score scorebits": the detection's corners TL, TR, BR, BL in the upright stored frame
+                int vh = orient & 1 ? W : H, vw = orient & 1 ? H : W, smp = a.count("view-samples") ? std::stoi(a["view-samples"]) : 1;
+                if (a.count("view-size") && std::sscanf(a["view-size"].c_str(), "%dx%d", &vh, &vw) != 2)
+                {
+                    throw std::runtime_error("--view-size takes HxW");
+                }
+                std::vector<std::array<float, 6>> views;
+                std::vector<int> frames;
+                for (const std::string& v : viewArgs)
+                {
+                    float x = 0, y = 0, w = 0, h = 0;
+                    double deg = 0;
+                    int frame = 0;
+                    if (std::sscanf(v.c_str(), "%f,%f,%f,%f,%lf,%d", &x, &y, &w, &h, &deg, &frame) < 4)
+                    {
+                        throw std::runtime_error("--view takes x,y,w,h[,deg[,frame]]");
+                    }
+                    views.push_back(HipDetector::viewFromBox({ { x, y, w, h } }, deg * 3.14159265358979323846 / 180.0, vh, vw));
+                    frames.push_back(frame);
+                }
+                readBatch(pin[0], cnt);
+                acf_hip_crop_source src{};
+                src.base_dev = pin[0];
+                src.n_frames = cnt;
+                src.yuv = &desc;
+                src.fmt = &fmt;
+                src.src_rows = H;
+                src.src_cols = W;
+                src.orient = orient;
+                det.setViewSize(vh, vw);
+                det.detectViews(src, views, frames, smp, objs, &scores);
+                for (size_t i = 0; i < views.size(); i++)
+                {
+                    std::printf("view %d %d\n", int(i), int(objs[i].size()));
+                    for (size_t k = 0; k < objs[i].size(); k++)
+                    {
+                        const std::array<float, 8> q = HipDetector::viewQuad(views[i], objs[i][k]);
+                        const float sc = float(scores[i][k]);
+                        uint32_t b;
+                        std::memcpy(&b, &sc, 4);
+                        std::printf("%.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %08x\n", q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], scores[i][k], b);
+                    }
+                }
+            }
+            else if (a.count("stream"))
             {
                 det.streamOpenYuv(H, W, desc, per, B, depth, 8192);
                 std::vector<std::pair<int, int>> inflight; // ticket, first frame

@@ -81,6 +81,12 @@ struct Api
     ACF_HIP_FN(acf_hip_crop_box)
     ACF_HIP_FN(acf_hip_crop_bytes)
     ACF_HIP_FN(acf_hip_crop_form)
+    ACF_HIP_FN(acf_hip_pyramid_view)
+    ACF_HIP_FN(acf_hip_run_view)
+    ACF_HIP_FN(acf_hip_view_from_box)
+    ACF_HIP_FN(acf_hip_view_quad)
+    ACF_HIP_FN(acf_hip_view_box)
+    ACF_HIP_FN(acf_hip_view_form)
     ACF_HIP_FN(acf_hip_unorient_rect)
     ACF_HIP_FN(acf_hip_resize_dims)
     ACF_HIP_FN(acf_hip_set_input_resize)

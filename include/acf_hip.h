@@ -839,6 +839,68 @@ ACF_HIP_API int acf_hip_crop_box(const int32_t det[4], double det_scale, float g
 ACF_HIP_API int acf_hip_crop_bytes(const acf_hip_crop_spec* spec, int channels, int64_t* bytes_per_crop);
 ACF_HIP_API int acf_hip_crop_form(const acf_hip_crop_spec* spec, const float box[4], int Hu, int Wu, int channels, int sample_bytes, int* form);
 
+/* ---- affine views of the stored frame: tilted, zoomed, cut out ----------
+ * The cascade only finds upright objects of the plan's frame.  These entries make every frame of the batch an AFFINE VIEW of a stored
+ * frame, sampled on the way in: the same frame at a few roll angles (or at the gyroscope's), a tracker's neighbourhood of the last box
+ * magnified, one quadrant of a large frame at full resolution, several windows of one frame in one batch — without a turned, scaled or
+ * cut copy in device memory and without a host round trip.  No reference counterpart: the definition below is this library's own.
+ *
+ * The stored frames are an acf_hip_crop_source, and the upright frame U (Hu x Wu = acf_hip_oriented_dims; C exact floats a pixel: an
+ * image's C = channels elements, a YUV source's integer R, G, B of the format's arithmetic, chroma chosen in SOURCE coordinates) is the
+ * one "crops of the stored frame" defines.
+ * A view is six floats m[6]: it maps the continuous coordinates of the plan's h x w frame into U's,
+ *     xu = m0 * x + m1 * y + m2,   yu = m3 * x + m4 * y + m5        (pixel c covers [c, c + 1) in both frames)
+ * Sampling.  For pixel (r, c) of view i, s = samples (1 .. 4), every operation an f32 operation rounded once, none fused:
+ *     inv = float(1.0 / s)
+ *     py = (float(r * s + a) + 0.5f) * inv          px = (float(c * s + b) + 0.5f) * inv          a, b = 0 .. s - 1
+ *     u  = (((m0 * px) + (m1 * py)) + m2) - 0.5f    v  = (((m3 * px) + (m4 * py)) + m5) - 0.5f
+ *     u  = u > 0.f ? u : 0.f;  u = u < float(Wu - 1) ? u : float(Wu - 1)       (v alike with Hu; NaN becomes 0: border replication)
+ *     c0 = int(floorf(u)) clamped to [0, Wu - 1], c1 = min(c0 + 1, Wu - 1), fx = u - float(c0)       (rows alike)
+ *     top = p00 + fx * (p01 - p00);  bot = p10 + fx * (p11 - p10);  sample = top + fy * (bot - top)
+ *     acc = 0; for a: for b: acc = acc + sample;      val = acc * float(1.0 / (s * s))
+ *     plane value = val * unit
+ * unit as for the crops: float(1 / 255.0) for 8-bit codes, float(1.0 / out_max) for video of more than 8 bits, 1 for floating images.
+ * From there on the call IS acf_hip_pyramid_image / acf_hip_run_image on a tight planar float32 image [n_views][C][h][w] holding those
+ * plane values: the colour-conversion mode the ingest picks for the plan's size, every level, hit, score bit and box, option "arith"
+ * = 1 included.  The clamp makes every bit pattern of m safe: no view makes a load leave the extent acf_hip_image_extent /
+ * acf_hip_video_extent give at src_rows x src_cols.  View i reads stored frame frame_dev[i] (frame_dev NULL: frame i); an index
+ * outside [0, n_frames) reads nothing and yields the frame of all-zero code values.
+ * Consequences: the identity view {1,0,0, 0,1,0} with s = 1 on a source whose Hu x Wu is the plan's size is the oriented image / video
+ * entry bit for bit (u = c exactly, fx = 0, val = p00; on sources without negative zeros); {1,0,tx, 0,1,ty} with integers tx, ty is
+ * acf_hip_run_image on the strided sub-view; video of more than 8 bits may be oriented here, which acf_hip_run_video refuses.
+ *  acf_hip_pyramid_view / acf_hip_run_view   n_views = 1 .. max_batch; view i becomes frame i of the batch.  Asynchronous on the context's
+ *                           stream; they allocate nothing after the first call, always run plainly and leave a captured graph of
+ *                           acf_hip_run valid.  ACF_HIP_TAP_IMAGE as after acf_hip_pyramid_u8.  The detections are in VIEW coordinates:
+ *                           acf_hip_cut_detections refuses after a view call (ACF_HIP_E_INVALID, "the last run was a view") until another
+ *                           run; the route to crops is acf_hip_view_box + acf_hip_cut_crops
+ *  acf_hip_view_from_box    host only, in double from the float inputs, rounded to float: the view whose frame is the box (x, y, w, h in
+ *                           U) turned by angle_rad about its centre: sx = bw / w, sy = bh / h, m0 = sx cos, m1 = -sy sin, m3 = sx sin,
+ *                           m4 = sy cos, m2 = cx - (m0 w + m1 h) / 2, m5 = cy - (m3 w + m4 h) / 2.  Angle 0: the plain cut-and-scale
+ *  acf_hip_view_quad        host only: a detection {x, y, w, h} of the view's frame as its corners TL, TR, BR, BL (x, y each) in U
+ *  acf_hip_view_box         host only: the bounding box (x, y, w, h) of that quad in U: what acf_hip_cut_crops takes
+ *  acf_hip_view_form        host only: the form k_ingest_view takes for tile (tile_x, tile_y) of the h x w frame (tiles of 64 x 64; channels
+ *                           and sample_bytes as acf_hip_crop_form): 0 staged, 1 gather
+ * One kernel, k_ingest_view (option "profile": k_ingest_view_image / k_ingest_view_yuv), grid (tiles x, tiles y, n_views), ending in the
+ * store phase of every ingest kernel.  Two forms chosen per tile, both giving the same bits: staged — the clamped coordinates of the
+ * tile's four corner samples, widened and clamped to U, give a rectangle that is loaded once along the stored rows into LDS as code
+ * values (YUV converted once per stored pixel) and sampled from there; a sample whose 2 x 2 neighbourhood is not wholly inside it
+ * fetches through the source's accessor — and gather — every sample fetches its four neighbours through the accessor: when the
+ * rectangle holds more than four stored pixels a sample, or does not fit the stage (wide codes under a tilt, three f32 channels).
+ * ACF_HIP_E_INVALID: null pointers; both or neither of image / yuv; what the oriented image / video entry refuses about the
+ * description, the format and the orientation; channels other than the plan's d; a five-plane plan; samples outside 1 .. 4; n_views
+ * outside 1 .. max_batch; frame_dev NULL with n_views > n_frames; an active acf_hip_set_input_resize.  ACF_HIP_E_UNSUPPORTED: option
+ * "streams" > 1.  ACF_HIP_E_NOPLAN: no plan.  Not covered: a streaming front end for views, a fill value other than border
+ * replication, perspective maps, area-exact reduction (samples is the anti-aliasing). */
+ACF_HIP_API int acf_hip_pyramid_view(acf_hip_ctx* ctx, const acf_hip_crop_source* src, const float* views_dev /* [n_views][6] */,
+    const int32_t* frame_dev /* [n_views], or NULL: view i reads stored frame i */, int n_views, int samples);
+ACF_HIP_API int acf_hip_run_view(acf_hip_ctx* ctx, const acf_hip_crop_source* src, const float* views_dev /* [n_views][6] */,
+    const int32_t* frame_dev /* [n_views], or NULL */, int n_views, int samples);
+ACF_HIP_API int acf_hip_view_from_box(const float box[4] /* x, y, w, h in U */, double angle_rad, int h, int w, float m[6]);
+ACF_HIP_API int acf_hip_view_quad(const float m[6], const int32_t det[4] /* x, y, w, h of the view's frame */, float quad[8] /* TL, TR, BR, BL in U */);
+ACF_HIP_API int acf_hip_view_box(const float m[6], const int32_t det[4], float box[4] /* the quad's bounding box in U */);
+ACF_HIP_API int acf_hip_view_form(const float m[6], int samples, int tile_x, int tile_y, int h, int w, int Hu, int Wu, int channels, int sample_bytes,
+    int* form);
+
 /* ---- streaming front end ---------------------------------------------
  * The overlap of transfer and compute that GPUDetectionPipeline::runFast gets
  * from its two-frame texture FIFO (GPUDetectionPipeline.cpp:357-437), expressed
