@@ -176,6 +176,7 @@ struct CascState
     RankChan* d_rankChan = nullptr;
     RankRec* d_rankRec = nullptr;
     int rankMaxRec = 0;
+    bool rankHasZero = false; // RankTables::hasZero: the rank kernels' forms with the select for negative cells
     RankJob* d_rankJobs = nullptr;
     uint16_t* d_pyrR = nullptr;
     int64_t pyrRCells = 0; // cells per frame

@@ -523,6 +523,7 @@ static int buildCascadeTables(acf_hip_ctx* c, const std::vector<acf_hip_level>& 
         }
         cs.pyrRCells = off;
         cs.rankMaxRec = rt.maxRec;
+        cs.rankHasZero = rt.hasZero;
         int rcl;
         // + slack: a tile's 16-byte fill chunks run up to rowsP cells past the last column of the last plane
         if ((rcl = devUpload(c, &cs.d_rankChan, rt.chan)) || (rcl = devUpload(c, &cs.d_rankRec, rt.rec)) || (rcl = devUpload(c, &cs.d_rankJobs, jobs)) ||

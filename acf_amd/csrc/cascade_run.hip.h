@@ -340,13 +340,14 @@ static int ensureRankCells(acf_hip_ctx* c, const CascState& cs, const CascadeCal
         return ACF_HIP_OK;
     }
     const size_t ldsR = size_t(cs.rankMaxRec) * sizeof(RankRec);
+    const auto kRank = cs.rankHasZero ? &k_rank<true> : &k_rank<false>;
     int rc;
-    if ((rc = allowLds(c, reinterpret_cast<const void*>(&k_rank), ldsR)))
+    if ((rc = allowLds(c, reinterpret_cast<const void*>(kRank), ldsR)))
     {
         return rc;
     }
     prof(c, c->stream, "k_rank");
-    hipLaunchKernelGGL(k_rank, dim3(cdiv(cs.rankMaxWP, RANK_CHUNK_COLS), cs.nLevels * call.in.nChns, call.in.nF), dim3(256), ldsR, c->stream, call.in.pyr,
+    hipLaunchKernelGGL(kRank, dim3(cdiv(cs.rankMaxWP, RANK_CHUNK_COLS), cs.nLevels * call.in.nChns, call.in.nF), dim3(256), ldsR, c->stream, call.in.pyr,
         call.in.pyr_fs, cs.d_pyrR, cs.pyrRCells, (const RankJob*)cs.d_rankJobs, call.in.nChns, (const RankChan*)cs.d_rankChan, (const RankRec*)cs.d_rankRec);
     LAUNCHCHK(c, "k_rank");
     *ranks = true;

@@ -522,27 +522,24 @@ inline int32_t rankKey(float v)
 }
 inline int rankBucket(const RankChan& c, int32_t key)
 {
-    const int b = (key >> c.shift) - c.base;
-    return b < 0 ? 0 : (b > c.nb - 1 ? c.nb - 1 : b);
+    // (clamp, then rebase, as the device does: a negative key lands in bucket 0 through the arithmetic shift)
+    const int32_t k = key >> c.shift, hi = c.base + c.nb - 1;
+    return (k < c.base ? c.base : (k > hi ? hi : k)) - c.base;
 }
 } // namespace
 
 uint32_t RankTables::rankOfCell(int chn, float v) const
 {
+    // the device's steps (rank_fetch, rankCount, the select of the hasZero forms), on the raw key as there
     const RankChan& c = chan[size_t(chn)];
-    if (v < 0.f)
-    {
-        return 0;
-    }
-    const int32_t key = rankKey(v);
+    int32_t key;
+    std::memcpy(&key, &v, 4);
     const RankRec& r = rec[size_t(c.recOff) + size_t(rankBucket(c, key))];
     const uint32_t low = uint32_t(key) & ((1u << c.shift) - 1u);
-    uint32_t n = r.lo;
-    for (int j = 0; j < RANK_WINDOW; j++)
-    {
-        n += (uint32_t(r.t(j)) <= low) ? 1u : 0u;
-    }
-    return n;
+    uint32_t w[4]; // the record as the device's one 16-byte read sees it (little-endian, as the device is)
+    std::memcpy(w, &r, sizeof w);
+    const uint32_t n = rankCount(w[0], w[1], w[2], w[3], low);
+    return (hasZero && v < 0.f) ? 0u : n;
 }
 
 uint32_t RankTables::rankOfThreshold(int chn, float t) const
@@ -642,20 +639,15 @@ void buildRankTables(const float* thrs, const int32_t* chnOfNode, size_t nNodes,
         c.nb = t.empty() ? 1 : int32_t((rankKey(t.back()) >> best) - c.base + 2);
         c.recOff = int32_t(out.rec.size());
         c.thrOff = int32_t(out.thr.size());
-        RankRec empty;
-        empty.lo = 0;
-        for (int j = 0; j < RANK_WINDOW; j++)
-        {
-            empty.t(j) = RANK_UNUSED;
-        }
-        out.rec.resize(out.rec.size() + size_t(c.nb), empty);
+        out.hasZero = out.hasZero || hasZero != 0;
+        out.rec.resize(out.rec.size() + size_t(c.nb), RankRec{}); // unused slots hold 0
         RankRec* rec = out.rec.data() + c.recOff;
         std::vector<int> fill(static_cast<size_t>(c.nb), 0);
         for (size_t j = 0; j < t.size(); j++)
         {
             const int32_t key = rankKey(t[j]);
             const int b = rankBucket(c, key);
-            rec[b].t(fill[size_t(b)]++) = uint16_t(uint32_t(key) & ((1u << best) - 1u));
+            rec[b].t(fill[size_t(b)]++) = rankSlot(uint32_t(key) & ((1u << best) - 1u));
         }
         uint32_t acc = hasZero;
         for (int b = 0; b < c.nb; b++)

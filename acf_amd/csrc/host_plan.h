@@ -13,6 +13,13 @@
 #include <string>
 #include <vector>
 
+// functions whose one text runs on the host and in the kernels
+#if defined(__HIPCC__)
+#define ACF_PLAN_HD __host__ __device__
+#else
+#define ACF_PLAN_HD
+#endif
+
 namespace acfhip
 {
 
@@ -104,17 +111,21 @@ int checkChnsParams(const acf_hip_params& p, int d_in, std::string& err);
 //
 // rank(v) without a search.  For v >= 0 the bit pattern of v is an order-preserving integer key.  Its top bits select a
 // bucket; a bucket's 16-byte record holds `lo` = the number of thresholds in lower buckets and the LOW `shift` bits of the
-// keys of its own thresholds (at most RANK_WINDOW = 7 of them; 0x8000 in unused slots).  Inside a bucket all keys share
+// keys of its own thresholds (at most RANK_WINDOW = 7 of them, encoded as below).  Inside a bucket all keys share
 // their top bits, so comparing low bits compares the floats:
-//     key = max(int(bits(v)), 0);  b = clamp((key >> shift) - base, 0, nb - 1);  low = key & ((1 << shift) - 1);
-//     rec = table[b] (one 16-byte read);  rank = rec.lo + #{ j : rec.t[j] <= low };   v < 0: rank = 0.
-// buildRankTables picks each channel's `shift` (<= 15, so that 0x8000 is above every low key) as the largest — i.e. the
+//     key = int(bits(v));  b = clamp(key >> shift, base, base + nb - 1) - base;  low = key & ((1 << shift) - 1);
+//     rec = table[b] (one 16-byte read);  rank = rec.lo + #{ j : rec.t[j] <= low }.
+// buildRankTables picks each channel's `shift` (<= 15, so that a low key stays below 0x8000) as the largest — i.e. the
 // smallest table — whose buckets hold at most RANK_WINDOW thresholds, or reports that none exists within
 // RANK_MAX_BUCKETS buckets (ok = false: the float pyramid stays the cascade's input).  Bucket 0 lies below and bucket
-// nb - 1 above every threshold's bucket: values outside the thresholds' range clamp into records without thresholds.
+// nb - 1 above every threshold's bucket: values outside the thresholds' range clamp into records without thresholds,
+// where `low` (garbage for them) meets no slot.
 // (A threshold of exactly 0 is <= every v >= -0: it is counted in every record's `lo` and has no slot.)
-// Exact for EVERY finite v (and -0.0 == +0.0) provided no threshold is negative — then a negative v is below all of
-// them, rank 0 — which buildRankTables also requires (a model with a negative threshold keeps the float cascade).
+// Exact for EVERY finite v (and -0.0 == +0.0) provided no threshold is negative, which buildRankTables requires (a model
+// with a negative threshold keeps the float cascade): a negative v, -0.0 included, has a negative key and clamps into
+// bucket 0, whose rank is its `lo` — 0, the right answer for a value below every threshold, unless the channel holds the
+// threshold 0 (lo = 1, right for -0.0 alone).  Only then does a negative v need `v < 0 ? 0 : rank` on top: RankTables::
+// hasZero says so once per model, and the kernels carry the select only in the forms chosen for such a model.
 constexpr int RANK_WINDOW = 7;
 constexpr int RANK_MAX_BUCKETS = 4096;
 
@@ -127,11 +138,13 @@ struct RankChan
     int32_t pad_[2];
 };
 
-// Record layout (round 3): dword 0 = t[0] | lo << 16, dwords 1..3 = t[1] | t[2] << 16, ...  Low keys are < 0x8000 and an
-// unused slot holds RANK_UNUSED = 0x8000, so with X = (low | 0x8000) in both halves of a dword, `X - dword` leaves
-// "t <= low" in bits 15 and 31 without a borrow between the halves: seven compares are four subtractions (the device's
-// rank_count; full-rate VALU instead of seven v_cmp + v_addc, which issue at half rate on gfx950).
-constexpr uint16_t RANK_UNUSED = 0x8000;
+// Record layout: dword 0 = t[0] | lo << 16, dwords 1..3 = t[1] | t[2] << 16, ...  A used slot holds 0x8000 - tlow (tlow =
+// the low `shift` bits of the threshold's key, <= 0x7fff), an unused slot 0.  With low <= 0x7fff, slot + low never exceeds
+// 0xffff, its bit 15 is set exactly when tlow <= low, and an unused slot never sets it: seven compares are four packed
+// 16-bit additions of `low` to the record's dwords, and the indicator bits (15 and 31 of every sum; dword 0's upper half is
+// lo + low, which the mask drops) are counted on top of `lo` by a chain of four popcount-and-add.  13 VALU instructions at
+// full rate on gfx950 (4 v_pk_add_u16 with op_sel_hi taking `low` for both halves, 4 v_and, 1 v_lshrrev, 4 v_bcnt); seven
+// v_cmp + v_addc issue at half rate there (profiles/ubench/valu_rate.hip).
 struct RankRec // 16 bytes
 {
     uint16_t t0;
@@ -140,6 +153,43 @@ struct RankRec // 16 bytes
     uint16_t& t(int j) { return j == 0 ? t0 : tr[j - 1]; }
     uint16_t t(int j) const { return j == 0 ? t0 : tr[j - 1]; }
 };
+ACF_PLAN_HD constexpr uint16_t rankSlot(uint32_t tlow) // a used slot
+{
+    return uint16_t(0x8000u - tlow);
+}
+// The count, one text for RankTables::rankOfCell and the kernels; the two helpers are the instructions the compiler does
+// not pick by itself (it splits the popcount chain into v_bcnt + v_add3 and builds `low` twice for a 32-bit add).
+ACF_PLAN_HD inline uint32_t rankAddLow(uint32_t dword, uint32_t low) // low (<= 0x7fff) added to both 16-bit halves
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t d;
+    asm("v_pk_add_u16 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(d) : "v"(dword), "v"(low));
+    return d;
+#else
+    // (the lower half never carries: slot + low <= 0xffff; the upper half wraps in both forms)
+    return dword + (low | (low << 16));
+#endif
+}
+ACF_PLAN_HD inline uint32_t rankPopAdd(uint32_t bits, uint32_t n) // popcount(bits) + n
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t d;
+    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(d) : "v"(bits), "v"(n));
+    return d;
+#else
+    return uint32_t(__builtin_popcount(bits)) + n;
+#endif
+}
+// r0 .. r3: the bucket's record; low: the cell's low key bits (no guard bit)
+ACF_PLAN_HD inline uint32_t rankCount(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t low)
+{
+    static_assert(RANK_WINDOW == 7 && sizeof(RankRec) == 16, "record layout");
+    const uint32_t d0 = rankAddLow(r0, low) & 0x00008000u;
+    const uint32_t d1 = rankAddLow(r1, low) & 0x80008000u;
+    const uint32_t d2 = rankAddLow(r2, low) & 0x80008000u;
+    const uint32_t d3 = rankAddLow(r3, low) & 0x80008000u;
+    return rankPopAdd(d3, rankPopAdd(d2, rankPopAdd(d1, rankPopAdd(d0, r0 >> 16))));
+}
 
 struct RankTables
 {
@@ -149,6 +199,7 @@ struct RankTables
     std::vector<RankRec> rec;
     std::vector<float> thr; // sorted distinct thresholds, channel after channel
     int maxRec = 0;         // largest per-channel record count: the kernels' LDS budget
+    bool hasZero = false;   // some channel holds the threshold 0: a negative cell needs the select (see above)
 
     uint32_t rankOfCell(int chn, float v) const;      // host mirror of the device function (tests, op entry)
     uint32_t rankOfThreshold(int chn, float t) const; // k + 1 of the text above (0: never true)
@@ -176,11 +227,6 @@ int buildResizeTables(int rows, int cols, double scale, ResizeTables& t);
 //     [x >> 6][(y + 8) >> 4][(x >> 4) & 3][(y + 8) & 15][2]
 // so that the 16 rows x 4 segments a wave of the y kernel takes per step (rows J + 8 .. J + 23 of its 64 columns) are 512
 // contiguous bytes.  nyb = triCkBlockRows(h); the index is the sum of its column part (y = -8) and its row part (x = 0).
-#if defined(__HIPCC__)
-#define ACF_PLAN_HD __host__ __device__
-#else
-#define ACF_PLAN_HD
-#endif
 ACF_PLAN_HD constexpr int triCkBlockRows(int h)
 {
     return (h + 8 + 15) / 16;

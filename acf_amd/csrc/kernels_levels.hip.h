@@ -335,40 +335,39 @@ __global__ void __launch_bounds__(256) k_resample_up(const float* __restrict__ s
 // ------------------------------------------------------------------------
 struct RankFn
 {
-    int32_t shift, base, nbm1;
+    int32_t shift, bLo, bHi; // buckets bLo .. bHi of key >> shift (bLo = the channel's `base`)
     uint32_t mask;
+    uint32_t bias;           // LDS byte address of the channel's records - 16 * bLo: record b is at 16 * b + bias
 };
-// the read: issue it early, count late (rank_count) — the level kernels put a column's other LDS traffic in between
-__device__ __forceinline__ uint4 rank_fetch(float v, const RankFn& f, const uint4* rec, uint32_t& low)
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(3))) u32x4* RankRecLds; // (a plain vector: uint4 is a class in the host pass)
+// the read: issue it early, count late (rank_count) — the level kernels put a column's other LDS traffic in between.
+// 4 VALU: shift, clamp, address (the records' base and -16 * bLo in one wave-uniform addend), low bits.
+__device__ __forceinline__ uint4 rank_fetch(float v, const RankFn& f, uint32_t& low)
 {
-    // (a negative v lands in bucket 0 through the arithmetic shift; its rank is forced to 0 in rank_count)
+    // (a negative v lands in bucket bLo through the arithmetic shift: host_plan.h)
     const int key = __float_as_int(v);
-    int b; // clamp to [0, nbm1] in one instruction (the compiler cannot prove nbm1 >= 0 and keeps v_max + v_min)
-    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(b) : "v"((key >> f.shift) - f.base), "v"(f.nbm1));
-    low = (uint32_t(key) & f.mask) | 0x8000u; // the guard bit of rank_count's packed compares
-    return rec[b];
+    int b; // clamp in one instruction (the compiler cannot prove bLo <= bHi and keeps v_max + v_min)
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(b) : "v"(key >> f.shift), "s"(f.bLo), "v"(f.bHi));
+    low = uint32_t(key) & f.mask;
+    const u32x4 r = *reinterpret_cast<RankRecLds>((uint32_t(b) << 4) + f.bias);
+    return make_uint4(r.x, r.y, r.z, r.w);
 }
+// NEG: the model holds a threshold of exactly 0 (RankTables::hasZero): bucket bLo's `lo` is 1 then, for -0.0, and a negative
+// cell is put below it here.  Every other model's negative cells rank 0 through the table alone: no compare, no select.
+// 13 VALU (rankCount, host_plan.h) + 2 with NEG.
+template <bool NEG>
 __device__ __forceinline__ uint32_t rank_count(float v, const uint4& r, uint32_t low)
 {
-    static_assert(RANK_WINDOW == 7 && sizeof(RankRec) == 16 && RANK_UNUSED == 0x8000, "record layout");
-    // Seven `t <= low` as four subtractions: low keys are < 0x8000 and carry the guard bit 0x8000 here, slots hold
-    // <= 0x8000, so (low | 0x8000) - t has bit 15 set exactly when t <= low and never borrows from the upper half.  The
-    // indicator bits (15 and 31 of every difference; dword 0's upper half is `lo`, not a slot) are moved to distinct
-    // positions and counted with one v_bcnt that also adds `lo`.  18 VALU at full rate; the seven v_cmp_le_u32_sdwa +
-    // v_addc/v_cndmask of the scalar form issue at half rate on gfx950 (profiles/ubench/valu_rate.hip).
-    const uint32_t X = low | (low << 16);
-    const uint32_t m0 = (X - r.x) & 0x00008000u;
-    const uint32_t m1 = (X - r.y) & 0x80008000u;
-    const uint32_t m2 = (X - r.z) & 0x80008000u;
-    const uint32_t m3 = (X - r.w) & 0x80008000u;
-    const uint32_t n = uint32_t(__builtin_popcount(m0 | (m1 >> 1) | (m2 >> 2) | (m3 >> 3))) + (r.x >> 16);
-    return v < 0.f ? 0u : n; // every threshold is >= 0 (buildRankTables): a negative cell is below all of them
+    const uint32_t n = rankCount(r.x, r.y, r.z, r.w, low);
+    return (NEG && v < 0.f) ? 0u : n;
 }
-__device__ __forceinline__ uint32_t rank_cell(float v, const RankFn& f, const uint4* rec)
+template <bool NEG>
+__device__ __forceinline__ uint32_t rank_cell(float v, const RankFn& f)
 {
     uint32_t low;
-    const uint4 r = rank_fetch(v, f, rec, low);
-    return rank_count(v, r, low);
+    const uint4 r = rank_fetch(v, f, low);
+    return rank_count<NEG>(v, r, low);
 }
 
 // copy a channel's records into LDS; returns the bucket function
@@ -381,9 +380,10 @@ __device__ __forceinline__ RankFn rank_tables_to_lds(const RankChan& rc, const R
     }
     RankFn f;
     f.shift = rc.shift;
-    f.base = rc.base;
-    f.nbm1 = rc.nb - 1;
+    f.bLo = rc.base;
+    f.bHi = rc.base + rc.nb - 1;
     f.mask = (1u << rc.shift) - 1u;
+    f.bias = uint32_t(reinterpret_cast<uintptr_t>((lptr_t)recL)) - 16u * uint32_t(rc.base);
     return f;
 }
 
@@ -396,6 +396,7 @@ struct RankJob
     int32_t hP, wP, pitchR, pad_;
 };
 constexpr int RANK_CHUNK_COLS = 64;
+template <bool NEG>
 __global__ void __launch_bounds__(256) k_rank(const float* __restrict__ pyr, int64_t pyr_fs, uint16_t* __restrict__ out, int64_t out_fs,
     const RankJob* __restrict__ jobs, int nChns, const RankChan* __restrict__ chan, const RankRec* __restrict__ recG)
 {
@@ -417,7 +418,7 @@ __global__ void __launch_bounds__(256) k_rank(const float* __restrict__ pyr, int
     {
         for (int r = lane; r < J.hP; r += 64)
         {
-            dst[int64_t(c) * J.pitchR + r] = uint16_t(rank_cell(src[int64_t(c) * J.hP + r], fn, ldsRec));
+            dst[int64_t(c) * J.pitchR + r] = uint16_t(rank_cell<NEG>(src[int64_t(c) * J.hP + r], fn));
         }
     }
 }
@@ -760,14 +761,14 @@ __device__ __forceinline__ void level_column(float (&v)[R], int xb, srd_t A, int
 enum
 {
     LO_F32 = 1,
-    LO_RANK = 2
+    LO_RANK = 2,
+    LO_RANK_NEG = 4 // with LO_RANK: the model holds a zero threshold, negative cells take rank_count's select
 };
 struct LevelRank
 {
     uint16_t* out;        // rank pyramid
     int64_t fs;           // cells per frame
-    RankFn fn;            // the channel's bucket function
-    const uint4* rec;     // the channel's bucket records, in LDS
+    RankFn fn;            // the channel's bucket function (its records are in LDS)
 };
 
 // A plane's column chain cut into speculative segments (SEG = 1; the smoothing's recursion is k_smooth_vec's: see
@@ -916,6 +917,11 @@ __device__ __forceinline__ void level_body(const LevelJob& J, const int64_t f, c
         xr = xrn;                                                                                                   \
         xrn = (MODE == LM_REAL) ? zrec : xrec[min((COL) + 2, w - 1)];                                               \
     }
+    // No select for the plane's edge columns.  Il = Im at i == 0 (convConst.cpp:503-507; a segment's warm-up starts the
+    // same way): `prev` is set to column xs after the prologue.  Ir = Im at i == w - 1: NXT was loaded as column
+    // min(i + 1, w - 1) with the column record of the same clamped index (LV_LOAD), i.e. column w - 1 again, from the
+    // same inputs by the same code in every mode — the same bits as Im; a segment that ends before w - 1 never gets
+    // there, and the tail's third step passes the same buffer twice.
 #define LV_FILTER(I, CUR, NXT)                                                                                      \
     {                                                                                                               \
         const int i_ = (I);                                                                                         \
@@ -923,8 +929,8 @@ __device__ __forceinline__ void level_body(const LevelJob& J, const int64_t f, c
         _Pragma("unroll") for (int k = 0; k < R; k++)                                                               \
         {                                                                                                           \
             const float Im = CUR[k];                                                                                \
-            const float Ir = (i_ < w - 1) ? NXT[k] : Im;                                                            \
-            const float Il = (i_ == xs) ? Im : prev[k]; /* Il = Im at i == 0 (convConst.cpp:503-507); a segment's warm-up starts the same way */ \
+            const float Ir = NXT[k];                                                                                \
+            const float Il = prev[k];                                                                               \
             T[k] = nrm * (Il + pv * Im + Ir);                                                                       \
             up[k] = wave_ror1(T[k]); /* T[y-1] for lanes 1..63 */                                                   \
             dn[k] = wave_rol1(T[k]); /* T[y+1] for lanes 0..62 */                                                   \
@@ -986,7 +992,7 @@ __device__ __forceinline__ void level_body(const LevelJob& J, const int64_t f, c
     {                                                                                                               \
         _Pragma("unroll") for (int k = 0; k < R; k++)                                                               \
         {                                                                                                           \
-            rrec[k] = rank_fetch(prev[k], rk.fn, rk.rec, rlow[k]);                                                  \
+            rrec[k] = rank_fetch(prev[k], rk.fn, rlow[k]);                                                          \
         }                                                                                                           \
     }
     // column COL of the rank level <- ranks of `prev` (COL < 0: nothing yet; the stores go out of the descriptor's range
@@ -999,19 +1005,36 @@ __device__ __forceinline__ void level_body(const LevelJob& J, const int64_t f, c
         uint32_t n_[R], up_[R];                                                                                     \
         _Pragma("unroll") for (int k = 0; k < R; k++)                                                               \
         {                                                                                                           \
-            n_[k] = rank_count(prev[k], rrec[k], rlow[k]);                                                          \
+            n_[k] = rank_count<(OUT & LO_RANK_NEG) != 0>(prev[k], rrec[k], rlow[k]);                                \
             up_[k] = __float_as_uint(wave_ror1(__uint_as_float(n_[k]))); /* row y-1's rank for lanes 1..63 */       \
         }                                                                                                           \
         _Pragma("unroll") for (int k = 0; k < R; k++)                                                               \
         {                                                                                                           \
             const uint32_t lo_ = (lane == 0) ? up_[k > 0 ? k - 1 : 0] : up_[k];                                     \
-            __builtin_amdgcn_raw_buffer_store_b32((n_[k] << 16) | (lo_ & 0xffffu), Rsrd, rvoff[k], so_, 0);         \
+            /* (lo_ is a rank: its upper half is zero, the pair is one v_lshl_or) */                                \
+            __builtin_amdgcn_raw_buffer_store_b32((n_[k] << 16) | lo_, Rsrd, rvoff[k], so_, 0);                     \
         }                                                                                                           \
     }
     // prologue: columns xs, xs + 1, xs + 2 -> b0, b1, b2
     LV_LOAD(b0, xs);
     LV_LOAD(b1, xs + 1);
     LV_LOAD(b2, xs + 2);
+    // the first column's left neighbour is the column itself (LV_FILTER).  Until the first filter step `prev` is also what
+    // the rank fetch of column xs - 1 reads — a finite value; its store is dropped — and never a segment's `spec` state
+    // (x0 > xs wherever spec is set: the warm-up is at least four columns).
+    if (MODE == LM_REAL)
+    {
+        // The copy waits for column xs anyway: wait for all three prologue columns, as an instruction the compiler's wait
+        // counting sees.  The waits at the loop's head must hold on entry as well as on the back edge, and the prologue
+        // issues its three columns interleaved: counted from there, "b1 has arrived" came out as vmcnt(3) — on the back
+        // edge a wait for the loads issued a few instructions earlier, every trip.  Nothing is in flight on entry now.
+        __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0), expcnt and lgkmcnt untouched
+    }
+#pragma unroll
+    for (int k = 0; k < R; k++)
+    {
+        prev[k] = b0[k];
+    }
     // a segment's state after its warm-up (x0 - xs is a multiple of 4: the loop below passes i == x0)
     const srd_t Ssrd = (SEG && sg.spec) ? make_srd(sg.spec, int64_t(h) * 4) : Osrd;
     int i = xs;
@@ -1161,7 +1184,6 @@ __global__ void __launch_bounds__(64 * LEVEL_WAVES) __attribute__((amdgpu_waves_
         rk.fn = rank_tables_to_lds(ra.chan[blockIdx.x], ra.rec, recL, threadIdx.x, 64 * LEVEL_WAVES);
         rk.out = ra.out;
         rk.fs = ra.fs;
-        rk.rec = recL;
         __syncthreads();
     }
     const int f = __builtin_amdgcn_readfirstlane(int(blockIdx.y) * LEVEL_WAVES + int(threadIdx.x >> 6));

@@ -115,8 +115,17 @@ static GradMagVecKernel gradMagVecKernel(bool blocked, bool x86)
     return x86 ? k_grad_mag_vec<false, true> : k_grad_mag_vec<false, false>;
 }
 
-static LevelAllKernel levelAllKernel(bool f32, bool rank, bool segmented)
+// rankNeg: the model holds a zero threshold (RankTables::hasZero): the rank forms that put negative cells below it
+static LevelAllKernel levelAllKernel(bool f32, bool rank, bool rankNeg, bool segmented)
 {
+    if (rank && rankNeg)
+    {
+        if (f32)
+        {
+            return segmented ? k_level_all<LO_F32 | LO_RANK | LO_RANK_NEG, 1> : k_level_all<LO_F32 | LO_RANK | LO_RANK_NEG, 0>;
+        }
+        return segmented ? k_level_all<LO_RANK | LO_RANK_NEG, 1> : k_level_all<LO_RANK | LO_RANK_NEG, 0>;
+    }
     if (f32 && rank)
     {
         return segmented ? k_level_all<LO_F32 | LO_RANK, 1> : k_level_all<LO_F32 | LO_RANK, 0>;
@@ -824,7 +833,7 @@ int PyramidRun::planLevels(int nLF)
     lc.lsa.spec = c->d_lvSpec;
     lc.lsa.tru = c->d_lvTrue;
     lc.lsa.redo = nullptr;
-    lc.allKernel = levelAllKernel(lc.emitF32, lc.emitRank, nSegL > 1);
+    lc.allKernel = levelAllKernel(lc.emitF32, lc.emitRank, c->cs.rankHasZero, nSegL > 1);
     return allowLds(c, reinterpret_cast<const void*>(lc.allKernel), lc.ldsL);
 }
 
