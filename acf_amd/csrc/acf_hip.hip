@@ -39,6 +39,7 @@ struct StripPlan
     int yt = 0, nty = 0, nSteps = 0, ntyB = 0, nStepsB = 0, tileY = 0, tileX = 0, rowsP = 0, maxCols = 0, slowRows = 0, fillRounds = 0, tileFloats = 0;
     uint32_t magic = 0;
     size_t lds = 0;
+    int why = 0; // !ok: the reason stripPlan refused (ACF_HIP_SF_WHY_*; 0: no plan was asked for)
 };
 
 struct RealScale
@@ -56,6 +57,7 @@ struct RealScale
     float* Ck = nullptr;
     int64_t ckFloats = 0;
     int triForm = 0;
+    int32_t scaleForm = 0; // acf_hip_get_scale_forms' run side (route, SLOW, xt, nty, nSplit), written by PyramidRun::imageResample
 };
 
 // Where the frames of a call come from: what every entry that takes frames hands to pyramidBody (input_run.hip.h holds the rest of
@@ -1964,6 +1966,25 @@ int acf_hip_get_level_forms(const acf_hip_ctx* c, int32_t* out, int cap, int* n)
     {
         const int32_t f = s->levelFormFused[size_t(i)], r = s->levelFormRaw[size_t(i)];
         out[ACF_HIP_LF_HEAD + i] = (f & why) | (path == ACF_HIP_LV_WAVE_SMOOTH ? r & form : path == ACF_HIP_LV_FUSED ? f & form : f & form & ~taker);
+    }
+    return ACF_HIP_OK;
+}
+
+int acf_hip_get_scale_forms(const acf_hip_ctx* c, int32_t* out, int cap, int* n)
+{
+    if (int rc = needPlanRead(c, "get_scale_forms")) return rc;
+    if (!n || (cap > 0 && !out))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    const acf_hip_ctx* s = c->kids.empty() ? c : c->kids[0]; // (sub-batch children hold the real scales; they all take the same routes)
+    *n = int(s->real.size());
+    for (int i = 0; i < *n && i < cap; i++)
+    {
+        // the run's side as imageResample wrote it, the plan's side as imageStrips / stripPlan left it
+        const RealScale& rs = s->real[size_t(i)];
+        out[i] = int32_t(uint32_t(rs.scaleForm) | (rs.strip.ok ? ACF_HIP_SF_PLAN_STRIP : 0) | (rs.stripPair.ok ? ACF_HIP_SF_PLAN_PAIR : 0) |
+            uint32_t(rs.strip.why) << 24 | uint32_t(rs.stripPair.why) << 28);
     }
     return ACF_HIP_OK;
 }

@@ -3,7 +3,7 @@
 // stream and ends with Scratch::download.
 //   acf_hip_op_yuv420_to_rgb, _op_resize_u8      the 8-bit front end's kernels on one frame
 //   acf_hip_op_nms                               bbNms of one list (k_nms)
-//   acf_hip_op_rgb_convert, _op_conv_tri, _op_gradient_mag, _op_gradient_hist, _op_im_resample   the channel operators (smoothOne, gradMagOne)
+//   acf_hip_op_rgb_convert, _op_conv_tri, _op_gradient_mag, _op_gradient_hist, _op_im_resample, _op_im_resample_pair   the channel operators (smoothOne, gradMagOne)
 //   acf_hip_chns_compute                         chnsCompute of one image at its own scale
 //   acf_hip_set_x86_tables, _selftest_x86, _selftest_gradmag   the reference-arithmetic tables and their checks on the device
 //   acf_hip_thrs_u8, opAcfDetect1 (acf_hip_op_acf_detect1, _u8), acf_hip_op_evaluate   the cascade on a caller's channel buffer
@@ -599,6 +599,32 @@ int acf_hip_op_gradient_hist(acf_hip_ctx* c, const float* M, const float* O, flo
     return Scratch::download(c, "op_gradient_hist", H, dH, size_t(nc) * nOrients);
 }
 
+// one output of the resample operators: the strip march where its plan holds, else k_resample_up, else the generic kernel
+static int resampleOpLaunch(acf_hip_ctx* c, const ResampleDesc& dd, const StripPlan& sp, const ResampleDesc* ddescs, int desc, const float* di, float* dout,
+    const int32_t* dit, const float* dft)
+{
+    if (sp.ok && !resampleGenericOnly())
+    {
+        // the strip march the pyramid uses for its down-sampled real scales
+        if (int rc = ensureConstTables(c))
+        {
+            return rc;
+        }
+        launchStrip(c, c->stream, sp, ddescs, desc, -1, dd.nplanes, di, dout, nullptr, dit, dft, 1);
+    }
+    else if (resampleUpOk(dd) && !resampleGenericOnly())
+    {
+        hipLaunchKernelGGL(k_resample_up, dim3(cdiv(dd.nplanes * cdiv(dd.hb, 256) * cdiv(dd.wb, RSU_XC), 4), 1, 1), dim3(256), 0, c->stream, di, dout, ddescs + desc,
+            dit, dft);
+    }
+    else
+    {
+        hipLaunchKernelGGL(k_resample, dim3(resampleBlocks(dd), 1, 1), dim3(64, 4), 0, c->stream, di, dout, ddescs + desc, dit, dft, RS_XT);
+    }
+    LAUNCHCHK(c, "k_resample");
+    return ACF_HIP_OK;
+}
+
 int acf_hip_op_im_resample(acf_hip_ctx* c, const float* in, float* out, int ha, int wa, int hb, int wb, int d, double nrm)
 {
     if (int rc = opBegin(c)) return rc;
@@ -629,23 +655,83 @@ int acf_hip_op_im_resample(acf_hip_ctx* c, const float* in, float* out, int ha, 
     {
         return fail(c, ACF_HIP_E_HIP, "op_im_resample: allocation");
     }
-    if (sp.ok && !resampleGenericOnly() && (rc = ensureConstTables(c)) == 0)
+    if ((rc = resampleOpLaunch(c, dd, sp, ddesc, 0, di, dout, dit, dft)))
     {
-        // the strip march the pyramid uses for its down-sampled real scales
-        launchStrip(c, c->stream, sp, ddesc, 0, -1, d, di, dout, nullptr, dit, dft, 1);
+        return rc;
     }
-    else if (resampleUpOk(dd) && !resampleGenericOnly())
+    return Scratch::download(c, "op_im_resample", out, dout, size_t(d) * hb * wb);
+}
+
+// Tests only: the two-output form of k_resample_strip, planned as PlanBuild::imageStrips plans two real scales of one source
+int acf_hip_op_im_resample_pair(acf_hip_ctx* c, const float* in, float* outA, float* outB, int ha, int wa, int hbA, int wbA, int hbB, int wbB, int d, double nrm,
+    uint64_t* word)
+{
+    if (int rc = opBegin(c)) return rc;
+    if (!in || !outA || !outB || !word || ha <= 0 || wa <= 0 || hbA <= 0 || wbA <= 0 || hbB <= 0 || wbB <= 0 || d <= 0 || hbB > hbA || wbB > wbA)
     {
-        hipLaunchKernelGGL(k_resample_up, dim3(cdiv(d * cdiv(hb, 256) * cdiv(wb, RSU_XC), 4), 1, 1), dim3(256), 0, c->stream, (const float*)di, dout,
-            (const ResampleDesc*)ddesc, (const int32_t*)dit, (const float*)dft);
+        return fail(c, ACF_HIP_E_INVALID, "op_im_resample_pair: arguments");
+    }
+    TableArena arena;
+    ResampleDesc dd[2];
+    const int hb[2] = { hbA, hbB }, wb[2] = { wbA, wbB };
+    const double ratio[3] = { nrm, nrm, nrm };
+    for (int i = 0; i < 2; i++)
+    {
+        if (int rc = buildResample(ha, wa, hb[i], wb[i], dd[i], arena))
+        {
+            return fail(c, rc, "op_im_resample_pair: degenerate geometry");
+        }
+        setResampleGain(dd[i], ratio, d, d);
+        dd[i].nplanes = d;
+        dd[i].src_frame_stride = int64_t(d) * ha * wa;
+        dd[i].dst_frame_stride = int64_t(d) * hb[i] * wb[i];
+    }
+    // (every plan appends its tile ranges to the int arena: all of them before the upload)
+    const StripPlan pair = resampleGenericOnly() ? StripPlan{} : stripPlan(dd[0], &dd[1], arena);
+    StripPlan one[2];
+    for (int i = 0; i < 2 && !pair.ok; i++)
+    {
+        one[i] = stripPlan(dd[i], nullptr, arena);
+    }
+    Scratch s;
+    float* di = s.upload(in, size_t(d) * ha * wa);
+    float* dout[2] = { s.alloc<float>(size_t(d) * hbA * wbA), s.alloc<float>(size_t(d) * hbB * wbB) };
+    ResampleDesc* ddesc = s.upload(dd, 2);
+    int32_t* dit = s.upload(arena.ints.data(), arena.ints.size());
+    float* dft = s.upload(arena.floats.data(), arena.floats.size());
+    if (!di || !dout[0] || !dout[1] || !ddesc || !dit || !dft)
+    {
+        return fail(c, ACF_HIP_E_HIP, "op_im_resample_pair: allocation");
+    }
+    int rc;
+    if (pair.ok)
+    {
+        if ((rc = ensureConstTables(c)))
+        {
+            return rc;
+        }
+        const int nSplit = launchStrip(c, c->stream, pair, ddesc, 0, 1, d, di, dout[0], dout[1], dit, dft, 1);
+        LAUNCHCHK(c, "k_resample_strip(pair)");
+        auto f = [](int v, int bits) { return uint64_t(std::min(v, (1 << bits) - 1)); };
+        *word = (pair.slowRows > 0 ? uint64_t(ACF_HIP_SF_SLOW) : 0) | f(pair.nty, 8) << 8 | f(pair.ntyB, 8) << 16 | f(nSplit, 8) << 24 | f(pair.nSteps, 16) << 32 |
+            f(pair.nStepsB, 16) << 48;
     }
     else
     {
-        hipLaunchKernelGGL(k_resample, dim3(resampleBlocks(dd), 1, 1), dim3(64, 4), 0, c->stream, (const float*)di, dout,
-            (const ResampleDesc*)ddesc, (const int32_t*)dit, (const float*)dft, RS_XT);
+        *word = uint64_t(pair.why);
+        for (int i = 0; i < 2; i++)
+        {
+            if ((rc = resampleOpLaunch(c, dd[i], one[i], ddesc, i, di, dout[i], dit, dft)))
+            {
+                return rc;
+            }
+        }
     }
-    LAUNCHCHK(c, "k_resample");
-    return Scratch::download(c, "op_im_resample", out, dout, size_t(d) * hb * wb);
+    if ((rc = Scratch::download(c, "op_im_resample_pair", outA, dout[0], size_t(d) * hbA * wbA)))
+    {
+        return rc;
+    }
+    return Scratch::download(c, "op_im_resample_pair", outB, dout[1], size_t(d) * hbB * wbB);
 }
 
 // thrs.convertTo(thrsU8, CV_8UC1, 255.0f) (ACFIOArchive.h:96-99): OpenCV's 32f->8u cvtScale works in f32 and rounds

@@ -338,6 +338,7 @@ int PyramidRun::realScale(size_t k)
     }
     const float* img = cur;
     int64_t img_fs = cur_fs;
+    rs.scaleForm = ACF_HIP_SF_ROUTE_NONE;
     if (rs.resampled && (rc = imageResample(k, img, img_fs)))
     {
         return rc;
@@ -389,9 +390,11 @@ int PyramidRun::imageResample(size_t k, const float*& img, int64_t& img_fs)
     const bool exactHalf = hd.xmode == RS_EXACT && hd.ymode == RS_EXACT && hd.xk == 2 && hd.yk == 2 && hd.ha % 4 == 0 && hd.hb % 2 == 0 &&
         hd.src_frame_stride % 4 == 0 && hd.dst_frame_stride % 2 == 0 && hd.src_off % 4 == 0 && hd.dst_off % 2 == 0 &&
         (uintptr_t(cur) & 15) == 0 && (uintptr_t(rs.img) & 7) == 0; // (k_resample_half's case: one thread per output pair)
+    // (rs.scaleForm: every branch writes down the route it is, for acf_hip_get_scale_forms)
     if (halfDone[k] || pairDone[k])
     {
         // already produced by the previous scale's k_smooth_vec, or together with the previous scale's image (k_resample_strip)
+        rs.scaleForm = halfDone[k] ? ACF_HIP_SF_ROUTE_HALF_FUSED : ACF_HIP_SF_ROUTE_PAIR_B;
     }
     else if (rs.strip.ok && !exactHalf && !resampleGenericOnly() && (uintptr_t(cur) & 15) == 0)
     {
@@ -401,14 +404,18 @@ int PyramidRun::imageResample(size_t k, const float*& img, int64_t& img_fs)
         {
             pairDone[k + 1] = 1;
         }
-        launchStrip(c, st, pair ? rs.stripPair : rs.strip, c->d_descs, rs.descIndex, pair ? c->real[k + 1].descIndex : -1, hd.nplanes, cur, rs.img,
+        const StripPlan& sp = pair ? rs.stripPair : rs.strip;
+        const int nSplit = launchStrip(c, st, sp, c->d_descs, rs.descIndex, pair ? c->real[k + 1].descIndex : -1, hd.nplanes, cur, rs.img,
             pair ? c->real[k + 1].img : nullptr, c->d_it, c->d_ft, nF);
+        rs.scaleForm = (pair ? ACF_HIP_SF_ROUTE_STRIP_PAIR_A : ACF_HIP_SF_ROUTE_STRIP) | (sp.slowRows > 0 ? ACF_HIP_SF_SLOW : 0) | std::min(sp.nty, 255) << 8 |
+            std::min(nSplit, 255) << 16;
     }
     else if (exactHalf)
     {
         const int64_t items = int64_t(hd.hb / 2) * hd.wb * hd.nplanes;
         hipLaunchKernelGGL(k_resample_half, dim3(cdiv(items, 256), 1, nF), dim3(256), 0, st, cur, rs.img,
             (const ResampleDesc*)(c->d_descs + rs.descIndex));
+        rs.scaleForm = ACF_HIP_SF_ROUTE_HALF;
     }
     else if (resampleUpOk(hd) && !resampleGenericOnly() && (uintptr_t(rs.img) & 15) == 0)
     {
@@ -416,6 +423,7 @@ int PyramidRun::imageResample(size_t k, const float*& img, int64_t& img_fs)
         const int nw = hd.nplanes * cdiv(hd.hb, 256) * cdiv(hd.wb, RSU_XC);
         hipLaunchKernelGGL(k_resample_up, dim3(cdiv(nw, 4), 1, nF), dim3(256), 0, st, cur, rs.img,
             (const ResampleDesc*)(c->d_descs + rs.descIndex), (const int32_t*)c->d_it, (const float*)c->d_ft);
+        rs.scaleForm = ACF_HIP_SF_ROUTE_UP;
     }
     else
     {
@@ -423,6 +431,7 @@ int PyramidRun::imageResample(size_t k, const float*& img, int64_t& img_fs)
         const int xt = int64_t(resampleBlocks(hd)) * nF < 4096 ? 2 : RS_XT;
         hipLaunchKernelGGL(k_resample, dim3(resampleBlocks(hd, xt), 1, nF), dim3(64, 4), 0, st, cur, rs.img,
             (const ResampleDesc*)(c->d_descs + rs.descIndex), (const int32_t*)c->d_it, (const float*)c->d_ft, xt);
+        rs.scaleForm = ACF_HIP_SF_ROUTE_GENERIC | (xt == 2 ? ACF_HIP_SF_XT2 : 0);
     }
     LAUNCHCHK(c, "k_resample(image)");
     img = rs.img;

@@ -9,10 +9,26 @@ static StripPlan stripPlan(const ResampleDesc& da, const ResampleDesc* db, Table
 {
     StripPlan sp;
     auto down = [](const ResampleDesc& d) { return (d.xmode == RS_DOWN || d.xmode == RS_EXACT) && (d.ymode == RS_DOWN || d.ymode == RS_EXACT); };
-    if (!down(da) || (db && !down(*db)) || da.ha % 4 || da.ha < 8 || da.src_frame_stride % 4 || da.src_off % 4 ||
-        (db && (db->ha != da.ha || db->wa != da.wa || db->nplanes != da.nplanes || db->src_frame_stride != da.src_frame_stride || db->src_off != da.src_off)))
-    {
+    // (every refusal leaves its reason in sp.why, ACF_HIP_SF_WHY_*: acf_hip_get_scale_forms reports it)
+    auto refuse = [&](int why) {
+        sp.why = why;
         return sp;
+    };
+    if (!down(da) || (db && !down(*db)))
+    {
+        return refuse(ACF_HIP_SF_WHY_NOT_DOWN);
+    }
+    if (da.ha % 4 || da.ha < 8)
+    {
+        return refuse(ACF_HIP_SF_WHY_ROWS);
+    }
+    if (da.src_frame_stride % 4 || da.src_off % 4)
+    {
+        return refuse(ACF_HIP_SF_WHY_ALIGN);
+    }
+    if (db && (db->ha != da.ha || db->wa != da.wa || db->nplanes != da.nplanes || db->src_frame_stride != da.src_frame_stride || db->src_off != da.src_off))
+    {
+        return refuse(ACF_HIP_SF_WHY_PAIR_MISMATCH);
     }
     const int32_t* it = arena.ints.data();
     auto rowRange = [&](const ResampleDesc& d, int yb0, int yb1, int& lo, int& hi) {
@@ -62,7 +78,7 @@ static StripPlan stripPlan(const ResampleDesc& da, const ResampleDesc* db, Table
     };
     if (!slowOk(da) || (db && !slowOk(*db)))
     {
-        return sp;
+        return refuse(ACF_HIP_SF_WHY_SLOW_TAPS);
     }
     auto fourTaps = [&](const ResampleDesc& d) {
         for (int x = 0; x < d.wb; x++)
@@ -76,12 +92,12 @@ static StripPlan stripPlan(const ResampleDesc& da, const ResampleDesc* db, Table
     };
     if (!fourTaps(da) || (db && !fourTaps(*db)))
     {
-        return sp; // (x ratios above 4: the generic kernels)
+        return refuse(ACF_HIP_SF_WHY_X_TAPS); // (x ratios above 4: the generic kernels)
     }
     const int nSteps = cdiv(da.wb, RS_XO), nStepsB = db ? cdiv(db->wb, RS_XO / 2) : 0;
     if (nStepsB > nSteps)
     {
-        return sp;
+        return refuse(ACF_HIP_SF_WHY_B_STEPS);
     }
     std::vector<int32_t> tx;
     int maxC = 0;
@@ -169,11 +185,11 @@ static StripPlan stripPlan(const ResampleDesc& da, const ResampleDesc* db, Table
         arena.ints.insert(arena.ints.end(), tx.begin(), tx.end());
         return sp;
     }
-    return sp;
+    return refuse(ACF_HIP_SF_WHY_NO_TILING);
 }
 
-// k_resample_strip for one output (descB < 0) or two outputs of one source
-static void launchStrip(acf_hip_ctx* c, hipStream_t st, const StripPlan& sp, const ResampleDesc* d_descs, int descA, int descB, int nplanes, const float* src, float* dstA,
+// k_resample_strip for one output (descB < 0) or two outputs of one source; returns the column segments it chose (nSplit)
+static int launchStrip(acf_hip_ctx* c, hipStream_t st, const StripPlan& sp, const ResampleDesc* d_descs, int descA, int descB, int nplanes, const float* src, float* dstA,
     float* dstB, const int32_t* d_it, const float* d_ft, int nF)
 {
     const bool pair = descB >= 0;
@@ -234,6 +250,7 @@ static void launchStrip(acf_hip_ctx* c, hipStream_t st, const StripPlan& sp, con
     {
         hipLaunchKernelGGL((k_resample_strip<false, false>), sgrid, dim3(RS_NT), ldsS, st, sa);
     }
+    return sa.nSplit;
 }
 
 // Tiling of a down-sampling descriptor for the passes on LDS tiles (k_ldcf_tile): output columns per tile (the largest of 32/16/8 whose

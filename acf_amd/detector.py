@@ -776,6 +776,25 @@ class HipDetector:
         return dict(path=self.LEVEL_PATHS[out[0]], emit_rank=bool(out[1]), emit_f32=bool(out[2]), segments=int(out[3]),
                     approx_first=bool(out[4]), levels=levels)
 
+    SCALE_ROUTES = ("none", "half_fused", "pair_b", "strip", "strip_pair_a", "half", "up", "generic")
+    STRIP_WHY = (None, "not_down", "rows", "align", "pair_mismatch", "slow_taps", "x_taps", "b_steps", "no_tiling")
+
+    def scale_forms(self):
+        """How each real scale's image was resampled (acf_hip_get_scale_forms): per real scale dict(route = a SCALE_ROUTES name of the
+        last pyramid call ("none" before the first), slow, xt2, nty, n_split of the launch it made, plan_strip / plan_pair = the plan
+        holds a strip plan of the scale alone / with the next scale, why / why_pair = the STRIP_WHY name of the plan's refusal or None)."""
+        cap = 64
+        n = C.c_int()
+        out = (C.c_int32 * cap)()
+        self._chk(self.lib.acf_hip_get_scale_forms(self.ctx, out, cap, C.byref(n)))
+        forms = []
+        for i in range(min(n.value, cap)):
+            w = int(out[i]) & 0xffffffff
+            forms.append(dict(route=self.SCALE_ROUTES[w & 15], slow=bool(w >> 4 & 1), xt2=bool(w >> 5 & 1), plan_strip=bool(w >> 6 & 1),
+                              plan_pair=bool(w >> 7 & 1), nty=w >> 8 & 255, n_split=w >> 16 & 255, why=self.STRIP_WHY[w >> 24 & 15],
+                              why_pair=self.STRIP_WHY[w >> 28 & 15]))
+        return forms
+
     def set_option(self, key, value):
         self._chk(self.lib.acf_hip_set_option(self.ctx, key.encode(), int(value)))
 
@@ -918,6 +937,21 @@ class HipDetector:
         out = np.zeros((d, wb, hb), dtype=np.float32)
         self._chk(self.lib.acf_hip_op_im_resample(self.ctx, capi.fptr(a), capi.fptr(out), ha, wa, hb, wb, d, float(nrm)))
         return out
+
+    def op_im_resample_pair(self, a, hbA, wbA, hbB, wbB, nrm=1.0):
+        """Two resamples of one source through k_resample_strip's two-output form (acf_hip_op_im_resample_pair, tests only) ->
+        (outA, outB, dict(pair = it was launched, why = the STRIP_WHY name of the pair plan's refusal or None, slow, nty, nty_b, n_split,
+        n_steps, n_steps_b of the launch))."""
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        d, wa, ha = a.shape
+        outA = np.zeros((d, wbA, hbA), dtype=np.float32)
+        outB = np.zeros((d, wbB, hbB), dtype=np.float32)
+        word = C.c_uint64()
+        self._chk(self.lib.acf_hip_op_im_resample_pair(self.ctx, capi.fptr(a), capi.fptr(outA), capi.fptr(outB), ha, wa, hbA, wbA, hbB, wbB, d, float(nrm),
+                                                       C.byref(word)))
+        w = int(word.value)
+        return outA, outB, dict(pair=(w & 15) == 0 and (w >> 8 & 255) > 0, why=self.STRIP_WHY[w & 15], slow=bool(w >> 4 & 1), nty=w >> 8 & 255,
+                                nty_b=w >> 16 & 255, n_split=w >> 24 & 255, n_steps=w >> 32 & 0xffff, n_steps_b=w >> 48 & 0xffff)
 
     def op_acf_detect1(self, chns, cap=1 << 16):
         chns = np.ascontiguousarray(chns, dtype=np.float32)

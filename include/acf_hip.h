@@ -983,6 +983,39 @@ ACF_HIP_API int acf_hip_get_tri_forms(const acf_hip_ctx* ctx, int32_t* out, int 
 #define ACF_HIP_LF_WHY_TALL (1 << 20)   /* taller than the tallest level kernel */
 #define ACF_HIP_LF_WHY_MIXED (1 << 21)  /* one axis up, the other down */
 ACF_HIP_API int acf_hip_get_level_forms(const acf_hip_ctx* ctx, int32_t* out, int cap, int* n);
+/* Read-only: how every real scale's image was resampled, written down where it is decided: the route and the launch by the last
+ * acf_hip_pyramid / acf_hip_run* call (zero before the first), the plan's side by acf_hip_plan.  out[i] for real scale i (at most
+ * `cap`; *n = their number):
+ *   bits 0-3   the route (ACF_HIP_SF_ROUTE_*)
+ *   bit 4      the launch was a SLOW instantiation of k_resample_strip (an output with more than four y taps)
+ *   bit 5      the generic k_resample ran with 2 columns per wave (else RS_XT)
+ *   bit 6, 7   the plan holds a strip plan of this scale alone / of this scale together with the next one
+ *   bits 8-15  nty, bits 16-23 nSplit: the row tiles and column segments of the k_resample_strip launch this scale made (routes
+ *              STRIP and STRIP_PAIR_A; 0 otherwise — PAIR_B made no launch of its own)
+ *   bits 24-27 why the plan of this scale alone was refused, bits 28-31 why the plan of the pair was (ACF_HIP_SF_WHY_*; 0: not
+ *              refused, or no plan was asked for)
+ * Additive: ACF_HIP_ABI_VERSION stays. */
+#define ACF_HIP_SF_ROUTE_NONE 0         /* not resampled: the frame itself */
+#define ACF_HIP_SF_ROUTE_HALF_FUSED 1   /* written by the previous scale's k_smooth_vec (its exact half) */
+#define ACF_HIP_SF_ROUTE_PAIR_B 2       /* output B of the previous scale's k_resample_strip<true, .> */
+#define ACF_HIP_SF_ROUTE_STRIP 3        /* k_resample_strip<false, .> */
+#define ACF_HIP_SF_ROUTE_STRIP_PAIR_A 4 /* k_resample_strip<true, .>, which wrote the next scale as well */
+#define ACF_HIP_SF_ROUTE_HALF 5         /* k_resample_half */
+#define ACF_HIP_SF_ROUTE_UP 6           /* k_resample_up */
+#define ACF_HIP_SF_ROUTE_GENERIC 7      /* k_resample */
+#define ACF_HIP_SF_SLOW (1 << 4)
+#define ACF_HIP_SF_XT2 (1 << 5)
+#define ACF_HIP_SF_PLAN_STRIP (1 << 6)
+#define ACF_HIP_SF_PLAN_PAIR (1 << 7)
+#define ACF_HIP_SF_WHY_NOT_DOWN 1       /* an axis up-sampled */
+#define ACF_HIP_SF_WHY_ROWS 2           /* source rows not a multiple of 4, or fewer than 8 */
+#define ACF_HIP_SF_WHY_ALIGN 3          /* the source planes are not 16-byte aligned */
+#define ACF_HIP_SF_WHY_PAIR_MISMATCH 4  /* the two outputs do not share their source */
+#define ACF_HIP_SF_WHY_SLOW_TAPS 5      /* more than 8 y taps, or taps further than 15 rows apart */
+#define ACF_HIP_SF_WHY_X_TAPS 6         /* more than 4 x taps */
+#define ACF_HIP_SF_WHY_B_STEPS 7        /* output B needs more column steps than output A */
+#define ACF_HIP_SF_WHY_NO_TILING 8      /* no row tiling fits the kernel's LDS, item and chunk bounds */
+ACF_HIP_API int acf_hip_get_scale_forms(const acf_hip_ctx* ctx, int32_t* out, int cap, int* n);
 /* Host only (tests): the checkpoint buffer of an h x w plane — out[0] = float index of the (T, U) pair that row y's replay of the
  * 16-column segment holding column x starts from, out[1] = floats per frame.  Per frame
  * [x >> 6][(y + 8) >> 4][(x >> 4) & 3][(y + 8) & 15][2]: the 16 rows x 4 segments a wave of the y kernel takes per step are 512
@@ -1067,6 +1100,13 @@ ACF_HIP_API int acf_hip_op_gradient_hist(acf_hip_ctx* ctx, const float* M, const
     int h, int w, int bin, int nOrients, int soft_bin, int full);
 /* imResample (imResampleMex.cpp:385-420). */
 ACF_HIP_API int acf_hip_op_im_resample(acf_hip_ctx* ctx, const float* in, float* out, int ha, int wa, int hb, int wb, int d, double nrm);
+/* Tests only: two imResample outputs of one source ([d][wa][ha] -> outA [d][wbA][hbA] and outB [d][wbB][hbB], B no larger than A
+ * on either axis), planned and launched as the pyramid plans two real scales of one source: k_resample_strip's two-output form
+ * where its plan holds, else each output as acf_hip_op_im_resample runs it.  *word says which: bits 0-3 = why the pair plan was
+ * refused (ACF_HIP_SF_WHY_*); 0 and bits 8-15 non-zero = the pair was launched, with bit 4 = a SLOW instantiation, bits 8-15 nty,
+ * 16-23 ntyB, 24-31 nSplit, 32-47 nSteps, 48-63 nStepsB.  Additive: ACF_HIP_ABI_VERSION stays. */
+ACF_HIP_API int acf_hip_op_im_resample_pair(acf_hip_ctx* ctx, const float* in, float* outA, float* outB, int ha, int wa, int hbA, int wbA, int hbB, int wbB,
+    int d, double nrm, uint64_t* word);
 /* Detector::acfDetect1 on one host channel buffer [nChns][wP][hP] (acfDetect1.cpp:309-335). */
 ACF_HIP_API int acf_hip_op_acf_detect1(acf_hip_ctx* ctx, const float* chns, int hP, int wP, int nChns,
     acf_hip_hit* out, int cap, int* count);
