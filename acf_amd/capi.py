@@ -19,6 +19,7 @@ NMS_CAP = 2048  # ACF_HIP_NMS_CAP
 CS_GRAY, CS_RGB, CS_LUV, CS_HSV, CS_ORIG = 0, 1, 2, 3, 4
 TAP_IMAGE, TAP_SMOOTHED, TAP_M, TAP_O, TAP_S, TAP_MNORM, TAP_CHNS, TAP_LDCF = range(8)
 LF_HEAD = 6  # ACF_HIP_LF_HEAD: acf_hip_get_level_forms' call-wide words
+CF_WORDS = 30  # ACF_HIP_CF_WORDS: acf_hip_get_cascade_forms' record
 
 
 class Params(C.Structure):
@@ -322,6 +323,7 @@ def load():
         "acf_hip_tri_ck_layout": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)], C.c_int),
         "acf_hip_get_level_forms": ([ctx, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)], C.c_int),
         "acf_hip_get_scale_forms": ([ctx, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_get_cascade_forms": ([ctx, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)], C.c_int),
         "acf_hip_profile_get": ([ctx, C.POINTER(C.c_int), C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int], C.c_int),
         "acf_hip_read_level": ([ctx, C.c_int, C.c_int, fp], C.c_int),
         "acf_hip_read_rank_level": ([ctx, C.c_int, C.c_int, C.POINTER(C.c_uint16)], C.c_int),
@@ -338,6 +340,7 @@ def load():
         "acf_hip_op_im_resample": ([ctx, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double], C.c_int),
         "acf_hip_op_im_resample_pair": ([ctx, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_uint64)], C.c_int),
         "acf_hip_op_acf_detect1": ([ctx, fp, C.c_int, C.c_int, C.c_int, C.POINTER(Hit), C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_op_acf_detect1_rank": ([ctx, fp, C.c_int, C.c_int, C.c_int, C.POINTER(Hit), C.c_int, C.POINTER(C.c_int)], C.c_int),
         "acf_hip_op_acf_detect1_u8": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(Hit), C.c_int, C.POINTER(C.c_int)], C.c_int),
         "acf_hip_thrs_u8": ([fp, C.c_int, C.c_void_p], C.c_int),
         "acf_hip_op_evaluate": ([ctx, fp, C.c_int, C.c_int, C.c_int, C.c_double, fp], C.c_int),
@@ -360,9 +363,9 @@ DECLARED_SYMBOLS = [
     "acf_hip_detect", "acf_hip_run", "acf_hip_run_host", "acf_hip_set_nms", "acf_hip_op_nms", "acf_hip_get_detections", "acf_hip_get_hits", "acf_hip_get_raw_detections",
     "acf_hip_pyramid_u8", "acf_hip_run_u8", "acf_hip_set_yuv_layout", "acf_hip_op_yuv420_to_rgb", "acf_hip_u8_frame_bytes", "acf_hip_resize_dims", "acf_hip_set_input_resize", "acf_hip_op_resize_u8", "acf_hip_stream_open", "acf_hip_stream_submit", "acf_hip_stream_collect",
     "acf_hip_stream_close", "acf_hip_host_alloc", "acf_hip_host_free",
-    "acf_hip_export_detections", "acf_hip_synchronize", "acf_hip_get_repairs", "acf_hip_get_tri_forms", "acf_hip_get_level_forms", "acf_hip_get_scale_forms", "acf_hip_tri_ck_layout", "acf_hip_profile_get", "acf_hip_read_level", "acf_hip_read_rank_level", "acf_hip_rank_cells_host", "acf_hip_read_tap",
+    "acf_hip_export_detections", "acf_hip_synchronize", "acf_hip_get_repairs", "acf_hip_get_tri_forms", "acf_hip_get_level_forms", "acf_hip_get_scale_forms", "acf_hip_get_cascade_forms", "acf_hip_tri_ck_layout", "acf_hip_profile_get", "acf_hip_read_level", "acf_hip_read_rank_level", "acf_hip_rank_cells_host", "acf_hip_read_tap",
     "acf_hip_op_rgb_convert", "acf_hip_op_conv_tri", "acf_hip_op_gradient_mag", "acf_hip_selftest_gradmag", "acf_hip_set_x86_tables", "acf_hip_selftest_x86", "acf_hip_chns_compute", "acf_hip_op_gradient_hist",
-    "acf_hip_op_im_resample", "acf_hip_op_im_resample_pair", "acf_hip_op_acf_detect1", "acf_hip_op_acf_detect1_u8", "acf_hip_thrs_u8", "acf_hip_op_evaluate",
+    "acf_hip_op_im_resample", "acf_hip_op_im_resample_pair", "acf_hip_op_acf_detect1", "acf_hip_op_acf_detect1_rank", "acf_hip_op_acf_detect1_u8", "acf_hip_thrs_u8", "acf_hip_op_evaluate",
     "acf_hip_evaluate_crops", "acf_hip_evaluate_crops_u8",
     "acf_hip_pyramid_image", "acf_hip_run_image", "acf_hip_image_extent",
     "acf_hip_pyramid_yuv", "acf_hip_run_yuv", "acf_hip_yuv_to_rgb8", "acf_hip_yuv_extent", "acf_hip_yuv_layout", "acf_hip_stream_open_yuv",

@@ -7,6 +7,7 @@
 #include "kernels.hip.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -342,6 +343,10 @@ struct PlanState : LastRun
     // raw list), and the call-wide words the last pyramid call's planLevels left
     std::vector<int32_t> levelFormFused, levelFormRaw;
     int32_t levelCallForm[ACF_HIP_LF_HEAD] = { 0, 0, 0, 0, 0, 0 };
+    // acf_hip_get_cascade_forms: the record of the last runCascade on this context (noteCascadeForms), and its place in the order
+    // of the process's cascade calls (0: none yet) — a parent's operator call against its sub-batch children's pipeline calls
+    int32_t cascadeForm[ACF_HIP_CF_WORDS] = {};
+    uint64_t cascadeFormSeq = 0;
     // k_smooth_vec's speculative column segments (kernels.hip.h): state of the segments' hand-overs, planes to repair
     float *d_specState = nullptr, *d_trueState = nullptr;
     int32_t* d_redo = nullptr;
@@ -1986,6 +1991,20 @@ int acf_hip_get_scale_forms(const acf_hip_ctx* c, int32_t* out, int cap, int* n)
         out[i] = int32_t(uint32_t(rs.scaleForm) | (rs.strip.ok ? ACF_HIP_SF_PLAN_STRIP : 0) | (rs.stripPair.ok ? ACF_HIP_SF_PLAN_PAIR : 0) |
             uint32_t(rs.strip.why) << 24 | uint32_t(rs.stripPair.why) << 28);
     }
+    return ACF_HIP_OK;
+}
+
+int acf_hip_get_cascade_forms(const acf_hip_ctx* c, int32_t* out, int cap, int* n)
+{
+    if (int rc = needCtx(c)) return rc;
+    if (!n || (cap > 0 && !out))
+    {
+        return ACF_HIP_E_INVALID;
+    }
+    // (sub-batch children run the pipeline's cascades, all in the same forms; the operator's runs on the context itself)
+    const acf_hip_ctx* s = !c->kids.empty() && c->kids[0]->cascadeFormSeq > c->cascadeFormSeq ? c->kids[0] : c;
+    *n = ACF_HIP_CF_WORDS;
+    std::copy(s->cascadeForm, s->cascadeForm + std::max(0, std::min(cap, ACF_HIP_CF_WORDS)), out);
     return ACF_HIP_OK;
 }
 

@@ -3,6 +3,7 @@
 //   planCascadeCall   decides ONCE what a call launches (CascadeCall): the path — depth 2 from LDS tiles (k_cascade_tile3 + tails), or
 //                     the staged path with, for depths 1, 3, 4, a tile stage in front (k_cascade_tile3D / tileD) —, cell type, stage
 //                     bounds, kernel forms and launch geometry.  cascadePath / wholeCascadeTiled answer from the same code.
+//   noteCascadeForms  copies that record into the context for acf_hip_get_cascade_forms (read-only: no launch reads the copy)
 //   runCascade        acfDetect1 on every level of a batch, straight down: clearCounters, ensureRankCells, launchTiled2 (+
 //                     launchTiled2Tails) or launchTileStageD + launchStages (+ launchStagedTail), then sortHits (k_expand_hits for
 //                     stride < shrink, k_sort_map: scale-ordered output + box mapping, ACF.cpp:302-329)
@@ -309,6 +310,44 @@ static CascadeCall planCascadeCall(const acf_hip_ctx* c, const CascState& cs, co
         planStaged(c, cs, call);
     }
     return call;
+}
+
+// acf_hip_get_cascade_forms' record: the call as the launch functions below will read it, word for word (include/acf_hip.h).  It
+// decides nothing and no launch reads it.
+static std::atomic<uint64_t> g_cascadeFormSeq{ 0 };
+
+static void noteCascadeForms(acf_hip_ctx* c, const CascState& cs, const CascadeCall& call)
+{
+    int32_t* w = c->cascadeForm;
+    std::fill(w, w + ACF_HIP_CF_WORDS, 0);
+    w[0] = call.path == CascPath::Tiled2 ? ACF_HIP_CF_PATH_TILED2 : call.path == CascPath::Staged ? ACF_HIP_CF_PATH_STAGED : ACF_HIP_CF_PATH_NONE;
+    w[1] = call.rank;
+    if (call.ts)
+    {
+        const TileGeom& g = call.ts->g;
+        w[2] = call.tile3 ? ACF_HIP_CF_TILE_3 : g.pooled ? ACF_HIP_CF_TILE_3D : ACF_HIP_CF_TILE_D;
+        w[3] = g.NW;
+        w[4] = g.TR;
+        w[5] = g.TC;
+        w[6] = g.passW;
+        w[7] = g.pooled;
+        std::copy(g.b, g.b + 5, w + 8);
+        w[13] = call.ts->nTiles;
+        w[14] = int32_t(call.grid.blocks);
+        w[15] = call.grid.persist;
+        w[16] = int32_t(call.tileLds);
+    }
+    w[17] = call.nStages;
+    std::copy(call.bounds, call.bounds + 4, w + 18);
+    w[22] = call.firstStage;
+    w[23] = call.mode;
+    w[24] = call.codeScan;
+    w[25] = call.pooledTail;
+    w[26] = call.waveTail;
+    w[27] = cs.codes.cap;
+    w[28] = cs.qcap;
+    w[29] = call.in.nF;
+    c->cascadeFormSeq = ++g_cascadeFormSeq;
 }
 
 // The counters of the call's path to zero: the hit counts and what QueueCounters lists for the path
@@ -719,6 +758,7 @@ static int sortHits(acf_hip_ctx* c, const CascState& cs, const CascadeCall& call
 static int runCascade(acf_hip_ctx* c, const CascState& cs, const CascInput& in, const BoxLevel* d_box, bool* ranks = nullptr)
 {
     const CascadeCall call = planCascadeCall(c, cs, in, ranks != nullptr);
+    noteCascadeForms(c, cs, call);
     prof(c, c->stream, "k_cascade");
     int rc;
     if ((!call.countersCleared && (rc = clearCounters(c, cs, call))) || (rc = ensureRankCells(c, cs, call, ranks)))

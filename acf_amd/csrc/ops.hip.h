@@ -6,7 +6,7 @@
 //   acf_hip_op_rgb_convert, _op_conv_tri, _op_gradient_mag, _op_gradient_hist, _op_im_resample, _op_im_resample_pair   the channel operators (smoothOne, gradMagOne)
 //   acf_hip_chns_compute                         chnsCompute of one image at its own scale
 //   acf_hip_set_x86_tables, _selftest_x86, _selftest_gradmag   the reference-arithmetic tables and their checks on the device
-//   acf_hip_thrs_u8, opAcfDetect1 (acf_hip_op_acf_detect1, _u8), acf_hip_op_evaluate   the cascade on a caller's channel buffer
+//   acf_hip_thrs_u8, opAcfDetect1 (acf_hip_op_acf_detect1, _u8, _rank), acf_hip_op_evaluate   the cascade on a caller's channel buffer
 #pragma once
 
 int acf_hip_op_yuv420_to_rgb(acf_hip_ctx* c, const uint8_t* src, int rows, int cols, int pix, int rowStride, int64_t chromaOff, uint8_t* dst)
@@ -755,7 +755,11 @@ int acf_hip_thrs_u8(const float* thrs, int n, uint8_t* out)
 
 // acfDetect1 on one caller's channel buffer: a cascade state of its own (one level, one frame, cap hits), built, run and freed
 // here.  The plan's state, its batch and its resident results are not touched.  thrs == nullptr: the model's thresholds.
-static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::vector<float>* thrs, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count)
+// rank: the call as acf_hip_detect makes it on a plan's pyramid with rank cells (acf_hip_op_acf_detect1_rank) — the rank set built
+// with the tables, the rank cells made from the caller's floats by runCascade's ensureRankCells; refused where the call would
+// not read them.
+static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::vector<float>* thrs, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count,
+    bool rank = false)
 {
     if (int rc = opBegin(c)) return rc;
     if (int rc = needModel(c, "op_acf_detect1")) return rc;
@@ -785,7 +789,7 @@ static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::ve
     float* dChn = nullptr;
     uint8_t* dBytes = nullptr;
     int rc;
-    if ((rc = buildCascadeTables(c, lv, nChns, p.shrink, 1, th, cs)) || (rc = allocCascadeRun(c, cs, lv, th, cap)) || (rc = devUpload(c, &dBox, box)) ||
+    if ((rc = buildCascadeTables(c, lv, nChns, p.shrink, 1, th, cs, rank)) || (rc = allocCascadeRun(c, cs, lv, th, cap)) || (rc = devUpload(c, &dBox, box)) ||
         (rc = devAlloc(c, &dChn, n + 64)) || (u8 && (rc = devAlloc(c, &dBytes, n))))
     {
         return rc;
@@ -802,7 +806,13 @@ static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::ve
             return fail(c, ACF_HIP_E_HIP, "launch k_widen_u8");
         }
     }
-    if ((rc = runCascade(c, cs, { dChn, 0, 1, nChns }, dBox)))
+    const CascInput in = { dChn, 0, 1, nChns };
+    if (rank && !planCascadeCall(c, cs, in, true).rank)
+    {
+        return fail(c, ACF_HIP_E_UNSUPPORTED, "op_acf_detect1_rank: this model, buffer and these options give no cascade on rank cells");
+    }
+    bool ranksWritten = false; // (the caller's buffer has floats only: k_rank runs)
+    if ((rc = runCascade(c, cs, in, dBox, rank ? &ranksWritten : nullptr)))
     {
         return rc;
     }
@@ -824,6 +834,12 @@ static int opAcfDetect1(acf_hip_ctx* c, const void* chns, bool u8, const std::ve
 int acf_hip_op_acf_detect1(acf_hip_ctx* c, const float* chns, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count)
 {
     return opAcfDetect1(c, chns, false, nullptr, hP, wP, nChns, out, cap, count);
+}
+
+// Tests only: the same call with rank cells standing for the floats
+int acf_hip_op_acf_detect1_rank(acf_hip_ctx* c, const float* chns, int hP, int wP, int nChns, acf_hip_hit* out, int cap, int* count)
+{
+    return opAcfDetect1(c, chns, false, nullptr, hP, wP, nChns, out, cap, count, true);
 }
 
 // The uint8_t body of acfDetect1 (acfDetect1.cpp:157-166,187-192): features and thresholds are bytes, compared after

@@ -795,6 +795,25 @@ class HipDetector:
                               why_pair=self.STRIP_WHY[w >> 28 & 15]))
         return forms
 
+    CASCADE_PATHS = ("none", "tiled2", "staged")
+    CASCADE_TILE_KERNELS = (None, "tile3", "tile3D", "tileD")
+
+    def cascade_forms(self):
+        """What the last cascade call decided (acf_hip_get_cascade_forms; the pipeline's or the operator's, whichever ran last; None
+        before the first): dict(path = a CASCADE_PATHS name, rank, kernel = a CASCADE_TILE_KERNELS name, NW, TR, TC, passW, pooled, b,
+        nTiles, blocks, persist, tileLds, nStages, bounds, firstStage, mode, codeScan, pooledTail, waveTail, codes_cap, qcap, frames)."""
+        n = C.c_int()
+        out = (C.c_int32 * capi.CF_WORDS)()
+        self._chk(self.lib.acf_hip_get_cascade_forms(self.ctx, out, capi.CF_WORDS, C.byref(n)))
+        assert n.value == capi.CF_WORDS
+        w = [int(v) for v in out]
+        if w[29] == 0:
+            return None
+        return dict(path=self.CASCADE_PATHS[w[0]], rank=bool(w[1]), kernel=self.CASCADE_TILE_KERNELS[w[2]], NW=w[3], TR=w[4], TC=w[5], passW=w[6],
+                    pooled=bool(w[7]), b=tuple(w[8:13]), nTiles=w[13], blocks=w[14], persist=bool(w[15]), tileLds=w[16], nStages=w[17],
+                    bounds=tuple(w[18:22]), firstStage=w[22], mode=w[23], codeScan=bool(w[24]), pooledTail=bool(w[25]), waveTail=bool(w[26]),
+                    codes_cap=w[27], qcap=w[28], frames=w[29])
+
     def set_option(self, key, value):
         self._chk(self.lib.acf_hip_set_option(self.ctx, key.encode(), int(value)))
 
@@ -959,6 +978,16 @@ class HipDetector:
         hits = np.zeros(cap, dtype=capi.HIT_DTYPE)
         n = C.c_int()
         self._chk(self.lib.acf_hip_op_acf_detect1(self.ctx, capi.fptr(chns), hP, wP, nC, hits.ctypes.data_as(C.POINTER(capi.Hit)), cap, C.byref(n)))
+        return hits[:n.value].copy()
+
+    def op_acf_detect1_rank(self, chns, cap=1 << 16):
+        """op_acf_detect1 with rank cells standing for the floats (acf_hip_op_acf_detect1_rank, tests only); HipError (unsupported) where
+        the call would not read rank cells."""
+        chns = np.ascontiguousarray(chns, dtype=np.float32)
+        nC, wP, hP = chns.shape
+        hits = np.zeros(cap, dtype=capi.HIT_DTYPE)
+        n = C.c_int()
+        self._chk(self.lib.acf_hip_op_acf_detect1_rank(self.ctx, capi.fptr(chns), hP, wP, nC, hits.ctypes.data_as(C.POINTER(capi.Hit)), cap, C.byref(n)))
         return hits[:n.value].copy()
 
     def op_acf_detect1_u8(self, chns, thrs_u8=None, cap=1 << 16):

@@ -1016,6 +1016,26 @@ ACF_HIP_API int acf_hip_get_level_forms(const acf_hip_ctx* ctx, int32_t* out, in
 #define ACF_HIP_SF_WHY_B_STEPS 7        /* output B needs more column steps than output A */
 #define ACF_HIP_SF_WHY_NO_TILING 8      /* no row tiling fits the kernel's LDS, item and chunk bounds */
 ACF_HIP_API int acf_hip_get_scale_forms(const acf_hip_ctx* ctx, int32_t* out, int cap, int* n);
+/* Read-only: what the last cascade call of this context decided (planCascadeCall's record, copied where runCascade made it): the
+ * cascade of acf_hip_detect / acf_hip_run*, or of acf_hip_op_acf_detect1* — whichever ran last; all zero before the first and
+ * again after acf_hip_plan.  Needs no plan.  *n = ACF_HIP_CF_WORDS; at most `cap` words are written:
+ *   [0] path (ACF_HIP_CF_PATH_*)            [1] rank cells stood for the floats      [2] the tile kernel (ACF_HIP_CF_TILE_*)
+ *   [3] NW  [4] TR  [5] TC  [6] passW  [7] pooled  [8..12] b[0..4]  [13] nTiles: the geometry of the tile set that kernel ran on
+ *                                            (zero without a tile kernel)
+ *   [14] workgroups of the tile launch       [15] they were persistent                [16] its dynamic LDS in bytes
+ *   [17] nStages  [18..21] bounds  [22] firstStage  [23] mode: the staged path's stages (zero on the other paths)
+ *   [24] codeScan (leaf codes + ordered scan)  [25] pooledTail (k_cascade_tile3D wrote the codes)  [26] waveTail (a wave per entry)
+ *   [27] codes.cap  [28] qcap                [29] frames of the call
+ * Additive: ACF_HIP_ABI_VERSION stays. */
+#define ACF_HIP_CF_WORDS 30
+#define ACF_HIP_CF_PATH_NONE 0   /* no windows */
+#define ACF_HIP_CF_PATH_TILED2 1 /* depth 2: k_cascade_tile3 + its tails */
+#define ACF_HIP_CF_PATH_STAGED 2 /* k_cascade_first / _queue / _tail, for depths 1, 3, 4 with a tile kernel in front */
+#define ACF_HIP_CF_TILE_NONE 0
+#define ACF_HIP_CF_TILE_3 1      /* k_cascade_tile3 */
+#define ACF_HIP_CF_TILE_3D 2     /* k_cascade_tile3D */
+#define ACF_HIP_CF_TILE_D 3      /* k_cascade_tileD */
+ACF_HIP_API int acf_hip_get_cascade_forms(const acf_hip_ctx* ctx, int32_t* out, int cap, int* n);
 /* Host only (tests): the checkpoint buffer of an h x w plane — out[0] = float index of the (T, U) pair that row y's replay of the
  * 16-column segment holding column x starts from, out[1] = floats per frame.  Per frame
  * [x >> 6][(y + 8) >> 4][(x >> 4) & 3][(y + 8) & 15][2]: the 16 rows x 4 segments a wave of the y kernel takes per step are 512
@@ -1109,6 +1129,13 @@ ACF_HIP_API int acf_hip_op_im_resample_pair(acf_hip_ctx* ctx, const float* in, f
     int d, double nrm, uint64_t* word);
 /* Detector::acfDetect1 on one host channel buffer [nChns][wP][hP] (acfDetect1.cpp:309-335). */
 ACF_HIP_API int acf_hip_op_acf_detect1(acf_hip_ctx* ctx, const float* chns, int hP, int wP, int nChns,
+    acf_hip_hit* out, int cap, int* count);
+/* Tests only: the same call on 16-bit threshold-rank cells, as acf_hip_detect runs it on a plan's pyramid: the rank tables and the
+ * rank tile set of the model are built for the buffer, k_rank makes the rank cells from the caller's floats, and the tile kernel
+ * (and, depth 2, the tail) read only those.  ACF_HIP_E_UNSUPPORTED where no rank set can be built or the call would not read it
+ * (option "rank_cells" or "cascade_tiles" off, a depth without a tile kernel, thresholds the rank tables do not admit): floats are
+ * never run in its place.  Additive: ACF_HIP_ABI_VERSION stays. */
+ACF_HIP_API int acf_hip_op_acf_detect1_rank(acf_hip_ctx* ctx, const float* chns, int hP, int wP, int nChns,
     acf_hip_hit* out, int cap, int* count);
 
 /* The uint8_t body of acfDetect1 (ParallelDetectionBody<uint8_t,...>, acfDetect1.cpp:157-166,187-192) on one host
