@@ -209,6 +209,23 @@ class CropSpec(C.Structure):
                 ("max_per_frame", C.c_int32), ("grow", C.c_float), ("reserved", C.c_int32)]
 
 
+class MergedDetection(C.Structure):
+    """struct acf_hip_merged_detection: a detection of a view in the upright stored frame (the bounding box of its quad)."""
+
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("w", C.c_float), ("h", C.c_float), ("score", C.c_float), ("view", C.c_int32),
+                ("index", C.c_int32), ("scale", C.c_int32)]
+
+
+MERGED_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("w", "<f4"), ("h", "<f4"), ("score", "<f4"), ("view", "<i4"), ("index", "<i4"), ("scale", "<i4")])
+MERGE_VIEWS_MAX = 1024   # n_views of acf_hip_merge_views
+
+
+class MergeSpec(C.Structure):
+    """struct acf_hip_merge_spec: the NMS across the views of one stored frame, records per frame and the growth of boxes_out."""
+
+    _fields_ = [("nms", NmsParams), ("max_per_frame", C.c_int32), ("grow", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
 _lib = None
 
 
@@ -298,6 +315,8 @@ def load():
         "acf_hip_view_quad": ([fp, C.POINTER(C.c_int32), fp], C.c_int),
         "acf_hip_view_box": ([fp, C.POINTER(C.c_int32), fp], C.c_int),
         "acf_hip_view_form": ([fp] + [C.c_int] * 9 + [C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_merge_views": ([ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(MergeSpec)] + [C.c_void_p] * 5, C.c_int),
+        "acf_hip_op_merge_views": ([ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(MergeSpec)] + [C.c_void_p] * 5, C.c_int),
         "acf_hip_unorient_rect": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
@@ -379,6 +398,7 @@ DECLARED_SYMBOLS = [
     "acf_hip_video_layout", "acf_hip_yuv_coeffs",
     "acf_hip_cut_crops", "acf_hip_cut_detections", "acf_hip_crop_box", "acf_hip_crop_bytes", "acf_hip_crop_form",
     "acf_hip_pyramid_view", "acf_hip_run_view", "acf_hip_view_from_box", "acf_hip_view_quad", "acf_hip_view_box", "acf_hip_view_form",
+    "acf_hip_merge_views", "acf_hip_op_merge_views",
 ]
 
 

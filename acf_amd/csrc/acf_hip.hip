@@ -2597,4 +2597,6 @@ int acf_hip_set_nms(acf_hip_ctx* c, const acf_hip_nms_params* q)
 
 #include "cut_run.hip.h"   // acf_hip_cut_crops / _cut_detections: crops of the stored frame under boxes or the last batch's detections (k_cut_crops)
 
+#include "merge_run.hip.h" // acf_hip_merge_views / _op_merge_views: the views' detections merged into their stored frames (k_merge_views)
+
 } // extern "C"

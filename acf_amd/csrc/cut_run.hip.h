@@ -206,7 +206,7 @@ int acf_hip_cut_detections(acf_hip_ctx* c, const acf_hip_crop_source* src, doubl
     }
     if (c->viewRun)
     {
-        return fail(c, ACF_HIP_E_INVALID, who + "the last run was a view (its boxes are in view coordinates: acf_hip_view_box, then acf_hip_cut_crops)");
+        return fail(c, ACF_HIP_E_INVALID, who + "the last run was a view (its boxes are in view coordinates: acf_hip_merge_views or acf_hip_view_box, then acf_hip_cut_crops)");
     }
     if (src->n_frames != c->lastBatch)
     {

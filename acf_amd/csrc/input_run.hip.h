@@ -1346,40 +1346,21 @@ int acf_hip_view_quad(const float m[6], const int32_t det[4], float quad[8])
     {
         return ACF_HIP_E_INVALID;
     }
-    const double x0 = det[0], y0 = det[1], x1 = double(det[0]) + det[2], y1 = double(det[1]) + det[3];
-    const double xs[4] = { x0, x1, x1, x0 }, ys[4] = { y0, y0, y1, y1 }; // TL, TR, BR, BL
-    for (int k = 0; k < 4; k++)
-    {
-        quad[2 * k] = float(double(m[0]) * xs[k] + double(m[1]) * ys[k] + double(m[2]));
-        quad[2 * k + 1] = float(double(m[3]) * xs[k] + double(m[4]) * ys[k] + double(m[5]));
-    }
+    float q[8];
+    view_quad_of(m, det[0], det[1], det[2], det[3], q); // (kernels_merge.hip.h: the arithmetic k_merge_views shares)
+    std::copy(q, q + 8, quad);
     return ACF_HIP_OK;
 }
 
 int acf_hip_view_box(const float m[6], const int32_t det[4], float box[4])
 {
-    float q[8];
-    if (!box || acf_hip_view_quad(m, det, q))
+    if (!m || !det || !box)
     {
         return ACF_HIP_E_INVALID;
     }
-    // (the corners in double once more: the box's extent is the difference of the unrounded extremes)
-    const double x0 = det[0], y0 = det[1], x1 = double(det[0]) + det[2], y1 = double(det[1]) + det[3];
-    const double xs[4] = { x0, x1, x1, x0 }, ys[4] = { y0, y0, y1, y1 };
-    double lo[2] = { 0, 0 }, hi[2] = { 0, 0 };
-    for (int k = 0; k < 4; k++)
-    {
-        const double p[2] = { double(m[0]) * xs[k] + double(m[1]) * ys[k] + double(m[2]), double(m[3]) * xs[k] + double(m[4]) * ys[k] + double(m[5]) };
-        for (int d = 0; d < 2; d++)
-        {
-            lo[d] = k == 0 || p[d] < lo[d] ? p[d] : lo[d];
-            hi[d] = k == 0 || p[d] > hi[d] ? p[d] : hi[d];
-        }
-    }
-    box[0] = float(lo[0]);
-    box[1] = float(lo[1]);
-    box[2] = float(hi[0] - lo[0]);
-    box[3] = float(hi[1] - lo[1]);
+    float o[4];
+    view_box_of(m, det[0], det[1], det[2], det[3], o);
+    std::copy(o, o + 4, box);
     return ACF_HIP_OK;
 }
 

@@ -46,9 +46,99 @@ __device__ __forceinline__ unsigned long long nms_key(double v) // monotonic: la
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
+// ---- the steps k_nms and k_merge_views (kernels_merge.hip.h) share, stated once.  Each is called by all T threads that stayed.
+// Bitonic sort of {key, idx}[P] in LDS, "before" = larger key, then smaller index
+__device__ __forceinline__ void nms_sort(unsigned long long* key, uint32_t* idx, int P, int T, int tid)
+{
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+    {
+        for (int j = k2 >> 1; j > 0; j >>= 1)
+        {
+            for (int t = tid; t < (P >> 1); t += T)
+            {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int hi = lo | j;
+                const bool up = (lo & k2) == 0; // ascending block: "before" elements first
+                const unsigned long long ka = key[lo], kb = key[hi];
+                const uint32_t ia = idx[lo], ib = idx[hi];
+                const bool aFirst = ka > kb || (ka == kb && ia < ib);
+                if (aFirst != up)
+                {
+                    key[lo] = kb;
+                    key[hi] = ka;
+                    idx[lo] = ib;
+                    idx[hi] = ia;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+// The survivors kp[0 .. m) in order: an exclusive scan over 4 entries per thread (s_wave: 16 ints, zero where no wave stayed), then
+// outIdx[0 .. total) = their idx.  Returns total.  outIdx may lie over dead keys; it is complete behind the last barrier here.
+__device__ __forceinline__ int nms_compact(const uint8_t* kp, const uint32_t* idx, int m, int tid, int* s_wave, uint32_t* outIdx)
+{
+    const int lane = tid & 63, wv = tid >> 6;
+    int c4[4], tot = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+    {
+        const int i = 4 * tid + q;
+        c4[q] = (i < m && kp[i]) ? 1 : 0;
+        tot += c4[q];
+    }
+    int incl = tot;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1)
+    {
+        const int v = __shfl_up(incl, d);
+        incl += (lane >= d) ? v : 0;
+    }
+    if (lane == 63)
+    {
+        s_wave[wv] = incl;
+    }
+    __syncthreads();
+    int base = incl - tot, total = 0;
+    for (int q = 0; q < 16; q++)
+    {
+        base += (q < wv) ? s_wave[q] : 0;
+        total += s_wave[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+    {
+        if (c4[q])
+        {
+            outIdx[base] = idx[4 * tid + q];
+            base++;
+        }
+    }
+    __syncthreads();
+    return total;
+}
+// ObjectDetector::prune (ObjectDetector.cpp:28-44) on the ordered survivors outIdx[0 .. total): how many stay.  score(q): the f64 score
+// of input q; *s_cut holds 0x7fffffff on entry
+template <class Score>
+__device__ __forceinline__ int nms_prune(const uint32_t* outIdx, int total, int maxCount, double ratio, int tid, int T, int* s_cut, Score score)
+{
+    const int L = min(maxCount, total);
+    const double s0 = score(outIdx[0]);
+    for (int i = 1 + tid; i < L; i += T)
+    {
+        if (score(outIdx[i]) < s0 * ratio)
+        {
+            atomicMin(s_cut, i);
+        }
+    }
+    __syncthreads();
+    return L < 2 ? 1 : (*s_cut < L ? *s_cut + 1 : L);
+}
+
 __global__ void __launch_bounds__(1024) k_nms(NmsArgs a)
 {
-    extern __shared__ unsigned long long nms_lds[];
+    extern __shared__ __align__(16) unsigned long long nms_lds[]; // (the int4 boxes: 16 bytes whatever static LDS lies in front)
     unsigned long long* key = nms_lds;                                // [NMS_CAP]
     int4* box = reinterpret_cast<int4*>(key + NMS_CAP);               // [NMS_CAP] {xs, ys, xe, ye} in sorted order
     uint32_t* idx = reinterpret_cast<uint32_t*>(box + NMS_CAP);       // [NMS_CAP]
@@ -120,29 +210,7 @@ __global__ void __launch_bounds__(1024) k_nms(NmsArgs a)
     __syncthreads();
     const int m = n - s_drop;
     // ---- 2. bitonic sort, "before" = larger key, then smaller index
-    for (int k2 = 2; k2 <= P; k2 <<= 1)
-    {
-        for (int j = k2 >> 1; j > 0; j >>= 1)
-        {
-            for (int t = tid; t < (P >> 1); t += T)
-            {
-                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int hi = lo | j;
-                const bool up = (lo & k2) == 0; // ascending block: "before" elements first
-                const unsigned long long ka = key[lo], kb = key[hi];
-                const uint32_t ia = idx[lo], ib = idx[hi];
-                const bool aFirst = ka > kb || (ka == kb && ia < ib);
-                if (aFirst != up)
-                {
-                    key[lo] = kb;
-                    key[hi] = ka;
-                    idx[lo] = ib;
-                    idx[hi] = ia;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    nms_sort(key, idx, P, T, tid);
     // ---- boxes in sorted order
     for (int i = tid; i < m; i += T)
     {
@@ -193,64 +261,13 @@ __global__ void __launch_bounds__(1024) k_nms(NmsArgs a)
         }
         __syncthreads();
     }
-    // ---- 4. survivors in order: exclusive scan over 4 entries per thread
-    const int lane = tid & 63, wv = tid >> 6;
-    int c4[4], tot = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-    {
-        const int i = 4 * tid + q;
-        c4[q] = (i < m && kp[i]) ? 1 : 0;
-        tot += c4[q];
-    }
-    int incl = tot;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-        const int v = __shfl_up(incl, d);
-        incl += (lane >= d) ? v : 0;
-    }
-    if (lane == 63)
-    {
-        s_wave[wv] = incl;
-    }
-    __syncthreads();
-    int base = incl - tot, total = 0;
-    for (int q = 0; q < 16; q++)
-    {
-        base += (q < wv) ? s_wave[q] : 0;
-        total += s_wave[q];
-    }
-    // prune (ObjectDetector.cpp:28-44) on the ordered survivors: needs their scores -> stage the output positions first
-    uint32_t* outIdx = reinterpret_cast<uint32_t*>(key); // the keys are dead: reuse as [total] original indices in output order
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-    {
-        if (c4[q])
-        {
-            outIdx[base] = idx[4 * tid + q];
-            base++;
-        }
-    }
-    __syncthreads();
+    // ---- 4. survivors in order (the keys are dead: reused as [total] original indices in output order), then prune on their scores
+    uint32_t* outIdx = reinterpret_cast<uint32_t*>(key);
+    const int total = nms_compact(kp, idx, m, tid, s_wave, outIdx);
     int finalCount = total;
     if (a.doPrune && total > 1)
     {
-        const int L = min(a.maxCount, total);
-        const uint32_t q0 = outIdx[0];
-        const double s0 = pipe ? double(D[q0].score) : a.scores[q0];
-        for (int i = 1 + tid; i < L; i += T)
-        {
-            const uint32_t qi = outIdx[i];
-            const double si = pipe ? double(D[qi].score) : a.scores[qi];
-            if (si < s0 * a.pruneRatio)
-            {
-                atomicMin(&s_cut, i);
-            }
-        }
-        __syncthreads();
-        finalCount = L < 2 ? 1 : (s_cut < L ? s_cut + 1 : L);
+        finalCount = nms_prune(outIdx, total, a.maxCount, a.pruneRatio, tid, T, &s_cut, [&](uint32_t q) { return pipe ? double(D[q].score) : a.scores[q]; });
     }
     for (int i = tid; i < finalCount; i += T)
     {

@@ -676,8 +676,78 @@ class HipDetector:
         self._view_call(False, source, views, frames, samples)
 
     def run_view(self, source, views, frames=None, samples=1):
-        """pyramid_view, then the cascade.  The detections are in VIEW coordinates: view_quad / view_box map them back."""
+        """pyramid_view, then the cascade.  The detections are in VIEW coordinates: view_quad / view_box map them back on the host,
+        merge_views maps and merges them into their stored frames on the device (and feeds cut_crops from there)."""
         self._view_call(True, source, views, frames, samples)
+
+    # ---- the views' detections merged into their stored frames (acf_hip_merge_views / acf_hip_op_merge_views)
+    @staticmethod
+    def merge_spec(nms=None, k=64, grow=1.0):
+        """capi.MergeSpec: nms a capi.NmsParams (capi.make_nms) applied across the views of one stored frame, or None (type 0: every
+        mapped detection in view order); k records per stored frame; grow: boxes_out grown about their centres."""
+        spec = capi.MergeSpec()
+        spec.nms = nms if nms is not None else capi.make_nms("none")
+        spec.max_per_frame, spec.grow = int(k), float(grow)
+        return spec
+
+    def merge_views(self, views, frames=None, n_frames=None, nms=None, k=64, grow=1.0, quads=False):
+        """The detections of the last run_view mapped into the upright stored frames and merged across the views of each stored frame
+        (bbNms's rule on the mapped boxes), on the device: views, frames as run_view was given them (numpy arrays are copied over
+        first), n_frames the stored frames (None: the number of views).  -> (records: uint8 [n_frames, k, 32] holding
+        capi.MERGED_DTYPE, counts int32 [n_frames] (the true number of survivors; -1: a frame over capacity), boxes float32
+        [n_frames, k, 4] grown by `grow`, frame_index int32 [n_frames, k], and with quads=True quads float32 [n_frames, k, 4, 2]), all
+        device tensors, nothing synchronised.  Record and quad slots at and beyond min(count, k) are NOT written: their content is
+        undefined.  boxes and frame_index are written in EVERY slot (zeros and -1 beyond the count):
+        cut_crops(source, boxes.view(-1, 4), frame_index.view(-1), ...) is the device-only route to crops."""
+        import torch
+        if not torch.is_tensor(views):
+            views = torch.from_numpy(np.ascontiguousarray(views, dtype=np.float32).reshape(-1, 6)).cuda()
+        if frames is not None and not torch.is_tensor(frames):
+            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.int32)).cuda()
+        n = int(views.shape[0])
+        if views.dtype != torch.float32 or views.dim() != 2 or views.shape[1] != 6 or not views.is_contiguous() or not views.is_cuda:
+            raise HipError(capi.E_INVALID, "merge_views: views float32 [n, 6], a contiguous device tensor")
+        if frames is not None and (frames.dtype != torch.int32 or tuple(frames.shape) != (n,) or not frames.is_contiguous() or not frames.is_cuda):
+            raise HipError(capi.E_INVALID, "merge_views: frames int32 [n], a contiguous device tensor")
+        nF = n if n_frames is None else int(n_frames)
+        spec = self.merge_spec(nms, k, grow)
+        kk, ff = max(int(k), 0), max(nF, 0)
+        # (torch.empty, never a fill: a fill would run on torch's stream, unordered with the kernel on the context's)
+        rec = torch.empty((ff, kk, capi.MERGED_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+        counts = torch.empty((ff,), dtype=torch.int32, device="cuda")
+        boxes = torch.empty((ff, kk, 4), dtype=torch.float32, device="cuda")
+        fidx = torch.empty((ff, kk), dtype=torch.int32, device="cuda")
+        qd = torch.empty((ff, kk, 4, 2), dtype=torch.float32, device="cuda") if quads else None
+        self._chk(self.lib.acf_hip_merge_views(self.ctx, C.c_void_p(views.data_ptr()), C.c_void_p(frames.data_ptr()) if frames is not None else None, n, nF,
+                                               C.byref(spec), C.c_void_p(rec.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(boxes.data_ptr()),
+                                               C.c_void_p(fidx.data_ptr()), C.c_void_p(qd.data_ptr()) if quads else None))
+        self._merge_keep = (views, frames)    # the call is asynchronous: what it reads lives until the next one
+        return (rec, counts, boxes, fidx, qd) if quads else (rec, counts, boxes, fidx)
+
+    def op_merge_views(self, dets, counts, views, frames=None, n_frames=None, nms=None, k=64, grow=1.0, fill=None):
+        """The same kernel on host lists: dets capi.DET_DTYPE [n_views, max_hits], counts int32 [n_views], views float32 [n_views, 6],
+        frames int32 [n_views] or None -> numpy (records capi.MERGED_DTYPE [n_frames, k], counts int32 [n_frames], boxes float32
+        [n_frames, k, 4], frame_index int32 [n_frames, k], quads float32 [n_frames, k, 4, 2]).  fill: a byte the outputs hold before
+        the call (None: 0) — slots the kernel does not write keep it."""
+        dets = np.ascontiguousarray(dets, dtype=capi.DET_DTYPE)
+        views = np.ascontiguousarray(views, dtype=np.float32).reshape(-1, 6)
+        n = len(views)
+        dets = dets.reshape(n, -1)
+        counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(n)
+        fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32).reshape(n)
+        nF = n if n_frames is None else int(n_frames)
+        spec = self.merge_spec(nms, k, grow)
+        kk, ff, b = max(int(k), 0), max(nF, 0), 0 if fill is None else int(fill)
+        rec = np.full((ff, kk, capi.MERGED_DTYPE.itemsize), b, dtype=np.uint8)
+        cnt = np.full((ff, 4), b, dtype=np.uint8)
+        boxes = np.full((ff, kk, 16), b, dtype=np.uint8)
+        fidx = np.full((ff, kk, 4), b, dtype=np.uint8)
+        qd = np.full((ff, kk, 32), b, dtype=np.uint8)
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        self._chk(self.lib.acf_hip_op_merge_views(self.ctx, ptr(dets), ptr(counts), dets.shape[1], ptr(views), ptr(fr), n, nF, C.byref(spec), ptr(rec), ptr(cnt),
+                                                  ptr(boxes), ptr(fidx), ptr(qd)))
+        return (rec.view(capi.MERGED_DTYPE).reshape(ff, kk), cnt.view(np.int32).reshape(ff), boxes.view(np.float32).reshape(ff, kk, 4),
+                fidx.view(np.int32).reshape(ff, kk), qd.view(np.float32).reshape(ff, kk, 4, 2))
 
     @staticmethod
     def view_from_box(box, angle_rad, h, w):

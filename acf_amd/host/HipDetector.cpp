@@ -742,6 +742,60 @@ int HipDetector::detectViews(const acf_hip_crop_source& src, const std::vector<s
     return detectViews(src, views, frames, samples, h, w, objects, scores);
 }
 
+int HipDetector::mergeViews(const std::vector<std::array<float, 6>>& views, const std::vector<int>& frames, int nFrames, const acf_hip_merge_spec& spec,
+    std::vector<MergedFrame>& merged, float* boxesDev, int32_t* framesDev)
+{
+    const int n = int(views.size()), K = spec.max_per_frame;
+    if (!m_ctx)
+    {
+        throw Exception(ACF_HIP_E_INVALID, "mergeViews: detectViews first");
+    }
+    if (n < 1 || (!frames.empty() && frames.size() != views.size()) || nFrames < 1 || K < 1 || K > ACF_HIP_NMS_CAP || (boxesDev == nullptr) != (framesDev == nullptr))
+    {
+        throw Exception(ACF_HIP_E_INVALID, "mergeViews: at least one view, a frame index for every view or none, nFrames >= 1, K 1 .. ACF_HIP_NMS_CAP, both or neither of boxesDev / framesDev");
+    }
+    // the views, the indices and the results go through the detector's pinned scratch (detectViews has waited: it is free)
+    const size_t slots = size_t(nFrames) * size_t(K);
+    const size_t oRec = 0, oQuad = oRec + slots * sizeof(acf_hip_merged_detection), oView = oQuad + slots * 8 * sizeof(float), oFrame = oView + size_t(n) * 6 * sizeof(float),
+                 oCount = oFrame + size_t(n) * sizeof(int32_t), bytes = oCount + size_t(nFrames) * sizeof(int32_t);
+    if (bytes > m_pinBytes)
+    {
+        pinnedFree(m_pin);
+        m_pin = pinnedAlloc(bytes);
+        m_pinBytes = bytes;
+    }
+    uint8_t* base = static_cast<uint8_t*>(m_pin);
+    acf_hip_merged_detection* rec = reinterpret_cast<acf_hip_merged_detection*>(base + oRec);
+    float* quad = reinterpret_cast<float*>(base + oQuad);
+    float* v = reinterpret_cast<float*>(base + oView);
+    int32_t* f = reinterpret_cast<int32_t*>(base + oFrame);
+    int32_t* counts = reinterpret_cast<int32_t*>(base + oCount);
+    for (int i = 0; i < n; i++)
+    {
+        std::copy(views[size_t(i)].begin(), views[size_t(i)].end(), v + size_t(i) * 6);
+        if (!frames.empty())
+        {
+            f[i] = frames[size_t(i)];
+        }
+    }
+    check(m_api->acf_hip_merge_views(m_ctx, v, frames.empty() ? nullptr : f, n, nFrames, &spec, rec, counts, boxesDev, framesDev, quad), "acf_hip_merge_views");
+    check(m_api->acf_hip_synchronize(m_ctx), "acf_hip_synchronize");
+    merged.assign(size_t(nFrames), MergedFrame());
+    for (int g = 0; g < nFrames; g++)
+    {
+        MergedFrame& m = merged[size_t(g)];
+        m.count = counts[g]; // (-1: over capacity — reported, not repaired)
+        for (int i = 0; i < std::min(m.count, K); i++)
+        {
+            const acf_hip_merged_detection& r = rec[size_t(g) * size_t(K) + size_t(i)];
+            MergedDetection d{ { { r.x, r.y, r.w, r.h } }, {}, r.score, r.view, r.index };
+            std::copy(quad + (size_t(g) * size_t(K) + size_t(i)) * 8, quad + (size_t(g) * size_t(K) + size_t(i)) * 8 + 8, d.quad.begin());
+            m.dets.push_back(d);
+        }
+    }
+    return 0;
+}
+
 std::array<float, 6> HipDetector::viewFromBox(const std::array<float, 4>& box, double angleRad, int h, int w)
 {
     std::array<float, 6> m{};

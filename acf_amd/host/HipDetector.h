@@ -348,6 +348,30 @@ public:
     static std::array<float, 6> viewFromBox(const std::array<float, 4>& box, double angleRad, int h, int w); // acf_hip_view_from_box
     static std::array<float, 8> viewQuad(const std::array<float, 6>& m, const Rect& o);                      // acf_hip_view_quad: TL, TR, BR, BL
     static std::array<float, 4> viewBox(const std::array<float, 6>& m, const Rect& o);                       // acf_hip_view_box
+    // After detectViews: the detections of its views mapped into the upright stored frames and merged ACROSS the views of each stored
+    // frame, on the device (include/acf_hip.h, acf_hip_merge_views; kernel k_merge_views) — the same object found under neighbouring
+    // angles or in overlapping windows once.  views, frames: what detectViews was given; nFrames: the stored frames; spec: the NMS across
+    // views, K = max_per_frame and the growth of the crop boxes.  The lists merged are the DEVICE-side ones (the per-view survivors when
+    // the NMS runs on the device, else the raw lists).  merged[f].dets holds the first min(count, K) survivors of stored frame f in
+    // order; merged[f].count is the true number of survivors, or -1: the frame's views hold more than ACF_HIP_NMS_CAP entries together
+    // (or one of them overflowed) — there is NO host fallback for such a frame, the -1 is the answer (search fewer views of it at once,
+    // or switch the per-view NMS on).  boxesDev [nFrames][K][4] floats and framesDev [nFrames][K] int32 (both or neither; memory the
+    // device writes, e.g. pinnedAlloc's): every slot written, grown boxes and f in the leading slots, zeros and -1 behind them —
+    // acf_hip_cut_crops(src, boxesDev, framesDev, nFrames * K, ...) is the device-only route to the crops.  Waits for the device.
+    struct MergedDetection
+    {
+        std::array<float, 4> box;  // x, y, w, h in the upright stored frame: the bounding box of quad
+        std::array<float, 8> quad; // TL, TR, BR, BL
+        float score;
+        int view, index;           // which view found it, and where in that view's device-side list
+    };
+    struct MergedFrame
+    {
+        std::vector<MergedDetection> dets;
+        int count = 0;
+    };
+    int mergeViews(const std::vector<std::array<float, 6>>& views, const std::vector<int>& frames, int nFrames, const acf_hip_merge_spec& spec,
+        std::vector<MergedFrame>& merged, float* boxesDev = nullptr, int32_t* framesDev = nullptr);
     // the descriptor of a named layout (ACF_HIP_YUV_*) of rows x cols; *frameBytes = the distance to the next frame
     static acf_hip_yuv_desc yuvLayout(int layout, int rows, int cols, int rowStrideBytes = 0, size_t* frameBytes = nullptr);
     // the same with the format's 1 or 2 bytes a sample (acf_hip_video_layout; P010 is ACF_HIP_YUV_NV12 with bits 10, shift 6)

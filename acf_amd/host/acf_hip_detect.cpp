@@ -20,6 +20,10 @@
 //                  --view x,y,w,h[,deg[,frame]] (repeatable, without --stream) [--view-size HxW] [--view-samples s]: every view is one
 //                  frame of the batch, the box of the upright stored frame turned by deg about its centre (detectViews); "view i n",
 //                  then a line "x0 y0 x1 y1 x2 y2 x3 y3 score scorebits" a detection: its corners in the upright stored frame
+//                  --merge OVR[:K] (with --view): the views' detections merged into their stored frames on the device (mergeViews, bbNms
+//                  maxg / union / OVR across the views of a stored frame): "frame f n" per STORED frame, then up to K lines
+//                  "x0 .. y3 score scorebits view index"; with --cut WxH --cut-prefix P the merged boxes' crops (acf_hip_cut_crops on
+//                  mergeViews' device-side boxes) as P_<frame>_<i>.ppm and a "crops f n" line a frame.  (--cut with --view needs --merge.)
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
@@ -297,7 +301,85 @@ int main(int argc, char** argv)
                 src.src_cols = W;
                 src.orient = orient;
                 det.setViewSize(vh, vw);
+                if (a.count("cut") && !a.count("merge"))
+                {
+                    throw std::runtime_error("--cut with --view needs --merge (the views' boxes are in view coordinates)");
+                }
                 det.detectViews(src, views, frames, smp, objs, &scores);
+                if (a.count("merge"))
+                {
+                    // --merge OVR[:K] (with --view): the views' detections merged into their stored frames on the device (mergeViews: bbNms
+                    // "maxg" over the union with overlap OVR across the views of one stored frame, the first K (default 16) survivors a
+                    // frame).  Output per STORED frame, not per view: "frame f n" (n: the survivors, -1: over capacity), then min(n, K) lines
+                    // "x0 y0 x1 y1 x2 y2 x3 y3 score scorebits view index".  With --cut WxH --cut-prefix P the merged boxes are cropped out
+                    // of the stored frames through mergeViews' boxes / frame indices and acf_hip_cut_crops — nothing comes to the host in
+                    // between — and written as P_<frame>_<i>.ppm, a "crops f n" line a frame
+                    double ovr = 0.5;
+                    int K = 16;
+                    if (std::sscanf(a["merge"].c_str(), "%lf:%d", &ovr, &K) < 1)
+                    {
+                        throw std::runtime_error("--merge takes OVR or OVR:K");
+                    }
+                    acf_hip_merge_spec ms{};
+                    ms.nms.type = 2;
+                    ms.nms.ovrDnmUnion = 1;
+                    ms.nms.overlap = ovr;
+                    ms.nms.thr = -1.7976931348623157e308;
+                    ms.max_per_frame = K;
+                    ms.grow = 1.f;
+                    int cw = 0, ch = 0;
+                    const bool cut = a.count("cut") != 0;
+                    if (cut && std::sscanf(a["cut"].c_str(), "%dx%d", &cw, &ch) < 2)
+                    {
+                        throw std::runtime_error("--cut takes WxH");
+                    }
+                    const size_t slots = size_t(cnt) * size_t(std::max(K, 1));
+                    float* boxes = cut ? static_cast<float*>(HipDetector::pinnedAlloc(slots * 4 * sizeof(float))) : nullptr;
+                    int32_t* fidx = cut ? static_cast<int32_t*>(HipDetector::pinnedAlloc(slots * sizeof(int32_t))) : nullptr;
+                    std::vector<HipDetector::MergedFrame> merged;
+                    det.mergeViews(views, frames, cnt, ms, merged, boxes, fidx);
+                    for (int f = 0; f < cnt; f++)
+                    {
+                        std::printf("frame %d %d\n", f, merged[size_t(f)].count);
+                        for (const HipDetector::MergedDetection& d : merged[size_t(f)].dets)
+                        {
+                            uint32_t b;
+                            std::memcpy(&b, &d.score, 4);
+                            const std::array<float, 8>& q = d.quad;
+                            std::printf("%.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %.9g %08x %d %d\n", q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], d.score, b, d.view,
+                                d.index);
+                        }
+                    }
+                    if (cut)
+                    {
+                        const acf_hip_crop_spec spec{ ch, cw, 1, ACF_HIP_T_U8, 1, 1, 1.f, 0 };
+                        const size_t cb = HipDetector::cropBytes(spec, 3);
+                        uint8_t* crops = static_cast<uint8_t*>(HipDetector::pinnedAlloc(cb * slots));
+                        if (acf::hip::load().acf_hip_cut_crops(det.context(), &src, boxes, fidx, int(slots), &spec, crops) ||
+                            acf::hip::load().acf_hip_synchronize(det.context()))
+                        {
+                            throw std::runtime_error("acf_hip_cut_crops");
+                        }
+                        const std::string prefix = a.count("cut-prefix") ? a["cut-prefix"] : "crop";
+                        for (int f = 0; f < cnt; f++)
+                        {
+                            const int nc = int(merged[size_t(f)].dets.size());
+                            std::printf("crops %d %d\n", f, nc);
+                            for (int i = 0; i < nc; i++)
+                            {
+                                std::ofstream os(prefix + "_" + std::to_string(f) + "_" + std::to_string(i) + ".ppm", std::ios::binary);
+                                os << "P6\n" << cw << " " << ch << "\n255\n";
+                                os.write(reinterpret_cast<const char*>(crops + cb * (size_t(f) * size_t(K) + size_t(i))), std::streamsize(cb));
+                            }
+                        }
+                        HipDetector::pinnedFree(crops);
+                        HipDetector::pinnedFree(boxes);
+                        HipDetector::pinnedFree(fidx);
+                    }
+                    HipDetector::pinnedFree(pin[0]);
+                    HipDetector::pinnedFree(pin[1]);
+                    return 0;
+                }
                 for (size_t i = 0; i < views.size(); i++)
                 {
                     std::printf("view %d %d\n", int(i), int(objs[i].size()));

@@ -103,6 +103,8 @@ static void doLoad(const std::string& path)
     ACF_HIP_FN(acf_hip_view_quad)
     ACF_HIP_FN(acf_hip_view_box)
     ACF_HIP_FN(acf_hip_view_form)
+    ACF_HIP_FN(acf_hip_merge_views)
+    ACF_HIP_FN(acf_hip_op_merge_views)
     ACF_HIP_FN(acf_hip_unorient_rect)
     ACF_HIP_FN(acf_hip_resize_dims)
     ACF_HIP_FN(acf_hip_set_input_resize)

@@ -872,7 +872,8 @@ ACF_HIP_API int acf_hip_crop_form(const acf_hip_crop_spec* spec, const float box
  *                           stream; they allocate nothing after the first call, always run plainly and leave a captured graph of
  *                           acf_hip_run valid.  ACF_HIP_TAP_IMAGE as after acf_hip_pyramid_u8.  The detections are in VIEW coordinates:
  *                           acf_hip_cut_detections refuses after a view call (ACF_HIP_E_INVALID, "the last run was a view") until another
- *                           run; the route to crops is acf_hip_view_box + acf_hip_cut_crops
+ *                           run; the device-only route to crops is acf_hip_merge_views + acf_hip_cut_crops (next section), the host's
+ *                           acf_hip_view_box + acf_hip_cut_crops
  *  acf_hip_view_from_box    host only, in double from the float inputs, rounded to float: the view whose frame is the box (x, y, w, h in
  *                           U) turned by angle_rad about its centre: sx = bw / w, sy = bh / h, m0 = sx cos, m1 = -sy sin, m3 = sx sin,
  *                           m4 = sy cos, m2 = cx - (m0 w + m1 h) / 2, m5 = cy - (m3 w + m4 h) / 2.  Angle 0: the plain cut-and-scale
@@ -900,6 +901,72 @@ ACF_HIP_API int acf_hip_view_quad(const float m[6], const int32_t det[4] /* x, y
 ACF_HIP_API int acf_hip_view_box(const float m[6], const int32_t det[4], float box[4] /* the quad's bounding box in U */);
 ACF_HIP_API int acf_hip_view_form(const float m[6], int samples, int tile_x, int tile_y, int h, int w, int Hu, int Wu, int channels, int sample_bytes,
     int* form);
+
+/* ---- merging the views' detections into the stored frame ----------------
+ * After acf_hip_run_view every view of the batch holds a list of its own, in VIEW coordinates, and the device NMS (acf_hip_set_nms) has
+ * worked per view.  acf_hip_merge_views maps every detection into the upright stored frame U on the device and suppresses the same
+ * object found under neighbouring angles or in overlapping windows ACROSS the views of one stored frame; its boxes_out / frames_out
+ * are what acf_hip_cut_crops takes, so a batch of views goes to crops of the merged detections without a device-to-host copy.
+ *
+ * The rule.  Every f64 operation rounded once, none fused.  For stored frame f = 0 .. n_frames - 1:
+ *  1. Concatenate: the views i with frame(i) == f in ascending i (frame(i) = frame_dev[i], or i when frame_dev is NULL; a view whose
+ *     index lies outside [0, n_frames) belongs to no frame), each view's list in its device order — the list acf_hip_cut_detections
+ *     would read: the per-view NMS survivors when acf_hip_set_nms is on, else the raw list.  View i contributes c_i entries.  A
+ *     contributing view with c_i < 0 (per-view NMS over capacity) or c_i > max_hits (an overflowed list, whose retained set is
+ *     unspecified), or a total above ACF_HIP_NMS_CAP, makes the frame unknowable: counts_out[f] = -1 and no record.
+ *  2. Map: box = acf_hip_view_box(views[i], det) (the four corners in f64 from the f32 view and the int box, the extremes of the
+ *     unrounded corners, each member rounded to f32), quad = acf_hip_view_quad's.  An entry whose box has a non-finite member, or
+ *     not (w > 0 and h > 0), is dropped: what a degenerate or NaN view gives.
+ *  3. nms.type 0: the remaining entries in concatenation order; every other field of nms is ignored.
+ *  4. nms.type 1 / 2: bbNms's rule (acf_hip_nms_params) on the float boxes.  Entries with double(score) < thr are dropped; the rest are
+ *     ordered by descending score, equal scores keeping concatenation order (view, then index).  In f64: xs = x, xe = x + w, ys = y,
+ *     ye = y + h, area = w * h.  For i in order (type 2: only a surviving i) every later j: iw = min(xe_i, xe_j) - max(xs_i, xs_j),
+ *     ih alike; if iw > 0 and ih > 0: o = iw * ih, u = ovrDnmUnion ? (area_i + area_j) - o : min(area_i, area_j), and j is suppressed
+ *     when o / u > overlap.  Then prune as ObjectDetector::prune (ObjectDetector.cpp:28-44).  For views that are integer
+ *     translations every quantity is an integer held exactly: the rule is bbNms on the translated int boxes.
+ *  5. Output, S survivors: counts_out[f] = S, the true number even when it exceeds K = max_per_frame.  Slots f * K + 0 .. min(S, K) - 1
+ *     of out, quads_out and boxes_out hold the survivors in order; the box of boxes_out is grown by acf_hip_crop_box's f32 steps (cx = x
+ *     + w * 0.5f, w' = w * grow, x' = cx - w' * 0.5f, y alike); frames_out there = f.  EVERY remaining slot of boxes_out and frames_out
+ *     is written too, with zeros and -1 (an unknowable frame: all K of them), so that
+ *         acf_hip_cut_crops(src, boxes_out, frames_out, n_frames * K, spec, dst)
+ *     is legal straight away and gives crops of zeros beyond the count: nothing uninitialised is read and no count comes to the host.
+ *     Record and quad slots beyond the count are not written.
+ *  acf_hip_merge_views      on the detections of the context's last acf_hip_run_view (n_views that call's; views_dev and frame_dev the
+ *                           ones it was given).  Asynchronous on the context's stream; allocates nothing, never waits for the device,
+ *                           changes no context state (acf_hip_get_detections answers as before, acf_hip_cut_detections keeps
+ *                           refusing) and leaves a captured graph of acf_hip_run valid
+ *  acf_hip_op_merge_views   the same kernel on host lists dets_host [n_views][max_hits] and counts_host [n_views], results to the host;
+ *                           a context, no model, no plan (like acf_hip_op_nms).  max_hits >= 1.  The caller's outputs go to the device
+ *                           first: a slot the kernel does not write keeps what it held
+ * One kernel, k_merge_views (so named under option "profile"): one workgroup per stored frame, everything resident in LDS — the views'
+ * counts prefix-summed into n_views + 1 offsets (hence n_views <= 1024), a concatenated index finding its (view, index) by binary search
+ * there, then k_nms's keys, bitonic sort, suppression, compaction and prune.
+ * ACF_HIP_E_INVALID: null required pointers; n_views outside 1 .. 1024; n_frames < 1; max_per_frame outside 1 .. ACF_HIP_NMS_CAP; grow
+ * not positive finite; nms.type outside 0 .. 2, nms.overlap NaN, nms.maxCount < 0 with prune; reserved not 0; merge_views without a
+ * preceding acf_hip_run_view or with another n_views.  ACF_HIP_E_UNSUPPORTED: option "streams" > 1.  What needs no device is checked
+ * before anything touches it.  Not covered: the overlap of the rotated quads themselves (the merged box is the quad's bounding box),
+ * merging across stored frames, a host fallback for an unknowable frame (the -1 is the answer). */
+typedef struct acf_hip_merged_detection {     /* 32 bytes */
+    float x, y, w, h;          /* acf_hip_view_box(views[view], det): the bounding box of the quad in U */
+    float score;
+    int32_t view;              /* which view of the batch found it */
+    int32_t index;             /* its position in that view's device list */
+    int32_t scale;
+} acf_hip_merged_detection;
+typedef struct acf_hip_merge_spec {
+    acf_hip_nms_params nms;    /* applied ACROSS the views of one stored frame */
+    int32_t max_per_frame;     /* K, 1 .. ACF_HIP_NMS_CAP */
+    float grow;                /* boxes_out only: acf_hip_crop_box's grow arithmetic; positive finite */
+    int32_t reserved[2];       /* 0 */
+} acf_hip_merge_spec;
+ACF_HIP_API int acf_hip_merge_views(acf_hip_ctx* ctx, const float* views_dev /* [n_views][6] */, const int32_t* frame_dev /* [n_views], or NULL */,
+    int n_views, int n_frames, const acf_hip_merge_spec* spec, acf_hip_merged_detection* out_dev /* [n_frames][K] */,
+    int32_t* counts_out_dev /* [n_frames] */, float* boxes_out_dev /* [n_frames][K][4], or NULL */, int32_t* frames_out_dev /* [n_frames][K], or NULL */,
+    float* quads_out_dev /* [n_frames][K][8], or NULL */);
+ACF_HIP_API int acf_hip_op_merge_views(acf_hip_ctx* ctx, const acf_hip_detection* dets_host /* [n_views][max_hits] */, const int32_t* counts_host /* [n_views] */,
+    int max_hits, const float* views_host /* [n_views][6] */, const int32_t* frame_host /* [n_views], or NULL */, int n_views, int n_frames,
+    const acf_hip_merge_spec* spec, acf_hip_merged_detection* out /* [n_frames][K] */, int32_t* counts_out /* [n_frames] */,
+    float* boxes_out /* [n_frames][K][4], or NULL */, int32_t* frames_out /* [n_frames][K], or NULL */, float* quads_out /* [n_frames][K][8], or NULL */);
 
 /* ---- streaming front end ---------------------------------------------
  * The overlap of transfer and compute that GPUDetectionPipeline::runFast gets
