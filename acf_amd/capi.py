@@ -226,6 +226,25 @@ class MergeSpec(C.Structure):
     _fields_ = [("nms", NmsParams), ("max_per_frame", C.c_int32), ("grow", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
+class BankDetection(C.Structure):
+    """struct acf_hip_bank_detection: a detection of one model of a bank (model 0: the context's own)."""
+
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("score", C.c_float), ("scale", C.c_int32),
+                ("model", C.c_int32), ("index", C.c_int32)]
+
+
+BANK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("score", "<f4"), ("scale", "<i4"), ("model", "<i4"), ("index", "<i4")])
+BANK_MAX = 8   # ACF_HIP_BANK_MAX: members of a bank (models 0 .. 8)
+
+
+class BankSpec(C.Structure):
+    """struct acf_hip_bank_spec: the NMS across (separate = 1: within) the models of one frame, records per frame, and
+    acf_hip_crop_box's grow and det_scale for boxes_out."""
+
+    _fields_ = [("nms", NmsParams), ("separate", C.c_int32), ("max_per_frame", C.c_int32), ("grow", C.c_float), ("det_scale", C.c_double),
+                ("reserved", C.c_int32 * 2)]
+
+
 _lib = None
 
 
@@ -317,6 +336,15 @@ def load():
         "acf_hip_view_form": ([fp] + [C.c_int] * 9 + [C.POINTER(C.c_int)], C.c_int),
         "acf_hip_merge_views": ([ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(MergeSpec)] + [C.c_void_p] * 5, C.c_int),
         "acf_hip_op_merge_views": ([ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(MergeSpec)] + [C.c_void_p] * 5, C.c_int),
+        "acf_hip_bank_check": ([C.POINTER(Params), C.POINTER(Params), C.c_char_p, C.c_int], C.c_int),
+        "acf_hip_set_bank": ([ctx, C.POINTER(Params), C.c_int], C.c_int),
+        "acf_hip_get_bank_levels": ([ctx, C.c_int, C.POINTER(Level), C.c_int], C.c_int),
+        "acf_hip_detect_bank": ([ctx], C.c_int),
+        "acf_hip_get_bank_detections": ([ctx, C.c_int, C.c_int, C.POINTER(Detection), C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_get_bank_hits": ([ctx, C.c_int, C.c_int, C.POINTER(Hit), C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_get_bank_forms": ([ctx, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)], C.c_int),
+        "acf_hip_join_bank": ([ctx, C.POINTER(BankSpec)] + [C.c_void_p] * 4, C.c_int),
+        "acf_hip_op_join_bank": ([ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(BankSpec)] + [C.c_void_p] * 4, C.c_int),
         "acf_hip_unorient_rect": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int),
         "acf_hip_set_yuv_layout": ([ctx, C.c_int64, C.c_int64], C.c_int),
         "acf_hip_op_yuv420_to_rgb": ([ctx, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p], C.c_int),
@@ -399,6 +427,8 @@ DECLARED_SYMBOLS = [
     "acf_hip_cut_crops", "acf_hip_cut_detections", "acf_hip_crop_box", "acf_hip_crop_bytes", "acf_hip_crop_form",
     "acf_hip_pyramid_view", "acf_hip_run_view", "acf_hip_view_from_box", "acf_hip_view_quad", "acf_hip_view_box", "acf_hip_view_form",
     "acf_hip_merge_views", "acf_hip_op_merge_views",
+    "acf_hip_bank_check", "acf_hip_set_bank", "acf_hip_get_bank_levels", "acf_hip_detect_bank", "acf_hip_get_bank_detections",
+    "acf_hip_get_bank_hits", "acf_hip_get_bank_forms", "acf_hip_join_bank", "acf_hip_op_join_bank",
 ]
 
 

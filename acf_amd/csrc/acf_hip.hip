@@ -284,6 +284,15 @@ struct ModelState
         uint32_t fidMax = 0;
         bool valid = false;
     } crop;
+    // acf_hip_set_bank: the members' parameters and arrays (p's pointers name the vectors beside it).  They were checked against this
+    // model, so acf_hip_set_model clears them
+    struct BankMember
+    {
+        acf_hip_params p{};
+        std::vector<uint32_t> fids, child;
+        std::vector<float> thrs, hs;
+    };
+    std::vector<BankMember> bank;
 };
 
 // ---- what the last pyramid / detect call left (part of the plan's state: a new plan starts without a batch; a replayed graph
@@ -297,6 +306,7 @@ struct LastRun
     bool countsFetched = false; // h_counts holds the last batch's counts
     const float* lastFrames = nullptr;
     bool viewRun = false;      // the last batch's frames were views (acf_hip_pyramid_view): its boxes are in view coordinates
+    bool bankValid = false;    // acf_hip_detect_bank has run on the last batch's pyramid
 };
 
 // ---- acf_hip_plan's: everything the plan builds, and what runs allocate lazily under it.  dropPlan frees `allocs` and assigns a
@@ -450,6 +460,15 @@ struct acf_hip_ctx : ModelState, PlanState, StreamFront
     // in this context's place, so they go with the plan (dropPlan).
     std::vector<acf_hip_ctx*> kids;
     int nStreams = 1, kidChunk = 0;
+    // The bank's members under a plan (bank_run.hip.h): a context each, with the member as its model, its own cascade state, box table
+    // and result buffers — and this context's device, stream and options; no pyramid of its own.  They go with the plan.
+    // What is meaningful on a member, and all that runCascade, readRecords and acf_hip_profile_get read of it: device, stream, numCus,
+    // ldsPerCu, opt, err, evPool / evUsed, evTurn; ModelState (p and the arrays); of PlanState hasPlan, plan (the owner's geometry, the
+    // level table with the member's window grid), maxBatch, maxHits, allocs, cs, d_boxLevels, h_counts, cascadeForm; of LastRun
+    // lastBatch, pyramidValid, detectValid, countsFetched (set by acf_hip_detect_bank).  Everything else keeps its default: d_pyr, d_chns,
+    // d_x86, the real scales, the job lists and the NMS buffers are null on a member — code that needs the cells takes them from the
+    // CascInput it is handed, never from a member's PlanState.
+    std::vector<acf_hip_ctx*> bankCtx;
     // option "graph": acf_hip_run replays a HIP graph captured from its own launches (same frames pointer, same batch size):
     // one host call instead of ~45 launches per frame — what a single frame's latency is made of when the kernels take 20 us
     int useGraph = 0;
@@ -749,6 +768,11 @@ void dropPlan(acf_hip_ctx* c)
         (void)acf_hip_destroy(k);
     }
     c->kids.clear();
+    for (acf_hip_ctx* m : c->bankCtx)
+    {
+        (void)acf_hip_destroy(m);
+    }
+    c->bankCtx.clear();
     for (void* p : c->allocs)
     {
         (void)hipFree(p);
@@ -1587,6 +1611,10 @@ int acf_hip_set_option(acf_hip_ctx* c, const char* key, int value)
     {
         set(k);
     }
+    for (acf_hip_ctx* m : c->bankCtx)
+    {
+        set(m);
+    }
     return ACF_HIP_OK;
 }
 
@@ -1774,6 +1802,7 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
     c->p.hs = c->hs.data();
     c->p.child = c->child.data();
     c->hasModel = true;
+    c->bank.clear(); // (the members were checked against the previous model)
     if (c->hasPlan)
     {
         (void)hipStreamSynchronize(c->stream);
@@ -1787,6 +1816,8 @@ int acf_hip_set_model(acf_hip_ctx* c, const acf_hip_params* p)
 #include "resample_plan.hip.h" // stripPlan, launchStrip, resampleTilePlan
 
 #include "plan_build.hip.h" // acf_hip_plan's stages (PlanBuild), after the helpers they call
+
+static int planBank(acf_hip_ctx* c, int max_batch, int max_hits); // (bank_run.hip.h)
 
 // acf_hip_plan's work on a context that dropPlan has just left without a plan
 static int planFresh(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int max_hits)
@@ -1840,7 +1871,7 @@ static int planFresh(acf_hip_ctx* c, int H, int W, int d_in, int max_batch, int 
     }
     PlanBuild b(c, H, W, d_in, max_batch, max_hits);
     if ((rc = b.colourBuffer()) || (rc = b.realScales()) || (rc = b.imageStrips()) || (rc = b.approxLevels()) || (rc = b.finalJobs()) || (rc = b.levelJobs()) ||
-        (rc = b.ldcf()) || (rc = b.uploadAndScratch()) || (rc = b.cascade()))
+        (rc = b.ldcf()) || (rc = b.uploadAndScratch()) || (rc = b.cascade()) || (rc = planBank(c, max_batch, max_hits)))
     {
         return rc;
     }
@@ -2598,5 +2629,7 @@ int acf_hip_set_nms(acf_hip_ctx* c, const acf_hip_nms_params* q)
 #include "cut_run.hip.h"   // acf_hip_cut_crops / _cut_detections: crops of the stored frame under boxes or the last batch's detections (k_cut_crops)
 
 #include "merge_run.hip.h" // acf_hip_merge_views / _op_merge_views: the views' detections merged into their stored frames (k_merge_views)
+
+#include "bank_run.hip.h"  // acf_hip_set_bank / _detect_bank / _join_bank: a bank of classifiers on one pyramid, their lists joined (k_join_bank)
 
 } // extern "C"

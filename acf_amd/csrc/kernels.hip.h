@@ -94,3 +94,4 @@ __global__ void __launch_bounds__(256) k_x86_digest(const uint32_t* __restrict__
 #include "kernels_cut.hip.h"        // crops of the stored frame under boxes or detections: k_cut_crops, staged and gather
 #include "kernels_view.hip.h"       // affine views of the stored frame as the batch's frames: k_ingest_view, staged and gather
 #include "kernels_merge.hip.h"      // the views' detections merged into their stored frames: k_merge_views
+#include "kernels_bank.hip.h"       // the lists of a bank of classifiers joined per frame: k_join_bank

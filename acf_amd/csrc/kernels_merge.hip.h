@@ -80,25 +80,6 @@ struct MergeArgs
     float* quadsOut;               // [nFrames][K][8], or null
 };
 
-// the view of concatenated index i: the largest v with off[v] <= i (views without entries share their successor's offset)
-__device__ __forceinline__ int merge_view_of(const int* off, int nViews, int i)
-{
-    int lo = 0, hi = nViews;
-    while (hi - lo > 1)
-    {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= i)
-        {
-            lo = mid;
-        }
-        else
-        {
-            hi = mid;
-        }
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(1024) k_merge_views(MergeArgs a)
 {
     extern __shared__ __align__(16) unsigned long long mrg_lds[]; // (the float4 boxes: 16 bytes whatever static LDS lies in front)
@@ -213,7 +194,7 @@ __global__ void __launch_bounds__(1024) k_merge_views(MergeArgs a)
         bool ok = false;
         if (i < n)
         {
-            const int v = merge_view_of(s_off, a.nViews, i);
+            const int v = nms_list_of(s_off, a.nViews, i);
             const acf_hip_detection d = a.dets[int64_t(v) * a.maxHits + (i - s_off[v])];
             float b[4];
             view_box_of(a.views + 6 * v, d.x, d.y, d.w, d.h, b);
@@ -254,7 +235,7 @@ __global__ void __launch_bounds__(1024) k_merge_views(MergeArgs a)
         for (int i = tid; i < m; i += T)
         {
             const int q = int(idx[i]);
-            const int v = merge_view_of(s_off, a.nViews, q);
+            const int v = nms_list_of(s_off, a.nViews, q);
             const acf_hip_detection d = a.dets[int64_t(v) * a.maxHits + (q - s_off[v])];
             float b[4];
             view_box_of(a.views + 6 * v, d.x, d.y, d.w, d.h, b);
@@ -305,7 +286,7 @@ __global__ void __launch_bounds__(1024) k_merge_views(MergeArgs a)
     if (sorted && a.doPrune && total > 1)
     {
         finalCount = nms_prune(outIdx, total, a.maxCount, a.pruneRatio, tid, T, &s_cut, [&](uint32_t q) {
-            const int v = merge_view_of(s_off, a.nViews, int(q));
+            const int v = nms_list_of(s_off, a.nViews, int(q));
             return double(a.dets[int64_t(v) * a.maxHits + (int(q) - s_off[v])].score);
         });
     }
@@ -317,7 +298,7 @@ __global__ void __launch_bounds__(1024) k_merge_views(MergeArgs a)
         if (i < nOut)
         {
             const int q = int(outIdx[i]);
-            const int v = merge_view_of(s_off, a.nViews, q);
+            const int v = nms_list_of(s_off, a.nViews, q);
             const int at = q - s_off[v];
             const acf_hip_detection d = a.dets[int64_t(v) * a.maxHits + at];
             const float* mv = a.views + 6 * v;

@@ -46,7 +46,7 @@ __device__ __forceinline__ unsigned long long nms_key(double v) // monotonic: la
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
-// ---- the steps k_nms and k_merge_views (kernels_merge.hip.h) share, stated once.  Each is called by all T threads that stayed.
+// ---- the steps k_nms, k_merge_views (kernels_merge.hip.h) and k_join_bank (kernels_bank.hip.h) share, stated once.  Each is called by all T threads that stayed.
 // Bitonic sort of {key, idx}[P] in LDS, "before" = larger key, then smaller index
 __device__ __forceinline__ void nms_sort(unsigned long long* key, uint32_t* idx, int P, int T, int tid)
 {
@@ -117,6 +117,25 @@ __device__ __forceinline__ int nms_compact(const uint8_t* kp, const uint32_t* id
     }
     __syncthreads();
     return total;
+}
+// Lists concatenated: off[0 .. nLists] holds the lists' prefix-summed counts.  The list of concatenated index i: the largest v with
+// off[v] <= i (lists without entries share their successor's offset); the entry's index in it is i - off[v]
+__device__ __forceinline__ int nms_list_of(const int* off, int nLists, int i)
+{
+    int lo = 0, hi = nLists;
+    while (hi - lo > 1)
+    {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= i)
+        {
+            lo = mid;
+        }
+        else
+        {
+            hi = mid;
+        }
+    }
+    return lo;
 }
 // ObjectDetector::prune (ObjectDetector.cpp:28-44) on the ordered survivors outIdx[0 .. total): how many stay.  score(q): the f64 score
 // of input q; *s_cut holds 0x7fffffff on entry

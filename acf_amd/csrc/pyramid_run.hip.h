@@ -1101,7 +1101,7 @@ int pyramidBody(acf_hip_ctx* c, const FrameSource& src, int nF)
         return fail(c, ACF_HIP_E_INVALID, "pyramid: n_frames out of range");
     }
     HIPCHK(c, hipSetDevice(c->device));
-    c->pyramidValid = c->detectValid = false;
+    c->pyramidValid = c->detectValid = c->bankValid = false;
     c->viewRun = src.kind == SRC_VIEW; // (every other run clears it)
     int rc;
     PyramidRun run(c, frames, nF);

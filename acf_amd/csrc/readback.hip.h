@@ -440,6 +440,22 @@ int acf_hip_profile_get(acf_hip_ctx* c, int* n, const char** names, float* ms, i
         }
     }
     c->evUsed = 0;
+    // the bank's members ran on this context's stream, each under its own markers
+    for (acf_hip_ctx* m : c->bankCtx)
+    {
+        int kn = 0;
+        const char* knames[64];
+        float kms[64];
+        int kl[64];
+        if (const int rc = acf_hip_profile_get(m, &kn, knames, kms, kl, 64))
+        {
+            return fail(c, rc, m->err);
+        }
+        for (int i = 0; i < std::min(kn, 64); i++)
+        {
+            tot.add(knames[i], kms[i], kl[i]);
+        }
+    }
     tot.write(n, names, ms, launches, cap);
     return ACF_HIP_OK;
 }

@@ -749,6 +749,112 @@ class HipDetector:
         return (rec.view(capi.MERGED_DTYPE).reshape(ff, kk), cnt.view(np.int32).reshape(ff), boxes.view(np.float32).reshape(ff, kk, 4),
                 fidx.view(np.int32).reshape(ff, kk), qd.view(np.float32).reshape(ff, kk, 4, 2))
 
+    # ---- a bank of classifiers on one pyramid (acf_hip_set_bank / _detect_bank / _join_bank)
+    @staticmethod
+    def bank_check(primary, member):
+        """acf_hip_bank_check on two model dicts -> (code, reason): capi.OK, or why `member` cannot share `primary`'s pyramid."""
+        pp, keep_p = capi.make_params(primary)
+        pm, keep_m = capi.make_params(member)
+        why = C.create_string_buffer(512)
+        rc = capi.load().acf_hip_bank_check(C.byref(pp), C.byref(pm), why, len(why))
+        del keep_p, keep_m
+        return rc, why.value.decode()
+
+    def set_bank(self, models):
+        """The bank's members (model dicts sharing every pyramid and channel field with the context's model; at most capi.BANK_MAX; an
+        empty list clears the bank).  Drops the plan: call plan() again."""
+        made = [capi.make_params(m) for m in models]
+        arr = (capi.Params * max(len(made), 1))(*[p for p, _ in made])
+        self._chk(self.lib.acf_hip_set_bank(self.ctx, arr if made else None, len(made)))
+        self.bank_models = list(models)
+        self.levels = []
+
+    def detect_bank(self):
+        """Every member's cascade on the pyramid of the last batch (after any pyramid* / run* entry), asynchronously."""
+        self._chk(self.lib.acf_hip_detect_bank(self.ctx))
+
+    def bank_detections(self, model, frame):
+        """Model `model`'s raw list of one frame after detect_bank (model 0: raw_detections)."""
+        det = np.zeros(self.max_hits, dtype=capi.DET_DTYPE)
+        n = C.c_int()
+        self._chk(self.lib.acf_hip_get_bank_detections(self.ctx, model, frame, det.ctypes.data_as(C.POINTER(capi.Detection)), self.max_hits, C.byref(n)))
+        return det[:n.value].copy()
+
+    def bank_hits(self, model, frame):
+        hits = np.zeros(self.max_hits, dtype=capi.HIT_DTYPE)
+        n = C.c_int()
+        self._chk(self.lib.acf_hip_get_bank_hits(self.ctx, model, frame, hits.ctypes.data_as(C.POINTER(capi.Hit)), self.max_hits, C.byref(n)))
+        return hits[:n.value].copy()
+
+    def bank_forms(self, model):
+        """cascade_forms() of model `model`'s last cascade (None before its first)."""
+        n = C.c_int()
+        out = (C.c_int32 * capi.CF_WORDS)()
+        self._chk(self.lib.acf_hip_get_bank_forms(self.ctx, model, out, capi.CF_WORDS, C.byref(n)))
+        return self._cascade_forms_of([int(v) for v in out])
+
+    def bank_levels(self, model):
+        """The plan's levels with model `model`'s window grid."""
+        lv = (capi.Level * len(self.levels))()
+        self._chk(self.lib.acf_hip_get_bank_levels(self.ctx, model, lv, len(self.levels)))
+        return list(lv)
+
+    @staticmethod
+    def bank_spec(nms=None, separate=False, k=64, grow=1.0, det_scale=None):
+        """capi.BankSpec: nms a capi.NmsParams applied across the models of one frame (separate: within each model), or None (type 0:
+        the lists concatenated); k records per frame; grow, det_scale: crop_box's, for boxes_out."""
+        spec = capi.BankSpec()
+        spec.nms = nms if nms is not None else capi.make_nms("none")
+        spec.separate, spec.max_per_frame, spec.grow = int(separate), int(k), float(grow)
+        spec.det_scale = 0.0 if det_scale is None else float(det_scale)
+        return spec
+
+    def join_bank(self, nms=None, separate=False, k=64, grow=1.0, det_scale=None):
+        """The lists of the last run* + detect_bank joined per frame on the device -> (records: uint8 [n_frames, k, 32] holding
+        capi.BANK_DTYPE, counts int32 [n_frames] (the true number of survivors; -1: an unknowable frame), boxes float32 [n_frames, k, 4]
+        = crop_box(det, det_scale, grow), frame_index int32 [n_frames, k]), all device tensors, nothing synchronised.  Record slots at
+        and beyond min(count, k) are NOT written; boxes and frame_index are written in EVERY slot (zeros and -1 beyond the count):
+        cut_crops(source, boxes.view(-1, 4), frame_index.view(-1), ...) is the device-only route to crops."""
+        import torch
+        spec = self.bank_spec(nms, separate, k, grow, det_scale)
+        # sized for the plan's batch: the kernel writes the frames of the context's last batch, never more than max_batch
+        kk, ff = max(int(k), 0), int(self.max_batch)
+        rec = torch.empty((ff, kk, capi.BANK_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+        counts = torch.empty((ff,), dtype=torch.int32, device="cuda")
+        boxes = torch.empty((ff, kk, 4), dtype=torch.float32, device="cuda")
+        fidx = torch.empty((ff, kk), dtype=torch.int32, device="cuda")
+        self._chk(self.lib.acf_hip_join_bank(self.ctx, C.byref(spec), C.c_void_p(rec.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(boxes.data_ptr()),
+                                             C.c_void_p(fidx.data_ptr())))
+        n = self._bank_frames()
+        return rec[:n], counts[:n], boxes[:n], fidx[:n]
+
+    def _bank_frames(self):
+        """Frames of the last detect_bank, to slice join_bank's outputs (which are allocated for max_batch frames, so this number
+        sizes nothing): the first member's cascade record holds them (a member runs nothing else)."""
+        out = (C.c_int32 * capi.CF_WORDS)()
+        n = C.c_int()
+        rc = self.lib.acf_hip_get_bank_forms(self.ctx, 1, out, capi.CF_WORDS, C.byref(n))
+        return min(int(out[29]), int(self.max_batch)) if rc == capi.OK and int(out[29]) > 0 else int(self.max_batch)
+
+    def op_join_bank(self, dets, counts, nms=None, separate=False, k=64, grow=1.0, det_scale=None, fill=None):
+        """The same kernel on host lists: dets capi.DET_DTYPE [n_models, n_frames, max_hits], counts int32 [n_models, n_frames] ->
+        numpy (records capi.BANK_DTYPE [n_frames, k], counts int32 [n_frames], boxes float32 [n_frames, k, 4], frame_index int32
+        [n_frames, k]).  fill: a byte the outputs hold before the call (None: 0) — slots the kernel does not write keep it."""
+        dets = np.ascontiguousarray(dets, dtype=capi.DET_DTYPE)
+        assert dets.ndim == 3
+        nM, nF, mh = dets.shape
+        counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(nM, nF)
+        spec = self.bank_spec(nms, separate, k, grow, det_scale)
+        kk, b = max(int(k), 0), 0 if fill is None else int(fill)
+        rec = np.full((nF, kk, capi.BANK_DTYPE.itemsize), b, dtype=np.uint8)
+        cnt = np.full((nF, 4), b, dtype=np.uint8)
+        boxes = np.full((nF, kk, 16), b, dtype=np.uint8)
+        fidx = np.full((nF, kk, 4), b, dtype=np.uint8)
+        ptr = lambda a: C.c_void_p(a.ctypes.data)
+        self._chk(self.lib.acf_hip_op_join_bank(self.ctx, ptr(dets), ptr(counts), nM, nF, mh, C.byref(spec), ptr(rec), ptr(cnt), ptr(boxes), ptr(fidx)))
+        return (rec.view(capi.BANK_DTYPE).reshape(nF, kk), cnt.view(np.int32).reshape(nF), boxes.view(np.float32).reshape(nF, kk, 4),
+                fidx.view(np.int32).reshape(nF, kk))
+
     @staticmethod
     def view_from_box(box, angle_rad, h, w):
         """float32 [6]: the view whose h x w frame is the box (x, y, w, h in the upright stored frame) turned by angle_rad about its centre."""
@@ -876,7 +982,10 @@ class HipDetector:
         out = (C.c_int32 * capi.CF_WORDS)()
         self._chk(self.lib.acf_hip_get_cascade_forms(self.ctx, out, capi.CF_WORDS, C.byref(n)))
         assert n.value == capi.CF_WORDS
-        w = [int(v) for v in out]
+        return self._cascade_forms_of([int(v) for v in out])
+
+    @classmethod
+    def _cascade_forms_of(self, w):
         if w[29] == 0:
             return None
         return dict(path=self.CASCADE_PATHS[w[0]], rank=bool(w[1]), kernel=self.CASCADE_TILE_KERNELS[w[2]], NW=w[3], TR=w[4], TC=w[5], passW=w[6],

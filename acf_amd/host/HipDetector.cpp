@@ -136,6 +136,11 @@ void HipDetector::setModel(const Options& o, const Classifier& c, int device)
 
 void HipDetector::fillParams(acf_hip_params& p) const
 {
+    fillParams(opts, clf, p);
+}
+
+void HipDetector::fillParams(const Options& opts, const Classifier& clf, acf_hip_params& p) const
+{
     p = acf_hip_params{};
     p.nTrees = clf.nTrees;
     p.nTreeNodes = clf.nTreeNodes;
@@ -223,6 +228,15 @@ void HipDetector::ensureModel()
         acf_hip_params p;
         fillParams(p);
         check(m_api->acf_hip_set_model(m_ctx, &p), "acf_hip_set_model");
+        if (!m_bank.empty()) // (acf_hip_set_model cleared the bank: the members were checked against the previous model)
+        {
+            std::vector<acf_hip_params> members(m_bank.size());
+            for (size_t i = 0; i < m_bank.size(); i++)
+            {
+                fillParams(m_bank[i].opts, m_bank[i].clf, members[i]);
+            }
+            check(m_api->acf_hip_set_bank(m_ctx, members.data(), int(members.size())), "acf_hip_set_bank");
+        }
         m_dirty = false;
         m_planH = 0;
     }
@@ -791,6 +805,51 @@ int HipDetector::mergeViews(const std::vector<std::array<float, 6>>& views, cons
             MergedDetection d{ { { r.x, r.y, r.w, r.h } }, {}, r.score, r.view, r.index };
             std::copy(quad + (size_t(g) * size_t(K) + size_t(i)) * 8, quad + (size_t(g) * size_t(K) + size_t(i)) * 8 + 8, d.quad.begin());
             m.dets.push_back(d);
+        }
+    }
+    return 0;
+}
+
+int HipDetector::joinBank(int nFrames, const acf_hip_bank_spec& spec, std::vector<BankFrame>& joined)
+{
+    const int K = spec.max_per_frame;
+    if (!m_ctx || m_bank.empty())
+    {
+        throw Exception(ACF_HIP_E_INVALID, "joinBank: setBank and a detect call first");
+    }
+    if (nFrames < 1 || nFrames > m_planBatch || K < 1 || K > ACF_HIP_NMS_CAP)
+    {
+        throw Exception(ACF_HIP_E_INVALID, "joinBank: nFrames 1 .. the plan's batch, K 1 .. ACF_HIP_NMS_CAP");
+    }
+    check(m_api->acf_hip_detect_bank(m_ctx), "acf_hip_detect_bank");
+    // the results go through the detector's pinned scratch (the detect call has waited: it is free)
+    // (sized for the plan's batch: the kernel writes the frames of the context's last batch, whatever nFrames says)
+    const size_t slots = size_t(m_planBatch) * size_t(K);
+    const size_t oCount = slots * sizeof(acf_hip_bank_detection), bytes = oCount + size_t(m_planBatch) * sizeof(int32_t);
+    if (bytes > m_pinBytes)
+    {
+        pinnedFree(m_pin);
+        m_pin = pinnedAlloc(bytes);
+        m_pinBytes = bytes;
+    }
+    uint8_t* base = static_cast<uint8_t*>(m_pin);
+    acf_hip_bank_detection* rec = reinterpret_cast<acf_hip_bank_detection*>(base);
+    int32_t* counts = reinterpret_cast<int32_t*>(base + oCount);
+    std::fill(counts, counts + m_planBatch, 0); // (a batch of fewer frames than nFrames leaves the rest empty)
+    check(m_api->acf_hip_join_bank(m_ctx, &spec, rec, counts, nullptr, nullptr), "acf_hip_join_bank");
+    check(m_api->acf_hip_synchronize(m_ctx), "acf_hip_synchronize");
+    joined.assign(size_t(nFrames), BankFrame());
+    for (int g = 0; g < nFrames; g++)
+    {
+        BankFrame& m = joined[size_t(g)];
+        m.count = counts[g]; // (-1: unknowable — reported, not repaired)
+        for (int i = 0; i < std::min(m.count, K); i++)
+        {
+            const acf_hip_bank_detection& r = rec[size_t(g) * size_t(K) + size_t(i)];
+            m.objects.push_back(Rect(r.x, r.y, r.w, r.h));
+            m.scores.push_back(double(r.score));
+            m.models.push_back(r.model);
+            m.indices.push_back(r.index);
         }
     }
     return 0;

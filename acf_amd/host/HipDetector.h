@@ -372,6 +372,28 @@ public:
     };
     int mergeViews(const std::vector<std::array<float, 6>>& views, const std::vector<int>& frames, int nFrames, const acf_hip_merge_spec& spec,
         std::vector<MergedFrame>& merged, float* boxesDev = nullptr, int32_t* framesDev = nullptr);
+    // A bank of classifiers on one pyramid (include/acf_hip.h, acf_hip_set_bank / acf_hip_detect_bank / acf_hip_join_bank).  setBank:
+    // up to ACF_HIP_BANK_MAX further models that share every pyramid and channel option with this detector's (checked when the model
+    // next goes to the context: an Exception names the member and the field); an empty vector clears the bank.  joinBank, after any
+    // detect call of nFrames frames: every member's cascade on the pyramid that call left, then the lists of the frame joined on the
+    // device — model 0's RAW list (whether or not the NMS runs on the device), then the members' — under spec's NMS across the models
+    // (spec.separate = 1: within each).  joined[f] holds the first min(count, K) survivors in order: boxes, scores, which model found
+    // each (0: this detector's, m: member m - 1) and where in that model's device list; count is the true number, or -1: a list
+    // overflowed or the frame holds more than ACF_HIP_NMS_CAP entries.  Waits for the device.
+    struct Model
+    {
+        Options opts;
+        Classifier clf;
+    };
+    struct BankFrame
+    {
+        RectVec objects;
+        RealVec scores;
+        std::vector<int> models, indices;
+        int count = 0;
+    };
+    void setBank(const std::vector<Model>& members) { m_bank = members; m_dirty = true; }
+    int joinBank(int nFrames, const acf_hip_bank_spec& spec, std::vector<BankFrame>& joined);
     // the descriptor of a named layout (ACF_HIP_YUV_*) of rows x cols; *frameBytes = the distance to the next frame
     static acf_hip_yuv_desc yuvLayout(int layout, int rows, int cols, int rowStrideBytes = 0, size_t* frameBytes = nullptr);
     // the same with the format's 1 or 2 bytes a sample (acf_hip_video_layout; P010 is ACF_HIP_YUV_NV12 with bits 10, shift 6)
@@ -464,6 +486,7 @@ public:
 private:
     void check(int rc, const char* what) const;
     void fillParams(acf_hip_params& p) const;
+    void fillParams(const Options& o, const Classifier& c, acf_hip_params& p) const; // (a bank member's: this detector's isLuv)
     void ensureContext(int device = 0); // the context, created at its first use
     void ensureModel();                 // the model on the context, pushed again after a change (m_dirty)
     void ensurePlan(int imgH, int imgW, int d, int batch);
@@ -503,6 +526,7 @@ private:
     bool m_taps = false; // "taps" option on: per-stage planes stay readable (needed by the logger)
     void* m_pin = nullptr; // pinned scratch of operator()(packed 8-bit)
     size_t m_pinBytes = 0;
+    std::vector<Model> m_bank; // setBank's members: they go to the context with the model (ensureModel)
 };
 
 // One acf::HipDetector per visible MI355X (the north star's "batched frames shard across the GPUs of one node", host side in

@@ -24,6 +24,12 @@
 //                  maxg / union / OVR across the views of a stored frame): "frame f n" per STORED frame, then up to K lines
 //                  "x0 .. y3 score scorebits view index"; with --cut WxH --cut-prefix P the merged boxes' crops (acf_hip_cut_crops on
 //                  mergeViews' device-side boxes) as P_<frame>_<i>.ppm and a "crops f n" line a frame.  (--cut with --view needs --merge.)
+//   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --batch --also m2.acfm [--also m3.acfm ...] [--join OVR[:separate]]
+//                  a bank of classifiers on one pyramid (setBank / joinBank): the frames as one batch through detectBatch, every --also
+//                  model (it must share the pyramid and channel options of --model) evaluated on the same pyramid, the lists joined on the
+//                  device.  "frame f n" (n: the true number of survivors, -1: unknowable), then a line "model x y w h score scorebits" a
+//                  detection (model 0: --model, m: the m-th --also).  Without --join the lists concatenated, model by model; --join OVR: bbNms
+//                  maxg / union / OVR across the models; --join OVR:separate: only within each model, the output in joint score order
 //   acf_hip_detect --model m.acfm --frames f.raw --rows W --cols H --channels d --count N --chns out.raw [--luv] [--log-taps] [--defaults]
 //                  Detector::chnsCompute per frame (static; --defaults: computeChannels' toolbox defaults instead of the model's Chns):
 //                  the channels [nChns][W/shrink][H/shrink] of every frame appended to out.raw, one "chns ..." line per frame
@@ -90,6 +96,7 @@ int main(int argc, char** argv)
 {
     std::map<std::string, std::string> a;
     std::vector<std::string> viewArgs; // every --view, in order
+    std::vector<std::string> alsoArgs; // every --also, in order
     for (int i = 1; i < argc; i++)
     {
         std::string k = argv[i];
@@ -100,6 +107,10 @@ int main(int argc, char** argv)
                 if (k == "--view")
                 {
                     viewArgs.push_back(argv[i + 1]);
+                }
+                if (k == "--also")
+                {
+                    alsoArgs.push_back(argv[i + 1]);
                 }
                 a[k.substr(2)] = argv[++i];
             }
@@ -180,6 +191,12 @@ int main(int argc, char** argv)
         {
             std::fprintf(stderr, "detector not good (no device / bad model)\n");
             return 3;
+        }
+        if ((!alsoArgs.empty() || a.count("join")) &&
+            (alsoArgs.empty() || !a.count("batch") || a.count("yuv") || a.count("u8") || a.count("pool") || a.count("via-images") || a.count("interleaved") ||
+                a.count("chns") || a.count("score-crops")))
+        {
+            throw std::runtime_error("--also / --join go with --batch on planar float frames, and --join needs an --also (said, not ignored)");
         }
         det.setIsLuv(a.count("luv") != 0);
         det.setDoNonMaximaSuppression(a.count("nms") != 0);
@@ -688,10 +705,59 @@ int main(int argc, char** argv)
                 }
             }
         }
-        else if (a.count("batch"))
+        else if (a.count("batch") || !alsoArgs.empty())
         {
+            if (!a.count("batch"))
+            {
+                throw std::runtime_error("--also needs --batch (the bank runs on the pyramid of one batch)");
+            }
             std::vector<HipDetector::RectVec> objs;
             std::vector<HipDetector::RealVec> scores;
+            if (!alsoArgs.empty())
+            {
+                std::vector<HipDetector::Model> bank(alsoArgs.size());
+                for (size_t i = 0; i < alsoArgs.size(); i++)
+                {
+                    if (!loadModel(alsoArgs[i], bank[i].opts, bank[i].clf))
+                    {
+                        throw std::runtime_error("cannot read model " + alsoArgs[i]);
+                    }
+                }
+                det.setBank(bank);
+                acf_hip_bank_spec bs{};
+                bs.max_per_frame = ACF_HIP_NMS_CAP;
+                bs.grow = 1.f;
+                if (a.count("join"))
+                {
+                    const std::string j = a["join"];
+                    const size_t colon = j.find(':');
+                    if (colon != std::string::npos && j.substr(colon + 1) != "separate")
+                    {
+                        throw std::runtime_error("--join takes OVR or OVR:separate");
+                    }
+                    bs.nms.type = 2;
+                    bs.nms.ovrDnmUnion = 1;
+                    bs.nms.overlap = std::stod(j.substr(0, colon));
+                    bs.nms.thr = -1.7976931348623157e308;
+                    bs.separate = colon != std::string::npos;
+                }
+                det.detectBatch(frames.data(), cnt, rows, cols, ch, objs, &scores);
+                std::vector<HipDetector::BankFrame> joined;
+                det.joinBank(cnt, bs, joined);
+                for (int f = 0; f < cnt; f++)
+                {
+                    const HipDetector::BankFrame& b = joined[size_t(f)];
+                    std::printf("frame %d %d\n", f, b.count);
+                    for (size_t i = 0; i < b.objects.size(); i++)
+                    {
+                        const float sc = float(b.scores[i]);
+                        uint32_t bits;
+                        std::memcpy(&bits, &sc, 4);
+                        std::printf("%d %d %d %d %d %.9g %08x\n", b.models[i], b.objects[i].x, b.objects[i].y, b.objects[i].width, b.objects[i].height, b.scores[i], bits);
+                    }
+                }
+                return 0;
+            }
             det.detectBatch(frames.data(), cnt, rows, cols, ch, objs, &scores);
             for (int f = 0; f < cnt; f++)
             {

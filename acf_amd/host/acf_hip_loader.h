@@ -89,6 +89,15 @@ struct Api
     ACF_HIP_FN(acf_hip_view_form)
     ACF_HIP_FN(acf_hip_merge_views)
     ACF_HIP_FN(acf_hip_op_merge_views)
+    ACF_HIP_FN(acf_hip_bank_check)
+    ACF_HIP_FN(acf_hip_set_bank)
+    ACF_HIP_FN(acf_hip_get_bank_levels)
+    ACF_HIP_FN(acf_hip_detect_bank)
+    ACF_HIP_FN(acf_hip_get_bank_detections)
+    ACF_HIP_FN(acf_hip_get_bank_hits)
+    ACF_HIP_FN(acf_hip_get_bank_forms)
+    ACF_HIP_FN(acf_hip_join_bank)
+    ACF_HIP_FN(acf_hip_op_join_bank)
     ACF_HIP_FN(acf_hip_unorient_rect)
     ACF_HIP_FN(acf_hip_resize_dims)
     ACF_HIP_FN(acf_hip_set_input_resize)

@@ -201,7 +201,8 @@ ACF_HIP_API const char* acf_hip_last_error(const acf_hip_ctx* ctx);
  * node, hence identical hits and scores — instead of the float pyramid; 0: floats),
  * "keep_pyramid" (1, default; 0: the caller wants detections only — acf_hip_run /
  * acf_hip_pyramid + acf_hip_detect — and when the levels leave as rank cells the float
- * pyramid is not written at all: acf_hip_read_level then fails with ACF_HIP_E_INVALID),
+ * pyramid is not written at all: acf_hip_read_level then fails with ACF_HIP_E_INVALID, and so
+ * does acf_hip_detect_bank, whose members read the float pyramid),
  * "cascade_turns" (0, default; for applications that run several contexts on one device,
  * the way the reference runs one Detector per thread: bit 0 = a context's cascade tile
  * kernel waits for the tile kernel submitted before it on that device, whichever
@@ -967,6 +968,103 @@ ACF_HIP_API int acf_hip_op_merge_views(acf_hip_ctx* ctx, const acf_hip_detection
     int max_hits, const float* views_host /* [n_views][6] */, const int32_t* frame_host /* [n_views], or NULL */, int n_views, int n_frames,
     const acf_hip_merge_spec* spec, acf_hip_merged_detection* out /* [n_frames][K] */, int32_t* counts_out /* [n_frames] */,
     float* boxes_out /* [n_frames][K][4], or NULL */, int32_t* frames_out /* [n_frames][K], or NULL */, float* quads_out /* [n_frames][K][8], or NULL */);
+
+/* ---- a bank of classifiers on one pyramid -------------------------------
+ * A context holds one classifier (acf_hip_set_model: model 0, the primary).  A bank adds up to ACF_HIP_BANK_MAX members — frontal and
+ * profile faces, a face model beside a pedestrian model, two aspect ratios of one class — that are evaluated on the pyramid the
+ * primary's parameters built: one pyramid, several cascades.
+ *
+ * A member is a classifier with its own window and cascade fields (nTrees, nTreeNodes, treeDepth 0 .. 8, fids / thrs / hs / child,
+ * modelDs, modelDsPad, stride, cascThr).  Every pyramid and channel field (nPerOct, nOctUp, nApprox, nLambdas, lambdas, pad, minDs,
+ * smooth; shrink, colorEnabled, colorSmooth, colorSpace, gradMagEnabled, colorChn, normRad, normConst, full, gradHistEnabled, binSize,
+ * nOrients, softBin, isLuv) must equal the primary's: the pyramid is then, bit for bit, the one a context with the member as its only
+ * model would build.
+ *  acf_hip_bank_check       host only, no context: ACF_HIP_OK, or the refusal with its reason in why[cap] — ACF_HIP_E_UNSUPPORTED for
+ *                           ldcfK > 0 on either side; ACF_HIP_E_INVALID for a deviating pyramid / channel field and for whatever
+ *                           acf_hip_check_model(member, nChns, ..) refuses, nChns derived from the channel fields (so: a feature id
+ *                           beyond nChns x the member's window cells, a bad child[])
+ *  acf_hip_set_bank         needs a model; checks every member, copies its arrays, and drops the plan (as acf_hip_set_model does).
+ *                           n = 0 or members = NULL clears the bank.  acf_hip_set_model clears it too: the members were checked against
+ *                           the previous primary.  acf_hip_plan then builds for every member what it builds for the primary's cascade
+ *                           — the window grid over the plan's levels from the member's modelDsPad and stride (a level smaller than
+ *                           the window has none), the cascade tables with a rank set, the run buffers for max_hits hits per frame, the
+ *                           box table from the member's modelDs.  Nothing is allocated after the plan.  acf_hip_set_option reaches the
+ *                           members; under option "profile" their launches are part of acf_hip_profile_get
+ *  acf_hip_get_bank_levels  the plan's levels with model `model`'s window grid (nWinR, nWinC); model 0: acf_hip_get_levels'
+ *  acf_hip_detect_bank      every member's cascade on the pyramid of the last batch, asynchronously on the context's stream, after any
+ *                           acf_hip_pyramid* / acf_hip_run* entry.  Member m's list is, bit for bit — hits, score bits, boxes, order —,
+ *                           what a context holding member m as its only model gives from acf_hip_run on the same frames.  The
+ *                           existing cascade kernels run, on a state of the member's own: its rank cells come from its own k_rank
+ *                           launch over the float pyramid wherever the member and the options admit them, else the float forms run;
+ *                           all forms give identical results and acf_hip_get_bank_forms reports the one taken.  It changes nothing
+ *                           the primary left (acf_hip_get_detections, acf_hip_cut_detections, acf_hip_merge_views answer as before; a
+ *                           captured graph of acf_hip_run stays valid).  Members get no device NMS of their own: their lists are raw.
+ *                           ACF_HIP_E_INVALID without a bank, a plan or a valid pyramid, and when the float pyramid of the batch was
+ *                           not written (option "keep_pyramid" = 0 with a primary on rank cells); ACF_HIP_E_UNSUPPORTED with option
+ *                           "streams" > 1
+ *  acf_hip_get_bank_detections / _hits   model `model`'s list of one frame after acf_hip_detect_bank, as acf_hip_get_raw_detections /
+ *                           acf_hip_get_hits return a list (model 0: exactly those two entries)
+ *  acf_hip_get_bank_forms   model `model`'s ACF_HIP_CF_* record of its last cascade (model 0: acf_hip_get_cascade_forms')
+ *
+ * Joining the lists.  For frame f = 0 .. n_frames - 1:
+ *  1. Concatenate: model 0's raw list (what acf_hip_get_raw_detections returns, whether or not the device NMS is on), then members
+ *     1 .. n in order, each list in its device order (scale, column, row).  A list with a count above max_hits (an overflowed list,
+ *     whose retained set is unspecified) or below 0, or a total above ACF_HIP_NMS_CAP, makes the frame unknowable: counts_out[f] = -1
+ *     and no record.
+ *  2. nms.type 0: the entries in concatenation order; every other field of nms, and separate, is ignored.
+ *  3. nms.type 1 / 2: k_nms's rule (acf_hip_nms_params, acf_hip_op_nms) on the int boxes.  Entries with double(score) < thr are dropped;
+ *     the rest are ordered by descending score, equal scores keeping concatenation order (model, then index); the suppression loop
+ *     (type 2: only a surviving i suppresses) with the overlap from int products, the quotient in f64; then prune.  separate = 0: every
+ *     pair is tested, so the same object found by two models is reported once.  separate = 1: only detections of the same model
+ *     suppress each other — the survivors are the union of the per-model acf_hip_op_nms survivors; the output order is still the
+ *     joint score order and prune is joint.
+ *  4. Output, S survivors: counts_out[f] = S, the true number even when it exceeds K = max_per_frame.  Slots f * K + 0 .. min(S, K) - 1
+ *     of out and boxes_out hold the survivors in order; boxes_out = acf_hip_crop_box(det, det_scale, grow) with the same f32
+ *     operations; frames_out there = f.  EVERY remaining slot of boxes_out and frames_out is written too, with zeros and -1 (an
+ *     unknowable frame: all K of them), so that acf_hip_cut_crops(src, boxes_out, frames_out, n_frames * K, spec, dst) is legal
+ *     straight away.  Record slots beyond the count are not written.
+ *  acf_hip_join_bank        on the lists of the last acf_hip_run* + acf_hip_detect_bank (n_frames that batch's).  Asynchronous on the
+ *                           context's stream; allocates nothing, never waits for the device, changes no context state
+ *  acf_hip_op_join_bank     the same kernel on host lists dets_host [n_models][n_frames][max_hits] and counts_host
+ *                           [n_models][n_frames], results to the host; a context, no model, no plan.  n_models 1 .. ACF_HIP_BANK_MAX + 1,
+ *                           max_hits >= 1.  The caller's outputs go to the device first: a slot the kernel does not write keeps what
+ *                           it held
+ * One kernel, k_join_bank (so named under option "profile"): one workgroup per frame, everything resident in LDS, k_nms's keys, sort,
+ * compaction and prune.
+ * ACF_HIP_E_INVALID: null required pointers; max_per_frame outside 1 .. ACF_HIP_NMS_CAP; grow not positive finite; nms.type outside
+ * 0 .. 2, nms.overlap NaN, nms.maxCount < 0 with prune; reserved not 0; separate outside {0, 1}; det_scale not 0 or positive finite;
+ * join_bank without detections of the primary and an acf_hip_detect_bank since the last pyramid.  ACF_HIP_E_UNSUPPORTED: option
+ * "streams" > 1.  What needs no device is checked before anything touches it.  Not covered: members with pyramid fields of their own,
+ * LDCF members, a per-model device NMS, bank records in the streaming front end. */
+#define ACF_HIP_BANK_MAX 8   /* members; model indices 0 (the context's model) .. 8 */
+typedef struct acf_hip_bank_detection {      /* 32 bytes */
+    int32_t x, y, w, h;
+    float score;
+    int32_t scale;
+    int32_t model;             /* 0: the context's model; m >= 1: member m - 1 of acf_hip_set_bank */
+    int32_t index;             /* its position in that model's device list */
+} acf_hip_bank_detection;
+typedef struct acf_hip_bank_spec {
+    acf_hip_nms_params nms;    /* applied ACROSS the models of one frame (separate = 1: within each model) */
+    int32_t separate;          /* 0 / 1 */
+    int32_t max_per_frame;     /* K, 1 .. ACF_HIP_NMS_CAP */
+    float grow;                /* boxes_out only: acf_hip_crop_box's grow; positive finite */
+    double det_scale;          /* boxes_out only: acf_hip_crop_box's det_scale; 0 (no resize) or positive finite */
+    int32_t reserved[2];       /* 0 */
+} acf_hip_bank_spec;
+ACF_HIP_API int acf_hip_bank_check(const acf_hip_params* primary, const acf_hip_params* member, char* why, int cap);
+ACF_HIP_API int acf_hip_set_bank(acf_hip_ctx* ctx, const acf_hip_params* members, int n);
+ACF_HIP_API int acf_hip_get_bank_levels(const acf_hip_ctx* ctx, int model, acf_hip_level* out, int cap);
+ACF_HIP_API int acf_hip_detect_bank(acf_hip_ctx* ctx);
+ACF_HIP_API int acf_hip_get_bank_detections(acf_hip_ctx* ctx, int model, int frame, acf_hip_detection* out, int cap, int* count);
+ACF_HIP_API int acf_hip_get_bank_hits(acf_hip_ctx* ctx, int model, int frame, acf_hip_hit* out, int cap, int* count);
+ACF_HIP_API int acf_hip_get_bank_forms(const acf_hip_ctx* ctx, int model, int32_t* out, int cap, int* n);
+ACF_HIP_API int acf_hip_join_bank(acf_hip_ctx* ctx, const acf_hip_bank_spec* spec, acf_hip_bank_detection* out_dev /* [n_frames][K] */,
+    int32_t* counts_out_dev /* [n_frames] */, float* boxes_out_dev /* [n_frames][K][4], or NULL */, int32_t* frames_out_dev /* [n_frames][K], or NULL */);
+ACF_HIP_API int acf_hip_op_join_bank(acf_hip_ctx* ctx, const acf_hip_detection* dets_host /* [n_models][n_frames][max_hits] */,
+    const int32_t* counts_host /* [n_models][n_frames] */, int n_models, int n_frames, int max_hits, const acf_hip_bank_spec* spec,
+    acf_hip_bank_detection* out /* [n_frames][K] */, int32_t* counts_out /* [n_frames] */, float* boxes_out /* [n_frames][K][4], or NULL */,
+    int32_t* frames_out /* [n_frames][K], or NULL */);
 
 /* ---- streaming front end ---------------------------------------------
  * The overlap of transfer and compute that GPUDetectionPipeline::runFast gets
